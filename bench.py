@@ -165,7 +165,14 @@ class _StubSolver:
     def solve_resident(self, reset=True, max_num_iterations=50, **kw):
         time.sleep(1e-3 * max_num_iterations * (1 + self.rank))      # rank r is (r + 1) x slower: max-over-ranks is visible
         return dict(lm_iterations=max_num_iterations, num_iterations=max_num_iterations + 1, message="stub", rmse=0.0,
-                    seconds_solve=0.0, seconds_total=0.0)
+                    seconds_solve=0.0, seconds_total=0.0, initial_cost=0.0, final_cost=0.0, iterations=[])
+
+    def download_params(self):
+        p = self.problem
+        return p.cam_rt.copy(), p.intr.copy(), p.board_rt.copy()
+
+    def gather_boards(self):
+        return self.problem.board_rt.copy()
 
     def kernel_time(self, enable=True):
         return 0, 0.0
@@ -200,6 +207,37 @@ def run_iterations(solver, n_iter, **extra):
             raise RuntimeError(f"expected {k} LM iterations, device ran {s['lm_iterations']} ({s['message']})")
         done += k
     return s
+
+
+DUMP_ITERATION_FIELDS = ("cost", "cost_change", "gradient_max_norm", "step_norm", "trust_region_radius", "step_is_successful")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, solver, summary, multi, write):
+    """--dump-outputs: what a caller of the timed path receives from its last solve -- the parameter blocks left on the
+    device (intr, cam_rt, board_rt; every rank's boards gathered first when frames are sharded, which every rank must
+    join) and the solve's summary (final cost, RMSE, the per-iteration trace) -- as <directory>/<name>.npy in float64.
+    The inputs are seeded and every timed solve restarts from the same resident initial guess, so two runs with the
+    same arguments compare output for output.  Untimed: called after the timed region."""
+    import numpy as np
+    cam_rt, intr, board_rt = solver.download_params()
+    if multi:
+        board_rt = solver.gather_boards()
+    if not write:
+        return []
+    its = summary["iterations"]
+    arrays = {"intr": intr, "cam_rt": cam_rt, "board_rt": board_rt,
+              "final_cost": [summary["final_cost"]], "initial_cost": [summary["initial_cost"]], "rmse": [summary["rmse"]]}
+    for k in DUMP_ITERATION_FIELDS:
+        arrays["iteration_" + k] = [it[k] for it in its]
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+    return sorted(arrays)
 
 
 def _grid_delta(api, intr_gpu, intr_cpu, device):
@@ -294,7 +332,12 @@ def main():
                     help="tscm_options.exec_flags for every solve (A/B runs: 4 = TSCM_EXEC_GRAM_16X16, 1 = separate T reduction)")
     ap.add_argument("--jacobian-fp32", action="store_true",
                     help="north_star's 1e-3 tier: fp32 derivatives + fp32 MFMA contraction (default: all fp64, the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed solve computed (parameters, cost, iteration trace) "
+                         "as DIR/<name>.npy in float64, for comparing two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     force_dist = os.environ.get("TSCM_BENCH_FORCE_DIST") == "1"
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or force_dist):
@@ -397,7 +440,7 @@ def main():
     solver.exchange_time()
     barrier()
     t0 = time.perf_counter()
-    run_iterations(solver, args.steps, **extra)
+    last = run_iterations(solver, args.steps, **extra)
     barrier()
     elapsed_local = time.perf_counter() - t0
     launches, kms = solver.kernel_time(enable=False)
@@ -414,6 +457,10 @@ def main():
             "allreduce_T_us": 1e3 * ms_xt / max(n_xt, 1), "allreduce_H_us": 1e3 * ms_xh / max(n_xh, 1),
             "allreduces_timed": [n_xt, n_xh]}
     per_rank = chan.gather(mine) if chan else [mine]
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, solver, last, multi, write=rank == 0)
+        if rank == 0:
+            print(f"--dump-outputs: {len(dumped)} arrays of the last timed solve written to {args.dump_outputs}", file=sys.stderr)
 
     if rank == 0:
         avg_ms = kms / max(launches, 1)

@@ -112,6 +112,33 @@ def test_a_failing_rank_takes_the_job_down():
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
 
 
+def test_dump_outputs_writes_the_same_arrays_on_every_run(tmp_path):
+    """--dump-outputs DIR: float64 .npy files of the last timed solve, the same on a second run with the same arguments and
+    from a sharded run (rank 0 writes the gathered boards); the result line is unchanged."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b", tmp_path / "two"]
+    for d, extra in zip(dirs, ([], [], ["--gpus", "2"])):
+        out = subprocess.run([sys.executable, BENCH, "--steps", "7", "--warmup", "0", "--dump-outputs", str(d), *extra],
+                             env=_clean_env(TSCM_BENCH_STUB="1"), capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 7
+    names = sorted(os.listdir(dirs[0]))
+    assert {"intr.npy", "cam_rt.npy", "board_rt.npy", "final_cost.npy", "iteration_cost.npy"} <= set(names)
+    assert sum(os.path.getsize(dirs[0] / n) for n in names) <= 64 << 20
+    for d in dirs[1:]:
+        assert sorted(os.listdir(d)) == names
+        for n in names:
+            a, b = np.load(dirs[0] / n), np.load(d / n)
+            assert a.dtype == np.float64 and np.array_equal(a, b), n
+
+
+def test_steps_below_one_is_refused():
+    out = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_clean_env(TSCM_BENCH_STUB="1"),
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
 # ---------------------------------------------------------------------------------------------- side channel
 def _chan_worker(rank, world, port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"

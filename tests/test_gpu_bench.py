@@ -118,3 +118,26 @@ def test_a_rank_that_is_gone_is_reported_not_waited_for(hip_device):
     assert out.returncode == 0 and len(lines) == 1, (out.stdout + out.stderr)[-3000:]
     assert lines[0]["peer_failure_detected"] and lines[0]["code"] == -7 and 5 < lines[0]["seconds"] < 60
     assert lines[0]["again_code"] == -7 and lines[0]["again_seconds"] < 2.0
+
+
+def test_dump_outputs_are_what_the_timed_solve_computes(hip_device, tmp_path):
+    """--dump-outputs: the arrays of the last timed solve (config 3, --steps 20: one solve of 20 forced iterations) against the
+    same solve run here through the API from the same start -- what a caller of the timed path receives."""
+    import numpy as np
+    import bench
+    from tscm_calib_amd import api, synth
+    d = _run({}, "--dump-outputs", str(tmp_path))
+    assert d["steps"] == 20
+    got = {n[:-4]: np.load(tmp_path / n) for n in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float64 for a in got.values())
+    with api.Solver(synth.make_config(3), device=hip_device) as s:
+        s.upload_params()
+        want = s.solve_resident(reset=True, max_num_iterations=20, **bench.BENCH_OPTS)
+        cam_rt, intr, board_rt = s.download_params()
+    assert want["lm_iterations"] == 20 and len(got["iteration_cost"]) == want["num_iterations"]
+    assert np.array_equal(got["iteration_step_is_successful"], [it["step_is_successful"] for it in want["iterations"]])
+    assert np.allclose(got["iteration_cost"], [it["cost"] for it in want["iterations"]], rtol=1e-9, atol=0)
+    assert abs(got["final_cost"][0] - want["final_cost"]) <= 1e-9 * want["final_cost"]
+    assert np.allclose(got["cam_rt"], cam_rt, rtol=0, atol=1e-8 * max(np.max(np.abs(cam_rt)), 1.0))
+    assert np.allclose(got["board_rt"], board_rt, rtol=0, atol=1e-8 * np.max(np.abs(board_rt)))
+    assert np.max(np.abs(got["intr"][:, :7] - intr[:, :7]) / np.abs(intr[:, :7])) < 1e-4
