@@ -279,6 +279,15 @@ int tscm_eval_normal_equations(const tscm_problem *problem, int device, double *
                                double *board_grad, double *view_cross, double *cam_gram,
                                double *cam_grad, double *cost);
 
+/* The same, formed by the Gram kernel a solve with `opt` runs (NULL = defaults, which
+ * is tscm_eval_normal_equations): opt->jacobian_fp32 selects the fp32-Jacobian tier,
+ * opt->exec_flags & TSCM_EXEC_GRAM_16X16 the 16x16-tile kernel; the other flags do not
+ * change the evaluation and are ignored.  struct_size and exec_flags are checked as
+ * tscm_solver_solve checks them (TSCM_E_INVALID).                                   */
+int tscm_eval_normal_equations_ex(const tscm_problem *problem, int device, const tscm_options *opt,
+                                  double *board_gram, double *board_grad, double *view_cross,
+                                  double *cam_gram, double *cam_grad, double *cost);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

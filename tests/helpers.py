@@ -34,6 +34,103 @@ def oracle_normal_equations(p: Problem) -> dict:
     return out
 
 
+def normal_equations_from(p: Problem, res, Jc, Jb, Ji, extra=None) -> dict:
+    """oracle_normal_equations from given Jacobians (oracle order: views in problem order, corners in order), batched over
+    views of equal corner count.  `extra` = (view, corner, weight) arrays: corner `corner`'s rows are added once more, times
+    `weight`, to view `view`'s products (weight -1 drops a row, +1 counts it twice or adds a foreign one).  Also returns the
+    diagonals of every view's own E^T E and F^T F and r^T r per board and per camera (the scales of gram_errors)."""
+    C, B, V = p.n_cameras, p.n_boards, p.n_views
+    cnt = np.asarray(p.view_count, dtype=np.int64)
+    start = np.cumsum(cnt) - cnt
+    vc, vb = np.asarray(p.view_camera, dtype=np.int64), np.asarray(p.view_board, dtype=np.int64)
+    Jc, Jb, Ji, res = Jc.reshape(-1, 2, 6), Jb.reshape(-1, 2, 6), Ji.reshape(-1, 2, 9), res.reshape(-1, 2)
+    out = dict(board_gram=np.zeros((B, 6, 6)), board_grad=np.zeros((B, 6)), view_cross=np.zeros((V, 6, 15)),
+               cam_gram=np.zeros((C, 15, 15)), cam_grad=np.zeros((C, 15)), cost=0.5 * float(np.sum(res * res)),
+               view_ediag=np.zeros((V, 6)), view_fdiag=np.zeros((V, 15)), board_rr=np.zeros(B), cam_rr=np.zeros(C))
+
+    def rows(idx):
+        # idx [nv, c] corner indices -> E [nv, 2c, 6], F [nv, 2c, 15], r [nv, 2c]
+        nv, c = idx.shape
+        E = Jb[idx].reshape(nv, 2 * c, 6)
+        F = np.concatenate([Jc[idx], Ji[idx]], axis=-1).reshape(nv, 2 * c, 15)
+        return E, F, res[idx].reshape(nv, 2 * c)
+
+    def add(vs, E, F, r):
+        np.add.at(out["board_gram"], vb[vs], np.einsum("vki,vkj->vij", E, E))
+        np.add.at(out["board_grad"], vb[vs], np.einsum("vki,vk->vi", E, r))
+        np.add.at(out["view_cross"], vs, np.einsum("vki,vkj->vij", E, F))
+        np.add.at(out["cam_gram"], vc[vs], np.einsum("vki,vkj->vij", F, F))
+        np.add.at(out["cam_grad"], vc[vs], np.einsum("vki,vk->vi", F, r))
+
+    for c in np.unique(cnt[cnt > 0]):
+        for vs in np.array_split(np.nonzero(cnt == c)[0], max(1, int(c) * int((cnt == c).sum()) // 200_000)):
+            E, F, r = rows(start[vs, None] + np.arange(c))
+            add(vs, E, F, r)
+            out["view_ediag"][vs] = np.einsum("vki,vki->vi", E, E)
+            out["view_fdiag"][vs] = np.einsum("vki,vki->vi", F, F)
+            rr = np.einsum("vk,vk->v", r, r)
+            np.add.at(out["board_rr"], vb[vs], rr)
+            np.add.at(out["cam_rr"], vc[vs], rr)
+    if extra is not None:
+        ev, ek, ew = (np.asarray(a) for a in extra)
+        E, F, r = rows(np.asarray(ek, dtype=np.int64)[:, None])
+        w = np.repeat(np.asarray(ew, dtype=np.float64)[:, None], 2, axis=1)
+        add(np.asarray(ev, dtype=np.int64), E * w[:, :, None], F, r * w)
+    return out
+
+
+def block_errors(g: dict, o: dict, mono: bool) -> dict:
+    """Largest entrywise error of each block of g against the reference o relative to the block's largest reference entry
+    (the fp64 measure of test_normal_equations: b, c columns and a mono problem's camera-pose columns not compared)."""
+    err = {}
+    for key in ("board_gram", "board_grad", "cam_gram", "cam_grad", "view_cross"):
+        a, b = np.array(g[key], dtype=np.float64), np.array(o[key], dtype=np.float64)
+        if key == "view_cross":
+            a[:, :, 13:] = 0.0; b[:, :, 13:] = 0.0
+            if mono:
+                a[:, :, :6] = 0.0; b[:, :, :6] = 0.0
+        if mono and key == "cam_gram":
+            a[:, :6, :] = 0; a[:, :, :6] = 0; b[:, :6, :] = 0; b[:, :, :6] = 0
+        if mono and key == "cam_grad":
+            a[:, :6] = 0; b[:, :6] = 0
+        err[key] = float(np.max(np.abs(a - b)) / np.abs(b).max())
+    return err
+
+
+def gram_errors(g: dict, o: dict, p: Problem) -> dict:
+    """Largest entrywise error of each block of g against the reference o, in units of the Cauchy-Schwarz bound of the
+    entry: sqrt(G_ii G_jj) of the reference Gram (each view's own E^T E / F^T F for view_cross), sqrt(G_ii r^T r) for the
+    gradients.  The b, c columns (structurally zero) are not compared, and the camera-pose columns of a mono problem (no
+    such block) neither.  An entry whose bound is 0 must match exactly.  The views and boards of fewer than four corners
+    (less than one k-step) are reported apart: view_cross_short, board_gram_short, board_grad_short."""
+    keep = np.ones(15, dtype=bool)
+    keep[13:] = False
+    if p.mono:
+        keep[:6] = False
+    dg = lambda G: np.diagonal(G, axis1=-2, axis2=-1)
+    bd, cd = dg(o["board_gram"]), dg(o["cam_gram"])
+    scale = dict(board_gram=np.sqrt(bd[:, :, None] * bd[:, None, :]),
+                 board_grad=np.sqrt(bd * o["board_rr"][:, None]),
+                 view_cross=np.sqrt(o["view_ediag"][:, :, None] * o["view_fdiag"][:, None, :]),
+                 cam_gram=np.sqrt(cd[:, :, None] * cd[:, None, :]),
+                 cam_grad=np.sqrt(cd * o["cam_rr"][:, None]))
+    board_corners = np.bincount(p.view_board, weights=p.view_count, minlength=p.n_boards)
+    short = dict(view_cross=np.asarray(p.view_count) < 4, board_gram=board_corners < 4, board_grad=board_corners < 4)
+    err = {}
+    for key, s in scale.items():
+        d = np.abs(np.asarray(g[key]) - o[key])
+        if key == "cam_gram":
+            d, s = d[:, keep][:, :, keep], s[:, keep][:, :, keep]
+        elif key in ("view_cross", "cam_grad"):
+            d, s = d[..., keep], s[..., keep]
+        e = np.where(s > 0, d / np.where(s > 0, s, 1.0), np.where(d > 0, np.inf, 0.0))
+        if key in short:
+            err[key + "_short"] = float(e[short[key]].max()) if short[key].any() else 0.0
+            e = e[~short[key]]
+        err[key] = float(e.max()) if e.size else 0.0
+    return err
+
+
 def rel_err(a, b, floor=0.0):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a - b) / np.maximum(np.abs(b), floor))) if a.size else 0.0

@@ -49,6 +49,21 @@ def test_no_gpu_means_loud_failure_not_fallback():
         api.project(synth.CALIB_INTR[0], np.zeros((1, 3)))
     with pytest.raises(lib.TscmError):
         api.refinement(p)
+    for kw in ({}, dict(jacobian_fp32=1), dict(exec_flags=lib.EXEC_GRAM_16X16)):
+        with pytest.raises(lib.TscmError) as e:
+            api.normal_equations(p, **kw)
+        assert e.value.code == -2, kw
+
+
+def test_normal_equations_ex_checks_options_like_the_solve():
+    """tscm_eval_normal_equations_ex refuses what tscm_solver_solve refuses (before it touches a device)."""
+    p = H.small_rig(4, 4, seed=1)
+    cp = lib.c_problem(p)
+    for field, value in (("struct_size", 8), ("struct_size", C.sizeof(lib.COptions) + 8), ("exec_flags", 1 << 12)):
+        o = lib.default_options(False)
+        setattr(o, field, value)
+        assert lib.lib().tscm_eval_normal_equations_ex(C.byref(cp), 0, C.byref(o), None, None, None, None, None, None) == -1, field
+        assert (b"struct_size" if field == "struct_size" else b"exec_flags") in lib.lib().tscm_last_error()
 
 
 def test_argument_validation_happens_before_device_use():

@@ -282,15 +282,18 @@ def evaluate_functor(problem: Problem, device: int = 0, jacobians: bool = True):
     return cost.value, res
 
 
-def normal_equations(problem: Problem, device: int = 0) -> dict:
+def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0) -> dict:
+    """Schur-form normal equations (unscaled) from the Gram kernel a solve with these options runs:
+    k_eval_gram4 by default, k_eval_gram_f32 with jacobian_fp32=1, k_eval_gram with exec_flags=EXEC_GRAM_16X16."""
     assert _is_normalised(problem)
     Cn, B, V = problem.n_cameras, problem.n_boards, problem.n_views
     out = dict(board_gram=np.zeros((B, 6, 6)), board_grad=np.zeros((B, 6)), view_cross=np.zeros((V, 6, 15)),
                cam_gram=np.zeros((Cn, 15, 15)), cam_grad=np.zeros((Cn, 15)))
     cost = C.c_double(0.0)
     cp = _l.c_problem(problem)
-    _l.check(_l.lib().tscm_eval_normal_equations(
-        C.byref(cp), device, _l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
+    o = _l.default_options(problem.mono, jacobian_fp32=jacobian_fp32, exec_flags=exec_flags)
+    _l.check(_l.lib().tscm_eval_normal_equations_ex(
+        C.byref(cp), device, C.byref(o), _l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
         _l.dptr(out["cam_gram"]), _l.dptr(out["cam_grad"]), C.byref(cost)))
     out["cost"] = cost.value
     return out

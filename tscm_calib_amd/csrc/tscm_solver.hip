@@ -749,6 +749,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     s->lds_eval = 4 * lds_eval_bytes;
     s->lds_eval32 = sizeof(double) * (size_t)eval_f32_lds_doubles(p->n_points, g4.ks);
     s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval32 = f32_kernel(g4.ks, g4.passes > 1);
+    if (s->lds_eval32 > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(s->eval32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
     // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory
     s->solve_variant = C <= 4 ? 0 : C <= kMaxCamLds ? 1 : 3;
     if (s->solve_variant == 0) {
@@ -1219,7 +1220,7 @@ struct LmRunGuard {
     ~LmRunGuard()
     {
         for (tscm_solver *s : run.m) {
-            s->f32_jacobian = false;         // the operator-level entry points are always fp64
+            s->f32_jacobian = false;         // (per solve: set again from the options of the next one)
             s->ev_used = 0;
             s->stream = s->own_stream;
         }
@@ -1227,6 +1228,22 @@ struct LmRunGuard {
 };
 
 static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, int reset, bool rerun, bool *late_handoff);
+
+// the caller's struct may be SHORTER than this library's (built against an older header of ABI >= 6): read what it has, the
+// rest keeps its default.  The shortest struct the library knows ends behind exec_flags (ABI 6); a size of 0, a smaller or a
+// larger one is refused -- a struct of ABI <= 5 has max_num_iterations where struct_size is and never passes
+static int read_options(const tscm_options *opt_in, int mono, tscm_options &opt)
+{
+    tscm_default_options(&opt, mono);
+    if (opt_in) {
+        constexpr size_t kMinOptions = offsetof(tscm_options, exec_flags) + sizeof(int);
+        if (opt_in->struct_size < kMinOptions || opt_in->struct_size > sizeof(tscm_options))
+            return fail(TSCM_E_INVALID, "tscm_options.struct_size is not a size this library knows (initialise the struct with tscm_default_options; ABI 6)");
+        std::memcpy(&opt, opt_in, opt_in->struct_size);
+        opt.struct_size = sizeof(tscm_options);
+    }
+    return 0;
+}
 
 // Waits for the solver's stream.  With a multi-rank RCCL communicator a peer that has failed (or died) leaves this
 // rank's all-reduce kernel spinning for ever -- over the intra-node transports an ncclCommAbort on the FAILING rank does
@@ -1292,18 +1309,8 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
 {
     tscm_solver *s0 = run.m[0];
     for (tscm_solver *s : run.m) if (!s->have_init) return fail(TSCM_E_INVALID, "tscm_solver_upload_params has not been called");
-    // the caller's struct may be SHORTER than this library's (built against an older header of ABI >= 6): read what it has, the
-    // rest keeps its default.  The shortest struct the library knows ends behind exec_flags (ABI 6); a size of 0, a smaller or a
-    // larger one is refused -- a struct of ABI <= 5 has max_num_iterations where struct_size is and never passes
     tscm_options opt;
-    tscm_default_options(&opt, s0->mono);
-    if (opt_in) {
-        constexpr size_t kMinOptions = offsetof(tscm_options, exec_flags) + sizeof(int);
-        if (opt_in->struct_size < kMinOptions || opt_in->struct_size > sizeof(tscm_options))
-            return fail(TSCM_E_INVALID, "tscm_options.struct_size is not a size this library knows (initialise the struct with tscm_default_options; ABI 6)");
-        std::memcpy(&opt, opt_in, opt_in->struct_size);
-        opt.struct_size = sizeof(tscm_options);
-    }
+    if (int rc = read_options(opt_in, s0->mono, opt)) return rc;
     if (opt.max_num_iterations < 0 || opt.max_num_iterations > TSCM_MAX_ITERATIONS) return fail(TSCM_E_INVALID, "max_num_iterations must be in [0, 255]");
     if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
     HIP_TRY(hipSetDevice(s0->device));
@@ -1348,11 +1355,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         for (tscm_solver *s : run.m) { HIP_TRY(hipStreamSynchronize(s->own_stream)); s->stream = g->stream; }
     }
     for (size_t r = 0; r < run.m.size(); ++r) std::memset(&sums[r], 0, sizeof(tscm_summary));
-    for (tscm_solver *s : run.m) {
-        s->f32_jacobian = opt.jacobian_fp32 != 0;
-        if (s->f32_jacobian && s->lds_eval32 > 64 * 1024)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(s->eval32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
-    }
+    for (tscm_solver *s : run.m) s->f32_jacobian = opt.jacobian_fp32 != 0;
 
     // control block (identical on every rank), counter of the fused T reduction, start point: one launch (k_begin_solve)
     const double t0 = wall();
@@ -1555,7 +1558,8 @@ extern "C" int tscm_solve_mono(const tscm_problem *p, const tscm_options *opt, t
 // operator level
 // ------------------------------------------------------------------------------------------------
 // upload the problem's current parameters into buffer 0 and compute the pose constants
-static int prepare_eval(tscm_solver *s)
+// with_floats: the fp32-Jacobian kernel also reads the float half of the per-view records
+static int prepare_eval(tscm_solver *s, int with_floats = 0)
 {
     int rc;
     if ((rc = tscm_solver_upload_params(s, s->h_cam_rt, s->h_intr, s->h_board_rt))) return rc;
@@ -1565,7 +1569,7 @@ static int prepare_eval(tscm_solver *s)
     HIP_TRY(hipMemcpy(S.intr[0], s->d_init_intr, sizeof(double) * 9 * s->C, hipMemcpyDeviceToDevice));
     if (s->B) HIP_TRY(hipMemcpy(S.board_rt[0], s->d_init_board, sizeof(double) * 6 * s->B, hipMemcpyDeviceToDevice));
     hipLaunchKernelGGL(k_pose_prep, dim3((s->P.B + s->P.C + 255) / 256), dim3(256), 0, s->stream, s->P, S, 0);
-    hipLaunchKernelGGL(k_view_prep, dim3((s->P.V + s->P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, s->P, S, 0, 0);
+    hipLaunchKernelGGL(k_view_prep, dim3((s->P.V + s->P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, s->P, S, 0, with_floats);
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -1616,11 +1620,25 @@ extern "C" int tscm_eval_functor(const tscm_problem *p, int device, double *resi
 extern "C" int tscm_eval_normal_equations(const tscm_problem *p, int device, double *board_gram, double *board_grad,
                                           double *view_cross, double *cam_gram, double *cam_grad, double *cost)
 {
-    tscm_solver *s = nullptr;
-    int rc = tscm_solver_create(p, device, &s);
+    return tscm_eval_normal_equations_ex(p, device, nullptr, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+}
+
+// the Gram kernel is the one a solve with these options runs: jacobian_fp32 -> k_eval_gram_f32, TSCM_EXEC_GRAM_16X16 ->
+// k_eval_gram, k_eval_gram4 otherwise (the other flags do not touch the evaluation).  Every kernel writes the same fp64
+// record layout, so the extraction below is shared
+extern "C" int tscm_eval_normal_equations_ex(const tscm_problem *p, int device, const tscm_options *opt_in, double *board_gram,
+                                             double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+{
+    tscm_options opt;
+    int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
+    if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
+    tscm_solver *s = nullptr;
+    if ((rc = tscm_solver_create(p, device, &s))) return rc;
     std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
-    if ((rc = prepare_eval(s))) return rc;
+    s->f32_jacobian = opt.jacobian_fp32 != 0;
+    s->gram16 = (opt.exec_flags & TSCM_EXEC_GRAM_16X16) != 0;
+    if ((rc = prepare_eval(s, s->f32_jacobian ? 1 : 0))) return rc;
     const DevProblem &P = s->P;
     DevState &S = s->S;
     if ((rc = launch_eval(s, 0))) return rc;
