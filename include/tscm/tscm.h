@@ -288,6 +288,19 @@ int tscm_eval_normal_equations_ex(const tscm_problem *problem, int device, const
                                   double *board_gram, double *board_grad, double *view_cross,
                                   double *cam_gram, double *cam_grad, double *cost);
 
+/* At the problem's parameters: the candidate point of the first trust-region step that
+ * a solve with `opt` takes (NULL = defaults).  The radius is
+ * opt->initial_trust_region_radius; the step also follows opt's LM diagonal clamps,
+ * jacobi_scaling, jacobian_fp32 and exec_flags.  Termination tolerances are ignored.
+ * cam_rt [C*6] (may be NULL for a mono problem), intr [C*9], board_rt [B*6] receive
+ * x + delta exactly as that solve evaluates it; constant blocks come back as their input.
+ * *valid = 0 if the step is invalid (the linear solve failed: no candidate).  summary
+ * (may be NULL) = the one-iteration summary.  Options are checked as in
+ * tscm_eval_normal_equations_ex.  For parity tests.                                 */
+int tscm_eval_step_ex(const tscm_problem *problem, int device, const tscm_options *opt,
+                      double *cam_rt, double *intr, double *board_rt, int *valid,
+                      tscm_summary *summary);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

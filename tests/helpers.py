@@ -269,3 +269,282 @@ def rig_with_unseen_boards(p: Problem, extra: int = 2) -> Problem:
                 p.cam_pose_constant, False,
                 meta=dict(p.meta, gt_board_rt=np.concatenate([p.meta["gt_board_rt"], np.zeros((extra, 6))])))
     return q.normalised()
+
+
+# ----------------------------------------------------------------------------- LM step (extended precision)
+# Intrinsic columns the solver moves: fx fy cx cy xi lambda alpha.  b, c (skew) have structurally zero Jacobian columns, so in
+# the oracle's program they are decoupled columns with a zero step; here they are left out.
+N_INTR_FREE = 7
+CAM_W = 6 + N_INTR_FREE
+
+
+def step_columns(p: Problem) -> dict:
+    """The oracle's column map (orc_solve's reduced program) as masks: a camera's 13 columns (pose 6, intrinsics 7) are free
+    when the camera has views (its pose also not constant, and not mono); a board is free when it has views and is not
+    constant; a board with views but a constant pose keeps its residual blocks (F columns only)."""
+    C, B = p.n_cameras, p.n_boards
+    cnt = np.asarray(p.view_count)
+    vc, vb = np.asarray(p.view_camera)[cnt > 0], np.asarray(p.view_board)[cnt > 0]
+    cam_active = np.zeros(C, dtype=bool); cam_active[vc] = True
+    board_seen = np.zeros(B, dtype=bool); board_seen[vb] = True
+    bconst = np.zeros(B, dtype=bool) if p.board_pose_constant is None else np.asarray(p.board_pose_constant, dtype=bool)
+    free = np.zeros((C, CAM_W), dtype=bool)
+    free[:, 6:] = cam_active[:, None]
+    free[:, :6] = (cam_active & ~np.asarray(p.cam_pose_constant, dtype=bool) & (not p.mono))[:, None]
+    return dict(cam_free=free, board_seen=board_seen, board_free=board_seen & ~bconst)
+
+
+def step_terms(p: Problem, jets=None, dtype=np.longdouble) -> dict:
+    """Per-view Gram products of the oracle's dual-number Jacobian in `dtype`, restricted to the solver's columns:
+    EE [V,6,6] = E^T E, EF [V,6,13] = E^T F, FF [V,13,13] = F^T F, Er [V,6], Fr [V,13], and the cost.  The products are
+    exact sums of fp64 products up to `dtype`'s rounding."""
+    cost, res, Jc, Jb, Ji = orc.evaluate(p, jets=True) if jets is None else jets
+    cnt = np.asarray(p.view_count, dtype=np.int64)
+    start = np.cumsum(cnt) - cnt
+    V = p.n_views
+    res = np.asarray(res, dtype=dtype).reshape(-1, 2)
+    E_all = np.asarray(Jb, dtype=dtype).reshape(-1, 2, 6)
+    F_all = np.concatenate([np.asarray(Jc, dtype=dtype).reshape(-1, 2, 6), np.asarray(Ji, dtype=dtype).reshape(-1, 2, 9)[:, :, :N_INTR_FREE]], axis=-1)
+    out = dict(EE=np.zeros((V, 6, 6), dtype), EF=np.zeros((V, 6, CAM_W), dtype), FF=np.zeros((V, CAM_W, CAM_W), dtype),
+               Er=np.zeros((V, 6), dtype), Fr=np.zeros((V, CAM_W), dtype), cost=float(cost))
+    for c in np.unique(cnt[cnt > 0]):
+        vs = np.nonzero(cnt == c)[0]
+        idx = start[vs, None] + np.arange(c)
+        E, F, r = E_all[idx].reshape(len(vs), 2 * c, 6), F_all[idx].reshape(len(vs), 2 * c, CAM_W), res[idx].reshape(len(vs), 2 * c)
+        out["EE"][vs] = np.einsum("vki,vkj->vij", E, E)
+        out["EF"][vs] = np.einsum("vki,vkj->vij", E, F)
+        out["FF"][vs] = np.einsum("vki,vkj->vij", F, F)
+        out["Er"][vs] = np.einsum("vki,vk->vi", E, r)
+        out["Fr"][vs] = np.einsum("vki,vk->vi", F, r)
+    return out
+
+
+def _chol(A):
+    """Lower Cholesky factor of the SPD matrix A in A's dtype (longdouble: numpy.linalg has no such path); None if A is not
+    positive definite."""
+    n = A.shape[0]
+    L = np.zeros_like(A)
+    R = A.copy()
+    for k in range(n):
+        d = R[k, k]
+        if not d > 0:
+            return None
+        L[k, k] = np.sqrt(d)
+        L[k + 1:, k] = R[k + 1:, k] / L[k, k]
+        R[k + 1:, k + 1:] -= np.outer(L[k + 1:, k], L[k + 1:, k])
+    return L
+
+
+def _chol_solve(L, b):
+    n = L.shape[0]
+    y = b.copy()
+    for k in range(n):
+        y[k] = (y[k] - L[k, :k] @ y[:k]) / L[k, k]
+    for k in range(n - 1, -1, -1):
+        y[k] = (y[k] - L[k + 1:, k] @ y[k + 1:]) / L[k, k]
+    return y
+
+
+def _batched_spd_inv(M):
+    """Inverses of a batch of small SPD matrices [n,k,k] by Gauss-Jordan without pivoting (SPD: no pivot needed) in M's
+    dtype; None if a pivot is not positive."""
+    n, k, _ = M.shape
+    A = np.concatenate([M.copy(), np.broadcast_to(np.eye(k, dtype=M.dtype), M.shape).copy()], axis=2)
+    for j in range(k):
+        piv = A[:, j, j].copy()
+        if not np.all(piv > 0):
+            return None
+        A[:, j, :] /= piv[:, None]
+        f = A[:, :, j].copy()
+        f[:, j] = 0
+        A -= f[:, :, None] * A[:, j, None, :]
+    inv = A[:, :, k:]
+    return (inv + np.swapaxes(inv, 1, 2)) / 2
+
+
+def reference_step(p: Problem, *, initial_trust_region_radius=1e4, min_lm_diagonal=1e-6, max_lm_diagonal=1e32,
+                   jacobi_scaling=1, terms=None, cols=None, mistake=None, **_ignored) -> dict:
+    """The first LM step of a solve with these options, in extended precision (np.longdouble), restated from Ceres'
+    LevenbergMarquardtStrategy + SchurEliminator as the oracle does it (orc_solve):
+      s = 1 / (1 + |column|)  (1 without jacobi_scaling),
+      D^2 = clamp(|column of J s|^2, min_lm_diagonal, max_lm_diagonal) / radius,
+      (S J^T J S + D^2) y = S J^T r  by eliminating every free board's 6x6 block, a Cholesky factorisation of the reduced
+      camera system and back-substitution,   delta = -s * y.
+    Returns delta by block (cam [C,13], board [B,6]; zero where not free), the scaled system (for backward errors), the
+    model cost change -(J delta)^T (r + J delta / 2), kappa_2 of the scaled, damped reduced system, and the masks.
+    `mistake` (tests/test_step_tolerance.py) alters the computation the way a kernel could get it wrong."""
+    t = step_terms(p) if terms is None else terms
+    cols = step_columns(p) if cols is None else cols
+    ld = t["EE"].dtype
+    C, B = p.n_cameras, p.n_boards
+    cnt = np.asarray(p.view_count)
+    vc, vb = np.asarray(p.view_camera, dtype=np.int64), np.asarray(p.view_board, dtype=np.int64)
+    live = cnt > 0
+    cf, bf = cols["cam_free"], cols["board_free"]
+    ve = live & bf[vb]                                  # views whose board is eliminated (E columns in J)
+    # column norms, scaling, damping
+    FFc = np.zeros((C, CAM_W, CAM_W), ld); np.add.at(FFc, vc[live], t["FF"][live])
+    Frc = np.zeros((C, CAM_W), ld); np.add.at(Frc, vc[live], t["Fr"][live])
+    EEb = np.zeros((B, 6, 6), ld); np.add.at(EEb, vb[ve], t["EE"][ve])
+    Erb = np.zeros((B, 6), ld); np.add.at(Erb, vb[ve], t["Er"][ve])
+    FFc *= (cf[:, :, None] & cf[:, None, :]); Frc *= cf
+    EEb *= bf[:, None, None]; Erb *= bf[:, None]
+    nc, nb = np.diagonal(FFc, axis1=1, axis2=2).copy(), np.diagonal(EEb, axis1=1, axis2=2).copy()
+    one = ld.type(1)
+    sc = one / (one + np.sqrt(nc)) if jacobi_scaling else np.ones_like(nc)
+    sb = one / (one + np.sqrt(nb)) if jacobi_scaling else np.ones_like(nb)
+    if mistake == "scale_rhs_twice":
+        Frc, Erb = Frc * sc, Erb * sb
+    radius = ld.type(initial_trust_region_radius)
+    lo, hi = ld.type(min_lm_diagonal), ld.type(max_lm_diagonal)
+    dc = np.clip(sc * sc * nc, lo, hi) / radius
+    db = np.clip(sb * sb * nb, lo, hi) / radius
+    # scaled system
+    Acc = sc[:, :, None] * FFc * sc[:, None, :]
+    Abb = sb[:, :, None] * EEb * sb[:, None, :]
+    W = sb[vb][:, :, None] * t["EF"] * sc[vc][:, None, :] * (ve[:, None, None] & cf[vc][:, None, :])
+    gc, gb = sc * Frc, sb * Erb
+    idx = np.arange(CAM_W)
+    Acc_d = Acc.copy(); Acc_d[:, idx, idx] += dc
+    Abb_d = Abb.copy(); Abb_d[:, np.arange(6), np.arange(6)] += db
+    if mistake == "e_block_undamped":
+        # on the >3-camera path (k_schur_factor) only: boards seen by more than three cameras
+        slow = np.nonzero(np.bincount(vb[ve], minlength=B) > 3)[0]
+        if slow.size:
+            Abb_d[slow[0]] = Abb[slow[0]]
+    # eliminate the free boards
+    fb = np.nonzero(bf)[0]
+    Einv = np.zeros((B, 6, 6), ld)
+    if fb.size:
+        inv = _batched_spd_inv(Abb_d[fb])
+        if inv is None:
+            return dict(ok=False)
+        Einv[fb] = inv
+    S = np.zeros((C, C, CAM_W, CAM_W), ld)
+    S[np.arange(C), np.arange(C)] = Acc_d
+    rhs = gc.copy()
+    ZW = np.einsum("vij,vjk->vik", Einv[vb], W)         # E^-1 W per view
+    Zg = np.einsum("bij,bj->bi", Einv, gb)
+    np.add.at(rhs, vc[ve], -np.einsum("vik,vi->vk", W[ve], Zg[vb[ve]]))
+    # every ordered pair of views of one eliminated board: boards grouped by their number of views
+    ev = np.nonzero(ve)[0]
+    ev = ev[np.argsort(vb[ev], kind="stable")]
+    nvb = np.bincount(vb[ev], minlength=B)
+    first = np.cumsum(nvb) - nvb
+    pv1, pv2 = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for k in np.unique(nvb[nvb > 0]):
+        grp = ev[first[nvb == k][:, None] + np.arange(k)]          # [boards, k] views
+        pv1.append(np.repeat(grp, k, axis=1).ravel()); pv2.append(np.tile(grp, (1, k)).ravel())
+    pv1, pv2 = np.concatenate(pv1), np.concatenate(pv2)
+    if pv1.size:
+        blk = np.einsum("pik,pil->pkl", W[pv1], ZW[pv2])
+        if mistake == "pair_tile_missing_board":
+            # one board's contribution left out of one off-diagonal camera-pair tile
+            sel = vc[pv1] != vc[pv2]
+            if sel.any():
+                b0 = vb[pv1[sel][0]]
+                m1, m2 = vc[pv1[sel][0]], vc[pv2[sel][0]]
+                drop = (vb[pv1] == b0) & (((vc[pv1] == m1) & (vc[pv2] == m2)) | ((vc[pv1] == m2) & (vc[pv2] == m1)))
+                blk[drop] = 0
+        if mistake == "pair_block_transposed":
+            # one off-diagonal camera-pair tile (both of its orientations) used transposed
+            sel = vc[pv1] != vc[pv2]
+            if sel.any():
+                m1, m2 = vc[pv1[sel][0]], vc[pv2[sel][0]]
+                sel = ((vc[pv1] == m1) & (vc[pv2] == m2)) | ((vc[pv1] == m2) & (vc[pv2] == m1))
+                blk[sel] = np.swapaxes(blk[sel], 1, 2)
+        np.add.at(S, (vc[pv1], vc[pv2]), -blk)
+    fmask = cf.ravel()
+    Sf = S.transpose(0, 2, 1, 3).reshape(C * CAM_W, C * CAM_W)[np.ix_(fmask, fmask)]
+    if mistake == "damping_shifted":
+        # the damping of the compact column behind a constant camera pose taken from its neighbour
+        cst = np.nonzero(cf[:, 6] & ~cf[:, 0])[0]
+        m = cst[-1] if cst.size else 0
+        pos = int(np.sum(cf[:m]))                     # compact index of camera m's first (intrinsic) column
+        dv = dc[cf]
+        Sf[pos, pos] += dv[pos + 1] - dv[pos]
+    L = _chol(Sf)
+    if L is None:
+        return dict(ok=False)
+    yf = np.zeros(C * CAM_W, ld)
+    yf[fmask] = _chol_solve(L, rhs.ravel()[fmask])
+    yc = yf.reshape(C, CAM_W)
+    # back-substitution
+    yv = yc[vc]
+    if mistake == "backsub_other_camera":
+        v0 = np.nonzero(ve)[0][0]
+        yv = yv.copy(); yv[v0] = yc[(vc[v0] + 1) % C]
+    acc = gb.copy()
+    np.add.at(acc, vb[ve], -np.einsum("vik,vk->vi", W[ve], yv[ve]))
+    yb = np.einsum("bij,bj->bi", Einv, acc) * bf[:, None]
+    dcam, dboard = -sc * yc, -sb * yb
+    # model cost change -(J d)^T (r + J d / 2) on the unscaled Gram products
+    Jr = np.sum(dcam * _sum_by(vc[live], t["Fr"][live], C) * cf)
+    Jr += np.sum(dboard * _sum_by(vb[ve], t["Er"][ve], B))
+    dd = np.einsum("ci,cij,cj->", dcam, _sum_by(vc[live], t["FF"][live], C) * (cf[:, :, None] & cf[:, None, :]), dcam)
+    dd += np.einsum("bi,bij,bj->", dboard, _sum_by(vb[ve], t["EE"][ve], B), dboard)
+    dd += 2 * np.einsum("vi,vij,vj->", dboard[vb[ve]], t["EF"][ve], dcam[vc[ve]] * cf[vc[ve]])
+    model = -(Jr + dd / 2)
+    ev = np.linalg.eigvalsh(np.asarray(Sf, dtype=np.float64)) if Sf.size else np.ones(1)
+    return dict(ok=True, cam=dcam, board=dboard, model_cost_change=float(model), kappa=float(ev[-1] / ev[0]),
+                cam_free=cf, board_free=bf, sc=sc, sb=sb, Acc=Acc_d, Abb=Abb_d, W=W, gc=gc, gb=gb, view_elim=ve,
+                nc=nc, nb=nb, cost=t["cost"])
+
+
+def _sum_by(index, values, n):
+    out = np.zeros((n,) + values.shape[1:], values.dtype)
+    np.add.at(out, index, values)
+    return out
+
+
+def step_errors(p: Problem, ref: dict, cand: dict) -> dict:
+    """A candidate (cam_rt, intr, board_rt: x + delta as a solve evaluates it) against the reference step at x = p's
+    parameters, in the scaled space of the reference system (A y = g, delta = -s y):
+      backward: largest blockwise backward error over the block rows (each camera's free columns, each free board):
+                |(A y^ - g)_i| / (sum_j |A_ij| (|y^_j| + u_j) + |g_i|),  u = one ulp of x in scaled units (the rounding of
+                the candidate);
+      forward_{cam_pose, intr, board}: |y^ - y| of that kind of block, less u entrywise, relative to |y| of that kind.
+    Norms: 2-norms of vectors, Frobenius norms of blocks."""
+    ld = ref["Acc"].dtype
+    cf, bf, ve = ref["cam_free"], ref["board_free"], ref["view_elim"]
+    vc, vb = np.asarray(p.view_camera, dtype=np.int64), np.asarray(p.view_board, dtype=np.int64)
+    x_c = np.concatenate([p.cam_rt, p.intr[:, :N_INTR_FREE]], axis=1)
+    c_c = np.concatenate([cand["cam_rt"], cand["intr"][:, :N_INTR_FREE]], axis=1)
+    dc_hat = np.where(cf, (c_c - x_c), 0.0).astype(ld)
+    db_hat = np.where(bf[:, None], cand["board_rt"] - p.board_rt, 0.0).astype(ld)
+    yc, yb = -dc_hat / ref["sc"], -db_hat / ref["sb"]
+    uc = np.where(cf, np.spacing(np.abs(x_c)), 0.0).astype(ld) / ref["sc"]
+    ub = np.where(bf[:, None], np.spacing(np.abs(p.board_rt)), 0.0).astype(ld) / ref["sb"]
+    W, Acc, Abb = ref["W"], ref["Acc"], ref["Abb"]
+    nrm = lambda a, ax: np.sqrt(np.sum(np.asarray(a, dtype=np.float64) ** 2, axis=ax))
+    n_yc, n_yb = nrm(yc, 1) + nrm(uc, 1), nrm(yb, 1) + nrm(ub, 1)
+    nW = nrm(W, (1, 2))
+    rc = np.einsum("cij,cj->ci", Acc, yc) - ref["gc"]
+    np.add.at(rc, vc[ve], np.einsum("vik,vi->vk", W[ve], yb[vb[ve]]))
+    rb = np.einsum("bij,bj->bi", Abb, yb) - ref["gb"]
+    np.add.at(rb, vb[ve], np.einsum("vik,vk->vi", W[ve], yc[vc[ve]]))
+    den_c = nrm(Acc, (1, 2)) * n_yc + nrm(ref["gc"], 1)
+    np.add.at(den_c, vc[ve], nW[ve] * n_yb[vb[ve]])
+    den_b = nrm(Abb, (1, 2)) * n_yb + nrm(ref["gb"], 1)
+    np.add.at(den_b, vb[ve], nW[ve] * n_yc[vc[ve]])
+    rc, rb = nrm(rc * cf, 1), nrm(rb * bf[:, None], 1)
+    bc = np.where(den_c > 0, rc / np.where(den_c > 0, den_c, 1.0), np.where(rc > 0, np.inf, 0.0))
+    bb = np.where(den_b > 0, rb / np.where(den_b > 0, den_b, 1.0), np.where(rb > 0, np.inf, 0.0))
+    y_c, y_b = -ref["cam"] / ref["sc"], -ref["board"] / ref["sb"]
+    fc = np.maximum(np.abs(np.asarray(yc - y_c, dtype=np.float64)) - np.asarray(uc, dtype=np.float64), 0.0)
+    fb = np.maximum(np.abs(np.asarray(yb - y_b, dtype=np.float64)) - np.asarray(ub, dtype=np.float64), 0.0)
+    def fwd(d, y):
+        ny, nd = np.linalg.norm(np.asarray(y, dtype=np.float64)), np.linalg.norm(d)
+        return float(nd / ny) if ny > 0 else (np.inf if nd > 0 else 0.0)
+    return dict(backward=float(max(bc.max(initial=0.0), bb.max(initial=0.0))),
+                backward_cam=bc, backward_board=bb,
+                forward_cam_pose=fwd(fc[:, :6], y_c[:, :6]), forward_intr=fwd(fc[:, 6:], y_c[:, 6:]),
+                forward_board=fwd(fb, y_b))
+
+
+def reference_candidate(p: Problem, ref: dict) -> dict:
+    """x + delta_ref rounded to fp64, in the caller's layout (constant blocks and b, c as they are)."""
+    cam, intr = p.cam_rt.copy(), p.intr.copy()
+    cam += np.asarray(ref["cam"][:, :6], dtype=np.float64) if not p.mono else 0.0
+    intr[:, :N_INTR_FREE] += np.asarray(ref["cam"][:, 6:], dtype=np.float64)
+    return dict(cam_rt=cam, intr=intr, board_rt=p.board_rt + np.asarray(ref["board"], dtype=np.float64))

@@ -53,6 +53,9 @@ def test_no_gpu_means_loud_failure_not_fallback():
         with pytest.raises(lib.TscmError) as e:
             api.normal_equations(p, **kw)
         assert e.value.code == -2, kw
+    with pytest.raises(lib.TscmError) as e:
+        api.step(p)
+    assert e.value.code == -2
 
 
 def test_normal_equations_ex_checks_options_like_the_solve():
@@ -63,6 +66,9 @@ def test_normal_equations_ex_checks_options_like_the_solve():
         o = lib.default_options(False)
         setattr(o, field, value)
         assert lib.lib().tscm_eval_normal_equations_ex(C.byref(cp), 0, C.byref(o), None, None, None, None, None, None) == -1, field
+        assert (b"struct_size" if field == "struct_size" else b"exec_flags") in lib.lib().tscm_last_error()
+        cam, intr, board, valid = np.zeros((4, 6)), np.zeros((4, 9)), np.zeros((p.n_boards, 6)), C.c_int(0)
+        assert lib.lib().tscm_eval_step_ex(C.byref(cp), 0, C.byref(o), lib.dptr(cam), lib.dptr(intr), lib.dptr(board), C.byref(valid), None) == -1, field
         assert (b"struct_size" if field == "struct_size" else b"exec_flags") in lib.lib().tscm_last_error()
 
 

@@ -299,6 +299,21 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
     return out
 
 
+def step(problem: Problem, device: int = 0, **options) -> dict:
+    """The candidate point of the first trust-region step a solve with these options takes (tscm_eval_step_ex), at the
+    problem's parameters, which stay as they are: cam_rt, intr, board_rt (x + delta as that solve evaluates it), valid
+    (False: the linear solve failed) and the one-iteration summary."""
+    assert _is_normalised(problem)
+    cam, intr, board = np.zeros_like(problem.cam_rt), np.zeros_like(problem.intr), np.zeros_like(problem.board_rt)
+    valid = C.c_int(0)
+    s = _l.CSummary()
+    cp = _l.c_problem(problem)
+    o = _l.default_options(problem.mono, **options)
+    _l.check(_l.lib().tscm_eval_step_ex(C.byref(cp), device, C.byref(o), _l.dptr(cam), _l.dptr(intr), _l.dptr(board),
+                                        C.byref(valid), C.byref(s)))
+    return dict(cam_rt=cam, intr=intr, board_rt=board, valid=bool(valid.value), summary=_l.summary_dict(s))
+
+
 def project(intr, points, device: int = 0) -> np.ndarray:
     intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(9)
     pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)

@@ -1478,19 +1478,25 @@ extern "C" int tscm_solver_solve_group(tscm_solver **solvers, int n, const tscm_
     return run_lm(run, opt, summaries, reset);
 }
 
-extern "C" int tscm_solver_download_params(tscm_solver *s, double *cam_rt, double *intr, double *board_rt)
+// parameter buffer `buf` (0: the accepted point, 1: the candidate) in the caller's layout
+static int download_buffer(tscm_solver *s, int buf, double *cam_rt, double *intr, double *board_rt)
 {
-    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
     HIP_TRY(hipSetDevice(s->device));
-    if (cam_rt && !s->mono) HIP_TRY(hipMemcpy(cam_rt, s->S.cam_rt[0], sizeof(double) * 6 * s->C, hipMemcpyDeviceToHost));
-    if (intr) HIP_TRY(hipMemcpy(intr, s->S.intr[0], sizeof(double) * 9 * s->C, hipMemcpyDeviceToHost));
+    if (cam_rt && !s->mono) HIP_TRY(hipMemcpy(cam_rt, s->S.cam_rt[buf], sizeof(double) * 6 * s->C, hipMemcpyDeviceToHost));
+    if (intr) HIP_TRY(hipMemcpy(intr, s->S.intr[buf], sizeof(double) * 9 * s->C, hipMemcpyDeviceToHost));
     // only the owned boards: the other entries of the caller's array are left untouched (see tscm_solver_gather_boards)
     if (board_rt && s->B) {
         std::vector<double> brd(6 * (size_t)s->B);
-        HIP_TRY(hipMemcpy(brd.data(), s->S.board_rt[0], sizeof(double) * 6 * s->B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(brd.data(), s->S.board_rt[buf], sizeof(double) * 6 * s->B, hipMemcpyDeviceToHost));
         for (int i = 0; i < s->B; ++i) std::memcpy(board_rt + 6 * ((size_t)s->b0 + s->board_perm[i]), brd.data() + 6 * (size_t)i, 6 * sizeof(double));
     }
     return 0;
+}
+
+extern "C" int tscm_solver_download_params(tscm_solver *s, double *cam_rt, double *intr, double *board_rt)
+{
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    return download_buffer(s, 0, cam_rt, intr, board_rt);
 }
 
 // After a sharded solve every rank holds the poses of its own boards.  This makes the caller's full-length array
@@ -1552,6 +1558,35 @@ extern "C" int tscm_solve_mono(const tscm_problem *p, const tscm_options *opt, t
 {
     if (p && !p->mono) return fail(TSCM_E_INVALID, "tscm_solve_mono called with a multi-camera problem");
     return solve_once(p, opt, sum);
+}
+
+// The candidate of a solve's first trust-region step: the solve itself, stopped after one iteration (termination
+// tolerances zeroed, so nothing ends it before the step is taken).  The first iteration writes its candidate into buffer 1
+// (ctrl->cur = 0 at the start); k_end_solve / k_finish_solve copy it into buffer 0 only if the step was accepted and never
+// write buffer 1, so buffer 1 holds the candidate whether the step was accepted or not
+extern "C" int tscm_eval_step_ex(const tscm_problem *p, int device, const tscm_options *opt_in, double *cam_rt, double *intr,
+                                 double *board_rt, int *valid, tscm_summary *summary)
+{
+    tscm_options opt;
+    int rc = read_options(opt_in, p ? p->mono : 0, opt);
+    if (rc) return rc;
+    if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
+    if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
+    opt.max_num_iterations = 1;
+    opt.function_tolerance = opt.gradient_tolerance = opt.parameter_tolerance = 0.0;
+    tscm_solver *s = nullptr;
+    if ((rc = tscm_solver_create(p, device, &s))) return rc;
+    std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    if ((rc = tscm_solver_upload_params(s, p->cam_rt, p->intr, p->board_rt))) return rc;
+    tscm_summary sum;
+    if ((rc = tscm_solver_solve_resident(s, &opt, &sum, 1))) return rc;
+    // what the device does not hold (a mono problem's camera pose, boards without views) is the input
+    if (cam_rt) { if (p->cam_rt) std::memcpy(cam_rt, p->cam_rt, sizeof(double) * 6 * p->n_cameras); else std::memset(cam_rt, 0, sizeof(double) * 6 * p->n_cameras); }
+    if (p->n_boards) std::memcpy(board_rt, p->board_rt, sizeof(double) * 6 * p->n_boards);
+    if ((rc = download_buffer(s, 1, cam_rt, intr, board_rt))) return rc;
+    *valid = sum.num_iterations > 1 && sum.iterations[1].step_is_valid ? 1 : 0;
+    if (summary) *summary = sum;
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -117,7 +117,7 @@ EXPORTS = [
     "tscm_solver_create", "tscm_solver_set_comm", "tscm_solver_debug_withhold_handoff", "tscm_solver_reruns", "tscm_solver_solve", "tscm_solver_upload_params",
     "tscm_solver_solve_resident", "tscm_solver_download_params", "tscm_solver_destroy",
     "tscm_solver_kernel_time", "tscm_solver_exchange_time", "tscm_solve_multi", "tscm_solve_mono", "tscm_eval_functor",
-    "tscm_eval_normal_equations", "tscm_eval_normal_equations_ex", "tscm_project_points", "tscm_unproject_pixels",
+    "tscm_eval_normal_equations", "tscm_eval_normal_equations_ex", "tscm_eval_step_ex", "tscm_project_points", "tscm_unproject_pixels",
     "tscm_reprojection_error", "tscm_comm_unique_id", "tscm_comm_create", "tscm_comm_destroy",
     "tscm_shard_frames", "tscm_solver_create_sharded", "tscm_comm_create_local", "tscm_comm_ipc_open", "tscm_comm_ipc_connect", "tscm_solver_solve_group",
     "tscm_solver_gather_boards", "tscm_comm_info", "tscm_rig_init", "tscm_yaml_format", "tscm_yaml_write", "tscm_yaml_parse",
@@ -183,6 +183,7 @@ def lib():
     L.tscm_eval_functor.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp, dp, dp]
     L.tscm_eval_normal_equations.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp, dp, dp, dp]
     L.tscm_eval_normal_equations_ex.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, dp, dp, dp, dp, dp]
+    L.tscm_eval_step_ex.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, dp, dp, ip, C.POINTER(CSummary)]
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]
