@@ -3,14 +3,32 @@
 //
 //   g++ -std=c++11 -I include examples/calibrate_from_corners.cpp -L tscm_calib_amd/csrc -ltscm_hip
 //       -Wl,-rpath,$PWD/tscm_calib_amd/csrc -o examples/calibrate_from_corners        (one command line)
-//   examples/calibrate_from_corners corners.txt calib.yaml
+//   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
+//   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL)
 #include <tscm/tscm_calib.hpp>
 
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s corners.txt calib.yaml\n", argv[0]); return 2; }
+    int loss = TSCM_LOSS_NONE;
+    double loss_scale = 1.0;
+    for (int i = 3; i < argc; ++i) {
+        if (!std::strcmp(argv[i], "--loss") && i + 1 < argc) {
+            const char *k = argv[++i];
+            loss = !std::strcmp(k, "huber") ? TSCM_LOSS_HUBER : !std::strcmp(k, "soft_l1") ? TSCM_LOSS_SOFT_L1 : !std::strcmp(k, "cauchy") ? TSCM_LOSS_CAUCHY : -1;
+        } else if (!std::strcmp(argv[i], "--loss-scale") && i + 1 < argc) {
+            loss_scale = std::strtod(argv[++i], nullptr);
+        } else {
+            argc = 0;
+        }
+    }
+    if (argc < 3 || loss < 0) {
+        std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]\n", argv[0]);
+        return 2;
+    }
     tscm_corner_set cs;
     if (tscm_corners_read(argv[1], &cs) != 0) { std::fprintf(stderr, "%s\n", tscm_last_error()); return 1; }
     int rc = 0;
@@ -30,6 +48,7 @@ int main(int argc, char **argv)
                 pixels[b].resize(n);
                 for (int j = 0; j < n; ++j) pixels[b][j] = tscm::Point2d{ cs.pix_u[((size_t)m * B + b) * n + j], cs.pix_v[((size_t)m * B + b) * n + j] };
             }
+            cameras[m].set_loss(loss, loss_scale);
             const bool ok = cameras[m].calibrate(pixels, has, worlds, image, board);
             std::printf("camera %d: %s, rmse %.4f px, fx %.3f fy %.3f cx %.3f cy %.3f xi %.4f lambda %.4f alpha %.4f\n", m, ok ? "converged" : "NOT converged",
                         cameras[m].summary.rmse, cameras[m].intrinsic_[0], cameras[m].intrinsic_[1], cameras[m].intrinsic_[2], cameras[m].intrinsic_[3],
@@ -38,6 +57,7 @@ int main(int argc, char **argv)
         }
         if (C > 1) {
             tscm::MultiCalib mul_calib(cameras, worlds);                     // main.cpp:233
+            mul_calib.set_loss(loss, loss_scale);
             mul_calib.calibrate();                                           // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             for (int m = 0; m < C; ++m) std::printf("camera_%d reprojection error: %.6f\n", m, mul_calib.camera_error[m]);

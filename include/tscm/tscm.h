@@ -178,7 +178,9 @@ typedef struct tscm_summary {
     char message[128];
     double seconds_solve;          /* minimiser loop on the device: first to last kernel */
     double seconds_total;          /* wall time of the call (tscm_solve_*: incl. upload/download) */
-    double rmse;                   /* sqrt(2*final_cost/N)                             */
+    double rmse;                   /* sqrt(2*final_cost/N); with a robust loss (below) */
+                                   /*   the plain pixel RMSE at the final parameters,  */
+                                   /*   what tscm_reprojection_error returns           */
 } tscm_summary;
 
 typedef struct tscm_solver tscm_solver;   /* opaque: device buffers, stream, layouts  */
@@ -300,6 +302,35 @@ int tscm_eval_normal_equations_ex(const tscm_problem *problem, int device, const
 int tscm_eval_step_ex(const tscm_problem *problem, int device, const tscm_options *opt,
                       double *cam_rt, double *intr, double *board_rt, int *valid,
                       tscm_summary *summary);
+
+/* ------------------------------------------------------------------ robust losses
+ * The loss function of ceres::Problem::AddResidualBlock, for every residual block (one corner,
+ * r = (r_u, r_v), s = |r|^2) of the problem.  Ceres' own HuberLoss(a), SoftLOneLoss(a) and
+ * CauchyLoss(a) with scale a > 0 in pixels (b = a^2):
+ *   HUBER    rho = s (s <= b), 2 a sqrt(s) - b (s > b)
+ *   SOFT_L1  rho = 2 b (sqrt(1 + s / b) - 1)
+ *   CAUCHY   rho = b log(1 + s / b)
+ * The cost of a block is rho(s) / 2: initial_cost, final_cost, the iteration costs, cost_change and
+ * relative_decrease all use it; the gradient, the normal equations and the tolerance tests use the
+ * Jacobian and residual scaled by sqrt(rho'(s)) (Ceres' Corrector: rho'' <= 0 for all three losses,
+ * so no rank-one term).  TSCM_LOSS_NONE is the plain least-squares solve, bit for bit.
+ * An unknown kind, or a scale that is not finite or <= 0: TSCM_E_INVALID, checked before any device
+ * is touched.  A loss with TSCM_EXEC_GRAM_16X16: TSCM_E_UNSUPPORTED.
+ *   new ceres::HuberLoss(1.0)  ->  tscm_solver_set_loss(s, TSCM_LOSS_HUBER, 1.0)              */
+enum { TSCM_LOSS_NONE = 0, TSCM_LOSS_HUBER = 1, TSCM_LOSS_SOFT_L1 = 2, TSCM_LOSS_CAUCHY = 3 };
+/* the loss of every later solve / solve_resident of s (scale ignored for TSCM_LOSS_NONE).  The shards
+ * of a local group must carry the same loss (tscm_solver_solve_group: TSCM_E_INVALID otherwise); with
+ * an RCCL or IPC communicator every rank must set the same loss -- this is not checked.            */
+int tscm_solver_set_loss(tscm_solver *s, int kind, double scale);
+/* tscm_solve_mono or tscm_solve_multi (by problem->mono) with a loss                               */
+int tscm_solve_robust(const tscm_problem *problem, const tscm_options *opt, int kind, double scale, tscm_summary *summary);
+/* tscm_eval_normal_equations_ex / tscm_eval_step_ex with a loss: the outputs are the corrected
+ * (sqrt(rho')-scaled) normal equations, *cost = sum rho / 2                                        */
+int tscm_eval_normal_equations_robust(const tscm_problem *problem, int device, const tscm_options *opt, int kind, double scale,
+                                      double *board_gram, double *board_grad, double *view_cross,
+                                      double *cam_gram, double *cam_grad, double *cost);
+int tscm_eval_step_robust(const tscm_problem *problem, int device, const tscm_options *opt, int kind, double scale,
+                          double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary);
 
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms

@@ -71,6 +71,10 @@ public:
     const std::vector<std::vector<Point2d> > &pixels() const { return pixels_; }
     tscm_summary summary;                                 // of the last refinement()
 
+    // the loss of every residual block of refinement(): TSCM_LOSS_HUBER / _SOFT_L1 / _CAUCHY with its scale in pixels
+    // (Ceres' HuberLoss(scale) etc.), TSCM_LOSS_NONE = the reference's NULL (the default).  Checked by the next refinement().
+    void set_loss(int kind, double scale) { loss_kind_ = kind; loss_scale_ = scale; }
+
     // TS.cpp:247-282: joint refinement of intrinsic_ and rt_[i]; returns termination_type == CONVERGENCE
     bool refinement(const std::vector<std::vector<Point2d> > &pixels, const std::vector<Point3d> &worlds,
                     const tscm_options *options = nullptr)
@@ -91,7 +95,8 @@ public:
         P.obs_u = u.data(); P.obs_v = v.data(); P.intr = intrinsic_.data(); P.board_rt = rt.data(); P.mono = 1;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 1);
-        check(tscm_solve_mono(&P, &o, &summary));
+        if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_mono(&P, &o, &summary));
+        else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
         return summary.termination_type == TSCM_CONVERGENCE;             // TS.cpp:281
     }
@@ -158,6 +163,8 @@ public:
         return status;
     }
     bool has_init_guess_ = false;
+    int loss_kind_ = TSCM_LOSS_NONE;
+    double loss_scale_ = 0.0;
 
     // TS.cpp:62-74
     void poses_from_Rt()
@@ -342,6 +349,8 @@ public:
     // Several GPUs, one process per GPU (no counterpart in the reference): rank / world of this process and the
     // communicator made from rank 0's tscm_comm_unique_id (tscm_comm_create).  calibrate() then shards the frames.
     void set_sharding(int rank, int world, tscm_comm *comm) { rank_ = rank; world_ = world; comm_ = comm; }
+    // the loss of every residual block of calibrate() (see TripleSphereCamera::set_loss); with sharding every rank must set the same
+    void set_loss(int kind, double scale) { loss_kind_ = kind; loss_scale_ = scale; }
 
     // multi_calib.cpp:155-283: joint LM, write-back (update_param), reprojection-error report
     void calibrate(const tscm_options *options = nullptr)
@@ -374,11 +383,13 @@ public:
             tscm_solver *s = nullptr;
             check(tscm_solver_create_sharded(&P, device_, rank_, world_, &s));
             int rc = tscm_solver_set_comm(s, comm_);
+            if (rc == 0) rc = tscm_solver_set_loss(s, loss_kind_, loss_scale_);
             if (rc == 0) rc = tscm_solver_solve(s, &o, &summary);
             tscm_solver_destroy(s);
             check(rc);
         } else {
-            check(tscm_solve_multi(&P, &o, &summary));
+            if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_multi(&P, &o, &summary));
+            else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         }
         for (int m = 0; m < C; ++m) {                                    // :221-226
             cameras_[m].rt_.assign(&crt[6 * (size_t)m], &crt[6 * (size_t)m] + 6);
@@ -412,6 +423,8 @@ public:
     std::vector<MultiCalib_chessboard> chessboards_;
     std::vector<Point3d> worlds_;
     int rank_ = 0, world_ = 1;                // set_sharding()
+    int loss_kind_ = TSCM_LOSS_NONE;          // set_loss()
+    double loss_scale_ = 0.0;
     tscm_comm *comm_ = nullptr;
     tscm_summary summary;                     // BriefReport data of the solve (:218)
     std::vector<double> camera_error;         // per-camera mean pixel error (:281)

@@ -9,6 +9,7 @@ ReprojectionError functors via AutoDiffCostFunction    evaluate_functor(problem)
 TripleSphereCamera::project (TS.cpp:332-344)           project(intr, points)
 get_unit_sphere_coordinate (TS.h:39-57)                unproject(intr, pixels)
 error report (multi_calib.cpp:233-283)                 reprojection_error(problem)
+AddResidualBlock(..., new ceres::HuberLoss(a), ...)    loss=("huber", a); Solver.set_loss("huber", a)
 
 Everything computes on the GPU through libtscm_hip.so; there is no CPU path.
 """
@@ -52,6 +53,12 @@ class Solver:
     def set_comm(self, comm: "Comm | None"):
         self._comm = comm
         _l.check(_l.lib().tscm_solver_set_comm(self._h, comm._h if comm else None))
+
+    def set_loss(self, kind, scale: float = 1.0):
+        """The robust loss of every later solve / solve_resident (tscm_solver_set_loss): kind "huber" | "soft_l1" |
+        "cauchy" with its scale in pixels -- Ceres' HuberLoss(scale) etc. on every corner -- or None for plain least squares."""
+        k, a = _l.loss_args(None if kind is None else (kind, scale))
+        _l.check(_l.lib().tscm_solver_set_loss(self._h, k, a))
 
     def debug_withhold_handoff(self, on=True):
         """Tests only: one producer of the device-side hand-off of the NEXT solve never reports in (tscm_solver_debug_withhold_handoff);
@@ -179,13 +186,18 @@ class Group:
     """`world` shards of one problem on ONE device, solved in lock step with the in-process exchange
     (tscm_comm_create_local + tscm_solver_solve_group): the frame-sharded solver without RCCL, e.g. on a one-GPU box."""
 
-    def __init__(self, problem: Problem, world: int, device: int = 0):
+    def __init__(self, problem: Problem, world: int, device: int = 0, *, loss=None):
+        """loss: None, or (kind, scale) as for calibrate(); every shard carries it (Solver.set_loss)."""
         self.problem = problem.normalised() if not _is_normalised(problem) else problem
         self.world = world
         self.comms = Comm.local_group(world, device)
         self.solvers = [Solver(self.problem, device, r, world) for r in range(world)]
         for s, c in zip(self.solvers, self.comms):
             s.set_comm(c)
+        if loss is not None:
+            k, a = _l.loss_args(loss)
+            for s in self.solvers:
+                _l.check(_l.lib().tscm_solver_set_loss(s._h, k, a))
 
     def solve(self, **options) -> "list[dict]":
         """In/out through the problem's arrays, like Solver.solve; returns one summary per rank."""
@@ -230,10 +242,12 @@ def _is_normalised(p: Problem) -> bool:
             and (p.board_pose_constant is None or ok(p.board_pose_constant, np.uint8)))
 
 
-def calibrate(problem: Problem, device: int = 0, **options) -> dict:
+def calibrate(problem: Problem, device: int = 0, *, loss=None, **options) -> dict:
     """The Ceres block of MultiCalib::calibrate() (multi_calib.cpp:157-218): joint LM over
     camera poses, board poses and intrinsics, in place on `problem`.  Like the reference,
-    the outcome is not turned into an error -- inspect summary['termination']."""
+    the outcome is not turned into an error -- inspect summary['termination'].
+    loss: None (the reference's NULL loss), or (kind, scale) with kind "huber" | "soft_l1" | "cauchy"
+    and scale in pixels: Ceres' HuberLoss(scale) etc. on every corner (tscm_solve_robust)."""
     if problem.mono:
         raise ValueError("calibrate() is the multi-camera solve; use refinement() for a mono problem")
     assert _is_normalised(problem), "use Problem.normalised()"
@@ -241,13 +255,14 @@ def calibrate(problem: Problem, device: int = 0, **options) -> dict:
     s = _l.CSummary()
     cp = _l.c_problem(problem)
     _select(device)
-    _l.check(_l.lib().tscm_solve_multi(C.byref(cp), C.byref(o), C.byref(s)))
+    _solve_one_shot(cp, o, s, loss, _l.lib().tscm_solve_multi)
     return _l.summary_dict(s)
 
 
-def refinement(problem: Problem, device: int = 0, **options):
+def refinement(problem: Problem, device: int = 0, *, loss=None, **options):
     """TripleSphereCamera::refinement (TS.cpp:247-282): returns (converged, summary) where
-    converged == (termination_type == CONVERGENCE), the reference's return value (:281)."""
+    converged == (termination_type == CONVERGENCE), the reference's return value (:281).
+    loss: as for calibrate()."""
     if not problem.mono:
         raise ValueError("refinement() is the mono solve")
     assert _is_normalised(problem), "use Problem.normalised()"
@@ -255,9 +270,17 @@ def refinement(problem: Problem, device: int = 0, **options):
     s = _l.CSummary()
     cp = _l.c_problem(problem)
     _select(device)
-    _l.check(_l.lib().tscm_solve_mono(C.byref(cp), C.byref(o), C.byref(s)))
+    _solve_one_shot(cp, o, s, loss, _l.lib().tscm_solve_mono)
     d = _l.summary_dict(s)
     return d["termination_type"] == 0, d
+
+
+def _solve_one_shot(cp, o, s, loss, plain):
+    if loss is None:
+        _l.check(plain(C.byref(cp), C.byref(o), C.byref(s)))
+    else:
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_solve_robust(C.byref(cp), C.byref(o), k, a, C.byref(s)))
 
 
 def _select(device: int):
@@ -282,9 +305,10 @@ def evaluate_functor(problem: Problem, device: int = 0, jacobians: bool = True):
     return cost.value, res
 
 
-def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0) -> dict:
+def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0, loss=None) -> dict:
     """Schur-form normal equations (unscaled) from the Gram kernel a solve with these options runs:
-    k_eval_gram4 by default, k_eval_gram_f32 with jacobian_fp32=1, k_eval_gram with exec_flags=EXEC_GRAM_16X16."""
+    k_eval_gram4 by default, k_eval_gram_f32 with jacobian_fp32=1, k_eval_gram with exec_flags=EXEC_GRAM_16X16.
+    loss (as for calibrate()): the corrected equations of a robust solve, cost = sum rho / 2."""
     assert _is_normalised(problem)
     Cn, B, V = problem.n_cameras, problem.n_boards, problem.n_views
     out = dict(board_gram=np.zeros((B, 6, 6)), board_grad=np.zeros((B, 6)), view_cross=np.zeros((V, 6, 15)),
@@ -292,25 +316,33 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
     cost = C.c_double(0.0)
     cp = _l.c_problem(problem)
     o = _l.default_options(problem.mono, jacobian_fp32=jacobian_fp32, exec_flags=exec_flags)
-    _l.check(_l.lib().tscm_eval_normal_equations_ex(
-        C.byref(cp), device, C.byref(o), _l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
-        _l.dptr(out["cam_gram"]), _l.dptr(out["cam_grad"]), C.byref(cost)))
+    outs = (_l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
+            _l.dptr(out["cam_gram"]), _l.dptr(out["cam_grad"]), C.byref(cost))
+    if loss is None:
+        _l.check(_l.lib().tscm_eval_normal_equations_ex(C.byref(cp), device, C.byref(o), *outs))
+    else:
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_eval_normal_equations_robust(C.byref(cp), device, C.byref(o), k, a, *outs))
     out["cost"] = cost.value
     return out
 
 
-def step(problem: Problem, device: int = 0, **options) -> dict:
+def step(problem: Problem, device: int = 0, *, loss=None, **options) -> dict:
     """The candidate point of the first trust-region step a solve with these options takes (tscm_eval_step_ex), at the
     problem's parameters, which stay as they are: cam_rt, intr, board_rt (x + delta as that solve evaluates it), valid
-    (False: the linear solve failed) and the one-iteration summary."""
+    (False: the linear solve failed) and the one-iteration summary.  loss: as for calibrate() (tscm_eval_step_robust)."""
     assert _is_normalised(problem)
     cam, intr, board = np.zeros_like(problem.cam_rt), np.zeros_like(problem.intr), np.zeros_like(problem.board_rt)
     valid = C.c_int(0)
     s = _l.CSummary()
     cp = _l.c_problem(problem)
     o = _l.default_options(problem.mono, **options)
-    _l.check(_l.lib().tscm_eval_step_ex(C.byref(cp), device, C.byref(o), _l.dptr(cam), _l.dptr(intr), _l.dptr(board),
-                                        C.byref(valid), C.byref(s)))
+    outs = (_l.dptr(cam), _l.dptr(intr), _l.dptr(board), C.byref(valid), C.byref(s))
+    if loss is None:
+        _l.check(_l.lib().tscm_eval_step_ex(C.byref(cp), device, C.byref(o), *outs))
+    else:
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_eval_step_robust(C.byref(cp), device, C.byref(o), k, a, *outs))
     return dict(cam_rt=cam, intr=intr, board_rt=board, valid=bool(valid.value), summary=_l.summary_dict(s))
 
 

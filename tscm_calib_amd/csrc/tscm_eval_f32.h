@@ -57,9 +57,11 @@ __host__ __device__ inline int eval_f32_lds_doubles(int n_points, int ks)
 #define TSCM_F32_WGS 4
 #endif
 
-// KS: k-steps of a pass; MULTI: boards of more than 56 corners, P.g4_per corners per pass (the pass plan of k_eval_gram4: g4_plan)
-template <int KS, bool MULTI>
-__global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem P, DevState S, int cand)
+// KS: k-steps of a pass; MULTI: boards of more than 56 corners, P.g4_per corners per pass (the pass plan of k_eval_gram4: g4_plan);
+// ROBUST: a loss L (robust_rho) -- w = sqrt(rho') from the fp64 residual scales the corner's fp32 entries and, in fp64, its
+// residual before the conversion; the cost entry is the fp64 sum of rho (where r^T r sits otherwise).  See k_eval_gram4.
+template <int KS, bool MULTI, bool ROBUST = false>
+__global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem P, DevState S, int cand, LossArg L)
 {
     static_assert(KS >= 1 && KS <= kG4MaxKS, "a pass holds at most 56 rows");
     // the control block is read together with the static chunk tables (one memory round trip, not two);
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem 
     double *const rec_buf[2] = { S.rec[0], S.rec[1] };
     const int col = lane & 15, kq = lane >> 4;
     d4 camU = { 0.0, 0.0, 0.0, 0.0 }, camV = { 0.0, 0.0, 0.0, 0.0 };
-    double rr = 0.0;                               // this lane's share of r^T r, fp64
+    double rr = 0.0;                               // this lane's share of r^T r (ROBUST: of sum(rho)), fp64
     for (int i = lane; i < kTile32; i += 64) lds[i] = 0.0;  // all positions incl. the all-zero 16th tile column and the ones no corner maps to
     int prev_nv = 0;
     double pf_u = 0.0, pf_v = 0.0;
@@ -150,7 +152,11 @@ __global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem 
         for (int c0 = 0; c0 < cnt; c0 += per) {
             const int j = c0 + lane;
             const bool valid = lane < (MULTI ? min(per, cnt - c0) : cnt);
-            auto PUT = [&](int c, float u, float v) { fw[c * kP2] = f2{ u, v }; };
+            float wf = 1.f;                                               // ROBUST: the corner's weight, for the fp32 entries
+            auto PUT = [&](int c, float u, float v) {
+                if constexpr (ROBUST) { u *= wf; v *= wf; }
+                fw[c * kP2] = f2{ u, v };
+            };
             if (valid) {
                 const double x = bxy[2 * j], y = bxy[2 * j + 1];
                 const double ou = pf_u, ov = pf_v;
@@ -171,7 +177,15 @@ __global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem 
                 const double mx = X * ik, my = Y * ik;
                 const double ru = ou - (cc[39] * mx + cc[41]);
                 const double rv = ov - (cc[40] * my + cc[42]);
-                rr += ru * ru + rv * rv;
+                double w = 1.0;
+                if constexpr (ROBUST) {
+                    double rho;
+                    robust_rho(L, ru * ru + rv * rv, rho, w);
+                    rr += rho;
+                    wf = (float)w;
+                } else {
+                    rr += ru * ru + rv * rv;
+                }
                 // ---- fp32: derivatives, (u-row, v-row) pairs ---------------------------------------------
                 const float xf = (float)x, yf = (float)y;
                 const float Xf = (float)X, Yf = (float)Y, Zf = (float)Z, z1f = (float)z1, z2f = (float)z2;
@@ -222,7 +236,8 @@ __global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem 
                 PUT(kTcXi, a.x, a.y);
                 PUT(kTcLam, b.x, b.y);
                 PUT(kTcAl, c.x, c.y);
-                PUT(kTcR, (float)ru, (float)rv);
+                if constexpr (ROBUST) fw[kTcR * kP2] = f2{ (float)(w * ru), (float)(w * rv) };
+                else PUT(kTcR, (float)ru, (float)rv);
             } else if (lane < prev_nv) {
 #pragma unroll
                 for (int c = 0; c < kTcols; ++c) PUT(c, 0.f, 0.f);

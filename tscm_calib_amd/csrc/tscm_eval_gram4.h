@@ -111,9 +111,12 @@ __device__ __forceinline__ double quad_tb(double x, double c0, double c1, double
     return fma(c2, x2, fma(c0, x0, c1 * x1));
 }
 
-// KS: k-steps of a pass (4 KS rows >= the corners of a pass); MULTI: boards of more than 56 corners, P.g4_per corners per pass
-template <int KS, bool MULTI>
-__global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S, int cand)
+// KS: k-steps of a pass (4 KS rows >= the corners of a pass); MULTI: boards of more than 56 corners, P.g4_per corners per pass;
+// ROBUST: a loss L (robust_rho): every entry a corner puts into the tile, r column included, is scaled by w = sqrt(rho'), and
+// the cost entry of the camera tile is the lanes' fp64 sum of rho instead of the contraction r^T r.  L is not read
+// by the ROBUST = false instantiations, which compile to the code they had before the switch existed.
+template <int KS, bool MULTI, bool ROBUST = false>
+__global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S, int cand, LossArg L)
 {
     static_assert(KS >= 1 && KS <= kG4MaxKS, "a pass holds at most 56 rows");
     constexpr int kTile = g4_tile_doubles(KS);
@@ -158,6 +161,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     int prev_nv = 0;
     double pf_u = 0.0, pf_v = 0.0;
     int warm = 0;
+    double rho_sum = 0.0;                       // ROBUST: this lane's share of sum(rho), fp64
     if (ctrl_done) return;
     const int tgt = cand ? (ctrl_cur ^ 1) : ctrl_cur;
     const __amdgpu_buffer_rsrc_t r_rec = make_rsrc(tgt ? rec_buf[1] : rec_buf[0], sizeof(double) * (size_t)kRec * P.V);
@@ -262,7 +266,17 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
             // semantic column -> tile column of this kernel
             constexpr int tcol[15] = { kG4Wb, kG4Wb + 1, kG4Wb + 2, kG4Tc, kG4Tc + 1, kG4Tc + 2, kG4Wc, kG4Wc + 1, kG4Wc + 2,
                                        kG4F, kG4One, kG4Xi, kG4Lam, kG4Al, kG4R };
-            corner_geometry(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], u, v); });
+            if constexpr (ROBUST) {
+                // the corner's weight from its residual first (corner_residual: the same operations corner_geometry starts
+                // with, merged with them by the compiler), then every entry scaled as it is handed out
+                double ru, rv, rho, w;
+                corner_residual(x, y, pf_u, pf_v, VC, CC, ru, rv);
+                robust_rho(L, ru * ru + rv * rv, rho, w);
+                rho_sum += rho;
+                corner_geometry(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], w * u, w * v); });
+            } else {
+                corner_geometry(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], u, v); });
+            }
         } else if (lane < prev_nv) {
 #pragma unroll
             for (int c = 0; c < kTcols; ++c) (c < 8 ? fu_lo : fu_hi)[4 * c] = 0.0;
@@ -345,6 +359,12 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         for (int k = 0; k < 4; ++k) g_tlv[(size_t)(4 + kTlViews) * chunk + k] = tl_w[k];
     }
 #endif
+    if constexpr (ROBUST) {
+        // the cost entry (r, r) -- tile column 3 with itself: block 0 of q0, lane 16 * 3 + 3 -- is sum(rho), not sum(rho' s)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) rho_sum += __shfl_xor(rho_sum, o);
+        if (lane == 16 * kG4R + kG4R) { camU[0] = rho_sum; camV[0] = 0.0; }
+    }
     // the camera tile leaves in the 16x16 layout and column numbering of k_eval_gram (both triangles: every entry is
     // written by the lane that holds it and, mirrored, by the same lane; the doubly held pairs carry the same bits)
     wave_lds_fence();

@@ -607,6 +607,30 @@ __device__ __forceinline__ void corner_geometry(double x, double y, double ou, d
     PUT(gcR, ou - (fx * mx + CC(41)), ov - (fy * my + CC(42)));
 }
 
+// the residual of corner_geometry alone, in its operation order (the robust Gram kernels weight a corner's entries by
+// sqrt(rho'(|r|^2)) as corner_geometry hands them out, instead of holding all 30 until the residual, its last output, is
+// known: that held 60 registers more and spilled)
+template <typename FV, typename FC>
+__device__ __forceinline__ void corner_residual(double x, double y, double ou, double ov, FV VC, FC CC, double &ru, double &rv)
+{
+    const double X = fma(x, VC(0), fma(y, VC(3), VC(6)));
+    const double Y = fma(x, VC(1), fma(y, VC(4), VC(7)));
+    const double Z = fma(x, VC(2), fma(y, VC(5), VC(8)));
+    const double xi = CC(43), lam = CC(44), beta = CC(45);
+    const double rho2 = X * X + Y * Y;
+    double d1, id1, d2, id2, d3, id3;
+    sqrt_and_inverse(rho2 + Z * Z, d1, id1);
+    const double z1 = Z + xi * d1;
+    sqrt_and_inverse(rho2 + z1 * z1, d2, id2);
+    const double z2 = z1 + lam * d2;
+    sqrt_and_inverse(rho2 + z2 * z2, d3, id3);
+    const double k = z2 + beta * d3;
+    const double ik = fast_rcp(k);
+    const double mx = X * ik, my = Y * ik;
+    ru = ou - (CC(39) * mx + CC(41));
+    rv = ov - (CC(40) * my + CC(42));
+}
+
 #ifdef TSCM_WAVE_TIMELINE
 constexpr int kTimelineWaves = 8192;
 __device__ long long g_timeline[4 * kTimelineWaves];     // per wave of k_eval_gram: HW_ID, XCC_ID, start, end (10 ns ticks)
@@ -909,6 +933,31 @@ __host__ __device__ inline G4Plan g4_plan(int n_points)
     if (g.ks < 1) g.ks = 1;
     g.per = 4 * g.ks;
     return g;
+}
+
+// Robust loss of a residual block (one corner, s = r_u^2 + r_v^2): Ceres' HuberLoss, SoftLOneLoss, CauchyLoss
+// (loss_function.cc), same operations.  a: scale in pixels, b = a^2, c = 1 / b (all three computed on the host, as Ceres'
+// constructors do).  Every one of them has rho'' <= 0, so Ceres' Corrector takes its alpha = 0 branch: the residuals and the
+// Jacobian rows of the block are both scaled by sqrt(rho'), and no rank-one term appears.  The robust Gram-kernel
+// instantiations get these values as a kernel argument (wave-uniform: scalar registers).
+enum { kLossNone = 0, kLossHuber = 1, kLossSoftL1 = 2, kLossCauchy = 3 };
+struct LossArg { double a, b, c; int kind, pad; };
+// rho(s) and w = sqrt(rho'(s)), rho' clamped from below as Ceres clamps it (std::numeric_limits<double>::min())
+__device__ __forceinline__ void robust_rho(const LossArg &L, double s, double &rho, double &w)
+{
+    constexpr double kMin = 2.2250738585072014e-308;
+    double r1;
+    if (L.kind == kLossHuber) {
+        if (s > L.b) { const double r = sqrt(s); rho = 2.0 * L.a * r - L.b; r1 = fmax(kMin, L.a / r); }
+        else { rho = s; r1 = 1.0; }
+    } else if (L.kind == kLossSoftL1) {
+        const double sum = 1.0 + s * L.c, tmp = sqrt(sum);
+        rho = 2.0 * L.b * (tmp - 1.0); r1 = fmax(kMin, 1.0 / tmp);
+    } else {
+        const double sum = 1.0 + s * L.c, inv = 1.0 / sum;
+        rho = L.b * log(sum); r1 = fmax(kMin, inv);
+    }
+    w = sqrt(r1);
 }
 
 #include "tscm_eval_f32.h"

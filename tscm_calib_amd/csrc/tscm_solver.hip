@@ -17,6 +17,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <numeric>
@@ -92,31 +93,40 @@ struct tscm_comm {
     int rank = 0, world = 1, device = 0;
 };
 
-// the Gram kernels share one signature; k_eval_gram4 is instantiated per k-step count of a pass (tscm_eval_gram4.h: g4_plan)
-typedef void (*EvalKernel)(DevProblem, DevState, int);
-static EvalKernel g4_kernel(int ks, bool multi)
+// the Gram kernels k_eval_gram4 / k_eval_gram_f32 share one signature; both are instantiated per k-step count of a pass
+// (tscm_eval_gram4.h: g4_plan), without and with a robust loss (ROBUST: DESIGN 14)
+typedef void (*EvalKernel)(DevProblem, DevState, int, LossArg);
+template <bool ROBUST>
+static EvalKernel g4_kernel_of(int ks, bool multi)
 {
     static const EvalKernel single[kG4MaxKS] = {
-        k_eval_gram4<1, false>, k_eval_gram4<2, false>, k_eval_gram4<3, false>, k_eval_gram4<4, false>, k_eval_gram4<5, false>,
-        k_eval_gram4<6, false>, k_eval_gram4<7, false>, k_eval_gram4<8, false>, k_eval_gram4<9, false>, k_eval_gram4<10, false>,
-        k_eval_gram4<11, false>, k_eval_gram4<12, false>, k_eval_gram4<13, false>, k_eval_gram4<14, false> };
+        k_eval_gram4<1, false, ROBUST>, k_eval_gram4<2, false, ROBUST>, k_eval_gram4<3, false, ROBUST>, k_eval_gram4<4, false, ROBUST>,
+        k_eval_gram4<5, false, ROBUST>, k_eval_gram4<6, false, ROBUST>, k_eval_gram4<7, false, ROBUST>, k_eval_gram4<8, false, ROBUST>,
+        k_eval_gram4<9, false, ROBUST>, k_eval_gram4<10, false, ROBUST>, k_eval_gram4<11, false, ROBUST>, k_eval_gram4<12, false, ROBUST>,
+        k_eval_gram4<13, false, ROBUST>, k_eval_gram4<14, false, ROBUST> };
     // several passes: ceil(n / passes) >= 29 corners per pass, i.e. at least 8 k-steps
     static const EvalKernel passes[kG4MaxKS] = {
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram4<8, true>, k_eval_gram4<9, true>, k_eval_gram4<10, true>,
-        k_eval_gram4<11, true>, k_eval_gram4<12, true>, k_eval_gram4<13, true>, k_eval_gram4<14, true> };
+        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram4<8, true, ROBUST>, k_eval_gram4<9, true, ROBUST>,
+        k_eval_gram4<10, true, ROBUST>, k_eval_gram4<11, true, ROBUST>, k_eval_gram4<12, true, ROBUST>, k_eval_gram4<13, true, ROBUST>,
+        k_eval_gram4<14, true, ROBUST> };
     return (multi ? passes : single)[ks - 1];
 }
-static EvalKernel f32_kernel(int ks, bool multi)     // the fp32-Jacobian tier on the same pass plan
+static EvalKernel g4_kernel(int ks, bool multi, bool robust) { return robust ? g4_kernel_of<true>(ks, multi) : g4_kernel_of<false>(ks, multi); }
+template <bool ROBUST>
+static EvalKernel f32_kernel_of(int ks, bool multi)     // the fp32-Jacobian tier on the same pass plan
 {
     static const EvalKernel single[kG4MaxKS] = {
-        k_eval_gram_f32<1, false>, k_eval_gram_f32<2, false>, k_eval_gram_f32<3, false>, k_eval_gram_f32<4, false>, k_eval_gram_f32<5, false>,
-        k_eval_gram_f32<6, false>, k_eval_gram_f32<7, false>, k_eval_gram_f32<8, false>, k_eval_gram_f32<9, false>, k_eval_gram_f32<10, false>,
-        k_eval_gram_f32<11, false>, k_eval_gram_f32<12, false>, k_eval_gram_f32<13, false>, k_eval_gram_f32<14, false> };
+        k_eval_gram_f32<1, false, ROBUST>, k_eval_gram_f32<2, false, ROBUST>, k_eval_gram_f32<3, false, ROBUST>, k_eval_gram_f32<4, false, ROBUST>,
+        k_eval_gram_f32<5, false, ROBUST>, k_eval_gram_f32<6, false, ROBUST>, k_eval_gram_f32<7, false, ROBUST>, k_eval_gram_f32<8, false, ROBUST>,
+        k_eval_gram_f32<9, false, ROBUST>, k_eval_gram_f32<10, false, ROBUST>, k_eval_gram_f32<11, false, ROBUST>, k_eval_gram_f32<12, false, ROBUST>,
+        k_eval_gram_f32<13, false, ROBUST>, k_eval_gram_f32<14, false, ROBUST> };
     static const EvalKernel passes[kG4MaxKS] = {
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram_f32<8, true>, k_eval_gram_f32<9, true>, k_eval_gram_f32<10, true>,
-        k_eval_gram_f32<11, true>, k_eval_gram_f32<12, true>, k_eval_gram_f32<13, true>, k_eval_gram_f32<14, true> };
+        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram_f32<8, true, ROBUST>, k_eval_gram_f32<9, true, ROBUST>,
+        k_eval_gram_f32<10, true, ROBUST>, k_eval_gram_f32<11, true, ROBUST>, k_eval_gram_f32<12, true, ROBUST>, k_eval_gram_f32<13, true, ROBUST>,
+        k_eval_gram_f32<14, true, ROBUST> };
     return (multi ? passes : single)[ks - 1];
 }
+static EvalKernel f32_kernel(int ks, bool multi, bool robust) { return robust ? f32_kernel_of<true>(ks, multi) : f32_kernel_of<false>(ks, multi); }
 
 struct tscm_solver {
     int device = 0;
@@ -176,6 +186,9 @@ struct tscm_solver {
     bool gram16 = false;                // this solve: TSCM_EXEC_GRAM_16X16
     size_t lds_eval4 = 0;               // dynamic LDS of k_eval_gram4
     EvalKernel eval4 = nullptr, eval32 = nullptr;   // ... and its instantiation for this problem's board (g4_kernel), the fp32-Jacobian tier's (f32_kernel)
+    EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
+    LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs eval4 / eval32
+    double *d_view_sq = nullptr;        // [2 V] k_reproj_error's output for the RMSE of a robust solve (allocated by the first one)
     // dominant-kernel timing
     int timing = 0;                     // 0 = off, n = bracket every n-th launch of the dominant kernel (and every n-th exchange) with HIP events
     unsigned ev_count[3] = { 0, 0, 0 }; // occurrences so far, by kind: 0 dominant kernel, 1 exchange of T, 2 exchange of H_stage
@@ -260,6 +273,27 @@ static int validate(const tscm_problem *p)
         if (p->view_count[v] < 0 || p->view_count[v] > p->n_points) return fail(TSCM_E_INVALID, "view_count outside [0, n_points]");
         if (p->view_offset[v] < 0) return fail(TSCM_E_INVALID, "negative view_offset");
     }
+    return 0;
+}
+
+// a loss of the C ABI -> the robust kernels' argument (Ceres' constructors: b = a^2, c = 1 / b); checked before any device is touched
+static int make_loss(int kind, double scale, LossArg &L)
+{
+    L = LossArg{};
+    if (kind < TSCM_LOSS_NONE || kind > TSCM_LOSS_CAUCHY) return fail(TSCM_E_INVALID, "unknown loss kind");
+    if (kind == TSCM_LOSS_NONE) return 0;
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(TSCM_E_INVALID, "the scale of a loss must be finite and > 0");
+    L.kind = kind; L.a = scale; L.b = scale * scale; L.c = 1.0 / L.b;
+    return 0;
+}
+static bool same_loss(const LossArg &x, const LossArg &y) { return x.kind == y.kind && (x.kind == TSCM_LOSS_NONE || x.a == y.a); }
+
+extern "C" int tscm_solver_set_loss(tscm_solver *s, int kind, double scale)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    s->loss = L;
     return 0;
 }
 
@@ -429,13 +463,14 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     if (4 * lds_eval_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval_gram<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * lds_eval_bytes)));
     // the default Gram kernel: k_eval_gram4 instantiated for this board's pass plan (KS k-steps per pass, ceil(n / 56) passes per view)
     const G4Plan g4 = g4_plan(p->n_points);
-    const EvalKernel eval4 = g4_kernel(g4.ks, g4.passes > 1);
+    const EvalKernel eval4 = g4_kernel(g4.ks, g4.passes > 1, false), eval4r = g4_kernel(g4.ks, g4.passes > 1, true);
     size_t lds_eval4 = 4 * sizeof(double) * (size_t)eval_gram4_lds_doubles(p->n_points, g4.ks);
 #ifdef TSCM_G4_LDS_PAD      // occupancy experiments (tools/wave_timeline.py): fewer workgroups per CU, same kernel
     lds_eval4 += TSCM_G4_LDS_PAD;
 #endif
     if (lds_eval4 > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board with too many corners for the Gram kernel's LDS (more than about 2,000)");
-    if (lds_eval4 > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(eval4), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
+    if (lds_eval4 > 64 * 1024)
+        for (EvalKernel k : { eval4, eval4r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
     int wgs_per_cu = 0;         // resident workgroups per CU (register- and LDS-limited)
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, reinterpret_cast<const void *>(eval4), 256, lds_eval4));
 #ifdef TSCM_EVAL_WAVES          // occupancy experiments: chunk tables for this many waves per SIMD
@@ -748,8 +783,10 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
 
     s->lds_eval = 4 * lds_eval_bytes;
     s->lds_eval32 = sizeof(double) * (size_t)eval_f32_lds_doubles(p->n_points, g4.ks);
-    s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval32 = f32_kernel(g4.ks, g4.passes > 1);
-    if (s->lds_eval32 > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(s->eval32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
+    s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval4r = eval4r;
+    s->eval32 = f32_kernel(g4.ks, g4.passes > 1, false); s->eval32r = f32_kernel(g4.ks, g4.passes > 1, true);
+    if (s->lds_eval32 > 64 * 1024)
+        for (EvalKernel k : { s->eval32, s->eval32r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
     // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory
     s->solve_variant = C <= 4 ? 0 : C <= kMaxCamLds ? 1 : 3;
     if (s->solve_variant == 0) {
@@ -919,10 +956,11 @@ static int timed_begin(tscm_solver *s, int kind, hipStream_t stream, hipEvent_t 
 // the events take the start and end time stamps of this kernel's packet on the solver's stream) -- two hipEventRecord
 // around it are two more packets with a drain each, 8.5 us per timed launch at config 4 and 3 % of the driver's
 // 20-step run
-static void launch_eval_kernel(EvalKernel kernel, dim3 grid, size_t lds, tscm_solver *s, hipEvent_t e0, hipEvent_t e1, int cand)
+template <typename K, typename... A>
+static void launch_eval_kernel(K kernel, dim3 grid, size_t lds, tscm_solver *s, hipEvent_t e0, hipEvent_t e1, int cand, A... extra)
 {
-    if (e0) hipExtLaunchKernelGGL(kernel, grid, dim3(256), (std::uint32_t)lds, s->stream, e0, e1, 0, s->P, s->S, cand);
-    else hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s->stream, s->P, s->S, cand);
+    if (e0) hipExtLaunchKernelGGL(kernel, grid, dim3(256), (std::uint32_t)lds, s->stream, e0, e1, 0, s->P, s->S, cand, extra...);
+    else hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s->stream, s->P, s->S, cand, extra...);
 }
 
 static int launch_eval(tscm_solver *s, int cand)
@@ -933,8 +971,10 @@ static int launch_eval(tscm_solver *s, int cand)
     if (int rc = timed_pair(s, 0, &e0, &e1)) return rc;
     const dim3 grid(P.n_chunks / 4);
     // 9x6 .. 7x8 boards (53..56 corners per pass) get the variant with a compile-time LDS pitch
-    if (s->f32_jacobian) launch_eval_kernel(s->eval32, grid, s->lds_eval32, s, e0, e1, cand);
-    else if (!s->gram16) launch_eval_kernel(s->eval4, grid, s->lds_eval4, s, e0, e1, cand);       // every board size (round 6)
+    // (a loss: the ROBUST instantiation; the 16x16 kernel has none -- refused before anything is launched)
+    const bool robust = s->loss.kind != TSCM_LOSS_NONE;
+    if (s->f32_jacobian) launch_eval_kernel(robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
+    else if (!s->gram16) launch_eval_kernel(robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand, s->loss);     // every board size (round 6)
     else if (P.rp == 58) launch_eval_kernel(k_eval_gram<58>, grid, s->lds_eval, s, e0, e1, cand);
     else launch_eval_kernel(k_eval_gram<0>, grid, s->lds_eval, s, e0, e1, cand);
     return 0;
@@ -1305,6 +1345,52 @@ static int run_lm(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, in
     return rc;
 }
 
+// device buffer freed on every exit path of the small entry points (and of robust_rmse)
+struct DevBuf {
+    double *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(double)); }
+};
+
+// sum of the squared pixel errors of this solver's corners at the accepted point (buffer 0): k_reproj_error, summed over the
+// views in device order -- what tscm_reprojection_error does on an unsharded solver of the same problem
+static int accepted_sq(tscm_solver *s, double &sq)
+{
+    sq = 0.0;
+    if (!s->V) return 0;
+    if (!s->d_view_sq) if (int rc = dev_alloc(s, &s->d_view_sq, 2 * (size_t)s->V)) return rc;
+    hipLaunchKernelGGL(k_reproj_error, dim3(s->V), dim3(64), 0, s->stream, s->P, s->S.cam_rt[0], s->S.intr[0], s->S.board_rt[0], s->d_view_sq, s->d_view_sq + s->V);
+    std::vector<double> q(s->V);
+    HIP_TRY(hipMemcpyAsync(q.data(), s->d_view_sq + s->V, sizeof(double) * s->V, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipGetLastError());
+    for (int v = 0; v < s->V; ++v) sq += q[v];
+    return 0;
+}
+// summary.rmse of a robust solve: one k_reproj_error launch per solver; the shards' sums are added (a local group) or
+// all-reduced (a communicator across processes), over N of the whole job
+static int robust_rmse(LmRun &run, tscm_summary *sums)
+{
+    double sq = 0.0;
+    for (tscm_solver *s : run.m) {
+        double q = 0.0;
+        if (int rc = accepted_sq(s, q)) return rc;
+        sq += q;
+    }
+    tscm_solver *s0 = run.m[0];
+    if (run.m.size() == 1 && s0->comm && s0->world > 1) {
+        DevBuf d;
+        HIP_TRY(d.alloc(1));
+        HIP_TRY(hipMemcpyAsync(d.p, &sq, sizeof(double), hipMemcpyHostToDevice, s0->stream));
+        if (int rc = comm_allreduce(s0->comm, d.p, 1, s0->stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(&sq, d.p, sizeof(double), hipMemcpyDeviceToHost, s0->stream));
+        HIP_TRY(hipStreamSynchronize(s0->stream));
+        if (int rc = comm_check(s0->comm)) return rc;
+    }
+    for (size_t r = 0; r < run.m.size(); ++r) sums[r].rmse = run.m[r]->N_total ? std::sqrt(sq / (double)run.m[r]->N_total) : 0.0;
+    return 0;
+}
+
 static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, int reset, bool rerun, bool *late_handoff)
 {
     tscm_solver *s0 = run.m[0];
@@ -1313,6 +1399,8 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     if (int rc = read_options(opt_in, s0->mono, opt)) return rc;
     if (opt.max_num_iterations < 0 || opt.max_num_iterations > TSCM_MAX_ITERATIONS) return fail(TSCM_E_INVALID, "max_num_iterations must be in [0, 255]");
     if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
+    for (tscm_solver *s : run.m) if (!same_loss(s->loss, s0->loss)) return fail(TSCM_E_INVALID, "the solvers of a group carry different losses (tscm_solver_set_loss)");
+    if (s0->loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
     HIP_TRY(hipSetDevice(s0->device));
     LmRunGuard guard{ run };
     for (tscm_solver *s : run.m) {
@@ -1451,6 +1539,8 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         sum->seconds_total = t1 - t0;                                     // wall time of the call
         sum->rmse = s->N_total ? std::sqrt(2.0 * h->x_cost / (double)s->N_total) : 0.0;     // cost and N of the WHOLE job
     }
+    // with a loss the cost is sum rho / 2, not the squared pixel error: the RMSE is measured at the accepted point instead
+    if (s0->loss.kind != TSCM_LOSS_NONE) return robust_rmse(run, sums);
     return 0;
 }
 
@@ -1536,13 +1626,14 @@ extern "C" int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_s
     return 0;
 }
 
-static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum)
+static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{})
 {
     tscm_solver *s = nullptr;
     int dev = 0;
     (void)hipGetDevice(&dev);
     int rc = tscm_solver_create(p, dev, &s);
     if (rc) return rc;
+    s->loss = loss;
     rc = tscm_solver_solve(s, opt, sum);
     tscm_solver_destroy(s);
     return rc;
@@ -1560,23 +1651,35 @@ extern "C" int tscm_solve_mono(const tscm_problem *p, const tscm_options *opt, t
     return solve_once(p, opt, sum);
 }
 
+extern "C" int tscm_solve_robust(const tscm_problem *p, const tscm_options *opt, int kind, double scale, tscm_summary *sum)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
+    if (L.kind != TSCM_LOSS_NONE && opt && opt->struct_size >= sizeof(tscm_options) && (opt->exec_flags & TSCM_EXEC_GRAM_16X16))
+        return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
+    return solve_once(p, opt, sum, L);
+}
+
 // The candidate of a solve's first trust-region step: the solve itself, stopped after one iteration (termination
 // tolerances zeroed, so nothing ends it before the step is taken).  The first iteration writes its candidate into buffer 1
 // (ctrl->cur = 0 at the start); k_end_solve / k_finish_solve copy it into buffer 0 only if the step was accepted and never
 // write buffer 1, so buffer 1 holds the candidate whether the step was accepted or not
-extern "C" int tscm_eval_step_ex(const tscm_problem *p, int device, const tscm_options *opt_in, double *cam_rt, double *intr,
-                                 double *board_rt, int *valid, tscm_summary *summary)
+static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *cam_rt, double *intr,
+                     double *board_rt, int *valid, tscm_summary *summary)
 {
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
     if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
     if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
+    if (loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
     opt.max_num_iterations = 1;
     opt.function_tolerance = opt.gradient_tolerance = opt.parameter_tolerance = 0.0;
     tscm_solver *s = nullptr;
     if ((rc = tscm_solver_create(p, device, &s))) return rc;
     std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    s->loss = loss;
     if ((rc = tscm_solver_upload_params(s, p->cam_rt, p->intr, p->board_rt))) return rc;
     tscm_summary sum;
     if ((rc = tscm_solver_solve_resident(s, &opt, &sum, 1))) return rc;
@@ -1587,6 +1690,20 @@ extern "C" int tscm_eval_step_ex(const tscm_problem *p, int device, const tscm_o
     *valid = sum.num_iterations > 1 && sum.iterations[1].step_is_valid ? 1 : 0;
     if (summary) *summary = sum;
     return 0;
+}
+
+extern "C" int tscm_eval_step_ex(const tscm_problem *p, int device, const tscm_options *opt, double *cam_rt, double *intr,
+                                 double *board_rt, int *valid, tscm_summary *summary)
+{
+    return eval_step(p, device, opt, LossArg{}, cam_rt, intr, board_rt, valid, summary);
+}
+
+extern "C" int tscm_eval_step_robust(const tscm_problem *p, int device, const tscm_options *opt, int kind, double scale, double *cam_rt,
+                                     double *intr, double *board_rt, int *valid, tscm_summary *summary)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1661,16 +1778,18 @@ extern "C" int tscm_eval_normal_equations(const tscm_problem *p, int device, dou
 // the Gram kernel is the one a solve with these options runs: jacobian_fp32 -> k_eval_gram_f32, TSCM_EXEC_GRAM_16X16 ->
 // k_eval_gram, k_eval_gram4 otherwise (the other flags do not touch the evaluation).  Every kernel writes the same fp64
 // record layout, so the extraction below is shared
-extern "C" int tscm_eval_normal_equations_ex(const tscm_problem *p, int device, const tscm_options *opt_in, double *board_gram,
-                                             double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+static int eval_normal_equations(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *board_gram,
+                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
 {
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
     if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
+    if (loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
     tscm_solver *s = nullptr;
     if ((rc = tscm_solver_create(p, device, &s))) return rc;
     std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    s->loss = loss;
     s->f32_jacobian = opt.jacobian_fp32 != 0;
     s->gram16 = (opt.exec_flags & TSCM_EXEC_GRAM_16X16) != 0;
     if ((rc = prepare_eval(s, s->f32_jacobian ? 1 : 0))) return rc;
@@ -1719,12 +1838,21 @@ extern "C" int tscm_eval_normal_equations_ex(const tscm_problem *p, int device, 
     return 0;
 }
 
-// device buffer freed on every exit path of the small entry points below
-struct DevBuf {
-    double *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(double)); }
-};
+extern "C" int tscm_eval_normal_equations_ex(const tscm_problem *p, int device, const tscm_options *opt, double *board_gram,
+                                             double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+{
+    return eval_normal_equations(p, device, opt, LossArg{}, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+}
+
+extern "C" int tscm_eval_normal_equations_robust(const tscm_problem *p, int device, const tscm_options *opt, int kind, double scale,
+                                                 double *board_gram, double *board_grad, double *view_cross, double *cam_gram,
+                                                 double *cam_grad, double *cost)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    return eval_normal_equations(p, device, opt, L, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+}
+
 
 extern "C" int tscm_project_points(const double *intr9, const double *points, int n, int device, double *pixels)
 {

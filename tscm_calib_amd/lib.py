@@ -27,6 +27,9 @@ EXEC_SEPARATE_CONTROL = 16
 EXEC_DENSE_REDUCED_ORDER = 32
 EXEC_GRAPH_REDUCED_ORDER = 64
 EXEC_SEPARATE_STATS = 128
+# robust losses (tscm.h: TSCM_LOSS_*), by the names the Python layer takes
+LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2, 3
+LOSS_KINDS = {None: LOSS_NONE, "none": LOSS_NONE, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY}
 
 E_NAMES = {0: "TSCM_OK", -1: "TSCM_E_INVALID", -2: "TSCM_E_NO_DEVICE", -3: "TSCM_E_HIP",
            -4: "TSCM_E_RCCL", -5: "TSCM_E_UNSUPPORTED", -6: "TSCM_E_NOMEM", -7: "TSCM_E_PEER"}
@@ -124,6 +127,7 @@ EXPORTS = [
     "tscm_yaml_read", "tscm_build_maps", "tscm_estimate_focal", "tscm_poses_from_r1r2t",
     "tscm_estimate_extrinsic", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
+    "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
 ]
 
 
@@ -184,6 +188,10 @@ def lib():
     L.tscm_eval_normal_equations.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp, dp, dp, dp]
     L.tscm_eval_normal_equations_ex.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, dp, dp, dp, dp, dp]
     L.tscm_eval_step_ex.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, dp, dp, ip, C.POINTER(CSummary)]
+    L.tscm_solver_set_loss.argtypes = [vp, C.c_int, C.c_double]
+    L.tscm_solve_robust.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), C.c_int, C.c_double, C.POINTER(CSummary)]
+    L.tscm_eval_normal_equations_robust.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), C.c_int, C.c_double, dp, dp, dp, dp, dp, dp]
+    L.tscm_eval_step_robust.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]
@@ -208,6 +216,19 @@ def lib():
     L.tscm_yaml_read.argtypes = [C.c_char_p, C.c_int, ip, dp, dp]
     _lib = L
     return L
+
+
+def loss_args(loss) -> tuple:
+    """(kind, scale) of the C ABI from None, a kind name, or a (kind name, scale in pixels) pair."""
+    if loss is None:
+        return LOSS_NONE, 0.0
+    if isinstance(loss, str):
+        kind, scale = loss, 1.0
+    else:
+        kind, scale = loss
+    if kind not in LOSS_KINDS:
+        raise ValueError(f"unknown loss {kind!r}: one of 'huber', 'soft_l1', 'cauchy' or None")
+    return LOSS_KINDS[kind], float(scale)
 
 
 def check(rc: int) -> None:
