@@ -573,6 +573,12 @@ int tscm_detect_corners(const unsigned char *gray, int width, int height, int st
 int tscm_detect_corners_batch(const unsigned char *const *images, int n_images, int width, int height, int stride, int sigma, double min_score,
                               int device, tscm_corner_candidates *out);
 void tscm_corner_candidates_free(tscm_corner_candidates *c);
+/* The image planes of tscm_detect_corners_batch, from the same launches: ig = the normalised and blurred image
+ * (findCorner.cpp:30-34, :106), metric = cxy + c45 (the input of the suppression) and ixy = Ixy (the input of the
+ * sub-pixel fit), each [n_images][height][width] fp64; any of the three may be NULL.  Arguments are checked as in
+ * tscm_detect_corners_batch.  For parity tests. */
+int tscm_corner_planes_batch(const unsigned char *const *images, int n_images, int width, int height, int stride, int sigma, int device,
+                             double *ig, double *metric, double *ixy);
 
 /* ------------------------------------------------------------------ chessboard structure (second stage)
  * tscm_chessboards_from_corners = chessboardsFromCorners (DetectCorner/chessboard.cpp:3-103): 3x3 seeds around every

@@ -401,6 +401,22 @@ def detect_corners(gray, sigma: int = 4, cap: int = 8192, planes: bool = False) 
     return out
 
 
+def corner_planes(gray, sigma: int = 4) -> dict:
+    """findCorner.cpp:30-34 + :103-142: the normalised and blurred image ig, metric = cxy + c45 and ixy, each (H, W)."""
+    g = np.asarray(gray)
+    if g.ndim != 2 or g.dtype != np.uint8 or g.strides[1] != 1 or g.strides[0] < g.shape[1]:
+        g = np.ascontiguousarray(g, dtype=np.uint8)
+    h, w = g.shape
+    ig, metric, ixy = np.empty((h, w)), np.empty((h, w)), np.empty((h, w))
+    f = lib().orc_corner_planes
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+    rc = f(g.ctypes.data, w, h, g.strides[0], sigma, ig.ctypes.data, metric.ctypes.data, ixy.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"orc_corner_planes failed ({rc})")
+    return dict(ig=ig, metric=metric, ixy=ixy)
+
+
 def chessboards_from_corners(x, y, v1, v2, max_boards: int = 16, max_cells: int = 4096) -> list:
     """DetectCorner/chessboard.cpp:3-103 -> list of index matrices (rows x cols, cols >= rows)."""
     x, y, v1, v2 = _f(x), _f(y), _f(v1), _f(v2)

@@ -224,6 +224,7 @@ void orc_corner_gradients(const unsigned char *gray, int w, int h, int stride, d
 void orc_corner_normalise(const unsigned char *gray, int w, int h, int stride, double *img);
 void orc_gaussian_kernel(int sigma, double *k);
 int orc_corner_metric(const double *I, int w, int h, int sigma, double *metric, double *Ixy);
+int orc_corner_planes(const unsigned char *gray, int width, int height, int stride, int sigma, double *ig, double *metric, double *ixy);
 int orc_corner_nms(const double *img, int width, int height, int n, double tau, int margin, int cap, double *px, double *py);
 void orc_corner_orientation(const double *angle, const double *weight, int width, int height, int cu, int cv, int r, double *v);
 double orc_corner_correlation_score(const double *img, const double *weight, int width, int u, int v, int r, const double *vv);

@@ -85,8 +85,9 @@ void orc_gaussian_kernel(int sigma, double *k)        /* ksize = 7 sigma + 1 coe
     for (int i = 0; i < n; ++i) k[i] *= sum;
 }
 
-/* :103-142 -- metric = cxy + c45 (the image the non-maximum suppression runs on) and Ixy (sub-pixel fit) */
-int orc_corner_metric(const double *I, int w, int h, int sigma, double *metric, double *Ixy)
+/* :103-142 -- metric = cxy + c45 (the image the non-maximum suppression runs on) and Ixy (sub-pixel fit);
+ * Ig_out (may be NULL) receives the blurred image */
+static int corner_metric(const double *I, int w, int h, int sigma, double *metric, double *Ixy, double *Ig_out)
 {
     const int n = 7 * sigma + 1, half = n / 2;
     const size_t N = (size_t)w * h;
@@ -133,8 +134,31 @@ int orc_corner_metric(const double *I, int w, int h, int sigma, double *metric, 
             metric[o] = cxy + c45;
             Ixy[o] = ixy;
         }
+    if (Ig_out) memcpy(Ig_out, Ig, sizeof(double) * N);
     free(k); free(tmp); free(Ig); free(Ix); free(Iy); free(I45);
     return 0;
+}
+
+int orc_corner_metric(const double *I, int w, int h, int sigma, double *metric, double *Ixy)
+{
+    return corner_metric(I, w, h, sigma, metric, Ixy, NULL);
+}
+
+/* :30-34 + :103-142 for one image: the normalised and blurred image Ig, metric = cxy + c45 and Ixy, each [h][w];
+ * any of the three may be NULL.  Returns 0, -1 (out of memory) or -2 (sigma refused). */
+int orc_corner_planes(const unsigned char *gray, int width, int height, int stride, int sigma, double *ig, double *metric_out, double *ixy_out)
+{
+    const size_t N = (size_t)width * height;
+    double *img = (double *)malloc(sizeof(double) * N), *metric = (double *)malloc(sizeof(double) * N), *Ixy = (double *)malloc(sizeof(double) * N);
+    int rc = -1;
+    if (img && metric && Ixy) {
+        orc_corner_normalise(gray, width, height, stride, img);
+        rc = corner_metric(img, width, height, sigma, metric, Ixy, ig);
+        if (rc == 0 && metric_out) memcpy(metric_out, metric, sizeof(double) * N);
+        if (rc == 0 && ixy_out) memcpy(ixy_out, Ixy, sizeof(double) * N);
+    }
+    free(img); free(metric); free(Ixy);
+    return rc;
 }
 
 /* :144-193 -- returns the number of maxima, at most cap are stored (x = column, y = row) */

@@ -42,22 +42,37 @@ def _unpack(out) -> dict:
                 score=arr(out.score, 1)[:, 0], sub=arr(out.sub, 2), seconds=out.seconds)
 
 
-def detect_corners_batch(images, sigma: int = 4, min_score: float = 0.01, device: int = 0) -> list:
+def _batch(images, stride, what: str):
+    """The images of a batch call as (arrays kept alive, pointer array, width, height, row stride).  stride None: each
+    image is made contiguous; otherwise every image must be a view with that row stride (e.g. buf[:, :w] of an
+    (H, stride) buffer), whose padding bytes are passed through untouched."""
+    if stride is None:
+        imgs = [np.ascontiguousarray(g) for g in images]
+    else:
+        imgs = [np.asarray(g) for g in images]
+    if not imgs:
+        return [], None, 0, 0, 0
+    h, w = imgs[0].shape[:2]
+    if any(g.ndim != 2 or g.dtype != np.uint8 or g.shape != (h, w) for g in imgs):
+        raise ValueError(f"{what} expects 2-D uint8 images of one size")
+    s = w if stride is None else int(stride)
+    if stride is not None and (s < w or any(g.strides != (s, 1) for g in imgs)):
+        raise ValueError(f"{what}: every image must have row stride {s} >= width {w} and contiguous rows")
+    return imgs, (C.c_void_p * len(imgs))(*[g.ctypes.data for g in imgs]), w, h, s
+
+
+def detect_corners_batch(images, sigma: int = 4, min_score: float = 0.01, device: int = 0, stride=None) -> list:
     """tscm_detect_corners_batch: a list of (H, W) uint8 images of one size -> list of candidate dicts, one pass of the
-    kernels for all of them."""
-    imgs = [np.ascontiguousarray(g) for g in images]
+    kernels for all of them.  stride: see corner_planes."""
+    imgs, ptrs, w, h, s = _batch(images, stride, "detect_corners_batch")
     if not imgs:
         return []
-    h, w = imgs[0].shape
-    if any(g.ndim != 2 or g.dtype != np.uint8 or g.shape != (h, w) for g in imgs):
-        raise ValueError("detect_corners_batch expects 2-D uint8 images of one size")
     n = len(imgs)
-    ptrs = (C.c_void_p * n)(*[g.ctypes.data for g in imgs])
     outs = (_l.CCornerCandidates * n)()
     f = _l.lib().tscm_detect_corners_batch
     f.restype = C.c_int
     f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p]
-    _l.check(f(ptrs, n, w, h, w, int(sigma), float(min_score), int(device), outs))
+    _l.check(f(ptrs, n, w, h, s, int(sigma), float(min_score), int(device), outs))
     fr = _l.lib().tscm_corner_candidates_free
     fr.restype = None
     fr.argtypes = [C.POINTER(_l.CCornerCandidates)]
@@ -66,6 +81,26 @@ def detect_corners_batch(images, sigma: int = 4, min_score: float = 0.01, device
     finally:
         for i in range(n):
             fr(C.byref(outs[i]))
+
+
+def corner_planes(images, sigma: int = 4, device: int = 0, stride=None, planes=("ig", "metric", "ixy")) -> dict:
+    """tscm_corner_planes_batch: the planes tscm_detect_corners_batch computes for a list of (H, W) uint8 images of one
+    size (or one image) -- ig (normalised and blurred image), metric (cxy + c45) and ixy -- each (n, H, W) fp64, for the
+    names in `planes`.  stride None: the images are made contiguous; otherwise every image must be a view with that row
+    stride (e.g. buf[:, :w] of an (H, stride) buffer) and the batch is passed with it."""
+    if isinstance(images, np.ndarray) and images.ndim == 2:
+        images = [images]
+    imgs, ptrs, w, h, s = _batch(images, stride, "corner_planes")
+    n = len(imgs)
+    out = {k: np.empty((n, h, w)) for k in planes}
+    if not imgs:
+        return out
+    f = _l.lib().tscm_corner_planes_batch
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+    p = [out[k].ctypes.data if k in out else None for k in ("ig", "metric", "ixy")]
+    _l.check(f(ptrs, n, w, h, s, int(sigma), int(device), *p))
+    return out
 
 
 def chessboards_from_corners(x, y, v1, v2) -> list:

@@ -646,6 +646,114 @@ struct ArenaCursor {
     }
 };
 
+// Argument checks shared by the entry points that take a batch of images
+int check_batch(const unsigned char *const *images, int n_images, int width, int height, int stride, int sigma, int device)
+{
+    for (int q = 0; q < n_images; ++q) if (!images[q]) return tscm_set_error(TSCM_E_INVALID, "NULL image");
+    if (width < 1 || height < 1 || stride < width) return tscm_set_error(TSCM_E_INVALID, "bad image description");
+    if (n_images > 65535) return tscm_set_error(TSCM_E_UNSUPPORTED, "more than 65535 images per batch");
+    if (width > 32767 || height > 32767) return tscm_set_error(TSCM_E_UNSUPPORTED, "images beyond 32767 pixels per side");
+    const int ntap = 7 * sigma + 1;
+    if (sigma < 1 || ntap % 2 == 0 || ntap > 64) return tscm_set_error(TSCM_E_UNSUPPORTED, "sigma must be even and at most 8 (cv::GaussianBlur needs an odd 7 sigma + 1; the reference uses 4)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (the corner detector has no CPU fallback)");
+    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
+    CRN_TRY(hipSetDevice(device));
+    if (device >= 16) return tscm_set_error(TSCM_E_UNSUPPORTED, "device index beyond 15");
+    return 0;
+}
+
+// The device working set of one batch, carved out of the device's arena
+struct CornerBuffers {
+    unsigned char *gray;
+    double *tmp, *Ig, *metric, *Ixy, *taps, *lut, *v, *score, *sub;
+    int *mm, *cell, *cand, *count;
+    DescribeTables *tab;
+    size_t N;
+    int ncx, ncy, ncell;
+};
+
+// Everything of a batch up to and including the corner metric: the arena, the uploads and the launches
+// extremes -> row pass -> column pass -> k_corner_metric, with the kernel choice by tap count and width.  Both
+// tscm_detect_corners_batch and tscm_corner_planes_batch run it, so the planes the latter returns are the ones the
+// suppression reads.  The caller holds arena.mu and has checked the arguments; tab (may be NULL) is uploaded with the
+// taps, e0 (may be NULL) is recorded in front of the first kernel.
+int corner_front(const unsigned char *const *images, int n_images, int width, int height, int stride, int sigma, Arena &arena,
+                 const DescribeTables *tab, hipEvent_t e0, CornerBuffers &d)
+{
+    const int ntap = 7 * sigma + 1;
+    std::vector<double> taps(ntap);
+    {
+        const double scale2x = -0.5 / ((double)sigma * sigma);
+        double sum = 0;
+        for (int i = 0; i < ntap; ++i) { const double x = i - (ntap - 1) * 0.5; taps[i] = std::exp(scale2x * x * x); sum += taps[i]; }
+        sum = 1. / sum;
+        for (int i = 0; i < ntap; ++i) taps[i] *= sum;
+    }
+
+    // ---- device buffers --------------------------------------------------------------------------------------------
+    const size_t N = (size_t)width * height;
+    constexpr int n = kNmsN, margin = kNmsMargin;
+    const int span_x = width - 2 * (n + margin), span_y = height - 2 * (n + margin);
+    const int ncx = span_x > 0 ? (span_x + n) / (n + 1) : 0, ncy = span_y > 0 ? (span_y + n) / (n + 1) : 0;
+    const int ncell = ncx * ncy;
+    const size_t B = (size_t)n_images;
+    const size_t cells_n = (size_t)(ncell > 0 ? ncell : 1) * B;
+    const size_t gbytes = (size_t)stride * height;
+    const size_t need = 256 * 26 + B * gbytes + 4 * B * N * sizeof(double) + 64 * sizeof(double) + B * 256 * sizeof(double) + B * kMmSlots * kMmStride * sizeof(int)
+                      + 2 * cells_n * sizeof(int) + B * sizeof(int) + sizeof(DescribeTables) + 7 * cells_n * sizeof(double);
+    if (arena.bytes < need) {
+        if (arena.base) { (void)hipFree(arena.base); arena.base = nullptr; arena.bytes = 0; }
+        CRN_TRY(hipMalloc(&arena.base, need));
+        arena.bytes = need;
+    }
+    ArenaCursor cur = { static_cast<char *>(arena.base), arena.bytes };
+    d.gray = cur.take<unsigned char>(B * gbytes);
+    d.tmp = cur.take<double>(B * N); d.Ig = cur.take<double>(B * N); d.metric = cur.take<double>(B * N); d.Ixy = cur.take<double>(B * N);
+    d.taps = cur.take<double>(64); d.lut = cur.take<double>(B * 256);
+    d.v = cur.take<double>(4 * cells_n); d.score = cur.take<double>(cells_n); d.sub = cur.take<double>(2 * cells_n);
+    d.mm = cur.take<int>(B * kMmSlots * kMmStride); d.cell = cur.take<int>(cells_n); d.cand = cur.take<int>(cells_n); d.count = cur.take<int>(B);
+    d.tab = cur.take<DescribeTables>(1);
+    d.N = N; d.ncx = ncx; d.ncy = ncy; d.ncell = ncell;
+    if (!d.tab || !d.count || !d.sub) return tscm_set_error(TSCM_E_HIP, "internal error: arena too small");
+    // a strided view (cv::Mat ROI, numpy column slice) only guarantees (height - 1) * stride + width bytes behind its pointer
+    const size_t host_bytes = (size_t)(height - 1) * (size_t)stride + (size_t)width;
+    for (size_t q = 0; q < B; ++q) CRN_TRY(hipMemcpy(d.gray + q * gbytes, images[q], std::min(gbytes, host_bytes), hipMemcpyHostToDevice));
+    CRN_TRY(hipMemcpy(d.taps, taps.data(), sizeof(double) * ntap, hipMemcpyHostToDevice));
+    if (tab) CRN_TRY(hipMemcpy(d.tab, tab, sizeof(DescribeTables), hipMemcpyHostToDevice));
+    {
+        std::vector<int> mm0(B * kMmSlots * kMmStride, 0);
+        for (size_t q = 0; q < B * kMmSlots; ++q) { mm0[q * kMmStride] = 255; mm0[q * kMmStride + 1] = 0; }
+        CRN_TRY(hipMemcpy(d.mm, mm0.data(), sizeof(int) * mm0.size(), hipMemcpyHostToDevice));
+    }
+    CRN_TRY(hipMemset(d.count, 0, sizeof(int) * B));
+
+    if (e0) CRN_TRY(hipEventRecord(e0, nullptr));
+    const dim3 grid2((width + 255) / 256, height, n_images);
+    if (stride == width)
+        hipLaunchKernelGGL(k_grey_extremes_flat, dim3((unsigned)((gbytes + 16383) / 16384), n_images), dim3(256), 0, nullptr, d.gray, gbytes, d.mm);
+    else
+        hipLaunchKernelGGL(k_grey_extremes, dim3((width + 4095) / 4096, height, n_images), dim3(256), 0, nullptr, d.gray, width, height, stride, d.mm);
+    if (ntap == 29) {
+        hipLaunchKernelGGL(k_norm_lut, dim3(n_images), dim3(256), 0, nullptr, d.mm, d.lut);
+        const int rows_y = (height + kRowsPerBlock - 1) / kRowsPerBlock;
+        if (width > 1024 && width <= 1280)       // one block per row at the reference's image width
+            hipLaunchKernelGGL((k_gauss_rows_n<29, 5>), dim3(1, rows_y, n_images), dim3(256), 0, nullptr, d.gray, width, height, stride, d.lut, d.taps, d.tmp, N);
+        else
+            hipLaunchKernelGGL((k_gauss_rows_n<29, 4>), dim3((width + 1023) / 1024, rows_y, n_images), dim3(256), 0, nullptr, d.gray, width, height, stride, d.lut,
+                               d.taps, d.tmp, N);
+    } else
+        hipLaunchKernelGGL(k_gauss_rows, grid2, dim3(256), 0, nullptr, d.gray, width, height, stride, d.mm, d.taps, ntap, d.tmp, N);
+    if (ntap == 29)
+        hipLaunchKernelGGL(k_gauss_cols_strip<29>, dim3((width + 255) / 256, (height + kStrip - 1) / kStrip, n_images), dim3(256), 0, nullptr, d.tmp, width, height,
+                           d.taps, d.Ig, N);
+    else
+        hipLaunchKernelGGL(k_gauss_cols, grid2, dim3(256), 0, nullptr, d.tmp, width, height, d.taps, ntap, d.Ig, N);
+    hipLaunchKernelGGL(k_corner_metric, dim3((width + 255) / 256, (height + kMetricRows - 1) / kMetricRows, n_images), dim3(256), 0, nullptr, d.Ig, width, height, sigma, std::cos(kPi / 4), std::cos(-kPi / 4), std::sin(kPi / 4),
+                       std::sin(-kPi / 4), d.metric, d.Ixy, N);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" void tscm_corner_candidates_free(tscm_corner_candidates *c)
@@ -662,26 +770,9 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
     if (n_images < 0 || (n_images > 0 && (!out || !images))) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
     if (n_images == 0) return 0;
     std::memset(out, 0, sizeof(*out) * (size_t)n_images);
-    for (int q = 0; q < n_images; ++q) if (!images[q]) return tscm_set_error(TSCM_E_INVALID, "NULL image");
-    if (width < 1 || height < 1 || stride < width) return tscm_set_error(TSCM_E_INVALID, "bad image description");
-    if (n_images > 65535) return tscm_set_error(TSCM_E_UNSUPPORTED, "more than 65535 images per batch");
-    if (width > 32767 || height > 32767) return tscm_set_error(TSCM_E_UNSUPPORTED, "images beyond 32767 pixels per side");
-    const int ntap = 7 * sigma + 1;
-    if (sigma < 1 || ntap % 2 == 0 || ntap > 64) return tscm_set_error(TSCM_E_UNSUPPORTED, "sigma must be even and at most 8 (cv::GaussianBlur needs an odd 7 sigma + 1; the reference uses 4)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (the corner detector has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    CRN_TRY(hipSetDevice(device));
+    if (int rc = check_batch(images, n_images, width, height, stride, sigma, device)) return rc;
 
     // ---- host-side constants (the C library the CPU path would use) -----------------------------------------------
-    std::vector<double> taps(ntap);
-    {
-        const double scale2x = -0.5 / ((double)sigma * sigma);
-        double sum = 0;
-        for (int i = 0; i < ntap; ++i) { const double x = i - (ntap - 1) * 0.5; taps[i] = std::exp(scale2x * x * x); sum += taps[i]; }
-        sum = 1. / sum;
-        for (int i = 0; i < ntap; ++i) taps[i] *= sum;
-    }
     const AtanConsts ac = { std::atan2(1.0, 1.0), std::atan2(1.0, -1.0), std::atan2(-1.0, 1.0), std::atan2(-1.0, -1.0),
                             std::atan2(1.0, 0.0), std::atan2(-1.0, 0.0), std::atan2(0.0, -1.0) };
     std::vector<DescribeTables> tab(1);
@@ -730,81 +821,28 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
             }
     }
 
-    // ---- device buffers --------------------------------------------------------------------------------------------
-    const size_t N = (size_t)width * height;
-    constexpr int n = kNmsN, margin = kNmsMargin;
-    const int span_x = width - 2 * (n + margin), span_y = height - 2 * (n + margin);
-    const int ncx = span_x > 0 ? (span_x + n) / (n + 1) : 0, ncy = span_y > 0 ? (span_y + n) / (n + 1) : 0;
-    const int ncell = ncx * ncy;
-    if (device >= 16) return tscm_set_error(TSCM_E_UNSUPPORTED, "device index beyond 15");
     Arena &arena = g_arena[device];
     std::lock_guard<std::mutex> lock(arena.mu);
     const size_t B = (size_t)n_images;
-    const size_t cells_n = (size_t)(ncell > 0 ? ncell : 1) * B;
-    const size_t gbytes = (size_t)stride * height;
-    const size_t need = 256 * 26 + B * gbytes + 4 * B * N * sizeof(double) + 64 * sizeof(double) + B * 256 * sizeof(double) + B * kMmSlots * kMmStride * sizeof(int)
-                      + 2 * cells_n * sizeof(int) + B * sizeof(int) + sizeof(DescribeTables) + 7 * cells_n * sizeof(double);
-    if (arena.bytes < need) {
-        if (arena.base) { (void)hipFree(arena.base); arena.base = nullptr; arena.bytes = 0; }
-        CRN_TRY(hipMalloc(&arena.base, need));
-        arena.bytes = need;
-    }
-    ArenaCursor cur = { static_cast<char *>(arena.base), arena.bytes };
-    struct { unsigned char *p; } d_gray = { cur.take<unsigned char>(B * gbytes) };
-    struct { double *p; } d_tmp = { cur.take<double>(B * N) }, d_Ig = { cur.take<double>(B * N) },
-                          d_metric = { cur.take<double>(B * N) }, d_Ixy = { cur.take<double>(B * N) }, d_taps = { cur.take<double>(64) }, d_lut = { cur.take<double>(B * 256) },
-                          d_v = { cur.take<double>(4 * cells_n) }, d_score = { cur.take<double>(cells_n) }, d_sub = { cur.take<double>(2 * cells_n) };
-    struct { int *p; } d_mm = { cur.take<int>(B * kMmSlots * kMmStride) }, d_cell = { cur.take<int>(cells_n) }, d_cand = { cur.take<int>(cells_n) },
-                       d_count = { cur.take<int>(B) };
-    struct { DescribeTables *p; } d_tab = { cur.take<DescribeTables>(1) };
-    if (!d_tab.p || !d_count.p || !d_sub.p) return tscm_set_error(TSCM_E_HIP, "internal error: arena too small");
-    // a strided view (cv::Mat ROI, numpy column slice) only guarantees (height - 1) * stride + width bytes behind its pointer
-    const size_t host_bytes = (size_t)(height - 1) * (size_t)stride + (size_t)width;
-    for (size_t q = 0; q < B; ++q) CRN_TRY(hipMemcpy(d_gray.p + q * gbytes, images[q], std::min(gbytes, host_bytes), hipMemcpyHostToDevice));
-    CRN_TRY(hipMemcpy(d_taps.p, taps.data(), sizeof(double) * ntap, hipMemcpyHostToDevice));
-    CRN_TRY(hipMemcpy(d_tab.p, tab.data(), sizeof(DescribeTables), hipMemcpyHostToDevice));
-    {
-        std::vector<int> mm0(B * kMmSlots * kMmStride, 0);
-        for (size_t q = 0; q < B * kMmSlots; ++q) { mm0[q * kMmStride] = 255; mm0[q * kMmStride + 1] = 0; }
-        CRN_TRY(hipMemcpy(d_mm.p, mm0.data(), sizeof(int) * mm0.size(), hipMemcpyHostToDevice));
-    }
-    CRN_TRY(hipMemset(d_count.p, 0, sizeof(int) * B));
-
     hipEvent_t e0, e1;
     CRN_TRY(hipEventCreate(&e0)); CRN_TRY(hipEventCreate(&e1));
-    CRN_TRY(hipEventRecord(e0, nullptr));
-    const dim3 grid2((width + 255) / 256, height, n_images);
-    if (stride == width)
-        hipLaunchKernelGGL(k_grey_extremes_flat, dim3((unsigned)((gbytes + 16383) / 16384), n_images), dim3(256), 0, nullptr, d_gray.p, gbytes, d_mm.p);
-    else
-        hipLaunchKernelGGL(k_grey_extremes, dim3((width + 4095) / 4096, height, n_images), dim3(256), 0, nullptr, d_gray.p, width, height, stride, d_mm.p);
-    if (ntap == 29) {
-        hipLaunchKernelGGL(k_norm_lut, dim3(n_images), dim3(256), 0, nullptr, d_mm.p, d_lut.p);
-        const int rows_y = (height + kRowsPerBlock - 1) / kRowsPerBlock;
-        if (width > 1024 && width <= 1280)       // one block per row at the reference's image width
-            hipLaunchKernelGGL((k_gauss_rows_n<29, 5>), dim3(1, rows_y, n_images), dim3(256), 0, nullptr, d_gray.p, width, height, stride, d_lut.p, d_taps.p, d_tmp.p, N);
-        else
-            hipLaunchKernelGGL((k_gauss_rows_n<29, 4>), dim3((width + 1023) / 1024, rows_y, n_images), dim3(256), 0, nullptr, d_gray.p, width, height, stride, d_lut.p,
-                               d_taps.p, d_tmp.p, N);
-    } else
-        hipLaunchKernelGGL(k_gauss_rows, grid2, dim3(256), 0, nullptr, d_gray.p, width, height, stride, d_mm.p, d_taps.p, ntap, d_tmp.p, N);
-    if (ntap == 29)
-        hipLaunchKernelGGL(k_gauss_cols_strip<29>, dim3((width + 255) / 256, (height + kStrip - 1) / kStrip, n_images), dim3(256), 0, nullptr, d_tmp.p, width, height,
-                           d_taps.p, d_Ig.p, N);
-    else
-        hipLaunchKernelGGL(k_gauss_cols, grid2, dim3(256), 0, nullptr, d_tmp.p, width, height, d_taps.p, ntap, d_Ig.p, N);
-    hipLaunchKernelGGL(k_corner_metric, dim3((width + 255) / 256, (height + kMetricRows - 1) / kMetricRows, n_images), dim3(256), 0, nullptr, d_Ig.p, width, height, sigma, std::cos(kPi / 4), std::cos(-kPi / 4), std::sin(kPi / 4),
-                       std::sin(-kPi / 4), d_metric.p, d_Ixy.p, N);
+    CornerBuffers d;
+    if (int rc = corner_front(images, n_images, width, height, stride, sigma, arena, tab.data(), e0, d)) {
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        return rc;
+    }
+    const size_t N = d.N;
+    const int ncell = d.ncell;
     std::vector<int> counts(B, 0);
     int n_top = 0;
     if (ncell > 0) {
-        hipLaunchKernelGGL(k_nms_cells, dim3((ncell + 255) / 256, n_images), dim3(256), 0, nullptr, d_metric.p, width, height, ncx, ncy, d_cell.p, N);
-        hipLaunchKernelGGL(k_nms_compact, dim3(n_images), dim3(1024), 0, nullptr, d_cell.p, ncell, ncell, d_cand.p, d_count.p);
-        CRN_TRY(hipMemcpy(counts.data(), d_count.p, sizeof(int) * B, hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(k_nms_cells, dim3((ncell + 255) / 256, n_images), dim3(256), 0, nullptr, d.metric, width, height, d.ncx, d.ncy, d.cell, N);
+        hipLaunchKernelGGL(k_nms_compact, dim3(n_images), dim3(1024), 0, nullptr, d.cell, ncell, ncell, d.cand, d.count);
+        CRN_TRY(hipMemcpy(counts.data(), d.count, sizeof(int) * B, hipMemcpyDeviceToHost));
         for (int c : counts) n_top = std::max(n_top, c);
         if (n_top > 0)
-            hipLaunchKernelGGL(k_corner_describe, dim3(n_top, n_images), dim3(256), 0, nullptr, d_gray.p, stride, d_mm.p, ac, d_Ixy.p, width, height,
-                               d_cand.p, d_tab.p, d_v.p, d_score.p, d_sub.p, N, ncell, d_count.p);
+            hipLaunchKernelGGL(k_corner_describe, dim3(n_top, n_images), dim3(256), 0, nullptr, d.gray, stride, d.mm, ac, d.Ixy, width, height,
+                               d.cand, d.tab, d.v, d.score, d.sub, N, ncell, d.count);
     }
     CRN_TRY(hipEventRecord(e1, nullptr));
     CRN_TRY(hipEventSynchronize(e1));
@@ -821,10 +859,10 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
         std::vector<int> cand(n_max);
         std::vector<double> v(4 * (size_t)n_max), score(n_max), sub(2 * (size_t)n_max);
         if (n_max > 0) {
-            CRN_TRY(hipMemcpy(cand.data(), d_cand.p + b * ncell, sizeof(int) * n_max, hipMemcpyDeviceToHost));
-            CRN_TRY(hipMemcpy(v.data(), d_v.p + b * 4 * ncell, sizeof(double) * 4 * n_max, hipMemcpyDeviceToHost));
-            CRN_TRY(hipMemcpy(score.data(), d_score.p + b * ncell, sizeof(double) * n_max, hipMemcpyDeviceToHost));
-            CRN_TRY(hipMemcpy(sub.data(), d_sub.p + b * 2 * ncell, sizeof(double) * 2 * n_max, hipMemcpyDeviceToHost));
+            CRN_TRY(hipMemcpy(cand.data(), d.cand + b * ncell, sizeof(int) * n_max, hipMemcpyDeviceToHost));
+            CRN_TRY(hipMemcpy(v.data(), d.v + b * 4 * ncell, sizeof(double) * 4 * n_max, hipMemcpyDeviceToHost));
+            CRN_TRY(hipMemcpy(score.data(), d.score + b * ncell, sizeof(double) * n_max, hipMemcpyDeviceToHost));
+            CRN_TRY(hipMemcpy(sub.data(), d.sub + b * 2 * ncell, sizeof(double) * 2 * n_max, hipMemcpyDeviceToHost));
         }
         int keep = 0;
         for (int q = 0; q < n_max; ++q) if (!(score[q] < min_score)) ++keep;
@@ -857,4 +895,23 @@ extern "C" int tscm_detect_corners(const unsigned char *gray, int width, int hei
     std::memset(out, 0, sizeof(*out));
     if (!gray) return tscm_set_error(TSCM_E_INVALID, "bad image description");
     return tscm_detect_corners_batch(&gray, 1, width, height, stride, sigma, min_score, device, out);
+}
+
+extern "C" int tscm_corner_planes_batch(const unsigned char *const *images, int n_images, int width, int height, int stride, int sigma, int device,
+                                        double *ig, double *metric, double *ixy)
+{
+    if (n_images < 0 || (n_images > 0 && !images)) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
+    if (n_images == 0) return 0;
+    if (int rc = check_batch(images, n_images, width, height, stride, sigma, device)) return rc;
+    Arena &arena = g_arena[device];
+    std::lock_guard<std::mutex> lock(arena.mu);
+    CornerBuffers d;
+    if (int rc = corner_front(images, n_images, width, height, stride, sigma, arena, nullptr, nullptr, d)) return rc;
+    CRN_TRY(hipDeviceSynchronize());
+    CRN_TRY(hipGetLastError());
+    const size_t bytes = sizeof(double) * d.N * (size_t)n_images;          // [n_images][height][width], as in the arena
+    if (ig) CRN_TRY(hipMemcpy(ig, d.Ig, bytes, hipMemcpyDeviceToHost));
+    if (metric) CRN_TRY(hipMemcpy(metric, d.metric, bytes, hipMemcpyDeviceToHost));
+    if (ixy) CRN_TRY(hipMemcpy(ixy, d.Ixy, bytes, hipMemcpyDeviceToHost));
+    return 0;
 }
