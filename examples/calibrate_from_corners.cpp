@@ -4,7 +4,10 @@
 //   g++ -std=c++11 -I include examples/calibrate_from_corners.cpp -L tscm_calib_amd/csrc -ltscm_hip
 //       -Wl,-rpath,$PWD/tscm_calib_amd/csrc -o examples/calibrate_from_corners        (one command line)
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
-//   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL)
+//                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
+//   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
+//    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
+//    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve)
 #include <tscm/tscm_calib.hpp>
 
 #include <cstdio>
@@ -15,20 +18,31 @@ int main(int argc, char **argv)
 {
     int loss = TSCM_LOSS_NONE;
     double loss_scale = 1.0;
-    for (int i = 3; i < argc; ++i) {
+    unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
+    bool bad_args = argc < 3;
+    for (int i = 3; i < argc && !bad_args; ++i) {
         if (!std::strcmp(argv[i], "--loss") && i + 1 < argc) {
             const char *k = argv[++i];
             loss = !std::strcmp(k, "huber") ? TSCM_LOSS_HUBER : !std::strcmp(k, "soft_l1") ? TSCM_LOSS_SOFT_L1 : !std::strcmp(k, "cauchy") ? TSCM_LOSS_CAUCHY : -1;
+            bad_args = loss < 0;
         } else if (!std::strcmp(argv[i], "--loss-scale") && i + 1 < argc) {
             loss_scale = std::strtod(argv[++i], nullptr);
+        } else if (!std::strcmp(argv[i], "--model") && i + 1 < argc) {
+            bad_args = !tscm::model_mask(argv[++i], model);
+        } else if (!std::strcmp(argv[i], "--fix") && i + 1 < argc) {
+            unsigned short w = 0;
+            bad_args = !tscm::fixed_list_mask(argv[++i], w);
+            fix = (unsigned short)(fix | w);
         } else {
-            argc = 0;
+            bad_args = true;
         }
     }
-    if (argc < 3 || loss < 0) {
-        std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]\n", argv[0]);
+    if (bad_args) {
+        std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha]\n", argv[0]);
         return 2;
     }
+    const unsigned short fixed = (unsigned short)(model | fix);
     tscm_corner_set cs;
     if (tscm_corners_read(argv[1], &cs) != 0) { std::fprintf(stderr, "%s\n", tscm_last_error()); return 1; }
     int rc = 0;
@@ -49,6 +63,7 @@ int main(int argc, char **argv)
                 for (int j = 0; j < n; ++j) pixels[b][j] = tscm::Point2d{ cs.pix_u[((size_t)m * B + b) * n + j], cs.pix_v[((size_t)m * B + b) * n + j] };
             }
             cameras[m].set_loss(loss, loss_scale);
+            cameras[m].set_fixed_intrinsics(fixed);                          // (a fresh calibrate starts at xi = lambda = 0)
             const bool ok = cameras[m].calibrate(pixels, has, worlds, image, board);
             std::printf("camera %d: %s, rmse %.4f px, fx %.3f fy %.3f cx %.3f cy %.3f xi %.4f lambda %.4f alpha %.4f\n", m, ok ? "converged" : "NOT converged",
                         cameras[m].summary.rmse, cameras[m].intrinsic_[0], cameras[m].intrinsic_[1], cameras[m].intrinsic_[2], cameras[m].intrinsic_[3],
@@ -58,6 +73,7 @@ int main(int argc, char **argv)
         if (C > 1) {
             tscm::MultiCalib mul_calib(cameras, worlds);                     // main.cpp:233
             mul_calib.set_loss(loss, loss_scale);
+            for (int m = 0; m < C; ++m) mul_calib.set_fixed_intrinsics(m, fixed);
             mul_calib.calibrate();                                           // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             for (int m = 0; m < C; ++m) std::printf("camera_%d reprojection error: %.6f\n", m, mul_calib.camera_error[m]);

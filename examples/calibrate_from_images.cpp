@@ -3,11 +3,14 @@
 //   chessboards with the flip rule, calibrate)  ->  MultiCalib(cameras, worlds) + calibrate (main.cpp:233-234)  ->  calib.yaml
 // Images are 8-bit binary PGM files (P5); the list file holds one line per camera: "<n_frames> path_0 path_1 ..." with "-"
 // for a frame the camera has no image of.  The viewer and the drawing calls of main.cpp are left out.
-//   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch]
+//   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
+//   (--model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
+//    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve)
 #include <tscm/tscm_calib.hpp>
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <sstream>
@@ -88,11 +91,30 @@ void monocular_calib(const std::vector<Image> &images, double size, tscm::Size b
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch]\n", argv[0]); return 2; }
-    const tscm::Size board = { argc > 5 ? std::atoi(argv[3]) : 9, argc > 5 ? std::atoi(argv[4]) : 6 };
-    const double size = argc > 5 ? std::atof(argv[5]) : 45.0;
-    std::ifstream list(argv[1]);
-    if (!list) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    std::vector<const char *> pos;                  // positional arguments: list, yaml, then cols rows pitch
+    unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
+    bool bad_args = false;
+    for (int i = 1; i < argc && !bad_args; ++i) {
+        if (!std::strcmp(argv[i], "--model") && i + 1 < argc) {
+            bad_args = !tscm::model_mask(argv[++i], model);
+        } else if (!std::strcmp(argv[i], "--fix") && i + 1 < argc) {
+            unsigned short w = 0;
+            bad_args = !tscm::fixed_list_mask(argv[++i], w);
+            fix = (unsigned short)(fix | w);
+        } else {
+            pos.push_back(argv[i]);
+        }
+    }
+    if (bad_args || pos.size() < 2) {
+        std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]\n", argv[0]);
+        return 2;
+    }
+    const unsigned short fixed = (unsigned short)(model | fix);
+    const bool dims = pos.size() >= 5;
+    const tscm::Size board = { dims ? std::atoi(pos[2]) : 9, dims ? std::atoi(pos[3]) : 6 };
+    const double size = dims ? std::atof(pos[4]) : 45.0;
+    std::ifstream list(pos[0]);
+    if (!list) { std::fprintf(stderr, "cannot open %s\n", pos[0]); return 2; }
     std::vector<std::vector<Image> > images;
     std::string line;
     while (std::getline(list, line)) {
@@ -108,16 +130,21 @@ int main(int argc, char **argv)
         for (int u = 0; u < board.height; ++u)
             for (int v = 0; v < board.width; ++v) worlds.push_back(tscm::Point3d{ v * size, u * size, 0.0 });
         std::vector<tscm::TripleSphereCamera> cameras(images.size());
-        for (size_t m = 0; m < images.size(); ++m) { std::printf("camera %zu: ", m); monocular_calib(images[m], size, board, worlds, cameras[m]); }
+        for (size_t m = 0; m < images.size(); ++m) {
+            std::printf("camera %zu: ", m);
+            cameras[m].set_fixed_intrinsics(fixed);                            // (the first calibrate starts at xi = lambda = 0)
+            monocular_calib(images[m], size, board, worlds, cameras[m]);
+        }
         if (cameras.size() > 1) {
             tscm::MultiCalib mul_calib(cameras, worlds);                       // main.cpp:233
+            for (size_t m = 0; m < cameras.size(); ++m) mul_calib.set_fixed_intrinsics((int)m, fixed);
             mul_calib.calibrate();                                             // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             std::printf("average reproject error: %.6f\n", mul_calib.mean_error);
-            mul_calib.write_yaml(argv[2]);                                     // main.cpp:305-319
+            mul_calib.write_yaml(pos[1]);                                     // main.cpp:305-319
         } else if (cameras.size() == 1) {
             const double I3[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t0[3] = { 0, 0, 0 };
-            tscm::check(tscm_yaml_write(argv[2], 1, cameras[0].intrinsic_.data(), I3, t0));
+            tscm::check(tscm_yaml_write(pos[1], 1, cameras[0].intrinsic_.data(), I3, t0));
         }
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s\n", e.what());

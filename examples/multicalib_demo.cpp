@@ -26,7 +26,7 @@ static std::vector<T> rd(FILE *f, size_t n)
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { fprintf(stderr, "usage: %s rig.bin result.bin calib.yaml\n", argv[0]); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: %s rig.bin result.bin calib.yaml [plain|sharded [TSCM_FIX_* word]]\n", argv[0]); return 2; }
     FILE *f = fopen(argv[1], "rb");
     if (!f) { perror(argv[1]); return 2; }
     const std::vector<int> h = rd<int>(f, 5);
@@ -64,6 +64,9 @@ int main(int argc, char **argv)
                mono0.summary.rmse, mono0.intrinsic_[0], cameras[0].intrinsic_[0]);
 
         tscm::MultiCalib mul_calib(cameras, worlds);           // main.cpp:233
+        // optional 5th argument: one TSCM_FIX_* word held for every camera in calibrate() (both branches)
+        const unsigned short fixed = argc > 5 ? (unsigned short)std::strtoul(argv[5], nullptr, 0) : 0;
+        for (int m = 0; m < C; ++m) mul_calib.set_fixed_intrinsics(m, fixed);
         if (argc > 4 && std::string(argv[4]) == "sharded") {
             // the multi-GPU form of the same call (one process per GPU in production; here one rank): the frames are
             // sharded over the ranks of a communicator, every rank ends with all parameters

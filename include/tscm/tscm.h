@@ -332,6 +332,39 @@ int tscm_eval_normal_equations_robust(const tscm_problem *problem, int device, c
 int tscm_eval_step_robust(const tscm_problem *problem, int device, const tscm_options *opt, int kind, double scale,
                           double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary);
 
+/* ------------------------------------------------------------------ held intrinsics
+ * A mask word per camera: bit k holds intrinsic k of fx fy cx cy xi lambda alpha b c (the 9-vector of
+ * tscm_problem.intr) at the value it has when the solve starts.  Ceres' semantics:
+ *   - some of bits 0-6: SubsetManifold on the camera's intrinsic block.  Held coordinates leave the
+ *     tangent space -- no column of the reduced system, no Jacobi scale, no LM diagonal, nothing in
+ *     the gradient norms (|x - Plus(x, -g)| is 0 there), the step or the step norm -- but their values
+ *     still count in x_norm (Ceres' ambient state), as b and c do.  Held values come back bit-identical.
+ *   - all of bits 0-6: SetParameterBlockConstant on the block, which leaves the program and x_norm like
+ *     a constant camera pose (tscm_problem.cam_pose_constant).
+ *   - bits 7-8 (b, c) are accepted and change nothing: b and c are inert in the model.
+ *   - bits 9 and up: TSCM_E_INVALID, checked before any device is touched.
+ *   - mask 0 for every camera (or fixed = NULL) is the solve without held intrinsics, bit for bit.
+ * Lambda = 0 makes the Triple Sphere model the Double Sphere model, xi = lambda = 0 the Unified Camera
+ * Model: TSCM_MODEL_DS / TSCM_MODEL_UCM with lambda (and xi) at 0 calibrate those models.
+ *   SetManifold(intrinsic_.data(), new SubsetManifold(9, {2, 3}))  ->  fixed[m] = TSCM_FIX_CX | TSCM_FIX_CY */
+enum {
+    TSCM_FIX_FX = 1, TSCM_FIX_FY = 2, TSCM_FIX_CX = 4, TSCM_FIX_CY = 8, TSCM_FIX_XI = 16, TSCM_FIX_LAMBDA = 32,
+    TSCM_FIX_ALPHA = 64, TSCM_FIX_B = 128, TSCM_FIX_C = 256,
+    TSCM_FIX_INTRINSICS = 127, TSCM_FIX_ALL = 511,
+    TSCM_MODEL_DS = TSCM_FIX_LAMBDA, TSCM_MODEL_UCM = TSCM_FIX_XI | TSCM_FIX_LAMBDA
+};
+/* the held intrinsics of every later solve / solve_resident of s: fixed[n_cameras], or NULL for none.
+ * May be called between solves.  The shards of a local group must hold the same intrinsics
+ * (tscm_solver_solve_group: TSCM_E_INVALID otherwise); with an RCCL or IPC communicator every rank
+ * must set the same masks -- this is not checked.                                                   */
+int tscm_solver_set_fixed_intrinsics(tscm_solver *s, const unsigned short *fixed);
+/* tscm_solve_robust with held intrinsics (kind TSCM_LOSS_NONE: no loss)                              */
+int tscm_solve_fixed(const tscm_problem *problem, const tscm_options *opt, const unsigned short *fixed, int kind, double scale,
+                     tscm_summary *summary);
+/* tscm_eval_step_robust with held intrinsics                                                         */
+int tscm_eval_step_fixed(const tscm_problem *problem, int device, const tscm_options *opt, const unsigned short *fixed, int kind,
+                         double scale, double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

@@ -40,6 +40,36 @@ struct Mat33 { double a[9]; };       // row-major, cv::Mat_<double>(3,3) order
 
 inline void check(int rc) { if (rc != 0) throw std::runtime_error(std::string("tscm: ") + tscm_last_error()); }
 
+// Command-line forms of the held-intrinsics masks (tscm.h, TSCM_FIX_*), for the example programs.
+// model_mask: "ts" -> 0, "ds" -> TSCM_MODEL_DS, "ucm" -> TSCM_MODEL_UCM; false for another name.
+inline bool model_mask(const char *name, unsigned short &word)
+{
+    const std::string n(name);
+    if (n == "ts") word = 0;
+    else if (n == "ds") word = TSCM_MODEL_DS;
+    else if (n == "ucm") word = TSCM_MODEL_UCM;
+    else return false;
+    return true;
+}
+// fixed_list_mask: "fx,cx,lambda" -> the OR of those bits (names of fx fy cx cy xi lambda alpha); false for an unknown or empty name.
+inline bool fixed_list_mask(const char *list, unsigned short &word)
+{
+    static const char *const names[7] = { "fx", "fy", "cx", "cy", "xi", "lambda", "alpha" };
+    const std::string l(list);
+    word = 0;
+    for (size_t b = 0; b <= l.size();) {
+        size_t e = l.find(',', b);
+        if (e == std::string::npos) e = l.size();
+        const std::string name = l.substr(b, e - b);
+        int k = 0;
+        while (k < 7 && name != names[k]) ++k;
+        if (k == 7) return false;
+        word = (unsigned short)(word | (1u << k));
+        b = e + 1;
+    }
+    return true;
+}
+
 // cv::Rodrigues(r -> R), the conversion update_param() does on the host (multi_calib.h:43-45,105-106)
 inline Mat33 rodrigues(const double r[3])
 {
@@ -74,6 +104,9 @@ public:
     // the loss of every residual block of refinement(): TSCM_LOSS_HUBER / _SOFT_L1 / _CAUCHY with its scale in pixels
     // (Ceres' HuberLoss(scale) etc.), TSCM_LOSS_NONE = the reference's NULL (the default).  Checked by the next refinement().
     void set_loss(int kind, double scale) { loss_kind_ = kind; loss_scale_ = scale; }
+    // intrinsics refinement() holds at their current values: TSCM_FIX_* bits (TSCM_MODEL_DS, TSCM_MODEL_UCM,
+    // TSCM_FIX_INTRINSICS, ...) -- SetManifold(intrinsic_.data(), new SubsetManifold(9, {...})).  0 = none (the default).
+    void set_fixed_intrinsics(unsigned short fixed) { fixed_ = fixed; }
 
     // TS.cpp:247-282: joint refinement of intrinsic_ and rt_[i]; returns termination_type == CONVERGENCE
     bool refinement(const std::vector<std::vector<Point2d> > &pixels, const std::vector<Point3d> &worlds,
@@ -95,7 +128,8 @@ public:
         P.obs_u = u.data(); P.obs_v = v.data(); P.intr = intrinsic_.data(); P.board_rt = rt.data(); P.mono = 1;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 1);
-        if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_mono(&P, &o, &summary));
+        if (fixed_) check(tscm_solve_fixed(&P, &o, &fixed_, loss_kind_, loss_scale_, &summary));
+        else if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_mono(&P, &o, &summary));
         else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
         return summary.termination_type == TSCM_CONVERGENCE;             // TS.cpp:281
@@ -165,6 +199,7 @@ public:
     bool has_init_guess_ = false;
     int loss_kind_ = TSCM_LOSS_NONE;
     double loss_scale_ = 0.0;
+    unsigned short fixed_ = 0;
 
     // TS.cpp:62-74
     void poses_from_Rt()
@@ -351,6 +386,12 @@ public:
     void set_sharding(int rank, int world, tscm_comm *comm) { rank_ = rank; world_ = world; comm_ = comm; }
     // the loss of every residual block of calibrate() (see TripleSphereCamera::set_loss); with sharding every rank must set the same
     void set_loss(int kind, double scale) { loss_kind_ = kind; loss_scale_ = scale; }
+    // intrinsics of camera m that calibrate() holds (TripleSphereCamera::set_fixed_intrinsics); with sharding every rank must set the same
+    void set_fixed_intrinsics(int m, unsigned short fixed)
+    {
+        if (fixed_.size() < (size_t)m + 1) fixed_.resize((size_t)m + 1, 0);
+        fixed_[(size_t)m] = fixed;
+    }
 
     // multi_calib.cpp:155-283: joint LM, write-back (update_param), reprojection-error report
     void calibrate(const tscm_options *options = nullptr)
@@ -376,6 +417,9 @@ public:
         P.cam_pose_constant = cc.data(); P.mono = 0;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 0);
+        std::vector<unsigned short> fixed(C, 0);
+        bool any_fixed = false;
+        for (int m = 0; m < C && m < (int)fixed_.size(); ++m) { fixed[m] = fixed_[m]; any_fixed = any_fixed || fixed_[m] != 0; }
         if (comm_) {
             // frame-sharded over the ranks of set_sharding(): every rank builds this same problem, keeps the boards it owns
             // and ends with ALL parameters updated (tscm.h, "multi-GPU").  (A one-rank communicator is legal: the library
@@ -384,11 +428,13 @@ public:
             check(tscm_solver_create_sharded(&P, device_, rank_, world_, &s));
             int rc = tscm_solver_set_comm(s, comm_);
             if (rc == 0) rc = tscm_solver_set_loss(s, loss_kind_, loss_scale_);
+            if (rc == 0 && any_fixed) rc = tscm_solver_set_fixed_intrinsics(s, fixed.data());
             if (rc == 0) rc = tscm_solver_solve(s, &o, &summary);
             tscm_solver_destroy(s);
             check(rc);
         } else {
-            if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_multi(&P, &o, &summary));
+            if (any_fixed) check(tscm_solve_fixed(&P, &o, fixed.data(), loss_kind_, loss_scale_, &summary));
+            else if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_multi(&P, &o, &summary));
             else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         }
         for (int m = 0; m < C; ++m) {                                    // :221-226
@@ -425,6 +471,7 @@ public:
     int rank_ = 0, world_ = 1;                // set_sharding()
     int loss_kind_ = TSCM_LOSS_NONE;          // set_loss()
     double loss_scale_ = 0.0;
+    std::vector<unsigned short> fixed_;       // set_fixed_intrinsics(), by camera (missing entries: 0)
     tscm_comm *comm_ = nullptr;
     tscm_summary summary;                     // BriefReport data of the solve (:218)
     std::vector<double> camera_error;         // per-camera mean pixel error (:281)

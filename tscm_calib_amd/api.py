@@ -10,6 +10,7 @@ TripleSphereCamera::project (TS.cpp:332-344)           project(intr, points)
 get_unit_sphere_coordinate (TS.h:39-57)                unproject(intr, pixels)
 error report (multi_calib.cpp:233-283)                 reprojection_error(problem)
 AddResidualBlock(..., new ceres::HuberLoss(a), ...)    loss=("huber", a); Solver.set_loss("huber", a)
+SetManifold(intrinsic_, new SubsetManifold(9, {..}))   fixed=("cx", "cy"); Solver.set_fixed_intrinsics(...)
 
 Everything computes on the GPU through libtscm_hip.so; there is no CPU path.
 """
@@ -59,6 +60,12 @@ class Solver:
         "cauchy" with its scale in pixels -- Ceres' HuberLoss(scale) etc. on every corner -- or None for plain least squares."""
         k, a = _l.loss_args(None if kind is None else (kind, scale))
         _l.check(_l.lib().tscm_solver_set_loss(self._h, k, a))
+
+    def set_fixed_intrinsics(self, fixed):
+        """The held intrinsics of every later solve / solve_resident (tscm_solver_set_fixed_intrinsics): None, names such as
+        ("cx", "cy") for every camera, a [C] int array of TSCM_FIX_* words or a [C, 9] bool array (lib.fixed_masks)."""
+        w = _l.fixed_masks(fixed, self.problem.n_cameras)
+        _l.check(_l.lib().tscm_solver_set_fixed_intrinsics(self._h, _l.ushort_ptr(w)))
 
     def debug_withhold_handoff(self, on=True):
         """Tests only: one producer of the device-side hand-off of the NEXT solve never reports in (tscm_solver_debug_withhold_handoff);
@@ -186,8 +193,9 @@ class Group:
     """`world` shards of one problem on ONE device, solved in lock step with the in-process exchange
     (tscm_comm_create_local + tscm_solver_solve_group): the frame-sharded solver without RCCL, e.g. on a one-GPU box."""
 
-    def __init__(self, problem: Problem, world: int, device: int = 0, *, loss=None):
-        """loss: None, or (kind, scale) as for calibrate(); every shard carries it (Solver.set_loss)."""
+    def __init__(self, problem: Problem, world: int, device: int = 0, *, loss=None, fixed=None):
+        """loss: None, or (kind, scale) as for calibrate(); every shard carries it (Solver.set_loss).
+        fixed: held intrinsics as for calibrate(); every shard holds them (Solver.set_fixed_intrinsics)."""
         self.problem = problem.normalised() if not _is_normalised(problem) else problem
         self.world = world
         self.comms = Comm.local_group(world, device)
@@ -198,6 +206,9 @@ class Group:
             k, a = _l.loss_args(loss)
             for s in self.solvers:
                 _l.check(_l.lib().tscm_solver_set_loss(s._h, k, a))
+        if fixed is not None:
+            for s in self.solvers:
+                s.set_fixed_intrinsics(fixed)
 
     def solve(self, **options) -> "list[dict]":
         """In/out through the problem's arrays, like Solver.solve; returns one summary per rank."""
@@ -242,12 +253,14 @@ def _is_normalised(p: Problem) -> bool:
             and (p.board_pose_constant is None or ok(p.board_pose_constant, np.uint8)))
 
 
-def calibrate(problem: Problem, device: int = 0, *, loss=None, **options) -> dict:
+def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, **options) -> dict:
     """The Ceres block of MultiCalib::calibrate() (multi_calib.cpp:157-218): joint LM over
     camera poses, board poses and intrinsics, in place on `problem`.  Like the reference,
     the outcome is not turned into an error -- inspect summary['termination'].
     loss: None (the reference's NULL loss), or (kind, scale) with kind "huber" | "soft_l1" | "cauchy"
-    and scale in pixels: Ceres' HuberLoss(scale) etc. on every corner (tscm_solve_robust)."""
+    and scale in pixels: Ceres' HuberLoss(scale) etc. on every corner (tscm_solve_robust).
+    fixed: intrinsics held at their start values (tscm_solve_fixed) -- None, names such as ("cx", "cy") for every
+    camera, a [C] int array of TSCM_FIX_* words (lib.FIX, lib.MODEL_DS, ...) or a [C, 9] bool array."""
     if problem.mono:
         raise ValueError("calibrate() is the multi-camera solve; use refinement() for a mono problem")
     assert _is_normalised(problem), "use Problem.normalised()"
@@ -255,14 +268,14 @@ def calibrate(problem: Problem, device: int = 0, *, loss=None, **options) -> dic
     s = _l.CSummary()
     cp = _l.c_problem(problem)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, _l.lib().tscm_solve_multi)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_multi)
     return _l.summary_dict(s)
 
 
-def refinement(problem: Problem, device: int = 0, *, loss=None, **options):
+def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, **options):
     """TripleSphereCamera::refinement (TS.cpp:247-282): returns (converged, summary) where
     converged == (termination_type == CONVERGENCE), the reference's return value (:281).
-    loss: as for calibrate()."""
+    loss, fixed: as for calibrate()."""
     if not problem.mono:
         raise ValueError("refinement() is the mono solve")
     assert _is_normalised(problem), "use Problem.normalised()"
@@ -270,13 +283,17 @@ def refinement(problem: Problem, device: int = 0, *, loss=None, **options):
     s = _l.CSummary()
     cp = _l.c_problem(problem)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, _l.lib().tscm_solve_mono)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_mono)
     d = _l.summary_dict(s)
     return d["termination_type"] == 0, d
 
 
-def _solve_one_shot(cp, o, s, loss, plain):
-    if loss is None:
+def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, plain):
+    if fixed is not None:
+        w = _l.fixed_masks(fixed, n_cameras)
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_solve_fixed(C.byref(cp), C.byref(o), _l.ushort_ptr(w), k, a, C.byref(s)))
+    elif loss is None:
         _l.check(plain(C.byref(cp), C.byref(o), C.byref(s)))
     else:
         k, a = _l.loss_args(loss)
@@ -327,10 +344,11 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
     return out
 
 
-def step(problem: Problem, device: int = 0, *, loss=None, **options) -> dict:
+def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, **options) -> dict:
     """The candidate point of the first trust-region step a solve with these options takes (tscm_eval_step_ex), at the
     problem's parameters, which stay as they are: cam_rt, intr, board_rt (x + delta as that solve evaluates it), valid
-    (False: the linear solve failed) and the one-iteration summary.  loss: as for calibrate() (tscm_eval_step_robust)."""
+    (False: the linear solve failed) and the one-iteration summary.  loss: as for calibrate() (tscm_eval_step_robust);
+    fixed: held intrinsics as for calibrate() (tscm_eval_step_fixed)."""
     assert _is_normalised(problem)
     cam, intr, board = np.zeros_like(problem.cam_rt), np.zeros_like(problem.intr), np.zeros_like(problem.board_rt)
     valid = C.c_int(0)
@@ -338,7 +356,11 @@ def step(problem: Problem, device: int = 0, *, loss=None, **options) -> dict:
     cp = _l.c_problem(problem)
     o = _l.default_options(problem.mono, **options)
     outs = (_l.dptr(cam), _l.dptr(intr), _l.dptr(board), C.byref(valid), C.byref(s))
-    if loss is None:
+    if fixed is not None:
+        w = _l.fixed_masks(fixed, problem.n_cameras)
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_eval_step_fixed(C.byref(cp), device, C.byref(o), _l.ushort_ptr(w), k, a, *outs))
+    elif loss is None:
         _l.check(_l.lib().tscm_eval_step_ex(C.byref(cp), device, C.byref(o), *outs))
     else:
         k, a = _l.loss_args(loss)

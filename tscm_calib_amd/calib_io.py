@@ -18,6 +18,31 @@ def _arrays(intr, cam_R, cam_t):
     return intr, cam_R, cam_t
 
 
+def to_double_sphere(intr):
+    """Double Sphere parameters (Usenko, Demmel, Cremers 2018) of Triple Sphere intrinsics with lambda = 0 (a
+    TSCM_MODEL_DS calibration): [..., 6] = (1 - alpha) fx, (1 - alpha) fy, cx, cy, xi, alpha.  With lambda = 0 the
+    Triple Sphere model is  u = fx x / (z + xi d1 + alpha / (1 - alpha) d2) + cx,  which is Usenko's
+    u = fx' x / (alpha d2 + (1 - alpha) (xi d1 + z)) + cx  with fx' = (1 - alpha) fx.  b and c (skew) must be 0."""
+    intr = np.asarray(intr, dtype=np.float64)
+    if intr.shape[-1] != 9:
+        raise ValueError("intrinsics are 9-vectors fx fy cx cy xi lambda alpha b c")
+    if np.any(intr[..., 5] != 0.0) or np.any(intr[..., 7:9] != 0.0):
+        raise ValueError("a Double Sphere camera has lambda = 0 and no skew (b = c = 0): calibrate with model='ds'")
+    a = intr[..., 6]
+    return np.stack([(1.0 - a) * intr[..., 0], (1.0 - a) * intr[..., 1], intr[..., 2], intr[..., 3], intr[..., 4], a], axis=-1)
+
+
+def to_ucm(intr):
+    """Unified Camera Model parameters in Usenko et al.'s convention of Triple Sphere intrinsics with xi = lambda = 0 (a
+    TSCM_MODEL_UCM calibration): [..., 5] = (1 - alpha) fx, (1 - alpha) fy, cx, cy, alpha, for
+    u = fx' x / (alpha d + (1 - alpha) z) + cx.  b and c (skew) must be 0."""
+    intr = np.asarray(intr, dtype=np.float64)
+    if intr.shape[-1] == 9 and np.any(intr[..., 4] != 0.0):
+        raise ValueError("a Unified Camera Model camera has xi = lambda = 0: calibrate with model='ucm'")
+    ds = to_double_sphere(intr)
+    return ds[..., [0, 1, 2, 3, 5]]
+
+
 def format_calib_yaml(intr, cam_R, cam_t) -> str:
     intr, cam_R, cam_t = _arrays(intr, cam_R, cam_t)
     L = _lib.lib()

@@ -199,14 +199,18 @@ struct DevProblem {
     const int4 *bc_desc;                       // the same per chunk in one 16-byte record: first board, end board, first slot, views per board
                                                // (device boards are numbered in signature order: a chunk's boards AND slots are contiguous)
     int n_bchunks, n_tiles;
-    const unsigned char *cam_const, *cam_active;
+    const unsigned char *col_ctl;      // [kMaxCam * 16] per padded camera-side parameter, for the control step: bit 0 = it counts in |x| (its
+                                       // block is part of the program), bit 1 = it is a tangent coordinate (has a gradient); 0 past n_pad
     const unsigned char *board_const;  // [B] device board: pose block held constant (tscm_problem.board_pose_constant)
     const unsigned char *col_active;   // [n_pad] 1 = column is a free camera-side parameter
     const int *act_map;                // [n_pad] compact index -> padded column (first n_act entries)
     int n_act;
-    // the compact numbering of the free camera-side columns in closed form for k_solve_reduced (<= 4 cameras): the free columns of
-    // camera q are compact [cam_pre[q], cam_pre[q + 1]) = padded cam_col0[q] + 0, 1, ...  (cam_pre[q] = n_act from q = C on)
-    int cam_pre[9], cam_col0[8];
+    // the compact numbering of the free camera-side columns from kernel arguments for k_solve_reduced (<= kMaxCamLds cameras): the
+    // free columns of camera q are compact [cam_pre[q], cam_pre[q + 1]) = padded 16 q + the set bits of cam_free[q] in ascending
+    // order (cam_pre[q] = n_act from q = C on).  Without held intrinsics the set bits are contiguous; with them the
+    // block of a camera has holes
+    int cam_pre[9];
+    unsigned short cam_free[8];
     unsigned long long pair_mask;      // bit mi * 8 + mj: the camera pair shares a board (its tile of T follows by a population count)
     const int4 *solve_map;             // [kSolveMapSlots / 4][256] operand offsets of every thread of k_solve_reduced (k_solve_map)
     int cam_wg[9];                     // cam_chunk_ptr by value for rigs of <= kMaxCamLds cameras (k_reduce_control: no index load in front of the tiles)
@@ -1142,7 +1146,7 @@ __global__ __launch_bounds__(256) void k_reduce_stats(DevProblem P, DevState S, 
 // (zero in the other ranks' slots): ONE sum all-reduce carries sums, the failure flag and the maximum.
 // What the control step reads from memory that does NOT depend on the evaluation being finalised: the LM state and the
 // target point's camera-side parameters, requested together with the first loads of the workgroup that runs the step.
-struct ControlPre { CtrlHead c; double x[2]; bool free_param[2]; };
+struct ControlPre { CtrlHead c; double x[2]; bool free_param[2], grad_param[2]; };   // free_param: counts in |x|; grad_param: has a gradient
 // what the kernel that runs the control step in its head goes on with (LDS, written by thread 0)
 struct CtlOut { int cur, done; double radius, dmin, dmax; };
 // `head`: where the LM state is read from -- S.ctrl where the calling workgroup is the only one that takes the step
@@ -1151,7 +1155,7 @@ struct CtlOut { int cur, done; double radius, dmin, dmax; };
 // ... split in two for a workgroup that has to WAIT for the evaluation's reductions first (k_schur_gram<NV, true>): what does not
 // depend on them -- the parameters of both buffers, the camera flags, the back-substitution's partials (summed per thread) -- is
 // requested in front of the wait, the LM state behind it
-struct ControlEarly { double x0[2], x1[2]; int act[2], cst[2]; double mb, ss; };
+struct ControlEarly { double x0[2], x1[2]; int cls[2]; double mb, ss; };
 __device__ __forceinline__ void control_early_params(const DevProblem &P, const DevState &S, ControlEarly &e)
 {
     // (both parameter buffers and the camera flags are requested without waiting for `cur`: one round trip, not two)
@@ -1162,7 +1166,8 @@ __device__ __forceinline__ void control_early_params(const DevProblem &P, const 
         const int ia = a < 6 ? 6 * m + a : 9 * m + min(a - 6, 8);
         e.x0[j] = a < 6 ? S.cam_rt[0][ia] : S.intr[0][ia];
         e.x1[j] = a < 6 ? S.cam_rt[1][ia] : S.intr[1][ia];
-        e.act[j] = P.cam_active[m]; e.cst[j] = P.cam_const[m];
+        // (bounded for any block size: the last entry is column 15 of camera kMaxCam - 1, a padding column whose class is 0)
+        e.cls[j] = P.col_ctl[min(p, 16 * kMaxCam - 1)];
     }
 }
 __device__ __forceinline__ void control_state(const DevProblem &P, int init, ControlPre &pre, const CtrlHead *head, const ControlEarly &e)
@@ -1185,7 +1190,8 @@ __device__ __forceinline__ void control_state(const DevProblem &P, int init, Con
         const int a = p & 15;
         const bool in = p < 16 * P.C && a < 15;
         pre.x[j] = in ? (tgt ? e.x1[j] : e.x0[j]) : 0.0;
-        pre.free_param[j] = in & (e.act[j] != 0) & !((a < 6) & (e.cst[j] != 0));
+        pre.free_param[j] = in & ((e.cls[j] & 1) != 0);
+        pre.grad_param[j] = in & ((e.cls[j] & 2) != 0);
     }
 }
 __device__ __forceinline__ void control_prefetch(const DevProblem &P, const DevState &S, int init, ControlPre &pre, const CtrlHead *head)
@@ -2730,7 +2736,7 @@ __device__ void control_step(const DevProblem &P, const DevState &S, int init, c
         const int m = p >> 4, a = p & 15;
         if (pre.free_param[j]) {
             const double x = pre.x[j];
-            const double g = a < kFA ? H[256 * m + a * 16 + kFR] : 0.0;   // b, c: zero gradient
+            const double g = pre.grad_param[j] ? H[256 * m + a * 16 + kFR] : 0.0;   // b, c and held intrinsics: zero gradient (d = 0)
             const double d = x - (x + (-g));
             gmax_c = fmax(gmax_c, fabs(d)); gsq_c += d * d; xsq_c += x * x;
         }

@@ -67,11 +67,13 @@ struct NdPlan {
     int dr_slot(int i, int k) const { return i < NP && phase_of[i] == phase_of[k] + 1 ? slot_of[i] : 0xff; }
 };
 
-// C cameras; ncols[m]: free columns of camera m (0: no views, 7: constant pose, 13), col0[m]: its first free padded column;
-// pair[mi * C + mj] (mi <= mj): the pair shares a board; bid_of[mi * C + mj]: its tile of T (-1: none).
+// C cameras; ncols[m]: free columns of camera m (0: no views, 7: constant pose, 13; fewer with held intrinsics), cols[16 m + j],
+// j < ncols[m]: its free padded columns in ascending order (a camera's block may have holes: DESIGN 15; its panels are padded
+// by the free count); pair[mi * C + mj] (mi <= mj): the pair shares a board; bid_of[mi * C + mj]: its tile of T (-1: none).
 // dense_only: one dense block (the ordering of the rounds before; TSCM_EXEC_DENSE_REDUCED_ORDER).
-// Returns false when the system does not fit the kernel (more than kNdMaxPanels panels or 2 x kNdTileThreads tiles).
-inline bool nd_build_plan(int C, const int *ncols, const int *col0, const unsigned char *pair, const int *bid_of, bool dense_only, NdPlan &pl)
+// Returns false when the system does not fit the kernel (more than kNdMaxPanels panels or 2 x kNdTileThreads tiles) or has
+// no free column at all.
+inline bool nd_build_plan_cols(int C, const int *ncols, const int *cols, const unsigned char *pair, const int *bid_of, bool dense_only, NdPlan &pl)
 {
     pl = NdPlan();
     std::vector<int> act;
@@ -134,7 +136,7 @@ inline bool nd_build_plan(int C, const int *ncols, const int *col0, const unsign
             first[q] = pl.NP;
             for (int j = 0; j < np; ++j) {
                 panel_cam.push_back(m);
-                for (int c = 0; c < 4; ++c) pl.pcol.push_back(4 * j + c < ncols[m] ? col0[m] + 4 * j + c : -1);
+                for (int c = 0; c < 4; ++c) pl.pcol.push_back(4 * j + c < ncols[m] ? cols[16 * m + 4 * j + c] : -1);
                 ++pl.NP;
             }
         }
@@ -155,11 +157,11 @@ inline bool nd_build_plan(int C, const int *ncols, const int *col0, const unsign
     }
     const int fin_p0 = pl.NP;
     {
-        std::vector<int> cols;
-        for (int m : fin) for (int j = 0; j < ncols[m]; ++j) cols.push_back(col0[m] + j);
-        const int np = ((int)cols.size() + 3) / 4;
+        std::vector<int> fcols;
+        for (int m : fin) for (int j = 0; j < ncols[m]; ++j) fcols.push_back(cols[16 * m + j]);
+        const int np = ((int)fcols.size() + 3) / 4;
         for (int j = 0; j < np; ++j) {
-            for (int c = 0; c < 4; ++c) { const int i = 4 * j + c; pl.pcol.push_back(i < (int)cols.size() ? cols[i] : -1); }
+            for (int c = 0; c < 4; ++c) { const int i = 4 * j + c; pl.pcol.push_back(i < (int)fcols.size() ? fcols[i] : -1); }
             pl.phase_of.push_back(pl.n_phases); pl.slot_of.push_back(0);
             pl.phase_panels.push_back(0xffffff00u | (unsigned)pl.NP);
             ++pl.NP; ++pl.n_phases;
@@ -314,12 +316,28 @@ inline bool nd_build_plan(int C, const int *ncols, const int *col0, const unsign
 // every camera block to whole panels, so a dense but incomplete pair graph of 8 free cameras can exceed the tile budget that
 // the dense packing of the same system meets: such a graph is solved on the dense plan (fell_back).  False only if the dense
 // plan does not fit either.
-inline bool nd_build_plans(int C, const int *ncols, const int *col0, const unsigned char *pair, const int *bid_of, NdPlan (&pl)[2], bool *fell_back = nullptr)
+inline bool nd_build_plans_cols(int C, const int *ncols, const int *cols, const unsigned char *pair, const int *bid_of, NdPlan (&pl)[2], bool *fell_back = nullptr)
 {
     if (fell_back) *fell_back = false;
-    if (!nd_build_plan(C, ncols, col0, pair, bid_of, /*dense_only=*/true, pl[1])) return false;
-    if (!nd_build_plan(C, ncols, col0, pair, bid_of, /*dense_only=*/false, pl[0])) { pl[0] = pl[1]; if (fell_back) *fell_back = true; }
+    if (!nd_build_plan_cols(C, ncols, cols, pair, bid_of, /*dense_only=*/true, pl[1])) return false;
+    if (!nd_build_plan_cols(C, ncols, cols, pair, bid_of, /*dense_only=*/false, pl[0])) { pl[0] = pl[1]; if (fell_back) *fell_back = true; }
     return true;
+}
+
+// contiguous free columns: camera m's are col0[m] + 0 .. ncols[m] - 1 (no held intrinsics)
+inline std::vector<int> nd_contiguous_cols(int C, const int *ncols, const int *col0)
+{
+    std::vector<int> cols((size_t)16 * C, -1);
+    for (int m = 0; m < C; ++m) for (int j = 0; j < ncols[m] && j < 16; ++j) cols[16 * (size_t)m + j] = col0[m] + j;
+    return cols;
+}
+inline bool nd_build_plan(int C, const int *ncols, const int *col0, const unsigned char *pair, const int *bid_of, bool dense_only, NdPlan &pl)
+{
+    return nd_build_plan_cols(C, ncols, nd_contiguous_cols(C, ncols, col0).data(), pair, bid_of, dense_only, pl);
+}
+inline bool nd_build_plans(int C, const int *ncols, const int *col0, const unsigned char *pair, const int *bid_of, NdPlan (&pl)[2], bool *fell_back = nullptr)
+{
+    return nd_build_plans_cols(C, ncols, nd_contiguous_cols(C, ncols, col0).data(), pair, bid_of, pl, fell_back);
 }
 
 }  // namespace tscm

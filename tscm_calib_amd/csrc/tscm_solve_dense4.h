@@ -18,13 +18,24 @@ __device__ __forceinline__ double load_T_small(const DevProblem &P, const double
     return ((m >> bit) & 1ull) ? T[256 * tile + a * 16 + b] : 0.0;
 }
 
+// position of the k-th (0-based) set bit of a 16-bit word that has more than k set bits, in registers (no loop)
+__host__ __device__ __forceinline__ int kth_set_bit16(unsigned w, int k)
+{
+    int pos = 0, c;
+    c = __builtin_popcount(w & 0xffu); if (k >= c) { k -= c; w >>= 8; pos += 8; }
+    c = __builtin_popcount(w & 0xfu);  if (k >= c) { k -= c; w >>= 4; pos += 4; }
+    c = __builtin_popcount(w & 0x3u);  if (k >= c) { k -= c; w >>= 2; pos += 2; }
+    c = (int)(w & 1u);                 if (k >= c) pos += 1;
+    return pos;
+}
 // compact index of the reduced system -> padded column (-1 past the last free column), from kernel arguments only
 __device__ __forceinline__ int compact_to_padded(const DevProblem &P, int ci)
 {
-    int base = 0, c0 = P.cam_col0[0];
+    int base = 0, q0 = 0;
+    unsigned w = P.cam_free[0];
 #pragma unroll
-    for (int q = 1; q < kMaxCamLds; ++q) { const bool ge = ci >= P.cam_pre[q]; base = ge ? P.cam_pre[q] : base; c0 = ge ? P.cam_col0[q] : c0; }
-    return ci < P.n_act ? c0 + (ci - base) : -1;
+    for (int q = 1; q < kMaxCamLds; ++q) { const bool ge = ci >= P.cam_pre[q]; base = ge ? P.cam_pre[q] : base; q0 = ge ? q : q0; w = ge ? P.cam_free[q] : w; }
+    return ci < P.n_act ? 16 * q0 + kth_set_bit16(w, ci - base) : -1;
 }
 // Tile of thread tid in k_solve_reduced's G x G grid (NP panels of free columns).  Lower tile (ti, tj) of the matrix on
 // thread ti * G + tj.  The right-hand side tiles (NP, p), p < NP, go to threads that own no matrix tile, counted
@@ -330,7 +341,7 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
     const bool dthread = tid == NT - 1;                     // no tile of its own: NP < G (host-checked)
     if (cj == 0 && ri > 0 && (mine || rhsrow)) publish_tile(Xb + ri * XT, a);
     if (ri == 1 && cj == 1 && mine) publish_tile(s_dt[0], a);
-    if (tid == 0) factor_diag(a, 0);
+    if (tid == 0 && NP > 0) factor_diag(a, 0);
     __syncthreads();
     for (int tk = 0; tk < NP; ++tk) {
         const double *Ar = Xb + (tk & 1) * (G * XT);

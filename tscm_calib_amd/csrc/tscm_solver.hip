@@ -188,6 +188,12 @@ struct tscm_solver {
     EvalKernel eval4 = nullptr, eval32 = nullptr;   // ... and its instantiation for this problem's board (g4_kernel), the fp32-Jacobian tier's (f32_kernel)
     EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
     LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs eval4 / eval32
+    // held intrinsics (tscm_solver_set_fixed_intrinsics): the mask word of every camera, and the whole-problem facts
+    // the free columns are derived from (build_columns)
+    std::vector<unsigned short> fixed;
+    std::vector<unsigned char> h_cam_const, h_cam_active, h_pair_present;
+    std::vector<int> h_bid_of;
+    int n_cu = 1;
     double *d_view_sq = nullptr;        // [2 V] k_reproj_error's output for the RMSE of a robust solve (allocated by the first one)
     // dominant-kernel timing
     int timing = 0;                     // 0 = off, n = bracket every n-th launch of the dominant kernel (and every n-th exchange) with HIP events
@@ -324,6 +330,148 @@ static void shard_owner(const tscm_problem *p, int world, std::vector<int> &owne
         owner[b] = std::min(r, world - 1);
         before += per_board[b];
     }
+}
+
+// frees a buffer of dev_alloc / dev_upload before the solver is destroyed (tables that build_columns rebuilds)
+template <typename T>
+static void dev_release(tscm_solver *s, const T *p)
+{
+    if (!p) return;
+    void *q = const_cast<void *>(static_cast<const void *>(p));
+    auto it = std::find(s->allocs.begin(), s->allocs.end(), q);
+    if (it != s->allocs.end()) { s->allocs.erase(it); (void)hipFree(q); }
+}
+
+// The free camera-side columns of the reduced system and every table derived from them.  A padded column
+// 16 m + a is free if camera m has views, a < kFA, the pose is not held (a < 6) and intrinsic a - 6 is not held (bit a - 6 of
+// fixed[m]).  Held intrinsics leave the tangent space: no column, no Jacobi scale, no LM diagonal, no gradient; their values
+// stay in |x| unless all seven are held, which makes the block constant (Ceres' SubsetManifold / SetParameterBlockConstant).
+// Written here: col_active, the control step's classes col_ctl, act_map / n_act, cam_pre / cam_free (kernel arguments of
+// k_solve_reduced), k_solve_map's operand map and both k_solve_nd plans.  Run by create and by tscm_solver_set_fixed_intrinsics;
+// with no held intrinsics the tables are the ones of the contiguous blocks, bit for bit.
+static int build_columns(tscm_solver *s)
+{
+    DevProblem &P = s->P;
+    const int C = s->C, n_pad = s->n_pad;
+    std::vector<unsigned char> col_active((size_t)n_pad, 0), col_ctl((size_t)16 * kMaxCam, 0);
+    std::vector<unsigned short> word(C, 0);
+    for (int i = 0; i < n_pad; ++i) {
+        const int m = i >> 4, a = i & 15;
+        const bool act = s->h_cam_active[m] != 0, cst = s->h_cam_const[m] != 0;
+        const unsigned f = s->fixed[m];
+        const bool held = a >= 6 && a < kFA && ((f >> (a - 6)) & 1u);
+        const bool block_const = (f & TSCM_FIX_INTRINSICS) == TSCM_FIX_INTRINSICS;
+        col_active[i] = (a < kFA && act && !(a < 6 && cst) && !held) ? 1 : 0;
+        const bool in_x = a < 6 ? (act && !cst) : a < 15 ? (act && !block_const) : false;
+        col_ctl[i] = (unsigned char)((in_x ? 1 : 0) | (col_active[i] ? 2 : 0));
+        if (col_active[i]) word[m] |= (unsigned short)(1u << a);
+    }
+    // compact numbering of the free camera-side columns: the reduced system is factored without the identity rows of held /
+    // padding columns
+    std::vector<int> act_map((size_t)n_pad, -1);
+    int n_act = 0;
+    for (int i = 0; i < n_pad; ++i) if (col_active[i]) act_map[n_act++] = i;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(const_cast<unsigned char *>(P.col_active), col_active.data(), col_active.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(const_cast<unsigned char *>(P.col_ctl), col_ctl.data(), col_ctl.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(const_cast<int *>(P.act_map), act_map.data(), sizeof(int) * act_map.size(), hipMemcpyHostToDevice));
+    P.n_act = n_act;
+    // the same map from kernel arguments for k_solve_reduced
+    for (int q = 0; q < 9; ++q) P.cam_pre[q] = n_act;
+    for (int q = 0; q < 8; ++q) P.cam_free[q] = 0;
+    if (C <= kMaxCamLds) {
+        int run = 0;
+        for (int m = 0; m < C; ++m) { P.cam_pre[m] = run; P.cam_free[m] = word[m]; run += __builtin_popcount(word[m]); }
+    }
+    if (s->solve_variant == 0) {
+        hipLaunchKernelGGL((k_solve_map<4, 16>), dim3(1), dim3(256), 0, s->stream, P, const_cast<int4 *>(P.solve_map));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (s->solve_variant <= 1 && n_act > 0) {
+        // two plans: [0] along the camera-pair graph, [1] the whole system as one dense block.  A graph whose per-camera panel
+        // padding does not fit the tile budget (dense but incomplete pair graphs of 8 free cameras) is solved on the dense plan;
+        // only a system that fits neither is refused.  (No free column at all: no plan -- that system is not factored, see
+        // enqueue_iteration.)
+        int ncols[kMaxCamLds];
+        std::vector<int> cols((size_t)16 * C, -1);
+        for (int m = 0; m < C; ++m) {
+            ncols[m] = 0;
+            for (int a = 0; a < 16; ++a) if ((word[m] >> a) & 1u) cols[16 * (size_t)m + ncols[m]++] = 16 * m + a;
+        }
+        NdPlan plan[2];
+        if (!nd_build_plans_cols(C, ncols, cols.data(), s->h_pair_present.data(), s->h_bid_of.data(), plan))
+            return fail(TSCM_E_UNSUPPORTED, "internal error: the reduced system does not fit the register/LDS solver");
+        for (int v = 0; v < 2; ++v) {
+            const NdPlan &pl = plan[v];
+            // (host replica check: the plan's columns are exactly the free columns)
+            std::vector<int> pc;
+            for (int c : pl.pcol) if (c >= 0) pc.push_back(c);
+            std::sort(pc.begin(), pc.end());
+            std::vector<int> want(act_map.begin(), act_map.begin() + n_act);
+            if (pc != want) return fail(TSCM_E_UNSUPPORTED, "internal error: elimination plan does not cover the free columns");
+        }
+        for (int v = 0; v < 2; ++v) {
+            const NdPlan &pl = plan[v];
+            dev_release(s, s->d_nd_map[v]); dev_release(s, s->d_nd_tab[v]); dev_release(s, s->d_nd_bs[v]);
+            s->d_nd_map[v] = nullptr; s->d_nd_tab[v] = nullptr; s->d_nd_bs[v] = nullptr;
+            const int4 *map = nullptr;
+            {
+                std::vector<int4> m4(pl.map.size() / 4);
+                std::memcpy(m4.data(), pl.map.data(), pl.map.size() * sizeof(int));
+                if (int rc = dev_upload(s, &map, m4)) return rc;
+            }
+            s->d_nd_map[v] = map;
+            if (int rc = dev_upload(s, &s->d_nd_tab[v], pl.tab)) return rc;
+            if (int rc = dev_upload(s, &s->d_nd_bs[v], pl.bs_tab)) return rc;
+            s->lds_nd[v] = sizeof(double) * pl.lds_doubles;
+            s->plan[v] = pl;
+        }
+        {
+            // ONE dynamic-LDS bound for the four instantiations (either plan may be launched, with or without riders), set
+            // before the occupancy queries that depend on it
+            const size_t lds_max = std::max(std::max(s->lds_nd[0], s->lds_nd[1]), s->lds_bs);
+            if (lds_max > 64 * 1024) {
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+            }
+        }
+        for (int v = 0; v < 2; ++v) {
+            // workgroups of the fused launch that are resident at once: the back-substitution workgroups that ride in it WAIT
+            // for the solver workgroup, so only as many are put there as fit the chip next to it (and the T producers)
+            const size_t lds = std::max(s->lds_nd[v], s->lds_bs);
+            int per_cu = 0;
+            if (s->plan[v].tpt == 1) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_nd<1, true>), kNdThreads, lds));
+            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_nd<2, true>), kNdThreads, lds));
+            s->nd_resident[v] = per_cu * s->n_cu;
+        }
+        s->lds_solve = std::max(s->lds_nd[0], s->lds_nd[1]);
+    }
+    if (s->solve_variant == 3) s->lds_solve = solve_big_lds_bytes((n_act + 15) & ~15, n_pad);
+    return 0;
+}
+
+// the mask words of tscm_solver_set_fixed_intrinsics / tscm_solve_fixed: checked before any device is touched
+static int check_fixed(const unsigned short *fixed, int C)
+{
+    if (fixed) for (int m = 0; m < C; ++m) if (fixed[m] & ~TSCM_FIX_ALL) return fail(TSCM_E_INVALID, "unknown bits in a fixed-intrinsics mask (bits 0-8 only)");
+    return 0;
+}
+
+extern "C" int tscm_solver_set_fixed_intrinsics(tscm_solver *s, const unsigned short *fixed)
+{
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    if (int rc = check_fixed(fixed, s->C)) return rc;
+    std::vector<unsigned short> f(s->C, 0);
+    if (fixed) f.assign(fixed, fixed + s->C);
+    if (f == s->fixed) return 0;
+    const std::vector<unsigned short> before = s->fixed;
+    s->fixed = f;
+    if (int rc = build_columns(s)) { s->fixed = before; (void)build_columns(s); return rc; }
+    return 0;
 }
 
 // Every rank is handed the WHOLE problem description (the view tables are small) and keeps the observations, records
@@ -694,39 +842,26 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         std::vector<short> lut(bid_of.begin(), bid_of.end());
         if ((rc = dev_upload(s, &P.bid_lut, lut))) return rc;
     }
-    std::vector<unsigned char> col_active_host;
-    if ((rc = dev_upload(s, &P.cam_const, cam_const))) return rc;
-    if ((rc = dev_upload(s, &P.cam_active, cam_active))) return rc;
     {
         std::vector<unsigned char> board_const((size_t)B, 0);
         if (p->board_pose_constant) for (int i = 0; i < B; ++i) board_const[i] = p->board_pose_constant[b0 + s->board_perm[i]] ? 1 : 0;
         if ((rc = dev_upload(s, &P.board_const, board_const))) return rc;
     }
+    P.pair_mask = 0;
+    if (C <= kMaxCamLds)
+        for (int mi = 0; mi < C; ++mi) for (int mj = mi; mj < C; ++mj) if (bid_of[mi * C + mj] >= 0) P.pair_mask |= 1ull << (mi * 8 + mj);
+    s->h_cam_const = cam_const; s->h_cam_active = cam_active; s->h_pair_present = pair_present; s->h_bid_of = bid_of;
+    s->n_cu = std::max(1, prop.multiProcessorCount);
+    s->fixed.assign(C, 0);
     {
-        std::vector<unsigned char> &col_active = col_active_host;
-        col_active.assign((size_t)s->n_pad, 0);
-        for (int i = 0; i < s->n_pad; ++i) { const int m = i >> 4, a = i & 15; col_active[i] = (a < kFA && cam_active[m] && !(a < 6 && cam_const[m])) ? 1 : 0; }
-        if ((rc = dev_upload(s, &P.col_active, col_active))) return rc;
-        // compact numbering of the free camera-side columns: the reduced system is factored without the
-        // identity rows of constant / padding columns
-        std::vector<int> act_map((size_t)s->n_pad, -1);
-        int n_act = 0;
-        for (int i = 0; i < s->n_pad; ++i) if (col_active[i]) act_map[n_act++] = i;
-        P.n_act = n_act;
-        // closed form of the same map for k_solve_reduced (kernel arguments, see DevProblem)
-        for (int q = 0; q < 9; ++q) P.cam_pre[q] = n_act;
-        for (int q = 0; q < 8; ++q) P.cam_col0[q] = 0;
-        P.pair_mask = 0;
-        if (C <= kMaxCamLds) {
-            for (int mi = 0; mi < C; ++mi) for (int mj = mi; mj < C; ++mj) if (bid_of[mi * C + mj] >= 0) P.pair_mask |= 1ull << (mi * 8 + mj);
-            int run = 0;
-            for (int m = 0; m < C; ++m) {
-                P.cam_pre[m] = run;
-                P.cam_col0[m] = 16 * m + (cam_const[m] ? 6 : 0);
-                if (cam_active[m]) run += cam_const[m] ? kFA - 6 : kFA;
-            }
-        }
-        if ((rc = dev_upload(s, &P.act_map, act_map))) return rc;
+        unsigned char *q = nullptr;
+        if ((rc = dev_alloc(s, &q, (size_t)s->n_pad))) return rc;
+        P.col_active = q;
+        if ((rc = dev_alloc(s, &q, (size_t)16 * kMaxCam))) return rc;
+        P.col_ctl = q;
+        int *am = nullptr;
+        if ((rc = dev_alloc(s, &am, (size_t)s->n_pad))) return rc;
+        P.act_map = am;
     }
 
     for (int k = 0; k < 2; ++k) {
@@ -790,11 +925,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory
     s->solve_variant = C <= 4 ? 0 : C <= kMaxCamLds ? 1 : 3;
     if (s->solve_variant == 0) {
-        // where every thread of k_solve_reduced finds its operands (camera / pair structure only): written once
+        // where every thread of k_solve_reduced finds its operands (written by build_columns)
         int4 *map = nullptr;
         if ((rc = dev_alloc(s, &map, (size_t)(kSolveMapSlots / 4) * 256))) return rc;
-        hipLaunchKernelGGL((k_solve_map<4, 16>), dim3(1), dim3(256), 0, 0, P, map);
-        HIP_TRY(hipGetLastError());
         P.solve_map = map;
         const size_t NN = 64, TT = 4, NPD = 64;
         s->lds_dense4 = sizeof(double) * (NN * (NN + 2) + 2 * (NN / TT) * (TT * TT + 2) + 2 * NN + 3 * NPD);
@@ -802,63 +935,17 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_reduced<4, 16, 64, true>), 256, std::max(s->lds_dense4, s->lds_bs)));
         s->dense4_resident = per_cu * prop.multiProcessorCount;
     }
-    if (s->solve_variant <= 1) {
-        int ncols[kMaxCamLds], col0[kMaxCamLds];
-        for (int m = 0; m < C; ++m) { ncols[m] = cam_active[m] ? (cam_const[m] ? kFA - 6 : kFA) : 0; col0[m] = 16 * m + (cam_const[m] ? 6 : 0); }
-        // two plans: [0] along the camera-pair graph, [1] the whole system as one dense block.  A graph whose per-camera panel
-        // padding does not fit the tile budget (dense but incomplete pair graphs of 8 free cameras) is solved on the dense plan;
-        // only a system that fits neither is refused
-        if (!nd_build_plans(C, ncols, col0, pair_present.data(), bid_of.data(), s->plan))
-            return fail(TSCM_E_UNSUPPORTED, "internal error: the reduced system does not fit the register/LDS solver");
-        for (int v = 0; v < 2; ++v) {
-            const NdPlan &pl = s->plan[v];
-            // (host replica check: the plan's columns are exactly the free columns)
-            std::vector<int> cols;
-            for (int pc : pl.pcol) if (pc >= 0) cols.push_back(pc);
-            std::sort(cols.begin(), cols.end());
-            std::vector<int> want;
-            for (int i = 0; i < s->n_pad; ++i) if (col_active_host[i]) want.push_back(i);
-            if (cols != want) return fail(TSCM_E_UNSUPPORTED, "internal error: elimination plan does not cover the free columns");
-            const int4 *map = nullptr;
-            {
-                std::vector<int4> m4(pl.map.size() / 4);
-                std::memcpy(m4.data(), pl.map.data(), pl.map.size() * sizeof(int));
-                if ((rc = dev_upload(s, &map, m4))) return rc;
-            }
-            s->d_nd_map[v] = map;
-            if ((rc = dev_upload(s, &s->d_nd_tab[v], pl.tab))) return rc;
-            if ((rc = dev_upload(s, &s->d_nd_bs[v], pl.bs_tab))) return rc;
-            s->lds_nd[v] = sizeof(double) * pl.lds_doubles;
-        }
-        {
-            // ONE dynamic-LDS bound for the four instantiations (either plan may be launched, with or without riders), set
-            // before the occupancy queries that depend on it
-            const size_t lds_max = std::max(std::max(s->lds_nd[0], s->lds_nd[1]), s->lds_bs);
-            if (lds_max > 64 * 1024) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            }
-        }
-        for (int v = 0; v < 2; ++v) {
-            // workgroups of the fused launch that are resident at once: the back-substitution workgroups that ride in it WAIT
-            // for the solver workgroup, so only as many are put there as fit the chip next to it (and the T producers)
-            const size_t lds = std::max(s->lds_nd[v], s->lds_bs);
-            int per_cu = 0;
-            if (s->plan[v].tpt == 1) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_nd<1, true>), kNdThreads, lds));
-            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_nd<2, true>), kNdThreads, lds));
-            s->nd_resident[v] = per_cu * prop.multiProcessorCount;
-        }
-        s->lds_solve = std::max(s->lds_nd[0], s->lds_nd[1]);
-    }
     if (s->solve_variant == 3) {
-        // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory
-        const int NN = (P.n_act + 15) & ~15;
-        s->lds_solve = solve_big_lds_bytes(NN, s->n_pad);
+        // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory, sized for every camera-side column free
+        // (held intrinsics only ever take columns away)
+        int n_max = 0;
+        for (int m = 0; m < C; ++m) if (cam_active[m]) n_max += cam_const[m] ? kFA - 6 : kFA;
+        const int NN = (n_max + 15) & ~15;
+        const size_t lds_max = solve_big_lds_bytes(NN, s->n_pad);
         if ((rc = dev_alloc(s, &S.Abig, (size_t)256 * (NN / 16 + 1) * (NN / 16 + 2) / 2))) return rc;      // packed lower triangle of 16x16 blocks, incl. the rhs block row
-        if (s->lds_solve > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_reduced_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_solve));
+        if (lds_max > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_reduced_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
     }
+    if ((rc = build_columns(s))) return rc;
     if (s->lds_eval > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board has too many corners for the LDS board-point tile");
     HIP_TRY(hipDeviceSynchronize());
     *out = sp.release();
@@ -1166,7 +1253,7 @@ static int enqueue_eval(LmRun &run, int cand, int init, int have_backsub, bool h
 
 // one GPU, up to 8 cameras: the T reduction rides in the reduced solve's launch (k_solve_nd<.., true>); with a communicator the
 // all-reduce of T sits between the two
-static bool fused_reduce(const tscm_solver *s) { return s->fuse_reduce && s->solve_variant <= 1 && !s->comm && s->P.n_bids > 0 && s->P.n_bids <= kSmallBids; }
+static bool fused_reduce(const tscm_solver *s) { return s->fuse_reduce && s->solve_variant <= 1 && !s->comm && s->P.n_bids > 0 && s->P.n_bids <= kSmallBids && s->P.n_act > 0; }
 
 static int enqueue_iteration(LmRun &run)
 {
@@ -1195,6 +1282,15 @@ static int enqueue_iteration(LmRun &run)
         const DevProblem &P = s->P;
         DevState &S = s->S;
         const int wf = s->f32_jacobian ? 1 : 0;
+        if (P.n_act == 0) {
+            // no free camera-side column (every intrinsic held where the pose is, e.g. a mono problem refining board poses only):
+            // nothing to factor.  k_solve_reduced_big on the empty system runs no panel and writes the zero camera step, the
+            // unchanged candidate camera parameters and the linear-solve flag; the back-substitution moves the boards
+            hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), solve_big_lds_bytes(0, s->n_pad), s->stream, P, S);
+            if (S.n_bs_blocks && s->bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
+            if (S.n_bs_blocks && s->bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
+            continue;
+        }
         if (s->solve_variant == 0 && !s->graph_order) {
             // up to 4 cameras, one dense block: the same launch shape with k_solve_reduced as the solver workgroup
             const int n_prod = fused_reduce(s) ? P.n_bids * (256 / kFusedEntries) : 0;
@@ -1400,6 +1496,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     if (opt.max_num_iterations < 0 || opt.max_num_iterations > TSCM_MAX_ITERATIONS) return fail(TSCM_E_INVALID, "max_num_iterations must be in [0, 255]");
     if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
     for (tscm_solver *s : run.m) if (!same_loss(s->loss, s0->loss)) return fail(TSCM_E_INVALID, "the solvers of a group carry different losses (tscm_solver_set_loss)");
+    for (tscm_solver *s : run.m) if (s->fixed != s0->fixed) return fail(TSCM_E_INVALID, "the solvers of a group hold different intrinsics (tscm_solver_set_fixed_intrinsics)");
     if (s0->loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
     HIP_TRY(hipSetDevice(s0->device));
     LmRunGuard guard{ run };
@@ -1626,7 +1723,7 @@ extern "C" int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_s
     return 0;
 }
 
-static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{})
+static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{}, const unsigned short *fixed = nullptr)
 {
     tscm_solver *s = nullptr;
     int dev = 0;
@@ -1634,6 +1731,7 @@ static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summa
     int rc = tscm_solver_create(p, dev, &s);
     if (rc) return rc;
     s->loss = loss;
+    if (fixed && (rc = tscm_solver_set_fixed_intrinsics(s, fixed))) { tscm_solver_destroy(s); return rc; }
     rc = tscm_solver_solve(s, opt, sum);
     tscm_solver_destroy(s);
     return rc;
@@ -1661,12 +1759,23 @@ extern "C" int tscm_solve_robust(const tscm_problem *p, const tscm_options *opt,
     return solve_once(p, opt, sum, L);
 }
 
+extern "C" int tscm_solve_fixed(const tscm_problem *p, const tscm_options *opt, const unsigned short *fixed, int kind, double scale, tscm_summary *sum)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
+    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
+    if (L.kind != TSCM_LOSS_NONE && opt && opt->struct_size >= sizeof(tscm_options) && (opt->exec_flags & TSCM_EXEC_GRAM_16X16))
+        return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
+    return solve_once(p, opt, sum, L, fixed);
+}
+
 // The candidate of a solve's first trust-region step: the solve itself, stopped after one iteration (termination
 // tolerances zeroed, so nothing ends it before the step is taken).  The first iteration writes its candidate into buffer 1
 // (ctrl->cur = 0 at the start); k_end_solve / k_finish_solve copy it into buffer 0 only if the step was accepted and never
 // write buffer 1, so buffer 1 holds the candidate whether the step was accepted or not
 static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *cam_rt, double *intr,
-                     double *board_rt, int *valid, tscm_summary *summary)
+                     double *board_rt, int *valid, tscm_summary *summary, const unsigned short *fixed = nullptr)
 {
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
@@ -1680,6 +1789,7 @@ static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_
     if ((rc = tscm_solver_create(p, device, &s))) return rc;
     std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
     s->loss = loss;
+    if (fixed && (rc = tscm_solver_set_fixed_intrinsics(s, fixed))) return rc;
     if ((rc = tscm_solver_upload_params(s, p->cam_rt, p->intr, p->board_rt))) return rc;
     tscm_summary sum;
     if ((rc = tscm_solver_solve_resident(s, &opt, &sum, 1))) return rc;
@@ -1704,6 +1814,16 @@ extern "C" int tscm_eval_step_robust(const tscm_problem *p, int device, const ts
     LossArg L;
     if (int rc = make_loss(kind, scale, L)) return rc;
     return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary);
+}
+
+extern "C" int tscm_eval_step_fixed(const tscm_problem *p, int device, const tscm_options *opt, const unsigned short *fixed, int kind, double scale,
+                                    double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    if (!p) return fail(TSCM_E_INVALID, "NULL argument");
+    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
+    return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary, fixed);
 }
 
 // ------------------------------------------------------------------------------------------------

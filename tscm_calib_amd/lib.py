@@ -30,6 +30,12 @@ EXEC_SEPARATE_STATS = 128
 # robust losses (tscm.h: TSCM_LOSS_*), by the names the Python layer takes
 LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2, 3
 LOSS_KINDS = {None: LOSS_NONE, "none": LOSS_NONE, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY}
+# held intrinsics (tscm.h: TSCM_FIX_*): bit k holds intrinsic k of the 9-vector
+INTRINSIC_NAMES = ("fx", "fy", "cx", "cy", "xi", "lambda", "alpha", "b", "c")
+FIX = {name: 1 << k for k, name in enumerate(INTRINSIC_NAMES)}
+FIX_INTRINSICS, FIX_ALL = 127, 511
+MODEL_DS = FIX["lambda"]
+MODEL_UCM = FIX["xi"] | FIX["lambda"]
 
 E_NAMES = {0: "TSCM_OK", -1: "TSCM_E_INVALID", -2: "TSCM_E_NO_DEVICE", -3: "TSCM_E_HIP",
            -4: "TSCM_E_RCCL", -5: "TSCM_E_UNSUPPORTED", -6: "TSCM_E_NOMEM", -7: "TSCM_E_PEER"}
@@ -128,6 +134,7 @@ EXPORTS = [
     "tscm_estimate_extrinsic", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_planes_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
+    "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed",
 ]
 
 
@@ -192,6 +199,10 @@ def lib():
     L.tscm_solve_robust.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), C.c_int, C.c_double, C.POINTER(CSummary)]
     L.tscm_eval_normal_equations_robust.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), C.c_int, C.c_double, dp, dp, dp, dp, dp, dp]
     L.tscm_eval_step_robust.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
+    usp = C.POINTER(C.c_ushort)
+    L.tscm_solver_set_fixed_intrinsics.argtypes = [vp, usp]
+    L.tscm_solve_fixed.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), usp, C.c_int, C.c_double, C.POINTER(CSummary)]
+    L.tscm_eval_step_fixed.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), usp, C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]
@@ -229,6 +240,50 @@ def loss_args(loss) -> tuple:
     if kind not in LOSS_KINDS:
         raise ValueError(f"unknown loss {kind!r}: one of 'huber', 'soft_l1', 'cauchy' or None")
     return LOSS_KINDS[kind], float(scale)
+
+
+def fixed_masks(fixed, n_cameras: int) -> np.ndarray:
+    """The [C] uint16 mask words of the C ABI (TSCM_FIX_*) from
+      - None: nothing held (all zero);
+      - an int: the same word for every camera;
+      - names, e.g. ("cx", "cy") or "lambda": those intrinsics of every camera (INTRINSIC_NAMES);
+      - a [C] integer array: one word per camera;
+      - a [C, 9] bool array: True = held.
+    Unknown names, other shapes and bits above 8 raise ValueError."""
+    C_ = int(n_cameras)
+    if fixed is None:
+        return np.zeros(C_, np.uint16)
+    if isinstance(fixed, str):
+        fixed = (fixed,)
+    if isinstance(fixed, (int, np.integer)) and not isinstance(fixed, bool):
+        words = np.full(C_, int(fixed), np.int64)
+    elif isinstance(fixed, (tuple, list)) and all(isinstance(x, str) for x in fixed):
+        w = 0
+        for name in fixed:
+            if name not in FIX:
+                raise ValueError(f"unknown intrinsic {name!r}: one of {', '.join(INTRINSIC_NAMES)}")
+            w |= FIX[name]
+        words = np.full(C_, w, np.int64)
+    else:
+        a = np.asarray(fixed)
+        if a.dtype == np.bool_:
+            if a.shape != (C_, 9):
+                raise ValueError(f"a bool mask has shape [{C_}, 9], not {list(a.shape)}")
+            words = (a.astype(np.int64) << np.arange(9, dtype=np.int64)).sum(axis=1)
+        elif np.issubdtype(a.dtype, np.integer):
+            if a.shape != (C_,):
+                raise ValueError(f"an integer mask has shape [{C_}], not {list(a.shape)}")
+            words = a.astype(np.int64)
+        else:
+            raise ValueError(f"fixed must be None, names, a [C] int array or a [C, 9] bool array, not {a.dtype}")
+    if np.any(words < 0) or np.any(words & ~FIX_ALL):
+        raise ValueError("unknown bits in a fixed-intrinsics mask (bits 0-8: fx fy cx cy xi lambda alpha b c)")
+    return words.astype(np.uint16)
+
+
+def ushort_ptr(a: np.ndarray):
+    assert a.dtype == np.uint16 and a.flags.c_contiguous
+    return a.ctypes.data_as(C.POINTER(C.c_ushort))
 
 
 def check(rc: int) -> None:

@@ -7,6 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import api, corners, maps, rig, synth
+from . import lib as _l
 from .problem import Problem
 
 
@@ -16,13 +17,35 @@ def board_points(cols: int, rows: int, pitch: float) -> np.ndarray:
     return np.stack([v.ravel() * pitch, u.ravel() * pitch, np.zeros(cols * rows)], axis=1).astype(np.float64)
 
 
-def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None):
+MODELS = {"ts": 0, "ds": _l.MODEL_DS, "ucm": _l.MODEL_UCM}
+
+
+def _model_masks(model: str, fixed, n_cameras: int) -> np.ndarray:
+    """[C] mask words of a model ("ts": Triple Sphere, "ds": lambda held at 0, "ucm": xi and lambda held at 0) and the
+    caller's held intrinsics (fixed: as for api.calibrate)."""
+    if model not in MODELS:
+        raise ValueError(f"unknown camera model {model!r}: one of 'ts', 'ds', 'ucm'")
+    return _l.fixed_masks(fixed, n_cameras) | np.uint16(MODELS[model])
+
+
+def _start_in_model(intr: np.ndarray, model: str) -> None:
+    """xi / lambda of [..., 9] intrinsics set to 0 where the model holds them there (in place)."""
+    if model in ("ds", "ucm"):
+        intr[..., 5] = 0.0
+    if model == "ucm":
+        intr[..., 4] = 0.0
+
+
+def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None):
     """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
     principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
     intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
     extrinsics are re-estimated (:52).  Then estimate_extrinsic, refinement.
     loss: None (the reference's plain least squares) or (kind, scale) of the refinement, see api.calibrate.
+    model: "ts" (Triple Sphere, the reference), "ds" (Double Sphere: lambda starts at 0 and is held there) or "ucm" (Unified
+    Camera Model: xi and lambda); fixed: further held intrinsics, as for api.calibrate.
     Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
+    w = _model_masks(model, fixed, 1)
     n = cols * rows
     W = board_points(cols, rows, pitch)
     count = (np.asarray(has, dtype=np.int32) * n).astype(np.int32)
@@ -31,13 +54,14 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
         intr[0] = intr[1] = rig.estimate_focal(pu, pv, count, cols, rows, intr[2], intr[3], device)[0]
     else:
         intr = np.array(init_intr, dtype=np.float64).reshape(9).copy()
+    _start_in_model(intr, model)
     Rt0, _ = rig.estimate_extrinsic(intr, pu, pv, count, W, cols, device)
     sel = np.flatnonzero(count > 0)
     V = sel.shape[0]
     q = Problem(1, V, W[:, :2].copy(), np.zeros(V, dtype=np.int32), np.arange(V, dtype=np.int32), (np.arange(V) * n).astype(np.int32),
                 np.full(V, n, dtype=np.int32), pu[sel].ravel().copy(), pv[sel].ravel().copy(), np.zeros((1, 6)), intr[None, :].copy(),
                 rig.poses_from_Rt(Rt0[sel]), np.ones(1, dtype=np.uint8), True).normalised()
-    _, summary = api.refinement(q, device, loss=loss)
+    _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
     R = synth.rodrigues(q.board_rt[:, :3])                                   # TS.cpp:88-102
     Rt = np.zeros((count.shape[0], 3, 3))
     Rt[sel] = np.stack([R[:, :, 0], R[:, :, 1], q.board_rt[:, 3:]], axis=2)
@@ -50,9 +74,11 @@ def _top_left_is_bright(board_img, pitch):
     return g(pitch / 2, pitch / 2) + g(pitch * 3 / 2, pitch * 3 / 2) > g(pitch * 3 / 2, pitch / 2) + g(pitch / 2, pitch * 3 / 2)
 
 
-def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None) -> dict:
+def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
+                    fixed=None) -> dict:
     """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
-    loss: the robust loss of both refinements (None: plain least squares, as the reference).
+    loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
+    and held intrinsics of both refinements (calibrate_camera).
     Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
     n, V = cols * rows, len(images)
     grey = [im if im.ndim == 2 else maps.remap(im, *np.meshgrid(np.arange(im.shape[1], dtype=np.float32), np.arange(im.shape[0], dtype=np.float32)),
@@ -63,7 +89,7 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     for i, pts in enumerate(corners.find_chessboards(grey, cols, rows, sigma=sigma, device=device)):     # :24-50, one batch
         if pts is not None:
             has[i], pu[i], pv[i] = 1, pts[:, 0], pts[:, 1]
-    intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss)          # :57
+    intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed)   # :57
     seen = np.flatnonzero(has)                                                # :59-126 refinement pass
     board_imgs = []
     for i in seen:
@@ -82,19 +108,27 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     # :127 -- the second calibrate() of the same object: a converged first refinement left has_init_guess_ set (TS.cpp:78),
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
-    intr, Rt, second = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr=warm, loss=loss)
+    intr, Rt, second = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr=warm, loss=loss, model=model,
+                                        fixed=fixed)
     return dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
 
 
-def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None) -> dict:
+def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
+                  fixed=None) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
-    and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference)."""
-    mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss) for imgs in images_by_camera]
+    and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
+    model ("ts" | "ds" | "ucm") and fixed (names or a [C] / [C, 9] mask, as for api.calibrate): held in every refinement and in
+    the joint solve; the YAML keeps the 9-vector with lambda (and xi) = 0 (calib_io.to_double_sphere / to_ucm convert)."""
+    n_cam = len(images_by_camera)
+    w = _model_masks(model, fixed, n_cam)
+    mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]))
+            for m, imgs in enumerate(images_by_camera)]
     W = board_points(cols, rows, pitch)
     inp = rig.RigInput(W, np.stack([m["intr"] for m in mono]), np.stack([m["has"] for m in mono]), np.stack([m["Rt"] for m in mono]),
                        np.stack([m["pix_u"] for m in mono]), np.stack([m["pix_v"] for m in mono])).normalised()
     g = rig.rig_init(inp, device)
     problem = rig.problem_from_rig(inp, g)
-    summary = api.calibrate(problem, device, loss=loss)
+    _start_in_model(problem.intr, model)
+    summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None)
     return dict(problem=problem, mono=mono, rig_init=g, summary=summary)
