@@ -461,6 +461,15 @@ typedef struct tscm_rig_result {
 } tscm_rig_result;
 
 int tscm_rig_init(const tscm_rig_input *in, int device, tscm_rig_result *out);
+/* One stage of the camera chaining without the choice: camera i (1 .. C-1) against camera i-1 posed at
+ * (Rp [9] row-major, tp [3]).  K = the number of boards both cameras see (has[i-1][j] && has[i][j]);
+ * Rs_out [K*9] / ts_out [K*3] receive the K pose hypotheses (multi_calib.cpp:29-48), err_out [K] the
+ * summed reprojection error of each (:50-78) as tscm_rig_init computes it.  ksplit = 0 slices the common
+ * boards by the host's rule, 1 .. K forces that many slices, anything else is TSCM_E_INVALID (checked
+ * before the device is touched).  info_out [4] (or NULL) = K, hypothesis groups of 64, slices, and
+ * 1 if the skew instantiation (b or c != 0 in either camera) ran.  For tests and diagnostics.   */
+int tscm_rig_stage_errors(const tscm_rig_input *in, int i, const double *Rp, const double *tp, int ksplit, int device,
+                          double *Rs_out, double *ts_out, double *err_out, int *info_out);
 
 
 /* ------------------------------------------------------------------ result I/O

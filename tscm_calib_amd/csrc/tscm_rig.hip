@@ -1,7 +1,8 @@
 // tscm_rig.hip -- rig initialisation on the MI355X: MultiCalib::MultiCalib
 // (multi_calib.cpp:6-153).  The quadratic hypothesis test (every common board's pose hypothesis
-// scored on every common board, both cameras) runs on the GPU, one thread per (hypothesis, board)
-// pair with board-major coalesced pixel loads; the 3x3 bookkeeping stays on the host.
+// scored on every common board, both cameras) runs on the GPU, one lane per hypothesis over a slice
+// of the common boards, whose prepared points and pixels reach the wave through scalar loads; the
+// slices are summed per hypothesis by a second kernel, and the 3x3 bookkeeping stays on the host.
 #include "tscm/tscm.h"
 #include "tscm_math.h"
 #include "tscm_fastmath.h"
@@ -168,7 +169,11 @@ __device__ __forceinline__ double pixel_error(const double *I, double beta, doub
         du = pu - __builtin_fma(I[0], mx, I[2]);
         dv = pv - __builtin_fma(I[1], my, I[3]);
     }
-    const double e2 = fmax(__builtin_fma(dv, dv, du * du), 1e-300);      // rsq(0) = inf
+    // floor: rsq(0) = inf.  fmax(NaN, 1e-300) = 1e-300 alone would score a NaN projection (a point at the camera
+    // centre, ksai = 0) as a zero error where the reference's error is NaN and the hypothesis never wins; s - s is
+    // +0 for every finite s and NaN otherwise, so the sum keeps the NaN at one add
+    const double s = __builtin_fma(dv, dv, du * du);
+    const double e2 = fmax(s, 1e-300) + (s - s);
     return e2 * fast_rsqrt(e2);
 }
 
@@ -305,6 +310,125 @@ struct DevBuf {
 
 double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// Rt_to_R_t of every (camera, board) with a detection: [C*B][R (9) | t (3)], zero where there is none
+std::vector<double> host_poses(const tscm_rig_input *in)
+{
+    const int C = in->n_cameras, B = in->n_boards;
+    std::vector<double> pose(12 * (size_t)C * B, 0.0);
+    for (int m = 0; m < C; ++m)
+        for (int j = 0; j < B; ++j) {
+            if (!in->has[(size_t)m * B + j]) continue;
+            M3 R; V3 t;
+            Rt_to_R_t(in->Rt + 9 * ((size_t)m * B + j), R, t);
+            std::memcpy(&pose[12 * ((size_t)m * B + j)], R.a, sizeof(R.a));
+            std::memcpy(&pose[12 * ((size_t)m * B + j) + 9], t.a, sizeof(t.a));
+        }
+    return pose;
+}
+
+// the boards cameras i-1 and i both see, in board order: hypothesis h comes from board common[h]
+std::vector<int> common_boards(const tscm_rig_input *in, int i)
+{
+    const int B = in->n_boards;
+    std::vector<int> common;
+    for (int j = 0; j < B; ++j) if (in->has[(size_t)(i - 1) * B + j] && in->has[(size_t)i * B + j]) common.push_back(j);
+    return common;
+}
+
+// everything the stages and the board choice read goes to the device once
+struct RigDevice {
+    DevBuf<double> worlds, intr, pose, pu, pv;
+    DevBuf<unsigned char> has;
+};
+
+int rig_upload(const tscm_rig_input *in, const std::vector<double> &pose, RigDevice &d)
+{
+    const int C = in->n_cameras, B = in->n_boards, n = in->n_points;
+    RIG_TRY(d.worlds.upload(in->worlds, 3 * (size_t)n));
+    RIG_TRY(d.intr.upload(in->intr, 9 * (size_t)C));
+    RIG_TRY(d.pose.upload(pose));
+    RIG_TRY(d.pu.upload(in->pix_u, (size_t)C * B * n));
+    RIG_TRY(d.pv.upload(in->pix_v, (size_t)C * B * n));
+    RIG_TRY(d.has.upload(in->has, (size_t)C * B));
+    return 0;
+}
+
+struct RigStage {
+    std::vector<double> Rs, ts, err;       // [K*9], [K*3], [K]
+    int jgroups = 0, ksplit = 0, skew = 0;
+    double seconds = 0.0;                  // device time of k_rig_hyp_errors + k_rig_hyp_reduce
+};
+
+// One stage of the camera chaining (multi_calib.cpp:25-85) up to its K summed errors: the hypotheses (:29-48) on
+// the host, the prepared points on the device, then k_rig_hyp_errors<SKEW> over (hypothesis groups x board slices)
+// and k_rig_hyp_reduce over the slices.  ksplit_req = 0 applies the host's slicing rule, 1..K forces that many
+// slices (the caller checks the range).  (Rp, tp) = pose of camera i-1.  The choice (:79-83) is the caller's.
+int rig_stage(const tscm_rig_input *in, const RigDevice &dev, const std::vector<double> &pose, int i,
+              const std::vector<int> &common, const M3 &Rp, const V3 &tp, int ksplit_req, const hipDeviceProp_t &prop,
+              RigStage &st)
+{
+    const int B = in->n_boards, n = in->n_points, K = (int)common.size();
+    st.Rs.assign(9 * (size_t)K, 0.0); st.ts.assign(3 * (size_t)K, 0.0); st.err.assign(K, 0.0);
+    for (int h = 0; h < K; ++h) {
+        const int j = common[h];
+        M3 Ri, Rk; V3 ti, tk;
+        std::memcpy(Ri.a, &pose[12 * ((size_t)i * B + j)], sizeof(Ri.a)); std::memcpy(ti.a, &pose[12 * ((size_t)i * B + j) + 9], sizeof(ti.a));
+        std::memcpy(Rk.a, &pose[12 * ((size_t)(i - 1) * B + j)], sizeof(Rk.a)); std::memcpy(tk.a, &pose[12 * ((size_t)(i - 1) * B + j) + 9], sizeof(tk.a));
+        const M3 Rik = mul(Ri, transpose(Rk));
+        const V3 tik = sub(ti, mul(Rik, tk));
+        const M3 Rh = mul(Rik, Rp);
+        const V3 th = add(mul(Rik, tp), tik);
+        std::memcpy(&st.Rs[9 * (size_t)h], Rh.a, sizeof(Rh.a)); std::memcpy(&st.ts[3 * (size_t)h], th.a, sizeof(th.a));
+    }
+    DevBuf<double> dRs, dts, dpart, derr;
+    DevBuf<HypPoint> dpts;
+    DevBuf<int> dcommon;
+    RIG_TRY(dRs.upload(st.Rs)); RIG_TRY(dts.upload(st.ts)); RIG_TRY(dcommon.upload(common));
+    RIG_TRY(dpts.alloc((size_t)K * 2 * n));
+    hipLaunchKernelGGL(k_rig_points, dim3((unsigned)(((size_t)K * n + 255) / 256)), dim3(256), 0, 0, K, n, B, i, dcommon.p, dev.pose.p, dev.pu.p,
+                       dev.pv.p, dev.worlds.p, dpts.p);
+    const bool skew = in->intr[9 * i + 7] != 0.0 || in->intr[9 * i + 8] != 0.0 || in->intr[9 * (i - 1) + 7] != 0.0 || in->intr[9 * (i - 1) + 8] != 0.0;
+    auto kern = skew ? k_rig_hyp_errors<true> : k_rig_hyp_errors<false>;
+    // one round of resident waves: slices of the boards so that (hypothesis groups x slices) fills the chip once
+    int per_cu = 0;
+    RIG_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0));
+    const int jgroups = (K + 63) / 64;
+    const int resident = std::max(1, per_cu) * prop.multiProcessorCount;
+    StageArgs s{};
+    s.J = K; s.K = K; s.n = n;
+    s.ksplit = ksplit_req > 0 ? ksplit_req : std::max(1, std::min(K, resident / jgroups));
+    s.Rs = dRs.p; s.ts = dts.p; s.pts = dpts.p;
+    std::memcpy(s.intrI, in->intr + 9 * i, sizeof(s.intrI)); std::memcpy(s.intrP, in->intr + 9 * (i - 1), sizeof(s.intrP));
+    s.Rp = Rp; s.tp = tp;
+    RIG_TRY(dpart.alloc((size_t)K * s.ksplit)); RIG_TRY(derr.alloc((size_t)K));
+    s.partial = dpart.p;
+    hipEvent_t e0, e1;
+    RIG_TRY(hipEventCreate(&e0)); RIG_TRY(hipEventCreate(&e1));
+    RIG_TRY(hipEventRecord(e0, 0));
+    hipLaunchKernelGGL(kern, dim3(jgroups, s.ksplit), dim3(64), 0, 0, s);
+    hipLaunchKernelGGL(k_rig_hyp_reduce, dim3((K + 255) / 256), dim3(256), 0, 0, dpart.p, K, s.ksplit, derr.p);
+    RIG_TRY(hipEventRecord(e1, 0));
+    RIG_TRY(hipEventSynchronize(e1));
+    float ms = 0.f;
+    RIG_TRY(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    RIG_TRY(hipGetLastError());
+    RIG_TRY(hipMemcpy(st.err.data(), derr.p, sizeof(double) * K, hipMemcpyDeviceToHost));
+    st.jgroups = jgroups; st.ksplit = s.ksplit; st.skew = skew ? 1 : 0;
+    st.seconds = 1e-3 * ms;
+    return 0;
+}
+
+int rig_open_device(int device, hipDeviceProp_t &prop, const char *who)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, std::string("no HIP device available (") + who + " has no CPU fallback)");
+    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
+    RIG_TRY(hipSetDevice(device));
+    RIG_TRY(hipGetDeviceProperties(&prop, device));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int tscm_poses_from_r1r2t(const double *Rt, const unsigned char *has, int n, double *rt)
@@ -328,34 +452,14 @@ extern "C" int tscm_rig_init(const tscm_rig_input *in, int device, tscm_rig_resu
     if (C > kRigMaxCam) return tscm_set_error(TSCM_E_UNSUPPORTED, "more than 32 cameras");
     if (!in->worlds || !in->intr || !in->has || !in->Rt || !in->pix_u || !in->pix_v) return tscm_set_error(TSCM_E_INVALID, "NULL input array");
     if (!out->cam_R || !out->cam_t || !out->cam_rt || !out->board_R || !out->board_t || !out->board_rt || !out->board_initial) return tscm_set_error(TSCM_E_INVALID, "NULL output array");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_rig_init has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    RIG_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    RIG_TRY(hipGetDeviceProperties(&prop, device));
+    if (int rc = rig_open_device(device, prop, "tscm_rig_init")) return rc;
     const double t_start = wall();
     out->seconds_hypotheses = 0.0; out->n_projections = 0;
 
-    // Rt_to_R_t of every (camera, board) with a detection
-    std::vector<double> pose(12 * (size_t)C * B, 0.0);
-    for (int m = 0; m < C; ++m)
-        for (int j = 0; j < B; ++j) {
-            if (!in->has[(size_t)m * B + j]) continue;
-            M3 R; V3 t;
-            Rt_to_R_t(in->Rt + 9 * ((size_t)m * B + j), R, t);
-            std::memcpy(&pose[12 * ((size_t)m * B + j)], R.a, sizeof(R.a));
-            std::memcpy(&pose[12 * ((size_t)m * B + j) + 9], t.a, sizeof(t.a));
-        }
-    // everything the two selection loops read goes to the device once
-    DevBuf<double> d_worlds, d_intr, d_pose, d_pu, d_pv;
-    DevBuf<unsigned char> d_has;
-    RIG_TRY(d_worlds.upload(in->worlds, 3 * (size_t)n));
-    RIG_TRY(d_intr.upload(in->intr, 9 * (size_t)C));
-    RIG_TRY(d_pose.upload(pose));
-    RIG_TRY(d_pu.upload(in->pix_u, (size_t)C * B * n));
-    RIG_TRY(d_pv.upload(in->pix_v, (size_t)C * B * n));
-    RIG_TRY(d_has.upload(in->has, (size_t)C * B));
+    const std::vector<double> pose = host_poses(in);
+    RigDevice dev;
+    if (int rc = rig_upload(in, pose, dev)) return rc;
 
     std::vector<M3> camR(C); std::vector<V3> camt(C);
     for (int i = 0; i < C; ++i) {
@@ -365,65 +469,18 @@ extern "C" int tscm_rig_init(const tscm_rig_input *in, int device, tscm_rig_resu
             camR[0] = M3{ { 1, 0, 0, 0, 1, 0, 0, 0, 1 } }; camt[0] = V3{ { 0, 0, 0 } };
             continue;
         }
-        std::vector<int> common;
-        for (int j = 0; j < B; ++j) if (in->has[(size_t)(i - 1) * B + j] && in->has[(size_t)i * B + j]) common.push_back(j);
+        const std::vector<int> common = common_boards(in, i);
         const int K = (int)common.size();
         if (K == 0) return tscm_set_error(TSCM_E_INVALID, "adjacent cameras " + std::to_string(i - 1) + " and " + std::to_string(i) + " share no board");
-        // hypotheses (:29-48) on the host, the prepared points of the stage on the device
-        std::vector<double> Rs(9 * (size_t)K), ts(3 * (size_t)K);
-        for (int h = 0; h < K; ++h) {
-            const int j = common[h];
-            M3 Ri, Rk; V3 ti, tk;
-            std::memcpy(Ri.a, &pose[12 * ((size_t)i * B + j)], sizeof(Ri.a)); std::memcpy(ti.a, &pose[12 * ((size_t)i * B + j) + 9], sizeof(ti.a));
-            std::memcpy(Rk.a, &pose[12 * ((size_t)(i - 1) * B + j)], sizeof(Rk.a)); std::memcpy(tk.a, &pose[12 * ((size_t)(i - 1) * B + j) + 9], sizeof(tk.a));
-            const M3 Rik = mul(Ri, transpose(Rk));
-            const V3 tik = sub(ti, mul(Rik, tk));
-            const M3 Rh = mul(Rik, camR[i - 1]);
-            const V3 th = add(mul(Rik, camt[i - 1]), tik);
-            std::memcpy(&Rs[9 * (size_t)h], Rh.a, sizeof(Rh.a)); std::memcpy(&ts[3 * (size_t)h], th.a, sizeof(th.a));
-        }
-        DevBuf<double> dRs, dts, dpart, derr;
-        DevBuf<HypPoint> dpts;
-        DevBuf<int> dcommon;
-        RIG_TRY(dRs.upload(Rs)); RIG_TRY(dts.upload(ts)); RIG_TRY(dcommon.upload(common));
-        RIG_TRY(dpts.alloc((size_t)K * 2 * n));
-        hipLaunchKernelGGL(k_rig_points, dim3((unsigned)(((size_t)K * n + 255) / 256)), dim3(256), 0, 0, K, n, B, i, dcommon.p, d_pose.p, d_pu.p, d_pv.p,
-                           d_worlds.p, dpts.p);
-        const bool skew = in->intr[9 * i + 7] != 0.0 || in->intr[9 * i + 8] != 0.0 || in->intr[9 * (i - 1) + 7] != 0.0 || in->intr[9 * (i - 1) + 8] != 0.0;
-        auto kern = skew ? k_rig_hyp_errors<true> : k_rig_hyp_errors<false>;
-        // one round of resident waves: slices of the boards so that (hypothesis groups x slices) fills the chip once
-        int per_cu = 0;
-        RIG_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0));
-        const int jgroups = (K + 63) / 64;
-        const int resident = std::max(1, per_cu) * prop.multiProcessorCount;
-        StageArgs s{};
-        s.J = K; s.K = K; s.n = n;
-        s.ksplit = std::max(1, std::min(K, resident / jgroups));
-        s.Rs = dRs.p; s.ts = dts.p; s.pts = dpts.p;
-        std::memcpy(s.intrI, in->intr + 9 * i, sizeof(s.intrI)); std::memcpy(s.intrP, in->intr + 9 * (i - 1), sizeof(s.intrP));
-        s.Rp = camR[i - 1]; s.tp = camt[i - 1];
-        RIG_TRY(dpart.alloc((size_t)K * s.ksplit)); RIG_TRY(derr.alloc((size_t)K));
-        s.partial = dpart.p;
-        hipEvent_t e0, e1;
-        RIG_TRY(hipEventCreate(&e0)); RIG_TRY(hipEventCreate(&e1));
-        RIG_TRY(hipEventRecord(e0, 0));
-        hipLaunchKernelGGL(kern, dim3(jgroups, s.ksplit), dim3(64), 0, 0, s);
-        hipLaunchKernelGGL(k_rig_hyp_reduce, dim3((K + 255) / 256), dim3(256), 0, 0, dpart.p, K, s.ksplit, derr.p);
-        RIG_TRY(hipEventRecord(e1, 0));
-        RIG_TRY(hipEventSynchronize(e1));
-        float ms = 0.f;
-        RIG_TRY(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        RIG_TRY(hipGetLastError());
-        out->seconds_hypotheses += 1e-3 * ms;
+        RigStage st;
+        if (int rc = rig_stage(in, dev, pose, i, common, camR[i - 1], camt[i - 1], 0, prop, st)) return rc;
+        out->seconds_hypotheses += st.seconds;
         out->n_projections += 2LL * n * (long long)K * K;
-        std::vector<double> err(K);
-        RIG_TRY(hipMemcpy(err.data(), derr.p, sizeof(double) * K, hipMemcpyDeviceToHost));
         double min_error = 1e10; int min_id = -1;
-        for (int j = 0; j < K; ++j) if (err[j] < min_error) { min_error = err[j]; min_id = j; }     // strict <: first minimum (:79-83)
+        for (int j = 0; j < K; ++j) if (st.err[j] < min_error) { min_error = st.err[j]; min_id = j; }     // strict <: first minimum (:79-83)
         if (min_id < 0) return tscm_set_error(TSCM_E_INVALID, "no pose hypothesis with a finite reprojection error < 1e10 (the reference indexes Rs[-1] here)");
-        std::memcpy(camR[i].a, &Rs[9 * (size_t)min_id], sizeof(camR[i].a));
-        std::memcpy(camt[i].a, &ts[3 * (size_t)min_id], sizeof(camt[i].a));
+        std::memcpy(camR[i].a, &st.Rs[9 * (size_t)min_id], sizeof(camR[i].a));
+        std::memcpy(camt[i].a, &st.ts[3 * (size_t)min_id], sizeof(camt[i].a));
         if (out->cam_choice) out->cam_choice[i] = min_id;
         if (out->cam_min_error) out->cam_min_error[i] = min_error;
     }
@@ -441,7 +498,7 @@ extern "C" int tscm_rig_init(const tscm_rig_input *in, int device, tscm_rig_resu
         DevBuf<double> dcR, dct, dbR, dbt;
         RIG_TRY(dcR.upload(cR)); RIG_TRY(dct.upload(ct));
         RIG_TRY(dbR.alloc(9 * (size_t)B)); RIG_TRY(dbt.alloc(3 * (size_t)B)); RIG_TRY(dinit.alloc((size_t)B));
-        hipLaunchKernelGGL(k_rig_boards, dim3((B + 127) / 128), dim3(128), 0, 0, C, B, n, d_has.p, d_pose.p, d_pu.p, d_pv.p, d_worlds.p, d_intr.p,
+        hipLaunchKernelGGL(k_rig_boards, dim3((B + 127) / 128), dim3(128), 0, 0, C, B, n, dev.has.p, dev.pose.p, dev.pu.p, dev.pv.p, dev.worlds.p, dev.intr.p,
                            dcR.p, dct.p, dbR.p, dbt.p, dinit.p);
         RIG_TRY(hipDeviceSynchronize());
         RIG_TRY(hipGetLastError());
@@ -462,5 +519,33 @@ extern "C" int tscm_rig_init(const tscm_rig_input *in, int device, tscm_rig_resu
         }
     }
     out->seconds_total = wall() - t_start;
+    return 0;
+}
+
+extern "C" int tscm_rig_stage_errors(const tscm_rig_input *in, int i, const double *Rp, const double *tp, int ksplit, int device,
+                                     double *Rs_out, double *ts_out, double *err_out, int *info_out)
+{
+    if (!in || !Rp || !tp || !Rs_out || !ts_out || !err_out) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
+    const int C = in->n_cameras, B = in->n_boards, n = in->n_points;
+    if (C < 2 || B < 0 || n < 1) return tscm_set_error(TSCM_E_INVALID, "bad rig dimensions");
+    if (i < 1 || i >= C) return tscm_set_error(TSCM_E_INVALID, "stage index out of range (1 .. n_cameras - 1)");
+    if (!in->worlds || !in->intr || !in->has || !in->Rt || !in->pix_u || !in->pix_v) return tscm_set_error(TSCM_E_INVALID, "NULL input array");
+    const std::vector<int> common = common_boards(in, i);
+    const int K = (int)common.size();
+    if (K == 0) return tscm_set_error(TSCM_E_INVALID, "adjacent cameras " + std::to_string(i - 1) + " and " + std::to_string(i) + " share no board");
+    if (ksplit < 0 || ksplit > K) return tscm_set_error(TSCM_E_INVALID, "ksplit must be 0 (the host's rule) or 1 .. K = " + std::to_string(K));
+    hipDeviceProp_t prop;
+    if (int rc = rig_open_device(device, prop, "tscm_rig_stage_errors")) return rc;
+    const std::vector<double> pose = host_poses(in);
+    RigDevice dev;
+    if (int rc = rig_upload(in, pose, dev)) return rc;
+    M3 R; V3 t;
+    std::memcpy(R.a, Rp, sizeof(R.a)); std::memcpy(t.a, tp, sizeof(t.a));
+    RigStage st;
+    if (int rc = rig_stage(in, dev, pose, i, common, R, t, ksplit, prop, st)) return rc;
+    std::memcpy(Rs_out, st.Rs.data(), sizeof(double) * st.Rs.size());
+    std::memcpy(ts_out, st.ts.data(), sizeof(double) * st.ts.size());
+    std::memcpy(err_out, st.err.data(), sizeof(double) * st.err.size());
+    if (info_out) { info_out[0] = K; info_out[1] = st.jgroups; info_out[2] = st.ksplit; info_out[3] = st.skew; }
     return 0;
 }

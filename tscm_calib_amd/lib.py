@@ -129,7 +129,7 @@ EXPORTS = [
     "tscm_eval_normal_equations", "tscm_eval_normal_equations_ex", "tscm_eval_step_ex", "tscm_project_points", "tscm_unproject_pixels",
     "tscm_reprojection_error", "tscm_comm_unique_id", "tscm_comm_create", "tscm_comm_destroy",
     "tscm_shard_frames", "tscm_solver_create_sharded", "tscm_comm_create_local", "tscm_comm_ipc_open", "tscm_comm_ipc_connect", "tscm_solver_solve_group",
-    "tscm_solver_gather_boards", "tscm_comm_info", "tscm_rig_init", "tscm_yaml_format", "tscm_yaml_write", "tscm_yaml_parse",
+    "tscm_solver_gather_boards", "tscm_comm_info", "tscm_rig_init", "tscm_rig_stage_errors", "tscm_yaml_format", "tscm_yaml_write", "tscm_yaml_parse",
     "tscm_yaml_read", "tscm_build_maps", "tscm_estimate_focal", "tscm_poses_from_r1r2t",
     "tscm_estimate_extrinsic", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_planes_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
@@ -212,6 +212,7 @@ def lib():
     L.tscm_comm_destroy.restype = None
     L.tscm_shard_frames.argtypes = [C.POINTER(CProblem), C.c_int, ip]
     L.tscm_rig_init.argtypes = [C.POINTER(CRigInput), C.c_int, C.POINTER(CRigResult)]
+    L.tscm_rig_stage_errors.argtypes = [C.POINTER(CRigInput), C.c_int, dp, dp, C.c_int, C.c_int, dp, dp, dp, ip]
     L.tscm_build_maps.argtypes = [C.POINTER(CMapDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                   C.c_size_t, dp]
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]

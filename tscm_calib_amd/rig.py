@@ -69,6 +69,31 @@ def rig_init(inp: RigInput, device: int = 0) -> dict:
     return out
 
 
+def stage_errors(inp: RigInput, i: int, Rp, tp, ksplit: int = 0, device: int = 0) -> dict:
+    """tscm_rig_stage_errors: stage i of the camera chaining (camera i against camera i-1 posed at Rp, tp) without
+    the choice.  Returns the K hypotheses Rs [K,3,3] / ts [K,3], all K summed errors, and the partition the kernels
+    ran: jgroups (hypothesis groups of 64), ksplit (board slices; 0 = the host's rule), skew (SKEW instantiation)."""
+    inp = inp.normalised()
+    Cn, B, n = inp.n_cameras, inp.n_boards, inp.n_points
+    if inp.has.shape != (Cn, B) or inp.Rt.shape != (Cn, B, 3, 3) or inp.pix_u.shape != (Cn, B, n) \
+            or inp.pix_v.shape != (Cn, B, n) or inp.worlds.shape != (n, 3) or inp.intr.shape != (Cn, 9):
+        raise ValueError("inconsistent RigInput shapes")
+    K = int(np.count_nonzero(inp.has[i - 1] & inp.has[i])) if 1 <= i < Cn else 0
+    q = _lib.CRigInput()
+    q.n_cameras, q.n_boards, q.n_points = Cn, B, n
+    for name in ("worlds", "intr", "has", "Rt", "pix_u", "pix_v"):
+        setattr(q, name, getattr(inp, name).ctypes.data)
+    Rp = np.ascontiguousarray(Rp, dtype=np.float64).reshape(9)
+    tp = np.ascontiguousarray(tp, dtype=np.float64).reshape(3)
+    Rs, ts, err = np.zeros((max(K, 1), 3, 3)), np.zeros((max(K, 1), 3)), np.zeros(max(K, 1))
+    info = np.zeros(4, dtype=np.int32)
+    _lib.check(_lib.lib().tscm_rig_stage_errors(C.byref(q), int(i), _lib.dptr(Rp), _lib.dptr(tp), int(ksplit), device,
+                                                _lib.dptr(Rs), _lib.dptr(ts), _lib.dptr(err),
+                                                info.ctypes.data_as(C.POINTER(C.c_int))))
+    assert info[0] == K
+    return dict(Rs=Rs[:K], ts=ts[:K], err=err[:K], K=K, jgroups=int(info[1]), ksplit=int(info[2]), skew=bool(info[3]))
+
+
 def problem_from_rig(inp: RigInput, init: dict) -> Problem:
     """The ceres::Problem MultiCalib::calibrate() builds from the constructor's result
     (multi_calib.cpp:157-207): one view per (camera, initialised board) with pixels."""
