@@ -28,14 +28,11 @@
 #include "tscm_math.h"
 #include "tscm_fastmath.h"
 #include "tscm_nd_plan.h"
+#include "tscm_layout.h"
 
 namespace tscm {
 
-constexpr int kRecW = 84;          // doubles per view in the W region: E^T [F | r], 14 columns x 6 rows, column-major
-constexpr int kRecE = 18;          // doubles per view in the E region: E^T E_wb, 3 columns x 6 rows, column-major
-constexpr int kRecG = 6;           // doubles per view in the G region: E^T r once more, compact (round 5): the board statistics read 48
-                                   // contiguous bytes per view instead of the last 48 of every 672-byte W record
-constexpr int kRec = kRecW + kRecE + kRecG;  // doubles per view over the regions (allocation size, offset limits)
+// the view record regions kRecW / kRecE / kRecG and the rig limits kMaxCamLds / kMaxCam / kSmallBids: tscm_layout.h
 constexpr int kWcolTc = 3;         // W columns of t_c: F index 3, 4, 5 (the gradient column E^T r is F index kFR = 13)
 // per-board factor record (doubles)
 constexpr int kFac = 56;
@@ -63,9 +60,6 @@ constexpr int kCst = 80;           // LDS constant block: [0,27) view, [27,75) c
 constexpr int kScal = 8;           // scalars appended to H_stage
 constexpr int kStStride = 16;      // doubles between the board-statistics partials of two workgroups: a 128-byte line each (written by ONE workgroup: see k_schur_gram<NV, true>)
 constexpr int kCamSl = 16;         // the per-camera tile reduction runs in slices of 32 of the 512 raw entries: C * kCamSl workgroups
-constexpr int kSmallBids = 36;     // camera-pair blocks of a rig of <= 8 cameras (8 + 28): their partial-tile ranges travel as kernel arguments
-constexpr int kMaxCamLds = 8;      // n_pad = 16*C <= 128: reduced system solved in registers/LDS (k_solve_reduced)
-constexpr int kMaxCam = 32;        // larger rigs: k_solve_reduced_big factors the system in global memory (n_pad <= 512)
 constexpr int kMaxLog = 256;
 
 // phase stamps of the fused kernels (make PHASES=1: -DTSCM_PHASE_PROFILE; s_memrealtime, 10 ns ticks; one line per
@@ -174,9 +168,10 @@ struct Ctrl : CtrlHead {
     IterLog log[kMaxLog];
 };
 
+// the problem on the device: the tables of tscm_layout.h's Layout (plan_layout), uploaded by tscm_solver_create_sharded
 struct DevProblem {
     int C, B, n_points, V, N, n_pad;
-    int n_chunks, n_pairs, n_pchunks, n_bids;
+    int n_chunks, n_pchunks, n_bids;
     int rp, half;                      // LDS pitch (doubles) and rows of the Jacobian tile
     int lds_wave;                      // doubles of LDS per wave of k_eval_gram
     const double *board_xy;
@@ -190,13 +185,11 @@ struct DevProblem {
     const int *slow_boards;            // boards seen by more than three cameras (factored by k_schur_factor, Gram by k_pair_gram)
     int n_slow;
     const int *pair_i, *pair_j;
-    const int *pc_begin, *pc_end, *pc_tile, *bid_mi, *bid_mj;
+    const int *pc_begin, *pc_end, *pc_tile;
     const int *bid_part_ptr;                   // per camera-pair block: contiguous range of its partial tiles in pairpart
-    const int *sslot;                          // first view slot of each board, boards grouped by camera-set signature
-    const int *sboard;                         // ... and the board itself (its factor record)
     const int *pair_board;                     // board of each fallback view pair
-    const int *bc_begin, *bc_end, *bc_nv, *bc_tile;   // board chunks: range in sslot, views per board, tile ids [chunk*6 + t]
-    const int4 *bc_desc;                       // the same per chunk in one 16-byte record: first board, end board, first slot, views per board
+    const int *bc_tile;                        // board chunks: tile ids [chunk*6 + t]
+    const int4 *bc_desc;                       // ... and per chunk one 16-byte record: first board, end board, first slot, views per board
                                                // (device boards are numbered in signature order: a chunk's boards AND slots are contiguous)
     int n_bchunks, n_tiles;
     const unsigned char *col_ctl;      // [kMaxCam * 16] per padded camera-side parameter, for the control step: bit 0 = it counts in |x| (its
@@ -1540,8 +1533,7 @@ __global__ __launch_bounds__(256) void k_schur_factor(DevProblem P, DevState S)
 //             anything twice and no operand has to be moved: 6 NT MFMAs and 27 NV FMAs per lane per four boards.
 //             The next group's columns are requested before the MFMAs, which cover their latency.
 // The four waves' tiles are summed in a fixed order through LDS.
-// grid (chunks of this NV) x 256
-constexpr int kChunkBoards = 64;
+// grid (chunks of this NV) x 256; a chunk has at most kChunkBoards boards (tscm_layout.h)
 
 
 // the forward-substitution values of a board factored by k_schur_factor, wave-uniform through the constant address

@@ -135,16 +135,11 @@ struct tscm_solver {
     DevState S{};
     std::vector<void *> allocs;
     tscm_comm *comm = nullptr;
-    // host copies of the layout
-    int C = 0, B = 0, V = 0, N = 0, n_points = 0, n_pad = 0;     // B, V, N: this rank's boards / views / corners
+    Layout L;                           // host copy of the layout (tscm_layout.h: plan_layout)
+    int C = 0, B = 0, V = 0, N = 0, n_points = 0, n_pad = 0;     // B, V, N: this rank's boards / views / corners (L.B, L.V, L.N)
     int rank = 0, world = 1;
-    int b0 = 0, B_total = 0;            // owned boards = [b0, b0 + B) of the caller's B_total
-    long N_total = 0;                   // corners of the whole job (RMSE, summary)
     hipStream_t own_stream = nullptr;   // `stream` is replaced by the group's while a local group solve runs
     bool mono = false;
-    std::vector<int> dev2orig;          // device view -> problem view
-    std::vector<int> h_view_obs, h_view_count, h_view_cam, h_view_board, h_view_slot;   // h_view_board: DEVICE board index
-    std::vector<int> board_perm;        // device board index -> board of the caller (relative to b0): see create
     // caller-owned parameter arrays (host)
     double *h_cam_rt = nullptr, *h_intr = nullptr, *h_board_rt = nullptr;
     // resident initial parameters for the benchmark
@@ -154,8 +149,6 @@ struct tscm_solver {
     Ctrl *h_ctrl = nullptr;             // pinned
     Ctrl *d_h_ctrl = nullptr;           // ... and its address on the device (k_finish_solve writes the control block there itself)
     size_t lds_eval = 0, lds_eval32 = 0, lds_solve = 0, lds_gram = 0, lds_bs = 0;
-    int bs_threads = 128;               // geometry of k_backsub_prep: 128 threads / 16 boards or 256 / 32
-    int nv_chunk0[4] = { 0, 0, 0, 0 }, nv_chunks[4] = { 0, 0, 0, 0 };      // chunk ranges of k_schur_gram<NV>
     bool fuse_reduce = true;            // this solve: k_T_reduce rides in the reduced solve's launch (tscm_options.exec_flags & TSCM_EXEC_SEPARATE_T_REDUCE clears it)
     bool fuse_backsub = true;           // this solve: k_backsub_prep rides in it too (TSCM_EXEC_SEPARATE_BACKSUB clears it)
     bool ctl_in_schur = false;          // this solve: the control step of a candidate's evaluation is taken in the head of the next k_schur_gram
@@ -188,11 +181,9 @@ struct tscm_solver {
     EvalKernel eval4 = nullptr, eval32 = nullptr;   // ... and its instantiation for this problem's board (g4_kernel), the fp32-Jacobian tier's (f32_kernel)
     EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
     LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs eval4 / eval32
-    // held intrinsics (tscm_solver_set_fixed_intrinsics): the mask word of every camera, and the whole-problem facts
-    // the free columns are derived from (build_columns)
+    // held intrinsics (tscm_solver_set_fixed_intrinsics): the mask word of every camera (the whole-problem facts the
+    // free columns are derived from are L.cam_const, L.cam_active, L.pair_present: build_columns)
     std::vector<unsigned short> fixed;
-    std::vector<unsigned char> h_cam_const, h_cam_active, h_pair_present;
-    std::vector<int> h_bid_of;
     int n_cu = 1;
     double *d_view_sq = nullptr;        // [2 V] k_reproj_error's output for the RMSE of a robust solve (allocated by the first one)
     // dominant-kernel timing
@@ -267,18 +258,8 @@ extern "C" void tscm_default_options(tscm_options *o, int mono)
 
 static int validate(const tscm_problem *p)
 {
-    if (!p) return fail(TSCM_E_INVALID, "problem is NULL");
-    if (p->n_cameras < 1 || p->n_boards < 0 || p->n_points < 1 || p->n_views < 0) return fail(TSCM_E_INVALID, "negative or zero problem dimensions");
-    if (p->mono && p->n_cameras != 1) return fail(TSCM_E_INVALID, "mono problem needs exactly one camera");
-    if (!p->board_xy || !p->intr || (!p->board_rt && p->n_boards) || (!p->mono && !p->cam_rt)) return fail(TSCM_E_INVALID, "NULL parameter/board array");
-    if (p->n_views && (!p->view_camera || !p->view_board || !p->view_offset || !p->view_count || !p->obs_u || !p->obs_v)) return fail(TSCM_E_INVALID, "NULL view/observation array");
-    if (p->n_cameras > kMaxCam) return fail(TSCM_E_UNSUPPORTED, "more than 32 cameras");
-    for (int v = 0; v < p->n_views; ++v) {
-        if (p->view_camera[v] < 0 || p->view_camera[v] >= p->n_cameras) return fail(TSCM_E_INVALID, "view_camera out of range");
-        if (p->view_board[v] < 0 || p->view_board[v] >= p->n_boards) return fail(TSCM_E_INVALID, "view_board out of range");
-        if (p->view_count[v] < 0 || p->view_count[v] > p->n_points) return fail(TSCM_E_INVALID, "view_count outside [0, n_points]");
-        if (p->view_offset[v] < 0) return fail(TSCM_E_INVALID, "negative view_offset");
-    }
+    std::string err;
+    if (int rc = tscm::validate(p, err)) return fail(rc, err);
     return 0;
 }
 
@@ -316,22 +297,6 @@ extern "C" void tscm_solver_destroy(tscm_solver *s)
     delete s;
 }
 
-// owner[b] = rank of board b: contiguous ranges balanced by corner count (shared by tscm_shard_frames and the solver)
-static void shard_owner(const tscm_problem *p, int world, std::vector<int> &owner)
-{
-    std::vector<double> per_board(p->n_boards, 0.0);
-    for (int v = 0; v < p->n_views; ++v) per_board[p->view_board[v]] += p->view_count[v];
-    double total = 0.0;
-    for (double x : per_board) total += x;
-    owner.assign(p->n_boards, 0);
-    double before = 0.0;
-    for (int b = 0; b < p->n_boards; ++b) {
-        const int r = total > 0.0 ? (int)(before * world / total) : 0;
-        owner[b] = std::min(r, world - 1);
-        before += per_board[b];
-    }
-}
-
 // frees a buffer of dev_alloc / dev_upload before the solver is destroyed (tables that build_columns rebuilds)
 template <typename T>
 static void dev_release(tscm_solver *s, const T *p)
@@ -357,7 +322,7 @@ static int build_columns(tscm_solver *s)
     std::vector<unsigned short> word(C, 0);
     for (int i = 0; i < n_pad; ++i) {
         const int m = i >> 4, a = i & 15;
-        const bool act = s->h_cam_active[m] != 0, cst = s->h_cam_const[m] != 0;
+        const bool act = s->L.cam_active[m] != 0, cst = s->L.cam_const[m] != 0;
         const unsigned f = s->fixed[m];
         const bool held = a >= 6 && a < kFA && ((f >> (a - 6)) & 1u);
         const bool block_const = (f & TSCM_FIX_INTRINSICS) == TSCM_FIX_INTRINSICS;
@@ -401,7 +366,7 @@ static int build_columns(tscm_solver *s)
             for (int a = 0; a < 16; ++a) if ((word[m] >> a) & 1u) cols[16 * (size_t)m + ncols[m]++] = 16 * m + a;
         }
         NdPlan plan[2];
-        if (!nd_build_plans_cols(C, ncols, cols.data(), s->h_pair_present.data(), s->h_bid_of.data(), plan))
+        if (!nd_build_plans_cols(C, ncols, cols.data(), s->L.pair_present.data(), s->L.bid_of.data(), plan))
             return fail(TSCM_E_UNSUPPORTED, "internal error: the reduced system does not fit the register/LDS solver");
         for (int v = 0; v < 2; ++v) {
             const NdPlan &pl = plan[v];
@@ -432,12 +397,10 @@ static int build_columns(tscm_solver *s)
             // ONE dynamic-LDS bound for the four instantiations (either plan may be launched, with or without riders), set
             // before the occupancy queries that depend on it
             const size_t lds_max = std::max(std::max(s->lds_nd[0], s->lds_nd[1]), s->lds_bs);
-            if (lds_max > 64 * 1024) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_nd<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            }
+            if (lds_max > 64 * 1024)
+                for (const void *k : { reinterpret_cast<const void *>(k_solve_nd<1, true>), reinterpret_cast<const void *>(k_solve_nd<2, true>),
+                                       reinterpret_cast<const void *>(k_solve_nd<1, false>), reinterpret_cast<const void *>(k_solve_nd<2, false>) })
+                    HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         }
         for (int v = 0; v < 2; ++v) {
             // workgroups of the fused launch that are resident at once: the back-substitution workgroups that ride in it WAIT
@@ -475,9 +438,9 @@ extern "C" int tscm_solver_set_fixed_intrinsics(tscm_solver *s, const unsigned s
 }
 
 // Every rank is handed the WHOLE problem description (the view tables are small) and keeps the observations, records
-// and pose blocks of the boards it owns.  What the ranks must agree on is derived from the whole problem, identically
-// on every rank: which cameras have views at all (free columns of the reduced system), which camera pairs share a
-// board (tiles of T) and the total corner count.
+// and pose blocks of the boards it owns; plan_layout (tscm_layout.h) derives this rank's layout, and what the ranks must
+// agree on identically on every rank.  Refusals in order: the arguments and validate(), the device, the board size the
+// Gram kernel's LDS takes, the layout's (plan_layout), then the LDS board-point tile of k_eval_gram.
 extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int rank, int world, tscm_solver **out)
 {
     if (!out) return fail(TSCM_E_INVALID, "out is NULL");
@@ -493,116 +456,16 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     tscm_solver *s = sp.get();
     s->device = device;
     s->rank = rank; s->world = world;
-    // ---- frame ownership ------------------------------------------------------------------------
-    std::vector<int> owner;
-    shard_owner(p, world, owner);
-    int b0 = 0, b1 = 0;
-    {
-        while (b0 < p->n_boards && owner[b0] < rank) ++b0;
-        b1 = b0;
-        while (b1 < p->n_boards && owner[b1] == rank) ++b1;
-    }
-    s->b0 = b0; s->B_total = p->n_boards;
-    s->C = p->n_cameras; s->B = b1 - b0; s->n_points = p->n_points; s->mono = p->mono != 0;
+    s->C = p->n_cameras; s->n_points = p->n_points; s->mono = p->mono != 0;
     s->n_pad = 16 * s->C;
     s->h_cam_rt = p->cam_rt; s->h_intr = p->intr; s->h_board_rt = p->board_rt;
     HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
     s->own_stream = s->stream;
-    const int C = s->C, B = s->B;
+    const int C = s->C;
 
-    // ---- whole-problem facts (identical on every rank) -------------------------------------------
-    std::vector<unsigned char> cam_const(C, 0), cam_active(C, 0);
-    for (int m = 0; m < C; ++m) cam_const[m] = (p->mono || (p->cam_pose_constant && p->cam_pose_constant[m])) ? 1 : 0;
-    std::vector<unsigned char> pair_present((size_t)C * C, 0);
-    long N_total = 0;
-    {
-        // cameras per board, then every camera pair (mi <= mj) that shares a board
-        std::vector<int> ptr(p->n_boards + 1, 0), cams;
-        for (int v = 0; v < p->n_views; ++v) if (p->view_count[v] > 0) ptr[p->view_board[v] + 1]++;
-        for (int b = 0; b < p->n_boards; ++b) ptr[b + 1] += ptr[b];
-        cams.resize(ptr[p->n_boards]);
-        std::vector<int> fill(p->n_boards, 0);
-        for (int v = 0; v < p->n_views; ++v) {
-            if (p->view_count[v] <= 0) continue;
-            const int b = p->view_board[v];
-            cams[ptr[b] + fill[b]++] = p->view_camera[v];
-            cam_active[p->view_camera[v]] = 1;
-            N_total += p->view_count[v];
-        }
-        for (int b = 0; b < p->n_boards; ++b)
-            for (int i = ptr[b]; i < ptr[b + 1]; ++i)
-                for (int j = ptr[b]; j < ptr[b + 1]; ++j) {
-                    const int mi = std::min(cams[i], cams[j]), mj = std::max(cams[i], cams[j]);
-                    pair_present[(size_t)mi * C + mj] = 1;
-                }
-    }
-    s->N_total = N_total;
-
-    // ---- device view order: this rank's views with corners, sorted by (camera, board) -----------
-    std::vector<int> order;
-    for (int v = 0; v < p->n_views; ++v) if (p->view_count[v] > 0 && p->view_board[v] >= b0 && p->view_board[v] < b1) order.push_back(v);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        if (p->view_camera[a] != p->view_camera[b]) return p->view_camera[a] < p->view_camera[b];
-        return p->view_board[a] < p->view_board[b];
-    });
-    for (size_t i = 1; i < order.size(); ++i)
-        if (p->view_camera[order[i]] == p->view_camera[order[i - 1]] && p->view_board[order[i]] == p->view_board[order[i - 1]])
-            return fail(TSCM_E_INVALID, "two views with the same (camera, board)");
-    const int V = (int)order.size();
-    // ---- device board order: boards grouped by camera-set signature (number of views, then the cameras), unseen boards
-    // last.  The Schur kernels work on chunks of boards of ONE signature; with this numbering a chunk is a contiguous
-    // range of boards AND of record slots, so its kernels derive every address from one small descriptor instead of
-    // chasing per-board index tables (each dependent global load costs about a microsecond at the head of a kernel).
-    std::vector<int> dev_board(B, -1);          // caller's board (relative to b0) -> device board
-    {
-        std::vector<int> ptr(B + 1, 0), cams(V);
-        for (int i = 0; i < V; ++i) ptr[p->view_board[order[i]] - b0 + 1]++;
-        for (int b = 0; b < B; ++b) ptr[b + 1] += ptr[b];
-        std::vector<int> fill(B, 0);
-        for (int i = 0; i < V; ++i) { const int b = p->view_board[order[i]] - b0; cams[ptr[b] + fill[b]++] = p->view_camera[order[i]]; }   // `order` is camera-major: sorted
-        std::vector<int> perm(B);
-        std::iota(perm.begin(), perm.end(), 0);
-        std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) {
-            const int nx = ptr[x + 1] - ptr[x], ny = ptr[y + 1] - ptr[y];
-            if ((nx == 0) != (ny == 0)) return ny == 0;           // boards without views go last
-            if (nx != ny) return nx < ny;
-            for (int k = 0; k < nx; ++k) if (cams[ptr[x] + k] != cams[ptr[y] + k]) return cams[ptr[x] + k] < cams[ptr[y] + k];
-            return false;
-        });
-        s->board_perm = perm;
-        for (int i = 0; i < B; ++i) dev_board[perm[i]] = i;
-    }
-    // views of one camera sorted by device board
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        if (p->view_camera[a] != p->view_camera[b]) return p->view_camera[a] < p->view_camera[b];
-        return dev_board[p->view_board[a] - b0] < dev_board[p->view_board[b] - b0];
-    });
-    s->V = V; s->dev2orig = order;
-    std::vector<int> view_cam(V), view_board(V), view_obs(V), view_count(V);
-    long N = 0;
-    for (int i = 0; i < V; ++i) {
-        const int v = order[i];
-        view_cam[i] = p->view_camera[v]; view_board[i] = dev_board[p->view_board[v] - b0]; view_count[i] = p->view_count[v];   // device board index
-        view_obs[i] = (int)N; N += p->view_count[v];
-    }
-    if (N > 0x7fffffffL) return fail(TSCM_E_UNSUPPORTED, "more than 2^31 corners");
-    // the Gram kernels address observations, per-view constants and records with 32-bit buffer offsets and
-    // park the stores of idle lanes at offset 0xffffe000, which must lie beyond the end of every buffer
-    if ((unsigned long long)N * sizeof(double) >= 0xffffe000ull || (unsigned long long)V * kRec * sizeof(double) >= 0xffffe000ull)
-        return fail(TSCM_E_UNSUPPORTED, "problem too large for 32-bit buffer offsets (more than 3.7 M views or 536 M corners on one GPU)");
-    s->N = (int)N;
-    s->h_view_obs = view_obs; s->h_view_count = view_count; s->h_view_cam = view_cam; s->h_view_board = view_board;
-    std::vector<double> u((size_t)N), w((size_t)N);
-    for (int i = 0; i < V; ++i) {
-        const int v = order[i];
-        std::memcpy(u.data() + view_obs[i], p->obs_u + p->view_offset[v], sizeof(double) * view_count[i]);
-        std::memcpy(w.data() + view_obs[i], p->obs_v + p->view_offset[v], sizeof(double) * view_count[i]);
-    }
-
-    // ---- chunks of views (one wave each), never straddling a camera ----------------------------
-    // one round of resident waves: LDS admits floor(160 KiB / lds_eval) single-wave workgroups per CU
-    // Jacobian tile geometry: HV rows (multiple of 8 covering min(64, n) corners -- the MFMA loops consume the k-steps
-    // of 4 rows in PAIRS, so the tile holds an even number of them; u-rows and v-rows take turns), pitch HV + 2
+    // ---- device setup: LDS and occupancy of the Gram and Schur kernels ---------------------------
+    // Jacobian tile geometry of k_eval_gram: HV rows (multiple of 8 covering min(64, n) corners -- the MFMA loops consume the
+    // k-steps of 4 rows in PAIRS, so the tile holds an even number of them; u-rows and v-rows take turns), pitch HV + 2
     // (= 2 * odd: the 16 columns x 2 rows of a 32-lane ds_read_b64 group then hit 32 distinct bank pairs)
     const int half_rows = 8 * ((std::min(64, p->n_points) + 7) / 8);
     const int rp = half_rows + 2;      // = 2 * odd (half_rows is a multiple of 8)
@@ -619,6 +482,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     if (lds_eval4 > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board with too many corners for the Gram kernel's LDS (more than about 2,000)");
     if (lds_eval4 > 64 * 1024)
         for (EvalKernel k : { eval4, eval4r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
+    // the Gram kernels' view chunks are sized for one round of resident waves: LayoutDevice
     int wgs_per_cu = 0;         // resident workgroups per CU (register- and LDS-limited)
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, reinterpret_cast<const void *>(eval4), 256, lds_eval4));
 #ifdef TSCM_EVAL_WAVES          // occupancy experiments: chunk tables for this many waves per SIMD
@@ -628,287 +492,97 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
 #endif
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
-    const int target_chunks = std::max(64, prop.multiProcessorCount * waves_per_cu - 4 * C);
-    const int per_chunk = std::max(1, (V + target_chunks - 1) / target_chunks);
-    std::vector<int> chunk_vb, chunk_ve, chunk_cam, cam_chunk_ptr(C + 1, 0);
-    {
-        int i = 0;
-        for (int m = 0; m < C; ++m) {
-            cam_chunk_ptr[m] = (int)chunk_vb.size() / 4;     // in workgroups
-            int e = i;
-            while (e < V && view_cam[e] == m) ++e;
-            for (int b0 = i; b0 < e; b0 += per_chunk) { chunk_vb.push_back(b0); chunk_ve.push_back(std::min(e, b0 + per_chunk)); chunk_cam.push_back(m); }
-            while (chunk_vb.size() % 4) { chunk_vb.push_back(e); chunk_ve.push_back(e); chunk_cam.push_back(m); }   // empty chunks: whole workgroups per camera
-            i = e;
-        }
-        cam_chunk_ptr[C] = (int)chunk_vb.size() / 4;
+    const void *schur[4][2] = { {}, { reinterpret_cast<const void *>(k_schur_gram<1>), reinterpret_cast<const void *>(k_schur_gram<1, true>) },
+                                { reinterpret_cast<const void *>(k_schur_gram<2>), reinterpret_cast<const void *>(k_schur_gram<2, true>) },
+                                { reinterpret_cast<const void *>(k_schur_gram<3>), reinterpret_cast<const void *>(k_schur_gram<3, true>) } };
+    for (int nv = 1; nv <= 3; ++nv) {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident[nv], schur[nv][0], 256, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident_ride[nv], schur[nv][1], 256, 0));
+        s->schur_resident[nv] *= prop.multiProcessorCount; s->schur_resident_ride[nv] *= prop.multiProcessorCount;
     }
-    // ---- board -> views (device order => increasing camera) --------------------------------------
-    std::vector<int> bv_ptr(B + 1, 0), bv_idx(V);
-    for (int i = 0; i < V; ++i) bv_ptr[view_board[i] + 1]++;
-    for (int b = 0; b < B; ++b) bv_ptr[b + 1] += bv_ptr[b];
-    {
-        std::vector<int> fill(B, 0);
-        for (int i = 0; i < V; ++i) { const int b = view_board[i]; bv_idx[bv_ptr[b] + fill[b]++] = i; }
-    }
-    // records are stored board-major: slot q of bv order <-> device view bv_idx[q]
-    std::vector<int> view_slot(V), slot_cam(V), slot_view(V), slot_board(V);
-    for (int q = 0; q < V; ++q) { view_slot[bv_idx[q]] = q; slot_cam[q] = view_cam[bv_idx[q]]; slot_view[q] = bv_idx[q]; slot_board[q] = view_board[bv_idx[q]]; }
-    s->h_view_slot = view_slot;
-    // ---- Schur-complement work lists ------------------------------------------------------------
-    // camera-pair blocks ("bids") of T: every pair that shares a board on ANY rank, in lexicographic order
-    std::vector<int> bid_of(C * C, -1), bid_mi, bid_mj;
-    for (int mi = 0; mi < C; ++mi)
-        for (int mj = mi; mj < C; ++mj)
-            if (pair_present[(size_t)mi * C + mj]) { bid_of[mi * C + mj] = (int)bid_mi.size(); bid_mi.push_back(mi); bid_mj.push_back(mj); }
-    auto get_bid = [&](int mi, int mj) { return bid_of[mi * C + mj]; };      // views of a board are sorted by camera: mi <= mj
-    // boards grouped by camera-set signature (views of a board are already sorted by camera)
-    std::vector<int> order_b;
-    for (int b = 0; b < B; ++b) if (bv_ptr[b + 1] > bv_ptr[b]) order_b.push_back(b);
-    auto sig_less = [&](int x, int y) {
-        const int nx = bv_ptr[x + 1] - bv_ptr[x], ny = bv_ptr[y + 1] - bv_ptr[y];
-        if (nx != ny) return nx < ny;
-        for (int k = 0; k < nx; ++k) {
-            const int cx = slot_cam[bv_ptr[x] + k], cy = slot_cam[bv_ptr[y] + k];
-            if (cx != cy) return cx < cy;
-        }
-        return false;
-    };
-    std::stable_sort(order_b.begin(), order_b.end(), sig_less);
-    // Every partial tile belongs to one camera-pair block; tiles of a block are numbered contiguously
-    // (two passes: count, then assign) so that k_T_reduce streams them without indirection.
-    struct ChunkT { int begin, end, nv, bid[6]; };
-    std::vector<ChunkT> bchunks;
-    std::vector<int> sslot, sboard, pair_i, pair_j, pair_board;
-    struct PChunk { int begin, end, bid; };
-    std::vector<PChunk> pchunks;
-    struct FbPair { int q1, q2, board; };
-    std::vector<std::vector<FbPair>> fb_pairs;      // fallback pairs per bid (boards with > 3 views)
-    {
-        size_t fast_boards = 0;
-        for (int b : order_b) if (bv_ptr[b + 1] - bv_ptr[b] <= 3) ++fast_boards;
-        // chunks of 16 .. kChunkBoards boards (k_schur_gram: 4 waves x groups of 4 boards), about 512 of them on big problems
-        // The Schur kernels stream the records and a CU sustains only its share of the memory system, so the CUs must
-        // get equal numbers of workgroups: two per CU on big problems (a multiple of the CU count), never more than
-        // kChunkBoards boards each, at least 16 (four waves of one group of four).
-        const int target_bchunks = 2 * std::max(1, prop.multiProcessorCount);
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident[1], reinterpret_cast<const void *>(k_schur_gram<1>), 256, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident[2], reinterpret_cast<const void *>(k_schur_gram<2>), 256, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident[3], reinterpret_cast<const void *>(k_schur_gram<3>), 256, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident_ride[1], reinterpret_cast<const void *>(k_schur_gram<1, true>), 256, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident_ride[2], reinterpret_cast<const void *>(k_schur_gram<2, true>), 256, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident_ride[3], reinterpret_cast<const void *>(k_schur_gram<3, true>), 256, 0));
-        for (int nv = 1; nv <= 3; ++nv) { s->schur_resident[nv] *= prop.multiProcessorCount; s->schur_resident_ride[nv] *= prop.multiProcessorCount; }
-        const int per_bchunk = std::min<int>(kChunkBoards, std::max<int>(16, (int)((fast_boards + target_bchunks - 1) / target_bchunks)));
-        size_t i = 0;
-        while (i < order_b.size()) {
-            size_t e = i + 1;
-            while (e < order_b.size() && !sig_less(order_b[i], order_b[e]) && !sig_less(order_b[e], order_b[i])) ++e;
-            const int b0 = order_b[i];
-            const int nv = bv_ptr[b0 + 1] - bv_ptr[b0];
-            if (nv <= 3) {
-                for (size_t c0 = i; c0 < e; c0 += per_bchunk) {
-                    const size_t c1 = std::min(e, c0 + per_bchunk);
-                    ChunkT ch{};
-                    ch.begin = (int)sslot.size();
-                    for (size_t k = c0; k < c1; ++k) { sslot.push_back(bv_ptr[order_b[k]]); sboard.push_back(order_b[k]); }
-                    ch.end = (int)sslot.size();
-                    ch.nv = nv;
-                    int t = 0;
-                    for (int p1 = 0; p1 < nv; ++p1)
-                        for (int p2 = p1; p2 < nv; ++p2) ch.bid[t++] = get_bid(slot_cam[bv_ptr[b0] + p1], slot_cam[bv_ptr[b0] + p2]);
-                    bchunks.push_back(ch);
-                }
-            } else {
-                for (size_t k = i; k < e; ++k) {
-                    const int b = order_b[k];
-                    for (int q1 = bv_ptr[b]; q1 < bv_ptr[b + 1]; ++q1)
-                        for (int q2 = q1; q2 < bv_ptr[b + 1]; ++q2) {
-                            const int bid = get_bid(slot_cam[q1], slot_cam[q2]);
-                            if ((int)fb_pairs.size() <= bid) fb_pairs.resize(bid + 1);
-                            fb_pairs[bid].push_back({ q1, q2, b });
-                        }
-                }
-            }
-            i = e;
-        }
-        size_t n_fb = 0;
-        for (auto &v : fb_pairs) n_fb += v.size();
-        const int per_pchunk = std::max<int>(1, (int)((n_fb + 511) / 512));
-        for (size_t bid = 0; bid < fb_pairs.size(); ++bid) {
-            const int base = (int)pair_i.size();
-            for (auto &pr : fb_pairs[bid]) { pair_i.push_back(pr.q1); pair_j.push_back(pr.q2); pair_board.push_back(pr.board); }
-            const int end = (int)pair_i.size();
-            for (int b0 = base; b0 < end; b0 += per_pchunk) pchunks.push_back({ b0, std::min(end, b0 + per_pchunk), (int)bid });
-        }
-    }
-    const int n_bids = (int)bid_mi.size();
-    std::vector<int> bid_part_ptr(n_bids + 1, 0);
-    for (auto &ch : bchunks) for (int t = 0; t < ch.nv * (ch.nv + 1) / 2; ++t) bid_part_ptr[ch.bid[t] + 1]++;
-    for (auto &pc : pchunks) bid_part_ptr[pc.bid + 1]++;
-    for (int b = 0; b < n_bids; ++b) bid_part_ptr[b + 1] += bid_part_ptr[b];
-    const int n_tiles = bid_part_ptr[n_bids];
-    std::vector<int> next_tile(bid_part_ptr.begin(), bid_part_ptr.end() - 1);
-    std::vector<int> bc_begin, bc_end, bc_nv, bc_tile, pc_begin, pc_end, pc_tile;
-    for (auto &ch : bchunks) {
-        bc_begin.push_back(ch.begin); bc_end.push_back(ch.end); bc_nv.push_back(ch.nv);
-        for (int t = 0; t < 6; ++t) bc_tile.push_back(t < ch.nv * (ch.nv + 1) / 2 ? next_tile[ch.bid[t]]++ : -1);
-    }
-    for (auto &pc : pchunks) { pc_begin.push_back(pc.begin); pc_end.push_back(pc.end); pc_tile.push_back(next_tile[pc.bid]++); }
-    const size_t n_pairs = pair_i.size();
+    s->n_cu = std::max(1, prop.multiProcessorCount);
 
-    // ---- upload --------------------------------------------------------------------------------
+    // ---- layout ----------------------------------------------------------------------------------
+    const Layout &L = s->L;
+    {
+        LayoutDevice dev;
+        dev.n_cu = prop.multiProcessorCount; dev.waves_per_cu = waves_per_cu;
+        std::string err;
+        if (int rc = plan_layout(p, rank, world, dev, s->L, err)) return fail(rc, err);
+    }
+    s->B = L.B; s->V = L.V; s->N = L.N;
+    const int B = L.B, V = L.V, N = L.N;
+    s->lds_bs = sizeof(double) * (size_t)(L.bs_threads == 256 ? BsGeom<256>::kLds : BsGeom<128>::kLds);
+    for (const void *k : { reinterpret_cast<const void *>(k_backsub_prep<128>), reinterpret_cast<const void *>(k_backsub_prep<256>) })
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bs));
+
+    // ---- upload: the observations gathered into device order, the layout's tables -------------------
+    std::vector<double> u((size_t)N), w((size_t)N);
+    for (int i = 0; i < V; ++i) {
+        const int v = L.dev2orig[i];
+        std::memcpy(u.data() + L.view_obs[i], p->obs_u + p->view_offset[v], sizeof(double) * L.view_count[i]);
+        std::memcpy(w.data() + L.view_obs[i], p->obs_v + p->view_offset[v], sizeof(double) * L.view_count[i]);
+    }
+    const std::vector<double> bxy(p->board_xy, p->board_xy + 2 * (size_t)p->n_points);
+    auto int4s = [](const std::vector<Int4> &h) {
+        std::vector<int4> d(h.size());
+        for (size_t i = 0; i < h.size(); ++i) d[i] = make_int4(h[i].x, h[i].y, h[i].z, h[i].w);
+        return d;
+    };
+    const std::vector<int4> chunk_desc = int4s(L.chunk_desc), bc_desc = int4s(L.bc_desc);
+    const std::vector<short> bid_lut(L.bid_of.begin(), L.bid_of.end());
     DevProblem &P = s->P;
     DevState &S = s->S;
-    P.C = C; P.B = B; P.n_points = p->n_points; P.V = V; P.N = (int)N; P.n_pad = s->n_pad;
+    P.C = C; P.B = B; P.n_points = p->n_points; P.V = V; P.N = N; P.n_pad = s->n_pad;
     P.rank = rank; P.world = world;
     P.rp = rp; P.half = half_rows; P.lds_wave = (int)(lds_eval_bytes / sizeof(double)); P.g4_per = g4.per;
-    P.n_chunks = (int)chunk_vb.size(); P.n_pairs = (int)n_pairs; P.n_pchunks = (int)pc_begin.size(); P.n_bids = n_bids;
-    P.n_bchunks = (int)bc_begin.size(); P.n_tiles = n_tiles;
-    std::vector<double> bxy(p->board_xy, p->board_xy + 2 * (size_t)p->n_points);
-    int rc;
-    if ((rc = dev_upload(s, &P.board_xy, bxy))) return rc;
-    if ((rc = dev_upload(s, &P.view_cam, view_cam))) return rc;
-    if ((rc = dev_upload(s, &P.view_board, view_board))) return rc;
-    if ((rc = dev_upload(s, &P.view_obs, view_obs))) return rc;
-    if ((rc = dev_upload(s, &P.view_count, view_count))) return rc;
-    if ((rc = dev_upload(s, &P.obs_u, u))) return rc;
-    if ((rc = dev_upload(s, &P.obs_v, w))) return rc;
-    if ((rc = dev_upload(s, &P.chunk_vb, chunk_vb))) return rc;
-    if ((rc = dev_upload(s, &P.chunk_ve, chunk_ve))) return rc;
-    if ((rc = dev_upload(s, &P.chunk_cam, chunk_cam))) return rc;
-    {
-        // the same per chunk in ONE 16-byte record (+ the observation offset of its first view): the head of k_eval_gram4 is
-        // control block + descriptor, then the data
-        std::vector<int4> cd(chunk_vb.size());
-        for (size_t q = 0; q < cd.size(); ++q) cd[q] = make_int4(chunk_cam[q], chunk_vb[q], chunk_ve[q], chunk_vb[q] < V ? view_obs[chunk_vb[q]] : 0);
-        if ((rc = dev_upload(s, &P.chunk_desc, cd))) return rc;
-    }
-    if ((rc = dev_upload(s, &P.cam_chunk_ptr, cam_chunk_ptr))) return rc;
-    for (int q = 0; q <= kMaxCamLds; ++q) P.cam_wg[q] = cam_chunk_ptr[std::min(q, C)];
-    if ((rc = dev_upload(s, &P.bv_ptr, bv_ptr))) return rc;
-    if ((rc = dev_upload(s, &P.view_slot, view_slot))) return rc;
-    if ((rc = dev_upload(s, &P.slot_cam, slot_cam))) return rc;
-    if ((rc = dev_upload(s, &P.slot_view, slot_view))) return rc;
-    if ((rc = dev_upload(s, &P.slot_board, slot_board))) return rc;
-    {
-        std::vector<int> slow;
-        for (int b : order_b) if (bv_ptr[b + 1] - bv_ptr[b] > 3) slow.push_back(b);
-        P.n_slow = (int)slow.size();
-        if ((rc = dev_upload(s, &P.slow_boards, slow))) return rc;
-        // chunks are in signature order, i.e. sorted by views per board: one launch of k_schur_gram<NV> per NV present
-        int max_boards = 1;
-        for (size_t c = 0; c < bchunks.size(); ++c) {
-            const int nv = bchunks[c].nv;
-            if (s->nv_chunks[nv]++ == 0) s->nv_chunk0[nv] = (int)c;
-            max_boards = std::max(max_boards, bchunks[c].end - bchunks[c].begin);
-        }
-        if (max_boards > kChunkBoards) return fail(TSCM_E_UNSUPPORTED, "internal error: board chunk larger than kChunkBoards");
-        s->lds_gram = 0;
-        // groups of 16 boards while they all fit the chip at once (5 workgroups per CU), groups of 32 beyond that
-        s->bs_threads = (B + 15) / 16 > 5 * std::max(1, prop.multiProcessorCount) * 3 / 2 ? 256 : 128;
-        // ... and groups of 32 (256 threads, the reduced solve's workgroup shape) wherever the back-substitution can ride
-        // in the reduced solve's launch (up to 8 cameras: k_solve_nd<.., true>)
-        if (C <= kMaxCamLds && n_bids > 0) s->bs_threads = 256;
-        s->lds_bs = sizeof(double) * (size_t)(s->bs_threads == 256 ? BsGeom<256>::kLds : BsGeom<128>::kLds);
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_backsub_prep<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bs));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_backsub_prep<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_bs));
-    }
-    if ((rc = dev_upload(s, &P.pair_i, pair_i))) return rc;
-    if ((rc = dev_upload(s, &P.pair_j, pair_j))) return rc;
-    if ((rc = dev_upload(s, &P.pc_begin, pc_begin))) return rc;
-    if ((rc = dev_upload(s, &P.pc_end, pc_end))) return rc;
-    if ((rc = dev_upload(s, &P.pc_tile, pc_tile))) return rc;
-    if ((rc = dev_upload(s, &P.bid_part_ptr, bid_part_ptr))) return rc;
-    static_assert(kSmallBids >= kMaxCamLds * (kMaxCamLds + 1) / 2, "every camera pair of a rig the register/LDS solver takes");
-    for (int b = 0; b <= kSmallBids; ++b) P.bid_part_small[b] = bid_part_ptr[std::min(b, n_bids)];
-    if ((rc = dev_upload(s, &P.sslot, sslot))) return rc;
-    if ((rc = dev_upload(s, &P.sboard, sboard))) return rc;
-    if ((rc = dev_upload(s, &P.pair_board, pair_board))) return rc;
-    if ((rc = dev_upload(s, &P.bc_begin, bc_begin))) return rc;
-    if ((rc = dev_upload(s, &P.bc_end, bc_end))) return rc;
-    if ((rc = dev_upload(s, &P.bc_nv, bc_nv))) return rc;
-    if ((rc = dev_upload(s, &P.bc_tile, bc_tile))) return rc;
-    {
-        // device boards are numbered in signature order, so entry k of the sorted board list IS board k
-        for (size_t k = 0; k < sboard.size(); ++k) if (sboard[k] != (int)k) return fail(TSCM_E_UNSUPPORTED, "internal error: device board order is not the signature order");
-        std::vector<int4> desc(bchunks.size());
-        for (size_t c = 0; c < bchunks.size(); ++c) desc[c] = make_int4(bchunks[c].begin, bchunks[c].end, bv_ptr[bchunks[c].begin], bchunks[c].nv);
-        if ((rc = dev_upload(s, &P.bc_desc, desc))) return rc;
-    }
-    if ((rc = dev_upload(s, &P.bid_mi, bid_mi))) return rc;
-    if ((rc = dev_upload(s, &P.bid_mj, bid_mj))) return rc;
-    {
-        std::vector<short> lut(bid_of.begin(), bid_of.end());
-        if ((rc = dev_upload(s, &P.bid_lut, lut))) return rc;
-    }
-    {
-        std::vector<unsigned char> board_const((size_t)B, 0);
-        if (p->board_pose_constant) for (int i = 0; i < B; ++i) board_const[i] = p->board_pose_constant[b0 + s->board_perm[i]] ? 1 : 0;
-        if ((rc = dev_upload(s, &P.board_const, board_const))) return rc;
-    }
-    P.pair_mask = 0;
-    if (C <= kMaxCamLds)
-        for (int mi = 0; mi < C; ++mi) for (int mj = mi; mj < C; ++mj) if (bid_of[mi * C + mj] >= 0) P.pair_mask |= 1ull << (mi * 8 + mj);
-    s->h_cam_const = cam_const; s->h_cam_active = cam_active; s->h_pair_present = pair_present; s->h_bid_of = bid_of;
-    s->n_cu = std::max(1, prop.multiProcessorCount);
+    P.n_chunks = (int)L.chunk_vb.size(); P.n_pchunks = (int)L.pc_begin.size(); P.n_bids = L.n_bids;
+    P.n_bchunks = (int)L.bc_desc.size(); P.n_tiles = L.n_tiles; P.n_slow = (int)L.slow_boards.size();
+    std::copy(std::begin(L.cam_wg), std::end(L.cam_wg), P.cam_wg);
+    std::copy(std::begin(L.bid_part_small), std::end(L.bid_part_small), P.bid_part_small);
+    P.pair_mask = L.pair_mask;
+    int rc = 0;         // the first failure of a run of uploads / allocations (the rest are skipped)
+    auto up = [&](auto **dst, const auto &h) { if (!rc) rc = dev_upload(s, dst, h); };
+    auto al = [&](auto **dst, size_t n) { if (!rc) rc = dev_alloc(s, dst, n); };
+    up(&P.board_xy, bxy);
+    up(&P.view_cam, L.view_cam); up(&P.view_board, L.view_board); up(&P.view_obs, L.view_obs); up(&P.view_count, L.view_count);
+    up(&P.obs_u, u); up(&P.obs_v, w);
+    up(&P.chunk_vb, L.chunk_vb); up(&P.chunk_ve, L.chunk_ve); up(&P.chunk_cam, L.chunk_cam); up(&P.chunk_desc, chunk_desc);
+    up(&P.cam_chunk_ptr, L.cam_chunk_ptr);
+    up(&P.bv_ptr, L.bv_ptr); up(&P.view_slot, L.view_slot); up(&P.slot_cam, L.slot_cam); up(&P.slot_view, L.slot_view); up(&P.slot_board, L.slot_board);
+    up(&P.slow_boards, L.slow_boards);
+    up(&P.pair_i, L.pair_i); up(&P.pair_j, L.pair_j); up(&P.pc_begin, L.pc_begin); up(&P.pc_end, L.pc_end); up(&P.pc_tile, L.pc_tile);
+    up(&P.bid_part_ptr, L.bid_part_ptr); up(&P.pair_board, L.pair_board); up(&P.bc_tile, L.bc_tile); up(&P.bc_desc, bc_desc);
+    up(&P.bid_lut, bid_lut); up(&P.board_const, L.board_const);
+    // written by build_columns
     s->fixed.assign(C, 0);
-    {
-        unsigned char *q = nullptr;
-        if ((rc = dev_alloc(s, &q, (size_t)s->n_pad))) return rc;
-        P.col_active = q;
-        if ((rc = dev_alloc(s, &q, (size_t)16 * kMaxCam))) return rc;
-        P.col_ctl = q;
-        int *am = nullptr;
-        if ((rc = dev_alloc(s, &am, (size_t)s->n_pad))) return rc;
-        P.act_map = am;
-    }
+    al(&P.col_active, s->n_pad); al(&P.col_ctl, (size_t)16 * kMaxCam); al(&P.act_map, s->n_pad);
 
     for (int k = 0; k < 2; ++k) {
-        if ((rc = dev_alloc(s, &S.cam_rt[k], 6 * (size_t)C))) return rc;
-        if ((rc = dev_alloc(s, &S.intr[k], 9 * (size_t)C))) return rc;
-        if ((rc = dev_alloc(s, &S.board_rt[k], 6 * (size_t)B))) return rc;
-        if ((rc = dev_alloc(s, &S.rec[k], (size_t)kRec * V))) return rc;
-        if ((rc = dev_alloc(s, &S.H[k], 256 * (size_t)C))) return rc;
+        al(&S.cam_rt[k], 6 * (size_t)C); al(&S.intr[k], 9 * (size_t)C); al(&S.board_rt[k], 6 * (size_t)B);
+        al(&S.rec[k], (size_t)kRec * V); al(&S.H[k], 256 * (size_t)C);
     }
-    if ((rc = dev_alloc(s, &s->d_init_cam, 6 * (size_t)C))) return rc;
-    if ((rc = dev_alloc(s, &s->d_init_intr, 9 * (size_t)C))) return rc;
-    if ((rc = dev_alloc(s, &s->d_init_board, 6 * (size_t)B))) return rc;
-    if ((rc = dev_alloc(s, &s->d_start_cam, 6 * (size_t)C))) return rc;
-    if ((rc = dev_alloc(s, &s->d_start_intr, 9 * (size_t)C))) return rc;
-    if ((rc = dev_alloc(s, &s->d_start_board, 6 * (size_t)B))) return rc;
-    if ((rc = dev_alloc(s, &S.board_pc, (size_t)kBoardConst * B))) return rc;
-    if ((rc = dev_alloc(s, &S.cam_pc, (size_t)kCamConst * C))) return rc;
-    if ((rc = dev_alloc(s, &S.vconst, (size_t)kVStride * V))) return rc;
-    for (int k = 0; k < 2; ++k) if ((rc = dev_alloc(s, &S.cconst[k], (size_t)kCStride * C))) return rc;
-    if ((rc = dev_alloc(s, &S.campart, 512 * (size_t)(P.n_chunks / 4)))) return rc;
-    if ((rc = dev_alloc(s, &S.campart2, 512 * (size_t)C))) return rc;
-    if ((rc = dev_alloc(s, &S.H_stage, 256 * (size_t)C + kScal + world))) return rc;
-    if ((rc = dev_alloc(s, &S.s_b, 6 * (size_t)B))) return rc;
-    if ((rc = dev_alloc(s, &S.s_c, (size_t)s->n_pad))) return rc;
-    if ((rc = dev_alloc(s, &S.fac, (size_t)kFac * B))) return rc;
-    if ((rc = dev_alloc(s, &S.pairpart, 256 * (size_t)P.n_tiles))) return rc;
-    if ((rc = dev_alloc(s, &S.T, 256 * (size_t)n_bids))) return rc;
-    if ((rc = dev_alloc(s, &S.t_count, 1))) return rc;
-    HIP_TRY(hipMemset(S.t_count, 0, sizeof(int)));
-    if ((rc = dev_alloc(s, &S.y_flag, 1))) return rc;
-    HIP_TRY(hipMemset(S.y_flag, 0, sizeof(int)));
-    if ((rc = dev_alloc(s, &S.fac_fail, 1))) return rc;
-    HIP_TRY(hipMemset(S.fac_fail, 0, sizeof(int)));
-    if ((rc = dev_alloc(s, &S.yhat, (size_t)s->n_pad))) return rc;
-    S.n_bs_blocks = (B + 15) / 16;                  // (upper bound for the allocation; set to the geometry's group count below)
+    al(&s->d_init_cam, 6 * (size_t)C); al(&s->d_init_intr, 9 * (size_t)C); al(&s->d_init_board, 6 * (size_t)B);
+    al(&s->d_start_cam, 6 * (size_t)C); al(&s->d_start_intr, 9 * (size_t)C); al(&s->d_start_board, 6 * (size_t)B);
+    al(&S.board_pc, (size_t)kBoardConst * B); al(&S.cam_pc, (size_t)kCamConst * C); al(&S.vconst, (size_t)kVStride * V);
+    al(&S.cconst[0], (size_t)kCStride * C); al(&S.cconst[1], (size_t)kCStride * C);
+    al(&S.campart, 512 * (size_t)(P.n_chunks / 4)); al(&S.campart2, 512 * (size_t)C);
+    al(&S.H_stage, 256 * (size_t)C + kScal + world);
+    al(&S.s_b, 6 * (size_t)B); al(&S.s_c, s->n_pad); al(&S.fac, (size_t)kFac * B);
+    al(&S.pairpart, 256 * (size_t)P.n_tiles); al(&S.T, 256 * (size_t)L.n_bids);
+    al(&S.t_count, 1); al(&S.y_flag, 1); al(&S.fac_fail, 1);
+    al(&S.yhat, s->n_pad);
     S.n_st_blocks = (B + 255) / 256;
-    if ((rc = dev_alloc(s, &S.bs_part, 2 * (size_t)S.n_bs_blocks))) return rc;
-    S.n_bs_blocks = (B + s->bs_threads / 8 - 1) / (s->bs_threads / 8);        // groups of k_backsub_prep's geometry
-    if ((rc = dev_alloc(s, &S.st_part, kStStride * (size_t)S.n_st_blocks))) return rc;
-    if ((rc = dev_alloc(s, &S.ctrl, 1))) return rc;
-    if ((rc = dev_alloc(s, &S.ctrl_snap, 1))) return rc;
-    if ((rc = dev_alloc(s, &S.ctl_pub, 1))) return rc;
-    if ((rc = dev_alloc(s, &S.stats_count, 64))) return rc;      // (256 bytes each: lines of their own)
-    if ((rc = dev_alloc(s, &S.stats_flag, 64))) return rc;
+    al(&S.bs_part, 2 * (size_t)((B + 15) / 16));     // (upper bound: groups of 16 boards)
+    al(&S.st_part, kStStride * (size_t)S.n_st_blocks);
+    S.n_bs_blocks = L.n_bs_blocks;
+    al(&S.ctrl, 1); al(&S.ctrl_snap, 1); al(&S.ctl_pub, 1);
+    al(&S.stats_count, 64); al(&S.stats_flag, 64);      // (256 bytes each: lines of their own)
+    if (rc) return rc;
+    for (int *flag : { S.t_count, S.y_flag, S.fac_fail }) HIP_TRY(hipMemset(flag, 0, sizeof(int)));
     HIP_TRY(hipMemset(S.stats_count, 0, 256)); HIP_TRY(hipMemset(S.stats_flag, 0, 256));
     HIP_TRY(hipMemset(S.ctl_pub, 0, sizeof(CtlPub)));
-    HIP_TRY(hipMemset(S.T, 0, sizeof(double) * 256 * (size_t)n_bids));
+    HIP_TRY(hipMemset(S.T, 0, sizeof(double) * 256 * (size_t)L.n_bids));
     HIP_TRY(hipMemset(S.H_stage, 0, sizeof(double) * (256 * (size_t)C + kScal + world)));
     HIP_TRY(hipMemset(S.campart2, 0, sizeof(double) * 512 * (size_t)C));
     HIP_TRY(hipMemset(S.ctrl, 0, sizeof(Ctrl)));
@@ -916,6 +590,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ctrl), sizeof(Ctrl)));
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&s->d_h_ctrl), s->h_ctrl, 0));
 
+    // ---- the evaluation and solve variants -------------------------------------------------------
     s->lds_eval = 4 * lds_eval_bytes;
     s->lds_eval32 = sizeof(double) * (size_t)eval_f32_lds_doubles(p->n_points, g4.ks);
     s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval4r = eval4r;
@@ -939,7 +614,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory, sized for every camera-side column free
         // (held intrinsics only ever take columns away)
         int n_max = 0;
-        for (int m = 0; m < C; ++m) if (cam_active[m]) n_max += cam_const[m] ? kFA - 6 : kFA;
+        for (int m = 0; m < C; ++m) if (L.cam_active[m]) n_max += L.cam_const[m] ? kFA - 6 : kFA;
         const int NN = (n_max + 15) & ~15;
         const size_t lds_max = solve_big_lds_bytes(NN, s->n_pad);
         if ((rc = dev_alloc(s, &S.Abig, (size_t)256 * (NN / 16 + 1) * (NN / 16 + 2) / 2))) return rc;      // packed lower triangle of 16x16 blocks, incl. the rhs block row
@@ -995,7 +670,7 @@ extern "C" int tscm_solver_set_comm(tscm_solver *s, tscm_comm *comm)
 
 extern "C" int tscm_solver_upload_params(tscm_solver *s, const double *cam_rt, const double *intr, const double *board_rt)
 {
-    if (!s || !intr || (!board_rt && s->B_total)) return fail(TSCM_E_INVALID, "NULL argument");
+    if (!s || !intr || (!board_rt && s->L.B_total)) return fail(TSCM_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(s->device));
     std::vector<double> zero(6 * (size_t)s->C, 0.0);
     const double *c = (s->mono || !cam_rt) ? zero.data() : cam_rt;
@@ -1003,7 +678,7 @@ extern "C" int tscm_solver_upload_params(tscm_solver *s, const double *cam_rt, c
     HIP_TRY(hipMemcpyAsync(s->d_init_intr, intr, sizeof(double) * 9 * s->C, hipMemcpyHostToDevice, s->stream));
     // board_rt is the caller's full-length array; this rank keeps the poses of the boards it owns, in device board order
     std::vector<double> brd(6 * (size_t)s->B);
-    for (int i = 0; i < s->B; ++i) std::memcpy(brd.data() + 6 * (size_t)i, board_rt + 6 * ((size_t)s->b0 + s->board_perm[i]), 6 * sizeof(double));
+    for (int i = 0; i < s->B; ++i) std::memcpy(brd.data() + 6 * (size_t)i, board_rt + 6 * ((size_t)s->L.b0 + s->L.board_perm[i]), 6 * sizeof(double));
     if (s->B) HIP_TRY(hipMemcpyAsync(s->d_init_board, brd.data(), sizeof(double) * 6 * s->B, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->have_init = true;
@@ -1266,13 +941,13 @@ static int enqueue_iteration(LmRun &run)
         const int ce = ctl ? ++s->ctl_epoch : 0;          // (ctl: 1 one GPU | 2 communicator, + 4: the initial evaluation's step, + 8: the reductions ride)
         if (ctl & 8) {
             const int ns = P.C * kCamSl + S.n_st_blocks, target = ns * ++s->stats_epoch;
-            if (s->nv_chunks[1]) hipLaunchKernelGGL((k_schur_gram<1, true>), dim3(std::max(ns, s->nv_chunks[1]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->nv_chunk0[1], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[1], ce, target, s->nv_chunks[1]);
-            if (s->nv_chunks[2]) hipLaunchKernelGGL((k_schur_gram<2, true>), dim3(std::max(ns, s->nv_chunks[2]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->nv_chunk0[2], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[2], ce, target, s->nv_chunks[2]);
-            if (s->nv_chunks[3]) hipLaunchKernelGGL((k_schur_gram<3, true>), dim3(std::max(ns, s->nv_chunks[3]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->nv_chunk0[3], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[3], ce, target, s->nv_chunks[3]);
+            if (s->L.nv_chunks[1]) hipLaunchKernelGGL((k_schur_gram<1, true>), dim3(std::max(ns, s->L.nv_chunks[1]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[1], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[1], ce, target, s->L.nv_chunks[1]);
+            if (s->L.nv_chunks[2]) hipLaunchKernelGGL((k_schur_gram<2, true>), dim3(std::max(ns, s->L.nv_chunks[2]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[2], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[2], ce, target, s->L.nv_chunks[2]);
+            if (s->L.nv_chunks[3]) hipLaunchKernelGGL((k_schur_gram<3, true>), dim3(std::max(ns, s->L.nv_chunks[3]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[3], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[3], ce, target, s->L.nv_chunks[3]);
         } else {
-            if (s->nv_chunks[1]) hipLaunchKernelGGL(k_schur_gram<1>, dim3(s->nv_chunks[1] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->nv_chunk0[1], ctl, s->schur_resident[1], ce, 0, s->nv_chunks[1]);
-            if (s->nv_chunks[2]) hipLaunchKernelGGL(k_schur_gram<2>, dim3(s->nv_chunks[2] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->nv_chunk0[2], ctl, s->schur_resident[2], ce, 0, s->nv_chunks[2]);
-            if (s->nv_chunks[3]) hipLaunchKernelGGL(k_schur_gram<3>, dim3(s->nv_chunks[3] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->nv_chunk0[3], ctl, s->schur_resident[3], ce, 0, s->nv_chunks[3]);
+            if (s->L.nv_chunks[1]) hipLaunchKernelGGL(k_schur_gram<1>, dim3(s->L.nv_chunks[1] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[1], ctl, s->schur_resident[1], ce, 0, s->L.nv_chunks[1]);
+            if (s->L.nv_chunks[2]) hipLaunchKernelGGL(k_schur_gram<2>, dim3(s->L.nv_chunks[2] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[2], ctl, s->schur_resident[2], ce, 0, s->L.nv_chunks[2]);
+            if (s->L.nv_chunks[3]) hipLaunchKernelGGL(k_schur_gram<3>, dim3(s->L.nv_chunks[3] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[3], ctl, s->schur_resident[3], ce, 0, s->L.nv_chunks[3]);
         }
         if (P.n_pchunks) hipLaunchKernelGGL(k_pair_gram, dim3(P.n_pchunks), dim3(256), 0, s->stream, P, S);
         if (P.n_bids && !fused_reduce(s)) hipLaunchKernelGGL(k_T_reduce, dim3(P.n_bids * (256 / kTEntries)), dim3(kTEntries * kTSlices), 0, s->stream, P, S);
@@ -1287,20 +962,20 @@ static int enqueue_iteration(LmRun &run)
             // nothing to factor.  k_solve_reduced_big on the empty system runs no panel and writes the zero camera step, the
             // unchanged candidate camera parameters and the linear-solve flag; the back-substitution moves the boards
             hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), solve_big_lds_bytes(0, s->n_pad), s->stream, P, S);
-            if (S.n_bs_blocks && s->bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-            if (S.n_bs_blocks && s->bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
+            if (S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
+            if (S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
             continue;
         }
         if (s->solve_variant == 0 && !s->graph_order) {
             // up to 4 cameras, one dense block: the same launch shape with k_solve_reduced as the solver workgroup
             const int n_prod = fused_reduce(s) ? P.n_bids * (256 / kFusedEntries) : 0;
-            const int n_bs = s->fuse_backsub && s->bs_threads == 256 && S.n_bs_blocks <= s->dense4_resident - 1 - n_prod ? S.n_bs_blocks : 0;       // all of them, or none: see below
+            const int n_bs = s->fuse_backsub && s->L.bs_threads == 256 && S.n_bs_blocks <= s->dense4_resident - 1 - n_prod ? S.n_bs_blocks : 0;       // all of them, or none: see below
             if (n_prod || n_bs)
                 hipLaunchKernelGGL((k_solve_reduced<4, 16, 64, true>), dim3(1 + n_prod + n_bs), dim3(256), std::max(s->lds_dense4, n_bs ? s->lds_bs : (size_t)0), s->stream,
                                    P, S, ++s->t_epoch, s->withhold == 1 ? 1 : 0, n_prod, n_bs, wf);
             else hipLaunchKernelGGL((k_solve_reduced<4, 16, 64>), dim3(1), dim3(256), s->lds_dense4, s->stream, P, S, 0, 0, 0, 0, 0);
-            if (!n_bs && S.n_bs_blocks && s->bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-            if (!n_bs && S.n_bs_blocks && s->bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
+            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
+            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
             continue;
         }
         if (s->solve_variant <= 1) {
@@ -1312,7 +987,7 @@ static int enqueue_iteration(LmRun &run)
             // per iteration -- the riders share the solver workgroup's CU and the rest needs its launch anyway
             const int v = s->nd;
             const int n_prod = fused_reduce(s) ? P.n_bids * (256 / kFusedEntries) : 0;
-            const int n_bs = s->fuse_backsub && s->bs_threads == 256 && S.n_bs_blocks <= s->nd_resident[v] - 1 - n_prod ? S.n_bs_blocks : 0;
+            const int n_bs = s->fuse_backsub && s->L.bs_threads == 256 && S.n_bs_blocks <= s->nd_resident[v] - 1 - n_prod ? S.n_bs_blocks : 0;
             const bool two = s->plan[v].tpt == 2;
             if (n_prod || n_bs) {
                 const size_t lds = std::max(s->lds_nd[v], n_bs ? s->lds_bs : (size_t)0);
@@ -1326,13 +1001,13 @@ static int enqueue_iteration(LmRun &run)
                 if (two) hipLaunchKernelGGL((k_solve_nd<2, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
                 else hipLaunchKernelGGL((k_solve_nd<1, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
             }
-            if (!n_bs && S.n_bs_blocks && s->bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-            if (!n_bs && S.n_bs_blocks && s->bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
+            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
+            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
             continue;
         }
         hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), s->lds_solve, s->stream, P, S);
-        if (S.n_bs_blocks && s->bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-        if (S.n_bs_blocks && s->bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
+        if (S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
+        if (S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
     }
     return enqueue_eval(run, /*cand=*/1, /*init=*/0, /*have_backsub=*/1);
 }
@@ -1483,7 +1158,7 @@ static int robust_rmse(LmRun &run, tscm_summary *sums)
         HIP_TRY(hipStreamSynchronize(s0->stream));
         if (int rc = comm_check(s0->comm)) return rc;
     }
-    for (size_t r = 0; r < run.m.size(); ++r) sums[r].rmse = run.m[r]->N_total ? std::sqrt(sq / (double)run.m[r]->N_total) : 0.0;
+    for (size_t r = 0; r < run.m.size(); ++r) sums[r].rmse = run.m[r]->L.N_total ? std::sqrt(sq / (double)run.m[r]->L.N_total) : 0.0;
     return 0;
 }
 
@@ -1506,7 +1181,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         s->fuse_backsub = !(opt.exec_flags & TSCM_EXEC_SEPARATE_BACKSUB);
         {
             // one GPU with <= 8 cameras (finish_evaluation's LDS fits k_schur_gram's) or a communicator; exactly one Schur kernel per iteration
-            const int n_variants = (s->nv_chunks[1] ? 1 : 0) + (s->nv_chunks[2] ? 1 : 0) + (s->nv_chunks[3] ? 1 : 0);
+            const int n_variants = (s->L.nv_chunks[1] ? 1 : 0) + (s->L.nv_chunks[2] ? 1 : 0) + (s->L.nv_chunks[3] ? 1 : 0);
             // (a grid of several rounds -- config 5 on one GPU: 1256 workgroups, 2.5 rounds -- pays the step in its first round
             // only: the later rounds read the outcome workgroup 0 publishes)
             s->ctl_in_schur = (s->comm || s->P.C <= kMaxCamLds) && s->P.n_slow == 0 && s->P.n_pchunks == 0 && n_variants == 1 &&
@@ -1516,9 +1191,9 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
             // (one GPU, the control step from the finished sums themselves: not behind an all-reduce)
             // -- and a grid of ONE round: every workgroup that takes a reduction block in front of its chunk is resident (they wait for
             // each other), and at config 5 (1256 chunks, 2.5 rounds) the ride costs 2.5 us where it saves 4 at config 4
-            const int nv_used = s->nv_chunks[1] ? 1 : s->nv_chunks[2] ? 2 : 3;
+            const int nv_used = s->L.nv_chunks[1] ? 1 : s->L.nv_chunks[2] ? 2 : 3;
             s->stats_ride = s->ctl_in_schur && !s->comm && s->P.C <= kMaxCamLds && !(opt.exec_flags & TSCM_EXEC_SEPARATE_STATS) &&
-                            std::max(s->P.C * kCamSl + s->S.n_st_blocks, s->nv_chunks[nv_used]) + 1 <= s->schur_resident_ride[nv_used];
+                            std::max(s->P.C * kCamSl + s->S.n_st_blocks, s->L.nv_chunks[nv_used]) + 1 <= s->schur_resident_ride[nv_used];
             s->stats_epoch = 0;
         }
         s->withhold = s->withhold_next; s->withhold_next = 0;
@@ -1622,7 +1297,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         sum->num_unsuccessful_steps = h->num_unsuccessful;
         sum->initial_cost = h->initial_cost;
         sum->final_cost = h->x_cost;
-        sum->n_residual_blocks = (int)s->N_total;
+        sum->n_residual_blocks = (int)s->L.N_total;
         sum->lm_iterations = h->lm_iterations;
         for (int i = 0; i < sum->num_iterations; ++i) {
             const IterLog &l = h->log[i];
@@ -1634,7 +1309,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         std::snprintf(sum->message, sizeof(sum->message), "%s", reason_message(h->term_reason));
         sum->seconds_solve = 1e-8 * (double)(h->t_end - h->t_begin);      // on the device: first to last kernel of the solve
         sum->seconds_total = t1 - t0;                                     // wall time of the call
-        sum->rmse = s->N_total ? std::sqrt(2.0 * h->x_cost / (double)s->N_total) : 0.0;     // cost and N of the WHOLE job
+        sum->rmse = s->L.N_total ? std::sqrt(2.0 * h->x_cost / (double)s->L.N_total) : 0.0;     // cost and N of the WHOLE job
     }
     // with a loss the cost is sum rho / 2, not the squared pixel error: the RMSE is measured at the accepted point instead
     if (s0->loss.kind != TSCM_LOSS_NONE) return robust_rmse(run, sums);
@@ -1675,7 +1350,7 @@ static int download_buffer(tscm_solver *s, int buf, double *cam_rt, double *intr
     if (board_rt && s->B) {
         std::vector<double> brd(6 * (size_t)s->B);
         HIP_TRY(hipMemcpy(brd.data(), s->S.board_rt[buf], sizeof(double) * 6 * s->B, hipMemcpyDeviceToHost));
-        for (int i = 0; i < s->B; ++i) std::memcpy(board_rt + 6 * ((size_t)s->b0 + s->board_perm[i]), brd.data() + 6 * (size_t)i, 6 * sizeof(double));
+        for (int i = 0; i < s->B; ++i) std::memcpy(board_rt + 6 * ((size_t)s->L.b0 + s->L.board_perm[i]), brd.data() + 6 * (size_t)i, 6 * sizeof(double));
     }
     return 0;
 }
@@ -1691,12 +1366,12 @@ extern "C" int tscm_solver_download_params(tscm_solver *s, double *cam_rt, doubl
 // slice in a zeroed full-length device buffer, one sum all-reduce (x + 0 is exact), one download.
 extern "C" int tscm_solver_gather_boards(tscm_solver *s, double *board_rt)
 {
-    if (!s || (!board_rt && s->B_total)) return fail(TSCM_E_INVALID, "NULL argument");
+    if (!s || (!board_rt && s->L.B_total)) return fail(TSCM_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(s->device));
     if (!s->comm_reg || s->world == 1 || s->comm_reg->group) return tscm_solver_download_params(s, nullptr, nullptr, board_rt);   // local groups share the caller's array
-    if (s->B_total == 0) return 0;
+    if (s->L.B_total == 0) return 0;
     double *full = nullptr;
-    const size_t n = 6 * (size_t)s->B_total;
+    const size_t n = 6 * (size_t)s->L.B_total;
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&full), n * sizeof(double)));
     std::unique_ptr<double, void (*)(double *)> guard(full, [](double *q) { (void)hipFree(q); });
     {
@@ -1856,7 +1531,7 @@ extern "C" int tscm_eval_functor(const tscm_problem *p, int device, double *resi
     if ((rc = prepare_eval(s))) return rc;
     const size_t N = (size_t)s->N;
     std::vector<int> corner_view(N);
-    for (int v = 0; v < s->V; ++v) for (int j = 0; j < s->h_view_count[v]; ++j) corner_view[s->h_view_obs[v] + j] = v;
+    for (int v = 0; v < s->V; ++v) for (int j = 0; j < s->L.view_count[v]; ++j) corner_view[s->L.view_obs[v] + j] = v;
     const int *d_cv = nullptr;
     double *d_res = nullptr, *d_Jc = nullptr, *d_Jb = nullptr, *d_Ji = nullptr;
     if ((rc = dev_upload(s, &d_cv, corner_view))) return rc;
@@ -1877,8 +1552,8 @@ extern "C" int tscm_eval_functor(const tscm_problem *p, int device, double *resi
     { long k = 0; for (int v = 0; v < p->n_views; ++v) { orig_row[v] = k; k += p->view_count[v]; } }
     double c = 0.0;
     for (int dv = 0; dv < s->V; ++dv) {
-        const long dst = orig_row[s->dev2orig[dv]], src = s->h_view_obs[dv];
-        const int cnt = s->h_view_count[dv];
+        const long dst = orig_row[s->L.dev2orig[dv]], src = s->L.view_obs[dv];
+        const int cnt = s->L.view_count[dv];
         if (residuals) std::memcpy(residuals + 2 * dst, h_res.data() + 2 * src, sizeof(double) * 2 * cnt);
         if (J_cam) std::memcpy(J_cam + 12 * dst, h_Jc.data() + 12 * src, sizeof(double) * 12 * cnt);
         if (J_board) std::memcpy(J_board + 12 * dst, h_Jb.data() + 12 * src, sizeof(double) * 12 * cnt);
@@ -1931,10 +1606,10 @@ static int eval_normal_equations(const tscm_problem *p, int device, const tscm_o
         // the view's record: W = E^T [F | r] (14 columns x 6 rows, column-major), E = E^T E_wb (3 columns x 6 rows); the
         // t_b x t_b block of E^T E follows from the t_c columns of W and the camera rotation (tb_tb), the block above
         // the diagonal by symmetry -- what the device-side consumers do
-        const double *rw = rec.data() + (size_t)kRecW * s->h_view_slot[dv];
-        const double *re = rec.data() + (size_t)kRecW * s->V + (size_t)kRecE * s->h_view_slot[dv];
-        const double *Rc = cc.data() + (size_t)kCStride * s->h_view_cam[dv];
-        const int b = s->b0 + s->board_perm[s->h_view_board[dv]], ov = s->dev2orig[dv];
+        const double *rw = rec.data() + (size_t)kRecW * s->L.view_slot[dv];
+        const double *re = rec.data() + (size_t)kRecW * s->V + (size_t)kRecE * s->L.view_slot[dv];
+        const double *Rc = cc.data() + (size_t)kCStride * s->L.view_cam[dv];
+        const int b = s->L.b0 + s->L.board_perm[s->L.view_board[dv]], ov = s->L.dev2orig[dv];
         for (int i = 0; i < 6; ++i) {
             if (board_gram)
                 for (int j = 0; j < 6; ++j) {
@@ -2028,7 +1703,7 @@ extern "C" int tscm_reprojection_error(const tscm_problem *p, int device, double
     std::vector<double> err(s->C, 0.0);
     std::vector<long> cnt(s->C, 0);
     double sq = 0.0;
-    for (int v = 0; v < s->V; ++v) { err[s->h_view_cam[v]] += e[v]; cnt[s->h_view_cam[v]] += s->h_view_count[v]; sq += q[v]; }
+    for (int v = 0; v < s->V; ++v) { err[s->L.view_cam[v]] += e[v]; cnt[s->L.view_cam[v]] += s->L.view_count[v]; sq += q[v]; }
     double tot = 0.0; long n = 0;
     for (int m = 0; m < s->C; ++m) { tot += err[m]; n += cnt[m]; if (per_camera_mean) per_camera_mean[m] = cnt[m] ? err[m] / (double)cnt[m] : 0.0; }
     if (global_mean) *global_mean = n ? tot / (double)n : 0.0;
