@@ -29,6 +29,7 @@
 #include "tscm_fastmath.h"
 #include "tscm_nd_plan.h"
 #include "tscm_layout.h"
+#include "tscm_exec_plan.h"
 
 namespace tscm {
 
@@ -59,7 +60,6 @@ constexpr int kCStride = 72;       // doubles per camera record in cconst: 48 do
 constexpr int kCst = 80;           // LDS constant block: [0,27) view, [27,75) camera
 constexpr int kScal = 8;           // scalars appended to H_stage
 constexpr int kStStride = 16;      // doubles between the board-statistics partials of two workgroups: a 128-byte line each (written by ONE workgroup: see k_schur_gram<NV, true>)
-constexpr int kCamSl = 16;         // the per-camera tile reduction runs in slices of 32 of the 512 raw entries: C * kCamSl workgroups
 constexpr int kMaxLog = 256;
 
 // phase stamps of the fused kernels (make PHASES=1: -DTSCM_PHASE_PROFILE; s_memrealtime, 10 ns ticks; one line per
@@ -1628,8 +1628,10 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
     PHASE_STAMP(tsk);
     // head of the kernel: the control block and the chunk descriptor travel together (one memory round trip), every
     // other address follows from them arithmetically -- the second round trip already brings the data
-    // (ctl & 4: the evaluation whose step is taken here is the solve's INITIAL one -- IterationZero: no back-substitution behind it,
+    // (kCtlInit: the evaluation whose step is taken here is the solve's INITIAL one -- IterationZero: no back-substitution behind it,
     // the Jacobi scaling of the camera columns written by the extra workgroup)
+    // (the bits of ctl: tscm_exec_plan.h; decoded by shifts, which is the code the kernel was tuned with)
+    static_assert(kCtlInit == 1 << 2 && kCtlWithhold == 1 << 4 && (kCtlOneGpu | kCtlComm) == 3, "k_schur_gram's decode of ctl");
     const int ctl_init = (ctl >> 2) & 1, withhold = (ctl >> 4) & 1;      // (withhold: fault injection, tscm_solver_debug_withhold_handoff(s, 3))
     ctl &= 3;
     const int n_stats = RIDE ? P.C * kCamSl + S.n_st_blocks : 0;
@@ -1999,7 +2001,7 @@ __global__ __launch_bounds__(256) void k_pair_gram(DevProblem P, DevState S)
     S.pairpart[(size_t)256 * P.pc_tile[pc] + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
 }
 
-constexpr int kTEntries = 64, kTSlices = 16;
+constexpr int kTEntries = 64;       // (kTSlices: tscm_exec_plan.h)
 // block blk of a (n_bids * 256 / ENTRIES)-block grid of ENTRIES * kTSlices threads, partial tiles [cb, ce) of its
 // camera-pair block; the summation order of an entry depends on kTSlices only, so every geometry produces the same bits
 template <int ENTRIES>
@@ -2126,7 +2128,6 @@ __device__ __forceinline__ void reduced_solution_tail(const DevProblem &P, const
 // ---------------------------------------------------------------------------------------------
 // Reduced camera system (DenseSchurComplementSolver), up to kMaxCamLds cameras: k_solve_nd (tscm_solve_nd.h).
 // ---------------------------------------------------------------------------------------------
-constexpr int kFusedEntries = 256 / kTSlices;        // fused T reduction: 16 entries x 16 slices = the solver's 256 threads
 // epoch: 1, 2, ... = the number of fused launches of this solve so far, this one included (the host resets the
 // counter to zero in front of every solve).  The arrival counter is MONOTONIC: a launch waits for epoch * producers,
 // so late arrivals of a launch that was given up on can never be mistaken for this launch's.

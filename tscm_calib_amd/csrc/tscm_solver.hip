@@ -149,34 +149,22 @@ struct tscm_solver {
     Ctrl *h_ctrl = nullptr;             // pinned
     Ctrl *d_h_ctrl = nullptr;           // ... and its address on the device (k_finish_solve writes the control block there itself)
     size_t lds_eval = 0, lds_eval32 = 0, lds_solve = 0, lds_gram = 0, lds_bs = 0;
-    bool fuse_reduce = true;            // this solve: k_T_reduce rides in the reduced solve's launch (tscm_options.exec_flags & TSCM_EXEC_SEPARATE_T_REDUCE clears it)
-    bool fuse_backsub = true;           // this solve: k_backsub_prep rides in it too (TSCM_EXEC_SEPARATE_BACKSUB clears it)
-    bool ctl_in_schur = false;          // this solve: the control step of a candidate's evaluation is taken in the head of the next k_schur_gram
-    int schur_resident_ride[4] = { 0, 0, 0, 0 };   // ... of k_schur_gram<NV, true>
-    int schur_resident[4] = { 0, 0, 0, 0 };   // workgroups of k_schur_gram<NV> that are resident at once (occupancy x CUs): the first round of its grid
+    ExecDevice dev;                     // residency figures of the launches whose workgroups wait for each other (tscm_exec_plan.h)
+    ExecPlan xp;                        // the launch sequence of the solve in progress (plan_exec)
     int ctl_epoch = 0;                  // control steps taken in k_schur_gram's head in this solve so far
-    bool stats_ride = false;            // this solve: the reductions behind a candidate's evaluation are the first workgroups of the next k_schur_gram (k_schur_gram<NV, true>)
     int stats_epoch = 0;                // launches of k_schur_gram<NV, true> in this solve so far (S.ctl_pub->stats_arrived counts their reduction workgroups)
-    int eval_pending = 0;               // ... and an evaluation is waiting for it: 1 = reductions complete (one GPU), 2 = all-reduced H_stage (communicator); + 4: the solve's initial evaluation
+    int eval_pending = 0;               // an evaluation is waiting for its control step in the next k_schur_gram: its kCtl* bits
     int t_epoch = 0;                    // fused launches of this solve so far (the hand-off counter is monotonic)
     int withhold = 0, withhold_next = 0; // this solve / the next one: fault injection (tscm_solver_debug_withhold_handoff)
     int n_reruns = 0;                   // solves that were run again on separate launches after a late hand-off
     bool no_rerun = false, no_rerun_next = false;      // fault injection: the late hand-off of this / the next solve stays an error
     tscm_comm *comm_reg = nullptr;      // what tscm_solver_set_comm registered; `comm` is what the current solve uses
-    int solve_variant = 0;              // 0: k_solve_reduced (up to 4 cameras: one dense block), 1: k_solve_nd (5..8 cameras, or TSCM_EXEC_GRAPH_REDUCED_ORDER), 3: k_solve_reduced_big (more than 8 cameras)
-    int dense4_resident = 0;            // workgroups of k_solve_reduced<4, 16, 64, true>'s launch that are resident at once
     // k_solve_nd: [0] the nested-dissection plan of the camera-pair graph, [1] one dense block (TSCM_EXEC_DENSE_REDUCED_ORDER; also what
-    // [0] is when the graph is complete); operand map and tables of each on the device; workgroups of the fused launch
-    // that are resident at once (occupancy x CUs)
+    // [0] is when the graph is complete); operand map and tables of each on the device
     NdPlan plan[2];
     const int4 *d_nd_map[2] = { nullptr, nullptr };
     const int *d_nd_tab[2] = { nullptr, nullptr }, *d_nd_bs[2] = { nullptr, nullptr };
     size_t lds_nd[2] = { 0, 0 }, lds_dense4 = 0;
-    int nd_resident[2] = { 0, 0 };
-    int nd = 0;                         // this solve: which of the two
-    bool graph_order = false;           // this solve: k_solve_nd also for a rig of up to 4 cameras (TSCM_EXEC_GRAPH_REDUCED_ORDER / _DENSE_REDUCED_ORDER there)
-    bool f32_jacobian = false;          // this solve runs k_eval_gram_f32 (tscm_options.jacobian_fp32)
-    bool gram16 = false;                // this solve: TSCM_EXEC_GRAM_16X16
     size_t lds_eval4 = 0;               // dynamic LDS of k_eval_gram4
     EvalKernel eval4 = nullptr, eval32 = nullptr;   // ... and its instantiation for this problem's board (g4_kernel), the fp32-Jacobian tier's (f32_kernel)
     EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
@@ -349,12 +337,12 @@ static int build_columns(tscm_solver *s)
         int run = 0;
         for (int m = 0; m < C; ++m) { P.cam_pre[m] = run; P.cam_free[m] = word[m]; run += __builtin_popcount(word[m]); }
     }
-    if (s->solve_variant == 0) {
+    if (C <= kDense4Cams) {
         hipLaunchKernelGGL((k_solve_map<4, 16>), dim3(1), dim3(256), 0, s->stream, P, const_cast<int4 *>(P.solve_map));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
-    if (s->solve_variant <= 1 && n_act > 0) {
+    if (C <= kMaxCamLds && n_act > 0) {
         // two plans: [0] along the camera-pair graph, [1] the whole system as one dense block.  A graph whose per-camera panel
         // padding does not fit the tile budget (dense but incomplete pair graphs of 8 free cameras) is solved on the dense plan;
         // only a system that fits neither is refused.  (No free column at all: no plan -- that system is not factored, see
@@ -409,11 +397,12 @@ static int build_columns(tscm_solver *s)
             int per_cu = 0;
             if (s->plan[v].tpt == 1) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_nd<1, true>), kNdThreads, lds));
             else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_nd<2, true>), kNdThreads, lds));
-            s->nd_resident[v] = per_cu * s->n_cu;
+            s->dev.nd_resident[v] = per_cu * s->n_cu;
+            s->dev.nd_tpt[v] = s->plan[v].tpt;
         }
         s->lds_solve = std::max(s->lds_nd[0], s->lds_nd[1]);
     }
-    if (s->solve_variant == 3) s->lds_solve = solve_big_lds_bytes((n_act + 15) & ~15, n_pad);
+    if (C > kMaxCamLds) s->lds_solve = solve_big_lds_bytes((n_act + 15) & ~15, n_pad);
     return 0;
 }
 
@@ -496,9 +485,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
                                 { reinterpret_cast<const void *>(k_schur_gram<2>), reinterpret_cast<const void *>(k_schur_gram<2, true>) },
                                 { reinterpret_cast<const void *>(k_schur_gram<3>), reinterpret_cast<const void *>(k_schur_gram<3, true>) } };
     for (int nv = 1; nv <= 3; ++nv) {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident[nv], schur[nv][0], 256, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->schur_resident_ride[nv], schur[nv][1], 256, 0));
-        s->schur_resident[nv] *= prop.multiProcessorCount; s->schur_resident_ride[nv] *= prop.multiProcessorCount;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->dev.schur_resident[nv], schur[nv][0], 256, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s->dev.schur_resident_ride[nv], schur[nv][1], 256, 0));
+        s->dev.schur_resident[nv] *= prop.multiProcessorCount; s->dev.schur_resident_ride[nv] *= prop.multiProcessorCount;
     }
     s->n_cu = std::max(1, prop.multiProcessorCount);
 
@@ -598,8 +587,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     if (s->lds_eval32 > 64 * 1024)
         for (EvalKernel k : { s->eval32, s->eval32r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
     // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory
-    s->solve_variant = C <= 4 ? 0 : C <= kMaxCamLds ? 1 : 3;
-    if (s->solve_variant == 0) {
+    if (C <= kDense4Cams) {
         // where every thread of k_solve_reduced finds its operands (written by build_columns)
         int4 *map = nullptr;
         if ((rc = dev_alloc(s, &map, (size_t)(kSolveMapSlots / 4) * 256))) return rc;
@@ -608,9 +596,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         s->lds_dense4 = sizeof(double) * (NN * (NN + 2) + 2 * (NN / TT) * (TT * TT + 2) + 2 * NN + 3 * NPD);
         int per_cu = 0;
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k_solve_reduced<4, 16, 64, true>), 256, std::max(s->lds_dense4, s->lds_bs)));
-        s->dense4_resident = per_cu * prop.multiProcessorCount;
+        s->dev.dense4_resident = per_cu * prop.multiProcessorCount;
     }
-    if (s->solve_variant == 3) {
+    if (C > kMaxCamLds) {
         // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory, sized for every camera-side column free
         // (held intrinsics only ever take columns away)
         int n_max = 0;
@@ -632,11 +620,7 @@ extern "C" int tscm_solver_create(const tscm_problem *p, int device, tscm_solver
     return tscm_solver_create_sharded(p, device, 0, 1, out);
 }
 
-static tscm_comm *effective_comm(const tscm_solver *s, int exec_flags)
-{
-    tscm_comm *c = s->comm_reg;
-    return (c && (c->world > 1 || c->group || (exec_flags & TSCM_EXEC_KEEP_SINGLE_RANK_COMM))) ? c : nullptr;
-}
+static CommKind comm_kind(const tscm_comm *c) { return !c ? kCommNone : c->world > 1 || c->group ? kCommShared : kCommOneRank; }
 
 // Fault injection for the tests of the device-side hand-off: in the NEXT solve of this solver one producer of the fused
 // hand-off never reports in, and the solve must end with TSCM_E_HIP within the hand-off's time bound.  Not an option of
@@ -662,9 +646,9 @@ extern "C" int tscm_solver_set_comm(tscm_solver *s, tscm_comm *comm)
     if (comm && (comm->world != s->world || comm->rank != s->rank))
         return fail(TSCM_E_INVALID, "communicator rank / world differ from the solver's shard (tscm_solver_create_sharded)");
     // a single-rank RCCL communicator is a no-op unless a solve asks for its code path (separate k_control,
-    // stream-ordered all-reduces) with TSCM_EXEC_KEEP_SINGLE_RANK_COMM: effective_comm()
+    // stream-ordered all-reduces) with TSCM_EXEC_KEEP_SINGLE_RANK_COMM: uses_comm()
     s->comm_reg = comm;
-    s->comm = effective_comm(s, 0);
+    s->comm = uses_comm(comm_kind(comm), 0) ? comm : nullptr;
     return 0;
 }
 
@@ -732,12 +716,11 @@ static int launch_eval(tscm_solver *s, int cand)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (int rc = timed_pair(s, 0, &e0, &e1)) return rc;
     const dim3 grid(P.n_chunks / 4);
-    // 9x6 .. 7x8 boards (53..56 corners per pass) get the variant with a compile-time LDS pitch
     // (a loss: the ROBUST instantiation; the 16x16 kernel has none -- refused before anything is launched)
-    const bool robust = s->loss.kind != TSCM_LOSS_NONE;
-    if (s->f32_jacobian) launch_eval_kernel(robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
-    else if (!s->gram16) launch_eval_kernel(robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand, s->loss);     // every board size (round 6)
-    else if (P.rp == 58) launch_eval_kernel(k_eval_gram<58>, grid, s->lds_eval, s, e0, e1, cand);
+    const bool robust = s->xp.robust;
+    if (s->xp.gram == Gram::F32) launch_eval_kernel(robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
+    else if (s->xp.gram == Gram::G4) launch_eval_kernel(robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand, s->loss);
+    else if (s->xp.gram == Gram::G16Pitch58) launch_eval_kernel(k_eval_gram<58>, grid, s->lds_eval, s, e0, e1, cand);
     else launch_eval_kernel(k_eval_gram<0>, grid, s->lds_eval, s, e0, e1, cand);
     return 0;
 }
@@ -862,7 +845,6 @@ static int comm_check(tscm_comm *c)
 
 struct LmRun {
     std::vector<tscm_solver *> m;
-    bool separate_control() const { return m[0]->comm != nullptr; }
 };
 
 static int exchange(LmRun &run, bool t_buffer)
@@ -886,128 +868,102 @@ static int exchange(LmRun &run, bool t_buffer)
     return 0;
 }
 
-// evaluation of the target point: pose constants, Gram kernel, reductions, statistics (+ all-reduce + control)
+// evaluation of the target point: pose constants, Gram kernel, reductions, statistics (+ all-reduce + control): ExecPlan::tail
 static int enqueue_eval(LmRun &run, int cand, int init, int have_backsub, bool have_view_constants = false)
 {
-    const bool sep = run.separate_control();
-    const bool fused = !sep && run.m[0]->P.C <= kMaxCamLds;     // (rigs of more than 8 cameras: k_control as a launch of its own)
     for (tscm_solver *s : run.m) {
         const DevProblem &P = s->P;
         DevState &S = s->S;
+        const int nr = P.C * kCamSl + S.n_st_blocks;
         // the constants of a candidate point were written by k_backsub_prep; the initial point needs them here
-        if (!have_backsub && !have_view_constants) hipLaunchKernelGGL(k_view_prep, dim3((P.V + P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, P, S, cand, s->f32_jacobian ? 1 : 0);
+        if (!have_backsub && !have_view_constants) hipLaunchKernelGGL(k_view_prep, dim3((P.V + P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, P, S, cand, s->xp.f32() ? 1 : 0);
         if (int rc = launch_eval(s, cand)) return rc;
-        if (fused && s->ctl_in_schur && (cand || init)) {
-            // ... or the reductions alone: the next k_schur_gram takes the control step in its head (k_control_tail behind the
-            // last evaluation of the solve).  Round 5: the solve's INITIAL evaluation as well (eval_pending = 1 | 4: IterationZero
-            // in the head of the first Schur kernel) -- k_reduce_control's last workgroup cost every solve 18.4 us where
-            // k_reduce_stats takes 5.5 and the head 4.4
-            // ... and a candidate's reductions ride in that launch as well (eval_pending | 8: k_schur_gram<NV, true>)
-            if (s->stats_ride && !init) { s->eval_pending = 1 | 8; continue; }
-            hipLaunchKernelGGL(k_reduce_stats, dim3(P.C * kCamSl + S.n_st_blocks), dim3(256), 0, s->stream, P, S, cand, init);
-            s->eval_pending = init ? 5 : 1;
-            continue;
+        const EvalTail t = s->xp.tail;
+        // a candidate's reductions ride in the next k_schur_gram<NV, true>
+        if (t == EvalTail::Ride && !init) s->eval_pending = kCtlOneGpu | kCtlRide;
+        else if (t == EvalTail::ReduceControl) hipLaunchKernelGGL(k_reduce_control, dim3(nr), dim3(256), 0, s->stream, P, S, cand, init, have_backsub);
+        else {
+            hipLaunchKernelGGL(k_reduce_stats, dim3(nr), dim3(256), 0, s->stream, P, S, cand, init);
+            if (t == EvalTail::Exchange) hipLaunchKernelGGL(k_finalize_eval, dim3(P.C + 1), dim3(256), 0, s->stream, P, S, have_backsub);
+            // ... or the reductions alone: the next k_schur_gram takes the control step in its head (k_control_tail behind the last
+            // evaluation of the solve).  Round 5: the solve's INITIAL evaluation as well (IterationZero in the head of the first
+            // Schur kernel) -- k_reduce_control's last workgroup cost every solve 18.4 us where k_reduce_stats takes 5.5 and the head 4.4
+            else s->eval_pending = kCtlOneGpu | (init ? kCtlInit : 0);
         }
-        if (fused) {
-            // one GPU: reductions, statistics and the control step in one launch
-            hipLaunchKernelGGL(k_reduce_control, dim3(P.C * kCamSl + S.n_st_blocks), dim3(256), 0, s->stream, P, S, cand, init, have_backsub);
-            continue;
-        }
-        hipLaunchKernelGGL(k_reduce_stats, dim3(P.C * kCamSl + S.n_st_blocks), dim3(256), 0, s->stream, P, S, cand, init);
-        hipLaunchKernelGGL(k_finalize_eval, dim3(P.C + 1), dim3(256), 0, s->stream, P, S, have_backsub);
     }
-    if (fused) return 0;
+    if (run.m[0]->xp.tail != EvalTail::Exchange) return 0;
     if (int rc = exchange(run, /*t_buffer=*/false)) return rc;
     for (tscm_solver *s : run.m) {
         // behind the all-reduce: k_control -- or, for a candidate's evaluation, the head of the next k_schur_gram
-        if (sep && s->ctl_in_schur && cand && !init) s->eval_pending = 2;
+        if (s->xp.ctl_in_schur && cand && !init) s->eval_pending = kCtlComm;
         else hipLaunchKernelGGL(k_control, dim3(1), dim3(256), 0, s->stream, s->P, s->S, init);
     }
     return 0;
 }
 
-// one GPU, up to 8 cameras: the T reduction rides in the reduced solve's launch (k_solve_nd<.., true>); with a communicator the
-// all-reduce of T sits between the two
-static bool fused_reduce(const tscm_solver *s) { return s->fuse_reduce && s->solve_variant <= 1 && !s->comm && s->P.n_bids > 0 && s->P.n_bids <= kSmallBids && s->P.n_act > 0; }
+// the Schur-complement kernel of one views-per-board class (NV = 1, 2, 3), if the layout has chunks of it; ctl: the
+// waiting evaluation's kCtl* bits (0: none), ce: its control epoch, target: the riding reductions' arrival count
+template <int NV>
+static void launch_schur(tscm_solver *s, int ctl, int ce, int target)
+{
+    const int n = s->L.nv_chunks[NV], c0 = s->L.nv_chunk0[NV], ns = s->P.C * kCamSl + s->S.n_st_blocks, arg = (ctl & ~kCtlRide) | (s->withhold == 2 ? kCtlWithhold : 0);
+    if (n && (ctl & kCtlRide)) hipLaunchKernelGGL((k_schur_gram<NV, true>), dim3(std::max(ns, n) + 1), dim3(256), s->lds_gram, s->stream, s->P, s->S, c0, arg, s->dev.schur_resident_ride[NV], ce, target, n);
+    else if (n) hipLaunchKernelGGL(k_schur_gram<NV>, dim3(n + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, s->P, s->S, c0, ctl, s->dev.schur_resident[NV], ce, 0, n);
+}
+
+// the back-substitution as a launch of its own (ExecPlan::bs_threads: 0 none)
+static void launch_backsub(tscm_solver *s, int wf)
+{
+    if (s->xp.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(s->S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, s->P, s->S, wf);
+    if (s->xp.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(s->S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, s->P, s->S, wf);
+}
 
 static int enqueue_iteration(LmRun &run)
 {
     for (tscm_solver *s : run.m) {
         const DevProblem &P = s->P;
         DevState &S = s->S;
-        const int ctl = s->eval_pending;                  // (ctl_in_schur: exactly one of the three variants below is launched)
+        const int ctl = s->eval_pending;                  // (ctl_in_schur: exactly one of the three variants is launched)
         s->eval_pending = 0;
         if (P.n_slow) hipLaunchKernelGGL(k_schur_factor, dim3((P.n_slow + 255) / 256), dim3(256), 0, s->stream, P, S);
-        const int ce = ctl ? ++s->ctl_epoch : 0;          // (ctl: 1 one GPU | 2 communicator, + 4: the initial evaluation's step, + 8: the reductions ride)
-        if (ctl & 8) {
-            const int ns = P.C * kCamSl + S.n_st_blocks, target = ns * ++s->stats_epoch;
-            if (s->L.nv_chunks[1]) hipLaunchKernelGGL((k_schur_gram<1, true>), dim3(std::max(ns, s->L.nv_chunks[1]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[1], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[1], ce, target, s->L.nv_chunks[1]);
-            if (s->L.nv_chunks[2]) hipLaunchKernelGGL((k_schur_gram<2, true>), dim3(std::max(ns, s->L.nv_chunks[2]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[2], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[2], ce, target, s->L.nv_chunks[2]);
-            if (s->L.nv_chunks[3]) hipLaunchKernelGGL((k_schur_gram<3, true>), dim3(std::max(ns, s->L.nv_chunks[3]) + 1), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[3], (ctl & 7) | (s->withhold == 2 ? 16 : 0), s->schur_resident_ride[3], ce, target, s->L.nv_chunks[3]);
-        } else {
-            if (s->L.nv_chunks[1]) hipLaunchKernelGGL(k_schur_gram<1>, dim3(s->L.nv_chunks[1] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[1], ctl, s->schur_resident[1], ce, 0, s->L.nv_chunks[1]);
-            if (s->L.nv_chunks[2]) hipLaunchKernelGGL(k_schur_gram<2>, dim3(s->L.nv_chunks[2] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[2], ctl, s->schur_resident[2], ce, 0, s->L.nv_chunks[2]);
-            if (s->L.nv_chunks[3]) hipLaunchKernelGGL(k_schur_gram<3>, dim3(s->L.nv_chunks[3] + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, P, S, s->L.nv_chunk0[3], ctl, s->schur_resident[3], ce, 0, s->L.nv_chunks[3]);
-        }
+        const int ce = ctl ? ++s->ctl_epoch : 0;
+        const int target = (ctl & kCtlRide) ? (P.C * kCamSl + S.n_st_blocks) * ++s->stats_epoch : 0;
+        launch_schur<1>(s, ctl, ce, target); launch_schur<2>(s, ctl, ce, target); launch_schur<3>(s, ctl, ce, target);
         if (P.n_pchunks) hipLaunchKernelGGL(k_pair_gram, dim3(P.n_pchunks), dim3(256), 0, s->stream, P, S);
-        if (P.n_bids && !fused_reduce(s)) hipLaunchKernelGGL(k_T_reduce, dim3(P.n_bids * (256 / kTEntries)), dim3(kTEntries * kTSlices), 0, s->stream, P, S);
+        if (P.n_bids && !s->xp.t_in_solve) hipLaunchKernelGGL(k_T_reduce, dim3(P.n_bids * (256 / kTEntries)), dim3(kTEntries * kTSlices), 0, s->stream, P, S);
     }
     if (int rc = exchange(run, /*t_buffer=*/true)) return rc;
     for (tscm_solver *s : run.m) {
         const DevProblem &P = s->P;
         DevState &S = s->S;
-        const int wf = s->f32_jacobian ? 1 : 0;
-        if (P.n_act == 0) {
-            // no free camera-side column (every intrinsic held where the pose is, e.g. a mono problem refining board poses only):
-            // nothing to factor.  k_solve_reduced_big on the empty system runs no panel and writes the zero camera step, the
-            // unchanged candidate camera parameters and the linear-solve flag; the back-substitution moves the boards
-            hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), solve_big_lds_bytes(0, s->n_pad), s->stream, P, S);
-            if (S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-            if (S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
-            continue;
-        }
-        if (s->solve_variant == 0 && !s->graph_order) {
+        const ExecPlan &x = s->xp;
+        const int wf = x.f32() ? 1 : 0;
+        // T producers, reduced solve and the waiting back-substitution workgroups in ONE launch where the plan puts them there
+        const bool ride = x.n_prod || x.n_bs;
+        const int epoch = ride ? ++s->t_epoch : 0, withhold = ride && s->withhold == 1 ? 1 : 0;
+        if (x.solver == Solver::Dense4) {
             // up to 4 cameras, one dense block: the same launch shape with k_solve_reduced as the solver workgroup
-            const int n_prod = fused_reduce(s) ? P.n_bids * (256 / kFusedEntries) : 0;
-            const int n_bs = s->fuse_backsub && s->L.bs_threads == 256 && S.n_bs_blocks <= s->dense4_resident - 1 - n_prod ? S.n_bs_blocks : 0;       // all of them, or none: see below
-            if (n_prod || n_bs)
-                hipLaunchKernelGGL((k_solve_reduced<4, 16, 64, true>), dim3(1 + n_prod + n_bs), dim3(256), std::max(s->lds_dense4, n_bs ? s->lds_bs : (size_t)0), s->stream,
-                                   P, S, ++s->t_epoch, s->withhold == 1 ? 1 : 0, n_prod, n_bs, wf);
+            if (ride)
+                hipLaunchKernelGGL((k_solve_reduced<4, 16, 64, true>), dim3(1 + x.n_prod + x.n_bs), dim3(256), std::max(s->lds_dense4, x.n_bs ? s->lds_bs : (size_t)0), s->stream,
+                                   P, S, epoch, withhold, x.n_prod, x.n_bs, wf);
             else hipLaunchKernelGGL((k_solve_reduced<4, 16, 64>), dim3(1), dim3(256), s->lds_dense4, s->stream, P, S, 0, 0, 0, 0, 0);
-            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
-            continue;
+        } else if (x.solver == Solver::Nd) {
+            // 5 to 8 cameras (and TSCM_EXEC_GRAPH_ / _DENSE_REDUCED_ORDER): k_solve_nd on plan x.nd
+            const int v = x.nd;
+            const dim3 grid(1 + x.n_prod + x.n_bs);
+            const size_t lds = std::max(s->lds_nd[v], x.n_bs ? s->lds_bs : (size_t)0);
+            if (ride && x.tpt == 2) hipLaunchKernelGGL((k_solve_nd<2, true>), grid, dim3(kNdThreads), lds, s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), epoch, withhold, x.n_prod, x.n_bs, wf);
+            else if (ride) hipLaunchKernelGGL((k_solve_nd<1, true>), grid, dim3(kNdThreads), lds, s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), epoch, withhold, x.n_prod, x.n_bs, wf);
+            else if (x.tpt == 2) hipLaunchKernelGGL((k_solve_nd<2, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
+            else hipLaunchKernelGGL((k_solve_nd<1, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
+        } else {
+            // 9 to 32 cameras -- or no free camera-side column (every intrinsic held where the pose is, e.g. a mono problem refining
+            // board poses only): nothing to factor.  k_solve_reduced_big on the empty system runs no panel and writes the zero camera
+            // step, the unchanged candidate camera parameters and the linear-solve flag; the back-substitution moves the boards
+            const size_t lds = x.solver == Solver::Empty ? solve_big_lds_bytes(0, s->n_pad) : s->lds_solve;
+            hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), lds, s->stream, P, S);
         }
-        if (s->solve_variant <= 1) {
-            // 5 to 8 cameras (and TSCM_EXEC_GRAPH_REDUCED_ORDER): T reduction (one GPU), reduced solve and -- unless TSCM_EXEC_SEPARATE_BACKSUB -- the back-substitution
-            // workgroups, which wait for the camera step with their operands loaded, in ONE launch -- if ALL of them are
-            // resident next to the solver workgroup and the producers (occupancy x CUs: a waiting workgroup that keeps the
-            // solver off the chip would wait for ever); otherwise the back-substitution is a launch of its own.  Splitting
-            // it between the two was measured and lost: at config 5 (5,000 groups, 255 of them riding) 364.3 against 356.7 us
-            // per iteration -- the riders share the solver workgroup's CU and the rest needs its launch anyway
-            const int v = s->nd;
-            const int n_prod = fused_reduce(s) ? P.n_bids * (256 / kFusedEntries) : 0;
-            const int n_bs = s->fuse_backsub && s->L.bs_threads == 256 && S.n_bs_blocks <= s->nd_resident[v] - 1 - n_prod ? S.n_bs_blocks : 0;
-            const bool two = s->plan[v].tpt == 2;
-            if (n_prod || n_bs) {
-                const size_t lds = std::max(s->lds_nd[v], n_bs ? s->lds_bs : (size_t)0);
-                const dim3 grid(1 + n_prod + n_bs);
-                if (two) {
-                    hipLaunchKernelGGL((k_solve_nd<2, true>), grid, dim3(kNdThreads), lds, s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), ++s->t_epoch, s->withhold == 1 ? 1 : 0, n_prod, n_bs, wf);
-                } else {
-                    hipLaunchKernelGGL((k_solve_nd<1, true>), grid, dim3(kNdThreads), lds, s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), ++s->t_epoch, s->withhold == 1 ? 1 : 0, n_prod, n_bs, wf);
-                }
-            } else {
-                if (two) hipLaunchKernelGGL((k_solve_nd<2, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
-                else hipLaunchKernelGGL((k_solve_nd<1, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
-            }
-            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-            if (!n_bs && S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
-            continue;
-        }
-        hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), s->lds_solve, s->stream, P, S);
-        if (S.n_bs_blocks && s->L.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, P, S, wf);
-        if (S.n_bs_blocks && s->L.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, P, S, wf);
+        launch_backsub(s, wf);
     }
     return enqueue_eval(run, /*cand=*/1, /*init=*/0, /*have_backsub=*/1);
 }
@@ -1031,7 +987,7 @@ struct LmRunGuard {
     ~LmRunGuard()
     {
         for (tscm_solver *s : run.m) {
-            s->f32_jacobian = false;         // (per solve: set again from the options of the next one)
+            s->xp = ExecPlan{};              // (per solve: planned again from the options of the next one)
             s->ev_used = 0;
             s->stream = s->own_stream;
         }
@@ -1055,6 +1011,7 @@ static int read_options(const tscm_options *opt_in, int mono, tscm_options &opt)
     }
     return 0;
 }
+static int check_options(const tscm_options &opt, int loss_kind) { std::string err; const int rc = check_exec_options(opt, loss_kind, err); return rc ? fail(rc, err) : 0; }
 
 // Waits for the solver's stream.  With a multi-rank RCCL communicator a peer that has failed (or died) leaves this
 // rank's all-reduce kernel spinning for ever -- over the intra-node transports an ncclCommAbort on the FAILING rank does
@@ -1168,40 +1125,17 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     for (tscm_solver *s : run.m) if (!s->have_init) return fail(TSCM_E_INVALID, "tscm_solver_upload_params has not been called");
     tscm_options opt;
     if (int rc = read_options(opt_in, s0->mono, opt)) return rc;
-    if (opt.max_num_iterations < 0 || opt.max_num_iterations > TSCM_MAX_ITERATIONS) return fail(TSCM_E_INVALID, "max_num_iterations must be in [0, 255]");
-    if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
+    if (int rc = check_options(opt, s0->loss.kind)) return rc;
     for (tscm_solver *s : run.m) if (!same_loss(s->loss, s0->loss)) return fail(TSCM_E_INVALID, "the solvers of a group carry different losses (tscm_solver_set_loss)");
     for (tscm_solver *s : run.m) if (s->fixed != s0->fixed) return fail(TSCM_E_INVALID, "the solvers of a group hold different intrinsics (tscm_solver_set_fixed_intrinsics)");
-    if (s0->loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
     HIP_TRY(hipSetDevice(s0->device));
     LmRunGuard guard{ run };
     for (tscm_solver *s : run.m) {
-        s->comm = effective_comm(s, opt.exec_flags);
-        s->fuse_reduce = !(opt.exec_flags & TSCM_EXEC_SEPARATE_T_REDUCE);
-        s->fuse_backsub = !(opt.exec_flags & TSCM_EXEC_SEPARATE_BACKSUB);
-        {
-            // one GPU with <= 8 cameras (finish_evaluation's LDS fits k_schur_gram's) or a communicator; exactly one Schur kernel per iteration
-            const int n_variants = (s->L.nv_chunks[1] ? 1 : 0) + (s->L.nv_chunks[2] ? 1 : 0) + (s->L.nv_chunks[3] ? 1 : 0);
-            // (a grid of several rounds -- config 5 on one GPU: 1256 workgroups, 2.5 rounds -- pays the step in its first round
-            // only: the later rounds read the outcome workgroup 0 publishes)
-            s->ctl_in_schur = (s->comm || s->P.C <= kMaxCamLds) && s->P.n_slow == 0 && s->P.n_pchunks == 0 && n_variants == 1 &&
-                              !(opt.exec_flags & TSCM_EXEC_SEPARATE_CONTROL);
-            s->eval_pending = 0;
-            s->ctl_epoch = 0;
-            // (one GPU, the control step from the finished sums themselves: not behind an all-reduce)
-            // -- and a grid of ONE round: every workgroup that takes a reduction block in front of its chunk is resident (they wait for
-            // each other), and at config 5 (1256 chunks, 2.5 rounds) the ride costs 2.5 us where it saves 4 at config 4
-            const int nv_used = s->L.nv_chunks[1] ? 1 : s->L.nv_chunks[2] ? 2 : 3;
-            s->stats_ride = s->ctl_in_schur && !s->comm && s->P.C <= kMaxCamLds && !(opt.exec_flags & TSCM_EXEC_SEPARATE_STATS) &&
-                            std::max(s->P.C * kCamSl + s->S.n_st_blocks, s->L.nv_chunks[nv_used]) + 1 <= s->schur_resident_ride[nv_used];
-            s->stats_epoch = 0;
-        }
+        s->xp = plan_exec(s->L, s->C, s->P.n_act, comm_kind(s->comm_reg), opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev);
+        s->comm = s->xp.comm ? s->comm_reg : nullptr;
+        s->eval_pending = s->ctl_epoch = s->stats_epoch = s->t_epoch = 0;
         s->withhold = s->withhold_next; s->withhold_next = 0;
         if (!rerun) { s->no_rerun = s->no_rerun_next; s->no_rerun_next = false; }
-        s->gram16 = (opt.exec_flags & TSCM_EXEC_GRAM_16X16) != 0;
-        s->nd = (opt.exec_flags & TSCM_EXEC_DENSE_REDUCED_ORDER) ? 1 : 0;
-        s->graph_order = (opt.exec_flags & TSCM_EXEC_GRAPH_REDUCED_ORDER) != 0 || (s->solve_variant == 0 && s->nd);
-        s->t_epoch = 0;
     }
     if (s0->comm && !s0->comm->group && !s0->comm->ipc && !s0->comm->comm) return fail(TSCM_E_RCCL, "the communicator was aborted by an earlier failure");
     if (s0->comm && s0->comm->ipc && s0->comm->ipc->dead) return fail(TSCM_E_PEER, "the IPC communicator is unusable after an earlier failure (a peer that did not arrive, or a failed solve)");
@@ -1215,7 +1149,6 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         for (tscm_solver *s : run.m) { HIP_TRY(hipStreamSynchronize(s->own_stream)); s->stream = g->stream; }
     }
     for (size_t r = 0; r < run.m.size(); ++r) std::memset(&sums[r], 0, sizeof(tscm_summary));
-    for (tscm_solver *s : run.m) s->f32_jacobian = opt.jacobian_fp32 != 0;
 
     // control block (identical on every rank), counter of the fused T reduction, start point: one launch (k_begin_solve)
     const double t0 = wall();
@@ -1243,7 +1176,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         hipLaunchKernelGGL(k_begin_view_prep, dim3((s->P.V + s->P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, s->P, s->S, h,
                            rerun ? s->d_start_cam : from_init ? s->d_init_cam : nullptr, rerun ? s->d_start_intr : from_init ? s->d_init_intr : nullptr,
                            rerun ? s->d_start_board : from_init ? s->d_init_board : nullptr,
-                           rerun ? nullptr : s->d_start_cam, rerun ? nullptr : s->d_start_intr, rerun ? nullptr : s->d_start_board, s->f32_jacobian ? 1 : 0);
+                           rerun ? nullptr : s->d_start_cam, rerun ? nullptr : s->d_start_intr, rerun ? nullptr : s->d_start_board, s->xp.f32() ? 1 : 0);
     }
 
     int rc;
@@ -1266,15 +1199,15 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     const size_t ctrl_bytes = sizeof(CtrlHead) + sizeof(IterLog) * (size_t)std::min(opt.max_num_iterations + 1, kMaxLog);
     for (tscm_solver *s : run.m) {
         const int nb = std::min(256, (6 * std::max(s->B, s->C) + 255) / 256 + 1);
-        if (s->eval_pending & 1) {
+        if (s->eval_pending & kCtlOneGpu) {
             // (the reductions of the solve's last evaluation found no Schur kernel to ride in)
-            if (s->eval_pending & 8) hipLaunchKernelGGL(k_reduce_stats, dim3(s->P.C * kCamSl + s->S.n_st_blocks), dim3(256), 0, s->stream, s->P, s->S, 1, 0);
-            const int was_init = (s->eval_pending >> 2) & 1;
+            if (s->eval_pending & kCtlRide) hipLaunchKernelGGL(k_reduce_stats, dim3(s->P.C * kCamSl + s->S.n_st_blocks), dim3(256), 0, s->stream, s->P, s->S, 1, 0);
+            const int was_init = (s->eval_pending & kCtlInit) ? 1 : 0;
             hipLaunchKernelGGL(k_finish_solve, dim3(nb + 1), dim3(256), 0, s->stream, s->P, s->S, was_init, !was_init, s->C, s->B, s->d_h_ctrl);
             s->eval_pending = 0;
             continue;
         }
-        if (s->eval_pending == 2) hipLaunchKernelGGL(k_control, dim3(1), dim3(256), 0, s->stream, s->P, s->S, 0);
+        if (s->eval_pending == kCtlComm) hipLaunchKernelGGL(k_control, dim3(1), dim3(256), 0, s->stream, s->P, s->S, 0);
         s->eval_pending = 0;
         hipLaunchKernelGGL(k_end_solve, dim3(nb), dim3(256), 0, s->stream, s->S, s->C, s->B);
         HIP_TRY(hipMemcpyAsync(s->h_ctrl, s->S.ctrl, ctrl_bytes, hipMemcpyDeviceToHost, s->stream));
@@ -1429,8 +1362,9 @@ extern "C" int tscm_solve_robust(const tscm_problem *p, const tscm_options *opt,
     LossArg L;
     if (int rc = make_loss(kind, scale, L)) return rc;
     if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
-    if (L.kind != TSCM_LOSS_NONE && opt && opt->struct_size >= sizeof(tscm_options) && (opt->exec_flags & TSCM_EXEC_GRAM_16X16))
-        return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
+    tscm_options o;
+    if (int rc = read_options(opt, p->mono, o)) return rc;
+    if (int rc = check_options(o, L.kind)) return rc;
     return solve_once(p, opt, sum, L);
 }
 
@@ -1440,8 +1374,9 @@ extern "C" int tscm_solve_fixed(const tscm_problem *p, const tscm_options *opt, 
     if (int rc = make_loss(kind, scale, L)) return rc;
     if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
     if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
-    if (L.kind != TSCM_LOSS_NONE && opt && opt->struct_size >= sizeof(tscm_options) && (opt->exec_flags & TSCM_EXEC_GRAM_16X16))
-        return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
+    tscm_options o;
+    if (int rc = read_options(opt, p->mono, o)) return rc;
+    if (int rc = check_options(o, L.kind)) return rc;
     return solve_once(p, opt, sum, L, fixed);
 }
 
@@ -1455,11 +1390,10 @@ static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
-    if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
-    if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
-    if (loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
     opt.max_num_iterations = 1;
     opt.function_tolerance = opt.gradient_tolerance = opt.parameter_tolerance = 0.0;
+    if ((rc = check_options(opt, loss.kind))) return rc;
+    if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
     tscm_solver *s = nullptr;
     if ((rc = tscm_solver_create(p, device, &s))) return rc;
     std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
@@ -1579,15 +1513,14 @@ static int eval_normal_equations(const tscm_problem *p, int device, const tscm_o
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
-    if (opt.exec_flags & ~TSCM_EXEC_ALL) return fail(TSCM_E_INVALID, "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)");
-    if (loss.kind != TSCM_LOSS_NONE && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel");
+    opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
+    if ((rc = check_options(opt, loss.kind))) return rc;
     tscm_solver *s = nullptr;
     if ((rc = tscm_solver_create(p, device, &s))) return rc;
     std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
     s->loss = loss;
-    s->f32_jacobian = opt.jacobian_fp32 != 0;
-    s->gram16 = (opt.exec_flags & TSCM_EXEC_GRAM_16X16) != 0;
-    if ((rc = prepare_eval(s, s->f32_jacobian ? 1 : 0))) return rc;
+    s->xp = plan_exec(s->L, s->C, s->P.n_act, kCommNone, opt.exec_flags, opt.jacobian_fp32, loss.kind, s->P.rp, s->dev);     // (its Gram kernel)
+    if ((rc = prepare_eval(s, s->xp.f32() ? 1 : 0))) return rc;
     const DevProblem &P = s->P;
     DevState &S = s->S;
     if ((rc = launch_eval(s, 0))) return rc;
