@@ -30,10 +30,13 @@
 #include "tscm_nd_plan.h"
 #include "tscm_layout.h"
 #include "tscm_exec_plan.h"
+#include "tscm_columns.h"
 
 namespace tscm {
 
 // the view record regions kRecW / kRecE / kRecG and the rig limits kMaxCamLds / kMaxCam / kSmallBids: tscm_layout.h
+// the operand map of k_solve_reduced (kMap*, kSolveMapSlots, kMapOne): tscm_columns.h
+static_assert(kColFree == kFA && kColGrad == kFR, "tscm_columns.h plans the columns of tscm_math.h's camera tile");
 constexpr int kWcolTc = 3;         // W columns of t_c: F index 3, 4, 5 (the gradient column E^T r is F index kFR = 13)
 // per-board factor record (doubles)
 constexpr int kFac = 56;
@@ -205,7 +208,7 @@ struct DevProblem {
     int cam_pre[9];
     unsigned short cam_free[8];
     unsigned long long pair_mask;      // bit mi * 8 + mj: the camera pair shares a board (its tile of T follows by a population count)
-    const int4 *solve_map;             // [kSolveMapSlots / 4][256] operand offsets of every thread of k_solve_reduced (k_solve_map)
+    const int4 *solve_map;             // [kSolveMapSlots / 4][256] operand offsets of every thread of k_solve_reduced (plan_solve_map)
     int cam_wg[9];                     // cam_chunk_ptr by value for rigs of <= kMaxCamLds cameras (k_reduce_control: no index load in front of the tiles)
     // frame sharding (tscm_solver_create_sharded): this rank / number of ranks; 0 / 1 on a single GPU
     int rank, world;

@@ -37,81 +37,6 @@ __device__ __forceinline__ int compact_to_padded(const DevProblem &P, int ci)
     for (int q = 1; q < kMaxCamLds; ++q) { const bool ge = ci >= P.cam_pre[q]; base = ge ? P.cam_pre[q] : base; q0 = ge ? q : q0; w = ge ? P.cam_free[q] : w; }
     return ci < P.n_act ? 16 * q0 + kth_set_bit16(w, ci - base) : -1;
 }
-// Tile of thread tid in k_solve_reduced's G x G grid (NP panels of free columns).  Lower tile (ti, tj) of the matrix on
-// thread ti * G + tj.  The right-hand side tiles (NP, p), p < NP, go to threads that own no matrix tile, counted
-// downwards from the end of the last wave that holds matrix tiles: tile p is needed up to panel step p, so the
-// longest-lived ones share a wave with the longest-lived matrix rows and the early waves retire early.  The
-// look-ahead thread (the last thread of the workgroup) is never used.
-struct SolveTile { bool mine, rhsrow; int ri, cj; };
-template <int TS, int G>
-__device__ __forceinline__ SolveTile solve_tile(int tid, int NP)
-{
-    constexpr int NT = (G * G + 63) / 64 * 64;
-    auto owns = [&](int t) { const int ti = t / G, tj = t % G; return tj <= ti && ti < NP; };
-    SolveTile t;
-    t.mine = owns(tid); t.rhsrow = false;
-    t.ri = tid / G; t.cj = tid % G;
-    if (t.mine || tid == NT - 1) return t;
-    const int last = min(NT - 2, ((NP - 1) * G + NP - 1) | 63);        // end of the wave of tile (NP-1, NP-1)
-    if (tid > last) return t;
-    int rank = 0;                                                       // free threads in (tid, last]
-    for (int u = tid + 1; u <= last; ++u) rank += owns(u) ? 0 : 1;
-    if (rank < NP) { t.rhsrow = true; t.ri = NP; t.cj = NP - 1 - rank; }
-    return t;
-}
-// slots of the per-thread operand map (ints): offsets into H[cur] and T per tile element (-1: the element is 0),
-// s_c indices of the tile's rows and columns (-1: padding / rhs row, where 1 is used through kMapOne)
-constexpr int kMapH = 0, kMapT = 16, kMapSci = 32, kMapScj = 36, kMapTile = 40, kSolveMapSlots = 44;   // kMapTile: row, column, 1 = matrix tile / 2 = rhs tile
-constexpr int kMapOne = 1 << 30;       // "scaling 1": the row of a right-hand side tile
-
-// Operand map of k_solve_reduced<TS, G> (run once per solver: the map depends on the camera/pair structure only).
-// grid 1 x NT
-template <int TS, int G>
-__global__ __launch_bounds__((G * G + 63) / 64 * 64) void k_solve_map(DevProblem P, int4 *map)
-{
-    static_assert(TS == 4, "the map holds 4 x 4 tiles");
-    constexpr int NT = (G * G + 63) / 64 * 64;
-    const int tid = threadIdx.x;
-    const int NP = (P.n_act + TS - 1) / TS;
-    const SolveTile tl = solve_tile<TS, G>(tid, NP);
-    auto cmap = [&](int ci) -> int { return compact_to_padded(P, ci); };
-    auto t_offset = [&](int i, int j) -> int {                  // as load_T_small
-        int lo = i >> 4, hi = j >> 4, a = i & 15, b = j & 15;
-        if (lo > hi) { const int t = lo; lo = hi; hi = t; const int u = a; a = b; b = u; }
-        const int bit = lo * 8 + hi;
-        const unsigned long long m = P.pair_mask;
-        return ((m >> bit) & 1ull) ? 256 * __popcll(m & ((1ull << bit) - 1ull)) + a * 16 + b : -1;
-    };
-    int off[kSolveMapSlots];
-    for (int q = 0; q < kSolveMapSlots; ++q) off[q] = -1;
-    off[kMapTile] = tl.ri; off[kMapTile + 1] = tl.cj; off[kMapTile + 2] = tl.mine ? 1 : tl.rhsrow ? 2 : 0;
-    if (tl.mine || tl.rhsrow) {
-        int mi[TS], mj[TS];
-        for (int r = 0; r < TS; ++r) { mi[r] = tl.mine ? cmap(tl.ri * TS + r) : -1; mj[r] = cmap(tl.cj * TS + r); }
-        for (int r = 0; r < TS; ++r) { off[kMapSci + r] = mi[r]; off[kMapScj + r] = mj[r]; }
-        if (tl.mine) {
-            for (int r = 0; r < TS; ++r)
-                for (int c = 0; c < TS; ++c) {
-                    const int i = mi[r], j = mj[c];
-                    if (i < 0 || j < 0) continue;
-                    if ((i >> 4) == (j >> 4)) off[kMapH + r * TS + c] = 256 * (i >> 4) + (i & 15) * 16 + (j & 15);
-                    off[kMapT + r * TS + c] = t_offset(i, j);
-                }
-        } else {
-            // right-hand side tile: row 0 = g - t_r of the panel's columns (the fused column kFR of H and T)
-            for (int c = 0; c < TS; ++c) {
-                const int j = mj[c];
-                if (j < 0) continue;
-                const int m = j >> 4, b = j & 15;
-                off[kMapH + c] = 256 * m + b * 16 + kFR;
-                off[kMapT + c] = t_offset(j, m * 16 + kFR);
-            }
-            off[kMapSci] = kMapOne;
-        }
-    }
-    for (int q = 0; q < kSolveMapSlots / 4; ++q) map[q * NT + tid] = make_int4(off[4 * q], off[4 * q + 1], off[4 * q + 2], off[4 * q + 3]);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Reduced camera system (DenseSchurComplementSolver): one 256-thread workgroup.
 //   A = S_c (H_cc - T) S_c + D_c^2, rhs = S_c (g_c - t_r); inactive columns (tile padding,
@@ -189,10 +114,10 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
     // The right-hand side rides along as tile row NP: row 0 of tile (NP, p) is the rhs slice of panel p (rows
     // 1..TS-1 are zero), so the forward substitution w = L^{-1} b falls out of the panel solves and trailing
     // updates and no thread treats it specially.  Those tiles live on idle threads of the last wave that holds
-    // matrix tiles (k_solve_map): the fewer waves take part in a panel step, the less they queue at the LDS.
-    // Where a thread's operands sit in H, T and s_c depends on the problem's structure only: k_solve_map wrote
-    // the offsets once, so the head of this kernel is two memory round trips (offsets + control block, then the
-    // operands) and next to no index arithmetic.
+    // matrix tiles (solve_tile): the fewer waves take part in a panel step, the less they queue at the LDS.
+    // Where a thread's operands sit in H, T and s_c depends on the problem's structure only: the host plans
+    // the offsets once (plan_solve_map, tscm_columns.h), so the head of this kernel is two memory round trips
+    // (offsets + control block, then the operands) and next to no index arithmetic.
     int off[kSolveMapSlots];
 #pragma unroll
     for (int q = 0; q < kSolveMapSlots / 4; ++q) {

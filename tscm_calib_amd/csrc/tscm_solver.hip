@@ -170,7 +170,7 @@ struct tscm_solver {
     EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
     LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs eval4 / eval32
     // held intrinsics (tscm_solver_set_fixed_intrinsics): the mask word of every camera (the whole-problem facts the
-    // free columns are derived from are L.cam_const, L.cam_active, L.pair_present: build_columns)
+    // free columns are derived from are L.cam_const, L.cam_active, L.pair_present: plan_columns)
     std::vector<unsigned short> fixed;
     int n_cu = 1;
     double *d_view_sq = nullptr;        // [2 V] k_reproj_error's output for the RMSE of a robust solve (allocated by the first one)
@@ -285,7 +285,7 @@ extern "C" void tscm_solver_destroy(tscm_solver *s)
     delete s;
 }
 
-// frees a buffer of dev_alloc / dev_upload before the solver is destroyed (tables that build_columns rebuilds)
+// frees a buffer of dev_alloc / dev_upload before the solver is destroyed (tables that apply_columns replaces)
 template <typename T>
 static void dev_release(tscm_solver *s, const T *p)
 {
@@ -295,78 +295,25 @@ static void dev_release(tscm_solver *s, const T *p)
     if (it != s->allocs.end()) { s->allocs.erase(it); (void)hipFree(q); }
 }
 
-// The free camera-side columns of the reduced system and every table derived from them.  A padded column
-// 16 m + a is free if camera m has views, a < kFA, the pose is not held (a < 6) and intrinsic a - 6 is not held (bit a - 6 of
-// fixed[m]).  Held intrinsics leave the tangent space: no column, no Jacobi scale, no LM diagonal, no gradient; their values
-// stay in |x| unless all seven are held, which makes the block constant (Ceres' SubsetManifold / SetParameterBlockConstant).
-// Written here: col_active, the control step's classes col_ctl, act_map / n_act, cam_pre / cam_free (kernel arguments of
-// k_solve_reduced), k_solve_map's operand map and both k_solve_nd plans.  Run by create and by tscm_solver_set_fixed_intrinsics;
-// with no held intrinsics the tables are the ones of the contiguous blocks, bit for bit.
-static int build_columns(tscm_solver *s)
+// Uploads a column plan (tscm_columns.h: plan_columns): col_active, the control step's classes col_ctl, act_map /
+// n_act, cam_pre / cam_free (kernel arguments of k_solve_reduced), k_solve_reduced's operand map and both k_solve_nd plans,
+// with the LDS bounds and residency that follow from them.  Run by create and by tscm_solver_set_fixed_intrinsics.
+static int apply_columns(tscm_solver *s, const ColumnPlan &c)
 {
     DevProblem &P = s->P;
-    const int C = s->C, n_pad = s->n_pad;
-    std::vector<unsigned char> col_active((size_t)n_pad, 0), col_ctl((size_t)16 * kMaxCam, 0);
-    std::vector<unsigned short> word(C, 0);
-    for (int i = 0; i < n_pad; ++i) {
-        const int m = i >> 4, a = i & 15;
-        const bool act = s->L.cam_active[m] != 0, cst = s->L.cam_const[m] != 0;
-        const unsigned f = s->fixed[m];
-        const bool held = a >= 6 && a < kFA && ((f >> (a - 6)) & 1u);
-        const bool block_const = (f & TSCM_FIX_INTRINSICS) == TSCM_FIX_INTRINSICS;
-        col_active[i] = (a < kFA && act && !(a < 6 && cst) && !held) ? 1 : 0;
-        const bool in_x = a < 6 ? (act && !cst) : a < 15 ? (act && !block_const) : false;
-        col_ctl[i] = (unsigned char)((in_x ? 1 : 0) | (col_active[i] ? 2 : 0));
-        if (col_active[i]) word[m] |= (unsigned short)(1u << a);
-    }
-    // compact numbering of the free camera-side columns: the reduced system is factored without the identity rows of held /
-    // padding columns
-    std::vector<int> act_map((size_t)n_pad, -1);
-    int n_act = 0;
-    for (int i = 0; i < n_pad; ++i) if (col_active[i]) act_map[n_act++] = i;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(const_cast<unsigned char *>(P.col_active), col_active.data(), col_active.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(const_cast<unsigned char *>(P.col_ctl), col_ctl.data(), col_ctl.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(const_cast<int *>(P.act_map), act_map.data(), sizeof(int) * act_map.size(), hipMemcpyHostToDevice));
-    P.n_act = n_act;
-    // the same map from kernel arguments for k_solve_reduced
-    for (int q = 0; q < 9; ++q) P.cam_pre[q] = n_act;
-    for (int q = 0; q < 8; ++q) P.cam_free[q] = 0;
-    if (C <= kMaxCamLds) {
-        int run = 0;
-        for (int m = 0; m < C; ++m) { P.cam_pre[m] = run; P.cam_free[m] = word[m]; run += __builtin_popcount(word[m]); }
-    }
-    if (C <= kDense4Cams) {
-        hipLaunchKernelGGL((k_solve_map<4, 16>), dim3(1), dim3(256), 0, s->stream, P, const_cast<int4 *>(P.solve_map));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    if (C <= kMaxCamLds && n_act > 0) {
-        // two plans: [0] along the camera-pair graph, [1] the whole system as one dense block.  A graph whose per-camera panel
-        // padding does not fit the tile budget (dense but incomplete pair graphs of 8 free cameras) is solved on the dense plan;
-        // only a system that fits neither is refused.  (No free column at all: no plan -- that system is not factored, see
-        // enqueue_iteration.)
-        int ncols[kMaxCamLds];
-        std::vector<int> cols((size_t)16 * C, -1);
-        for (int m = 0; m < C; ++m) {
-            ncols[m] = 0;
-            for (int a = 0; a < 16; ++a) if ((word[m] >> a) & 1u) cols[16 * (size_t)m + ncols[m]++] = 16 * m + a;
-        }
-        NdPlan plan[2];
-        if (!nd_build_plans_cols(C, ncols, cols.data(), s->L.pair_present.data(), s->L.bid_of.data(), plan))
-            return fail(TSCM_E_UNSUPPORTED, "internal error: the reduced system does not fit the register/LDS solver");
+    HIP_TRY(hipMemcpy(const_cast<unsigned char *>(P.col_active), c.col_active.data(), c.col_active.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(const_cast<unsigned char *>(P.col_ctl), c.col_ctl.data(), c.col_ctl.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(const_cast<int *>(P.act_map), c.act_map.data(), sizeof(int) * c.act_map.size(), hipMemcpyHostToDevice));
+    P.n_act = c.n_act;
+    std::copy(std::begin(c.cam_pre), std::end(c.cam_pre), P.cam_pre);
+    std::copy(std::begin(c.cam_free), std::end(c.cam_free), P.cam_free);
+    static_assert(sizeof(Int4) == sizeof(int4), "the operand map is uploaded as it is");
+    if (!c.solve_map.empty()) HIP_TRY(hipMemcpy(const_cast<int4 *>(P.solve_map), c.solve_map.data(), sizeof(Int4) * c.solve_map.size(), hipMemcpyHostToDevice));
+    if (c.has_nd) {
         for (int v = 0; v < 2; ++v) {
-            const NdPlan &pl = plan[v];
-            // (host replica check: the plan's columns are exactly the free columns)
-            std::vector<int> pc;
-            for (int c : pl.pcol) if (c >= 0) pc.push_back(c);
-            std::sort(pc.begin(), pc.end());
-            std::vector<int> want(act_map.begin(), act_map.begin() + n_act);
-            if (pc != want) return fail(TSCM_E_UNSUPPORTED, "internal error: elimination plan does not cover the free columns");
-        }
-        for (int v = 0; v < 2; ++v) {
-            const NdPlan &pl = plan[v];
+            const NdPlan &pl = c.nd[v];
             dev_release(s, s->d_nd_map[v]); dev_release(s, s->d_nd_tab[v]); dev_release(s, s->d_nd_bs[v]);
             s->d_nd_map[v] = nullptr; s->d_nd_tab[v] = nullptr; s->d_nd_bs[v] = nullptr;
             const int4 *map = nullptr;
@@ -402,7 +349,7 @@ static int build_columns(tscm_solver *s)
         }
         s->lds_solve = std::max(s->lds_nd[0], s->lds_nd[1]);
     }
-    if (C > kMaxCamLds) s->lds_solve = solve_big_lds_bytes((n_act + 15) & ~15, n_pad);
+    if (s->C > kMaxCamLds) s->lds_solve = solve_big_lds_bytes((c.n_act + 15) & ~15, s->n_pad);
     return 0;
 }
 
@@ -420,9 +367,12 @@ extern "C" int tscm_solver_set_fixed_intrinsics(tscm_solver *s, const unsigned s
     std::vector<unsigned short> f(s->C, 0);
     if (fixed) f.assign(fixed, fixed + s->C);
     if (f == s->fixed) return 0;
-    const std::vector<unsigned short> before = s->fixed;
+    // planned first: a refusal leaves the solver as it was
+    ColumnPlan c;
+    std::string err;
+    if (int rc = plan_columns(s->L, s->C, f.data(), c, err)) return fail(rc, err);
+    if (int rc = apply_columns(s, c)) return rc;
     s->fixed = f;
-    if (int rc = build_columns(s)) { s->fixed = before; (void)build_columns(s); return rc; }
     return 0;
 }
 
@@ -543,7 +493,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     up(&P.pair_i, L.pair_i); up(&P.pair_j, L.pair_j); up(&P.pc_begin, L.pc_begin); up(&P.pc_end, L.pc_end); up(&P.pc_tile, L.pc_tile);
     up(&P.bid_part_ptr, L.bid_part_ptr); up(&P.pair_board, L.pair_board); up(&P.bc_tile, L.bc_tile); up(&P.bc_desc, bc_desc);
     up(&P.bid_lut, bid_lut); up(&P.board_const, L.board_const);
-    // written by build_columns
+    // written by apply_columns
     s->fixed.assign(C, 0);
     al(&P.col_active, s->n_pad); al(&P.col_ctl, (size_t)16 * kMaxCam); al(&P.act_map, s->n_pad);
 
@@ -586,11 +536,18 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     s->eval32 = f32_kernel(g4.ks, g4.passes > 1, false); s->eval32r = f32_kernel(g4.ks, g4.passes > 1, true);
     if (s->lds_eval32 > 64 * 1024)
         for (EvalKernel k : { s->eval32, s->eval32r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
-    // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory
+    // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory.
+    // The columns of the creation plan (no held intrinsics) are every camera-side column that can be free: held intrinsics
+    // only ever take columns away, so the sizes below hold for every mask
+    ColumnPlan cols;
+    {
+        std::string err;
+        if ((rc = plan_columns(L, C, nullptr, cols, err))) return fail(rc, err);
+    }
     if (C <= kDense4Cams) {
-        // where every thread of k_solve_reduced finds its operands (written by build_columns)
+        // where every thread of k_solve_reduced finds its operands (written by apply_columns)
         int4 *map = nullptr;
-        if ((rc = dev_alloc(s, &map, (size_t)(kSolveMapSlots / 4) * 256))) return rc;
+        if ((rc = dev_alloc(s, &map, (size_t)(kSolveMapSlots / 4) * kSolveMapThreads))) return rc;
         P.solve_map = map;
         const size_t NN = 64, TT = 4, NPD = 64;
         s->lds_dense4 = sizeof(double) * (NN * (NN + 2) + 2 * (NN / TT) * (TT * TT + 2) + 2 * NN + 3 * NPD);
@@ -599,16 +556,13 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         s->dev.dense4_resident = per_cu * prop.multiProcessorCount;
     }
     if (C > kMaxCamLds) {
-        // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory, sized for every camera-side column free
-        // (held intrinsics only ever take columns away)
-        int n_max = 0;
-        for (int m = 0; m < C; ++m) if (L.cam_active[m]) n_max += L.cam_const[m] ? kFA - 6 : kFA;
-        const int NN = (n_max + 15) & ~15;
+        // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory
+        const int NN = (cols.n_act + 15) & ~15;
         const size_t lds_max = solve_big_lds_bytes(NN, s->n_pad);
         if ((rc = dev_alloc(s, &S.Abig, (size_t)256 * (NN / 16 + 1) * (NN / 16 + 2) / 2))) return rc;      // packed lower triangle of 16x16 blocks, incl. the rhs block row
         if (lds_max > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_reduced_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
     }
-    if ((rc = build_columns(s))) return rc;
+    if ((rc = apply_columns(s, cols))) return rc;
     if (s->lds_eval > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board has too many corners for the LDS board-point tile");
     HIP_TRY(hipDeviceSynchronize());
     *out = sp.release();
