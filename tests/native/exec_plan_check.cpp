@@ -5,74 +5,26 @@
 //   usage: exec_plan_check rows                         one JSON line: per row, the facts the Python test asserts
 //          exec_plan_check random <seed> <problems>     one JSON line: counts of what the problems exercised
 //          exec_plan_check refusals                     one JSON line: code and message of every refusal case
-#include "../../tscm_calib_amd/csrc/tscm_layout.h"
-#include "../../tscm_calib_amd/csrc/tscm_exec_plan.h"
+#include "exec_problems.h"
+#include "../../tscm_calib_amd/csrc/tscm_launch_seq.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
 #include <string>
-#include <vector>
 
 using namespace tscm;
 
-// a problem's view tables (the parameter arrays only need to be non-NULL: the plan does not read them)
-struct Prob {
-    int C = 1, B = 0, n_points = 54;
-    std::vector<int> cam, board, offset, count;
-    double dummy[2] = { 0.0, 0.0 };
-    tscm_problem p{};
-    void add(int c, int b, int n) { offset.push_back(offset.empty() ? 0 : offset.back() + count.back()); cam.push_back(c); board.push_back(b); count.push_back(n); }
-    Layout plan(int n_cu = 256) {
-        p = tscm_problem{};
-        p.n_cameras = C; p.n_boards = B; p.n_points = n_points; p.n_views = (int)cam.size();
-        p.board_xy = dummy; p.intr = dummy; p.board_rt = dummy; p.cam_rt = dummy; p.obs_u = dummy; p.obs_v = dummy;
-        p.view_camera = cam.data(); p.view_board = board.data(); p.view_offset = offset.data(); p.view_count = count.data();
-        Layout L;
-        std::string err;
-        LayoutDevice dev;
-        dev.n_cu = n_cu; dev.waves_per_cu = 16;
-        if (plan_layout(&p, 0, 1, dev, L, err)) { std::fprintf(stderr, "plan_layout: %s\n", err.c_str()); std::exit(2); }
-        return L;
-    }
-};
-
-// a ring of C cameras: board b is seen by cameras b mod C and b + 1 mod C (and by `extra` more cameras every 10th board)
-static Prob ring(int C, int B, int extra = 0)
+// kernel launches of one iteration whose evaluation is a candidate's (the exchange markers not counted): seq_iteration's list
+static int launches(const ExecPlan &x, const Layout &L, int C)
 {
-    Prob q;
-    q.C = C; q.B = B;
-    for (int b = 0; b < B; ++b) {
-        const int k = 2 + (b % 10 == 0 ? extra : 0);
-        for (int i = 0; i < k && i < C; ++i) q.add((b + i) % C, b, q.n_points);
-    }
-    return q;
-}
-
-static ExecDevice ample()
-{
-    ExecDevice d;
-    for (int nv = 1; nv <= 3; ++nv) d.schur_resident[nv] = d.schur_resident_ride[nv] = 1 << 20;
-    d.dense4_resident = d.nd_resident[0] = d.nd_resident[1] = 1 << 20;
-    d.nd_tpt[0] = 2; d.nd_tpt[1] = 1;
-    return d;
-}
-
-static int nv_classes(const Layout &L) { return (L.nv_chunks[1] ? 1 : 0) + (L.nv_chunks[2] ? 1 : 0) + (L.nv_chunks[3] ? 1 : 0); }
-static int used_nv(const Layout &L) { return L.nv_chunks[1] ? 1 : L.nv_chunks[2] ? 2 : 3; }
-
-// kernel launches of one iteration whose evaluation is a candidate's (the exchanges not counted): DESIGN 4's table
-static int launches(const ExecPlan &x, const Layout &L)
-{
-    int n = (L.slow_boards.empty() ? 0 : 1) + nv_classes(L) + (L.pc_begin.empty() ? 0 : 1);
-    n += L.n_bids && !x.t_in_solve ? 1 : 0;
-    n += 1 + (x.bs_threads ? 1 : 0) + 1;                 // reduced solve, back-substitution of its own, Gram kernel
-    switch (x.tail) {
-    case EvalTail::Ride: break;
-    case EvalTail::StatsThenHead: case EvalTail::ReduceControl: n += 1; break;
-    case EvalTail::Exchange: n += 2 + (x.ctl_in_schur ? 0 : 1); break;
-    }
+    SeqState st;
+    LaunchList q;
+    seq_begin(L, C, x, Start::Current, st, q);
+    seq_iteration(L, C, x, ample(), 0, st, q);
+    int n = 0;
+    for (int i = 0; i < q.n; ++i) n += is_exchange(q.at[i].k) ? 0 : 1;
     return n;
 }
 
@@ -82,11 +34,11 @@ static std::string g_fail;
 static const char *solver_name(Solver s) { return s == Solver::Empty ? "empty" : s == Solver::Dense4 ? "dense4" : s == Solver::Nd ? "nd" : "big"; }
 static const char *tail_name(EvalTail t) { return t == EvalTail::Ride ? "ride" : t == EvalTail::StatsThenHead ? "stats_head" : t == EvalTail::ReduceControl ? "reduce_control" : "exchange"; }
 
-static void row(const char *name, const ExecPlan &x, const Layout &L, bool last = false)
+static void row(const char *name, const ExecPlan &x, const Layout &L, int C, bool last = false)
 {
     std::printf("\"%s\": {\"launches\": %d, \"tail\": \"%s\", \"ctl_in_schur\": %d, \"stats_ride\": %d, \"t_in_solve\": %d, \"solver\": \"%s\", "
                 "\"nd\": %d, \"tpt\": %d, \"n_prod\": %d, \"n_bs\": %d, \"n_bs_blocks\": %d, \"bs_threads\": %d, \"comm\": %d, \"gram\": %d}%s",
-                name, launches(x, L), tail_name(x.tail), x.ctl_in_schur, x.stats_ride, x.t_in_solve, solver_name(x.solver), x.nd, x.tpt,
+                name, launches(x, L, C), tail_name(x.tail), x.ctl_in_schur, x.stats_ride, x.t_in_solve, solver_name(x.solver), x.nd, x.tpt,
                 x.n_prod, x.n_bs, L.n_bs_blocks, x.bs_threads, x.comm, (int)x.gram, last ? "" : ", ");
 }
 
@@ -97,13 +49,13 @@ static int rows()
     {   // config 4: 4 cameras, every board seen by two of them, ample residency
         const Layout L = ring(4, 5000).plan();
         const ExecDevice d = ample();
-        row("config4", plan_exec(L, 4, 48, none, 0, 0, 0, 58, d), L);
-        row("config4_separate_stats", plan_exec(L, 4, 48, none, TSCM_EXEC_SEPARATE_STATS, 0, 0, 58, d), L);
-        row("config4_comm", plan_exec(L, 4, 48, kCommShared, 0, 0, 0, 58, d), L);
-        row("config4_one_rank_comm", plan_exec(L, 4, 48, kCommOneRank, 0, 0, 0, 58, d), L);
-        row("config4_keep_one_rank_comm", plan_exec(L, 4, 48, kCommOneRank, TSCM_EXEC_KEEP_SINGLE_RANK_COMM, 0, 0, 58, d), L);
-        row("config4_graph_order", plan_exec(L, 4, 48, none, TSCM_EXEC_GRAPH_REDUCED_ORDER, 0, 0, 58, d), L);
-        row("config4_dense_order", plan_exec(L, 4, 48, none, TSCM_EXEC_DENSE_REDUCED_ORDER, 0, 0, 58, d), L);
+        row("config4", plan_exec(L, 4, 48, none, 0, 0, 0, 58, d), L, 4);
+        row("config4_separate_stats", plan_exec(L, 4, 48, none, TSCM_EXEC_SEPARATE_STATS, 0, 0, 58, d), L, 4);
+        row("config4_comm", plan_exec(L, 4, 48, kCommShared, 0, 0, 0, 58, d), L, 4);
+        row("config4_one_rank_comm", plan_exec(L, 4, 48, kCommOneRank, 0, 0, 0, 58, d), L, 4);
+        row("config4_keep_one_rank_comm", plan_exec(L, 4, 48, kCommOneRank, TSCM_EXEC_KEEP_SINGLE_RANK_COMM, 0, 0, 58, d), L, 4);
+        row("config4_graph_order", plan_exec(L, 4, 48, none, TSCM_EXEC_GRAPH_REDUCED_ORDER, 0, 0, 58, d), L, 4);
+        row("config4_dense_order", plan_exec(L, 4, 48, none, TSCM_EXEC_DENSE_REDUCED_ORDER, 0, 0, 58, d), L, 4);
     }
     {   // 8-camera ring whose Schur grid is more than one resident round: the back-substitution rides iff all of it fits
         const Layout L = ring(8, 5000).plan();
@@ -111,49 +63,31 @@ static int rows()
         d.schur_resident_ride[2] = std::max(reduction_blocks(L, 8), L.nv_chunks[2]);       // one short of the riding grid
         ExecPlan x = plan_exec(L, 8, 100, none, 0, 0, 0, 58, d);
         d.nd_resident[0] = 1 + x.n_prod + L.n_bs_blocks;
-        row("ring8_bs_fits", plan_exec(L, 8, 100, none, 0, 0, 0, 58, d), L);
+        row("ring8_bs_fits", plan_exec(L, 8, 100, none, 0, 0, 0, 58, d), L, 8);
         d.nd_resident[0] -= 1;
-        row("ring8_bs_one_short", plan_exec(L, 8, 100, none, 0, 0, 0, 58, d), L);
-        row("ring8_comm", plan_exec(L, 8, 100, kCommShared, 0, 0, 0, 58, ample()), L);
+        row("ring8_bs_one_short", plan_exec(L, 8, 100, none, 0, 0, 0, 58, d), L, 8);
+        row("ring8_comm", plan_exec(L, 8, 100, kCommShared, 0, 0, 0, 58, ample()), L, 8);
     }
     {   // 12-camera rig: k_solve_reduced_big, the T reduction and the back-substitution on launches of their own
         const Layout L = ring(12, 3000).plan();
-        row("rig12", plan_exec(L, 12, 150, none, 0, 0, 0, 58, ample()), L);
-        row("rig12_comm", plan_exec(L, 12, 150, kCommShared, 0, 0, 0, 58, ample()), L);
+        row("rig12", plan_exec(L, 12, 150, none, 0, 0, 0, 58, ample()), L, 12);
+        row("rig12_comm", plan_exec(L, 12, 150, kCommShared, 0, 0, 0, 58, ample()), L, 12);
     }
     {   // boards seen by four cameras: k_schur_factor + k_pair_gram, the control step out of the Schur head
         const Layout L = ring(4, 2000, 2).plan();
         std::printf("\"slow_boards\": %d, ", (int)L.slow_boards.size());
-        row("seen_by_four", plan_exec(L, 4, 48, none, 0, 0, 0, 58, ample()), L);
-        row("seen_by_four_comm", plan_exec(L, 4, 48, kCommShared, 0, 0, 0, 58, ample()), L);
+        row("seen_by_four", plan_exec(L, 4, 48, none, 0, 0, 0, 58, ample()), L, 4);
+        row("seen_by_four_comm", plan_exec(L, 4, 48, kCommShared, 0, 0, 0, 58, ample()), L, 4);
     }
     {   // no free camera-side column
         const Layout L = ring(4, 500).plan();
-        row("empty", plan_exec(L, 4, 0, none, 0, 0, 0, 58, ample()), L, true);
+        row("empty", plan_exec(L, 4, 0, none, 0, 0, 0, 58, ample()), L, 4, true);
     }
     std::printf("}\n");
     return 0;
 }
 
 // ---- random problems -------------------------------------------------------------------------------
-static Prob random_problem(std::mt19937_64 &rng)
-{
-    auto uni = [&](int lo, int hi) { return (int)std::uniform_int_distribution<int>(lo, hi)(rng); };
-    Prob q;
-    q.C = uni(0, 2) == 0 ? uni(1, 32) : uni(1, 9);
-    q.n_points = uni(4, 90);
-    q.B = uni(0, 3) == 0 ? uni(0, 12) : uni(100, 2000);
-    const int wide = uni(0, 3) == 0;          // boards seen by more than three cameras
-    for (int b = 0; b < q.B; ++b) {
-        int k = uni(0, 9) < 1 ? 0 : wide && uni(0, 4) == 0 ? uni(4, 8) : uni(1, 3);
-        if (!wide) k = std::min(k, uni(0, 1) ? 2 : 3);
-        k = std::min(k, q.C);
-        const int m0 = uni(0, q.C - 1);
-        for (int i = 0; i < k; ++i) q.add((m0 + i) % q.C, b, uni(1, q.n_points));
-    }
-    return q;
-}
-
 // the fields of a plan, one bit each, for "a flag changes only what it names"
 enum { F_COMM = 1, F_GRAM = 2, F_ROBUST = 4, F_TAIL = 8, F_CTL = 16, F_RIDE = 32, F_TSOLVE = 64, F_SOLVER = 128, F_ND = 256, F_TPT = 512,
        F_PROD = 1024, F_BS = 2048, F_BSTH = 4096 };
@@ -242,15 +176,11 @@ static int random_run(unsigned long long seed, int problems)
             ExecDevice d = ample();
             d.nd_tpt[0] = uni(1, 2); d.nd_tpt[1] = uni(1, 2);
             const int kind = uni(0, 2), flags = uni(0, 1) ? 0 : uni(0, TSCM_EXEC_ALL);
-            if (trial % 3 == 1) {
-                for (int nv = 1; nv <= 3; ++nv) { d.schur_resident[nv] = uni(1, 4000); d.schur_resident_ride[nv] = uni(1, 4000); }
-                d.dense4_resident = uni(1, 2000); d.nd_resident[0] = uni(1, 2000); d.nd_resident[1] = uni(1, 2000);
-            } else if (trial % 3 == 2) {
+            if (trial % 3 == 1) random_residency(rng, d);
+            else if (trial % 3 == 2) {
                 const int below = uni(0, 1);
                 const ExecPlan x0 = plan_exec(L, C, n_act, kind, flags, fp32, loss, rp, d);
-                d.dense4_resident = d.nd_resident[0] = d.nd_resident[1] = 1 + x0.n_prod + L.n_bs_blocks - below;
-                const int nv = used_nv(L);
-                d.schur_resident_ride[nv] = std::max(reduction_blocks(L, C), L.nv_chunks[nv]) + 1 - below;
+                limit_residency(L, C, x0, below, d);
                 const ExecPlan x = plan_exec(L, C, n_act, kind, flags, fp32, loss, rp, d);
                 const bool could_bs = (x.solver == Solver::Dense4 || x.solver == Solver::Nd) && L.bs_threads == 256 && L.n_bs_blocks > 0 && !(flags & TSCM_EXEC_SEPARATE_BACKSUB);
                 if (could_bs) { CHECK((x.n_bs > 0) == !below); ++g_count[C_BS_LIMIT]; }

@@ -1,6 +1,6 @@
 // tscm_exec_plan.h -- host side of a solve's launch sequence: which kernels one LM iteration enqueues and where the
 // hand-offs between them ride, decided once per solve from the layout, the options and the residency figures measured at
-// creation.  Plain C++17 like tscm_layout.h; tscm_solver.hip's enqueue code reads the plan, and
+// creation.  Plain C++17 like tscm_layout.h; tscm_launch_seq.h turns the plan into the launches, and
 // tests/native/exec_plan_check.cpp checks it against the launch table of DESIGN 4 on the CPU.
 #ifndef TSCM_EXEC_PLAN_H
 #define TSCM_EXEC_PLAN_H
@@ -14,7 +14,9 @@ namespace tscm {
 
 constexpr int kCamSl = 16;         // the per-camera tile reduction runs in slices of 32 of the 512 raw entries: C * kCamSl workgroups
 constexpr int kTSlices = 16;       // slices of the T reduction (k_T_reduce and its fused form)
+constexpr int kTEntries = 64;      // entries of a tile per workgroup of k_T_reduce: n_bids * 256 / kTEntries workgroups
 constexpr int kFusedEntries = 256 / kTSlices;        // fused T reduction: 16 entries x 16 slices = the solver's 256 threads
+constexpr int kVPrepThreads = 128; // workgroup of k_view_prep / k_begin_view_prep: a thread per view or camera
 constexpr int kDense4Cams = 4;     // rigs of up to 4 cameras: k_solve_reduced factors the reduced system as one dense block
 
 // Bits of k_schur_gram's `ctl` argument, and of the host's eval_pending: an evaluation waits for its control step, which

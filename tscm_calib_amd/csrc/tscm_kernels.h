@@ -31,6 +31,7 @@
 #include "tscm_layout.h"
 #include "tscm_exec_plan.h"
 #include "tscm_columns.h"
+#include "tscm_ctrl.h"
 
 namespace tscm {
 
@@ -63,7 +64,6 @@ constexpr int kCStride = 72;       // doubles per camera record in cconst: 48 do
 constexpr int kCst = 80;           // LDS constant block: [0,27) view, [27,75) camera
 constexpr int kScal = 8;           // scalars appended to H_stage
 constexpr int kStStride = 16;      // doubles between the board-statistics partials of two workgroups: a 128-byte line each (written by ONE workgroup: see k_schur_gram<NV, true>)
-constexpr int kMaxLog = 256;
 
 // phase stamps of the fused kernels (make PHASES=1: -DTSCM_PHASE_PROFILE; s_memrealtime, 10 ns ticks; one line per
 // launch from workgroups 0 and 200 -- profiling builds only)
@@ -136,36 +136,7 @@ __device__ __forceinline__ const double *rec_w(const double *rec, int slot) { re
 __device__ __forceinline__ const double *rec_e(const double *rec, int V, int slot) { return rec + (size_t)kRecW * V + (size_t)kRecE * slot; }
 __device__ __forceinline__ const double *rec_g(const double *rec, int V, int slot) { return rec + (size_t)(kRecW + kRecE) * V + (size_t)kRecG * slot; }
 
-struct Options {
-    int max_num_iterations;
-    double function_tolerance, gradient_tolerance, parameter_tolerance;
-    double initial_radius, max_radius, min_radius;
-    double min_relative_decrease, min_lm_diagonal, max_lm_diagonal;
-    int max_invalid;
-    int jacobi_scaling;
-};
-
-struct IterLog {
-    int iteration, step_is_valid, step_is_successful, pad;
-    double cost, cost_change, gradient_max_norm, gradient_norm, step_norm, relative_decrease, radius;
-};
-
 enum TermReason { kNone = 0, kMaxIter, kGradTol, kMinRadius, kParamTol, kFuncTol, kInvalidSteps };
-
-struct CtrlHead {
-    // ---- header (polled by the host) ----
-    int done, term_type, term_reason, iteration;
-    int cur, lin_fail, num_successful, num_unsuccessful;
-    int num_invalid, n_log, lm_iterations, fin_count;   // fin_count: arrival counter of k_reduce_control
-    int fault, pad0;                    // fault: a device-side hand-off timed out (sticky; the host turns it into TSCM_E_HIP)
-    double radius, decrease_factor;
-    double x_cost, x_norm, gmax, gnorm;
-    double model_cam, stepsq_cam;
-    double se_min, se_cur, se_ref, se_cand, se_acc_ref, se_acc_cand;
-    double initial_cost;
-    Options opt;
-    long long t_begin, t_end;           // s_memrealtime (100 MHz) in k_begin_solve / k_end_solve: device time of the solve
-};
 
 struct Ctrl : CtrlHead {
     IterLog log[kMaxLog];
@@ -372,7 +343,6 @@ __device__ __forceinline__ void write_camera_record(const DevState &S, int tgt, 
 constexpr int kVStride = 48;      // doubles per view record in vconst: 27 doubles (+5 pad), then at byte 256 the same 27 values as
                                   // floats (read by the fp32-Jacobian kernel): 384 bytes
 constexpr int kVFloatOff = 32;    // offset of the float copy, in doubles
-constexpr int kVPrepThreads = 128;
 
 // (the point's parameters come from explicit arrays: buffer `tgt` -- or, in the first launch of a solve, the registered start point)
 __device__ __forceinline__ void view_prep_body(const DevProblem &P, const DevState &S, int tgt, int with_floats, const double *cam_rt, const double *intr, const double *board_rt)
@@ -2004,7 +1974,7 @@ __global__ __launch_bounds__(256) void k_pair_gram(DevProblem P, DevState S)
     S.pairpart[(size_t)256 * P.pc_tile[pc] + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
 }
 
-constexpr int kTEntries = 64;       // (kTSlices: tscm_exec_plan.h)
+// (kTEntries, kTSlices: tscm_exec_plan.h)
 // block blk of a (n_bids * 256 / ENTRIES)-block grid of ENTRIES * kTSlices threads, partial tiles [cb, ce) of its
 // camera-pair block; the summation order of an entry depends on kTSlices only, so every geometry produces the same bits
 template <int ENTRIES>

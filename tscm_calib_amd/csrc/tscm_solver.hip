@@ -8,6 +8,7 @@
 // iteration costs no host<->device round trip.
 #include "tscm/tscm.h"
 #include "tscm_kernels.h"
+#include "tscm_launch_seq.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -148,14 +149,11 @@ struct tscm_solver {
     bool have_init = false;
     Ctrl *h_ctrl = nullptr;             // pinned
     Ctrl *d_h_ctrl = nullptr;           // ... and its address on the device (k_finish_solve writes the control block there itself)
-    size_t lds_eval = 0, lds_eval32 = 0, lds_solve = 0, lds_gram = 0, lds_bs = 0;
+    size_t lds_eval = 0, lds_eval32 = 0, lds_solve = 0, lds_bs = 0;
     ExecDevice dev;                     // residency figures of the launches whose workgroups wait for each other (tscm_exec_plan.h)
-    ExecPlan xp;                        // the launch sequence of the solve in progress (plan_exec)
-    int ctl_epoch = 0;                  // control steps taken in k_schur_gram's head in this solve so far
-    int stats_epoch = 0;                // launches of k_schur_gram<NV, true> in this solve so far (S.ctl_pub->stats_arrived counts their reduction workgroups)
-    int eval_pending = 0;               // an evaluation is waiting for its control step in the next k_schur_gram: its kCtl* bits
-    int t_epoch = 0;                    // fused launches of this solve so far (the hand-off counter is monotonic)
-    int withhold = 0, withhold_next = 0; // this solve / the next one: fault injection (tscm_solver_debug_withhold_handoff)
+    ExecPlan xp;                        // the launch plan of the solve in progress (plan_exec)
+    CtrlHead head;                      // ... and the control block it starts from (ctrl_head_from_options)
+    int withhold = 0, withhold_next = 0; // this solve / the next one: fault injection, 0 or kWithhold* (tscm_solver_debug_withhold_handoff)
     int n_reruns = 0;                   // solves that were run again on separate launches after a late hand-off
     bool no_rerun = false, no_rerun_next = false;      // fault injection: the late hand-off of this / the next solve stays an error
     tscm_comm *comm_reg = nullptr;      // what tscm_solver_set_comm registered; `comm` is what the current solve uses
@@ -582,7 +580,7 @@ static CommKind comm_kind(const tscm_comm *c) { return !c ? kCommNone : c->world
 extern "C" int tscm_solver_debug_withhold_handoff(tscm_solver *s, int on)
 {
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
-    s->withhold_next = on == 3 ? 2 : on ? 1 : 0;      // (3: a reduction block riding in the Schur-complement launch, not a producer of the tiles)
+    s->withhold_next = on == 3 ? kWithholdStats : on ? kWithholdProducer : 0;      // (3: a reduction block riding in the Schur-complement launch, not a producer of the tiles)
     s->no_rerun_next = on == 2;          // 2: ... and the solve is NOT run again on separate launches (the error path itself)
     return 0;
 }
@@ -797,8 +795,15 @@ static int comm_check(tscm_comm *c)
     return 0;
 }
 
+// the members of a run and, per member, the launch sequence of the phase in progress (tscm_launch_seq.h)
+struct LmSeq {
+    SeqState st;
+    LaunchList todo;
+    int at = 0;                         // next entry of todo to enqueue
+};
 struct LmRun {
     std::vector<tscm_solver *> m;
+    std::vector<LmSeq> seq;             // [m.size()], sized once per solve
 };
 
 static int exchange(LmRun &run, bool t_buffer)
@@ -822,104 +827,92 @@ static int exchange(LmRun &run, bool t_buffer)
     return 0;
 }
 
-// evaluation of the target point: pose constants, Gram kernel, reductions, statistics (+ all-reduce + control): ExecPlan::tail
-static int enqueue_eval(LmRun &run, int cand, int init, int have_backsub, bool have_view_constants = false)
+// The only place the LM loop's kernels are launched: one entry of a launch sequence -> its kernel, workgroup size, LDS and
+// arguments (the exchange markers are walk()'s)
+static int enqueue(tscm_solver *s, const Launch &l)
 {
-    for (tscm_solver *s : run.m) {
-        const DevProblem &P = s->P;
-        DevState &S = s->S;
-        const int nr = P.C * kCamSl + S.n_st_blocks;
-        // the constants of a candidate point were written by k_backsub_prep; the initial point needs them here
-        if (!have_backsub && !have_view_constants) hipLaunchKernelGGL(k_view_prep, dim3((P.V + P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, P, S, cand, s->xp.f32() ? 1 : 0);
-        if (int rc = launch_eval(s, cand)) return rc;
-        const EvalTail t = s->xp.tail;
-        // a candidate's reductions ride in the next k_schur_gram<NV, true>
-        if (t == EvalTail::Ride && !init) s->eval_pending = kCtlOneGpu | kCtlRide;
-        else if (t == EvalTail::ReduceControl) hipLaunchKernelGGL(k_reduce_control, dim3(nr), dim3(256), 0, s->stream, P, S, cand, init, have_backsub);
-        else {
-            hipLaunchKernelGGL(k_reduce_stats, dim3(nr), dim3(256), 0, s->stream, P, S, cand, init);
-            if (t == EvalTail::Exchange) hipLaunchKernelGGL(k_finalize_eval, dim3(P.C + 1), dim3(256), 0, s->stream, P, S, have_backsub);
-            // ... or the reductions alone: the next k_schur_gram takes the control step in its head (k_control_tail behind the last
-            // evaluation of the solve).  Round 5: the solve's INITIAL evaluation as well (IterationZero in the head of the first
-            // Schur kernel) -- k_reduce_control's last workgroup cost every solve 18.4 us where k_reduce_stats takes 5.5 and the head 4.4
-            else s->eval_pending = kCtlOneGpu | (init ? kCtlInit : 0);
-        }
+    const DevProblem &P = s->P;
+    const DevState &S = s->S;
+    hipStream_t st = s->stream;
+    const dim3 grid(l.grid);
+    auto schur = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, P, S, l.chunk0, l.ctl, l.first_round, l.ce, l.target, l.n_chunks); };
+    auto nd = [&](auto kernel) {
+        const int v = l.nd;
+        hipLaunchKernelGGL(kernel, grid, dim3(kNdThreads), std::max(s->lds_nd[v], l.n_bs ? s->lds_bs : (size_t)0), st, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v],
+                           s->plan[v].dims(), l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32);
+    };
+    const size_t lds_dense4 = std::max(s->lds_dense4, l.n_bs ? s->lds_bs : (size_t)0);
+    switch (l.k) {
+    case Kern::BeginViewPrep: {
+        const bool init = l.start == Start::Init, bak = l.start == Start::Backup;
+        hipLaunchKernelGGL(k_begin_view_prep, grid, dim3(kVPrepThreads), 0, st, P, S, s->head,
+                           init ? s->d_init_cam : bak ? s->d_start_cam : nullptr, init ? s->d_init_intr : bak ? s->d_start_intr : nullptr,
+                           init ? s->d_init_board : bak ? s->d_start_board : nullptr,
+                           bak ? nullptr : s->d_start_cam, bak ? nullptr : s->d_start_intr, bak ? nullptr : s->d_start_board, l.f32);
+        break;
     }
-    if (run.m[0]->xp.tail != EvalTail::Exchange) return 0;
-    if (int rc = exchange(run, /*t_buffer=*/false)) return rc;
-    for (tscm_solver *s : run.m) {
-        // behind the all-reduce: k_control -- or, for a candidate's evaluation, the head of the next k_schur_gram
-        if (s->xp.ctl_in_schur && cand && !init) s->eval_pending = kCtlComm;
-        else hipLaunchKernelGGL(k_control, dim3(1), dim3(256), 0, s->stream, s->P, s->S, init);
+    case Kern::Eval: return launch_eval(s, l.cand);
+    case Kern::ReduceControl: hipLaunchKernelGGL(k_reduce_control, grid, dim3(256), 0, st, P, S, l.cand, l.init, l.have_backsub); break;
+    case Kern::ReduceStats: hipLaunchKernelGGL(k_reduce_stats, grid, dim3(256), 0, st, P, S, l.cand, l.init); break;
+    case Kern::FinalizeEval: hipLaunchKernelGGL(k_finalize_eval, grid, dim3(256), 0, st, P, S, l.have_backsub); break;
+    case Kern::Control: hipLaunchKernelGGL(k_control, grid, dim3(256), 0, st, P, S, l.init); break;
+    case Kern::SchurFactor: hipLaunchKernelGGL(k_schur_factor, grid, dim3(256), 0, st, P, S); break;
+    case Kern::Schur1: schur(k_schur_gram<1>); break;
+    case Kern::Schur2: schur(k_schur_gram<2>); break;
+    case Kern::Schur3: schur(k_schur_gram<3>); break;
+    case Kern::SchurRide1: schur(k_schur_gram<1, true>); break;
+    case Kern::SchurRide2: schur(k_schur_gram<2, true>); break;
+    case Kern::SchurRide3: schur(k_schur_gram<3, true>); break;
+    case Kern::PairGram: hipLaunchKernelGGL(k_pair_gram, grid, dim3(256), 0, st, P, S); break;
+    case Kern::TReduce: hipLaunchKernelGGL(k_T_reduce, grid, dim3(kTEntries * kTSlices), 0, st, P, S); break;
+    case Kern::SolveDense4: hipLaunchKernelGGL((k_solve_reduced<4, 16, 64>), grid, dim3(256), lds_dense4, st, P, S, l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32); break;
+    case Kern::SolveDense4Ride: hipLaunchKernelGGL((k_solve_reduced<4, 16, 64, true>), grid, dim3(256), lds_dense4, st, P, S, l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32); break;
+    case Kern::SolveNd1: nd(k_solve_nd<1, false>); break;
+    case Kern::SolveNd2: nd(k_solve_nd<2, false>); break;
+    case Kern::SolveNd1Ride: nd(k_solve_nd<1, true>); break;
+    case Kern::SolveNd2Ride: nd(k_solve_nd<2, true>); break;
+    // 9 to 32 cameras -- or no free camera-side column (every intrinsic held where the pose is, e.g. a mono problem refining board
+    // poses only): nothing to factor.  k_solve_reduced_big on the empty system runs no panel and writes the zero camera step, the
+    // unchanged candidate camera parameters and the linear-solve flag; the back-substitution moves the boards
+    case Kern::SolveBig: hipLaunchKernelGGL(k_solve_reduced_big, grid, dim3(kBigNT), s->lds_solve, st, P, S); break;
+    case Kern::SolveEmpty: hipLaunchKernelGGL(k_solve_reduced_big, grid, dim3(kBigNT), solve_big_lds_bytes(0, s->n_pad), st, P, S); break;
+    case Kern::Backsub128: hipLaunchKernelGGL(k_backsub_prep<128>, grid, dim3(128), s->lds_bs, st, P, S, l.f32); break;
+    case Kern::Backsub256: hipLaunchKernelGGL(k_backsub_prep<256>, grid, dim3(256), s->lds_bs, st, P, S, l.f32); break;
+    case Kern::FinishSolve: hipLaunchKernelGGL(k_finish_solve, grid, dim3(256), 0, st, P, S, l.init, l.have_backsub, s->C, s->B, s->d_h_ctrl); break;
+    case Kern::EndSolve: hipLaunchKernelGGL(k_end_solve, grid, dim3(256), 0, st, S, s->C, s->B); break;
+    case Kern::CopyCtrl: {
+        static_assert(sizeof(Ctrl) == sizeof(CtrlHead) + sizeof(IterLog) * kMaxLog, "the log follows the head without padding");
+        const size_t bytes = sizeof(CtrlHead) + sizeof(IterLog) * (size_t)std::min(s->head.opt.max_num_iterations + 1, kMaxLog);
+        HIP_TRY(hipMemcpyAsync(s->h_ctrl, S.ctrl, bytes, hipMemcpyDeviceToHost, st));
+        break;
+    }
+    case Kern::ExchangeT: case Kern::ExchangeH: break;
     }
     return 0;
 }
 
-// the Schur-complement kernel of one views-per-board class (NV = 1, 2, 3), if the layout has chunks of it; ctl: the
-// waiting evaluation's kCtl* bits (0: none), ce: its control epoch, target: the riding reductions' arrival count
-template <int NV>
-static void launch_schur(tscm_solver *s, int ctl, int ce, int target)
+// Enqueues the members' sequences of one phase (run.seq[r].todo) in rounds, member after member: a round of a member ends in
+// front of an evaluation (all members' Schur sides, solves, evaluations follow each other in turn on a LOCAL group's shared
+// stream) or at an exchange marker, where exchange() runs once for the run -- every member's sequence has the same markers
+static int walk(LmRun &run)
 {
-    const int n = s->L.nv_chunks[NV], c0 = s->L.nv_chunk0[NV], ns = s->P.C * kCamSl + s->S.n_st_blocks, arg = (ctl & ~kCtlRide) | (s->withhold == 2 ? kCtlWithhold : 0);
-    if (n && (ctl & kCtlRide)) hipLaunchKernelGGL((k_schur_gram<NV, true>), dim3(std::max(ns, n) + 1), dim3(256), s->lds_gram, s->stream, s->P, s->S, c0, arg, s->dev.schur_resident_ride[NV], ce, target, n);
-    else if (n) hipLaunchKernelGGL(k_schur_gram<NV>, dim3(n + (ctl ? 1 : 0)), dim3(256), s->lds_gram, s->stream, s->P, s->S, c0, ctl, s->dev.schur_resident[NV], ce, 0, n);
-}
-
-// the back-substitution as a launch of its own (ExecPlan::bs_threads: 0 none)
-static void launch_backsub(tscm_solver *s, int wf)
-{
-    if (s->xp.bs_threads == 128) hipLaunchKernelGGL(k_backsub_prep<128>, dim3(s->S.n_bs_blocks), dim3(128), s->lds_bs, s->stream, s->P, s->S, wf);
-    if (s->xp.bs_threads == 256) hipLaunchKernelGGL(k_backsub_prep<256>, dim3(s->S.n_bs_blocks), dim3(256), s->lds_bs, s->stream, s->P, s->S, wf);
-}
-
-static int enqueue_iteration(LmRun &run)
-{
-    for (tscm_solver *s : run.m) {
-        const DevProblem &P = s->P;
-        DevState &S = s->S;
-        const int ctl = s->eval_pending;                  // (ctl_in_schur: exactly one of the three variants is launched)
-        s->eval_pending = 0;
-        if (P.n_slow) hipLaunchKernelGGL(k_schur_factor, dim3((P.n_slow + 255) / 256), dim3(256), 0, s->stream, P, S);
-        const int ce = ctl ? ++s->ctl_epoch : 0;
-        const int target = (ctl & kCtlRide) ? (P.C * kCamSl + S.n_st_blocks) * ++s->stats_epoch : 0;
-        launch_schur<1>(s, ctl, ce, target); launch_schur<2>(s, ctl, ce, target); launch_schur<3>(s, ctl, ce, target);
-        if (P.n_pchunks) hipLaunchKernelGGL(k_pair_gram, dim3(P.n_pchunks), dim3(256), 0, s->stream, P, S);
-        if (P.n_bids && !s->xp.t_in_solve) hipLaunchKernelGGL(k_T_reduce, dim3(P.n_bids * (256 / kTEntries)), dim3(kTEntries * kTSlices), 0, s->stream, P, S);
-    }
-    if (int rc = exchange(run, /*t_buffer=*/true)) return rc;
-    for (tscm_solver *s : run.m) {
-        const DevProblem &P = s->P;
-        DevState &S = s->S;
-        const ExecPlan &x = s->xp;
-        const int wf = x.f32() ? 1 : 0;
-        // T producers, reduced solve and the waiting back-substitution workgroups in ONE launch where the plan puts them there
-        const bool ride = x.n_prod || x.n_bs;
-        const int epoch = ride ? ++s->t_epoch : 0, withhold = ride && s->withhold == 1 ? 1 : 0;
-        if (x.solver == Solver::Dense4) {
-            // up to 4 cameras, one dense block: the same launch shape with k_solve_reduced as the solver workgroup
-            if (ride)
-                hipLaunchKernelGGL((k_solve_reduced<4, 16, 64, true>), dim3(1 + x.n_prod + x.n_bs), dim3(256), std::max(s->lds_dense4, x.n_bs ? s->lds_bs : (size_t)0), s->stream,
-                                   P, S, epoch, withhold, x.n_prod, x.n_bs, wf);
-            else hipLaunchKernelGGL((k_solve_reduced<4, 16, 64>), dim3(1), dim3(256), s->lds_dense4, s->stream, P, S, 0, 0, 0, 0, 0);
-        } else if (x.solver == Solver::Nd) {
-            // 5 to 8 cameras (and TSCM_EXEC_GRAPH_ / _DENSE_REDUCED_ORDER): k_solve_nd on plan x.nd
-            const int v = x.nd;
-            const dim3 grid(1 + x.n_prod + x.n_bs);
-            const size_t lds = std::max(s->lds_nd[v], x.n_bs ? s->lds_bs : (size_t)0);
-            if (ride && x.tpt == 2) hipLaunchKernelGGL((k_solve_nd<2, true>), grid, dim3(kNdThreads), lds, s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), epoch, withhold, x.n_prod, x.n_bs, wf);
-            else if (ride) hipLaunchKernelGGL((k_solve_nd<1, true>), grid, dim3(kNdThreads), lds, s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), epoch, withhold, x.n_prod, x.n_bs, wf);
-            else if (x.tpt == 2) hipLaunchKernelGGL((k_solve_nd<2, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
-            else hipLaunchKernelGGL((k_solve_nd<1, false>), dim3(1), dim3(kNdThreads), s->lds_nd[v], s->stream, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v], s->plan[v].dims(), 0, 0, 0, 0, 0);
-        } else {
-            // 9 to 32 cameras -- or no free camera-side column (every intrinsic held where the pose is, e.g. a mono problem refining
-            // board poses only): nothing to factor.  k_solve_reduced_big on the empty system runs no panel and writes the zero camera
-            // step, the unchanged candidate camera parameters and the linear-solve flag; the back-substitution moves the boards
-            const size_t lds = x.solver == Solver::Empty ? solve_big_lds_bytes(0, s->n_pad) : s->lds_solve;
-            hipLaunchKernelGGL(k_solve_reduced_big, dim3(1), dim3(kBigNT), lds, s->stream, P, S);
+    for (LmSeq &q : run.seq) q.at = 0;
+    for (bool left = true; left;) {
+        left = false;
+        const Launch *mark = nullptr;
+        for (size_t r = 0; r < run.m.size(); ++r) {
+            LmSeq &q = run.seq[r];
+            for (const int from = q.at; q.at < q.todo.n; ++q.at) {
+                const Launch &l = q.todo.at[q.at];
+                if (is_exchange(l.k) || (l.k == Kern::Eval && q.at > from)) break;
+                if (int rc = enqueue(run.m[r], l)) return rc;
+            }
+            if (q.at < q.todo.n && is_exchange(q.todo.at[q.at].k)) mark = &q.todo.at[q.at++];
+            left = left || q.at < q.todo.n;
         }
-        launch_backsub(s, wf);
+        if (mark) if (int rc = exchange(run, mark->k == Kern::ExchangeT)) return rc;
     }
-    return enqueue_eval(run, /*cand=*/1, /*init=*/0, /*have_backsub=*/1);
+    return 0;
 }
 
 static const char *reason_message(int r)
@@ -1087,7 +1080,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     for (tscm_solver *s : run.m) {
         s->xp = plan_exec(s->L, s->C, s->P.n_act, comm_kind(s->comm_reg), opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev);
         s->comm = s->xp.comm ? s->comm_reg : nullptr;
-        s->eval_pending = s->ctl_epoch = s->stats_epoch = s->t_epoch = 0;
+        s->head = ctrl_head_from_options(opt);
         s->withhold = s->withhold_next; s->withhold_next = 0;
         if (!rerun) { s->no_rerun = s->no_rerun_next; s->no_rerun_next = false; }
     }
@@ -1104,41 +1097,20 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     }
     for (size_t r = 0; r < run.m.size(); ++r) std::memset(&sums[r], 0, sizeof(tscm_summary));
 
-    // control block (identical on every rank), counter of the fused T reduction, start point: one launch (k_begin_solve)
+    // plan -> walk, per phase: the start (k_begin_view_prep and the initial evaluation), the iterations with a poll of the
+    // control block every check_every, the end (one synchronisation for the whole solve)
     const double t0 = wall();
-    for (tscm_solver *s : run.m) {
-        CtrlHead h;
-        std::memset(&h, 0, sizeof(h));
-        h.radius = opt.initial_trust_region_radius;
-        h.decrease_factor = 2.0;
-        h.opt.max_num_iterations = opt.max_num_iterations;
-        h.opt.function_tolerance = opt.function_tolerance;
-        h.opt.gradient_tolerance = opt.gradient_tolerance;
-        h.opt.parameter_tolerance = opt.parameter_tolerance;
-        h.opt.initial_radius = opt.initial_trust_region_radius;
-        h.opt.max_radius = opt.max_trust_region_radius;
-        h.opt.min_radius = opt.min_trust_region_radius;
-        h.opt.min_relative_decrease = opt.min_relative_decrease;
-        h.opt.min_lm_diagonal = opt.min_lm_diagonal;
-        h.opt.max_lm_diagonal = opt.max_lm_diagonal;
-        h.opt.max_invalid = opt.max_num_consecutive_invalid_steps;
-        h.opt.jacobi_scaling = opt.jacobi_scaling;
-        // ... and the constants of the initial evaluation (k_view_prep's work) in the same launch
-        // (start point: the registered arrays with `reset`, buffer 0 otherwise, the backup of the first attempt on a re-run -- the
-        // first attempt leaves that backup behind)
-        const bool from_init = reset && !rerun;
-        hipLaunchKernelGGL(k_begin_view_prep, dim3((s->P.V + s->P.C + kVPrepThreads - 1) / kVPrepThreads), dim3(kVPrepThreads), 0, s->stream, s->P, s->S, h,
-                           rerun ? s->d_start_cam : from_init ? s->d_init_cam : nullptr, rerun ? s->d_start_intr : from_init ? s->d_init_intr : nullptr,
-                           rerun ? s->d_start_board : from_init ? s->d_init_board : nullptr,
-                           rerun ? nullptr : s->d_start_cam, rerun ? nullptr : s->d_start_intr, rerun ? nullptr : s->d_start_board, s->xp.f32() ? 1 : 0);
-    }
-
+    run.seq.assign(run.m.size(), LmSeq{});
+    // (start point: the registered arrays with `reset`, buffer 0 otherwise, the backup of the first attempt on a re-run)
+    const Start start = rerun ? Start::Backup : reset ? Start::Init : Start::Current;
+    for (size_t r = 0; r < run.m.size(); ++r) { tscm_solver *s = run.m[r]; seq_begin(s->L, s->C, s->xp, start, run.seq[r].st, run.seq[r].todo); }
     int rc;
-    if ((rc = enqueue_eval(run, /*cand=*/0, /*init=*/1, /*have_backsub=*/0, /*have_view_constants=*/true))) return rc;
+    if ((rc = walk(run))) return rc;
     const int check_every = std::max(1, opt.check_every);
     bool done = false;
     for (int it = 1; it <= opt.max_num_iterations && !done; ++it) {
-        if ((rc = enqueue_iteration(run))) return rc;
+        for (size_t r = 0; r < run.m.size(); ++r) { tscm_solver *s = run.m[r]; seq_iteration(s->L, s->C, s->xp, s->dev, s->withhold, run.seq[r].st, run.seq[r].todo); }
+        if ((rc = walk(run))) return rc;
         if (it % check_every == 0 && it < opt.max_num_iterations) {
             // every rank takes the same decisions from the same all-reduced bits: polling one member is enough
             HIP_TRY(hipMemcpyAsync(s0->h_ctrl, s0->S.ctrl, 64, hipMemcpyDeviceToHost, s0->stream));
@@ -1146,26 +1118,8 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
             done = s0->h_ctrl->done != 0;
         }
     }
-    // The end of the solve, enqueued behind the last iteration -- ONE synchronisation for the whole solve: the last evaluation's
-    // control step if the steps were taken in k_schur_gram's head, the accepted point into buffer 0, the control block and the
-    // iteration log to the host.  One GPU: one launch (k_finish_solve); communicator: k_control, k_end_solve and a copy.
-    static_assert(sizeof(Ctrl) == sizeof(CtrlHead) + sizeof(IterLog) * kMaxLog, "the log follows the head without padding");
-    const size_t ctrl_bytes = sizeof(CtrlHead) + sizeof(IterLog) * (size_t)std::min(opt.max_num_iterations + 1, kMaxLog);
-    for (tscm_solver *s : run.m) {
-        const int nb = std::min(256, (6 * std::max(s->B, s->C) + 255) / 256 + 1);
-        if (s->eval_pending & kCtlOneGpu) {
-            // (the reductions of the solve's last evaluation found no Schur kernel to ride in)
-            if (s->eval_pending & kCtlRide) hipLaunchKernelGGL(k_reduce_stats, dim3(s->P.C * kCamSl + s->S.n_st_blocks), dim3(256), 0, s->stream, s->P, s->S, 1, 0);
-            const int was_init = (s->eval_pending & kCtlInit) ? 1 : 0;
-            hipLaunchKernelGGL(k_finish_solve, dim3(nb + 1), dim3(256), 0, s->stream, s->P, s->S, was_init, !was_init, s->C, s->B, s->d_h_ctrl);
-            s->eval_pending = 0;
-            continue;
-        }
-        if (s->eval_pending == kCtlComm) hipLaunchKernelGGL(k_control, dim3(1), dim3(256), 0, s->stream, s->P, s->S, 0);
-        s->eval_pending = 0;
-        hipLaunchKernelGGL(k_end_solve, dim3(nb), dim3(256), 0, s->stream, s->S, s->C, s->B);
-        HIP_TRY(hipMemcpyAsync(s->h_ctrl, s->S.ctrl, ctrl_bytes, hipMemcpyDeviceToHost, s->stream));
-    }
+    for (size_t r = 0; r < run.m.size(); ++r) seq_finish(run.m[r]->L, run.m[r]->C, run.seq[r].st, run.seq[r].todo);
+    if ((rc = walk(run))) return rc;
     if ((rc = sync_stream(s0))) return rc;
     for (tscm_solver *s : run.m) if (s->stream != s0->stream) HIP_TRY(hipStreamSynchronize(s->stream));
     if ((rc = comm_check(s0->comm))) return rc;
