@@ -548,6 +548,34 @@ int tscm_poses_from_r1r2t(const double *Rt, const unsigned char *has, int n, dou
 int tscm_estimate_extrinsic(const double *intr9, const double *pix_u, const double *pix_v, const int *count,
                             int n_views, const double *worlds, int n_points, int board_w, int device,
                             double *Rt, int *n_estimated);
+/* Stage outputs of the same two launches, for tests and diagnostics.
+ * tscm_estimate_focal_rows: the arguments of tscm_estimate_focal, and gamma [n_views*board_h] receives
+ *   what the row kernel wrote for row i of image k at k*board_h + i: -1 for an image without a board,
+ *   -2 for a rejected row (t < 0 or nx^2 + ny^2 > 0.95, TS.cpp:149, :153), otherwise the sample (NaN
+ *   where the row holds a NaN: neither rejection test fires on it).  Both entry points run one host
+ *   helper, so tscm_estimate_focal's *focal / *n_used are the mean / number of the values >= 0 or NaN
+ *   here, summed in (image, row) order.
+ * tscm_estimate_extrinsic_stages: the arguments of tscm_estimate_extrinsic (Rt and *n_estimated as
+ *   there), and per image k: T [9k..] the look-at turn R2*R1 (:175-187), H [9k..] the de-normalised
+ *   homography (h33 = 1 before de-normalisation), pose0 [6k..] = (rv0, t0) from the columns of H after
+ *   the polar factor, pose [6k..] = (rv, t) after Gauss-Newton, steps[k] = Gauss-Newton updates applied
+ *   (0 .. 10), exit_code[k] = one of TSCM_EXTRINSIC_*.  Stage values an image does not reach are NaN
+ *   (steps -1).  A pose is written to Rt exactly when exit_code >= TSCM_EXTRINSIC_CONVERGED.  A NaN
+ *   pixel, or a reference corner outside the model's domain (alpha > 0.5 and a ray past the sphere),
+ *   reaches the DLT as NaN and ends there with TSCM_EXTRINSIC_DLT_FAILED.                          */
+#define TSCM_EXTRINSIC_NO_BOARD 1           /* count[k] == 0                                        */
+#define TSCM_EXTRINSIC_DEGENERATE_BOARD 2   /* mean distance of the board points to their centre == 0 (or NaN) */
+#define TSCM_EXTRINSIC_DLT_FAILED 3         /* the 8x8 normal equations are not positive definite  */
+#define TSCM_EXTRINSIC_ZERO_COLUMN 4        /* a column of H has norm 0 (or NaN)                   */
+#define TSCM_EXTRINSIC_CONVERGED 5          /* the Gauss-Newton step met the stopping rule         */
+#define TSCM_EXTRINSIC_ITERATION_CAP 6      /* 10 Gauss-Newton updates without meeting it          */
+#define TSCM_EXTRINSIC_GN_CHOLESKY 7        /* J^T J not positive definite: the last iterate is kept */
+int tscm_estimate_focal_rows(const double *pix_u, const double *pix_v, const int *count, int n_views,
+                             int board_w, int board_h, double cx, double cy, int device, double *gamma);
+int tscm_estimate_extrinsic_stages(const double *intr9, const double *pix_u, const double *pix_v,
+                                   const int *count, int n_views, const double *worlds, int n_points,
+                                   int board_w, int device, double *Rt, int *n_estimated, double *T,
+                                   double *H, double *pose0, double *pose, int *steps, int *exit_code);
 
 
 /* ------------------------------------------------------------------ corner lists

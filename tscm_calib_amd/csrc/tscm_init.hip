@@ -169,6 +169,12 @@ __device__ void rotation_vector_dev(const double *Min, double *rv)
     }
 }
 
+// STAGES = false: Rt_out [n_views][9], ok_out[k] = 1 where a pose was written (tscm_estimate_extrinsic).
+// STAGES = true: Rt_out [n_views][kStageRec] = Rt | T | H | rv0 t0 | rv t | GN steps, ok_out[k] = the
+// TSCM_EXTRINSIC_* exit code (tscm_estimate_extrinsic_stages); stage fields not reached keep their values.
+constexpr int kStageRec = 40;
+
+template <bool STAGES>
 __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restrict__ intr, const double *__restrict__ pu, const double *__restrict__ pv,
                                                            const int *__restrict__ count, int n_views, const double *__restrict__ worlds, int n, int board_w,
                                                            double *__restrict__ Rt_out, unsigned char *__restrict__ ok_out)
@@ -176,7 +182,11 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restr
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_views) return;
     ok_out[k] = 0;
-    if (count[k] == 0) return;
+    double *stage = Rt_out + (size_t)kStageRec * k;                         // STAGES only
+    if (count[k] == 0) {
+        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_NO_BOARD;
+        return;
+    }
     double I[9];
     for (int i = 0; i < 9; ++i) I[i] = intr[i];
     const double *u = pu + (size_t)k * n, *v = pv + (size_t)k * n;
@@ -187,6 +197,8 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restr
     const double alpha = atan2(p[0], p[2]), beta = asin(p[1]);
     const double ca = cos(alpha), sa = sin(alpha), cb = cos(beta), sb = sin(beta);
     const double T[9] = { ca, 0.0, -sa, -sb * sa, cb, -sb * ca, cb * sa, sb, cb * ca };       // R2 * R1
+    if constexpr (STAGES)
+        for (int i = 0; i < 9; ++i) stage[9 + i] = T[i];
     auto normalised = [&](int i, double &x, double &y) {
         double q[3];
         tscm::unproject_pixel(I, u[i], v[i], q);
@@ -199,7 +211,10 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restr
     cx /= n; cy /= n;
     for (int i = 0; i < n; ++i) { const double dx = worlds[3 * i] - cx, dy = worlds[3 * i + 1] - cy; md += sqrt(dx * dx + dy * dy); }
     md /= n;
-    if (!(md > 0.0)) return;
+    if (!(md > 0.0)) {
+        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_DEGENERATE_BOARD;
+        return;
+    }
     const double s = sqrt(2.0) / md;
     // DLT: 8x8 normal equations
     double A[64], b[8];
@@ -215,23 +230,35 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restr
             b[a] += r1[a] * x + r2[a] * y;
         }
     }
-    if (!chol_solve_dev<8>(A, b)) return;
+    if (!chol_solve_dev<8>(A, b)) {
+        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_DLT_FAILED;
+        return;
+    }
     const double Hn[9] = { b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], 1.0 };
     double H[9];
     for (int r = 0; r < 3; ++r) {
         H[3 * r] = Hn[3 * r] * s; H[3 * r + 1] = Hn[3 * r + 1] * s;
         H[3 * r + 2] = Hn[3 * r + 2] - s * (Hn[3 * r] * cx + Hn[3 * r + 1] * cy);
     }
+    if constexpr (STAGES)
+        for (int i = 0; i < 9; ++i) stage[18 + i] = H[i];
     const double n1 = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]), n2 = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
-    if (!(n1 > 0.0) || !(n2 > 0.0)) return;
+    if (!(n1 > 0.0) || !(n2 > 0.0)) {
+        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_ZERO_COLUMN;
+        return;
+    }
     double lam = 2.0 / (n1 + n2);
     if (H[8] < 0) lam = -lam;
     double M[9], t[3], rv[3];
     for (int r = 0; r < 3; ++r) { M[3 * r] = lam * H[3 * r]; M[3 * r + 1] = lam * H[3 * r + 1]; t[r] = lam * H[3 * r + 2]; }
     M[2] = M[3] * M[7] - M[6] * M[4]; M[5] = M[6] * M[1] - M[0] * M[7]; M[8] = M[0] * M[4] - M[3] * M[1];
     rotation_vector_dev(M, rv);
+    if constexpr (STAGES)
+        for (int i = 0; i < 3; ++i) { stage[27 + i] = rv[i]; stage[30 + i] = t[i]; }
     // Gauss-Newton on (rv, t), analytic Jacobian
     double R[9], dR[27];
+    int steps = 0;                                                          // STAGES only
+    unsigned char exit_code = TSCM_EXTRINSIC_ITERATION_CAP;
     for (int it = 0; it < 10; ++it) {
         tscm::rotation_and_derivatives(rv, R, dR);
         double JtJ[36], Jtr[6];
@@ -256,40 +283,49 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restr
             }
         }
         for (int a = 0; a < 6; ++a) JtJ[7 * a] *= 1.0 + 1e-12;
-        if (!chol_solve_dev<6>(JtJ, Jtr)) break;
+        if (!chol_solve_dev<6>(JtJ, Jtr)) {
+            if constexpr (STAGES) exit_code = TSCM_EXTRINSIC_GN_CHOLESKY;
+            break;
+        }
         double step = 0.0;
         for (int a = 0; a < 3; ++a) { rv[a] -= Jtr[a]; t[a] -= Jtr[3 + a]; step += Jtr[a] * Jtr[a] + Jtr[3 + a] * Jtr[3 + a] / fmax(1.0, t[a] * t[a]); }
-        if (step < 1e-24) break;
+        if constexpr (STAGES) ++steps;
+        if (step < 1e-24) {
+            if constexpr (STAGES) exit_code = TSCM_EXTRINSIC_CONVERGED;
+            break;
+        }
+    }
+    if constexpr (STAGES) {
+        for (int i = 0; i < 3; ++i) { stage[33 + i] = rv[i]; stage[36 + i] = t[i]; }
+        stage[39] = steps;
     }
     tscm::rotation_and_derivatives(rv, R, dR);
-    double *o = Rt_out + 9 * (size_t)k;                                     // Rt = transform^T [r1 r2 t]  (:195-200)
+    double *o = STAGES ? stage : Rt_out + 9 * (size_t)k;                    // Rt = transform^T [r1 r2 t]  (:195-200)
     for (int r = 0; r < 3; ++r) {
         o[3 * r] = T[r] * R[0] + T[3 + r] * R[3] + T[6 + r] * R[6];
         o[3 * r + 1] = T[r] * R[1] + T[3 + r] * R[4] + T[6 + r] * R[7];
         o[3 * r + 2] = T[r] * t[0] + T[3 + r] * t[1] + T[6 + r] * t[2];
     }
-    ok_out[k] = 1;
+    ok_out[k] = STAGES ? exit_code : 1;
 }
 
 }  // namespace
 
-extern "C" int tscm_estimate_focal(const double *pix_u, const double *pix_v, const int *count, int n_views, int board_w, int board_h,
-                                   double cx, double cy, int device, double *focal, int *n_used)
+// k_focal_rows over every (image, row): g[k * board_h + i] = the kernel's value.  Both focal entry points call this.
+static int focal_rows(const double *pix_u, const double *pix_v, const int *count, int n_views, int board_w, int board_h,
+                      double cx, double cy, int device, std::vector<double> &g)
 {
-    if (!focal || !n_used || n_views < 0 || (n_views > 0 && (!pix_u || !pix_v || !count))) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
     if (board_w < 4 || board_h < 1) return tscm_set_error(TSCM_E_UNSUPPORTED, "estimate_focal needs boards at least 4 corners wide");
     if (board_w > kMaxBoardW) return tscm_set_error(TSCM_E_UNSUPPORTED, "boards wider than 32 corners");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_estimate_focal has no CPU fallback)");
     if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
     INIT_TRY(hipSetDevice(device));
-    *focal = 0.0; *n_used = 0;
     const size_t rows = (size_t)n_views * board_h, npix = rows * board_w;
+    g.assign(rows, 0.0);
     if (rows == 0) return 0;
     double *d_u = nullptr, *d_v = nullptr, *d_g = nullptr;
     int *d_c = nullptr;
-    std::vector<double> g(rows);
-    int rc = 0;
     auto body = [&]() -> int {
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_u), npix * sizeof(double)));
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_v), npix * sizeof(double)));
@@ -303,61 +339,118 @@ extern "C" int tscm_estimate_focal(const double *pix_u, const double *pix_v, con
         INIT_TRY(hipMemcpy(g.data(), d_g, rows * sizeof(double), hipMemcpyDeviceToHost));
         return 0;
     };
-    rc = body();
+    const int rc = body();
     (void)hipFree(d_u); (void)hipFree(d_v); (void)hipFree(d_g); (void)hipFree(d_c);
+    return rc;
+}
+
+extern "C" int tscm_estimate_focal(const double *pix_u, const double *pix_v, const int *count, int n_views, int board_w, int board_h,
+                                   double cx, double cy, int device, double *focal, int *n_used)
+{
+    if (!focal || !n_used || n_views < 0 || (n_views > 0 && (!pix_u || !pix_v || !count))) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
+    std::vector<double> g;
+    const int rc = focal_rows(pix_u, pix_v, count, n_views, board_w, board_h, cx, cy, device, g);
     if (rc) return rc;
     double f = 0.0;
     int total = 0;
-    for (size_t r = 0; r < rows; ++r) {                     // focal_ += gamma in (image, row) order (:155-156)
-        if (g[r] < 0.0) continue;                           // markers; NaN samples are summed like the reference does
-        f += g[r]; ++total;
+    for (const double x : g) {                              // focal_ += gamma in (image, row) order (:155-156)
+        if (x < 0.0) continue;                              // markers; NaN samples are summed like the reference does
+        f += x; ++total;
     }
     if (total > 0) f /= total;
     *focal = f; *n_used = total;
     return 0;
 }
 
-extern "C" int tscm_estimate_extrinsic(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,
-                                       const double *worlds, int n_points, int board_w, int device, double *Rt, int *n_estimated)
+extern "C" int tscm_estimate_focal_rows(const double *pix_u, const double *pix_v, const int *count, int n_views, int board_w, int board_h,
+                                        double cx, double cy, int device, double *gamma)
 {
-    if (!intr9 || !worlds || n_views < 0 || n_points < 4 || (n_views > 0 && (!pix_u || !pix_v || !count || !Rt))) return tscm_set_error(TSCM_E_INVALID, "NULL or inconsistent argument");
+    if (n_views < 0 || (n_views > 0 && (!pix_u || !pix_v || !count || !gamma))) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
+    std::vector<double> g;
+    const int rc = focal_rows(pix_u, pix_v, count, n_views, board_w, board_h, cx, cy, device, g);
+    if (rc) return rc;
+    for (size_t r = 0; r < g.size(); ++r) gamma[r] = g[r];
+    return 0;
+}
+
+// One launch of k_estimate_extrinsic<STAGES> over every image.  rec: [n_views][STAGES ? kStageRec : 9] host records,
+// uploaded and read back whole (so the fields a view does not reach keep the caller's values); ok: [n_views].
+template <bool STAGES>
+static int extrinsic_views(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,
+                           const double *worlds, int n_points, int board_w, int device, double *rec, unsigned char *ok)
+{
     if (board_w < 1 || n_points / 2 - board_w / 2 - 1 < 0) return tscm_set_error(TSCM_E_INVALID, "board width does not fit the corner count");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_estimate_extrinsic has no CPU fallback)");
     if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
     INIT_TRY(hipSetDevice(device));
-    if (n_estimated) *n_estimated = 0;
     if (n_views == 0) return 0;
-    const size_t npix = (size_t)n_views * n_points;
+    const size_t npix = (size_t)n_views * n_points, nrec = (size_t)n_views * (STAGES ? kStageRec : 9);
     double *d_i = nullptr, *d_u = nullptr, *d_v = nullptr, *d_w = nullptr, *d_rt = nullptr;
     int *d_c = nullptr;
     unsigned char *d_ok = nullptr;
-    std::vector<unsigned char> ok(n_views);
     auto body = [&]() -> int {
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_i), 9 * sizeof(double)));
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_u), npix * sizeof(double)));
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_v), npix * sizeof(double)));
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_w), 3 * (size_t)n_points * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_rt), 9 * (size_t)n_views * sizeof(double)));
+        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_rt), nrec * sizeof(double)));
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_c), (size_t)n_views * sizeof(int)));
         INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_ok), (size_t)n_views));
         INIT_TRY(hipMemcpy(d_i, intr9, 9 * sizeof(double), hipMemcpyHostToDevice));
         INIT_TRY(hipMemcpy(d_u, pix_u, npix * sizeof(double), hipMemcpyHostToDevice));
         INIT_TRY(hipMemcpy(d_v, pix_v, npix * sizeof(double), hipMemcpyHostToDevice));
         INIT_TRY(hipMemcpy(d_w, worlds, 3 * (size_t)n_points * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_rt, Rt, 9 * (size_t)n_views * sizeof(double), hipMemcpyHostToDevice));      // views without a pose keep the caller's values
+        INIT_TRY(hipMemcpy(d_rt, rec, nrec * sizeof(double), hipMemcpyHostToDevice));      // views without a pose keep the caller's values
         INIT_TRY(hipMemcpy(d_c, count, (size_t)n_views * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_estimate_extrinsic, dim3((unsigned)((n_views + 63) / 64)), dim3(64), 0, 0, d_i, d_u, d_v, d_c, n_views, d_w, n_points, board_w, d_rt, d_ok);
+        hipLaunchKernelGGL(k_estimate_extrinsic<STAGES>, dim3((unsigned)((n_views + 63) / 64)), dim3(64), 0, 0, d_i, d_u, d_v, d_c, n_views, d_w, n_points, board_w, d_rt, d_ok);
         INIT_TRY(hipGetLastError());
-        INIT_TRY(hipMemcpy(Rt, d_rt, 9 * (size_t)n_views * sizeof(double), hipMemcpyDeviceToHost));
-        INIT_TRY(hipMemcpy(ok.data(), d_ok, (size_t)n_views, hipMemcpyDeviceToHost));
+        INIT_TRY(hipMemcpy(rec, d_rt, nrec * sizeof(double), hipMemcpyDeviceToHost));
+        INIT_TRY(hipMemcpy(ok, d_ok, (size_t)n_views, hipMemcpyDeviceToHost));
         return 0;
     };
     const int rc = body();
     (void)hipFree(d_i); (void)hipFree(d_u); (void)hipFree(d_v); (void)hipFree(d_w); (void)hipFree(d_rt); (void)hipFree(d_c); (void)hipFree(d_ok);
+    return rc;
+}
+
+extern "C" int tscm_estimate_extrinsic(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,
+                                       const double *worlds, int n_points, int board_w, int device, double *Rt, int *n_estimated)
+{
+    if (!intr9 || !worlds || n_views < 0 || n_points < 4 || (n_views > 0 && (!pix_u || !pix_v || !count || !Rt))) return tscm_set_error(TSCM_E_INVALID, "NULL or inconsistent argument");
+    if (n_estimated) *n_estimated = 0;
+    std::vector<unsigned char> ok(n_views);
+    const int rc = extrinsic_views<false>(intr9, pix_u, pix_v, count, n_views, worlds, n_points, board_w, device, Rt, ok.data());
     if (rc) return rc;
     int done = 0;
     for (unsigned char f : ok) done += f;
+    if (n_estimated) *n_estimated = done;
+    return 0;
+}
+
+extern "C" int tscm_estimate_extrinsic_stages(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,
+                                              const double *worlds, int n_points, int board_w, int device, double *Rt, int *n_estimated,
+                                              double *T, double *H, double *pose0, double *pose, int *steps, int *exit_code)
+{
+    if (!intr9 || !worlds || n_views < 0 || n_points < 4 ||
+        (n_views > 0 && (!pix_u || !pix_v || !count || !Rt || !T || !H || !pose0 || !pose || !steps || !exit_code)))
+        return tscm_set_error(TSCM_E_INVALID, "NULL or inconsistent argument");
+    if (n_estimated) *n_estimated = 0;
+    std::vector<double> rec((size_t)n_views * kStageRec, NAN);
+    for (int k = 0; k < n_views; ++k)
+        for (int i = 0; i < 9; ++i) rec[(size_t)kStageRec * k + i] = Rt[9 * (size_t)k + i];
+    std::vector<unsigned char> code(n_views);
+    const int rc = extrinsic_views<true>(intr9, pix_u, pix_v, count, n_views, worlds, n_points, board_w, device, rec.data(), code.data());
+    if (rc) return rc;
+    int done = 0;
+    for (int k = 0; k < n_views; ++k) {
+        const double *r = rec.data() + (size_t)kStageRec * k;
+        for (int i = 0; i < 9; ++i) { Rt[9 * (size_t)k + i] = r[i]; T[9 * (size_t)k + i] = r[9 + i]; H[9 * (size_t)k + i] = r[18 + i]; }
+        for (int i = 0; i < 6; ++i) { pose0[6 * (size_t)k + i] = r[27 + i]; pose[6 * (size_t)k + i] = r[33 + i]; }
+        steps[k] = std::isnan(r[39]) ? -1 : (int)r[39];
+        exit_code[k] = code[k];
+        done += code[k] >= TSCM_EXTRINSIC_CONVERGED;
+    }
     if (n_estimated) *n_estimated = done;
     return 0;
 }

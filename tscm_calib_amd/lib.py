@@ -131,7 +131,7 @@ EXPORTS = [
     "tscm_shard_frames", "tscm_solver_create_sharded", "tscm_comm_create_local", "tscm_comm_ipc_open", "tscm_comm_ipc_connect", "tscm_solver_solve_group",
     "tscm_solver_gather_boards", "tscm_comm_info", "tscm_rig_init", "tscm_rig_stage_errors", "tscm_yaml_format", "tscm_yaml_write", "tscm_yaml_parse",
     "tscm_yaml_read", "tscm_build_maps", "tscm_estimate_focal", "tscm_poses_from_r1r2t",
-    "tscm_estimate_extrinsic", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
+    "tscm_estimate_extrinsic", "tscm_estimate_focal_rows", "tscm_estimate_extrinsic_stages", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_planes_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed",
@@ -218,6 +218,8 @@ def lib():
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]
     L.tscm_poses_from_r1r2t.argtypes = [dp, C.c_void_p, C.c_int, dp]
     L.tscm_estimate_extrinsic.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip]
+    L.tscm_estimate_focal_rows.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp]
+    L.tscm_estimate_extrinsic_stages.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, ip, ip]
     L.tscm_corners_write.argtypes = [C.c_char_p, C.POINTER(CCornerSet)]
     L.tscm_corners_read.argtypes = [C.c_char_p, C.POINTER(CCornerSet)]
     L.tscm_corners_free.argtypes = [C.POINTER(CCornerSet)]

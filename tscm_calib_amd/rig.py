@@ -125,6 +125,20 @@ def estimate_focal(pix_u, pix_v, count, board_w: int, board_h: int, cx: float, c
     return focal.value, used.value
 
 
+def estimate_focal_rows(pix_u, pix_v, count, board_w: int, board_h: int, cx: float, cy: float, device: int = 0) -> np.ndarray:
+    """tscm_estimate_focal_rows -> [n_views, board_h]: the row kernel's output, -1 (image without a board), -2 (row
+    rejected) or the sample gamma.  estimate_focal returns the mean and number of the values that are not markers."""
+    pix_u = np.ascontiguousarray(pix_u, dtype=np.float64)
+    pix_v = np.ascontiguousarray(pix_v, dtype=np.float64)
+    count = np.ascontiguousarray(count, dtype=np.int32)
+    if pix_u.size != count.shape[0] * board_w * board_h or pix_v.size != pix_u.size:
+        raise ValueError("pix_u / pix_v must hold n_views * board_w * board_h values")
+    g = np.zeros((count.shape[0], max(board_h, 0)))
+    _lib.check(_lib.lib().tscm_estimate_focal_rows(_lib.dptr(pix_u), _lib.dptr(pix_v), count.ctypes.data_as(C.POINTER(C.c_int)),
+                                                   count.shape[0], board_w, board_h, cx, cy, device, _lib.dptr(g)))
+    return g
+
+
 def poses_from_Rt(Rt, has=None) -> np.ndarray:
     """tscm_poses_from_r1r2t (TS.cpp:62-74): [n,3,3] [r1 r2 t] -> [n,6] angle-axis + t (host-only)."""
     Rt = np.ascontiguousarray(Rt, dtype=np.float64).reshape(-1, 3, 3)
@@ -134,9 +148,7 @@ def poses_from_Rt(Rt, has=None) -> np.ndarray:
     return rt
 
 
-def estimate_extrinsic(intr, pix_u, pix_v, count, worlds, board_w: int, device: int = 0):
-    """tscm_estimate_extrinsic (TripleSphereCamera::estimate_extrinsic, TS.cpp:170-203, with a deterministic
-    planar PnP in place of cv::solvePnPRansac) -> Rt [V,3,3] = [r1 r2 t] per image, number of poses."""
+def _extrinsic_args(intr, pix_u, pix_v, count, worlds, Rt_init):
     intr = np.ascontiguousarray(intr, dtype=np.float64).reshape(9)
     pix_u = np.ascontiguousarray(pix_u, dtype=np.float64)
     pix_v = np.ascontiguousarray(pix_v, dtype=np.float64)
@@ -145,9 +157,37 @@ def estimate_extrinsic(intr, pix_u, pix_v, count, worlds, board_w: int, device: 
     V, n = count.shape[0], worlds.shape[0]
     if pix_u.size != V * n or pix_v.size != V * n:
         raise ValueError("pix_u / pix_v must hold n_views * n_points values")
-    Rt = np.zeros((V, 3, 3))
+    Rt = np.zeros((V, 3, 3)) if Rt_init is None else np.array(Rt_init, dtype=np.float64).reshape(V, 3, 3)
+    return intr, pix_u, pix_v, count, worlds, V, n, Rt
+
+
+def estimate_extrinsic(intr, pix_u, pix_v, count, worlds, board_w: int, device: int = 0, Rt_init=None):
+    """tscm_estimate_extrinsic (TripleSphereCamera::estimate_extrinsic, TS.cpp:170-203, with a deterministic
+    planar PnP in place of cv::solvePnPRansac) -> Rt [V,3,3] = [r1 r2 t] per image, number of poses.
+    Images without a pose keep Rt_init (a copy; zeros when None)."""
+    intr, pix_u, pix_v, count, worlds, V, n, Rt = _extrinsic_args(intr, pix_u, pix_v, count, worlds, Rt_init)
     done = C.c_int(0)
     _lib.check(_lib.lib().tscm_estimate_extrinsic(_lib.dptr(intr), _lib.dptr(pix_u), _lib.dptr(pix_v),
                                                   count.ctypes.data_as(C.POINTER(C.c_int)), V, _lib.dptr(worlds), n, board_w,
                                                   device, _lib.dptr(Rt), C.byref(done)))
     return Rt, done.value
+
+
+def estimate_extrinsic_stages(intr, pix_u, pix_v, count, worlds, board_w: int, device: int = 0, Rt_init=None) -> dict:
+    """tscm_estimate_extrinsic_stages: the launch of estimate_extrinsic with every stage of every image.  Returns
+    Rt [V,3,3] and n_estimated as estimate_extrinsic does, T [V,3,3] (look-at turn), H [V,3,3] (homography),
+    rv0/t0 [V,3] (pose from the columns), rv/t [V,3] (after Gauss-Newton), steps [V] and code [V]
+    (TSCM_EXTRINSIC_*: 1 no board, 2 degenerate board, 3 DLT failed, 4 zero column, 5 converged, 6 iteration
+    cap, 7 Gauss-Newton Cholesky failure).  Stages an image does not reach are NaN (steps -1)."""
+    intr, pix_u, pix_v, count, worlds, V, n, Rt = _extrinsic_args(intr, pix_u, pix_v, count, worlds, Rt_init)
+    T, H, pose0, pose = np.zeros((V, 3, 3)), np.zeros((V, 3, 3)), np.zeros((V, 6)), np.zeros((V, 6))
+    steps, code = np.zeros(V, dtype=np.int32), np.zeros(V, dtype=np.int32)
+    done = C.c_int(0)
+    ip = C.POINTER(C.c_int)
+    _lib.check(_lib.lib().tscm_estimate_extrinsic_stages(_lib.dptr(intr), _lib.dptr(pix_u), _lib.dptr(pix_v),
+                                                         count.ctypes.data_as(ip), V, _lib.dptr(worlds), n, board_w, device,
+                                                         _lib.dptr(Rt), C.byref(done), _lib.dptr(T), _lib.dptr(H),
+                                                         _lib.dptr(pose0), _lib.dptr(pose), steps.ctypes.data_as(ip),
+                                                         code.ctypes.data_as(ip)))
+    return dict(Rt=Rt, n_estimated=done.value, T=T, H=H, rv0=pose0[:, :3], t0=pose0[:, 3:], rv=pose[:, :3], t=pose[:, 3:],
+                steps=steps, code=code)
