@@ -365,6 +365,22 @@ int tscm_solve_fixed(const tscm_problem *problem, const tscm_options *opt, const
 int tscm_eval_step_fixed(const tscm_problem *problem, int device, const tscm_options *opt, const unsigned short *fixed, int kind,
                          double scale, double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary);
 
+/* n independent TripleSphereCamera::refinement problems (TS.cpp:247-282) solved together on one device -- main.cpp's
+ * per-camera monocular_calib refinements in one call.  Every problem is solved exactly as
+ * tscm_solve_fixed(problems[k], opt, fixed ? fixed + k : NULL, kind, scale) would solve it alone: its own trust region,
+ * its own termination, its own summary (to rounding: the batched route has its own kernels).  Parameters are updated in
+ * place in each problem's arrays; a problem that has terminated is frozen while the others go on.
+ *   - opt and the loss are shared; fixed[k] (or NULL) is problem k's mask (TSCM_FIX_*, TSCM_MODEL_DS / _UCM).
+ *   - every problem: mono, n_cameras == 1, the same n_points and board_xy (else TSCM_E_UNSUPPORTED), at most 256 corners.
+ *   - refused before any device is touched: n_problems <= 0, bad masks, losses or options (the codes of tscm_solve_fixed);
+ *     jacobian_fp32 or any exec_flags bit (TSCM_E_UNSUPPORTED).
+ *   - a problem without a single corner comes back as tscm_solve_fixed returns it alone.
+ *   - summaries[k].seconds_solve / seconds_total are the batch's times (the same in every summary); rmse and
+ *     n_residual_blocks are the problem's own. */
+int tscm_solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt,
+                          const unsigned short *fixed /* [n_problems] or NULL */, int loss_kind, double loss_scale,
+                          tscm_summary *summaries /* [n_problems] */);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

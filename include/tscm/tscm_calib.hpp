@@ -8,6 +8,7 @@
 //
 //   reference                                              here
 //   TripleSphereCamera::refinement       TS.cpp:247-282    TripleSphereCamera::refinement      -> tscm_solve_mono
+//                                                           TripleSphereCamera::refinement_batch (several cameras) -> tscm_solve_mono_batch
 //   TripleSphereCamera::estimate_focal   TS.cpp:110-168    TripleSphereCamera::estimate_focal  -> tscm_estimate_focal
 //   TripleSphereCamera::estimate_extrinsic TS.cpp:170-203  TripleSphereCamera::estimate_extrinsic -> tscm_estimate_extrinsic (*)
 //   loop Rt_ -> rt_                      TS.cpp:62-74      TripleSphereCamera::poses_from_Rt   -> tscm_poses_from_r1r2t
@@ -133,6 +134,58 @@ public:
         else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
         return summary.termination_type == TSCM_CONVERGENCE;             // TS.cpp:281
+    }
+
+    // refinement() of several cameras in ONE batch (tscm_solve_mono_batch): cams[k] is refined on pixels[k], all against the
+    // same worlds, each with the post-conditions of cams[k]->refinement(pixels[k], worlds, options) -- intrinsic_, rt_ and
+    // summary updated, its own fixed mask honoured -- and returns, per camera, termination_type == CONVERGENCE.  The loss is
+    // shared by a batch: cameras with different losses (set_loss) are refused with std::invalid_argument before anything runs.
+    static std::vector<bool> refinement_batch(const std::vector<TripleSphereCamera *> &cams,
+                                              const std::vector<std::vector<std::vector<Point2d> > > &pixels,
+                                              const std::vector<Point3d> &worlds, const tscm_options *options = nullptr)
+    {
+        const size_t K = cams.size();
+        if (K == 0 || pixels.size() != K) throw std::invalid_argument("tscm: refinement_batch needs one pixel set per camera");
+        for (size_t k = 1; k < K; ++k)
+            if (cams[k]->loss_kind_ != cams[0]->loss_kind_ || (cams[0]->loss_kind_ != TSCM_LOSS_NONE && cams[k]->loss_scale_ != cams[0]->loss_scale_))
+                throw std::invalid_argument("tscm: refinement_batch: the cameras of a batch must share one loss (set_loss)");
+        const int n = (int)worlds.size();
+        std::vector<double> bxy(2 * (size_t)n);
+        for (int j = 0; j < n; ++j) { bxy[2 * j] = worlds[j].x; bxy[2 * j + 1] = worlds[j].y; }
+        std::vector<std::vector<double> > u(K), v(K), rt(K);
+        std::vector<std::vector<int> > vc(K), vb(K), vo(K), vn(K);
+        std::vector<tscm_problem> P(K);
+        std::vector<unsigned short> fixed(K);
+        for (size_t k = 0; k < K; ++k) {
+            const TripleSphereCamera &c = *cams[k];
+            const int V = (int)pixels[k].size();
+            rt[k].assign(6 * (size_t)V, 0.0);
+            for (int i = 0; i < V; ++i) {
+                if (!c.has_chessboard_[i]) continue;                         // TS.cpp:253
+                vc[k].push_back(0); vb[k].push_back(i); vo[k].push_back((int)u[k].size()); vn[k].push_back((int)pixels[k][i].size());
+                for (const Point2d &p : pixels[k][i]) { u[k].push_back(p.x); v[k].push_back(p.y); }
+                std::memcpy(&rt[k][6 * (size_t)i], c.rt_[i].data(), 6 * sizeof(double));
+            }
+            tscm_problem &q = P[k];
+            q = tscm_problem();
+            q.n_cameras = 1; q.n_boards = V; q.n_points = n; q.n_views = (int)vc[k].size();
+            q.board_xy = bxy.data(); q.view_camera = vc[k].data(); q.view_board = vb[k].data(); q.view_offset = vo[k].data();
+            q.view_count = vn[k].data(); q.obs_u = u[k].data(); q.obs_v = v[k].data(); q.intr = cams[k]->intrinsic_.data();
+            q.board_rt = rt[k].data(); q.mono = 1;
+            fixed[k] = c.fixed_;
+        }
+        tscm_options o;
+        if (options) o = *options; else tscm_default_options(&o, 1);
+        std::vector<tscm_summary> sums(K);
+        check(tscm_solve_mono_batch(P.data(), (int)K, cams[0]->device_, &o, fixed.data(), cams[0]->loss_kind_, cams[0]->loss_scale_, sums.data()));
+        std::vector<bool> converged(K);
+        for (size_t k = 0; k < K; ++k) {
+            TripleSphereCamera &c = *cams[k];
+            for (size_t i = 0; i < pixels[k].size(); ++i) if (c.has_chessboard_[i]) c.rt_[i].assign(&rt[k][6 * i], &rt[k][6 * i] + 6);
+            c.summary = sums[k];
+            converged[k] = sums[k].termination_type == TSCM_CONVERGENCE;    // TS.cpp:281
+        }
+        return converged;
     }
 
     // TS.cpp:110-168: fx = fy = mean circle-fit focal length; 0 when no row is usable

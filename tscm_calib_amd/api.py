@@ -288,6 +288,37 @@ def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, **op
     return d["termination_type"] == 0, d
 
 
+def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, **options):
+    """n TripleSphereCamera::refinement solves (TS.cpp:247-282) in one batch on one device (tscm_solve_mono_batch):
+    returns [(converged, summary), ...] in problem order, each as refinement() would return it for that problem alone.
+    Parameters are updated in place.  loss: shared, as for refinement(); fixed: None, or one mask per problem (anything
+    fixed_masks takes for one camera: an int, names, a [9] bool array, or None)."""
+    problems = list(problems)
+    if not problems:
+        raise ValueError("refinement_batch() needs at least one problem")
+    for p in problems:
+        if not p.mono:
+            raise ValueError("refinement_batch() takes mono problems only")
+        assert _is_normalised(p), "use Problem.normalised()"
+    n = len(problems)
+    o = _l.default_options(True, **options)
+    cps = (_l.CProblem * n)(*[_l.c_problem(p) for p in problems])
+    sums = (_l.CSummary * n)()
+    if fixed is None:
+        w = None
+    else:
+        if len(fixed) != n:
+            raise ValueError("fixed: one mask per problem")
+        w = np.array([_l.fixed_masks(f, 1)[0] for f in fixed], dtype=np.uint16)
+    k, a = _l.loss_args(loss)
+    _l.check(_l.lib().tscm_solve_mono_batch(cps, n, device, C.byref(o), _l.ushort_ptr(w) if w is not None else None, k, a, sums))
+    out = []
+    for i in range(n):
+        d = _l.summary_dict(sums[i])
+        out.append((d["termination_type"] == 0, d))
+    return out
+
+
 def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, plain):
     if fixed is not None:
         w = _l.fixed_masks(fixed, n_cameras)

@@ -2680,6 +2680,8 @@ __global__ __launch_bounds__(NTH) void k_backsub_prep(DevProblem P, DevState S, 
 // writer = false: the step is taken redundantly (k_schur_gram: every workgroup runs it in its head, on the same inputs,
 // to the same bits -- no hand-off, no kernel of its own); only the writer touches global memory.  out: the new state for
 // the calling workgroup.
+// (The batched mono route repeats this function's scalar trust-region logic in k_mb_control, tscm_mono_batch.h, on an array of
+// control blocks: a change to the step, the tolerance tests or the radius update here must be made there too -- DESIGN 16.)
 __device__ void control_step(const DevProblem &P, const DevState &S, int init, const ControlPre &pre, double *sm, const double *H, const double *sc, double *stage_copy,
                              bool writer, CtlOut *out)
 {

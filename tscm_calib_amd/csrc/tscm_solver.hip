@@ -9,6 +9,7 @@
 #include "tscm/tscm.h"
 #include "tscm_kernels.h"
 #include "tscm_launch_seq.h"
+#include "tscm_mono_batch.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -1549,6 +1550,217 @@ extern "C" int tscm_reprojection_error(const tscm_problem *p, int device, double
     for (int m = 0; m < s->C; ++m) { tot += err[m]; n += cnt[m]; if (per_camera_mean) per_camera_mean[m] = cnt[m] ? err[m] / (double)cnt[m] : 0.0; }
     if (global_mean) *global_mean = n ? tot / (double)n : 0.0;
     if (rmse) *rmse = n ? std::sqrt(sq / (double)n) : 0.0;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// batched mono refinement (tscm_mono_batch.h)
+// ------------------------------------------------------------------------------------------------
+// device allocations of one batch call, freed on every exit path
+struct MbAllocs {
+    std::vector<void *> p;
+    ~MbAllocs() { for (void *q : p) (void)hipFree(q); }
+    template <typename T>
+    hipError_t alloc(T **out, size_t n)
+    {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) p.push_back(q);
+        *out = static_cast<T *>(q);
+        return e;
+    }
+};
+struct MbStream {
+    hipStream_t s = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~MbStream() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (s) (void)hipStreamDestroy(s); }
+};
+
+// plain pixel RMSE of one problem at its parameters (a robust solve's summary.rmse, as tscm_reprojection_error computes it)
+static double mb_pixel_rmse(const tscm_problem &p)
+{
+    ViewConst vc;
+    for (int q = 0; q < 9; ++q) vc.Rc[q] = (q % 4 == 0) ? 1.0 : 0.0;
+    for (int q = 0; q < 3; ++q) vc.tc[q] = 0.0;
+    for (int q = 0; q < 27; ++q) vc.dRc[q] = 0.0;
+    const double *I = p.intr;
+    vc.fx = I[0]; vc.fy = I[1]; vc.cx = I[2]; vc.cy = I[3]; vc.xi = I[4]; vc.lam = I[5]; vc.al = I[6];
+    double sq = 0.0;
+    long n = 0;
+    for (int v = 0; v < p.n_views; ++v) {
+        if (p.view_count[v] <= 0) continue;
+        const double *rt = p.board_rt + 6 * (size_t)p.view_board[v];
+        double bc[kBoardConst];
+        board_constants(rt, bc);
+        for (int q = 0; q < 3; ++q) { vc.r1[q] = bc[q]; vc.r2[q] = bc[3 + q]; vc.tb[q] = rt[3 + q]; }
+        for (int kk = 0; kk < 3; ++kk) for (int q = 0; q < 6; ++q) vc.db[kk][q] = bc[6 + 6 * kk + q];
+        for (int j = 0; j < p.view_count[v]; ++j) {
+            double r[2], JE[2][kE], JF[2][kFA];
+            const int o = p.view_offset[v] + j;
+            corner_residual_jacobian(vc, p.board_xy[2 * j], p.board_xy[2 * j + 1], p.obs_u[o], p.obs_v[o], r, JE, JF);
+            sq += r[0] * r[0] + r[1] * r[1];
+        }
+        n += p.view_count[v];
+    }
+    return n ? std::sqrt(sq / (double)n) : 0.0;
+}
+
+extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in,
+                                     const unsigned short *fixed, int loss_kind, double loss_scale, tscm_summary *summaries)
+{
+    const double t_call = wall();
+    if (!summaries) return fail(TSCM_E_INVALID, "summaries is NULL");
+    tscm_options opt;
+    if (int rc = read_options(opt_in, 1, opt)) return rc;
+    BatchPlan bp;
+    {
+        std::string err;
+        if (int rc = plan_batch(problems, n_problems, opt, fixed, loss_kind, loss_scale, bp, err)) return fail(rc, err);
+    }
+    LossArg loss;
+    if (int rc = make_loss(loss_kind, loss_scale, loss)) return rc;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(TSCM_E_NO_DEVICE, "no HIP device");
+    if (device < 0 || device >= n_dev) return fail(TSCM_E_NO_DEVICE, "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    for (int i = 0; i < n_problems; ++i) std::memset(&summaries[i], 0, sizeof(tscm_summary));
+
+    const int K = bp.K, nc = (int)bp.chunk.size(), ns = (int)bp.slot_prob.size(), B = bp.B;
+    double seconds_solve = 0.0;
+    if (K > 0) {
+        // ---- upload: concatenated observations (slot order), boards, intrinsics; both parameter buffers hold the start point
+        std::vector<double> ou((size_t)bp.N), ov((size_t)bp.N), intr((size_t)9 * K), board((size_t)6 * B, 0.0);
+        for (int s = 0; s < ns; ++s) {
+            const tscm_problem &p = problems[bp.dev_prob[bp.slot_prob[s]]];
+            const int v = bp.slot_view[s];
+            for (int j = 0; j < bp.slot_count[s]; ++j) { ou[bp.slot_obs[s] + j] = p.obs_u[p.view_offset[v] + j]; ov[bp.slot_obs[s] + j] = p.obs_v[p.view_offset[v] + j]; }
+        }
+        for (int k = 0; k < K; ++k) {
+            const tscm_problem &p = problems[bp.dev_prob[k]];
+            std::memcpy(&intr[9 * (size_t)k], p.intr, 9 * sizeof(double));
+            if (p.n_boards) std::memcpy(&board[6 * (size_t)bp.board_ptr[k]], p.board_rt, 6 * sizeof(double) * p.n_boards);
+        }
+        std::vector<int4> chunk(nc);
+        for (int c = 0; c < nc; ++c) chunk[c] = make_int4(bp.chunk[c].x, bp.chunk[c].y, bp.chunk[c].z, 0);
+
+        MbAllocs A;
+        MbDev D{};
+        D.K = K; D.n_points = bp.n_points; D.n_chunks = nc; D.n_slots = ns; D.loss = loss;
+        double *d_xy = nullptr, *d_u = nullptr, *d_v = nullptr;
+        int4 *d_chunk = nullptr;
+        int *d_cptr = nullptr, *d_bptr = nullptr, *d_sb = nullptr, *d_so = nullptr, *d_sc = nullptr;
+        unsigned char *d_sa = nullptr;
+        unsigned short *d_mask = nullptr;
+        char *d_ctrl = nullptr;
+        const size_t ctrl_bytes = sizeof(CtrlHead) * (size_t)K + sizeof(IterLog) * (size_t)kMaxLog * K;
+        HIP_TRY(A.alloc(&d_xy, 2 * (size_t)bp.n_points)); HIP_TRY(A.alloc(&d_u, (size_t)bp.N)); HIP_TRY(A.alloc(&d_v, (size_t)bp.N));
+        HIP_TRY(A.alloc(&d_chunk, (size_t)nc)); HIP_TRY(A.alloc(&d_cptr, (size_t)K + 1)); HIP_TRY(A.alloc(&d_bptr, (size_t)K + 1));
+        HIP_TRY(A.alloc(&d_sb, (size_t)ns)); HIP_TRY(A.alloc(&d_so, (size_t)ns)); HIP_TRY(A.alloc(&d_sc, (size_t)ns));
+        HIP_TRY(A.alloc(&d_sa, (size_t)ns)); HIP_TRY(A.alloc(&d_mask, (size_t)K));
+        for (int b = 0; b < 2; ++b) {
+            HIP_TRY(A.alloc(&D.intr[b], 9 * (size_t)K)); HIP_TRY(A.alloc(&D.board[b], 6 * (size_t)B));
+            HIP_TRY(A.alloc(&D.rec[b], (size_t)kMbRec * ns)); HIP_TRY(A.alloc(&D.part[b], (size_t)kMbPart * nc)); HIP_TRY(A.alloc(&D.tot[b], (size_t)kMbTot * K));
+        }
+        HIP_TRY(A.alloc(&D.schur, (size_t)kMbSp * nc)); HIP_TRY(A.alloc(&D.solvep, 4 * (size_t)nc)); HIP_TRY(A.alloc(&D.cam_mp, 4 * (size_t)K));
+        HIP_TRY(A.alloc(&D.s_b, 6 * (size_t)ns)); HIP_TRY(A.alloc(&D.s_f, 7 * (size_t)K));
+        HIP_TRY(A.alloc(&d_ctrl, ctrl_bytes)); HIP_TRY(A.alloc(&D.n_done, 1)); HIP_TRY(A.alloc(&D.out, 9 * (size_t)K + 6 * (size_t)B));
+        HIP_TRY(hipMemcpy(d_xy, problems[0].board_xy, 2 * sizeof(double) * bp.n_points, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_u, ou.data(), sizeof(double) * ou.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_v, ov.data(), sizeof(double) * ov.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_chunk, chunk.data(), sizeof(int4) * nc, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_cptr, bp.chunk_ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_bptr, bp.board_ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_sb, bp.slot_board.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_so, bp.slot_obs.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_sc, bp.slot_count.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_sa, bp.slot_active.data(), ns, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_mask, bp.mask.data(), sizeof(unsigned short) * K, hipMemcpyHostToDevice));
+        for (int b = 0; b < 2; ++b) {
+            HIP_TRY(hipMemcpy(D.intr[b], intr.data(), sizeof(double) * intr.size(), hipMemcpyHostToDevice));
+            if (B) HIP_TRY(hipMemcpy(D.board[b], board.data(), sizeof(double) * board.size(), hipMemcpyHostToDevice));
+        }
+        D.board_xy = d_xy; D.obs_u = d_u; D.obs_v = d_v; D.chunk = d_chunk; D.chunk_ptr = d_cptr; D.board_ptr = d_bptr;
+        D.slot_board = d_sb; D.slot_obs = d_so; D.slot_count = d_sc; D.slot_active = d_sa; D.mask = d_mask;
+        D.head = reinterpret_cast<CtrlHead *>(d_ctrl);
+        D.log = reinterpret_cast<IterLog *>(d_ctrl + sizeof(CtrlHead) * (size_t)K);
+
+        // ---- the loop: four launches per iteration for the whole batch; the host polls the count of terminated problems
+        MbStream ms;
+        HIP_TRY(hipStreamCreateWithFlags(&ms.s, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreate(&ms.e0)); HIP_TRY(hipEventCreate(&ms.e1));
+        const hipStream_t st = ms.s;
+        const CtrlHead head = ctrl_head_from_options(opt);
+        const size_t lds_eval = sizeof(double) * (2 * kMbJw + 1) * (size_t)bp.n_points;
+        HIP_TRY(hipEventRecord(ms.e0, st));
+        hipLaunchKernelGGL(k_mb_begin, dim3((K + 255) / 256), dim3(256), 0, st, D, head);
+        hipLaunchKernelGGL(k_mb_eval, dim3(nc), dim3(kMbThreads), lds_eval, st, D, 1);
+        hipLaunchKernelGGL(k_mb_control, dim3(K), dim3(64), 0, st, D, 1);
+        HIP_TRY(hipGetLastError());
+        const int check_every = std::max(1, opt.check_every);
+        for (int it = 1; it <= opt.max_num_iterations; ++it) {
+            hipLaunchKernelGGL(k_mb_schur, dim3(nc), dim3(kMbThreads), 0, st, D);
+            hipLaunchKernelGGL(k_mb_solve, dim3(nc), dim3(kMbThreads), 0, st, D);
+            hipLaunchKernelGGL(k_mb_eval, dim3(nc), dim3(kMbThreads), lds_eval, st, D, 0);
+            hipLaunchKernelGGL(k_mb_control, dim3(K), dim3(64), 0, st, D, 0);
+            HIP_TRY(hipGetLastError());
+            if (it % check_every == 0 && it < opt.max_num_iterations) {
+                int done = 0;
+                HIP_TRY(hipMemcpyAsync(&done, D.n_done, sizeof(int), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                if (done >= K) break;
+            }
+        }
+        hipLaunchKernelGGL(k_mb_finish, dim3(K), dim3(256), 0, st, D);
+        HIP_TRY(hipEventRecord(ms.e1, st));
+        std::vector<double> out(9 * (size_t)K + 6 * (size_t)B);
+        std::vector<char> ctrl(ctrl_bytes);
+        HIP_TRY(hipMemcpyAsync(out.data(), D.out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctrl.data(), d_ctrl, ctrl_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError());
+        float ms_solve = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms_solve, ms.e0, ms.e1));
+        seconds_solve = 1e-3 * (double)ms_solve;
+
+        // ---- results: parameters in place, one summary per problem
+        const CtrlHead *heads = reinterpret_cast<const CtrlHead *>(ctrl.data());
+        const IterLog *logs = reinterpret_cast<const IterLog *>(ctrl.data() + sizeof(CtrlHead) * (size_t)K);
+        for (int k = 0; k < K; ++k) if (!heads[k].done) return fail(TSCM_E_HIP, "device LM loop of a batch problem did not terminate");
+        for (int k = 0; k < K; ++k) {
+            const int i = bp.dev_prob[k];
+            const tscm_problem &p = problems[i];
+            const CtrlHead &h = heads[k];
+            tscm_summary *sum = &summaries[i];
+            std::memcpy(p.intr, &out[9 * (size_t)k], 9 * sizeof(double));
+            if (p.n_boards) std::memcpy(p.board_rt, &out[9 * (size_t)K + 6 * (size_t)bp.board_ptr[k]], 6 * sizeof(double) * p.n_boards);
+            const long N_k = bp.obs_ptr[k + 1] - bp.obs_ptr[k];
+            sum->termination_type = h.term_type;
+            sum->num_iterations = std::min(h.n_log, TSCM_MAX_ITERATIONS + 1);
+            sum->num_successful_steps = h.num_successful;
+            sum->num_unsuccessful_steps = h.num_unsuccessful;
+            sum->initial_cost = h.initial_cost;
+            sum->final_cost = h.x_cost;
+            sum->n_residual_blocks = (int)N_k;
+            sum->lm_iterations = h.lm_iterations;
+            for (int j = 0; j < sum->num_iterations; ++j) {
+                const IterLog &l = logs[(size_t)kMaxLog * k + j];
+                tscm_iteration &o = sum->iterations[j];
+                o.iteration = l.iteration; o.step_is_valid = l.step_is_valid; o.step_is_successful = l.step_is_successful;
+                o.cost = l.cost; o.cost_change = l.cost_change; o.gradient_max_norm = l.gradient_max_norm; o.gradient_norm = l.gradient_norm;
+                o.step_norm = l.step_norm; o.relative_decrease = l.relative_decrease; o.trust_region_radius = l.radius;
+            }
+            std::snprintf(sum->message, sizeof(sum->message), "%s", reason_message(h.term_reason));
+            sum->rmse = loss.kind != TSCM_LOSS_NONE ? mb_pixel_rmse(p) : N_k ? std::sqrt(2.0 * h.x_cost / (double)N_k) : 0.0;
+        }
+    }
+    // problems without a single corner: what the single-problem entry point returns for them
+    for (int i = 0; i < n_problems; ++i) {
+        if (bp.dev_of[i] >= 0) continue;
+        if (int rc = solve_once(&problems[i], opt_in, &summaries[i], loss, fixed ? fixed + i : nullptr)) return rc;
+    }
+    // the batch's times in every summary
+    const double t_end = wall();
+    for (int i = 0; i < n_problems; ++i) { summaries[i].seconds_total = t_end - t_call; summaries[i].seconds_solve = seconds_solve; }
     return 0;
 }
 

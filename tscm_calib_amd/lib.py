@@ -134,7 +134,7 @@ EXPORTS = [
     "tscm_estimate_extrinsic", "tscm_estimate_focal_rows", "tscm_estimate_extrinsic_stages", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_planes_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
-    "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed",
+    "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
 ]
 
 
@@ -202,6 +202,8 @@ def lib():
     usp = C.POINTER(C.c_ushort)
     L.tscm_solver_set_fixed_intrinsics.argtypes = [vp, usp]
     L.tscm_solve_fixed.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), usp, C.c_int, C.c_double, C.POINTER(CSummary)]
+    L.tscm_solve_mono_batch.argtypes = [C.POINTER(CProblem), C.c_int, C.c_int, C.POINTER(COptions), usp, C.c_int, C.c_double,
+                                        C.POINTER(CSummary)]
     L.tscm_eval_step_fixed.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), usp, C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]

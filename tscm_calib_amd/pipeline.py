@@ -36,16 +36,8 @@ def _start_in_model(intr: np.ndarray, model: str) -> None:
         intr[..., 4] = 0.0
 
 
-def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None):
-    """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
-    principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
-    intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
-    extrinsics are re-estimated (:52).  Then estimate_extrinsic, refinement.
-    loss: None (the reference's plain least squares) or (kind, scale) of the refinement, see api.calibrate.
-    model: "ts" (Triple Sphere, the reference), "ds" (Double Sphere: lambda starts at 0 and is held there) or "ucm" (Unified
-    Camera Model: xi and lambda); fixed: further held intrinsics, as for api.calibrate.
-    Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
-    w = _model_masks(model, fixed, 1)
+def _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, model="ts"):
+    """calibrate_camera up to its refinement: the start intrinsics, the poses and the mono problem of the refinement."""
     n = cols * rows
     W = board_points(cols, rows, pitch)
     count = (np.asarray(has, dtype=np.int32) * n).astype(np.int32)
@@ -61,11 +53,40 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
     q = Problem(1, V, W[:, :2].copy(), np.zeros(V, dtype=np.int32), np.arange(V, dtype=np.int32), (np.arange(V) * n).astype(np.int32),
                 np.full(V, n, dtype=np.int32), pu[sel].ravel().copy(), pv[sel].ravel().copy(), np.zeros((1, 6)), intr[None, :].copy(),
                 rig.poses_from_Rt(Rt0[sel]), np.ones(1, dtype=np.uint8), True).normalised()
-    _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
-    R = synth.rodrigues(q.board_rt[:, :3])                                   # TS.cpp:88-102
+    return q, count, sel
+
+
+def _finish_camera(q, count, sel):
+    """calibrate_camera behind its refinement (TS.cpp:88-102): intr[9] and Rt[V,3,3] = [r1 r2 t] from the refined problem."""
+    R = synth.rodrigues(q.board_rt[:, :3])
     Rt = np.zeros((count.shape[0], 3, 3))
     Rt[sel] = np.stack([R[:, :, 0], R[:, :, 1], q.board_rt[:, 3:]], axis=2)
-    return q.intr[0].copy(), Rt, summary
+    return q.intr[0].copy(), Rt
+
+
+def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None):
+    """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
+    principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
+    intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
+    extrinsics are re-estimated (:52).  Then estimate_extrinsic, refinement.
+    loss: None (the reference's plain least squares) or (kind, scale) of the refinement, see api.calibrate.
+    model: "ts" (Triple Sphere, the reference), "ds" (Double Sphere: lambda starts at 0 and is held there) or "ucm" (Unified
+    Camera Model: xi and lambda); fixed: further held intrinsics, as for api.calibrate.
+    Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
+    w = _model_masks(model, fixed, 1)
+    q, count, sel = _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr, model)
+    _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
+    intr, Rt = _finish_camera(q, count, sel)
+    return intr, Rt, summary
+
+
+def _calibrate_cameras_batched(pus, pvs, hases, cols, rows, pitch, img_sizes, device, init_intrs, loss, model, masks):
+    """calibrate_camera for every camera, the refinements of all of them in ONE batch (api.refinement_batch): the same
+    start, poses and post-processing per camera, each camera's refinement as refinement() would return it alone."""
+    prep = [_prepare_camera(pu, pv, has, cols, rows, pitch, size, device, init, model)
+            for pu, pv, has, size, init in zip(pus, pvs, hases, img_sizes, init_intrs)]
+    res = api.refinement_batch([q for q, _, _ in prep], device, loss=loss, fixed=[int(w) for w in masks])
+    return [_finish_camera(q, count, sel) + (summary,) for (q, count, sel), (_, summary) in zip(prep, res)]
 
 
 def _top_left_is_bright(board_img, pitch):
@@ -74,23 +95,24 @@ def _top_left_is_bright(board_img, pitch):
     return g(pitch / 2, pitch / 2) + g(pitch * 3 / 2, pitch * 3 / 2) > g(pitch * 3 / 2, pitch / 2) + g(pitch / 2, pitch * 3 / 2)
 
 
-def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                    fixed=None) -> dict:
-    """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
-    loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
-    and held intrinsics of both refinements (calibrate_camera).
-    Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
+def _detect(images, cols, rows, sigma, device):
+    """main.cpp:24-50: the grey images, their size, has [V] and the detected corners pu / pv [V, n]."""
     n, V = cols * rows, len(images)
     grey = [im if im.ndim == 2 else maps.remap(im, *np.meshgrid(np.arange(im.shape[1], dtype=np.float32), np.arange(im.shape[0], dtype=np.float32)),
                                                 to_gray=True, device=device) for im in images]
     img_size = (grey[0].shape[1], grey[0].shape[0])
     has = np.zeros(V, dtype=np.uint8)
     pu, pv = np.zeros((V, n)), np.zeros((V, n))
-    for i, pts in enumerate(corners.find_chessboards(grey, cols, rows, sigma=sigma, device=device)):     # :24-50, one batch
+    for i, pts in enumerate(corners.find_chessboards(grey, cols, rows, sigma=sigma, device=device)):     # one batch
         if pts is not None:
             has[i], pu[i], pv[i] = 1, pts[:, 0], pts[:, 1]
-    intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed)   # :57
-    seen = np.flatnonzero(has)                                                # :59-126 refinement pass
+    return img_size, has, pu, pv
+
+
+def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device):
+    """main.cpp:59-126, the refinement pass on the remapped chessboards with the flip rule (pu / pv in place)."""
+    n = cols * rows
+    seen = np.flatnonzero(has)
     board_imgs = []
     for i in seen:
         desc = maps.chessboard_desc(intr, Rt[i], cols, rows, pitch)
@@ -105,6 +127,17 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
             pu[i], pv[i] = uv[:, 0], uv[:, 1]
         if _top_left_is_bright(board_img, pitch):                             # :72-89 / :107-121 flip rule
             pu[i], pv[i] = pu[i][::-1].copy(), pv[i][::-1].copy()
+
+
+def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
+                    fixed=None) -> dict:
+    """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
+    loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
+    and held intrinsics of both refinements (calibrate_camera).
+    Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
+    img_size, has, pu, pv = _detect(images, cols, rows, sigma, device)
+    intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed)   # :57
+    _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device)
     # :127 -- the second calibrate() of the same object: a converged first refinement left has_init_guess_ set (TS.cpp:78),
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
@@ -113,17 +146,43 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     return dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
 
 
+def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None,
+                          model="ts", masks=None) -> list:
+    """monocular_calib for every camera, stage by stage across the cameras: detection, the first calibrate, the refinement
+    pass, the second calibrate -- each of the two refinements of all cameras in one batch (api.refinement_batch).
+    masks: [C] mask words (model included).  Returns monocular_calib's dict per camera."""
+    n_cam = len(images_by_camera)
+    masks = np.zeros(n_cam, dtype=np.uint16) if masks is None else masks
+    det = [_detect(imgs, cols, rows, sigma, device) for imgs in images_by_camera]
+    sizes = [d[0] for d in det]
+    has = [d[1] for d in det]
+    pu = [d[2] for d in det]
+    pv = [d[3] for d in det]
+    first = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, [None] * n_cam, loss, model, masks)
+    for m, imgs in enumerate(images_by_camera):
+        _refine_pixels(imgs, first[m][0], first[m][1], has[m], pu[m], pv[m], cols, rows, pitch, sigma, device)
+    warm = [f[0] if f[2]["termination_type"] == 0 else None for f in first]
+    second = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, warm, loss, model, masks)
+    return [dict(intr=second[m][0], Rt=second[m][1], has=has[m], pix_u=pu[m], pix_v=pv[m], first=first[m][2], second=second[m][2])
+            for m in range(n_cam)]
+
+
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None) -> dict:
+                  fixed=None, batch_mono=False) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
     model ("ts" | "ds" | "ucm") and fixed (names or a [C] / [C, 9] mask, as for api.calibrate): held in every refinement and in
-    the joint solve; the YAML keeps the 9-vector with lambda (and xi) = 0 (calib_io.to_double_sphere / to_ucm convert)."""
+    the joint solve; the YAML keeps the 9-vector with lambda (and xi) = 0 (calib_io.to_double_sphere / to_ucm convert).
+    batch_mono: the per-camera flow stage by stage across the cameras, each of its two refinement passes one batch call for
+    all cameras (monocular_calib_batch); False (the default) runs monocular_calib camera after camera."""
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
-    mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]))
-            for m, imgs in enumerate(images_by_camera)]
+    if batch_mono:
+        mono = monocular_calib_batch(images_by_camera, cols, rows, pitch, sigma, device, loss=loss, model=model, masks=w)
+    else:
+        mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]))
+                for m, imgs in enumerate(images_by_camera)]
     W = board_points(cols, rows, pitch)
     inp = rig.RigInput(W, np.stack([m["intr"] for m in mono]), np.stack([m["has"] for m in mono]), np.stack([m["Rt"] for m in mono]),
                        np.stack([m["pix_u"] for m in mono]), np.stack([m["pix_v"] for m in mono])).normalised()
