@@ -136,8 +136,6 @@ __device__ __forceinline__ const double *rec_w(const double *rec, int slot) { re
 __device__ __forceinline__ const double *rec_e(const double *rec, int V, int slot) { return rec + (size_t)kRecW * V + (size_t)kRecE * slot; }
 __device__ __forceinline__ const double *rec_g(const double *rec, int V, int slot) { return rec + (size_t)(kRecW + kRecE) * V + (size_t)kRecG * slot; }
 
-enum TermReason { kNone = 0, kMaxIter, kGradTol, kMinRadius, kParamTol, kFuncTol, kInvalidSteps };
-
 struct Ctrl : CtrlHead {
     IterLog log[kMaxLog];
 };
@@ -2680,8 +2678,6 @@ __global__ __launch_bounds__(NTH) void k_backsub_prep(DevProblem P, DevState S, 
 // writer = false: the step is taken redundantly (k_schur_gram: every workgroup runs it in its head, on the same inputs,
 // to the same bits -- no hand-off, no kernel of its own); only the writer touches global memory.  out: the new state for
 // the calling workgroup.
-// (The batched mono route repeats this function's scalar trust-region logic in k_mb_control, tscm_mono_batch.h, on an array of
-// control blocks: a change to the step, the tolerance tests or the radius update here must be made there too -- DESIGN 16.)
 __device__ void control_step(const DevProblem &P, const DevState &S, int init, const ControlPre &pre, double *sm, const double *H, const double *sc, double *stage_copy,
                              bool writer, CtlOut *out)
 {
@@ -2740,80 +2736,8 @@ __device__ void control_step(const DevProblem &P, const DevState &S, int init, c
     KTLX(6, true);
 
     IterLog it;
-    it.pad = 0;
-    if (init) {
-        c.x_cost = cost; c.initial_cost = cost; c.x_norm = xnorm_t; c.gmax = gmax_t; c.gnorm = gnorm_t;
-        c.se_min = c.se_cur = c.se_ref = c.se_cand = cost; c.se_acc_ref = 0.0; c.se_acc_cand = 0.0;
-        it.iteration = 0; it.step_is_valid = 1; it.step_is_successful = 1;
-        it.cost = cost; it.cost_change = 0.0; it.gradient_max_norm = gmax_t; it.gradient_norm = gnorm_t;
-        it.step_norm = 0.0; it.relative_decrease = 0.0;
-        c.iteration = 0;
-    } else {
-        c.iteration += 1;
-        c.lm_iterations += 1;
-        it.iteration = c.iteration;
-        const double model = sc[0] + c.model_cam;
-        const double step_norm = sqrt(sc[1] + c.stepsq_cam);
-        const bool valid = !c.lin_fail && isfinite(model) && isfinite(step_norm) && model > 0.0;
-        c.lin_fail = 0;
-        it.step_is_valid = valid ? 1 : 0;
-        it.gradient_max_norm = c.gmax; it.gradient_norm = c.gnorm;
-        if (!valid) {
-            // HandleInvalidStep
-            if (++c.num_invalid >= o.max_invalid) { c.done = 1; c.term_type = 2; c.term_reason = kInvalidSteps; commit(); return; }
-            c.radius = c.radius / c.decrease_factor; c.decrease_factor *= 2.0;
-            it.cost = c.x_cost; it.cost_change = 0.0; it.step_norm = 0.0; it.relative_decrease = 0.0; it.step_is_successful = 0;
-        } else {
-            c.num_invalid = 0;
-            double cand = cost;
-            if (!isfinite(cand)) cand = DBL_MAX;
-            it.step_norm = step_norm;
-            it.cost_change = c.x_cost - cand;
-            it.cost = c.x_cost;
-            it.relative_decrease = 0.0;
-            it.step_is_successful = 0;
-            // ParameterToleranceReached / FunctionToleranceReached: return before accepting
-            if (step_norm <= o.parameter_tolerance * (c.x_norm + o.parameter_tolerance)) {
-                c.done = 1; c.term_type = 0; c.term_reason = kParamTol; commit(); return;
-            }
-            if (fabs(it.cost_change) <= o.function_tolerance * c.x_cost) {
-                c.done = 1; c.term_type = 0; c.term_reason = kFuncTol; commit(); return;
-            }
-            double q;
-            if (cand >= DBL_MAX) q = -DBL_MAX;
-            else {
-                const double rel = (c.se_cur - cand) / model;
-                const double hist = (c.se_ref - cand) / (c.se_acc_ref + model);
-                q = rel > hist ? rel : hist;
-            }
-            it.relative_decrease = q;
-            if (q > o.min_relative_decrease) {
-                // HandleSuccessfulStep
-                c.cur = tgt;
-                c.x_cost = cand; c.x_norm = xnorm_t; c.gmax = gmax_t; c.gnorm = gnorm_t;
-                it.cost = cand; it.gradient_max_norm = gmax_t; it.gradient_norm = gnorm_t;
-                it.step_is_successful = 1;
-                { const double w = 2.0 * q - 1.0; c.radius = c.radius / fmax(1.0 / 3.0, 1.0 - w * w * w); }
-                c.radius = fmin(o.max_radius, c.radius);
-                c.decrease_factor = 2.0;
-                c.se_cur = cand; c.se_acc_cand += model; c.se_acc_ref += model;
-                if (c.se_cur < c.se_min) { c.se_min = c.se_cur; c.se_cand = c.se_cur; c.se_acc_cand = 0.0; }
-                else if (c.se_cur > c.se_cand) { c.se_cand = c.se_cur; c.se_acc_cand = 0.0; }
-                c.se_ref = c.se_cand; c.se_acc_ref = c.se_acc_cand;
-            } else {
-                it.cost = cand;
-                c.radius = c.radius / c.decrease_factor; c.decrease_factor *= 2.0;
-            }
-        }
-    }
-    // FinalizeIterationAndCheckIfMinimizerCanContinue
-    if (it.step_is_successful) ++c.num_successful; else ++c.num_unsuccessful;
-    it.radius = c.radius;
-    if (writer && c.n_log < kMaxLog) g.log[c.n_log] = it;
-    ++c.n_log;
-    if (it.iteration >= o.max_num_iterations) { c.done = 1; c.term_type = 1; c.term_reason = kMaxIter; commit(); return; }
-    if (it.step_is_successful && it.gradient_max_norm <= o.gradient_tolerance) { c.done = 1; c.term_type = 0; c.term_reason = kGradTol; commit(); return; }
-    if (c.radius <= o.min_radius) { c.done = 1; c.term_type = 0; c.term_reason = kMinRadius; commit(); return; }
+    const StepInput in = { cost, gmax_t, gnorm_t, xnorm_t, sc[0] + c.model_cam, sqrt(sc[1] + c.stepsq_cam) };
+    if (lm_step(c, init, tgt, in, it) && writer && c.n_log <= kMaxLog) g.log[c.n_log - 1] = it;
     commit();
 }
 

@@ -143,6 +143,15 @@ struct ViewConst {
     double fx, fy, cx, cy, xi, lam, al;
 };
 
+// a mono problem's view: the camera pose is the identity, the intrinsics are I[0..6]
+TSCM_HD void mono_view_const(const double *I, ViewConst &vc)
+{
+    for (int q = 0; q < 9; ++q) vc.Rc[q] = (q % 4 == 0) ? 1.0 : 0.0;
+    for (int q = 0; q < 3; ++q) vc.tc[q] = 0.0;
+    for (int q = 0; q < 27; ++q) vc.dRc[q] = 0.0;
+    vc.fx = I[0]; vc.fy = I[1]; vc.cx = I[2]; vc.cy = I[3]; vc.xi = I[4]; vc.lam = I[5]; vc.al = I[6];
+}
+
 // residual r[2] and Jacobian rows JE[2][6] (board pose), JF[2][13] (camera pose 6, intrinsics 7)
 // of one corner with board point (x, y, 0) and observation (ou, ov).
 TSCM_HD void corner_residual_jacobian(const ViewConst &vc, double x, double y, double ou, double ov,

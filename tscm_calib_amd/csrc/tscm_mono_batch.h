@@ -10,8 +10,8 @@
 //                 -- then the back-substitution of the chunk's boards and the candidate
 //   k_mb_eval     one workgroup per chunk: residuals and Jacobians of the candidate's corners, the view records and the
 //                 chunk's camera-side partials
-//   k_mb_control  one workgroup per problem: the partials in chunk order, then the trust-region step of control_step
-//                 (tscm_kernels.h) on the problem's own control block
+//   k_mb_control  one workgroup per problem: the partials in chunk order, then the trust-region step (lm_step,
+//                 tscm_ctrl.h) on the problem's own control block
 // Every kernel of a problem whose control block says done returns at once: a terminated problem is frozen.  All problem
 // state is double-buffered like the single-problem route's (cur / cur ^ 1 per problem: a candidate goes into buffer
 // cur ^ 1 and becomes current on acceptance).
@@ -147,10 +147,7 @@ __global__ __launch_bounds__(kMbThreads) void k_mb_eval(MbDev D, int init)
     const int buf = init ? D.head[k].cur : D.head[k].cur ^ 1;
     const double *I = D.intr[buf] + 9 * k;
     ViewConst vc;
-    for (int q = 0; q < 9; ++q) vc.Rc[q] = (q % 4 == 0) ? 1.0 : 0.0;
-    for (int q = 0; q < 3; ++q) vc.tc[q] = 0.0;
-    for (int q = 0; q < 27; ++q) vc.dRc[q] = 0.0;
-    vc.fx = I[0]; vc.fy = I[1]; vc.cx = I[2]; vc.cy = I[3]; vc.xi = I[4]; vc.lam = I[5]; vc.al = I[6];
+    mono_view_const(I, vc);
     const bool robust = D.loss.kind != kLossNone;
     int oa = 0, ob = 0;
     if (t < kMbOuts - 1) mb_out_cols(t, oa, ob);
@@ -158,8 +155,8 @@ __global__ __launch_bounds__(kMbThreads) void k_mb_eval(MbDev D, int init)
     double gmax = 0.0, gsq = 0.0, xsq = 0.0;            // thread 0: the chunk's board-side norms
     for (int s = ch.y; s < ch.z; ++s) {
         const double *rt = D.board[buf] + 6 * (size_t)D.slot_board[s];
-        double bc[kBoardConst];
-        board_constants(rt, bc);
+        double bc[kBoardConst];                         // (in line, not a helper shared with the host: behind a call the
+        board_constants(rt, bc);                        // compiler pairs the Jacobian's products differently and bits move)
         for (int q = 0; q < 3; ++q) { vc.r1[q] = bc[q]; vc.r2[q] = bc[3 + q]; vc.tb[q] = rt[3 + q]; }
         for (int kk = 0; kk < 3; ++kk) for (int q = 0; q < 6; ++q) vc.db[kk][q] = bc[6 + 6 * kk + q];
         const int n = D.slot_count[s], o0 = D.slot_obs[s];
@@ -362,10 +359,8 @@ __global__ __launch_bounds__(kMbThreads) void k_mb_solve(MbDev D)
     }
 }
 
-// The problem's evaluation partials in chunk order, then the trust-region step: the scalar logic of control_step
-// (tscm_kernels.h) on this problem's control block, its log and its camera-side norms.  A copy, not a shared function:
-// control_step keeps its state in registers across a fused launch's barriers and writes through DevState, and factoring its
-// body out would recompile every single-problem kernel that inlines it.  Keep the two in step.
+// The problem's evaluation partials in chunk order, then the trust-region step (lm_step, tscm_ctrl.h) on this problem's
+// control block, its log and its camera-side norms.
 __global__ __launch_bounds__(64) void k_mb_control(MbDev D, int init)
 {
     __shared__ double sv[64];
@@ -407,86 +402,20 @@ __global__ __launch_bounds__(64) void k_mb_control(MbDev D, int init)
     const double gnorm_t = sqrt(gsq_c + sv[58]);
     const double xnorm_t = sqrt(xsq_c + sv[59]);
     const double *cm = D.cam_mp + 4 * k;
-    auto commit = [&]() {
-        const bool now_done = c.done != 0;
-        D.head[k] = c;
-        if (now_done) atomicAdd(D.n_done, 1);
-    };
+    StepInput in = { cost, gmax_t, gnorm_t, xnorm_t, 0.0, 0.0 };
     IterLog it;
-    it.pad = 0;
-    if (init) {
-        c.x_cost = cost; c.initial_cost = cost; c.x_norm = xnorm_t; c.gmax = gmax_t; c.gnorm = gnorm_t;
-        c.se_min = c.se_cur = c.se_ref = c.se_cand = cost; c.se_acc_ref = 0.0; c.se_acc_cand = 0.0;
-        it.iteration = 0; it.step_is_valid = 1; it.step_is_successful = 1;
-        it.cost = cost; it.cost_change = 0.0; it.gradient_max_norm = gmax_t; it.gradient_norm = gnorm_t;
-        it.step_norm = 0.0; it.relative_decrease = 0.0;
-        c.iteration = 0;
-    } else {
-        c.iteration += 1;
-        c.lm_iterations += 1;
-        it.iteration = c.iteration;
+    bool logged;
+    if (init) logged = lm_step(c, 1, buf, in, it);      // no step yet: cam_mp and solvep are not written
+    else {
         c.lin_fail = cm[2] != 0.0 ? 1 : 0;
-        const double model = sv[60] + cm[0];
-        const double step_norm = sqrt(sv[61] + cm[1]);
         // the model cost change of Ceres is -(J h)^T (r + J h / 2); the partials hold its negation
-        const double mcc = -model;
-        const bool valid = !c.lin_fail && isfinite(mcc) && isfinite(step_norm) && mcc > 0.0;
-        c.lin_fail = 0;
-        it.step_is_valid = valid ? 1 : 0;
-        it.gradient_max_norm = c.gmax; it.gradient_norm = c.gnorm;
-        if (!valid) {
-            if (++c.num_invalid >= o.max_invalid) { c.done = 1; c.term_type = 2; c.term_reason = kInvalidSteps; commit(); return; }
-            c.radius = c.radius / c.decrease_factor; c.decrease_factor *= 2.0;
-            it.cost = c.x_cost; it.cost_change = 0.0; it.step_norm = 0.0; it.relative_decrease = 0.0; it.step_is_successful = 0;
-        } else {
-            c.num_invalid = 0;
-            double cand = cost;
-            if (!isfinite(cand)) cand = DBL_MAX;
-            it.step_norm = step_norm;
-            it.cost_change = c.x_cost - cand;
-            it.cost = c.x_cost;
-            it.relative_decrease = 0.0;
-            it.step_is_successful = 0;
-            if (step_norm <= o.parameter_tolerance * (c.x_norm + o.parameter_tolerance)) {
-                c.done = 1; c.term_type = 0; c.term_reason = kParamTol; commit(); return;
-            }
-            if (fabs(it.cost_change) <= o.function_tolerance * c.x_cost) {
-                c.done = 1; c.term_type = 0; c.term_reason = kFuncTol; commit(); return;
-            }
-            double q;
-            if (cand >= DBL_MAX) q = -DBL_MAX;
-            else {
-                const double rel = (c.se_cur - cand) / mcc;
-                const double hist = (c.se_ref - cand) / (c.se_acc_ref + mcc);
-                q = rel > hist ? rel : hist;
-            }
-            it.relative_decrease = q;
-            if (q > o.min_relative_decrease) {
-                c.cur = buf;
-                c.x_cost = cand; c.x_norm = xnorm_t; c.gmax = gmax_t; c.gnorm = gnorm_t;
-                it.cost = cand; it.gradient_max_norm = gmax_t; it.gradient_norm = gnorm_t;
-                it.step_is_successful = 1;
-                { const double w = 2.0 * q - 1.0; c.radius = c.radius / fmax(1.0 / 3.0, 1.0 - w * w * w); }
-                c.radius = fmin(o.max_radius, c.radius);
-                c.decrease_factor = 2.0;
-                c.se_cur = cand; c.se_acc_cand += mcc; c.se_acc_ref += mcc;
-                if (c.se_cur < c.se_min) { c.se_min = c.se_cur; c.se_cand = c.se_cur; c.se_acc_cand = 0.0; }
-                else if (c.se_cur > c.se_cand) { c.se_cand = c.se_cur; c.se_acc_cand = 0.0; }
-                c.se_ref = c.se_cand; c.se_acc_ref = c.se_acc_cand;
-            } else {
-                it.cost = cand;
-                c.radius = c.radius / c.decrease_factor; c.decrease_factor *= 2.0;
-            }
-        }
+        in.model_cost_change = -(sv[60] + cm[0]);
+        in.step_norm = sqrt(sv[61] + cm[1]);
+        logged = lm_step(c, 0, buf, in, it);
     }
-    if (it.step_is_successful) ++c.num_successful; else ++c.num_unsuccessful;
-    it.radius = c.radius;
-    if (c.n_log < kMaxLog) D.log[(size_t)kMaxLog * k + c.n_log] = it;
-    ++c.n_log;
-    if (it.iteration >= o.max_num_iterations) { c.done = 1; c.term_type = 1; c.term_reason = kMaxIter; commit(); return; }
-    if (it.step_is_successful && it.gradient_max_norm <= o.gradient_tolerance) { c.done = 1; c.term_type = 0; c.term_reason = kGradTol; commit(); return; }
-    if (c.radius <= o.min_radius) { c.done = 1; c.term_type = 0; c.term_reason = kMinRadius; commit(); return; }
-    commit();
+    if (logged && c.n_log <= kMaxLog) D.log[(size_t)kMaxLog * k + c.n_log - 1] = it;
+    D.head[k] = c;
+    if (c.done) atomicAdd(D.n_done, 1);
 }
 
 // the accepted point of every problem into one output buffer (intrinsics, then the concatenated boards)

@@ -942,6 +942,28 @@ struct LmRunGuard {
     }
 };
 
+// a terminated control block and its iteration log as a summary (times excepted); rmse: that of a plain loss, sqrt(2 cost / N)
+static void fill_summary(const CtrlHead &h, const IterLog *log, long N, tscm_summary *sum)
+{
+    sum->termination_type = h.term_type;
+    sum->num_iterations = std::min(h.n_log, TSCM_MAX_ITERATIONS + 1);
+    sum->num_successful_steps = h.num_successful;
+    sum->num_unsuccessful_steps = h.num_unsuccessful;
+    sum->initial_cost = h.initial_cost;
+    sum->final_cost = h.x_cost;
+    sum->n_residual_blocks = (int)N;
+    sum->lm_iterations = h.lm_iterations;
+    for (int i = 0; i < sum->num_iterations; ++i) {
+        const IterLog &l = log[i];
+        tscm_iteration &o = sum->iterations[i];
+        o.iteration = l.iteration; o.step_is_valid = l.step_is_valid; o.step_is_successful = l.step_is_successful;
+        o.cost = l.cost; o.cost_change = l.cost_change; o.gradient_max_norm = l.gradient_max_norm; o.gradient_norm = l.gradient_norm;
+        o.step_norm = l.step_norm; o.relative_decrease = l.relative_decrease; o.trust_region_radius = l.radius;
+    }
+    std::snprintf(sum->message, sizeof(sum->message), "%s", reason_message(h.term_reason));
+    sum->rmse = N ? std::sqrt(2.0 * h.x_cost / (double)N) : 0.0;
+}
+
 static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, int reset, bool rerun, bool *late_handoff);
 
 // the caller's struct may be SHORTER than this library's (built against an older header of ABI >= 6): read what it has, the
@@ -1133,25 +1155,9 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         if ((rc = collect_timing(s))) return rc;
         if (h->fault) { *late_handoff = true; return fail(TSCM_E_HIP, "a device-side hand-off (Schur-complement tiles -> reduced solve) did not arrive within its time bound: the solve was stopped"); }
         if (!h->done) return fail(TSCM_E_HIP, "device LM loop did not terminate");
-        sum->termination_type = h->term_type;
-        sum->num_iterations = std::min(h->n_log, TSCM_MAX_ITERATIONS + 1);
-        sum->num_successful_steps = h->num_successful;
-        sum->num_unsuccessful_steps = h->num_unsuccessful;
-        sum->initial_cost = h->initial_cost;
-        sum->final_cost = h->x_cost;
-        sum->n_residual_blocks = (int)s->L.N_total;
-        sum->lm_iterations = h->lm_iterations;
-        for (int i = 0; i < sum->num_iterations; ++i) {
-            const IterLog &l = h->log[i];
-            tscm_iteration &o = sum->iterations[i];
-            o.iteration = l.iteration; o.step_is_valid = l.step_is_valid; o.step_is_successful = l.step_is_successful;
-            o.cost = l.cost; o.cost_change = l.cost_change; o.gradient_max_norm = l.gradient_max_norm; o.gradient_norm = l.gradient_norm;
-            o.step_norm = l.step_norm; o.relative_decrease = l.relative_decrease; o.trust_region_radius = l.radius;
-        }
-        std::snprintf(sum->message, sizeof(sum->message), "%s", reason_message(h->term_reason));
+        fill_summary(*h, h->log, (long)s->L.N_total, sum);                // cost and N of the WHOLE job
         sum->seconds_solve = 1e-8 * (double)(h->t_end - h->t_begin);      // on the device: first to last kernel of the solve
         sum->seconds_total = t1 - t0;                                     // wall time of the call
-        sum->rmse = s->L.N_total ? std::sqrt(2.0 * h->x_cost / (double)s->L.N_total) : 0.0;     // cost and N of the WHOLE job
     }
     // with a loss the cost is sum rho / 2, not the squared pixel error: the RMSE is measured at the accepted point instead
     if (s0->loss.kind != TSCM_LOSS_NONE) return robust_rmse(run, sums);
@@ -1580,11 +1586,7 @@ struct MbStream {
 static double mb_pixel_rmse(const tscm_problem &p)
 {
     ViewConst vc;
-    for (int q = 0; q < 9; ++q) vc.Rc[q] = (q % 4 == 0) ? 1.0 : 0.0;
-    for (int q = 0; q < 3; ++q) vc.tc[q] = 0.0;
-    for (int q = 0; q < 27; ++q) vc.dRc[q] = 0.0;
-    const double *I = p.intr;
-    vc.fx = I[0]; vc.fy = I[1]; vc.cx = I[2]; vc.cy = I[3]; vc.xi = I[4]; vc.lam = I[5]; vc.al = I[6];
+    mono_view_const(p.intr, vc);
     double sq = 0.0;
     long n = 0;
     for (int v = 0; v < p.n_views; ++v) {
@@ -1734,23 +1736,8 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
             std::memcpy(p.intr, &out[9 * (size_t)k], 9 * sizeof(double));
             if (p.n_boards) std::memcpy(p.board_rt, &out[9 * (size_t)K + 6 * (size_t)bp.board_ptr[k]], 6 * sizeof(double) * p.n_boards);
             const long N_k = bp.obs_ptr[k + 1] - bp.obs_ptr[k];
-            sum->termination_type = h.term_type;
-            sum->num_iterations = std::min(h.n_log, TSCM_MAX_ITERATIONS + 1);
-            sum->num_successful_steps = h.num_successful;
-            sum->num_unsuccessful_steps = h.num_unsuccessful;
-            sum->initial_cost = h.initial_cost;
-            sum->final_cost = h.x_cost;
-            sum->n_residual_blocks = (int)N_k;
-            sum->lm_iterations = h.lm_iterations;
-            for (int j = 0; j < sum->num_iterations; ++j) {
-                const IterLog &l = logs[(size_t)kMaxLog * k + j];
-                tscm_iteration &o = sum->iterations[j];
-                o.iteration = l.iteration; o.step_is_valid = l.step_is_valid; o.step_is_successful = l.step_is_successful;
-                o.cost = l.cost; o.cost_change = l.cost_change; o.gradient_max_norm = l.gradient_max_norm; o.gradient_norm = l.gradient_norm;
-                o.step_norm = l.step_norm; o.relative_decrease = l.relative_decrease; o.trust_region_radius = l.radius;
-            }
-            std::snprintf(sum->message, sizeof(sum->message), "%s", reason_message(h.term_reason));
-            sum->rmse = loss.kind != TSCM_LOSS_NONE ? mb_pixel_rmse(p) : N_k ? std::sqrt(2.0 * h.x_cost / (double)N_k) : 0.0;
+            fill_summary(h, logs + (size_t)kMaxLog * k, N_k, sum);
+            if (loss.kind != TSCM_LOSS_NONE) sum->rmse = mb_pixel_rmse(p);
         }
     }
     // problems without a single corner: what the single-problem entry point returns for them
