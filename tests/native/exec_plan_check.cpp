@@ -5,6 +5,7 @@
 //   usage: exec_plan_check rows                         one JSON line: per row, the facts the Python test asserts
 //          exec_plan_check random <seed> <problems>     one JSON line: counts of what the problems exercised
 //          exec_plan_check refusals                     one JSON line: code and message of every refusal case
+//          exec_plan_check g4 <n>...                    one JSON line: kG4MaxKS and g4_plan's passes, per, ks of every board size n
 #include "exec_problems.h"
 #include "../../tscm_calib_amd/csrc/tscm_launch_seq.h"
 
@@ -242,11 +243,24 @@ static int refusals()
     return 0;
 }
 
+// ---- the Gram kernels' pass plan ----------------------------------------------------------------------
+static int g4(int n, char **sizes)
+{
+    std::printf("{\"max_ks\": %d, \"plans\": {", kG4MaxKS);
+    for (int i = 0; i < n; ++i) {
+        const G4Plan g = g4_plan(std::atoi(sizes[i]));
+        std::printf("\"%d\": [%d, %d, %d]%s", std::atoi(sizes[i]), g.passes, g.per, g.ks, i + 1 < n ? ", " : "");
+    }
+    std::printf("}}\n");
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && !std::strcmp(argv[1], "rows")) return rows();
     if (argc >= 4 && !std::strcmp(argv[1], "random")) return random_run(std::strtoull(argv[2], nullptr, 10), std::atoi(argv[3]));
     if (argc >= 2 && !std::strcmp(argv[1], "refusals")) return refusals();
-    std::fprintf(stderr, "usage: exec_plan_check rows | random <seed> <problems> | refusals\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "g4")) return g4(argc - 2, argv + 2);
+    std::fprintf(stderr, "usage: exec_plan_check rows | random <seed> <problems> | refusals | g4 <n>...\n");
     return 2;
 }

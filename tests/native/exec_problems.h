@@ -17,20 +17,23 @@ namespace tscm {
 
 // a problem's view tables (the parameter arrays only need to be non-NULL: the plan does not read them)
 struct Prob {
-    int C = 1, B = 0, n_points = 54;
+    int C = 1, B = 0, n_points = 54, mono = 0;
     std::vector<int> cam, board, offset, count;
+    std::vector<unsigned char> cam_const, board_const;      // held pose blocks; empty: the problem carries no such array
     double dummy[2] = { 0.0, 0.0 };
     tscm_problem p{};
     void add(int c, int b, int n) { offset.push_back(offset.empty() ? 0 : offset.back() + count.back()); cam.push_back(c); board.push_back(b); count.push_back(n); }
-    Layout plan(int n_cu = 256) {
+    Layout plan(int n_cu = 256, int waves_per_cu = 16) {
         p = tscm_problem{};
-        p.n_cameras = C; p.n_boards = B; p.n_points = n_points; p.n_views = (int)cam.size();
+        p.n_cameras = C; p.n_boards = B; p.n_points = n_points; p.n_views = (int)cam.size(); p.mono = mono;
+        p.cam_pose_constant = cam_const.empty() ? nullptr : cam_const.data();
+        p.board_pose_constant = board_const.empty() ? nullptr : board_const.data();
         p.board_xy = dummy; p.intr = dummy; p.board_rt = dummy; p.cam_rt = dummy; p.obs_u = dummy; p.obs_v = dummy;
         p.view_camera = cam.data(); p.view_board = board.data(); p.view_offset = offset.data(); p.view_count = count.data();
         Layout L;
         std::string err;
         LayoutDevice dev;
-        dev.n_cu = n_cu; dev.waves_per_cu = 16;
+        dev.n_cu = n_cu; dev.waves_per_cu = waves_per_cu;
         if (plan_layout(&p, 0, 1, dev, L, err)) { std::fprintf(stderr, "plan_layout: %s\n", err.c_str()); std::exit(2); }
         return L;
     }

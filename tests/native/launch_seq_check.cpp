@@ -6,7 +6,9 @@
 //   usage: launch_seq_check rows                         one JSON line: per fixed configuration, the kernels of each phase
 //          launch_seq_check random <seed> <problems>     one JSON line: counts of what the solves exercised
 //          launch_seq_check head                         one JSON line: ctrl_head_from_options against every option field
+//          launch_seq_check route < problem              one JSON line: layout, columns, plan and kernels of the problem on stdin
 #include "exec_problems.h"
+#include "../../tscm_calib_amd/csrc/tscm_columns.h"
 #include "../../tscm_calib_amd/csrc/tscm_launch_seq.h"
 
 #include <cstdio>
@@ -343,11 +345,85 @@ static int head()
     return 0;
 }
 
+// ---- one problem from stdin: what creation and a solve of two iterations decide on the host ------------------------------
+// Whitespace-separated integers:
+//   C B n_points mono   V   V x (camera board count)   C x cam_pose_constant   has B x board_pose_constant   has C x fixed mask
+//   exec_flags jacobian_fp32 loss_kind comm_kind   n_cu waves_per_cu
+//   workgroups per CU: k_schur_gram<1..3>, k_schur_gram<1..3, true>, k_solve_reduced<4, 16, 64, true>, k_solve_nd<tpt, true> on a plan
+//   of up to `split` bytes of LDS and on a larger one, then `split`
+static int next_int()
+{
+    int v = 0;
+    if (std::scanf("%d", &v) != 1) { std::fprintf(stderr, "route: input ends early\n"); std::exit(2); }
+    return v;
+}
+
+static int route()
+{
+    Prob q;
+    q.C = next_int(); q.B = next_int(); q.n_points = next_int(); q.mono = next_int();
+    for (int v = next_int(); v > 0; --v) { const int c = next_int(), b = next_int(); q.add(c, b, next_int()); }
+    for (int m = 0; m < q.C; ++m) q.cam_const.push_back((unsigned char)next_int());
+    if (next_int()) for (int b = 0; b < q.B; ++b) q.board_const.push_back((unsigned char)next_int());
+    std::vector<unsigned short> fixed;
+    if (next_int()) for (int m = 0; m < q.C; ++m) fixed.push_back((unsigned short)next_int());
+    tscm_options o{};
+    o.struct_size = sizeof(o);
+    o.exec_flags = next_int(); o.jacobian_fp32 = next_int();
+    const int loss = next_int(), comm = next_int(), n_cu = next_int(), waves_per_cu = next_int();
+    std::string err;
+    if (check_exec_options(o, loss, err)) { std::fprintf(stderr, "route: %s\n", err.c_str()); return 2; }
+    // tscm_solver_create_sharded: the layout, the residency of the launches that wait, the columns (apply_columns: both
+    // k_solve_nd plans' tpt and residency); tscm_solver_set_fixed_intrinsics: the columns under the mask
+    const Layout L = q.plan(n_cu, waves_per_cu);
+    ExecDevice d;
+    for (int nv = 1; nv <= 3; ++nv) d.schur_resident[nv] = next_int() * n_cu;
+    for (int nv = 1; nv <= 3; ++nv) d.schur_resident_ride[nv] = next_int() * n_cu;
+    const int dense4_per_cu = next_int(), nd_per_cu[2] = { next_int(), next_int() }, nd_lds_split = next_int();
+    if (q.C <= kDense4Cams) d.dense4_resident = dense4_per_cu * n_cu;
+    ColumnPlan cols;
+    if (int rc = plan_columns(L, q.C, fixed.empty() ? nullptr : fixed.data(), cols, err)) { std::fprintf(stderr, "route: %d %s\n", rc, err.c_str()); return 2; }
+    if (cols.has_nd)
+        for (int v = 0; v < 2; ++v) {
+            d.nd_resident[v] = nd_per_cu[sizeof(double) * cols.nd[v].lds_doubles > (size_t)nd_lds_split ? 1 : 0] * n_cu;
+            d.nd_tpt[v] = cols.nd[v].tpt;
+        }
+    // run_lm_inner: the plan (rp: the Jacobian tile's pitch of tscm_solver_create_sharded), then begin, two iterations, finish
+    Case c;
+    c.L = &L; c.C = q.C; c.d = d;
+    const int rp = 8 * ((std::min(64, q.n_points) + 7) / 8) + 2;
+    c.x = plan_exec(L, q.C, cols.n_act, comm, o.exec_flags, o.jacobian_fp32, loss, rp, d);
+    const ExecPlan &x = c.x;
+    // the back-substitution is a launch of its own only because the solve's launch would not be resident with it
+    ExecDevice roomy = d;
+    roomy.dense4_resident = roomy.nd_resident[0] = roomy.nd_resident[1] = 1 << 24;
+    const bool bs_ride_refused = !x.n_bs && plan_exec(L, q.C, cols.n_act, comm, o.exec_flags, o.jacobian_fp32, loss, rp, roomy).n_bs;
+    SeqState st;
+    int max_len = 0;
+    const std::vector<LaunchList> ph = plan_solve(c, 2, 0, Start::Init, st, &max_len);
+    replay(c, ph, Start::Init, 2);
+    static const char *solver[] = { "empty", "dense4", "nd", "big" }, *tail[] = { "reduce_control", "stats_head", "ride", "exchange" };
+    std::printf("{\"bs_threads\": %d, \"n_bs_blocks\": %d, \"nv_chunks\": [0, %d, %d, %d], \"n_bids\": %d, \"slow_boards\": %d, \"fallback_pairs\": %d, "
+                "\"n_act\": %d, \"dense4_cams\": %d, \"bs_ride_refused\": %d, ", L.bs_threads, L.n_bs_blocks, L.nv_chunks[1], L.nv_chunks[2], L.nv_chunks[3], L.n_bids, (int)L.slow_boards.size(),
+                (int)L.pair_i.size(), cols.n_act, kDense4Cams, (int)bs_ride_refused);
+    std::printf("\"plan\": {\"comm\": %d, \"gram\": %d, \"robust\": %d, \"tail\": \"%s\", \"ctl_in_schur\": %d, \"stats_ride\": %d, \"t_in_solve\": %d, "
+                "\"solver\": \"%s\", \"nd\": %d, \"tpt\": %d, \"n_prod\": %d, \"n_bs\": %d, \"bs_threads\": %d}, ", x.comm, (int)x.gram, x.robust,
+                tail[(int)x.tail], x.ctl_in_schur, x.stats_ride, x.t_in_solve, solver[(int)x.solver], x.nd, x.tpt, x.n_prod, x.n_bs, x.bs_threads);
+    if (x.solver == Solver::Nd) std::printf("\"nd_tpt\": %d, \"nd_dense\": %d, ", cols.nd[x.nd].tpt, (int)cols.nd[x.nd].dense);
+    std::printf("\"begin\": "); print_list(ph[0]);
+    std::printf(", \"first\": "); print_list(ph[1]);
+    std::printf(", \"iteration\": "); print_list(ph[2]);
+    std::printf(", \"finish\": "); print_list(ph[3]);
+    std::printf(", \"ok\": %s, \"failed\": \"%s\"}\n", g_fail.empty() ? "true" : "false", g_fail.c_str());
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc >= 2 && !std::strcmp(argv[1], "rows")) return rows();
     if (argc >= 4 && !std::strcmp(argv[1], "random")) return random_run(std::strtoull(argv[2], nullptr, 10), std::atoi(argv[3]));
     if (argc >= 2 && !std::strcmp(argv[1], "head")) return head();
-    std::fprintf(stderr, "usage: launch_seq_check rows | random <seed> <problems> | head\n");
+    if (argc >= 2 && !std::strcmp(argv[1], "route")) return route();
+    std::fprintf(stderr, "usage: launch_seq_check rows | random <seed> <problems> | head | route < problem\n");
     return 2;
 }

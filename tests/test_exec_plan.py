@@ -3,56 +3,25 @@ tests/native/exec_plan_check.cpp: the rows of DESIGN 4's launch table as decisio
 boundary residency figures, that a re-run never waits inside a launch, that every launch whose workgroups wait for each other
 fits on the chip and that each exec flag changes only what it names; and the option refusals.  Built twice: plain, and under
 AddressSanitizer + UBSan.  No GPU."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "exec_plan_check.cpp")
+from tests import native_check as N
+
 E_INVALID, E_UNSUPPORTED = -1, -5
 ITERATIONS = "max_num_iterations must be in [0, 255]"
 UNKNOWN_BITS = "unknown bits in tscm_options.exec_flags (an options struct of an older ABI?)"
 NO_ROBUST = "TSCM_EXEC_GRAM_16X16 has no robust-loss kernel"
 
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-
-
-def build(name, flags):
-    exe = os.path.join(ROOT, "tmp", name)
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-o", exe, SRC], capture_output=True, text=True)
-    return exe, r
-
-
-@pytest.fixture(scope="module", params=["plain", "asan_ubsan"])
-def checker(request):
-    if request.param == "plain":
-        exe, r = build("exec_plan_check", ["-O2"])
-    else:
-        exe, r = build("exec_plan_check_san", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
-        if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower():
-            pytest.skip("sanitizer runtime not installed")
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-def run(exe, *args):
-    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    return json.loads(r.stdout)
+pytestmark = N.NEEDS_GXX
+checker = N.checker_fixture("exec_plan_check.cpp", "exec_plan_check")
 
 
 def test_header_is_plain_cpp17():
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", os.path.join(ROOT, "tscm_calib_amd", "csrc", "tscm_exec_plan.h")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    N.assert_plain_cpp17("tscm_exec_plan.h")
 
 
 def test_design_table_rows(checker):
-    r = run(checker, "rows")
+    r = N.run(checker, "rows")
     # config 4 (one GPU, 4 cameras, every board seen by two): k_schur_gram<2, true> with the reductions riding ->
     # k_solve_reduced<4, 16, 64, true> with the T producers and every back-substitution workgroup -> the Gram kernel
     c4 = r["config4"]
@@ -95,7 +64,7 @@ def test_design_table_rows(checker):
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_random_problems(checker, seed):
-    r = run(checker, "random", seed, 200)
+    r = N.run(checker, "random", seed, 200)
     assert r["ok"], r
     # what the sample must have exercised: both rides, each at its boundary, every solver and every flag changing something
     assert r["stats_ride"] > 0 and r["bs_ride"] > 0 and r["bs_limit"] > 0 and r["stats_limit"] > 0, r
@@ -104,7 +73,7 @@ def test_random_problems(checker, seed):
 
 
 def test_refusals(checker):
-    r = run(checker, "refusals")
+    r = N.run(checker, "refusals")
     assert r == {
         "valid": [0, ""],
         "iterations_0": [0, ""],

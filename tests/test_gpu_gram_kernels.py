@@ -13,6 +13,7 @@ Reference: the oracle's dual-number Jacobian with numpy products (tests/helpers.
                 this tier too) within 1e-12 of gram4's
 tests/test_gram_tolerance.py shows, without a GPU, that these tolerances see a dropped, doubled or stale row.
 """
+import functools
 import time
 
 import numpy as np
@@ -22,6 +23,7 @@ from oracle import pyoracle as orc
 from tscm_calib_amd import api, lib, synth
 from tscm_calib_amd.problem import shard_frames
 from tests import helpers as H
+from tests import native_check as N
 
 # fp32 tier: largest entrywise error in units of sqrt(G_ii G_jj) (sqrt(G_ii r^T r) for gradients).  fp32 rounding of the
 # derivatives and <= 56 rows of fp32 accumulation per pass: measured <= 3.3e-6 on an MI355X, every board shape, views and
@@ -40,14 +42,17 @@ def f32_excess(e: dict) -> float:
     return max(v / TOL_F32[k] for k, v in e.items())
 
 
-# mirror of g4_plan (tscm_kernels.h): ceil(n / 56) passes of `per` = 4 KS corners, the last pass takes what is left
-MAX_KS = 14
+@functools.lru_cache(maxsize=None)
+def _g4():
+    """kG4MaxKS and g4_plan(n) of tscm_exec_plan.h for every board the library takes (up to about 2,000 corners), as one
+    run of tests/native/exec_plan_check.cpp prints them."""
+    r = N.run(N.built("exec_plan_check.cpp", "exec_plan_check"), "g4", *range(1, 2049))
+    return r["max_ks"], {int(n): tuple(plan) for n, plan in r["plans"].items()}
 
 
 def g4_plan(n):
-    passes = max(1, (n + 4 * MAX_KS - 1) // (4 * MAX_KS))
-    ks = max(1, ((n + passes - 1) // passes + 3) // 4)
-    return passes, 4 * ks, ks
+    """(passes, per, ks): ceil(n / 56) passes of `per` = 4 KS corners, the last pass takes what is left."""
+    return _g4()[1][n]
 
 
 SINGLE = [(2, 2), (3, 2), (3, 3), (4, 4), (5, 4), (6, 4), (7, 4), (6, 5), (7, 5), (8, 5), (7, 6), (8, 6), (7, 7), (9, 6)]
@@ -59,6 +64,8 @@ def test_shapes_reach_every_instantiation_of_the_pass_plan():
     """Every k_eval_gram4 / k_eval_gram_f32 instantiation (KS = 1..14 single-pass, 8..14 multi-pass) is run by the
     parametrisations below, and three- and four-pass views are among them."""
     plans = {(c, r): g4_plan(c * r) for c, r, _ in SHAPES}
+    MAX_KS = _g4()[0]
+    assert MAX_KS == 14
     reached = {(ks, passes > 1) for passes, _, ks in plans.values()}
     assert reached == {(k, False) for k in range(1, MAX_KS + 1)} | {(k, True) for k in range(8, MAX_KS + 1)}
     assert {passes for passes, _, _ in plans.values()} == {1, 2, 3, 4}

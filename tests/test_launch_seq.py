@@ -5,53 +5,22 @@ replayed against a model of the device's hand-off counters (riding reductions, c
 one control step per evaluation, no reductions dropped at the end, every waiting launch resident, a re-run without waiting
 launches, the fault injection on exactly the launches it names and the exchange markers where DESIGN 4 puts them; and the
 control block's head.  Built twice: plain, and under AddressSanitizer + UBSan.  No GPU."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "launch_seq_check.cpp")
-
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+from tests import native_check as N
 
 
-def build(name, flags):
-    exe = os.path.join(ROOT, "tmp", name)
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-o", exe, SRC], capture_output=True, text=True)
-    return exe, r
-
-
-@pytest.fixture(scope="module", params=["plain", "asan_ubsan"])
-def checker(request):
-    if request.param == "plain":
-        exe, r = build("launch_seq_check", ["-O2"])
-    else:
-        exe, r = build("launch_seq_check_san", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
-        if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower():
-            pytest.skip("sanitizer runtime not installed")
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-def run(exe, *args):
-    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    return json.loads(r.stdout)
+pytestmark = N.NEEDS_GXX
+checker = N.checker_fixture("launch_seq_check.cpp", "launch_seq_check")
 
 
 @pytest.mark.parametrize("header", ["tscm_launch_seq.h", "tscm_ctrl.h"])
 def test_header_is_plain_cpp17(header):
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", os.path.join(ROOT, "tscm_calib_amd", "csrc", header)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    N.assert_plain_cpp17(header)
 
 
 def test_design_table_sequences(checker):
-    r = run(checker, "rows")
+    r = N.run(checker, "rows")
     assert r.pop("ok"), r["failed"]
     r.pop("failed")
     # config 4: the initial evaluation's step in the first Schur head, the candidates' reductions riding in the next one, the
@@ -84,7 +53,7 @@ def test_design_table_sequences(checker):
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_random_solves(checker, seed):
-    r = run(checker, "random", seed, 150)
+    r = N.run(checker, "random", seed, 150)
     assert r["ok"], r
     # what the sample must have exercised: both rides, the head's control steps, the end-of-solve reductions of a riding plan,
     # both fault injections, the communicator, 9+ cameras, the re-run options; and the lists stayed within their capacity
@@ -94,5 +63,5 @@ def test_random_solves(checker, seed):
 
 
 def test_ctrl_head_carries_every_option(checker):
-    r = run(checker, "head")
+    r = N.run(checker, "head")
     assert r["ok"], r

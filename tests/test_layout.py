@@ -3,55 +3,24 @@ frame ownership, device view and board order, the Gram kernels' view chunks, the
 blocks of T, the Schur kernels' board chunks, fallback pairs and tile numbering -- checked on random problems for every rank
 by tests/native/layout_check.cpp, which re-derives each invariant from the problem, and the refusals at the problem-size
 limits, planned on view tables without observations.  Built twice: plain, and under AddressSanitizer + UBSan.  No GPU."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "native", "layout_check.cpp")
+from tests import native_check as N
+
 E_INVALID, E_UNSUPPORTED = -1, -5
 TOO_LARGE = "problem too large for 32-bit buffer offsets (more than 3.7 M views or 536 M corners on one GPU)"
 
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-
-
-def build(name, flags):
-    exe = os.path.join(ROOT, "tmp", name)
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", *flags, "-o", exe, SRC], capture_output=True, text=True)
-    return exe, r
-
-
-@pytest.fixture(scope="module", params=["plain", "asan_ubsan"])
-def checker(request):
-    if request.param == "plain":
-        exe, r = build("layout_check", ["-O2"])
-    else:
-        exe, r = build("layout_check_san", ["-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
-        if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower():
-            pytest.skip("sanitizer runtime not installed")
-    assert r.returncode == 0, r.stderr[-2000:]
-    return exe
-
-
-def run(exe, *args):
-    r = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    return json.loads(r.stdout)
+pytestmark = N.NEEDS_GXX
+checker = N.checker_fixture("layout_check.cpp", "layout_check")
 
 
 def test_header_is_plain_cpp17():
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-fsyntax-only", os.path.join(ROOT, "tscm_calib_amd", "csrc", "tscm_layout.h")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+    N.assert_plain_cpp17("tscm_layout.h")
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3, 4])
 def test_random_problems_every_rank(checker, seed):
-    r = run(checker, "random", seed, 250)
+    r = N.run(checker, "random", seed, 250)
     assert r["ok"], r
     # what the sample must have exercised: several worlds, mono and rigs past the register solver, views without corners,
     # boards of more than three views (fallback pairs), full board chunks and Gram chunks of several views
@@ -61,7 +30,7 @@ def test_random_problems_every_rank(checker, seed):
 
 
 def test_refusals(checker):
-    r = run(checker, "refusals")
+    r = N.run(checker, "refusals")
     expect = {
         "duplicate_view": [E_INVALID, "two views with the same (camera, board)"],
         "duplicate_empty_view": [0, ""],

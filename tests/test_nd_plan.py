@@ -2,26 +2,18 @@
 camera-pair graph -- levels of non-adjacent cameras, panels, steps, the structurally non-zero tiles -- and the tile
 algorithm k_solve_nd runs over it, emulated on the CPU by tests/native/nd_plan_check.cpp (same schedule, same masks, same
 double buffering between the same barriers) against a dense Cholesky solve of the same system.  No GPU."""
-import json
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tmp", "nd_plan_check")
+from tests import native_check as N
 
 
 @pytest.fixture(scope="module")
 def checker():
-    os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-o", EXE, os.path.join(ROOT, "tests", "native", "nd_plan_check.cpp")])
-    return EXE
+    return N.built("nd_plan_check.cpp", "nd_plan_check")
 
 
 def run(exe, C, graph, const_mask=1, inactive=0, dense=0, seed=1):
-    out = subprocess.check_output([exe, str(C), graph, str(const_mask), str(inactive), str(dense), str(seed)], text=True)
-    return json.loads(out)
+    return N.run(exe, C, graph, const_mask, inactive, dense, seed)
 
 
 CASES = [(C, g) for C in range(1, 9) for g in ("ring", "chain", "complete", "star")] + [

@@ -6,24 +6,27 @@
 2. Negative control: the reference is taken again with six mistakes a reduced-camera solver could make, and the backward
    error of test_gpu_step must see every one by at least MARGIN x its tolerance, fp64 and fp32 (the smallest signal
    measured is 3.6e-4: the right-hand side scaled twice on the mono problem, against TAU_B32 = 1e-6).
-3. Coverage: from the problem definitions alone (camera count, flags, camera-pair graph, cameras per board, constant
-   blocks), the cases of test_gpu_step reach every solver instantiation and option of its table.
+3. Coverage: by the library's own host plan of each problem (tests/native/launch_seq_check.cpp route: no Python copy of a
+   dispatch rule), the cases of test_gpu_step reach every solver instantiation and option of its table.
 """
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from oracle import pyoracle as orc
 from tscm_calib_amd import lib, synth
 from tests import helpers as H
+from tests import native_check as N
 from tests import test_gpu_step as G
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MARGIN = 20.0
-N_CUS = 256          # MI355X compute units: what the solver's residency rules are evaluated with
+# Device figures the coverage section plans with (tscm_layout.h: LayoutDevice, tscm_exec_plan.h: ExecDevice), as the library
+# measured them at creation on an MI355X for every problem of test_gpu_step: compute units, resident waves per CU of the
+# Gram kernel, and resident workgroups per CU of the launches whose workgroups wait for each other
+N_CUS, EVAL_WAVES_PER_CU = 256, 16
+SCHUR_WGS_PER_CU = SCHUR_RIDE_WGS_PER_CU = (2, 2, 1)    # k_schur_gram<1..3> and k_schur_gram<1..3, true>
+DENSE4_WGS_PER_CU = 3                                   # k_solve_reduced<4, 16, 64, true>
+# k_solve_nd<tpt, true>: 2 on plans of 16,896 to 59,840 bytes of LDS, 1 on plans of 71,312 and 75,424 (8 cameras, dense)
+ND_WGS_PER_CU, ND_LDS_SPLIT = (2, 1), 64 * 1024
 
 
 def _opt_key(opt):
@@ -172,63 +175,57 @@ def test_backward_error_of_the_reference_candidate_is_rounding_only():
 
 # ----------------------------------------------------------------------------- 3. coverage
 @pytest.fixture(scope="module")
-def nd_plan():
-    exe = os.path.join(ROOT, "tmp", "nd_plan_check")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tests", "native", "nd_plan_check.cpp")])
-    return exe
+def planner():
+    return N.built("launch_seq_check.cpp", "launch_seq_check")
 
 
-def cams_per_board(p):
-    cnt = np.asarray(p.view_count)
-    return [tuple(sorted(set(np.asarray(p.view_camera)[(np.asarray(p.view_board) == b) & (cnt > 0)].tolist()))) for b in range(p.n_boards)]
+def plan_of(p, opt, planner):
+    """What creation and a solve decide on the host for problem p: `launch_seq_check route` runs plan_layout, plan_columns,
+    plan_exec and the launch sequence of two iterations on the problem's view tables, flags and the figures above."""
+    rows = np.stack([np.asarray(p.view_camera), np.asarray(p.view_board), np.asarray(p.view_count)], axis=1)
+    bc = p.board_pose_constant
+    words = [p.n_cameras, p.n_boards, p.n_points, int(p.mono), len(rows), *rows.ravel().tolist(),
+             *np.asarray(p.cam_pose_constant).tolist(), *([0] if bc is None else [1, *np.asarray(bc).tolist()]), 0,
+             opt.get("exec_flags", 0), opt.get("jacobian_fp32", 0), lib.LOSS_NONE, 0,
+             N_CUS, EVAL_WAVES_PER_CU, *SCHUR_WGS_PER_CU, *SCHUR_RIDE_WGS_PER_CU, DENSE4_WGS_PER_CU, *ND_WGS_PER_CU, ND_LDS_SPLIT]
+    out = N.run(planner, "route", stdin=" ".join(map(str, words)))
+    assert out["ok"], out
+    return out
 
 
-def route(case, nd_plan):
-    """What a solve of this case runs, mirrored from tscm_solver.hip (tscm_solver_create_sharded, run_lm_inner,
-    enqueue_iteration) from the problem's definition alone."""
+def route(case, planner):
+    """What a solve of this case runs: the kernels and plan fields `launch_seq_check route` reports for it (the library's
+    own host headers), and the facts about the problem and its options that the table names."""
     name, prob, opt = case
     p = G.problem(prob)
-    C, B = p.n_cameras, p.n_boards
-    fl = opt.get("exec_flags", 0)
-    cpb = cams_per_board(p)
-    seen = [c for c in cpb if c]
     cols = H.step_columns(p)
+    out = plan_of(p, opt, planner)
+    x = out["plan"]
+    kernels = set(out["begin"] + out["first"] + out["iteration"] + out["finish"])
     r = set()
-    variant = 0 if C <= 4 else 1 if C <= 8 else 3
-    nd = 1 if fl & lib.EXEC_DENSE_REDUCED_ORDER else 0
-    graph = bool(fl & lib.EXEC_GRAPH_REDUCED_ORDER) or (variant == 0 and nd)
-    if variant == 0 and not graph:
+    if x["solver"] == "dense4":
         r.add("k_solve_reduced<4,16,64>")
-    elif variant <= 1:
-        pairs = sorted({(a, b) for c in seen for a in c for b in c if a < b})
-        gdesc = "pairs:" + ",".join(f"{a}-{b}" for a, b in pairs) if pairs else "pairs:"
-        const_mask = sum(1 << m for m in range(C) if p.cam_pose_constant[m]) if not p.mono else (1 << C) - 1
-        inactive = sum(1 << m for m in range(C) if not cols["cam_free"][m, 6])
-        out = json.loads(subprocess.check_output([nd_plan, str(C), gdesc, str(const_mask), str(inactive), str(nd), "1"], text=True))
-        assert out["ok"], (name, out)
-        r.add(f"k_solve_nd<{out['tpt']}>" + (" dense plan" if out["dense"] else " graph plan") + (" C<=4" if C <= 4 else ""))
-    else:
+    elif x["solver"] == "nd":
+        r.add(f"k_solve_nd<{out['nd_tpt']}>" + (" dense plan" if out["nd_dense"] else " graph plan") + (f" C<={out['dense4_cams']}" if p.n_cameras <= out["dense4_cams"] else ""))
+    elif x["solver"] == "big":
         r.add("k_solve_reduced_big")
-        n_compact = int(cols["cam_free"].sum())
-        r.add("compact columns % 16 == 0" if n_compact % 16 == 0 else "compact columns % 16 != 0")
+        r.add("compact columns % 16 == 0" if out["n_act"] % 16 == 0 else "compact columns % 16 != 0")
         if p.cam_pose_constant[1:].any():
             r.add("constant camera pose after camera 0")
-    # T reduction and back-substitution: fused into the reduced solve's launch on <= 8 cameras unless separated
-    small = C <= 8
-    r.add("k_T_reduce fused" if small and not fl & lib.EXEC_SEPARATE_T_REDUCE else "k_T_reduce")
-    bs_threads = 256 if (B + 15) // 16 > 5 * N_CUS * 3 // 2 or small else 128
-    n_bs = (B + (32 if bs_threads == 256 else 16) - 1) // (32 if bs_threads == 256 else 16)
-    resident = 3 * N_CUS            # (k_solve_reduced / k_solve_nd fused launch: three workgroups per CU)
-    if small and not fl & lib.EXEC_SEPARATE_BACKSUB and n_bs > resident - 1:
-        r.add("fused back-substitution does not fit resident")
-    elif small and not fl & lib.EXEC_SEPARATE_BACKSUB:
+    # T reduction and back-substitution: in the reduced solve's launch, or launches of their own
+    if x["t_in_solve"]:
+        r.add("k_T_reduce fused")
+    if "T_reduce" in kernels:
+        r.add("k_T_reduce")
+    if x["n_bs"]:
         r.add("k_backsub_prep fused")
-    r.add(f"k_backsub_prep<{bs_threads}>")
+    elif out["bs_ride_refused"]:
+        r.add("fused back-substitution does not fit resident")
+    r.add(f"k_backsub_prep<{out['bs_threads']}>")
+    r |= {f"k_schur_gram<{nv}>" for nv in (1, 2, 3) if {f"schur{nv}", f"schur_ride{nv}"} & kernels}
+    if "schur_factor" in kernels and "pair_gram" in kernels:
+        r.add("k_schur_factor + k_pair_gram")
     bf = cols["board_free"]
-    for b, c in enumerate(cpb):
-        if c and bf[b]:
-            r.add(f"k_schur_gram<{len(c)}>" if len(c) <= 3 else "k_schur_factor + k_pair_gram")
     if (~bf & cols["board_seen"]).any():
         r.add("constant board poses")
     if not cols["board_seen"].all():
@@ -270,14 +267,15 @@ EXPECTED = {
 }
 
 
-def test_cases_reach_every_row_of_the_table(nd_plan):
+def test_cases_reach_every_row_of_the_table(planner):
     reached = {}
     for case in G.CASES:
-        for x in route(case, nd_plan):
+        for x in route(case, planner):
             reached.setdefault(x, []).append(case[0])
     missing = EXPECTED - set(reached)
     assert not missing, missing
     # the solver rows each have a case of their own (distinct instantiation or option)
     assert "ring4-separate" in reached["k_T_reduce"] and "ring4" in reached["k_T_reduce fused"]
+    assert "ring4" in reached["k_solve_reduced<4,16,64>"] and "ring4-graph" in reached["k_solve_nd<1> graph plan C<=4"]
     assert "many_boards4" in reached["fused back-substitution does not fit resident"]
     assert set(G.VARIANT_CASES) <= set(G.CASE_BY_ID)

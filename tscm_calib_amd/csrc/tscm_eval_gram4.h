@@ -38,7 +38,7 @@
 // (included from tscm_kernels.h inside namespace tscm)
 
 constexpr int kG4Stride = 68;                   // doubles per k-step of the tile
-// (kG4MaxKS, g4_plan: tscm_kernels.h, in front of the fp32-Jacobian tier's kernel, which runs on the same pass plan)
+// (kG4MaxKS, g4_plan: tscm_exec_plan.h, next to plan_gram: the fp32-Jacobian tier's kernel runs on the same pass plan)
 // doubles of LDS per wave: the tile (>= the 512-double camera-tile exchange), then the board points
 __host__ __device__ constexpr int g4_tile_doubles(int ks) { return ks * kG4Stride > 512 ? ks * kG4Stride : 512; }
 __host__ __device__ inline int eval_gram4_lds_doubles(int n_points, int ks) { return g4_tile_doubles(ks) + 2 * n_points; }

@@ -10,6 +10,13 @@
 #include <algorithm>
 #include <string>
 
+// g4_plan is shared with device code (as lm_step, tscm_ctrl.h): unmarked under a plain C++ compiler
+#ifdef __HIPCC__
+#define TSCM_PLAN_FN __host__ __device__ inline
+#else
+#define TSCM_PLAN_FN inline
+#endif
+
 namespace tscm {
 
 constexpr int kCamSl = 16;         // the per-camera tile reduction runs in slices of 32 of the 512 raw entries: C * kCamSl workgroups
@@ -75,6 +82,21 @@ inline Gram plan_gram(int exec_flags, int jacobian_fp32, int rp)
     if (jacobian_fp32) return Gram::F32;
     if (!(exec_flags & TSCM_EXEC_GRAM_16X16)) return Gram::G4;
     return rp == 58 ? Gram::G16Pitch58 : Gram::G16;
+}
+
+// Pass plan of the Gram kernels k_eval_gram4 / k_eval_gram_f32 (round 6: every board size): a pass holds 4 KS <= 56 rows
+constexpr int kG4MaxKS = 14;                    // k-steps of a pass: at most 56 rows
+// pass plan of a board of n corners: ceil(n / 56) passes of `per` corners each (a multiple of four; the last pass takes what is left)
+struct G4Plan { int passes, per, ks; };
+TSCM_PLAN_FN G4Plan g4_plan(int n_points)
+{
+    G4Plan g;
+    g.passes = (n_points + 4 * kG4MaxKS - 1) / (4 * kG4MaxKS);
+    if (g.passes < 1) g.passes = 1;
+    g.ks = ((n_points + g.passes - 1) / g.passes + 3) / 4;
+    if (g.ks < 1) g.ks = 1;
+    g.per = 4 * g.ks;
+    return g;
 }
 
 inline ExecPlan plan_exec(const Layout &L, int C, int n_act, int comm_kind, int exec_flags, int jacobian_fp32, int loss_kind, int rp,

@@ -888,21 +888,6 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram(DevProblem P, DevState S, 
     }
 }
 
-// Pass plan of the Gram kernels k_eval_gram4 / k_eval_gram_f32 (round 6: every board size): a pass holds 4 KS <= 56 rows
-constexpr int kG4MaxKS = 14;                    // k-steps of a pass: at most 56 rows
-// pass plan of a board of n corners: ceil(n / 56) passes of `per` corners each (a multiple of four; the last pass takes what is left)
-struct G4Plan { int passes, per, ks; };
-__host__ __device__ inline G4Plan g4_plan(int n_points)
-{
-    G4Plan g;
-    g.passes = (n_points + 4 * kG4MaxKS - 1) / (4 * kG4MaxKS);
-    if (g.passes < 1) g.passes = 1;
-    g.ks = ((n_points + g.passes - 1) / g.passes + 3) / 4;
-    if (g.ks < 1) g.ks = 1;
-    g.per = 4 * g.ks;
-    return g;
-}
-
 // Robust loss of a residual block (one corner, s = r_u^2 + r_v^2): Ceres' HuberLoss, SoftLOneLoss, CauchyLoss
 // (loss_function.cc), same operations.  a: scale in pixels, b = a^2, c = 1 / b (all three computed on the host, as Ceres'
 // constructors do).  Every one of them has rho'' <= 0, so Ceres' Corrector takes its alpha = 0 branch: the residuals and the

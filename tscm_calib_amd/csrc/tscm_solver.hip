@@ -96,7 +96,7 @@ struct tscm_comm {
 };
 
 // the Gram kernels k_eval_gram4 / k_eval_gram_f32 share one signature; both are instantiated per k-step count of a pass
-// (tscm_eval_gram4.h: g4_plan), without and with a robust loss (ROBUST: DESIGN 14)
+// (tscm_exec_plan.h: g4_plan), without and with a robust loss (ROBUST: DESIGN 14)
 typedef void (*EvalKernel)(DevProblem, DevState, int, LossArg);
 template <bool ROBUST>
 static EvalKernel g4_kernel_of(int ks, bool multi)
