@@ -539,6 +539,40 @@ typedef struct tscm_map_desc {
 int tscm_build_maps(const tscm_map_desc *maps, int n_maps, int device, int exact, float *mapx,
                     float *mapy, size_t n_elems, double *seconds_kernel);
 
+/* Output images that are not pinholes.  A pinhole image cannot reach 90 degrees off axis; the Triple Sphere model is for
+ * lenses of 180 degrees and more, and the overlap of two adjacent cameras of a rig lies near the edge of both images.
+ * The projection kind of map m travels beside its descriptor (tscm_map_desc is frozen).  With a = (j - cx)/fx and
+ * b = (i - cy)/fy the ray before R is
+ *   PERSPECTIVE    (a, b, 1)                                        fx, fy: pixels per unit tangent (tscm_build_maps)
+ *   LONGLAT        (sin a, cos a sin b, cos a cos b)                pixels per radian; rows are planes through the x-axis,
+ *                                                                   so with R = R_cam^T * R_pair rows are epipolar lines
+ *   CYLINDRICAL    (sin a, b, cos a)                                fx: pixels per radian about y, fy: per unit height
+ *   STEREOGRAPHIC  (a, b, 1 - r2/4) / (1 + r2/4), r2 = a^2 + b^2    pixels per unit of 2 tan(theta/2)
+ *   EQUIRECT       (cos b sin a, sin b, cos b cos a)                pixels per radian: longitude about y, latitude
+ * All send the centre pixel to (0, 0, 1) and agree with the pinhole to first order there.  Everything after the ray -- R,
+ * the projection with its skew terms, check_w2, the offsets, out_stride / out_offset, untouched gaps, the refusals -- is
+ * tscm_build_maps.  An unknown kind is TSCM_E_INVALID (before any device is touched; the text names the map).
+ * projection == NULL or all PERSPECTIVE: the kernel of tscm_build_maps, the same bits.  PERSPECTIVE maps of a mixed
+ * batch keep those bits too.  For the other kinds `exact` selects the exact-order arithmetic of the part AFTER the ray;
+ * the ray itself comes from the device's fp64 sincos, which is accurate but not correctly rounded, so no bit-for-bit
+ * promise is made for them.                                                                                          */
+enum { TSCM_PROJ_PERSPECTIVE = 0, TSCM_PROJ_LONGLAT = 1, TSCM_PROJ_CYLINDRICAL = 2,
+       TSCM_PROJ_STEREOGRAPHIC = 3, TSCM_PROJ_EQUIRECT = 4 };
+
+int tscm_build_maps_ex(const tscm_map_desc *maps, const int *projection /* [n_maps], NULL = all perspective */,
+                       int n_maps, int device, int exact, float *mapx, float *mapy, size_t n_elems,
+                       double *seconds_kernel);
+
+/* The inverse direction for single points: pixel of the sampled camera -> get_unit_sphere_coordinate -> R^T -> the
+ * inverse of the table above (x/z, y/z | atan2(x, hypot(y, z)), atan2(y, z) | atan2(x, z), y/hypot(x, z) |
+ * 2(x, y)/(1 + z) | atan2(x, z), atan2(y, hypot(x, z))) -> out = (a fx + cx, b fy + cy), a position in the OUTPUT image.
+ * offset_x / offset_y do not enter: they belong to the sampled image (subtract them from the pixels first if the table
+ * carries them).  valid[k] = 0 and out = NaN when the pixel is outside the model's domain, when the ray is outside the
+ * projection's (PERSPECTIVE z <= 0, CYLINDRICAL x = z = 0, STEREOGRAPHIC z = -1), or when check_w2 is set and the ray
+ * fails the w2 rule.  n == 0 returns 0 without touching a device.                                                     */
+int tscm_rectify_points(const tscm_map_desc *map, int projection, const double *pixels /* [n*2] in the sampled camera */,
+                        int n, int device, double *out /* [n*2] (x, y) in the output image */, unsigned char *valid /* [n] */);
+
 
 /* ------------------------------------------------------------------ mono initialisation pieces
  * tscm_estimate_focal = TripleSphereCamera::estimate_focal (TS.cpp:110-168): one circle fit

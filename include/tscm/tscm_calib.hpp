@@ -17,6 +17,8 @@
 //   get_unit_sphere_coordinate           TS.h:39-57        get_unit_sphere_coordinate (batch)  -> tscm_unproject_pixels
 //   TripleSphereCamera::undistort        TS.cpp:284-306    TripleSphereCamera::undistort       -> tscm_build_maps
 //   undistort_chessboard (table)         TS.cpp:308-330    undistort_chessboard_maps           -> tscm_build_maps
+//   (none: pinhole tables only)                            undistort(..., projection), rectify_pair_maps -> tscm_build_maps_ex
+//   (none)                                                 TripleSphereCamera::rectify_point   -> tscm_rectify_points
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
@@ -302,6 +304,33 @@ public:
         check(tscm_build_maps(&d, 1, device_, exact ? 1 : 0, mapx.data(), mapy.data(), n, nullptr));
     }
 
+    // undistort with an output image of kind `projection` (TSCM_PROJ_*: fx, fy are pixels per radian for the angle kinds)
+    void undistort(double fx, double fy, double cx, double cy, Size img_size, std::vector<float> &mapx, std::vector<float> &mapy, bool exact, int projection) const
+    {
+        tscm_map_desc d = tscm_map_desc();
+        std::memcpy(d.intr, intrinsic_.data(), sizeof(d.intr));
+        d.R[0] = d.R[4] = d.R[8] = 1.0;
+        d.fx = fx; d.fy = fy; d.cx = cx; d.cy = cy;
+        d.width = img_size.width; d.height = img_size.height; d.out_stride = img_size.width;
+        const size_t n = (size_t)img_size.width * img_size.height;
+        mapx.assign(n, 0.f); mapy.assign(n, 0.f);
+        check(tscm_build_maps_ex(&d, &projection, 1, device_, exact ? 1 : 0, mapx.data(), mapy.data(), n, nullptr));
+    }
+
+    // where a pixel of this camera lands in the output image (fx, fy, cx, cy, R, projection) of undistort / a rectification
+    // table (R == nullptr: identity); false when it has no place there (tscm.h: tscm_rectify_points)
+    bool rectify_point(const Point2d &pixel, double fx, double fy, double cx, double cy, const Mat33 *R, int projection, Point2d &out) const
+    {
+        tscm_map_desc d = tscm_map_desc();
+        std::memcpy(d.intr, intrinsic_.data(), sizeof(d.intr));
+        if (R) std::memcpy(d.R, R->a, sizeof(d.R));
+        else d.R[0] = d.R[4] = d.R[8] = 1.0;
+        d.fx = fx; d.fy = fy; d.cx = cx; d.cy = cy;
+        unsigned char valid = 0;
+        check(tscm_rectify_points(&d, projection, &pixel.x, 1, device_, &out.x, &valid));
+        return valid != 0;
+    }
+
     // the table of undistort_chessboard(src, index, chessboard, chessboard_size), TS.cpp:308-328
     Size undistort_chessboard_maps(int index, Size chessboard, double chessboard_size, std::vector<float> &mapx, std::vector<float> &mapy,
                                    bool exact = true) const
@@ -578,6 +607,58 @@ inline Chessboarder_t findCorner(const unsigned char *gray, int width, int heigh
     tscm_chessboards_free(&b);
     tscm_corner_candidates_free(&c);
     return out;
+}
+
+// Remap::calc_R (rectify.cpp:234-248): x along the baseline t2 - t1, z horizontal, y = z x x
+inline Mat33 rectify_pair_rotation(const double t1[3], const double t2[3])
+{
+    double x[3] = { t2[0] - t1[0], t2[1] - t1[1], t2[2] - t1[2] };
+    double n = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    if (n != 0) for (int k = 0; k < 3; ++k) x[k] /= n;
+    double z[3] = { -x[2], 0.0, x[0] };
+    n = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+    if (n != 0) for (int k = 0; k < 3; ++k) z[k] /= n;
+    double y[3] = { -z[2] * x[1] + z[1] * x[2], z[2] * x[0] - z[0] * x[2], -z[1] * x[0] + z[0] * x[1] };
+    n = std::sqrt(y[0] * y[0] + y[1] * y[1] + y[2] * y[2]);
+    if (n != 0) for (int k = 0; k < 3; ++k) y[k] /= n;
+    Mat33 R;
+    for (int k = 0; k < 3; ++k) { R.a[3 * k] = x[k]; R.a[3 * k + 1] = y[k]; R.a[3 * k + 2] = z[k]; }
+    return R;
+}
+
+// The two tables that rectify a camera pair in an output image of kind `projection` spanning fov_x by fov_y radians:
+// intr [9] and Twc (row-major 3x4 [R | t], camera to rig, as tscm_yaml_read returns them) of both cameras; R of table k
+// is R_cam^T * rectify_pair_rotation(t_a, t_b), check_w2 = 1, offsets 0.  With TSCM_PROJ_LONGLAT a scene point lies on
+// the same row of both images over the whole hemisphere (fov_x up to pi).  Fills desc[2]; maps are size.height x size.width.
+inline void rectify_pair_maps(const double *intr_a, const double *Twc_a, const double *intr_b, const double *Twc_b, int projection, Size size,
+                              double fov_x, double fov_y, tscm_map_desc desc[2], std::vector<float> mapx[2], std::vector<float> mapy[2],
+                              bool exact = true, int device = 0)
+{
+    const double pi = 3.14159265358979323846;
+    const bool tan_x = projection == TSCM_PROJ_PERSPECTIVE, tan_y = tan_x || projection == TSCM_PROJ_CYLINDRICAL;
+    if ((tan_x && !(fov_x < pi)) || (tan_y && !(fov_y < pi))) throw std::runtime_error("tscm: a tangent axis cannot span 180 degrees or more");
+    double fx = size.width / fov_x, fy = size.height / fov_y;                      // pixels per radian
+    if (tan_x) fx = 0.5 * size.width / std::tan(0.5 * fov_x);
+    if (tan_y) fy = 0.5 * size.height / std::tan(0.5 * fov_y);
+    if (projection == TSCM_PROJ_STEREOGRAPHIC) { fx = 0.25 * size.width / std::tan(0.25 * fov_x); fy = 0.25 * size.height / std::tan(0.25 * fov_y); }
+    const double ta[3] = { Twc_a[3], Twc_a[7], Twc_a[11] }, tb[3] = { Twc_b[3], Twc_b[7], Twc_b[11] };
+    const Mat33 Rp = rectify_pair_rotation(ta, tb);
+    const size_t n = (size_t)size.width * size.height;
+    const int kinds[2] = { projection, projection };
+    for (int k = 0; k < 2; ++k) {
+        const double *T = k ? Twc_b : Twc_a;
+        tscm_map_desc &d = desc[k];
+        d = tscm_map_desc();
+        std::memcpy(d.intr, k ? intr_b : intr_a, sizeof(d.intr));
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) d.R[3 * r + c] = T[r] * Rp.a[c] + T[4 + r] * Rp.a[3 + c] + T[8 + r] * Rp.a[6 + c];      // R_cam^T * Rp
+        d.fx = fx; d.fy = fy; d.cx = 0.5 * size.width; d.cy = 0.5 * size.height;
+        d.width = size.width; d.height = size.height; d.out_stride = size.width;
+        d.check_w2 = 1; d.w2 = 0.42399;                                            // rectify.cpp:7
+        mapx[k].assign(n, 0.f); mapy[k].assign(n, 0.f);
+    }
+    // two launches: each table has its own host arrays
+    for (int k = 0; k < 2; ++k) check(tscm_build_maps_ex(&desc[k], &kinds[k], 1, device, exact ? 1 : 0, mapx[k].data(), mapy[k].data(), n, nullptr));
 }
 
 }  // namespace tscm

@@ -17,10 +17,28 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tscm_calib_amd import maps, synth  # noqa: E402
+from tscm_calib_amd import calib_io, lib, maps, synth  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0
 BYTES_PER_PIXEL = 8            # two float32 tables; the descriptors are 224 B per 141,750 pixels
+
+
+def rectify_tables(a):
+    """--tables rectify: kernel time (median and min over --repeats warm launches) of the reference's rectification set and
+    of one full-size undistortion table in the chosen kind, fast and exact."""
+    intr, Twc = calib_io.read_calib_yaml(os.path.join(ROOT, "tests", "golden", "reference_calib.yaml"))
+    eight, n8 = maps.rectify_descs(intr, Twc)
+    one = [maps.undistort_desc(intr[0], 300.0, 300.0, 639.5, 539.5, 1280, 1080)]
+    out = dict(metric="remap_table_kernel_seconds", unit="s", n_gpus=1, higher_is_better=False, projection=a.projection, repeats=a.repeats)
+    for name, descs, n in (("rectify_8x400x400", eight, n8), ("undistort_1280x1080", one, 1280 * 1080)):
+        for d in descs:
+            d.projection = lib.PROJ_KINDS[a.projection]
+        for exact in (False, True):
+            maps.build_maps(descs, n, exact=exact)
+            sec = sorted(maps.build_maps(descs, n, exact=exact)[2] for _ in range(a.repeats))
+            out[name + ("_exact" if exact else "_fast")] = dict(median=sec[len(sec) // 2], min=sec[0], pixels=n)
+    out["value"] = out["rectify_8x400x400_fast"]["median"]
+    print(json.dumps(out))
 
 
 def main():
@@ -29,7 +47,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--cpu-maps", type=int, default=40)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--projection", default="perspective", choices=list(lib.PROJ_KINDS),
+                    help="kind of the output images (tscm_build_maps_ex); the same tables, a and b in the kind's units")
+    ap.add_argument("--tables", default="chessboard", choices=["chessboard", "rectify"],
+                    help="rectify: the eight 400x400 tables of Remap::init_remap for the golden calibration and one 1280x1080 undistortion table")
     a = ap.parse_args()
+    if a.tables == "rectify":
+        return rectify_tables(a)
     p = synth.make_problem(4, a.views, 20244)
     views = np.nonzero(p.view_camera == 0)[0][: a.views]
     descs, off = [], 0
@@ -37,6 +61,7 @@ def main():
         rt = p.meta["gt_board_rt"][p.view_board[v]]
         R = synth.rodrigues(rt[:3])
         d = maps.chessboard_desc(p.meta["gt_intr"][0], np.stack([R[:, 0], R[:, 1], rt[3:]], axis=1), 9, 6, 45.0, out_offset=off)
+        d.projection = lib.PROJ_KINDS[a.projection]
         descs.append(d)
         off += (d.width * d.height + 3) // 4 * 4       # every table 16-byte aligned, like separately allocated cv::Mat
     out = dict(metric="remap_table_pixels_per_second", unit="pixels/s", n_gpus=1, higher_is_better=True, dtype="f64->f32",
@@ -60,6 +85,9 @@ def main():
         traffic = None
     out["roofline"] = dict(bound="hbm", achieved=gbs, peak=HBM_PEAK_GBS, unit="GB/s", frac=gbs / HBM_PEAK_GBS, traffic=traffic,
                            exact_variant_GBs=out["exact"]["pixels_per_second"] * BYTES_PER_PIXEL / 1e9)
+    if a.projection != "perspective":
+        out["config"]["projection"] = a.projection
+        a.no_cpu = True                      # the oracle builds pinhole tables only
     if not a.no_cpu:
         from oracle import pyoracle as orc   # cpu_baseline leg only
         sample = descs[: a.cpu_maps]

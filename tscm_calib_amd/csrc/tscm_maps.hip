@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tscm_fastmath.h"
+#include "tscm_math.h"
 
 #include <string>
 #include <vector>
@@ -114,6 +115,166 @@ __global__ __launch_bounds__(256) void k_build_maps(const tscm_map_desc *__restr
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Output images that are not pinholes (tscm.h: TSCM_PROJ_*).  Only the ray of an output element changes; from the ray
+// on -- R, TripleSphereCamera::project, the w2 rule, the offsets -- the arithmetic is that of map_pixel_*, with the
+// third ray component no longer the constant 1.
+__device__ __forceinline__ void map_ray_exact(const tscm_map_desc &m, double beta, double x, double y, double z, float &mx, float &my)
+{
+    const double X = __dadd_rn(__dadd_rn(__dmul_rn(m.R[0], x), __dmul_rn(m.R[1], y)), __dmul_rn(m.R[2], z));
+    const double Y = __dadd_rn(__dadd_rn(__dmul_rn(m.R[3], x), __dmul_rn(m.R[4], y)), __dmul_rn(m.R[5], z));
+    const double Z = __dadd_rn(__dadd_rn(__dmul_rn(m.R[6], x), __dmul_rn(m.R[7], y)), __dmul_rn(m.R[8], z));
+    const double rho2 = __dadd_rn(__dmul_rn(X, X), __dmul_rn(Y, Y));
+    const double d1 = __dsqrt_rn(__dadd_rn(rho2, __dmul_rn(Z, Z)));
+    const double z1 = __dadd_rn(Z, __dmul_rn(m.intr[4], d1));
+    const double d2 = __dsqrt_rn(__dadd_rn(rho2, __dmul_rn(z1, z1)));
+    const double z2 = __dadd_rn(z1, __dmul_rn(m.intr[5], d2));
+    const double d3 = __dsqrt_rn(__dadd_rn(rho2, __dmul_rn(z2, z2)));
+    const double ksai = __dadd_rn(z2, __dmul_rn(beta, d3));
+    double u = __dadd_rn(__dadd_rn(__ddiv_rn(__dmul_rn(m.intr[0], X), ksai), __ddiv_rn(__dmul_rn(m.intr[7], Y), ksai)), m.intr[2]);
+    double v = __dadd_rn(__dadd_rn(__ddiv_rn(__dmul_rn(m.intr[8], X), ksai), __ddiv_rn(__dmul_rn(m.intr[1], Y), ksai)), m.intr[3]);
+    if (m.check_w2 && Z <= __dmul_rn(-m.w2, d1)) { u = -1.0; v = -1.0; }
+    mx = (float)__dadd_rn(u, m.offset_x);
+    my = (float)__dadd_rn(v, m.offset_y);
+}
+
+__device__ __forceinline__ void map_ray_fast(const tscm_map_desc &m, double beta, double x, double y, double z, float &mx, float &my)
+{
+    const double X = __builtin_fma(m.R[0], x, __builtin_fma(m.R[1], y, m.R[2] * z));
+    const double Y = __builtin_fma(m.R[3], x, __builtin_fma(m.R[4], y, m.R[5] * z));
+    const double Z = __builtin_fma(m.R[6], x, __builtin_fma(m.R[7], y, m.R[8] * z));
+    const double rho2 = __builtin_fma(Y, Y, X * X);
+    const double s1 = __builtin_fma(Z, Z, rho2);
+    const double d1 = s1 * fast_rsqrt(s1);
+    const double z1 = __builtin_fma(m.intr[4], d1, Z);
+    const double s2 = __builtin_fma(z1, z1, rho2);
+    const double d2 = s2 * fast_rsqrt(s2);
+    const double z2 = __builtin_fma(m.intr[5], d2, z1);
+    const double s3 = __builtin_fma(z2, z2, rho2);
+    const double d3 = s3 * fast_rsqrt(s3);
+    const double ik = fast_rcp(__builtin_fma(beta, d3, z2));
+    const double xn = X * ik, yn = Y * ik;
+    double u = __builtin_fma(m.intr[0], xn, __builtin_fma(m.intr[7], yn, m.intr[2]));
+    double v = __builtin_fma(m.intr[8], xn, __builtin_fma(m.intr[1], yn, m.intr[3]));
+    if (m.check_w2 && Z <= -m.w2 * d1) { u = -1.0; v = -1.0; }
+    mx = (float)(u + m.offset_x);
+    my = (float)(v + m.offset_y);
+}
+
+// The part of the ray that depends on the output row alone: b = (i - cy)/fy for CYLINDRICAL and STEREOGRAPHIC,
+// (sin b, cos b) for LONGLAT and EQUIRECT.  One per quad (and one more where a flat quad runs over a row end).
+template <bool EXACT>
+__device__ __forceinline__ void row_term(const tscm_map_desc &m, int kind, double ify, int i, double &p, double &q)
+{
+    const double b = EXACT ? __ddiv_rn(__dsub_rn((double)i, m.cy), m.fy) : ((double)i - m.cy) * ify;
+    p = b; q = 0.0;
+    if (kind == TSCM_PROJ_LONGLAT || kind == TSCM_PROJ_EQUIRECT) sincos(b, &p, &q);
+}
+
+// k_build_maps for batches with a projection kind other than PERSPECTIVE among them: same grid, same quads, same stores;
+// the kind of a map comes from a second wave-uniform array, so the branch on it is uniform.  PERSPECTIVE maps of the batch
+// go through map_pixel_exact / map_pixel_fast and keep their bits.
+template <bool EXACT>
+__global__ __launch_bounds__(256) void k_build_maps_proj(const tscm_map_desc *__restrict__ maps, const int *__restrict__ kinds, float *__restrict__ mapx,
+                                                         float *__restrict__ mapy)
+{
+    const tscm_map_desc m = maps[blockIdx.y];
+    const int kind = kinds[blockIdx.y];
+    const bool flat = m.out_stride == m.width;
+    const int qpr = (m.width + 3) >> 2;
+    const long long total = (long long)m.width * m.height;
+    const long long nquads = flat ? (total + 3) >> 2 : (long long)qpr * m.height;
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= nquads) return;
+    const int den = flat ? m.width : qpr;
+    const long long num = flat ? 4 * q : q;
+    int i = (int)((double)num * fast_rcp((double)den));
+    int r = (int)(num - (long long)i * den);
+    if (r < 0) { --i; r += den; }
+    if (r >= den) { ++i; r -= den; }
+    int j = flat ? r : r * 4;
+    const double beta = EXACT ? __ddiv_rn(m.intr[6], __dsub_rn(1.0, m.intr[6])) : m.intr[6] * fast_rcp(1.0 - m.intr[6]);
+    const double ifx = EXACT ? 0.0 : fast_rcp(m.fx), ify = EXACT ? 0.0 : fast_rcp(m.fy);
+    const long long base = m.out_offset + (flat ? 4 * q : (long long)i * m.out_stride + j);
+    const int n = flat ? (int)min(4LL, total - 4 * q) : min(4, m.width - j);
+    float ox[4], oy[4];
+    if (kind == TSCM_PROJ_PERSPECTIVE) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (EXACT) map_pixel_exact(m, beta, i, j, ox[k], oy[k]);
+            else map_pixel_fast(m, beta, ifx, ify, i, j, ox[k], oy[k]);
+            if (++j == m.width) { j = 0; ++i; }
+        }
+    } else {
+        double rp, rq;
+        row_term<EXACT>(m, kind, ify, i, rp, rq);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double a = EXACT ? __ddiv_rn(__dsub_rn((double)j, m.cx), m.fx) : ((double)j - m.cx) * ifx;
+            double x, y, z;
+            if (kind == TSCM_PROJ_STEREOGRAPHIC) {
+                const double h = 0.25 * __builtin_fma(a, a, rp * rp);
+                const double inv = EXACT ? __ddiv_rn(1.0, 1.0 + h) : fast_rcp(1.0 + h);
+                x = a * inv; y = rp * inv; z = (1.0 - h) * inv;
+            } else {
+                double sa, ca;
+                sincos(a, &sa, &ca);
+                if (kind == TSCM_PROJ_LONGLAT) { x = sa; y = ca * rp; z = ca * rq; }
+                else if (kind == TSCM_PROJ_CYLINDRICAL) { x = sa; y = rp; z = ca; }
+                else { x = rq * sa; y = rp; z = rq * ca; }                      // EQUIRECT
+            }
+            if (EXACT) map_ray_exact(m, beta, x, y, z, ox[k], oy[k]);
+            else map_ray_fast(m, beta, x, y, z, ox[k], oy[k]);
+            if (++j == m.width) { j = 0; ++i; if (k < 3) row_term<EXACT>(m, kind, ify, i, rp, rq); }
+        }
+    }
+    if (n == 4 && (base & 3) == 0) {
+        *reinterpret_cast<float4 *>(mapx + base) = make_float4(ox[0], ox[1], ox[2], ox[3]);
+        *reinterpret_cast<float4 *>(mapy + base) = make_float4(oy[0], oy[1], oy[2], oy[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) { mapx[base + k] = ox[k]; mapy[base + k] = oy[k]; }
+    }
+}
+
+// tscm_rectify_points: one thread per pixel of the sampled camera -> its place in the output image of `m`
+__global__ __launch_bounds__(256) void k_rectify_points(const tscm_map_desc *__restrict__ map, int kind, const double *__restrict__ pixels, int n,
+                                                        double *__restrict__ out, unsigned char *__restrict__ valid)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const tscm_map_desc m = map[0];
+    double c[3];
+    unproject_pixel(m.intr, pixels[2 * t], pixels[2 * t + 1], c);
+    bool ok = c[0] == c[0] && c[1] == c[1] && c[2] == c[2];
+    if (m.check_w2 && c[2] <= -m.w2 * sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2])) ok = false;
+    const double x = m.R[0] * c[0] + m.R[3] * c[1] + m.R[6] * c[2];              // R^T
+    const double y = m.R[1] * c[0] + m.R[4] * c[1] + m.R[7] * c[2];
+    const double z = m.R[2] * c[0] + m.R[5] * c[1] + m.R[8] * c[2];
+    double a = 0.0, b = 0.0;
+    if (kind == TSCM_PROJ_PERSPECTIVE) {
+        if (z <= 0.0) ok = false;
+        a = x / z; b = y / z;
+    } else if (kind == TSCM_PROJ_LONGLAT) {
+        a = atan2(x, hypot(y, z)); b = atan2(y, z);
+    } else if (kind == TSCM_PROJ_CYLINDRICAL) {
+        const double h = hypot(x, z);
+        if (h == 0.0) ok = false;
+        a = atan2(x, z); b = y / h;
+    } else if (kind == TSCM_PROJ_STEREOGRAPHIC) {
+        const double nrm = sqrt(x * x + y * y + z * z), d = nrm + z;
+        if (!(d > 0.0)) ok = false;
+        a = 2.0 * x / d; b = 2.0 * y / d;
+    } else {
+        a = atan2(x, z); b = atan2(y, hypot(x, z));
+    }
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    out[2 * t] = ok ? a * m.fx + m.cx : nan;
+    out[2 * t + 1] = ok ? b * m.fy + m.cy : nan;
+    valid[t] = ok ? 1 : 0;
+}
+
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
@@ -123,8 +284,9 @@ struct DevBuf {
 
 }  // namespace
 
-extern "C" int tscm_build_maps(const tscm_map_desc *maps, int n_maps, int device, int exact, float *mapx, float *mapy, size_t n_elems,
-                               double *seconds_kernel)
+// kinds == NULL: every map is a pinhole, k_build_maps; otherwise [n_maps] valid kinds, k_build_maps_proj
+static int build_maps_host(const tscm_map_desc *maps, const int *kinds, int n_maps, int device, int exact, float *mapx, float *mapy, size_t n_elems,
+                           double *seconds_kernel)
 {
     if (n_maps < 0 || (n_maps > 0 && (!maps || !mapx || !mapy))) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
     if (n_maps > 65535) return tscm_set_error(TSCM_E_UNSUPPORTED, "more than 65535 maps in one call");
@@ -149,6 +311,11 @@ extern "C" int tscm_build_maps(const tscm_map_desc *maps, int n_maps, int device
     DevBuf<float> d_x, d_y;
     MAP_TRY(d_maps.alloc(n_maps)); MAP_TRY(d_x.alloc(n_elems)); MAP_TRY(d_y.alloc(n_elems));
     MAP_TRY(hipMemcpy(d_maps.p, maps, sizeof(tscm_map_desc) * n_maps, hipMemcpyHostToDevice));
+    DevBuf<int> d_kinds;
+    if (kinds) {
+        MAP_TRY(d_kinds.alloc(n_maps));
+        MAP_TRY(hipMemcpy(d_kinds.p, kinds, sizeof(int) * n_maps, hipMemcpyHostToDevice));
+    }
     // elements no map covers (row padding, gaps) keep the caller's values
     if (covered < n_elems) {
         MAP_TRY(hipMemcpy(d_x.p, mapx, sizeof(float) * n_elems, hipMemcpyHostToDevice));
@@ -158,8 +325,13 @@ extern "C" int tscm_build_maps(const tscm_map_desc *maps, int n_maps, int device
     MAP_TRY(hipEventCreate(&e0)); MAP_TRY(hipEventCreate(&e1));
     MAP_TRY(hipEventRecord(e0, 0));
     const dim3 grid((unsigned)((max_quads + 255) / 256), (unsigned)n_maps);
-    if (exact) hipLaunchKernelGGL(k_build_maps<true>, grid, dim3(256), 0, 0, d_maps.p, d_x.p, d_y.p);
-    else hipLaunchKernelGGL(k_build_maps<false>, grid, dim3(256), 0, 0, d_maps.p, d_x.p, d_y.p);
+    if (!kinds) {
+        if (exact) hipLaunchKernelGGL(k_build_maps<true>, grid, dim3(256), 0, 0, d_maps.p, d_x.p, d_y.p);
+        else hipLaunchKernelGGL(k_build_maps<false>, grid, dim3(256), 0, 0, d_maps.p, d_x.p, d_y.p);
+    } else {
+        if (exact) hipLaunchKernelGGL(k_build_maps_proj<true>, grid, dim3(256), 0, 0, d_maps.p, d_kinds.p, d_x.p, d_y.p);
+        else hipLaunchKernelGGL(k_build_maps_proj<false>, grid, dim3(256), 0, 0, d_maps.p, d_kinds.p, d_x.p, d_y.p);
+    }
     MAP_TRY(hipEventRecord(e1, 0));
     MAP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -169,6 +341,48 @@ extern "C" int tscm_build_maps(const tscm_map_desc *maps, int n_maps, int device
     if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
     MAP_TRY(hipMemcpy(mapx, d_x.p, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
     MAP_TRY(hipMemcpy(mapy, d_y.p, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int tscm_build_maps(const tscm_map_desc *maps, int n_maps, int device, int exact, float *mapx, float *mapy, size_t n_elems,
+                               double *seconds_kernel)
+{
+    return build_maps_host(maps, nullptr, n_maps, device, exact, mapx, mapy, n_elems, seconds_kernel);
+}
+
+static bool known_projection(int kind) { return kind >= TSCM_PROJ_PERSPECTIVE && kind <= TSCM_PROJ_EQUIRECT; }
+
+extern "C" int tscm_build_maps_ex(const tscm_map_desc *maps, const int *projection, int n_maps, int device, int exact, float *mapx, float *mapy,
+                                  size_t n_elems, double *seconds_kernel)
+{
+    bool pinholes = true;
+    for (int m = 0; projection && m < n_maps; ++m) {
+        if (!known_projection(projection[m]))
+            return tscm_set_error(TSCM_E_INVALID, "map " + std::to_string(m) + ": unknown projection kind " + std::to_string(projection[m]));
+        pinholes = pinholes && projection[m] == TSCM_PROJ_PERSPECTIVE;
+    }
+    return build_maps_host(maps, pinholes ? nullptr : projection, n_maps, device, exact, mapx, mapy, n_elems, seconds_kernel);
+}
+
+extern "C" int tscm_rectify_points(const tscm_map_desc *map, int projection, const double *pixels, int n, int device, double *out, unsigned char *valid)
+{
+    if (!map || n < 0 || (n > 0 && (!pixels || !out || !valid))) return tscm_set_error(TSCM_E_INVALID, n < 0 ? "negative point count" : "NULL argument");
+    if (!known_projection(projection)) return tscm_set_error(TSCM_E_INVALID, "map 0: unknown projection kind " + std::to_string(projection));
+    if (n == 0) return 0;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_rectify_points has no CPU fallback)");
+    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
+    MAP_TRY(hipSetDevice(device));
+    DevBuf<tscm_map_desc> d_map;
+    DevBuf<double> d_p, d_o;
+    DevBuf<unsigned char> d_v;
+    MAP_TRY(d_map.alloc(1)); MAP_TRY(d_p.alloc(2 * (size_t)n)); MAP_TRY(d_o.alloc(2 * (size_t)n)); MAP_TRY(d_v.alloc((size_t)n));
+    MAP_TRY(hipMemcpy(d_map.p, map, sizeof(tscm_map_desc), hipMemcpyHostToDevice));
+    MAP_TRY(hipMemcpy(d_p.p, pixels, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_rectify_points, dim3((n + 255) / 256), dim3(256), 0, 0, d_map.p, projection, d_p.p, n, d_o.p, d_v.p);
+    MAP_TRY(hipGetLastError());
+    MAP_TRY(hipMemcpy(out, d_o.p, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    MAP_TRY(hipMemcpy(valid, d_v.p, (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -30,6 +30,10 @@ EXEC_SEPARATE_STATS = 128
 # robust losses (tscm.h: TSCM_LOSS_*), by the names the Python layer takes
 LOSS_NONE, LOSS_HUBER, LOSS_SOFT_L1, LOSS_CAUCHY = 0, 1, 2, 3
 LOSS_KINDS = {None: LOSS_NONE, "none": LOSS_NONE, "huber": LOSS_HUBER, "soft_l1": LOSS_SOFT_L1, "cauchy": LOSS_CAUCHY}
+# output-image kinds of the remap tables (tscm.h: TSCM_PROJ_*)
+PROJ_PERSPECTIVE, PROJ_LONGLAT, PROJ_CYLINDRICAL, PROJ_STEREOGRAPHIC, PROJ_EQUIRECT = 0, 1, 2, 3, 4
+PROJ_KINDS = {"perspective": PROJ_PERSPECTIVE, "longlat": PROJ_LONGLAT, "cylindrical": PROJ_CYLINDRICAL,
+              "stereographic": PROJ_STEREOGRAPHIC, "equirect": PROJ_EQUIRECT}
 # held intrinsics (tscm.h: TSCM_FIX_*): bit k holds intrinsic k of the 9-vector
 INTRINSIC_NAMES = ("fx", "fy", "cx", "cy", "xi", "lambda", "alpha", "b", "c")
 FIX = {name: 1 << k for k, name in enumerate(INTRINSIC_NAMES)}
@@ -135,6 +139,7 @@ EXPORTS = [
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_planes_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
+    "tscm_build_maps_ex", "tscm_rectify_points",
 ]
 
 
@@ -217,6 +222,9 @@ def lib():
     L.tscm_rig_stage_errors.argtypes = [C.POINTER(CRigInput), C.c_int, dp, dp, C.c_int, C.c_int, dp, dp, dp, ip]
     L.tscm_build_maps.argtypes = [C.POINTER(CMapDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                   C.c_size_t, dp]
+    L.tscm_build_maps_ex.argtypes = [C.POINTER(CMapDesc), ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                     C.c_size_t, dp]
+    L.tscm_rectify_points.argtypes = [C.POINTER(CMapDesc), C.c_int, dp, C.c_int, C.c_int, dp, C.POINTER(C.c_ubyte)]
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]
     L.tscm_poses_from_r1r2t.argtypes = [dp, C.c_void_p, C.c_int, dp]
     L.tscm_estimate_extrinsic.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip]

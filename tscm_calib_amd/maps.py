@@ -1,6 +1,7 @@
 """Remap tables: host-side mirror of TripleSphereCamera::undistort (TS.cpp:284-306), the table of
 undistort_chessboard (TS.cpp:308-330) and Remap::init_remap (EpipolarRectify/rectify.cpp:86-199),
-all built by tscm_build_maps on the device."""
+all built by tscm_build_maps on the device; output images that are not pinholes (long-lat, cylindrical,
+stereographic, equirect: tscm_build_maps_ex) and the point direction tscm_rectify_points."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,10 +28,21 @@ class MapDesc:
     out_stride: int = 0         # 0 -> width
     check_w2: int = 0
     w2: float = 0.42399         # rectify.cpp:7
+    projection: int | str = 0   # tscm.h TSCM_PROJ_*, or "perspective", "longlat", "cylindrical", "stereographic", "equirect"
 
     def __post_init__(self):
         if self.out_stride == 0:
             self.out_stride = self.width
+        self.projection = projection_kind(self.projection)
+
+
+def projection_kind(projection) -> int:
+    """TSCM_PROJ_* of a kind name; integers pass (the C ABI refuses the ones it does not know)."""
+    if isinstance(projection, str):
+        if projection not in _lib.PROJ_KINDS:
+            raise ValueError(f"unknown projection {projection!r}: one of {', '.join(_lib.PROJ_KINDS)}")
+        return _lib.PROJ_KINDS[projection]
+    return int(projection)
 
 
 def undistort_desc(intr, fx, fy, cx, cy, width, height, **kw) -> MapDesc:
@@ -83,6 +95,51 @@ def rectify_descs(intr4, Twc4, size=400, mosaic_w=1280.0, mosaic_h=1080.0):
     return descs, 8 * block
 
 
+def _pinhole_of(kind: int, width: int, height: int, fov_x: float, fov_y: float):
+    """fx, fy, cx, cy of an output image of `kind` that spans fov_x by fov_y radians about its centre."""
+    def scale(n, fov, how):
+        if how == "angle":
+            return n / fov
+        if how == "tan":
+            if not fov < np.pi:
+                raise ValueError("a tangent axis cannot span 180 degrees or more")
+            return 0.5 * n / np.tan(0.5 * fov)
+        return 0.5 * n / (2.0 * np.tan(0.25 * fov))               # stereographic: 2 tan(theta / 2)
+    how = {_lib.PROJ_PERSPECTIVE: ("tan", "tan"), _lib.PROJ_LONGLAT: ("angle", "angle"), _lib.PROJ_CYLINDRICAL: ("angle", "tan"),
+           _lib.PROJ_STEREOGRAPHIC: ("stereo", "stereo"), _lib.PROJ_EQUIRECT: ("angle", "angle")}
+    if kind not in how:
+        raise ValueError(f"unknown projection kind {kind}")
+    return scale(width, fov_x, how[kind][0]), scale(height, fov_y, how[kind][1]), width / 2.0, height / 2.0
+
+
+def rectify_pair_descs(intr_a, Twc_a, intr_b, Twc_b, projection="longlat", width: int = 640, height: int = 320,
+                       fov_x: float = np.pi, fov_y: float = np.pi / 2):
+    """Two tables that rectify the camera pair (a, b): R = R_cam^T * rectify_pair_rotation(t_a, t_b), the x-axis of both
+    output images along the baseline.  With "longlat" (and "perspective") a scene point lies on the same row of both; the
+    long-lat image keeps that over the whole hemisphere (fov_x up to pi), where a pinhole cannot go."""
+    kind = projection_kind(projection)
+    fx, fy, cx, cy = _pinhole_of(kind, width, height, fov_x, fov_y)
+    Ta, Tb = np.asarray(Twc_a, dtype=np.float64).reshape(3, 4), np.asarray(Twc_b, dtype=np.float64).reshape(3, 4)
+    Rp = rectify_pair_rotation(Ta[:, 3], Tb[:, 3])
+    return [MapDesc(np.asarray(intr, dtype=np.float64), T[:, :3].T @ Rp, fx, fy, cx, cy, width, height, check_w2=1, projection=kind)
+            for intr, T in ((intr_a, Ta), (intr_b, Tb))]
+
+
+def panorama_descs(intr, Twc, width: int, height: int, projection="equirect"):
+    """One table per camera of the rig over the full 360 x 180 degrees in the rig frame (R = R_cam^T, check_w2 = 1):
+    element (i, j) of every table looks along the same rig-frame ray.  "equirect", or "cylindrical" (rows at unit height
+    per fx pixels).  No blending: the caller composes the tables' images."""
+    kind = projection_kind(projection)
+    if kind not in (_lib.PROJ_EQUIRECT, _lib.PROJ_CYLINDRICAL):
+        raise ValueError("a panorama is equirect or cylindrical")
+    fx = width / (2.0 * np.pi)
+    fy = height / np.pi if kind == _lib.PROJ_EQUIRECT else fx
+    intr = np.asarray(intr, dtype=np.float64).reshape(-1, 9)
+    Twc = np.asarray(Twc, dtype=np.float64).reshape(-1, 3, 4)
+    return [MapDesc(intr[k], Twc[k, :, :3].T.copy(), fx, fy, width / 2.0, height / 2.0, width, height, check_w2=1, projection=kind)
+            for k in range(intr.shape[0])]
+
+
 def _c_descs(descs):
     arr = (_lib.CMapDesc * len(descs))()
     for m, d in zip(arr, descs):
@@ -101,9 +158,25 @@ def build_maps(descs, n_elems: int | None = None, device: int = 0, exact: bool =
     fp = C.POINTER(C.c_float)
     sec = C.c_double(0.0)
     arr = _c_descs(descs)
+    kinds = [projection_kind(d.projection) for d in descs]
+    if any(kinds):                       # some output image is not a pinhole
+        _lib.check(_lib.lib().tscm_build_maps_ex(arr, (C.c_int * len(kinds))(*kinds), len(descs), device, 1 if exact else 0,
+                                                  mapx.ctypes.data_as(fp), mapy.ctypes.data_as(fp), n_elems,
+                                                  C.cast(C.byref(sec), C.POINTER(C.c_double))))
+        return mapx, mapy, sec.value
     _lib.check(_lib.lib().tscm_build_maps(arr, len(descs), device, 1 if exact else 0, mapx.ctypes.data_as(fp),
                                            mapy.ctypes.data_as(fp), n_elems, C.cast(C.byref(sec), C.POINTER(C.c_double))))
     return mapx, mapy, sec.value
+
+
+def rectify_points(desc: MapDesc, pixels, device: int = 0):
+    """tscm_rectify_points: pixels [n, 2] of the sampled camera -> (xy [n, 2] in the output image of `desc`, valid [n] bool).
+    desc.offset_x / offset_y do not enter (they belong to the sampled image); invalid points are NaN."""
+    px = np.ascontiguousarray(pixels, dtype=np.float64).reshape(-1, 2)
+    out, valid = np.zeros_like(px), np.zeros(px.shape[0], dtype=np.uint8)
+    _lib.check(_lib.lib().tscm_rectify_points(_c_descs([desc]), projection_kind(desc.projection), _lib.dptr(px), px.shape[0], device,
+                                               _lib.dptr(out), valid.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return out, valid.astype(bool)
 
 
 def remap(src, mapx, mapy, to_gray: bool = False, device: int = 0) -> np.ndarray:
