@@ -425,7 +425,7 @@ int tscm_comm_create_local(int world, int device, tscm_comm **out /* [world] */)
 /* IPC  one process per rank like RCCL; the exchange is the library's own one-shot all-reduce over buffers the ranks map
  *      from each other (hipIpcMemHandle).  Ranks MAY share a device (RCCL refuses that): the multi-process path on a
  *      one-GPU box.  Every rank calls tscm_comm_ipc_open (max_doubles >= 256 * max(camera-pair blocks, cameras) + 8 +
- *      world: api.Comm.ipc computes it), the 64-byte handles are all-gathered by the caller (socket, file, MPI ...),
+ *      world: api.Comm.ipc computes it), the handles (TSCM_IPC_HANDLE_BYTES each) are all-gathered by the caller (socket, file, MPI ...),
  *      every rank calls tscm_comm_ipc_connect with all of them in rank order; then tscm_solver_set_comm as with RCCL.
  *      Exercised between processes on one device; RCCL is the production path across devices. */
 #define TSCM_IPC_HANDLE_BYTES 80      /* (64 until ABI 5) the HIP handle, then the device's PCI address and the buffer's kind */

@@ -19,6 +19,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "tscm_host.h"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -27,14 +29,6 @@
 #include <mutex>
 #include <string>
 #include <vector>
-
-int tscm_set_error(int code, const std::string &msg);   // tscm_solver.hip
-
-#define CRN_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return tscm_set_error(TSCM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -655,10 +649,7 @@ int check_batch(const unsigned char *const *images, int n_images, int width, int
     if (width > 32767 || height > 32767) return tscm_set_error(TSCM_E_UNSUPPORTED, "images beyond 32767 pixels per side");
     const int ntap = 7 * sigma + 1;
     if (sigma < 1 || ntap % 2 == 0 || ntap > 64) return tscm_set_error(TSCM_E_UNSUPPORTED, "sigma must be even and at most 8 (cv::GaussianBlur needs an odd 7 sigma + 1; the reference uses 4)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (the corner detector has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    CRN_TRY(hipSetDevice(device));
+    if (int rc = tscm::select_device(device, "the corner detector")) return rc;
     if (device >= 16) return tscm_set_error(TSCM_E_UNSUPPORTED, "device index beyond 15");
     return 0;
 }
@@ -704,7 +695,7 @@ int corner_front(const unsigned char *const *images, int n_images, int width, in
                       + 2 * cells_n * sizeof(int) + B * sizeof(int) + sizeof(DescribeTables) + 7 * cells_n * sizeof(double);
     if (arena.bytes < need) {
         if (arena.base) { (void)hipFree(arena.base); arena.base = nullptr; arena.bytes = 0; }
-        CRN_TRY(hipMalloc(&arena.base, need));
+        HIP_TRY(hipMalloc(&arena.base, need));
         arena.bytes = need;
     }
     ArenaCursor cur = { static_cast<char *>(arena.base), arena.bytes };
@@ -718,17 +709,17 @@ int corner_front(const unsigned char *const *images, int n_images, int width, in
     if (!d.tab || !d.count || !d.sub) return tscm_set_error(TSCM_E_HIP, "internal error: arena too small");
     // a strided view (cv::Mat ROI, numpy column slice) only guarantees (height - 1) * stride + width bytes behind its pointer
     const size_t host_bytes = (size_t)(height - 1) * (size_t)stride + (size_t)width;
-    for (size_t q = 0; q < B; ++q) CRN_TRY(hipMemcpy(d.gray + q * gbytes, images[q], std::min(gbytes, host_bytes), hipMemcpyHostToDevice));
-    CRN_TRY(hipMemcpy(d.taps, taps.data(), sizeof(double) * ntap, hipMemcpyHostToDevice));
-    if (tab) CRN_TRY(hipMemcpy(d.tab, tab, sizeof(DescribeTables), hipMemcpyHostToDevice));
+    for (size_t q = 0; q < B; ++q) HIP_TRY(hipMemcpy(d.gray + q * gbytes, images[q], std::min(gbytes, host_bytes), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.taps, taps.data(), sizeof(double) * ntap, hipMemcpyHostToDevice));
+    if (tab) HIP_TRY(hipMemcpy(d.tab, tab, sizeof(DescribeTables), hipMemcpyHostToDevice));
     {
         std::vector<int> mm0(B * kMmSlots * kMmStride, 0);
         for (size_t q = 0; q < B * kMmSlots; ++q) { mm0[q * kMmStride] = 255; mm0[q * kMmStride + 1] = 0; }
-        CRN_TRY(hipMemcpy(d.mm, mm0.data(), sizeof(int) * mm0.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d.mm, mm0.data(), sizeof(int) * mm0.size(), hipMemcpyHostToDevice));
     }
-    CRN_TRY(hipMemset(d.count, 0, sizeof(int) * B));
+    HIP_TRY(hipMemset(d.count, 0, sizeof(int) * B));
 
-    if (e0) CRN_TRY(hipEventRecord(e0, nullptr));
+    if (e0) HIP_TRY(hipEventRecord(e0, nullptr));
     const dim3 grid2((width + 255) / 256, height, n_images);
     if (stride == width)
         hipLaunchKernelGGL(k_grey_extremes_flat, dim3((unsigned)((gbytes + 16383) / 16384), n_images), dim3(256), 0, nullptr, d.gray, gbytes, d.mm);
@@ -825,7 +816,7 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
     std::lock_guard<std::mutex> lock(arena.mu);
     const size_t B = (size_t)n_images;
     hipEvent_t e0, e1;
-    CRN_TRY(hipEventCreate(&e0)); CRN_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
     CornerBuffers d;
     if (int rc = corner_front(images, n_images, width, height, stride, sigma, arena, tab.data(), e0, d)) {
         (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -838,17 +829,17 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
     if (ncell > 0) {
         hipLaunchKernelGGL(k_nms_cells, dim3((ncell + 255) / 256, n_images), dim3(256), 0, nullptr, d.metric, width, height, d.ncx, d.ncy, d.cell, N);
         hipLaunchKernelGGL(k_nms_compact, dim3(n_images), dim3(1024), 0, nullptr, d.cell, ncell, ncell, d.cand, d.count);
-        CRN_TRY(hipMemcpy(counts.data(), d.count, sizeof(int) * B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(counts.data(), d.count, sizeof(int) * B, hipMemcpyDeviceToHost));
         for (int c : counts) n_top = std::max(n_top, c);
         if (n_top > 0)
             hipLaunchKernelGGL(k_corner_describe, dim3(n_top, n_images), dim3(256), 0, nullptr, d.gray, stride, d.mm, ac, d.Ixy, width, height,
                                d.cand, d.tab, d.v, d.score, d.sub, N, ncell, d.count);
     }
-    CRN_TRY(hipEventRecord(e1, nullptr));
-    CRN_TRY(hipEventSynchronize(e1));
-    CRN_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    HIP_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipGetLastError());
     float ms = 0;
-    CRN_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     // ---- score filter (findCorner.cpp:47-66) per image, order preserved ---------------------------------------------
     for (size_t b = 0; b < B; ++b) {
@@ -859,10 +850,10 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
         std::vector<int> cand(n_max);
         std::vector<double> v(4 * (size_t)n_max), score(n_max), sub(2 * (size_t)n_max);
         if (n_max > 0) {
-            CRN_TRY(hipMemcpy(cand.data(), d.cand + b * ncell, sizeof(int) * n_max, hipMemcpyDeviceToHost));
-            CRN_TRY(hipMemcpy(v.data(), d.v + b * 4 * ncell, sizeof(double) * 4 * n_max, hipMemcpyDeviceToHost));
-            CRN_TRY(hipMemcpy(score.data(), d.score + b * ncell, sizeof(double) * n_max, hipMemcpyDeviceToHost));
-            CRN_TRY(hipMemcpy(sub.data(), d.sub + b * 2 * ncell, sizeof(double) * 2 * n_max, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(cand.data(), d.cand + b * ncell, sizeof(int) * n_max, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(v.data(), d.v + b * 4 * ncell, sizeof(double) * 4 * n_max, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(score.data(), d.score + b * ncell, sizeof(double) * n_max, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(sub.data(), d.sub + b * 2 * ncell, sizeof(double) * 2 * n_max, hipMemcpyDeviceToHost));
         }
         int keep = 0;
         for (int q = 0; q < n_max; ++q) if (!(score[q] < min_score)) ++keep;
@@ -907,11 +898,11 @@ extern "C" int tscm_corner_planes_batch(const unsigned char *const *images, int 
     std::lock_guard<std::mutex> lock(arena.mu);
     CornerBuffers d;
     if (int rc = corner_front(images, n_images, width, height, stride, sigma, arena, nullptr, nullptr, d)) return rc;
-    CRN_TRY(hipDeviceSynchronize());
-    CRN_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
     const size_t bytes = sizeof(double) * d.N * (size_t)n_images;          // [n_images][height][width], as in the arena
-    if (ig) CRN_TRY(hipMemcpy(ig, d.Ig, bytes, hipMemcpyDeviceToHost));
-    if (metric) CRN_TRY(hipMemcpy(metric, d.metric, bytes, hipMemcpyDeviceToHost));
-    if (ixy) CRN_TRY(hipMemcpy(ixy, d.Ixy, bytes, hipMemcpyDeviceToHost));
+    if (ig) HIP_TRY(hipMemcpy(ig, d.Ig, bytes, hipMemcpyDeviceToHost));
+    if (metric) HIP_TRY(hipMemcpy(metric, d.metric, bytes, hipMemcpyDeviceToHost));
+    if (ixy) HIP_TRY(hipMemcpy(ixy, d.Ixy, bytes, hipMemcpyDeviceToHost));
     return 0;
 }

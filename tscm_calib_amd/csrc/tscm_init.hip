@@ -8,19 +8,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "tscm_host.h"
 #include "tscm_math.h"
 
 #include <cmath>
 #include <string>
 #include <vector>
-
-int tscm_set_error(int code, const std::string &msg);   // tscm_solver.hip
-
-#define INIT_TRY(expr)                                                                              \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return tscm_set_error(TSCM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -317,31 +310,22 @@ static int focal_rows(const double *pix_u, const double *pix_v, const int *count
 {
     if (board_w < 4 || board_h < 1) return tscm_set_error(TSCM_E_UNSUPPORTED, "estimate_focal needs boards at least 4 corners wide");
     if (board_w > kMaxBoardW) return tscm_set_error(TSCM_E_UNSUPPORTED, "boards wider than 32 corners");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_estimate_focal has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    INIT_TRY(hipSetDevice(device));
+    if (int rc = tscm::select_device(device, "tscm_estimate_focal")) return rc;
     const size_t rows = (size_t)n_views * board_h, npix = rows * board_w;
     g.assign(rows, 0.0);
     if (rows == 0) return 0;
-    double *d_u = nullptr, *d_v = nullptr, *d_g = nullptr;
-    int *d_c = nullptr;
-    auto body = [&]() -> int {
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_u), npix * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_v), npix * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_g), rows * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_c), (size_t)n_views * sizeof(int)));
-        INIT_TRY(hipMemcpy(d_u, pix_u, npix * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_v, pix_v, npix * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_c, count, (size_t)n_views * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_focal_rows, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, 0, d_u, d_v, d_c, n_views, board_w, board_h, cx, cy, d_g);
-        INIT_TRY(hipGetLastError());
-        INIT_TRY(hipMemcpy(g.data(), d_g, rows * sizeof(double), hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipFree(d_u); (void)hipFree(d_v); (void)hipFree(d_g); (void)hipFree(d_c);
-    return rc;
+    tscm::DeviceMem mem;
+    const double *d_u = nullptr, *d_v = nullptr;
+    const int *d_c = nullptr;
+    double *d_g = nullptr;
+    HIP_TRY(mem.upload(&d_u, pix_u, npix));
+    HIP_TRY(mem.upload(&d_v, pix_v, npix));
+    HIP_TRY(mem.upload(&d_c, count, (size_t)n_views));
+    HIP_TRY(mem.alloc(&d_g, rows));
+    hipLaunchKernelGGL(k_focal_rows, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, 0, d_u, d_v, d_c, n_views, board_w, board_h, cx, cy, d_g);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(g.data(), d_g, rows * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int tscm_estimate_focal(const double *pix_u, const double *pix_v, const int *count, int n_views, int board_w, int board_h,
@@ -380,38 +364,26 @@ static int extrinsic_views(const double *intr9, const double *pix_u, const doubl
                            const double *worlds, int n_points, int board_w, int device, double *rec, unsigned char *ok)
 {
     if (board_w < 1 || n_points / 2 - board_w / 2 - 1 < 0) return tscm_set_error(TSCM_E_INVALID, "board width does not fit the corner count");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_estimate_extrinsic has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    INIT_TRY(hipSetDevice(device));
+    if (int rc = tscm::select_device(device, "tscm_estimate_extrinsic")) return rc;
     if (n_views == 0) return 0;
     const size_t npix = (size_t)n_views * n_points, nrec = (size_t)n_views * (STAGES ? kStageRec : 9);
-    double *d_i = nullptr, *d_u = nullptr, *d_v = nullptr, *d_w = nullptr, *d_rt = nullptr;
-    int *d_c = nullptr;
+    tscm::DeviceMem mem;
+    const double *d_i = nullptr, *d_u = nullptr, *d_v = nullptr, *d_w = nullptr;
+    const int *d_c = nullptr;
+    double *d_rt = nullptr;
     unsigned char *d_ok = nullptr;
-    auto body = [&]() -> int {
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_i), 9 * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_u), npix * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_v), npix * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_w), 3 * (size_t)n_points * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_rt), nrec * sizeof(double)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_c), (size_t)n_views * sizeof(int)));
-        INIT_TRY(hipMalloc(reinterpret_cast<void **>(&d_ok), (size_t)n_views));
-        INIT_TRY(hipMemcpy(d_i, intr9, 9 * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_u, pix_u, npix * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_v, pix_v, npix * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_w, worlds, 3 * (size_t)n_points * sizeof(double), hipMemcpyHostToDevice));
-        INIT_TRY(hipMemcpy(d_rt, rec, nrec * sizeof(double), hipMemcpyHostToDevice));      // views without a pose keep the caller's values
-        INIT_TRY(hipMemcpy(d_c, count, (size_t)n_views * sizeof(int), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_estimate_extrinsic<STAGES>, dim3((unsigned)((n_views + 63) / 64)), dim3(64), 0, 0, d_i, d_u, d_v, d_c, n_views, d_w, n_points, board_w, d_rt, d_ok);
-        INIT_TRY(hipGetLastError());
-        INIT_TRY(hipMemcpy(rec, d_rt, nrec * sizeof(double), hipMemcpyDeviceToHost));
-        INIT_TRY(hipMemcpy(ok, d_ok, (size_t)n_views, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipFree(d_i); (void)hipFree(d_u); (void)hipFree(d_v); (void)hipFree(d_w); (void)hipFree(d_rt); (void)hipFree(d_c); (void)hipFree(d_ok);
-    return rc;
+    HIP_TRY(mem.upload(&d_i, intr9, 9));
+    HIP_TRY(mem.upload(&d_u, pix_u, npix));
+    HIP_TRY(mem.upload(&d_v, pix_v, npix));
+    HIP_TRY(mem.upload(&d_w, worlds, 3 * (size_t)n_points));
+    HIP_TRY(mem.upload(&d_rt, rec, nrec));      // views without a pose keep the caller's values
+    HIP_TRY(mem.upload(&d_c, count, (size_t)n_views));
+    HIP_TRY(mem.alloc(&d_ok, (size_t)n_views));
+    hipLaunchKernelGGL(k_estimate_extrinsic<STAGES>, dim3((unsigned)((n_views + 63) / 64)), dim3(64), 0, 0, d_i, d_u, d_v, d_c, n_views, d_w, n_points, board_w, d_rt, d_ok);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(rec, d_rt, nrec * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ok, d_ok, (size_t)n_views, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int tscm_estimate_extrinsic(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,

@@ -8,20 +8,13 @@
 #include <hip/hip_runtime.h>
 
 #include "tscm_fastmath.h"
+#include "tscm_host.h"
 #include "tscm_math.h"
 
 #include <string>
 #include <vector>
 
 using namespace tscm;
-
-int tscm_set_error(int code, const std::string &msg);   // tscm_solver.hip
-
-#define MAP_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return tscm_set_error(TSCM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -275,13 +268,6 @@ __global__ __launch_bounds__(256) void k_rectify_points(const tscm_map_desc *__r
     valid[t] = ok ? 1 : 0;
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 // kinds == NULL: every map is a pinhole, k_build_maps; otherwise [n_maps] valid kinds, k_build_maps_proj
@@ -301,46 +287,41 @@ static int build_maps_host(const tscm_map_desc *maps, const int *kinds, int n_ma
         max_quads = std::max(max_quads, d.out_stride == d.width ? ((long long)d.width * d.height + 3) / 4 : (long long)((d.width + 3) / 4) * d.height);
         covered += (unsigned long long)d.width * d.height;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_build_maps has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    MAP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "tscm_build_maps")) return rc;
     if (seconds_kernel) *seconds_kernel = 0.0;
     if (n_maps == 0 || max_quads == 0) return 0;
-    DevBuf<tscm_map_desc> d_maps;
-    DevBuf<float> d_x, d_y;
-    MAP_TRY(d_maps.alloc(n_maps)); MAP_TRY(d_x.alloc(n_elems)); MAP_TRY(d_y.alloc(n_elems));
-    MAP_TRY(hipMemcpy(d_maps.p, maps, sizeof(tscm_map_desc) * n_maps, hipMemcpyHostToDevice));
-    DevBuf<int> d_kinds;
-    if (kinds) {
-        MAP_TRY(d_kinds.alloc(n_maps));
-        MAP_TRY(hipMemcpy(d_kinds.p, kinds, sizeof(int) * n_maps, hipMemcpyHostToDevice));
-    }
+    DeviceMem mem;
+    const tscm_map_desc *d_maps = nullptr;
+    const int *d_kinds = nullptr;
+    float *d_x = nullptr, *d_y = nullptr;
+    HIP_TRY(mem.upload(&d_maps, maps, (size_t)n_maps));
+    if (kinds) HIP_TRY(mem.upload(&d_kinds, kinds, (size_t)n_maps));
     // elements no map covers (row padding, gaps) keep the caller's values
     if (covered < n_elems) {
-        MAP_TRY(hipMemcpy(d_x.p, mapx, sizeof(float) * n_elems, hipMemcpyHostToDevice));
-        MAP_TRY(hipMemcpy(d_y.p, mapy, sizeof(float) * n_elems, hipMemcpyHostToDevice));
+        HIP_TRY(mem.upload(&d_x, mapx, n_elems)); HIP_TRY(mem.upload(&d_y, mapy, n_elems));
+    } else {
+        HIP_TRY(mem.alloc(&d_x, n_elems)); HIP_TRY(mem.alloc(&d_y, n_elems));
     }
     hipEvent_t e0, e1;
-    MAP_TRY(hipEventCreate(&e0)); MAP_TRY(hipEventCreate(&e1));
-    MAP_TRY(hipEventRecord(e0, 0));
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, 0));
     const dim3 grid((unsigned)((max_quads + 255) / 256), (unsigned)n_maps);
     if (!kinds) {
-        if (exact) hipLaunchKernelGGL(k_build_maps<true>, grid, dim3(256), 0, 0, d_maps.p, d_x.p, d_y.p);
-        else hipLaunchKernelGGL(k_build_maps<false>, grid, dim3(256), 0, 0, d_maps.p, d_x.p, d_y.p);
+        if (exact) hipLaunchKernelGGL(k_build_maps<true>, grid, dim3(256), 0, 0, d_maps, d_x, d_y);
+        else hipLaunchKernelGGL(k_build_maps<false>, grid, dim3(256), 0, 0, d_maps, d_x, d_y);
     } else {
-        if (exact) hipLaunchKernelGGL(k_build_maps_proj<true>, grid, dim3(256), 0, 0, d_maps.p, d_kinds.p, d_x.p, d_y.p);
-        else hipLaunchKernelGGL(k_build_maps_proj<false>, grid, dim3(256), 0, 0, d_maps.p, d_kinds.p, d_x.p, d_y.p);
+        if (exact) hipLaunchKernelGGL(k_build_maps_proj<true>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_x, d_y);
+        else hipLaunchKernelGGL(k_build_maps_proj<false>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_x, d_y);
     }
-    MAP_TRY(hipEventRecord(e1, 0));
-    MAP_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipEventRecord(e1, 0));
+    HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
-    MAP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    MAP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
-    MAP_TRY(hipMemcpy(mapx, d_x.p, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
-    MAP_TRY(hipMemcpy(mapy, d_y.p, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mapx, d_x, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mapy, d_y, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -369,20 +350,18 @@ extern "C" int tscm_rectify_points(const tscm_map_desc *map, int projection, con
     if (!map || n < 0 || (n > 0 && (!pixels || !out || !valid))) return tscm_set_error(TSCM_E_INVALID, n < 0 ? "negative point count" : "NULL argument");
     if (!known_projection(projection)) return tscm_set_error(TSCM_E_INVALID, "map 0: unknown projection kind " + std::to_string(projection));
     if (n == 0) return 0;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (tscm_rectify_points has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    MAP_TRY(hipSetDevice(device));
-    DevBuf<tscm_map_desc> d_map;
-    DevBuf<double> d_p, d_o;
-    DevBuf<unsigned char> d_v;
-    MAP_TRY(d_map.alloc(1)); MAP_TRY(d_p.alloc(2 * (size_t)n)); MAP_TRY(d_o.alloc(2 * (size_t)n)); MAP_TRY(d_v.alloc((size_t)n));
-    MAP_TRY(hipMemcpy(d_map.p, map, sizeof(tscm_map_desc), hipMemcpyHostToDevice));
-    MAP_TRY(hipMemcpy(d_p.p, pixels, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_rectify_points, dim3((n + 255) / 256), dim3(256), 0, 0, d_map.p, projection, d_p.p, n, d_o.p, d_v.p);
-    MAP_TRY(hipGetLastError());
-    MAP_TRY(hipMemcpy(out, d_o.p, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    MAP_TRY(hipMemcpy(valid, d_v.p, (size_t)n, hipMemcpyDeviceToHost));
+    if (int rc = select_device(device, "tscm_rectify_points")) return rc;
+    DeviceMem mem;
+    const tscm_map_desc *d_map = nullptr;
+    const double *d_p = nullptr;
+    double *d_o = nullptr;
+    unsigned char *d_v = nullptr;
+    HIP_TRY(mem.upload(&d_map, map, 1)); HIP_TRY(mem.upload(&d_p, pixels, 2 * (size_t)n));
+    HIP_TRY(mem.alloc(&d_o, 2 * (size_t)n)); HIP_TRY(mem.alloc(&d_v, (size_t)n));
+    hipLaunchKernelGGL(k_rectify_points, dim3((n + 255) / 256), dim3(256), 0, 0, d_map, projection, d_p, n, d_o, d_v);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(valid, d_v, (size_t)n, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -422,11 +401,6 @@ __global__ __launch_bounds__(256) void k_remap(const unsigned char *src, int w, 
     }
 }
 
-struct DevBytes {
-    void *p = nullptr;
-    ~DevBytes() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 extern "C" int tscm_remap(const unsigned char *src, int width, int height, int stride, int channels, const float *mapx, const float *mapy, int map_width,
@@ -439,26 +413,23 @@ extern "C" int tscm_remap(const unsigned char *src, int width, int height, int s
         return tscm_set_error(TSCM_E_INVALID, "bad image / map description");
     if (width > 32767 || height > 32767) return tscm_set_error(TSCM_E_UNSUPPORTED, "images beyond 32767 pixels per side");
     if (map_width == 0 || map_height == 0) return 0;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, "no HIP device available (remap has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    MAP_TRY(hipSetDevice(device));
-    DevBytes d_src, d_mx, d_my, d_dst;
+    if (int rc = select_device(device, "tscm_remap")) return rc;
+    DeviceMem mem;
+    const unsigned char *d_src = nullptr;
+    unsigned char *d_dst = nullptr;
+    float *d_mx = nullptr, *d_my = nullptr;
     const size_t nmap = (size_t)map_width * map_height, dst_row = (size_t)map_width * out_ch;
-    MAP_TRY(hipMalloc(&d_src.p, (size_t)stride * height));
-    MAP_TRY(hipMalloc(&d_mx.p, nmap * sizeof(float))); MAP_TRY(hipMalloc(&d_my.p, nmap * sizeof(float)));
-    MAP_TRY(hipMalloc(&d_dst.p, dst_row * map_height));
-    MAP_TRY(hipMemcpy(d_src.p, src, (size_t)stride * height, hipMemcpyHostToDevice));
-    MAP_TRY(hipMemcpy2D(d_mx.p, (size_t)map_width * sizeof(float), mapx, (size_t)map_stride * sizeof(float), (size_t)map_width * sizeof(float), map_height, hipMemcpyHostToDevice));
-    MAP_TRY(hipMemcpy2D(d_my.p, (size_t)map_width * sizeof(float), mapy, (size_t)map_stride * sizeof(float), (size_t)map_width * sizeof(float), map_height, hipMemcpyHostToDevice));
+    HIP_TRY(mem.upload(&d_src, src, (size_t)stride * height));
+    HIP_TRY(mem.alloc(&d_mx, nmap)); HIP_TRY(mem.alloc(&d_my, nmap));
+    HIP_TRY(mem.alloc(&d_dst, dst_row * map_height));
+    HIP_TRY(hipMemcpy2D(d_mx, (size_t)map_width * sizeof(float), mapx, (size_t)map_stride * sizeof(float), (size_t)map_width * sizeof(float), map_height, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy2D(d_my, (size_t)map_width * sizeof(float), mapy, (size_t)map_stride * sizeof(float), (size_t)map_width * sizeof(float), map_height, hipMemcpyHostToDevice));
     const dim3 grid((map_width + 255) / 256, map_height);
     if (channels == 1)
-        hipLaunchKernelGGL(k_remap<1>, grid, dim3(256), 0, nullptr, static_cast<const unsigned char *>(d_src.p), width, height, stride, static_cast<const float *>(d_mx.p),
-                           static_cast<const float *>(d_my.p), map_width, map_height, 0, static_cast<unsigned char *>(d_dst.p), (int)dst_row);
+        hipLaunchKernelGGL(k_remap<1>, grid, dim3(256), 0, nullptr, d_src, width, height, stride, d_mx, d_my, map_width, map_height, 0, d_dst, (int)dst_row);
     else
-        hipLaunchKernelGGL(k_remap<3>, grid, dim3(256), 0, nullptr, static_cast<const unsigned char *>(d_src.p), width, height, stride, static_cast<const float *>(d_mx.p),
-                           static_cast<const float *>(d_my.p), map_width, map_height, to_gray ? 1 : 0, static_cast<unsigned char *>(d_dst.p), (int)dst_row);
-    MAP_TRY(hipGetLastError());
-    MAP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, d_dst.p, dst_row, dst_row, map_height, hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(k_remap<3>, grid, dim3(256), 0, nullptr, d_src, width, height, stride, d_mx, d_my, map_width, map_height, to_gray ? 1 : 0, d_dst, (int)dst_row);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, d_dst, dst_row, dst_row, map_height, hipMemcpyDeviceToHost));
     return 0;
 }

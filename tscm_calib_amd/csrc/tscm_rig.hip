@@ -4,6 +4,7 @@
 // of the common boards, whose prepared points and pixels reach the wave through scalar loads; the
 // slices are summed per hypothesis by a second kernel, and the 3x3 bookkeeping stays on the host.
 #include "tscm/tscm.h"
+#include "tscm_host.h"
 #include "tscm_math.h"
 #include "tscm_fastmath.h"
 
@@ -16,14 +17,6 @@
 #include <vector>
 
 using namespace tscm;
-
-int tscm_set_error(int code, const std::string &msg);   // tscm_solver.hip
-
-#define RIG_TRY(expr)                                                                               \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return tscm_set_error(TSCM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -299,15 +292,6 @@ __global__ void k_rig_boards(int C, int B, int n, const unsigned char *has, cons
     for (int i = 0; i < 3; ++i) board_t[3 * (size_t)b + i] = ts[best].a[i];
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)); }
-    hipError_t upload(const T *h, size_t n) { hipError_t e = alloc(n); if (e != hipSuccess || n == 0) return e; return hipMemcpy(p, h, n * sizeof(T), hipMemcpyHostToDevice); }
-    hipError_t upload(const std::vector<T> &h) { hipError_t e = alloc(h.size()); if (e != hipSuccess || h.empty()) return e; return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice); }
-};
-
 double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Rt_to_R_t of every (camera, board) with a detection: [C*B][R (9) | t (3)], zero where there is none
@@ -337,19 +321,20 @@ std::vector<int> common_boards(const tscm_rig_input *in, int i)
 
 // everything the stages and the board choice read goes to the device once
 struct RigDevice {
-    DevBuf<double> worlds, intr, pose, pu, pv;
-    DevBuf<unsigned char> has;
+    DeviceMem mem;
+    const double *worlds = nullptr, *intr = nullptr, *pose = nullptr, *pu = nullptr, *pv = nullptr;
+    const unsigned char *has = nullptr;
 };
 
 int rig_upload(const tscm_rig_input *in, const std::vector<double> &pose, RigDevice &d)
 {
     const int C = in->n_cameras, B = in->n_boards, n = in->n_points;
-    RIG_TRY(d.worlds.upload(in->worlds, 3 * (size_t)n));
-    RIG_TRY(d.intr.upload(in->intr, 9 * (size_t)C));
-    RIG_TRY(d.pose.upload(pose));
-    RIG_TRY(d.pu.upload(in->pix_u, (size_t)C * B * n));
-    RIG_TRY(d.pv.upload(in->pix_v, (size_t)C * B * n));
-    RIG_TRY(d.has.upload(in->has, (size_t)C * B));
+    HIP_TRY(d.mem.upload(&d.worlds, in->worlds, 3 * (size_t)n));
+    HIP_TRY(d.mem.upload(&d.intr, in->intr, 9 * (size_t)C));
+    HIP_TRY(d.mem.upload(&d.pose, pose));
+    HIP_TRY(d.mem.upload(&d.pu, in->pix_u, (size_t)C * B * n));
+    HIP_TRY(d.mem.upload(&d.pv, in->pix_v, (size_t)C * B * n));
+    HIP_TRY(d.mem.upload(&d.has, in->has, (size_t)C * B));
     return 0;
 }
 
@@ -380,40 +365,42 @@ int rig_stage(const tscm_rig_input *in, const RigDevice &dev, const std::vector<
         const V3 th = add(mul(Rik, tp), tik);
         std::memcpy(&st.Rs[9 * (size_t)h], Rh.a, sizeof(Rh.a)); std::memcpy(&st.ts[3 * (size_t)h], th.a, sizeof(th.a));
     }
-    DevBuf<double> dRs, dts, dpart, derr;
-    DevBuf<HypPoint> dpts;
-    DevBuf<int> dcommon;
-    RIG_TRY(dRs.upload(st.Rs)); RIG_TRY(dts.upload(st.ts)); RIG_TRY(dcommon.upload(common));
-    RIG_TRY(dpts.alloc((size_t)K * 2 * n));
-    hipLaunchKernelGGL(k_rig_points, dim3((unsigned)(((size_t)K * n + 255) / 256)), dim3(256), 0, 0, K, n, B, i, dcommon.p, dev.pose.p, dev.pu.p,
-                       dev.pv.p, dev.worlds.p, dpts.p);
+    DeviceMem mem;                         // this stage's buffers
+    const double *dRs = nullptr, *dts = nullptr;
+    double *dpart = nullptr, *derr = nullptr;
+    HypPoint *dpts = nullptr;
+    const int *dcommon = nullptr;
+    HIP_TRY(mem.upload(&dRs, st.Rs)); HIP_TRY(mem.upload(&dts, st.ts)); HIP_TRY(mem.upload(&dcommon, common));
+    HIP_TRY(mem.alloc(&dpts, (size_t)K * 2 * n));
+    hipLaunchKernelGGL(k_rig_points, dim3((unsigned)(((size_t)K * n + 255) / 256)), dim3(256), 0, 0, K, n, B, i, dcommon, dev.pose, dev.pu,
+                       dev.pv, dev.worlds, dpts);
     const bool skew = in->intr[9 * i + 7] != 0.0 || in->intr[9 * i + 8] != 0.0 || in->intr[9 * (i - 1) + 7] != 0.0 || in->intr[9 * (i - 1) + 8] != 0.0;
     auto kern = skew ? k_rig_hyp_errors<true> : k_rig_hyp_errors<false>;
     // one round of resident waves: slices of the boards so that (hypothesis groups x slices) fills the chip once
     int per_cu = 0;
-    RIG_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, 0));
     const int jgroups = (K + 63) / 64;
     const int resident = std::max(1, per_cu) * prop.multiProcessorCount;
     StageArgs s{};
     s.J = K; s.K = K; s.n = n;
     s.ksplit = ksplit_req > 0 ? ksplit_req : std::max(1, std::min(K, resident / jgroups));
-    s.Rs = dRs.p; s.ts = dts.p; s.pts = dpts.p;
+    s.Rs = dRs; s.ts = dts; s.pts = dpts;
     std::memcpy(s.intrI, in->intr + 9 * i, sizeof(s.intrI)); std::memcpy(s.intrP, in->intr + 9 * (i - 1), sizeof(s.intrP));
     s.Rp = Rp; s.tp = tp;
-    RIG_TRY(dpart.alloc((size_t)K * s.ksplit)); RIG_TRY(derr.alloc((size_t)K));
-    s.partial = dpart.p;
+    HIP_TRY(mem.alloc(&dpart, (size_t)K * s.ksplit)); HIP_TRY(mem.alloc(&derr, (size_t)K));
+    s.partial = dpart;
     hipEvent_t e0, e1;
-    RIG_TRY(hipEventCreate(&e0)); RIG_TRY(hipEventCreate(&e1));
-    RIG_TRY(hipEventRecord(e0, 0));
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, 0));
     hipLaunchKernelGGL(kern, dim3(jgroups, s.ksplit), dim3(64), 0, 0, s);
-    hipLaunchKernelGGL(k_rig_hyp_reduce, dim3((K + 255) / 256), dim3(256), 0, 0, dpart.p, K, s.ksplit, derr.p);
-    RIG_TRY(hipEventRecord(e1, 0));
-    RIG_TRY(hipEventSynchronize(e1));
+    hipLaunchKernelGGL(k_rig_hyp_reduce, dim3((K + 255) / 256), dim3(256), 0, 0, dpart, K, s.ksplit, derr);
+    HIP_TRY(hipEventRecord(e1, 0));
+    HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
-    RIG_TRY(hipEventElapsedTime(&ms, e0, e1));
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    RIG_TRY(hipGetLastError());
-    RIG_TRY(hipMemcpy(st.err.data(), derr.p, sizeof(double) * K, hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(st.err.data(), derr, sizeof(double) * K, hipMemcpyDeviceToHost));
     st.jgroups = jgroups; st.ksplit = s.ksplit; st.skew = skew ? 1 : 0;
     st.seconds = 1e-3 * ms;
     return 0;
@@ -421,11 +408,8 @@ int rig_stage(const tscm_rig_input *in, const RigDevice &dev, const std::vector<
 
 int rig_open_device(int device, hipDeviceProp_t &prop, const char *who)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return tscm_set_error(TSCM_E_NO_DEVICE, std::string("no HIP device available (") + who + " has no CPU fallback)");
-    if (device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "device index out of range");
-    RIG_TRY(hipSetDevice(device));
-    RIG_TRY(hipGetDeviceProperties(&prop, device));
+    if (int rc = select_device(device, who)) return rc;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     return 0;
 }
 
@@ -494,17 +478,18 @@ extern "C" int tscm_rig_init(const tscm_rig_input *in, int device, tscm_rig_resu
     if (B > 0) {
         std::vector<double> cR(9 * (size_t)C), ct(3 * (size_t)C);
         for (int i = 0; i < C; ++i) { std::memcpy(&cR[9 * (size_t)i], camR[i].a, sizeof(camR[i].a)); std::memcpy(&ct[3 * (size_t)i], camt[i].a, sizeof(camt[i].a)); }
-        DevBuf<unsigned char> dinit;
-        DevBuf<double> dcR, dct, dbR, dbt;
-        RIG_TRY(dcR.upload(cR)); RIG_TRY(dct.upload(ct));
-        RIG_TRY(dbR.alloc(9 * (size_t)B)); RIG_TRY(dbt.alloc(3 * (size_t)B)); RIG_TRY(dinit.alloc((size_t)B));
-        hipLaunchKernelGGL(k_rig_boards, dim3((B + 127) / 128), dim3(128), 0, 0, C, B, n, dev.has.p, dev.pose.p, dev.pu.p, dev.pv.p, dev.worlds.p, dev.intr.p,
-                           dcR.p, dct.p, dbR.p, dbt.p, dinit.p);
-        RIG_TRY(hipDeviceSynchronize());
-        RIG_TRY(hipGetLastError());
-        RIG_TRY(hipMemcpy(out->board_R, dbR.p, sizeof(double) * 9 * (size_t)B, hipMemcpyDeviceToHost));
-        RIG_TRY(hipMemcpy(out->board_t, dbt.p, sizeof(double) * 3 * (size_t)B, hipMemcpyDeviceToHost));
-        RIG_TRY(hipMemcpy(out->board_initial, dinit.p, (size_t)B, hipMemcpyDeviceToHost));
+        unsigned char *dinit = nullptr;
+        const double *dcR = nullptr, *dct = nullptr;
+        double *dbR = nullptr, *dbt = nullptr;
+        HIP_TRY(dev.mem.upload(&dcR, cR)); HIP_TRY(dev.mem.upload(&dct, ct));
+        HIP_TRY(dev.mem.alloc(&dbR, 9 * (size_t)B)); HIP_TRY(dev.mem.alloc(&dbt, 3 * (size_t)B)); HIP_TRY(dev.mem.alloc(&dinit, (size_t)B));
+        hipLaunchKernelGGL(k_rig_boards, dim3((B + 127) / 128), dim3(128), 0, 0, C, B, n, dev.has, dev.pose, dev.pu, dev.pv, dev.worlds, dev.intr,
+                           dcR, dct, dbR, dbt, dinit);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out->board_R, dbR, sizeof(double) * 9 * (size_t)B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out->board_t, dbt, sizeof(double) * 3 * (size_t)B, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out->board_initial, dinit, (size_t)B, hipMemcpyDeviceToHost));
         for (int b = 0; b < B; ++b) {
             std::memset(out->board_rt + 6 * (size_t)b, 0, 6 * sizeof(double));
             if (!out->board_initial[b]) continue;

@@ -7,6 +7,7 @@
 // the trust-region radius and the termination tests all run on the GPU (k_control), so one LM
 // iteration costs no host<->device round trip.
 #include "tscm/tscm.h"
+#include "tscm_host.h"
 #include "tscm_kernels.h"
 #include "tscm_launch_seq.h"
 #include "tscm_mono_batch.h"
@@ -32,14 +33,7 @@ using namespace tscm;
 // ------------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-int tscm_set_error(int code, const std::string &msg) { return fail(code, msg); }   // for tscm_rig.hip
-
-#define HIP_TRY(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return fail(TSCM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
+int tscm_set_error(int code, const std::string &msg) { return fail(code, msg); }   // tscm_host.h: HIP_TRY, select_device
 
 #define NCCL_TRY(expr)                                                                                 \
     do {                                                                                               \
@@ -58,6 +52,8 @@ struct tscm_local_group {
     int world = 0, device = 0, refs = 0;
     hipStream_t stream = nullptr;
     double **d_ptrs = nullptr;           // [world] device array of the members' exchange buffers (rewritten per exchange)
+    DeviceMem mem;                       // owns d_ptrs
+    ~tscm_local_group() { if (stream) (void)hipStreamDestroy(stream); }
 };
 // IPC: one process per rank like RCCL, but the exchange is this library's own one-shot all-reduce over memory the ranks
 // map from each other (hipIpcMemHandle: the same device, or peers over xGMI).  Every rank owns a buffer of
@@ -77,8 +73,8 @@ struct IpcPeers { double *base[kIpcMaxWorld]; };
 struct tscm_ipc {
     int world = 0, rank = 0;
     size_t max_doubles = 0;             // per slot
-    void *own = nullptr;                // this rank's buffer (hipMalloc)
-    void *mapped[kIpcMaxWorld] = {};    // the peers' buffers as mapped here (own at [rank])
+    DeviceMem mem;                      // owns this rank's buffer and d_fault
+    void *mapped[kIpcMaxWorld] = {};    // the ranks' buffers as mapped here (this rank's own at [rank])
     bool connected = false;
     long long count = 0;                // exchanges so far: parity and flag value of the next one
     int *d_fault = nullptr;             // raised by a kernel whose peers did not arrive within the bound
@@ -135,7 +131,7 @@ struct tscm_solver {
     hipStream_t stream = nullptr;
     DevProblem P{};
     DevState S{};
-    std::vector<void *> allocs;
+    DeviceMem mem;                      // every device buffer of the solver
     tscm_comm *comm = nullptr;
     Layout L;                           // host copy of the layout (tscm_layout.h: plan_layout)
     int C = 0, B = 0, V = 0, N = 0, n_points = 0, n_pad = 0;     // B, V, N: this rank's boards / views / corners (L.B, L.V, L.N)
@@ -183,23 +179,15 @@ struct tscm_solver {
     double t_ms[3] = { 0.0, 0.0, 0.0 };
 };
 
-template <typename T>
-static int dev_alloc(tscm_solver *s, T **p, size_t n)
-{
-    void *q = nullptr;
-    HIP_TRY(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    s->allocs.push_back(q);
-    *p = static_cast<T *>(q);
-    return 0;
-}
+struct SolverDelete { void operator()(tscm_solver *s) const { tscm_solver_destroy(s); } };
+using SolverPtr = std::unique_ptr<tscm_solver, SolverDelete>;
 
-template <typename T>
-static int dev_upload(tscm_solver *s, const T **p, const std::vector<T> &h)
+// a solver of `p` on `device` that lives as long as `sp`: the create / use / destroy entry points
+static int create_scoped(const tscm_problem *p, int device, SolverPtr &sp)
 {
-    T *q = nullptr;
-    if (int rc = dev_alloc(s, &q, h.size())) return rc;
-    if (!h.empty()) HIP_TRY(hipMemcpy(q, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    *p = q;
+    tscm_solver *s = nullptr;
+    if (int rc = tscm_solver_create(p, device, &s)) return rc;
+    sp.reset(s);
     return 0;
 }
 
@@ -216,9 +204,7 @@ extern "C" int tscm_device_count(void)
 
 extern "C" int tscm_device_synchronize(int device)
 {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return fail(TSCM_E_NO_DEVICE, "no usable HIP device");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "tscm_device_synchronize")) return rc;
     HIP_TRY(hipDeviceSynchronize());
     return 0;
 }
@@ -278,20 +264,9 @@ extern "C" void tscm_solver_destroy(tscm_solver *s)
     s->stream = s->own_stream;
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     for (auto &e : s->ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-    for (void *q : s->allocs) (void)hipFree(q);
     if (s->h_ctrl) (void)hipHostFree(s->h_ctrl);
     if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
-
-// frees a buffer of dev_alloc / dev_upload before the solver is destroyed (tables that apply_columns replaces)
-template <typename T>
-static void dev_release(tscm_solver *s, const T *p)
-{
-    if (!p) return;
-    void *q = const_cast<void *>(static_cast<const void *>(p));
-    auto it = std::find(s->allocs.begin(), s->allocs.end(), q);
-    if (it != s->allocs.end()) { s->allocs.erase(it); (void)hipFree(q); }
+    delete s;                           // (s->mem frees the device buffers)
 }
 
 // Uploads a column plan (tscm_columns.h: plan_columns): col_active, the control step's classes col_ctl, act_map /
@@ -313,17 +288,11 @@ static int apply_columns(tscm_solver *s, const ColumnPlan &c)
     if (c.has_nd) {
         for (int v = 0; v < 2; ++v) {
             const NdPlan &pl = c.nd[v];
-            dev_release(s, s->d_nd_map[v]); dev_release(s, s->d_nd_tab[v]); dev_release(s, s->d_nd_bs[v]);
+            s->mem.release(s->d_nd_map[v]); s->mem.release(s->d_nd_tab[v]); s->mem.release(s->d_nd_bs[v]);
             s->d_nd_map[v] = nullptr; s->d_nd_tab[v] = nullptr; s->d_nd_bs[v] = nullptr;
-            const int4 *map = nullptr;
-            {
-                std::vector<int4> m4(pl.map.size() / 4);
-                std::memcpy(m4.data(), pl.map.data(), pl.map.size() * sizeof(int));
-                if (int rc = dev_upload(s, &map, m4)) return rc;
-            }
-            s->d_nd_map[v] = map;
-            if (int rc = dev_upload(s, &s->d_nd_tab[v], pl.tab)) return rc;
-            if (int rc = dev_upload(s, &s->d_nd_bs[v], pl.bs_tab)) return rc;
+            HIP_TRY(s->mem.upload(&s->d_nd_map[v], reinterpret_cast<const int4 *>(pl.map.data()), pl.map.size() / 4));
+            HIP_TRY(s->mem.upload(&s->d_nd_tab[v], pl.tab));
+            HIP_TRY(s->mem.upload(&s->d_nd_bs[v], pl.bs_tab));
             s->lds_nd[v] = sizeof(double) * pl.lds_doubles;
             s->plan[v] = pl;
         }
@@ -385,12 +354,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     *out = nullptr;
     if (int rc = validate(p)) return rc;
     if (world < 1 || rank < 0 || rank >= world) return fail(TSCM_E_INVALID, "rank / world out of range");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(TSCM_E_NO_DEVICE, "no HIP device available (the TSCM solver has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(TSCM_E_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "the TSCM solver")) return rc;
 
-    std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> sp(new tscm_solver, tscm_solver_destroy);
+    SolverPtr sp(new tscm_solver);
     tscm_solver *s = sp.get();
     s->device = device;
     s->rank = rank; s->world = world;
@@ -479,9 +445,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     std::copy(std::begin(L.cam_wg), std::end(L.cam_wg), P.cam_wg);
     std::copy(std::begin(L.bid_part_small), std::end(L.bid_part_small), P.bid_part_small);
     P.pair_mask = L.pair_mask;
-    int rc = 0;         // the first failure of a run of uploads / allocations (the rest are skipped)
-    auto up = [&](auto **dst, const auto &h) { if (!rc) rc = dev_upload(s, dst, h); };
-    auto al = [&](auto **dst, size_t n) { if (!rc) rc = dev_alloc(s, dst, n); };
+    hipError_t he = hipSuccess;     // the first failure of a run of uploads / allocations (the rest are skipped)
+    auto up = [&](auto **dst, const auto &h) { if (he == hipSuccess) he = s->mem.upload(dst, h); };
+    auto al = [&](auto **dst, size_t n) { if (he == hipSuccess) he = s->mem.alloc(dst, n); };
     up(&P.board_xy, bxy);
     up(&P.view_cam, L.view_cam); up(&P.view_board, L.view_board); up(&P.view_obs, L.view_obs); up(&P.view_count, L.view_count);
     up(&P.obs_u, u); up(&P.obs_v, w);
@@ -516,7 +482,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     S.n_bs_blocks = L.n_bs_blocks;
     al(&S.ctrl, 1); al(&S.ctrl_snap, 1); al(&S.ctl_pub, 1);
     al(&S.stats_count, 64); al(&S.stats_flag, 64);      // (256 bytes each: lines of their own)
-    if (rc) return rc;
+    HIP_TRY(he);
     for (int *flag : { S.t_count, S.y_flag, S.fac_fail }) HIP_TRY(hipMemset(flag, 0, sizeof(int)));
     HIP_TRY(hipMemset(S.stats_count, 0, 256)); HIP_TRY(hipMemset(S.stats_flag, 0, 256));
     HIP_TRY(hipMemset(S.ctl_pub, 0, sizeof(CtlPub)));
@@ -541,12 +507,12 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     ColumnPlan cols;
     {
         std::string err;
-        if ((rc = plan_columns(L, C, nullptr, cols, err))) return fail(rc, err);
+        if (int rc = plan_columns(L, C, nullptr, cols, err)) return fail(rc, err);
     }
     if (C <= kDense4Cams) {
         // where every thread of k_solve_reduced finds its operands (written by apply_columns)
         int4 *map = nullptr;
-        if ((rc = dev_alloc(s, &map, (size_t)(kSolveMapSlots / 4) * kSolveMapThreads))) return rc;
+        HIP_TRY(s->mem.alloc(&map, (size_t)(kSolveMapSlots / 4) * kSolveMapThreads));
         P.solve_map = map;
         const size_t NN = 64, TT = 4, NPD = 64;
         s->lds_dense4 = sizeof(double) * (NN * (NN + 2) + 2 * (NN / TT) * (TT * TT + 2) + 2 * NN + 3 * NPD);
@@ -558,10 +524,10 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         // rigs of 9..32 cameras: the compact system (+ rhs row) lives in global memory
         const int NN = (cols.n_act + 15) & ~15;
         const size_t lds_max = solve_big_lds_bytes(NN, s->n_pad);
-        if ((rc = dev_alloc(s, &S.Abig, (size_t)256 * (NN / 16 + 1) * (NN / 16 + 2) / 2))) return rc;      // packed lower triangle of 16x16 blocks, incl. the rhs block row
+        HIP_TRY(s->mem.alloc(&S.Abig, (size_t)256 * (NN / 16 + 1) * (NN / 16 + 2) / 2));      // packed lower triangle of 16x16 blocks, incl. the rhs block row
         if (lds_max > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_solve_reduced_big), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
     }
-    if ((rc = apply_columns(s, cols))) return rc;
+    if (int rc = apply_columns(s, cols)) return rc;
     if (s->lds_eval > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board has too many corners for the LDS board-point tile");
     HIP_TRY(hipDeviceSynchronize());
     *out = sp.release();
@@ -1043,20 +1009,13 @@ static int run_lm(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, in
     return rc;
 }
 
-// device buffer freed on every exit path of the small entry points (and of robust_rmse)
-struct DevBuf {
-    double *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void **>(&p), std::max<size_t>(n, 1) * sizeof(double)); }
-};
-
 // sum of the squared pixel errors of this solver's corners at the accepted point (buffer 0): k_reproj_error, summed over the
 // views in device order -- what tscm_reprojection_error does on an unsharded solver of the same problem
 static int accepted_sq(tscm_solver *s, double &sq)
 {
     sq = 0.0;
     if (!s->V) return 0;
-    if (!s->d_view_sq) if (int rc = dev_alloc(s, &s->d_view_sq, 2 * (size_t)s->V)) return rc;
+    if (!s->d_view_sq) HIP_TRY(s->mem.alloc(&s->d_view_sq, 2 * (size_t)s->V));
     hipLaunchKernelGGL(k_reproj_error, dim3(s->V), dim3(64), 0, s->stream, s->P, s->S.cam_rt[0], s->S.intr[0], s->S.board_rt[0], s->d_view_sq, s->d_view_sq + s->V);
     std::vector<double> q(s->V);
     HIP_TRY(hipMemcpyAsync(q.data(), s->d_view_sq + s->V, sizeof(double) * s->V, hipMemcpyDeviceToHost, s->stream));
@@ -1077,11 +1036,12 @@ static int robust_rmse(LmRun &run, tscm_summary *sums)
     }
     tscm_solver *s0 = run.m[0];
     if (run.m.size() == 1 && s0->comm && s0->world > 1) {
-        DevBuf d;
-        HIP_TRY(d.alloc(1));
-        HIP_TRY(hipMemcpyAsync(d.p, &sq, sizeof(double), hipMemcpyHostToDevice, s0->stream));
-        if (int rc = comm_allreduce(s0->comm, d.p, 1, s0->stream)) return rc;
-        HIP_TRY(hipMemcpyAsync(&sq, d.p, sizeof(double), hipMemcpyDeviceToHost, s0->stream));
+        DeviceMem mem;
+        double *d = nullptr;
+        HIP_TRY(mem.alloc(&d, 1));
+        HIP_TRY(hipMemcpyAsync(d, &sq, sizeof(double), hipMemcpyHostToDevice, s0->stream));
+        if (int rc = comm_allreduce(s0->comm, d, 1, s0->stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(&sq, d, sizeof(double), hipMemcpyDeviceToHost, s0->stream));
         HIP_TRY(hipStreamSynchronize(s0->stream));
         if (int rc = comm_check(s0->comm)) return rc;
     }
@@ -1218,15 +1178,12 @@ extern "C" int tscm_solver_gather_boards(tscm_solver *s, double *board_rt)
     HIP_TRY(hipSetDevice(s->device));
     if (!s->comm_reg || s->world == 1 || s->comm_reg->group) return tscm_solver_download_params(s, nullptr, nullptr, board_rt);   // local groups share the caller's array
     if (s->L.B_total == 0) return 0;
-    double *full = nullptr;
     const size_t n = 6 * (size_t)s->L.B_total;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&full), n * sizeof(double)));
-    std::unique_ptr<double, void (*)(double *)> guard(full, [](double *q) { (void)hipFree(q); });
-    {
-        std::vector<double> mine(n, 0.0);
-        if (int rc = tscm_solver_download_params(s, nullptr, nullptr, mine.data())) return rc;     // owned boards at their own positions
-        HIP_TRY(hipMemcpy(full, mine.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    }
+    std::vector<double> mine(n, 0.0);
+    if (int rc = tscm_solver_download_params(s, nullptr, nullptr, mine.data())) return rc;     // owned boards at their own positions
+    DeviceMem mem;
+    double *full = nullptr;
+    HIP_TRY(mem.upload(&full, mine));
     if (int rc = comm_allreduce(s->comm_reg, full, n, s->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(board_rt, full, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1248,16 +1205,13 @@ extern "C" int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_s
 
 static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{}, const unsigned short *fixed = nullptr)
 {
-    tscm_solver *s = nullptr;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    int rc = tscm_solver_create(p, dev, &s);
-    if (rc) return rc;
-    s->loss = loss;
-    if (fixed && (rc = tscm_solver_set_fixed_intrinsics(s, fixed))) { tscm_solver_destroy(s); return rc; }
-    rc = tscm_solver_solve(s, opt, sum);
-    tscm_solver_destroy(s);
-    return rc;
+    SolverPtr sp;
+    if (int rc = create_scoped(p, dev, sp)) return rc;
+    sp->loss = loss;
+    if (fixed) if (int rc = tscm_solver_set_fixed_intrinsics(sp.get(), fixed)) return rc;
+    return tscm_solver_solve(sp.get(), opt, sum);
 }
 
 extern "C" int tscm_solve_multi(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum)
@@ -1309,9 +1263,9 @@ static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_
     opt.function_tolerance = opt.gradient_tolerance = opt.parameter_tolerance = 0.0;
     if ((rc = check_options(opt, loss.kind))) return rc;
     if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
-    tscm_solver *s = nullptr;
-    if ((rc = tscm_solver_create(p, device, &s))) return rc;
-    std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    SolverPtr sp;
+    if ((rc = create_scoped(p, device, sp))) return rc;
+    tscm_solver *s = sp.get();
     s->loss = loss;
     if (fixed && (rc = tscm_solver_set_fixed_intrinsics(s, fixed))) return rc;
     if ((rc = tscm_solver_upload_params(s, p->cam_rt, p->intr, p->board_rt))) return rc;
@@ -1373,21 +1327,21 @@ static int prepare_eval(tscm_solver *s, int with_floats = 0)
 extern "C" int tscm_eval_functor(const tscm_problem *p, int device, double *residuals, double *J_cam,
                                  double *J_board, double *J_intr, double *cost)
 {
-    tscm_solver *s = nullptr;
-    int rc = tscm_solver_create(p, device, &s);
+    SolverPtr sp;
+    int rc = create_scoped(p, device, sp);
     if (rc) return rc;
-    std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    tscm_solver *s = sp.get();
     if ((rc = prepare_eval(s))) return rc;
     const size_t N = (size_t)s->N;
     std::vector<int> corner_view(N);
     for (int v = 0; v < s->V; ++v) for (int j = 0; j < s->L.view_count[v]; ++j) corner_view[s->L.view_obs[v] + j] = v;
     const int *d_cv = nullptr;
     double *d_res = nullptr, *d_Jc = nullptr, *d_Jb = nullptr, *d_Ji = nullptr;
-    if ((rc = dev_upload(s, &d_cv, corner_view))) return rc;
-    if ((rc = dev_alloc(s, &d_res, 2 * N))) return rc;
-    if (J_cam && (rc = dev_alloc(s, &d_Jc, 12 * N))) return rc;
-    if (J_board && (rc = dev_alloc(s, &d_Jb, 12 * N))) return rc;
-    if (J_intr && (rc = dev_alloc(s, &d_Ji, 18 * N))) return rc;
+    HIP_TRY(s->mem.upload(&d_cv, corner_view));
+    HIP_TRY(s->mem.alloc(&d_res, 2 * N));
+    if (J_cam) HIP_TRY(s->mem.alloc(&d_Jc, 12 * N));
+    if (J_board) HIP_TRY(s->mem.alloc(&d_Jb, 12 * N));
+    if (J_intr) HIP_TRY(s->mem.alloc(&d_Ji, 18 * N));
     if (N) hipLaunchKernelGGL(k_eval_functor, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->P, s->S, d_cv, d_res, d_Jc, d_Jb, d_Ji);
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipGetLastError());
@@ -1430,9 +1384,9 @@ static int eval_normal_equations(const tscm_problem *p, int device, const tscm_o
     if (rc) return rc;
     opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
     if ((rc = check_options(opt, loss.kind))) return rc;
-    tscm_solver *s = nullptr;
-    if ((rc = tscm_solver_create(p, device, &s))) return rc;
-    std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    SolverPtr sp;
+    if ((rc = create_scoped(p, device, sp))) return rc;
+    tscm_solver *s = sp.get();
     s->loss = loss;
     s->xp = plan_exec(s->L, s->C, s->P.n_act, kCommNone, opt.exec_flags, opt.jacobian_fp32, loss.kind, s->P.rp, s->dev);     // (its Gram kernel)
     if ((rc = prepare_eval(s, s->xp.f32() ? 1 : 0))) return rc;
@@ -1497,52 +1451,44 @@ extern "C" int tscm_eval_normal_equations_robust(const tscm_problem *p, int devi
 }
 
 
+// k_project (3 -> 2) and k_unproject (2 -> 3): n rows of `in` through one camera's intrinsics
+static int map_rows(void (*kernel)(const double *, const double *, int, double *), const char *who, const double *intr9, const double *in, int w_in,
+                    int n, int device, double *out, int w_out)
+{
+    if (!intr9 || (n > 0 && (!in || !out)) || n < 0) return fail(TSCM_E_INVALID, "NULL argument");
+    if (int rc = select_device(device, who)) return rc;
+    if (n == 0) return 0;
+    DeviceMem mem;
+    const double *d_i = nullptr, *d_p = nullptr;
+    double *d_o = nullptr;
+    HIP_TRY(mem.upload(&d_i, intr9, 9));
+    HIP_TRY(mem.upload(&d_p, in, w_in * (size_t)n));
+    HIP_TRY(mem.alloc(&d_o, w_out * (size_t)n));
+    hipLaunchKernelGGL(kernel, dim3((n + 255) / 256), dim3(256), 0, 0, d_i, d_p, n, d_o);
+    HIP_TRY(hipMemcpy(out, d_o, w_out * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int tscm_project_points(const double *intr9, const double *points, int n, int device, double *pixels)
 {
-    if (!intr9 || (n > 0 && (!points || !pixels)) || n < 0) return fail(TSCM_E_INVALID, "NULL argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(TSCM_E_NO_DEVICE, "no usable HIP device");
-    HIP_TRY(hipSetDevice(device));
-    if (n == 0) return 0;
-    DevBuf d_i, d_p, d_o;
-    HIP_TRY(d_i.alloc(9));
-    HIP_TRY(d_p.alloc(3 * (size_t)n));
-    HIP_TRY(d_o.alloc(2 * (size_t)n));
-    HIP_TRY(hipMemcpy(d_i.p, intr9, 9 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_p.p, points, 3 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_project, dim3((n + 255) / 256), dim3(256), 0, 0, d_i.p, d_p.p, n, d_o.p);
-    HIP_TRY(hipMemcpy(pixels, d_o.p, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return map_rows(k_project, "tscm_project_points", intr9, points, 3, n, device, pixels, 2);
 }
 
 extern "C" int tscm_unproject_pixels(const double *intr9, const double *pixels, int n, int device, double *rays)
 {
-    if (!intr9 || (n > 0 && (!pixels || !rays)) || n < 0) return fail(TSCM_E_INVALID, "NULL argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(TSCM_E_NO_DEVICE, "no usable HIP device");
-    HIP_TRY(hipSetDevice(device));
-    if (n == 0) return 0;
-    DevBuf d_i, d_p, d_o;
-    HIP_TRY(d_i.alloc(9));
-    HIP_TRY(d_p.alloc(2 * (size_t)n));
-    HIP_TRY(d_o.alloc(3 * (size_t)n));
-    HIP_TRY(hipMemcpy(d_i.p, intr9, 9 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_p.p, pixels, 2 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_unproject, dim3((n + 255) / 256), dim3(256), 0, 0, d_i.p, d_p.p, n, d_o.p);
-    HIP_TRY(hipMemcpy(rays, d_o.p, 3 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
+    return map_rows(k_unproject, "tscm_unproject_pixels", intr9, pixels, 2, n, device, rays, 3);
 }
 
 extern "C" int tscm_reprojection_error(const tscm_problem *p, int device, double *per_camera_mean, double *global_mean, double *rmse)
 {
-    tscm_solver *s = nullptr;
-    int rc = tscm_solver_create(p, device, &s);
+    SolverPtr sp;
+    int rc = create_scoped(p, device, sp);
     if (rc) return rc;
-    std::unique_ptr<tscm_solver, void (*)(tscm_solver *)> guard(s, tscm_solver_destroy);
+    tscm_solver *s = sp.get();
     if ((rc = tscm_solver_upload_params(s, s->h_cam_rt, s->h_intr, s->h_board_rt))) return rc;
     double *d_e = nullptr, *d_q = nullptr;
-    if ((rc = dev_alloc(s, &d_e, (size_t)s->V))) return rc;
-    if ((rc = dev_alloc(s, &d_q, (size_t)s->V))) return rc;
+    HIP_TRY(s->mem.alloc(&d_e, (size_t)s->V));
+    HIP_TRY(s->mem.alloc(&d_q, (size_t)s->V));
     if (s->V) hipLaunchKernelGGL(k_reproj_error, dim3(s->V), dim3(64), 0, s->stream, s->P, s->d_init_cam, s->d_init_intr, s->d_init_board, d_e, d_q);
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipGetLastError());
@@ -1562,20 +1508,6 @@ extern "C" int tscm_reprojection_error(const tscm_problem *p, int device, double
 // ------------------------------------------------------------------------------------------------
 // batched mono refinement (tscm_mono_batch.h)
 // ------------------------------------------------------------------------------------------------
-// device allocations of one batch call, freed on every exit path
-struct MbAllocs {
-    std::vector<void *> p;
-    ~MbAllocs() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    hipError_t alloc(T **out, size_t n)
-    {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) p.push_back(q);
-        *out = static_cast<T *>(q);
-        return e;
-    }
-};
 struct MbStream {
     hipStream_t s = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1621,10 +1553,7 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
     }
     LossArg loss;
     if (int rc = make_loss(loss_kind, loss_scale, loss)) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(TSCM_E_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= n_dev) return fail(TSCM_E_NO_DEVICE, "device index out of range");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "tscm_solve_mono_batch")) return rc;
     for (int i = 0; i < n_problems; ++i) std::memset(&summaries[i], 0, sizeof(tscm_summary));
 
     const int K = bp.K, nc = (int)bp.chunk.size(), ns = (int)bp.slot_prob.size(), B = bp.B;
@@ -1645,44 +1574,25 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
         std::vector<int4> chunk(nc);
         for (int c = 0; c < nc; ++c) chunk[c] = make_int4(bp.chunk[c].x, bp.chunk[c].y, bp.chunk[c].z, 0);
 
-        MbAllocs A;
+        DeviceMem A;
         MbDev D{};
         D.K = K; D.n_points = bp.n_points; D.n_chunks = nc; D.n_slots = ns; D.loss = loss;
-        double *d_xy = nullptr, *d_u = nullptr, *d_v = nullptr;
-        int4 *d_chunk = nullptr;
-        int *d_cptr = nullptr, *d_bptr = nullptr, *d_sb = nullptr, *d_so = nullptr, *d_sc = nullptr;
-        unsigned char *d_sa = nullptr;
-        unsigned short *d_mask = nullptr;
         char *d_ctrl = nullptr;
         const size_t ctrl_bytes = sizeof(CtrlHead) * (size_t)K + sizeof(IterLog) * (size_t)kMaxLog * K;
-        HIP_TRY(A.alloc(&d_xy, 2 * (size_t)bp.n_points)); HIP_TRY(A.alloc(&d_u, (size_t)bp.N)); HIP_TRY(A.alloc(&d_v, (size_t)bp.N));
-        HIP_TRY(A.alloc(&d_chunk, (size_t)nc)); HIP_TRY(A.alloc(&d_cptr, (size_t)K + 1)); HIP_TRY(A.alloc(&d_bptr, (size_t)K + 1));
-        HIP_TRY(A.alloc(&d_sb, (size_t)ns)); HIP_TRY(A.alloc(&d_so, (size_t)ns)); HIP_TRY(A.alloc(&d_sc, (size_t)ns));
-        HIP_TRY(A.alloc(&d_sa, (size_t)ns)); HIP_TRY(A.alloc(&d_mask, (size_t)K));
+        HIP_TRY(A.upload(&D.board_xy, problems[0].board_xy, 2 * (size_t)bp.n_points));
+        HIP_TRY(A.upload(&D.obs_u, ou)); HIP_TRY(A.upload(&D.obs_v, ov));
+        HIP_TRY(A.upload(&D.chunk, chunk));
+        HIP_TRY(A.upload(&D.chunk_ptr, bp.chunk_ptr)); HIP_TRY(A.upload(&D.board_ptr, bp.board_ptr));      // [K + 1]
+        HIP_TRY(A.upload(&D.slot_board, bp.slot_board)); HIP_TRY(A.upload(&D.slot_obs, bp.slot_obs));      // [ns]
+        HIP_TRY(A.upload(&D.slot_count, bp.slot_count)); HIP_TRY(A.upload(&D.slot_active, bp.slot_active));
+        HIP_TRY(A.upload(&D.mask, bp.mask));                                                                // [K]
         for (int b = 0; b < 2; ++b) {
-            HIP_TRY(A.alloc(&D.intr[b], 9 * (size_t)K)); HIP_TRY(A.alloc(&D.board[b], 6 * (size_t)B));
+            HIP_TRY(A.upload(&D.intr[b], intr)); HIP_TRY(A.upload(&D.board[b], board));
             HIP_TRY(A.alloc(&D.rec[b], (size_t)kMbRec * ns)); HIP_TRY(A.alloc(&D.part[b], (size_t)kMbPart * nc)); HIP_TRY(A.alloc(&D.tot[b], (size_t)kMbTot * K));
         }
         HIP_TRY(A.alloc(&D.schur, (size_t)kMbSp * nc)); HIP_TRY(A.alloc(&D.solvep, 4 * (size_t)nc)); HIP_TRY(A.alloc(&D.cam_mp, 4 * (size_t)K));
         HIP_TRY(A.alloc(&D.s_b, 6 * (size_t)ns)); HIP_TRY(A.alloc(&D.s_f, 7 * (size_t)K));
         HIP_TRY(A.alloc(&d_ctrl, ctrl_bytes)); HIP_TRY(A.alloc(&D.n_done, 1)); HIP_TRY(A.alloc(&D.out, 9 * (size_t)K + 6 * (size_t)B));
-        HIP_TRY(hipMemcpy(d_xy, problems[0].board_xy, 2 * sizeof(double) * bp.n_points, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_u, ou.data(), sizeof(double) * ou.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_v, ov.data(), sizeof(double) * ov.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_chunk, chunk.data(), sizeof(int4) * nc, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_cptr, bp.chunk_ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_bptr, bp.board_ptr.data(), sizeof(int) * (K + 1), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sb, bp.slot_board.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_so, bp.slot_obs.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sc, bp.slot_count.data(), sizeof(int) * ns, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_sa, bp.slot_active.data(), ns, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_mask, bp.mask.data(), sizeof(unsigned short) * K, hipMemcpyHostToDevice));
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(hipMemcpy(D.intr[b], intr.data(), sizeof(double) * intr.size(), hipMemcpyHostToDevice));
-            if (B) HIP_TRY(hipMemcpy(D.board[b], board.data(), sizeof(double) * board.size(), hipMemcpyHostToDevice));
-        }
-        D.board_xy = d_xy; D.obs_u = d_u; D.obs_v = d_v; D.chunk = d_chunk; D.chunk_ptr = d_cptr; D.board_ptr = d_bptr;
-        D.slot_board = d_sb; D.slot_obs = d_so; D.slot_count = d_sc; D.slot_active = d_sa; D.mask = d_mask;
         D.head = reinterpret_cast<CtrlHead *>(d_ctrl);
         D.log = reinterpret_cast<IterLog *>(d_ctrl + sizeof(CtrlHead) * (size_t)K);
 
@@ -1770,9 +1680,7 @@ extern "C" int tscm_comm_create(const unsigned char id[TSCM_UNIQUE_ID_BYTES], in
 {
     if (!id || !out || world < 1 || rank < 0 || rank >= world) return fail(TSCM_E_INVALID, "bad communicator arguments");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(TSCM_E_NO_DEVICE, "no usable HIP device");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "tscm_comm_create")) return rc;
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof(u));
     std::unique_ptr<tscm_comm> c(new tscm_comm);
@@ -1786,16 +1694,11 @@ extern "C" int tscm_comm_create_local(int world, int device, tscm_comm **out)
 {
     if (!out || world < 1) return fail(TSCM_E_INVALID, "bad communicator arguments");
     for (int r = 0; r < world; ++r) out[r] = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(TSCM_E_NO_DEVICE, "no usable HIP device");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "tscm_comm_create_local")) return rc;
     std::unique_ptr<tscm_local_group> g(new tscm_local_group);
     g->world = world; g->device = device;
     HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    if (hipMalloc(reinterpret_cast<void **>(&g->d_ptrs), sizeof(double *) * 2 * (size_t)world) != hipSuccess) {
-        (void)hipStreamDestroy(g->stream);
-        return fail(TSCM_E_NOMEM, "hipMalloc of the group's pointer table failed");
-    }
+    if (g->mem.alloc(&g->d_ptrs, 2 * (size_t)world) != hipSuccess) return fail(TSCM_E_NOMEM, "hipMalloc of the group's pointer table failed");
     for (int r = 0; r < world; ++r) {
         tscm_comm *c = new tscm_comm;
         c->rank = r; c->world = world; c->device = device; c->group = g.get();
@@ -1813,31 +1716,34 @@ extern "C" int tscm_comm_ipc_open(int rank, int world, int device, size_t max_do
 {
     if (!out || !handle || world < 1 || world > kIpcMaxWorld || rank < 0 || rank >= world || max_doubles == 0) return fail(TSCM_E_INVALID, "bad communicator arguments (IPC: up to 16 ranks)");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(TSCM_E_NO_DEVICE, "no usable HIP device");
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = select_device(device, "tscm_comm_ipc_open")) return rc;
     std::unique_ptr<tscm_comm> c(new tscm_comm);
     std::unique_ptr<tscm_ipc> x(new tscm_ipc);
     c->rank = rank; c->world = world; c->device = device;
     x->rank = rank; x->world = world; x->max_doubles = (max_doubles + 1) & ~(size_t)1;
-    if (hipMalloc(reinterpret_cast<void **>(&x->d_fault), sizeof(int)) != hipSuccess) return fail(TSCM_E_NOMEM, "hipMalloc failed");
+    if (x->mem.alloc(&x->d_fault, 1) != hipSuccess) return fail(TSCM_E_NOMEM, "hipMalloc failed");
     hipIpcMemHandle_t h;
     // fine-grained first (what a peer on ANOTHER device needs for its system-scope flag stores and my loads of them to meet);
     // where that cannot be had or exported, ordinary device memory -- enough for ranks that share this device, and the handle
     // says so: a peer on another device then refuses to connect
     hipError_t e = hipErrorUnknown;
+    char *own = nullptr;
     for (int attempt = 0; attempt < 2 && e != hipSuccess; ++attempt) {
         x->fine = attempt == 0;
-        e = x->fine ? hipExtMallocWithFlags(&x->own, x->total_bytes(), hipDeviceMallocFinegrained) : hipMalloc(&x->own, x->total_bytes());
-        if (e != hipSuccess) { x->own = nullptr; (void)hipGetLastError(); continue; }
-        e = hipMemset(x->own, 0, x->total_bytes());
+        if (x->fine) {
+            e = hipExtMallocWithFlags(reinterpret_cast<void **>(&own), x->total_bytes(), hipDeviceMallocFinegrained);
+            if (e == hipSuccess) x->mem.adopt(own);
+        } else {
+            e = x->mem.alloc(&own, x->total_bytes());
+        }
+        if (e != hipSuccess) { (void)hipGetLastError(); continue; }
+        e = hipMemset(own, 0, x->total_bytes());
         if (e == hipSuccess) e = hipMemset(x->d_fault, 0, sizeof(int));
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipIpcGetMemHandle(&h, x->own);
-        if (e != hipSuccess) { (void)hipFree(x->own); x->own = nullptr; (void)hipGetLastError(); }
+        if (e == hipSuccess) e = hipIpcGetMemHandle(&h, own);
+        if (e != hipSuccess) { x->mem.release(own); (void)hipGetLastError(); }
     }
     if (e != hipSuccess) {
-        (void)hipFree(x->d_fault);
         return fail(TSCM_E_HIP, std::string("IPC exchange buffer: ") + hipGetErrorString(e) + " (hipIpcGetMemHandle needs HSA_ENABLE_IPC_MODE_LEGACY=0 on hosts whose driver only supports dmabuf IPC)");
     }
     std::memset(handle, 0, TSCM_IPC_HANDLE_BYTES);
@@ -1850,7 +1756,7 @@ extern "C" int tscm_comm_ipc_open(int rank, int world, int device, size_t max_do
         id.pci[0] = prop.pciDomainID; id.pci[1] = prop.pciBusID; id.pci[2] = prop.pciDeviceID; id.fine = x->fine ? 1 : 0;
         std::memcpy(handle + sizeof(h), &id, sizeof(id));
     }
-    x->mapped[rank] = x->own;
+    x->mapped[rank] = own;
     g_err = x->fine ? "note: IPC exchange buffer in fine-grained device memory" : "note: IPC exchange buffer in ordinary device memory (ranks on this device only)";
     c->ipc = x.release();
     *out = c.release();
@@ -1874,8 +1780,8 @@ extern "C" int tscm_comm_ipc_connect(tscm_comm *c, const unsigned char *handles)
         if (std::memcmp(id.pci, me.pci, sizeof(id.pci)) != 0) {
             // a peer on another device: both buffers fine-grained, and peer access enabled here and now (not lazily)
             if (!id.fine || !x->fine) return fail(TSCM_E_UNSUPPORTED, "IPC exchange across devices needs fine-grained exchange buffers on both ranks (one of them is ordinary device memory): put the ranks on one device or use RCCL");
-            int ndev = 0, peer = -1;
-            HIP_TRY(hipGetDeviceCount(&ndev));
+            const int ndev = tscm_device_count();
+            int peer = -1;
             for (int d = 0; d < ndev && peer < 0; ++d) {
                 hipDeviceProp_t prop;
                 HIP_TRY(hipGetDeviceProperties(&prop, d));
@@ -1916,16 +1822,12 @@ extern "C" void tscm_comm_destroy(tscm_comm *c)
         (void)hipSetDevice(c->device);
         (void)hipDeviceSynchronize();
         for (int r = 0; r < c->ipc->world; ++r) if (r != c->ipc->rank && c->ipc->mapped[r]) (void)hipIpcCloseMemHandle(c->ipc->mapped[r]);
-        (void)hipFree(c->ipc->own);
-        (void)hipFree(c->ipc->d_fault);
-        delete c->ipc;
+        delete c->ipc;                  // (its DeviceMem frees the buffer and the fault word)
     }
     if (c->group && --c->group->refs == 0) {
         (void)hipSetDevice(c->group->device);
         (void)hipStreamSynchronize(c->group->stream);
-        (void)hipFree(c->group->d_ptrs);
-        (void)hipStreamDestroy(c->group->stream);
-        delete c->group;
+        delete c->group;                // (frees the pointer table, destroys the stream)
     }
     delete c;
 }

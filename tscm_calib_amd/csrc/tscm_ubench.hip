@@ -9,9 +9,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include <string>
+#include "tscm_host.h"
 
-int tscm_set_error(int code, const std::string &msg);      // tscm_solver.hip
+#include <string>
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -104,6 +104,17 @@ bool time_launches(F launch, int reps, double *ms_per_launch)
     return ok && hipGetLastError() == hipSuccess;
 }
 
+// the device of a measurement and one double per thread of 8 workgroups of 4 waves per CU (8 waves per SIMD)
+int peak_setup(int device, const char *who, tscm::DeviceMem &mem, int *blocks, double **out)
+{
+    if (tscm::select_device(device, who)) return TSCM_E_NO_DEVICE;      // (a refused hipSetDevice too)
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return tscm_set_error(TSCM_E_HIP, "hipGetDeviceProperties failed");
+    *blocks = prop.multiProcessorCount * 8;
+    if (mem.alloc(out, 256 * (size_t)*blocks) != hipSuccess) return tscm_set_error(TSCM_E_NOMEM, "hipMalloc failed");
+    return 0;
+}
+
 }  // namespace
 
 // peaks[0] = v_mfma_f64_16x16x4_f64, peaks[1] = v_mfma_f64_4x4x4_4b_f64, peaks[2] = v_fma_f64, TFLOP/s
@@ -111,15 +122,13 @@ extern "C" int tscm_device_peak_fp64_ex(int device, double peaks[3])
 {
     if (!peaks) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
     if (int rc = tscm_device_peak_fp64(device, &peaks[0], &peaks[2])) return rc;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return tscm_set_error(TSCM_E_HIP, "hipGetDeviceProperties failed");
-    const int blocks = prop.multiProcessorCount * 8;
+    tscm::DeviceMem mem;
+    int blocks = 0;
     double *out = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&out), sizeof(double) * 256 * (size_t)blocks) != hipSuccess) return tscm_set_error(TSCM_E_NOMEM, "hipMalloc failed");
+    if (int rc = peak_setup(device, "tscm_device_peak_fp64_ex", mem, &blocks, &out)) return rc;
     const int iters = 8000, reps = 5;
     double ms = 0.0;
     const bool ok = time_launches([&] { hipLaunchKernelGGL(k_peak_mfma4, dim3(blocks), dim3(256), 0, 0, out, iters, 1.0); }, reps, &ms);
-    (void)hipFree(out);
     if (!ok || ms <= 0.0) return tscm_set_error(TSCM_E_HIP, "fp64 peak measurement failed");
     peaks[1] = 512.0 * 8.0 * iters * 4.0 * blocks / (ms * 1e-3) / 1e12;       // 4 blocks x 4x4x4x2 flop per instruction, 8 per wave and iteration, 4 waves
     return 0;
@@ -129,18 +138,13 @@ extern "C" int tscm_device_peak_fp64_ex(int device, double peaks[3])
 extern "C" int tscm_device_peak_fp32_mfma(int device, double *tflops)
 {
     if (!tflops) return tscm_set_error(TSCM_E_INVALID, "NULL argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "no usable HIP device");
-    if (hipSetDevice(device) != hipSuccess) return tscm_set_error(TSCM_E_NO_DEVICE, "hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return tscm_set_error(TSCM_E_HIP, "hipGetDeviceProperties failed");
-    const int blocks = prop.multiProcessorCount * 8;
+    tscm::DeviceMem mem;
+    int blocks = 0;
     double *out = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&out), sizeof(double) * 256 * (size_t)blocks) != hipSuccess) return tscm_set_error(TSCM_E_NOMEM, "hipMalloc failed");
+    if (int rc = peak_setup(device, "tscm_device_peak_fp32_mfma", mem, &blocks, &out)) return rc;
     const int iters = 8000, reps = 5;
     double ms = 0.0;
     const bool ok = time_launches([&] { hipLaunchKernelGGL(k_peak_mfma_f32, dim3(blocks), dim3(256), 0, 0, out, iters, 1.f); }, reps, &ms);
-    (void)hipFree(out);
     if (!ok || ms <= 0.0) return tscm_set_error(TSCM_E_HIP, "fp32 MFMA peak measurement failed");
     *tflops = 2048.0 * 4.0 * iters * 4.0 * blocks / (ms * 1e-3) / 1e12;       // 16x16x4x2 flop per instruction, 4 per wave and iteration, 4 waves
     return 0;
@@ -148,19 +152,14 @@ extern "C" int tscm_device_peak_fp32_mfma(int device, double *tflops)
 
 extern "C" int tscm_device_peak_fp64(int device, double *mfma_tflops, double *valu_tflops)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return tscm_set_error(TSCM_E_NO_DEVICE, "no usable HIP device");
-    if (hipSetDevice(device) != hipSuccess) return tscm_set_error(TSCM_E_NO_DEVICE, "hipSetDevice failed");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return tscm_set_error(TSCM_E_HIP, "hipGetDeviceProperties failed");
-    const int blocks = prop.multiProcessorCount * 8;             // 8 workgroups of 4 waves per CU: 8 waves per SIMD
+    tscm::DeviceMem mem;
+    int blocks = 0;
     double *out = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&out), sizeof(double) * 256 * (size_t)blocks) != hipSuccess) return tscm_set_error(TSCM_E_NOMEM, "hipMalloc failed");
+    if (int rc = peak_setup(device, "tscm_device_peak_fp64", mem, &blocks, &out)) return rc;
     const int iters = 4000, reps = 5;
     double ms_fma = 0.0, ms_mfma = 0.0;
     const bool ok1 = time_launches([&] { hipLaunchKernelGGL(k_peak_fma, dim3(blocks), dim3(256), 0, 0, out, iters, 1.0); }, reps, &ms_fma);
     const bool ok2 = time_launches([&] { hipLaunchKernelGGL(k_peak_mfma, dim3(blocks), dim3(256), 0, 0, out, iters, 1.0); }, reps, &ms_mfma);
-    (void)hipFree(out);
     if (!ok1 || !ok2 || ms_fma <= 0.0 || ms_mfma <= 0.0) return tscm_set_error(TSCM_E_HIP, "fp64 peak measurement failed");
     const double fl_fma = 2.0 * 8.0 * iters * 256.0 * blocks;                  // 8 FMAs per lane and iteration
     const double fl_mfma = 2048.0 * 4.0 * iters * 4.0 * blocks;               // 16x16x4x2 flop per instruction, 4 per wave and iteration, 4 waves
