@@ -1,0 +1,94 @@
+// stereo_pair_demo.cpp -- from two fisheye images of adjacent cameras of a calibrated rig to 3-D points: the long-lat
+// rectification of rectify_pair_demo.cpp (tscm_build_maps_ex, tscm_remap), then census + semi-global matching along the
+// rows (tscm_stereo_match) and the points of the disparities in the pair frame of camera a (tscm_stereo_points).
+// Images are 8-bit binary PGM files (P5).
+//   usage: stereo_pair_demo calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]
+// disparity.pgm: disparity in pixels (saturated at 255), 0 where invalid; points.txt: one "column row X Y Z" line per
+// valid pixel, X Y Z in the units of the calibration's translations, pair frame (x along the baseline from a to b).
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "tscm/tscm_calib.hpp"
+
+static bool read_pgm(const char *path, std::vector<unsigned char> &pix, int &w, int &h)
+{
+    std::ifstream f(path, std::ios::binary);
+    std::string magic;
+    int maxval = 0;
+    if (!(f >> magic >> w >> h >> maxval) || magic != "P5" || maxval != 255 || w < 1 || h < 1) return false;
+    f.get();
+    pix.resize((size_t)w * h);
+    f.read(reinterpret_cast<char *>(pix.data()), (std::streamsize)pix.size());
+    return (size_t)f.gcount() == pix.size();
+}
+
+static bool write_pgm(const char *path, const std::vector<unsigned char> &pix, int w, int h)
+{
+    std::ofstream f(path, std::ios::binary);
+    f << "P5\n" << w << " " << h << "\n255\n";
+    f.write(reinterpret_cast<const char *>(pix.data()), (std::streamsize)pix.size());
+    return (bool)f;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc < 8) {
+        std::fprintf(stderr, "usage: %s calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]\n", argv[0]);
+        return 2;
+    }
+    const int cam[2] = { std::atoi(argv[2]), std::atoi(argv[3]) };
+    tscm::Size size = { argc > 9 ? std::atoi(argv[8]) : 640, argc > 9 ? std::atoi(argv[9]) : 320 };
+    const double pi = 3.14159265358979323846;
+    try {
+        enum { kMaxCameras = 32 };
+        std::vector<double> intr(9 * kMaxCameras), Twc(12 * kMaxCameras);
+        int n_cameras = 0;
+        tscm::check(tscm_yaml_read(argv[1], kMaxCameras, &n_cameras, intr.data(), Twc.data()));
+        for (int k = 0; k < 2; ++k)
+            if (cam[k] < 0 || cam[k] >= n_cameras) { std::fprintf(stderr, "%s has cameras 0..%d\n", argv[1], n_cameras - 1); return 2; }
+        const double *Ta = &Twc[12 * cam[0]], *Tb = &Twc[12 * cam[1]];
+        tscm_map_desc desc[2];
+        std::vector<float> mapx[2], mapy[2];
+        tscm::rectify_pair_maps(&intr[9 * cam[0]], Ta, &intr[9 * cam[1]], Tb, TSCM_PROJ_LONGLAT, size, pi, pi / 2, desc, mapx, mapy);
+        std::vector<unsigned char> rect[2];
+        for (int k = 0; k < 2; ++k) {
+            std::vector<unsigned char> img;
+            int w = 0, h = 0;
+            if (!read_pgm(argv[4 + k], img, w, h)) { std::fprintf(stderr, "cannot read %s as an 8-bit binary PGM\n", argv[4 + k]); return 2; }
+            rect[k].assign((size_t)size.width * size.height, 0);
+            tscm::check(tscm_remap(img.data(), w, h, w, 1, mapx[k].data(), mapy[k].data(), size.width, size.height, size.width, 0, 0, rect[k].data(), size.width));
+        }
+        tscm_stereo_params params;
+        tscm_stereo_default_params(&params);
+        if (argc > 10) params.num_disparities = std::atoi(argv[10]);
+        if (argc > 11) params.paths = std::atoi(argv[11]);
+        const std::vector<short> disparity = tscm::stereo_match(rect[0].data(), rect[1].data(), size, &params);
+        const double dt[3] = { Tb[3] - Ta[3], Tb[7] - Ta[7], Tb[11] - Ta[11] };
+        const double baseline = std::sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
+        std::vector<unsigned char> valid;
+        const std::vector<tscm::Point3d> points = tscm::stereo_points(disparity, size, params.min_disparity, desc[0], TSCM_PROJ_LONGLAT, baseline, valid);
+        std::vector<unsigned char> shown(disparity.size(), 0);
+        std::ofstream list(argv[7]);
+        list.precision(9);
+        size_t n_valid = 0;
+        for (size_t e = 0; e < disparity.size(); ++e) {
+            if (!valid[e]) continue;
+            ++n_valid;
+            const int px = (disparity[e] + 8) / 16;
+            shown[e] = (unsigned char)(px < 0 ? 0 : px > 255 ? 255 : px);
+            list << e % (size_t)size.width << " " << e / (size_t)size.width << " " << points[e].x << " " << points[e].y << " " << points[e].z << "\n";
+        }
+        if (!list || !write_pgm(argv[6], shown, size.width, size.height)) { std::fprintf(stderr, "cannot write %s / %s\n", argv[6], argv[7]); return 2; }
+        std::printf("cameras %d, %d: baseline %.3f, %d x %d, %d disparities, %d paths: %zu of %zu pixels with a point\n", cam[0], cam[1], baseline, size.width,
+                    size.height, params.num_disparities, params.paths, n_valid, disparity.size());
+    } catch (const std::exception &e) {
+        std::cerr << e.what() << "\n";
+        return 3;
+    }
+    return 0;
+}

@@ -718,6 +718,69 @@ typedef struct tscm_chessboards {
 int tscm_chessboards_from_corners(int n, const double *x, const double *y, const double *v1, const double *v2, tscm_chessboards *out);
 void tscm_chessboards_free(tscm_chessboards *b);
 
+/* ------------------------------------------------------------------ stereo matching on a rectified pair
+ * What the rectified pair of tscm_build_maps_ex + tscm_remap is for: matching along rows (PERSPECTIVE or LONGLAT tables of
+ * rectify_pair_descs / rectify_pair_maps, where a scene point lies on the same row of both images) and the 3-D points of
+ * the disparities.  Census + semi-global matching, integer arithmetic throughout, defined here operation by operation so
+ * that a host restatement gives the same bits (tests/stereo_ref.py).  D = num_disparities, d_k = min_disparity + k.
+ *   census   9 wide x 7 high window, dy = -3..3 outer, dx = -4..4 inner, centre skipped, coordinates clamped to the image:
+ *            code = (code << 1) | (neighbour < centre); 62 bits.
+ *   cost     C(y, x, k) = popcount(censusL(y, x) ^ censusR(y, x - d_k)); 64 where x - d_k is outside [0, width).
+ *   paths    directions (dx, dy) in the order (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1) (-1,1), the first `paths`.
+ *            L_r(p, k) = C(p, k) where p - r is outside the image, otherwise
+ *            C(p, k) + min(L_r(p-r, k), L_r(p-r, k-1) + p1, L_r(p-r, k+1) + p1, m + p2) - m,  m = min_k L_r(p-r, k);
+ *            terms with k +- 1 outside [0, D) are absent.  S = sum_r L_r (uint16; p2 <= 255 and C <= 64 rule out overflow).
+ *   winner   k* = the lowest k at which S is minimal.
+ *   uniqueness_ratio > 0: invalid if any k with |k - k*| > 1 has S(k) * (100 - ratio) < S(k*) * 100.
+ *   disp12_max_diff >= 0: kR(y, x2) = the lowest k minimising S(y, x2 + d_k, k) over the k whose x2 + d_k is inside the
+ *            image; with x2 = x - d_k*: invalid if x2 is outside the image or |kR(y, x2) - k*| > disp12_max_diff.
+ *   output   16 d_k*, plus for 0 < k* < D - 1 the parabola term floor(((S(k*-1) - S(k*+1)) * 16 + den) / (2 den)) with
+ *            den = max(S(k*-1) + S(k*+1) - 2 S(k*), 1) (floor division, as OpenCV's StereoSGBM); invalid pixels get
+ *            16 (min_disparity - 1).
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: NULL images / params /
+ * disparity, stride or disp_stride < width, a struct_size other than sizeof(tscm_stereo_params), num_disparities not a
+ * multiple of 16 in 16..256, paths other than 4 or 8, p1 or p2 outside 0 <= p1 <= p2 <= 255, uniqueness_ratio outside
+ * 0..99, a min_disparity whose 16-fold output leaves 16 bits (below -2047, or min_disparity + D above 2047).
+ * width == 0 or height == 0 returns 0 without touching a device.  Elements of `disparity` between width and disp_stride
+ * keep the caller's values.  device_index: as `device` elsewhere, TSCM_E_NO_DEVICE outside [0, tscm_device_count()).
+ * seconds_kernel (may be NULL): device time of the kernels (HIP events), without the copies. */
+typedef struct tscm_stereo_params {
+    int struct_size;        /* sizeof(tscm_stereo_params)                     */
+    int min_disparity;      /* may be negative                                */
+    int num_disparities;    /* D: multiple of 16, 16..256                     */
+    int p1, p2;             /* 0 <= p1 <= p2 <= 255                           */
+    int paths;              /* 4 or 8                                         */
+    int uniqueness_ratio;   /* 0..99, 0 = off                                 */
+    int disp12_max_diff;    /* < 0 = no left-right check                      */
+} tscm_stereo_params;
+void tscm_stereo_default_params(tscm_stereo_params *p);   /* 0, 128, 8, 32, 8, 10, 1 */
+
+int tscm_stereo_match(const unsigned char *left, const unsigned char *right, int width, int height, int stride,
+                      const tscm_stereo_params *params, int device_index,
+                      short *disparity /* [height][disp_stride], 16 * d, invalid = 16 * (min_disparity - 1) */,
+                      int disp_stride, double *seconds_kernel /* may be NULL */);
+
+/* The stages of the same launches, for parity tests (like tscm_corner_planes_batch): any output may be NULL. */
+int tscm_stereo_stages(const unsigned char *left, const unsigned char *right, int width, int height, int stride,
+                       const tscm_stereo_params *params, int device_index,
+                       unsigned long long *census_left, unsigned long long *census_right /* [h*w] */,
+                       unsigned char *cost /* [h*w*D] */, unsigned short *aggregated /* [h*w*D] */);
+
+/* Device seconds of the calling thread's last tscm_stereo_match / tscm_stereo_stages by stage: census (both images), cost,
+ * path aggregation, kR of the left-right check, winner. */
+int tscm_stereo_stage_times(double *seconds /* [5] */);
+
+/* Points of a disparity map in the pair frame of the left camera (x along the baseline, the right camera at +baseline, so
+ * disparities are positive).  With x, y the pixel, d = disparity / 16.0 and fx fy cx cy of left_map (fp64):
+ *   PERSPECTIVE  Z = fx B / d,  X = (x - cx)/fx Z,  Y = (y - cy)/fy Z
+ *   LONGLAT      aL = (x - cx)/fx, aR = aL - d/fx, b = (y - cy)/fy, r = B cos aR / sin(aL - aR)  [law of sines in the
+ *                epipolar plane],  P = r (sin aL, cos aL sin b, cos aL cos b)
+ * valid = 0 and P = NaN where the disparity is the invalid value 16 (min_disparity - 1) or d <= 0.  Any other projection,
+ * a NULL pointer or disp_stride < width: TSCM_E_INVALID before any device is touched. */
+int tscm_stereo_points(const short *disparity, int width, int height, int disp_stride, int min_disparity,
+                       const tscm_map_desc *left_map, int projection, double baseline, int device_index,
+                       double *points /* [h*w*3] */, unsigned char *valid /* [h*w] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@
 //   undistort_chessboard (table)         TS.cpp:308-330    undistort_chessboard_maps           -> tscm_build_maps
 //   (none: pinhole tables only)                            undistort(..., projection), rectify_pair_maps -> tscm_build_maps_ex
 //   (none)                                                 TripleSphereCamera::rectify_point   -> tscm_rectify_points
+//   (none: the rectified pair is its last product)         stereo_match, stereo_points         -> tscm_stereo_match, tscm_stereo_points
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
@@ -659,6 +660,34 @@ inline void rectify_pair_maps(const double *intr_a, const double *Twc_a, const d
     }
     // two launches: each table has its own host arrays
     for (int k = 0; k < 2; ++k) check(tscm_build_maps_ex(&desc[k], &kinds[k], 1, device, exact ? 1 : 0, mapx[k].data(), mapy[k].data(), n, nullptr));
+}
+
+// What the rectified pair is for.  stereo_match: census + semi-global matching of two rectified 8-bit images of `size`
+// (rows of size.width bytes) -> 16 * disparity per pixel of the left image, invalid pixels 16 * (min_disparity - 1);
+// params == NULL: tscm_stereo_default_params.
+inline std::vector<short> stereo_match(const unsigned char *left, const unsigned char *right, Size size, const tscm_stereo_params *params = NULL, int device = 0)
+{
+    tscm_stereo_params p;
+    if (params) p = *params;
+    else tscm_stereo_default_params(&p);
+    std::vector<short> disparity((size_t)size.width * size.height);
+    check(tscm_stereo_match(left, right, size.width, size.height, size.width, &p, device, disparity.data(), size.width, NULL));
+    return disparity;
+}
+
+// stereo_points: the disparities of stereo_match on the pair of rectify_pair_maps (left_map = desc[0], projection
+// TSCM_PROJ_PERSPECTIVE or TSCM_PROJ_LONGLAT, baseline = |t_b - t_a|) -> points in the pair frame of camera a
+// (P_rig = rectify_pair_rotation(t_a, t_b) * P + t_a); points of invalid pixels are NaN, valid[k] = 0.
+inline std::vector<Point3d> stereo_points(const std::vector<short> &disparity, Size size, int min_disparity, const tscm_map_desc &left_map, int projection,
+                                          double baseline, std::vector<unsigned char> &valid, int device = 0)
+{
+    if (disparity.size() != (size_t)size.width * size.height) throw std::runtime_error("tscm: the disparity map does not have the given size");
+    std::vector<Point3d> points(disparity.size());
+    valid.assign(disparity.size(), 0);
+    if (points.empty()) return points;
+    check(tscm_stereo_points(disparity.data(), size.width, size.height, size.width, min_disparity, &left_map, projection, baseline, device,
+                             &points[0].x, valid.data()));
+    return points;
 }
 
 }  // namespace tscm

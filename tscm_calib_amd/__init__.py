@@ -6,6 +6,7 @@ Only what the reprojection-error LM hot path of imuncle/TSCM_Calib and its immed
   api.py       host-side mirror of the reference interface (calibrate / refinement / functor eval)
   rig.py       rig initialisation (MultiCalib constructor), focal estimate, [r1 r2 t] -> pose
   maps.py      remap tables (undistort, undistort_chessboard, epipolar rectification)
+  stereo.py    census + semi-global matching on a rectified pair, points, pair_depth
   calib_io.py  calibration YAML in the cv::FileStorage layout
   problem.py   problem container, frame sharding
   synth.py     deterministic synthetic chessboard observations (BASELINE.json configs)

@@ -117,6 +117,12 @@ class CMapDesc(C.Structure):
     ]
 
 
+class CStereoParams(C.Structure):
+    """tscm_stereo_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("min_disparity", C.c_int), ("num_disparities", C.c_int), ("p1", C.c_int), ("p2", C.c_int),
+                ("paths", C.c_int), ("uniqueness_ratio", C.c_int), ("disp12_max_diff", C.c_int)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -140,6 +146,7 @@ EXPORTS = [
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
     "tscm_build_maps_ex", "tscm_rectify_points",
+    "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
 ]
 
 
@@ -225,6 +232,15 @@ def lib():
     L.tscm_build_maps_ex.argtypes = [C.POINTER(CMapDesc), ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                      C.c_size_t, dp]
     L.tscm_rectify_points.argtypes = [C.POINTER(CMapDesc), C.c_int, dp, C.c_int, C.c_int, dp, C.POINTER(C.c_ubyte)]
+    ubp = C.POINTER(C.c_ubyte)
+    L.tscm_stereo_default_params.argtypes = [C.POINTER(CStereoParams)]
+    L.tscm_stereo_default_params.restype = None
+    L.tscm_stereo_match.argtypes = [ubp, ubp, C.c_int, C.c_int, C.c_int, C.POINTER(CStereoParams), C.c_int, C.POINTER(C.c_short), C.c_int, dp]
+    L.tscm_stereo_stages.argtypes = [ubp, ubp, C.c_int, C.c_int, C.c_int, C.POINTER(CStereoParams), C.c_int, C.POINTER(C.c_ulonglong),
+                                     C.POINTER(C.c_ulonglong), ubp, usp]
+    L.tscm_stereo_stage_times.argtypes = [dp]
+    L.tscm_stereo_points.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CMapDesc), C.c_int, C.c_double, C.c_int,
+                                     dp, ubp]
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]
     L.tscm_poses_from_r1r2t.argtypes = [dp, C.c_void_p, C.c_int, dp]
     L.tscm_estimate_extrinsic.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip]

@@ -1,0 +1,120 @@
+"""Stereo matching and depth on a rectified pair (tscm.h: tscm_stereo_*): census + semi-global matching on the device,
+the 3-D points of a disparity map, and pair_depth, the chain from two fisheye images of a calibrated rig to points:
+rectify_pair_descs -> build_maps -> remap -> match -> points."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import lib as _lib
+from . import maps as _maps
+
+PARAM_NAMES = ("min_disparity", "num_disparities", "p1", "p2", "paths", "uniqueness_ratio", "disp12_max_diff")
+STAGE_NAMES = ("census", "cost", "aggregate", "right_winner", "winner")
+
+
+def params(**over) -> _lib.CStereoParams:
+    """tscm_stereo_default_params with the given fields replaced."""
+    p = _lib.CStereoParams()
+    _lib.lib().tscm_stereo_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in PARAM_NAMES:
+            raise TypeError(f"unknown stereo parameter {k!r}: one of {', '.join(PARAM_NAMES)}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _gray(img) -> np.ndarray:
+    a = np.asarray(img)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError("stereo images are 2-D uint8 arrays")
+    if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def _pair(left, right):
+    left, right = _gray(left), _gray(right)
+    if left.shape != right.shape:
+        raise ValueError("left and right images differ in shape")
+    if left.strides[0] != right.strides[0]:
+        left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    return left, right
+
+
+def match(left, right, device: int = 0, out: np.ndarray | None = None, with_seconds: bool = False, **over):
+    """tscm_stereo_match -> int16 [h, w]: 16 * disparity, invalid pixels 16 * (min_disparity - 1).  Rows of `left` / `right`
+    may be padded (a view of a wider array); `out` may be such a view too, and its padding keeps its values."""
+    left, right = _pair(left, right)
+    h, w = left.shape
+    p = params(**over)
+    if out is None:
+        out = np.zeros((h, w), dtype=np.int16)
+    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
+        raise ValueError("out must be an int16 array (or row-padded view) of the images' shape")
+    ub = C.POINTER(C.c_ubyte)
+    sec = C.c_double(0.0)
+    _lib.check(_lib.lib().tscm_stereo_match(left.ctypes.data_as(ub), right.ctypes.data_as(ub), w, h, left.strides[0] if h else w, C.byref(p), device,
+                                            out.ctypes.data_as(C.POINTER(C.c_short)), out.strides[0] // 2 if h else w, C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
+
+
+def stages(left, right, device: int = 0, **over) -> dict:
+    """tscm_stereo_stages -> census_left / census_right uint64 [h, w], cost uint8 [h, w, D], aggregated uint16 [h, w, D]."""
+    left, right = _pair(left, right)
+    h, w = left.shape
+    p = params(**over)
+    D = max(int(p.num_disparities), 0)
+    cl, cr = np.zeros((h, w), dtype=np.uint64), np.zeros((h, w), dtype=np.uint64)
+    cost, agg = np.zeros((h, w, D), dtype=np.uint8), np.zeros((h, w, D), dtype=np.uint16)
+    ub, ull = C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong)
+    _lib.check(_lib.lib().tscm_stereo_stages(left.ctypes.data_as(ub), right.ctypes.data_as(ub), w, h, left.strides[0] if h else w, C.byref(p), device,
+                                             cl.ctypes.data_as(ull), cr.ctypes.data_as(ull), cost.ctypes.data_as(ub), _lib.ushort_ptr(agg)))
+    return dict(census_left=cl, census_right=cr, cost=cost, aggregated=agg)
+
+
+def stage_times() -> dict:
+    """Device seconds of this thread's last match / stages call by stage (tscm_stereo_stage_times)."""
+    t = np.zeros(5)
+    _lib.check(_lib.lib().tscm_stereo_stage_times(_lib.dptr(t)))
+    return dict(zip(STAGE_NAMES, t.tolist()))
+
+
+def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0):
+    """tscm_stereo_points: the disparity map of the left image of a PERSPECTIVE or LONGLAT pair (desc = its MapDesc) ->
+    (points [h, w, 3] fp64 in the pair frame of the left camera, valid [h, w] bool); invalid points are NaN."""
+    disp = np.asarray(disp)
+    if disp.ndim != 2 or disp.dtype != np.int16:
+        raise ValueError("a disparity map is a 2-D int16 array")
+    if disp.strides[1] != 2 or disp.strides[0] % 2 or disp.strides[0] < 2 * disp.shape[1]:
+        disp = np.ascontiguousarray(disp)
+    h, w = disp.shape
+    pts, valid = np.zeros((h, w, 3)), np.zeros((h, w), dtype=np.uint8)
+    _lib.check(_lib.lib().tscm_stereo_points(disp.ctypes.data_as(C.POINTER(C.c_short)), w, h, disp.strides[0] // 2 if h else w, int(min_disparity),
+                                             _maps._c_descs([desc]), _maps.projection_kind(desc.projection), float(baseline), device, _lib.dptr(pts),
+                                             valid.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return pts, valid.astype(bool)
+
+
+def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat", width: int = 640, height: int = 320, fov_x: float = np.pi,
+               fov_y: float = np.pi / 2, device: int = 0, matcher=None, **over):
+    """Two grey fisheye images of cameras a and b of a calibrated rig -> (points [height, width, 3] in the pair frame of
+    camera a, valid [height, width], R_pair).  R_pair = rectify_pair_rotation(t_a, t_b) turns pair-frame vectors into the
+    rig frame: P_rig = R_pair @ P + t_a.  Camera a is the left image: b lies at +|t_b - t_a| on the pair frame's x-axis.
+    `matcher` replaces match (same signature without device; for comparisons with a reference matcher)."""
+    kind = _maps.projection_kind(projection)
+    if kind not in (_lib.PROJ_PERSPECTIVE, _lib.PROJ_LONGLAT):
+        raise ValueError("pair_depth needs rows that are epipolar lines: 'longlat' or 'perspective'")
+    if kind == _lib.PROJ_PERSPECTIVE and fov_x >= np.pi:
+        fov_x = np.pi / 2
+    descs = _maps.rectify_pair_descs(intr_a, Twc_a, intr_b, Twc_b, kind, width, height, fov_x, fov_y)
+    rect = []
+    for img, d in zip((img_a, img_b), descs):
+        mx, my, _ = _maps.build_maps([d], device=device)
+        rect.append(_maps.remap(_gray(img), mx.reshape(height, width), my.reshape(height, width), device=device))
+    disp = matcher(rect[0], rect[1], **over) if matcher is not None else match(rect[0], rect[1], device=device, **over)
+    Ta, Tb = np.asarray(Twc_a, dtype=np.float64).reshape(3, 4), np.asarray(Twc_b, dtype=np.float64).reshape(3, 4)
+    baseline = float(np.linalg.norm(Tb[:, 3] - Ta[:, 3]))
+    pts, valid = points(disp, descs[0], baseline, min_disparity=int(over.get("min_disparity", 0)), device=device)
+    return pts, valid, _maps.rectify_pair_rotation(Ta[:, 3], Tb[:, 3])
