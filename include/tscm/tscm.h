@@ -781,6 +781,80 @@ int tscm_stereo_points(const short *disparity, int width, int height, int disp_s
                        const tscm_map_desc *left_map, int projection, double baseline, int device_index,
                        double *points /* [h*w*3] */, unsigned char *valid /* [h*w] */);
 
+/* ------------------------------------------------------------------ panorama of a calibrated rig
+ * What the tables of panorama_descs (one EQUIRECT or CYLINDRICAL table per camera, all in the rig frame) are for: the
+ * stitched image.  A handle keeps everything that does not depend on a frame on the device -- the sample positions, the
+ * alphas, the seam labels, the mask pyramids -- so a frame costs its upload, the kernels and the download of the panorama.
+ * Every step up to the output bytes is integer arithmetic, defined here operation by operation so that a host restatement
+ * gives the same bits (tests/pano_ref.py).  n = n_cameras, C = channels, (i, j) = output row, column.
+ *   sample     v_k[c] = the arithmetic of the remap entry point above on image k: sx = round(32 mapx), ix = sat16(sx >> 5),
+ *              fx = sx & 31 (y alike), weights 32 (32 - fx)(32 - fy), 32 fx (32 - fy), 32 (32 - fx) fy, 32 fx fy with 32768
+ *              replaced by 32767 and the last weight by 1, (acc + 2^14) >> 15, taps outside the image 0.
+ *              a_k = the same arithmetic on weight image k (one channel); a NULL weight is a constant 255 image, whose border
+ *              taps still ramp a_k to 0, so the (-1, -1) entries of check_w2 give a_k = 0 without a special case.
+ *              With a gain g (Q8): v_k[c] = min(255, (v_k[c] g + 128) >> 8).
+ *   label      the lowest k whose a_k is maximal, 255 when that maximum is 0.   coverage = the number of k with a_k > 0.
+ *   SEAM       out = v_label, 0 without a label.
+ *   FEATHER    A = sum_k a_k:  out[c] = A ? (sum_k a_k v_k[c] + (A >> 1)) / A : 0.
+ *   MULTIBAND  L = levels; pano_w and pano_h are multiples of 2^L.  Per camera G^0 = v_k (int16), M^0 = 255 where
+ *              label == k, else 0.  With taps t = [1, 4, 6, 4, 1], rows clamped (cy) and columns wrapped when wrap_x is set,
+ *              else clamped (cx), all shifts arithmetic:
+ *                reduce  R(x)(i, j) = (sum_a sum_b t_a t_b x(cy(2i + a - 2), cx(2j + b - 2)) + 128) >> 8
+ *                expand  E(x)(i, j) = (sum over a, b in -2..2 with i + a and j + b both even of
+ *                                      t_a t_b x(cy((i + a) / 2), cx((j + b) / 2)) + 32) >> 6        (x on the half-size grid)
+ *              G^(l+1) = R(G^l), M^(l+1) = R(M^l);  Lap^l = G^l - E(G^(l+1)) for l < L, Lap^L = G^L.
+ *              Per level, W = sum_k M_k^l:  B^l[c] = W ? floor((sum_k M_k^l Lap_k^l[c] + (W >> 1)) / W) : 0 -- the division
+ *              rounds towards minus infinity.  Collapse R^L = B^L, R^l = B^l + E(R^(l+1)); out = clamp(R^0, 0, 255), and 0
+ *              where coverage == 0.  This is OpenCV's multi-band blender, its known weakness included: at the coarse levels
+ *              black leaks in within about 2^(L+1) pixels of the edge of a camera's coverage.
+ *              With one camera, a NULL weight and every sample inside the image the result is the remapped image, byte for
+ *              byte: floor((M x + (M >> 1)) / M) = x.
+ *   overlap    lum = v before any gain (C = 1), or its BGR2GRAY value (b 1868 + g 9617 + r 4899 + 2^13) >> 14 (C = 3);
+ *              count[a][b] = the number of pixels with a_a > 0 and a_b > 0, sum[a][b] = the sum of lum_a over them; the
+ *              diagonal is camera a's own coverage.  Integer sums: the result does not depend on the order.
+ * Pyramids of the stage outputs: levels 0..L one after the other, level l a [pano_h >> l][pano_w >> l] plane, S elements in
+ * all; mask_pyramid [n][S] (uint8), lap_pyramid [n][C][S] and blend_pyramid [C][S] (int16, B^l before the collapse);
+ * sampled [n][pano_h][pano_w][C] (after the gain), alpha [n][pano_h][pano_w], label [pano_h][pano_w].
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a required pointer that is NULL,
+ * n_cameras outside 1..16, channels other than 1 or 3, an unknown mode, levels outside 1..6 in MULTIBAND, pano_w or pano_h
+ * below 1 or (MULTIBAND) no multiple of 2^levels, a struct_size other than sizeof(tscm_panorama_params), stride <
+ * width * channels, dst_stride < pano_w * channels, a gain outside 1..4095, a source image with a side below 1 or above 32767,
+ * a pyramid output of the stages call when the mode is not MULTIBAND.  device_index: as `device` elsewhere, TSCM_E_NO_DEVICE
+ * outside [0, tscm_device_count()), after the argument checks.  Bytes of dst between pano_w * channels and dst_stride keep
+ * the caller's values.  seconds_kernel (may be NULL): device time of the frame's kernels (HIP events), without the copies.
+ * A handle serves one thread at a time. */
+enum { TSCM_PANO_SEAM = 0, TSCM_PANO_FEATHER = 1, TSCM_PANO_MULTIBAND = 2 };
+
+typedef struct tscm_panorama_params {
+    int struct_size;        /* sizeof(tscm_panorama_params)                                     */
+    int mode;               /* TSCM_PANO_*                                                      */
+    int levels;             /* MULTIBAND: 1..6, otherwise ignored                               */
+    int wrap_x;             /* 1: column -1 is column pano_w - 1 (full 360 degree tables)       */
+} tscm_panorama_params;
+void tscm_panorama_default_params(tscm_panorama_params *p);   /* MULTIBAND, 4, 1 */
+
+typedef struct tscm_panorama tscm_panorama;   /* opaque: tables, alphas, seam labels, mask pyramids on the device */
+
+int tscm_panorama_create(int n_cameras, int width, int height, int channels /* the source images, all alike */,
+                         const unsigned char *const *weights /* [n] of [height][width]; NULL or a NULL entry = all 255 */,
+                         const float *mapx, const float *mapy /* [n][pano_h][pano_w] */, int pano_w, int pano_h,
+                         const tscm_panorama_params *params, int device_index, tscm_panorama **out);
+
+int tscm_panorama_compose(tscm_panorama *p, const unsigned char *const *images /* [n] of [height][stride] */, int stride,
+                          const unsigned short *gain_q8 /* [n], NULL = 256 */,
+                          unsigned char *dst /* [pano_h][dst_stride] */, int dst_stride,
+                          unsigned char *coverage /* [pano_h][pano_w], may be NULL */, double *seconds_kernel);
+
+/* The stages of the same kernels, for parity tests: any output may be NULL. */
+int tscm_panorama_stages(tscm_panorama *p, const unsigned char *const *images, int stride, const unsigned short *gain_q8,
+                         unsigned char *sampled, unsigned char *alpha, unsigned char *label,
+                         unsigned char *mask_pyramid, short *lap_pyramid, short *blend_pyramid);
+
+int tscm_panorama_overlap(tscm_panorama *p, const unsigned char *const *images, int stride,
+                          long long *count /* [n*n] */, long long *sum /* [n*n] */);
+
+void tscm_panorama_destroy(tscm_panorama *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -690,5 +690,121 @@ inline std::vector<Point3d> stereo_points(const std::vector<short> &disparity, S
     return points;
 }
 
+// The panorama of a calibrated rig: one equirect (or cylindrical) table per camera in the rig frame (R = R_cam^T,
+// check_w2 = 1, as maps.panorama_descs builds them), kept on the device with the alphas, seam labels and mask pyramids by a
+// tscm_panorama handle; compose() blends one frame.  intr [9 n], Twc [12 n] (row-major 3x4 [R | t]) as tscm_yaml_read
+// returns them; weights: NULL (all 255) or n images of image_size (entries may be NULL); params == NULL:
+// tscm_panorama_default_params (multi-band, 4 levels).
+class Panorama {
+public:
+    Panorama(int n_cameras, const double *intr, const double *Twc, Size image_size, int channels, Size pano_size, const tscm_panorama_params *params = NULL,
+             const unsigned char *const *weights = NULL, int projection = TSCM_PROJ_EQUIRECT, int device = 0)
+        : n_(n_cameras), channels_(channels), image_(image_size), pano_(pano_size), handle_(NULL)
+    {
+        if (projection != TSCM_PROJ_EQUIRECT && projection != TSCM_PROJ_CYLINDRICAL) throw std::runtime_error("tscm: a panorama is equirect or cylindrical");
+        if (n_cameras < 1 || pano_size.width < 1 || pano_size.height < 1) throw std::runtime_error("tscm: a panorama needs cameras and a size");
+        const double pi = 3.14159265358979323846;
+        const size_t npix = (size_t)pano_.width * pano_.height;
+        std::vector<tscm_map_desc> desc((size_t)n_);
+        std::vector<int> kinds((size_t)n_, projection);
+        for (int k = 0; k < n_; ++k) {
+            tscm_map_desc &d = desc[(size_t)k];
+            d = tscm_map_desc();
+            std::memcpy(d.intr, intr + 9 * k, sizeof(d.intr));
+            const double *T = Twc + 12 * k;
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 3; ++c) d.R[3 * r + c] = T[4 * c + r];           // R_cam^T
+            d.fx = pano_.width / (2.0 * pi);
+            d.fy = projection == TSCM_PROJ_EQUIRECT ? pano_.height / pi : d.fx;
+            d.cx = 0.5 * pano_.width; d.cy = 0.5 * pano_.height;
+            d.width = pano_.width; d.height = pano_.height; d.out_stride = pano_.width;
+            d.out_offset = (long long)k * (long long)npix;
+            d.check_w2 = 1; d.w2 = 0.42399;
+        }
+        std::vector<float> mapx(npix * n_), mapy(npix * n_);
+        check(tscm_build_maps_ex(desc.data(), kinds.data(), n_, device, 1, mapx.data(), mapy.data(), mapx.size(), NULL));
+        tscm_panorama_params p;
+        if (params) p = *params;
+        else tscm_panorama_default_params(&p);
+        check(tscm_panorama_create(n_, image_.width, image_.height, channels_, weights, mapx.data(), mapy.data(), pano_.width, pano_.height, &p, device, &handle_));
+    }
+    ~Panorama() { tscm_panorama_destroy(handle_); }
+
+    // images: n rows-of-`stride`-bytes images (stride 0: image width * channels); gain_q8: NULL or n Q8 gains (exposure_gains)
+    // -> pano_size.height rows of pano_size.width * channels bytes
+    std::vector<unsigned char> compose(const unsigned char *const *images, int stride = 0, const unsigned short *gain_q8 = NULL, double *seconds_kernel = NULL)
+    {
+        const int row = pano_.width * channels_;
+        std::vector<unsigned char> out((size_t)row * pano_.height);
+        check(tscm_panorama_compose(handle_, images, stride ? stride : image_.width * channels_, gain_q8, out.data(), row, NULL, seconds_kernel));
+        return out;
+    }
+    // count, sum [n * n]: pixels that cameras a and b both cover, and camera a's luminance summed over them
+    void overlap(const unsigned char *const *images, int stride, std::vector<long long> &count, std::vector<long long> &sum)
+    {
+        count.assign((size_t)n_ * n_, 0); sum.assign((size_t)n_ * n_, 0);
+        check(tscm_panorama_overlap(handle_, images, stride ? stride : image_.width * channels_, count.data(), sum.data()));
+    }
+    int cameras() const { return n_; }
+    Size size() const { return pano_; }
+
+private:
+    Panorama(const Panorama &);
+    Panorama &operator=(const Panorama &);
+    int n_, channels_;
+    Size image_, pano_;
+    tscm_panorama *handle_;
+};
+
+// Gain compensation of Brown & Lowe (OpenCV's GainCompensator) from Panorama::overlap: minimises
+// sum_ij N_ij [(g_i I_ij - g_j I_ji)^2 / sigma_n^2 + (1 - g_i)^2 / sigma_g^2], N = count, I = sum / count; the n x n system
+// is solved in fp64 by Gaussian elimination with partial pivoting.  Returns round(256 g) clipped to 64..1024.
+inline std::vector<unsigned short> exposure_gains(int n, const std::vector<long long> &count, const std::vector<long long> &sum, double sigma_n = 10.0,
+                                                  double sigma_g = 0.1)
+{
+    if (n < 1 || count.size() != (size_t)n * n || sum.size() != (size_t)n * n) throw std::runtime_error("tscm: count and sum are n x n");
+    std::vector<unsigned short> out((size_t)n, 256);
+    if (n == 1) return out;
+    const double alpha = 1.0 / (sigma_n * sigma_n), beta = 1.0 / (sigma_g * sigma_g);
+    std::vector<double> A((size_t)n * n, 0.0), b((size_t)n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const double N = (double)count[(size_t)i * n + j], Nji = (double)count[(size_t)j * n + i];
+            const double Iij = N > 0 ? (double)sum[(size_t)i * n + j] / N : 0.0, Iji = Nji > 0 ? (double)sum[(size_t)j * n + i] / Nji : 0.0;
+            b[(size_t)i] += beta * N;
+            A[(size_t)i * n + i] += beta * N;
+            if (j == i) continue;
+            A[(size_t)i * n + i] += 2.0 * alpha * Iij * Iij * N;
+            A[(size_t)i * n + j] -= 2.0 * alpha * Iij * Iji * N;
+        }
+    for (int i = 0; i < n; ++i)
+        if (A[(size_t)i * n + i] == 0.0) { A[(size_t)i * n + i] = 1.0; b[(size_t)i] = 1.0; }       // a camera that covers nothing keeps gain 1
+    for (int c = 0; c < n; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < n; ++r)
+            if (std::fabs(A[(size_t)r * n + c]) > std::fabs(A[(size_t)piv * n + c])) piv = r;
+        if (A[(size_t)piv * n + c] == 0.0) throw std::runtime_error("tscm: singular gain system");
+        if (piv != c) {
+            for (int k = 0; k < n; ++k) std::swap(A[(size_t)c * n + k], A[(size_t)piv * n + k]);
+            std::swap(b[(size_t)c], b[(size_t)piv]);
+        }
+        for (int r = c + 1; r < n; ++r) {
+            const double f = A[(size_t)r * n + c] / A[(size_t)c * n + c];
+            for (int k = c; k < n; ++k) A[(size_t)r * n + k] -= f * A[(size_t)c * n + k];
+            b[(size_t)r] -= f * b[(size_t)c];
+        }
+    }
+    for (int r = n - 1; r >= 0; --r) {
+        double v = b[(size_t)r];
+        for (int k = r + 1; k < n; ++k) v -= A[(size_t)r * n + k] * b[(size_t)k];
+        b[(size_t)r] = v / A[(size_t)r * n + r];
+    }
+    for (int i = 0; i < n; ++i) {
+        const double q = std::floor(256.0 * b[(size_t)i] + 0.5);
+        out[(size_t)i] = (unsigned short)(q < 64.0 ? 64.0 : (q > 1024.0 ? 1024.0 : q));
+    }
+    return out;
+}
+
 }  // namespace tscm
 #endif

@@ -1,0 +1,263 @@
+"""CPU tests of the panorama composer's definition (include/tscm/tscm.h: tscm_panorama_*) on its host restatement
+tests/pano_ref.py: hand-worked cases of every formula, the one-camera identity, the refusals of the C ABI that come before
+any device is touched, the gain compensation, and a quality check of the blends on a four-camera rig without parallax."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import pyoracle as orc
+from tscm_calib_amd import lib, maps, panorama, synth
+from tests import maps_proj_ref as mref
+from tests import pano_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_INVALID, E_NO_DEVICE = -1, -2
+
+
+# ------------------------------------------------------------------------------------------------ hand-worked cases
+def test_reduce_and_expand_of_one_row_by_hand():
+    x = np.array([[0, 16, 32, 48, 64, 80, 96, 112], [0, 16, 32, 48, 64, 80, 96, 112]])
+    # rows clamp, so the vertical taps sum to 16 on equal rows: R = (16 * sum_b t_b x(2j + b - 2) + 128) >> 8
+    # clamp:  j = 0: 16 (0 + 0 + 0 + 64 + 32) = 1536 -> 6;  j = 1: 16 * 16 * 32 -> 32;  j = 2: 64;  j = 3: 16 (64 + 320 + 576 + 448 + 112) -> 95
+    assert R.reduce(x, False).tolist() == [[6, 32, 64, 95]]
+    # wrap:   j = 0: 16 (96 + 4 * 112 + 0 + 64 + 32) = 10240 -> 40;  j = 3: 16 (64 + 320 + 576 + 448 + 0) = 22528 -> 88
+    assert R.reduce(x, True).tolist() == [[40, 32, 64, 88]]
+    c = np.array([[8, 24, 40, 56]])
+    # one coarse row: the vertical taps of an even row are 1 + 6 + 1, of an odd row 4 + 4, on equal (clamped) rows: 8 both times
+    # even j: 8 (x(j/2 - 1) + 6 x(j/2) + x(j/2 + 1));  odd j: 8 * 4 (x((j - 1)/2) + x((j + 1)/2));  + 32, >> 6
+    # clamp: j = 0: 8 (8 + 48 + 24) -> 10;  j = 1: 32 * 32 -> 16;  j = 2: 8 * 192 -> 24;  j = 6: 8 (40 + 336 + 56) -> 54;  j = 7: 32 * 112 -> 56
+    assert R.expand(c, False).tolist() == [[10, 16, 24, 32, 40, 48, 54, 56]] * 2
+    # wrap:  j = 0: 8 (56 + 48 + 24) -> 16;  j = 6: 8 (40 + 336 + 8) -> 48;  j = 7: 32 (56 + 8) -> 32
+    assert R.expand(c, True).tolist() == [[16, 16, 24, 32, 40, 48, 48, 32]] * 2
+
+
+def test_feather_of_two_constant_images_by_hand():
+    v = np.stack([np.full((2, 3, 1), 100), np.full((2, 3, 1), 200)])
+    a = np.stack([np.full((2, 3), 255), np.full((2, 3), 85)])
+    # (255 * 100 + 85 * 200 + 170) / 340 = 42670 / 340 = 125.5 -> 125
+    assert np.all(R.feather(v, a) == 125)
+    a[1, 0, 0] = 0
+    a[0, 0, 1], a[1, 0, 1] = 0, 0
+    out = R.feather(v, a)
+    assert out[0, 0, 0] == 100 and out[0, 1, 0] == 0
+
+
+def test_label_takes_the_lowest_of_equal_alphas():
+    a = np.array([[[0, 7, 7, 3]], [[0, 7, 9, 3]], [[0, 2, 9, 3]]])
+    lab, cov = R.label_coverage(a)
+    assert lab.tolist() == [[255, 0, 1, 0]] and cov.tolist() == [[0, 3, 3, 3]]
+    v = np.arange(12).reshape(3, 1, 4, 1) + 10
+    assert R.seam(v, lab)[0, :, 0].tolist() == [0, 11, 16, 13]
+
+
+def test_blend_divides_towards_minus_infinity():
+    """Two cameras on a 2 x 2 panorama with a checkerboard of labels, one level.  With clamped borders the reduce weighs
+    row / column 0 by 1 + 4 + 6 = 11 and row / column 1 by 4 + 1 = 5, so M^1 = (255 (121 + 25) + 128) >> 8 = 145 for camera 0
+    and (255 * 110 + 128) >> 8 = 110 for camera 1, W = 255.  Camera 1 at a constant -3 has G^1 = (-3 * 256 + 128) >> 8 = -3:
+    B^1 = (110 * -3 + 127) / 255 = -203 / 255, which is -1 rounded towards minus infinity and 0 when truncated."""
+    lab = np.array([[0, 1], [1, 0]], dtype=np.uint8)
+    cov = np.ones((2, 2), dtype=np.uint8)
+    v = np.zeros((2, 2, 2, 1), dtype=np.int64)
+    v[1] = -3
+    res = R.multiband(v, lab, cov, 1, False)
+    assert res["mask"][1][:, 0, 0].tolist() == [145, 110]
+    assert res["lap"][1][:, 0, 0, 0].tolist() == [0, -3]
+    assert res["blend"][1][0, 0, 0] == -1 and int(-203 / 255) == 0
+
+
+def test_gain_saturates_at_255():
+    v = np.array([0, 1, 100, 200, 255])
+    assert R.apply_gain(v, 256).tolist() == [0, 1, 100, 200, 255]
+    assert R.apply_gain(v, 512).tolist() == [0, 2, 200, 255, 255]
+    assert R.apply_gain(v, 4095).tolist() == [0, 16, 255, 255, 255]          # (4095 + 128) >> 8 = 16
+    assert R.apply_gain(v, 1).tolist() == [0, 0, 0, 1, 1]                    # (200 + 128) >> 8 = 1
+
+
+@pytest.mark.parametrize("levels", [1, 2, 3])
+def test_one_camera_multiband_is_the_remapped_image(levels):
+    rng = np.random.default_rng(levels)
+    img = rng.integers(0, 256, (40, 48, 3)).astype(np.uint8)
+    mx = rng.uniform(0.0, 46.9, (1, 16, 24)).astype(np.float32)
+    my = rng.uniform(0.0, 38.9, (1, 16, 24)).astype(np.float32)
+    for wrap in (False, True):
+        res = R.compose([img], None, mx, my, R.MULTIBAND, levels, wrap)
+        assert res["coverage"].min() == 1 and res["alpha"].min() == 255
+        assert np.array_equal(res["out"], orc.remap(img, mx[0], my[0]))
+
+
+# ------------------------------------------------------------------------------------------------ refusals of the C ABI
+def _create(n=2, w=16, h=12, ch=1, pw=32, ph=16, mode=lib.PANO_MULTIBAND, levels=2, device=0, struct_size=None, mapx=True, mapy=True, params=True, out=True,
+            weights=None):
+    L = lib.lib()
+    p = lib.CPanoramaParams()
+    L.tscm_panorama_default_params(C.byref(p))
+    assert (p.struct_size, p.mode, p.levels, p.wrap_x) == (16, lib.PANO_MULTIBAND, 4, 1)
+    p.mode, p.levels = mode, levels
+    if struct_size is not None:
+        p.struct_size = struct_size
+    tab = np.zeros(max(n, 1) * max(pw, 1) * max(ph, 1), np.float32)
+    fp = tab.ctypes.data_as(C.POINTER(C.c_float))
+    hdl = C.c_void_p()
+    rc = L.tscm_panorama_create(n, w, h, ch, weights, fp if mapx else None, fp if mapy else None, pw, ph, C.byref(p) if params else None, device,
+                                C.byref(hdl) if out else None)
+    assert hdl.value is None
+    return rc, L.tscm_last_error()
+
+
+@pytest.mark.parametrize("kw,text", [
+    (dict(out=False), b"out"), (dict(mapx=False), b"mapx"), (dict(mapy=False), b"mapy"), (dict(params=False), b"params"),
+    (dict(n=0), b"n_cameras"), (dict(n=17), b"n_cameras"), (dict(ch=2), b"channels"), (dict(ch=4), b"channels"),
+    (dict(mode=3), b"mode"), (dict(mode=-1), b"mode"), (dict(levels=0), b"levels"), (dict(levels=7), b"levels"),
+    (dict(pw=0), b"pano_w"), (dict(ph=0), b"pano_h"), (dict(pw=30), b"pano_w"), (dict(ph=18), b"pano_h"), (dict(pw=48, ph=24, levels=4), b"pano_h"),
+    (dict(struct_size=12), b"struct_size"), (dict(struct_size=20), b"struct_size"),
+    (dict(w=32768), b"width"), (dict(h=32768), b"height"), (dict(w=0), b"width"),
+])
+def test_create_refuses_before_any_device_is_touched(kw, text):
+    rc, msg = _create(device=99, **kw)               # the bad device index would answer TSCM_E_NO_DEVICE: the arguments come first
+    assert rc == E_INVALID and text in msg, (rc, msg)
+
+
+def test_levels_and_multiples_matter_only_in_multiband():
+    for mode in (lib.PANO_SEAM, lib.PANO_FEATHER):
+        rc, msg = _create(device=99, mode=mode, levels=0, pw=31, ph=17)
+        assert rc == E_NO_DEVICE, msg
+
+
+def test_device_index_out_of_range_is_no_device():
+    rc, msg = _create(device=99)
+    assert rc == E_NO_DEVICE and b"tscm_panorama_create" in msg
+    rc, msg = _create(device=-1)
+    assert rc == E_NO_DEVICE
+
+
+def test_frame_calls_refuse_a_null_handle():
+    L = lib.lib()
+    img = np.zeros((12, 16), np.uint8)
+    ptrs = (C.c_void_p * 1)(img.ctypes.data)
+    dst = np.zeros((16, 32), np.uint8).ctypes.data_as(C.POINTER(C.c_ubyte))
+    cnt = np.zeros(4, np.int64).ctypes.data_as(C.POINTER(C.c_longlong))
+    assert L.tscm_panorama_compose(None, ptrs, 16, None, dst, 32, None, None) == E_INVALID and b"p is NULL" in L.tscm_last_error()
+    assert L.tscm_panorama_stages(None, ptrs, 16, None, None, None, None, None, None, None) == E_INVALID
+    assert L.tscm_panorama_overlap(None, ptrs, 16, cnt, cnt) == E_INVALID
+    L.tscm_panorama_destroy(None)
+
+
+def test_composer_checks_its_arguments_on_the_host():
+    with pytest.raises(ValueError):
+        panorama.params("median")
+    with pytest.raises(ValueError):
+        panorama.Composer.from_tables(np.zeros((2, 8, 8), np.float32), np.zeros((2, 8, 4), np.float32), (16, 12))
+    with pytest.raises(ValueError):
+        panorama.Composer.from_tables(np.zeros((2, 8, 8), np.float32), np.zeros((2, 8, 8), np.float32), (16, 12), weights=[None])
+    with pytest.raises(lib.TscmError) as e:
+        panorama.Composer.from_tables(np.zeros((2, 8, 8), np.float32), np.zeros((2, 8, 8), np.float32), (16, 12), levels=4)
+    assert e.value.code == E_INVALID
+
+
+# ------------------------------------------------------------------------------------------------ gain compensation
+def test_exposure_gains_of_two_cameras_by_hand():
+    N = np.array([[1000, 400], [400, 900]])
+    S = np.array([[1000 * 90, 400 * 100], [400 * 80, 900 * 70]])
+    a, b = 1.0 / 100.0, 1.0 / 0.01                     # 1 / sigma_n^2, 1 / sigma_g^2
+    A00 = b * 1400 + 2 * a * 100 * 100 * 400
+    A11 = b * 1300 + 2 * a * 80 * 80 * 400
+    A01 = -2 * a * 100 * 80 * 400
+    b0, b1 = b * 1400, b * 1300
+    det = A00 * A11 - A01 * A01
+    g0, g1 = (b0 * A11 - A01 * b1) / det, (A00 * b1 - A01 * b0) / det
+    got = panorama.exposure_gains(N, S)
+    assert got.dtype == np.uint16 and got.tolist() == [int(np.rint(256 * g0)), int(np.rint(256 * g1))]
+    assert g0 < 1.0 < g1
+
+
+def test_exposure_gains_of_one_camera_and_the_clip():
+    assert panorama.exposure_gains(np.array([[500]]), np.array([[500 * 77]])).tolist() == [256]
+    # nearly no prior and a pair 40 : 1 apart: the error term alone is smallest at g = 0, so the bright camera's gain falls
+    # below 1/4 and is clipped
+    N = np.array([[100, 100], [100, 100]])
+    S = np.array([[100 * 200, 100 * 200], [100 * 5, 100 * 5]])
+    g = panorama.exposure_gains(N, S, sigma_n=1.0, sigma_g=100.0)
+    assert g[0] == 64 and 64 <= g[1] <= 1024
+
+
+def test_exposure_gains_recover_a_darker_camera():
+    """Image b = 0.8 x image a on their overlap: g_b / g_a within 2 % of 1.25.  The prior (1 - g)^2 / sigma_g^2 pulls both
+    gains towards 1 and so the ratio below 1.25 by design; with the default sigma_g = 0.1 and grey levels near 200 that pull
+    alone is about 3 %, so the check is made with the prior weakened to sigma_g = 1."""
+    rng = np.random.default_rng(3)
+    a = rng.integers(150, 251, 5000).astype(np.int64)
+    b = (a * 4 + 2) // 5
+    N = np.array([[9000, 5000], [5000, 8000]])
+    S = np.array([[9000 * 190, a.sum()], [b.sum(), 8000 * 150]])
+    g = panorama.exposure_gains(N, S, sigma_g=1.0).astype(np.float64)
+    assert abs(g[1] / g[0] / 1.25 - 1.0) < 0.02, g
+
+
+# ------------------------------------------------------------------------------------------------ quality on a rig without parallax
+PW, PH = 256, 128
+
+
+def _texture(rays):
+    """A smooth grey texture indexed by direction: 128 + a few low harmonics of the rig-frame unit ray, within 40..216."""
+    x, y, z = rays[..., 0], rays[..., 1], rays[..., 2]
+    return 128.0 + 40.0 * np.sin(3.0 * x + 1.0) * np.cos(2.0 * z) + 30.0 * np.sin(2.5 * y - 0.5) + 18.0 * x * z
+
+
+@functools.lru_cache(maxsize=None)
+def _rig_scene():
+    w, h = int(synth.IMG_W), int(synth.IMG_H)
+    Twc = synth.CALIB_TWC.copy().reshape(4, 3, 4)
+    Twc[:, :, 3] = 0.0                                                    # co-centred: no parallax
+    descs = maps.panorama_descs(synth.CALIB_INTR, Twc, PW, PH)
+    tabs = [mref.build_map_ref(d) for d in descs]
+    mx, my = np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs])
+    v, u = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    images, weights = [], []
+    for k in range(4):
+        rays = synth.unproject_pixels_np(synth.CALIB_INTR[k], u, v)        # camera frame
+        weights.append(panorama.weights_from_rays(rays, np.radians(100.0)))
+        world = rays @ Twc[k, :, :3].T                                     # rig frame
+        images.append(np.clip(np.rint(np.nan_to_num(_texture(world), nan=0.0)), 0, 255).astype(np.uint8))
+    # the texture along the panorama's own rays
+    i, j = np.meshgrid(np.arange(PH), np.arange(PW), indexing="ij")
+    truth = _texture(mref.ray(lib.PROJ_EQUIRECT, (j - descs[0].cx) / descs[0].fx, (i - descs[0].cy) / descs[0].fy))
+    return images, weights, mx, my, truth
+
+
+def _seam_step(out, lab):
+    """Mean absolute difference across horizontally adjacent pixels whose labels differ (both labelled)."""
+    o = out[..., 0].astype(np.int64)
+    edge = (lab[:, 1:] != lab[:, :-1]) & (lab[:, 1:] != 255) & (lab[:, :-1] != 255)
+    assert edge.sum() > 50
+    return float(np.abs(o[:, 1:] - o[:, :-1])[edge].mean())
+
+
+def test_multiband_and_gains_shrink_the_step_at_the_seams():
+    images, weights, mx, my, truth = _rig_scene()
+    dark = list(images)
+    dark[1] = ((images[1].astype(np.int64) * 4 + 2) // 5).astype(np.uint8)          # camera 1 at 0.8 x
+    seam = R.compose(dark, weights, mx, my, R.SEAM)
+    band = R.compose(dark, weights, mx, my, R.MULTIBAND, 4, True)
+    gains = panorama.exposure_gains(seam["count"], seam["sum"])
+    comp = R.compose(dark, weights, mx, my, R.MULTIBAND, 4, True, gains)
+    lab, cov = seam["label"], seam["coverage"]
+    rows = slice(PH // 2 - PH // 8, PH // 2 + PH // 8)                                # +- 22.5 degrees about the horizon
+    assert cov[rows].min() >= 1
+    steps = [_seam_step(r["out"], lab) for r in (seam, band, comp)]
+    print("seam steps (SEAM, MULTIBAND, MULTIBAND + gains):", steps)
+    assert steps[0] > steps[1] > steps[2], steps
+    # against the texture itself, with every camera at its true exposure
+    clean = R.compose(images, weights, mx, my, R.MULTIBAND, 4, True)
+    err = float(np.abs(clean["out"][rows, :, 0].astype(np.float64) - truth[rows]).mean())
+    print("mean |MULTIBAND - texture| on the horizon band:", err)
+    assert err <= 1.25 * 0.2536, err      # the restatement's own 0.2535 plus 25 %: more means the definition changed
+
+
+def test_panorama_demo_compiles_and_links(tmp_path):
+    csrc = os.path.join(ROOT, "tscm_calib_amd", "csrc")
+    subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "panorama_demo.cpp"),
+                           "-L", csrc, "-ltscm_hip", "-Wl,-rpath," + csrc, "-o", str(tmp_path / "a.out")])

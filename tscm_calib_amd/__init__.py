@@ -7,8 +7,10 @@ Only what the reprojection-error LM hot path of imuncle/TSCM_Calib and its immed
   rig.py       rig initialisation (MultiCalib constructor), focal estimate, [r1 r2 t] -> pose
   maps.py      remap tables (undistort, undistort_chessboard, epipolar rectification)
   stereo.py    census + semi-global matching on a rectified pair, points, pair_depth
+  panorama.py  the rig's panorama: Composer (seam / feather / multi-band), radial_weights, exposure_gains
   calib_io.py  calibration YAML in the cv::FileStorage layout
   problem.py   problem container, frame sharding
   synth.py     deterministic synthetic chessboard observations (BASELINE.json configs)
 """
 from .problem import Problem, shard_frames  # noqa: F401
+from . import panorama  # noqa: F401,E402

@@ -34,6 +34,9 @@ LOSS_KINDS = {None: LOSS_NONE, "none": LOSS_NONE, "huber": LOSS_HUBER, "soft_l1"
 PROJ_PERSPECTIVE, PROJ_LONGLAT, PROJ_CYLINDRICAL, PROJ_STEREOGRAPHIC, PROJ_EQUIRECT = 0, 1, 2, 3, 4
 PROJ_KINDS = {"perspective": PROJ_PERSPECTIVE, "longlat": PROJ_LONGLAT, "cylindrical": PROJ_CYLINDRICAL,
               "stereographic": PROJ_STEREOGRAPHIC, "equirect": PROJ_EQUIRECT}
+# panorama blend modes (tscm.h: TSCM_PANO_*)
+PANO_SEAM, PANO_FEATHER, PANO_MULTIBAND = 0, 1, 2
+PANO_MODES = {"seam": PANO_SEAM, "feather": PANO_FEATHER, "multiband": PANO_MULTIBAND}
 # held intrinsics (tscm.h: TSCM_FIX_*): bit k holds intrinsic k of the 9-vector
 INTRINSIC_NAMES = ("fx", "fy", "cx", "cy", "xi", "lambda", "alpha", "b", "c")
 FIX = {name: 1 << k for k, name in enumerate(INTRINSIC_NAMES)}
@@ -123,6 +126,11 @@ class CStereoParams(C.Structure):
                 ("paths", C.c_int), ("uniqueness_ratio", C.c_int), ("disp12_max_diff", C.c_int)]
 
 
+class CPanoramaParams(C.Structure):
+    """tscm_panorama_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -147,6 +155,7 @@ EXPORTS = [
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
+    "tscm_panorama_default_params", "tscm_panorama_create", "tscm_panorama_compose", "tscm_panorama_stages", "tscm_panorama_overlap", "tscm_panorama_destroy",
 ]
 
 
@@ -241,6 +250,15 @@ def lib():
     L.tscm_stereo_stage_times.argtypes = [dp]
     L.tscm_stereo_points.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CMapDesc), C.c_int, C.c_double, C.c_int,
                                      dp, ubp]
+    fp, shp, llp, vpp = C.POINTER(C.c_float), C.POINTER(C.c_short), C.POINTER(C.c_longlong), C.POINTER(vp)
+    L.tscm_panorama_default_params.argtypes = [C.POINTER(CPanoramaParams)]
+    L.tscm_panorama_default_params.restype = None
+    L.tscm_panorama_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vpp, fp, fp, C.c_int, C.c_int, C.POINTER(CPanoramaParams), C.c_int, vpp]
+    L.tscm_panorama_compose.argtypes = [vp, vpp, C.c_int, usp, ubp, C.c_int, ubp, dp]
+    L.tscm_panorama_stages.argtypes = [vp, vpp, C.c_int, usp, ubp, ubp, ubp, ubp, shp, shp]
+    L.tscm_panorama_overlap.argtypes = [vp, vpp, C.c_int, llp, llp]
+    L.tscm_panorama_destroy.argtypes = [vp]
+    L.tscm_panorama_destroy.restype = None
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]
     L.tscm_poses_from_r1r2t.argtypes = [dp, C.c_void_p, C.c_int, dp]
     L.tscm_estimate_extrinsic.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip]
