@@ -1,6 +1,6 @@
 // tscm_eval_f32.h -- mixed-precision variant of k_eval_gram (north_star's "fp32 Jacobian" tier).
 //
-// Same data flow, tile columns, record layout and fp64 epilogue as k_eval_gram (tscm_kernels.h);
+// Same data flow, tile columns, record layout and fp64 epilogue as k_eval_gram (tscm_eval_gram16.h);
 // what changes is the arithmetic type of the Jacobian:
 //   fp64  board -> camera transform, triple-sphere projection, residual and the cost r^T r
 //   fp32  every derivative (the 2 x 15 tile row of a corner), computed two at a time (u-row, v-row)
@@ -29,7 +29,7 @@
 //   * the u- and v-row MFMAs alternate: two independent accumulators, so the 40-cycle dependent latency of the
 //     instruction (32 to issue) is not paid 2 K times per view.
 // Measured (round 4, config 4, same box, alternating): 46.0 -> 43.5 us per launch; five workgroups per CU (86 VGPRs and
-// the smaller tile allow it: make variant EXTRA="-DTSCM_F32_WGS=5 -DTSCM_EVAL_WAVES=5") give nothing -- the SIMD's one
+// the smaller tile allow it: launch bound 5, chunk tables for five waves per SIMD) give nothing -- the SIMD's one
 // pipe is busy, not waiting.
 #pragma once
 // (included from tscm_kernels.h inside namespace tscm)
@@ -53,15 +53,11 @@ __host__ __device__ inline int eval_f32_lds_doubles(int n_points, int ks)
     return 4 * (tile > 512 ? tile : 512) + 2 * n_points;
 }
 
-#ifndef TSCM_F32_WGS
-#define TSCM_F32_WGS 4
-#endif
-
 // KS: k-steps of a pass; MULTI: boards of more than 56 corners, P.g4_per corners per pass (the pass plan of k_eval_gram4: g4_plan);
 // ROBUST: a loss L (robust_rho) -- w = sqrt(rho') from the fp64 residual scales the corner's fp32 entries and, in fp64, its
 // residual before the conversion; the cost entry is the fp64 sum of rho (where r^T r sits otherwise).  See k_eval_gram4.
 template <int KS, bool MULTI, bool ROBUST = false>
-__global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem P, DevState S, int cand, LossArg L)
+__global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState S, int cand, LossArg L)
 {
     static_assert(KS >= 1 && KS <= kG4MaxKS, "a pass holds at most 56 rows");
     // the control block is read together with the static chunk tables (one memory round trip, not two);
@@ -143,9 +139,7 @@ __global__ __launch_bounds__(256, TSCM_F32_WGS) void k_eval_gram_f32(DevProblem 
         const int off = off_next;
         off_next = off + cnt;
         wave_lds_fence();                       // previous view's epilogue has finished with LDS
-#if TSCM_PRIO
         set_prio(3 - min(3, 8 * (view - vb) / max(1, ve - vb) % 4));      // priority by progress: see k_eval_gram
-#endif
         const cptr4 cst = (cptr4)(S.vconst + (size_t)kVStride * view);                 // this view's constants, doubles
         const fptr4 cs = (fptr4)(S.vconst + (size_t)kVStride * view + kVFloatOff);     // ... and floats
         d4 accU = { 0.0, 0.0, 0.0, 0.0 }, accV = { 0.0, 0.0, 0.0, 0.0 };

@@ -1,6 +1,6 @@
 // tscm_eval_gram4.h -- the dominant kernel with the Gram contraction on v_mfma_f64_4x4x4_4b_f64 (round 3).
 //
-// Same inputs, same outputs, same bits as k_eval_gram<58> (tscm_kernels.h); what changes is the matrix instruction.
+// Same inputs, same outputs, same bits as k_eval_gram<58> (tscm_eval_gram16.h); what changes is the matrix instruction.
 // Measured on gfx950 (tools/ubench_mfma64.hip, four waves per SIMD): v_mfma_f64_16x16x4_f64 occupies the fp64 pipe for
 // ~90 clocks (2048 flop: 23 flop/clock/SIMD -- the 49 TFLOP/s ceiling bench.py reports), v_mfma_f64_4x4x4_4b_f64 for
 // ~12.5 clocks (4 blocks of 4x4x4 = 512 flop: 41 flop/clock/SIMD), and the 16x16 tile computes every off-diagonal
@@ -237,7 +237,6 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         const int off = off_next;               // (MULTI: the later passes' observations)
         off_next += cnt;
         wave_lds_fence();                       // the previous view's MFMA phase has finished with the tile
-#if TSCM_PRIO
         // priority by progress: see k_eval_gram.  Short chunks (round 5): the last three views step down 3 | 2 | 1 (geometry), 0 (the
         // rest of the last view), so that the four waves of a SIMD -- served oldest first among equals -- enter the last
         // equal-priority stretch half a view apart, not a view and a quarter: -0.4 us at 10 views per wave; at 40 the stretch is a
@@ -245,7 +244,6 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         const int left = ve - 1 - view;
         const bool tail_steps = left <= 2 && ve - vb <= 16;
         set_prio(tail_steps ? left + 1 : 3 - min(3, 8 * (view - vb) / max(1, ve - vb) % 4));
-#endif
 #ifdef TSCM_WAVE_TIMELINE
         if (tl_on && tl_nv < kTlViews) g_tlv[(size_t)(4 + kTlViews) * chunk + 4 + tl_nv] = wall_clock64();
         ++tl_nv;
@@ -295,9 +293,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         }
         prev_nv = MULTI ? min(per, max(cnt - pb, 0)) : cnt;
         wave_lds_fence();
-#if TSCM_PRIO
         if (tail_steps && left == 0) set_prio(0);
-#endif
         TL_STAMP(ts1);
 #ifdef TSCM_WAVE_TIMELINE
         if (tl_nv == 1) tl_w[1] = wall_clock64();

@@ -379,21 +379,14 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     // the default Gram kernel: k_eval_gram4 instantiated for this board's pass plan (KS k-steps per pass, ceil(n / 56) passes per view)
     const G4Plan g4 = g4_plan(p->n_points);
     const EvalKernel eval4 = g4_kernel(g4.ks, g4.passes > 1, false), eval4r = g4_kernel(g4.ks, g4.passes > 1, true);
-    size_t lds_eval4 = 4 * sizeof(double) * (size_t)eval_gram4_lds_doubles(p->n_points, g4.ks);
-#ifdef TSCM_G4_LDS_PAD      // occupancy experiments (tools/wave_timeline.py): fewer workgroups per CU, same kernel
-    lds_eval4 += TSCM_G4_LDS_PAD;
-#endif
+    const size_t lds_eval4 = 4 * sizeof(double) * (size_t)eval_gram4_lds_doubles(p->n_points, g4.ks);
     if (lds_eval4 > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board with too many corners for the Gram kernel's LDS (more than about 2,000)");
     if (lds_eval4 > 64 * 1024)
         for (EvalKernel k : { eval4, eval4r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
     // the Gram kernels' view chunks are sized for one round of resident waves: LayoutDevice
     int wgs_per_cu = 0;         // resident workgroups per CU (register- and LDS-limited)
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, reinterpret_cast<const void *>(eval4), 256, lds_eval4));
-#ifdef TSCM_EVAL_WAVES          // occupancy experiments: chunk tables for this many waves per SIMD
-    const int waves_per_cu = 4 * TSCM_EVAL_WAVES;
-#else
     const int waves_per_cu = 4 * std::max(1, std::min(4, wgs_per_cu));
-#endif
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const void *schur[4][2] = { {}, { reinterpret_cast<const void *>(k_schur_gram<1>), reinterpret_cast<const void *>(k_schur_gram<1, true>) },
