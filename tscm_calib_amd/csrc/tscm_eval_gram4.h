@@ -111,6 +111,16 @@ __device__ __forceinline__ double quad_tb(double x, double c0, double c1, double
     return fma(c2, x2, fma(c0, x0, c1 * x1));
 }
 
+// `take` in the lanes of the DPP rows ROW (bit i: lanes 16 i .. 16 i + 15) and banks BANK (bit b: lanes 4 b .. 4 b + 3 of a row),
+// `keep` in the others: two masked identity moves
+template <int ROW, int BANK>
+__device__ __forceinline__ double lane_pick(double keep, double take)
+{
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(keep), __double2loint(take), 0xE4, ROW, BANK, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(keep), __double2hiint(take), 0xE4, ROW, BANK, false);
+    return __hiloint2double(hi, lo);
+}
+
 // KS: k-steps of a pass (4 KS rows >= the corners of a pass); MULTI: boards of more than 56 corners, P.g4_per corners per pass;
 // ROBUST: a loss L (robust_rho): every entry a corner puts into the tile, r column included, is scaled by w = sqrt(rho'), and
 // the cost entry of the camera tile is the lanes' fp64 sum of rho instead of the contraction r^T r.  L is not read
@@ -149,7 +159,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     // the same place at the same time).  Trip 1, scalar: the control block and the chunk's 16-byte descriptor; vector: the
     // lane's board point.  Trip 2, everything that hangs on the descriptor at once: R_c, the metadata of the chunk's first
     // 64 views, the first view's observations (all 64 lanes: a lane without a corner reads the next view's value or, past
-    // the end, zero, and never uses it), and one dword of every 64-byte line of the first view's and of the camera's
+    // the end, zero -- the offset is in the vector operand, which the range check covers -- and never uses it), and one dword of every 64-byte line of the first view's and of the camera's
     // constants through the SCALAR cache, so that the geometry's scalar loads hit there.
     const v4i cd = *(const v4i __attribute__((address_space(4))) *)(const void *)(P.chunk_desc + chunk);
     const int cam = cd[0], vb = cd[1], ve = cd[2];
@@ -172,7 +182,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     int off_next = cd[3];
     int m_cnt0 = 0, m_slot0 = 0;
     if (vb + lane < min(ve, vb + 64)) { m_cnt0 = P.view_count[vb + lane]; m_slot0 = P.view_slot[vb + lane]; }
-    if (vb < ve) { pf_u = buf_load_f64(r_u, 8u * lane, 8u * (unsigned)off_next); pf_v = buf_load_f64(r_v, 8u * lane, 8u * (unsigned)off_next); }
+    if (vb < ve) { pf_u = buf_load_f64(r_u, 8u * ((unsigned)off_next + lane), 0); pf_v = buf_load_f64(r_v, 8u * ((unsigned)off_next + lane), 0); }
     // the scalar cache's lines of the first view's 27 constants (4 lines) and of the camera's 48 (6 lines); retired in front of the loop
     typedef const int __attribute__((address_space(4))) *cptr4i;
     const cptr4i vc0 = (cptr4i)(S.vconst + (size_t)kVStride * min(vb, P.V - 1)), cc0 = (cptr4i)ccs;
@@ -223,13 +233,15 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     tl_w[0] = wall_clock64();
     const bool tl_on = lane == 0 && tl_iter == 5 && cand && chunk < kTimelineWaves;
 #endif
+    const int prio_n = max(1, ve - vb);
+    int prio_q = 0, prio_rem = 0;
     for (int vbase = vb; vbase < ve; vbase += 64) {
     const int vend = min(ve, vbase + 64);
     int m_cnt = 0, m_slot = 0;
     if (vbase == vb) { m_cnt = m_cnt0; m_slot = m_slot0; }
     else {
         if (vbase + lane < vend) { m_cnt = P.view_count[vbase + lane]; m_slot = P.view_slot[vbase + lane]; }
-        pf_u = buf_load_f64(r_u, 8u * lane, 8u * (unsigned)off_next); pf_v = buf_load_f64(r_v, 8u * lane, 8u * (unsigned)off_next);
+        pf_u = buf_load_f64(r_u, 8u * ((unsigned)off_next + lane), 0); pf_v = buf_load_f64(r_v, 8u * ((unsigned)off_next + lane), 0);
     }
     asm volatile("" : "+v"(m_cnt), "+v"(m_slot));
     for (int view = vbase; view < vend; ++view) {
@@ -243,7 +255,10 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         // twentieth of the chunk either way and the wrap of the levels in front of it costs more than it brings (+1.6 us)
         const int left = ve - 1 - view;
         const bool tail_steps = left <= 2 && ve - vb <= 16;
-        set_prio(tail_steps ? left + 1 : 3 - min(3, 8 * (view - vb) / max(1, ve - vb) % 4));
+        set_prio(tail_steps ? left + 1 : 3 - (prio_q & 3));
+        // eighths of the chunk behind this view, prio_q = floor(8 (view - vb) / prio_n), counted up instead of divided out per view
+        // (the empty asm keeps the compiler from turning the count back into a division)
+        for (prio_rem += 8; prio_rem >= prio_n; prio_rem -= prio_n) { ++prio_q; asm volatile("" : "+s"(prio_q)); }
 #ifdef TSCM_WAVE_TIMELINE
         if (tl_on && tl_nv < kTlViews) g_tlv[(size_t)(4 + kTlViews) * chunk + 4 + tl_nv] = wall_clock64();
         ++tl_nv;
@@ -256,7 +271,8 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         const int pb = MULTI ? pbv : 0;
         TL_STAMP(ts0);
         if constexpr (MULTI) { if (pb) wave_lds_fence(); }      // ... and so has the previous pass's
-        const bool valid = lane < (MULTI ? min(per, cnt - pb) : cnt);
+        const int nv = MULTI ? min(per, cnt - pb) : cnt;         // corners of this pass
+        const bool valid = lane < nv;
         double fv[16];                          // v-rows wait in registers until the u-rows have been consumed (index = tile column)
         auto PUT = [&](int c, double u, double v) { (c < 8 ? fu_lo : fu_hi)[4 * c] = u; fv[c] = v; };
         if (valid) {
@@ -275,21 +291,28 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
             } else {
                 corner_geometry(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], u, v); });
             }
-        } else if (lane < prev_nv) {
+        }
+        // rows of lanes that lost their corner: only behind a view (pass) that had more corners -- with the same count from view to
+        // view, the usual chunk, the wave skips this on a scalar compare
+        if (nv < prev_nv) {
+            if (!valid && lane < prev_nv) {
 #pragma unroll
-            for (int c = 0; c < kTcols; ++c) (c < 8 ? fu_lo : fu_hi)[4 * c] = 0.0;
+                for (int c = 0; c < kTcols; ++c) (c < 8 ? fu_lo : fu_hi)[4 * c] = 0.0;
+            }
         }
         {
-            // prefetch of the next view (see k_eval_gram): observations, and the constant record into the L2
+            // prefetch of the next view (see k_eval_gram): observations, and the constant record into the L2.  All 64 lanes load: a
+            // lane without a corner there reads the value of the view behind it and never uses it (selecting the lanes cost a
+            // readlane, a compare and a select per view; the ten idle lanes of a 54-corner view touch the next 80 bytes a view early,
+            // and the kernel's measured reads went from 46.9 to 50.9 MB per launch at config 4 with it -- 2.4 us faster all the same).  The whole offset is in the
+            // VECTOR operand, the one the descriptor's range check covers: past the end of the array a lane reads zero
             const int vn = min(view + 1, vend - 1);
-            const int cn = view + 1 < vend ? __builtin_amdgcn_readlane(m_cnt, vn - vbase) : 0;
             if (!MULTI || pb == 0) warm = __builtin_amdgcn_raw_buffer_load_b32(r_vc, lane < 4 ? 64 * lane : (int)0xffffe000u, (int)(8u * (unsigned)kVStride * (unsigned)vn), 0);
             // MULTI: the next pass of this view, or the first pass of the next one
             const bool more = MULTI && pb + per < cnt;
-            const int ncnt = MULTI ? (more ? min(per, cnt - pb - per) : min(per, cn)) : cn;
             const unsigned noff = more ? (unsigned)(off + pb + per) : (unsigned)off_next;
-            pf_u = buf_load_f64(r_u, lane < ncnt ? 8u * lane : 0xffffe000u, 8u * noff);
-            pf_v = buf_load_f64(r_v, lane < ncnt ? 8u * lane : 0xffffe000u, 8u * noff);
+            pf_u = buf_load_f64(r_u, 8u * (noff + lane), 0);
+            pf_v = buf_load_f64(r_v, 8u * (noff + lane), 0);
         }
         prev_nv = MULTI ? min(per, max(cnt - pb, 0)) : cnt;
         wave_lds_fence();
@@ -318,26 +341,29 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         for (int q = 0; q < 3; ++q) { camU[q] += accU[q]; camV[q] += accV[q]; }
         // ---- epilogue: the view's record (same values, same operation order as store_view_record) ------------------
         {
-            int le = lane;
-            asm volatile("" : "+v"(le));         // lane predicates are rebuilt per view instead of living in SGPR pairs
-            const int b = (le >> 2) & 3, i = le >> 4;
             const unsigned slot = (unsigned)__builtin_amdgcn_readlane(m_slot, view - vbase);
             const unsigned offW = 8u * (unsigned)kRecW * slot, offE = 8u * ((unsigned)kRecW * (unsigned)P.V + (unsigned)kRecE * slot);
             const double T0 = accU[0] + accV[0], T1 = accU[1] + accV[1], T2 = accU[2] + accV[2];
-            const double tb0 = quad_tb(T0, rc0, rc1, rc2), tb1 = quad_tb(T1, rc0, rc1, rc2), tb2 = quad_tb(T2, rc0, rc1, rc2);
-            const double tbU2 = quad_tb(accU[2], rc0, rc1, rc2);
-            const bool split1 = b == 3 && i == 0, split2 = (le & 3) == 3 ? b == 0 : (b == 2 ? i == 3 : (b == 3 && i == 0));
-            buf_store_f64(r_rec, o1e, offE, T0);
-            buf_store_f64(r_rec, o1w, offW, b == 1 ? tb0 : T0);
-            buf_store_f64(r_rec, o2, offW, split1 ? accU[1] : (i == 3 ? tb1 : T1));
-            buf_store_f64(r_rec, o3e, offE, tb1);
-            const double a4 = b != 0 ? tb2 : T2, u4 = b != 0 ? tbU2 : accU[2];
-            buf_store_f64(r_rec, o4, offW, split2 ? u4 : a4);
-            buf_store_f64(r_rec, o5, offW, T1 - accU[1]);
-            buf_store_f64(r_rec, o6, offW, a4 - u4);
+            // A lane's block b is its DPP bank and its row i its DPP row: every choice by (b, i) below is a pair of masked moves
+            // (lane_pick) -- no compare, no mask in an SGPR pair.  The t_b rows: block 1 stores those of T0 (o1w), block 0 those of
+            // T1 (o2, o3e, o7b), blocks 2 and 3 those of T2 (o4, o6), so ONE quad_tb of the block's own T serves all three; the
+            // products and FMAs of a stored value are the ones quad_tb(T0 | T1 | T2) performed for it.
+            const double X = lane_pick<0xF, 0x1>(lane_pick<0xF, 0x2>(T2, T0), T1);
+            const double tbX = quad_tb(X, rc0, rc1, rc2), tbU2 = quad_tb(accU[2], rc0, rc1, rc2);
+            // (a pick overwrites its `keep` operand: each one below is the last use of that value, so none costs a copy)
             const unsigned offG = 8u * ((unsigned)(kRecW + kRecE) * (unsigned)P.V + (unsigned)kRecG * slot);
+            buf_store_f64(r_rec, o1e, offE, T0);
             buf_store_f64(r_rec, o7a, offG, T0);          // E^T r once more, compact (k_reduce_stats reads it there)
-            buf_store_f64(r_rec, o7b, offG, tb1);
+            buf_store_f64(r_rec, o1w, offW, lane_pick<0xF, 0x2>(T0, tbX));
+            buf_store_f64(r_rec, o5, offW, T1 - accU[1]);
+            // o2: T1; row 3 (of block 0: the other blocks store nothing from it) the t_b rows; row 0 of block 3 the u-part
+            buf_store_f64(r_rec, o2, offW, lane_pick<0x1, 0x8>(lane_pick<0x8, 0xF>(T1, tbX), accU[1]));
+            buf_store_f64(r_rec, o3e, offE, tbX);
+            buf_store_f64(r_rec, o7b, offG, tbX);
+            const double a4 = lane_pick<0xF, 0xE>(T2, tbX), u4 = lane_pick<0xF, 0x1>(tbU2, accU[2]);
+            // the lanes that store the u-part through o4 are the lanes with an entry in o6 (which takes the v-part, a4 - u4)
+            buf_store_f64(r_rec, o4, offW, (int)o6 >= 0 ? u4 : a4);
+            buf_store_f64(r_rec, o6, offW, a4 - u4);
         }
 #ifdef TSCM_WAVE_TIMELINE
         { TL_STAMP(ts5); TL_ADD(4, ts4e, ts5); }
