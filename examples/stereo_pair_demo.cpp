@@ -1,13 +1,17 @@
 // stereo_pair_demo.cpp -- from two fisheye images of adjacent cameras of a calibrated rig to 3-D points: the long-lat
 // rectification of rectify_pair_demo.cpp (tscm_build_maps_ex, tscm_remap), then census + semi-global matching along the
-// rows (tscm_stereo_match) and the points of the disparities in the pair frame of camera a (tscm_stereo_points).
-// Images are 8-bit binary PGM files (P5).
-//   usage: stereo_pair_demo calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]
+// rows (tscm_stereo_match), optionally the post-filter of the disparity map (tscm_stereo_filter) and the points of the
+// disparities in the pair frame of camera a (tscm_stereo_points).  Images are 8-bit binary PGM files (P5).
+//   usage: stereo_pair_demo [--speckle N,R] [--median M] calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt
+//                           [width height [num_disparities [paths]]]
+// --speckle N,R: components of at most N pixels whose neighbours differ by at most R disparities are dropped;
+// --median M: masked median of M x M (3 or 5) afterwards.
 // disparity.pgm: disparity in pixels (saturated at 255), 0 where invalid; points.txt: one "column row X Y Z" line per
 // valid pixel, X Y Z in the units of the calibration's translations, pair frame (x along the baseline from a to b).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 #include <string>
@@ -35,10 +39,22 @@ static bool write_pgm(const char *path, const std::vector<unsigned char> &pix, i
     return (bool)f;
 }
 
-int main(int argc, char **argv)
+int main(int argc_all, char **argv_all)
 {
-    if (argc < 8) {
-        std::fprintf(stderr, "usage: %s calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]\n", argv[0]);
+    // the options may stand anywhere; what is left are the positional arguments
+    int speckle_window = 0, speckle_range = 0, median = 0;
+    bool bad_option = false;
+    std::vector<char *> argv(1, argv_all[0]);
+    for (int k = 1; k < argc_all; ++k) {
+        if (!std::strcmp(argv_all[k], "--speckle") && k + 1 < argc_all) bad_option |= std::sscanf(argv_all[++k], "%d,%d", &speckle_window, &speckle_range) != 2;
+        else if (!std::strcmp(argv_all[k], "--median") && k + 1 < argc_all) median = std::atoi(argv_all[++k]);
+        else if (!std::strncmp(argv_all[k], "--", 2)) bad_option = true;
+        else argv.push_back(argv_all[k]);
+    }
+    const int argc = (int)argv.size();
+    if (argc < 8 || bad_option) {
+        std::fprintf(stderr, "usage: %s [--speckle N,R] [--median M] calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]\n",
+                     argv[0]);
         return 2;
     }
     const int cam[2] = { std::atoi(argv[2]), std::atoi(argv[3]) };
@@ -67,7 +83,15 @@ int main(int argc, char **argv)
         tscm_stereo_default_params(&params);
         if (argc > 10) params.num_disparities = std::atoi(argv[10]);
         if (argc > 11) params.paths = std::atoi(argv[11]);
-        const std::vector<short> disparity = tscm::stereo_match(rect[0].data(), rect[1].data(), size, &params);
+        std::vector<short> disparity = tscm::stereo_match(rect[0].data(), rect[1].data(), size, &params);
+        if (speckle_window > 0 || median > 0) {
+            tscm_stereo_filter_params post;
+            tscm_stereo_filter_default_params(&post);
+            post.min_disparity = params.min_disparity;
+            post.speckle_window_size = speckle_window; post.speckle_range = speckle_range;
+            post.median = median;
+            disparity = tscm::stereo_filter(disparity, size, &post);
+        }
         const double dt[3] = { Tb[3] - Ta[3], Tb[7] - Ta[7], Tb[11] - Ta[11] };
         const double baseline = std::sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
         std::vector<unsigned char> valid;

@@ -781,6 +781,49 @@ int tscm_stereo_points(const short *disparity, int width, int height, int disp_s
                        const tscm_map_desc *left_map, int projection, double baseline, int device_index,
                        double *points /* [h*w*3] */, unsigned char *valid /* [h*w] */);
 
+/* Post-filter of a disparity map: speckle removal (OpenCV's speckleWindowSize / speckleRange, which the matcher above
+ * leaves out) and a masked median.  Integers throughout, defined here so that a host restatement gives the same bits
+ * (tests/stereo_filter_ref.py).
+ *   input       d [height][disp_stride] int16; invalid = 16 (min_disparity - 1); a pixel is valid iff d != invalid.
+ *   edges       two 4-neighbours p, q are joined iff both are valid and |d(p) - d(q)| <= 16 speckle_range, the difference
+ *               taken in int32.  This is the relation cv::filterSpeckles grows regions by (it compares with the current
+ *               pixel, not with the seed), so a ramp whose steps each stay within the range is one component however far
+ *               apart its ends are.
+ *   components  the connected components of that graph.  label(p) = the smallest linear index y * width + x of p's
+ *               component, -1 for an invalid p; size(p) = the component's pixel count, 0 for an invalid p.  Neither
+ *               depends on an order of traversal.
+ *   speckle     speckle_window_size > 0: every pixel with size(p) <= speckle_window_size becomes invalid (<=, as OpenCV);
+ *               0 switches the rule off.
+ *   median      median = 3 or 5, on the map after the speckle rule: an invalid pixel stays invalid (no hole filling); for
+ *               a valid pixel take the valid pixels of the median x median window that lie inside the image (nothing is
+ *               clamped or replicated), n >= 1 of them, sort them ascending: the output is the element at index
+ *               (n - 1) >> 1.  median = 0: no median.
+ * With speckle_window_size = 0 and median = 0 the output equals the input.  out == disparity with equal strides is allowed
+ * (the device works on its own copies); elements of `out` between width and out_stride keep the caller's values.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL disparity / params / out,
+ * disp_stride or out_stride < width, a struct_size other than sizeof(tscm_stereo_filter_params), speckle_window_size < 0,
+ * speckle_range outside 0..255, median other than 0, 3, 5, a min_disparity outside -2047..2031 (what the matcher accepts
+ * at its smallest num_disparities), width * height above INT_MAX (labels are int32).  width == 0 or height == 0 returns 0
+ * without touching a device.  device_index and seconds_kernel: as for the matcher. */
+typedef struct tscm_stereo_filter_params {
+    int struct_size;          /* sizeof(tscm_stereo_filter_params)                  */
+    int min_disparity;        /* defines the invalid value, as for the matcher      */
+    int speckle_window_size;  /* 0 = off; components of at most this many pixels go */
+    int speckle_range;        /* whole disparities, 0..255; the edge test uses 16 x */
+    int median;               /* 0, 3 or 5                                          */
+} tscm_stereo_filter_params;
+void tscm_stereo_filter_default_params(tscm_stereo_filter_params *p);   /* 0, 100, 2, 0 */
+
+int tscm_stereo_filter(const short *disparity, int width, int height, int disp_stride,
+                       const tscm_stereo_filter_params *params, int device_index,
+                       short *out /* [height][out_stride] */, int out_stride, double *seconds_kernel /* may be NULL */);
+
+/* The stages of the same launches, for parity tests: any output may be NULL.  despeckled: the map after the speckle rule
+ * and before the median (the input itself with speckle_window_size = 0). */
+int tscm_stereo_filter_stages(const short *disparity, int width, int height, int disp_stride,
+                              const tscm_stereo_filter_params *params, int device_index,
+                              int *label /* [h*w] */, int *size /* [h*w] */, short *despeckled /* [h*w] */);
+
 /* ------------------------------------------------------------------ panorama of a calibrated rig
  * What the tables of panorama_descs (one EQUIRECT or CYLINDRICAL table per camera, all in the rig frame) are for: the
  * stitched image.  A handle keeps everything that does not depend on a frame on the device -- the sample positions, the

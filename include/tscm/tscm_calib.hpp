@@ -20,6 +20,7 @@
 //   (none: pinhole tables only)                            undistort(..., projection), rectify_pair_maps -> tscm_build_maps_ex
 //   (none)                                                 TripleSphereCamera::rectify_point   -> tscm_rectify_points
 //   (none: the rectified pair is its last product)         stereo_match, stereo_points         -> tscm_stereo_match, tscm_stereo_points
+//   (none: cv::filterSpeckles / medianBlur downstream)     stereo_filter                       -> tscm_stereo_filter
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
@@ -673,6 +674,20 @@ inline std::vector<short> stereo_match(const unsigned char *left, const unsigned
     std::vector<short> disparity((size_t)size.width * size.height);
     check(tscm_stereo_match(left, right, size.width, size.height, size.width, &p, device, disparity.data(), size.width, NULL));
     return disparity;
+}
+
+// stereo_filter: speckle removal and masked median of a disparity map of `size` (rows of size.width elements) -> the
+// filtered map; params == NULL: tscm_stereo_filter_default_params (set min_disparity to the matcher's).
+inline std::vector<short> stereo_filter(const std::vector<short> &disparity, Size size, const tscm_stereo_filter_params *params = NULL, int device = 0)
+{
+    if (disparity.size() != (size_t)size.width * size.height) throw std::runtime_error("tscm: the disparity map does not have the given size");
+    tscm_stereo_filter_params p;
+    if (params) p = *params;
+    else tscm_stereo_filter_default_params(&p);
+    std::vector<short> out(disparity.size());
+    if (out.empty()) return out;
+    check(tscm_stereo_filter(disparity.data(), size.width, size.height, size.width, &p, device, out.data(), size.width, NULL));
+    return out;
 }
 
 // stereo_points: the disparities of stereo_match on the pair of rectify_pair_maps (left_map = desc[0], projection

@@ -126,6 +126,12 @@ class CStereoParams(C.Structure):
                 ("paths", C.c_int), ("uniqueness_ratio", C.c_int), ("disp12_max_diff", C.c_int)]
 
 
+class CStereoFilterParams(C.Structure):
+    """tscm_stereo_filter_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("min_disparity", C.c_int), ("speckle_window_size", C.c_int), ("speckle_range", C.c_int),
+                ("median", C.c_int)]
+
+
 class CPanoramaParams(C.Structure):
     """tscm_panorama_params (tscm.h)"""
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int)]
@@ -155,6 +161,7 @@ EXPORTS = [
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
+    "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
     "tscm_panorama_default_params", "tscm_panorama_create", "tscm_panorama_compose", "tscm_panorama_stages", "tscm_panorama_overlap", "tscm_panorama_destroy",
 ]
 
@@ -250,6 +257,11 @@ def lib():
     L.tscm_stereo_stage_times.argtypes = [dp]
     L.tscm_stereo_points.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CMapDesc), C.c_int, C.c_double, C.c_int,
                                      dp, ubp]
+    L.tscm_stereo_filter_default_params.argtypes = [C.POINTER(CStereoFilterParams)]
+    L.tscm_stereo_filter_default_params.restype = None
+    L.tscm_stereo_filter.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFilterParams), C.c_int, C.POINTER(C.c_short), C.c_int, dp]
+    L.tscm_stereo_filter_stages.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFilterParams), C.c_int, C.POINTER(C.c_int),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_short)]
     fp, shp, llp, vpp = C.POINTER(C.c_float), C.POINTER(C.c_short), C.POINTER(C.c_longlong), C.POINTER(vp)
     L.tscm_panorama_default_params.argtypes = [C.POINTER(CPanoramaParams)]
     L.tscm_panorama_default_params.restype = None

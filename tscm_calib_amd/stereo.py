@@ -1,6 +1,7 @@
 """Stereo matching and depth on a rectified pair (tscm.h: tscm_stereo_*): census + semi-global matching on the device,
-the 3-D points of a disparity map, and pair_depth, the chain from two fisheye images of a calibrated rig to points:
-rectify_pair_descs -> build_maps -> remap -> match -> points."""
+the post-filter of a disparity map (speckle removal, masked median), the 3-D points of a disparity map, and pair_depth,
+the chain from two fisheye images of a calibrated rig to points:
+rectify_pair_descs -> build_maps -> remap -> match [-> filter] -> points."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,6 +13,7 @@ from . import maps as _maps
 
 PARAM_NAMES = ("min_disparity", "num_disparities", "p1", "p2", "paths", "uniqueness_ratio", "disp12_max_diff")
 STAGE_NAMES = ("census", "cost", "aggregate", "right_winner", "winner")
+FILTER_PARAM_NAMES = ("min_disparity", "speckle_window_size", "speckle_range", "median")
 
 
 def params(**over) -> _lib.CStereoParams:
@@ -81,6 +83,56 @@ def stage_times() -> dict:
     return dict(zip(STAGE_NAMES, t.tolist()))
 
 
+def filter_params(**over) -> _lib.CStereoFilterParams:
+    """tscm_stereo_filter_default_params with the given fields replaced."""
+    p = _lib.CStereoFilterParams()
+    _lib.lib().tscm_stereo_filter_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in FILTER_PARAM_NAMES:
+            raise TypeError(f"unknown stereo filter parameter {k!r}: one of {', '.join(FILTER_PARAM_NAMES)}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _disparity_map(disp) -> np.ndarray:
+    disp = np.asarray(disp)
+    if disp.ndim != 2 or disp.dtype != np.int16:
+        raise ValueError("a disparity map is a 2-D int16 array")
+    if disp.strides[1] != 2 or disp.strides[0] % 2 or disp.strides[0] < 2 * disp.shape[1]:
+        disp = np.ascontiguousarray(disp)
+    return disp
+
+
+def filter(disp, device: int = 0, out: np.ndarray | None = None, with_seconds: bool = False, **over):
+    """tscm_stereo_filter: speckle removal and masked median of a disparity map -> int16 [h, w].  `disp` may be a
+    row-padded view; `out` may be one too (its padding keeps its values) and may be `disp` itself."""
+    disp = _disparity_map(disp)
+    h, w = disp.shape
+    p = filter_params(**over)
+    if out is None:
+        out = np.zeros((h, w), dtype=np.int16)
+    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
+        raise ValueError("out must be an int16 array (or row-padded view) of the map's shape")
+    sp = C.POINTER(C.c_short)
+    sec = C.c_double(0.0)
+    _lib.check(_lib.lib().tscm_stereo_filter(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, C.byref(p), device,
+                                             out.ctypes.data_as(sp), out.strides[0] // 2 if h else w, C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
+
+
+def filter_stages(disp, device: int = 0, **over) -> dict:
+    """tscm_stereo_filter_stages -> label int32 [h, w] (the smallest linear index of the pixel's component, -1 invalid),
+    size int32 [h, w] (its pixel count, 0 invalid), despeckled int16 [h, w] (the map before the median)."""
+    disp = _disparity_map(disp)
+    h, w = disp.shape
+    p = filter_params(**over)
+    label, size, desp = np.zeros((h, w), dtype=np.int32), np.zeros((h, w), dtype=np.int32), np.zeros((h, w), dtype=np.int16)
+    ip, sp = C.POINTER(C.c_int), C.POINTER(C.c_short)
+    _lib.check(_lib.lib().tscm_stereo_filter_stages(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, C.byref(p), device,
+                                                    label.ctypes.data_as(ip), size.ctypes.data_as(ip), desp.ctypes.data_as(sp)))
+    return dict(label=label, size=size, despeckled=desp)
+
+
 def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0):
     """tscm_stereo_points: the disparity map of the left image of a PERSPECTIVE or LONGLAT pair (desc = its MapDesc) ->
     (points [h, w, 3] fp64 in the pair frame of the left camera, valid [h, w] bool); invalid points are NaN."""
@@ -98,11 +150,15 @@ def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0)
 
 
 def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat", width: int = 640, height: int = 320, fov_x: float = np.pi,
-               fov_y: float = np.pi / 2, device: int = 0, matcher=None, **over):
+               fov_y: float = np.pi / 2, device: int = 0, matcher=None, post=None, **over):
     """Two grey fisheye images of cameras a and b of a calibrated rig -> (points [height, width, 3] in the pair frame of
     camera a, valid [height, width], R_pair).  R_pair = rectify_pair_rotation(t_a, t_b) turns pair-frame vectors into the
     rig frame: P_rig = R_pair @ P + t_a.  Camera a is the left image: b lies at +|t_b - t_a| on the pair frame's x-axis.
-    `matcher` replaces match (same signature without device; for comparisons with a reference matcher)."""
+    `matcher` replaces match (same signature without device; for comparisons with a reference matcher).  `post`: a dict
+    of filter parameters (speckle_window_size, speckle_range, median); the disparity map then passes through filter, with
+    the matcher's min_disparity, before its points are taken.  None: no filter."""
+    if post is not None and "min_disparity" in post:
+        raise TypeError("post: min_disparity is the matcher's")
     kind = _maps.projection_kind(projection)
     if kind not in (_lib.PROJ_PERSPECTIVE, _lib.PROJ_LONGLAT):
         raise ValueError("pair_depth needs rows that are epipolar lines: 'longlat' or 'perspective'")
@@ -114,6 +170,8 @@ def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat",
         mx, my, _ = _maps.build_maps([d], device=device)
         rect.append(_maps.remap(_gray(img), mx.reshape(height, width), my.reshape(height, width), device=device))
     disp = matcher(rect[0], rect[1], **over) if matcher is not None else match(rect[0], rect[1], device=device, **over)
+    if post is not None:
+        disp = filter(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **post)
     Ta, Tb = np.asarray(Twc_a, dtype=np.float64).reshape(3, 4), np.asarray(Twc_b, dtype=np.float64).reshape(3, 4)
     baseline = float(np.linalg.norm(Tb[:, 3] - Ta[:, 3]))
     pts, valid = points(disp, descs[0], baseline, min_disparity=int(over.get("min_disparity", 0)), device=device)
