@@ -563,6 +563,27 @@ int tscm_build_maps_ex(const tscm_map_desc *maps, const int *projection /* [n_ma
                        int n_maps, int device, int exact, float *mapx, float *mapy, size_t n_elems,
                        double *seconds_kernel);
 
+/* Tables of a sphere sweep (tscm_sweep_* below): n_cameras x D tables on one output grid.  maps[k] is camera k's table as
+ * panorama_descs gives it (R = R_cam^T, all of one width x height), centers[k] the camera centre in the output frame (the
+ * translation column of Twc), inv_distance[z] the inverse distance of hypothesis z.  Table (k, z) uses the ray
+ *     dir(i, j) - inv_distance[z] * centers[k]
+ * in front of R, dir being the ray of the map's projection kind exactly as tscm_build_maps_ex forms it: the point
+ * dir / inv seen from camera k, scaled by inv.  The projection ignores the scale, so inv = 0 (infinity) needs no special
+ * case and gives the table of tscm_build_maps_ex, bit for bit.  Everything after the ray is tscm_build_maps_ex: R, the
+ * projection with its skew terms, check_w2, the offsets, `exact`.  The hypothesis surface is dir / inv: a sphere for
+ * EQUIRECT, LONGLAT and STEREOGRAPHIC, a cylinder about y for CYLINDRICAL.  The output is dense: plane (k, z) starts at
+ * element (k * D + z) * height * width of mapx / mapy.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL pointer, n_cameras < 1,
+ * D < 1, descriptors whose width / height differ from each other, out_stride != width or out_offset != 0, n_elems below
+ * n_cameras * D * height * width, an inv_distance that is negative, not finite or not strictly increasing, a centre that is
+ * not finite, an unknown projection kind.  TSCM_PROJ_PERSPECTIVE (plane sweep) is TSCM_E_UNSUPPORTED, as are more than
+ * 65535 tables in one call.  device_index: as `device` of tscm_build_maps_ex, TSCM_E_NO_DEVICE outside
+ * [0, tscm_device_count()), after the argument checks. */
+int tscm_build_sweep_maps(const tscm_map_desc *maps /* [n_cameras] */, const int *projection /* [n_cameras] */, int n_cameras,
+                          const double *centers /* [n_cameras][3] */, const double *inv_distance /* [D] */, int D,
+                          int device_index, int exact, float *mapx, float *mapy /* [n_cameras][D][height][width] */,
+                          size_t n_elems, double *seconds_kernel);
+
 /* The inverse direction for single points: pixel of the sampled camera -> get_unit_sphere_coordinate -> R^T -> the
  * inverse of the table above (x/z, y/z | atan2(x, hypot(y, z)), atan2(y, z) | atan2(x, z), y/hypot(x, z) |
  * 2(x, y)/(1 + z) | atan2(x, z), atan2(y, hypot(x, z))) -> out = (a fx + cx, b fy + cy), a position in the OUTPUT image.
@@ -897,6 +918,76 @@ int tscm_panorama_overlap(tscm_panorama *p, const unsigned char *const *images, 
                           long long *count /* [n*n] */, long long *sum /* [n*n] */);
 
 void tscm_panorama_destroy(tscm_panorama *p);
+
+/* ------------------------------------------------------------------ sphere-sweep depth of a calibrated rig
+ * Depth in the rig frame over the whole panorama, from all cameras at once: for each pixel (i, j) of the rig-frame panorama
+ * and each inverse-distance hypothesis z the point dir(i, j) / inv_distance[z] is projected into every camera (the tables of
+ * tscm_build_sweep_maps), the cameras that see it are compared by their census codes, and the cost volume is regularised and
+ * searched as the stereo matcher's is.  A handle keeps the n x D packed tables on the device: n * D * pano_w * pano_h * 8
+ * bytes.  Integer arithmetic up to the index map, defined here operation by operation so that a host restatement gives the
+ * same bits (tests/sweep_ref.py).  n = n_cameras, D = num_hypotheses, V(i, j, z) = { k : a_k(i, j, z) > 0 }.
+ *   sample     v_k(i, j, z) and a_k(i, j, z): the `sample` rule of the panorama above on table (k, z), one channel, no
+ *              gain: 1/32 px positions, 15-bit weights, (acc + 2^14) >> 15, taps outside the image 0; a NULL weight is a
+ *              constant 255 image whose border taps ramp a_k to 0.
+ *   census     the 9 x 7 code of tscm_stereo_match on the plane v_k(., ., z): rows clamped, columns wrapped when wrap_x is
+ *              set and clamped otherwise.  A neighbour without coverage takes part with its sampled value (0 outside the
+ *              image); there is no special case.
+ *   cost       |V| < 2: C(i, j, z) = 64.  Otherwise, with P = |V| (|V| - 1) / 2 pairs,
+ *              C(i, j, z) = (sum over a < b in V of popcount(census_a ^ census_b) + (P >> 1)) / P, at most 62.  So C == 64
+ *              says exactly that fewer than two cameras see the point.
+ *   paths, S, winner, uniqueness, parabola: the rules of tscm_stereo_match on this C (the diagonal paths restart at the
+ *              column ends, also with wrap_x: the aggregation does not run over the 360 degree seam), with
+ *              min_disparity = 0 and no left-right check, and one more rule: the pixel is invalid if C(i, j, k*) == 64.
+ *   output     index16 = 16 k* + the parabola term (int16); invalid = -16.
+ *   points     (fp64) s = index16 / 16, k0 = min(floor(s), D - 2),
+ *              inv = inv_distance[k0] + (s - k0) (inv_distance[k0 + 1] - inv_distance[k0]),  P = dir(i, j) / inv in the
+ *              output (rig) frame, dir the ray of pano_map's projection kind before R; valid = 0 and P = NaN for an invalid
+ *              pixel (index16 < 0) or inv <= 0.
+ * Stage outputs: sampled, alpha [n][D][pano_h][pano_w] uint8, census alike uint64, cost [pano_h][pano_w][D] uint8,
+ * aggregated alike uint16; any of them may be NULL.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a required pointer that is NULL,
+ * a struct_size other than sizeof(tscm_sweep_params), num_hypotheses not a multiple of 16 in 16..256, p1 or p2 outside
+ * 0 <= p1 <= p2 <= 255, paths other than 4 or 8, uniqueness_ratio outside 0..99, n_cameras outside 2..8, a source image
+ * with a side below 1 or above 32767, pano_w or pano_h below 1, stride < width, out_stride < pano_w; for the points a
+ * stride < pano_w, D outside 2..2048, an inv_distance that is not finite, an unknown projection kind (PERSPECTIVE is
+ * TSCM_E_UNSUPPORTED, as is a panorama of more than 2^31 - 1 pixels).  device_index: as `device` elsewhere,
+ * TSCM_E_NO_DEVICE outside [0, tscm_device_count()), after the argument checks.  Elements of index16 between pano_w and
+ * out_stride keep the caller's values.  seconds_kernel (may be NULL): device time of the frame's kernels (HIP events),
+ * without the copies.  A handle serves one thread at a time. */
+typedef struct tscm_sweep_params {
+    int struct_size;        /* sizeof(tscm_sweep_params)                                                     */
+    int num_hypotheses;     /* D: multiple of 16, 16..256 (what the aggregation serves)                      */
+    int p1, p2;             /* 0 <= p1 <= p2 <= 255                                                          */
+    int paths;              /* 4 or 8                                                                        */
+    int uniqueness_ratio;   /* 0..99, 0 = off                                                                */
+    int wrap_x;             /* 1: the census window wraps over the column ends (full 360 degree tables)      */
+} tscm_sweep_params;
+void tscm_sweep_default_params(tscm_sweep_params *p);   /* 64, 8, 32, 8, 10, 1 */
+
+typedef struct tscm_sweep tscm_sweep;   /* opaque: the packed tables and the frame's volumes on the device */
+
+int tscm_sweep_create(int n_cameras /* 2..8 */, int width, int height /* grey source images, all alike */,
+                      const unsigned char *const *weights /* as tscm_panorama_create */,
+                      const float *mapx, const float *mapy /* [n][D][pano_h][pano_w] */, int pano_w, int pano_h,
+                      const tscm_sweep_params *params, int device_index, tscm_sweep **out);
+
+int tscm_sweep_depth(tscm_sweep *s, const unsigned char *const *images /* [n] of [height][stride] */, int stride,
+                     short *index16 /* [pano_h][out_stride] */, int out_stride, double *seconds_kernel);
+
+/* The stages of the same kernels, for parity tests: any output may be NULL. */
+int tscm_sweep_stages(tscm_sweep *s, const unsigned char *const *images, int stride,
+                      unsigned char *sampled, unsigned char *alpha, unsigned long long *census,
+                      unsigned char *cost, unsigned short *aggregated);
+
+/* Device seconds of the calling thread's last tscm_sweep_depth / tscm_sweep_stages by stage: cost volume, path
+ * aggregation, winner. */
+int tscm_sweep_stage_times(double *seconds /* [3] */);
+
+int tscm_sweep_points(const short *index16, int pano_w, int pano_h, int stride, const tscm_map_desc *pano_map, int projection,
+                      const double *inv_distance /* [D] */, int D, int device_index,
+                      double *points /* [h*w*3], rig frame */, unsigned char *valid /* [h*w] */);
+
+void tscm_sweep_destroy(tscm_sweep *s);
 
 #ifdef __cplusplus
 }

@@ -821,5 +821,94 @@ inline std::vector<unsigned short> exposure_gains(int n, const std::vector<long 
     return out;
 }
 
+// Sphere-sweep depth of a calibrated rig: for every pixel of the rig-frame panorama the inverse-distance hypothesis at which
+// the cameras that see the point agree best (tscm.h: tscm_sweep_*).  The tables come from tscm_build_sweep_maps on the
+// descriptors a Panorama uses, with the camera centres Twc[:, 3]; inv_distance: D = params.num_hypotheses values, not
+// negative and strictly increasing (0 = infinity).  intr [9 n], Twc [12 n] as tscm_yaml_read returns them; grey images;
+// weights: NULL (all 255) or n images of image_size (entries may be NULL); params == NULL: tscm_sweep_default_params with
+// num_hypotheses = inv_distance.size().
+class Sweep {
+public:
+    Sweep(int n_cameras, const double *intr, const double *Twc, Size image_size, Size pano_size, const std::vector<double> &inv_distance,
+          const tscm_sweep_params *params = NULL, const unsigned char *const *weights = NULL, int projection = TSCM_PROJ_EQUIRECT, int device = 0)
+        : n_(n_cameras), image_(image_size), pano_(pano_size), projection_(projection), device_(device), inv_(inv_distance), handle_(NULL)
+    {
+        if (projection != TSCM_PROJ_EQUIRECT && projection != TSCM_PROJ_CYLINDRICAL) throw std::runtime_error("tscm: a panorama is equirect or cylindrical");
+        if (n_cameras < 1 || pano_size.width < 1 || pano_size.height < 1 || inv_.empty()) throw std::runtime_error("tscm: a sweep needs cameras, a size and hypotheses");
+        const double pi = 3.14159265358979323846;
+        const int D = (int)inv_.size();
+        std::vector<tscm_map_desc> desc((size_t)n_);
+        std::vector<int> kinds((size_t)n_, projection);
+        std::vector<double> centers(3 * (size_t)n_);
+        for (int k = 0; k < n_; ++k) {
+            tscm_map_desc &d = desc[(size_t)k];
+            d = tscm_map_desc();
+            std::memcpy(d.intr, intr + 9 * k, sizeof(d.intr));
+            const double *T = Twc + 12 * k;
+            for (int r = 0; r < 3; ++r) {
+                for (int c = 0; c < 3; ++c) d.R[3 * r + c] = T[4 * c + r];           // R_cam^T
+                centers[3 * (size_t)k + r] = T[4 * r + 3];
+            }
+            d.fx = pano_.width / (2.0 * pi);
+            d.fy = projection == TSCM_PROJ_EQUIRECT ? pano_.height / pi : d.fx;
+            d.cx = 0.5 * pano_.width; d.cy = 0.5 * pano_.height;
+            d.width = pano_.width; d.height = pano_.height; d.out_stride = pano_.width;
+            d.check_w2 = 1; d.w2 = 0.42399;
+        }
+        pano_map_ = desc[0];
+        const size_t n_elems = (size_t)n_ * D * pano_.width * pano_.height;
+        std::vector<float> mapx(n_elems), mapy(n_elems);
+        check(tscm_build_sweep_maps(desc.data(), kinds.data(), n_, centers.data(), inv_.data(), D, device, 1, mapx.data(), mapy.data(), n_elems, NULL));
+        tscm_sweep_params p;
+        if (params) p = *params;
+        else { tscm_sweep_default_params(&p); p.num_hypotheses = D; }
+        if (p.num_hypotheses != D) throw std::runtime_error("tscm: params.num_hypotheses is not the number of inverse distances");
+        check(tscm_sweep_create(n_, image_.width, image_.height, weights, mapx.data(), mapy.data(), pano_.width, pano_.height, &p, device, &handle_));
+    }
+    ~Sweep() { tscm_sweep_destroy(handle_); }
+
+    // images: n rows-of-`stride`-bytes grey images (stride 0: the image width) -> pano_size.height rows of pano_size.width
+    // values 16 k* + sub-index term, -16 where invalid
+    std::vector<short> depth(const unsigned char *const *images, int stride = 0, double *seconds_kernel = NULL)
+    {
+        std::vector<short> out((size_t)pano_.width * pano_.height);
+        check(tscm_sweep_depth(handle_, images, stride ? stride : image_.width, out.data(), pano_.width, seconds_kernel));
+        return out;
+    }
+    // the points of an index map of depth() in the rig frame; NaN and valid[k] = 0 where invalid or at infinity
+    std::vector<Point3d> points(const std::vector<short> &index16, std::vector<unsigned char> &valid) const;
+    int cameras() const { return n_; }
+    Size size() const { return pano_; }
+
+private:
+    Sweep(const Sweep &);
+    Sweep &operator=(const Sweep &);
+    int n_;
+    Size image_, pano_;
+    int projection_, device_;
+    std::vector<double> inv_;
+    tscm_map_desc pano_map_;
+    tscm_sweep *handle_;
+};
+
+// sweep_points: an index map of a sweep over the panorama `pano_map` (fx fy cx cy of the output grid; kind `projection`) ->
+// points dir(i, j) / inv in the rig frame, inv interpolated between the hypotheses; NaN and valid[k] = 0 where invalid.
+inline std::vector<Point3d> sweep_points(const std::vector<short> &index16, Size size, const tscm_map_desc &pano_map, int projection,
+                                         const std::vector<double> &inv_distance, std::vector<unsigned char> &valid, int device = 0)
+{
+    if (index16.size() != (size_t)size.width * size.height) throw std::runtime_error("tscm: the index map does not have the given size");
+    std::vector<Point3d> points(index16.size());
+    valid.assign(index16.size(), 0);
+    if (points.empty()) return points;
+    check(tscm_sweep_points(index16.data(), size.width, size.height, size.width, &pano_map, projection, inv_distance.data(), (int)inv_distance.size(), device,
+                            &points[0].x, valid.data()));
+    return points;
+}
+
+inline std::vector<Point3d> Sweep::points(const std::vector<short> &index16, std::vector<unsigned char> &valid) const
+{
+    return sweep_points(index16, pano_, pano_map_, projection_, inv_, valid, device_);
+}
+
 }  // namespace tscm
 #endif

@@ -8,6 +8,7 @@ Only what the reprojection-error LM hot path of imuncle/TSCM_Calib and its immed
   maps.py      remap tables (undistort, undistort_chessboard, epipolar rectification)
   stereo.py    census + semi-global matching on a rectified pair, points, pair_depth
   panorama.py  the rig's panorama: Composer (seam / feather / multi-band), radial_weights, exposure_gains
+  sweep.py     sphere-sweep depth over the panorama from all cameras: Sweeper, inverse_distances, rig_depth
   calib_io.py  calibration YAML in the cv::FileStorage layout
   problem.py   problem container, frame sharding
   synth.py     deterministic synthetic chessboard observations (BASELINE.json configs)

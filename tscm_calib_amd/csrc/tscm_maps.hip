@@ -11,6 +11,7 @@
 #include "tscm_host.h"
 #include "tscm_math.h"
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -231,6 +232,67 @@ __global__ __launch_bounds__(256) void k_build_maps_proj(const tscm_map_desc *__
     }
 }
 
+// tscm_build_sweep_maps: the sibling of k_build_maps_proj for the sphere sweep.  Table (k, z) = blockIdx.y of [n][D] looks
+// from camera k at the point dir / inv_distance[z]: the ray in front of R is dir - inv_distance[z] * centers[k] (the point
+// seen from the camera centre, scaled by inv, which the projection ignores; inv = 0 leaves dir itself, bit for bit).  Same
+// quads, same stores; the output is dense, plane (k, z) at element (k * D + z) * width * height.
+template <bool EXACT>
+__global__ __launch_bounds__(256) void k_build_maps_sweep(const tscm_map_desc *__restrict__ maps, const int *__restrict__ kinds, const double *__restrict__ centers,
+                                                          const double *__restrict__ inv_distance, int D, float *__restrict__ mapx, float *__restrict__ mapy)
+{
+    const int cam = blockIdx.y / D, hyp = blockIdx.y - cam * D;
+    const tscm_map_desc m = maps[cam];
+    const int kind = kinds[cam];
+    const double inv = inv_distance[hyp], tx = centers[3 * cam], ty = centers[3 * cam + 1], tz = centers[3 * cam + 2];
+    const long long total = (long long)m.width * m.height;
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (total + 3) >> 2) return;
+    const long long num = 4 * q;
+    int i = (int)((double)num * fast_rcp((double)m.width));
+    int j = (int)(num - (long long)i * m.width);
+    if (j < 0) { --i; j += m.width; }
+    if (j >= m.width) { ++i; j -= m.width; }
+    const double beta = EXACT ? __ddiv_rn(m.intr[6], __dsub_rn(1.0, m.intr[6])) : m.intr[6] * fast_rcp(1.0 - m.intr[6]);
+    const double ifx = EXACT ? 0.0 : fast_rcp(m.fx), ify = EXACT ? 0.0 : fast_rcp(m.fy);
+    const long long base = (long long)blockIdx.y * total + 4 * q;
+    const int n = (int)min(4LL, total - 4 * q);
+    float ox[4], oy[4];
+    double rp, rq;
+    row_term<EXACT>(m, kind, ify, i, rp, rq);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double a = EXACT ? __ddiv_rn(__dsub_rn((double)j, m.cx), m.fx) : ((double)j - m.cx) * ifx;
+        double x, y, z;
+        if (kind == TSCM_PROJ_STEREOGRAPHIC) {
+            const double h = 0.25 * __builtin_fma(a, a, rp * rp);
+            const double ih = EXACT ? __ddiv_rn(1.0, 1.0 + h) : fast_rcp(1.0 + h);
+            x = a * ih; y = rp * ih; z = (1.0 - h) * ih;
+        } else {
+            double sa, ca;
+            sincos(a, &sa, &ca);
+            if (kind == TSCM_PROJ_LONGLAT) { x = sa; y = ca * rp; z = ca * rq; }
+            else if (kind == TSCM_PROJ_CYLINDRICAL) { x = sa; y = rp; z = ca; }
+            else { x = rq * sa; y = rp; z = rq * ca; }                      // EQUIRECT
+        }
+        if (EXACT) {
+            x = __dsub_rn(x, __dmul_rn(inv, tx)); y = __dsub_rn(y, __dmul_rn(inv, ty)); z = __dsub_rn(z, __dmul_rn(inv, tz));
+            map_ray_exact(m, beta, x, y, z, ox[k], oy[k]);
+        } else {
+            x = __builtin_fma(-inv, tx, x); y = __builtin_fma(-inv, ty, y); z = __builtin_fma(-inv, tz, z);
+            map_ray_fast(m, beta, x, y, z, ox[k], oy[k]);
+        }
+        if (++j == m.width) { j = 0; ++i; if (k < 3) row_term<EXACT>(m, kind, ify, i, rp, rq); }
+    }
+    if (n == 4 && (base & 3) == 0) {
+        *reinterpret_cast<float4 *>(mapx + base) = make_float4(ox[0], ox[1], ox[2], ox[3]);
+        *reinterpret_cast<float4 *>(mapy + base) = make_float4(oy[0], oy[1], oy[2], oy[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) { mapx[base + k] = ox[k]; mapy[base + k] = oy[k]; }
+    }
+}
+
 // tscm_rectify_points: one thread per pixel of the sampled camera -> its place in the output image of `m`
 __global__ __launch_bounds__(256) void k_rectify_points(const tscm_map_desc *__restrict__ map, int kind, const double *__restrict__ pixels, int n,
                                                         double *__restrict__ out, unsigned char *__restrict__ valid)
@@ -343,6 +405,72 @@ extern "C" int tscm_build_maps_ex(const tscm_map_desc *maps, const int *projecti
         pinholes = pinholes && projection[m] == TSCM_PROJ_PERSPECTIVE;
     }
     return build_maps_host(maps, pinholes ? nullptr : projection, n_maps, device, exact, mapx, mapy, n_elems, seconds_kernel);
+}
+
+extern "C" int tscm_build_sweep_maps(const tscm_map_desc *maps, const int *projection, int n_cameras, const double *centers, const double *inv_distance, int D,
+                                     int device, int exact, float *mapx, float *mapy, size_t n_elems, double *seconds_kernel)
+{
+    if (!maps) return tscm_set_error(TSCM_E_INVALID, "maps is NULL");
+    if (!projection) return tscm_set_error(TSCM_E_INVALID, "projection is NULL");
+    if (!centers) return tscm_set_error(TSCM_E_INVALID, "centers is NULL");
+    if (!inv_distance) return tscm_set_error(TSCM_E_INVALID, "inv_distance is NULL");
+    if (!mapx) return tscm_set_error(TSCM_E_INVALID, "mapx is NULL");
+    if (!mapy) return tscm_set_error(TSCM_E_INVALID, "mapy is NULL");
+    if (n_cameras < 1) return tscm_set_error(TSCM_E_INVALID, "n_cameras " + std::to_string(n_cameras) + " below 1");
+    if (D < 1) return tscm_set_error(TSCM_E_INVALID, "D " + std::to_string(D) + " below 1");
+    for (int k = 0; k < n_cameras; ++k) {
+        const tscm_map_desc &d = maps[k];
+        if (d.width < 0 || d.height < 0) return tscm_set_error(TSCM_E_INVALID, "maps[" + std::to_string(k) + "]: negative width or height");
+        if (d.width != maps[0].width || d.height != maps[0].height)
+            return tscm_set_error(TSCM_E_INVALID, "maps[" + std::to_string(k) + "]: width / height differ from maps[0]; the tables of a sweep share one output grid");
+        if (d.out_stride != d.width) return tscm_set_error(TSCM_E_INVALID, "maps[" + std::to_string(k) + "]: out_stride " + std::to_string(d.out_stride) + " is not width; the output is dense");
+        if (d.out_offset != 0) return tscm_set_error(TSCM_E_INVALID, "maps[" + std::to_string(k) + "]: out_offset is not 0; the output is dense");
+        if (!known_projection(projection[k])) return tscm_set_error(TSCM_E_INVALID, "projection[" + std::to_string(k) + "]: unknown projection kind " + std::to_string(projection[k]));
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(centers[3 * k + c])) return tscm_set_error(TSCM_E_INVALID, "centers[" + std::to_string(k) + "] is not finite");
+    }
+    for (int z = 0; z < D; ++z) {
+        if (!std::isfinite(inv_distance[z]) || inv_distance[z] < 0.0)
+            return tscm_set_error(TSCM_E_INVALID, "inv_distance[" + std::to_string(z) + "] is negative or not finite");
+        if (z > 0 && !(inv_distance[z] > inv_distance[z - 1])) return tscm_set_error(TSCM_E_INVALID, "inv_distance[" + std::to_string(z) + "] is not above its predecessor");
+    }
+    const unsigned long long total = (unsigned long long)maps[0].width * (unsigned long long)maps[0].height;
+    const unsigned long long planes = (unsigned long long)n_cameras * (unsigned long long)D;
+    if (total && planes > (unsigned long long)n_elems / total)
+        return tscm_set_error(TSCM_E_INVALID, "n_elems " + std::to_string(n_elems) + " below n_cameras * D * height * width");
+    for (int k = 0; k < n_cameras; ++k)
+        if (projection[k] == TSCM_PROJ_PERSPECTIVE) return tscm_set_error(TSCM_E_UNSUPPORTED, "projection[" + std::to_string(k) + "]: PERSPECTIVE (plane sweep) is not built");
+    if (planes > 65535) return tscm_set_error(TSCM_E_UNSUPPORTED, "more than 65535 tables in one call");
+    if (int rc = select_device(device, "tscm_build_sweep_maps")) return rc;
+    if (seconds_kernel) *seconds_kernel = 0.0;
+    if (total == 0) return 0;
+    const size_t n_out = (size_t)(planes * total);
+    DeviceMem mem;
+    const tscm_map_desc *d_maps = nullptr;
+    const int *d_kinds = nullptr;
+    const double *d_centers = nullptr, *d_inv = nullptr;
+    float *d_x = nullptr, *d_y = nullptr;
+    HIP_TRY(mem.upload(&d_maps, maps, (size_t)n_cameras));
+    HIP_TRY(mem.upload(&d_kinds, projection, (size_t)n_cameras));
+    HIP_TRY(mem.upload(&d_centers, centers, 3 * (size_t)n_cameras));
+    HIP_TRY(mem.upload(&d_inv, inv_distance, (size_t)D));
+    HIP_TRY(mem.alloc(&d_x, n_out)); HIP_TRY(mem.alloc(&d_y, n_out));
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, 0));
+    const dim3 grid((unsigned)(((total + 3) / 4 + 255) / 256), (unsigned)planes);
+    if (exact) hipLaunchKernelGGL(k_build_maps_sweep<true>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_centers, d_inv, D, d_x, d_y);
+    else hipLaunchKernelGGL(k_build_maps_sweep<false>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_centers, d_inv, D, d_x, d_y);
+    HIP_TRY(hipEventRecord(e1, 0));
+    HIP_TRY(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    HIP_TRY(hipGetLastError());
+    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    HIP_TRY(hipMemcpy(mapx, d_x, sizeof(float) * n_out, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mapy, d_y, sizeof(float) * n_out, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int tscm_rectify_points(const tscm_map_desc *map, int projection, const double *pixels, int n, int device, double *out, unsigned char *valid)

@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tscm_host.h"
+#include "tscm_remap_sample.h"
 
 #include <cstdint>
 #include <memory>
@@ -42,36 +43,7 @@ constexpr int kHaloW = kTileW / 2 + 2, kHaloH = kTileH / 2 + 2;
 struct Gains { unsigned short g[kMaxCameras]; };
 
 // ------------------------------------------------------------------------------------------------ sampling
-__device__ __forceinline__ void tap_weights(unsigned py, int (&wgt)[4])
-{
-    const int fx = py & 31, fy = (py >> 5) & 31;
-    wgt[0] = 32 * (32 - fx) * (32 - fy); wgt[1] = 32 * fx * (32 - fy); wgt[2] = 32 * (32 - fx) * fy; wgt[3] = 32 * fx * fy;
-    if (wgt[0] == 32768) { wgt[0] = 32767; wgt[3] = 1; }
-}
-
-// the arithmetic of k_remap for one output pixel of one image (rows of w * CH bytes)
-template <int CH>
-__device__ __forceinline__ void sample_px(const unsigned char *__restrict__ img, int w, int h, uint2 pk, int (&px)[CH])
-{
-    const int ix = (int)(short)(pk.x & 0xffffu), iy = (int)pk.x >> 16;
-    int wgt[4];
-    tap_weights(pk.y, wgt);
-    int acc[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) acc[c] = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int x = ix + (k & 1), y = iy + (k >> 1);
-        if (x >= 0 && x < w && y >= 0 && y < h) {
-            const unsigned char *q = img + ((size_t)y * w + x) * CH;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) acc[c] += wgt[k] * q[c];
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < CH; ++c) px[c] = max(0, min(255, (acc[c] + (1 << 14)) >> 15));
-}
-
+// tap_weights, sample_px: tscm_remap_sample.h
 __device__ __forceinline__ int apply_gain(int v, int g) { return min(255, (v * g + 128) >> 8); }
 
 // grid (ceil(npix / 256), n) x 256: the packed sample and a_k of camera blockIdx.y; weight_mask bit k: camera k has a

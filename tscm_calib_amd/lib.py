@@ -137,6 +137,12 @@ class CPanoramaParams(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int)]
 
 
+class CSweepParams(C.Structure):
+    """tscm_sweep_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("num_hypotheses", C.c_int), ("p1", C.c_int), ("p2", C.c_int), ("paths", C.c_int),
+                ("uniqueness_ratio", C.c_int), ("wrap_x", C.c_int)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -163,6 +169,8 @@ EXPORTS = [
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
     "tscm_panorama_default_params", "tscm_panorama_create", "tscm_panorama_compose", "tscm_panorama_stages", "tscm_panorama_overlap", "tscm_panorama_destroy",
+    "tscm_build_sweep_maps",
+    "tscm_sweep_default_params", "tscm_sweep_create", "tscm_sweep_depth", "tscm_sweep_stages", "tscm_sweep_stage_times", "tscm_sweep_points", "tscm_sweep_destroy",
 ]
 
 
@@ -271,6 +279,16 @@ def lib():
     L.tscm_panorama_overlap.argtypes = [vp, vpp, C.c_int, llp, llp]
     L.tscm_panorama_destroy.argtypes = [vp]
     L.tscm_panorama_destroy.restype = None
+    L.tscm_build_sweep_maps.argtypes = [C.POINTER(CMapDesc), ip, C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, fp, fp, C.c_size_t, dp]
+    L.tscm_sweep_default_params.argtypes = [C.POINTER(CSweepParams)]
+    L.tscm_sweep_default_params.restype = None
+    L.tscm_sweep_create.argtypes = [C.c_int, C.c_int, C.c_int, vpp, fp, fp, C.c_int, C.c_int, C.POINTER(CSweepParams), C.c_int, vpp]
+    L.tscm_sweep_depth.argtypes = [vp, vpp, C.c_int, shp, C.c_int, dp]
+    L.tscm_sweep_stages.argtypes = [vp, vpp, C.c_int, ubp, ubp, C.POINTER(C.c_ulonglong), ubp, usp]
+    L.tscm_sweep_stage_times.argtypes = [dp]
+    L.tscm_sweep_points.argtypes = [shp, C.c_int, C.c_int, C.c_int, C.POINTER(CMapDesc), C.c_int, dp, C.c_int, C.c_int, dp, ubp]
+    L.tscm_sweep_destroy.argtypes = [vp]
+    L.tscm_sweep_destroy.restype = None
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]
     L.tscm_poses_from_r1r2t.argtypes = [dp, C.c_void_p, C.c_int, dp]
     L.tscm_estimate_extrinsic.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip]

@@ -1,7 +1,8 @@
 """Remap tables: host-side mirror of TripleSphereCamera::undistort (TS.cpp:284-306), the table of
 undistort_chessboard (TS.cpp:308-330) and Remap::init_remap (EpipolarRectify/rectify.cpp:86-199),
 all built by tscm_build_maps on the device; output images that are not pinholes (long-lat, cylindrical,
-stereographic, equirect: tscm_build_maps_ex) and the point direction tscm_rectify_points."""
+stereographic, equirect: tscm_build_maps_ex), the tables of a sphere sweep (tscm_build_sweep_maps) and the point direction
+tscm_rectify_points."""
 from __future__ import annotations
 
 import ctypes as C
@@ -166,6 +167,25 @@ def build_maps(descs, n_elems: int | None = None, device: int = 0, exact: bool =
         return mapx, mapy, sec.value
     _lib.check(_lib.lib().tscm_build_maps(arr, len(descs), device, 1 if exact else 0, mapx.ctypes.data_as(fp),
                                            mapy.ctypes.data_as(fp), n_elems, C.cast(C.byref(sec), C.POINTER(C.c_double))))
+    return mapx, mapy, sec.value
+
+
+def build_sweep_maps(descs, centers, inv_distance, device: int = 0, exact: bool = True):
+    """tscm_build_sweep_maps -> mapx, mapy (float32 [n, D, height, width]), seconds_kernel.  descs: one table per camera on
+    one output grid (panorama_descs); centers [n, 3]: the camera centres in the output frame (Twc[:, :, 3]); inv_distance
+    [D]: non-negative and strictly increasing, 0 = infinity."""
+    centers = np.ascontiguousarray(centers, dtype=np.float64).reshape(-1, 3)
+    inv = np.ascontiguousarray(inv_distance, dtype=np.float64).ravel()
+    n, D = len(descs), inv.size
+    if centers.shape[0] != n:
+        raise ValueError(f"{n} tables need {n} centres")
+    h, w = (descs[0].height, descs[0].width) if n else (0, 0)
+    mapx, mapy = np.zeros((n, D, h, w), dtype=np.float32), np.zeros((n, D, h, w), dtype=np.float32)
+    fp = C.POINTER(C.c_float)
+    sec = C.c_double(0.0)
+    kinds = [projection_kind(d.projection) for d in descs]
+    _lib.check(_lib.lib().tscm_build_sweep_maps(_c_descs(descs), (C.c_int * max(n, 1))(*kinds), n, _lib.dptr(centers), _lib.dptr(inv), D, device,
+                                                 1 if exact else 0, mapx.ctypes.data_as(fp), mapy.ctypes.data_as(fp), mapx.size, C.byref(sec)))
     return mapx, mapy, sec.value
 
 

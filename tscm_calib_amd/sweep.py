@@ -1,0 +1,193 @@
+"""Sphere-sweep depth of a calibrated rig (tscm.h: tscm_sweep_*): Sweeper keeps the n x D packed sweep tables on the device
+and gives one index map per frame -- 16 x the winning inverse-distance hypothesis of every panorama pixel -- and its 3-D
+points in the rig frame; rig_depth does it in one call."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import lib as _lib
+from . import maps as _maps
+
+INVALID = -16
+
+
+def params(**over) -> _lib.CSweepParams:
+    """tscm_sweep_default_params with fields replaced: num_hypotheses, p1, p2, paths, uniqueness_ratio, wrap_x."""
+    p = _lib.CSweepParams()
+    _lib.lib().tscm_sweep_default_params(C.byref(p))
+    for k, v in over.items():
+        if k == "struct_size" or not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v))
+    return p
+
+
+def inverse_distances(near: float, far: float = np.inf, D: int = 64) -> np.ndarray:
+    """D hypotheses uniform in inverse distance, index 0 = far (inverse distance 0 for far = inf), index D - 1 = near."""
+    if not (near > 0 and far > near):
+        raise ValueError("0 < near < far")
+    return np.linspace(0.0 if np.isinf(far) else 1.0 / far, 1.0 / near, int(D))
+
+
+class Sweeper:
+    """Context manager around a tscm_sweep handle: Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv_distance, ...)
+    builds the tables through maps.panorama_descs / maps.build_sweep_maps, Sweeper.from_tables(mapx, mapy, size, ...) takes
+    tables [n, D, pano_h, pano_w] of the caller's.  size = (width, height) of the grey source images.  weights: None (all
+    255), "radial" (from_rig: panorama.radial_weights per camera) or n arrays [height, width] uint8 (entries may be None)."""
+
+    def __init__(self):
+        raise TypeError("use Sweeper.from_rig or Sweeper.from_tables")
+
+    @classmethod
+    def from_tables(cls, mapx, mapy, size, weights=None, device: int = 0, pano_desc=None, inv_distance=None, **over):
+        self = cls.__new__(cls)
+        self._handle = None
+        mapx, mapy = np.ascontiguousarray(mapx, dtype=np.float32), np.ascontiguousarray(mapy, dtype=np.float32)
+        if mapx.ndim != 4 or mapx.shape != mapy.shape:
+            raise ValueError("mapx and mapy are [n, D, pano_h, pano_w] tables of the same shape")
+        self.n, self.D, self.pano_h, self.pano_w = mapx.shape
+        self.width, self.height, self.device = int(size[0]), int(size[1]), int(device)
+        self.params = params(num_hypotheses=self.D, **over)
+        self.pano_desc = pano_desc
+        self.inv_distance = None if inv_distance is None else np.ascontiguousarray(inv_distance, dtype=np.float64).ravel()
+        if self.inv_distance is not None and self.inv_distance.size != self.D:
+            raise ValueError(f"{self.D} tables per camera need {self.D} inverse distances")
+        wptr = None
+        self.weights = None
+        if weights is not None:
+            if len(weights) != self.n:
+                raise ValueError(f"{self.n} cameras need {self.n} weight entries")
+            self.weights = [None if x is None else np.ascontiguousarray(x, dtype=np.uint8) for x in weights]
+            for x in self.weights:
+                if x is not None and x.shape != (self.height, self.width):
+                    raise ValueError("a weight image has the shape [height, width] of the source images")
+            wptr = (C.c_void_p * self.n)(*[None if x is None else x.ctypes.data for x in self.weights])
+        fp = C.POINTER(C.c_float)
+        hdl = C.c_void_p()
+        _lib.check(_lib.lib().tscm_sweep_create(self.n, self.width, self.height, wptr, mapx.ctypes.data_as(fp), mapy.ctypes.data_as(fp), self.pano_w, self.pano_h,
+                                                C.byref(self.params), self.device, C.byref(hdl)))
+        self._handle = hdl
+        return self
+
+    @classmethod
+    def from_rig(cls, intr, Twc, size, pano_w: int, pano_h: int, inv_distance, weights=None, projection="equirect", device: int = 0, exact: bool = True,
+                 max_theta: float = np.radians(100.0), keep_tables: bool = False, **over):
+        intr = np.asarray(intr, dtype=np.float64).reshape(-1, 9)
+        Twc = np.asarray(Twc, dtype=np.float64).reshape(-1, 3, 4)
+        descs = _maps.panorama_descs(intr, Twc, int(pano_w), int(pano_h), projection)
+        mapx, mapy, _ = _maps.build_sweep_maps(descs, Twc[:, :, 3], inv_distance, device=device, exact=exact)
+        if isinstance(weights, str):
+            if weights != "radial":
+                raise ValueError("weights: 'radial', None or one array per camera")
+            from . import panorama
+            weights = [panorama.radial_weights(intr[k], int(size[0]), int(size[1]), max_theta, device=device) for k in range(len(descs))]
+        over.setdefault("wrap_x", 1)
+        self = cls.from_tables(mapx, mapy, size, weights=weights, device=device, pano_desc=descs[0], inv_distance=inv_distance, **over)
+        if keep_tables:
+            self.mapx, self.mapy = mapx, mapy
+        return self
+
+    # ------------------------------------------------------------------ lifetime
+    def close(self):
+        if self._handle is not None:
+            _lib.lib().tscm_sweep_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ frames
+    def _frame(self, images):
+        if self._handle is None:
+            raise ValueError("the sweeper is closed")
+        if len(images) != self.n:
+            raise ValueError(f"{self.n} cameras need {self.n} images")
+        imgs = []
+        for x in images:
+            a = np.asarray(x)
+            if a.dtype != np.uint8 or a.shape != (self.height, self.width):
+                raise ValueError(f"images are uint8 arrays of shape {(self.height, self.width)}")
+            imgs.append(a if a.strides[1] == 1 and a.strides[0] >= self.width else np.ascontiguousarray(a))
+        if len({a.strides[0] for a in imgs}) > 1:
+            imgs = [np.ascontiguousarray(a) for a in imgs]
+        return imgs, (C.c_void_p * self.n)(*[a.ctypes.data for a in imgs]), int(imgs[0].strides[0])
+
+    def depth(self, images, out: np.ndarray | None = None, with_seconds: bool = False):
+        """tscm_sweep_depth -> int16 [pano_h, pano_w]: 16 x the hypothesis index with its sub-index term, INVALID = -16.
+        `out` may be a row-padded view, whose padding keeps its values."""
+        imgs, ptrs, stride = self._frame(images)
+        if out is None:
+            out = np.zeros((self.pano_h, self.pano_w), dtype=np.int16)
+        if out.dtype != np.int16 or out.shape != (self.pano_h, self.pano_w) or out.strides[1] != 2 or out.strides[0] % 2:
+            raise ValueError("out must be an int16 array (or row-padded view) of the panorama's shape")
+        sec = C.c_double(0.0)
+        _lib.check(_lib.lib().tscm_sweep_depth(self._handle, ptrs, stride, out.ctypes.data_as(C.POINTER(C.c_short)), int(out.strides[0] // 2), C.byref(sec)))
+        return (out, sec.value) if with_seconds else out
+
+    def stages(self, images) -> dict:
+        """tscm_sweep_stages -> sampled, alpha [n, D, ph, pw] uint8, census alike uint64, cost [ph, pw, D] uint8, aggregated
+        alike uint16."""
+        imgs, ptrs, stride = self._frame(images)
+        n, D, ph, pw = self.n, self.D, self.pano_h, self.pano_w
+        res = dict(sampled=np.zeros((n, D, ph, pw), np.uint8), alpha=np.zeros((n, D, ph, pw), np.uint8), census=np.zeros((n, D, ph, pw), np.uint64),
+                   cost=np.zeros((ph, pw, D), np.uint8), aggregated=np.zeros((ph, pw, D), np.uint16))
+        ub = C.POINTER(C.c_ubyte)
+        _lib.check(_lib.lib().tscm_sweep_stages(self._handle, ptrs, stride, res["sampled"].ctypes.data_as(ub), res["alpha"].ctypes.data_as(ub),
+                                                res["census"].ctypes.data_as(C.POINTER(C.c_ulonglong)), res["cost"].ctypes.data_as(ub),
+                                                res["aggregated"].ctypes.data_as(C.POINTER(C.c_ushort))))
+        return res
+
+    def stage_times(self) -> np.ndarray:
+        """Device seconds of the last depth / stages call: cost volume, aggregation, winner."""
+        t = np.zeros(3)
+        _lib.check(_lib.lib().tscm_sweep_stage_times(_lib.dptr(t)))
+        return t
+
+    def points(self, index16):
+        """tscm_sweep_points with the panorama and the inverse distances the sweeper was built from (from_rig, or from_tables
+        with pano_desc and inv_distance) -> (points [ph, pw, 3] in the rig frame, valid [ph, pw] bool)."""
+        if self.pano_desc is None or self.inv_distance is None:
+            raise ValueError("points need the panorama's descriptor and the inverse distances")
+        return points(index16, self.pano_desc, self.inv_distance, device=self.device)
+
+
+def points(index16, pano_desc, inv_distance, device: int = 0):
+    """tscm_sweep_points -> (points [h, w, 3] float64 in the rig frame, NaN where invalid; valid [h, w] bool)."""
+    idx = np.asarray(index16)
+    if idx.dtype != np.int16 or idx.ndim != 2 or idx.strides[1] != 2 or idx.strides[0] % 2:
+        raise ValueError("index16 is an int16 [h, w] array (or row-padded view)")
+    h, w = idx.shape
+    inv = np.ascontiguousarray(inv_distance, dtype=np.float64).ravel()
+    pts, valid = np.zeros((h, w, 3)), np.zeros((h, w), dtype=np.uint8)
+    _lib.check(_lib.lib().tscm_sweep_points(idx.ctypes.data_as(C.POINTER(C.c_short)), w, h, int(idx.strides[0] // 2) if h else w, _maps._c_descs([pano_desc]),
+                                            _maps.projection_kind(pano_desc.projection), _lib.dptr(inv), inv.size, device, _lib.dptr(pts),
+                                            valid.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return pts, valid.astype(bool)
+
+
+def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: float = 500.0, far: float = np.inf, D: int = 64, weights="radial",
+              projection="equirect", device: int = 0, post=None, **over):
+    """One call from a calibration and a frame to (index16 [ph, pw], points [ph, pw, 3] in the rig frame, valid [ph, pw]).
+    near / far in the units of Twc's translations.  post: keyword arguments of stereo.filter (speckle_window_size,
+    speckle_range, median), applied to the index map before the points; an index map is a disparity map with
+    min_disparity = 0."""
+    size = (np.asarray(images[0]).shape[1], np.asarray(images[0]).shape[0])
+    inv = inverse_distances(near, far, D)
+    with Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv, weights=weights, projection=projection, device=device, **over) as s:
+        idx = s.depth(images)
+        if post:
+            from . import stereo
+            idx = stereo.filter(idx, min_disparity=0, device=device, **post)
+        pts, valid = s.points(idx)
+    return idx, pts, valid
