@@ -1,0 +1,107 @@
+// sweep_panorama_demo.cpp -- the parallax-free panorama of a calibrated rig: the sphere sweep gives the depth of every
+// panorama pixel (tscm_sweep_depth, on the grey values of the frame), and the frame is blended at that depth
+// (tscm_sweep_compose) instead of at infinity, so that near objects are not doubled where two cameras overlap.
+// Images are binary PGM (P5, grey) or PPM (P6, read as 3 channels in file order) files of one size and kind, one per camera.
+//   usage: sweep_panorama_demo calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8]
+//                              [--mode seam|feather|multiband] [--levels L]
+// writes sweep_panorama.pgm or .ppm into the working directory.  near: in the units of the calibration's translations.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "tscm/tscm_calib.hpp"
+
+// P5 -> 1 channel, P6 -> 3 channels
+static bool read_pnm(const char *path, std::vector<unsigned char> &pix, int &w, int &h, int &channels)
+{
+    std::ifstream f(path, std::ios::binary);
+    std::string magic;
+    int maxval = 0;
+    if (!(f >> magic >> w >> h >> maxval) || (magic != "P5" && magic != "P6") || maxval != 255 || w < 1 || h < 1) return false;
+    f.get();
+    channels = magic == "P5" ? 1 : 3;
+    pix.resize((size_t)w * h * channels);
+    f.read(reinterpret_cast<char *>(pix.data()), (std::streamsize)pix.size());
+    return (size_t)f.gcount() == pix.size();
+}
+
+int main(int argc, char **argv)
+{
+    std::vector<const char *> files;
+    tscm::Size pano = { 1024, 512 };
+    double near = 500.0;
+    tscm_sweep_params params;
+    tscm_sweep_default_params(&params);
+    tscm_sweep_compose_params blend;
+    tscm_sweep_compose_default_params(&blend);
+    bool bad = false;
+    for (int a = 2; a < argc; ++a) {
+        if (!std::strcmp(argv[a], "--size") && a + 2 < argc) { pano.width = std::atoi(argv[a + 1]); pano.height = std::atoi(argv[a + 2]); a += 2; }
+        else if (!std::strcmp(argv[a], "--near") && a + 1 < argc) near = std::atof(argv[++a]);
+        else if (!std::strcmp(argv[a], "--hypotheses") && a + 1 < argc) params.num_hypotheses = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--paths") && a + 1 < argc) params.paths = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--levels") && a + 1 < argc) blend.levels = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--mode") && a + 1 < argc) {
+            const std::string m = argv[++a];
+            if (m == "seam") blend.mode = TSCM_PANO_SEAM;
+            else if (m == "feather") blend.mode = TSCM_PANO_FEATHER;
+            else if (m == "multiband") blend.mode = TSCM_PANO_MULTIBAND;
+            else bad = true;
+        } else files.push_back(argv[a]);
+    }
+    if (bad || argc < 4 || files.size() < 2 || !(near > 0.0) || params.num_hypotheses < 2) {
+        std::fprintf(stderr, "usage: %s calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--mode seam|feather|multiband] [--levels L]\n",
+                     argv[0]);
+        return 2;
+    }
+    try {
+        enum { kMaxCameras = 8 };
+        std::vector<double> intr(9 * kMaxCameras), Twc(12 * kMaxCameras);
+        int n = 0;
+        tscm::check(tscm_yaml_read(argv[1], kMaxCameras, &n, intr.data(), Twc.data()));
+        if ((int)files.size() != n) { std::fprintf(stderr, "%s has %d cameras, %d images given\n", argv[1], n, (int)files.size()); return 2; }
+        std::vector<std::vector<unsigned char> > img((size_t)n), grey((size_t)n);
+        std::vector<const unsigned char *> ptr((size_t)n), gptr((size_t)n);
+        tscm::Size size = { 0, 0 };
+        int channels = 0;
+        for (int k = 0; k < n; ++k) {
+            int w = 0, h = 0, ch = 0;
+            if (!read_pnm(files[(size_t)k], img[(size_t)k], w, h, ch)) { std::fprintf(stderr, "%s: not a binary 8-bit PGM or PPM\n", files[(size_t)k]); return 2; }
+            if (k && (w != size.width || h != size.height || ch != channels)) { std::fprintf(stderr, "%s: the images differ in size or kind\n", files[(size_t)k]); return 2; }
+            size.width = w; size.height = h; channels = ch;
+            ptr[(size_t)k] = img[(size_t)k].data();
+            // the depth pass works on grey values: the composer's BGR2GRAY integers on the three bytes in file order
+            if (ch == 3) {
+                grey[(size_t)k].resize((size_t)w * h);
+                for (size_t t = 0; t < grey[(size_t)k].size(); ++t) {
+                    const unsigned char *q = &img[(size_t)k][3 * t];
+                    grey[(size_t)k][t] = (unsigned char)((q[0] * 1868 + q[1] * 9617 + q[2] * 4899 + (1 << 13)) >> 14);
+                }
+                gptr[(size_t)k] = grey[(size_t)k].data();
+            } else gptr[(size_t)k] = ptr[(size_t)k];
+        }
+        // uniform in inverse distance, index 0 = infinity: a pixel without depth is composed there (fallback_index 0)
+        const int D = params.num_hypotheses;
+        std::vector<double> inv((size_t)D);
+        for (int z = 0; z < D; ++z) inv[(size_t)z] = (double)z / ((double)(D - 1) * near);
+        tscm::Sweep sweep(n, intr.data(), Twc.data(), size, pano, inv, &params);
+        double sec_depth = 0.0, sec_compose = 0.0;
+        const std::vector<short> index16 = sweep.depth(gptr.data(), 0, &sec_depth);
+        const std::vector<unsigned char> out = sweep.compose(ptr.data(), channels, NULL, &blend, NULL, 0, NULL, &sec_compose);
+        size_t n_valid = 0;
+        for (size_t t = 0; t < index16.size(); ++t) n_valid += index16[t] >= 0;
+        const char *name = channels == 1 ? "sweep_panorama.pgm" : "sweep_panorama.ppm";
+        std::ofstream f(name, std::ios::binary);
+        f << (channels == 1 ? "P5\n" : "P6\n") << pano.width << " " << pano.height << "\n255\n";
+        f.write(reinterpret_cast<const char *>(out.data()), (std::streamsize)out.size());
+        std::printf("%s: %d x %d from %d cameras, %d hypotheses, %zu pixels with depth, kernels %.3f ms depth + %.3f ms compose\n", name, pano.width, pano.height, n, D,
+                    n_valid, 1e3 * sec_depth, 1e3 * sec_compose);
+        return f ? 0 : 1;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "%s\n", e.what());
+        return 1;
+    }
+}

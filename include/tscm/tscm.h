@@ -987,6 +987,54 @@ int tscm_sweep_points(const short *index16, int pano_w, int pano_h, int stride, 
                       const double *inv_distance /* [D] */, int D, int device_index,
                       double *points /* [h*w*3], rig frame */, unsigned char *valid /* [h*w] */);
 
+/* The frame composed at the swept depth.  tscm_panorama_compose samples every camera through its table at infinity, so
+ * whatever is nearer than a few tens of metres is doubled where two cameras overlap; the handle already keeps the record of
+ * every camera, hypothesis and panorama pixel, the same 8-byte record with its alpha, so the frame can be composed at the
+ * hypothesis the index map names.  Integer arithmetic throughout, restated in tests/sweep_compose_ref.py.
+ *   hypothesis z(i, j) = index16(i, j) < 0 ? fallback_index : min(D - 1, (index16(i, j) + 8) >> 4): the nearest hypothesis,
+ *              no interpolation between two.  Any int16 map is accepted, the raw one of tscm_sweep_depth or one filtered
+ *              by tscm_stereo_filter.
+ *   sample     v_k(i, j)[c] = the panorama's `sample` rule on the record (k, z(i, j)) at pixel (i, j), on the caller's
+ *              images of 1 or 3 channels (they need not be the grey images of the depth pass), then the Q8 gain;
+ *              a_k(i, j) = that record's alpha.
+ *   blending   label, coverage, SEAM, FEATHER and MULTIBAND (masks, reduce, expand, floor division, collapse, wrap_x) are
+ *              the panorama's rules on these v_k and a_k, unchanged.  Labels, coverage and the mask pyramids therefore
+ *              depend on the frame.
+ * So with a constant map 16 z0 the output equals tscm_panorama_compose on the tables (., z0) byte for byte, and with
+ * inv_distance[0] = 0, an all-invalid map and fallback_index = 0 it equals today's panorama at infinity.
+ * Stage outputs: hypothesis [pano_h][pano_w] uint8; sampled [n][pano_h][pano_w][C] (after the gain), alpha
+ * [n][pano_h][pano_w], label [pano_h][pano_w]; the pyramids as tscm_panorama_stages lays them out; any of them may be NULL.
+ * index16 == NULL: the map of this handle's last tscm_sweep_depth, which is still on the device.  The composer's buffers are
+ * allocated by the first call and again only when (channels, mode, levels) changes; tscm_sweep_create and tscm_sweep_depth
+ * are as before.
+ * Refused with TSCM_E_INVALID, the text naming the argument, a NULL handle before any device is touched: what
+ * tscm_panorama_compose refuses (a required pointer that is NULL, channels other than 1 or 3, stride < width * channels,
+ * dst_stride < pano_w * channels, an unknown mode, levels outside 1..6 and pano_w or pano_h no multiple of 2^levels in
+ * MULTIBAND, a gain outside 1..4095, a pyramid output of the stages call when the mode is not MULTIBAND, a wrong
+ * struct_size), a fallback_index outside 0..D - 1, index_stride < pano_w, a NULL index16 on a handle that has not run
+ * tscm_sweep_depth.  Bytes of dst between pano_w * channels and dst_stride keep the caller's values. */
+typedef struct tscm_sweep_compose_params {
+    int struct_size;        /* sizeof(tscm_sweep_compose_params)                                */
+    int mode;               /* TSCM_PANO_*                                                      */
+    int levels;             /* MULTIBAND: 1..6, otherwise ignored                               */
+    int wrap_x;             /* 1: the pyramids wrap over the column ends                        */
+    int fallback_index;     /* 0..D - 1: the hypothesis of an invalid pixel                     */
+} tscm_sweep_compose_params;
+void tscm_sweep_compose_default_params(tscm_sweep_compose_params *p);   /* MULTIBAND, 4, 1, 0 */
+
+int tscm_sweep_compose(tscm_sweep *s, const unsigned char *const *images /* [n] of [height][stride] */, int stride, int channels,
+                       const short *index16 /* [pano_h][index_stride], or NULL */, int index_stride,
+                       const tscm_sweep_compose_params *params, const unsigned short *gain_q8 /* [n], NULL = 256 */,
+                       unsigned char *dst /* [pano_h][dst_stride] */, int dst_stride,
+                       unsigned char *coverage /* [pano_h][pano_w], may be NULL */, double *seconds_kernel);
+
+/* The stages of the same kernels, for parity tests. */
+int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *const *images, int stride, int channels,
+                              const short *index16, int index_stride, const tscm_sweep_compose_params *params,
+                              const unsigned short *gain_q8, unsigned char *hypothesis, unsigned char *sampled,
+                              unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid,
+                              short *blend_pyramid);
+
 void tscm_sweep_destroy(tscm_sweep *s);
 
 #ifdef __cplusplus

@@ -875,6 +875,26 @@ public:
         check(tscm_sweep_depth(handle_, images, stride ? stride : image_.width, out.data(), pano_.width, seconds_kernel));
         return out;
     }
+    // The frame blended at the hypothesis the index map names per pixel (tscm_sweep_compose): the panorama without the parallax
+    // of a composition at infinity.  images: n rows-of-`stride`-bytes images of `channels` (1 or 3) bytes per pixel (stride 0:
+    // image width * channels); index16: a map of depth(), raw or filtered, or NULL for the one the last depth() left on the
+    // device; params == NULL: tscm_sweep_compose_default_params; gain_q8: NULL or n Q8 gains
+    // -> pano_size.height rows of pano_size.width * channels bytes
+    std::vector<unsigned char> compose(const unsigned char *const *images, int channels, const std::vector<short> *index16 = NULL,
+                                       const tscm_sweep_compose_params *params = NULL, const unsigned short *gain_q8 = NULL, int stride = 0,
+                                       std::vector<unsigned char> *coverage = NULL, double *seconds_kernel = NULL)
+    {
+        if (index16 && index16->size() != (size_t)pano_.width * pano_.height) throw std::runtime_error("tscm: the index map does not have the panorama's size");
+        tscm_sweep_compose_params p;
+        if (params) p = *params;
+        else tscm_sweep_compose_default_params(&p);
+        const int row = pano_.width * channels;
+        std::vector<unsigned char> out((size_t)(row > 0 ? row : 0) * pano_.height);
+        if (coverage) coverage->assign((size_t)pano_.width * pano_.height, 0);
+        check(tscm_sweep_compose(handle_, images, stride ? stride : image_.width * channels, channels, index16 ? index16->data() : NULL, pano_.width, &p, gain_q8,
+                                 out.data(), row, coverage ? coverage->data() : NULL, seconds_kernel));
+        return out;
+    }
     // the points of an index map of depth() in the rig frame; NaN and valid[k] = 0 where invalid or at infinity
     std::vector<Point3d> points(const std::vector<short> &index16, std::vector<unsigned char> &valid) const;
     int cameras() const { return n_; }

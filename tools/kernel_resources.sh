@@ -14,7 +14,7 @@ for blk in re.split(r'\n  - \.agpr_count', txt)[1:]:
     blk = '.agpr_count' + blk
     g = lambda k: (re.search(r'\.' + k + r':\s+(\S+)', blk) or [None, '?'])[1]
     name = subprocess.run(['c++filt', g('name')], capture_output=True, text=True).stdout.strip()
-    name = re.sub(r'\(.*', '', name).replace('void ', '').replace('tscm::', '')
+    name = re.sub(r'\(.*', '', name.replace('(anonymous namespace)::', '')).replace('void ', '').replace('tscm::', '')
     if re.search(r'''$pat''', name):
         print(f\"{name:48s} vgpr {g('vgpr_count'):>4s} agpr {g('agpr_count'):>4s} sgpr {g('sgpr_count'):>4s}  lds {g('group_segment_fixed_size'):>6s}  scratch {g('private_segment_fixed_size'):>5s}  spills v{g('vgpr_spill_count')} s{g('sgpr_spill_count')}\")
 "

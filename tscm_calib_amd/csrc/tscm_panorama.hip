@@ -13,17 +13,15 @@
 //                    samples with 4- to 16-byte loads, skips a camera that no lane of the wave needs (ballot), and stores 4
 //                    or 12 packed output bytes; no per-camera plane is written
 //   k_pano_sample    MULTIBAND: G^0 of every camera and channel as int16 planes, 4 pixels per thread
-//   k_pano_reduce    32 x 8 outputs per block from a 67 x 19 halo tile in LDS; the halo load clamps rows and wraps columns
-//   k_pano_lapblend  64 x 16 tile of level l: per camera the 34 x 10 coarse halo of G^(l+1) in LDS, Lap = G^l - E(.) in
-//                    registers, the weighted sum over the cameras, the floor division by W^l; a camera whose mask is zero
-//                    over the whole tile is skipped
-//   k_pano_collapse  R^l = B^l + E(R^(l+1)) in place; at level 0 the clamp, the coverage rule and the interleaved bytes
+//   k_pano_reduce, k_pano_lapblend, k_pano_collapse (and k_pano_wsum at create): tscm_pano_kernels.h, shared with the
+//                    sweep's composer
 //   k_pano_overlap   count / sum of the camera pairs: LDS partials per block, then 64-bit integer atomics
 #include "tscm/tscm.h"
 
 #include <hip/hip_runtime.h>
 
 #include "tscm_host.h"
+#include "tscm_pano_kernels.h"
 #include "tscm_remap_sample.h"
 
 #include <cstdint>
@@ -35,16 +33,10 @@ using namespace tscm;
 
 namespace {
 
-constexpr int kMaxCameras = 16, kMaxLevels = 6;
-constexpr int kRedW = 32, kRedH = 8;          // k_pano_reduce: outputs per block
-constexpr int kTileW = 64, kTileH = 16;       // k_pano_lapblend / k_pano_collapse: fine pixels per block
-constexpr int kHaloW = kTileW / 2 + 2, kHaloH = kTileH / 2 + 2;
-
-struct Gains { unsigned short g[kMaxCameras]; };
+constexpr int kMaxCameras = kPanoMaxCameras, kMaxLevels = kPanoMaxLevels;
 
 // ------------------------------------------------------------------------------------------------ sampling
-// tap_weights, sample_px: tscm_remap_sample.h
-__device__ __forceinline__ int apply_gain(int v, int g) { return min(255, (v * g + 128) >> 8); }
+// tap_weights, sample_px: tscm_remap_sample.h; Gains, apply_gain: tscm_pano_kernels.h
 
 // grid (ceil(npix / 256), n) x 256: the packed sample and a_k of camera blockIdx.y; weight_mask bit k: camera k has a
 // weight image (at wimg + k * w * h), otherwise a constant 255 inside the image
@@ -89,37 +81,6 @@ __global__ __launch_bounds__(256) void k_pano_label(const unsigned char *__restr
     label[t] = (unsigned char)lab; cover[t] = (unsigned char)cnt; mask[t] = (unsigned short)bits;
     if (mpyr)
         for (int k = 0; k < n; ++k) mpyr[k * Sp + t] = lab == k ? 255 : 0;
-}
-
-// W = sum_k M_k over a whole pyramid plane (padding included: zero)
-__global__ __launch_bounds__(256) void k_pano_wsum(const unsigned char *__restrict__ mpyr, int n, size_t Sp, unsigned short *__restrict__ wsum)
-{
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= Sp) return;
-    int s = 0;
-    for (int k = 0; k < n; ++k) s += mpyr[k * Sp + t];
-    wsum[t] = (unsigned short)s;
-}
-
-// 4 or 12 output bytes of a quad: packed 32-bit stores when the quad is whole and its first byte is 4-aligned
-template <int CH>
-__device__ __forceinline__ void store_quad(unsigned char *__restrict__ out, size_t first_px, int nv, const int (&v)[4][CH])
-{
-    unsigned char b[4 * CH];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int c = 0; c < CH; ++c) b[e * CH + c] = (unsigned char)v[e][c];
-    unsigned char *q = out + first_px * CH;
-    if (nv == 4 && (reinterpret_cast<uintptr_t>(q) & 3) == 0) {
-#pragma unroll
-        for (int i = 0; i < CH; ++i)
-            reinterpret_cast<unsigned *>(q)[i] = (unsigned)b[4 * i] | ((unsigned)b[4 * i + 1] << 8) | ((unsigned)b[4 * i + 2] << 16) | ((unsigned)b[4 * i + 3] << 24);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4 * CH; ++i)
-            if (i < nv * CH) q[i] = b[i];
-    }
 }
 
 // grid ceil(npix / 1024) x 256: quad q = output pixels [4q, 4q + 4) of the flat panorama
@@ -209,175 +170,6 @@ __global__ __launch_bounds__(256) void k_pano_sample(const uint2 *__restrict__ p
     }
 }
 
-// ------------------------------------------------------------------------------------------------ pyramids
-__device__ __forceinline__ int col_index(int c, int W, int wrap) { return wrap ? ((c % W) + W) % W : min(max(c, 0), W - 1); }
-
-// grid (ceil(dw / 32), ceil(dh / 8), planes) x 256: level (sw x sh at soff) -> level (sw / 2 x sh / 2 at doff) of every plane
-template <typename T>
-__global__ __launch_bounds__(256) void k_pano_reduce(T *__restrict__ pyr, int sw, int sh, size_t stride, size_t soff, size_t doff, int wrap)
-{
-    constexpr int LW = 2 * kRedW + 3, LH = 2 * kRedH + 3;
-    __shared__ int tile[LH][LW + 1];
-    const int dw = sw >> 1, dh = sh >> 1;
-    const int x0 = blockIdx.x * kRedW, y0 = blockIdx.y * kRedH;
-    const T *src = pyr + (size_t)blockIdx.z * stride + soff;
-    for (int e = threadIdx.x; e < LW * LH; e += 256) {
-        const int ty = e / LW, tx = e - ty * LW;
-        const int gy = min(max(2 * y0 - 2 + ty, 0), sh - 1), gx = col_index(2 * x0 - 2 + tx, sw, wrap);
-        tile[ty][tx] = (int)src[(size_t)gy * sw + gx];
-    }
-    __syncthreads();
-    const int tx = threadIdx.x & (kRedW - 1), ty = threadIdx.x / kRedW;
-    if (x0 + tx >= dw || y0 + ty >= dh) return;
-    const int t[5] = { 1, 4, 6, 4, 1 };
-    int acc = 0;
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-#pragma unroll
-        for (int b = 0; b < 5; ++b) acc += t[a] * t[b] * tile[2 * ty + a][2 * tx + b];
-    pyr[(size_t)blockIdx.z * stride + doff + (size_t)(y0 + ty) * dw + x0 + tx] = (T)((acc + 128) >> 8);
-}
-
-// the coarse halo of a 64 x 16 fine tile at (x0, y0): coarse rows y0 / 2 - 1 .. y0 / 2 + 8, columns x0 / 2 - 1 .. x0 / 2 + 32
-__device__ __forceinline__ void load_halo(short (*halo)[kHaloW + 2], const short *__restrict__ coarse, int Wc, int Hc, int x0, int y0, int wrap)
-{
-    for (int e = threadIdx.x; e < kHaloW * kHaloH; e += 256) {
-        const int ry = e / kHaloW, rx = e - ry * kHaloW;
-        const int gy = min(max(y0 / 2 - 1 + ry, 0), Hc - 1), gx = col_index(x0 / 2 - 1 + rx, Wc, wrap);
-        halo[ry][rx] = coarse[(size_t)gy * Wc + gx];
-    }
-}
-
-// E(x) at the tile's local fine pixel (ly, lx): an even coordinate takes coarse neighbours -1, 0, +1 with taps 1, 6, 1, an
-// odd one the two it lies between with taps 4, 4
-__device__ __forceinline__ int expand_at(const short (*halo)[kHaloW + 2], int ly, int lx)
-{
-    const int ry = ly >> 1, rx = lx >> 1;
-    const int wy0 = (ly & 1) ? 0 : 1, wy1 = (ly & 1) ? 4 : 6, wy2 = (ly & 1) ? 4 : 1;
-    const int wx0 = (lx & 1) ? 0 : 1, wx1 = (lx & 1) ? 4 : 6, wx2 = (lx & 1) ? 4 : 1;
-    const int r0 = wx0 * halo[ry][rx] + wx1 * halo[ry][rx + 1] + wx2 * halo[ry][rx + 2];
-    const int r1 = wx0 * halo[ry + 1][rx] + wx1 * halo[ry + 1][rx + 1] + wx2 * halo[ry + 1][rx + 2];
-    const int r2 = wx0 * halo[ry + 2][rx] + wx1 * halo[ry + 2][rx + 1] + wx2 * halo[ry + 2][rx + 2];
-    return (wy0 * r0 + wy1 * r1 + wy2 * r2 + 32) >> 6;
-}
-
-__device__ __forceinline__ int floor_div(int num, int den)     // den > 0
-{
-    int q = num / den;
-    if (num < 0 && q * den != num) --q;
-    return q;
-}
-
-// grid (ceil(W / 64), ceil(H / 16)) x 256: thread (tx, ty) of 16 x 16 owns fine pixels (x0 + 4 tx .. + 3, y0 + ty) of level l
-// (W x H at off; the coarse level Wc x Hc at offc; top: l == L, Lap = G).  lap != NULL: the Laplacians are written too.
-template <int CH>
-__global__ __launch_bounds__(256) void k_pano_lapblend(const short *__restrict__ G, const unsigned char *__restrict__ mpyr, const unsigned short *__restrict__ wsum,
-                                                       int n, int W, int H, size_t off, size_t offc, size_t Sp, int top, int wrap, short *__restrict__ B,
-                                                       short *__restrict__ lap)
-{
-    __shared__ short halo[CH][kHaloH][kHaloW + 2];
-    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int x = x0 + 4 * tx, y = y0 + ty;
-    const int nv = (y < H && x < W) ? min(4, W - x) : 0;
-    const bool vec = nv == 4 && (W & 3) == 0;
-    const size_t at = off + (size_t)y * W + x;
-    const int Wc = W >> 1, Hc = H >> 1;
-    int acc[CH][4];
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[c][e] = 0;
-    for (int k = 0; k < n; ++k) {
-        int m[4] = { 0, 0, 0, 0 };
-        if (vec) {
-            const unsigned mv = *reinterpret_cast<const unsigned *>(mpyr + k * Sp + at);
-            m[0] = mv & 0xff; m[1] = (mv >> 8) & 0xff; m[2] = (mv >> 16) & 0xff; m[3] = mv >> 24;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (e < nv) m[e] = mpyr[k * Sp + at + e];
-        }
-        // also the barrier between the previous camera's reads of the halo and this camera's load
-        const int used = __syncthreads_or(m[0] | m[1] | m[2] | m[3]);
-        if (!used && !lap) continue;                          // block-uniform
-        if (!top) {
-#pragma unroll
-            for (int c = 0; c < CH; ++c) load_halo(halo[c], G + (size_t)(k * CH + c) * Sp + offc, Wc, Hc, x0, y0, wrap);
-            __syncthreads();
-        }
-        if (nv == 0) continue;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const short *g = G + (size_t)(k * CH + c) * Sp + at;
-            int gv[4] = { 0, 0, 0, 0 };
-            if (vec) {
-                const uint2 q = *reinterpret_cast<const uint2 *>(g);
-                gv[0] = (short)(q.x & 0xffffu); gv[1] = (int)q.x >> 16; gv[2] = (short)(q.y & 0xffffu); gv[3] = (int)q.y >> 16;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (e < nv) gv[e] = g[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (e >= nv) continue;
-                const int lv = gv[e] - (top ? 0 : expand_at(halo[c], ty, 4 * tx + e));
-                if (lap) lap[(size_t)(k * CH + c) * Sp + at + e] = (short)lv;
-                acc[c][e] += m[e] * lv;
-            }
-        }
-    }
-    if (nv == 0) return;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        if (e >= nv) continue;
-        const int Wsum = wsum[at + e];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) B[(size_t)c * Sp + at + e] = (short)(Wsum ? floor_div(acc[c][e] + (Wsum >> 1), Wsum) : 0);
-    }
-}
-
-// same grid and ownership: R^l = B^l + E(R^(l+1)), in place; FINAL (l == 0): the output bytes instead
-template <int CH, int FINAL>
-__global__ __launch_bounds__(256) void k_pano_collapse(short *__restrict__ B, int W, int H, size_t off, size_t offc, size_t Sp, int wrap,
-                                                       const unsigned char *__restrict__ cover, unsigned char *__restrict__ out)
-{
-    __shared__ short halo[CH][kHaloH][kHaloW + 2];
-    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int x = x0 + 4 * tx, y = y0 + ty;
-    const int nv = (y < H && x < W) ? min(4, W - x) : 0;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) load_halo(halo[c], B + (size_t)c * Sp + offc, W >> 1, H >> 1, x0, y0, wrap);
-    __syncthreads();
-    if (nv == 0) return;
-    const size_t at = off + (size_t)y * W + x;
-    int v[4][CH];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            v[e][c] = 0;
-            if (e < nv) v[e][c] = B[(size_t)c * Sp + at + e] + expand_at(halo[c], ty, 4 * tx + e);
-        }
-    if (FINAL) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool seen = e < nv && cover[at + e] > 0;       // off == 0 at level 0
-#pragma unroll
-            for (int c = 0; c < CH; ++c) v[e][c] = seen ? max(0, min(255, v[e][c])) : 0;
-        }
-        store_quad<CH>(out, at, nv, v);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-                if (e < nv) B[(size_t)c * Sp + at + e] = (short)v[e][c];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ overlap
 // grid ceil(npix / 1024) x 256; acc[a * 16 + b] = count, acc[256 + a * 16 + b] = sum.  A block sees at most 1024 pixels, so
 // its partials fit 32 bits.
@@ -415,11 +207,9 @@ __global__ __launch_bounds__(256) void k_pano_overlap(const uint2 *__restrict__ 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host
-struct tscm_panorama {
-    int n = 0, w = 0, h = 0, ch = 0, pw = 0, ph = 0, mode = 0, levels = 0, wrap = 0, device = 0;
+struct tscm_panorama : PyramidLayout {
+    int n = 0, w = 0, h = 0, ch = 0, pw = 0, ph = 0, mode = 0, wrap = 0, device = 0;      // levels: 0 unless MULTIBAND
     size_t npix = 0, plane = 0;             // output pixels; the same rounded up to 4
-    int lw[kMaxLevels + 1] = {}, lh[kMaxLevels + 1] = {};
-    size_t loff[kMaxLevels + 1] = {}, toff[kMaxLevels + 1] = {}, Sp = 0, S = 0;    // level offsets on the device / in the stage outputs
     DeviceMem mem;
     uint2 *pack = nullptr;
     unsigned char *alpha = nullptr, *label = nullptr, *cover = nullptr, *mpyr = nullptr, *img = nullptr, *out = nullptr;
@@ -455,33 +245,19 @@ int upload_frame(tscm_panorama *p, const unsigned char *const *images, int strid
     return 0;
 }
 
-unsigned quad_blocks(size_t npix) { return (unsigned)((npix + 1023) / 1024); }
-
 template <int CH>
 void launch_sample(const tscm_panorama *p, const Gains &g, short *G, size_t stride)
 {
     hipLaunchKernelGGL(k_pano_sample<CH>, dim3(quad_blocks(p->npix), (unsigned)p->n), dim3(256), 0, 0, p->pack, p->img, p->w, p->h, p->npix, p->plane, g, G, stride);
 }
 
-dim3 tile_grid(int W, int H) { return dim3((unsigned)((W + kTileW - 1) / kTileW), (unsigned)((H + kTileH - 1) / kTileH)); }
-
 // MULTIBAND up to B^l (collapse == false) or to the output bytes
 template <int CH>
 void launch_multiband(const tscm_panorama *p, const Gains &g, short *lap, bool collapse)
 {
-    const int L = p->levels;
     launch_sample<CH>(p, g, p->G, p->Sp);
-    for (int l = 0; l < L; ++l)
-        hipLaunchKernelGGL(k_pano_reduce<short>, dim3((unsigned)((p->lw[l + 1] + kRedW - 1) / kRedW), (unsigned)((p->lh[l + 1] + kRedH - 1) / kRedH), (unsigned)(p->n * CH)),
-                           dim3(256), 0, 0, p->G, p->lw[l], p->lh[l], p->Sp, p->loff[l], p->loff[l + 1], p->wrap);
-    for (int l = 0; l <= L; ++l)
-        hipLaunchKernelGGL(k_pano_lapblend<CH>, tile_grid(p->lw[l], p->lh[l]), dim3(256), 0, 0, p->G, p->mpyr, p->wsum, p->n, p->lw[l], p->lh[l], p->loff[l],
-                           l < L ? p->loff[l + 1] : (size_t)0, p->Sp, l == L ? 1 : 0, p->wrap, p->B, lap);
-    if (!collapse) return;
-    for (int l = L - 1; l >= 1; --l)
-        hipLaunchKernelGGL((k_pano_collapse<CH, 0>), tile_grid(p->lw[l], p->lh[l]), dim3(256), 0, 0, p->B, p->lw[l], p->lh[l], p->loff[l], p->loff[l + 1], p->Sp, p->wrap,
-                           p->cover, p->out);
-    hipLaunchKernelGGL((k_pano_collapse<CH, 1>), tile_grid(p->pw, p->ph), dim3(256), 0, 0, p->B, p->pw, p->ph, (size_t)0, p->loff[1], p->Sp, p->wrap, p->cover, p->out);
+    launch_reduce(*p, p->G, p->n * CH, p->wrap);
+    launch_blend<CH>(*p, p->G, p->mpyr, p->wsum, p->n, p->wrap, p->B, lap, collapse, p->cover, p->out);
 }
 
 template <int CH>
@@ -494,18 +270,6 @@ void launch_compose(const tscm_panorama *p, const Gains &g)
     else
         hipLaunchKernelGGL((k_pano_compose<CH, TSCM_PANO_FEATHER>), dim3(quad_blocks(p->npix)), dim3(256), 0, 0, p->pack, p->label, p->mask, p->img, p->n, p->w, p->h,
                            p->npix, p->plane, g, p->out);
-}
-
-// `planes` device planes of Sp elements -> planes of S elements, the levels one after the other without padding
-template <typename T>
-int download_pyramid(const tscm_panorama *p, const T *dev, int planes, T *host)
-{
-    std::vector<T> tmp((size_t)planes * p->Sp);
-    HIP_TRY(hipMemcpy(tmp.data(), dev, tmp.size() * sizeof(T), hipMemcpyDeviceToHost));
-    for (int q = 0; q < planes; ++q)
-        for (int l = 0; l <= p->levels; ++l)
-            std::copy_n(tmp.data() + (size_t)q * p->Sp + p->loff[l], (size_t)p->lw[l] * p->lh[l], host + (size_t)q * p->S + p->toff[l]);
-    return 0;
 }
 
 int create_on_device(tscm_panorama *p, const unsigned char *const *weights, const float *mapx, const float *mapy)
@@ -542,9 +306,7 @@ int create_on_device(tscm_panorama *p, const unsigned char *const *weights, cons
     hipLaunchKernelGGL(k_pano_prepare, dim3(blocks, (unsigned)n), dim3(256), 0, 0, d_mx, d_my, d_w, weight_mask, p->w, p->h, p->npix, p->plane, p->pack, p->alpha);
     hipLaunchKernelGGL(k_pano_label, dim3(blocks), dim3(256), 0, 0, p->alpha, n, p->npix, p->plane, p->label, p->cover, p->mask, p->mpyr, p->Sp);
     if (p->mode == TSCM_PANO_MULTIBAND) {
-        for (int l = 0; l < p->levels; ++l)
-            hipLaunchKernelGGL(k_pano_reduce<unsigned char>, dim3((unsigned)((p->lw[l + 1] + kRedW - 1) / kRedW), (unsigned)((p->lh[l + 1] + kRedH - 1) / kRedH), (unsigned)n),
-                               dim3(256), 0, 0, p->mpyr, p->lw[l], p->lh[l], p->Sp, p->loff[l], p->loff[l + 1], p->wrap);
+        launch_reduce(*p, p->mpyr, n, p->wrap);
         hipLaunchKernelGGL(k_pano_wsum, dim3((unsigned)((p->Sp + 255) / 256)), dim3(256), 0, 0, p->mpyr, n, p->Sp, p->wsum);
     }
     HIP_TRY(hipGetLastError());
@@ -587,15 +349,10 @@ extern "C" int tscm_panorama_create(int n_cameras, int width, int height, int ch
     if (int rc = select_device(device_index, "tscm_panorama_create")) return rc;
     std::unique_ptr<tscm_panorama> p(new tscm_panorama);
     p->n = n_cameras; p->w = width; p->h = height; p->ch = channels; p->pw = pano_w; p->ph = pano_h;
-    p->mode = params->mode; p->levels = L; p->wrap = params->wrap_x ? 1 : 0; p->device = device_index;
+    p->mode = params->mode; p->wrap = params->wrap_x ? 1 : 0; p->device = device_index;
     p->npix = (size_t)pano_w * pano_h;
     p->plane = (p->npix + 3) & ~(size_t)3;
-    for (int l = 0; l <= L; ++l) {
-        p->lw[l] = pano_w >> l; p->lh[l] = pano_h >> l;
-        p->loff[l] = p->Sp; p->toff[l] = p->S;
-        p->S += (size_t)p->lw[l] * p->lh[l];
-        p->Sp = (p->Sp + (size_t)p->lw[l] * p->lh[l] + 7) & ~(size_t)7;
-    }
+    p->set_levels(pano_w, pano_h, L);
     if (int rc = create_on_device(p.get(), weights, mapx, mapy)) return rc;
     *out = p.release();
     return 0;
@@ -659,9 +416,9 @@ extern "C" int tscm_panorama_stages(tscm_panorama *p, const unsigned char *const
     }
     if (alpha) HIP_TRY(hipMemcpy2D(alpha, p->npix, p->alpha, p->plane, p->npix, (size_t)n, hipMemcpyDeviceToHost));
     if (label) HIP_TRY(hipMemcpy(label, p->label, p->npix, hipMemcpyDeviceToHost));
-    if (mask_pyramid) if (int rc = download_pyramid(p, p->mpyr, n, mask_pyramid)) return rc;
-    if (lap_pyramid) if (int rc = download_pyramid(p, d_lap, n * ch, lap_pyramid)) return rc;
-    if (blend_pyramid) if (int rc = download_pyramid(p, p->B, ch, blend_pyramid)) return rc;
+    if (mask_pyramid) if (int rc = download_pyramid(*p, p->mpyr, n, mask_pyramid)) return rc;
+    if (lap_pyramid) if (int rc = download_pyramid(*p, d_lap, n * ch, lap_pyramid)) return rc;
+    if (blend_pyramid) if (int rc = download_pyramid(*p, p->B, ch, blend_pyramid)) return rc;
     return 0;
 }
 

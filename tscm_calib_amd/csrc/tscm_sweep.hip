@@ -15,11 +15,21 @@
 //   k_aggregate      tscm_stereo_kernels.h, on the new volume
 //   k_sweep_winner   winner_value of tscm_stereo_kernels.h with the rule C(k*) == 64 -> invalid
 //   k_sweep_points   one thread per pixel, fp64
+// The frame composed at the swept depth (tscm_sweep_compose): the panorama's blends on the record (k, z(i, j)) of every pixel,
+// z the hypothesis the index map names.  Labels, coverage and mask pyramids depend on the index map, so they are per frame:
+//   k_sweep_compose  SEAM / FEATHER in one launch: a thread owns 4 adjacent output pixels, forms their z, reads the n records
+//                    at (k, z) with 8-byte loads (the 4 pixels lie in different hypothesis planes), and stores 4 or 12 packed
+//                    output bytes and 4 coverage bytes; no per-camera plane is written.  SEAM keeps the record of the largest
+//                    alpha and samples once per pixel; FEATHER skips the gathers of a camera that no lane of the wave sees
+//                    (ballot)
+//   k_sweep_gather   MULTIBAND: G^0 of every camera and channel as int16 planes, label, coverage and level 0 of the masks
+//   then k_pano_reduce on the images and the masks, k_pano_wsum, k_pano_lapblend, k_pano_collapse (tscm_pano_kernels.h)
 #include "tscm/tscm.h"
 
 #include <hip/hip_runtime.h>
 
 #include "tscm_host.h"
+#include "tscm_pano_kernels.h"
 #include "tscm_remap_sample.h"
 #include "tscm_stereo_kernels.h"
 
@@ -27,6 +37,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <vector>
 
 using namespace tscm;
 
@@ -257,12 +268,171 @@ __global__ __launch_bounds__(256) void k_sweep_points(const short *__restrict__ 
     valid[pix] = ok ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------ compose
+// z of the quad at t0 (tscm.h: hypothesis index) and where the record of pixel t0 + e lies inside a camera's D planes;
+// elements at and beyond nv are not read
+__device__ __forceinline__ void quad_records(const short *__restrict__ index16, size_t t0, int nv, int D, int fallback, size_t npix, int (&z)[4], size_t (&at)[4])
+{
+    int raw[4] = { -1, -1, -1, -1 };
+    if (nv == 4) {
+        const uint2 q = *reinterpret_cast<const uint2 *>(index16 + t0);
+        raw[0] = (short)(q.x & 0xffffu); raw[1] = (int)q.x >> 16; raw[2] = (short)(q.y & 0xffffu); raw[3] = (int)q.y >> 16;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (e < nv) raw[e] = index16[t0 + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        z[e] = raw[e] < 0 ? fallback : min(D - 1, (raw[e] + 8) >> 4);
+        at[e] = (size_t)z[e] * npix + t0 + e;
+    }
+}
+
+// grid ceil(npix / 1024) x 256: quad q = output pixels [4q, 4q + 4) of the flat panorama
+template <int CH, int MODE>
+__global__ __launch_bounds__(256) void k_sweep_compose(const uint2 *__restrict__ pack, const short *__restrict__ index16, const unsigned char *__restrict__ img, int n,
+                                                       int w, int h, int D, int fallback, size_t npix, Gains gains, unsigned char *__restrict__ out,
+                                                       unsigned char *__restrict__ cover)
+{
+    const size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (t0 >= npix) return;
+    const int nv = (int)min((size_t)4, npix - t0);
+    const size_t img_bytes = (size_t)w * h * CH, cam = (size_t)D * npix;
+    int z[4];
+    size_t at[4];
+    quad_records(index16, t0, nv, D, fallback, npix, z, at);
+    int v[4][CH], cnt[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        cnt[e] = 0;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) v[e][c] = 0;
+    }
+    if (MODE == TSCM_PANO_SEAM) {
+        // the record, camera and gain of the largest alpha so far: the first of equal maxima stays
+        uint2 rec[4];
+        int best[4] = { 0, 0, 0, 0 }, lab[4] = { 0, 0, 0, 0 }, g[4] = { 256, 256, 256, 256 };
+#pragma unroll
+        for (int e = 0; e < 4; ++e) rec[e] = make_uint2(0, 0);
+        for (int k = 0; k < n; ++k) {
+            const int gk = gains.g[k];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (e >= nv) continue;
+                const uint2 r = pack[k * cam + at[e]];
+                const int a = (int)(r.y >> 16);
+                if (a > 0) ++cnt[e];
+                if (a > best[e]) { best[e] = a; rec[e] = r; lab[e] = k; g[e] = gk; }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (best[e] == 0) continue;
+            int px[CH];
+            sample_px<CH>(img + lab[e] * img_bytes, w, h, rec[e], px);
+#pragma unroll
+            for (int c = 0; c < CH; ++c) v[e][c] = apply_gain(px[c], g[e]);
+        }
+    } else {
+        int num[4][CH], A[4] = { 0, 0, 0, 0 };
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int c = 0; c < CH; ++c) num[e][c] = 0;
+        for (int k = 0; k < n; ++k) {
+            uint2 r[4];
+            int any = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                r[e] = e < nv ? pack[k * cam + at[e]] : make_uint2(0, 0);
+                any |= (int)(r[e].y >> 16);
+            }
+            if (__ballot(any != 0) == 0) continue;               // no lane of the wave sees camera k: its gathers are skipped
+            const int g = gains.g[k];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int a = (int)(r[e].y >> 16);
+                if (a == 0) continue;
+                int px[CH];
+                sample_px<CH>(img + k * img_bytes, w, h, r[e], px);
+#pragma unroll
+                for (int c = 0; c < CH; ++c) num[e][c] += a * apply_gain(px[c], g);
+                A[e] += a;
+                ++cnt[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int c = 0; c < CH; ++c) v[e][c] = A[e] ? (int)(((unsigned)num[e][c] + ((unsigned)A[e] >> 1)) / (unsigned)A[e]) : 0;
+    }
+    store_quad<CH>(out, t0, nv, v);
+    int cv[4][1] = { { cnt[0] }, { cnt[1] }, { cnt[2] }, { cnt[3] } };
+    store_quad<1>(cover, t0, nv, cv);
+}
+
+// same grid and ownership.  G^0 of every camera at planes (k * CH + c) * Sp, label, cover and (mpyr != NULL) level 0 of the
+// masks; hypothesis [npix], sampled [n][npix][CH], alpha [n][npix]: the stage outputs, any of them NULL.
+template <int CH>
+__global__ __launch_bounds__(256) void k_sweep_gather(const uint2 *__restrict__ pack, const short *__restrict__ index16, const unsigned char *__restrict__ img, int n,
+                                                      int w, int h, int D, int fallback, size_t npix, Gains gains, short *__restrict__ G, size_t Sp,
+                                                      unsigned char *__restrict__ label, unsigned char *__restrict__ cover, unsigned char *__restrict__ mpyr,
+                                                      unsigned char *__restrict__ hypothesis, unsigned char *__restrict__ sampled, unsigned char *__restrict__ alpha)
+{
+    const size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (t0 >= npix) return;
+    const int nv = (int)min((size_t)4, npix - t0);
+    const size_t img_bytes = (size_t)w * h * CH, cam = (size_t)D * npix;
+    int z[4];
+    size_t at[4];
+    quad_records(index16, t0, nv, D, fallback, npix, z, at);
+    int best[4] = { 0, 0, 0, 0 }, lab[4][1] = { { 255 }, { 255 }, { 255 }, { 255 } }, cnt[4][1] = { { 0 }, { 0 }, { 0 }, { 0 } };
+    for (int k = 0; k < n; ++k) {
+        const int g = gains.g[k];
+        int v[4][CH];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) v[e][c] = 0;
+            if (e >= nv) continue;
+            const uint2 r = pack[k * cam + at[e]];
+            const int a = (int)(r.y >> 16);
+            sample_px<CH>(img + k * img_bytes, w, h, r, v[e]);
+#pragma unroll
+            for (int c = 0; c < CH; ++c) v[e][c] = apply_gain(v[e][c], g);
+            if (a > 0) ++cnt[e][0];
+            if (a > best[e]) { best[e] = a; lab[e][0] = k; }
+            if (alpha) alpha[k * npix + t0 + e] = (unsigned char)a;
+        }
+        if (sampled) store_quad<CH>(sampled + k * npix * CH, t0, nv, v);
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            short *q = G + (size_t)(k * CH + c) * Sp + t0;
+            if (nv == 4) *reinterpret_cast<uint2 *>(q) = make_uint2((unsigned)v[0][c] | ((unsigned)v[1][c] << 16), (unsigned)v[2][c] | ((unsigned)v[3][c] << 16));
+            else
+                for (int e = 0; e < nv; ++e) q[e] = (short)v[e][c];
+        }
+    }
+    store_quad<1>(label, t0, nv, lab);
+    store_quad<1>(cover, t0, nv, cnt);
+    if (mpyr)
+        for (int k = 0; k < n; ++k) {
+            const int m[4][1] = { { lab[0][0] == k ? 255 : 0 }, { lab[1][0] == k ? 255 : 0 }, { lab[2][0] == k ? 255 : 0 }, { lab[3][0] == k ? 255 : 0 } };
+            store_quad<1>(mpyr + k * Sp, t0, nv, m);
+        }
+    if (hypothesis) {
+        const int zz[4][1] = { { z[0] }, { z[1] }, { z[2] }, { z[3] } };
+        store_quad<1>(hypothesis, t0, nv, zz);
+    }
+}
+
 thread_local double g_stage_seconds[3];
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host
-struct tscm_sweep {
+struct tscm_sweep : PyramidLayout {         // the base: the levels of the composer's pyramids
     int n = 0, w = 0, h = 0, pw = 0, ph = 0, D = 0, p1 = 0, p2 = 0, paths = 0, uniqueness = 0, wrap = 0, device = 0;
     size_t npix = 0;
     DeviceMem mem;
@@ -270,6 +440,13 @@ struct tscm_sweep {
     unsigned char *img = nullptr, *cost = nullptr;
     unsigned short *sum = nullptr;
     short *index16 = nullptr;
+    bool has_index = false;                 // index16 holds the map of a tscm_sweep_depth
+    // the composer's buffers, allocated by the first tscm_sweep_compose for (c_ch, c_mode, levels)
+    int c_ch = 0, c_mode = -1;
+    size_t plane = 0;                       // npix rounded up to 4
+    unsigned char *c_img = nullptr, *c_out = nullptr, *c_label = nullptr, *c_cover = nullptr, *c_mpyr = nullptr;
+    unsigned short *c_wsum = nullptr;
+    short *c_G = nullptr, *c_B = nullptr, *c_index = nullptr;
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
     ~tscm_sweep() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
@@ -339,6 +516,7 @@ int run_frame(tscm_sweep *s, const unsigned char *const *images, int stride, uns
     HIP_TRY(hipEventRecord(s->ev[3], 0));
     HIP_TRY(hipEventSynchronize(s->ev[3]));
     HIP_TRY(hipGetLastError());
+    if (with_winner) s->has_index = true;
     double total = 0.0;
     for (int k = 0; k < 3; ++k) {
         float ms = 0.f;
@@ -453,6 +631,205 @@ extern "C" int tscm_sweep_stage_times(double *seconds)
 {
     if (!seconds) return tscm_set_error(TSCM_E_INVALID, "seconds is NULL");
     for (int k = 0; k < 3; ++k) seconds[k] = g_stage_seconds[k];
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ compose: host
+namespace {
+
+struct ComposeStages {
+    unsigned char *hypothesis, *sampled, *alpha, *label, *mask_pyramid;
+    short *lap_pyramid, *blend_pyramid;
+};
+
+// the checks of tscm_sweep_compose / _stages that they share, in the panorama's wording
+int check_compose(const tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                  const tscm_sweep_compose_params *p, const unsigned short *gain_q8, Gains *gains)
+{
+    if (!s) return tscm_set_error(TSCM_E_INVALID, "s is NULL");
+    if (!images) return tscm_set_error(TSCM_E_INVALID, "images is NULL");
+    for (int k = 0; k < s->n; ++k)
+        if (!images[k]) return tscm_set_error(TSCM_E_INVALID, "images[" + std::to_string(k) + "] is NULL");
+    if (channels != 1 && channels != 3) return tscm_set_error(TSCM_E_INVALID, "channels " + std::to_string(channels) + " is not 1 or 3");
+    if (stride < s->w * channels) return tscm_set_error(TSCM_E_INVALID, "stride " + std::to_string(stride) + " < width * channels = " + std::to_string(s->w * channels));
+    if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
+    if (p->struct_size != (int)sizeof(tscm_sweep_compose_params))
+        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_sweep_compose_params) = " + std::to_string(sizeof(tscm_sweep_compose_params)));
+    if (p->mode != TSCM_PANO_SEAM && p->mode != TSCM_PANO_FEATHER && p->mode != TSCM_PANO_MULTIBAND)
+        return tscm_set_error(TSCM_E_INVALID, "params: unknown mode " + std::to_string(p->mode));
+    const bool multiband = p->mode == TSCM_PANO_MULTIBAND;
+    if (multiband && (p->levels < 1 || p->levels > kPanoMaxLevels)) return tscm_set_error(TSCM_E_INVALID, "params: levels " + std::to_string(p->levels) + " outside 1..6");
+    if (p->fallback_index < 0 || p->fallback_index >= s->D)
+        return tscm_set_error(TSCM_E_INVALID, "params: fallback_index " + std::to_string(p->fallback_index) + " outside 0.." + std::to_string(s->D - 1));
+    const int L = multiband ? p->levels : 0;
+    if (s->pw % (1 << L)) return tscm_set_error(TSCM_E_INVALID, "pano_w " + std::to_string(s->pw) + " is no multiple of 2^levels = " + std::to_string(1 << L));
+    if (s->ph % (1 << L)) return tscm_set_error(TSCM_E_INVALID, "pano_h " + std::to_string(s->ph) + " is no multiple of 2^levels = " + std::to_string(1 << L));
+    if (!index16 && !s->has_index) return tscm_set_error(TSCM_E_INVALID, "index16 is NULL and the handle has not run tscm_sweep_depth yet");
+    if (index16 && index_stride < s->pw) return tscm_set_error(TSCM_E_INVALID, "index_stride " + std::to_string(index_stride) + " < pano_w " + std::to_string(s->pw));
+    for (int k = 0; k < kPanoMaxCameras; ++k) gains->g[k] = 256;
+    for (int k = 0; gain_q8 && k < s->n; ++k) {
+        if (gain_q8[k] < 1 || gain_q8[k] > 4095) return tscm_set_error(TSCM_E_INVALID, "gain_q8[" + std::to_string(k) + "] = " + std::to_string(gain_q8[k]) + " outside 1..4095");
+        gains->g[k] = gain_q8[k];
+    }
+    return 0;
+}
+
+// the composer's buffers for (channels, mode, levels); kept until one of the three changes
+int compose_buffers(tscm_sweep *s, int ch, int mode, int L)
+{
+    if (s->c_ch == ch && s->c_mode == mode && s->levels == L) return 0;
+    for (const void *q : { (const void *)s->c_img, (const void *)s->c_out, (const void *)s->c_label, (const void *)s->c_cover, (const void *)s->c_mpyr,
+                           (const void *)s->c_wsum, (const void *)s->c_G, (const void *)s->c_B, (const void *)s->c_index })
+        s->mem.release(q);
+    s->c_img = s->c_out = s->c_label = s->c_cover = s->c_mpyr = nullptr;
+    s->c_wsum = nullptr;
+    s->c_G = s->c_B = s->c_index = nullptr;
+    s->c_mode = -1;
+    s->plane = (s->npix + 3) & ~(size_t)3;
+    s->set_levels(s->pw, s->ph, L);
+    const size_t n = (size_t)s->n;
+    HIP_TRY(s->mem.alloc(&s->c_img, n * s->w * s->h * ch));
+    HIP_TRY(s->mem.alloc(&s->c_out, s->plane * ch));
+    HIP_TRY(s->mem.alloc(&s->c_label, s->plane));
+    HIP_TRY(s->mem.alloc(&s->c_cover, s->plane));
+    HIP_TRY(s->mem.alloc(&s->c_index, s->plane));
+    if (mode == TSCM_PANO_MULTIBAND) {                        // the padding between the levels is never written: it stays zero
+        HIP_TRY(s->mem.alloc(&s->c_mpyr, n * s->Sp)); HIP_TRY(hipMemset(s->c_mpyr, 0, n * s->Sp));
+        HIP_TRY(s->mem.alloc(&s->c_wsum, s->Sp));
+        HIP_TRY(s->mem.alloc(&s->c_G, n * ch * s->Sp)); HIP_TRY(hipMemset(s->c_G, 0, n * ch * s->Sp * sizeof(short)));
+        HIP_TRY(s->mem.alloc(&s->c_B, (size_t)ch * s->Sp)); HIP_TRY(hipMemset(s->c_B, 0, (size_t)ch * s->Sp * sizeof(short)));
+    }
+    s->c_ch = ch; s->c_mode = mode;
+    return 0;
+}
+
+template <int CH>
+void launch_gather(const tscm_sweep *s, const short *idx, int fallback, const Gains &g, short *G, size_t stride, unsigned char *mpyr, unsigned char *d_hyp,
+                   unsigned char *d_sampled, unsigned char *d_alpha)
+{
+    hipLaunchKernelGGL(k_sweep_gather<CH>, dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback, s->npix, g, G, stride,
+                       s->c_label, s->c_cover, mpyr, d_hyp, d_sampled, d_alpha);
+}
+
+// MULTIBAND behind the gather, up to B^l (collapse == false) or to the output bytes: the mask pyramids and their sums are
+// per frame here, next to the image pyramids
+template <int CH>
+void launch_pyramids(const tscm_sweep *s, int wrap, short *lap, bool collapse)
+{
+    launch_reduce(*s, s->c_G, s->n * CH, wrap);
+    launch_reduce(*s, s->c_mpyr, s->n, wrap);
+    hipLaunchKernelGGL(k_pano_wsum, dim3((unsigned)((s->Sp + 255) / 256)), dim3(256), 0, 0, s->c_mpyr, s->n, s->Sp, s->c_wsum);
+    launch_blend<CH>(*s, s->c_G, s->c_mpyr, s->c_wsum, s->n, wrap, s->c_B, lap, collapse, s->c_cover, s->c_out);
+}
+
+template <int CH>
+void launch_compose(const tscm_sweep *s, const short *idx, int fallback, int wrap, const Gains &g)
+{
+    if (s->c_mode == TSCM_PANO_MULTIBAND) {
+        launch_gather<CH>(s, idx, fallback, g, s->c_G, s->Sp, s->c_mpyr, nullptr, nullptr, nullptr);
+        launch_pyramids<CH>(s, wrap, nullptr, true);
+    } else if (s->c_mode == TSCM_PANO_SEAM)
+        hipLaunchKernelGGL((k_sweep_compose<CH, TSCM_PANO_SEAM>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback,
+                           s->npix, g, s->c_out, s->c_cover);
+    else
+        hipLaunchKernelGGL((k_sweep_compose<CH, TSCM_PANO_FEATHER>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback,
+                           s->npix, g, s->c_out, s->c_cover);
+}
+
+// buffers, the colour images and the index map (the caller's, or the one tscm_sweep_depth left) on the device
+int upload_compose(tscm_sweep *s, const unsigned char *const *images, int stride, int ch, const short *index16, int index_stride,
+                   const tscm_sweep_compose_params *p, const short **idx)
+{
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = compose_buffers(s, ch, p->mode, p->mode == TSCM_PANO_MULTIBAND ? p->levels : 0)) return rc;
+    const size_t row = (size_t)s->w * ch;
+    for (int k = 0; k < s->n; ++k) HIP_TRY(hipMemcpy2D(s->c_img + (size_t)k * row * s->h, row, images[k], (size_t)stride, row, (size_t)s->h, hipMemcpyHostToDevice));
+    *idx = s->index16;
+    if (index16) {
+        HIP_TRY(hipMemcpy2D(s->c_index, (size_t)s->pw * sizeof(short), index16, (size_t)index_stride * sizeof(short), (size_t)s->pw * sizeof(short), (size_t)s->ph,
+                            hipMemcpyHostToDevice));
+        *idx = s->c_index;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" void tscm_sweep_compose_default_params(tscm_sweep_compose_params *p)
+{
+    if (!p) return;
+    p->struct_size = (int)sizeof(tscm_sweep_compose_params);
+    p->mode = TSCM_PANO_MULTIBAND; p->levels = 4; p->wrap_x = 1; p->fallback_index = 0;
+}
+
+extern "C" int tscm_sweep_compose(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                                  const tscm_sweep_compose_params *params, const unsigned short *gain_q8, unsigned char *dst, int dst_stride, unsigned char *coverage,
+                                  double *seconds_kernel)
+{
+    Gains g;
+    if (int rc = check_compose(s, images, stride, channels, index16, index_stride, params, gain_q8, &g)) return rc;
+    if (!dst) return tscm_set_error(TSCM_E_INVALID, "dst is NULL");
+    if (dst_stride < s->pw * channels) return tscm_set_error(TSCM_E_INVALID, "dst_stride " + std::to_string(dst_stride) + " < pano_w * channels = " + std::to_string(s->pw * channels));
+    if (seconds_kernel) *seconds_kernel = 0.0;
+    const short *idx = nullptr;
+    if (int rc = upload_compose(s, images, stride, channels, index16, index_stride, params, &idx)) return rc;
+    const int wrap = params->wrap_x ? 1 : 0;                 // the pyramids' wrap is the composer's own, not the census window's
+    HIP_TRY(hipEventRecord(s->ev[0], 0));
+    if (channels == 1) launch_compose<1>(s, idx, params->fallback_index, wrap, g);
+    else launch_compose<3>(s, idx, params->fallback_index, wrap, g);
+    HIP_TRY(hipEventRecord(s->ev[1], 0));
+    HIP_TRY(hipEventSynchronize(s->ev[1]));
+    HIP_TRY(hipGetLastError());
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    const size_t row = (size_t)s->pw * channels;
+    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, s->c_out, row, row, (size_t)s->ph, hipMemcpyDeviceToHost));
+    if (coverage) HIP_TRY(hipMemcpy(coverage, s->c_cover, s->npix, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                                         const tscm_sweep_compose_params *params, const unsigned short *gain_q8, unsigned char *hypothesis, unsigned char *sampled,
+                                         unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid, short *blend_pyramid)
+{
+    Gains g;
+    if (int rc = check_compose(s, images, stride, channels, index16, index_stride, params, gain_q8, &g)) return rc;
+    const bool multiband = params->mode == TSCM_PANO_MULTIBAND;
+    if (!multiband && (mask_pyramid || lap_pyramid || blend_pyramid))
+        return tscm_set_error(TSCM_E_INVALID, std::string(mask_pyramid ? "mask_pyramid" : lap_pyramid ? "lap_pyramid" : "blend_pyramid") + ": the mode is not MULTIBAND");
+    const short *idx = nullptr;
+    if (int rc = upload_compose(s, images, stride, channels, index16, index_stride, params, &idx)) return rc;
+    const int n = s->n, ch = channels;
+    const size_t nplane = (size_t)n * s->npix;
+    DeviceMem tmp;
+    unsigned char *d_hyp = nullptr, *d_sampled = nullptr, *d_alpha = nullptr;
+    short *d_lap = nullptr, *d_G = s->c_G;
+    size_t gstride = s->Sp;
+    if (hypothesis) HIP_TRY(tmp.alloc(&d_hyp, s->plane));
+    if (sampled) HIP_TRY(tmp.alloc(&d_sampled, nplane * ch));
+    if (alpha) HIP_TRY(tmp.alloc(&d_alpha, nplane));
+    if (!multiband) {                                         // SEAM and FEATHER keep no planes: the gather writes into a scratch set
+        gstride = s->plane;
+        HIP_TRY(tmp.alloc(&d_G, (size_t)n * ch * gstride));
+    } else if (lap_pyramid) HIP_TRY(tmp.alloc(&d_lap, (size_t)n * ch * s->Sp));
+    const int wrap = params->wrap_x ? 1 : 0;
+    if (ch == 1) {
+        launch_gather<1>(s, idx, params->fallback_index, g, d_G, gstride, s->c_mpyr, d_hyp, d_sampled, d_alpha);
+        if (multiband) launch_pyramids<1>(s, wrap, d_lap, false);
+    } else {
+        launch_gather<3>(s, idx, params->fallback_index, g, d_G, gstride, s->c_mpyr, d_hyp, d_sampled, d_alpha);
+        if (multiband) launch_pyramids<3>(s, wrap, d_lap, false);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (hypothesis) HIP_TRY(hipMemcpy(hypothesis, d_hyp, s->npix, hipMemcpyDeviceToHost));
+    if (sampled) HIP_TRY(hipMemcpy(sampled, d_sampled, nplane * ch, hipMemcpyDeviceToHost));
+    if (alpha) HIP_TRY(hipMemcpy(alpha, d_alpha, nplane, hipMemcpyDeviceToHost));
+    if (label) HIP_TRY(hipMemcpy(label, s->c_label, s->npix, hipMemcpyDeviceToHost));
+    if (mask_pyramid) if (int rc = download_pyramid(*s, s->c_mpyr, n, mask_pyramid)) return rc;
+    if (lap_pyramid) if (int rc = download_pyramid(*s, d_lap, n * ch, lap_pyramid)) return rc;
+    if (blend_pyramid) if (int rc = download_pyramid(*s, s->c_B, ch, blend_pyramid)) return rc;
     return 0;
 }
 

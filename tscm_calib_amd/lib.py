@@ -143,6 +143,11 @@ class CSweepParams(C.Structure):
                 ("uniqueness_ratio", C.c_int), ("wrap_x", C.c_int)]
 
 
+class CSweepComposeParams(C.Structure):
+    """tscm_sweep_compose_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int), ("fallback_index", C.c_int)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -171,6 +176,7 @@ EXPORTS = [
     "tscm_panorama_default_params", "tscm_panorama_create", "tscm_panorama_compose", "tscm_panorama_stages", "tscm_panorama_overlap", "tscm_panorama_destroy",
     "tscm_build_sweep_maps",
     "tscm_sweep_default_params", "tscm_sweep_create", "tscm_sweep_depth", "tscm_sweep_stages", "tscm_sweep_stage_times", "tscm_sweep_points", "tscm_sweep_destroy",
+    "tscm_sweep_compose_default_params", "tscm_sweep_compose", "tscm_sweep_compose_stages",
 ]
 
 
@@ -287,6 +293,10 @@ def lib():
     L.tscm_sweep_stages.argtypes = [vp, vpp, C.c_int, ubp, ubp, C.POINTER(C.c_ulonglong), ubp, usp]
     L.tscm_sweep_stage_times.argtypes = [dp]
     L.tscm_sweep_points.argtypes = [shp, C.c_int, C.c_int, C.c_int, C.POINTER(CMapDesc), C.c_int, dp, C.c_int, C.c_int, dp, ubp]
+    L.tscm_sweep_compose_default_params.argtypes = [C.POINTER(CSweepComposeParams)]
+    L.tscm_sweep_compose_default_params.restype = None
+    L.tscm_sweep_compose.argtypes = [vp, vpp, C.c_int, C.c_int, shp, C.c_int, C.POINTER(CSweepComposeParams), usp, ubp, C.c_int, ubp, dp]
+    L.tscm_sweep_compose_stages.argtypes = [vp, vpp, C.c_int, C.c_int, shp, C.c_int, C.POINTER(CSweepComposeParams), usp, ubp, ubp, ubp, ubp, ubp, shp, shp]
     L.tscm_sweep_destroy.argtypes = [vp]
     L.tscm_sweep_destroy.restype = None
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]

@@ -1,6 +1,7 @@
 """Sphere-sweep depth of a calibrated rig (tscm.h: tscm_sweep_*): Sweeper keeps the n x D packed sweep tables on the device
 and gives one index map per frame -- 16 x the winning inverse-distance hypothesis of every panorama pixel -- and its 3-D
-points in the rig frame; rig_depth does it in one call."""
+points in the rig frame; rig_depth does it in one call.  Sweeper.compose blends the frame at the swept depth -- the panorama
+without the parallax of a composition at infinity -- and rig_panorama runs depth, the optional filter and compose in one call."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,6 +23,32 @@ def params(**over) -> _lib.CSweepParams:
             raise AttributeError(k)
         setattr(p, k, int(v))
     return p
+
+
+def compose_params(**over) -> _lib.CSweepComposeParams:
+    """tscm_sweep_compose_default_params with fields replaced: mode ("seam", "feather", "multiband" or TSCM_PANO_*), levels,
+    wrap_x, fallback_index."""
+    p = _lib.CSweepComposeParams()
+    _lib.lib().tscm_sweep_compose_default_params(C.byref(p))
+    for k, v in over.items():
+        if k == "struct_size" or not hasattr(p, k):
+            raise AttributeError(k)
+        if k == "mode" and isinstance(v, str):
+            if v not in _lib.PANO_MODES:
+                raise ValueError(f"unknown mode {v!r}: one of {', '.join(_lib.PANO_MODES)}")
+            v = _lib.PANO_MODES[v]
+        setattr(p, k, int(v))
+    return p
+
+
+def bgr_to_gray(img) -> np.ndarray:
+    """The composer's BGR2GRAY integers (tscm.h, overlap): (b 1868 + g 9617 + r 4899 + 2^13) >> 14; a grey image is returned
+    as it is."""
+    a = np.asarray(img)
+    if a.ndim == 2:
+        return a
+    v = a.astype(np.int64)
+    return ((v[..., 0] * 1868 + v[..., 1] * 9617 + v[..., 2] * 4899 + (1 << 13)) >> 14).astype(np.uint8)
 
 
 def inverse_distances(near: float, far: float = np.inf, D: int = 64) -> np.ndarray:
@@ -148,6 +175,81 @@ class Sweeper:
                                                 res["aggregated"].ctypes.data_as(C.POINTER(C.c_ushort))))
         return res
 
+    def _colour_frame(self, images):
+        """n images [height, width] or [height, width, 3] uint8, all alike -> (arrays, pointers, stride, channels)"""
+        if self._handle is None:
+            raise ValueError("the sweeper is closed")
+        if len(images) != self.n:
+            raise ValueError(f"{self.n} cameras need {self.n} images")
+        first = np.asarray(images[0])
+        ch = 1 if first.ndim == 2 else 3
+        shape = (self.height, self.width) if ch == 1 else (self.height, self.width, 3)
+        imgs = []
+        for x in images:
+            a = np.asarray(x)
+            if a.dtype != np.uint8 or a.shape != shape:
+                raise ValueError(f"images are uint8 arrays of shape {shape}")
+            inner = a.strides[1:] == ((3, 1) if ch == 3 else (1,))
+            imgs.append(a if inner and a.strides[0] >= self.width * ch else np.ascontiguousarray(a))
+        if len({a.strides[0] for a in imgs}) > 1:
+            imgs = [np.ascontiguousarray(a) for a in imgs]
+        return imgs, (C.c_void_p * self.n)(*[a.ctypes.data for a in imgs]), int(imgs[0].strides[0]), ch
+
+    def _compose_args(self, index16, gains, over):
+        p = over if isinstance(over, _lib.CSweepComposeParams) else compose_params(**over)
+        idx, iptr, istride = None, None, 0
+        if index16 is not None:
+            idx = np.asarray(index16)
+            if idx.dtype != np.int16 or idx.shape != (self.pano_h, self.pano_w) or idx.strides[1] != 2 or idx.strides[0] % 2:
+                raise ValueError("index16 is an int16 array (or row-padded view) of the panorama's shape")
+            iptr, istride = idx.ctypes.data_as(C.POINTER(C.c_short)), int(idx.strides[0] // 2)
+        g, gptr = None, None
+        if gains is not None:
+            g = np.ascontiguousarray(gains, dtype=np.uint16)
+            if g.shape != (self.n,):
+                raise ValueError(f"gains: {self.n} Q8 values")
+            gptr = _lib.ushort_ptr(g)
+        return p, (idx, iptr, istride), (g, gptr)
+
+    def compose(self, images, index16=None, gains=None, out: np.ndarray | None = None, with_coverage: bool = False, with_seconds: bool = False, **params):
+        """tscm_sweep_compose -> uint8 [pano_h, pano_w] or [pano_h, pano_w, 3]: the frame blended at the hypothesis that
+        index16 names per pixel (None: the map of this sweeper's last depth(), still on the device).  images: grey or
+        3-channel, they need not be those of the depth pass.  params: the fields of compose_params.  `out` may be a
+        row-padded view, whose padding keeps its values."""
+        imgs, ptrs, stride, ch = self._colour_frame(images)
+        p, (idx, iptr, istride), (g, gptr) = self._compose_args(index16, gains, params)
+        shape = (self.pano_h, self.pano_w) if ch == 1 else (self.pano_h, self.pano_w, ch)
+        if out is None:
+            out = np.zeros(shape, dtype=np.uint8)
+        inner = out.strides[1:] == ((ch, 1) if ch > 1 else (1,))
+        if out.dtype != np.uint8 or out.shape != shape or not inner:
+            raise ValueError("out must be a uint8 array (or row-padded view) of the panorama's shape")
+        cov = np.zeros((self.pano_h, self.pano_w), dtype=np.uint8) if with_coverage else None
+        ub = C.POINTER(C.c_ubyte)
+        sec = C.c_double(0.0)
+        _lib.check(_lib.lib().tscm_sweep_compose(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), gptr, out.ctypes.data_as(ub), int(out.strides[0]),
+                                                 None if cov is None else cov.ctypes.data_as(ub), C.byref(sec)))
+        res = (out,) + ((cov,) if with_coverage else ()) + ((sec.value,) if with_seconds else ())
+        return res[0] if len(res) == 1 else res
+
+    def compose_stages(self, images, index16=None, gains=None, **params) -> dict:
+        """tscm_sweep_compose_stages -> hypothesis [ph, pw], sampled [n, ph, pw, C], alpha [n, ph, pw], label [ph, pw] and, in
+        MULTIBAND mode, mask_pyramid [n, S], lap_pyramid [n, C, S], blend_pyramid [C, S] (levels 0..L one after the other)."""
+        imgs, ptrs, stride, ch = self._colour_frame(images)
+        p, (idx, iptr, istride), (g, gptr) = self._compose_args(index16, gains, params)
+        n, ph, pw = self.n, self.pano_h, self.pano_w
+        res = dict(hypothesis=np.zeros((ph, pw), np.uint8), sampled=np.zeros((n, ph, pw, ch), np.uint8), alpha=np.zeros((n, ph, pw), np.uint8),
+                   label=np.zeros((ph, pw), np.uint8))
+        ub, sh = C.POINTER(C.c_ubyte), C.POINTER(C.c_short)
+        pyr = [None, None, None]
+        if p.mode == _lib.PANO_MULTIBAND:
+            S = sum((ph >> l) * (pw >> l) for l in range(max(int(p.levels), 0) + 1))
+            res.update(mask_pyramid=np.zeros((n, S), np.uint8), lap_pyramid=np.zeros((n, ch, S), np.int16), blend_pyramid=np.zeros((ch, S), np.int16))
+            pyr = [res["mask_pyramid"].ctypes.data_as(ub), res["lap_pyramid"].ctypes.data_as(sh), res["blend_pyramid"].ctypes.data_as(sh)]
+        _lib.check(_lib.lib().tscm_sweep_compose_stages(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), gptr, res["hypothesis"].ctypes.data_as(ub),
+                                                        res["sampled"].ctypes.data_as(ub), res["alpha"].ctypes.data_as(ub), res["label"].ctypes.data_as(ub), *pyr))
+        return res
+
     def stage_times(self) -> np.ndarray:
         """Device seconds of the last depth / stages call: cost volume, aggregation, winner."""
         t = np.zeros(3)
@@ -191,3 +293,20 @@ def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: fl
             idx = stereo.filter(idx, min_disparity=0, device=device, **post)
         pts, valid = s.points(idx)
     return idx, pts, valid
+
+
+def rig_panorama(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: float = 500.0, far: float = np.inf, D: int = 64, weights="radial",
+                 projection="equirect", device: int = 0, post=None, mode="multiband", levels: int = 4, gains=None, fallback_index: int = 0, **over):
+    """One call from a calibration and a frame to the parallax-free panorama: (panorama uint8 [ph, pw] or [ph, pw, 3],
+    index16 [ph, pw], coverage [ph, pw]).  Colour images (BGR) go through bgr_to_gray for the depth pass and are blended in
+    colour.  post: keyword arguments of stereo.filter for the index map, as in rig_depth; the filtered map is the one the
+    frame is composed at and the one returned.  fallback_index: the hypothesis of a pixel without depth (0 = far)."""
+    size = (np.asarray(images[0]).shape[1], np.asarray(images[0]).shape[0])
+    inv = inverse_distances(near, far, D)
+    with Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv, weights=weights, projection=projection, device=device, **over) as s:
+        idx = s.depth([bgr_to_gray(x) for x in images])
+        if post:
+            from . import stereo
+            idx = stereo.filter(idx, min_disparity=0, device=device, **post)
+        pano, cov = s.compose(images, index16=idx if post else None, gains=gains, with_coverage=True, mode=mode, levels=levels, fallback_index=fallback_index)
+    return pano, idx, cov
