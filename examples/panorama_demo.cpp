@@ -32,18 +32,21 @@ int main(int argc, char **argv)
     tscm::Size pano = { 2048, 1024 };
     tscm_panorama_params params;
     tscm_panorama_default_params(&params);
-    bool gains = true;
+    bool gains = true, bad = false;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--size") && a + 2 < argc) { pano.width = std::atoi(argv[a + 1]); pano.height = std::atoi(argv[a + 2]); a += 2; }
         else if (!std::strcmp(argv[a], "--mode") && a + 1 < argc) {
             const std::string m = argv[++a];
-            params.mode = m == "seam" ? TSCM_PANO_SEAM : m == "feather" ? TSCM_PANO_FEATHER : TSCM_PANO_MULTIBAND;
+            if (m == "seam") params.mode = TSCM_PANO_SEAM;
+            else if (m == "feather") params.mode = TSCM_PANO_FEATHER;
+            else if (m == "multiband") params.mode = TSCM_PANO_MULTIBAND;
+            else bad = true;
         }
         else if (!std::strcmp(argv[a], "--levels") && a + 1 < argc) params.levels = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--no-gains")) gains = false;
         else files.push_back(argv[a]);
     }
-    if (argc < 3 || files.empty()) {
+    if (bad || argc < 3 || files.empty()) {
         std::fprintf(stderr, "usage: %s calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--mode seam|feather|multiband] [--levels L] [--no-gains]\n", argv[0]);
         return 2;
     }

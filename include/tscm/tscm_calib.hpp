@@ -709,7 +709,8 @@ inline std::vector<Point3d> stereo_points(const std::vector<short> &disparity, S
 // check_w2 = 1, as maps.panorama_descs builds them), kept on the device with the alphas, seam labels and mask pyramids by a
 // tscm_panorama handle; compose() blends one frame.  intr [9 n], Twc [12 n] (row-major 3x4 [R | t]) as tscm_yaml_read
 // returns them; weights: NULL (all 255) or n images of image_size (entries may be NULL); params == NULL:
-// tscm_panorama_default_params (multi-band, 4 levels).
+// tscm_panorama_default_params (multi-band, 4 levels).  tests/test_gpu_cpp_mirror.py runs the class through
+// tests/native/mirror_perception.cpp and holds overlap, gains and the composed bytes to panorama.Composer.
 class Panorama {
 public:
     Panorama(int n_cameras, const double *intr, const double *Twc, Size image_size, int channels, Size pano_size, const tscm_panorama_params *params = NULL,
@@ -826,7 +827,8 @@ inline std::vector<unsigned short> exposure_gains(int n, const std::vector<long 
 // descriptors a Panorama uses, with the camera centres Twc[:, 3]; inv_distance: D = params.num_hypotheses values, not
 // negative and strictly increasing (0 = infinity).  intr [9 n], Twc [12 n] as tscm_yaml_read returns them; grey images;
 // weights: NULL (all 255) or n images of image_size (entries may be NULL); params == NULL: tscm_sweep_default_params with
-// num_hypotheses = inv_distance.size().
+// num_hypotheses = inv_distance.size().  tests/test_gpu_cpp_mirror.py runs depth, compose and points through
+// tests/native/mirror_perception.cpp and holds them to sweep.Sweeper, and the all-invalid compose to Panorama::compose.
 class Sweep {
 public:
     Sweep(int n_cameras, const double *intr, const double *Twc, Size image_size, Size pano_size, const std::vector<double> &inv_distance,

@@ -31,14 +31,17 @@ def built(src, name):
     return exe
 
 
-def checker_fixture(src, stem):
-    """The module's `checker` fixture: the check built plain, and under AddressSanitizer + UBSan."""
+def checker_fixture(src, stem, include=None):
+    """The module's `checker` fixture: the check built plain, and under AddressSanitizer + UBSan.  include: one more include
+    path, relative to the repository (for a check of a header under include/)."""
+    extra = ["-I", os.path.join(ROOT, include)] if include else []
+
     @pytest.fixture(scope="module", params=["plain", "asan_ubsan"])
     def checker(request):
         if request.param == "plain":
-            exe, r = build(src, stem, ["-O2"])
+            exe, r = build(src, stem, ["-O2", *extra])
         else:
-            exe, r = build(src, stem + "_san", SANITIZE)
+            exe, r = build(src, stem + "_san", [*SANITIZE, *extra])
             if r.returncode != 0 and "asan" in (r.stderr + r.stdout).lower():
                 pytest.skip("sanitizer runtime not installed")
         assert r.returncode == 0, r.stderr[-2000:]

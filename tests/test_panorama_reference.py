@@ -259,5 +259,10 @@ def test_multiband_and_gains_shrink_the_step_at_the_seams():
 
 def test_panorama_demo_compiles_and_links(tmp_path):
     csrc = os.path.join(ROOT, "tscm_calib_amd", "csrc")
+    exe = str(tmp_path / "a.out")
     subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "panorama_demo.cpp"),
-                           "-L", csrc, "-ltscm_hip", "-Wl,-rpath," + csrc, "-o", str(tmp_path / "a.out")])
+                           "-L", csrc, "-ltscm_hip", "-Wl,-rpath," + csrc, "-o", exe])
+    # a mode it does not know is answered with the usage text, as sweep_panorama_demo answers it, not blended as multiband
+    for args in ([], ["calib.yaml", "a.ppm", "b.ppm", "--mode", "average"]):
+        run = subprocess.run([exe, *args], capture_output=True, text=True)
+        assert run.returncode == 2 and "usage" in run.stderr, (args, run.returncode, run.stderr)
