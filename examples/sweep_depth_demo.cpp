@@ -3,6 +3,9 @@
 // (tscm_sweep_depth) and the 3-D points of the index map (tscm_sweep_points).
 // Images are binary grey PGM (P5) files of one size, one per camera of the file.
 //   usage: sweep_depth_demo calib.yaml cam0.pgm cam1.pgm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8]
+//                           [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]
+// --fill: every pixel without depth gets the lowest | second_lowest | median of the nearest valid indices along the 8 path
+// directions, over the seam too (tscm_stereo_fill with wrap_x = 1), before the points are taken.
 // writes sweep_index.pgm (16-bit, big-endian as PGM has it: 16 x hypothesis index + 16, so 0 = invalid) and sweep_points.ply
 // (ASCII, the valid points in the rig frame) into the working directory.  near: in the units of the calibration's translations.
 #include <cstdio>
@@ -33,15 +36,21 @@ int main(int argc, char **argv)
     double near = 500.0;
     tscm_sweep_params params;
     tscm_sweep_default_params(&params);
+    bool fill = false, bad = false;
+    tscm_stereo_fill_params fill_params;
+    tscm_stereo_fill_default_params(&fill_params);
+    fill_params.wrap_x = 1;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--size") && a + 2 < argc) { pano.width = std::atoi(argv[a + 1]); pano.height = std::atoi(argv[a + 2]); a += 2; }
         else if (!std::strcmp(argv[a], "--near") && a + 1 < argc) near = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--hypotheses") && a + 1 < argc) params.num_hypotheses = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--paths") && a + 1 < argc) params.paths = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--fill") && a + 1 < argc) { fill = true; bad |= !tscm::parse_fill_option(argv[++a], &fill_params); }
         else files.push_back(argv[a]);
     }
-    if (argc < 4 || files.size() < 2 || !(near > 0.0) || params.num_hypotheses < 2) {
-        std::fprintf(stderr, "usage: %s calib.yaml cam0.pgm cam1.pgm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8]\n", argv[0]);
+    if (bad || argc < 4 || files.size() < 2 || !(near > 0.0) || params.num_hypotheses < 2) {
+        std::fprintf(stderr, "usage: %s calib.yaml cam0.pgm cam1.pgm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]\n",
+                     argv[0]);
         return 2;
     }
     try {
@@ -66,7 +75,8 @@ int main(int argc, char **argv)
         for (int z = 0; z < D; ++z) inv[(size_t)z] = (double)z / ((double)(D - 1) * near);
         tscm::Sweep sweep(n, intr.data(), Twc.data(), size, pano, inv, &params);
         double seconds = 0.0;
-        const std::vector<short> index16 = sweep.depth(ptr.data(), 0, &seconds);
+        std::vector<short> index16 = sweep.depth(ptr.data(), 0, &seconds);
+        if (fill) index16 = tscm::stereo_fill(index16, pano, &fill_params);
         std::vector<unsigned char> valid;
         const std::vector<tscm::Point3d> pts = sweep.points(index16, valid);
         std::ofstream f("sweep_index.pgm", std::ios::binary);

@@ -3,7 +3,9 @@
 // (tscm_sweep_compose) instead of at infinity, so that near objects are not doubled where two cameras overlap.
 // Images are binary PGM (P5, grey) or PPM (P6, read as 3 channels in file order) files of one size and kind, one per camera.
 //   usage: sweep_panorama_demo calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8]
-//                              [--mode seam|feather|multiband] [--levels L]
+//                              [--mode seam|feather|multiband] [--levels L] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]
+// --fill: every pixel without depth gets the lowest | second_lowest | median of the nearest valid indices along the 8 path
+// directions, over the seam too (tscm_stereo_fill with wrap_x = 1), and the frame is composed at the filled map.
 // writes sweep_panorama.pgm or .ppm into the working directory.  near: in the units of the calibration's translations.
 #include <cstdio>
 #include <cstdlib>
@@ -37,13 +39,17 @@ int main(int argc, char **argv)
     tscm_sweep_default_params(&params);
     tscm_sweep_compose_params blend;
     tscm_sweep_compose_default_params(&blend);
-    bool bad = false;
+    bool bad = false, fill = false;
+    tscm_stereo_fill_params fill_params;
+    tscm_stereo_fill_default_params(&fill_params);
+    fill_params.wrap_x = 1;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--size") && a + 2 < argc) { pano.width = std::atoi(argv[a + 1]); pano.height = std::atoi(argv[a + 2]); a += 2; }
         else if (!std::strcmp(argv[a], "--near") && a + 1 < argc) near = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--hypotheses") && a + 1 < argc) params.num_hypotheses = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--paths") && a + 1 < argc) params.paths = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--levels") && a + 1 < argc) blend.levels = std::atoi(argv[++a]);
+        else if (!std::strcmp(argv[a], "--fill") && a + 1 < argc) { fill = true; bad |= !tscm::parse_fill_option(argv[++a], &fill_params); }
         else if (!std::strcmp(argv[a], "--mode") && a + 1 < argc) {
             const std::string m = argv[++a];
             if (m == "seam") blend.mode = TSCM_PANO_SEAM;
@@ -53,7 +59,7 @@ int main(int argc, char **argv)
         } else files.push_back(argv[a]);
     }
     if (bad || argc < 4 || files.size() < 2 || !(near > 0.0) || params.num_hypotheses < 2) {
-        std::fprintf(stderr, "usage: %s calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--mode seam|feather|multiband] [--levels L]\n",
+        std::fprintf(stderr, "usage: %s calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--mode seam|feather|multiband] [--levels L] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]\n",
                      argv[0]);
         return 2;
     }
@@ -89,8 +95,9 @@ int main(int argc, char **argv)
         for (int z = 0; z < D; ++z) inv[(size_t)z] = (double)z / ((double)(D - 1) * near);
         tscm::Sweep sweep(n, intr.data(), Twc.data(), size, pano, inv, &params);
         double sec_depth = 0.0, sec_compose = 0.0;
-        const std::vector<short> index16 = sweep.depth(gptr.data(), 0, &sec_depth);
-        const std::vector<unsigned char> out = sweep.compose(ptr.data(), channels, NULL, &blend, NULL, 0, NULL, &sec_compose);
+        std::vector<short> index16 = sweep.depth(gptr.data(), 0, &sec_depth);
+        if (fill) index16 = tscm::stereo_fill(index16, pano, &fill_params);
+        const std::vector<unsigned char> out = sweep.compose(ptr.data(), channels, fill ? &index16 : NULL, &blend, NULL, 0, NULL, &sec_compose);
         size_t n_valid = 0;
         for (size_t t = 0; t < index16.size(); ++t) n_valid += index16[t] >= 0;
         const char *name = channels == 1 ? "sweep_panorama.pgm" : "sweep_panorama.ppm";

@@ -845,6 +845,57 @@ int tscm_stereo_filter_stages(const short *disparity, int width, int height, int
                               const tscm_stereo_filter_params *params, int device_index,
                               int *label /* [h*w] */, int *size /* [h*w] */, short *despeckled /* [h*w] */);
 
+/* Hole filling of a disparity map or a sweep index map: the interpolation of Hirschmueller's SGM paper, section 2.6.  Every
+ * stage above can only invalidate; this one puts values back.  Integers throughout and nothing depends on an order, defined
+ * here so that a host restatement gives the same bits (tests/stereo_fill_ref.py).
+ *   input       d [height][disp_stride] int16; invalid = 16 (min_disparity - 1); a pixel is valid iff d != invalid.  A sweep
+ *               index map (tscm_sweep_depth) is such a map with min_disparity = 0.
+ *   directions  (dx, dy) in the matcher's order: (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1) (-1,1); the first `paths`
+ *               of them are used, paths = 4 or 8.
+ *   walk        for a pixel p = (x, y) and a direction r visit (x + t dx, y + t dy), t = 1, 2, ...  The walk ends without a
+ *               result when the row leaves [0, height), when max_distance > 0 and t > max_distance, and with wrap_x = 0 when
+ *               the column leaves [0, width).  With wrap_x = 1 the column is taken modulo width, and a horizontal walk ends
+ *               after t = width - 1, so it never reaches p itself; diagonals continue over the seam.  The first valid pixel
+ *               met gives the candidate v_r and its distance t_r.  The walk reads the input map only, never a filled value.
+ *               Candidates are defined for every pixel, valid or not.
+ *   fill        a valid pixel keeps its value, mask 0.  For an invalid pixel let n be the number of directions with a
+ *               candidate: n < min_directions leaves it invalid, mask 2; otherwise, mask 1, the candidates are sorted
+ *               ascending as int32, v[0] <= ... <= v[n - 1], and the output is
+ *                 TSCM_FILL_LOWEST         v[0]
+ *                 TSCM_FILL_SECOND_LOWEST  v[min(1, n - 1)]     (the background of an occlusion)
+ *                 TSCM_FILL_MEDIAN         v[(n - 1) >> 1]      (a mismatch)
+ * out == disparity with equal strides is allowed (the device works on its own copies); elements of `out` between width and
+ * out_stride keep the caller's values.  mask [h*w] may be NULL.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL disparity / params / out,
+ * disp_stride or out_stride < width, a struct_size other than sizeof(tscm_stereo_fill_params), rule outside 0..2, paths
+ * other than 4 or 8, min_directions outside 1..paths, max_distance outside 0..32767, wrap_x other than 0 or 1, a
+ * min_disparity outside -2047..2031 (the filter's range), width or height above 32767 (distances are int16).  width == 0 or
+ * height == 0 returns 0 without touching a device.  device_index and seconds_kernel: as for the matcher. */
+#define TSCM_FILL_LOWEST 0
+#define TSCM_FILL_SECOND_LOWEST 1
+#define TSCM_FILL_MEDIAN 2
+typedef struct tscm_stereo_fill_params {
+    int struct_size;     /* sizeof(tscm_stereo_fill_params)                              */
+    int min_disparity;   /* defines the invalid value, as for the matcher; 0 for a sweep */
+    int rule;            /* TSCM_FILL_*                                                  */
+    int paths;           /* 4 or 8                                                       */
+    int max_distance;    /* 0 = unlimited; else the longest walk, 1..32767               */
+    int min_directions;  /* 1..paths: fewer candidates leave the pixel invalid           */
+    int wrap_x;          /* 1: column 0 follows column width - 1 (a 360 degree map)      */
+} tscm_stereo_fill_params;
+void tscm_stereo_fill_default_params(tscm_stereo_fill_params *p);   /* 0, MEDIAN, 8, 0, 1, 0 */
+
+int tscm_stereo_fill(const short *disparity, int width, int height, int disp_stride,
+                     const tscm_stereo_fill_params *params, int device_index,
+                     short *out /* [height][out_stride] */, int out_stride, unsigned char *mask /* [h*w], may be NULL */,
+                     double *seconds_kernel /* may be NULL */);
+
+/* The candidates of the same launches, for parity tests: value and distance [paths][h*w], either may be NULL.  Without a
+ * candidate value holds the invalid value and distance 0. */
+int tscm_stereo_fill_stages(const short *disparity, int width, int height, int disp_stride,
+                            const tscm_stereo_fill_params *params, int device_index,
+                            short *value /* [paths][h*w] */, short *distance /* [paths][h*w], 0 = none */);
+
 /* ------------------------------------------------------------------ panorama of a calibrated rig
  * What the tables of panorama_descs (one EQUIRECT or CYLINDRICAL table per camera, all in the rig frame) are for: the
  * stitched image.  A handle keeps everything that does not depend on a frame on the device -- the sample positions, the

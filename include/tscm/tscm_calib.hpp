@@ -21,6 +21,7 @@
 //   (none)                                                 TripleSphereCamera::rectify_point   -> tscm_rectify_points
 //   (none: the rectified pair is its last product)         stereo_match, stereo_points         -> tscm_stereo_match, tscm_stereo_points
 //   (none: cv::filterSpeckles / medianBlur downstream)     stereo_filter                       -> tscm_stereo_filter
+//   (none: hole filling is left to the caller)             stereo_fill, parse_fill_option      -> tscm_stereo_fill
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
@@ -31,6 +32,7 @@
 #include <tscm/tscm.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -688,6 +690,50 @@ inline std::vector<short> stereo_filter(const std::vector<short> &disparity, Siz
     if (out.empty()) return out;
     check(tscm_stereo_filter(disparity.data(), size.width, size.height, size.width, &p, device, out.data(), size.width, NULL));
     return out;
+}
+
+// stereo_fill: every invalid pixel of a disparity or sweep index map of `size` gets the lowest, second-lowest or median of
+// the nearest valid values along the path directions -> the filled map; params == NULL: tscm_stereo_fill_default_params
+// (set min_disparity to the matcher's, wrap_x = 1 for a 360 degree map).  mask: NULL, or receives 0 valid on input / 1 filled /
+// 2 left invalid per pixel.
+inline std::vector<short> stereo_fill(const std::vector<short> &disparity, Size size, const tscm_stereo_fill_params *params = NULL, int device = 0,
+                                      std::vector<unsigned char> *mask = NULL)
+{
+    if (disparity.size() != (size_t)size.width * size.height) throw std::runtime_error("tscm: the disparity map does not have the given size");
+    tscm_stereo_fill_params p;
+    if (params) p = *params;
+    else tscm_stereo_fill_default_params(&p);
+    std::vector<short> out(disparity.size());
+    if (mask) mask->assign(disparity.size(), 0);
+    if (out.empty()) return out;
+    check(tscm_stereo_fill(disparity.data(), size.width, size.height, size.width, &p, device, out.data(), size.width, mask ? mask->data() : NULL, NULL));
+    return out;
+}
+
+// The demos' --fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]] with RULE lowest | second_lowest | median -> the three fields of p;
+// false when the text is none of that (the ranges are the library's to refuse).
+inline bool parse_fill_option(const char *text, tscm_stereo_fill_params *p)
+{
+    const std::string s(text);
+    const size_t comma = s.find(',');
+    const std::string rule = s.substr(0, comma);
+    if (rule == "lowest") p->rule = TSCM_FILL_LOWEST;
+    else if (rule == "second_lowest") p->rule = TSCM_FILL_SECOND_LOWEST;
+    else if (rule == "median") p->rule = TSCM_FILL_MEDIAN;
+    else return false;
+    if (comma == std::string::npos) return true;
+    int *const field[2] = { &p->max_distance, &p->min_directions };
+    const char *q = s.c_str() + comma + 1;
+    for (int k = 0; k < 2; ++k) {                               // whole decimal numbers, nothing before, between or after them
+        char *end = NULL;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || (*q != '-' && (*q < '0' || *q > '9')) || v < -1000000 || v > 1000000) return false;
+        *field[k] = (int)v;
+        if (!*end) return true;
+        if (*end != ',' || k == 1) return false;
+        q = end + 1;
+    }
+    return false;
 }
 
 // stereo_points: the disparities of stereo_match on the pair of rectify_pair_maps (left_map = desc[0], projection

@@ -36,6 +36,7 @@ PROJ_KINDS = {"perspective": PROJ_PERSPECTIVE, "longlat": PROJ_LONGLAT, "cylindr
               "stereographic": PROJ_STEREOGRAPHIC, "equirect": PROJ_EQUIRECT}
 # panorama blend modes (tscm.h: TSCM_PANO_*)
 PANO_SEAM, PANO_FEATHER, PANO_MULTIBAND = 0, 1, 2
+FILL_LOWEST, FILL_SECOND_LOWEST, FILL_MEDIAN = 0, 1, 2
 PANO_MODES = {"seam": PANO_SEAM, "feather": PANO_FEATHER, "multiband": PANO_MULTIBAND}
 # held intrinsics (tscm.h: TSCM_FIX_*): bit k holds intrinsic k of the 9-vector
 INTRINSIC_NAMES = ("fx", "fy", "cx", "cy", "xi", "lambda", "alpha", "b", "c")
@@ -132,6 +133,12 @@ class CStereoFilterParams(C.Structure):
                 ("median", C.c_int)]
 
 
+class CStereoFillParams(C.Structure):
+    """tscm_stereo_fill_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("min_disparity", C.c_int), ("rule", C.c_int), ("paths", C.c_int), ("max_distance", C.c_int),
+                ("min_directions", C.c_int), ("wrap_x", C.c_int)]
+
+
 class CPanoramaParams(C.Structure):
     """tscm_panorama_params (tscm.h)"""
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int)]
@@ -173,6 +180,7 @@ EXPORTS = [
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
+    "tscm_stereo_fill_default_params", "tscm_stereo_fill", "tscm_stereo_fill_stages",
     "tscm_panorama_default_params", "tscm_panorama_create", "tscm_panorama_compose", "tscm_panorama_stages", "tscm_panorama_overlap", "tscm_panorama_destroy",
     "tscm_build_sweep_maps",
     "tscm_sweep_default_params", "tscm_sweep_create", "tscm_sweep_depth", "tscm_sweep_stages", "tscm_sweep_stage_times", "tscm_sweep_points", "tscm_sweep_destroy",
@@ -276,6 +284,11 @@ def lib():
     L.tscm_stereo_filter.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFilterParams), C.c_int, C.POINTER(C.c_short), C.c_int, dp]
     L.tscm_stereo_filter_stages.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFilterParams), C.c_int, C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.POINTER(C.c_short)]
+    L.tscm_stereo_fill_default_params.argtypes = [C.POINTER(CStereoFillParams)]
+    L.tscm_stereo_fill_default_params.restype = None
+    L.tscm_stereo_fill.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFillParams), C.c_int, C.POINTER(C.c_short), C.c_int, ubp, dp]
+    L.tscm_stereo_fill_stages.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFillParams), C.c_int, C.POINTER(C.c_short),
+                                          C.POINTER(C.c_short)]
     fp, shp, llp, vpp = C.POINTER(C.c_float), C.POINTER(C.c_short), C.POINTER(C.c_longlong), C.POINTER(vp)
     L.tscm_panorama_default_params.argtypes = [C.POINTER(CPanoramaParams)]
     L.tscm_panorama_default_params.restype = None

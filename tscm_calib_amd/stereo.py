@@ -1,7 +1,7 @@
 """Stereo matching and depth on a rectified pair (tscm.h: tscm_stereo_*): census + semi-global matching on the device,
-the post-filter of a disparity map (speckle removal, masked median), the 3-D points of a disparity map, and pair_depth,
-the chain from two fisheye images of a calibrated rig to points:
-rectify_pair_descs -> build_maps -> remap -> match [-> filter] -> points."""
+the post-filter of a disparity map (speckle removal, masked median), hole filling from the nearest valid values along the
+path directions, the 3-D points of a disparity map, and pair_depth, the chain from two fisheye images of a calibrated rig
+to points: rectify_pair_descs -> build_maps -> remap -> match [-> filter] [-> fill] -> points."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,6 +14,8 @@ from . import maps as _maps
 PARAM_NAMES = ("min_disparity", "num_disparities", "p1", "p2", "paths", "uniqueness_ratio", "disp12_max_diff")
 STAGE_NAMES = ("census", "cost", "aggregate", "right_winner", "winner")
 FILTER_PARAM_NAMES = ("min_disparity", "speckle_window_size", "speckle_range", "median")
+FILL_PARAM_NAMES = ("min_disparity", "rule", "paths", "max_distance", "min_directions", "wrap_x")
+FILL_RULES = dict(lowest=_lib.FILL_LOWEST, second_lowest=_lib.FILL_SECOND_LOWEST, median=_lib.FILL_MEDIAN)
 
 
 def params(**over) -> _lib.CStereoParams:
@@ -133,6 +135,59 @@ def filter_stages(disp, device: int = 0, **over) -> dict:
     return dict(label=label, size=size, despeckled=desp)
 
 
+def fill_params(**over) -> _lib.CStereoFillParams:
+    """tscm_stereo_fill_default_params with the given fields replaced; rule also as "lowest" | "second_lowest" | "median"."""
+    p = _lib.CStereoFillParams()
+    _lib.lib().tscm_stereo_fill_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in FILL_PARAM_NAMES:
+            raise TypeError(f"unknown stereo fill parameter {k!r}: one of {', '.join(FILL_PARAM_NAMES)}")
+        if k == "rule" and isinstance(v, str):
+            if v not in FILL_RULES:
+                raise ValueError(f"unknown fill rule {v!r}: one of {', '.join(FILL_RULES)}")
+            v = FILL_RULES[v]
+        setattr(p, k, int(v))
+    return p
+
+
+def fill(disp, device: int = 0, out: np.ndarray | None = None, with_mask: bool = False, with_seconds: bool = False, **over):
+    """tscm_stereo_fill: every invalid pixel of a disparity (or sweep index) map gets the lowest, second-lowest or median of
+    the nearest valid values along the path directions -> int16 [h, w]; with_mask adds uint8 [h, w]: 0 valid on input,
+    1 filled, 2 left invalid.  `disp` may be a row-padded view; `out` may be one too (its padding keeps its values) and may
+    be `disp` itself."""
+    disp = _disparity_map(disp)
+    h, w = disp.shape
+    p = fill_params(**over)
+    if out is None:
+        out = np.zeros((h, w), dtype=np.int16)
+    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
+        raise ValueError("out must be an int16 array (or row-padded view) of the map's shape")
+    mask = np.zeros((h, w), dtype=np.uint8) if with_mask else None
+    sp = C.POINTER(C.c_short)
+    sec = C.c_double(0.0)
+    _lib.check(_lib.lib().tscm_stereo_fill(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, C.byref(p), device,
+                                           out.ctypes.data_as(sp), out.strides[0] // 2 if h else w,
+                                           None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(sec)))
+    res = (out,) + ((mask,) if with_mask else ()) + ((sec.value,) if with_seconds else ())
+    return res[0] if len(res) == 1 else res
+
+
+_fill = fill                # pair_depth has a keyword of that name
+
+
+def fill_stages(disp, device: int = 0, **over) -> dict:
+    """tscm_stereo_fill_stages -> value, distance int16 [paths, h, w]: per direction the nearest valid value and the steps
+    to it (the invalid value and 0 without one), for every pixel."""
+    disp = _disparity_map(disp)
+    h, w = disp.shape
+    p = fill_params(**over)
+    value, distance = np.zeros((max(int(p.paths), 0), h, w), dtype=np.int16), np.zeros((max(int(p.paths), 0), h, w), dtype=np.int16)
+    sp = C.POINTER(C.c_short)
+    _lib.check(_lib.lib().tscm_stereo_fill_stages(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, C.byref(p), device,
+                                                  value.ctypes.data_as(sp), distance.ctypes.data_as(sp)))
+    return dict(value=value, distance=distance)
+
+
 def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0):
     """tscm_stereo_points: the disparity map of the left image of a PERSPECTIVE or LONGLAT pair (desc = its MapDesc) ->
     (points [h, w, 3] fp64 in the pair frame of the left camera, valid [h, w] bool); invalid points are NaN."""
@@ -150,15 +205,19 @@ def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0)
 
 
 def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat", width: int = 640, height: int = 320, fov_x: float = np.pi,
-               fov_y: float = np.pi / 2, device: int = 0, matcher=None, post=None, **over):
+               fov_y: float = np.pi / 2, device: int = 0, matcher=None, post=None, fill=None, **over):
     """Two grey fisheye images of cameras a and b of a calibrated rig -> (points [height, width, 3] in the pair frame of
     camera a, valid [height, width], R_pair).  R_pair = rectify_pair_rotation(t_a, t_b) turns pair-frame vectors into the
     rig frame: P_rig = R_pair @ P + t_a.  Camera a is the left image: b lies at +|t_b - t_a| on the pair frame's x-axis.
     `matcher` replaces match (same signature without device; for comparisons with a reference matcher).  `post`: a dict
     of filter parameters (speckle_window_size, speckle_range, median); the disparity map then passes through filter, with
-    the matcher's min_disparity, before its points are taken.  None: no filter."""
+    the matcher's min_disparity, before its points are taken.  None: no filter.  `fill`: a dict of fill parameters (rule,
+    paths, max_distance, min_directions, wrap_x), applied after `post`, also with the matcher's min_disparity.  None: no
+    filling."""
     if post is not None and "min_disparity" in post:
         raise TypeError("post: min_disparity is the matcher's")
+    if fill is not None and "min_disparity" in fill:
+        raise TypeError("fill: min_disparity is the matcher's")
     kind = _maps.projection_kind(projection)
     if kind not in (_lib.PROJ_PERSPECTIVE, _lib.PROJ_LONGLAT):
         raise ValueError("pair_depth needs rows that are epipolar lines: 'longlat' or 'perspective'")
@@ -172,6 +231,8 @@ def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat",
     disp = matcher(rect[0], rect[1], **over) if matcher is not None else match(rect[0], rect[1], device=device, **over)
     if post is not None:
         disp = filter(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **post)
+    if fill is not None:
+        disp = _fill(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **fill)
     Ta, Tb = np.asarray(Twc_a, dtype=np.float64).reshape(3, 4), np.asarray(Twc_b, dtype=np.float64).reshape(3, 4)
     baseline = float(np.linalg.norm(Tb[:, 3] - Ta[:, 3]))
     pts, valid = points(disp, descs[0], baseline, min_disparity=int(over.get("min_disparity", 0)), device=device)
