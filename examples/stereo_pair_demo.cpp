@@ -2,13 +2,16 @@
 // rectification of rectify_pair_demo.cpp (tscm_build_maps_ex, tscm_remap), then census + semi-global matching along the
 // rows (tscm_stereo_match), optionally the post-filter of the disparity map (tscm_stereo_filter) and the points of the
 // disparities in the pair frame of camera a (tscm_stereo_points).  Images are 8-bit binary PGM files (P5).
-//   usage: stereo_pair_demo [--speckle N,R] [--median M] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt
-//                           [width height [num_disparities [paths]]]
+//   usage: stereo_pair_demo [--speckle N,R] [--median M] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]]
+//                           calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]
 // --speckle N,R: components of at most N pixels whose neighbours differ by at most R disparities are dropped;
 // --median M: masked median of M x M (3 or 5) afterwards;
 // --fill RULE: after those, every invalid pixel gets the lowest | second_lowest | median of the nearest valid disparities
 // along the 8 path directions (tscm_stereo_fill), no further than MAX_DISTANCE pixels (0: any) and from at least
-// MIN_DIRECTIONS of them (1).
+// MIN_DIRECTIONS of them (1);
+// --refine RADIUS,SIGMA: last, the weighted median of every pixel's (2 RADIUS + 1)^2 window (tscm_stereo_refine), a neighbour
+// weighted by exp(-|difference of grey values in the rectified left image| / SIGMA), in ITERATIONS passes (1); FILL 1 gives
+// invalid pixels a value too (0).
 // disparity.pgm: disparity in pixels (saturated at 255), 0 where invalid; points.txt: one "column row X Y Z" line per
 // valid pixel, X Y Z in the units of the calibration's translations, pair frame (x along the baseline from a to b).
 #include <cmath>
@@ -46,20 +49,24 @@ int main(int argc_all, char **argv_all)
 {
     // the options may stand anywhere; what is left are the positional arguments
     int speckle_window = 0, speckle_range = 0, median = 0;
-    bool bad_option = false, fill = false;
+    bool bad_option = false, fill = false, refine = false;
     tscm_stereo_fill_params fill_params;
     tscm_stereo_fill_default_params(&fill_params);
+    tscm_stereo_refine_params refine_params;
+    tscm_stereo_refine_default_params(&refine_params);
+    double sigma = 0.0;
     std::vector<char *> argv(1, argv_all[0]);
     for (int k = 1; k < argc_all; ++k) {
         if (!std::strcmp(argv_all[k], "--speckle") && k + 1 < argc_all) bad_option |= std::sscanf(argv_all[++k], "%d,%d", &speckle_window, &speckle_range) != 2;
         else if (!std::strcmp(argv_all[k], "--median") && k + 1 < argc_all) median = std::atoi(argv_all[++k]);
         else if (!std::strcmp(argv_all[k], "--fill") && k + 1 < argc_all) { fill = true; bad_option |= !tscm::parse_fill_option(argv_all[++k], &fill_params); }
+        else if (!std::strcmp(argv_all[k], "--refine") && k + 1 < argc_all) { refine = true; bad_option |= !tscm::parse_refine_option(argv_all[++k], &refine_params, &sigma); }
         else if (!std::strncmp(argv_all[k], "--", 2)) bad_option = true;
         else argv.push_back(argv_all[k]);
     }
     const int argc = (int)argv.size();
     if (argc < 8 || bad_option) {
-        std::fprintf(stderr, "usage: %s [--speckle N,R] [--median M] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]\n",
+        std::fprintf(stderr, "usage: %s [--speckle N,R] [--median M] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]] calib.yaml cam_a cam_b a.pgm b.pgm disparity.pgm points.txt [width height [num_disparities [paths]]]\n",
                      argv[0]);
         return 2;
     }
@@ -101,6 +108,11 @@ int main(int argc_all, char **argv_all)
         if (fill) {
             fill_params.min_disparity = params.min_disparity;
             disparity = tscm::stereo_fill(disparity, size, &fill_params);
+        }
+        if (refine) {
+            refine_params.min_disparity = params.min_disparity;
+            const std::vector<unsigned char> table = tscm::range_weights(sigma);
+            disparity = tscm::stereo_refine(disparity, rect[0], size, &table, &refine_params);
         }
         const double dt[3] = { Tb[3] - Ta[3], Tb[7] - Ta[7], Tb[11] - Ta[11] };
         const double baseline = std::sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);

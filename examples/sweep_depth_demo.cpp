@@ -3,9 +3,12 @@
 // (tscm_sweep_depth) and the 3-D points of the index map (tscm_sweep_points).
 // Images are binary grey PGM (P5) files of one size, one per camera of the file.
 //   usage: sweep_depth_demo calib.yaml cam0.pgm cam1.pgm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8]
-//                           [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]
+//                           [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]]
 // --fill: every pixel without depth gets the lowest | second_lowest | median of the nearest valid indices along the 8 path
 // directions, over the seam too (tscm_stereo_fill with wrap_x = 1), before the points are taken.
+// --refine: after that, the weighted median of every pixel's (2 RADIUS + 1)^2 window, over the seam too (tscm_stereo_refine
+// with wrap_x = 1), a neighbour weighted by exp(-|difference of grey values| / SIGMA) in the frame composed by seam at the
+// map as it stands, in ITERATIONS passes (1); FILL 1 gives pixels without depth a value too (0).
 // writes sweep_index.pgm (16-bit, big-endian as PGM has it: 16 x hypothesis index + 16, so 0 = invalid) and sweep_points.ply
 // (ASCII, the valid points in the rig frame) into the working directory.  near: in the units of the calibration's translations.
 #include <cstdio>
@@ -36,20 +39,25 @@ int main(int argc, char **argv)
     double near = 500.0;
     tscm_sweep_params params;
     tscm_sweep_default_params(&params);
-    bool fill = false, bad = false;
+    bool fill = false, refine = false, bad = false;
     tscm_stereo_fill_params fill_params;
     tscm_stereo_fill_default_params(&fill_params);
     fill_params.wrap_x = 1;
+    tscm_stereo_refine_params refine_params;
+    tscm_stereo_refine_default_params(&refine_params);
+    refine_params.wrap_x = 1;
+    double sigma = 0.0;
     for (int a = 2; a < argc; ++a) {
         if (!std::strcmp(argv[a], "--size") && a + 2 < argc) { pano.width = std::atoi(argv[a + 1]); pano.height = std::atoi(argv[a + 2]); a += 2; }
         else if (!std::strcmp(argv[a], "--near") && a + 1 < argc) near = std::atof(argv[++a]);
         else if (!std::strcmp(argv[a], "--hypotheses") && a + 1 < argc) params.num_hypotheses = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--paths") && a + 1 < argc) params.paths = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--fill") && a + 1 < argc) { fill = true; bad |= !tscm::parse_fill_option(argv[++a], &fill_params); }
+        else if (!std::strcmp(argv[a], "--refine") && a + 1 < argc) { refine = true; bad |= !tscm::parse_refine_option(argv[++a], &refine_params, &sigma); }
         else files.push_back(argv[a]);
     }
     if (bad || argc < 4 || files.size() < 2 || !(near > 0.0) || params.num_hypotheses < 2) {
-        std::fprintf(stderr, "usage: %s calib.yaml cam0.pgm cam1.pgm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]\n",
+        std::fprintf(stderr, "usage: %s calib.yaml cam0.pgm cam1.pgm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]]\n",
                      argv[0]);
         return 2;
     }
@@ -77,6 +85,13 @@ int main(int argc, char **argv)
         double seconds = 0.0;
         std::vector<short> index16 = sweep.depth(ptr.data(), 0, &seconds);
         if (fill) index16 = tscm::stereo_fill(index16, pano, &fill_params);
+        if (refine) {                                           // the guide: the grey frame at the map as it stands, holes at infinity
+            tscm_sweep_compose_params seam;
+            tscm_sweep_compose_default_params(&seam);
+            seam.mode = TSCM_PANO_SEAM;
+            const std::vector<unsigned char> guide = sweep.compose(ptr.data(), 1, &index16, &seam), table = tscm::range_weights(sigma);
+            index16 = tscm::stereo_refine(index16, guide, pano, &table, &refine_params);
+        }
         std::vector<unsigned char> valid;
         const std::vector<tscm::Point3d> pts = sweep.points(index16, valid);
         std::ofstream f("sweep_index.pgm", std::ios::binary);

@@ -896,6 +896,61 @@ int tscm_stereo_fill_stages(const short *disparity, int width, int height, int d
                             const tscm_stereo_fill_params *params, int device_index,
                             short *value /* [paths][h*w] */, short *distance /* [paths][h*w], 0 = none */);
 
+/* Edge-aware refinement of a disparity map or a sweep index map: the joint weighted median (Ma et al., "Constant time
+ * weighted median filtering for stereo matching and beyond", ICCV 2013).  Every stage above looks at the map alone; this one
+ * looks at the image the map belongs to: each pixel takes the median of its window, the neighbours weighted by how close
+ * their grey value is to the centre's, so that a depth edge moves back to the intensity edge and the streaks of a fill are
+ * smoothed without a value invented between foreground and background.  Integers throughout and nothing depends on an
+ * order, defined here so that a host restatement gives the same bits (tests/stereo_refine_ref.py).
+ * One pass on a map d [height][disp_stride] int16 with the guide g [height][guide_stride] uint8 (one channel), the table
+ * lut = range_weight (NULL: every entry 255) and inv = 16 (min_disparity - 1):
+ *   participants  of p = (x, y): the offsets (dx, dy), |dx|, |dy| <= radius, (0, 0) included, for which the row y + dy lies
+ *                 in [0, height) (rows are never clamped or wrapped), the column x + dx lies in [0, width) -- or wrap_x is
+ *                 set and it is taken modulo width -- and d(q) != inv at that pixel q.  With wrap_x and a window wider than
+ *                 the map a pixel takes part once per offset that names it.
+ *   weight        w_q = lut[|g(p) - g(q)|], the difference taken in int.
+ *   stage values  W(p) = sum of w_q and count(p) = the number of participants, for every pixel, valid or not;
+ *                 W <= 225 * 255.
+ *   output        d(p) == inv and fill_invalid == 0: inv.  Otherwise W(p) == 0: d(p).  Otherwise the smallest v among the
+ *                 participants' values, compared as int32, with 2 * (sum of w_q over the participants with d(q) <= v) >= W(p):
+ *                 the lower weighted median.  Equal values accumulate.
+ *   passes        pass i + 1 reads the whole output of pass i (Jacobi), never a value of its own pass; guide and table stay.
+ * Consequences: with all weights equal and non-zero and fill_invalid = 0, radius 1 / 2 is the median 3 / 5 of
+ * tscm_stereo_filter with the speckle rule off, bit for bit; a constant valid map is a fixed point.
+ * tscm_stereo_refine_weights (host code only): lut[k] = floor(255 exp(-k / sigma) + 0.5) in double for sigma > 0, +infinity
+ * giving 255 throughout; a sigma that is not > 0 (NaN included) gives 255, 0, 0, ...
+ * out == disparity with equal strides is allowed (the device works on its own copies); elements of `out` between width and
+ * out_stride keep the caller's values.  Any int16 is accepted as a value, -32768 and 32767 included.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL disparity / guide / params /
+ * out, disp_stride, guide_stride or out_stride < width, a struct_size other than sizeof(tscm_stereo_refine_params), radius
+ * outside 1..7, iterations outside 1..8, fill_invalid or wrap_x other than 0 or 1, a min_disparity outside -2047..2031,
+ * width * height above INT_MAX.  width == 0 or height == 0 returns 0 without touching a device.  device_index and
+ * seconds_kernel: as for the fill. */
+typedef struct tscm_stereo_refine_params {
+    int struct_size;     /* sizeof(tscm_stereo_refine_params)                                  */
+    int min_disparity;   /* defines the invalid value 16 (min_disparity - 1); 0 for a sweep    */
+    int radius;          /* 1..7: the window is (2 radius + 1)^2, at most 225 pixels           */
+    int iterations;      /* 1..8 passes, each on the whole output of the one before            */
+    int fill_invalid;    /* 0: an invalid pixel stays invalid; 1: it is refined like any other */
+    int wrap_x;          /* 1: columns are taken modulo width (a 360 degree map)               */
+} tscm_stereo_refine_params;
+void tscm_stereo_refine_default_params(tscm_stereo_refine_params *p);   /* 0, 3, 1, 0, 0 */
+
+void tscm_stereo_refine_weights(double sigma, unsigned char *range_weight /* [256] */);
+
+int tscm_stereo_refine(const short *disparity, int width, int height, int disp_stride,
+                       const unsigned char *guide /* [height][guide_stride], one channel */, int guide_stride,
+                       const unsigned char *range_weight /* [256], NULL = all 255 */,
+                       const tscm_stereo_refine_params *params, int device_index,
+                       short *out /* [height][out_stride] */, int out_stride, double *seconds_kernel /* may be NULL */);
+
+/* The stage values of the first pass, for parity tests: weight_sum, count and the map after that pass, each [h*w], any of
+ * them may be NULL. */
+int tscm_stereo_refine_stages(const short *disparity, int width, int height, int disp_stride,
+                              const unsigned char *guide, int guide_stride, const unsigned char *range_weight,
+                              const tscm_stereo_refine_params *params, int device_index,
+                              int *weight_sum /* [h*w] */, unsigned char *count /* [h*w] */, short *first_pass /* [h*w] */);
+
 /* ------------------------------------------------------------------ panorama of a calibrated rig
  * What the tables of panorama_descs (one EQUIRECT or CYLINDRICAL table per camera, all in the rig frame) are for: the
  * stitched image.  A handle keeps everything that does not depend on a frame on the device -- the sample positions, the

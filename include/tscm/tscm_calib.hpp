@@ -22,6 +22,7 @@
 //   (none: the rectified pair is its last product)         stereo_match, stereo_points         -> tscm_stereo_match, tscm_stereo_points
 //   (none: cv::filterSpeckles / medianBlur downstream)     stereo_filter                       -> tscm_stereo_filter
 //   (none: hole filling is left to the caller)             stereo_fill, parse_fill_option      -> tscm_stereo_fill
+//   (none: cv::ximgproc::weightedMedianFilter downstream)  stereo_refine, range_weights, parse_refine_option -> tscm_stereo_refine
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
@@ -734,6 +735,63 @@ inline bool parse_fill_option(const char *text, tscm_stereo_fill_params *p)
         q = end + 1;
     }
     return false;
+}
+
+// range_weights: the table of tscm_stereo_refine_weights, floor(255 exp(-k / sigma) + 0.5) for k = 0..255.
+inline std::vector<unsigned char> range_weights(double sigma)
+{
+    std::vector<unsigned char> table(256);
+    tscm_stereo_refine_weights(sigma, table.data());
+    return table;
+}
+
+// stereo_refine: every pixel of a disparity or sweep index map of `size` takes the lower weighted median of the valid pixels
+// of its window, a neighbour weighted by weights[|guide(p) - guide(q)|] -> the refined map.  guide: one grey byte per pixel
+// of the map; weights: NULL (every weight 255) or 256 entries, e.g. range_weights(sigma); params == NULL:
+// tscm_stereo_refine_default_params (set min_disparity to the matcher's, wrap_x = 1 for a 360 degree map).
+inline std::vector<short> stereo_refine(const std::vector<short> &disparity, const std::vector<unsigned char> &guide, Size size,
+                                        const std::vector<unsigned char> *weights = NULL, const tscm_stereo_refine_params *params = NULL, int device = 0)
+{
+    if (disparity.size() != (size_t)size.width * size.height) throw std::runtime_error("tscm: the disparity map does not have the given size");
+    if (guide.size() != disparity.size()) throw std::runtime_error("tscm: the guide does not have the map's size");
+    if (weights && weights->size() != 256) throw std::runtime_error("tscm: the weight table does not have 256 entries");
+    tscm_stereo_refine_params p;
+    if (params) p = *params;
+    else tscm_stereo_refine_default_params(&p);
+    std::vector<short> out(disparity.size());
+    if (out.empty()) return out;
+    check(tscm_stereo_refine(disparity.data(), size.width, size.height, size.width, guide.data(), size.width, weights ? weights->data() : NULL, &p, device, out.data(),
+                             size.width, NULL));
+    return out;
+}
+
+// The demos' --refine RADIUS,SIGMA[,ITERATIONS[,FILL]] -> radius, iterations and fill_invalid of p, and sigma; false when the
+// text is none of that or a number lies outside what tscm_stereo_refine takes (radius 1..7, iterations 1..8, FILL 0 or 1).
+inline bool parse_refine_option(const char *text, tscm_stereo_refine_params *p, double *sigma)
+{
+    int field[4] = { 0, 0, p->iterations, p->fill_invalid };
+    const char *q = text;
+    int k = 0;
+    for (; k < 4; ++k) {                                        // whole numbers, nothing before, between or after them
+        char *end = NULL;
+        if (*q != '-' && *q != '.' && (*q < '0' || *q > '9')) return false;
+        if (k == 1) {
+            *sigma = std::strtod(q, &end);
+        } else {
+            const long v = std::strtol(q, &end, 10);
+            if (v < -1000 || v > 1000) return false;
+            field[k] = (int)v;
+        }
+        if (end == q) return false;
+        if (!*end) break;
+        if (*end != ',' || k == 3) return false;
+        q = end + 1;
+    }
+    if (k < 1 || field[0] < 1 || field[0] > 7 || field[2] < 1 || field[2] > 8 || (field[3] != 0 && field[3] != 1)) return false;
+    p->radius = field[0];
+    p->iterations = field[2];
+    p->fill_invalid = field[3];
+    return true;
 }
 
 // stereo_points: the disparities of stereo_match on the pair of rectify_pair_maps (left_map = desc[0], projection

@@ -139,6 +139,12 @@ class CStereoFillParams(C.Structure):
                 ("min_directions", C.c_int), ("wrap_x", C.c_int)]
 
 
+class CStereoRefineParams(C.Structure):
+    """tscm_stereo_refine_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("min_disparity", C.c_int), ("radius", C.c_int), ("iterations", C.c_int), ("fill_invalid", C.c_int),
+                ("wrap_x", C.c_int)]
+
+
 class CPanoramaParams(C.Structure):
     """tscm_panorama_params (tscm.h)"""
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int)]
@@ -181,6 +187,7 @@ EXPORTS = [
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
     "tscm_stereo_fill_default_params", "tscm_stereo_fill", "tscm_stereo_fill_stages",
+    "tscm_stereo_refine_default_params", "tscm_stereo_refine_weights", "tscm_stereo_refine", "tscm_stereo_refine_stages",
     "tscm_panorama_default_params", "tscm_panorama_create", "tscm_panorama_compose", "tscm_panorama_stages", "tscm_panorama_overlap", "tscm_panorama_destroy",
     "tscm_build_sweep_maps",
     "tscm_sweep_default_params", "tscm_sweep_create", "tscm_sweep_depth", "tscm_sweep_stages", "tscm_sweep_stage_times", "tscm_sweep_points", "tscm_sweep_destroy",
@@ -289,6 +296,14 @@ def lib():
     L.tscm_stereo_fill.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFillParams), C.c_int, C.POINTER(C.c_short), C.c_int, ubp, dp]
     L.tscm_stereo_fill_stages.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, C.POINTER(CStereoFillParams), C.c_int, C.POINTER(C.c_short),
                                           C.POINTER(C.c_short)]
+    L.tscm_stereo_refine_default_params.argtypes = [C.POINTER(CStereoRefineParams)]
+    L.tscm_stereo_refine_default_params.restype = None
+    L.tscm_stereo_refine_weights.argtypes = [C.c_double, ubp]
+    L.tscm_stereo_refine_weights.restype = None
+    L.tscm_stereo_refine.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, ubp, C.c_int, ubp, C.POINTER(CStereoRefineParams), C.c_int,
+                                     C.POINTER(C.c_short), C.c_int, dp]
+    L.tscm_stereo_refine_stages.argtypes = [C.POINTER(C.c_short), C.c_int, C.c_int, C.c_int, ubp, C.c_int, ubp, C.POINTER(CStereoRefineParams), C.c_int,
+                                            C.POINTER(C.c_int), ubp, C.POINTER(C.c_short)]
     fp, shp, llp, vpp = C.POINTER(C.c_float), C.POINTER(C.c_short), C.POINTER(C.c_longlong), C.POINTER(vp)
     L.tscm_panorama_default_params.argtypes = [C.POINTER(CPanoramaParams)]
     L.tscm_panorama_default_params.restype = None

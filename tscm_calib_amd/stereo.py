@@ -1,7 +1,8 @@
 """Stereo matching and depth on a rectified pair (tscm.h: tscm_stereo_*): census + semi-global matching on the device,
 the post-filter of a disparity map (speckle removal, masked median), hole filling from the nearest valid values along the
-path directions, the 3-D points of a disparity map, and pair_depth, the chain from two fisheye images of a calibrated rig
-to points: rectify_pair_descs -> build_maps -> remap -> match [-> filter] [-> fill] -> points."""
+path directions, the edge-aware weighted median guided by the image, the 3-D points of a disparity map, and pair_depth,
+the chain from two fisheye images of a calibrated rig to points:
+rectify_pair_descs -> build_maps -> remap -> match [-> filter] [-> fill] [-> refine] -> points."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +16,7 @@ PARAM_NAMES = ("min_disparity", "num_disparities", "p1", "p2", "paths", "uniquen
 STAGE_NAMES = ("census", "cost", "aggregate", "right_winner", "winner")
 FILTER_PARAM_NAMES = ("min_disparity", "speckle_window_size", "speckle_range", "median")
 FILL_PARAM_NAMES = ("min_disparity", "rule", "paths", "max_distance", "min_directions", "wrap_x")
+REFINE_PARAM_NAMES = ("min_disparity", "radius", "iterations", "fill_invalid", "wrap_x")
 FILL_RULES = dict(lowest=_lib.FILL_LOWEST, second_lowest=_lib.FILL_SECOND_LOWEST, median=_lib.FILL_MEDIAN)
 
 
@@ -188,6 +190,85 @@ def fill_stages(disp, device: int = 0, **over) -> dict:
     return dict(value=value, distance=distance)
 
 
+def refine_params(**over) -> _lib.CStereoRefineParams:
+    """tscm_stereo_refine_default_params with the given fields replaced."""
+    p = _lib.CStereoRefineParams()
+    _lib.lib().tscm_stereo_refine_default_params(C.byref(p))
+    for k, v in over.items():
+        if k not in REFINE_PARAM_NAMES:
+            raise TypeError(f"unknown stereo refine parameter {k!r}: one of {', '.join(REFINE_PARAM_NAMES)}")
+        setattr(p, k, int(v))
+    return p
+
+
+def range_weights(sigma: float) -> np.ndarray:
+    """tscm_stereo_refine_weights -> uint8 [256]: floor(255 exp(-k / sigma) + 0.5); 255, 0, 0, ... for a sigma that is not > 0."""
+    t = np.zeros(256, dtype=np.uint8)
+    _lib.lib().tscm_stereo_refine_weights(float(sigma), t.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    return t
+
+
+def _refine_args(disp, guide, weights, sigma):
+    """-> (disp, guide, table or None): the guide as one grey channel of the map's shape, the table from weights or sigma"""
+    disp = _disparity_map(disp)
+    g = np.asarray(guide)
+    if g.ndim == 3:
+        from .sweep import bgr_to_gray
+        g = bgr_to_gray(g)
+    g = _gray(g)
+    if g.shape != disp.shape:
+        raise ValueError("the guide does not have the map's shape")
+    if weights is not None and sigma is not None:
+        raise TypeError("weights and sigma: give one of them")
+    table = None
+    if sigma is not None:
+        table = range_weights(sigma)
+    elif weights is not None:
+        table = np.ascontiguousarray(weights)
+        if table.dtype != np.uint8 or table.shape != (256,):
+            raise ValueError("weights is a uint8 table of 256 entries")
+    return disp, g, table
+
+
+def refine(disp, guide, device: int = 0, out: np.ndarray | None = None, weights=None, sigma=None, with_seconds: bool = False, **over):
+    """tscm_stereo_refine: every pixel of a disparity (or sweep index) map takes the lower weighted median of the valid
+    pixels of its (2 radius + 1)^2 window, a neighbour weighted by weights[|guide(p) - guide(q)|] -> int16 [h, w].  guide:
+    uint8 [h, w], or BGR [h, w, 3], which goes through sweep.bgr_to_gray.  weights: a uint8 table of 256 entries; sigma:
+    short for range_weights(sigma); neither: every weight 255.  `disp` and `guide` may be row-padded views; `out` may be one
+    too (its padding keeps its values) and may be `disp` itself."""
+    disp, g, table = _refine_args(disp, guide, weights, sigma)
+    h, w = disp.shape
+    p = refine_params(**over)
+    if out is None:
+        out = np.zeros((h, w), dtype=np.int16)
+    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
+        raise ValueError("out must be an int16 array (or row-padded view) of the map's shape")
+    sp, ub = C.POINTER(C.c_short), C.POINTER(C.c_ubyte)
+    sec = C.c_double(0.0)
+    _lib.check(_lib.lib().tscm_stereo_refine(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, g.ctypes.data_as(ub), g.strides[0] if h else w,
+                                             None if table is None else table.ctypes.data_as(ub), C.byref(p), device,
+                                             out.ctypes.data_as(sp), out.strides[0] // 2 if h else w, C.byref(sec)))
+    return (out, sec.value) if with_seconds else out
+
+
+_refine = refine            # pair_depth has a keyword of that name
+
+
+def refine_stages(disp, guide, device: int = 0, weights=None, sigma=None, **over) -> dict:
+    """tscm_stereo_refine_stages -> weight_sum int32 [h, w] and count uint8 [h, w] (the summed weights and the number of the
+    participants of every pixel's window) and first_pass int16 [h, w], the map after one pass."""
+    disp, g, table = _refine_args(disp, guide, weights, sigma)
+    h, w = disp.shape
+    p = refine_params(**over)
+    res = dict(weight_sum=np.zeros((h, w), dtype=np.int32), count=np.zeros((h, w), dtype=np.uint8), first_pass=np.zeros((h, w), dtype=np.int16))
+    sp, ub = C.POINTER(C.c_short), C.POINTER(C.c_ubyte)
+    _lib.check(_lib.lib().tscm_stereo_refine_stages(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, g.ctypes.data_as(ub), g.strides[0] if h else w,
+                                                    None if table is None else table.ctypes.data_as(ub), C.byref(p), device,
+                                                    res["weight_sum"].ctypes.data_as(C.POINTER(C.c_int)), res["count"].ctypes.data_as(ub),
+                                                    res["first_pass"].ctypes.data_as(sp)))
+    return res
+
+
 def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0):
     """tscm_stereo_points: the disparity map of the left image of a PERSPECTIVE or LONGLAT pair (desc = its MapDesc) ->
     (points [h, w, 3] fp64 in the pair frame of the left camera, valid [h, w] bool); invalid points are NaN."""
@@ -205,7 +286,7 @@ def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0)
 
 
 def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat", width: int = 640, height: int = 320, fov_x: float = np.pi,
-               fov_y: float = np.pi / 2, device: int = 0, matcher=None, post=None, fill=None, **over):
+               fov_y: float = np.pi / 2, device: int = 0, matcher=None, post=None, fill=None, refine=None, **over):
     """Two grey fisheye images of cameras a and b of a calibrated rig -> (points [height, width, 3] in the pair frame of
     camera a, valid [height, width], R_pair).  R_pair = rectify_pair_rotation(t_a, t_b) turns pair-frame vectors into the
     rig frame: P_rig = R_pair @ P + t_a.  Camera a is the left image: b lies at +|t_b - t_a| on the pair frame's x-axis.
@@ -213,11 +294,14 @@ def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat",
     of filter parameters (speckle_window_size, speckle_range, median); the disparity map then passes through filter, with
     the matcher's min_disparity, before its points are taken.  None: no filter.  `fill`: a dict of fill parameters (rule,
     paths, max_distance, min_directions, wrap_x), applied after `post`, also with the matcher's min_disparity.  None: no
-    filling."""
+    filling.  `refine`: a dict of refine arguments (radius, iterations, fill_invalid, wrap_x, sigma or weights), applied after
+    `fill` with the rectified left image as the guide and the matcher's min_disparity.  None: no refinement."""
     if post is not None and "min_disparity" in post:
         raise TypeError("post: min_disparity is the matcher's")
     if fill is not None and "min_disparity" in fill:
         raise TypeError("fill: min_disparity is the matcher's")
+    if refine is not None and "min_disparity" in refine:
+        raise TypeError("refine: min_disparity is the matcher's")
     kind = _maps.projection_kind(projection)
     if kind not in (_lib.PROJ_PERSPECTIVE, _lib.PROJ_LONGLAT):
         raise ValueError("pair_depth needs rows that are epipolar lines: 'longlat' or 'perspective'")
@@ -233,6 +317,8 @@ def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat",
         disp = filter(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **post)
     if fill is not None:
         disp = _fill(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **fill)
+    if refine is not None:
+        disp = _refine(disp, rect[0], device=device, min_disparity=int(over.get("min_disparity", 0)), **refine)
     Ta, Tb = np.asarray(Twc_a, dtype=np.float64).reshape(3, 4), np.asarray(Twc_b, dtype=np.float64).reshape(3, 4)
     baseline = float(np.linalg.norm(Tb[:, 3] - Ta[:, 3]))
     pts, valid = points(disp, descs[0], baseline, min_disparity=int(over.get("min_disparity", 0)), device=device)

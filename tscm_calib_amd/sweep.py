@@ -283,14 +283,30 @@ def _check_fill(fill):
         raise TypeError("fill: min_disparity is 0 for an index map")
 
 
+def _check_refine(refine):
+    if refine is not None and "min_disparity" in refine:
+        raise TypeError("refine: min_disparity is 0 for an index map")
+
+
+def _refine_index(s, grey, idx, refine, fallback_index, device):
+    """stereo.refine of an index map (wrap_x = 1 unless the dict says otherwise), guided by the grey frame that the sweeper
+    composes in SEAM mode at that map"""
+    from . import stereo
+    guide = s.compose(grey, index16=idx, mode="seam", fallback_index=fallback_index)
+    return stereo.refine(idx, guide, device=device, min_disparity=0, **{"wrap_x": 1, **refine})
+
+
 def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: float = 500.0, far: float = np.inf, D: int = 64, weights="radial",
-              projection="equirect", device: int = 0, post=None, fill=None, **over):
+              projection="equirect", device: int = 0, post=None, fill=None, refine=None, **over):
     """One call from a calibration and a frame to (index16 [ph, pw], points [ph, pw, 3] in the rig frame, valid [ph, pw]).
     near / far in the units of Twc's translations.  post: keyword arguments of stereo.filter (speckle_window_size,
     speckle_range, median), applied to the index map before the points; an index map is a disparity map with
     min_disparity = 0.  fill: keyword arguments of stereo.fill (rule, paths, max_distance, min_directions, wrap_x; wrap_x
-    defaults to 1 here), applied after post."""
+    defaults to 1 here), applied after post.  refine: keyword arguments of stereo.refine (radius, iterations, fill_invalid,
+    wrap_x, sigma or weights; wrap_x defaults to 1 here), applied after fill; the guide is the frame composed in SEAM mode at
+    the map as it stands, pixels without depth at hypothesis 0."""
     _check_fill(fill)
+    _check_refine(refine)
     size = (np.asarray(images[0]).shape[1], np.asarray(images[0]).shape[0])
     inv = inverse_distances(near, far, D)
     with Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv, weights=weights, projection=projection, device=device, **over) as s:
@@ -301,27 +317,37 @@ def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: fl
         if fill is not None:
             from . import stereo
             idx = stereo.fill(idx, device=device, min_disparity=0, **{"wrap_x": 1, **fill})
+        if refine is not None:
+            idx = _refine_index(s, images, idx, refine, 0, device)
         pts, valid = s.points(idx)
     return idx, pts, valid
 
 
 def rig_panorama(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: float = 500.0, far: float = np.inf, D: int = 64, weights="radial",
-                 projection="equirect", device: int = 0, post=None, mode="multiband", levels: int = 4, gains=None, fallback_index: int = 0, fill=None, **over):
+                 projection="equirect", device: int = 0, post=None, mode="multiband", levels: int = 4, gains=None, fallback_index: int = 0, fill=None,
+                 refine=None, **over):
     """One call from a calibration and a frame to the parallax-free panorama: (panorama uint8 [ph, pw] or [ph, pw, 3],
     index16 [ph, pw], coverage [ph, pw]).  Colour images (BGR) go through bgr_to_gray for the depth pass and are blended in
     colour.  post: keyword arguments of stereo.filter for the index map, as in rig_depth; the filtered map is the one the
     frame is composed at and the one returned.  fill: keyword arguments of stereo.fill, as in rig_depth, applied after
-    post; the frame is then composed at the filled map.  fallback_index: the hypothesis of a pixel without depth (0 = far)."""
+    post; the frame is then composed at the filled map.  refine: keyword arguments of stereo.refine, as in rig_depth,
+    applied after fill and guided by the grey frame composed in SEAM mode at the map as it stands (pixels without depth at
+    fallback_index); the returned frame is composed at the refined map.  fallback_index: the hypothesis of a pixel without
+    depth (0 = far)."""
     _check_fill(fill)
+    _check_refine(refine)
     size = (np.asarray(images[0]).shape[1], np.asarray(images[0]).shape[0])
     inv = inverse_distances(near, far, D)
     with Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv, weights=weights, projection=projection, device=device, **over) as s:
-        idx = s.depth([bgr_to_gray(x) for x in images])
+        grey = [bgr_to_gray(x) for x in images]
+        idx = s.depth(grey)
         if post:
             from . import stereo
             idx = stereo.filter(idx, min_disparity=0, device=device, **post)
         if fill is not None:
             from . import stereo
             idx = stereo.fill(idx, device=device, min_disparity=0, **{"wrap_x": 1, **fill})
-        pano, cov = s.compose(images, index16=idx if post or fill is not None else None, gains=gains, with_coverage=True, mode=mode, levels=levels, fallback_index=fallback_index)
+        if refine is not None:
+            idx = _refine_index(s, grey, idx, refine, fallback_index, device)
+        pano, cov = s.compose(images, index16=idx if post or fill is not None or refine is not None else None, gains=gains, with_coverage=True, mode=mode, levels=levels, fallback_index=fallback_index)
     return pano, idx, cov
