@@ -34,19 +34,21 @@ def oracle_normal_equations(p: Problem) -> dict:
     return out
 
 
-def normal_equations_from(p: Problem, res, Jc, Jb, Ji, extra=None) -> dict:
+def normal_equations_from(p: Problem, res, Jc, Jb, Ji, extra=None, dtype=np.float64) -> dict:
     """oracle_normal_equations from given Jacobians (oracle order: views in problem order, corners in order), batched over
     views of equal corner count.  `extra` = (view, corner, weight) arrays: corner `corner`'s rows are added once more, times
     `weight`, to view `view`'s products (weight -1 drops a row, +1 counts it twice or adds a foreign one).  Also returns the
-    diagonals of every view's own E^T E and F^T F and r^T r per board and per camera (the scales of gram_errors)."""
+    diagonals of every view's own E^T E and F^T F and r^T r per board and per camera (the scales of gram_errors).
+    dtype: the type of the sums (np.longdouble with longdouble rows: nothing is rounded to fp64 on the way)."""
     C, B, V = p.n_cameras, p.n_boards, p.n_views
     cnt = np.asarray(p.view_count, dtype=np.int64)
     start = np.cumsum(cnt) - cnt
     vc, vb = np.asarray(p.view_camera, dtype=np.int64), np.asarray(p.view_board, dtype=np.int64)
     Jc, Jb, Ji, res = Jc.reshape(-1, 2, 6), Jb.reshape(-1, 2, 6), Ji.reshape(-1, 2, 9), res.reshape(-1, 2)
-    out = dict(board_gram=np.zeros((B, 6, 6)), board_grad=np.zeros((B, 6)), view_cross=np.zeros((V, 6, 15)),
-               cam_gram=np.zeros((C, 15, 15)), cam_grad=np.zeros((C, 15)), cost=0.5 * float(np.sum(res * res)),
-               view_ediag=np.zeros((V, 6)), view_fdiag=np.zeros((V, 15)), board_rr=np.zeros(B), cam_rr=np.zeros(C))
+    z = lambda *shape: np.zeros(shape, dtype=dtype)
+    out = dict(board_gram=z(B, 6, 6), board_grad=z(B, 6), view_cross=z(V, 6, 15),
+               cam_gram=z(C, 15, 15), cam_grad=z(C, 15), cost=0.5 * float(np.sum(res * res)),
+               view_ediag=z(V, 6), view_fdiag=z(V, 15), board_rr=z(B), cam_rr=z(C))
 
     def rows(idx):
         # idx [nv, c] corner indices -> E [nv, 2c, 6], F [nv, 2c, 15], r [nv, 2c]
@@ -97,12 +99,11 @@ def block_errors(g: dict, o: dict, mono: bool) -> dict:
     return err
 
 
-def gram_errors(g: dict, o: dict, p: Problem) -> dict:
-    """Largest entrywise error of each block of g against the reference o, in units of the Cauchy-Schwarz bound of the
-    entry: sqrt(G_ii G_jj) of the reference Gram (each view's own E^T E / F^T F for view_cross), sqrt(G_ii r^T r) for the
-    gradients.  The b, c columns (structurally zero) are not compared, and the camera-pose columns of a mono problem (no
-    such block) neither.  An entry whose bound is 0 must match exactly.  The views and boards of fewer than four corners
-    (less than one k-step) are reported apart: view_cross_short, board_gram_short, board_grad_short."""
+def gram_entry_errors(g: dict, o: dict, p: Problem) -> dict:
+    """Entrywise errors of each block of g against the reference o, in units of the Cauchy-Schwarz bound of the entry:
+    sqrt(G_ii G_jj) of the reference Gram (each view's own E^T E / F^T F for view_cross), sqrt(G_ii r^T r) for the
+    gradients.  The b, c columns (structurally zero) are left out, and the camera-pose columns of a mono problem (no
+    such block) too: `columns` lists the F columns kept.  An entry whose bound is 0 is inf unless it matches exactly."""
     keep = np.ones(15, dtype=bool)
     keep[13:] = False
     if p.mono:
@@ -114,16 +115,26 @@ def gram_errors(g: dict, o: dict, p: Problem) -> dict:
                  view_cross=np.sqrt(o["view_ediag"][:, :, None] * o["view_fdiag"][:, None, :]),
                  cam_gram=np.sqrt(cd[:, :, None] * cd[:, None, :]),
                  cam_grad=np.sqrt(cd * o["cam_rr"][:, None]))
-    board_corners = np.bincount(p.view_board, weights=p.view_count, minlength=p.n_boards)
-    short = dict(view_cross=np.asarray(p.view_count) < 4, board_gram=board_corners < 4, board_grad=board_corners < 4)
-    err = {}
+    out = dict(columns=np.nonzero(keep)[0])
     for key, s in scale.items():
         d = np.abs(np.asarray(g[key]) - o[key])
         if key == "cam_gram":
             d, s = d[:, keep][:, :, keep], s[:, keep][:, :, keep]
         elif key in ("view_cross", "cam_grad"):
             d, s = d[..., keep], s[..., keep]
-        e = np.where(s > 0, d / np.where(s > 0, s, 1.0), np.where(d > 0, np.inf, 0.0))
+        out[key] = np.asarray(np.where(s > 0, d / np.where(s > 0, s, 1.0), np.where(d > 0, np.inf, 0.0)), dtype=np.float64)
+    return out
+
+
+def gram_errors(g: dict, o: dict, p: Problem) -> dict:
+    """Largest of gram_entry_errors per block.  The views and boards of fewer than four corners (less than one k-step)
+    are reported apart: view_cross_short, board_gram_short, board_grad_short."""
+    board_corners = np.bincount(p.view_board, weights=p.view_count, minlength=p.n_boards)
+    short = dict(view_cross=np.asarray(p.view_count) < 4, board_gram=board_corners < 4, board_grad=board_corners < 4)
+    err = {}
+    for key, e in gram_entry_errors(g, o, p).items():
+        if key == "columns":
+            continue
         if key in short:
             err[key + "_short"] = float(e[short[key]].max()) if short[key].any() else 0.0
             e = e[~short[key]]
