@@ -4,13 +4,16 @@
 // Images are binary PGM (P5, grey) or PPM (P6, read as 3 channels in file order) files of one size and kind, one per camera.
 //   usage: sweep_panorama_demo calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8]
 //                              [--mode seam|feather|multiband] [--levels L] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]]
-//                              [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]]
+//                              [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]] [--visibility SHIFT,TOLERANCE[,DILATE]]
 // --fill: every pixel without depth gets the lowest | second_lowest | median of the nearest valid indices along the 8 path
 // directions, over the seam too (tscm_stereo_fill with wrap_x = 1), and the frame is composed at the filled map.
 // --refine: after that, the weighted median of every pixel's (2 RADIUS + 1)^2 window, over the seam too (tscm_stereo_refine
 // with wrap_x = 1), a neighbour weighted by exp(-|difference of grey values| / SIGMA) in the grey frame composed by seam at
 // the map as it stands, in ITERATIONS passes (1); FILL 1 gives pixels without depth a value too (0).  The frame is composed
 // at the refined map.
+// --visibility: the frame is composed under per-camera visibility (tscm_sweep_compose_visible): at every pixel a camera that
+// looks at the point through something nearer -- by more than TOLERANCE hypotheses, in a depth buffer of 2^SHIFT x 2^SHIFT
+// source pixels per cell, read over (2 DILATE + 1)^2 cells (DILATE 0) -- is left out, unless no camera would remain.
 // writes sweep_panorama.pgm or .ppm into the working directory.  near: in the units of the calibration's translations.
 #include <cstdio>
 #include <cstdlib>
@@ -44,7 +47,9 @@ int main(int argc, char **argv)
     tscm_sweep_default_params(&params);
     tscm_sweep_compose_params blend;
     tscm_sweep_compose_default_params(&blend);
-    bool bad = false, fill = false, refine = false;
+    bool bad = false, fill = false, refine = false, visible = false;
+    tscm_sweep_visibility_params vis_params;
+    tscm_sweep_visibility_default_params(&vis_params);
     tscm_stereo_fill_params fill_params;
     tscm_stereo_fill_default_params(&fill_params);
     fill_params.wrap_x = 1;
@@ -60,6 +65,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[a], "--levels") && a + 1 < argc) blend.levels = std::atoi(argv[++a]);
         else if (!std::strcmp(argv[a], "--fill") && a + 1 < argc) { fill = true; bad |= !tscm::parse_fill_option(argv[++a], &fill_params); }
         else if (!std::strcmp(argv[a], "--refine") && a + 1 < argc) { refine = true; bad |= !tscm::parse_refine_option(argv[++a], &refine_params, &sigma); }
+        else if (!std::strcmp(argv[a], "--visibility") && a + 1 < argc) { visible = true; bad |= !tscm::parse_visibility_option(argv[++a], &vis_params); }
         else if (!std::strcmp(argv[a], "--mode") && a + 1 < argc) {
             const std::string m = argv[++a];
             if (m == "seam") blend.mode = TSCM_PANO_SEAM;
@@ -69,7 +75,7 @@ int main(int argc, char **argv)
         } else files.push_back(argv[a]);
     }
     if (bad || argc < 4 || files.size() < 2 || !(near > 0.0) || params.num_hypotheses < 2) {
-        std::fprintf(stderr, "usage: %s calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--mode seam|feather|multiband] [--levels L] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]]\n",
+        std::fprintf(stderr, "usage: %s calib.yaml cam0.ppm cam1.ppm ... [--size W H] [--near N] [--hypotheses D] [--paths 4|8] [--mode seam|feather|multiband] [--levels L] [--fill RULE[,MAX_DISTANCE[,MIN_DIRECTIONS]]] [--refine RADIUS,SIGMA[,ITERATIONS[,FILL]]] [--visibility SHIFT,TOLERANCE[,DILATE]]\n",
                      argv[0]);
         return 2;
     }
@@ -115,7 +121,9 @@ int main(int argc, char **argv)
             const std::vector<unsigned char> guide = sweep.compose(gptr.data(), 1, &index16, &seam), table = tscm::range_weights(sigma);
             index16 = tscm::stereo_refine(index16, guide, pano, &table, &refine_params);
         }
-        const std::vector<unsigned char> out = sweep.compose(ptr.data(), channels, fill || refine ? &index16 : NULL, &blend, NULL, 0, NULL, &sec_compose);
+        const std::vector<short> *at = fill || refine ? &index16 : NULL;     // NULL: the map the depth pass left on the device
+        const std::vector<unsigned char> out = visible ? sweep.compose(ptr.data(), channels, at, &blend, vis_params, NULL, 0, NULL, &sec_compose)
+                                                       : sweep.compose(ptr.data(), channels, at, &blend, NULL, 0, NULL, &sec_compose);
         size_t n_valid = 0;
         for (size_t t = 0; t < index16.size(); ++t) n_valid += index16[t] >= 0;
         const char *name = channels == 1 ? "sweep_panorama.pgm" : "sweep_panorama.ppm";

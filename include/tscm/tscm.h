@@ -1141,6 +1141,70 @@ int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *const *images,
                               unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid,
                               short *blend_pyramid);
 
+/* Per-camera visibility at the swept depth.  tscm_sweep_compose samples every camera whose record has alpha > 0 at the
+ * hypothesis of a pixel, whether or not that camera sees the point: a camera off the rig centre that looks at a background
+ * point through a nearer object contributes the object's texture.  The handle's records hold the integer camera position
+ * (ix, iy) and the alpha a of every (camera, hypothesis, panorama pixel), and the index map lies on the same grid, so
+ * visibility is a depth buffer per camera over cells of its image, in ranks of the hypothesis.  Integers throughout, restated
+ * in tests/sweep_visibility_ref.py.  rec(k, z, p): the record of camera k, hypothesis z, panorama pixel p; s = cell_shift.
+ *   hypothesis   p is tested iff index16(p) >= 0; then z(p) = min(D - 1, (index16(p) + 8) >> 4), the composer's rule, and the
+ *                rank q(p) = near_is_high ? z(p) : D - 1 - z(p): a larger rank is nearer.  An untested pixel neither
+ *                occludes nor is occluded.
+ *   cell         camera k's grid has cw = ((width - 1) >> s) + 1 by ch = ((height - 1) >> s) + 1 cells; the cell of a
+ *                record is (clamp(ix, 0, width - 1) >> s, clamp(iy, 0, height - 1) >> s).
+ *   depth buffer zbuf[k][cy][cx] = the maximum of q(p) + 1 over the tested p with rec(k, z(p), p).a > 0 whose cell is
+ *                (cx, cy), 0 for an empty cell: a maximum, so no order enters.
+ *   test         for a tested p and a camera with a_k = rec(k, z(p), p).a > 0: m = the maximum of zbuf[k] over the cells
+ *                (cx + dx, cy + dy) inside the grid with |dx|, |dy| <= dilate; visible_k(p) = (m <= q(p) + 1 + tolerance).
+ *                a_k == 0 gives visible_k = 0.
+ *   state, use   state 0: p is not tested, use_k = 1 for every k; 1: tested and no camera has a_k > 0, use_k = 0; 2: every
+ *                camera with a_k > 0 is visible, use_k = (a_k > 0); 3: some of them are occluded and some visible,
+ *                use_k = visible_k; 4: all of them are occluded, use_k = (a_k > 0) -- the guard: a pixel never loses its
+ *                last source.
+ *   composer     tscm_sweep_compose_visible is tscm_sweep_compose with a_k(i, j) replaced by use_k(i, j) ? a_k(i, j) : 0
+ *                before label, coverage, SEAM, FEATHER and the MULTIBAND masks (the alpha stage output is the replaced one);
+ *                pixels without depth use the record at fallback_index as before, with use_k = 1.
+ * So tolerance = 255 gives the states 0, 1, 2 only and the bytes of tscm_sweep_compose, as does a constant valid map, and
+ * with dilate = 0 the nearest tested pixel of a cell is visible in that camera.
+ * Outputs, any of them NULL: use [n][pano_h][pano_w] uint8 0 / 1, state [pano_h][pano_w] uint8; stages: hypothesis
+ * [pano_h][pano_w] uint8 (0 where not tested), depth_buffer [n][ch][cw] uint16, cell [n][pano_h][pano_w] int32 =
+ * cy * cw + cx (-1 where a == 0 or p is not tested), visible [n][pano_h][pano_w] uint8.  index16 == NULL: the map of the
+ * handle's last tscm_sweep_depth, as for the composer.  The buffers of the pass are allocated by its first call on a handle.
+ * Refused with TSCM_E_INVALID, the text naming the argument, a NULL handle before any device is touched: what
+ * tscm_sweep_compose refuses (the composing calls), a NULL vparams or a wrong struct_size, cell_shift outside 0..8, tolerance
+ * outside 0..255, dilate outside 0..2, near_is_high other than 0 or 1, index_stride < pano_w, a NULL index16 on a handle that
+ * has not run tscm_sweep_depth. */
+typedef struct tscm_sweep_visibility_params {
+    int struct_size;   /* sizeof(tscm_sweep_visibility_params)                                     */
+    int cell_shift;    /* 0..8: a depth-buffer cell is 2^cell_shift x 2^cell_shift source pixels   */
+    int tolerance;     /* 0..255 hypotheses: an occluder must be nearer by more than this          */
+    int dilate;        /* 0..2: the test reads the (2 dilate + 1)^2 cells around the pixel's cell  */
+    int near_is_high;  /* 1: index D - 1 is the nearest; 0: index 0 is                             */
+} tscm_sweep_visibility_params;
+void tscm_sweep_visibility_default_params(tscm_sweep_visibility_params *p);   /* 2, 2, 0, 1 */
+
+int tscm_sweep_visibility(tscm_sweep *s, const short *index16 /* [pano_h][index_stride], or NULL */, int index_stride,
+                          const tscm_sweep_visibility_params *vparams, unsigned char *use, unsigned char *state,
+                          double *seconds_kernel);
+
+int tscm_sweep_visibility_stages(tscm_sweep *s, const short *index16, int index_stride,
+                                 const tscm_sweep_visibility_params *vparams, unsigned char *hypothesis,
+                                 unsigned short *depth_buffer, int *cell, unsigned char *visible, unsigned char *use,
+                                 unsigned char *state);
+
+int tscm_sweep_compose_visible(tscm_sweep *s, const unsigned char *const *images, int stride, int channels,
+                               const short *index16, int index_stride, const tscm_sweep_compose_params *params,
+                               const tscm_sweep_visibility_params *vparams, const unsigned short *gain_q8,
+                               unsigned char *dst, int dst_stride, unsigned char *coverage, double *seconds_kernel);
+
+/* The stages of tscm_sweep_compose_stages under visibility, and use and state. */
+int tscm_sweep_compose_visible_stages(tscm_sweep *s, const unsigned char *const *images, int stride, int channels,
+                                      const short *index16, int index_stride, const tscm_sweep_compose_params *params,
+                                      const tscm_sweep_visibility_params *vparams, const unsigned short *gain_q8,
+                                      unsigned char *hypothesis, unsigned char *sampled, unsigned char *alpha,
+                                      unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid,
+                                      short *blend_pyramid, unsigned char *use, unsigned char *state);
+
 void tscm_sweep_destroy(tscm_sweep *s);
 
 #ifdef __cplusplus

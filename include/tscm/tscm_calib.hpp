@@ -23,6 +23,7 @@
 //   (none: cv::filterSpeckles / medianBlur downstream)     stereo_filter                       -> tscm_stereo_filter
 //   (none: hole filling is left to the caller)             stereo_fill, parse_fill_option      -> tscm_stereo_fill
 //   (none: cv::ximgproc::weightedMedianFilter downstream)  stereo_refine, range_weights, parse_refine_option -> tscm_stereo_refine
+//   (none: occlusion is not handled)                       Sweep::visibility, parse_visibility_option -> tscm_sweep_visibility
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
@@ -794,6 +795,30 @@ inline bool parse_refine_option(const char *text, tscm_stereo_refine_params *p, 
     return true;
 }
 
+// The sweep demo's --visibility SHIFT,TOLERANCE[,DILATE] -> cell_shift, tolerance and dilate of p; false when the text is none
+// of that or a number lies outside what tscm_sweep_visibility takes (SHIFT 0..8, TOLERANCE 0..255, DILATE 0..2).
+inline bool parse_visibility_option(const char *text, tscm_sweep_visibility_params *p)
+{
+    int field[3] = { 0, 0, p->dilate };
+    const char *q = text;
+    int k = 0;
+    for (; k < 3; ++k) {                                        // whole numbers, nothing before, between or after them
+        char *end = NULL;
+        if (*q != '-' && (*q < '0' || *q > '9')) return false;
+        const long v = std::strtol(q, &end, 10);
+        if (end == q || v < -1000 || v > 1000) return false;
+        field[k] = (int)v;
+        if (!*end) break;
+        if (*end != ',' || k == 2) return false;
+        q = end + 1;
+    }
+    if (k < 1 || field[0] < 0 || field[0] > 8 || field[1] < 0 || field[1] > 255 || field[2] < 0 || field[2] > 2) return false;
+    p->cell_shift = field[0];
+    p->tolerance = field[1];
+    p->dilate = field[2];
+    return true;
+}
+
 // stereo_points: the disparities of stereo_match on the pair of rectify_pair_maps (left_map = desc[0], projection
 // TSCM_PROJ_PERSPECTIVE or TSCM_PROJ_LONGLAT, baseline = |t_b - t_a|) -> points in the pair frame of camera a
 // (P_rig = rectify_pair_rotation(t_a, t_b) * P + t_a); points of invalid pixels are NaN, valid[k] = 0.
@@ -1000,6 +1025,38 @@ public:
         check(tscm_sweep_compose(handle_, images, stride ? stride : image_.width * channels, channels, index16 ? index16->data() : NULL, pano_.width, &p, gain_q8,
                                  out.data(), row, coverage ? coverage->data() : NULL, seconds_kernel));
         return out;
+    }
+    // compose under per-camera visibility (tscm_sweep_compose_visible): a camera that looks at a pixel's point through
+    // something nearer is left out of that pixel.  visibility: as for visibility() below, not NULL
+    std::vector<unsigned char> compose(const unsigned char *const *images, int channels, const std::vector<short> *index16, const tscm_sweep_compose_params *params,
+                                       const tscm_sweep_visibility_params &visibility, const unsigned short *gain_q8 = NULL, int stride = 0,
+                                       std::vector<unsigned char> *coverage = NULL, double *seconds_kernel = NULL)
+    {
+        if (index16 && index16->size() != (size_t)pano_.width * pano_.height) throw std::runtime_error("tscm: the index map does not have the panorama's size");
+        tscm_sweep_compose_params p;
+        if (params) p = *params;
+        else tscm_sweep_compose_default_params(&p);
+        const int row = pano_.width * channels;
+        std::vector<unsigned char> out((size_t)(row > 0 ? row : 0) * pano_.height);
+        if (coverage) coverage->assign((size_t)pano_.width * pano_.height, 0);
+        check(tscm_sweep_compose_visible(handle_, images, stride ? stride : image_.width * channels, channels, index16 ? index16->data() : NULL, pano_.width, &p,
+                                         &visibility, gain_q8, out.data(), row, coverage ? coverage->data() : NULL, seconds_kernel));
+        return out;
+    }
+    // Which cameras the composer takes at every pixel (tscm_sweep_visibility): use[k * pixels + p] = 1 or 0, cameras() planes of
+    // the panorama's size; state (may be NULL): 0 no depth, 1 seen by nobody, 2 all visible, 3 some occluded, 4 all occluded
+    // and all kept.  index16: NULL for the map the last depth() left on the device; params == NULL: the defaults
+    std::vector<unsigned char> visibility(const std::vector<short> *index16 = NULL, const tscm_sweep_visibility_params *params = NULL,
+                                          std::vector<unsigned char> *state = NULL, double *seconds_kernel = NULL)
+    {
+        if (index16 && index16->size() != (size_t)pano_.width * pano_.height) throw std::runtime_error("tscm: the index map does not have the panorama's size");
+        tscm_sweep_visibility_params p;
+        if (params) p = *params;
+        else tscm_sweep_visibility_default_params(&p);
+        std::vector<unsigned char> use((size_t)n_ * pano_.width * pano_.height);
+        if (state) state->assign((size_t)pano_.width * pano_.height, 0);
+        check(tscm_sweep_visibility(handle_, index16 ? index16->data() : NULL, pano_.width, &p, use.data(), state ? state->data() : NULL, seconds_kernel));
+        return use;
     }
     // the points of an index map of depth() in the rig frame; NaN and valid[k] = 0 where invalid or at infinity
     std::vector<Point3d> points(const std::vector<short> &index16, std::vector<unsigned char> &valid) const;

@@ -24,6 +24,14 @@
 //                    (ballot)
 //   k_sweep_gather   MULTIBAND: G^0 of every camera and channel as int16 planes, label, coverage and level 0 of the masks
 //   then k_pano_reduce on the images and the masks, k_pano_wsum, k_pano_lapblend, k_pano_collapse (tscm_pano_kernels.h)
+// Per-camera visibility at the swept depth (tscm_sweep_visibility, tscm_sweep_compose_visible): a depth buffer of every camera
+// over cells of its image, in ranks of the hypothesis, and the test of every (pixel, camera) against it:
+//   hipMemsetAsync   zbuf [n][ch][cw] uint32 = 0
+//   k_sweep_splat    the composer's quads; every tested pixel raises the cell of its record in every camera that sees it to
+//                    rank + 1 with a no-return atomic max (order-independent)
+//   k_sweep_vis_test the composer's quads; per pixel the n-bit masks seen / visible, then state and use: 4 use bytes per quad
+//                    and camera and 4 state bytes per quad in one 32-bit store each
+//   k_sweep_compose / k_sweep_gather with VIS = true read the 4 use bytes of a quad and camera and zero the alpha
 #include "tscm/tscm.h"
 
 #include <hip/hip_runtime.h>
@@ -289,11 +297,15 @@ __device__ __forceinline__ void quad_records(const short *__restrict__ index16, 
     }
 }
 
+// the 4 use bytes of a quad and camera; planes of `use` are padded to whole quads
+__device__ __forceinline__ unsigned quad_use(const unsigned char *__restrict__ use, size_t first) { return *reinterpret_cast<const unsigned *>(use + first); }
+
 // grid ceil(npix / 1024) x 256: quad q = output pixels [4q, 4q + 4) of the flat panorama
-template <int CH, int MODE>
+// VIS: use [n][plane] (tscm.h, visibility: state and use) zeroes the alpha of the cameras a pixel does not use
+template <int CH, int MODE, bool VIS>
 __global__ __launch_bounds__(256) void k_sweep_compose(const uint2 *__restrict__ pack, const short *__restrict__ index16, const unsigned char *__restrict__ img, int n,
                                                        int w, int h, int D, int fallback, size_t npix, Gains gains, unsigned char *__restrict__ out,
-                                                       unsigned char *__restrict__ cover)
+                                                       unsigned char *__restrict__ cover, const unsigned char *__restrict__ use, size_t plane)
 {
     const size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (t0 >= npix) return;
@@ -317,11 +329,12 @@ __global__ __launch_bounds__(256) void k_sweep_compose(const uint2 *__restrict__
         for (int e = 0; e < 4; ++e) rec[e] = make_uint2(0, 0);
         for (int k = 0; k < n; ++k) {
             const int gk = gains.g[k];
+            const unsigned used = VIS ? quad_use(use, k * plane + t0) : 0u;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (e >= nv) continue;
                 const uint2 r = pack[k * cam + at[e]];
-                const int a = (int)(r.y >> 16);
+                const int a = VIS && !((used >> (8 * e)) & 0xffu) ? 0 : (int)(r.y >> 16);
                 if (a > 0) ++cnt[e];
                 if (a > best[e]) { best[e] = a; rec[e] = r; lab[e] = k; g[e] = gk; }
             }
@@ -343,9 +356,11 @@ __global__ __launch_bounds__(256) void k_sweep_compose(const uint2 *__restrict__
         for (int k = 0; k < n; ++k) {
             uint2 r[4];
             int any = 0;
+            const unsigned used = VIS ? quad_use(use, k * plane + t0) : 0u;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 r[e] = e < nv ? pack[k * cam + at[e]] : make_uint2(0, 0);
+                if (VIS && !((used >> (8 * e)) & 0xffu)) r[e].y &= 0xffffu;
                 any |= (int)(r[e].y >> 16);
             }
             if (__ballot(any != 0) == 0) continue;               // no lane of the wave sees camera k: its gathers are skipped
@@ -374,11 +389,12 @@ __global__ __launch_bounds__(256) void k_sweep_compose(const uint2 *__restrict__
 
 // same grid and ownership.  G^0 of every camera at planes (k * CH + c) * Sp, label, cover and (mpyr != NULL) level 0 of the
 // masks; hypothesis [npix], sampled [n][npix][CH], alpha [n][npix]: the stage outputs, any of them NULL.
-template <int CH>
+template <int CH, bool VIS>
 __global__ __launch_bounds__(256) void k_sweep_gather(const uint2 *__restrict__ pack, const short *__restrict__ index16, const unsigned char *__restrict__ img, int n,
                                                       int w, int h, int D, int fallback, size_t npix, Gains gains, short *__restrict__ G, size_t Sp,
                                                       unsigned char *__restrict__ label, unsigned char *__restrict__ cover, unsigned char *__restrict__ mpyr,
-                                                      unsigned char *__restrict__ hypothesis, unsigned char *__restrict__ sampled, unsigned char *__restrict__ alpha)
+                                                      unsigned char *__restrict__ hypothesis, unsigned char *__restrict__ sampled, unsigned char *__restrict__ alpha,
+                                                      const unsigned char *__restrict__ use, size_t plane)
 {
     const size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (t0 >= npix) return;
@@ -390,6 +406,7 @@ __global__ __launch_bounds__(256) void k_sweep_gather(const uint2 *__restrict__ 
     int best[4] = { 0, 0, 0, 0 }, lab[4][1] = { { 255 }, { 255 }, { 255 }, { 255 } }, cnt[4][1] = { { 0 }, { 0 }, { 0 }, { 0 } };
     for (int k = 0; k < n; ++k) {
         const int g = gains.g[k];
+        const unsigned used = VIS ? quad_use(use, k * plane + t0) : 0u;
         int v[4][CH];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -397,7 +414,7 @@ __global__ __launch_bounds__(256) void k_sweep_gather(const uint2 *__restrict__ 
             for (int c = 0; c < CH; ++c) v[e][c] = 0;
             if (e >= nv) continue;
             const uint2 r = pack[k * cam + at[e]];
-            const int a = (int)(r.y >> 16);
+            const int a = VIS && !((used >> (8 * e)) & 0xffu) ? 0 : (int)(r.y >> 16);
             sample_px<CH>(img + k * img_bytes, w, h, r, v[e]);
 #pragma unroll
             for (int c = 0; c < CH; ++c) v[e][c] = apply_gain(v[e][c], g);
@@ -427,6 +444,100 @@ __global__ __launch_bounds__(256) void k_sweep_gather(const uint2 *__restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ visibility
+// the depth-buffer cell of a record (tscm.h, visibility: cell): always inside the cw x ch grid
+__device__ __forceinline__ void record_cell(const uint2 r, int w, int h, int shift, int &cx, int &cy)
+{
+    const int ix = (short)(r.x & 0xffffu), iy = (int)r.x >> 16;
+    cx = min(max(ix, 0), w - 1) >> shift;
+    cy = min(max(iy, 0), h - 1) >> shift;
+}
+
+// Same grid and ownership as k_sweep_compose.  zbuf [n][cells], cells = cw * ch, cleared before: the maximum of rank + 1 over
+// the tested pixels that a camera sees in a cell.  An untested pixel has z = -1 here (the fallback of quad_records).
+__global__ __launch_bounds__(256) void k_sweep_splat(const uint2 *__restrict__ pack, const short *__restrict__ index16, int n, int w, int h, int D, size_t npix, int shift,
+                                                     int cw, size_t cells, int near_is_high, unsigned *__restrict__ zbuf)
+{
+    const size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (t0 >= npix) return;
+    const int nv = (int)min((size_t)4, npix - t0);
+    const size_t cam = (size_t)D * npix;
+    int z[4];
+    size_t at[4];
+    quad_records(index16, t0, nv, D, -1, npix, z, at);
+#pragma unroll 1
+    for (int k = 0; k < n; ++k) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (z[e] < 0) continue;
+            const uint2 r = pack[k * cam + at[e]];
+            if ((r.y >> 16) == 0) continue;
+            int cx, cy;
+            record_cell(r, w, h, shift, cx, cy);
+            const unsigned rank1 = (unsigned)(near_is_high ? z[e] : D - 1 - z[e]) + 1u;
+            // relaxed, agent scope, the result unused: one vector atomic without return
+            (void)__hip_atomic_fetch_max(zbuf + k * cells + (size_t)cy * cw + cx, rank1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// Same grid and ownership.  use [n][plane] and state [plane], plane = npix rounded up to 4 (the bytes behind npix are written
+// too); hypothesis [npix], cell [n][npix], visible [n][npix]: the stage outputs, any of them NULL.
+__global__ __launch_bounds__(256) void k_sweep_vis_test(const uint2 *__restrict__ pack, const short *__restrict__ index16, int n, int w, int h, int D, size_t npix,
+                                                        size_t plane, int shift, int cw, int ch, int tolerance, int dilate, int near_is_high,
+                                                        const unsigned *__restrict__ zbuf, unsigned char *__restrict__ use, unsigned char *__restrict__ state,
+                                                        unsigned char *__restrict__ hypothesis, int *__restrict__ cell, unsigned char *__restrict__ visible)
+{
+    const size_t t0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (t0 >= npix) return;
+    const int nv = (int)min((size_t)4, npix - t0);
+    const size_t cam = (size_t)D * npix, cells = (size_t)cw * ch;
+    int z[4];
+    size_t at[4];
+    quad_records(index16, t0, nv, D, -1, npix, z, at);
+    unsigned seen[4] = { 0, 0, 0, 0 }, vis[4] = { 0, 0, 0, 0 };                 // bit k: a_k > 0, visible_k
+#pragma unroll 1
+    for (int k = 0; k < n; ++k) {
+        const unsigned *zk = zbuf + k * cells;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int c = -1, ok = 0;
+            if (z[e] >= 0) {
+                const uint2 r = pack[k * cam + at[e]];
+                if ((r.y >> 16) != 0) {
+                    int cx, cy;
+                    record_cell(r, w, h, shift, cx, cy);
+                    c = cy * cw + cx;
+                    unsigned m = 0;
+                    for (int yy = max(cy - dilate, 0); yy <= min(cy + dilate, ch - 1); ++yy)
+                        for (int xx = max(cx - dilate, 0); xx <= min(cx + dilate, cw - 1); ++xx) m = max(m, zk[(size_t)yy * cw + xx]);
+                    const unsigned rank1 = (unsigned)(near_is_high ? z[e] : D - 1 - z[e]) + 1u;
+                    ok = m <= rank1 + (unsigned)tolerance;
+                    seen[e] |= 1u << k;
+                    vis[e] |= (unsigned)ok << k;
+                }
+            }
+            if (cell && e < nv) cell[k * npix + t0 + e] = c;
+            if (visible && e < nv) visible[k * npix + t0 + e] = (unsigned char)ok;
+        }
+    }
+    unsigned st = 0, used[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        // 0 untested, 1 nobody sees it, 2 all visible, 3 some occluded, 4 all occluded: the guard keeps every source
+        const unsigned s = z[e] < 0 ? 0u : seen[e] == 0 ? 1u : vis[e] == seen[e] ? 2u : vis[e] == 0 ? 4u : 3u;
+        used[e] = s == 0 ? 0xffu : s == 3 ? vis[e] : seen[e];
+        st |= s << (8 * e);
+    }
+    *reinterpret_cast<unsigned *>(state + t0) = st;
+    for (int k = 0; k < n; ++k)
+        *reinterpret_cast<unsigned *>(use + k * plane + t0) = ((used[0] >> k) & 1u) | (((used[1] >> k) & 1u) << 8) | (((used[2] >> k) & 1u) << 16) | (((used[3] >> k) & 1u) << 24);
+    if (hypothesis) {
+        const int zz[4][1] = { { max(z[0], 0) }, { max(z[1], 0) }, { max(z[2], 0) }, { max(z[3], 0) } };
+        store_quad<1>(hypothesis, t0, nv, zz);
+    }
+}
+
 thread_local double g_stage_seconds[3];
 
 }  // namespace
@@ -447,6 +558,11 @@ struct tscm_sweep : PyramidLayout {         // the base: the levels of the compo
     unsigned char *c_img = nullptr, *c_out = nullptr, *c_label = nullptr, *c_cover = nullptr, *c_mpyr = nullptr;
     unsigned short *c_wsum = nullptr;
     short *c_G = nullptr, *c_B = nullptr, *c_index = nullptr;
+    // the buffers of the visibility pass, allocated by its first call: the depth buffers for cell_shift = 0 (the largest grid)
+    unsigned *v_zbuf = nullptr;
+    unsigned char *v_use = nullptr, *v_state = nullptr;
+    short *v_index = nullptr;
+    size_t v_plane = 0;                     // npix rounded up to 4
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
     ~tscm_sweep() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
 };
@@ -703,12 +819,28 @@ int compose_buffers(tscm_sweep *s, int ch, int mode, int L)
     return 0;
 }
 
+// use: NULL, or the use planes of the visibility pass
 template <int CH>
 void launch_gather(const tscm_sweep *s, const short *idx, int fallback, const Gains &g, short *G, size_t stride, unsigned char *mpyr, unsigned char *d_hyp,
-                   unsigned char *d_sampled, unsigned char *d_alpha)
+                   unsigned char *d_sampled, unsigned char *d_alpha, const unsigned char *use)
 {
-    hipLaunchKernelGGL(k_sweep_gather<CH>, dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback, s->npix, g, G, stride,
-                       s->c_label, s->c_cover, mpyr, d_hyp, d_sampled, d_alpha);
+    if (use)
+        hipLaunchKernelGGL((k_sweep_gather<CH, true>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback, s->npix, g, G,
+                           stride, s->c_label, s->c_cover, mpyr, d_hyp, d_sampled, d_alpha, use, s->v_plane);
+    else
+        hipLaunchKernelGGL((k_sweep_gather<CH, false>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback, s->npix, g, G,
+                           stride, s->c_label, s->c_cover, mpyr, d_hyp, d_sampled, d_alpha, nullptr, (size_t)0);
+}
+
+template <int CH, int MODE>
+void launch_direct(const tscm_sweep *s, const short *idx, int fallback, const Gains &g, const unsigned char *use)
+{
+    if (use)
+        hipLaunchKernelGGL((k_sweep_compose<CH, MODE, true>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback, s->npix, g,
+                           s->c_out, s->c_cover, use, s->v_plane);
+    else
+        hipLaunchKernelGGL((k_sweep_compose<CH, MODE, false>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback, s->npix, g,
+                           s->c_out, s->c_cover, nullptr, (size_t)0);
 }
 
 // MULTIBAND behind the gather, up to B^l (collapse == false) or to the output bytes: the mask pyramids and their sums are
@@ -723,17 +855,13 @@ void launch_pyramids(const tscm_sweep *s, int wrap, short *lap, bool collapse)
 }
 
 template <int CH>
-void launch_compose(const tscm_sweep *s, const short *idx, int fallback, int wrap, const Gains &g)
+void launch_compose(const tscm_sweep *s, const short *idx, int fallback, int wrap, const Gains &g, const unsigned char *use)
 {
     if (s->c_mode == TSCM_PANO_MULTIBAND) {
-        launch_gather<CH>(s, idx, fallback, g, s->c_G, s->Sp, s->c_mpyr, nullptr, nullptr, nullptr);
+        launch_gather<CH>(s, idx, fallback, g, s->c_G, s->Sp, s->c_mpyr, nullptr, nullptr, nullptr, use);
         launch_pyramids<CH>(s, wrap, nullptr, true);
-    } else if (s->c_mode == TSCM_PANO_SEAM)
-        hipLaunchKernelGGL((k_sweep_compose<CH, TSCM_PANO_SEAM>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback,
-                           s->npix, g, s->c_out, s->c_cover);
-    else
-        hipLaunchKernelGGL((k_sweep_compose<CH, TSCM_PANO_FEATHER>), dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->c_img, s->n, s->w, s->h, s->D, fallback,
-                           s->npix, g, s->c_out, s->c_cover);
+    } else if (s->c_mode == TSCM_PANO_SEAM) launch_direct<CH, TSCM_PANO_SEAM>(s, idx, fallback, g, use);
+    else launch_direct<CH, TSCM_PANO_FEATHER>(s, idx, fallback, g, use);
 }
 
 // buffers, the colour images and the index map (the caller's, or the one tscm_sweep_depth left) on the device
@@ -753,6 +881,137 @@ int upload_compose(tscm_sweep *s, const unsigned char *const *images, int stride
     return 0;
 }
 
+// ---- visibility
+struct VisibilityStages {
+    unsigned char *hypothesis;
+    unsigned short *depth_buffer;
+    int *cell;
+    unsigned char *visible;
+};
+
+int check_visibility(const tscm_sweep_visibility_params *p)
+{
+    if (!p) return tscm_set_error(TSCM_E_INVALID, "vparams is NULL");
+    if (p->struct_size != (int)sizeof(tscm_sweep_visibility_params))
+        return tscm_set_error(TSCM_E_INVALID, "vparams: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_sweep_visibility_params) = " + std::to_string(sizeof(tscm_sweep_visibility_params)));
+    if (p->cell_shift < 0 || p->cell_shift > 8) return tscm_set_error(TSCM_E_INVALID, "vparams: cell_shift " + std::to_string(p->cell_shift) + " outside 0..8");
+    if (p->tolerance < 0 || p->tolerance > 255) return tscm_set_error(TSCM_E_INVALID, "vparams: tolerance " + std::to_string(p->tolerance) + " outside 0..255");
+    if (p->dilate < 0 || p->dilate > 2) return tscm_set_error(TSCM_E_INVALID, "vparams: dilate " + std::to_string(p->dilate) + " outside 0..2");
+    if (p->near_is_high != 0 && p->near_is_high != 1) return tscm_set_error(TSCM_E_INVALID, "vparams: near_is_high " + std::to_string(p->near_is_high) + " is not 0 or 1");
+    return 0;
+}
+
+int visibility_buffers(tscm_sweep *s)
+{
+    if (s->v_zbuf) return 0;
+    s->v_plane = (s->npix + 3) & ~(size_t)3;
+    HIP_TRY(s->mem.alloc(&s->v_use, (size_t)s->n * s->v_plane));
+    HIP_TRY(s->mem.alloc(&s->v_state, s->v_plane));
+    HIP_TRY(s->mem.alloc(&s->v_index, s->v_plane));
+    HIP_TRY(s->mem.alloc(&s->v_zbuf, (size_t)s->n * s->w * s->h));
+    return 0;
+}
+
+// clear, splat and test on the index map `idx` on the device, into v_use and v_state; st (may be NULL): device pointers of
+// the stage outputs.  The caller synchronises.
+int launch_visibility(const tscm_sweep *s, const short *idx, const tscm_sweep_visibility_params *p, const VisibilityStages *st)
+{
+    const int cw = ((s->w - 1) >> p->cell_shift) + 1, ch = ((s->h - 1) >> p->cell_shift) + 1;
+    const size_t cells = (size_t)cw * ch;
+    HIP_TRY(hipMemsetAsync(s->v_zbuf, 0, (size_t)s->n * cells * sizeof(unsigned), 0));
+    hipLaunchKernelGGL(k_sweep_splat, dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->n, s->w, s->h, s->D, s->npix, p->cell_shift, cw, cells, p->near_is_high,
+                       s->v_zbuf);
+    hipLaunchKernelGGL(k_sweep_vis_test, dim3(quad_blocks(s->npix)), dim3(256), 0, 0, s->pack, idx, s->n, s->w, s->h, s->D, s->npix, s->v_plane, p->cell_shift, cw, ch,
+                       p->tolerance, p->dilate, p->near_is_high, s->v_zbuf, s->v_use, s->v_state, st ? st->hypothesis : nullptr, st ? st->cell : nullptr,
+                       st ? st->visible : nullptr);
+    return 0;
+}
+
+// use [n][npix] and state [npix] of the last launch_visibility, either may be NULL
+int download_use_state(const tscm_sweep *s, unsigned char *use, unsigned char *state)
+{
+    if (use) HIP_TRY(hipMemcpy2D(use, s->npix, s->v_use, s->v_plane, s->npix, (size_t)s->n, hipMemcpyDeviceToHost));
+    if (state) HIP_TRY(hipMemcpy(state, s->v_state, s->npix, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int visibility_call(tscm_sweep *s, const short *index16, int index_stride, const tscm_sweep_visibility_params *p, const VisibilityStages *host, unsigned char *use,
+                    unsigned char *state, double *seconds_kernel)
+{
+    if (!s) return tscm_set_error(TSCM_E_INVALID, "s is NULL");
+    if (int rc = check_visibility(p)) return rc;
+    if (!index16 && !s->has_index) return tscm_set_error(TSCM_E_INVALID, "index16 is NULL and the handle has not run tscm_sweep_depth yet");
+    if (index16 && index_stride < s->pw) return tscm_set_error(TSCM_E_INVALID, "index_stride " + std::to_string(index_stride) + " < pano_w " + std::to_string(s->pw));
+    if (seconds_kernel) *seconds_kernel = 0.0;
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = visibility_buffers(s)) return rc;
+    const short *idx = s->index16;
+    if (index16) {
+        HIP_TRY(hipMemcpy2D(s->v_index, (size_t)s->pw * sizeof(short), index16, (size_t)index_stride * sizeof(short), (size_t)s->pw * sizeof(short), (size_t)s->ph,
+                            hipMemcpyHostToDevice));
+        idx = s->v_index;
+    }
+    const size_t nplane = (size_t)s->n * s->npix;
+    DeviceMem tmp;
+    VisibilityStages dev = { nullptr, nullptr, nullptr, nullptr };
+    if (host && host->hypothesis) HIP_TRY(tmp.alloc(&dev.hypothesis, s->v_plane));
+    if (host && host->cell) HIP_TRY(tmp.alloc(&dev.cell, nplane));
+    if (host && host->visible) HIP_TRY(tmp.alloc(&dev.visible, nplane));
+    HIP_TRY(hipEventRecord(s->ev[0], 0));
+    if (int rc = launch_visibility(s, idx, p, host ? &dev : nullptr)) return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], 0));
+    HIP_TRY(hipEventSynchronize(s->ev[1]));
+    HIP_TRY(hipGetLastError());
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    if (int rc = download_use_state(s, use, state)) return rc;
+    if (host && host->hypothesis) HIP_TRY(hipMemcpy(host->hypothesis, dev.hypothesis, s->npix, hipMemcpyDeviceToHost));
+    if (host && host->cell) HIP_TRY(hipMemcpy(host->cell, dev.cell, nplane * sizeof(int), hipMemcpyDeviceToHost));
+    if (host && host->visible) HIP_TRY(hipMemcpy(host->visible, dev.visible, nplane, hipMemcpyDeviceToHost));
+    if (host && host->depth_buffer) {                         // rank + 1 <= 256: the 32-bit cells of the atomics as uint16
+        const size_t cells = (size_t)s->n * (((s->w - 1) >> p->cell_shift) + 1) * (((s->h - 1) >> p->cell_shift) + 1);
+        std::vector<unsigned> z(cells);
+        HIP_TRY(hipMemcpy(z.data(), s->v_zbuf, cells * sizeof(unsigned), hipMemcpyDeviceToHost));
+        for (size_t t = 0; t < cells; ++t) host->depth_buffer[t] = (unsigned short)z[t];
+    }
+    return 0;
+}
+
+// tscm_sweep_compose (visible == false) and tscm_sweep_compose_visible
+int compose_call(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                 const tscm_sweep_compose_params *params, const tscm_sweep_visibility_params *vp, bool visible, const unsigned short *gain_q8, unsigned char *dst,
+                 int dst_stride, unsigned char *coverage, double *seconds_kernel)
+{
+    Gains g;
+    if (int rc = check_compose(s, images, stride, channels, index16, index_stride, params, gain_q8, &g)) return rc;
+    if (!dst) return tscm_set_error(TSCM_E_INVALID, "dst is NULL");
+    if (dst_stride < s->pw * channels) return tscm_set_error(TSCM_E_INVALID, "dst_stride " + std::to_string(dst_stride) + " < pano_w * channels = " + std::to_string(s->pw * channels));
+    if (visible)
+        if (int rc = check_visibility(vp)) return rc;
+    if (seconds_kernel) *seconds_kernel = 0.0;
+    const short *idx = nullptr;
+    if (int rc = upload_compose(s, images, stride, channels, index16, index_stride, params, &idx)) return rc;
+    if (visible)
+        if (int rc = visibility_buffers(s)) return rc;
+    const int wrap = params->wrap_x ? 1 : 0;                 // the pyramids' wrap is the composer's own, not the census window's
+    HIP_TRY(hipEventRecord(s->ev[0], 0));
+    if (visible)
+        if (int rc = launch_visibility(s, idx, vp, nullptr)) return rc;
+    if (channels == 1) launch_compose<1>(s, idx, params->fallback_index, wrap, g, visible ? s->v_use : nullptr);
+    else launch_compose<3>(s, idx, params->fallback_index, wrap, g, visible ? s->v_use : nullptr);
+    HIP_TRY(hipEventRecord(s->ev[1], 0));
+    HIP_TRY(hipEventSynchronize(s->ev[1]));
+    HIP_TRY(hipGetLastError());
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    const size_t row = (size_t)s->pw * channels;
+    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, s->c_out, row, row, (size_t)s->ph, hipMemcpyDeviceToHost));
+    if (coverage) HIP_TRY(hipMemcpy(coverage, s->c_cover, s->npix, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" void tscm_sweep_compose_default_params(tscm_sweep_compose_params *p)
@@ -766,40 +1025,32 @@ extern "C" int tscm_sweep_compose(tscm_sweep *s, const unsigned char *const *ima
                                   const tscm_sweep_compose_params *params, const unsigned short *gain_q8, unsigned char *dst, int dst_stride, unsigned char *coverage,
                                   double *seconds_kernel)
 {
-    Gains g;
-    if (int rc = check_compose(s, images, stride, channels, index16, index_stride, params, gain_q8, &g)) return rc;
-    if (!dst) return tscm_set_error(TSCM_E_INVALID, "dst is NULL");
-    if (dst_stride < s->pw * channels) return tscm_set_error(TSCM_E_INVALID, "dst_stride " + std::to_string(dst_stride) + " < pano_w * channels = " + std::to_string(s->pw * channels));
-    if (seconds_kernel) *seconds_kernel = 0.0;
-    const short *idx = nullptr;
-    if (int rc = upload_compose(s, images, stride, channels, index16, index_stride, params, &idx)) return rc;
-    const int wrap = params->wrap_x ? 1 : 0;                 // the pyramids' wrap is the composer's own, not the census window's
-    HIP_TRY(hipEventRecord(s->ev[0], 0));
-    if (channels == 1) launch_compose<1>(s, idx, params->fallback_index, wrap, g);
-    else launch_compose<3>(s, idx, params->fallback_index, wrap, g);
-    HIP_TRY(hipEventRecord(s->ev[1], 0));
-    HIP_TRY(hipEventSynchronize(s->ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
-    const size_t row = (size_t)s->pw * channels;
-    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, s->c_out, row, row, (size_t)s->ph, hipMemcpyDeviceToHost));
-    if (coverage) HIP_TRY(hipMemcpy(coverage, s->c_cover, s->npix, hipMemcpyDeviceToHost));
-    return 0;
+    return compose_call(s, images, stride, channels, index16, index_stride, params, nullptr, false, gain_q8, dst, dst_stride, coverage, seconds_kernel);
 }
 
-extern "C" int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
-                                         const tscm_sweep_compose_params *params, const unsigned short *gain_q8, unsigned char *hypothesis, unsigned char *sampled,
-                                         unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid, short *blend_pyramid)
+namespace {
+
+// tscm_sweep_compose_stages (visible == false) and tscm_sweep_compose_visible_stages
+int compose_stages_call(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                        const tscm_sweep_compose_params *params, const tscm_sweep_visibility_params *vp, bool visible, const unsigned short *gain_q8,
+                        unsigned char *hypothesis, unsigned char *sampled, unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid,
+                        short *blend_pyramid, unsigned char *use_out, unsigned char *state_out)
 {
     Gains g;
     if (int rc = check_compose(s, images, stride, channels, index16, index_stride, params, gain_q8, &g)) return rc;
     const bool multiband = params->mode == TSCM_PANO_MULTIBAND;
     if (!multiband && (mask_pyramid || lap_pyramid || blend_pyramid))
         return tscm_set_error(TSCM_E_INVALID, std::string(mask_pyramid ? "mask_pyramid" : lap_pyramid ? "lap_pyramid" : "blend_pyramid") + ": the mode is not MULTIBAND");
+    if (visible)
+        if (int rc = check_visibility(vp)) return rc;
     const short *idx = nullptr;
     if (int rc = upload_compose(s, images, stride, channels, index16, index_stride, params, &idx)) return rc;
+    const unsigned char *use = nullptr;
+    if (visible) {
+        if (int rc = visibility_buffers(s)) return rc;
+        if (int rc = launch_visibility(s, idx, vp, nullptr)) return rc;
+        use = s->v_use;
+    }
     const int n = s->n, ch = channels;
     const size_t nplane = (size_t)n * s->npix;
     DeviceMem tmp;
@@ -815,10 +1066,10 @@ extern "C" int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *con
     } else if (lap_pyramid) HIP_TRY(tmp.alloc(&d_lap, (size_t)n * ch * s->Sp));
     const int wrap = params->wrap_x ? 1 : 0;
     if (ch == 1) {
-        launch_gather<1>(s, idx, params->fallback_index, g, d_G, gstride, s->c_mpyr, d_hyp, d_sampled, d_alpha);
+        launch_gather<1>(s, idx, params->fallback_index, g, d_G, gstride, s->c_mpyr, d_hyp, d_sampled, d_alpha, use);
         if (multiband) launch_pyramids<1>(s, wrap, d_lap, false);
     } else {
-        launch_gather<3>(s, idx, params->fallback_index, g, d_G, gstride, s->c_mpyr, d_hyp, d_sampled, d_alpha);
+        launch_gather<3>(s, idx, params->fallback_index, g, d_G, gstride, s->c_mpyr, d_hyp, d_sampled, d_alpha, use);
         if (multiband) launch_pyramids<3>(s, wrap, d_lap, false);
     }
     HIP_TRY(hipGetLastError());
@@ -830,7 +1081,55 @@ extern "C" int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *con
     if (mask_pyramid) if (int rc = download_pyramid(*s, s->c_mpyr, n, mask_pyramid)) return rc;
     if (lap_pyramid) if (int rc = download_pyramid(*s, d_lap, n * ch, lap_pyramid)) return rc;
     if (blend_pyramid) if (int rc = download_pyramid(*s, s->c_B, ch, blend_pyramid)) return rc;
+    if (visible) return download_use_state(s, use_out, state_out);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int tscm_sweep_compose_stages(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                                         const tscm_sweep_compose_params *params, const unsigned short *gain_q8, unsigned char *hypothesis, unsigned char *sampled,
+                                         unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid, short *lap_pyramid, short *blend_pyramid)
+{
+    return compose_stages_call(s, images, stride, channels, index16, index_stride, params, nullptr, false, gain_q8, hypothesis, sampled, alpha, label, mask_pyramid,
+                               lap_pyramid, blend_pyramid, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ visibility: entry points
+extern "C" void tscm_sweep_visibility_default_params(tscm_sweep_visibility_params *p)
+{
+    if (!p) return;
+    p->struct_size = (int)sizeof(tscm_sweep_visibility_params);
+    p->cell_shift = 2; p->tolerance = 2; p->dilate = 0; p->near_is_high = 1;
+}
+
+extern "C" int tscm_sweep_visibility(tscm_sweep *s, const short *index16, int index_stride, const tscm_sweep_visibility_params *vparams, unsigned char *use,
+                                     unsigned char *state, double *seconds_kernel)
+{
+    return visibility_call(s, index16, index_stride, vparams, nullptr, use, state, seconds_kernel);
+}
+
+extern "C" int tscm_sweep_visibility_stages(tscm_sweep *s, const short *index16, int index_stride, const tscm_sweep_visibility_params *vparams, unsigned char *hypothesis,
+                                            unsigned short *depth_buffer, int *cell, unsigned char *visible, unsigned char *use, unsigned char *state)
+{
+    const VisibilityStages host = { hypothesis, depth_buffer, cell, visible };
+    return visibility_call(s, index16, index_stride, vparams, &host, use, state, nullptr);
+}
+
+extern "C" int tscm_sweep_compose_visible(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                                          const tscm_sweep_compose_params *params, const tscm_sweep_visibility_params *vparams, const unsigned short *gain_q8,
+                                          unsigned char *dst, int dst_stride, unsigned char *coverage, double *seconds_kernel)
+{
+    return compose_call(s, images, stride, channels, index16, index_stride, params, vparams, true, gain_q8, dst, dst_stride, coverage, seconds_kernel);
+}
+
+extern "C" int tscm_sweep_compose_visible_stages(tscm_sweep *s, const unsigned char *const *images, int stride, int channels, const short *index16, int index_stride,
+                                                 const tscm_sweep_compose_params *params, const tscm_sweep_visibility_params *vparams, const unsigned short *gain_q8,
+                                                 unsigned char *hypothesis, unsigned char *sampled, unsigned char *alpha, unsigned char *label, unsigned char *mask_pyramid,
+                                                 short *lap_pyramid, short *blend_pyramid, unsigned char *use, unsigned char *state)
+{
+    return compose_stages_call(s, images, stride, channels, index16, index_stride, params, vparams, true, gain_q8, hypothesis, sampled, alpha, label, mask_pyramid,
+                               lap_pyramid, blend_pyramid, use, state);
 }
 
 extern "C" int tscm_sweep_points(const short *index16, int pano_w, int pano_h, int stride, const tscm_map_desc *pano_map, int projection, const double *inv_distance, int D,

@@ -161,6 +161,11 @@ class CSweepComposeParams(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("levels", C.c_int), ("wrap_x", C.c_int), ("fallback_index", C.c_int)]
 
 
+class CSweepVisibilityParams(C.Structure):
+    """tscm_sweep_visibility_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("cell_shift", C.c_int), ("tolerance", C.c_int), ("dilate", C.c_int), ("near_is_high", C.c_int)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -192,6 +197,7 @@ EXPORTS = [
     "tscm_build_sweep_maps",
     "tscm_sweep_default_params", "tscm_sweep_create", "tscm_sweep_depth", "tscm_sweep_stages", "tscm_sweep_stage_times", "tscm_sweep_points", "tscm_sweep_destroy",
     "tscm_sweep_compose_default_params", "tscm_sweep_compose", "tscm_sweep_compose_stages",
+    "tscm_sweep_visibility_default_params", "tscm_sweep_visibility", "tscm_sweep_visibility_stages", "tscm_sweep_compose_visible", "tscm_sweep_compose_visible_stages",
 ]
 
 
@@ -325,6 +331,14 @@ def lib():
     L.tscm_sweep_compose_default_params.restype = None
     L.tscm_sweep_compose.argtypes = [vp, vpp, C.c_int, C.c_int, shp, C.c_int, C.POINTER(CSweepComposeParams), usp, ubp, C.c_int, ubp, dp]
     L.tscm_sweep_compose_stages.argtypes = [vp, vpp, C.c_int, C.c_int, shp, C.c_int, C.POINTER(CSweepComposeParams), usp, ubp, ubp, ubp, ubp, ubp, shp, shp]
+    vis = C.POINTER(CSweepVisibilityParams)
+    L.tscm_sweep_visibility_default_params.argtypes = [vis]
+    L.tscm_sweep_visibility_default_params.restype = None
+    L.tscm_sweep_visibility.argtypes = [vp, shp, C.c_int, vis, ubp, ubp, dp]
+    L.tscm_sweep_visibility_stages.argtypes = [vp, shp, C.c_int, vis, ubp, usp, ip, ubp, ubp, ubp]
+    L.tscm_sweep_compose_visible.argtypes = [vp, vpp, C.c_int, C.c_int, shp, C.c_int, C.POINTER(CSweepComposeParams), vis, usp, ubp, C.c_int, ubp, dp]
+    L.tscm_sweep_compose_visible_stages.argtypes = [vp, vpp, C.c_int, C.c_int, shp, C.c_int, C.POINTER(CSweepComposeParams), vis, usp, ubp, ubp, ubp, ubp, ubp, shp, shp,
+                                                    ubp, ubp]
     L.tscm_sweep_destroy.argtypes = [vp]
     L.tscm_sweep_destroy.restype = None
     L.tscm_estimate_focal.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]

@@ -41,6 +41,21 @@ def compose_params(**over) -> _lib.CSweepComposeParams:
     return p
 
 
+def visibility_params(**over) -> _lib.CSweepVisibilityParams:
+    """tscm_sweep_visibility_default_params with fields replaced: cell_shift, tolerance, dilate, near_is_high."""
+    p = _lib.CSweepVisibilityParams()
+    _lib.lib().tscm_sweep_visibility_default_params(C.byref(p))
+    for k, v in over.items():
+        if k == "struct_size" or not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, int(v))
+    return p
+
+
+def _visibility_struct(visibility) -> _lib.CSweepVisibilityParams:
+    return visibility if isinstance(visibility, _lib.CSweepVisibilityParams) else visibility_params(**visibility)
+
+
 def bgr_to_gray(img) -> np.ndarray:
     """The composer's BGR2GRAY integers (tscm.h, overlap): (b 1868 + g 9617 + r 4899 + 2^13) >> 14; a grey image is returned
     as it is."""
@@ -211,11 +226,13 @@ class Sweeper:
             gptr = _lib.ushort_ptr(g)
         return p, (idx, iptr, istride), (g, gptr)
 
-    def compose(self, images, index16=None, gains=None, out: np.ndarray | None = None, with_coverage: bool = False, with_seconds: bool = False, **params):
+    def compose(self, images, index16=None, gains=None, out: np.ndarray | None = None, with_coverage: bool = False, with_seconds: bool = False, visibility=None,
+                **params):
         """tscm_sweep_compose -> uint8 [pano_h, pano_w] or [pano_h, pano_w, 3]: the frame blended at the hypothesis that
         index16 names per pixel (None: the map of this sweeper's last depth(), still on the device).  images: grey or
         3-channel, they need not be those of the depth pass.  params: the fields of compose_params.  `out` may be a
-        row-padded view, whose padding keeps its values."""
+        row-padded view, whose padding keeps its values.  visibility: None, or the fields of visibility_params as a dict (or
+        the struct): tscm_sweep_compose_visible, which leaves out the cameras that do not see a pixel's point."""
         imgs, ptrs, stride, ch = self._colour_frame(images)
         p, (idx, iptr, istride), (g, gptr) = self._compose_args(index16, gains, params)
         shape = (self.pano_h, self.pano_w) if ch == 1 else (self.pano_h, self.pano_w, ch)
@@ -227,14 +244,18 @@ class Sweeper:
         cov = np.zeros((self.pano_h, self.pano_w), dtype=np.uint8) if with_coverage else None
         ub = C.POINTER(C.c_ubyte)
         sec = C.c_double(0.0)
-        _lib.check(_lib.lib().tscm_sweep_compose(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), gptr, out.ctypes.data_as(ub), int(out.strides[0]),
-                                                 None if cov is None else cov.ctypes.data_as(ub), C.byref(sec)))
+        tail = (gptr, out.ctypes.data_as(ub), int(out.strides[0]), None if cov is None else cov.ctypes.data_as(ub), C.byref(sec))
+        if visibility is None:
+            _lib.check(_lib.lib().tscm_sweep_compose(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), *tail))
+        else:
+            _lib.check(_lib.lib().tscm_sweep_compose_visible(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), C.byref(_visibility_struct(visibility)), *tail))
         res = (out,) + ((cov,) if with_coverage else ()) + ((sec.value,) if with_seconds else ())
         return res[0] if len(res) == 1 else res
 
-    def compose_stages(self, images, index16=None, gains=None, **params) -> dict:
+    def compose_stages(self, images, index16=None, gains=None, visibility=None, **params) -> dict:
         """tscm_sweep_compose_stages -> hypothesis [ph, pw], sampled [n, ph, pw, C], alpha [n, ph, pw], label [ph, pw] and, in
-        MULTIBAND mode, mask_pyramid [n, S], lap_pyramid [n, C, S], blend_pyramid [C, S] (levels 0..L one after the other)."""
+        MULTIBAND mode, mask_pyramid [n, S], lap_pyramid [n, C, S], blend_pyramid [C, S] (levels 0..L one after the other).
+        visibility (as for compose): tscm_sweep_compose_visible_stages, which adds use [n, ph, pw] and state [ph, pw]."""
         imgs, ptrs, stride, ch = self._colour_frame(images)
         p, (idx, iptr, istride), (g, gptr) = self._compose_args(index16, gains, params)
         n, ph, pw = self.n, self.pano_h, self.pano_w
@@ -246,8 +267,47 @@ class Sweeper:
             S = sum((ph >> l) * (pw >> l) for l in range(max(int(p.levels), 0) + 1))
             res.update(mask_pyramid=np.zeros((n, S), np.uint8), lap_pyramid=np.zeros((n, ch, S), np.int16), blend_pyramid=np.zeros((ch, S), np.int16))
             pyr = [res["mask_pyramid"].ctypes.data_as(ub), res["lap_pyramid"].ctypes.data_as(sh), res["blend_pyramid"].ctypes.data_as(sh)]
-        _lib.check(_lib.lib().tscm_sweep_compose_stages(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), gptr, res["hypothesis"].ctypes.data_as(ub),
-                                                        res["sampled"].ctypes.data_as(ub), res["alpha"].ctypes.data_as(ub), res["label"].ctypes.data_as(ub), *pyr))
+        tail = (gptr, res["hypothesis"].ctypes.data_as(ub), res["sampled"].ctypes.data_as(ub), res["alpha"].ctypes.data_as(ub), res["label"].ctypes.data_as(ub), *pyr)
+        if visibility is None:
+            _lib.check(_lib.lib().tscm_sweep_compose_stages(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), *tail))
+        else:
+            res.update(use=np.zeros((n, ph, pw), np.uint8), state=np.zeros((ph, pw), np.uint8))
+            _lib.check(_lib.lib().tscm_sweep_compose_visible_stages(self._handle, ptrs, stride, ch, iptr, istride, C.byref(p), C.byref(_visibility_struct(visibility)),
+                                                                    *tail, res["use"].ctypes.data_as(ub), res["state"].ctypes.data_as(ub)))
+        return res
+
+    def visibility(self, index16=None, with_state: bool = False, with_seconds: bool = False, **params):
+        """tscm_sweep_visibility -> use uint8 [n, pano_h, pano_w] (1: the composer takes camera k at that pixel) and, with_state,
+        state uint8 [pano_h, pano_w] (0 no depth, 1 seen by nobody, 2 all visible, 3 some occluded, 4 all occluded and all
+        kept).  index16: None for the map of the last depth().  params: the fields of visibility_params."""
+        if self._handle is None:
+            raise ValueError("the sweeper is closed")
+        vp = visibility_params(**params)
+        _, (idx, iptr, istride), _ = self._compose_args(index16, None, {})
+        use, state = np.zeros((self.n, self.pano_h, self.pano_w), np.uint8), np.zeros((self.pano_h, self.pano_w), np.uint8)
+        ub = C.POINTER(C.c_ubyte)
+        sec = C.c_double(0.0)
+        _lib.check(_lib.lib().tscm_sweep_visibility(self._handle, iptr, istride, C.byref(vp), use.ctypes.data_as(ub), state.ctypes.data_as(ub) if with_state else None,
+                                                    C.byref(sec)))
+        res = (use,) + ((state,) if with_state else ()) + ((sec.value,) if with_seconds else ())
+        return res[0] if len(res) == 1 else res
+
+    def visibility_stages(self, index16=None, **params) -> dict:
+        """tscm_sweep_visibility_stages -> hypothesis [ph, pw] uint8, depth_buffer [n, ch, cw] uint16, cell [n, ph, pw] int32,
+        visible [n, ph, pw], use [n, ph, pw], state [ph, pw] uint8."""
+        if self._handle is None:
+            raise ValueError("the sweeper is closed")
+        vp = visibility_params(**params)
+        _, (idx, iptr, istride), _ = self._compose_args(index16, None, {})
+        n, ph, pw = self.n, self.pano_h, self.pano_w
+        shift = min(max(vp.cell_shift, 0), 8)                        # outside 0..8: refused below
+        cw, ch = ((self.width - 1) >> shift) + 1, ((self.height - 1) >> shift) + 1
+        res = dict(hypothesis=np.zeros((ph, pw), np.uint8), depth_buffer=np.zeros((n, ch, cw), np.uint16), cell=np.zeros((n, ph, pw), np.int32),
+                   visible=np.zeros((n, ph, pw), np.uint8), use=np.zeros((n, ph, pw), np.uint8), state=np.zeros((ph, pw), np.uint8))
+        ub = C.POINTER(C.c_ubyte)
+        _lib.check(_lib.lib().tscm_sweep_visibility_stages(self._handle, iptr, istride, C.byref(vp), res["hypothesis"].ctypes.data_as(ub),
+                                                           res["depth_buffer"].ctypes.data_as(C.POINTER(C.c_ushort)), res["cell"].ctypes.data_as(C.POINTER(C.c_int)),
+                                                           res["visible"].ctypes.data_as(ub), res["use"].ctypes.data_as(ub), res["state"].ctypes.data_as(ub)))
         return res
 
     def stage_times(self) -> np.ndarray:
@@ -325,7 +385,7 @@ def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: fl
 
 def rig_panorama(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: float = 500.0, far: float = np.inf, D: int = 64, weights="radial",
                  projection="equirect", device: int = 0, post=None, mode="multiband", levels: int = 4, gains=None, fallback_index: int = 0, fill=None,
-                 refine=None, **over):
+                 refine=None, visibility=None, **over):
     """One call from a calibration and a frame to the parallax-free panorama: (panorama uint8 [ph, pw] or [ph, pw, 3],
     index16 [ph, pw], coverage [ph, pw]).  Colour images (BGR) go through bgr_to_gray for the depth pass and are blended in
     colour.  post: keyword arguments of stereo.filter for the index map, as in rig_depth; the filtered map is the one the
@@ -333,7 +393,9 @@ def rig_panorama(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near:
     post; the frame is then composed at the filled map.  refine: keyword arguments of stereo.refine, as in rig_depth,
     applied after fill and guided by the grey frame composed in SEAM mode at the map as it stands (pixels without depth at
     fallback_index); the returned frame is composed at the refined map.  fallback_index: the hypothesis of a pixel without
-    depth (0 = far)."""
+    depth (0 = far).  visibility: None, or the fields of visibility_params as a dict: the returned frame leaves out, per pixel,
+    the cameras that look at its point through something nearer (Sweeper.compose with visibility), judged at the map the
+    frame is composed at."""
     _check_fill(fill)
     _check_refine(refine)
     size = (np.asarray(images[0]).shape[1], np.asarray(images[0]).shape[0])
@@ -349,5 +411,5 @@ def rig_panorama(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near:
             idx = stereo.fill(idx, device=device, min_disparity=0, **{"wrap_x": 1, **fill})
         if refine is not None:
             idx = _refine_index(s, grey, idx, refine, fallback_index, device)
-        pano, cov = s.compose(images, index16=idx if post or fill is not None or refine is not None else None, gains=gains, with_coverage=True, mode=mode, levels=levels, fallback_index=fallback_index)
+        pano, cov = s.compose(images, index16=idx if post or fill is not None or refine is not None else None, gains=gains, with_coverage=True, visibility=visibility, mode=mode, levels=levels, fallback_index=fallback_index)
     return pano, idx, cov
