@@ -331,6 +331,17 @@ int tscm_eval_normal_equations_robust(const tscm_problem *problem, int device, c
                                       double *cam_gram, double *cam_grad, double *cost);
 int tscm_eval_step_robust(const tscm_problem *problem, int device, const tscm_options *opt, int kind, double scale,
                           double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary);
+/* The outputs of tscm_eval_normal_equations_ex at the problem's parameters, from a solver (one rank;
+ * a sharded one: TSCM_E_UNSUPPORTED) and with its loss (tscm_solver_set_loss).  as_solved != 0: from
+ * the evaluation launch exactly as a solve makes it -- the default Gram kernel forms no rotation
+ * columns for a camera whose pose block is constant (cam_pose_constant, every camera of a mono
+ * problem): the reduced system has no column for them.  Those rows and columns of cam_gram /
+ * cam_grad and columns 0-2 of such a view's view_cross are exactly 0 on a solver that has evaluated
+ * nothing else; every other entry has the bits of as_solved == 0.  With jacobian_fp32 or
+ * TSCM_EXEC_GRAM_16X16 both give the same.  The solver's next solve starts afresh.               */
+int tscm_solver_eval_normal_equations(tscm_solver *s, const tscm_options *opt, int as_solved,
+                                      double *board_gram, double *board_grad, double *view_cross,
+                                      double *cam_gram, double *cam_grad, double *cost);
 
 /* ------------------------------------------------------------------ held intrinsics
  * A mask word per camera: bit k holds intrinsic k of fx fy cx cy xi lambda alpha b c (the 9-vector of

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """usage: python3 tools/isa_counts.py [--asm FILE.s] [--kernel REGEX] [--label NAME]
 Opcode-class counts of ONE kernel's view loop from the gfx950 assembly of the solver's translation unit (no GPU needed).
-Without --asm the unit is compiled to assembly first (device side only, the flags of csrc/Makefile).  The view loop is the
-smallest backward-branch range that holds all of the kernel's MFMAs; inside it the MFMAs are the landmarks of the phases the
+Without --asm the unit is compiled to assembly first (device side only, the flags of csrc/Makefile).  A view loop is the
+smallest backward-branch range around an MFMA -- k_eval_gram4 has two, the full path and the constant-pose path, reported one
+after the other; inside it the MFMAs are the landmarks of the phases the
 wave timeline stamps: geometry (loop top .. first MFMA), MFMA u (first half of the MFMAs), copy (between the halves), MFMA v,
 epilogue (last MFMA .. loop end).  The scheduler moves instructions across those landmarks, so the split is where the
 instructions ARE ISSUED, not where the source wrote them; the totals per iteration do not depend on it.  Blocks the loop jumps
@@ -74,24 +75,34 @@ def main():
         target = r.split()[-1] if r else ""
         if op.startswith(("s_cbranch", "s_branch")) and target in labels and labels[target] <= k:
             loops.append((labels[target], k))
-    loops = [lp for lp in loops if lp[0] <= mf[0] and mf[-1] <= lp[1]]
-    if not loops: sys.exit("no loop holds all MFMAs of the kernel")
-    lo, hi = min(loops, key=lambda lp: lp[1] - lp[0])
-    half = len(mf) // 2
-    marks = [mf[0], mf[half - 1] + 1, mf[half], mf[-1] + 1]      # first instruction of mfma_u, copy, mfma_v, epilogue
-    tab = {p: dict.fromkeys(CLASSES, 0) for p in PHASES}
-    for k in range(lo, hi + 1):
-        tab[PHASES[sum(k >= m for m in marks)]][classify(*ins[k])] += 1
+    # the view loop of each path: the smallest backward-branch range around an MFMA (one range for a kernel with one loop; two
+    # for k_eval_gram4: the full path and, with two thirds of its MFMAs, the constant-pose path)
+    paths = {}
+    for m in mf:
+        around = [lp for lp in loops if lp[0] <= m <= lp[1]]
+        if not around: sys.exit("an MFMA of the kernel stands outside every loop")
+        paths.setdefault(min(around, key=lambda lp: lp[1] - lp[0]), []).append(m)
+    paths = sorted(paths.items(), key=lambda kv: -len(kv[1]))
+    names = ["full path", "constant-pose path"] if len(paths) == 2 else [f"loop {k}" for k in range(len(paths))]
+    tabs = []
+    for (lo, hi), pm in paths:
+        half = len(pm) // 2
+        marks = [pm[0], pm[half - 1] + 1, pm[half], pm[-1] + 1]      # first instruction of mfma_u, copy, mfma_v, epilogue
+        tab = {p: dict.fromkeys(CLASSES, 0) for p in PHASES}
+        for k in range(lo, hi + 1):
+            tab[PHASES[sum(k >= m for m in marks)]][classify(*ins[k])] += 1
+        tabs.append((lo, hi, pm, tab))
     # resources: the kernel descriptor's directives and the compiler's remarks behind the function
     txt = "\n".join(lines[end:end + 400])
     remarks = [("vgpr", r"; NumVgprs: (\d+)"), ("agpr", r"; NumAgprs: (\d+)"), ("sgpr", r"; TotalNumSgprs: (\d+)"), ("scratch", r"; ScratchSize: (\d+)"),
                ("occupancy", r"; Occupancy: (\d+)"), ("lds_static", r"; LDSByteSize: (\d+)"), ("code_bytes", r"; codeLenInByte = (\d+)")]
     res = {k: (re.search(p, txt) or [None, "?"])[1] for k, p in remarks}
-    print(f"# {a.kernel}{'  [' + a.label + ']' if a.label else ''}: one iteration of the view loop ({hi - lo + 1} instructions, {len(mf)} MFMAs in the kernel's text)")
-    print(f"{'class':14s}" + "".join(f"{p:>10s}" for p in PHASES) + f"{'total':>10s}")
-    for c in CLASSES:
-        print(f"{c:14s}" + "".join(f"{tab[p][c]:10d}" for p in PHASES) + f"{sum(tab[p][c] for p in PHASES):10d}")
-    print(f"{'VALU (all)':14s}" + "".join(f"{sum(tab[p][c] for c in VALU):10d}" for p in PHASES) + f"{sum(tab[p][c] for p in PHASES for c in VALU):10d}")
+    for name, (lo, hi, pm, tab) in zip(names, tabs):
+        print(f"# {a.kernel}{'  [' + a.label + ']' if a.label else ''}, {name}: one iteration of the view loop ({hi - lo + 1} instructions, {len(pm)} MFMAs)")
+        print(f"{'class':14s}" + "".join(f"{p:>10s}" for p in PHASES) + f"{'total':>10s}")
+        for c in CLASSES:
+            print(f"{c:14s}" + "".join(f"{tab[p][c]:10d}" for p in PHASES) + f"{sum(tab[p][c] for p in PHASES):10d}")
+        print(f"{'VALU (all)':14s}" + "".join(f"{sum(tab[p][c] for c in VALU):10d}" for p in PHASES) + f"{sum(tab[p][c] for p in PHASES for c in VALU):10d}")
     print("resources: " + "  ".join(f"{k} {v}" for k, v in res.items()))
 
 

@@ -135,6 +135,11 @@ def placement(L, tmin):
         for k, b in enumerate(order):
             pos[(blks.index(b), k)] += 1
     print(f"  SIMDs with four waves: {len(full)}; they finish in block order on {in_order}, in reverse block order on {rev_order}")
+    # how the quarters of the grid share the SIMDs (config 4: a quarter is a camera, the first one the constant camera, whose
+    # waves take k_eval_gram4's shorter constant-pose path)
+    nblk = max(r[0] for r in L) + 1
+    first = collections.Counter(sum(1 for _, b in v if 4 * b < nblk) for v in full)
+    print(f"  waves of the first quarter of the grid per four-wave SIMD: {dict(sorted(first.items()))}")
     print("  rows: rank by block index; columns: 1st..4th to finish")
     for r in range(4):
         print("   ", [pos[(r, k)] for k in range(4)])

@@ -353,10 +353,13 @@ def evaluate_functor(problem: Problem, device: int = 0, jacobians: bool = True):
     return cost.value, res
 
 
-def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0, loss=None) -> dict:
+def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0, loss=None,
+                     as_solved: bool = False) -> dict:
     """Schur-form normal equations (unscaled) from the Gram kernel a solve with these options runs:
     k_eval_gram4 by default, k_eval_gram_f32 with jacobian_fp32=1, k_eval_gram with exec_flags=EXEC_GRAM_16X16.
-    loss (as for calibrate()): the corrected equations of a robust solve, cost = sum rho / 2."""
+    loss (as for calibrate()): the corrected equations of a robust solve, cost = sum rho / 2.
+    as_solved: the evaluation launch exactly as a solve makes it, on a fresh solver (tscm_solver_eval_normal_equations):
+    k_eval_gram4 forms no rotation columns for a camera whose pose block is constant, and those entries are 0."""
     assert _is_normalised(problem)
     Cn, B, V = problem.n_cameras, problem.n_boards, problem.n_views
     out = dict(board_gram=np.zeros((B, 6, 6)), board_grad=np.zeros((B, 6)), view_cross=np.zeros((V, 6, 15)),
@@ -366,7 +369,12 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
     o = _l.default_options(problem.mono, jacobian_fp32=jacobian_fp32, exec_flags=exec_flags)
     outs = (_l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
             _l.dptr(out["cam_gram"]), _l.dptr(out["cam_grad"]), C.byref(cost))
-    if loss is None:
+    if as_solved:
+        with Solver(problem, device) as s:
+            if loss is not None:
+                s.set_loss(*((loss,) if isinstance(loss, str) else loss))
+            _l.check(_l.lib().tscm_solver_eval_normal_equations(s._h, C.byref(o), 1, *outs))
+    elif loss is None:
         _l.check(_l.lib().tscm_eval_normal_equations_ex(C.byref(cp), device, C.byref(o), *outs))
     else:
         k, a = _l.loss_args(loss)

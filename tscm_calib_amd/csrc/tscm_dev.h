@@ -23,6 +23,11 @@ constexpr int kTcols = 15;         // columns of the single MFMA Gram tile (see 
 // register 0 of the lanes kq = 0, 1, 2.
 constexpr int kTcWb = 0, kTcWc = 4, kTcF = 8, kTcOne = 9, kTcXi = 10, kTcLam = 12, kTcAl = 13, kTcR = 14;
 __host__ __device__ constexpr int tc_tc(int j) { return 3 + 4 * j; }
+// word 0 of a chunk descriptor (DevProblem::chunk_desc): the camera, and whether its pose block is constant
+constexpr int kChunkConstPose = 1 << 30, kChunkCamMask = kChunkConstPose - 1;
+// bits of the Gram kernels' `cand` argument: the candidate point; k_eval_gram4 only: chunks of a constant-pose camera form no
+// w_c columns (ExecPlan::skip_const_pose)
+constexpr int kEvalCand = 1, kEvalSkipConst = 2;
 constexpr int kVConst = 27;        // per-view constants: R_c r1, R_c r2, R_c t_b + t_c (board point -> camera frame in two FMAs per
                                    // component), then R_c dR_b/dw_k [:,0:2]
 constexpr int kCConst = 48;        // per-camera constants: [0,9) R_c, [9,12) t_c, [12,21) a_k (dR_c/dw_k = [a_k]x R_c), [21,24) w if the

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
     // head in two dependent round trips, as in k_eval_gram4 (round 5): control block + 16-byte chunk descriptor + the first 128
     // board coordinates; then everything that hangs on the descriptor at once (below)
     const v4i cd = *(const v4i __attribute__((address_space(4))) *)(const void *)(P.chunk_desc + chunk);
-    const int cam = cd[0], vb = cd[1], ve = cd[2];
+    const int cam = cd[0] & kChunkCamMask, vb = cd[1], ve = cd[2];       // (word 0 also carries k_eval_gram4's kChunkConstPose)
     const int n2 = 2 * P.n_points;
     const double bx0 = P.board_xy[min(lane, n2 - 1)], bx1 = P.board_xy[min(lane + 64, n2 - 1)];
     // wave-uniform constants through the constant address space: scalar loads into SGPR operands; the

@@ -22,6 +22,9 @@
 // numbering of k_eval_gram: the whole solve is bit-identical (tools/regress_bits.py).
 //
 // Tile columns here (groups of four):  0-2 w_b, 3 r | 4-6 t_c, 7 alpha | 8-10 w_c, 11 f* | 12 one*, 13 xi, 14 lambda, 15 zero.
+// A chunk of a camera whose pose block is constant, in a solve's launch (the constant-pose path, CP below):
+//                                       0-2 w_b, 3 r | 4-6 t_c, 7 alpha | 8-11 never written: zero | 12 one*, 13 xi, 14 lambda, 15 f*
+// -- three groups, six pairs, TWO instructions per four rows, no w_c block in the geometry (g4_live, kG4FCp).
 // LDS tile: element (k-step t, column c, row k) at double t * 68 + 4 c + (k ^ 2 (c >> 3)):
 //   * the three operand vectors are conflict-free ds_read_b64 (32-lane groups, banks mod 64: columns c and c + 8 would
 //     share a bank pair, the xor puts them on complementary halves);
@@ -60,9 +63,27 @@ __device__ __forceinline__ constexpr int g4_wcol(int c)
 __device__ __forceinline__ constexpr int g4_cgroup(int b, int q) { return q == 0 ? b : q == 1 ? ((b + 1) & 3) : (b == 0 ? 2 : b == 1 ? 3 : 1); }
 __device__ __forceinline__ int g4_elem(int c, int k) { return 4 * c + (k ^ ((c >> 3) << 1)); }     // within a k-step
 
-// one k-step: three operand vectors, three instructions; operands requested D k-steps ahead
-template <int KS, int D, bool ACC, int T = 0>
-__device__ __forceinline__ void gram4_steps(unsigned aN, unsigned aR, unsigned aB, double (&n)[KS], double (&r)[KS], double (&b)[KS], double (&acc)[3])
+// The constant-pose path (CP): a chunk is one camera, and a camera whose pose block is held constant has no pose column in
+// the reduced system (plan_columns), so a solve's launch (ExecPlan::skip_const_pose) takes such a chunk's waves down a
+// path without the w_c columns.  Same tile addresses; f* moves from column 11 into the zero column 15, columns 8-11 are
+// never written and stay zero.  Three groups are left -- 0 (w_b, r), 1 (t_c, alpha), 3' (one*, xi, lambda, f*) -- and their
+// six pairs fit TWO instructions per four rows.  A = N in blocks 0, 1, 3; the lanes of the idle block 2 read group 3':
+//   q0  B = N in blocks 0, 1, 3, group 0 in block 2       pairs (0,0) (1,1) (3',0) (3',3')
+//   q1  B = group 1 (t_c) in every block                   pairs (0,1) (1,1) (3',1) (3',1)
+// Every pair that meets the t_c group has it as the column group, as on the full path, and block 2 of q0 holds what block
+// 3 of the full path's q1 holds (rows one*, xi, lambda x columns w_b) plus the f* row of its q2 block 0, transposed: the
+// same products summed in the same order, the same bits.
+constexpr int kG4FCp = 15;                      // tile column of f* on the constant-pose path
+// (kChunkConstPose, kChunkCamMask, kEvalCand, kEvalSkipConst: tscm_dev.h)
+template <bool CP> __device__ __forceinline__ constexpr bool g4_live(int c) { return CP ? (c < 8 || c >= 12) : c < kTcols; }   // columns a corner writes
+template <bool CP> __device__ __forceinline__ constexpr int g4_old_col_of(int c) { return CP && c == kG4FCp ? kTcF : g4_old_col(c); }
+// W column of member i of group 3' (one*, xi, lambda, f*); one* and f* are the first of a (u-part, v-part) pair
+__device__ __forceinline__ constexpr int g4_wcol_cp(int i) { return i == 0 ? 8 : i == 1 ? 10 : i == 2 ? 11 : 6; }
+
+// one k-step: three operand vectors, three instructions (NQ = 2, the constant-pose path: n is A of both, r and b their B);
+// operands requested D k-steps ahead
+template <int KS, int D, bool ACC, int NQ, int T = 0>
+__device__ __forceinline__ void gram4_steps(unsigned aN, unsigned aR, unsigned aB, double (&n)[KS], double (&r)[KS], double (&b)[KS], double (&acc)[NQ])
 {
     if constexpr (T < KS) {
         if constexpr (T + D < KS) {
@@ -72,15 +93,17 @@ __device__ __forceinline__ void gram4_steps(unsigned aN, unsigned aR, unsigned a
         }
         constexpr int newer = 3 * (KS - 1 - T < D ? KS - 1 - T : D);      // requests younger than this k-step's three
         lgkm_wait<newer + 2>(n[T]);
-        if constexpr (T == 0 && !ACC) acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], n[T], 0.0, 0, 0, 0);
-        else acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], n[T], acc[0], 0, 0, 0);
+        if constexpr (NQ == 3) {
+            if constexpr (T == 0 && !ACC) acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], n[T], 0.0, 0, 0, 0);
+            else acc[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], n[T], acc[0], 0, 0, 0);
+        }
         lgkm_wait<newer + 1>(r[T]);
-        if constexpr (T == 0 && !ACC) acc[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], r[T], 0.0, 0, 0, 0);
-        else acc[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], r[T], acc[1], 0, 0, 0);
+        if constexpr (T == 0 && !ACC) acc[NQ - 2] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], r[T], 0.0, 0, 0, 0);
+        else acc[NQ - 2] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], r[T], acc[NQ - 2], 0, 0, 0);
         lgkm_wait<newer>(b[T]);
-        if constexpr (T == 0 && !ACC) acc[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], b[T], 0.0, 0, 0, 0);
-        else acc[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], b[T], acc[2], 0, 0, 0);
-        gram4_steps<KS, D, ACC, T + 1>(aN, aR, aB, n, r, b, acc);
+        if constexpr (T == 0 && !ACC) acc[NQ - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], b[T], 0.0, 0, 0, 0);
+        else acc[NQ - 1] = __builtin_amdgcn_mfma_f64_4x4x4f64(n[T], b[T], acc[NQ - 1], 0, 0, 0);
+        gram4_steps<KS, D, ACC, NQ, T + 1>(aN, aR, aB, n, r, b, acc);
     }
 }
 template <int KS, int D, int T = 0>
@@ -94,13 +117,13 @@ __device__ __forceinline__ void gram4_prime(unsigned aN, unsigned aR, unsigned a
     }
 }
 // ACC: the accumulators carry the earlier passes of the view (otherwise the first k-step starts from C = 0)
-template <int KS, bool ACC>
-__device__ __forceinline__ void gram4_full(unsigned aN, unsigned aR, unsigned aB, double (&acc)[3])
+template <int KS, bool ACC, int NQ>
+__device__ __forceinline__ void gram4_full(unsigned aN, unsigned aR, unsigned aB, double (&acc)[NQ])
 {
     constexpr int D = KS < 2 ? KS : 2;      // (round 5: 1, 2, 3 and 4 k-steps ahead measure the same to 0.1 us -- the MFMA phases do not wait for the LDS)
     double n[KS], r[KS], b[KS];
     gram4_prime<KS, D>(aN, aR, aB, n, r, b);
-    gram4_steps<KS, D, ACC>(aN, aR, aB, n, r, b, acc);
+    gram4_steps<KS, D, ACC, NQ>(aN, aR, aB, n, r, b, acc);
 }
 
 // t_b entry of this lane's quad: lanes j = 0, 1, 2 of a quad hold the t_c0, t_c1, t_c2 entries of one tile column; lane
@@ -125,13 +148,16 @@ __device__ __forceinline__ double lane_pick(double keep, double take)
 // ROBUST: a loss L (robust_rho): every entry a corner puts into the tile, r column included, is scaled by w = sqrt(rho'), and
 // the cost entry of the camera tile is the lanes' fp64 sum of rho instead of the contraction r^T r.  L is not read
 // by the ROBUST = false instantiations, which compile to the code they had before the switch existed.
-template <int KS, bool MULTI, bool ROBUST = false>
-__global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S, int cand, LossArg L)
+// CP: the constant-pose path (above).  The kernel below takes the first trip of the head -- cd: the chunk's descriptor,
+// ctrl_done, ctrl_cur: the control block, my_xy: the lane's board point -- and then one wave-uniform branch into the
+// instantiation of its chunk; cand: 0 or 1.
+template <int KS, bool MULTI, bool ROBUST, bool CP>
+__device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevState &S, const int cand, const LossArg &L, const v4i cd,
+                                                const int ctrl_done, const int ctrl_cur, const d2 my_xy)
 {
     static_assert(KS >= 1 && KS <= kG4MaxKS, "a pass holds at most 56 rows");
     constexpr int kTile = g4_tile_doubles(KS);
-    KTL(0);
-    const int ctrl_done = S.ctrl->done, ctrl_cur = S.ctrl->cur;
+    constexpr int NQ = CP ? 2 : 3;              // instructions per four rows
 #ifdef TSCM_WAVE_TIMELINE
     const long long tl_t0 = wall_clock64();
     const int tl_iter = S.ctrl->iteration;
@@ -153,7 +179,9 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     double *Fl = lds;                          // the tile: holds the u-rows, then the v-rows
     double *bxy = lds + kTile;
     const int lane = threadIdx.x & 63;
+#ifdef TSCM_WAVE_TIMELINE
     const int chunk = blockIdx.x * 4 + wave;
+#endif
     // Head in TWO dependent round trips (round 5; it was six: control block | board points, twice | view range | camera
     // constants | view metadata | observations -- 7 us from a wave's start to its first MFMA, with every wave of the chip in
     // the same place at the same time).  Trip 1, scalar: the control block and the chunk's 16-byte descriptor; vector: the
@@ -161,12 +189,10 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     // 64 views, the first view's observations (all 64 lanes: a lane without a corner reads the next view's value or, past
     // the end, zero -- the offset is in the vector operand, which the range check covers -- and never uses it), and one dword of every 64-byte line of the first view's and of the camera's
     // constants through the SCALAR cache, so that the geometry's scalar loads hit there.
-    const v4i cd = *(const v4i __attribute__((address_space(4))) *)(const void *)(P.chunk_desc + chunk);
-    const int cam = cd[0], vb = cd[1], ve = cd[2];
-    const d2 my_xy = *reinterpret_cast<const d2 *>(P.board_xy + 2 * min(lane, P.n_points - 1));
+    const int cam = cd[0] & kChunkCamMask, vb = cd[1], ve = cd[2];
     double *const cc_buf[2] = { S.cconst[0], S.cconst[1] };
     double *const rec_buf[2] = { S.rec[0], S.rec[1] };
-    double camU[3] = { 0.0, 0.0, 0.0 }, camV[3] = { 0.0, 0.0, 0.0 };
+    double camU[NQ] = {}, camV[NQ] = {};
     for (int i = lane; i < KS * kG4Stride; i += 64) Fl[i] = 0.0;     // rows of lanes without a corner, the zero column, the padding
     int prev_nv = 0;
     double pf_u = 0.0, pf_v = 0.0;
@@ -195,9 +221,10 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     // as an MFMA lane: k = i = lane / 16, c16 = 4 b + j
     const int li = lane >> 4, c16 = lane & 15, lb = c16 >> 2, lj = c16 & 3;
     const unsigned lds0 = lds_addr(Fl);
-    const unsigned aN = lds0 + 8u * (unsigned)g4_elem(c16, li);
-    const unsigned aR = lds0 + 8u * (unsigned)g4_elem((c16 + 4) & 15, li);
-    const unsigned aB = lds0 + 8u * (unsigned)g4_elem(4 * g4_cgroup(lb, 2) + lj, li);
+    // (CP: aN the A operand of both instructions, aR and aB their B operands)
+    const unsigned aN = lds0 + 8u * (unsigned)g4_elem(CP && lb == 2 ? 12 + lj : c16, li);
+    const unsigned aR = lds0 + 8u * (unsigned)g4_elem(CP ? (lb == 2 ? lj : c16) : (c16 + 4) & 15, li);
+    const unsigned aB = lds0 + 8u * (unsigned)g4_elem(CP ? 4 + lj : 4 * g4_cgroup(lb, 2) + lj, li);
     // R_c[m][j] of this lane's quad position (t_b rows), fixed for the chunk
     const double rc0 = lj == 0 ? ccs[0] : lj == 1 ? ccs[1] : ccs[2];
     const double rc1 = lj == 0 ? ccs[3] : lj == 1 ? ccs[4] : ccs[5];
@@ -215,6 +242,15 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         if (b == 1 && j < 3) o1w = W(f1, 3 + j);                             // t_b rows x (t_c | alpha)
         if (b == 0 && i < 3) o2 = W(f1j, i);                                 // w_b rows x (t_c | alpha)
         if (b == 0 && i == 3 && j < 3) { o2 = W(kFR, 3 + j); o7b = 8u * (unsigned)(3 + j); }       // t_b rows x r (G region)
+        if constexpr (CP) {
+            // seven stores (o5, o6 unused): o2 also takes the rows of group 3' -- block 2 x w_b (held transposed), block 3 x t_b --,
+            // the u-part where the row is one* or f*, and o4 their v-part in the next record column (cy, fy)
+            const int f3c = g4_wcol_cp(i);
+            if (b == 2 && j < 3) o2 = W(f3c, j);
+            if (b == 3 && j < 3) o2 = W(f3c, 3 + j);
+            if (b == 2 && j < 3 && (i == 0 || i == 3)) o4 = W(f3c + 1, j);
+            if (b == 3 && j < 3 && (i == 0 || i == 3)) o4 = W(f3c + 1, 3 + j);
+        } else {
         if (b == 3 && j < 3 && i < 3) o2 = W(f3, j);                         // w_b rows x (one* | xi | lambda), held transposed
         if (b == 0 && i < 3) o4 = W(f2j, i);                                 // w_b rows x (w_c | f*)
         if (b == 2 && j < 3) o4 = W(f2, 3 + j);                              // t_b rows x (w_c | f*)
@@ -222,6 +258,14 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         if (b == 3 && i == 0 && j < 3) { o5 = W(9, j); o6 = W(9, 3 + j); }   // v-row parts: cy
         if (b == 0 && j == 3 && i < 3) o6 = W(7, i);                         // ... fy
         if (b == 2 && i == 3 && j < 3) o6 = W(7, 3 + j);
+        }
+    }
+    // (the E and G regions' start goes into the lane's own offset, once: two scalar registers and two additions per view less)
+    {
+        const unsigned baseE = 8u * (unsigned)kRecW * (unsigned)P.V, baseG = 8u * (unsigned)(kRecW + kRecE) * (unsigned)P.V;
+        if (o1e != BAD) { o1e += baseE; o3e += baseE; }
+        if (o7a != BAD) o7a += baseG;
+        if (o7b != BAD) o7b += baseG;
     }
     if (lane < P.n_points) *reinterpret_cast<d2 *>(bxy + 2 * lane) = my_xy;
     if constexpr (MULTI) {
@@ -265,7 +309,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
 #endif
         const cptr4 vcs = (cptr4)(S.vconst + (size_t)kVStride * view);
         auto VC = [&](int k) { return vcs[k]; };
-        double accU[3] = { 0.0, 0.0, 0.0 }, accV[3] = { 0.0, 0.0, 0.0 };
+        double accU[NQ] = {}, accV[NQ] = {};
         int pbv = 0;                            // first corner of the pass (MULTI)
         do {
         const int pb = MULTI ? pbv : 0;
@@ -279,7 +323,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
             const double x = bxy[2 * (pb + lane)], y = bxy[2 * (pb + lane) + 1];
             // semantic column -> tile column of this kernel
             constexpr int tcol[15] = { kG4Wb, kG4Wb + 1, kG4Wb + 2, kG4Tc, kG4Tc + 1, kG4Tc + 2, kG4Wc, kG4Wc + 1, kG4Wc + 2,
-                                       kG4F, kG4One, kG4Xi, kG4Lam, kG4Al, kG4R };
+                                       CP ? kG4FCp : kG4F, kG4One, kG4Xi, kG4Lam, kG4Al, kG4R };
             if constexpr (ROBUST) {
                 // the corner's weight from its residual first (corner_residual: the same operations corner_geometry starts
                 // with, merged with them by the compiler), then every entry scaled as it is handed out
@@ -287,9 +331,9 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
                 corner_residual(x, y, pf_u, pf_v, VC, CC, ru, rv);
                 robust_rho(L, ru * ru + rv * rv, rho, w);
                 rho_sum += rho;
-                corner_geometry(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], w * u, w * v); });
+                corner_geometry<!CP>(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], w * u, w * v); });
             } else {
-                corner_geometry(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], u, v); });
+                corner_geometry<!CP>(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], u, v); });
             }
         }
         // rows of lanes that lost their corner: only behind a view (pass) that had more corners -- with the same count from view to
@@ -297,7 +341,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         if (nv < prev_nv) {
             if (!valid && lane < prev_nv) {
 #pragma unroll
-                for (int c = 0; c < kTcols; ++c) (c < 8 ? fu_lo : fu_hi)[4 * c] = 0.0;
+                for (int c = 0; c < 16; ++c) if (g4_live<CP>(c)) (c < 8 ? fu_lo : fu_hi)[4 * c] = 0.0;
             }
         }
         {
@@ -321,16 +365,16 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
 #ifdef TSCM_WAVE_TIMELINE
         if (tl_nv == 1) tl_w[1] = wall_clock64();
 #endif
-        gram4_full<KS, MULTI>(aN, aR, aB, accU);
+        gram4_full<KS, MULTI, NQ>(aN, aR, aB, accU);
         wave_lds_fence();
         TL_STAMP(ts2);
         if (valid) {
 #pragma unroll
-            for (int c = 0; c < kTcols; ++c) (c < 8 ? fu_lo : fu_hi)[4 * c] = fv[c];
+            for (int c = 0; c < 16; ++c) if (g4_live<CP>(c)) (c < 8 ? fu_lo : fu_hi)[4 * c] = fv[c];
         }
         wave_lds_fence();
         TL_STAMP(ts3);
-        gram4_full<KS, MULTI>(aN, aR, aB, accV);
+        gram4_full<KS, MULTI, NQ>(aN, aR, aB, accV);
         TL_STAMP(ts4);
         TL_ADD(0, ts0, ts1); TL_ADD(1, ts1, ts2); TL_ADD(2, ts2, ts3); TL_ADD(3, ts3, ts4);
         pbv += per;
@@ -338,20 +382,38 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
         TL_STAMP(ts4e);
         asm volatile("" :: "v"(warm));       // the warming load retires here, before this view's record stores
 #pragma unroll
-        for (int q = 0; q < 3; ++q) { camU[q] += accU[q]; camV[q] += accV[q]; }
+        for (int q = 0; q < NQ; ++q) { camU[q] += accU[q]; camV[q] += accV[q]; }
         // ---- epilogue: the view's record (same values, same operation order as store_view_record) ------------------
         {
             const unsigned slot = (unsigned)__builtin_amdgcn_readlane(m_slot, view - vbase);
-            const unsigned offW = 8u * (unsigned)kRecW * slot, offE = 8u * ((unsigned)kRecW * (unsigned)P.V + (unsigned)kRecE * slot);
-            const double T0 = accU[0] + accV[0], T1 = accU[1] + accV[1], T2 = accU[2] + accV[2];
+            const unsigned offW = 8u * (unsigned)kRecW * slot, offE = 8u * (unsigned)kRecE * slot, offG = 8u * (unsigned)kRecG * slot;
+            if constexpr (CP) {
+            // The same scheme as below with two tiles.  The t_b rows: block 1 stores those of T0 (o1w), blocks 0 and 3 those of
+            // T1; the rows of group 3' are T0 in block 2 (x w_b) and tb(T1) in block 3 (x t_b), and their rows 0 (one*) and 3 (f*)
+            // leave as u-part and v-part = total - u-part.  The W columns of w_c and their E^T-side rows are not written: both
+            // record buffers are zero from the solver's creation on.
+            const double T0 = accU[0] + accV[0], T1 = accU[1] + accV[1];
+            const double X = lane_pick<0xF, 0x2>(T1, T0);
+            const double tbX = quad_tb(X, rc0, rc1, rc2), tbU1 = quad_tb(accU[1], rc0, rc1, rc2);
+            buf_store_f64(r_rec, o1e, offE, T0);
+            buf_store_f64(r_rec, o7a, offG, T0);
+            // Z: the total, ZU: the u-part of what blocks 2 and 3 store (Z in block 0: its t_b rows)
+            const double Z = lane_pick<0xF, 0x9>(T0, tbX), ZU = lane_pick<0xF, 0x8>(accU[0], tbU1);
+            buf_store_f64(r_rec, o4, offW, Z - ZU);
+            buf_store_f64(r_rec, o1w, offW, lane_pick<0xF, 0x2>(T0, tbX));
+            // o2: block 0 rows 0-2 T1, row 3 its t_b rows; blocks 2 and 3 rows 1, 2 the total, rows 0, 3 the u-part
+            buf_store_f64(r_rec, o2, offW, lane_pick<0x9, 0xC>(lane_pick<0x7, 0x1>(Z, T1), ZU));
+            buf_store_f64(r_rec, o3e, offE, tbX);
+            buf_store_f64(r_rec, o7b, offG, tbX);
+            } else {
+            const double T0 = accU[0] + accV[0], T1 = accU[1] + accV[1], T2 = accU[NQ - 1] + accV[NQ - 1];
             // A lane's block b is its DPP bank and its row i its DPP row: every choice by (b, i) below is a pair of masked moves
             // (lane_pick) -- no compare, no mask in an SGPR pair.  The t_b rows: block 1 stores those of T0 (o1w), block 0 those of
             // T1 (o2, o3e, o7b), blocks 2 and 3 those of T2 (o4, o6), so ONE quad_tb of the block's own T serves all three; the
             // products and FMAs of a stored value are the ones quad_tb(T0 | T1 | T2) performed for it.
             const double X = lane_pick<0xF, 0x1>(lane_pick<0xF, 0x2>(T2, T0), T1);
-            const double tbX = quad_tb(X, rc0, rc1, rc2), tbU2 = quad_tb(accU[2], rc0, rc1, rc2);
+            const double tbX = quad_tb(X, rc0, rc1, rc2), tbU2 = quad_tb(accU[NQ - 1], rc0, rc1, rc2);
             // (a pick overwrites its `keep` operand: each one below is the last use of that value, so none costs a copy)
-            const unsigned offG = 8u * ((unsigned)(kRecW + kRecE) * (unsigned)P.V + (unsigned)kRecG * slot);
             buf_store_f64(r_rec, o1e, offE, T0);
             buf_store_f64(r_rec, o7a, offG, T0);          // E^T r once more, compact (k_reduce_stats reads it there)
             buf_store_f64(r_rec, o1w, offW, lane_pick<0xF, 0x2>(T0, tbX));
@@ -360,10 +422,11 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
             buf_store_f64(r_rec, o2, offW, lane_pick<0x1, 0x8>(lane_pick<0x8, 0xF>(T1, tbX), accU[1]));
             buf_store_f64(r_rec, o3e, offE, tbX);
             buf_store_f64(r_rec, o7b, offG, tbX);
-            const double a4 = lane_pick<0xF, 0xE>(T2, tbX), u4 = lane_pick<0xF, 0x1>(tbU2, accU[2]);
+            const double a4 = lane_pick<0xF, 0xE>(T2, tbX), u4 = lane_pick<0xF, 0x1>(tbU2, accU[NQ - 1]);
             // the lanes that store the u-part through o4 are the lanes with an entry in o6 (which takes the v-part, a4 - u4)
             buf_store_f64(r_rec, o4, offW, (int)o6 >= 0 ? u4 : a4);
             buf_store_f64(r_rec, o6, offW, a4 - u4);
+            }
         }
 #ifdef TSCM_WAVE_TIMELINE
         { TL_STAMP(ts5); TL_ADD(4, ts4e, ts5); }
@@ -390,9 +453,15 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     // the camera tile leaves in the 16x16 layout and column numbering of k_eval_gram (both triangles: every entry is
     // written by the lane that holds it and, mirrored, by the same lane; the doubly held pairs carry the same bits)
     wave_lds_fence();
+    if constexpr (CP) {
+        // ... with zeros in the rows and columns of w_c
+        for (int i = lane; i < 512; i += 64) lds[i] = 0.0;
+        wave_lds_fence();
+    }
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const int r = g4_old_col(4 * lb + li), c = g4_old_col(4 * g4_cgroup(lb, q) + lj);
+    for (int q = 0; q < NQ; ++q) {
+        const int rg = CP && lb == 2 ? 3 : lb, cg = !CP ? g4_cgroup(lb, q) : q == 1 ? 1 : lb == 2 ? 0 : lb;
+        const int r = g4_old_col_of<CP>(4 * rg + li), c = g4_old_col_of<CP>(4 * cg + lj);
         lds[16 * r + c] = camU[q]; lds[16 * c + r] = camU[q];
         lds[256 + 16 * r + c] = camV[q]; lds[256 + 16 * c + r] = camV[q];
     }
@@ -407,4 +476,21 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
 #ifdef TSCM_WAVE_TIMELINE
     if (lane == 0 && tl_iter == 5 && cand && chunk < kTimelineWaves) g_tlv[(size_t)(4 + kTlViews) * chunk + 2] = wall_clock64();     // [2]: the wave's very end (camera tile handed on)
 #endif
+}
+
+// KS: k-steps of a pass; MULTI, ROBUST: see eval_gram4_wave.  cand: kEvalCand | kEvalSkipConst.
+template <int KS, bool MULTI, bool ROBUST = false>
+__global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S, int cand, LossArg L)
+{
+    KTL(0);
+    const int ctrl_done = S.ctrl->done, ctrl_cur = S.ctrl->cur;
+    const int chunk = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const v4i cd = *(const v4i __attribute__((address_space(4))) *)(const void *)(P.chunk_desc + chunk);
+    const d2 my_xy = *reinterpret_cast<const d2 *>(P.board_xy + 2 * min((int)(threadIdx.x & 63), P.n_points - 1));
+    // one camera per chunk and whole workgroups per camera (plan_layout): the branch is uniform in the workgroup
+#ifndef TSCM_G4_FULL_PATH
+    if ((cand & kEvalSkipConst) && (cd[0] & kChunkConstPose)) eval_gram4_wave<KS, MULTI, ROBUST, true>(P, S, cand & kEvalCand, L, cd, ctrl_done, ctrl_cur, my_xy);
+    else
+#endif
+        eval_gram4_wave<KS, MULTI, ROBUST, false>(P, S, cand & kEvalCand, L, cd, ctrl_done, ctrl_cur, my_xy);
 }

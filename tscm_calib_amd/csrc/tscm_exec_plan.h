@@ -61,6 +61,10 @@ struct ExecPlan {
     bool comm = false;                  // the communicator path: two all-reduces per iteration
     Gram gram = Gram::G4;
     bool robust = false;                // the ROBUST instantiation of the Gram kernel (a loss)
+    // k_eval_gram4 leaves out the rotation columns w_c of a camera whose pose block is constant (L.cam_const: no pose column
+    // in the reduced system, plan_columns): what a solve does.  The inspection entries (tscm_eval_normal_equations*) return
+    // every column and plan with inspect = true; the 16x16 and fp32 kernels always form all columns
+    bool skip_const_pose = false;
     EvalTail tail = EvalTail::ReduceControl;
     bool ctl_in_schur = false;          // the control step of an evaluation is taken in the head of the next k_schur_gram
     bool stats_ride = false;            // a candidate's reductions ride in it (tail == Ride)
@@ -100,12 +104,13 @@ TSCM_PLAN_FN G4Plan g4_plan(int n_points)
 }
 
 inline ExecPlan plan_exec(const Layout &L, int C, int n_act, int comm_kind, int exec_flags, int jacobian_fp32, int loss_kind, int rp,
-                          const ExecDevice &dev)
+                          const ExecDevice &dev, bool inspect = false)
 {
     ExecPlan p;
     p.comm = uses_comm(comm_kind, exec_flags);
     p.gram = plan_gram(exec_flags, jacobian_fp32, rp);
     p.robust = loss_kind != TSCM_LOSS_NONE;
+    p.skip_const_pose = !inspect && p.gram == Gram::G4;
     // one GPU with <= 8 cameras (finish_evaluation's LDS fits k_schur_gram's) or a communicator; exactly one Schur kernel
     // per iteration.  (A grid of several rounds -- config 5 on one GPU: 1256 workgroups, 2.5 rounds -- pays the step in its
     // first round only: the later rounds read the outcome workgroup 0 publishes)

@@ -98,7 +98,9 @@ __device__ __forceinline__ void store_view_record(__amdgpu_buffer_rsrc_t r_rec, 
 // ---------------------------------------------------------------------------------------------
 enum GCol { gcWb0 = 0, gcWb1, gcWb2, gcTc0, gcTc1, gcTc2, gcWc0, gcWc1, gcWc2, gcF, gcOne, gcXi, gcLam, gcAl, gcR };
 
-template <typename FV, typename FC, typename FP>
+// WC = false (k_eval_gram4's path for a camera whose pose is held constant): the camera-rotation columns gcWc0..2 are neither
+// computed nor handed out; every other entry comes from the same operations in the same order.
+template <bool WC = true, typename FV, typename FC, typename FP>
 __device__ __forceinline__ void corner_geometry(double x, double y, double ou, double ov, FV VC, FC CC, FP PUT)
 {
     const double X = fma(x, VC(0), fma(y, VC(3), VC(6)));
@@ -137,7 +139,7 @@ __device__ __forceinline__ void corner_geometry(double x, double y, double ou, d
         PUT(gcWb0 + kk, n00 * h0 + n01 * h1 + n02 * h2, n10 * h0 + n11 * h1 + n12 * h2);
     }
     // w_c: -A (dR_c/dw_k P_w) = a_k . (Q' x n)
-    {
+    if constexpr (WC) {
         double Q0 = X - CC(9), Q1 = Y - CC(10), Q2 = Z - CC(11);
         if (CC(24) != 0.0) {                  // small-angle branch of the camera rotation (wave-uniform): Q' = Q - w x Q
             const double w0 = CC(21), w1 = CC(22), w2 = CC(23);

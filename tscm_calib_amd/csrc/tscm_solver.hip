@@ -136,6 +136,7 @@ struct tscm_solver {
     Layout L;                           // host copy of the layout (tscm_layout.h: plan_layout)
     int C = 0, B = 0, V = 0, N = 0, n_points = 0, n_pad = 0;     // B, V, N: this rank's boards / views / corners (L.B, L.V, L.N)
     int rank = 0, world = 1;
+    int n_views = 0;                    // views of the caller's problem (this rank's with corners: V)
     hipStream_t own_stream = nullptr;   // `stream` is replaced by the group's while a local group solve runs
     bool mono = false;
     // caller-owned parameter arrays (host)
@@ -360,7 +361,7 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     tscm_solver *s = sp.get();
     s->device = device;
     s->rank = rank; s->world = world;
-    s->C = p->n_cameras; s->n_points = p->n_points; s->mono = p->mono != 0;
+    s->C = p->n_cameras; s->n_points = p->n_points; s->mono = p->mono != 0; s->n_views = p->n_views;
     s->n_pad = 16 * s->C;
     s->h_cam_rt = p->cam_rt; s->h_intr = p->intr; s->h_board_rt = p->board_rt;
     HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
@@ -426,7 +427,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         for (size_t i = 0; i < h.size(); ++i) d[i] = make_int4(h[i].x, h[i].y, h[i].z, h[i].w);
         return d;
     };
-    const std::vector<int4> chunk_desc = int4s(L.chunk_desc), bc_desc = int4s(L.bc_desc);
+    std::vector<int4> chunk_desc = int4s(L.chunk_desc);
+    const std::vector<int4> bc_desc = int4s(L.bc_desc);
+    for (int4 &d : chunk_desc) if (L.cam_const[d.x]) d.x |= kChunkConstPose;     // (k_eval_gram4's constant-pose path)
     const std::vector<short> bid_lut(L.bid_of.begin(), L.bid_of.end());
     DevProblem &P = s->P;
     DevState &S = s->S;
@@ -477,6 +480,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     al(&S.stats_count, 64); al(&S.stats_flag, 64);      // (256 bytes each: lines of their own)
     HIP_TRY(he);
     for (int *flag : { S.t_count, S.y_flag, S.fac_fail }) HIP_TRY(hipMemset(flag, 0, sizeof(int)));
+    // (the W columns of w_c of a constant camera's views are never written by k_eval_gram4's constant-pose path: zero, not
+    // uninitialised, in front of the back-substitution's zero step)
+    for (int k = 0; k < 2; ++k) if (V) HIP_TRY(hipMemset(S.rec[k], 0, sizeof(double) * (size_t)kRec * V));
     HIP_TRY(hipMemset(S.stats_count, 0, 256)); HIP_TRY(hipMemset(S.stats_flag, 0, 256));
     HIP_TRY(hipMemset(S.ctl_pub, 0, sizeof(CtlPub)));
     HIP_TRY(hipMemset(S.T, 0, sizeof(double) * 256 * (size_t)L.n_bids));
@@ -631,7 +637,8 @@ static int launch_eval(tscm_solver *s, int cand)
     // (a loss: the ROBUST instantiation; the 16x16 kernel has none -- refused before anything is launched)
     const bool robust = s->xp.robust;
     if (s->xp.gram == Gram::F32) launch_eval_kernel(robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
-    else if (s->xp.gram == Gram::G4) launch_eval_kernel(robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand, s->loss);
+    else if (s->xp.gram == Gram::G4)
+        launch_eval_kernel(robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand | (s->xp.skip_const_pose ? kEvalSkipConst : 0), s->loss);
     else if (s->xp.gram == Gram::G16Pitch58) launch_eval_kernel(k_eval_gram<58>, grid, s->lds_eval, s, e0, e1, cand);
     else launch_eval_kernel(k_eval_gram<0>, grid, s->lds_eval, s, e0, e1, cand);
     return 0;
@@ -1369,19 +1376,12 @@ extern "C" int tscm_eval_normal_equations(const tscm_problem *p, int device, dou
 // the Gram kernel is the one a solve with these options runs: jacobian_fp32 -> k_eval_gram_f32, TSCM_EXEC_GRAM_16X16 ->
 // k_eval_gram, k_eval_gram4 otherwise (the other flags do not touch the evaluation).  Every kernel writes the same fp64
 // record layout, so the extraction below is shared
-static int eval_normal_equations(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *board_gram,
-                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+// as_solved: the launch a solve makes (ExecPlan::skip_const_pose); otherwise every column (inspection)
+static int solver_normal_equations(tscm_solver *s, const tscm_options &opt, bool as_solved, double *board_gram, double *board_grad,
+                                   double *view_cross, double *cam_gram, double *cam_grad, double *cost)
 {
-    tscm_options opt;
-    int rc = read_options(opt_in, p ? p->mono : 0, opt);
-    if (rc) return rc;
-    opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
-    if ((rc = check_options(opt, loss.kind))) return rc;
-    SolverPtr sp;
-    if ((rc = create_scoped(p, device, sp))) return rc;
-    tscm_solver *s = sp.get();
-    s->loss = loss;
-    s->xp = plan_exec(s->L, s->C, s->P.n_act, kCommNone, opt.exec_flags, opt.jacobian_fp32, loss.kind, s->P.rp, s->dev);     // (its Gram kernel)
+    int rc;
+    s->xp = plan_exec(s->L, s->C, s->P.n_act, kCommNone, opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev, !as_solved);     // (its Gram kernel)
     if ((rc = prepare_eval(s, s->xp.f32() ? 1 : 0))) return rc;
     const DevProblem &P = s->P;
     DevState &S = s->S;
@@ -1396,7 +1396,7 @@ static int eval_normal_equations(const tscm_problem *p, int device, const tscm_o
     HIP_TRY(hipMemcpy(cc.data(), S.cconst[0], sizeof(double) * cc.size(), hipMemcpyDeviceToHost));
     if (board_gram) std::memset(board_gram, 0, sizeof(double) * 36 * (size_t)s->B);
     if (board_grad) std::memset(board_grad, 0, sizeof(double) * 6 * (size_t)s->B);
-    if (view_cross) std::memset(view_cross, 0, sizeof(double) * 90 * (size_t)p->n_views);
+    if (view_cross) std::memset(view_cross, 0, sizeof(double) * 90 * (size_t)s->n_views);
     for (int dv = 0; dv < s->V; ++dv) {
         // the view's record: W = E^T [F | r] (14 columns x 6 rows, column-major), E = E^T E_wb (3 columns x 6 rows); the
         // t_b x t_b block of E^T E follows from the t_c columns of W and the camera rotation (tb_tb), the block above
@@ -1426,6 +1426,36 @@ static int eval_normal_equations(const tscm_problem *p, int device, const tscm_o
     }
     if (cost) *cost = c;
     return 0;
+}
+
+static int eval_normal_equations(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *board_gram,
+                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+{
+    tscm_options opt;
+    int rc = read_options(opt_in, p ? p->mono : 0, opt);
+    if (rc) return rc;
+    opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
+    if ((rc = check_options(opt, loss.kind))) return rc;
+    SolverPtr sp;
+    if ((rc = create_scoped(p, device, sp))) return rc;
+    sp->loss = loss;
+    return solver_normal_equations(sp.get(), opt, false, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+}
+
+extern "C" int tscm_solver_eval_normal_equations(tscm_solver *s, const tscm_options *opt_in, int as_solved, double *board_gram,
+                                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+{
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    if (s->world != 1) return fail(TSCM_E_UNSUPPORTED, "tscm_solver_eval_normal_equations: a sharded solver holds a part of the problem");
+    tscm_options opt;
+    int rc = read_options(opt_in, s->mono ? 1 : 0, opt);
+    if (rc) return rc;
+    opt.max_num_iterations = 0;
+    if ((rc = check_options(opt, s->loss.kind))) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    rc = solver_normal_equations(s, opt, as_solved != 0, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+    s->xp = ExecPlan{};                 // (per solve: planned again from the options of the next one)
+    return rc;
 }
 
 extern "C" int tscm_eval_normal_equations_ex(const tscm_problem *p, int device, const tscm_options *opt, double *board_gram,

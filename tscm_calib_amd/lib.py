@@ -187,6 +187,7 @@ EXPORTS = [
     "tscm_estimate_extrinsic", "tscm_estimate_focal_rows", "tscm_estimate_extrinsic_stages", "tscm_corners_write", "tscm_corners_read", "tscm_corners_free",
     "tscm_detect_corners", "tscm_detect_corners_batch", "tscm_corner_planes_batch", "tscm_corner_candidates_free", "tscm_chessboards_from_corners", "tscm_chessboards_free", "tscm_remap",
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
+    "tscm_solver_eval_normal_equations",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
@@ -262,6 +263,7 @@ def lib():
     L.tscm_solve_robust.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), C.c_int, C.c_double, C.POINTER(CSummary)]
     L.tscm_eval_normal_equations_robust.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), C.c_int, C.c_double, dp, dp, dp, dp, dp, dp]
     L.tscm_eval_step_robust.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
+    L.tscm_solver_eval_normal_equations.argtypes = [vp, C.POINTER(COptions), C.c_int, dp, dp, dp, dp, dp, dp]
     usp = C.POINTER(C.c_ushort)
     L.tscm_solver_set_fixed_intrinsics.argtypes = [vp, usp]
     L.tscm_solve_fixed.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), usp, C.c_int, C.c_double, C.POINTER(CSummary)]
