@@ -161,15 +161,19 @@ def test_refusals_that_need_a_handle(hip_device):
     d = dst.ctypes.data_as(ub)
     with _composer(n, ch, pw, ph, "feather", 0, True, False, hip_device) as c:
         h = c._handle
-        for gains, text in (((0, 256), b"gain_q8[0]"), ((256, 4096), b"gain_q8[1]")):
+        for gains, text, full in (((0, 256), b"gain_q8[0]", b"gain_q8[0] = 0 outside 1..4095"), ((256, 4096), b"gain_q8[1]", b"gain_q8[1] = 4096 outside 1..4095")):
             g = np.array(gains, np.uint16)
             assert L.tscm_panorama_compose(h, ptrs, SRC_W, lib.ushort_ptr(g), d, pw, None, None) == -1
             assert text in L.tscm_last_error()
+            assert L.tscm_last_error() == full               # the sentences the sweep's composer shares: the whole text
         assert L.tscm_panorama_compose(h, ptrs, SRC_W - 1, None, d, pw, None, None) == -1 and b"stride" in L.tscm_last_error()
+        assert L.tscm_last_error() == b"stride %d < width * channels = %d" % (SRC_W - 1, SRC_W)
         assert L.tscm_panorama_compose(h, ptrs, SRC_W, None, d, pw - 1, None, None) == -1 and b"dst_stride" in L.tscm_last_error()
         assert L.tscm_panorama_compose(h, ptrs, SRC_W, None, None, pw, None, None) == -1 and b"dst" in L.tscm_last_error()
         holed = (C.c_void_p * n)(imgs[0].ctypes.data, None)
         assert L.tscm_panorama_compose(h, holed, SRC_W, None, d, pw, None, None) == -1 and b"images[1]" in L.tscm_last_error()
+        assert L.tscm_last_error() == b"images[1] is NULL"
+        assert L.tscm_panorama_compose(h, None, SRC_W, None, d, pw, None, None) == -1 and L.tscm_last_error() == b"images is NULL"
         assert L.tscm_panorama_overlap(h, ptrs, SRC_W, None, None) == -1 and b"count" in L.tscm_last_error()
         pyr = np.zeros(8 * pw * ph, np.int16).ctypes.data_as(C.POINTER(C.c_short))
         assert L.tscm_panorama_stages(h, ptrs, SRC_W, None, None, None, None, None, None, pyr) == -1 and b"blend_pyramid" in L.tscm_last_error()

@@ -209,32 +209,37 @@ def test_refusals_that_need_a_handle(hip_device):
     o, ix = out.ctypes.data_as(C.POINTER(C.c_ubyte)), idx.ctypes.data_as(C.POINTER(C.c_short))
     mk = lambda **kw: C.byref(sweep.compose_params(**dict(dict(mode="seam"), **kw)))
 
-    def refused(word, images=ptrs, stride=SRC_W, ch=1, index=ix, istride=pw, params=None, gains=None, dst=o, dstride=pw):
+    def refused(word, images=ptrs, stride=SRC_W, ch=1, index=ix, istride=pw, params=None, gains=None, dst=o, dstride=pw, full=None):
         rc = L.tscm_sweep_compose(h, images, stride, ch, index, istride, params or mk(), gains, dst, dstride, None, None)
         assert rc == -1 and word in L.tscm_last_error(), (word, rc, L.tscm_last_error())
+        assert full is None or L.tscm_last_error() == full, (full, L.tscm_last_error())      # the sentences shared with other entry points: the whole text
 
     with sweep.Sweeper.from_tables(mx, my, (SRC_W, SRC_H), device=hip_device) as s:
         h = s._handle
-        refused(b"index16 is NULL", index=None)                       # no frame yet
-        refused(b"images is NULL", images=None)
-        refused(b"images[1]", images=(C.c_void_p * n)(imgs[0].ctypes.data, None))
+        refused(b"index16 is NULL", index=None, full=b"index16 is NULL and the handle has not run tscm_sweep_depth yet")       # no frame yet
+        refused(b"images is NULL", images=None, full=b"images is NULL")
+        refused(b"images[1]", images=(C.c_void_p * n)(imgs[0].ctypes.data, None), full=b"images[1] is NULL")
         refused(b"channels", ch=2)
         refused(b"channels", ch=4)
-        refused(b"stride", stride=SRC_W - 1)
-        refused(b"stride", stride=3 * SRC_W - 1, ch=3)
+        refused(b"images is NULL", images=None, ch=2, full=b"images is NULL")          # two faults: the images come first, then channels, then stride
+        refused(b"images[1]", images=(C.c_void_p * n)(imgs[0].ctypes.data, None), ch=2, full=b"images[1] is NULL")
+        refused(b"channels", ch=2, stride=0, full=b"channels 2 is not 1 or 3")
+        refused(b"stride", stride=SRC_W - 1, full=b"stride %d < width * channels = %d" % (SRC_W - 1, SRC_W))
+        refused(b"stride", stride=3 * SRC_W - 1, ch=3, full=b"stride %d < width * channels = %d" % (3 * SRC_W - 1, 3 * SRC_W))
         assert L.tscm_sweep_compose(h, ptrs, SRC_W, 1, ix, pw, None, None, o, pw, None, None) == -1 and b"params is NULL" in L.tscm_last_error()
         bad = sweep.compose_params(mode="seam")
         bad.struct_size -= 4
-        refused(b"struct_size", params=C.byref(bad))
+        refused(b"struct_size", params=C.byref(bad), full=b"params: struct_size %d is not sizeof(tscm_sweep_compose_params) = %d"
+                % (bad.struct_size, C.sizeof(lib.CSweepComposeParams)))
         refused(b"unknown mode", params=mk(mode=3))
         refused(b"levels", params=mk(mode="multiband", levels=0))
         refused(b"levels", params=mk(mode="multiband", levels=7))
         refused(b"pano_w", params=mk(mode="multiband", levels=4))      # 72 is no multiple of 16
         refused(b"fallback_index", params=mk(fallback_index=-1))
         refused(b"fallback_index", params=mk(fallback_index=D))
-        refused(b"index_stride", istride=pw - 1)
-        refused(b"gain_q8[1]", gains=(C.c_ushort * n)(256, 0))
-        refused(b"gain_q8[0]", gains=(C.c_ushort * n)(4096, 256))
+        refused(b"index_stride", istride=pw - 1, full=b"index_stride %d < pano_w %d" % (pw - 1, pw))
+        refused(b"gain_q8[1]", gains=(C.c_ushort * n)(256, 0), full=b"gain_q8[1] = 0 outside 1..4095")
+        refused(b"gain_q8[0]", gains=(C.c_ushort * n)(4096, 256), full=b"gain_q8[0] = 4096 outside 1..4095")
         refused(b"dst is NULL", dst=None)
         refused(b"dst_stride", dstride=pw - 1)
         refused(b"dst_stride", dstride=3 * pw - 1, ch=3, stride=3 * SRC_W)

@@ -225,7 +225,9 @@ def test_refusals_that_need_a_handle(hip_device):
         for check in (refused, pass_refused):
             check(b"index16 is NULL", index=None)                     # no frame yet
             check(b"index_stride", istride=pw - 1)
+            assert L.tscm_last_error() == b"index_stride %d < pano_w %d" % (pw - 1, pw)           # shared sentences: the whole text
             check(b"struct_size", vparams=C.byref(bad))
+            assert L.tscm_last_error() == b"vparams: struct_size %d is not sizeof(tscm_sweep_visibility_params) = %d" % (bad.struct_size, C.sizeof(lib.CSweepVisibilityParams))
             check(b"cell_shift", vparams=mv(cell_shift=-1))
             check(b"cell_shift", vparams=mv(cell_shift=9))
             check(b"tolerance", vparams=mv(tolerance=-1))

@@ -668,9 +668,9 @@ struct CornerBuffers {
 // extremes -> row pass -> column pass -> k_corner_metric, with the kernel choice by tap count and width.  Both
 // tscm_detect_corners_batch and tscm_corner_planes_batch run it, so the planes the latter returns are the ones the
 // suppression reads.  The caller holds arena.mu and has checked the arguments; tab (may be NULL) is uploaded with the
-// taps, e0 (may be NULL) is recorded in front of the first kernel.
+// taps, timer (may be NULL) gets its mark 0 in front of the first kernel.
 int corner_front(const unsigned char *const *images, int n_images, int width, int height, int stride, int sigma, Arena &arena,
-                 const DescribeTables *tab, hipEvent_t e0, CornerBuffers &d)
+                 const DescribeTables *tab, tscm::EventSpan *timer, CornerBuffers &d)
 {
     const int ntap = 7 * sigma + 1;
     std::vector<double> taps(ntap);
@@ -719,7 +719,7 @@ int corner_front(const unsigned char *const *images, int n_images, int width, in
     }
     HIP_TRY(hipMemset(d.count, 0, sizeof(int) * B));
 
-    if (e0) HIP_TRY(hipEventRecord(e0, nullptr));
+    if (timer) HIP_TRY(timer->mark(0));
     const dim3 grid2((width + 255) / 256, height, n_images);
     if (stride == width)
         hipLaunchKernelGGL(k_grey_extremes_flat, dim3((unsigned)((gbytes + 16383) / 16384), n_images), dim3(256), 0, nullptr, d.gray, gbytes, d.mm);
@@ -815,13 +815,10 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
     Arena &arena = g_arena[device];
     std::lock_guard<std::mutex> lock(arena.mu);
     const size_t B = (size_t)n_images;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    tscm::EventSpan timer;
+    HIP_TRY(timer.create(2));
     CornerBuffers d;
-    if (int rc = corner_front(images, n_images, width, height, stride, sigma, arena, tab.data(), e0, d)) {
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        return rc;
-    }
+    if (int rc = corner_front(images, n_images, width, height, stride, sigma, arena, tab.data(), &timer, d)) return rc;
     const size_t N = d.N;
     const int ncell = d.ncell;
     std::vector<int> counts(B, 0);
@@ -835,17 +832,13 @@ extern "C" int tscm_detect_corners_batch(const unsigned char *const *images, int
             hipLaunchKernelGGL(k_corner_describe, dim3(n_top, n_images), dim3(256), 0, nullptr, d.gray, stride, d.mm, ac, d.Ixy, width, height,
                                d.cand, d.tab, d.v, d.score, d.sub, N, ncell, d.count);
     }
-    HIP_TRY(hipEventRecord(e1, nullptr));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    double seconds = 0.0;
+    HIP_TRY(timer.finish(1, nullptr, &seconds));
     // ---- score filter (findCorner.cpp:47-66) per image, order preserved ---------------------------------------------
     for (size_t b = 0; b < B; ++b) {
         tscm_corner_candidates *o = out + b;
         const int n_max = counts[b];
-        o->seconds = ms * 1e-3 / (double)B;          // share of the batch's device time
+        o->seconds = seconds / (double)B;          // share of the batch's device time
         o->n_maxima = n_max;
         std::vector<int> cand(n_max);
         std::vector<double> v(4 * (size_t)n_max), score(n_max), sub(2 * (size_t)n_max);

@@ -364,9 +364,9 @@ static int build_maps_host(const tscm_map_desc *maps, const int *kinds, int n_ma
     } else {
         HIP_TRY(mem.alloc(&d_x, n_elems)); HIP_TRY(mem.alloc(&d_y, n_elems));
     }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
+    EventSpan span;
+    HIP_TRY(span.create(2));
+    HIP_TRY(span.mark(0));
     const dim3 grid((unsigned)((max_quads + 255) / 256), (unsigned)n_maps);
     if (!kinds) {
         if (exact) hipLaunchKernelGGL(k_build_maps<true>, grid, dim3(256), 0, 0, d_maps, d_x, d_y);
@@ -375,13 +375,7 @@ static int build_maps_host(const tscm_map_desc *maps, const int *kinds, int n_ma
         if (exact) hipLaunchKernelGGL(k_build_maps_proj<true>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_x, d_y);
         else hipLaunchKernelGGL(k_build_maps_proj<false>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_x, d_y);
     }
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(hipGetLastError());
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    HIP_TRY(span.finish(1, nullptr, seconds_kernel));
     HIP_TRY(hipMemcpy(mapx, d_x, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(mapy, d_y, sizeof(float) * n_elems, hipMemcpyDeviceToHost));
     return 0;
@@ -455,19 +449,13 @@ extern "C" int tscm_build_sweep_maps(const tscm_map_desc *maps, const int *proje
     HIP_TRY(mem.upload(&d_centers, centers, 3 * (size_t)n_cameras));
     HIP_TRY(mem.upload(&d_inv, inv_distance, (size_t)D));
     HIP_TRY(mem.alloc(&d_x, n_out)); HIP_TRY(mem.alloc(&d_y, n_out));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
+    EventSpan span;
+    HIP_TRY(span.create(2));
+    HIP_TRY(span.mark(0));
     const dim3 grid((unsigned)(((total + 3) / 4 + 255) / 256), (unsigned)planes);
     if (exact) hipLaunchKernelGGL(k_build_maps_sweep<true>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_centers, d_inv, D, d_x, d_y);
     else hipLaunchKernelGGL(k_build_maps_sweep<false>, grid, dim3(256), 0, 0, d_maps, d_kinds, d_centers, d_inv, D, d_x, d_y);
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(hipGetLastError());
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    HIP_TRY(span.finish(1, nullptr, seconds_kernel));
     HIP_TRY(hipMemcpy(mapx, d_x, sizeof(float) * n_out, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(mapy, d_y, sizeof(float) * n_out, hipMemcpyDeviceToHost));
     return 0;
@@ -550,14 +538,14 @@ extern "C" int tscm_remap(const unsigned char *src, int width, int height, int s
     HIP_TRY(mem.upload(&d_src, src, (size_t)stride * height));
     HIP_TRY(mem.alloc(&d_mx, nmap)); HIP_TRY(mem.alloc(&d_my, nmap));
     HIP_TRY(mem.alloc(&d_dst, dst_row * map_height));
-    HIP_TRY(hipMemcpy2D(d_mx, (size_t)map_width * sizeof(float), mapx, (size_t)map_stride * sizeof(float), (size_t)map_width * sizeof(float), map_height, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy2D(d_my, (size_t)map_width * sizeof(float), mapy, (size_t)map_stride * sizeof(float), (size_t)map_width * sizeof(float), map_height, hipMemcpyHostToDevice));
+    HIP_TRY(copy_rows(d_mx, map_width, mapx, map_stride, map_width, map_height, hipMemcpyHostToDevice));
+    HIP_TRY(copy_rows(d_my, map_width, mapy, map_stride, map_width, map_height, hipMemcpyHostToDevice));
     const dim3 grid((map_width + 255) / 256, map_height);
     if (channels == 1)
         hipLaunchKernelGGL(k_remap<1>, grid, dim3(256), 0, nullptr, d_src, width, height, stride, d_mx, d_my, map_width, map_height, 0, d_dst, (int)dst_row);
     else
         hipLaunchKernelGGL(k_remap<3>, grid, dim3(256), 0, nullptr, d_src, width, height, stride, d_mx, d_my, map_width, map_height, to_gray ? 1 : 0, d_dst, (int)dst_row);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, d_dst, dst_row, dst_row, map_height, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_rows(dst, dst_stride, d_dst, dst_row, dst_row, map_height, hipMemcpyDeviceToHost));
     return 0;
 }

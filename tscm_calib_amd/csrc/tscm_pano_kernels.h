@@ -276,15 +276,27 @@ void launch_blend(const PyramidLayout &y, const short *G, const unsigned char *m
     hipLaunchKernelGGL((k_pano_collapse<CH, 1>), tile_grid(y.lw[0], y.lh[0]), dim3(256), 0, 0, B, y.lw[0], y.lh[0], (size_t)0, y.loff[1], y.Sp, wrap, cover, out);
 }
 
-// `planes` device planes of Sp elements -> planes of S elements
+// `planes` device planes of Sp elements -> planes of S elements; host == NULL: the output was not asked for
 template <typename T>
 int download_pyramid(const PyramidLayout &y, const T *dev, int planes, T *host)
 {
+    if (!host) return 0;
     std::vector<T> tmp((size_t)planes * y.Sp);
     HIP_TRY(hipMemcpy(tmp.data(), dev, tmp.size() * sizeof(T), hipMemcpyDeviceToHost));
     for (int q = 0; q < planes; ++q)
         for (int l = 0; l <= y.levels; ++l)
             std::copy_n(tmp.data() + (size_t)q * y.Sp + y.loff[l], (size_t)y.lw[l] * y.lh[l], host + (size_t)q * y.S + y.toff[l]);
+    return 0;
+}
+
+// the per-camera gains of a frame: gain_q8[0 .. n), or 256 (= 1.0) for every camera when it is NULL
+inline int check_gains(const unsigned short *gain_q8, int n, Gains *gains)
+{
+    for (int k = 0; k < kPanoMaxCameras; ++k) gains->g[k] = 256;
+    for (int k = 0; gain_q8 && k < n; ++k) {
+        if (gain_q8[k] < 1 || gain_q8[k] > 4095) return tscm_set_error(TSCM_E_INVALID, "gain_q8[" + std::to_string(k) + "] = " + std::to_string(gain_q8[k]) + " outside 1..4095");
+        gains->g[k] = gain_q8[k];
+    }
     return 0;
 }
 

@@ -36,7 +36,7 @@ namespace {
 constexpr int kMaxCameras = kPanoMaxCameras, kMaxLevels = kPanoMaxLevels;
 
 // ------------------------------------------------------------------------------------------------ sampling
-// tap_weights, sample_px: tscm_remap_sample.h; Gains, apply_gain: tscm_pano_kernels.h
+// pack_record, sample_px: tscm_remap_sample.h; Gains, apply_gain: tscm_pano_kernels.h
 
 // grid (ceil(npix / 256), n) x 256: the packed sample and a_k of camera blockIdx.y; weight_mask bit k: camera k has a
 // weight image (at wimg + k * w * h), otherwise a constant 255 inside the image
@@ -47,22 +47,9 @@ __global__ __launch_bounds__(256) void k_pano_prepare(const float *__restrict__ 
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int k = blockIdx.y;
     if (t >= npix) return;
-    const int sx = __float2int_rn(mapx[k * npix + t] * 32.0f), sy = __float2int_rn(mapy[k * npix + t] * 32.0f);
-    const int ix = max(-32768, min(32767, sx >> 5)), iy = max(-32768, min(32767, sy >> 5));
-    const unsigned frac = (unsigned)(sx & 31) | ((unsigned)(sy & 31) << 5);
-    int wgt[4];
-    tap_weights(frac, wgt);
-    const bool has = (weight_mask >> k) & 1u;
-    const unsigned char *wk = wimg + (size_t)k * w * h;
-    int acc = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int x = ix + (q & 1), y = iy + (q >> 1);
-        if (x >= 0 && x < w && y >= 0 && y < h) acc += wgt[q] * (has ? (int)wk[(size_t)y * w + x] : 255);
-    }
-    const int a = max(0, min(255, (acc + (1 << 14)) >> 15));
-    pack[k * plane + t] = make_uint2(((unsigned)ix & 0xffffu) | ((unsigned)iy << 16), frac | ((unsigned)a << 16));
-    alpha[k * plane + t] = (unsigned char)a;
+    const uint2 rec = pack_record(mapx[k * npix + t], mapy[k * npix + t], wimg + (size_t)k * w * h, (weight_mask >> k) & 1u, w, h);
+    pack[k * plane + t] = rec;
+    alpha[k * plane + t] = (unsigned char)(rec.y >> 16);
 }
 
 // one thread per output pixel: label, coverage, the bit mask of the covering cameras and (mpyr != NULL) level 0 of the masks
@@ -216,8 +203,7 @@ struct tscm_panorama : PyramidLayout {
     unsigned short *mask = nullptr, *wsum = nullptr;
     short *G = nullptr, *B = nullptr;
     unsigned long long *acc = nullptr;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    ~tscm_panorama() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+    EventSpan span;
 };
 
 namespace {
@@ -225,23 +211,15 @@ namespace {
 int check_frame(const tscm_panorama *p, const unsigned char *const *images, int stride, const unsigned short *gain_q8, Gains *gains)
 {
     if (!p) return tscm_set_error(TSCM_E_INVALID, "p is NULL");
-    if (!images) return tscm_set_error(TSCM_E_INVALID, "images is NULL");
-    for (int k = 0; k < p->n; ++k)
-        if (!images[k]) return tscm_set_error(TSCM_E_INVALID, "images[" + std::to_string(k) + "] is NULL");
-    if (stride < p->w * p->ch) return tscm_set_error(TSCM_E_INVALID, "stride " + std::to_string(stride) + " < width * channels = " + std::to_string(p->w * p->ch));
-    for (int k = 0; k < kMaxCameras; ++k) gains->g[k] = 256;
-    for (int k = 0; gain_q8 && k < p->n; ++k) {
-        if (gain_q8[k] < 1 || gain_q8[k] > 4095) return tscm_set_error(TSCM_E_INVALID, "gain_q8[" + std::to_string(k) + "] = " + std::to_string(gain_q8[k]) + " outside 1..4095");
-        gains->g[k] = gain_q8[k];
-    }
-    return 0;
+    if (int rc = check_image_list(images, p->n, stride, p->w * p->ch, "width * channels = ")) return rc;
+    return check_gains(gain_q8, p->n, gains);
 }
 
 int upload_frame(tscm_panorama *p, const unsigned char *const *images, int stride)
 {
     HIP_TRY(hipSetDevice(p->device));
     const size_t row = (size_t)p->w * p->ch;
-    for (int k = 0; k < p->n; ++k) HIP_TRY(hipMemcpy2D(p->img + (size_t)k * row * p->h, row, images[k], (size_t)stride, row, (size_t)p->h, hipMemcpyHostToDevice));
+    for (int k = 0; k < p->n; ++k) HIP_TRY(copy_rows(p->img + (size_t)k * row * p->h, row, images[k], stride, row, p->h, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -276,7 +254,7 @@ int create_on_device(tscm_panorama *p, const unsigned char *const *weights, cons
 {
     const int n = p->n;
     const size_t simg = (size_t)p->w * p->h;
-    HIP_TRY(hipEventCreate(&p->ev[0])); HIP_TRY(hipEventCreate(&p->ev[1]));
+    HIP_TRY(p->span.create(2));
     HIP_TRY(p->mem.alloc(&p->pack, n * p->plane)); HIP_TRY(hipMemset(p->pack, 0, n * p->plane * sizeof(uint2)));
     HIP_TRY(p->mem.alloc(&p->alpha, n * p->plane)); HIP_TRY(hipMemset(p->alpha, 0, n * p->plane));
     HIP_TRY(p->mem.alloc(&p->label, p->plane)); HIP_TRY(hipMemset(p->label, 0xff, p->plane));
@@ -332,8 +310,7 @@ extern "C" int tscm_panorama_create(int n_cameras, int width, int height, int ch
     if (!mapx) return tscm_set_error(TSCM_E_INVALID, "mapx is NULL");
     if (!mapy) return tscm_set_error(TSCM_E_INVALID, "mapy is NULL");
     if (!params) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (params->struct_size != (int)sizeof(tscm_panorama_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(params->struct_size) + " is not sizeof(tscm_panorama_params) = " + std::to_string(sizeof(tscm_panorama_params)));
+    if (int rc = check_struct_size(params, "tscm_panorama_params")) return rc;
     if (n_cameras < 1 || n_cameras > kMaxCameras) return tscm_set_error(TSCM_E_INVALID, "n_cameras " + std::to_string(n_cameras) + " outside 1..16");
     if (channels != 1 && channels != 3) return tscm_set_error(TSCM_E_INVALID, "channels " + std::to_string(channels) + " is not 1 or 3");
     if (width < 1 || height < 1 || width > 32767 || height > 32767)
@@ -367,17 +344,12 @@ extern "C" int tscm_panorama_compose(tscm_panorama *p, const unsigned char *cons
     if (dst_stride < p->pw * p->ch) return tscm_set_error(TSCM_E_INVALID, "dst_stride " + std::to_string(dst_stride) + " < pano_w * channels = " + std::to_string(p->pw * p->ch));
     if (seconds_kernel) *seconds_kernel = 0.0;
     if (int rc = upload_frame(p, images, stride)) return rc;
-    HIP_TRY(hipEventRecord(p->ev[0], 0));
+    HIP_TRY(p->span.mark(0));
     if (p->ch == 1) launch_compose<1>(p, g);
     else launch_compose<3>(p, g);
-    HIP_TRY(hipEventRecord(p->ev[1], 0));
-    HIP_TRY(hipEventSynchronize(p->ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    HIP_TRY(p->span.finish(1, nullptr, seconds_kernel));
     const size_t row = (size_t)p->pw * p->ch;
-    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, p->out, row, row, (size_t)p->ph, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_rows(dst, dst_stride, p->out, row, row, p->ph, hipMemcpyDeviceToHost));
     if (coverage) HIP_TRY(hipMemcpy(coverage, p->cover, p->npix, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -414,12 +386,11 @@ extern "C" int tscm_panorama_stages(tscm_panorama *p, const unsigned char *const
             for (int c = 0; c < ch; ++c)
                 for (size_t t = 0; t < p->npix; ++t) sampled[((size_t)k * p->npix + t) * ch + c] = (unsigned char)planes[(size_t)(k * ch + c) * gstride + t];
     }
-    if (alpha) HIP_TRY(hipMemcpy2D(alpha, p->npix, p->alpha, p->plane, p->npix, (size_t)n, hipMemcpyDeviceToHost));
+    if (alpha) HIP_TRY(copy_rows(alpha, p->npix, p->alpha, p->plane, p->npix, n, hipMemcpyDeviceToHost));
     if (label) HIP_TRY(hipMemcpy(label, p->label, p->npix, hipMemcpyDeviceToHost));
-    if (mask_pyramid) if (int rc = download_pyramid(*p, p->mpyr, n, mask_pyramid)) return rc;
-    if (lap_pyramid) if (int rc = download_pyramid(*p, d_lap, n * ch, lap_pyramid)) return rc;
-    if (blend_pyramid) if (int rc = download_pyramid(*p, p->B, ch, blend_pyramid)) return rc;
-    return 0;
+    if (int rc = download_pyramid(*p, p->mpyr, n, mask_pyramid)) return rc;
+    if (int rc = download_pyramid(*p, d_lap, n * ch, lap_pyramid)) return rc;
+    return download_pyramid(*p, p->B, ch, blend_pyramid);
 }
 
 extern "C" int tscm_panorama_overlap(tscm_panorama *p, const unsigned char *const *images, int stride, long long *count, long long *sum)

@@ -14,6 +14,25 @@ __device__ __forceinline__ void tap_weights(unsigned py, int (&wgt)[4])
     if (wgt[0] == 32768) { wgt[0] = 32767; wgt[3] = 1; }
 }
 
+// The packed record of one table entry (mx, my): the coordinates rounded to 1/32 px, the tap origin clamped to int16, and
+// alpha = the bilinear sample of the camera's w x h weight image wk (has == false: a constant 255 inside the image).
+__device__ __forceinline__ uint2 pack_record(float mx, float my, const unsigned char *__restrict__ wk, bool has, int w, int h)
+{
+    const int sx = __float2int_rn(mx * 32.0f), sy = __float2int_rn(my * 32.0f);
+    const int ix = max(-32768, min(32767, sx >> 5)), iy = max(-32768, min(32767, sy >> 5));
+    const unsigned frac = (unsigned)(sx & 31) | ((unsigned)(sy & 31) << 5);
+    int wgt[4];
+    tap_weights(frac, wgt);
+    int acc = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int x = ix + (q & 1), y = iy + (q >> 1);
+        if (x >= 0 && x < w && y >= 0 && y < h) acc += wgt[q] * (has ? (int)wk[(size_t)y * w + x] : 255);
+    }
+    const int a = max(0, min(255, (acc + (1 << 14)) >> 15));
+    return make_uint2(((unsigned)ix & 0xffffu) | ((unsigned)iy << 16), frac | ((unsigned)a << 16));
+}
+
 // the arithmetic of k_remap for one output pixel of one image (rows of w * CH bytes)
 template <int CH>
 __device__ __forceinline__ void sample_px(const unsigned char *__restrict__ img, int w, int h, uint2 pk, int (&px)[CH])

@@ -389,20 +389,14 @@ int rig_stage(const tscm_rig_input *in, const RigDevice &dev, const std::vector<
     s.Rp = Rp; s.tp = tp;
     HIP_TRY(mem.alloc(&dpart, (size_t)K * s.ksplit)); HIP_TRY(mem.alloc(&derr, (size_t)K));
     s.partial = dpart;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, 0));
+    EventSpan span;
+    HIP_TRY(span.create(2));
+    HIP_TRY(span.mark(0));
     hipLaunchKernelGGL(kern, dim3(jgroups, s.ksplit), dim3(64), 0, 0, s);
     hipLaunchKernelGGL(k_rig_hyp_reduce, dim3((K + 255) / 256), dim3(256), 0, 0, dpart, K, s.ksplit, derr);
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(span.finish(1, nullptr, &st.seconds));
     HIP_TRY(hipMemcpy(st.err.data(), derr, sizeof(double) * K, hipMemcpyDeviceToHost));
     st.jgroups = jgroups; st.ksplit = s.ksplit; st.skew = skew ? 1 : 0;
-    st.seconds = 1e-3 * ms;
     return 0;
 }
 

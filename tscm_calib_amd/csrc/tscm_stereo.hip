@@ -153,8 +153,7 @@ __global__ __launch_bounds__(256) void k_stereo_points(const short *__restrict__
 int check_params(const tscm_stereo_params *p)
 {
     if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (p->struct_size != (int)sizeof(tscm_stereo_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_stereo_params) = " + std::to_string(sizeof(tscm_stereo_params)));
+    if (int rc = check_struct_size(p, "tscm_stereo_params")) return rc;
     if (p->num_disparities < 16 || p->num_disparities > 256 || p->num_disparities % 16)
         return tscm_set_error(TSCM_E_INVALID, "params: num_disparities " + std::to_string(p->num_disparities) + " is not a multiple of 16 in 16..256");
     if (p->min_disparity < -2047 || p->min_disparity + p->num_disparities > 2047)
@@ -184,9 +183,11 @@ int stereo_run(const unsigned char *left, const unsigned char *right, int w, int
                int disp_stride, double *seconds_kernel)
 {
     if (int rc = select_device(device, who)) return rc;
-    const int D = p.num_disparities, dmin = p.min_disparity, npl = (D + 63) / 64;
+    const int D = p.num_disparities, dmin = p.min_disparity;
     const size_t npix = (size_t)w * h, nvol = npix * D;
     DeviceMem mem;
+    StageOutputs stages(mem);
+    EventSpan span;
     unsigned char *d_img[2] = { nullptr, nullptr }, *d_cost = nullptr;
     unsigned long long *d_census[2] = { nullptr, nullptr };
     unsigned short *d_sum = nullptr;
@@ -194,56 +195,39 @@ int stereo_run(const unsigned char *left, const unsigned char *right, int w, int
     const unsigned char *host_img[2] = { left, right };
     for (int k = 0; k < 2; ++k) {
         HIP_TRY(mem.alloc(&d_img[k], npix));
-        HIP_TRY(hipMemcpy2D(d_img[k], (size_t)w, host_img[k], (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+        HIP_TRY(copy_rows(d_img[k], w, host_img[k], stride, w, h, hipMemcpyHostToDevice));
         HIP_TRY(mem.alloc(&d_census[k], npix));
     }
     HIP_TRY(mem.alloc(&d_cost, nvol));
     HIP_TRY(mem.alloc(&d_sum, nvol));
     if (disparity) { HIP_TRY(mem.alloc(&d_kr, npix)); HIP_TRY(mem.alloc(&d_disp, npix)); }
-    hipEvent_t ev[6];
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    stages.from(census_left, d_census[0], npix);
+    stages.from(census_right, d_census[1], npix);
+    stages.from(cost, d_cost, nvol);
+    stages.from(aggregated, d_sum, nvol);
+    HIP_TRY(span.create(6));
     const int nseg = (w + kCostSegment - 1) / kCostSegment;
-    HIP_TRY(hipEventRecord(ev[0], 0));
+    HIP_TRY(span.mark(0));
     const dim3 cgrid((w + kCensusTileW - 1) / kCensusTileW, (h + kCensusTileH - 1) / kCensusTileH);
     for (int k = 0; k < 2; ++k) hipLaunchKernelGGL(k_census, cgrid, dim3(256), 0, 0, d_img[k], w, h, w, d_census[k]);
-    HIP_TRY(hipEventRecord(ev[1], 0));
+    HIP_TRY(span.mark(1));
     hipLaunchKernelGGL(k_cost, dim3((unsigned)(nseg * h)), dim3(256), 0, 0, d_census[0], d_census[1], w, h, D, dmin, d_cost);
-    HIP_TRY(hipEventRecord(ev[2], 0));
+    HIP_TRY(span.mark(2));
     launch_aggregate(d_cost, d_sum, w, h, D, p.p1, p.p2, p.paths);
-    HIP_TRY(hipEventRecord(ev[3], 0));
-    if (disparity && p.disp12_max_diff >= 0) {
-        const dim3 g((unsigned)(nseg * h));
-        if (npl == 1) hipLaunchKernelGGL(k_right_winner<1>, g, dim3(256), 0, 0, d_sum, w, h, D, dmin, d_kr);
-        else if (npl == 2) hipLaunchKernelGGL(k_right_winner<2>, g, dim3(256), 0, 0, d_sum, w, h, D, dmin, d_kr);
-        else if (npl == 3) hipLaunchKernelGGL(k_right_winner<3>, g, dim3(256), 0, 0, d_sum, w, h, D, dmin, d_kr);
-        else hipLaunchKernelGGL(k_right_winner<4>, g, dim3(256), 0, 0, d_sum, w, h, D, dmin, d_kr);
-    }
-    HIP_TRY(hipEventRecord(ev[4], 0));
-    if (disparity) {
-        const dim3 g((unsigned)((npix + 3) / 4));
-        if (npl == 1) hipLaunchKernelGGL(k_winner<1>, g, dim3(256), 0, 0, d_sum, d_kr, w, h, D, dmin, p.uniqueness_ratio, p.disp12_max_diff, d_disp);
-        else if (npl == 2) hipLaunchKernelGGL(k_winner<2>, g, dim3(256), 0, 0, d_sum, d_kr, w, h, D, dmin, p.uniqueness_ratio, p.disp12_max_diff, d_disp);
-        else if (npl == 3) hipLaunchKernelGGL(k_winner<3>, g, dim3(256), 0, 0, d_sum, d_kr, w, h, D, dmin, p.uniqueness_ratio, p.disp12_max_diff, d_disp);
-        else hipLaunchKernelGGL(k_winner<4>, g, dim3(256), 0, 0, d_sum, d_kr, w, h, D, dmin, p.uniqueness_ratio, p.disp12_max_diff, d_disp);
-    }
-    HIP_TRY(hipEventRecord(ev[5], 0));
-    HIP_TRY(hipEventSynchronize(ev[5]));
-    HIP_TRY(hipGetLastError());
-    double total = 0.0;
-    for (int k = 0; k < 5; ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-        g_stage_seconds[k] = 1e-3 * ms;
-        total += 1e-3 * ms;
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    if (seconds_kernel) *seconds_kernel = total;
-    if (census_left) HIP_TRY(hipMemcpy(census_left, d_census[0], npix * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (census_right) HIP_TRY(hipMemcpy(census_right, d_census[1], npix * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (cost) HIP_TRY(hipMemcpy(cost, d_cost, nvol, hipMemcpyDeviceToHost));
-    if (aggregated) HIP_TRY(hipMemcpy(aggregated, d_sum, nvol * sizeof(unsigned short), hipMemcpyDeviceToHost));
-    if (disparity)          // row padding of the caller's array keeps its values
-        HIP_TRY(hipMemcpy2D(disparity, (size_t)disp_stride * sizeof(short), d_disp, (size_t)w * sizeof(short), (size_t)w * sizeof(short), (size_t)h, hipMemcpyDeviceToHost));
+    HIP_TRY(span.mark(3));
+    if (disparity && p.disp12_max_diff >= 0)
+        with_planes(D, [&](auto npl) {
+            hipLaunchKernelGGL(k_right_winner<decltype(npl)::value>, dim3((unsigned)(nseg * h)), dim3(256), 0, 0, d_sum, w, h, D, dmin, d_kr);
+        });
+    HIP_TRY(span.mark(4));
+    if (disparity)
+        with_planes(D, [&](auto npl) {
+            hipLaunchKernelGGL(k_winner<decltype(npl)::value>, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, 0, d_sum, d_kr, w, h, D, dmin, p.uniqueness_ratio,
+                               p.disp12_max_diff, d_disp);
+        });
+    HIP_TRY(span.finish(5, g_stage_seconds, seconds_kernel));
+    HIP_TRY(stages.fetch());
+    if (disparity) HIP_TRY(copy_rows(disparity, disp_stride, d_disp, w, w, h, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -308,8 +292,7 @@ extern "C" int tscm_stereo_points(const short *disparity, int width, int height,
     double *d_pts = nullptr;
     unsigned char *d_valid = nullptr;
     HIP_TRY(mem.alloc(&d_disp, npix)); HIP_TRY(mem.alloc(&d_pts, 3 * npix)); HIP_TRY(mem.alloc(&d_valid, npix));
-    HIP_TRY(hipMemcpy2D(d_disp, (size_t)width * sizeof(short), disparity, (size_t)disp_stride * sizeof(short), (size_t)width * sizeof(short), (size_t)height,
-                        hipMemcpyHostToDevice));
+    HIP_TRY(copy_rows(d_disp, width, disparity, disp_stride, width, height, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_stereo_points, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, d_disp, width, height, 16 * (min_disparity - 1), projection,
                        left_map->fx, left_map->fy, left_map->cx, left_map->cy, baseline, d_pts, d_valid);
     HIP_TRY(hipGetLastError());

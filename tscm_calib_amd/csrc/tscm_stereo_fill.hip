@@ -167,21 +167,14 @@ __global__ __launch_bounds__(256) void k_fill_select(const short *__restrict__ d
 // ------------------------------------------------------------------------------------------------ host
 int check_fill_args(const short *disparity, int width, int height, int disp_stride, const tscm_stereo_fill_params *p)
 {
-    if (!disparity) return tscm_set_error(TSCM_E_INVALID, "disparity is NULL");
-    if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (width < 0 || height < 0) return tscm_set_error(TSCM_E_INVALID, "negative width or height");
-    if (disp_stride < width) return tscm_set_error(TSCM_E_INVALID, "disp_stride " + std::to_string(disp_stride) + " < width " + std::to_string(width));
-    if (p->struct_size != (int)sizeof(tscm_stereo_fill_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_stereo_fill_params) = " +
-                                                  std::to_string(sizeof(tscm_stereo_fill_params)));
+    if (int rc = check_map_args(disparity, width, height, disp_stride, p, "tscm_stereo_fill_params")) return rc;
     if (p->rule < TSCM_FILL_LOWEST || p->rule > TSCM_FILL_MEDIAN) return tscm_set_error(TSCM_E_INVALID, "params: rule " + std::to_string(p->rule) + " outside 0..2");
     if (p->paths != 4 && p->paths != 8) return tscm_set_error(TSCM_E_INVALID, "params: paths " + std::to_string(p->paths) + " is not 4 or 8");
     if (p->min_directions < 1 || p->min_directions > p->paths)
         return tscm_set_error(TSCM_E_INVALID, "params: min_directions " + std::to_string(p->min_directions) + " outside 1.." + std::to_string(p->paths) + " (paths)");
     if (p->max_distance < 0 || p->max_distance > 32767) return tscm_set_error(TSCM_E_INVALID, "params: max_distance " + std::to_string(p->max_distance) + " outside 0..32767");
     if (p->wrap_x != 0 && p->wrap_x != 1) return tscm_set_error(TSCM_E_INVALID, "params: wrap_x " + std::to_string(p->wrap_x) + " is not 0 or 1");
-    if (p->min_disparity < -2047 || p->min_disparity > 2047 - 16)
-        return tscm_set_error(TSCM_E_INVALID, "params: min_disparity " + std::to_string(p->min_disparity) + " outside -2047..2031, what the matcher accepts");
+    if (int rc = check_map_min_disparity(p->min_disparity)) return rc;
     if (width > 32767 || height > 32767)
         return tscm_set_error(TSCM_E_INVALID, "width " + std::to_string(width) + " or height " + std::to_string(height) + " above 32767: distances are int16");
     return 0;
@@ -194,33 +187,27 @@ int fill_run(const short *disparity, int w, int h, int disp_stride, const tscm_s
     if (int rc = select_device(device, who)) return rc;
     const int n = w * h, invalid = 16 * (p.min_disparity - 1), maxd = p.max_distance > 0 ? p.max_distance : INT_MAX;
     DeviceMem mem;
+    StageOutputs stages(mem);
+    EventSpan span;
     short *d_in = nullptr, *d_out = nullptr;
     unsigned *d_cand = nullptr;
     unsigned char *d_mask = nullptr;
     HIP_TRY(mem.alloc(&d_in, (size_t)n));
     HIP_TRY(mem.alloc(&d_cand, (size_t)p.paths * n));
     if (out) HIP_TRY(mem.alloc(&d_out, (size_t)n));
-    if (out && mask) HIP_TRY(mem.alloc(&d_mask, (size_t)n));
-    HIP_TRY(hipMemcpy2D(d_in, (size_t)w * sizeof(short), disparity, (size_t)disp_stride * sizeof(short), (size_t)w * sizeof(short), (size_t)h, hipMemcpyHostToDevice));
-    hipEvent_t ev[2];
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev[0], 0));
+    if (out) HIP_TRY(stages.scratch(&d_mask, mask, (size_t)n));
+    HIP_TRY(copy_rows(d_in, w, disparity, disp_stride, w, h, hipMemcpyHostToDevice));
+    HIP_TRY(span.create(2));
+    HIP_TRY(span.mark(0));
     hipLaunchKernelGGL(k_fill_rows, dim3((unsigned)((h + 3) / 4), 2), dim3(256), 0, 0, d_in, w, h, invalid, maxd, p.wrap_x, d_cand);
     hipLaunchKernelGGL(k_fill_lines, dim3((unsigned)((w + 63) / 64), (unsigned)(p.paths - 2)), dim3(64), 0, 0, d_in, w, h, invalid, maxd, p.wrap_x, d_cand);
     if (out) {
         auto *const f = p.paths == 4 ? k_fill_select<4> : k_fill_select<8>;
         hipLaunchKernelGGL(f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, d_cand, n, invalid, p.rule, p.min_directions, d_out, d_mask);
     }
-    HIP_TRY(hipEventRecord(ev[1], 0));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
-    if (out)                // row padding of the caller's array keeps its values
-        HIP_TRY(hipMemcpy2D(out, (size_t)out_stride * sizeof(short), d_out, (size_t)w * sizeof(short), (size_t)w * sizeof(short), (size_t)h, hipMemcpyDeviceToHost));
-    if (out && mask) HIP_TRY(hipMemcpy(mask, d_mask, (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(span.finish(1, nullptr, seconds_kernel));
+    if (out) HIP_TRY(copy_rows(out, out_stride, d_out, w, w, h, hipMemcpyDeviceToHost));
+    HIP_TRY(stages.fetch());
     if (value || distance) {                                 // the packed planes, taken apart on the host
         std::vector<unsigned> c((size_t)p.paths * n);
         HIP_TRY(hipMemcpy(c.data(), d_cand, c.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -251,8 +238,7 @@ extern "C" int tscm_stereo_fill(const short *disparity, int width, int height, i
                                 int out_stride, unsigned char *mask, double *seconds_kernel)
 {
     if (int rc = check_fill_args(disparity, width, height, disp_stride, params)) return rc;
-    if (!out) return tscm_set_error(TSCM_E_INVALID, "out is NULL");
-    if (out_stride < width) return tscm_set_error(TSCM_E_INVALID, "out_stride " + std::to_string(out_stride) + " < width " + std::to_string(width));
+    if (int rc = check_map_out(out, out_stride, width)) return rc;
     if (seconds_kernel) *seconds_kernel = 0.0;
     if (width == 0 || height == 0) return 0;
     return fill_run(disparity, width, height, disp_stride, *params, device, "tscm_stereo_fill", out, out_stride, mask, nullptr, nullptr, seconds_kernel);

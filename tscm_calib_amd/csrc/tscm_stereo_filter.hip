@@ -236,18 +236,11 @@ __global__ __launch_bounds__(256) void k_speckle_median(const short *__restrict_
 // ------------------------------------------------------------------------------------------------ host
 int check_filter_args(const short *disparity, int width, int height, int disp_stride, const tscm_stereo_filter_params *p)
 {
-    if (!disparity) return tscm_set_error(TSCM_E_INVALID, "disparity is NULL");
-    if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (width < 0 || height < 0) return tscm_set_error(TSCM_E_INVALID, "negative width or height");
-    if (disp_stride < width) return tscm_set_error(TSCM_E_INVALID, "disp_stride " + std::to_string(disp_stride) + " < width " + std::to_string(width));
-    if (p->struct_size != (int)sizeof(tscm_stereo_filter_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_stereo_filter_params) = " +
-                                                  std::to_string(sizeof(tscm_stereo_filter_params)));
+    if (int rc = check_map_args(disparity, width, height, disp_stride, p, "tscm_stereo_filter_params")) return rc;
     if (p->speckle_window_size < 0) return tscm_set_error(TSCM_E_INVALID, "params: speckle_window_size " + std::to_string(p->speckle_window_size) + " is negative");
     if (p->speckle_range < 0 || p->speckle_range > 255) return tscm_set_error(TSCM_E_INVALID, "params: speckle_range " + std::to_string(p->speckle_range) + " outside 0..255");
     if (p->median != 0 && p->median != 3 && p->median != 5) return tscm_set_error(TSCM_E_INVALID, "params: median " + std::to_string(p->median) + " is not 0, 3 or 5");
-    if (p->min_disparity < -2047 || p->min_disparity > 2047 - 16)          // the matcher's range at its smallest num_disparities
-        return tscm_set_error(TSCM_E_INVALID, "params: min_disparity " + std::to_string(p->min_disparity) + " outside -2047..2031, what the matcher accepts");
+    if (int rc = check_map_min_disparity(p->min_disparity)) return rc;
     if ((long long)width * height > (long long)INT_MAX)
         return tscm_set_error(TSCM_E_INVALID, "width * height = " + std::to_string((long long)width * height) + " does not fit the int32 labels");
     return 0;
@@ -263,21 +256,23 @@ int filter_run(const short *disparity, int w, int h, int disp_stride, const tscm
     const int tiles_x = (w + kTileW - 1) / kTileW, tiles_y = (h + kTileH - 1) / kTileH;
     const bool components = p.speckle_window_size > 0 || label || size;
     DeviceMem mem;
+    StageOutputs stages(mem);
+    EventSpan span;
     short *d_in = nullptr, *d_out = nullptr, *d_desp = nullptr;
     int *d_parent = nullptr, *d_cnt = nullptr, *d_label = nullptr, *d_rootsize = nullptr, *d_size = nullptr;
     HIP_TRY(mem.alloc(&d_in, (size_t)n));
     HIP_TRY(mem.alloc(&d_out, (size_t)n));
-    HIP_TRY(hipMemcpy2D(d_in, (size_t)w * sizeof(short), disparity, (size_t)disp_stride * sizeof(short), (size_t)w * sizeof(short), (size_t)h, hipMemcpyHostToDevice));
+    HIP_TRY(copy_rows(d_in, w, disparity, disp_stride, w, h, hipMemcpyHostToDevice));
     if (components) {
         HIP_TRY(mem.alloc(&d_parent, (size_t)n)); HIP_TRY(mem.alloc(&d_cnt, (size_t)n));
         HIP_TRY(mem.alloc(&d_label, (size_t)n)); HIP_TRY(mem.alloc(&d_rootsize, (size_t)n));
     }
-    if (size) HIP_TRY(mem.alloc(&d_size, (size_t)n));
-    if (despeckled) HIP_TRY(mem.alloc(&d_desp, (size_t)n));
-    hipEvent_t ev[2];
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    stages.from(label, d_label, (size_t)n);
+    HIP_TRY(stages.scratch(&d_size, size, (size_t)n));
+    HIP_TRY(stages.scratch(&d_desp, despeckled, (size_t)n));
+    HIP_TRY(span.create(2));
     const dim3 tiles((unsigned)(tiles_x * tiles_y)), pixels((unsigned)((n + 255) / 256)), block(256);
-    HIP_TRY(hipEventRecord(ev[0], 0));
+    HIP_TRY(span.mark(0));
     if (components) {
         hipLaunchKernelGGL(k_ccl_tile, tiles, block, 0, 0, d_in, w, h, tiles_x, invalid, thr, d_parent, d_cnt);
         const long long seam_pairs = (long long)(tiles_x - 1) * h + (long long)(tiles_y - 1) * w;
@@ -288,18 +283,9 @@ int filter_run(const short *disparity, int w, int h, int disp_stride, const tscm
     }
     auto *const f = p.median == 0 ? k_speckle_median<0> : p.median == 3 ? k_speckle_median<3> : k_speckle_median<5>;
     hipLaunchKernelGGL(f, tiles, block, 0, 0, d_in, d_label, d_rootsize, w, h, tiles_x, invalid, p.speckle_window_size, d_out, d_size, d_desp);
-    HIP_TRY(hipEventRecord(ev[1], 0));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
-    if (out)                // row padding of the caller's array keeps its values
-        HIP_TRY(hipMemcpy2D(out, (size_t)out_stride * sizeof(short), d_out, (size_t)w * sizeof(short), (size_t)w * sizeof(short), (size_t)h, hipMemcpyDeviceToHost));
-    if (label) HIP_TRY(hipMemcpy(label, d_label, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    if (size) HIP_TRY(hipMemcpy(size, d_size, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    if (despeckled) HIP_TRY(hipMemcpy(despeckled, d_desp, (size_t)n * sizeof(short), hipMemcpyDeviceToHost));
+    HIP_TRY(span.finish(1, nullptr, seconds_kernel));
+    if (out) HIP_TRY(copy_rows(out, out_stride, d_out, w, w, h, hipMemcpyDeviceToHost));
+    HIP_TRY(stages.fetch());
     return 0;
 }
 
@@ -318,8 +304,7 @@ extern "C" int tscm_stereo_filter(const short *disparity, int width, int height,
                                   short *out, int out_stride, double *seconds_kernel)
 {
     if (int rc = check_filter_args(disparity, width, height, disp_stride, params)) return rc;
-    if (!out) return tscm_set_error(TSCM_E_INVALID, "out is NULL");
-    if (out_stride < width) return tscm_set_error(TSCM_E_INVALID, "out_stride " + std::to_string(out_stride) + " < width " + std::to_string(width));
+    if (int rc = check_map_out(out, out_stride, width)) return rc;
     if (seconds_kernel) *seconds_kernel = 0.0;
     if (width == 0 || height == 0) return 0;
     return filter_run(disparity, width, height, disp_stride, *params, device, "tscm_stereo_filter", out, out_stride, nullptr, nullptr, nullptr, seconds_kernel);

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace {
 
@@ -206,8 +207,19 @@ __global__ __launch_bounds__(256) void k_winner(const unsigned short *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------ host
-using AggregateKernel = void (*)(const unsigned char *, unsigned short *, int, int, int, int, int, int);
+// f(std::integral_constant<int, NPL>()) for the NPL = 1..4 planes of 64 hypotheses that hold D of them: the one place that
+// picks among the <1> .. <4> instantiations of k_aggregate and the winner kernels
+template <typename F>
+inline auto with_planes(int D, F &&f)
+{
+    const int npl = (D + 63) / 64;
+    if (npl == 1) return f(std::integral_constant<int, 1>());
+    if (npl == 2) return f(std::integral_constant<int, 2>());
+    if (npl == 3) return f(std::integral_constant<int, 3>());
+    return f(std::integral_constant<int, 4>());
+}
 
+using AggregateKernel = void (*)(const unsigned char *, unsigned short *, int, int, int, int, int, int);
 
 template <int NPL>
 AggregateKernel aggregate_kernel(int dir)
@@ -227,9 +239,8 @@ AggregateKernel aggregate_kernel(int dir)
 // the `paths` launches of one volume on the current stream: S = sum of L_r over the directions
 inline void launch_aggregate(const unsigned char *cost, unsigned short *sum, int w, int h, int D, int p1, int p2, int paths)
 {
-    const int npl = (D + 63) / 64;
     for (int dir = 0; dir < paths; ++dir) {
-        const AggregateKernel f = npl == 1 ? aggregate_kernel<1>(dir) : npl == 2 ? aggregate_kernel<2>(dir) : npl == 3 ? aggregate_kernel<3>(dir) : aggregate_kernel<4>(dir);
+        const AggregateKernel f = with_planes(D, [dir](auto npl) { return aggregate_kernel<decltype(npl)::value>(dir); });
         const int n_lines = dir < 2 ? h : w;
         hipLaunchKernelGGL(f, dim3((n_lines + 3) / 4), dim3(256), 0, 0, cost, sum, w, h, D, p1, p2, dir > 0 ? 1 : 0);
     }

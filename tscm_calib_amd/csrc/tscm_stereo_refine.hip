@@ -111,21 +111,12 @@ const refine_kernel kKernels[7] = { k_refine<1>, k_refine<2>, k_refine<3>, k_ref
 // ------------------------------------------------------------------------------------------------ host
 int check_refine_args(const short *disparity, int width, int height, int disp_stride, const unsigned char *guide, int guide_stride, const tscm_stereo_refine_params *p)
 {
-    if (!disparity) return tscm_set_error(TSCM_E_INVALID, "disparity is NULL");
-    if (!guide) return tscm_set_error(TSCM_E_INVALID, "guide is NULL");
-    if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (width < 0 || height < 0) return tscm_set_error(TSCM_E_INVALID, "negative width or height");
-    if (disp_stride < width) return tscm_set_error(TSCM_E_INVALID, "disp_stride " + std::to_string(disp_stride) + " < width " + std::to_string(width));
-    if (guide_stride < width) return tscm_set_error(TSCM_E_INVALID, "guide_stride " + std::to_string(guide_stride) + " < width " + std::to_string(width));
-    if (p->struct_size != (int)sizeof(tscm_stereo_refine_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_stereo_refine_params) = " +
-                                                  std::to_string(sizeof(tscm_stereo_refine_params)));
+    if (int rc = check_map_args(disparity, width, height, disp_stride, p, "tscm_stereo_refine_params", &guide, guide_stride)) return rc;
     if (p->radius < 1 || p->radius > 7) return tscm_set_error(TSCM_E_INVALID, "params: radius " + std::to_string(p->radius) + " outside 1..7");
     if (p->iterations < 1 || p->iterations > 8) return tscm_set_error(TSCM_E_INVALID, "params: iterations " + std::to_string(p->iterations) + " outside 1..8");
     if (p->fill_invalid != 0 && p->fill_invalid != 1) return tscm_set_error(TSCM_E_INVALID, "params: fill_invalid " + std::to_string(p->fill_invalid) + " is not 0 or 1");
     if (p->wrap_x != 0 && p->wrap_x != 1) return tscm_set_error(TSCM_E_INVALID, "params: wrap_x " + std::to_string(p->wrap_x) + " is not 0 or 1");
-    if (p->min_disparity < -2047 || p->min_disparity > 2047 - 16)
-        return tscm_set_error(TSCM_E_INVALID, "params: min_disparity " + std::to_string(p->min_disparity) + " outside -2047..2031, what the matcher accepts");
+    if (int rc = check_map_min_disparity(p->min_disparity)) return rc;
     if ((long long)width * height > INT_MAX)
         return tscm_set_error(TSCM_E_INVALID, "width " + std::to_string(width) + " x height " + std::to_string(height) + " above INT_MAX pixels");
     return 0;
@@ -143,6 +134,8 @@ int refine_run(const short *disparity, int w, int h, int disp_stride, const unsi
     unsigned char table[256];
     for (int k = 0; k < 256; ++k) table[k] = range_weight ? range_weight[k] : 255;
     DeviceMem mem;
+    StageOutputs stages(mem);
+    EventSpan span;
     short *d_map[2] = { nullptr, nullptr };
     unsigned char *d_guide = nullptr, *d_table = nullptr, *d_count = nullptr;
     int *d_sum = nullptr;
@@ -150,29 +143,19 @@ int refine_run(const short *disparity, int w, int h, int disp_stride, const unsi
     HIP_TRY(mem.alloc(&d_map[1], n));
     HIP_TRY(mem.alloc(&d_guide, n));
     HIP_TRY(mem.upload(&d_table, table, (size_t)256));
-    if (weight_sum) HIP_TRY(mem.alloc(&d_sum, n));
-    if (count) HIP_TRY(mem.alloc(&d_count, n));
-    HIP_TRY(hipMemcpy2D(d_map[0], (size_t)w * sizeof(short), disparity, (size_t)disp_stride * sizeof(short), (size_t)w * sizeof(short), (size_t)h, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy2D(d_guide, (size_t)w, guide, (size_t)guide_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+    HIP_TRY(stages.scratch(&d_sum, weight_sum, n));
+    HIP_TRY(stages.scratch(&d_count, count, n));
+    HIP_TRY(copy_rows(d_map[0], w, disparity, disp_stride, w, h, hipMemcpyHostToDevice));
+    HIP_TRY(copy_rows(d_guide, w, guide, guide_stride, w, h, hipMemcpyHostToDevice));
     const unsigned tiles_x = (unsigned)(((long long)w + kTileW - 1) / kTileW), tiles_y = (unsigned)((h + kTileH - 1) / kTileH);
-    hipEvent_t ev[2];
-    for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev[0], 0));
+    HIP_TRY(span.create(2));
+    HIP_TRY(span.mark(0));
     for (int i = 0; i < passes; ++i)                         // Jacobi: pass i + 1 reads the whole output of pass i
         hipLaunchKernelGGL(kKernels[p.radius - 1], dim3(tiles_x * tiles_y), dim3(256), 0, 0, d_map[i & 1], d_guide, d_table, w, h, invalid, p.fill_invalid, p.wrap_x,
                            tiles_x, d_map[(i + 1) & 1], i == 0 ? d_sum : nullptr, i == 0 ? d_count : nullptr);
-    HIP_TRY(hipEventRecord(ev[1], 0));
-    HIP_TRY(hipEventSynchronize(ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
-    if (out)                // row padding of the caller's array keeps its values
-        HIP_TRY(hipMemcpy2D(out, (size_t)out_stride * sizeof(short), d_map[passes & 1], (size_t)w * sizeof(short), (size_t)w * sizeof(short), (size_t)h,
-                            hipMemcpyDeviceToHost));
-    if (weight_sum) HIP_TRY(hipMemcpy(weight_sum, d_sum, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (count) HIP_TRY(hipMemcpy(count, d_count, n, hipMemcpyDeviceToHost));
+    HIP_TRY(span.finish(1, nullptr, seconds_kernel));
+    if (out) HIP_TRY(copy_rows(out, out_stride, d_map[passes & 1], w, w, h, hipMemcpyDeviceToHost));
+    HIP_TRY(stages.fetch());
     return 0;
 }
 
@@ -201,8 +184,7 @@ extern "C" int tscm_stereo_refine(const short *disparity, int width, int height,
                                   double *seconds_kernel)
 {
     if (int rc = check_refine_args(disparity, width, height, disp_stride, guide, guide_stride, params)) return rc;
-    if (!out) return tscm_set_error(TSCM_E_INVALID, "out is NULL");
-    if (out_stride < width) return tscm_set_error(TSCM_E_INVALID, "out_stride " + std::to_string(out_stride) + " < width " + std::to_string(width));
+    if (int rc = check_map_out(out, out_stride, width)) return rc;
     if (seconds_kernel) *seconds_kernel = 0.0;
     if (width == 0 || height == 0) return 0;
     return refine_run(disparity, width, height, disp_stride, guide, guide_stride, range_weight, *params, params->iterations, device, "tscm_stereo_refine", out, out_stride,

@@ -67,21 +67,7 @@ __global__ __launch_bounds__(256) void k_sweep_prepare(const float *__restrict__
     if (t >= npix) return;
     const int k = blockIdx.y / D;
     const size_t at = (size_t)blockIdx.y * npix + t;
-    const int sx = __float2int_rn(mapx[at] * 32.0f), sy = __float2int_rn(mapy[at] * 32.0f);
-    const int ix = max(-32768, min(32767, sx >> 5)), iy = max(-32768, min(32767, sy >> 5));
-    const unsigned frac = (unsigned)(sx & 31) | ((unsigned)(sy & 31) << 5);
-    int wgt[4];
-    tap_weights(frac, wgt);
-    const bool has = (weight_mask >> k) & 1u;
-    const unsigned char *wk = wimg + (size_t)k * w * h;
-    int acc = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int x = ix + (q & 1), y = iy + (q >> 1);
-        if (x >= 0 && x < w && y >= 0 && y < h) acc += wgt[q] * (has ? (int)wk[(size_t)y * w + x] : 255);
-    }
-    const int a = max(0, min(255, (acc + (1 << 14)) >> 15));
-    pack[at] = make_uint2(((unsigned)ix & 0xffffu) | ((unsigned)iy << 16), frac | ((unsigned)a << 16));
+    pack[at] = pack_record(mapx[at], mapy[at], wimg + (size_t)k * w * h, (weight_mask >> k) & 1u, w, h);
 }
 
 // ------------------------------------------------------------------------------------------------ cost
@@ -563,8 +549,7 @@ struct tscm_sweep : PyramidLayout {         // the base: the levels of the compo
     unsigned char *v_use = nullptr, *v_state = nullptr;
     short *v_index = nullptr;
     size_t v_plane = 0;                     // npix rounded up to 4
-    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };
-    ~tscm_sweep() { for (auto e : ev) if (e) (void)hipEventDestroy(e); }
+    EventSpan span;
 };
 
 namespace {
@@ -572,8 +557,7 @@ namespace {
 int check_params(const tscm_sweep_params *p)
 {
     if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (p->struct_size != (int)sizeof(tscm_sweep_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_sweep_params) = " + std::to_string(sizeof(tscm_sweep_params)));
+    if (int rc = check_struct_size(p, "tscm_sweep_params")) return rc;
     if (p->num_hypotheses < 16 || p->num_hypotheses > 256 || p->num_hypotheses % 16)
         return tscm_set_error(TSCM_E_INVALID, "params: num_hypotheses " + std::to_string(p->num_hypotheses) + " is not a multiple of 16 in 16..256");
     if (p->paths != 4 && p->paths != 8) return tscm_set_error(TSCM_E_INVALID, "params: paths " + std::to_string(p->paths) + " is not 4 or 8");
@@ -586,11 +570,7 @@ int check_params(const tscm_sweep_params *p)
 int check_frame(const tscm_sweep *s, const unsigned char *const *images, int stride)
 {
     if (!s) return tscm_set_error(TSCM_E_INVALID, "s is NULL");
-    if (!images) return tscm_set_error(TSCM_E_INVALID, "images is NULL");
-    for (int k = 0; k < s->n; ++k)
-        if (!images[k]) return tscm_set_error(TSCM_E_INVALID, "images[" + std::to_string(k) + "] is NULL");
-    if (stride < s->w) return tscm_set_error(TSCM_E_INVALID, "stride " + std::to_string(stride) + " < width " + std::to_string(s->w));
-    return 0;
+    return check_image_list(images, s->n, stride, s->w, "width ");
 }
 
 using CostKernel = void (*)(const uint2 *, const unsigned char *, int, int, int, int, int, int, unsigned char *, unsigned char *, unsigned char *, unsigned long long *);
@@ -614,33 +594,20 @@ int run_frame(tscm_sweep *s, const unsigned char *const *images, int stride, uns
 {
     HIP_TRY(hipSetDevice(s->device));
     const size_t simg = (size_t)s->w * s->h;
-    for (int k = 0; k < s->n; ++k) HIP_TRY(hipMemcpy2D(s->img + k * simg, (size_t)s->w, images[k], (size_t)stride, (size_t)s->w, (size_t)s->h, hipMemcpyHostToDevice));
-    HIP_TRY(hipEventRecord(s->ev[0], 0));
+    for (int k = 0; k < s->n; ++k) HIP_TRY(copy_rows(s->img + k * simg, s->w, images[k], stride, s->w, s->h, hipMemcpyHostToDevice));
+    HIP_TRY(s->span.mark(0));
     const dim3 grid((unsigned)((s->pw + kTileW - 1) / kTileW), (unsigned)((s->ph + kTileH - 1) / kTileH), (unsigned)(s->D / kZGroup));
     hipLaunchKernelGGL(cost_kernel(s->n), grid, dim3(256), 0, 0, s->pack, s->img, s->w, s->h, s->pw, s->ph, s->D, s->wrap, s->cost, d_sampled, d_alpha, d_census);
-    HIP_TRY(hipEventRecord(s->ev[1], 0));
+    HIP_TRY(s->span.mark(1));
     launch_aggregate(s->cost, s->sum, s->pw, s->ph, s->D, s->p1, s->p2, s->paths);
-    HIP_TRY(hipEventRecord(s->ev[2], 0));
-    if (with_winner) {
-        const dim3 g((unsigned)((s->npix + 3) / 4));
-        const int npl = (s->D + 63) / 64;
-        if (npl == 1) hipLaunchKernelGGL(k_sweep_winner<1>, g, dim3(256), 0, 0, s->sum, s->cost, s->pw, s->ph, s->D, s->uniqueness, s->index16);
-        else if (npl == 2) hipLaunchKernelGGL(k_sweep_winner<2>, g, dim3(256), 0, 0, s->sum, s->cost, s->pw, s->ph, s->D, s->uniqueness, s->index16);
-        else if (npl == 3) hipLaunchKernelGGL(k_sweep_winner<3>, g, dim3(256), 0, 0, s->sum, s->cost, s->pw, s->ph, s->D, s->uniqueness, s->index16);
-        else hipLaunchKernelGGL(k_sweep_winner<4>, g, dim3(256), 0, 0, s->sum, s->cost, s->pw, s->ph, s->D, s->uniqueness, s->index16);
-    }
-    HIP_TRY(hipEventRecord(s->ev[3], 0));
-    HIP_TRY(hipEventSynchronize(s->ev[3]));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(s->span.mark(2));
+    if (with_winner)
+        with_planes(s->D, [s](auto npl) {
+            hipLaunchKernelGGL(k_sweep_winner<decltype(npl)::value>, dim3((unsigned)((s->npix + 3) / 4)), dim3(256), 0, 0, s->sum, s->cost, s->pw, s->ph, s->D, s->uniqueness,
+                               s->index16);
+        });
+    HIP_TRY(s->span.finish(3, g_stage_seconds, seconds_kernel));
     if (with_winner) s->has_index = true;
-    double total = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[k], s->ev[k + 1]));
-        g_stage_seconds[k] = 1e-3 * ms;
-        total += 1e-3 * ms;
-    }
-    if (seconds_kernel) *seconds_kernel = total;
     return 0;
 }
 
@@ -648,7 +615,7 @@ int create_on_device(tscm_sweep *s, const unsigned char *const *weights, const f
 {
     const int n = s->n;
     const size_t simg = (size_t)s->w * s->h, ntab = (size_t)n * s->D * s->npix, nvol = s->npix * s->D;
-    for (auto &e : s->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(s->span.create(4));
     HIP_TRY(s->mem.alloc(&s->pack, ntab));
     HIP_TRY(s->mem.alloc(&s->img, n * simg));
     HIP_TRY(s->mem.alloc(&s->cost, nvol));
@@ -716,9 +683,7 @@ extern "C" int tscm_sweep_depth(tscm_sweep *s, const unsigned char *const *image
     if (out_stride < s->pw) return tscm_set_error(TSCM_E_INVALID, "out_stride " + std::to_string(out_stride) + " < pano_w " + std::to_string(s->pw));
     if (seconds_kernel) *seconds_kernel = 0.0;
     if (int rc = run_frame(s, images, stride, nullptr, nullptr, nullptr, true, seconds_kernel)) return rc;
-    // row padding of the caller's array keeps its values
-    HIP_TRY(hipMemcpy2D(index16, (size_t)out_stride * sizeof(short), s->index16, (size_t)s->pw * sizeof(short), (size_t)s->pw * sizeof(short), (size_t)s->ph,
-                        hipMemcpyDeviceToHost));
+    HIP_TRY(copy_rows(index16, out_stride, s->index16, s->pw, s->pw, s->ph, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -729,17 +694,16 @@ extern "C" int tscm_sweep_stages(tscm_sweep *s, const unsigned char *const *imag
     HIP_TRY(hipSetDevice(s->device));
     const size_t ntab = (size_t)s->n * s->D * s->npix, nvol = s->npix * s->D;
     DeviceMem tmp;
+    StageOutputs stages(tmp);
     unsigned char *d_sampled = nullptr, *d_alpha = nullptr;
     unsigned long long *d_census = nullptr;
-    if (sampled) HIP_TRY(tmp.alloc(&d_sampled, ntab));
-    if (alpha) HIP_TRY(tmp.alloc(&d_alpha, ntab));
-    if (census) HIP_TRY(tmp.alloc(&d_census, ntab));
+    HIP_TRY(stages.scratch(&d_sampled, sampled, ntab));
+    HIP_TRY(stages.scratch(&d_alpha, alpha, ntab));
+    HIP_TRY(stages.scratch(&d_census, census, ntab));
+    stages.from(cost, s->cost, nvol);
+    stages.from(aggregated, s->sum, nvol);
     if (int rc = run_frame(s, images, stride, d_sampled, d_alpha, d_census, false, nullptr)) return rc;
-    if (sampled) HIP_TRY(hipMemcpy(sampled, d_sampled, ntab, hipMemcpyDeviceToHost));
-    if (alpha) HIP_TRY(hipMemcpy(alpha, d_alpha, ntab, hipMemcpyDeviceToHost));
-    if (census) HIP_TRY(hipMemcpy(census, d_census, ntab * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (cost) HIP_TRY(hipMemcpy(cost, s->cost, nvol, hipMemcpyDeviceToHost));
-    if (aggregated) HIP_TRY(hipMemcpy(aggregated, s->sum, nvol * sizeof(unsigned short), hipMemcpyDeviceToHost));
+    HIP_TRY(stages.fetch());
     return 0;
 }
 
@@ -763,14 +727,11 @@ int check_compose(const tscm_sweep *s, const unsigned char *const *images, int s
                   const tscm_sweep_compose_params *p, const unsigned short *gain_q8, Gains *gains)
 {
     if (!s) return tscm_set_error(TSCM_E_INVALID, "s is NULL");
-    if (!images) return tscm_set_error(TSCM_E_INVALID, "images is NULL");
-    for (int k = 0; k < s->n; ++k)
-        if (!images[k]) return tscm_set_error(TSCM_E_INVALID, "images[" + std::to_string(k) + "] is NULL");
+    if (int rc = check_image_pointers(images, s->n)) return rc;
     if (channels != 1 && channels != 3) return tscm_set_error(TSCM_E_INVALID, "channels " + std::to_string(channels) + " is not 1 or 3");
-    if (stride < s->w * channels) return tscm_set_error(TSCM_E_INVALID, "stride " + std::to_string(stride) + " < width * channels = " + std::to_string(s->w * channels));
+    if (int rc = check_image_stride(stride, s->w * channels, "width * channels = ")) return rc;
     if (!p) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
-    if (p->struct_size != (int)sizeof(tscm_sweep_compose_params))
-        return tscm_set_error(TSCM_E_INVALID, "params: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_sweep_compose_params) = " + std::to_string(sizeof(tscm_sweep_compose_params)));
+    if (int rc = check_struct_size(p, "tscm_sweep_compose_params")) return rc;
     if (p->mode != TSCM_PANO_SEAM && p->mode != TSCM_PANO_FEATHER && p->mode != TSCM_PANO_MULTIBAND)
         return tscm_set_error(TSCM_E_INVALID, "params: unknown mode " + std::to_string(p->mode));
     const bool multiband = p->mode == TSCM_PANO_MULTIBAND;
@@ -780,14 +741,8 @@ int check_compose(const tscm_sweep *s, const unsigned char *const *images, int s
     const int L = multiband ? p->levels : 0;
     if (s->pw % (1 << L)) return tscm_set_error(TSCM_E_INVALID, "pano_w " + std::to_string(s->pw) + " is no multiple of 2^levels = " + std::to_string(1 << L));
     if (s->ph % (1 << L)) return tscm_set_error(TSCM_E_INVALID, "pano_h " + std::to_string(s->ph) + " is no multiple of 2^levels = " + std::to_string(1 << L));
-    if (!index16 && !s->has_index) return tscm_set_error(TSCM_E_INVALID, "index16 is NULL and the handle has not run tscm_sweep_depth yet");
-    if (index16 && index_stride < s->pw) return tscm_set_error(TSCM_E_INVALID, "index_stride " + std::to_string(index_stride) + " < pano_w " + std::to_string(s->pw));
-    for (int k = 0; k < kPanoMaxCameras; ++k) gains->g[k] = 256;
-    for (int k = 0; gain_q8 && k < s->n; ++k) {
-        if (gain_q8[k] < 1 || gain_q8[k] > 4095) return tscm_set_error(TSCM_E_INVALID, "gain_q8[" + std::to_string(k) + "] = " + std::to_string(gain_q8[k]) + " outside 1..4095");
-        gains->g[k] = gain_q8[k];
-    }
-    return 0;
+    if (int rc = check_index_map(index16, index_stride, s->has_index, s->pw)) return rc;
+    return check_gains(gain_q8, s->n, gains);
 }
 
 // the composer's buffers for (channels, mode, levels); kept until one of the three changes
@@ -871,11 +826,10 @@ int upload_compose(tscm_sweep *s, const unsigned char *const *images, int stride
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = compose_buffers(s, ch, p->mode, p->mode == TSCM_PANO_MULTIBAND ? p->levels : 0)) return rc;
     const size_t row = (size_t)s->w * ch;
-    for (int k = 0; k < s->n; ++k) HIP_TRY(hipMemcpy2D(s->c_img + (size_t)k * row * s->h, row, images[k], (size_t)stride, row, (size_t)s->h, hipMemcpyHostToDevice));
+    for (int k = 0; k < s->n; ++k) HIP_TRY(copy_rows(s->c_img + (size_t)k * row * s->h, row, images[k], stride, row, s->h, hipMemcpyHostToDevice));
     *idx = s->index16;
     if (index16) {
-        HIP_TRY(hipMemcpy2D(s->c_index, (size_t)s->pw * sizeof(short), index16, (size_t)index_stride * sizeof(short), (size_t)s->pw * sizeof(short), (size_t)s->ph,
-                            hipMemcpyHostToDevice));
+        HIP_TRY(copy_rows(s->c_index, s->pw, index16, index_stride, s->pw, s->ph, hipMemcpyHostToDevice));
         *idx = s->c_index;
     }
     return 0;
@@ -892,8 +846,7 @@ struct VisibilityStages {
 int check_visibility(const tscm_sweep_visibility_params *p)
 {
     if (!p) return tscm_set_error(TSCM_E_INVALID, "vparams is NULL");
-    if (p->struct_size != (int)sizeof(tscm_sweep_visibility_params))
-        return tscm_set_error(TSCM_E_INVALID, "vparams: struct_size " + std::to_string(p->struct_size) + " is not sizeof(tscm_sweep_visibility_params) = " + std::to_string(sizeof(tscm_sweep_visibility_params)));
+    if (int rc = check_struct_size(p, "tscm_sweep_visibility_params", "vparams")) return rc;
     if (p->cell_shift < 0 || p->cell_shift > 8) return tscm_set_error(TSCM_E_INVALID, "vparams: cell_shift " + std::to_string(p->cell_shift) + " outside 0..8");
     if (p->tolerance < 0 || p->tolerance > 255) return tscm_set_error(TSCM_E_INVALID, "vparams: tolerance " + std::to_string(p->tolerance) + " outside 0..255");
     if (p->dilate < 0 || p->dilate > 2) return tscm_set_error(TSCM_E_INVALID, "vparams: dilate " + std::to_string(p->dilate) + " outside 0..2");
@@ -930,7 +883,7 @@ int launch_visibility(const tscm_sweep *s, const short *idx, const tscm_sweep_vi
 // use [n][npix] and state [npix] of the last launch_visibility, either may be NULL
 int download_use_state(const tscm_sweep *s, unsigned char *use, unsigned char *state)
 {
-    if (use) HIP_TRY(hipMemcpy2D(use, s->npix, s->v_use, s->v_plane, s->npix, (size_t)s->n, hipMemcpyDeviceToHost));
+    if (use) HIP_TRY(copy_rows(use, s->npix, s->v_use, s->v_plane, s->npix, s->n, hipMemcpyDeviceToHost));
     if (state) HIP_TRY(hipMemcpy(state, s->v_state, s->npix, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -940,35 +893,29 @@ int visibility_call(tscm_sweep *s, const short *index16, int index_stride, const
 {
     if (!s) return tscm_set_error(TSCM_E_INVALID, "s is NULL");
     if (int rc = check_visibility(p)) return rc;
-    if (!index16 && !s->has_index) return tscm_set_error(TSCM_E_INVALID, "index16 is NULL and the handle has not run tscm_sweep_depth yet");
-    if (index16 && index_stride < s->pw) return tscm_set_error(TSCM_E_INVALID, "index_stride " + std::to_string(index_stride) + " < pano_w " + std::to_string(s->pw));
+    if (int rc = check_index_map(index16, index_stride, s->has_index, s->pw)) return rc;
     if (seconds_kernel) *seconds_kernel = 0.0;
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = visibility_buffers(s)) return rc;
     const short *idx = s->index16;
     if (index16) {
-        HIP_TRY(hipMemcpy2D(s->v_index, (size_t)s->pw * sizeof(short), index16, (size_t)index_stride * sizeof(short), (size_t)s->pw * sizeof(short), (size_t)s->ph,
-                            hipMemcpyHostToDevice));
+        HIP_TRY(copy_rows(s->v_index, s->pw, index16, index_stride, s->pw, s->ph, hipMemcpyHostToDevice));
         idx = s->v_index;
     }
     const size_t nplane = (size_t)s->n * s->npix;
     DeviceMem tmp;
+    StageOutputs stages(tmp);
     VisibilityStages dev = { nullptr, nullptr, nullptr, nullptr };
-    if (host && host->hypothesis) HIP_TRY(tmp.alloc(&dev.hypothesis, s->v_plane));
-    if (host && host->cell) HIP_TRY(tmp.alloc(&dev.cell, nplane));
-    if (host && host->visible) HIP_TRY(tmp.alloc(&dev.visible, nplane));
-    HIP_TRY(hipEventRecord(s->ev[0], 0));
+    if (host) {
+        HIP_TRY(stages.scratch(&dev.hypothesis, host->hypothesis, s->npix, s->v_plane));
+        HIP_TRY(stages.scratch(&dev.cell, host->cell, nplane));
+        HIP_TRY(stages.scratch(&dev.visible, host->visible, nplane));
+    }
+    HIP_TRY(s->span.mark(0));
     if (int rc = launch_visibility(s, idx, p, host ? &dev : nullptr)) return rc;
-    HIP_TRY(hipEventRecord(s->ev[1], 0));
-    HIP_TRY(hipEventSynchronize(s->ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    HIP_TRY(s->span.finish(1, nullptr, seconds_kernel));
     if (int rc = download_use_state(s, use, state)) return rc;
-    if (host && host->hypothesis) HIP_TRY(hipMemcpy(host->hypothesis, dev.hypothesis, s->npix, hipMemcpyDeviceToHost));
-    if (host && host->cell) HIP_TRY(hipMemcpy(host->cell, dev.cell, nplane * sizeof(int), hipMemcpyDeviceToHost));
-    if (host && host->visible) HIP_TRY(hipMemcpy(host->visible, dev.visible, nplane, hipMemcpyDeviceToHost));
+    HIP_TRY(stages.fetch());
     if (host && host->depth_buffer) {                         // rank + 1 <= 256: the 32-bit cells of the atomics as uint16
         const size_t cells = (size_t)s->n * (((s->w - 1) >> p->cell_shift) + 1) * (((s->h - 1) >> p->cell_shift) + 1);
         std::vector<unsigned> z(cells);
@@ -995,19 +942,14 @@ int compose_call(tscm_sweep *s, const unsigned char *const *images, int stride, 
     if (visible)
         if (int rc = visibility_buffers(s)) return rc;
     const int wrap = params->wrap_x ? 1 : 0;                 // the pyramids' wrap is the composer's own, not the census window's
-    HIP_TRY(hipEventRecord(s->ev[0], 0));
+    HIP_TRY(s->span.mark(0));
     if (visible)
         if (int rc = launch_visibility(s, idx, vp, nullptr)) return rc;
     if (channels == 1) launch_compose<1>(s, idx, params->fallback_index, wrap, g, visible ? s->v_use : nullptr);
     else launch_compose<3>(s, idx, params->fallback_index, wrap, g, visible ? s->v_use : nullptr);
-    HIP_TRY(hipEventRecord(s->ev[1], 0));
-    HIP_TRY(hipEventSynchronize(s->ev[1]));
-    HIP_TRY(hipGetLastError());
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    if (seconds_kernel) *seconds_kernel = 1e-3 * ms;
+    HIP_TRY(s->span.finish(1, nullptr, seconds_kernel));
     const size_t row = (size_t)s->pw * channels;
-    HIP_TRY(hipMemcpy2D(dst, (size_t)dst_stride, s->c_out, row, row, (size_t)s->ph, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_rows(dst, dst_stride, s->c_out, row, row, s->ph, hipMemcpyDeviceToHost));
     if (coverage) HIP_TRY(hipMemcpy(coverage, s->c_cover, s->npix, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1054,12 +996,14 @@ int compose_stages_call(tscm_sweep *s, const unsigned char *const *images, int s
     const int n = s->n, ch = channels;
     const size_t nplane = (size_t)n * s->npix;
     DeviceMem tmp;
+    StageOutputs stages(tmp);
     unsigned char *d_hyp = nullptr, *d_sampled = nullptr, *d_alpha = nullptr;
     short *d_lap = nullptr, *d_G = s->c_G;
     size_t gstride = s->Sp;
-    if (hypothesis) HIP_TRY(tmp.alloc(&d_hyp, s->plane));
-    if (sampled) HIP_TRY(tmp.alloc(&d_sampled, nplane * ch));
-    if (alpha) HIP_TRY(tmp.alloc(&d_alpha, nplane));
+    HIP_TRY(stages.scratch(&d_hyp, hypothesis, s->npix, s->plane));
+    HIP_TRY(stages.scratch(&d_sampled, sampled, nplane * ch));
+    HIP_TRY(stages.scratch(&d_alpha, alpha, nplane));
+    stages.from(label, s->c_label, s->npix);
     if (!multiband) {                                         // SEAM and FEATHER keep no planes: the gather writes into a scratch set
         gstride = s->plane;
         HIP_TRY(tmp.alloc(&d_G, (size_t)n * ch * gstride));
@@ -1074,13 +1018,10 @@ int compose_stages_call(tscm_sweep *s, const unsigned char *const *images, int s
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    if (hypothesis) HIP_TRY(hipMemcpy(hypothesis, d_hyp, s->npix, hipMemcpyDeviceToHost));
-    if (sampled) HIP_TRY(hipMemcpy(sampled, d_sampled, nplane * ch, hipMemcpyDeviceToHost));
-    if (alpha) HIP_TRY(hipMemcpy(alpha, d_alpha, nplane, hipMemcpyDeviceToHost));
-    if (label) HIP_TRY(hipMemcpy(label, s->c_label, s->npix, hipMemcpyDeviceToHost));
-    if (mask_pyramid) if (int rc = download_pyramid(*s, s->c_mpyr, n, mask_pyramid)) return rc;
-    if (lap_pyramid) if (int rc = download_pyramid(*s, d_lap, n * ch, lap_pyramid)) return rc;
-    if (blend_pyramid) if (int rc = download_pyramid(*s, s->c_B, ch, blend_pyramid)) return rc;
+    HIP_TRY(stages.fetch());
+    if (int rc = download_pyramid(*s, s->c_mpyr, n, mask_pyramid)) return rc;
+    if (int rc = download_pyramid(*s, d_lap, n * ch, lap_pyramid)) return rc;
+    if (int rc = download_pyramid(*s, s->c_B, ch, blend_pyramid)) return rc;
     if (visible) return download_use_state(s, use_out, state_out);
     return 0;
 }
@@ -1157,7 +1098,7 @@ extern "C" int tscm_sweep_points(const short *index16, int pano_w, int pano_h, i
     unsigned char *d_valid = nullptr;
     HIP_TRY(mem.alloc(&d_idx, npix)); HIP_TRY(mem.alloc(&d_pts, 3 * npix)); HIP_TRY(mem.alloc(&d_valid, npix));
     HIP_TRY(mem.upload(&d_inv, inv_distance, (size_t)D));
-    HIP_TRY(hipMemcpy2D(d_idx, (size_t)pano_w * sizeof(short), index16, (size_t)stride * sizeof(short), (size_t)pano_w * sizeof(short), (size_t)pano_h, hipMemcpyHostToDevice));
+    HIP_TRY(copy_rows(d_idx, pano_w, index16, stride, pano_w, pano_h, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_sweep_points, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, 0, d_idx, pano_w, pano_h, projection, pano_map->fx, pano_map->fy, pano_map->cx,
                        pano_map->cy, d_inv, D, d_pts, d_valid);
     HIP_TRY(hipGetLastError());

@@ -360,6 +360,24 @@ def lib():
     return L
 
 
+def _params_struct(struct, default_fn: str, names, what, over: dict, enums=None):
+    """`struct` filled by the library's `default_fn`, then the fields in `over` replaced.  names: the fields a caller may
+    set; another one raises TypeError naming `what`, or AttributeError where `what` is None.  enums: {field: (kind, {string:
+    value})} for the fields that also take a string."""
+    p = struct()
+    getattr(lib(), default_fn)(C.byref(p))
+    for k, v in over.items():
+        if k not in names:                  # the sweep's builders have always raised AttributeError, the stereo ones TypeError with a text
+            raise AttributeError(k) if what is None else TypeError(f"unknown {what} parameter {k!r}: one of {', '.join(names)}")
+        if enums and k in enums and isinstance(v, str):
+            kind, table = enums[k]
+            if v not in table:
+                raise ValueError(f"unknown {kind} {v!r}: one of {', '.join(table)}")
+            v = table[v]
+        setattr(p, k, int(v))
+    return p
+
+
 def loss_args(loss) -> tuple:
     """(kind, scale) of the C ABI from None, a kind name, or a (kind name, scale in pixels) pair."""
     if loss is None:

@@ -22,13 +22,7 @@ FILL_RULES = dict(lowest=_lib.FILL_LOWEST, second_lowest=_lib.FILL_SECOND_LOWEST
 
 def params(**over) -> _lib.CStereoParams:
     """tscm_stereo_default_params with the given fields replaced."""
-    p = _lib.CStereoParams()
-    _lib.lib().tscm_stereo_default_params(C.byref(p))
-    for k, v in over.items():
-        if k not in PARAM_NAMES:
-            raise TypeError(f"unknown stereo parameter {k!r}: one of {', '.join(PARAM_NAMES)}")
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CStereoParams, "tscm_stereo_default_params", PARAM_NAMES, "stereo", over)
 
 
 def _gray(img) -> np.ndarray:
@@ -55,10 +49,7 @@ def match(left, right, device: int = 0, out: np.ndarray | None = None, with_seco
     left, right = _pair(left, right)
     h, w = left.shape
     p = params(**over)
-    if out is None:
-        out = np.zeros((h, w), dtype=np.int16)
-    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
-        raise ValueError("out must be an int16 array (or row-padded view) of the images' shape")
+    out = _out_map(out, h, w, "images'")
     ub = C.POINTER(C.c_ubyte)
     sec = C.c_double(0.0)
     _lib.check(_lib.lib().tscm_stereo_match(left.ctypes.data_as(ub), right.ctypes.data_as(ub), w, h, left.strides[0] if h else w, C.byref(p), device,
@@ -89,13 +80,7 @@ def stage_times() -> dict:
 
 def filter_params(**over) -> _lib.CStereoFilterParams:
     """tscm_stereo_filter_default_params with the given fields replaced."""
-    p = _lib.CStereoFilterParams()
-    _lib.lib().tscm_stereo_filter_default_params(C.byref(p))
-    for k, v in over.items():
-        if k not in FILTER_PARAM_NAMES:
-            raise TypeError(f"unknown stereo filter parameter {k!r}: one of {', '.join(FILTER_PARAM_NAMES)}")
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CStereoFilterParams, "tscm_stereo_filter_default_params", FILTER_PARAM_NAMES, "stereo filter", over)
 
 
 def _disparity_map(disp) -> np.ndarray:
@@ -107,16 +92,22 @@ def _disparity_map(disp) -> np.ndarray:
     return disp
 
 
+def _out_map(out, h: int, w: int, whose: str = "map's") -> np.ndarray:
+    """the caller's `out`, checked, or a new int16 [h, w] map"""
+    if out is None:
+        return np.zeros((h, w), dtype=np.int16)
+    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
+        raise ValueError(f"out must be an int16 array (or row-padded view) of the {whose} shape")
+    return out
+
+
 def filter(disp, device: int = 0, out: np.ndarray | None = None, with_seconds: bool = False, **over):
     """tscm_stereo_filter: speckle removal and masked median of a disparity map -> int16 [h, w].  `disp` may be a
     row-padded view; `out` may be one too (its padding keeps its values) and may be `disp` itself."""
     disp = _disparity_map(disp)
     h, w = disp.shape
     p = filter_params(**over)
-    if out is None:
-        out = np.zeros((h, w), dtype=np.int16)
-    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
-        raise ValueError("out must be an int16 array (or row-padded view) of the map's shape")
+    out = _out_map(out, h, w)
     sp = C.POINTER(C.c_short)
     sec = C.c_double(0.0)
     _lib.check(_lib.lib().tscm_stereo_filter(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, C.byref(p), device,
@@ -139,17 +130,7 @@ def filter_stages(disp, device: int = 0, **over) -> dict:
 
 def fill_params(**over) -> _lib.CStereoFillParams:
     """tscm_stereo_fill_default_params with the given fields replaced; rule also as "lowest" | "second_lowest" | "median"."""
-    p = _lib.CStereoFillParams()
-    _lib.lib().tscm_stereo_fill_default_params(C.byref(p))
-    for k, v in over.items():
-        if k not in FILL_PARAM_NAMES:
-            raise TypeError(f"unknown stereo fill parameter {k!r}: one of {', '.join(FILL_PARAM_NAMES)}")
-        if k == "rule" and isinstance(v, str):
-            if v not in FILL_RULES:
-                raise ValueError(f"unknown fill rule {v!r}: one of {', '.join(FILL_RULES)}")
-            v = FILL_RULES[v]
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CStereoFillParams, "tscm_stereo_fill_default_params", FILL_PARAM_NAMES, "stereo fill", over, {"rule": ("fill rule", FILL_RULES)})
 
 
 def fill(disp, device: int = 0, out: np.ndarray | None = None, with_mask: bool = False, with_seconds: bool = False, **over):
@@ -160,10 +141,7 @@ def fill(disp, device: int = 0, out: np.ndarray | None = None, with_mask: bool =
     disp = _disparity_map(disp)
     h, w = disp.shape
     p = fill_params(**over)
-    if out is None:
-        out = np.zeros((h, w), dtype=np.int16)
-    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
-        raise ValueError("out must be an int16 array (or row-padded view) of the map's shape")
+    out = _out_map(out, h, w)
     mask = np.zeros((h, w), dtype=np.uint8) if with_mask else None
     sp = C.POINTER(C.c_short)
     sec = C.c_double(0.0)
@@ -192,13 +170,7 @@ def fill_stages(disp, device: int = 0, **over) -> dict:
 
 def refine_params(**over) -> _lib.CStereoRefineParams:
     """tscm_stereo_refine_default_params with the given fields replaced."""
-    p = _lib.CStereoRefineParams()
-    _lib.lib().tscm_stereo_refine_default_params(C.byref(p))
-    for k, v in over.items():
-        if k not in REFINE_PARAM_NAMES:
-            raise TypeError(f"unknown stereo refine parameter {k!r}: one of {', '.join(REFINE_PARAM_NAMES)}")
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CStereoRefineParams, "tscm_stereo_refine_default_params", REFINE_PARAM_NAMES, "stereo refine", over)
 
 
 def range_weights(sigma: float) -> np.ndarray:
@@ -239,10 +211,7 @@ def refine(disp, guide, device: int = 0, out: np.ndarray | None = None, weights=
     disp, g, table = _refine_args(disp, guide, weights, sigma)
     h, w = disp.shape
     p = refine_params(**over)
-    if out is None:
-        out = np.zeros((h, w), dtype=np.int16)
-    if out.dtype != np.int16 or out.shape != (h, w) or (w and out.strides[1] != 2) or out.strides[0] % 2:
-        raise ValueError("out must be an int16 array (or row-padded view) of the map's shape")
+    out = _out_map(out, h, w)
     sp, ub = C.POINTER(C.c_short), C.POINTER(C.c_ubyte)
     sec = C.c_double(0.0)
     _lib.check(_lib.lib().tscm_stereo_refine(disp.ctypes.data_as(sp), w, h, disp.strides[0] // 2 if h else w, g.ctypes.data_as(ub), g.strides[0] if h else w,
@@ -267,6 +236,19 @@ def refine_stages(disp, guide, device: int = 0, weights=None, sigma=None, **over
                                                     res["weight_sum"].ctypes.data_as(C.POINTER(C.c_int)), res["count"].ctypes.data_as(ub),
                                                     res["first_pass"].ctypes.data_as(sp)))
     return res
+
+
+def _post_fill_refine(disp, post, fill, refine, min_disparity: int, wrap_x, guide, device: int) -> np.ndarray:
+    """filter -> fill -> refine of a disparity or index map, each for a dict of its arguments that is not None.  wrap_x: None,
+    or what fill and refine take where their dict does not say; guide(map) yields the guide of refine."""
+    wrap = {} if wrap_x is None else {"wrap_x": wrap_x}
+    if post is not None:
+        disp = filter(disp, device=device, min_disparity=min_disparity, **post)
+    if fill is not None:
+        disp = _fill(disp, device=device, min_disparity=min_disparity, **{**wrap, **fill})
+    if refine is not None:
+        disp = _refine(disp, guide(disp), device=device, min_disparity=min_disparity, **{**wrap, **refine})
+    return disp
 
 
 def points(disp, desc, baseline: float, min_disparity: int = 0, device: int = 0):
@@ -313,12 +295,7 @@ def pair_depth(img_a, img_b, intr_a, Twc_a, intr_b, Twc_b, projection="longlat",
         mx, my, _ = _maps.build_maps([d], device=device)
         rect.append(_maps.remap(_gray(img), mx.reshape(height, width), my.reshape(height, width), device=device))
     disp = matcher(rect[0], rect[1], **over) if matcher is not None else match(rect[0], rect[1], device=device, **over)
-    if post is not None:
-        disp = filter(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **post)
-    if fill is not None:
-        disp = _fill(disp, device=device, min_disparity=int(over.get("min_disparity", 0)), **fill)
-    if refine is not None:
-        disp = _refine(disp, rect[0], device=device, min_disparity=int(over.get("min_disparity", 0)), **refine)
+    disp = _post_fill_refine(disp, post, fill, refine, int(over.get("min_disparity", 0)), None, lambda d: rect[0], device)
     Ta, Tb = np.asarray(Twc_a, dtype=np.float64).reshape(3, 4), np.asarray(Twc_b, dtype=np.float64).reshape(3, 4)
     baseline = float(np.linalg.norm(Tb[:, 3] - Ta[:, 3]))
     pts, valid = points(disp, descs[0], baseline, min_disparity=int(over.get("min_disparity", 0)), device=device)

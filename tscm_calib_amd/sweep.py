@@ -14,42 +14,25 @@ from . import maps as _maps
 INVALID = -16
 
 
+def _fields(struct) -> tuple:
+    return tuple(k for k, _ in struct._fields_ if k != "struct_size")
+
+
 def params(**over) -> _lib.CSweepParams:
     """tscm_sweep_default_params with fields replaced: num_hypotheses, p1, p2, paths, uniqueness_ratio, wrap_x."""
-    p = _lib.CSweepParams()
-    _lib.lib().tscm_sweep_default_params(C.byref(p))
-    for k, v in over.items():
-        if k == "struct_size" or not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CSweepParams, "tscm_sweep_default_params", _fields(_lib.CSweepParams), None, over)
 
 
 def compose_params(**over) -> _lib.CSweepComposeParams:
     """tscm_sweep_compose_default_params with fields replaced: mode ("seam", "feather", "multiband" or TSCM_PANO_*), levels,
     wrap_x, fallback_index."""
-    p = _lib.CSweepComposeParams()
-    _lib.lib().tscm_sweep_compose_default_params(C.byref(p))
-    for k, v in over.items():
-        if k == "struct_size" or not hasattr(p, k):
-            raise AttributeError(k)
-        if k == "mode" and isinstance(v, str):
-            if v not in _lib.PANO_MODES:
-                raise ValueError(f"unknown mode {v!r}: one of {', '.join(_lib.PANO_MODES)}")
-            v = _lib.PANO_MODES[v]
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CSweepComposeParams, "tscm_sweep_compose_default_params", _fields(_lib.CSweepComposeParams), None, over,
+                              {"mode": ("mode", _lib.PANO_MODES)})
 
 
 def visibility_params(**over) -> _lib.CSweepVisibilityParams:
     """tscm_sweep_visibility_default_params with fields replaced: cell_shift, tolerance, dilate, near_is_high."""
-    p = _lib.CSweepVisibilityParams()
-    _lib.lib().tscm_sweep_visibility_default_params(C.byref(p))
-    for k, v in over.items():
-        if k == "struct_size" or not hasattr(p, k):
-            raise AttributeError(k)
-        setattr(p, k, int(v))
-    return p
+    return _lib._params_struct(_lib.CSweepVisibilityParams, "tscm_sweep_visibility_default_params", _fields(_lib.CSweepVisibilityParams), None, over)
 
 
 def _visibility_struct(visibility) -> _lib.CSweepVisibilityParams:
@@ -348,12 +331,11 @@ def _check_refine(refine):
         raise TypeError("refine: min_disparity is 0 for an index map")
 
 
-def _refine_index(s, grey, idx, refine, fallback_index, device):
-    """stereo.refine of an index map (wrap_x = 1 unless the dict says otherwise), guided by the grey frame that the sweeper
-    composes in SEAM mode at that map"""
+def _post_fill_refine(s, grey, idx, post, fill, refine, fallback_index, device):
+    """The chain of stereo on an index map: min_disparity 0, wrap_x = 1 unless a dict says otherwise, refine guided by the
+    grey frame that the sweeper composes in SEAM mode at the map as it stands."""
     from . import stereo
-    guide = s.compose(grey, index16=idx, mode="seam", fallback_index=fallback_index)
-    return stereo.refine(idx, guide, device=device, min_disparity=0, **{"wrap_x": 1, **refine})
+    return stereo._post_fill_refine(idx, post or None, fill, refine, 0, 1, lambda m: s.compose(grey, index16=m, mode="seam", fallback_index=fallback_index), device)
 
 
 def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: float = 500.0, far: float = np.inf, D: int = 64, weights="radial",
@@ -371,14 +353,7 @@ def rig_depth(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near: fl
     inv = inverse_distances(near, far, D)
     with Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv, weights=weights, projection=projection, device=device, **over) as s:
         idx = s.depth(images)
-        if post:
-            from . import stereo
-            idx = stereo.filter(idx, min_disparity=0, device=device, **post)
-        if fill is not None:
-            from . import stereo
-            idx = stereo.fill(idx, device=device, min_disparity=0, **{"wrap_x": 1, **fill})
-        if refine is not None:
-            idx = _refine_index(s, images, idx, refine, 0, device)
+        idx = _post_fill_refine(s, images, idx, post, fill, refine, 0, device)
         pts, valid = s.points(idx)
     return idx, pts, valid
 
@@ -403,13 +378,6 @@ def rig_panorama(images, intr, Twc, pano_w: int = 1024, pano_h: int = 512, near:
     with Sweeper.from_rig(intr, Twc, size, pano_w, pano_h, inv, weights=weights, projection=projection, device=device, **over) as s:
         grey = [bgr_to_gray(x) for x in images]
         idx = s.depth(grey)
-        if post:
-            from . import stereo
-            idx = stereo.filter(idx, min_disparity=0, device=device, **post)
-        if fill is not None:
-            from . import stereo
-            idx = stereo.fill(idx, device=device, min_disparity=0, **{"wrap_x": 1, **fill})
-        if refine is not None:
-            idx = _refine_index(s, grey, idx, refine, fallback_index, device)
+        idx = _post_fill_refine(s, grey, idx, post, fill, refine, fallback_index, device)
         pano, cov = s.compose(images, index16=idx if post or fill is not None or refine is not None else None, gains=gains, with_coverage=True, visibility=visibility, mode=mode, levels=levels, fallback_index=fallback_index)
     return pano, idx, cov
