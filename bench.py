@@ -31,16 +31,23 @@ TSCM_BENCH_EXCHANGE=ipc replaces RCCL by the library's IPC exchange back-end (ts
 share a device (rank r on device r mod n_devices) -- the multi-process path on a one-GPU box; the line says "exchange": "ipc" and
 that it is not a scaling measurement.  Without it, more ranks than devices is an error.
 
-Before anything is timed (all of it untimed, none of it skipping work inside the timed region): the device's fp64
-ceilings are measured (three dense kernels, ~70 ms: they are part of the roofline block anyway and leave the device
-at sustained clocks), the natural solve runs, and the hot path itself is run for TSCM_BENCH_PREHEAT_MS (60 ms) -- then
-the W warmup steps of the contract, the barrier, and exactly K timed steps.  With 5 warmup steps alone the first
-timed steps ran on a device still ramping from idle (dominant kernel 62 us instead of 55-57).
+A plain run does what the headline figure needs and nothing else: it builds the workload, creates the solver, runs the
+hot path itself for TSCM_BENCH_PREHEAT_MS (60 ms, untimed) -- then the W warmup steps of the contract, the barrier, and
+exactly K timed steps -- writes --dump-outputs if asked and prints the line.  With 5 warmup steps alone the first timed
+steps ran on a device still ramping from idle (dominant kernel 62 us instead of 55-57).
+
+--full adds everything else the benchmark measures or checks, all of it untimed and none of it touching the timed
+region: before the preheat the device's fp64 ceilings (three dense kernels, ~70 ms; with --jacobian-fp32 the fp32 MFMA
+ceiling too) and the natural solve (reference options, termination tests on); after the timed steps the roofline
+block's comparison with those ceilings and with the recorded HBM traffic (profiles/pmc_eval_gram.json), and
+`cpu_baseline` -- the CPU oracle (a plain-C port of the reference's Ceres path) on the full workload, 1 thread like
+the reference, plus an all-cores figure and the parity of the GPU's result with it (--no-cpu-baseline leaves that one
+out of a --full run).  The timed steps, their inputs and the line's headline fields are the same with and without it.
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel k_eval_gram4, timed with HIP events on the
-solver's own stream (the event pair rides in the kernel's dispatch: hipExtLaunchKernelGGL); `cpu_baseline` is the CPU
-oracle (a plain-C port of the reference's Ceres path) on the full workload, 1 thread like the reference, plus an
-all-cores figure.
+solver's own stream (the event pair rides in the kernel's dispatch: hipExtLaunchKernelGGL) inside the timed region of
+every run; its `peak_measured_*`, `measured_floor_ms`, `frac_of_measured_ceiling` and `traffic*` entries, `natural_solve`
+and `cpu_baseline` are in the line of a --full run only.
 """
 import argparse
 import hashlib
@@ -327,7 +334,12 @@ def main():
     ap.add_argument("--board", default="9x6", metavar="CxR",
                     help="inner corners of the chessboard (default 9x6: BASELINE's workload and the headline; 11x8 is the reference's own "
                          "board, main.cpp:190-191).  The board keeps its 360 mm extent, the views / frames of --config are unchanged")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need (all untimed): the device's measured fp64 / fp32 "
+                         "ceilings and the roofline entries built on them, the recorded HBM traffic, the natural solve, and the CPU "
+                         "baseline with the GPU's parity against it.  Off by default: a plain run sets up, warms up, times the steps "
+                         "and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline (~35 s) out")
     ap.add_argument("--exec-flags", type=int, default=0,
                     help="tscm_options.exec_flags for every solve (A/B runs: 4 = TSCM_EXEC_GRAM_16X16, 1 = separate T reduction)")
     ap.add_argument("--jacobian-fp32", action="store_true",
@@ -410,24 +422,23 @@ def main():
         if chan:
             chan.barrier()
 
-    # measured fp64 ceilings of THIS device (three dense kernels, ~50 ms), before anything is timed: they also take the
-    # device from its idle state to sustained clocks -- with 5 warmup steps (0.7 ms) alone the first timed steps run
-    # on a device that is still ramping (k_eval_gram4 62 us instead of 57)
+    # --full: measured fp64 ceilings of THIS device (three dense kernels, ~50 ms), before anything is timed
     pk = None
-    if not stub:
+    if args.full and not stub:
         import ctypes
         pk = (ctypes.c_double * 3)()
         lib.check(lib.lib().tscm_device_peak_fp64_ex(device, pk))
         pk32 = ctypes.c_double(0.0)
         if args.jacobian_fp32:
             lib.check(lib.lib().tscm_device_peak_fp32_mfma(device, ctypes.byref(pk32)))
-    # natural solve (reference options, termination tests on): untimed, doubles as warmup
     extra = dict(jacobian_fp32=1) if args.jacobian_fp32 else {}
     if args.exec_flags:
         extra["exec_flags"] = args.exec_flags
-    natural = solver.solve_resident(reset=True, **extra)
-    # the hot path itself for PREHEAT_MS before the W warmup steps (untimed): the fp64 ceilings above leave the device
-    # at sustained clocks, this keeps it there through the host-side work in between
+    # --full: natural solve (reference options, termination tests on), untimed
+    natural = solver.solve_resident(reset=True, **extra) if args.full else None
+    # the hot path itself for PREHEAT_MS before the W warmup steps (untimed): it takes the device from its idle state to
+    # sustained clocks -- with 5 warmup steps (0.7 ms) alone the first timed steps run on a device that is still
+    # ramping (k_eval_gram4 62 us instead of 57)
     t_pre = time.perf_counter()
     while not stub and (time.perf_counter() - t_pre) * 1e3 < PREHEAT_MS:
         run_iterations(solver, ITERS_PER_SOLVE, **extra)
@@ -488,7 +499,7 @@ def main():
             # over the wall time of a step on all N GPUs -- LM iterations/s follows this figure, not the kernel's `frac`
             "iteration_frac": (full.n_corners * FLOP_PER_CORNER / (elapsed / args.steps) / 1e12) / (peak * world) if elapsed > 0 else 0.0,
         }
-        if not stub and args.jacobian_fp32:
+        if pk is not None and args.jacobian_fp32:
             # fp32-Jacobian tier: the contraction (836 flop per corner) runs on v_mfma_f32_16x16x4, the projection and
             # residual in fp64 and the derivatives in packed fp32 on the VALU.  `peak` above is the fp32 datasheet figure
             # (what BASELINE's "fp64 vs fp32" asks to see); the floor prices the 600 VALU flop at the measured fp64 VALU
@@ -496,7 +507,7 @@ def main():
             floor_ms = 1e3 * n_local * (FLOP_MFMA_PER_CORNER / (pk32.value * 1e12) + FLOP_VALU_PER_CORNER / (pk[2] * 1e12))
             roof.update(peak_measured_mfma_f32_16x16x4=pk32.value, peak_measured_valu_f64=pk[2], measured_floor_ms=floor_ms,
                         frac_of_measured_ceiling=floor_ms / avg_ms if avg_ms > 0 else 0.0)
-        if not stub and not args.jacobian_fp32:
+        if pk is not None and not args.jacobian_fp32:
             # measured ceilings of THIS device (taken before the warmup).  fp64 MFMA and fp64 VALU share the DP pipe
             # (no overlap: tools/ubench_fp64.hip), so the kernel's floor is the SUM of its two parts at their own rates
             # the kernel contracts with v_mfma_f64_4x4x4_4b (TSCM_EXEC_GRAM_16X16: with v_mfma_f64_16x16x4): its ceiling
@@ -547,12 +558,13 @@ def main():
             # (the IPC back-end between DEVICES -- fine-grained buffers, explicit peer access: ABI 6 -- has never met a second device)
             "exchange_note": ("IPC exchange across devices: correct by construction, never measured; RCCL is the production back-end"
                               if multi and exchange == "ipc" and not stub and min(world, n_dev) > 1 else None),
-            "natural_solve": {"termination": natural["message"], "iterations": natural["num_iterations"] - 1,
-                              "rmse_px": natural["rmse"], "seconds": natural["seconds_total"],
-                              "device_seconds": natural["seconds_solve"],
-                              "create_seconds_incl_H2D_of_observations": t_create},
             "roofline": roof,
         }
+        if natural is not None:
+            out["natural_solve"] = {"termination": natural["message"], "iterations": natural["num_iterations"] - 1,
+                                    "rmse_px": natural["rmse"], "seconds": natural["seconds_total"],
+                                    "device_seconds": natural["seconds_solve"],
+                                    "create_seconds_incl_H2D_of_observations": t_create}
         if world > 1 or multi:
             # per iteration every rank runs its share of the kernels plus two sum all-reduces (T after the Schur
             # complement, H_stage after the evaluation); an all-reduce's HIP-event time includes the wait for the
@@ -566,7 +578,7 @@ def main():
                 "timed_every": stride, "note": "HIP events on the solver stream around the all-reduce (ncclAllReduce, or the IPC back-end's kernel: the wait for the slowest peer included), max over ranks of each rank's mean",
             }
             out["per_rank"] = per_rank
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = cpu_baseline(full, local_rank)
         print(json.dumps(out), flush=True)
     if chan:

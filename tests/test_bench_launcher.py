@@ -103,6 +103,22 @@ def test_single_process_default_is_untouched():
     assert d["n_gpus"] == 1 and 0.9 <= d["ms_per_step"] < 2.5
 
 
+def test_full_is_an_option_and_off_by_default():
+    """A plain run sets up, warms up, times the steps and prints the line; the natural solve (like the measured ceilings and the
+    CPU baseline, which the stub does not have) belongs to --full.  The headline fields are there either way."""
+    lines = {}
+    for extra in ((), ("--full",)):
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", *extra],
+                             env=_clean_env(TSCM_BENCH_STUB="1"), capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0, out.stderr
+        lines[extra] = d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"} <= set(d)
+        assert d["steps"] == 5 and d["warmup"] == 2 and 0.9 <= d["ms_per_step"] < 2.5
+    assert "natural_solve" not in lines[()] and "cpu_baseline" not in lines[()]
+    assert lines[("--full",)]["natural_solve"]["iterations"] == 50
+    assert set(lines[("--full",)]) - set(lines[()]) == {"natural_solve"}
+
+
 def test_a_failing_rank_takes_the_job_down():
     """A rank that dies must not leave its peers (and the launcher) waiting for it forever."""
     # (the real case is a rank whose device does not exist; the stub's rank 1 exits before the rendezvous instead)

@@ -1,6 +1,7 @@
 """bench.py on the GPU: the multi-process entry point (launcher -> rank process -> TCP side channel -> RCCL communicator)
 with ONE rank, which is all a one-GPU box can run (RCCL refuses two ranks on a device), and the plain single-process
-line next to it.  Config 3 keeps it short."""
+line next to it.  Config 3 keeps it short.  The tests that read the natural solve or the measured ceilings run the benchmark
+with --full (without the CPU baseline); the others run it plain."""
 import json
 import os
 import subprocess
@@ -14,11 +15,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
 
-def _run(env_extra, *args):
+def _run(env_extra, *args, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
                                                             "TSCM_RDZV_PORT", "TSCM_BENCH_FORCE_DIST", "TSCM_BENCH_STUB")}
     env.update(env_extra)
-    out = subprocess.run([sys.executable, BENCH, "--config", "3", "--steps", "20", "--warmup", "10", "--no-cpu-baseline", *args],
+    more = ("--full", "--no-cpu-baseline") if full else ()
+    out = subprocess.run([sys.executable, BENCH, "--config", "3", "--steps", "20", "--warmup", "10", *more, *args],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -50,7 +52,7 @@ def test_more_ranks_than_gpus_fails_loudly(hip_device):
     from tscm_calib_amd import lib
     n = lib.lib().tscm_device_count()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, BENCH, "--config", "3", "--gpus", str(n + 1), "--steps", "5", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, BENCH, "--config", "3", "--gpus", str(n + 1), "--steps", "5"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode != 0
     assert "needs" in out.stderr and "GPUs" in out.stderr
@@ -97,7 +99,7 @@ def test_the_drivers_torchrun_command_with_two_ranks_on_this_device(hip_device):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["TSCM_BENCH_EXCHANGE"] = "ipc"
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), BENCH, "--gpus", "2", "--config", "3", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+                          "--master-port", str(port), BENCH, "--gpus", "2", "--config", "3", "--steps", "20", "--warmup", "5"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
@@ -122,12 +124,18 @@ def test_a_rank_that_is_gone_is_reported_not_waited_for(hip_device):
 
 def test_dump_outputs_are_what_the_timed_solve_computes(hip_device, tmp_path):
     """--dump-outputs: the arrays of the last timed solve (config 3, --steps 20: one solve of 20 forced iterations) against the
-    same solve run here through the API from the same start -- what a caller of the timed path receives."""
+    same solve run here through the API from the same start -- what a caller of the timed path receives.  A plain run (no
+    --full): its line has the headline fields and the dominant kernel's HIP-event figures, and none of what --full adds."""
     import numpy as np
     import bench
     from tscm_calib_amd import api, synth
-    d = _run({}, "--dump-outputs", str(tmp_path))
+    d = _run({}, "--dump-outputs", str(tmp_path), full=False)
     assert d["steps"] == 20
+    assert d["unit"] == "LM iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6
+    assert d["roofline"]["launches"] > 0 and d["roofline"]["avg_launch_ms"] > 0 and d["roofline"]["traffic"] is None
+    assert not {"natural_solve", "cpu_baseline"} & set(d)
+    assert not [k for k in d["roofline"] if k.startswith("peak_measured") or "measured_ceiling" in k or "measured_floor" in k]
     got = {n[:-4]: np.load(tmp_path / n) for n in os.listdir(tmp_path)}
     assert all(a.dtype == np.float64 for a in got.values())
     with api.Solver(synth.make_config(3), device=hip_device) as s:

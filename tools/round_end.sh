@@ -42,13 +42,13 @@ if [ "$part" = "1" ]; then
   fi
   tail -14 $o/${t}_prof.txt; tail -12 $o/${t}_c5_prof.txt; cat $o/${t}_shards_config4_bench.json $o/${t}_shards_config5_bench.json
 elif [ "$part" = "2" ]; then
-  python3 bench.py > $o/${t}_bench.json 2> $o/${t}_bench.err
+  python3 bench.py --full > $o/${t}_bench.json 2> $o/${t}_bench.err
   python3 bench.py --gpus 1 --steps 20 --warmup 5 > $o/${t}_bench_driver.json 2> /dev/null
-  python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline > $o/${t}_bench_100.json 2> /dev/null
-  python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --jacobian-fp32 > $o/${t}_bench_100_f32.json 2> /dev/null
-  python3 bench.py --config 5 --steps 100 --warmup 10 --no-cpu-baseline > $o/${t}_c5_bench.json 2> /dev/null
-  python3 bench.py --config 5 --steps 100 --warmup 10 --no-cpu-baseline --jacobian-fp32 > $o/${t}_c5_bench_f32.json 2> /dev/null
-  for c in 1 2 3; do python3 bench.py --config $c --steps 100 --warmup 10 --no-cpu-baseline > $o/${t}_c${c}_bench.json 2> /dev/null; done
+  python3 bench.py --steps 100 --warmup 20 --full --no-cpu-baseline > $o/${t}_bench_100.json 2> /dev/null
+  python3 bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --jacobian-fp32 > $o/${t}_bench_100_f32.json 2> /dev/null
+  python3 bench.py --config 5 --steps 100 --warmup 10 --full --no-cpu-baseline > $o/${t}_c5_bench.json 2> /dev/null
+  python3 bench.py --config 5 --steps 100 --warmup 10 --full --no-cpu-baseline --jacobian-fp32 > $o/${t}_c5_bench_f32.json 2> /dev/null
+  for c in 1 2 3; do python3 bench.py --config $c --steps 100 --warmup 10 --full --no-cpu-baseline > $o/${t}_c${c}_bench.json 2> /dev/null; done
   line ${t}_bench ${t}_bench_driver ${t}_bench_100 ${t}_bench_100_f32 ${t}_c5_bench ${t}_c5_bench_f32 ${t}_c1_bench ${t}_c2_bench ${t}_c3_bench
 else
   newest() { ls -t $o/prof_$1/*/*_kernel_stats.csv | head -1; }
