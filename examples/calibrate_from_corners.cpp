@@ -5,9 +5,12 @@
 //       -Wl,-rpath,$PWD/tscm_calib_amd/csrc -o examples/calibrate_from_corners        (one command line)
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
 //                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
+//                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
-//    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve)
+//    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
+//    --ransac: the start poses come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view without consensus leaves
+//    the calibration, and per camera the views kept and the share of inlier corners are printed)
 #include <tscm/tscm_calib.hpp>
 
 #include <cstdio>
@@ -19,7 +22,9 @@ int main(int argc, char **argv)
     int loss = TSCM_LOSS_NONE;
     double loss_scale = 1.0;
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
-    bool bad_args = argc < 3;
+    bool bad_args = argc < 3, use_ransac = false;
+    tscm_ransac_params ransac;
+    tscm_ransac_default_params(&ransac);
     for (int i = 3; i < argc && !bad_args; ++i) {
         if (!std::strcmp(argv[i], "--loss") && i + 1 < argc) {
             const char *k = argv[++i];
@@ -33,13 +38,16 @@ int main(int argc, char **argv)
             unsigned short w = 0;
             bad_args = !tscm::fixed_list_mask(argv[++i], w);
             fix = (unsigned short)(fix | w);
+        } else if (!std::strcmp(argv[i], "--ransac") && i + 1 < argc) {
+            use_ransac = true;
+            bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
         } else {
             bad_args = true;
         }
     }
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -64,7 +72,9 @@ int main(int argc, char **argv)
             }
             cameras[m].set_loss(loss, loss_scale);
             cameras[m].set_fixed_intrinsics(fixed);                          // (a fresh calibrate starts at xi = lambda = 0)
+            if (use_ransac) cameras[m].set_ransac(&ransac);
             const bool ok = cameras[m].calibrate(pixels, has, worlds, image, board);
+            if (use_ransac) tscm::print_ransac_summary(cameras[m], has, m);
             std::printf("camera %d: %s, rmse %.4f px, fx %.3f fy %.3f cx %.3f cy %.3f xi %.4f lambda %.4f alpha %.4f\n", m, ok ? "converged" : "NOT converged",
                         cameras[m].summary.rmse, cameras[m].intrinsic_[0], cameras[m].intrinsic_[1], cameras[m].intrinsic_[2], cameras[m].intrinsic_[3],
                         cameras[m].intrinsic_[4], cameras[m].intrinsic_[5], cameras[m].intrinsic_[6]);

@@ -4,8 +4,11 @@
 // Images are 8-bit binary PGM files (P5); the list file holds one line per camera: "<n_frames> path_0 path_1 ..." with "-"
 // for a frame the camera has no image of.  The viewer and the drawing calls of main.cpp are left out.
 //   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
+//                                [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]
 //   (--model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
-//    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve)
+//    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
+//    --ransac: the start poses of both calibrate() calls come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view
+//    without consensus leaves the calibration, and per camera the views kept and the share of inlier corners are printed)
 #include <tscm/tscm_calib.hpp>
 
 #include <cstdio>
@@ -81,6 +84,7 @@ void monocular_calib(const std::vector<Image> &images, double size, tscm::Size b
         }
     }
     const bool ok = cam.calibrate(pixels, has, worlds, img_size, board);       // :127
+    if (cam.use_ransac_) tscm::print_ransac_summary(cam, has, -1);
     int n_has = 0;
     for (int i = 0; i < V; ++i) n_has += has[i] ? 1 : 0;
     std::printf("%s, boards %d of %d, rmse %.4f px, fx %.3f fy %.3f cx %.3f cy %.3f xi %.4f lambda %.4f alpha %.4f\n", ok ? "converged" : "NOT converged", n_has, V,
@@ -93,7 +97,9 @@ int main(int argc, char **argv)
 {
     std::vector<const char *> pos;                  // positional arguments: list, yaml, then cols rows pitch
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
-    bool bad_args = false;
+    bool bad_args = false, use_ransac = false;
+    tscm_ransac_params ransac;
+    tscm_ransac_default_params(&ransac);
     for (int i = 1; i < argc && !bad_args; ++i) {
         if (!std::strcmp(argv[i], "--model") && i + 1 < argc) {
             bad_args = !tscm::model_mask(argv[++i], model);
@@ -101,12 +107,18 @@ int main(int argc, char **argv)
             unsigned short w = 0;
             bad_args = !tscm::fixed_list_mask(argv[++i], w);
             fix = (unsigned short)(fix | w);
+        } else if (!std::strcmp(argv[i], "--ransac") && i + 1 < argc) {
+            use_ransac = true;
+            bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
+        } else if (!std::strcmp(argv[i], "--ransac")) {
+            bad_args = true;
         } else {
             pos.push_back(argv[i]);
         }
     }
     if (bad_args || pos.size() < 2) {
-        std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] "
+                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -133,6 +145,7 @@ int main(int argc, char **argv)
         for (size_t m = 0; m < images.size(); ++m) {
             std::printf("camera %zu: ", m);
             cameras[m].set_fixed_intrinsics(fixed);                            // (the first calibrate starts at xi = lambda = 0)
+            if (use_ransac) cameras[m].set_ransac(&ransac);
             monocular_calib(images[m], size, board, worlds, cameras[m]);
         }
         if (cameras.size() > 1) {

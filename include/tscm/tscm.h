@@ -659,6 +659,76 @@ int tscm_estimate_extrinsic_stages(const double *intr9, const double *pix_u, con
                                    int board_w, int device, double *Rt, int *n_estimated, double *T,
                                    double *H, double *pose0, double *pose, int *steps, int *exit_code);
 
+/* ------------------------------------------------------------------ outlier-tolerant pose initialisation
+ * tscm_estimate_extrinsic_ransac: the consensus search that cv::solvePnPRansac runs at the end of
+ * TripleSphereCamera::estimate_extrinsic (TS.cpp:170-203), as a defined, repeatable procedure: a start pose that ignores
+ * mislabelled or displaced corners, and a per-corner verdict.  tscm_estimate_extrinsic is not changed by it.
+ * Per view k with count[k] != 0 (full boards only, corner i paired with board point worlds[i]):
+ *   Turn      T = the look-at turn of tscm_estimate_extrinsic (same reference corner n_points/2 - board_w/2 - 1), and
+ *             (x_i, y_i) = (X/Z, Y/Z) of the turned unit ray T ray(u_i, v_i).  Corner i is USABLE when u_i, v_i, x_i, y_i
+ *             are finite and the turned Z > 0.
+ *   Samples   hypothesis h = 0 .. n_hypotheses-1 draws 4 distinct corner indices by a partial Fisher-Yates shuffle of
+ *             0 .. n_points-1: for draw d = 0..3 the word r = mix(mix(mix(mix(seed + 0x9e3779b9) + k) + h) + d) picks
+ *             position j = d + ((uint64(r) * (n_points - d)) >> 32), the draw is the element there, and positions d and j
+ *             are swapped.  mix = MurmurHash3's 32-bit finaliser fmix32 (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13;
+ *             h *= 0xc2b2ae35; h ^= h >> 16), all arithmetic modulo 2^32.  A sample is REJECTED when it holds a corner
+ *             that is not usable, or when three of its corners are collinear on the integer lattice
+ *             (i mod board_w, i div board_w).  A rejected sample is not redrawn: its hypothesis scores -1.
+ *   H_h       the exact homography through the 4 pairs, by two projective bases: with p_j = (X, Y, 1) of sampled board
+ *             point j = 1..4, c_1 = p_2 x p_3, c_2 = p_3 x p_1, c_3 = p_1 x p_2, lam_j = c_j . p_4, and the same on the
+ *             image side (q_j = (x, y, 1), d_j, mu_j):  H_h = sum_{j=1..3} mu_j lam_{j+1} lam_{j+2} q_j c_j^T (indices
+ *             cyclic), negated when its third row times p_1 is negative.
+ *   Score     (a, b, w) = H_h (X_i, Y_i, 1) for every corner i of the view.  Corner i is an inlier when it is usable,
+ *             w > 0, and du^2 + dv^2 <= threshold_px^2, (du, dv) = (u_i, v_i) - the Triple Sphere projection
+ *             (tscm_project_points' arithmetic, skew terms included) of the ray T^T (a/w, b/w, 1).  Comparisons with NaN
+ *             are false.  The score is the number of inliers.  threshold_px is in pixels of the camera.
+ *   Winner    the highest score, ties to the lowest h.  No hypothesis with a score >= 0: TSCM_EXTRINSIC_NO_HYPOTHESIS.
+ *             Winner's score < min_inliers (0 means max(4, ceil(n_points / 2))): TSCM_EXTRINSIC_FEW_INLIERS.  In both
+ *             cases Rt keeps the caller's values, inlier is all 0 and n_inliers 0.
+ *   Mask      inlier[k*n_points + i] = 1 for the winner's inliers, n_inliers[k] their number.
+ *   Refit     tscm_estimate_extrinsic's steps on the masked corners: Hartley normalisation over the masked board points,
+ *             DLT with h33 = 1, pose from the columns, polar factor, up to 10 Gauss-Newton updates with the same stopping
+ *             rule; exit codes 2..7 keep their meaning on the masked set (the mask stays the winner's for 2..4), and
+ *             Rt = T^T [r1 r2 t].
+ * A pose is written to Rt exactly when the exit code is TSCM_EXTRINSIC_CONVERGED, _ITERATION_CAP or _GN_CHOLESKY (5..7);
+ * the rule "exit_code >= TSCM_EXTRINSIC_CONVERGED" of tscm_estimate_extrinsic_stages does NOT carry over, because the two
+ * codes below are larger.  *n_estimated counts the views with 5..7.  The sums of the refit are taken over the wave in a
+ * fixed order: two calls give the same bytes.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL pointer (n_inliers,
+ * exit_code and seconds_kernel may be NULL; the per-view arrays may be NULL when n_views == 0), a struct_size that is not
+ * sizeof(tscm_ransac_params), a threshold_px that is not > 0 (NaN included), n_hypotheses outside 1..4096, min_inliers
+ * outside 0..n_points or in 1..3, n_points < 4, a board_w that tscm_estimate_extrinsic refuses.  n_points > 1024:
+ * TSCM_E_UNSUPPORTED.  n_views == 0 returns 0 without touching a device.  device_index: as `device` elsewhere,
+ * TSCM_E_NO_DEVICE outside [0, tscm_device_count()), after the argument checks.
+ * tscm_estimate_extrinsic_ransac_stages: the same launch, and per view samples [k][h][4] (-1 where rejected),
+ * score [k][h], winner [k] (-1: none), T, H_best (the winner's H_h at unit Frobenius norm), H_refit (the refit's
+ * de-normalised homography), pose0 = (rv0, t0), pose = (rv, t), steps and rms_px [k]: the RMS over the masked corners of
+ * the pixel residual at the refit pose, through the full model.  Stage values a view does not reach are NaN (steps -1),
+ * samples and score of a view without a board -1.                                                                     */
+#define TSCM_EXTRINSIC_NO_HYPOTHESIS 8      /* every sample was rejected                             */
+#define TSCM_EXTRINSIC_FEW_INLIERS 9        /* the winner's score is below min_inliers               */
+typedef struct tscm_ransac_params {
+    int struct_size;                        /* sizeof(tscm_ransac_params)                            */
+    double threshold_px;                    /* inlier distance in pixels, default 8.0                */
+    int n_hypotheses;                       /* 1 .. 4096, default 256                                */
+    int min_inliers;                        /* 0 = max(4, ceil(n_points / 2)), else 4 .. n_points    */
+    unsigned seed;                          /* default 0                                             */
+} tscm_ransac_params;
+void tscm_ransac_default_params(tscm_ransac_params *p);
+int tscm_estimate_extrinsic_ransac(const double *intr9, const double *pix_u, const double *pix_v, const int *count,
+                                   int n_views, const double *worlds, int n_points, int board_w,
+                                   const tscm_ransac_params *params, int device_index, double *Rt /* [V*9] */,
+                                   unsigned char *inlier /* [V*n_points] */, int *n_inliers /* [V], may be NULL */,
+                                   int *exit_code /* [V], may be NULL */, int *n_estimated,
+                                   double *seconds_kernel /* may be NULL */);
+int tscm_estimate_extrinsic_ransac_stages(const double *intr9, const double *pix_u, const double *pix_v, const int *count,
+                                          int n_views, const double *worlds, int n_points, int board_w,
+                                          const tscm_ransac_params *params, int device_index, double *Rt,
+                                          unsigned char *inlier, int *n_inliers, int *exit_code, int *n_estimated,
+                                          double *seconds_kernel, int *samples /* [V][H][4] */, int *score /* [V][H] */,
+                                          int *winner /* [V] */, double *T, double *H_best, double *H_refit, double *pose0,
+                                          double *pose, int *steps, double *rms_px);
+
 
 /* ------------------------------------------------------------------ corner lists
  * The reference has no on-disk form of its input: corners go straight from findCorner() into

@@ -27,6 +27,8 @@
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
+//   (cv::solvePnPRansac inside estimate_extrinsic)         TripleSphereCamera::estimate_extrinsic_ransac, set_ransac,
+//                                                          parse_ransac_option                 -> tscm_estimate_extrinsic_ransac
 // (*) deterministic planar PnP in place of cv::solvePnPRansac (see tscm.h)
 #ifndef TSCM_CALIB_HPP
 #define TSCM_CALIB_HPP
@@ -34,6 +36,7 @@
 #include <tscm/tscm.h>
 
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -48,6 +51,31 @@ struct Size { int width, height; };
 struct Mat33 { double a[9]; };       // row-major, cv::Mat_<double>(3,3) order
 
 inline void check(int rc) { if (rc != 0) throw std::runtime_error(std::string("tscm: ") + tscm_last_error()); }
+
+// The calibration demos' --ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] -> threshold_px, n_hypotheses and min_inliers of p;
+// false when the text is none of that, the threshold is not > 0 or HYPOTHESES lies outside 1..4096 (min_inliers depends on the
+// board and is left to tscm_estimate_extrinsic_ransac).
+inline bool parse_ransac_option(const char *text, tscm_ransac_params *p)
+{
+    const char *q = text;
+    double thr = 0.0;
+    long field[3] = { 0, p->n_hypotheses, p->min_inliers };
+    for (int k = 0; k < 3; ++k) {                               // numbers, nothing before, between or after them
+        char *end = NULL;
+        if (*q != '.' && (*q < '0' || *q > '9')) return false;
+        if (k == 0) thr = std::strtod(q, &end);
+        else field[k] = std::strtol(q, &end, 10);
+        if (end == q) return false;
+        if (!*end) break;
+        if (*end != ',' || k == 2) return false;
+        q = end + 1;
+    }
+    if (!(thr > 0.0) || field[1] < 1 || field[1] > 4096 || field[2] < 0 || field[2] > 1024) return false;
+    p->threshold_px = thr;
+    p->n_hypotheses = (int)field[1];
+    p->min_inliers = (int)field[2];
+    return true;
+}
 
 // Command-line forms of the held-intrinsics masks (tscm.h, TSCM_FIX_*), for the example programs.
 // model_mask: "ts" -> 0, "ds" -> TSCM_MODEL_DS, "ucm" -> TSCM_MODEL_UCM; false for another name.
@@ -231,6 +259,46 @@ public:
         return done;
     }
 
+    // The same step with tscm_estimate_extrinsic_ransac (a consensus search over 4-corner homographies and a refit on the
+    // winner's inliers, see tscm.h): fills Rt_ for the views with exit code 5..7, ransac_code_ for every view, and *inliers
+    // (may be NULL) with one 0/1 flag per corner and view.  params NULL: the library's defaults.  Returns the poses written.
+    int estimate_extrinsic_ransac(const std::vector<std::vector<Point2d> > &pixels, const std::vector<Point3d> &worlds, Size chessboard_num,
+                                  const tscm_ransac_params *params = NULL, std::vector<std::vector<unsigned char> > *inliers = NULL)
+    {
+        const int V = (int)pixels.size(), n = (int)worlds.size();
+        std::vector<double> u((size_t)V * n, 0.0), v((size_t)V * n, 0.0), W(3 * (size_t)n), M(9 * (size_t)V, 0.0);
+        std::vector<int> cnt(V), n_in(V);
+        std::vector<unsigned char> mask((size_t)V * n, 0);
+        for (int c = 0; c < n; ++c) { W[3 * c] = worlds[c].x; W[3 * c + 1] = worlds[c].y; W[3 * c + 2] = worlds[c].z; }
+        for (int k = 0; k < V; ++k) {
+            cnt[k] = has_chessboard_[k] ? (int)pixels[k].size() : 0;
+            for (size_t j = 0; j < pixels[k].size() && j < (size_t)n; ++j) { u[(size_t)k * n + j] = pixels[k][j].x; v[(size_t)k * n + j] = pixels[k][j].y; }
+        }
+        tscm_ransac_params def;
+        tscm_ransac_default_params(&def);
+        int done = 0;
+        ransac_code_.assign(V, 0);
+        check(tscm_estimate_extrinsic_ransac(intrinsic_.data(), u.data(), v.data(), cnt.data(), V, W.data(), n, chessboard_num.width, params ? params : &def,
+                                             device_, M.data(), mask.data(), n_in.data(), ransac_code_.data(), &done, NULL));
+        Rt_.resize(V);
+        for (int k = 0; k < V; ++k)
+            if (ransac_code_[k] >= TSCM_EXTRINSIC_CONVERGED && ransac_code_[k] <= TSCM_EXTRINSIC_GN_CHOLESKY) std::memcpy(Rt_[k].a, &M[9 * (size_t)k], sizeof(Rt_[k].a));
+        if (inliers) {
+            inliers->assign(V, std::vector<unsigned char>());
+            for (int k = 0; k < V; ++k) (*inliers)[k].assign(mask.begin() + (size_t)k * n, mask.begin() + (size_t)(k + 1) * n);
+        }
+        return done;
+    }
+    // calibrate() takes its start poses from estimate_extrinsic_ransac with *params (NULL: from estimate_extrinsic again, the
+    // default), clears has_chessboard_ for the views without a pose there, and keeps the masks in ransac_inliers_.
+    void set_ransac(const tscm_ransac_params *params)
+    {
+        use_ransac_ = params != NULL;
+        if (params) ransac_ = *params;
+    }
+    std::vector<int> ransac_code_;                                    // TSCM_EXTRINSIC_* per view of the last estimate_extrinsic_ransac
+    std::vector<std::vector<unsigned char> > ransac_inliers_;         // per view and corner, of the last calibrate() with set_ransac
+
     // TS.cpp:30-105: initial guess (unless a previous calibration succeeded), poses, refinement
     bool calibrate(const std::vector<std::vector<Point2d> > &pixels, const std::vector<bool> &has_chessboard,
                    const std::vector<Point3d> &worlds, Size img_size, Size chessboard_num)
@@ -246,7 +314,13 @@ public:
             intrinsic_[6] = 0.5;
             if (estimate_focal(pixels, chessboard_num) == 0.0) return false;          // :48-50
         }
-        estimate_extrinsic(pixels, worlds, chessboard_num);                           // :52
+        if (use_ransac_) {
+            estimate_extrinsic_ransac(pixels, worlds, chessboard_num, &ransac_, &ransac_inliers_);
+            for (size_t i = 0; i < has_chessboard_.size(); ++i)
+                if (ransac_code_[i] < TSCM_EXTRINSIC_CONVERGED || ransac_code_[i] > TSCM_EXTRINSIC_GN_CHOLESKY) has_chessboard_[i] = false;
+        } else {
+            estimate_extrinsic(pixels, worlds, chessboard_num);                       // :52
+        }
         poses_from_Rt();                                                              // :62-74
         const bool status = refinement(pixels, worlds);                               // :76-78
         if (status) has_init_guess_ = true;
@@ -261,6 +335,8 @@ public:
     int loss_kind_ = TSCM_LOSS_NONE;
     double loss_scale_ = 0.0;
     unsigned short fixed_ = 0;
+    bool use_ransac_ = false;                 // set_ransac()
+    tscm_ransac_params ransac_;
 
     // TS.cpp:62-74
     void poses_from_Rt()
@@ -377,6 +453,21 @@ public:
 private:
     int device_;
 };
+
+// What the calibration demos print behind a calibrate() with set_ransac: of the views offered (has), those that kept a pose,
+// and the share of inlier corners in them.  camera < 0: no "camera N:" in front.
+inline void print_ransac_summary(const TripleSphereCamera &cam, const std::vector<bool> &has, int camera)
+{
+    size_t offered = 0, kept = 0, corners = 0, inliers = 0;
+    for (size_t i = 0; i < has.size(); ++i) {
+        offered += has[i] ? 1 : 0;
+        if (!has[i] || i >= cam.has_chessboard_.size() || !cam.has_chessboard_[i]) continue;
+        ++kept;
+        for (size_t j = 0; j < cam.ransac_inliers_[i].size(); ++j) { ++corners; inliers += cam.ransac_inliers_[i][j] ? 1 : 0; }
+    }
+    if (camera >= 0) std::printf("camera %d: ", camera);
+    std::printf("ransac kept %zu of %zu views, %.1f %% of their corners are inliers\n", kept, offered, corners ? 100.0 * inliers / corners : 0.0);
+}
 
 // multi_calib.h:8-83
 class MultiCalib_camera {

@@ -1,0 +1,222 @@
+"""k_estimate_extrinsic_ransac against the extended-precision restatement of tests/init_ransac_ref.py: samples bit for bit,
+scores / winner / mask wherever the restatement's rounding bounds leave no decision open, every stage of the masked refit
+within the bounds of init_ref, repeatability, and pose-level robustness against planted outliers."""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import init_ransac_ref as Q
+from tests import init_ref as R
+from tscm_calib_amd import rig
+
+pytestmark = pytest.mark.gpu
+
+ESTIMATED = R.ESTIMATED
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    worst = {}
+    yield worst
+    capped = worst.pop("_capped", set())
+    for k, (r, name) in sorted(worst.items()):
+        print(f"\n[init ransac] {k}: {r:.3g} (case {name})")
+    for name in sorted(capped):
+        print(f"\n[init ransac] compared with the reference's iterate (no convergence in 10 steps): {name}")
+
+
+def _note(report, kind, value, name):
+    if kind not in report or value > report[kind][0]:
+        report[kind] = (float(value), name)
+
+
+def _ratio(diff, bound):
+    diff = np.abs(diff)
+    return float(np.max(np.where(diff == 0, 0.0, diff / np.where(bound > 0, bound, 1e-300))))
+
+
+def _sentinel(V):
+    return np.arange(9 * V, dtype=np.float64).reshape(V, 3, 3) * -1.25 - 7.0
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """The case's data and the restatement of every view, computed once and shared (never written to)."""
+    c = Q.case(name)
+    intr, pu, pv, count, W, cols, Hn, seed, thr = c[:9]
+    return c, Q.ransac_refs(intr, pu, pv, count, W, cols, threshold_px=thr, n_hypotheses=Hn, seed=seed)
+
+
+def _same_bytes(a: dict, b: dict):
+    for key, x in a.items():
+        if key == "seconds_kernel":
+            continue
+        y = b[key]
+        assert np.asarray(x).tobytes() == np.asarray(y).tobytes(), key
+
+
+@pytest.mark.parametrize("name", [c[0] for c in Q.CASES])
+def test_ransac_stages_every_view(hip_device, name, _report):
+    (intr, pu, pv, count, W, cols, Hn, seed, thr, kinds, moved), refs = _case(name)
+    V, n = pu.shape
+    prm = rig.ransac_params(threshold_px=thr, n_hypotheses=Hn, seed=seed)
+    init = _sentinel(V)
+    g = rig.estimate_extrinsic_ransac_stages(intr, pu, pv, count, W, cols, prm, hip_device, Rt_init=init)
+    open_views = [k for k, r in enumerate(refs) if not r["decisive"]]
+    _note(_report, "share of views the reference leaves open", len(open_views) / V, name)
+    assert len(open_views) <= 0.05 * V, open_views
+    written = 0
+    for k, r in enumerate(refs):
+        where = f"{name} view {k} ({kinds[k]})"
+        code = int(g["code"][k])
+        if code not in ESTIMATED:
+            assert np.array_equal(g["Rt"][k], init[k]), where                 # the caller's values stay
+        else:
+            written += 1
+        if r["code"] == R.NO_BOARD:
+            assert code == R.NO_BOARD and g["winner"][k] == -1 and not g["inlier"][k].any() and g["n_inliers"][k] == 0, where
+            assert np.all(g["samples"][k] == -1) and np.all(g["score"][k] == -1), where
+            continue
+        assert np.array_equal(g["samples"][k], r["samples"]), where
+        assert np.array_equal(g["score"][k] < 0, r["score"] < 0), where
+        assert np.array_equal(g["score"][k][r["clean"]], r["score"][r["clean"]]), (where, np.flatnonzero(g["score"][k] != r["score"]))
+        lo, hi = r["lo"], r["hi"]
+        assert np.all((g["score"][k] >= lo) & (g["score"][k] <= hi)), where
+        rt = np.max(np.abs(g["T"][k] - r["T"].astype(np.float64))) / r["bT"] if np.all(np.isfinite(r["T"].astype(np.float64))) else 0.0
+        assert rt <= 1.0, (where, rt)
+        _note(_report, "T / bound", rt, name)
+        if not r["decisive"]:
+            assert int(g["winner"][k]) in r["allowed"], where
+            continue
+        assert g["winner"][k] == r["winner"], (where, g["winner"][k], r["winner"])
+        assert np.array_equal(g["inlier"][k], r["mask"]), where
+        assert g["n_inliers"][k] == r["n_inliers"] == int(g["inlier"][k].sum()), where
+        if r["winner"] >= 0:
+            eh = _ratio(g["H_best"][k] - r["H_best"].astype(np.float64), r["bH_best"])
+            assert eh <= 1.0, (where, eh)
+            _note(_report, "H_best / bound", eh, name)
+        if r["code"] in (Q.NO_HYPOTHESIS, Q.FEW_INLIERS):
+            assert code == r["code"], (where, code)
+            assert np.isnan(g["H_refit"][k]).all() and g["steps"][k] == -1 and np.isnan(g["rms_px"][k]), where
+            continue
+        assert g["n_inliers"][k] == g["score"][k][g["winner"][k]], where
+        f = r["refit"]
+        if f["decisive_code"]:
+            assert code == f["code"], (where, code, f["code"])
+        else:
+            ok = {f["code"]} | ({R.CONVERGED, R.ITERATION_CAP} if f["code"] in (R.CONVERGED, R.ITERATION_CAP) else set())
+            assert code in ok, (where, code, f["code"])
+        if f.get("H") is None:
+            continue
+        E = ((g["H_refit"][k].astype(R.LD) - f["H"]) @ R.inv3(f["Nt"])).astype(np.float64)
+        rh = np.max(np.abs(E)) / f["bHn"]
+        assert rh <= 1.0, (where, rh)
+        _note(_report, "H_refit (Hartley space) / bound", rh, name)
+        if f.get("rv0") is None:
+            continue
+        p0 = np.concatenate([g["rv0"][k], g["t0"][k]])
+        r0 = np.concatenate([f["rv0"], f["t0"]]).astype(np.float64)
+        rp0 = _ratio(p0 - r0, f["bpose0"])
+        if not f["rod_decisive"]:
+            alt = [R.column_pose(f["H"], (b, s))[:2] for b, s in (("identity", None), ("pi", True), ("pi", False), ("generic", None))]
+            rp0 = min([rp0] + [_ratio(p0 - np.concatenate(a).astype(np.float64), f["bpose0"]) for a in alt])
+        assert rp0 <= 1.0, (where, rp0)
+        _note(_report, "rv0, t0 / bound", rp0, name)
+        if code not in ESTIMATED:
+            continue
+        pf = np.concatenate([g["rv"][k], g["t"][k]])
+        if f["capped_ref"]:
+            hist = f["hist"]
+            ref = hist[min(int(g["steps"][k]), len(hist) - 1)]
+            _report.setdefault("_capped", set()).add(where)
+        else:
+            ref = (f["rv"], f["t"])
+        rf = _ratio(pf - np.concatenate(ref).astype(np.float64), f["bpose"])
+        assert rf <= 1.0, (where, rf)
+        _note(_report, "rv, t (final) / bound", rf, name)
+        want = R.rt_from_stages(g["T"][k], g["rv"][k], g["t"][k]).astype(np.float64)
+        scale = np.array([1.0, 1.0, max(1.0, float(np.max(np.abs(g["t"][k]))))])
+        assert np.max(np.abs(g["Rt"][k] - want) / scale) < 1e-13, where
+        # rms_px from the kernel's own pose: a pixel coordinate below 4096 carries at most 256 u 4096 = 1.2e-10 px of
+        # rounding through the projection, the RMS of such errors at most sqrt(2) of it; 1e-9 px leaves a factor 4
+        rms = float(Q.rms_px(intr, g["T"][k], g["rv"][k], g["t"][k], W, pu[k], pv[k], g["inlier"][k]))
+        assert abs(g["rms_px"][k] - rms) <= 1e-9, (where, g["rms_px"][k], rms)
+    assert g["n_estimated"] == written == int(np.isin(g["code"], ESTIMATED).sum())
+    # a second run gives the same bytes, and the plain instantiation the same poses, masks, counts and codes
+    _same_bytes(g, rig.estimate_extrinsic_ransac_stages(intr, pu, pv, count, W, cols, prm, hip_device, Rt_init=init))
+    Rt, inl, ninl, code, nest = rig.estimate_extrinsic_ransac(intr, pu, pv, count, W, cols, prm, hip_device, Rt_init=init)
+    assert nest == g["n_estimated"] and np.array_equal(ninl, g["n_inliers"]) and np.array_equal(code, g["code"])
+    assert Rt.tobytes() == g["Rt"].tobytes() and np.array_equal(inl, g["inlier"])
+    Rt2 = rig.estimate_extrinsic_ransac(intr, pu, pv, count, W, cols, prm, hip_device, Rt_init=init)[0]
+    assert Rt2.tobytes() == Rt.tobytes()
+
+
+def test_outlier_free_view_matches_the_plain_entry(hip_device, _report):
+    """No outliers and a large threshold: every corner is in the mask, and the refit is the plain entry's fit of the same
+    corners -- both within the restatement's bounds of it (the wave's summation order differs from the serial one)."""
+    intr, pu, pv, count, W, cols, kinds = R.extrinsic_case("v12_9x6")
+    keep = [k for k, kind in enumerate(kinds) if kind == "generic"]
+    pu, pv, count = pu[keep], pv[keep], count[keep]
+    prm = rig.ransac_params(threshold_px=1e3, n_hypotheses=64, seed=1)
+    g = rig.estimate_extrinsic_ransac_stages(intr, pu, pv, count, W, cols, prm, hip_device)
+    q = rig.estimate_extrinsic_stages(intr, pu, pv, count, W, cols, hip_device)
+    assert g["inlier"].all() and np.all(g["n_inliers"] == W.shape[0]) and len(keep) >= 4
+    for k in range(len(keep)):
+        r = R.extrinsic_view(intr, pu[k], pv[k], W, cols)
+        assert r["code"] == R.CONVERGED and g["code"][k] == q["code"][k] == R.CONVERGED
+        ref = np.concatenate([r["rv"], r["t"]]).astype(np.float64)
+        for out, label in ((g, "ransac"), (q, "plain")):
+            rf = _ratio(np.concatenate([out["rv"][k], out["t"][k]]) - ref, r["bpose"])
+            assert rf <= 1.0, (label, k, rf)
+            _note(_report, f"all-inlier view, {label} rv, t / bound", rf, "v12_9x6")
+        E = ((g["H_refit"][k].astype(R.LD) - r["H"]) @ R.inv3(r["Nt"])).astype(np.float64)
+        assert np.max(np.abs(E)) / r["bHn"] <= 1.0
+
+
+# kind: (rotation error, translation error) of the restatement's pose against the true one, computed on the CPU
+# (Q.pose_errors over Q.robust_case(kind) with Q.ROBUST_PARAMS); the CPU oracle's plain estimate_extrinsic on the same data
+# gives (1.387, 0.2398), (0.8652, 0.1512), (1.039, 0.3095) and (0.1372, 0.1339) on the four cases with outliers.
+ROBUST_REFERENCE = {"clean": (0.002245, 0.001038), "outlier1": (0.002169, 0.0009365), "outliers5": (0.0023, 0.0009892),
+                    "outliers20": (0.002348, 0.001393), "row_shift": (0.00293, 0.00111)}
+
+
+@pytest.mark.parametrize("kind", Q.ROBUST_KINDS)
+def test_pose_survives_planted_outliers(hip_device, kind):
+    """8 views of the golden rig's camera 0 at the true intrinsics, 0.1 px noise, and in every view: no outlier, 1 corner,
+    5 % or 20 % of the corners displaced by 30-200 px, or one board row labelled one column late.  Pose error against the
+    truth (largest |[r1 r2] - truth|, largest |t - truth| / |truth| over the views) of the restatement on the CPU:
+        clean 0.002245 / 0.001038, outlier1 0.002169 / 0.0009365, outliers5 0.0023 / 0.0009892,
+        outliers20 0.002348 / 0.001393, row_shift 0.00293 / 0.00111
+    (the noise floor of a 54-corner pose at 0.1 px).  The device's bound is twice that.  The plain entry's least-squares
+    pose on the same data is off by 0.14 to 1.4 / 0.13 to 0.31 (CPU oracle), 40 times and more: it must be the larger."""
+    intr, pu, pv, count, W, bw, moved, Rt_true = Q.robust_case(kind)
+    Rt, inl, ninl, code, nest = rig.estimate_extrinsic_ransac(intr, pu, pv, count, W, bw, rig.ransac_params(**Q.ROBUST_PARAMS), hip_device)
+    assert nest == len(count) and np.all(code == R.CONVERGED)
+    assert not (inl & moved).any() and np.array_equal(inl, ~moved)             # exactly the planted corners are out
+    rot, tr = Q.pose_errors(Rt, Rt_true)
+    ref_rot, ref_tr = ROBUST_REFERENCE[kind]
+    print(f"\n[init ransac] {kind}: pose error {rot:.4g} / {tr:.4g} (restatement {ref_rot:.4g} / {ref_tr:.4g})")
+    assert rot <= 2 * ref_rot and tr <= 2 * ref_tr, (rot, tr)
+    if kind != "clean":
+        plain, k = rig.estimate_extrinsic(intr, pu, pv, count, W, bw, hip_device)
+        prot, ptr = Q.pose_errors(plain, Rt_true)
+        assert k == len(count) and prot > rot and ptr > tr, (prot, ptr)
+
+
+def test_rough_start_mask(hip_device):
+    """The pipeline's start: principal point at the image centre, xi = lambda = 0, alpha = 0.5, focal from estimate_focal.
+    The model is off by pixels there, so only the mask is judged, at the default 8 px: no planted corner (5 % per view) is
+    in it, and it keeps at least the share of the other corners that the restatement keeps."""
+    _, pu, pv, count, W, bw, moved, _ = Q.robust_case("outliers5")
+    clean = Q.robust_case("clean")
+    focal, used = rig.estimate_focal(clean[1], clean[2], count, 9, 6, 639.5, 539.5, hip_device)
+    assert used > 0
+    intr = np.array([focal, focal, 639.5, 539.5, 0.0, 0.0, 0.5, 0.0, 0.0])
+    prm = rig.ransac_params(n_hypotheses=256, seed=11)
+    assert prm.threshold_px == 8.0
+    Rt, inl, ninl, code, nest = rig.estimate_extrinsic_ransac(intr, pu, pv, count, W, bw, prm, hip_device)
+    refs = Q.ransac_refs(intr, pu, pv, count, W, bw, threshold_px=8.0, n_hypotheses=256, seed=11, with_refit=False)
+    assert np.all(np.isin(code, ESTIMATED)) and not (inl & moved).any()
+    kept_ref = sum(int((r["mask"] & ~moved[k]).sum()) for k, r in enumerate(refs))
+    assert int((inl & ~moved).sum()) >= kept_ref > 0.9 * int((~moved).sum())

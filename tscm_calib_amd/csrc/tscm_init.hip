@@ -4,6 +4,8 @@
 // reflections in thread-private memory, and the null vector (cv::SVD::solveZ) comes from a
 // one-sided Jacobi SVD of that factor held in registers.  The accepted samples are averaged on the
 // host in the reference's (image, row) order.
+// Below it the pose of every image (estimate_extrinsic, TS.cpp:170-203): the least-squares planar PnP, one thread per
+// image, and the consensus search with a refit on the inliers, one wave per image (tscm_init_ransac.h).
 #include "tscm/tscm.h"
 
 #include <hip/hip_runtime.h>
@@ -161,6 +163,8 @@ __device__ void rotation_vector_dev(const double *Min, double *rv)
         rv[0] = rx * vth; rv[1] = ry * vth; rv[2] = rz * vth;
     }
 }
+
+#include "tscm_init_ransac.h"
 
 // STAGES = false: Rt_out [n_views][9], ok_out[k] = 1 where a pose was written (tscm_estimate_extrinsic).
 // STAGES = true: Rt_out [n_views][kStageRec] = Rt | T | H | rv0 t0 | rv t | GN steps, ok_out[k] = the
@@ -425,4 +429,149 @@ extern "C" int tscm_estimate_extrinsic_stages(const double *intr9, const double 
     }
     if (n_estimated) *n_estimated = done;
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// tscm_estimate_extrinsic_ransac: argument checks, one launch of k_estimate_extrinsic_ransac<STAGES>, read-back.
+// ---------------------------------------------------------------------------------------------------
+extern "C" void tscm_ransac_default_params(tscm_ransac_params *p)
+{
+    if (!p) return;
+    p->struct_size = (int)sizeof(tscm_ransac_params);
+    p->threshold_px = 8.0;
+    p->n_hypotheses = 256;
+    p->min_inliers = 0;
+    p->seed = 0;
+}
+
+namespace {
+
+struct RansacStages {                       // host pointers of the stages entry, all non-NULL there
+    int *samples, *score, *winner;
+    double *T, *H_best, *H_refit, *pose0, *pose;
+    int *steps;
+    double *rms_px;
+};
+
+template <bool STAGES>
+int ransac_views(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views, const double *worlds,
+                 int n_points, int board_w, const tscm_ransac_params *params, int device_index, double *Rt, unsigned char *inlier,
+                 int *n_inliers, int *exit_code, int *n_estimated, double *seconds_kernel, const RansacStages &st)
+{
+    const char *who = STAGES ? "tscm_estimate_extrinsic_ransac_stages" : "tscm_estimate_extrinsic_ransac";
+    if (!intr9) return tscm_set_error(TSCM_E_INVALID, "intr9 is NULL");
+    if (!worlds) return tscm_set_error(TSCM_E_INVALID, "worlds is NULL");
+    if (!params) return tscm_set_error(TSCM_E_INVALID, "params is NULL");
+    if (!n_estimated) return tscm_set_error(TSCM_E_INVALID, "n_estimated is NULL");
+    if (n_views < 0) return tscm_set_error(TSCM_E_INVALID, "n_views is negative");
+    if (n_points < 4) return tscm_set_error(TSCM_E_INVALID, "n_points " + std::to_string(n_points) + " < 4");
+    if (n_views > 0) {
+        if (!pix_u) return tscm_set_error(TSCM_E_INVALID, "pix_u is NULL");
+        if (!pix_v) return tscm_set_error(TSCM_E_INVALID, "pix_v is NULL");
+        if (!count) return tscm_set_error(TSCM_E_INVALID, "count is NULL");
+        if (!Rt) return tscm_set_error(TSCM_E_INVALID, "Rt is NULL");
+        if (!inlier) return tscm_set_error(TSCM_E_INVALID, "inlier is NULL");
+        if constexpr (STAGES) {
+            const void *ptr[] = { st.samples, st.score, st.winner, st.T, st.H_best, st.H_refit, st.pose0, st.pose, st.steps, st.rms_px };
+            const char *name[] = { "samples", "score", "winner", "T", "H_best", "H_refit", "pose0", "pose", "steps", "rms_px" };
+            for (int i = 0; i < 10; ++i)
+                if (!ptr[i]) return tscm_set_error(TSCM_E_INVALID, std::string(name[i]) + " is NULL");
+        }
+    }
+    if (int rc = tscm::check_struct_size(params, "tscm_ransac_params")) return rc;
+    if (!(params->threshold_px > 0.0)) return tscm_set_error(TSCM_E_INVALID, "params: threshold_px " + std::to_string(params->threshold_px) + " is not > 0");
+    if (params->n_hypotheses < 1 || params->n_hypotheses > kRansacMaxHypotheses)
+        return tscm_set_error(TSCM_E_INVALID, "params: n_hypotheses " + std::to_string(params->n_hypotheses) + " outside 1..4096");
+    if (params->min_inliers < 0 || params->min_inliers > n_points || (params->min_inliers >= 1 && params->min_inliers <= 3))
+        return tscm_set_error(TSCM_E_INVALID, "params: min_inliers " + std::to_string(params->min_inliers) + " is neither 0 nor in 4..n_points");
+    if (board_w < 1 || n_points / 2 - board_w / 2 - 1 < 0) return tscm_set_error(TSCM_E_INVALID, "board_w: board width does not fit the corner count");
+    if (n_points > kRansacMaxPoints) return tscm_set_error(TSCM_E_UNSUPPORTED, "n_points: more than 1024 corners per view");
+    *n_estimated = 0;
+    if (seconds_kernel) *seconds_kernel = 0.0;
+    if (n_views == 0) return 0;
+    if (int rc = tscm::select_device(device_index, who)) return rc;
+    const int min_inliers = params->min_inliers ? params->min_inliers : std::max(4, (n_points + 1) / 2);
+    const int H = params->n_hypotheses;
+    const size_t V = (size_t)n_views, npix = V * n_points;
+    tscm::DeviceMem mem;
+    const double *d_i = nullptr, *d_u = nullptr, *d_v = nullptr, *d_w = nullptr;
+    const int *d_c = nullptr;
+    double *d_rt = nullptr, *d_stage = nullptr;
+    unsigned char *d_in = nullptr;
+    int *d_ninl = nullptr, *d_code = nullptr, *d_samples = nullptr, *d_score = nullptr, *d_winner = nullptr;
+    HIP_TRY(mem.upload(&d_i, intr9, 9));
+    HIP_TRY(mem.upload(&d_u, pix_u, npix));
+    HIP_TRY(mem.upload(&d_v, pix_v, npix));
+    HIP_TRY(mem.upload(&d_w, worlds, 3 * (size_t)n_points));
+    HIP_TRY(mem.upload(&d_rt, Rt, 9 * V));      // views without a pose keep the caller's values
+    HIP_TRY(mem.upload(&d_c, count, V));
+    HIP_TRY(mem.alloc(&d_in, npix));
+    HIP_TRY(hipMemset(d_in, 0, npix));
+    HIP_TRY(mem.alloc(&d_ninl, V));
+    HIP_TRY(mem.alloc(&d_code, V));
+    std::vector<double> rec;
+    if constexpr (STAGES) {
+        HIP_TRY(mem.alloc(&d_samples, 4 * V * H));
+        HIP_TRY(mem.alloc(&d_score, V * H));
+        HIP_TRY(hipMemset(d_samples, 0xff, 4 * V * H * sizeof(int)));       // -1
+        HIP_TRY(hipMemset(d_score, 0xff, V * H * sizeof(int)));
+        HIP_TRY(mem.alloc(&d_winner, V));
+        rec.assign(V * kRansacRec, NAN);
+        HIP_TRY(mem.upload(&d_stage, rec));
+    }
+    const size_t lds = ((size_t)34 * n_points + 7) / 8 * 8;
+    const double thr2 = params->threshold_px * params->threshold_px;
+    tscm::EventSpan span;
+    HIP_TRY(span.create(2));
+    HIP_TRY(span.mark(0));
+    hipLaunchKernelGGL(k_estimate_extrinsic_ransac<STAGES>, dim3((unsigned)n_views), dim3(64), lds, 0, d_i, d_u, d_v, d_c, d_w, n_points, board_w, thr2, H,
+                       min_inliers, params->seed, d_rt, d_in, d_ninl, d_code, d_samples, d_score, d_winner, d_stage);
+    HIP_TRY(span.finish(1, nullptr, seconds_kernel));
+    std::vector<int> code(V), ninl(V);
+    HIP_TRY(hipMemcpy(Rt, d_rt, 9 * V * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(inlier, d_in, npix, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(code.data(), d_code, V * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ninl.data(), d_ninl, V * sizeof(int), hipMemcpyDeviceToHost));
+    if constexpr (STAGES) {
+        HIP_TRY(hipMemcpy(st.samples, d_samples, 4 * V * H * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st.score, d_score, V * H * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st.winner, d_winner, V * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rec.data(), d_stage, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < V; ++k) {
+            const double *r = rec.data() + kRansacRec * k;
+            for (int i = 0; i < 9; ++i) { st.T[9 * k + i] = r[i]; st.H_best[9 * k + i] = r[9 + i]; st.H_refit[9 * k + i] = r[18 + i]; }
+            for (int i = 0; i < 6; ++i) { st.pose0[6 * k + i] = r[27 + i]; st.pose[6 * k + i] = r[33 + i]; }
+            st.steps[k] = std::isnan(r[39]) ? -1 : (int)r[39];
+            st.rms_px[k] = r[40];
+        }
+    }
+    int done = 0;
+    for (size_t k = 0; k < V; ++k) {
+        if (exit_code) exit_code[k] = code[k];
+        if (n_inliers) n_inliers[k] = ninl[k];
+        done += code[k] >= TSCM_EXTRINSIC_CONVERGED && code[k] <= TSCM_EXTRINSIC_GN_CHOLESKY;
+    }
+    *n_estimated = done;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int tscm_estimate_extrinsic_ransac(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,
+                                              const double *worlds, int n_points, int board_w, const tscm_ransac_params *params, int device_index,
+                                              double *Rt, unsigned char *inlier, int *n_inliers, int *exit_code, int *n_estimated, double *seconds_kernel)
+{
+    return ransac_views<false>(intr9, pix_u, pix_v, count, n_views, worlds, n_points, board_w, params, device_index, Rt, inlier, n_inliers, exit_code,
+                               n_estimated, seconds_kernel, RansacStages{});
+}
+
+extern "C" int tscm_estimate_extrinsic_ransac_stages(const double *intr9, const double *pix_u, const double *pix_v, const int *count, int n_views,
+                                                     const double *worlds, int n_points, int board_w, const tscm_ransac_params *params, int device_index,
+                                                     double *Rt, unsigned char *inlier, int *n_inliers, int *exit_code, int *n_estimated,
+                                                     double *seconds_kernel, int *samples, int *score, int *winner, double *T, double *H_best,
+                                                     double *H_refit, double *pose0, double *pose, int *steps, double *rms_px)
+{
+    const RansacStages st{ samples, score, winner, T, H_best, H_refit, pose0, pose, steps, rms_px };
+    return ransac_views<true>(intr9, pix_u, pix_v, count, n_views, worlds, n_points, board_w, params, device_index, Rt, inlier, n_inliers, exit_code,
+                              n_estimated, seconds_kernel, st);
 }

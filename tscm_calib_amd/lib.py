@@ -166,6 +166,12 @@ class CSweepVisibilityParams(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("cell_shift", C.c_int), ("tolerance", C.c_int), ("dilate", C.c_int), ("near_is_high", C.c_int)]
 
 
+class CRansacParams(C.Structure):
+    """tscm_ransac_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("threshold_px", C.c_double), ("n_hypotheses", C.c_int), ("min_inliers", C.c_int),
+                ("seed", C.c_uint)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -199,6 +205,7 @@ EXPORTS = [
     "tscm_sweep_default_params", "tscm_sweep_create", "tscm_sweep_depth", "tscm_sweep_stages", "tscm_sweep_stage_times", "tscm_sweep_points", "tscm_sweep_destroy",
     "tscm_sweep_compose_default_params", "tscm_sweep_compose", "tscm_sweep_compose_stages",
     "tscm_sweep_visibility_default_params", "tscm_sweep_visibility", "tscm_sweep_visibility_stages", "tscm_sweep_compose_visible", "tscm_sweep_compose_visible_stages",
+    "tscm_ransac_default_params", "tscm_estimate_extrinsic_ransac", "tscm_estimate_extrinsic_ransac_stages",
 ]
 
 
@@ -348,6 +355,12 @@ def lib():
     L.tscm_estimate_extrinsic.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip]
     L.tscm_estimate_focal_rows.argtypes = [dp, dp, ip, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp]
     L.tscm_estimate_extrinsic_stages.argtypes = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, ip, dp, dp, dp, dp, ip, ip]
+    rp = C.POINTER(CRansacParams)
+    L.tscm_ransac_default_params.argtypes = [rp]
+    L.tscm_ransac_default_params.restype = None
+    ransac = [dp, dp, dp, ip, C.c_int, dp, C.c_int, C.c_int, rp, C.c_int, dp, ubp, ip, ip, ip, dp]
+    L.tscm_estimate_extrinsic_ransac.argtypes = ransac
+    L.tscm_estimate_extrinsic_ransac_stages.argtypes = ransac + [ip, ip, ip, dp, dp, dp, dp, dp, ip, dp]
     L.tscm_corners_write.argtypes = [C.c_char_p, C.POINTER(CCornerSet)]
     L.tscm_corners_read.argtypes = [C.c_char_p, C.POINTER(CCornerSet)]
     L.tscm_corners_free.argtypes = [C.POINTER(CCornerSet)]

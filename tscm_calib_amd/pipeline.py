@@ -36,8 +36,10 @@ def _start_in_model(intr: np.ndarray, model: str) -> None:
         intr[..., 4] = 0.0
 
 
-def _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, model="ts"):
-    """calibrate_camera up to its refinement: the start intrinsics, the poses and the mono problem of the refinement."""
+def _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, model="ts", ransac=None):
+    """calibrate_camera up to its refinement: the start intrinsics, the poses and the mono problem of the refinement.
+    ransac: None, or rig.ransac_params(...): the start poses come from rig.estimate_extrinsic_ransac, and a view whose exit
+    code is not 5..7 leaves the refinement (count 0).  Returns q, count, sel and None or dict(inlier [V,n], code [V], has [V])."""
     n = cols * rows
     W = board_points(cols, rows, pitch)
     count = (np.asarray(has, dtype=np.int32) * n).astype(np.int32)
@@ -47,13 +49,20 @@ def _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_int
     else:
         intr = np.array(init_intr, dtype=np.float64).reshape(9).copy()
     _start_in_model(intr, model)
-    Rt0, _ = rig.estimate_extrinsic(intr, pu, pv, count, W, cols, device)
+    found = None
+    if ransac is None:
+        Rt0, _ = rig.estimate_extrinsic(intr, pu, pv, count, W, cols, device)
+    else:
+        Rt0, inlier, _, code, _ = rig.estimate_extrinsic_ransac(intr, pu, pv, count, W, cols, ransac, device)
+        kept = (code >= 5) & (code <= 7)
+        count = np.where(kept, count, 0).astype(np.int32)
+        found = dict(inlier=inlier, code=code, has=kept.astype(np.uint8))
     sel = np.flatnonzero(count > 0)
     V = sel.shape[0]
     q = Problem(1, V, W[:, :2].copy(), np.zeros(V, dtype=np.int32), np.arange(V, dtype=np.int32), (np.arange(V) * n).astype(np.int32),
                 np.full(V, n, dtype=np.int32), pu[sel].ravel().copy(), pv[sel].ravel().copy(), np.zeros((1, 6)), intr[None, :].copy(),
                 rig.poses_from_Rt(Rt0[sel]), np.ones(1, dtype=np.uint8), True).normalised()
-    return q, count, sel
+    return q, count, sel, found
 
 
 def _finish_camera(q, count, sel):
@@ -64,7 +73,7 @@ def _finish_camera(q, count, sel):
     return q.intr[0].copy(), Rt
 
 
-def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None):
+def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None, ransac=None):
     """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
     principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
     intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
@@ -72,21 +81,31 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
     loss: None (the reference's plain least squares) or (kind, scale) of the refinement, see api.calibrate.
     model: "ts" (Triple Sphere, the reference), "ds" (Double Sphere: lambda starts at 0 and is held there) or "ucm" (Unified
     Camera Model: xi and lambda); fixed: further held intrinsics, as for api.calibrate.
+    ransac: None (the poses start from the least-squares fit of all corners), or rig.ransac_params(...): they start from
+    rig.estimate_extrinsic_ransac, a view without a pose there (exit code outside 5..7) is left out of the refinement (its Rt
+    stays 0), and summary["ransac"] = dict(inlier [V,n] bool, code [V], has [V]: the views that were kept).
     Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
     w = _model_masks(model, fixed, 1)
-    q, count, sel = _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr, model)
+    q, count, sel, found = _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr, model, ransac)
     _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
     intr, Rt = _finish_camera(q, count, sel)
+    if found is not None:
+        summary["ransac"] = found
     return intr, Rt, summary
 
 
-def _calibrate_cameras_batched(pus, pvs, hases, cols, rows, pitch, img_sizes, device, init_intrs, loss, model, masks):
+def _calibrate_cameras_batched(pus, pvs, hases, cols, rows, pitch, img_sizes, device, init_intrs, loss, model, masks, ransac=None):
     """calibrate_camera for every camera, the refinements of all of them in ONE batch (api.refinement_batch): the same
     start, poses and post-processing per camera, each camera's refinement as refinement() would return it alone."""
-    prep = [_prepare_camera(pu, pv, has, cols, rows, pitch, size, device, init, model)
+    prep = [_prepare_camera(pu, pv, has, cols, rows, pitch, size, device, init, model, ransac)
             for pu, pv, has, size, init in zip(pus, pvs, hases, img_sizes, init_intrs)]
-    res = api.refinement_batch([q for q, _, _ in prep], device, loss=loss, fixed=[int(w) for w in masks])
-    return [_finish_camera(q, count, sel) + (summary,) for (q, count, sel), (_, summary) in zip(prep, res)]
+    res = api.refinement_batch([p[0] for p in prep], device, loss=loss, fixed=[int(w) for w in masks])
+    out = []
+    for (q, count, sel, found), (_, summary) in zip(prep, res):
+        if found is not None:
+            summary["ransac"] = found
+        out.append(_finish_camera(q, count, sel) + (summary,))
+    return out
 
 
 def _top_left_is_bright(board_img, pitch):
@@ -130,27 +149,35 @@ def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, devi
 
 
 def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                    fixed=None) -> dict:
+                    fixed=None, ransac=None) -> dict:
     """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
     loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
     and held intrinsics of both refinements (calibrate_camera).
+    ransac: None, or rig.ransac_params(...) for the start poses of both calibrate() calls (calibrate_camera); a view either
+    call drops leaves `has`, and the result carries ransac = the second call's dict(inlier, code, has).
     Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
     img_size, has, pu, pv = _detect(images, cols, rows, sigma, device)
-    intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed)   # :57
+    intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed,
+                                       ransac=ransac)                                                                            # :57
+    if ransac is not None:
+        has = first["ransac"]["has"]
     _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device)
     # :127 -- the second calibrate() of the same object: a converged first refinement left has_init_guess_ set (TS.cpp:78),
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
     intr, Rt, second = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr=warm, loss=loss, model=model,
-                                        fixed=fixed)
-    return dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
+                                        fixed=fixed, ransac=ransac)
+    out = dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
+    if ransac is not None:
+        out.update(has=second["ransac"]["has"], ransac=second["ransac"])
+    return out
 
 
 def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None,
-                          model="ts", masks=None) -> list:
+                          model="ts", masks=None, ransac=None) -> list:
     """monocular_calib for every camera, stage by stage across the cameras: detection, the first calibrate, the refinement
     pass, the second calibrate -- each of the two refinements of all cameras in one batch (api.refinement_batch).
-    masks: [C] mask words (model included).  Returns monocular_calib's dict per camera."""
+    masks: [C] mask words (model included); ransac: as for monocular_calib.  Returns monocular_calib's dict per camera."""
     n_cam = len(images_by_camera)
     masks = np.zeros(n_cam, dtype=np.uint16) if masks is None else masks
     det = [_detect(imgs, cols, rows, sigma, device) for imgs in images_by_camera]
@@ -158,30 +185,38 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
     has = [d[1] for d in det]
     pu = [d[2] for d in det]
     pv = [d[3] for d in det]
-    first = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, [None] * n_cam, loss, model, masks)
+    first = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, [None] * n_cam, loss, model, masks, ransac)
+    if ransac is not None:
+        has = [f[2]["ransac"]["has"] for f in first]
     for m, imgs in enumerate(images_by_camera):
         _refine_pixels(imgs, first[m][0], first[m][1], has[m], pu[m], pv[m], cols, rows, pitch, sigma, device)
     warm = [f[0] if f[2]["termination_type"] == 0 else None for f in first]
-    second = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, warm, loss, model, masks)
-    return [dict(intr=second[m][0], Rt=second[m][1], has=has[m], pix_u=pu[m], pix_v=pv[m], first=first[m][2], second=second[m][2])
-            for m in range(n_cam)]
+    second = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, warm, loss, model, masks, ransac)
+    out = [dict(intr=second[m][0], Rt=second[m][1], has=has[m], pix_u=pu[m], pix_v=pv[m], first=first[m][2], second=second[m][2])
+           for m in range(n_cam)]
+    if ransac is not None:
+        for o in out:
+            o.update(has=o["second"]["ransac"]["has"], ransac=o["second"]["ransac"])
+    return out
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False) -> dict:
+                  fixed=None, batch_mono=False, ransac=None) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
     model ("ts" | "ds" | "ucm") and fixed (names or a [C] / [C, 9] mask, as for api.calibrate): held in every refinement and in
     the joint solve; the YAML keeps the 9-vector with lambda (and xi) = 0 (calib_io.to_double_sphere / to_ucm convert).
     batch_mono: the per-camera flow stage by stage across the cameras, each of its two refinement passes one batch call for
-    all cameras (monocular_calib_batch); False (the default) runs monocular_calib camera after camera."""
+    all cameras (monocular_calib_batch); False (the default) runs monocular_calib camera after camera.
+    ransac: None, or rig.ransac_params(...) for the start poses of every mono calibration (monocular_calib): the views it drops
+    are out of `has` when the rig is initialised, and mono[m]["ransac"] holds each camera's masks and codes."""
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
     if batch_mono:
-        mono = monocular_calib_batch(images_by_camera, cols, rows, pitch, sigma, device, loss=loss, model=model, masks=w)
+        mono = monocular_calib_batch(images_by_camera, cols, rows, pitch, sigma, device, loss=loss, model=model, masks=w, ransac=ransac)
     else:
-        mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]))
+        mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]), ransac=ransac)
                 for m, imgs in enumerate(images_by_camera)]
     W = board_points(cols, rows, pitch)
     inp = rig.RigInput(W, np.stack([m["intr"] for m in mono]), np.stack([m["has"] for m in mono]), np.stack([m["Rt"] for m in mono]),

@@ -191,3 +191,64 @@ def estimate_extrinsic_stages(intr, pix_u, pix_v, count, worlds, board_w: int, d
                                                          code.ctypes.data_as(ip)))
     return dict(Rt=Rt, n_estimated=done.value, T=T, H=H, rv0=pose0[:, :3], t0=pose0[:, 3:], rv=pose[:, :3], t=pose[:, 3:],
                 steps=steps, code=code)
+
+
+def ransac_params(threshold_px=None, n_hypotheses=None, min_inliers=None, seed=None) -> _lib.CRansacParams:
+    """tscm_ransac_params with the library's defaults (8.0 px, 256 hypotheses, min_inliers 0 = max(4, ceil(n / 2)),
+    seed 0), the given fields replaced."""
+    p = _lib.CRansacParams()
+    _lib.lib().tscm_ransac_default_params(C.byref(p))
+    if threshold_px is not None:
+        p.threshold_px = float(threshold_px)
+    if n_hypotheses is not None:
+        p.n_hypotheses = int(n_hypotheses)
+    if min_inliers is not None:
+        p.min_inliers = int(min_inliers)
+    if seed is not None:
+        p.seed = int(seed)
+    return p
+
+
+def _ransac_call(stages: bool, intr, pix_u, pix_v, count, worlds, board_w, params, device, Rt_init):
+    intr, pix_u, pix_v, count, worlds, V, n, Rt = _extrinsic_args(intr, pix_u, pix_v, count, worlds, Rt_init)
+    params = ransac_params() if params is None else params
+    inlier = np.zeros((V, n), dtype=np.uint8)
+    n_inl, code = np.zeros(V, dtype=np.int32), np.zeros(V, dtype=np.int32)
+    done, seconds = C.c_int(0), C.c_double(0.0)
+    ip = C.POINTER(C.c_int)
+    args = [_lib.dptr(intr), _lib.dptr(pix_u), _lib.dptr(pix_v), count.ctypes.data_as(ip), V, _lib.dptr(worlds), n, board_w,
+            C.byref(params), device, _lib.dptr(Rt), inlier.ctypes.data_as(C.POINTER(C.c_ubyte)), n_inl.ctypes.data_as(ip),
+            code.ctypes.data_as(ip), C.byref(done), C.byref(seconds)]
+    out = dict(Rt=Rt, n_inliers=n_inl, code=code)
+    if not stages:
+        _lib.check(_lib.lib().tscm_estimate_extrinsic_ransac(*args))
+    else:
+        H = params.n_hypotheses
+        samples, score = np.zeros((V, max(H, 0), 4), dtype=np.int32), np.zeros((V, max(H, 0)), dtype=np.int32)
+        winner, steps = np.zeros(V, dtype=np.int32), np.zeros(V, dtype=np.int32)
+        T, Hb, Hr, pose0, pose, rms = (np.zeros((V, 3, 3)), np.zeros((V, 3, 3)), np.zeros((V, 3, 3)), np.zeros((V, 6)),
+                                       np.zeros((V, 6)), np.zeros(V))
+        _lib.check(_lib.lib().tscm_estimate_extrinsic_ransac_stages(
+            *args, samples.ctypes.data_as(ip), score.ctypes.data_as(ip), winner.ctypes.data_as(ip), _lib.dptr(T), _lib.dptr(Hb),
+            _lib.dptr(Hr), _lib.dptr(pose0), _lib.dptr(pose), steps.ctypes.data_as(ip), _lib.dptr(rms)))
+        out.update(samples=samples, score=score, winner=winner, T=T, H_best=Hb, H_refit=Hr, rv0=pose0[:, :3], t0=pose0[:, 3:],
+                   rv=pose[:, :3], t=pose[:, 3:], steps=steps, rms_px=rms)
+    out.update(inlier=inlier.astype(bool), n_estimated=done.value, seconds_kernel=seconds.value)
+    return out
+
+
+def estimate_extrinsic_ransac(intr, pix_u, pix_v, count, worlds, board_w: int, params=None, device: int = 0, Rt_init=None):
+    """tscm_estimate_extrinsic_ransac: consensus search over 4-corner homographies and a refit on the winner's inliers
+    (definition: tscm.h) -> Rt [V,3,3], inlier [V,n] bool, n_inliers [V], code [V] (TSCM_EXTRINSIC_*, 8 no hypothesis,
+    9 few inliers), n_estimated.  A pose is written exactly where code is 5, 6 or 7; other views keep Rt_init (a copy;
+    zeros when None).  params: ransac_params(...), None for the defaults."""
+    r = _ransac_call(False, intr, pix_u, pix_v, count, worlds, board_w, params, device, Rt_init)
+    return r["Rt"], r["inlier"], r["n_inliers"], r["code"], r["n_estimated"]
+
+
+def estimate_extrinsic_ransac_stages(intr, pix_u, pix_v, count, worlds, board_w: int, params=None, device: int = 0, Rt_init=None) -> dict:
+    """tscm_estimate_extrinsic_ransac_stages: the same launch with every stage of every view.  Returns what
+    estimate_extrinsic_ransac returns under Rt, inlier, n_inliers, code, n_estimated, and samples [V,H,4] (-1 rejected),
+    score [V,H], winner [V], T, H_best, H_refit [V,3,3], rv0/t0, rv/t [V,3], steps [V], rms_px [V], seconds_kernel.
+    Stages a view does not reach are NaN (steps -1)."""
+    return _ransac_call(True, intr, pix_u, pix_v, count, worlds, board_w, params, device, Rt_init)
