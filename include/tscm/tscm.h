@@ -231,6 +231,9 @@ int tscm_solver_set_comm(tscm_solver *s, tscm_comm *comm);   /* frame-sharded mu
  * (s, 3): like 1 for the other hand-off of an iteration -- one of the reductions behind the evaluation that ride in
  * the Schur-complement launch never counts itself in. */
 int tscm_solver_debug_withhold_handoff(tscm_solver *s, int on);
+/* TESTS ONLY: which wave of a Schur-complement workgroup contracts which boards of its chunk does not change a bit of a
+ * solve.  rot = 0 (the default) or 2: every workgroup of every later solve of `s` starts its deal at wave 0 / wave 2. */
+int tscm_solver_debug_schur_rot(tscm_solver *s, int rot);
 int tscm_solver_reruns(const tscm_solver *s);                /* solves of `s` that were run again so far (>= 0) */
 int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_summary *summary);
 /* Same as _solve but parameters start from / are left in device memory (used by the

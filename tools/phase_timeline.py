@@ -5,7 +5,10 @@ solve, the launches of LM iteration 5.  Per kernel: when its workgroups start an
 order in which the workgroups started (the grid's rounds), and how many workgroups are in their LOAD phase against time -- a
 kernel streams if that number is constant, it runs in lock step if it is a square wave.
 
-    python tools/phase_timeline.py [--config 5]        (GPU box)"""
+    python tools/phase_timeline.py [--config 5] [--rot 0|2] [--n-cu 256]        (GPU box)
+
+--rot puts every workgroup of k_schur_gram at that rot (tscm_solver_debug_schur_rot); the last lines are the Gram phase per
+workgroup, split by the first and the second workgroup of a CU (--n-cu: the device's CU count)."""
 import ctypes
 import os
 import sys
@@ -57,10 +60,30 @@ def report(name, st, phases, n_cam_blocks=0):
         print(f"  {t:6.1f}   " + "  ".join(f"{c:10d}" for c in cnt))
 
 
+def gram_report(st, n_cu):
+    """k_schur_gram's phase 1 per workgroup: thread 0 stamps the end of ITS wave's contraction ("Gram"); the workgroup is through
+    when its slowest wave is, which is where the barrier of the "tiles" phase lets go -- so Gram + tiles is the phase as the launch
+    sees it.  Split by the first / second workgroup of a CU (workgroups b and b + n_cu share one), whose deals differ by rot."""
+    idx = np.nonzero(st[:, 0] > 0)[0]
+    idx = idx[st[idx, 6] > 0]
+    g0, gt = (st[idx, 4] - st[idx, 3]) / 100.0, (st[idx, 5] - st[idx, 3]) / 100.0
+    t0 = st[idx, 0].min()
+    print(f"Gram phase of {len(idx)} workgroups [us]: wave 0's contraction median {np.median(g0):.2f} mean {g0.mean():.2f} max {g0.max():.2f}; "
+          f"Gram + tiles median {np.median(gt):.2f} mean {gt.mean():.2f} p90 {np.quantile(gt, 0.9):.2f} max {gt.max():.2f}; "
+          f"last workgroup through {((st[idx, 5] - t0) / 100.0).max():.2f} us after the launch's first start")
+    for name, sel in (("first of its CU ", (idx // n_cu) % 2 == 0), ("second of its CU", (idx // n_cu) % 2 == 1)):
+        if sel.any():
+            print(f"  {name}: {int(sel.sum()):4d} workgroups, wave 0 median {np.median(g0[sel]):.2f}, Gram + tiles median {np.median(gt[sel]):.2f} max {gt[sel].max():.2f}")
+
+
 def main():
     cfg = int(sys.argv[sys.argv.index("--config") + 1]) if "--config" in sys.argv else 5
+    rot = int(sys.argv[sys.argv.index("--rot") + 1]) if "--rot" in sys.argv else None      # 0 / 2: every workgroup of k_schur_gram at that rot
+    n_cu = int(sys.argv[sys.argv.index("--n-cu") + 1]) if "--n-cu" in sys.argv else 256
     p = synth.make_config(cfg).normalised()
     with api.Solver(p) as s:
+        if rot is not None:
+            s.debug_schur_rot(rot)
         s.solve(max_num_iterations=10, function_tolerance=-1.0, parameter_tolerance=-1.0, gradient_tolerance=-1.0, min_trust_region_radius=0.0)
         G = 2048
         buf = np.zeros(3 * 8 * G, dtype=np.int64)
@@ -78,6 +101,7 @@ def main():
                     print(f"{name} ({len(r)}), us after the launch's first start: start {a[:, 0].mean():.2f}, results computed and stores issued {a[:, 1].mean():.2f} (max {a[:, 1].max():.2f}), "
                           f"stores acknowledged {a[:, 2].mean():.2f} (max {a[:, 2].max():.2f}), counted in {a[:, 3].mean():.2f} (max {a[:, 3].max():.2f})")
         report("k_schur_gram", st[0], ["head/control", "records+E sums", "factor", "Gram", "tiles"], n_cam_blocks=16 * p.n_cameras)
+        gram_report(st[0], n_cu)
         report("k_backsub_prep / riders", st[1][:, [0, 1, 2, 3, 4, 5, 6, 7]][:, [1, 2, 3, 4, 5, 5, 6, 7]], ["W.yhat", "board solve", "view constants"])
 
 

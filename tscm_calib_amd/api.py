@@ -73,6 +73,11 @@ class Solver:
         the Schur-complement launch."""
         _l.check(_l.lib().tscm_solver_debug_withhold_handoff(self._h, int(on)))
 
+    def debug_schur_rot(self, rot=0):
+        """Tests only: every Schur-complement workgroup of the later solves starts its deal of board groups at wave 0 or 2
+        (tscm_solver_debug_schur_rot; 0 is the default).  The bits must not depend on it."""
+        _l.check(_l.lib().tscm_solver_debug_schur_rot(self._h, int(rot)))
+
     def reruns(self) -> int:
         """Solves of this solver that were run again on separate launches after a late device-side hand-off."""
         n = _l.lib().tscm_solver_reruns(self._h)

@@ -28,6 +28,33 @@ constexpr int kMaxCam = 32;        // larger rigs: k_solve_reduced_big factors t
 constexpr int kChunkBoards = 64;   // boards of one chunk of k_schur_gram at most (its LDS holds their factors)
 static_assert(kSmallBids >= kMaxCamLds * (kMaxCamLds + 1) / 2, "every camera pair of a rig the register/LDS solver takes");
 
+// shared with device code (k_schur_gram): unmarked under a plain C++ compiler
+#ifdef __HIPCC__
+#define TSCM_LAYOUT_FN __host__ __device__ inline
+#else
+#define TSCM_LAYOUT_FN inline
+#endif
+
+// Phase 1 of k_schur_gram contracts a chunk of nbd <= kChunkBoards boards in groups of four (the last one ragged), and the
+// four waves of the workgroup share the n = ceil(nbd / 4) groups evenly, each a run of adjacent groups: VIRTUAL wave v takes
+// floor(n / 4) groups, the first n mod 4 waves one more; its k-th group is returned, or -1 when it has no such group (then it
+// has none for any later k either).  40 boards: 3, 3, 2, 2 groups (0-2, 3-5, 6-7, 8-9), not the 4, 4, 2, 0 of "wave w takes
+// boards 16 w .. 16 w + 15"; 64 boards: 4, 4, 4, 4, which IS that assignment -- a full chunk keeps its bits and its access
+// pattern.  (Dealing the groups round-robin, v, v + 4, .., balances the same and measured the same at config 4, but a wave's
+// requests then stride over the chunk and config 5's launch was 0.45 us slower: DESIGN 13.)
+// Sums are ordered by the virtual wave -- a wave adds its groups in ascending k, the four waves' tiles are added as
+// (v0 + v1) + (v2 + v3) -- and physical wave (v + rot) & 3 plays virtual wave v: the result does not depend on rot, which only
+// decides which wave (and with it which SIMD of the CU) does the work.  Every launch runs at rot 0: giving the second
+// workgroup of a CU rot 2 (3, 3, 2, 2 groups against 2, 2, 3, 3 on the four SIMDs) was measured and bought nothing
+// (DESIGN 13); the argument stays for the tests, which ask for the same bits at rot 0 and 2.
+TSCM_LAYOUT_FN int schur_group_of(int nbd, int v, int k)
+{
+    const int n = (nbd + 3) >> 2, base = n >> 2, rem = n & 3;
+    return k < base + (v < rem ? 1 : 0) ? v * base + (v < rem ? v : rem) + k : -1;
+}
+// ... and the virtual wave that physical wave `wave` plays under rot
+TSCM_LAYOUT_FN int schur_virtual_wave(int wave, int rot) { return (wave - rot) & 3; }
+
 struct Int4 { int x, y, z, w; };   // what the device reads as int4 (the upload converts)
 
 // the device facts the layout depends on: compute units, and resident waves per CU of the Gram kernel (k_eval_gram4)

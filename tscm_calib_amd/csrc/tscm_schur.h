@@ -117,16 +117,22 @@ __global__ __launch_bounds__(256) void k_schur_factor(DevProblem P, DevState S)
 // Y = L^-1 S_b W) in ONE launch.  Boards are grouped by their camera set ("signature"); one 4-wave workgroup per
 // chunk of <= 64 boards of ONE signature, so the NV(NV+1)/2 16x16 tiles of a chunk map to fixed camera-pair blocks
 // and stay in registers as MFMA accumulators.
-//   phase 0a  16 lanes per board sum the E records of its views (contiguous: coalesced) into LDS
+//   phase 0a  16 lanes per board sum the E records of its views (contiguous: coalesced) into LDS, 16 boards per pass; in the
+//             RIDE instantiation a pass whose boards all lie beyond the chunk's end requests nothing and stores nothing
+//             (-0.3 us at config 4's 40 boards; the same two conditions cost the non-riding instantiation 0.85 us at
+//             config 5, where no pass is ever empty -- this kernel's code is that touchy, HISTORY A.6 -- so it does without)
 //   phase 0b  one lane per board: damped Cholesky -> the board's factor record, in LDS
 //   (then the records leave for HBM -- the back-substitution needs them -- as one coalesced stream per board)
-//   phase 1   a wave takes FOUR boards at a time: lane (a, kq) loads column a of the W records of board kq of the
+//   phase 1   the chunk's groups of FOUR boards are shared evenly among the four waves (schur_group_of: a chunk of 40
+//             boards is 3, 3, 2, 2 groups, not 4, 4, 2, 0 -- the phase is bound by the SIMD's one fp64 pipe and lies on the
+//             launch's critical path).
+//             A wave takes four boards at a time: lane (a, kq) loads column a of the W records of board kq of the
 //             group and runs the 21-FMA forward substitution with that board's multipliers (LDS).  The matrix core
 //             contracts over k, and T is a sum over boards -- so the k index of v_mfma_f64_16x16x4 IS the board:
 //             for each of the 6 rows r, one MFMA per tile adds sum_{4 boards} Y_p[r][i] Y_q[r][j].  No lane computes
 //             anything twice and no operand has to be moved: 6 NT MFMAs and 27 NV FMAs per lane per four boards.
 //             The next group's columns are requested before the MFMAs, which cover their latency.
-// The four waves' tiles are summed in a fixed order through LDS.
+// The four waves' tiles are summed in a fixed order through LDS: by VIRTUAL wave, so the bits do not depend on `rot` (tests: tscm_solver_debug_schur_rot).
 // grid (chunks of this NV) x 256; a chunk has at most kChunkBoards boards (tscm_layout.h)
 
 
@@ -214,7 +220,7 @@ struct RawTc {
 // launch invalidated (what k_reduce_stats wrote has always reached the next launch's plain loads that way) -- so the first touch
 // of a line from an XCD fetches what was written through, or hits the writer's own written-through copy.
 template <int NV, bool RIDE = false>
-__global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(DevProblem P, DevState S, int chunk0, int ctl, int first_round, int ctl_epoch, int stats_target, int n_chunks)
+__global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(DevProblem P, DevState S, int chunk0, int ctl, int first_round, int ctl_epoch, int stats_target, int n_chunks, int rot)
 {
 #ifdef TSCM_WAVE_TIMELINE
     KtlScope ktl_scope(3, ctl && !RIDE ? S.ctrl_snap : static_cast<const CtrlHead *>(S.ctrl));      // (the snapshot: the writer workgroup advances S.ctrl while later rounds start)
@@ -248,6 +254,8 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int a = lane & 15, kq = lane >> 4;
+    // phase 1's deal (tscm_layout.h): this wave plays virtual wave vw and takes the groups schur_group_of(nbd, vw, 0 .. 3)
+    const int vw = schur_virtual_wave(wave, rot);
     const int c0 = desc.x, nbd = desc.y - desc.x, slot0 = desc.z;       // boards c0 .. c0 + nbd - 1 (<= kChunkBoards), views at slots slot0 + NV * i
     constexpr unsigned BAD = 0xffffe000u;
     double ev[4][NJ];
@@ -274,7 +282,7 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int bf = 16 * i + (tid >> 4);
-                    const unsigned o0 = idx < NE ? first + per_slot * (unsigned)(slot0 + NV * min(bf, nbd - 1)) : BAD;
+                    const unsigned o0 = idx < NE && 16 * i < nbd ? first + per_slot * (unsigned)(slot0 + NV * min(bf, nbd - 1)) : BAD;
                     double acc = 0.0;
 #pragma unroll
                     for (int p = 0; p < NV; ++p) acc += buf_load_f64(r_w, (p == 0 || summed) ? o0 : BAD, per_slot * (unsigned)p);
@@ -284,8 +292,8 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int bg = 16 * wave + 4 * g + kq;
-            const unsigned base = (a < 14 && bg < nbd) ? 8u * ((unsigned)kRecW * (unsigned)(slot0 + NV * bg) + 6u * (unsigned)a) : BAD;
+            const int bg = 4 * schur_group_of(nbd, vw, g) + kq;             // (no such group: negative)
+            const unsigned base = (a < 14 && bg >= 0 && bg < nbd) ? 8u * ((unsigned)kRecW * (unsigned)(slot0 + NV * bg) + 6u * (unsigned)a) : BAD;
 #pragma unroll
             for (int p = 0; p < NV; ++p)
 #pragma unroll
@@ -464,8 +472,8 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int bg = 16 * wave + 4 * g + kq;
-            const unsigned base = (a < 14 && bg < nbd) ? 8u * ((unsigned)kRecW * (unsigned)(slot0 + NV * bg) + 6u * (unsigned)a) : BAD;
+            const int bg = 4 * schur_group_of(nbd, vw, g) + kq;             // (no such group: negative)
+            const unsigned base = (a < 14 && bg >= 0 && bg < nbd) ? 8u * ((unsigned)kRecW * (unsigned)(slot0 + NV * bg) + 6u * (unsigned)a) : BAD;
 #pragma unroll
             for (int p = 0; p < NV; ++p)
 #pragma unroll
@@ -485,9 +493,11 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
     {
         const int e = tid & 15, grp = tid >> 4;
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i) {
+            if (RIDE && 16 * i >= nbd) break;                                // workgroup-uniform: a pass without boards (RIDE: see the head)
 #pragma unroll
             for (int j = 0; j < NJ; ++j) if (e + 16 * j < NE) sumE[16 * i + grp][e + 16 * j] = ev[i][j];
+        }
     }
     __syncthreads();
     PHASE_STAMP(ts1);
@@ -521,8 +531,9 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
     const bool grad_col = a == kFR;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        if (16 * wave + 4 * g >= nbd) break;                              // wave-uniform
-        const int bg = 16 * wave + 4 * g + kq;
+        const int grp = schur_group_of(nbd, vw, g);
+        if (grp < 0) break;                                               // wave-uniform
+        const int bg = 4 * grp + kq;
         const bool valid = bg < nbd;
         const int bl = min(bg, nbd - 1);
         FacFwd F;
@@ -547,7 +558,7 @@ __global__ __launch_bounds__(256, RIDE && NV <= 2 ? 2 : 1) void k_schur_gram(Dev
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) tiles[wave][t][(kq + 4 * r) * 16 + a] = acc[t][r];
+        for (int r = 0; r < 4; ++r) tiles[vw][t][(kq + 4 * r) * 16 + a] = acc[t][r];
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < NT; ++t)

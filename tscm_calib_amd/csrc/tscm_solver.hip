@@ -169,6 +169,7 @@ struct tscm_solver {
     // free columns are derived from are L.cam_const, L.cam_active, L.pair_present: plan_columns)
     std::vector<unsigned short> fixed;
     int n_cu = 1;
+    int schur_rot = 0;                  // k_schur_gram's rot: the wave its workgroups start their deal of board groups at, 0 (tests: 2, tscm_solver_debug_schur_rot)
     double *d_view_sq = nullptr;        // [2 V] k_reproj_error's output for the RMSE of a robust solve (allocated by the first one)
     // dominant-kernel timing
     int timing = 0;                     // 0 = off, n = bracket every n-th launch of the dominant kernel (and every n-th exchange) with HIP events
@@ -551,6 +552,15 @@ extern "C" int tscm_solver_debug_withhold_handoff(tscm_solver *s, int on)
     return 0;
 }
 
+// For the tests of k_schur_gram's deal: which wave of a workgroup contracts which boards must not change a bit.
+extern "C" int tscm_solver_debug_schur_rot(tscm_solver *s, int rot)
+{
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    if (rot != 0 && rot != 2) return fail(TSCM_E_INVALID, "rot must be 0 or 2");
+    s->schur_rot = rot;
+    return 0;
+}
+
 extern "C" int tscm_solver_reruns(const tscm_solver *s)
 {
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
@@ -802,7 +812,7 @@ static int enqueue(tscm_solver *s, const Launch &l)
     const DevState &S = s->S;
     hipStream_t st = s->stream;
     const dim3 grid(l.grid);
-    auto schur = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, P, S, l.chunk0, l.ctl, l.first_round, l.ce, l.target, l.n_chunks); };
+    auto schur = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, P, S, l.chunk0, l.ctl, l.first_round, l.ce, l.target, l.n_chunks, s->schur_rot); };
     auto nd = [&](auto kernel) {
         const int v = l.nd;
         hipLaunchKernelGGL(kernel, grid, dim3(kNdThreads), std::max(s->lds_nd[v], l.n_bs ? s->lds_bs : (size_t)0), st, P, S, s->d_nd_map[v], s->d_nd_tab[v], s->d_nd_bs[v],
