@@ -3,6 +3,10 @@
 // wherever it sits in the batch; the refusals come back with their codes.  Prints one JSON line; exit code 1 on a failure.
 //   batch_plan_check random <seed> <batches>
 //   batch_plan_check refusals
+//   batch_plan_check plan <n_points> <problem>...     plans the batch described on the command line and prints its shape:
+//       <problem> = <n_boards>/<corner count of view 0>,<of view 1>,.../<constant board>,<constant board>,...
+//       (view v sees board v; the list of constant boards may be empty): per problem its chunks (slots of each) and the
+//       active flag of every slot, in slot order
 #include "../../tscm_calib_amd/csrc/tscm_batch_plan.h"
 
 #include <cstdio>
@@ -240,12 +244,86 @@ int refusals_mode()
     return 0;
 }
 
+// a comma-separated list of non-negative integers; false on anything else
+bool int_list(const std::string &s, std::vector<int> &out)
+{
+    out.clear();
+    size_t at = 0;
+    while (at < s.size()) {
+        size_t end = s.find(',', at);
+        if (end == std::string::npos) end = s.size();
+        if (end == at || end - at > 9) return false;
+        int v = 0;
+        for (size_t i = at; i < end; ++i) {
+            if (s[i] < '0' || s[i] > '9') return false;
+            v = 10 * v + (s[i] - '0');
+        }
+        out.push_back(v);
+        at = end + 1;
+    }
+    return s.empty() || s.back() != ',';
+}
+
+int plan_mode(int argc, char **argv)
+{
+    std::vector<int> one;
+    if (!int_list(argv[2], one) || one.size() != 1 || one[0] < 1 || one[0] > 4096) { std::fprintf(stderr, "plan: bad n_points\n"); return 2; }
+    const int n_points = one[0], n = argc - 3;
+    std::vector<double> xy;
+    for (int j = 0; j < n_points; ++j) { xy.push_back(45.0 * (j % 16)); xy.push_back(45.0 * (j / 16)); }
+    std::vector<Owned> own(n);
+    std::vector<tscm_problem> ps(n);
+    for (int i = 0; i < n; ++i) {
+        const std::string a = argv[3 + i];
+        const size_t s1 = a.find('/'), s2 = s1 == std::string::npos ? s1 : a.find('/', s1 + 1);
+        std::vector<int> nb, cnt, cst;
+        if (s2 == std::string::npos || !int_list(a.substr(0, s1), nb) || nb.size() != 1 || !int_list(a.substr(s1 + 1, s2 - s1 - 1), cnt) ||
+            !int_list(a.substr(s2 + 1), cst) || (int)cnt.size() > nb[0]) { std::fprintf(stderr, "plan: bad problem '%s'\n", a.c_str()); return 2; }
+        Owned &o = own[i];
+        const int B = nb[0], V = (int)cnt.size();
+        o.cam.assign(V, 0); o.board.resize(V); o.off.resize(V); o.cnt = cnt;
+        int total = 0;
+        for (int v = 0; v < V; ++v) { o.board[v] = v; o.off[v] = total; total += cnt[v]; }
+        o.u.assign(std::max(total, 1), 0.0); o.v.assign(std::max(total, 1), 0.0);
+        o.intr.assign(9, 1.0); o.board_rt.assign(6 * (size_t)std::max(B, 1), 0.0);
+        o.bconst.assign(std::max(B, 1), 0);
+        for (int b : cst) { if (b >= B) { std::fprintf(stderr, "plan: constant board %d of %d\n", b, B); return 2; } o.bconst[b] = 1; }
+        tscm_problem &p = o.p;
+        p = tscm_problem{};
+        p.n_cameras = 1; p.n_boards = B; p.n_points = n_points; p.n_views = V;
+        p.board_xy = xy.data(); p.view_camera = o.cam.data(); p.view_board = o.board.data(); p.view_offset = o.off.data();
+        p.view_count = o.cnt.data(); p.obs_u = o.u.data(); p.obs_v = o.v.data(); p.intr = o.intr.data(); p.board_rt = o.board_rt.data();
+        p.mono = 1;
+        p.board_pose_constant = cst.empty() ? nullptr : o.bconst.data();
+        ps[i] = p;
+    }
+    BatchPlan b;
+    std::string err;
+    const int rc = plan_batch(ps.data(), n, defaults(), nullptr, TSCM_LOSS_NONE, 0.0, b, err);
+    if (rc) { std::printf("{\"ok\": false, \"rc\": %d, \"why\": \"%s\"}\n", rc, err.c_str()); return 0; }
+    std::printf("{\"ok\": true, \"n_chunks\": %d, \"n_slots\": %d, \"n_boards\": %d, \"min_chunk\": %d, \"max_chunks\": %d, \"max_chunk_slots\": %d, \"max_points\": %d, \"problems\": [",
+                (int)b.chunk.size(), (int)b.slot_prob.size(), b.B, kMbMinChunk, kMbMaxChunks, kMbMaxChunkSlots, kMbMaxPoints);
+    for (int i = 0; i < n; ++i) {
+        const int k = b.dev_of[i];
+        std::printf("%s{\"device\": %s, \"chunks\": [", i ? ", " : "", k >= 0 ? "true" : "false");
+        if (k >= 0) for (int c = b.chunk_ptr[k]; c < b.chunk_ptr[k + 1]; ++c) std::printf("%s%d", c > b.chunk_ptr[k] ? ", " : "", b.chunk[c].z - b.chunk[c].y);
+        std::printf("], \"active\": [");
+        if (k >= 0) for (int q = b.slot_ptr[k]; q < b.slot_ptr[k + 1]; ++q) std::printf("%s%d", q > b.slot_ptr[k] ? ", " : "", (int)b.slot_active[q]);
+        std::printf("], \"counts\": [");
+        if (k >= 0) for (int q = b.slot_ptr[k]; q < b.slot_ptr[k + 1]; ++q) std::printf("%s%d", q > b.slot_ptr[k] ? ", " : "", b.slot_count[q]);
+        std::printf("], \"boards\": %d}", k >= 0 ? b.board_ptr[k + 1] - b.board_ptr[k] : 0);
+    }
+    std::printf("]}\n");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
 {
     if (argc >= 4 && !std::strcmp(argv[1], "random")) return random_mode((unsigned)std::atoi(argv[2]), std::atoi(argv[3]));
     if (argc >= 2 && !std::strcmp(argv[1], "refusals")) return refusals_mode();
-    std::fprintf(stderr, "usage: batch_plan_check random <seed> <batches> | refusals\n");
+    if (argc >= 4 && !std::strcmp(argv[1], "plan")) return plan_mode(argc, argv);
+    std::fprintf(stderr, "usage: batch_plan_check random <seed> <batches> | refusals | plan <n_points> <problem>...\n");
     return 2;
 }

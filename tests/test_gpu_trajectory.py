@@ -28,8 +28,8 @@ def _pattern(s):
     return "".join("A" if it["step_is_successful"] else ("r" if it["step_is_valid"] else "x") for it in s["iterations"][1:])
 
 
-def _compare(gs, os_, upto=None, cost_rtol=1e-5, radius_rtol=2e-2):
-    assert gs["num_iterations"] == os_["num_iterations"] == 51 and gs["lm_iterations"] == 50
+def _compare(gs, os_, upto=None, cost_rtol=1e-5, radius_rtol=2e-2, lm_iterations=50):
+    assert gs["num_iterations"] == os_["num_iterations"] == lm_iterations + 1 and gs["lm_iterations"] == lm_iterations
     n = len(os_["iterations"]) if upto is None else upto
     assert _pattern(gs)[:n - 1] == _pattern(os_)[:n - 1]
     for a, b in list(zip(gs["iterations"], os_["iterations"]))[:n]:
