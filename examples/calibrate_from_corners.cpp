@@ -5,14 +5,18 @@
 //       -Wl,-rpath,$PWD/tscm_calib_amd/csrc -o examples/calibrate_from_corners        (one command line)
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
 //                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
-//                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]
+//                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
 //    --ransac: the start poses come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view without consensus leaves
-//    the calibration, and per camera the views kept and the share of inlier corners are printed)
+//    the calibration, and per camera the views kept and the share of inlier corners are printed.
+//    --covariance (rigs): after the joint solve, one line per camera parameter, `name value +- standard deviation`
+//    (MultiCalib::covariance; 0 for a held parameter), then sigma and min_pivot_ratio -- near 0 when the views do not
+//    determine some parameter)
 #include <tscm/tscm_calib.hpp>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,7 +26,7 @@ int main(int argc, char **argv)
     int loss = TSCM_LOSS_NONE;
     double loss_scale = 1.0;
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
-    bool bad_args = argc < 3, use_ransac = false;
+    bool bad_args = argc < 3, use_ransac = false, covariance = false;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
     for (int i = 3; i < argc && !bad_args; ++i) {
@@ -41,13 +45,15 @@ int main(int argc, char **argv)
         } else if (!std::strcmp(argv[i], "--ransac") && i + 1 < argc) {
             use_ransac = true;
             bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
+        } else if (!std::strcmp(argv[i], "--covariance")) {
+            covariance = true;
         } else {
             bad_args = true;
         }
     }
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -89,6 +95,18 @@ int main(int argc, char **argv)
             for (int m = 0; m < C; ++m) std::printf("camera_%d reprojection error: %.6f\n", m, mul_calib.camera_error[m]);
             std::printf("average reproject error: %.6f\n", mul_calib.mean_error);
             mul_calib.write_yaml(argv[2]);                                   // main.cpp:305-319
+            if (covariance) {
+                const tscm::MultiCalib::Covariance cov = mul_calib.covariance();
+                static const char *const names[15] = { "r0", "r1", "r2", "t0", "t1", "t2", "fx", "fy", "cx", "cy", "xi", "lambda", "alpha", "b", "c" };
+                if (cov.info.status != 0) std::printf("covariance: singular %s (%d)\n", cov.info.status == 1 ? "board block" : "reduced system", cov.info.where);
+                for (int m = 0; m < C; ++m)
+                    for (int a = 0; a < 13; ++a) {
+                        const double value = a < 6 ? mul_calib.cameras_[m].rt_[a] : mul_calib.cameras_[m].intrinsic_[a - 6];
+                        const double sd = a < 6 ? cov.cam_rt_std[6 * (size_t)m + a] : cov.intr_std[9 * (size_t)m + a - 6];
+                        std::printf("camera_%d %s %.17g +- %.17g\n", m, names[a], value, sd);
+                    }
+                std::printf("sigma %.17g  min_pivot_ratio %.17g  free columns %d\n", std::sqrt(cov.sigma2), cov.info.min_pivot_ratio, cov.info.n_free);
+            }
         } else if (C == 1) {
             const double I3[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t0[3] = { 0, 0, 0 };
             tscm::check(tscm_yaml_write(argv[2], 1, cameras[0].intrinsic_.data(), I3, t0));

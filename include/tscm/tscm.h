@@ -395,6 +395,66 @@ int tscm_solve_mono_batch(const tscm_problem *problems, int n_problems, int devi
                           const unsigned short *fixed /* [n_problems] or NULL */, int loss_kind, double loss_scale,
                           tscm_summary *summaries /* [n_problems] */);
 
+/* ------------------------------------------------------------------ parameter covariance
+ * What ceres::Covariance gives a Ceres user: Sigma = (J^T J)^-1 over the free columns of the problem at its current
+ * parameters, NOT multiplied by sigma^2 (Ceres' convention), plus sigma^2 and the standard deviations that follow.  A
+ * stand-alone stage behind a solve; it runs no kernel of the LM iteration.
+ *
+ * Free columns.  A camera's 15 columns are (pose 6, fx fy cx cy xi lambda alpha b c).
+ *   - pose columns are free unless the problem is mono, cam_pose_constant[m] is set, or the camera has no view with corners;
+ *   - intrinsic k < 7 is free unless it is held (bit k of fixed[m], TSCM_FIX_*) or the camera has no view with corners;
+ *   - b and c are never free;
+ *   - a board's 6 columns are free if the board has a view with corners and board_pose_constant[i] is not set;
+ *   - n_free = free camera columns + 6 * free boards.
+ * Jacobian.  J is the Jacobian at the problem's parameters, corrected by the loss as a robust solve corrects it
+ * (sqrt(rho') on a corner's rows): the blocks are board_gram, view_cross, cam_gram and cost of
+ * tscm_eval_normal_equations_robust with default options (the fp64 Gram kernel).
+ * Covariance.  With B_i = board_gram[i], W_v = view_cross[v] restricted to the free camera columns, C =
+ * blockdiag(cam_gram) and Z_v = B_i^-1 W_v:
+ *   S        = C - sum over free boards i, over the views v, v' of board i, of W_v^T Z_v'   (free camera columns, dense)
+ *   Sigma_cc = S^-1
+ *   Sigma_bb,i = B_i^-1 + sum over the views v, v' of board i of Z_v Sigma_cc[m_v, m_v'] Z_v'^T
+ * Board-camera cross blocks are not formed.  S is scaled to unit diagonal, factored by Cholesky, inverted from the factor
+ * and scaled back; every B_i by a 6 x 6 Cholesky.
+ * Scale.  sigma2 = 2 cost / (n_residuals - n_free), n_residuals = 2 * corners; NaN when that difference is <= 0.  The
+ * standard deviations are sqrt(sigma2 * diagonal), and exactly 0 for columns that are not free.
+ * Singularity.  A Cholesky pivot that is not > 0 (NaN included) ends the call with TSCM_OK, every element of the five output
+ * arrays NaN and info->status = 1 (a board block; where = the lowest such board) or 2 (the reduced system; where = camera *
+ * 15 + column of the first such pivot); info keeps n_free, n_residuals, cost and sigma2.  min_pivot_ratio is the smallest
+ * pivot of the scaled reduced system, whose diagonal is 1 before the factorisation (the failing pivot with status 2, NaN
+ * with status 1, 1 when no camera column is free): near 0 for a rig without a constant camera pose (gauge freedom) or an
+ * unobservable parameter.  The library applies no threshold of its own.
+ * Two calls on the same input give the same bytes (no floating-point atomics, every sum in a fixed order).
+ *
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL problem, info or required
+ * block; info->struct_size other than sizeof(tscm_covariance_info); mask bits 9 and up; an unknown loss kind, or a scale that
+ * is not finite and > 0; a view_camera or view_board out of range; n_cameras outside 1..32; cam_free set for b or c.
+ * device_index: as `device` elsewhere, TSCM_E_NO_DEVICE outside [0, tscm_device_count()), after the argument checks. */
+typedef struct tscm_covariance_info {
+    int struct_size;               /* sizeof(tscm_covariance_info), set by the caller                                 */
+    int status;                    /* 0 ok, 1 singular board block, 2 singular reduced system                          */
+    int where;                     /* status 1: board; status 2: camera * 15 + column; else -1                         */
+    int n_free;
+    long long n_residuals;         /* 2 * corners (tscm_covariance only, else 0)                                       */
+    double cost, sigma2;           /* tscm_covariance only; else 0 and NaN                                             */
+    double min_pivot_ratio;
+    double seconds_kernel[4];      /* device seconds: board factor, Schur complement, reduced inverse, board marginals */
+} tscm_covariance_info;
+
+/* cam_cov [C*15][C*15] and board_cov [B][6][6]: zero rows / columns / blocks where not free; either may be NULL, as may
+ * cam_rt_std [C*6], intr_std [C*9] and board_rt_std [B*6].  fixed: [C] mask words or NULL.  Host pointers. */
+int tscm_covariance(const tscm_problem *problem, int device_index, const unsigned short *fixed, int loss_kind, double loss_scale,
+                    double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std,
+                    tscm_covariance_info *info);
+
+/* The same kernels on blocks the caller gives (the host layout of tscm_eval_normal_equations; board_grad, cam_grad and the
+ * cost are not needed) and the caller's masks cam_free [C*15], board_free [B]; every view counts.  For parity tests and
+ * crafted inputs.  cost, sigma2 and n_residuals stay 0 / NaN / 0. */
+int tscm_covariance_from_normal_equations(int n_cameras, int n_boards, int n_views, const int *view_camera, const int *view_board,
+                                          const double *board_gram, const double *view_cross, const double *cam_gram,
+                                          const unsigned char *cam_free, const unsigned char *board_free, int device_index,
+                                          double *cam_cov, double *board_cov, tscm_covariance_info *info);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

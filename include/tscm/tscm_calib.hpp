@@ -572,33 +572,53 @@ public:
         fixed_[(size_t)m] = fixed;
     }
 
-    // multi_calib.cpp:155-283: joint LM, write-back (update_param), reprojection-error report
-    void calibrate(const tscm_options *options = nullptr)
+    // the problem of multi_calib.cpp:157-207 at the objects' current parameters (the arrays P points into live in here)
+    struct JointProblem {
+        std::vector<double> bxy, u, v, crt, I, brt;
+        std::vector<int> vc, vb, vo, vn;
+        std::vector<unsigned char> cc;
+        std::vector<unsigned short> fixed;
+        bool any_fixed;
+        tscm_problem P;
+    };
+    void joint_problem(JointProblem &q) const
     {
         const int C = (int)cameras_.size(), B = (int)chessboards_.size(), n = (int)worlds_.size();
-        std::vector<double> bxy(2 * (size_t)n), u, v, crt(6 * (size_t)C), I(9 * (size_t)C), brt(6 * (size_t)B, 0.0);
-        std::vector<int> vc, vb, vo, vn;
-        std::vector<unsigned char> cc(C, 0);
-        for (int j = 0; j < n; ++j) { bxy[2 * j] = worlds_[j].x; bxy[2 * j + 1] = worlds_[j].y; }
+        q.bxy.assign(2 * (size_t)n, 0.0); q.crt.assign(6 * (size_t)C, 0.0); q.I.assign(9 * (size_t)C, 0.0); q.brt.assign(6 * (size_t)B, 0.0);
+        q.cc.assign(C, 0);
+        for (int j = 0; j < n; ++j) { q.bxy[2 * j] = worlds_[j].x; q.bxy[2 * j + 1] = worlds_[j].y; }
         for (int m = 0; m < C; ++m)                                      // :162-207: camera m, board i, corner j
             for (int i = 0; i < B; ++i) {
                 if (!chessboards_[i].is_initial() || cameras_[m].pixel_coordinates_[i].empty()) continue;
-                vc.push_back(m); vb.push_back(i); vo.push_back((int)u.size()); vn.push_back((int)cameras_[m].pixel_coordinates_[i].size());
-                for (const Point2d &p : cameras_[m].pixel_coordinates_[i]) { u.push_back(p.x); v.push_back(p.y); }
+                q.vc.push_back(m); q.vb.push_back(i); q.vo.push_back((int)q.u.size()); q.vn.push_back((int)cameras_[m].pixel_coordinates_[i].size());
+                for (const Point2d &p : cameras_[m].pixel_coordinates_[i]) { q.u.push_back(p.x); q.v.push_back(p.y); }
             }
-        for (int m = 0; m < C; ++m) { std::memcpy(&crt[6 * (size_t)m], cameras_[m].rt_.data(), 6 * sizeof(double)); std::memcpy(&I[9 * (size_t)m], cameras_[m].intrinsic_.data(), 9 * sizeof(double)); }
-        for (int i = 0; i < B; ++i) if (chessboards_[i].is_initial()) std::memcpy(&brt[6 * (size_t)i], chessboards_[i].rt_.data(), 6 * sizeof(double));
-        if (C) cc[0] = 1;                                                // SetParameterBlockConstant(cameras_[0].rt_), :186
-        tscm_problem P = tscm_problem();
-        P.n_cameras = C; P.n_boards = B; P.n_points = n; P.n_views = (int)vc.size();
-        P.board_xy = bxy.data(); P.view_camera = vc.data(); P.view_board = vb.data(); P.view_offset = vo.data(); P.view_count = vn.data();
-        P.obs_u = u.data(); P.obs_v = v.data(); P.cam_rt = crt.data(); P.intr = I.data(); P.board_rt = brt.data();
-        P.cam_pose_constant = cc.data(); P.mono = 0;
+        for (int m = 0; m < C; ++m) { std::memcpy(&q.crt[6 * (size_t)m], cameras_[m].rt_.data(), 6 * sizeof(double)); std::memcpy(&q.I[9 * (size_t)m], cameras_[m].intrinsic_.data(), 9 * sizeof(double)); }
+        for (int i = 0; i < B; ++i) if (chessboards_[i].is_initial()) std::memcpy(&q.brt[6 * (size_t)i], chessboards_[i].rt_.data(), 6 * sizeof(double));
+        if (C) q.cc[0] = 1;                                              // SetParameterBlockConstant(cameras_[0].rt_), :186
+        tscm_problem &P = q.P;
+        P = tscm_problem();
+        P.n_cameras = C; P.n_boards = B; P.n_points = n; P.n_views = (int)q.vc.size();
+        P.board_xy = q.bxy.data(); P.view_camera = q.vc.data(); P.view_board = q.vb.data(); P.view_offset = q.vo.data(); P.view_count = q.vn.data();
+        P.obs_u = q.u.data(); P.obs_v = q.v.data(); P.cam_rt = q.crt.data(); P.intr = q.I.data(); P.board_rt = q.brt.data();
+        P.cam_pose_constant = q.cc.data(); P.mono = 0;
+        q.fixed.assign(C, 0);
+        q.any_fixed = false;
+        for (int m = 0; m < C && m < (int)fixed_.size(); ++m) { q.fixed[m] = fixed_[m]; q.any_fixed = q.any_fixed || fixed_[m] != 0; }
+    }
+
+    // multi_calib.cpp:155-283: joint LM, write-back (update_param), reprojection-error report
+    void calibrate(const tscm_options *options = nullptr)
+    {
+        const int C = (int)cameras_.size(), B = (int)chessboards_.size();
+        JointProblem q;
+        joint_problem(q);
+        tscm_problem &P = q.P;
+        std::vector<double> &crt = q.crt, &I = q.I, &brt = q.brt;
+        std::vector<unsigned short> &fixed = q.fixed;
+        const bool any_fixed = q.any_fixed;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 0);
-        std::vector<unsigned short> fixed(C, 0);
-        bool any_fixed = false;
-        for (int m = 0; m < C && m < (int)fixed_.size(); ++m) { fixed[m] = fixed_[m]; any_fixed = any_fixed || fixed_[m] != 0; }
         if (comm_) {
             // frame-sharded over the ranks of set_sharding(): every rank builds this same problem, keeps the boards it owns
             // and ends with ALL parameters updated (tscm.h, "multi-GPU").  (A one-rank communicator is legal: the library
@@ -629,6 +649,32 @@ public:
         camera_error.assign(C, 0.0);                                     // :233-283
         double rmse = 0.0;
         check(tscm_reprojection_error(&P, device_, camera_error.data(), &mean_error, &rmse));
+    }
+
+    // What ceres::Covariance would give for the joint problem at the objects' current parameters (tscm_covariance), with the
+    // loss and held intrinsics set on this object: call it after calibrate().  Ceres' convention: the blocks are (J^T J)^-1,
+    // not multiplied by sigma2; the standard deviations are.  status != 0: a singular block, every vector NaN (tscm.h).
+    struct Covariance {
+        tscm_covariance_info info;
+        double sigma2;
+        std::vector<double> cam_cov;           // [C*15][C*15], a camera's columns: rt (6), intrinsic (9)
+        std::vector<double> board_cov;         // [B][6][6]
+        std::vector<double> cam_rt_std, intr_std, board_rt_std;      // [C*6], [C*9], [B*6]; 0 where the column is not free
+    };
+    Covariance covariance() const
+    {
+        const size_t C = cameras_.size(), B = chessboards_.size();
+        JointProblem q;
+        joint_problem(q);
+        Covariance out;
+        out.cam_cov.assign(15 * C * 15 * C, 0.0); out.board_cov.assign(36 * B, 0.0);
+        out.cam_rt_std.assign(6 * C, 0.0); out.intr_std.assign(9 * C, 0.0); out.board_rt_std.assign(6 * B, 0.0);
+        out.info = tscm_covariance_info();
+        out.info.struct_size = (int)sizeof(tscm_covariance_info);
+        check(tscm_covariance(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, loss_kind_, loss_scale_, out.cam_cov.data(), out.board_cov.data(),
+                              out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
+        out.sigma2 = out.info.sigma2;
+        return out;
     }
 
     // main.cpp:305-319

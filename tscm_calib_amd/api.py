@@ -444,3 +444,52 @@ def shard_owner(problem: Problem, world: int) -> np.ndarray:
     cp = _l.c_problem(problem)
     _l.check(_l.lib().tscm_shard_frames(C.byref(cp), world, owner.ctypes.data_as(C.POINTER(C.c_int))))
     return owner
+
+
+def _covariance_dict(info, Cn: int, B: int, cam_cov, board_cov) -> dict:
+    dof = int(info.n_residuals) - int(info.n_free)
+    return dict(status=info.status, where=info.where, n_free=info.n_free, dof=dof, sigma2=info.sigma2, cost=info.cost,
+                min_pivot_ratio=info.min_pivot_ratio, cam_cov=cam_cov.reshape(Cn, 15, Cn, 15), board_cov=board_cov.reshape(B, 6, 6),
+                seconds_kernel=tuple(info.seconds_kernel))
+
+
+def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None) -> dict:
+    """What ceres::Covariance gives a Ceres user, at the problem's parameters (tscm_covariance): (J^T J)^-1 over the free
+    columns in Ceres' convention (not multiplied by sigma2), sigma2 = 2 cost / dof and the standard deviations
+    sqrt(sigma2 * diagonal).  loss, fixed: as for calibrate() -- pass what the solve had.
+    -> status (0 ok, 1 singular board block, 2 singular reduced system: every array is then NaN), where, n_free, dof, sigma2,
+    cost, min_pivot_ratio (near 0: gauge freedom or an unobservable parameter), cam_cov [C,15,C,15] and board_cov [B,6,6]
+    (zero where not free), cam_rt_std [C,6], intr_std [C,9], board_rt_std [B,6] (0 where not free), seconds_kernel (board
+    factor, Schur complement, reduced inverse, board marginals)."""
+    assert _is_normalised(problem), "use Problem.normalised()"
+    Cn, B = problem.n_cameras, problem.n_boards
+    cam_cov, board_cov = np.zeros((Cn * 15, Cn * 15)), np.zeros((B, 6, 6))
+    cam_std, intr_std, board_std = np.zeros((Cn, 6)), np.zeros((Cn, 9)), np.zeros((B, 6))
+    info = _l.CCovarianceInfo(struct_size=C.sizeof(_l.CCovarianceInfo))
+    cp = _l.c_problem(problem)
+    w = None if fixed is None else _l.fixed_masks(fixed, Cn)
+    k, a = _l.loss_args(loss)
+    _l.check(_l.lib().tscm_covariance(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), k, a, _l.dptr(cam_cov), _l.dptr(board_cov),
+                                      _l.dptr(cam_std), _l.dptr(intr_std), _l.dptr(board_std), C.byref(info)))
+    out = _covariance_dict(info, Cn, B, cam_cov, board_cov)
+    out.update(cam_rt_std=cam_std, intr_std=intr_std, board_rt_std=board_std)
+    return out
+
+
+def covariance_from_normal_equations(view_camera, view_board, board_gram, view_cross, cam_gram, cam_free, board_free, device: int = 0) -> dict:
+    """The covariance kernels on blocks the caller gives (tscm_covariance_from_normal_equations): board_gram [B,6,6],
+    view_cross [V,6,15], cam_gram [C,15,15] in the layout of normal_equations(), cam_free [C,15] and board_free [B] (true =
+    free).  -> the dict of covariance() without the standard deviations; cost, sigma2 and dof carry nothing."""
+    vc, vb = np.ascontiguousarray(view_camera, dtype=np.int32), np.ascontiguousarray(view_board, dtype=np.int32)
+    bg, vx, cg = (np.ascontiguousarray(x, dtype=np.float64) for x in (board_gram, view_cross, cam_gram))
+    cf, bf = np.ascontiguousarray(cam_free, dtype=np.uint8), np.ascontiguousarray(board_free, dtype=np.uint8)
+    Cn, B, V = cg.shape[0], bf.size, vc.size
+    if cg.shape != (Cn, 15, 15) or bg.shape != (B, 6, 6) or vx.shape != (V, 6, 15) or cf.size != Cn * 15 or vb.size != V:
+        raise ValueError("shapes: board_gram [B,6,6], view_cross [V,6,15], cam_gram [C,15,15], cam_free [C,15], board_free [B], view_* [V]")
+    cam_cov, board_cov = np.zeros((Cn * 15, Cn * 15)), np.zeros((B, 6, 6))
+    info = _l.CCovarianceInfo(struct_size=C.sizeof(_l.CCovarianceInfo))
+    ip, ubp = C.POINTER(C.c_int), C.POINTER(C.c_ubyte)
+    _l.check(_l.lib().tscm_covariance_from_normal_equations(Cn, B, V, vc.ctypes.data_as(ip), vb.ctypes.data_as(ip), _l.dptr(bg), _l.dptr(vx), _l.dptr(cg),
+                                                            cf.ctypes.data_as(ubp), bf.ctypes.data_as(ubp), device, _l.dptr(cam_cov), _l.dptr(board_cov),
+                                                            C.byref(info)))
+    return _covariance_dict(info, Cn, B, cam_cov, board_cov)

@@ -172,6 +172,12 @@ class CRansacParams(C.Structure):
                 ("seed", C.c_uint)]
 
 
+class CCovarianceInfo(C.Structure):
+    """tscm_covariance_info (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("status", C.c_int), ("where", C.c_int), ("n_free", C.c_int), ("n_residuals", C.c_longlong),
+                ("cost", C.c_double), ("sigma2", C.c_double), ("min_pivot_ratio", C.c_double), ("seconds_kernel", C.c_double * 4)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -195,6 +201,7 @@ EXPORTS = [
     "tscm_solver_set_loss", "tscm_solve_robust", "tscm_eval_normal_equations_robust", "tscm_eval_step_robust",
     "tscm_solver_eval_normal_equations",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
+    "tscm_covariance", "tscm_covariance_from_normal_equations",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
@@ -278,6 +285,10 @@ def lib():
     L.tscm_solve_mono_batch.argtypes = [C.POINTER(CProblem), C.c_int, C.c_int, C.POINTER(COptions), usp, C.c_int, C.c_double,
                                         C.POINTER(CSummary)]
     L.tscm_eval_step_fixed.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), usp, C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
+    cip = C.POINTER(CCovarianceInfo)
+    L.tscm_covariance.argtypes = [C.POINTER(CProblem), C.c_int, usp, C.c_int, C.c_double, dp, dp, dp, dp, dp, cip]
+    L.tscm_covariance_from_normal_equations.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_int,
+                                                        dp, dp, cip]
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]

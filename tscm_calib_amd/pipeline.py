@@ -201,7 +201,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -210,7 +210,9 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     batch_mono: the per-camera flow stage by stage across the cameras, each of its two refinement passes one batch call for
     all cameras (monocular_calib_batch); False (the default) runs monocular_calib camera after camera.
     ransac: None, or rig.ransac_params(...) for the start poses of every mono calibration (monocular_calib): the views it drops
-    are out of `has` when the rig is initialised, and mono[m]["ransac"] holds each camera's masks and codes."""
+    are out of `has` when the rig is initialised, and mono[m]["ransac"] holds each camera's masks and codes.
+    covariance: True adds result["covariance"] = api.covariance at the solved parameters, with the loss and masks of the joint
+    solve (standard deviations, sigma2, min_pivot_ratio: how well the views determine each parameter)."""
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
     if batch_mono:
@@ -225,4 +227,7 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     problem = rig.problem_from_rig(inp, g)
     _start_in_model(problem.intr, model)
     summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None)
-    return dict(problem=problem, mono=mono, rig_init=g, summary=summary)
+    out = dict(problem=problem, mono=mono, rig_init=g, summary=summary)
+    if covariance:
+        out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None)
+    return out
