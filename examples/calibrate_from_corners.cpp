@@ -6,6 +6,7 @@
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
 //                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
 //                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance]
+//                                   [--uncertainty STEP[,INV_DISTANCE]]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
@@ -13,9 +14,15 @@
 //    the calibration, and per camera the views kept and the share of inlier corners are printed.
 //    --covariance (rigs): after the joint solve, one line per camera parameter, `name value +- standard deviation`
 //    (MultiCalib::covariance; 0 for a held parameter), then sigma and min_pivot_ratio -- near 0 when the views do not
-//    determine some parameter)
+//    determine some parameter.
+//    --uncertainty (rigs; implies --covariance): projection uncertainty maps (MultiCalib::projection_uncertainty) on the grid
+//    x, y = 0, STEP, 2 STEP, ... of the corner file's image size at INV_DISTANCE (1 / distance in 1 / the pitch's unit; default
+//    0, infinity): per camera the largest and the median sd_worst of a fixed point seen in that camera, per pair of adjacent
+//    cameras the largest and the median sd_across of a pixel transferred from the first to the second -- the pixels by which
+//    rectified rows stop being rows)
 #include <tscm/tscm_calib.hpp>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,7 +33,8 @@ int main(int argc, char **argv)
     int loss = TSCM_LOSS_NONE;
     double loss_scale = 1.0;
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
-    bool bad_args = argc < 3, use_ransac = false, covariance = false;
+    bool bad_args = argc < 3, use_ransac = false, covariance = false, uncertainty = false;
+    double unc_step = 0.0, unc_inv_distance = 0.0;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
     for (int i = 3; i < argc && !bad_args; ++i) {
@@ -47,13 +55,24 @@ int main(int argc, char **argv)
             bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
         } else if (!std::strcmp(argv[i], "--covariance")) {
             covariance = true;
+        } else if (!std::strcmp(argv[i], "--uncertainty") && i + 1 < argc) {
+            char *end = nullptr;
+            unc_step = std::strtod(argv[++i], &end);
+            bad_args = end == argv[i] || !(unc_step > 0.0) || !std::isfinite(unc_step);
+            if (!bad_args && *end == ',') {
+                const char *second = end + 1;
+                unc_inv_distance = std::strtod(second, &end);
+                bad_args = end == second || !(unc_inv_distance >= 0.0) || !std::isfinite(unc_inv_distance);
+            }
+            bad_args = bad_args || *end != '\0';
+            uncertainty = covariance = true;
         } else {
             bad_args = true;
         }
     }
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -106,6 +125,21 @@ int main(int argc, char **argv)
                         std::printf("camera_%d %s %.17g +- %.17g\n", m, names[a], value, sd);
                     }
                 std::printf("sigma %.17g  min_pivot_ratio %.17g  free columns %d\n", std::sqrt(cov.sigma2), cov.info.min_pivot_ratio, cov.info.n_free);
+                if (uncertainty) {
+                    const std::vector<tscm_uncertainty_request> req = mul_calib.uncertainty_requests(std::vector<double>(1, unc_inv_distance));
+                    const tscm::MultiCalib::Uncertainty unc = mul_calib.projection_uncertainty(cov, tscm::MultiCalib::image_grid(image.width, image.height, unc_step), req);
+                    const size_t npix = (size_t)unc.nx * unc.ny;
+                    for (size_t r = 0; r < req.size(); ++r) {
+                        const bool observe = req[r].camera_a == req[r].camera_b;
+                        const double *sd = unc.plane((int)r, observe ? 5 : 6);
+                        std::vector<double> v;                               // the numbers among the plane's values, sorted
+                        for (size_t p = 0; p < npix; ++p) if (sd[p] == sd[p]) v.push_back(sd[p]);
+                        std::sort(v.begin(), v.end());
+                        const double nan = std::nan(""), vmax = v.empty() ? nan : v.back(), vmed = v.empty() ? nan : v[v.size() / 2];
+                        if (observe) std::printf("uncertainty camera_%d sd_worst max %.17g median %.17g valid %lld\n", req[r].camera_a, vmax, vmed, unc.n_valid[r]);
+                        else std::printf("uncertainty camera_%d->camera_%d sd_across max %.17g median %.17g valid %lld\n", req[r].camera_a, req[r].camera_b, vmax, vmed, unc.n_valid[r]);
+                    }
+                }
             }
         } else if (C == 1) {
             const double I3[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t0[3] = { 0, 0, 0 };

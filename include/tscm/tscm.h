@@ -455,6 +455,83 @@ int tscm_covariance_from_normal_equations(int n_cameras, int n_boards, int n_vie
                                           const unsigned char *cam_free, const unsigned char *board_free, int device_index,
                                           double *cam_cov, double *board_cov, tscm_covariance_info *info);
 
+/* ------------------------------------------------------------------ projection uncertainty maps
+ * The covariance of a projected pixel under the joint parameter covariance of tscm_covariance: what a standard deviation
+ * on xi or lambda means in pixels.  A stage of its own behind tscm_covariance; it runs no other kernel of the library.
+ *
+ * Model.  The functor's (multi_calib.h:146-195): b and c are inert in both directions, P_c = R_c P_rig + t_c, angle-axis
+ * rotations with both branches of ceres::AngleAxisRotatePoint.  I = (fx fy cx cy xi lambda alpha) below.
+ * Request (camera_a, camera_b, inv_distance i >= 0), for the grid pixel q = (x0 + col * dx, y0 + row * dy) of camera a:
+ *   r   = get_unit_sphere_coordinate(I_a, q) with b = c = 0                       (TS.h:39-57), a unit ray
+ *   s   = r - i t_a,   D = R_a^T s        the point at distance 1 / i from a's centre, scaled by i, in the rig frame
+ *   p_b = R_b D + i t_b
+ *   rho2 = X^2 + Y^2, d1 = sqrt(rho2 + Z^2), z1 = Z + xi d1, d2 = sqrt(rho2 + z1^2), z2 = z1 + lambda d2,
+ *   d3 = sqrt(rho2 + z2^2), beta = alpha / (1 - alpha), k = z2 + beta d3          at (X, Y, Z) = p_b with I_b
+ *   q_b = (fx X / k + cx, fy Y / k + cy)
+ * The projection does not change under a positive scale of p_b, so i = 0 is the point at infinity without a special case
+ * (the convention of tscm_build_sweep_maps).
+ * Derivatives of the projection at a point p = (X, Y, Z) with intrinsics I, as the functor's Jacobian has them:
+ *   c1 = 1 + xi Z / d1, c2 = 1 + lambda z1 / d2, c3 = 1 + beta z2 / d3, g = beta / d3 + c3 (lambda / d2 + c2 xi / d1),
+ *   kz = c1 c2 c3, mx = X / k, my = Y / k
+ *   A(p, I) = d(u, v) / dp = [ fx/k (1 - X mx g)   -fx/k mx Y g        -fx/k mx kz ]
+ *                            [ -fy/k my X g        fy/k (1 - Y my g)   -fy/k my kz ]        (its rows are orthogonal to p)
+ *   G(p, I) = d(u, v) / dI = [ mx 0 1 0 -hu c3 c2 d1  -hu c3 d2  -hu d3 / (1 - alpha)^2 ]   hu = fx/k mx
+ *                            [ 0 my 0 1 -hv c3 c2 d1  -hv c3 d2  -hv d3 / (1 - alpha)^2 ]   hv = fy/k my
+ * Transfer (a != b): theta = (w_a, t_a, I_a, w_b, t_b, I_b), 26 columns, J = d q_b / d theta with q and i held.  With
+ * A_b = A(p_b, I_b), AR = A_b R_b, M = AR R_a^T, A_a = A(r, I_a), G_a = G(r, I_a) and dR_k = dR / dw_k:
+ *   columns w_a,k :  AR (dR_a,k)^T s
+ *   columns t_a   :  -i M
+ *   columns I_a   :  -(M A_a^T) (A_a A_a^T)^-1 G_a     (pi(I_a, r) = q for every I_a gives dr = -A_a^T (A_a A_a^T)^-1 G_a dI_a)
+ *   columns w_b,k :  A_b dR_b,k D
+ *   columns t_b   :  i A_b
+ *   columns I_b   :  G(p_b, I_b)
+ * Observe (a == b == m): D is held, theta = (w_m, t_m, I_m), 13 columns: the three column groups of camera b above -- the
+ * functor's negated camera-side Jacobian with D in the place of the rig point, the translation columns times i because D is
+ * the point times i.  p_b is r up to rounding and q_b is q: how far the image of a fixed rig-frame point moves in camera m.
+ * Covariance.  Sigma_theta [n][n] (n = 26 or 13) is gathered from cam_cov as tscm_covariance lays it out: theta column c
+ * of camera m is row 15 m + c, c = 0..12 (b and c skipped); the lower triangle is read.  Rows that are not free are zero
+ * there.  With row i of Sigma taken in order i = 0..n-1 and s_x = sum_{j<i} Sigma_ij J_xj (j ascending):
+ *   c_uu += J_ui (Sigma_ii J_ui + 2 s_u),  c_vv += J_vi (Sigma_ii J_vi + 2 s_v),  c_uv += J_ui (Sigma_ii J_vi + s_v) + J_vi s_u
+ *   Cov(q_b) = sigma2 * (c_uu c_uv; c_uv c_vv)
+ * Outputs per request, planes [ny][nx] in this order: u_b, v_b, c_uu, c_uv, c_vv (sigma2 applied),
+ *   sd_worst  = sqrt((c_uu + c_vv + sqrt((c_uu - c_vv)^2 + 4 c_uv^2)) / 2)        the larger eigenvalue's root
+ *   sd_across = sqrt((e_v^2 c_uu - 2 e_u e_v c_uv + e_u^2 c_vv) / (e_u^2 + e_v^2)),  e = d q_b / d i = A_b t_b - M t_a, the
+ *               epipolar direction at q_b: the deviation across the epipolar line.  NaN in observe mode and where e = 0.
+ * flags, a byte per pixel: bit 0 the pixel unprojects (every square-root argument of the unprojection is > 0); bit 1 p_b
+ * projects (k > 0; only with bit 0); bit 2 q_b is inside camera b's image, 0 <= u_b <= width_b - 1 and 0 <= v_b <=
+ * height_b - 1 (only with bits 0 and 1, and only when width_b > 0 and height_b > 0).  Without bits 0 and 1 all seven doubles
+ * of the pixel are NaN.
+ * Summary per request: n_valid = pixels with bits 0 and 1; max_sd = the largest sd_worst among them (0 without any; a NaN
+ * sd_worst is passed over), taken by an integer maximum of the bit patterns of the non-negative doubles.
+ * Two calls on the same input give the same bytes (no floating-point atomics, every sum in a fixed order).  All requests
+ * of a call run in one launch.
+ *
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: cam_rt, intr, cam_cov, grid,
+ * requests, planes or flags NULL; grid->struct_size other than sizeof(tscm_uncertainty_grid); nx, ny or n_requests <= 0
+ * (or nx * ny above 2^30, n_requests above 65535); camera_a or camera_b outside [0, n_cameras); inv_distance negative or not
+ * finite; sigma2 negative or NaN; x0, y0, dx or dy not finite; n_cameras outside 1..32.  device_index as elsewhere, after
+ * the argument checks. */
+typedef struct tscm_uncertainty_grid {
+    int struct_size;               /* sizeof(tscm_uncertainty_grid), set by the caller                                 */
+    int nx, ny;                    /* grid columns and rows                                                            */
+    int width_b, height_b;         /* image size of the target cameras for flag bit 2; 0: the bit stays 0              */
+    double x0, y0, dx, dy;         /* pixel (col, row) of the grid is (x0 + col * dx, y0 + row * dy) in camera a       */
+} tscm_uncertainty_grid;
+
+typedef struct tscm_uncertainty_request {
+    int camera_a, camera_b;        /* equal: observe mode                                                              */
+    double inv_distance;           /* 1 / distance from camera a's centre, in 1 / the unit of the translations; 0: infinity */
+} tscm_uncertainty_request;
+
+/* cam_rt [C*6], intr [C*9] (b and c are not read), cam_cov [C*15][C*15] and sigma2 as tscm_covariance returned them;
+ * planes [n_requests][7][ny][nx], flags [n_requests][ny][nx]; max_sd and n_valid [n_requests] or NULL.  Host pointers. */
+int tscm_projection_uncertainty(int n_cameras, const double *cam_rt, const double *intr, const double *cam_cov, double sigma2,
+                                const tscm_uncertainty_grid *grid, const tscm_uncertainty_request *requests, int n_requests,
+                                int device_index, double *planes, unsigned char *flags, double *max_sd, long long *n_valid);
+/* device seconds of the kernel of this thread's last tscm_projection_uncertainty call (HIP events around its one launch;
+ * uploads and read-back are outside); 0 after a call that was refused or failed */
+double tscm_projection_uncertainty_seconds(void);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

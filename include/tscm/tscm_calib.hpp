@@ -677,6 +677,59 @@ public:
         return out;
     }
 
+    // Projection uncertainty maps (tscm_projection_uncertainty) at the objects' current parameters under the covariance that
+    // covariance() returned: per request (camera_a, camera_b, inv_distance) the covariance of a grid pixel of camera a
+    // transferred to camera b (a == b: of a fixed rig-frame point in its own camera), in pixels.
+    struct Uncertainty {
+        int nx, ny, n_requests;
+        std::vector<double> planes;            // [n_requests][7][ny][nx]: u_b v_b c_uu c_uv c_vv sd_worst sd_across
+        std::vector<unsigned char> flags;      // [n_requests][ny][nx]: bit 0 unprojects, 1 projects, 2 inside camera b's image
+        std::vector<double> max_sd;            // [n_requests]: the largest sd_worst of the valid pixels
+        std::vector<long long> n_valid;        // [n_requests]
+        const double *plane(int request, int k) const { return planes.data() + ((size_t)request * 7 + k) * (size_t)nx * ny; }
+    };
+    Uncertainty projection_uncertainty(const Covariance &cov, tscm_uncertainty_grid grid, const std::vector<tscm_uncertainty_request> &requests) const
+    {
+        const size_t C = cameras_.size(), R = requests.size();
+        std::vector<double> crt(6 * C), I(9 * C);
+        for (size_t m = 0; m < C; ++m) { std::memcpy(&crt[6 * m], cameras_[m].rt_.data(), 6 * sizeof(double)); std::memcpy(&I[9 * m], cameras_[m].intrinsic_.data(), 9 * sizeof(double)); }
+        grid.struct_size = (int)sizeof(tscm_uncertainty_grid);
+        Uncertainty out;
+        out.nx = grid.nx; out.ny = grid.ny; out.n_requests = (int)R;
+        const size_t npix = (size_t)(grid.nx > 0 ? grid.nx : 0) * (size_t)(grid.ny > 0 ? grid.ny : 0);
+        out.planes.assign(R * 7 * npix + 1, 0.0); out.flags.assign(R * npix + 1, 0);
+        out.max_sd.assign(R + 1, 0.0); out.n_valid.assign(R + 1, 0);
+        check(tscm_projection_uncertainty((int)C, crt.data(), I.data(), cov.cam_cov.data(), cov.sigma2, &grid, requests.data(), (int)R, device_, out.planes.data(),
+                                          out.flags.data(), out.max_sd.data(), out.n_valid.data()));
+        out.planes.resize(R * 7 * npix); out.flags.resize(R * npix); out.max_sd.resize(R); out.n_valid.resize(R);
+        return out;
+    }
+    // the grid of the CLI and of pipeline.calibrate_rig: x, y = 0, step, 2 step, ... inside a width x height image
+    static tscm_uncertainty_grid image_grid(int width, int height, double step)
+    {
+        tscm_uncertainty_grid g = tscm_uncertainty_grid();
+        g.struct_size = (int)sizeof(tscm_uncertainty_grid);
+        g.nx = (int)std::floor((width - 1) / step) + 1; g.ny = (int)std::floor((height - 1) / step) + 1;
+        g.width_b = width; g.height_b = height;
+        g.x0 = 0.0; g.y0 = 0.0; g.dx = step; g.dy = step;
+        return g;
+    }
+    // the requests of the CLI and of pipeline.calibrate_rig: an observe request per camera (at the first inverse distance), then
+    // per inverse distance a transfer request per ordered pair of adjacent cameras (m, m + 1; with three and more also last, first)
+    std::vector<tscm_uncertainty_request> uncertainty_requests(const std::vector<double> &inv_distances) const
+    {
+        const int C = (int)cameras_.size();
+        std::vector<tscm_uncertainty_request> req;
+        for (int m = 0; m < C; ++m) req.push_back(tscm_uncertainty_request{ m, m, inv_distances.empty() ? 0.0 : inv_distances[0] });
+        for (double i : inv_distances)
+            for (int m = 0; m < (C > 2 ? C : C - 1); ++m) {
+                const int b = (m + 1) % C;
+                req.push_back(tscm_uncertainty_request{ m, b, i });
+                req.push_back(tscm_uncertainty_request{ b, m, i });
+            }
+        return req;
+    }
+
     // main.cpp:305-319
     void write_yaml(const std::string &path) const
     {

@@ -493,3 +493,38 @@ def covariance_from_normal_equations(view_camera, view_board, board_gram, view_c
                                                             cf.ctypes.data_as(ubp), bf.ctypes.data_as(ubp), device, _l.dptr(cam_cov), _l.dptr(board_cov),
                                                             C.byref(info)))
     return _covariance_dict(info, Cn, B, cam_cov, board_cov)
+
+
+UNCERTAINTY_PLANES = ("u_b", "v_b", "c_uu", "c_uv", "c_vv", "sd_worst", "sd_across")
+
+
+def uncertainty_grid(nx: int, ny: int, x0: float = 0.0, y0: float = 0.0, dx: float = 1.0, dy: float = 1.0, width_b: int = 0, height_b: int = 0) -> dict:
+    """The pixel grid of projection_uncertainty: pixel (col, row) is (x0 + col dx, y0 + row dy) in camera a; width_b x height_b
+    is the target cameras' image for the `inside` flag (0: not asked)."""
+    return dict(nx=int(nx), ny=int(ny), x0=float(x0), y0=float(y0), dx=float(dx), dy=float(dy), width_b=int(width_b), height_b=int(height_b))
+
+
+def projection_uncertainty(cam_rt, intr, cov: dict, requests, grid: dict, device: int = 0) -> dict:
+    """Projection uncertainty maps (tscm_projection_uncertainty): the 2 x 2 covariance of a pixel of camera a transferred to
+    camera b at inverse distance i (a == b: of a fixed rig-frame point observed in its own camera) under the joint parameter
+    covariance.  cam_rt [C,6], intr [C,9]: the calibration; cov: the dict of covariance() (cam_cov and sigma2 are used);
+    requests: (camera_a, camera_b, inv_distance) triples; grid: uncertainty_grid(...).
+    -> planes [R,7,ny,nx] and its views u_b, v_b, c_uu, c_uv, c_vv, sd_worst, sd_across [R,ny,nx] (NaN where the pixel does
+    not unproject or its point does not project; sd_across also in observe mode), flags [R,ny,nx] uint8 (bit 0 unprojects,
+    1 projects, 2 inside camera b's image), max_sd and n_valid [R], seconds_kernel."""
+    rt, I = np.ascontiguousarray(cam_rt, dtype=np.float64), np.ascontiguousarray(intr, dtype=np.float64)
+    Cn = rt.shape[0]
+    cc = np.ascontiguousarray(cov["cam_cov"], dtype=np.float64)
+    if rt.shape != (Cn, 6) or I.shape != (Cn, 9) or cc.size != (15 * Cn) ** 2:
+        raise ValueError("shapes: cam_rt [C,6], intr [C,9], cov['cam_cov'] [C,15,C,15]")
+    req = (_l.CUncertaintyRequest * max(len(requests), 1))(*[_l.CUncertaintyRequest(int(a), int(b), float(i)) for a, b, i in requests])
+    g = _l.CUncertaintyGrid(struct_size=C.sizeof(_l.CUncertaintyGrid), **grid)
+    R, ny, nx = len(requests), max(g.ny, 0), max(g.nx, 0)
+    planes, flags = np.zeros((R, 7, ny, nx)), np.zeros((R, ny, nx), dtype=np.uint8)
+    max_sd, n_valid = np.zeros(R), np.zeros(R, dtype=np.int64)
+    _l.check(_l.lib().tscm_projection_uncertainty(Cn, _l.dptr(rt), _l.dptr(I), _l.dptr(cc), float(cov["sigma2"]), C.byref(g), req, R, device, _l.dptr(planes),
+                                                  flags.ctypes.data_as(C.POINTER(C.c_ubyte)), _l.dptr(max_sd), n_valid.ctypes.data_as(C.POINTER(C.c_longlong))))
+    out = dict(planes=planes, flags=flags, max_sd=max_sd, n_valid=n_valid, requests=[(int(a), int(b), float(i)) for a, b, i in requests], grid=dict(grid),
+               seconds_kernel=float(_l.lib().tscm_projection_uncertainty_seconds()))
+    out.update({name: planes[:, k] for k, name in enumerate(UNCERTAINTY_PLANES)})
+    return out

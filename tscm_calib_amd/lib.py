@@ -178,6 +178,17 @@ class CCovarianceInfo(C.Structure):
                 ("cost", C.c_double), ("sigma2", C.c_double), ("min_pivot_ratio", C.c_double), ("seconds_kernel", C.c_double * 4)]
 
 
+class CUncertaintyGrid(C.Structure):
+    """tscm_uncertainty_grid (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("width_b", C.c_int), ("height_b", C.c_int),
+                ("x0", C.c_double), ("y0", C.c_double), ("dx", C.c_double), ("dy", C.c_double)]
+
+
+class CUncertaintyRequest(C.Structure):
+    """tscm_uncertainty_request (tscm.h)"""
+    _fields_ = [("camera_a", C.c_int), ("camera_b", C.c_int), ("inv_distance", C.c_double)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -202,6 +213,7 @@ EXPORTS = [
     "tscm_solver_eval_normal_equations",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
     "tscm_covariance", "tscm_covariance_from_normal_equations",
+    "tscm_projection_uncertainty", "tscm_projection_uncertainty_seconds",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
@@ -289,6 +301,10 @@ def lib():
     L.tscm_covariance.argtypes = [C.POINTER(CProblem), C.c_int, usp, C.c_int, C.c_double, dp, dp, dp, dp, dp, cip]
     L.tscm_covariance_from_normal_equations.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_int,
                                                         dp, dp, cip]
+    L.tscm_projection_uncertainty.argtypes = [C.c_int, dp, dp, dp, C.c_double, C.POINTER(CUncertaintyGrid), C.POINTER(CUncertaintyRequest), C.c_int, C.c_int,
+                                              dp, C.POINTER(C.c_ubyte), dp, C.POINTER(C.c_longlong)]
+    L.tscm_projection_uncertainty_seconds.argtypes = []
+    L.tscm_projection_uncertainty_seconds.restype = C.c_double
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]

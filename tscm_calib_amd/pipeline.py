@@ -201,7 +201,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None, covariance=False) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -212,7 +212,12 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     ransac: None, or rig.ransac_params(...) for the start poses of every mono calibration (monocular_calib): the views it drops
     are out of `has` when the rig is initialised, and mono[m]["ransac"] holds each camera's masks and codes.
     covariance: True adds result["covariance"] = api.covariance at the solved parameters, with the loss and masks of the joint
-    solve (standard deviations, sigma2, min_pivot_ratio: how well the views determine each parameter)."""
+    solve (standard deviations, sigma2, min_pivot_ratio: how well the views determine each parameter).
+    uncertainty: None, or dict(step=pixels between grid points, inv_distances=(...)) -- implies covariance and adds
+    result["uncertainty"] = api.projection_uncertainty on the grid x, y = 0, step, 2 step, ... of the image, with one observe
+    request per camera (at the first inverse distance) and one transfer request per ordered pair of adjacent cameras (m, m + 1
+    and back; for three and more cameras also the last and the first) per inverse distance: how many pixels a transferred pixel
+    -- and above all its component across the epipolar line -- is uncertain (uncertainty_requests lists them)."""
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
     if batch_mono:
@@ -228,6 +233,24 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     _start_in_model(problem.intr, model)
     summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None)
     out = dict(problem=problem, mono=mono, rig_init=g, summary=summary)
-    if covariance:
+    if covariance or uncertainty is not None:
         out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None)
+    if uncertainty is not None:
+        step = float(uncertainty["step"])
+        img_w, img_h = images_by_camera[0][0].shape[1], images_by_camera[0][0].shape[0]
+        grid = api.uncertainty_grid(int((img_w - 1) // step) + 1, int((img_h - 1) // step) + 1, 0.0, 0.0, step, step, img_w, img_h)
+        out["uncertainty"] = api.projection_uncertainty(problem.cam_rt, problem.intr, out["covariance"], uncertainty_requests(n_cam, uncertainty["inv_distances"]),
+                                                        grid, device)
     return out
+
+
+def uncertainty_requests(n_cameras: int, inv_distances) -> list:
+    """The requests of calibrate_rig(uncertainty=...): an observe request per camera, then per inverse distance a transfer
+    request per ordered adjacent pair."""
+    inv = [float(i) for i in inv_distances]
+    pairs = [(m, m + 1) for m in range(n_cameras - 1)] + ([(n_cameras - 1, 0)] if n_cameras > 2 else [])
+    req = [(m, m, inv[0]) for m in range(n_cameras)]
+    for i in inv:
+        for a, b in pairs:
+            req += [(a, b, i), (b, a, i)]
+    return req
