@@ -8,6 +8,7 @@ import pytest
 
 from tests import init_ransac_ref as Q
 from tests import init_ref as R
+from tests import init_stage_checks as S
 from tscm_calib_amd import rig
 
 pytestmark = pytest.mark.gpu
@@ -26,14 +27,7 @@ def _report():
         print(f"\n[init ransac] compared with the reference's iterate (no convergence in 10 steps): {name}")
 
 
-def _note(report, kind, value, name):
-    if kind not in report or value > report[kind][0]:
-        report[kind] = (float(value), name)
-
-
-def _ratio(diff, bound):
-    diff = np.abs(diff)
-    return float(np.max(np.where(diff == 0, 0.0, diff / np.where(bound > 0, bound, 1e-300))))
+_note, _ratio = S.note, S.ratio
 
 
 def _sentinel(V):
@@ -102,42 +96,11 @@ def test_ransac_stages_every_view(hip_device, name, _report):
             continue
         assert g["n_inliers"][k] == g["score"][k][g["winner"][k]], where
         f = r["refit"]
-        if f["decisive_code"]:
-            assert code == f["code"], (where, code, f["code"])
-        else:
-            ok = {f["code"]} | ({R.CONVERGED, R.ITERATION_CAP} if f["code"] in (R.CONVERGED, R.ITERATION_CAP) else set())
-            assert code in ok, (where, code, f["code"])
-        if f.get("H") is None:
-            continue
-        E = ((g["H_refit"][k].astype(R.LD) - f["H"]) @ R.inv3(f["Nt"])).astype(np.float64)
-        rh = np.max(np.abs(E)) / f["bHn"]
-        assert rh <= 1.0, (where, rh)
-        _note(_report, "H_refit (Hartley space) / bound", rh, name)
-        if f.get("rv0") is None:
-            continue
-        p0 = np.concatenate([g["rv0"][k], g["t0"][k]])
-        r0 = np.concatenate([f["rv0"], f["t0"]]).astype(np.float64)
-        rp0 = _ratio(p0 - r0, f["bpose0"])
-        if not f["rod_decisive"]:
-            alt = [R.column_pose(f["H"], (b, s))[:2] for b, s in (("identity", None), ("pi", True), ("pi", False), ("generic", None))]
-            rp0 = min([rp0] + [_ratio(p0 - np.concatenate(a).astype(np.float64), f["bpose0"]) for a in alt])
-        assert rp0 <= 1.0, (where, rp0)
-        _note(_report, "rv0, t0 / bound", rp0, name)
+        S.assert_exit_code(code, f, where)
+        v = {key: g[key][k] for key in ("T", "rv0", "t0", "rv", "t", "steps", "Rt")}
+        S.assert_fit_stages(dict(v, H=g["H_refit"][k]), code, f, where, name, _report, S.RANSAC_LABELS)
         if code not in ESTIMATED:
             continue
-        pf = np.concatenate([g["rv"][k], g["t"][k]])
-        if f["capped_ref"]:
-            hist = f["hist"]
-            ref = hist[min(int(g["steps"][k]), len(hist) - 1)]
-            _report.setdefault("_capped", set()).add(where)
-        else:
-            ref = (f["rv"], f["t"])
-        rf = _ratio(pf - np.concatenate(ref).astype(np.float64), f["bpose"])
-        assert rf <= 1.0, (where, rf)
-        _note(_report, "rv, t (final) / bound", rf, name)
-        want = R.rt_from_stages(g["T"][k], g["rv"][k], g["t"][k]).astype(np.float64)
-        scale = np.array([1.0, 1.0, max(1.0, float(np.max(np.abs(g["t"][k]))))])
-        assert np.max(np.abs(g["Rt"][k] - want) / scale) < 1e-13, where
         # rms_px from the kernel's own pose: a pixel coordinate below 4096 carries at most 256 u 4096 = 1.2e-10 px of
         # rounding through the projection, the RMS of such errors at most sqrt(2) of it; 1e-9 px leaves a factor 4
         rms = float(Q.rms_px(intr, g["T"][k], g["rv"][k], g["t"][k], W, pu[k], pv[k], g["inlier"][k]))

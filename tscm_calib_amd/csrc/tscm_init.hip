@@ -5,13 +5,14 @@
 // one-sided Jacobi SVD of that factor held in registers.  The accepted samples are averaged on the
 // host in the reference's (image, row) order.
 // Below it the pose of every image (estimate_extrinsic, TS.cpp:170-203): the least-squares planar PnP, one thread per
-// image, and the consensus search with a refit on the inliers, one wave per image (tscm_init_ransac.h).
+// image, and the consensus search with a refit on the inliers, one wave per image (tscm_init_ransac.h).  Both run the one
+// fit of tscm_planar_pose.h.
 #include "tscm/tscm.h"
 
 #include <hip/hip_runtime.h>
 
 #include "tscm_host.h"
-#include "tscm_math.h"
+#include "tscm_init_ransac.h"
 
 #include <cmath>
 #include <string>
@@ -101,76 +102,12 @@ __global__ __launch_bounds__(64) void k_focal_rows(const double *__restrict__ pu
     gamma[t] = fabs(c3 * d / nz);
 }
 
-// ---------------------------------------------------------------------------------------------------
-// estimate_extrinsic (TS.cpp:170-203), one thread per image.  cv::solvePnPRansac (external, randomised)
-// is replaced by the deterministic planar PnP its iterative method performs on an all-inlier set:
-// DLT homography (Hartley-normalised board points, h33 = 1, 8x8 normal equations), pose from the
-// columns, polar orthonormalisation, Gauss-Newton on the 6 pose parameters with the analytic Jacobian.
-// ---------------------------------------------------------------------------------------------------
-template <int NN>
-__device__ bool chol_solve_dev(double *A, double *b)
-{
-    for (int j = 0; j < NN; ++j) {
-        double d = A[j * NN + j];
-        for (int k = 0; k < j; ++k) d -= A[j * NN + k] * A[j * NN + k];
-        if (!(d > 0.0)) return false;
-        d = sqrt(d);
-        A[j * NN + j] = d;
-        for (int i = j + 1; i < NN; ++i) {
-            double s = A[i * NN + j];
-            for (int k = 0; k < j; ++k) s -= A[i * NN + k] * A[j * NN + k];
-            A[i * NN + j] = s / d;
-        }
-    }
-    for (int i = 0; i < NN; ++i) { double s = b[i]; for (int k = 0; k < i; ++k) s -= A[i * NN + k] * b[k]; b[i] = s / A[i * NN + i]; }
-    for (int i = NN - 1; i >= 0; --i) { double s = b[i]; for (int k = i + 1; k < NN; ++k) s -= A[k * NN + i] * b[k]; b[i] = s / A[i * NN + i]; }
-    return true;
-}
-
-// orthogonal polar factor by Newton iteration X <- (X + X^-T) / 2, then the angle-axis vector (cv::Rodrigues)
-__device__ void rotation_vector_dev(const double *Min, double *rv)
-{
-    double X[9];
-    for (int i = 0; i < 9; ++i) X[i] = Min[i];
-    for (int it = 0; it < 50; ++it) {
-        const double c00 = X[4] * X[8] - X[5] * X[7], c01 = X[5] * X[6] - X[3] * X[8], c02 = X[3] * X[7] - X[4] * X[6];
-        const double c10 = X[2] * X[7] - X[1] * X[8], c11 = X[0] * X[8] - X[2] * X[6], c12 = X[1] * X[6] - X[0] * X[7];
-        const double c20 = X[1] * X[5] - X[2] * X[4], c21 = X[2] * X[3] - X[0] * X[5], c22 = X[0] * X[4] - X[1] * X[3];
-        const double det = X[0] * c00 + X[1] * c01 + X[2] * c02;
-        const double cof[9] = { c00, c01, c02, c10, c11, c12, c20, c21, c22 };
-        double diff = 0.0;
-        for (int i = 0; i < 9; ++i) { const double y = 0.5 * (X[i] + cof[i] / det); diff = fmax(diff, fabs(y - X[i])); X[i] = y; }
-        if (diff < 1e-16) break;
-    }
-    double rx = X[7] - X[5], ry = X[2] - X[6], rz = X[3] - X[1];
-    const double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
-    double c = (X[0] + X[4] + X[8] - 1.0) * 0.5;
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-    double theta = acos(c);
-    if (s < 1e-5) {
-        if (c > 0) { rv[0] = rv[1] = rv[2] = 0.0; return; }
-        double t = (X[0] + 1.0) * 0.5;
-        rx = sqrt(fmax(t, 0.0));
-        t = (X[4] + 1.0) * 0.5;
-        ry = sqrt(fmax(t, 0.0)) * (X[1] < 0 ? -1.0 : 1.0);
-        t = (X[8] + 1.0) * 0.5;
-        rz = sqrt(fmax(t, 0.0)) * (X[2] < 0 ? -1.0 : 1.0);
-        if (fabs(rx) < fabs(ry) && fabs(rx) < fabs(rz) && ((X[5] > 0) != (ry * rz > 0))) rz = -rz;
-        theta /= sqrt(rx * rx + ry * ry + rz * rz);
-        rv[0] = rx * theta; rv[1] = ry * theta; rv[2] = rz * theta;
-    } else {
-        const double vth = theta / (2.0 * s);
-        rv[0] = rx * vth; rv[1] = ry * vth; rv[2] = rz * vth;
-    }
-}
-
-#include "tscm_init_ransac.h"
-
 // STAGES = false: Rt_out [n_views][9], ok_out[k] = 1 where a pose was written (tscm_estimate_extrinsic).
 // STAGES = true: Rt_out [n_views][kStageRec] = Rt | T | H | rv0 t0 | rv t | GN steps, ok_out[k] = the
 // TSCM_EXTRINSIC_* exit code (tscm_estimate_extrinsic_stages); stage fields not reached keep their values.
-constexpr int kStageRec = 40;
+constexpr int kStageRec = 40, kStageT = 9;
 
+// estimate_extrinsic (TS.cpp:170-203), one thread per image: tscm_planar_pose.h's fit over all corners, serial sums.
 template <bool STAGES>
 __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restrict__ intr, const double *__restrict__ pu, const double *__restrict__ pv,
                                                            const int *__restrict__ count, int n_views, const double *__restrict__ worlds, int n, int board_w,
@@ -178,132 +115,31 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic(const double *__restr
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_views) return;
-    ok_out[k] = 0;
-    double *stage = Rt_out + (size_t)kStageRec * k;                         // STAGES only
+    double *stage = STAGES ? Rt_out + (size_t)kStageRec * k : nullptr;
     if (count[k] == 0) {
-        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_NO_BOARD;
+        ok_out[k] = STAGES ? TSCM_EXTRINSIC_NO_BOARD : 0;
         return;
     }
     double I[9];
     for (int i = 0; i < 9; ++i) I[i] = intr[i];
     const double *u = pu + (size_t)k * n, *v = pv + (size_t)k * n;
-    // transform = R2 * R1 turning the camera towards the board (:175-187)
-    double p[3];
     const int ref = n / 2 - board_w / 2 - 1;
-    tscm::unproject_pixel(I, u[ref], v[ref], p);
-    const double alpha = atan2(p[0], p[2]), beta = asin(p[1]);
-    const double ca = cos(alpha), sa = sin(alpha), cb = cos(beta), sb = sin(beta);
-    const double T[9] = { ca, 0.0, -sa, -sb * sa, cb, -sb * ca, cb * sa, sb, cb * ca };       // R2 * R1
+    double T[9];
+    tscm::look_at_turn(I, u[ref], v[ref], T);
     if constexpr (STAGES)
-        for (int i = 0; i < 9; ++i) stage[9 + i] = T[i];
-    auto normalised = [&](int i, double &x, double &y) {
-        double q[3];
-        tscm::unproject_pixel(I, u[i], v[i], q);
-        const double X = T[0] * q[0] + T[1] * q[1] + T[2] * q[2], Y = T[3] * q[0] + T[4] * q[1] + T[5] * q[2], Z = T[6] * q[0] + T[7] * q[1] + T[8] * q[2];
-        x = X / Z; y = Y / Z;
+        for (int i = 0; i < 9; ++i) stage[kStageT + i] = T[i];
+    auto normalised = [&](int i, double &x, double &y) {                  // every corner takes part
+        double Z;
+        tscm::turned_corner(I, T, u[i], v[i], x, y, Z);
+        return true;
     };
-    // Hartley normalisation of the board points
-    double cx = 0, cy = 0, md = 0;
-    for (int i = 0; i < n; ++i) { cx += worlds[3 * i]; cy += worlds[3 * i + 1]; }
-    cx /= n; cy /= n;
-    for (int i = 0; i < n; ++i) { const double dx = worlds[3 * i] - cx, dy = worlds[3 * i + 1] - cy; md += sqrt(dx * dx + dy * dy); }
-    md /= n;
-    if (!(md > 0.0)) {
-        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_DEGENERATE_BOARD;
-        return;
-    }
-    const double s = sqrt(2.0) / md;
-    // DLT: 8x8 normal equations
-    double A[64], b[8];
-    for (int i = 0; i < 64; ++i) A[i] = 0.0;
-    for (int i = 0; i < 8; ++i) b[i] = 0.0;
-    for (int i = 0; i < n; ++i) {
-        double x, y;
-        normalised(i, x, y);
-        const double X = (worlds[3 * i] - cx) * s, Y = (worlds[3 * i + 1] - cy) * s;
-        const double r1[8] = { X, Y, 1, 0, 0, 0, -x * X, -x * Y }, r2[8] = { 0, 0, 0, X, Y, 1, -y * X, -y * Y };
-        for (int a = 0; a < 8; ++a) {
-            for (int c = 0; c < 8; ++c) A[8 * a + c] += r1[a] * r1[c] + r2[a] * r2[c];
-            b[a] += r1[a] * x + r2[a] * y;
-        }
-    }
-    if (!chol_solve_dev<8>(A, b)) {
-        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_DLT_FAILED;
-        return;
-    }
-    const double Hn[9] = { b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], 1.0 };
-    double H[9];
-    for (int r = 0; r < 3; ++r) {
-        H[3 * r] = Hn[3 * r] * s; H[3 * r + 1] = Hn[3 * r + 1] * s;
-        H[3 * r + 2] = Hn[3 * r + 2] - s * (Hn[3 * r] * cx + Hn[3 * r + 1] * cy);
-    }
-    if constexpr (STAGES)
-        for (int i = 0; i < 9; ++i) stage[18 + i] = H[i];
-    const double n1 = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]), n2 = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
-    if (!(n1 > 0.0) || !(n2 > 0.0)) {
-        if constexpr (STAGES) ok_out[k] = TSCM_EXTRINSIC_ZERO_COLUMN;
-        return;
-    }
-    double lam = 2.0 / (n1 + n2);
-    if (H[8] < 0) lam = -lam;
-    double M[9], t[3], rv[3];
-    for (int r = 0; r < 3; ++r) { M[3 * r] = lam * H[3 * r]; M[3 * r + 1] = lam * H[3 * r + 1]; t[r] = lam * H[3 * r + 2]; }
-    M[2] = M[3] * M[7] - M[6] * M[4]; M[5] = M[6] * M[1] - M[0] * M[7]; M[8] = M[0] * M[4] - M[3] * M[1];
-    rotation_vector_dev(M, rv);
-    if constexpr (STAGES)
-        for (int i = 0; i < 3; ++i) { stage[27 + i] = rv[i]; stage[30 + i] = t[i]; }
-    // Gauss-Newton on (rv, t), analytic Jacobian
-    double R[9], dR[27];
-    int steps = 0;                                                          // STAGES only
-    unsigned char exit_code = TSCM_EXTRINSIC_ITERATION_CAP;
-    for (int it = 0; it < 10; ++it) {
+    double rv[3], t[3], R[9], dR[27];
+    const int code = tscm::fit_planar_pose(tscm::SerialLanes{}, normalised, n, worlds, n, stage, rv, t);
+    if (code >= TSCM_EXTRINSIC_CONVERGED) {
         tscm::rotation_and_derivatives(rv, R, dR);
-        double JtJ[36], Jtr[6];
-        for (int i = 0; i < 36; ++i) JtJ[i] = 0.0;
-        for (int i = 0; i < 6; ++i) Jtr[i] = 0.0;
-        for (int i = 0; i < n; ++i) {
-            double x, y;
-            normalised(i, x, y);
-            const double wx = worlds[3 * i], wy = worlds[3 * i + 1];
-            const double PX = R[0] * wx + R[1] * wy + t[0], PY = R[3] * wx + R[4] * wy + t[1], PZ = R[6] * wx + R[7] * wy + t[2];
-            const double iz = 1.0 / PZ, rx = PX * iz - x, ry = PY * iz - y;
-            double J[2][6];
-            for (int q = 0; q < 3; ++q) {                                   // d P / d w_q = dR_q (wx, wy, 0)
-                const double dX = dR[9 * q] * wx + dR[9 * q + 1] * wy, dY = dR[9 * q + 3] * wx + dR[9 * q + 4] * wy, dZ = dR[9 * q + 6] * wx + dR[9 * q + 7] * wy;
-                J[0][q] = (dX - PX * iz * dZ) * iz; J[1][q] = (dY - PY * iz * dZ) * iz;
-            }
-            J[0][3] = iz; J[0][4] = 0.0; J[0][5] = -PX * iz * iz;
-            J[1][3] = 0.0; J[1][4] = iz; J[1][5] = -PY * iz * iz;
-            for (int a = 0; a < 6; ++a) {
-                for (int c = 0; c < 6; ++c) JtJ[6 * a + c] += J[0][a] * J[0][c] + J[1][a] * J[1][c];
-                Jtr[a] += J[0][a] * rx + J[1][a] * ry;
-            }
-        }
-        for (int a = 0; a < 6; ++a) JtJ[7 * a] *= 1.0 + 1e-12;
-        if (!chol_solve_dev<6>(JtJ, Jtr)) {
-            if constexpr (STAGES) exit_code = TSCM_EXTRINSIC_GN_CHOLESKY;
-            break;
-        }
-        double step = 0.0;
-        for (int a = 0; a < 3; ++a) { rv[a] -= Jtr[a]; t[a] -= Jtr[3 + a]; step += Jtr[a] * Jtr[a] + Jtr[3 + a] * Jtr[3 + a] / fmax(1.0, t[a] * t[a]); }
-        if constexpr (STAGES) ++steps;
-        if (step < 1e-24) {
-            if constexpr (STAGES) exit_code = TSCM_EXTRINSIC_CONVERGED;
-            break;
-        }
+        tscm::compose_rt(T, R, t, STAGES ? stage : Rt_out + 9 * (size_t)k);
     }
-    if constexpr (STAGES) {
-        for (int i = 0; i < 3; ++i) { stage[33 + i] = rv[i]; stage[36 + i] = t[i]; }
-        stage[39] = steps;
-    }
-    tscm::rotation_and_derivatives(rv, R, dR);
-    double *o = STAGES ? stage : Rt_out + 9 * (size_t)k;                    // Rt = transform^T [r1 r2 t]  (:195-200)
-    for (int r = 0; r < 3; ++r) {
-        o[3 * r] = T[r] * R[0] + T[3 + r] * R[3] + T[6 + r] * R[6];
-        o[3 * r + 1] = T[r] * R[1] + T[3 + r] * R[4] + T[6 + r] * R[7];
-        o[3 * r + 2] = T[r] * t[0] + T[3 + r] * t[1] + T[6 + r] * t[2];
-    }
-    ok_out[k] = STAGES ? exit_code : 1;
+    ok_out[k] = STAGES ? code : code >= TSCM_EXTRINSIC_CONVERGED;
 }
 
 }  // namespace
@@ -361,6 +197,35 @@ extern "C" int tscm_estimate_focal_rows(const double *pix_u, const double *pix_v
     return 0;
 }
 
+// What both pose kernels read, on the device: the inputs, and in `rec` the caller's nrec doubles (Rt, or the stage
+// records of k_estimate_extrinsic<true>), uploaded so that views without a pose keep the caller's values.
+struct PoseInputs {
+    const double *intr = nullptr, *u = nullptr, *v = nullptr, *worlds = nullptr;
+    const int *count = nullptr;
+    double *rec = nullptr;
+
+    int upload(tscm::DeviceMem &mem, const double *intr9, const double *pix_u, const double *pix_v, const int *cnt, size_t n_views,
+               const double *w, int n_points, const double *caller_rec, size_t nrec)
+    {
+        HIP_TRY(mem.upload(&intr, intr9, 9));
+        HIP_TRY(mem.upload(&u, pix_u, n_views * n_points));
+        HIP_TRY(mem.upload(&v, pix_v, n_views * n_points));
+        HIP_TRY(mem.upload(&worlds, w, 3 * (size_t)n_points));
+        HIP_TRY(mem.upload(&rec, caller_rec, nrec));
+        HIP_TRY(mem.upload(&count, cnt, n_views));
+        return 0;
+    }
+};
+
+// H, pose0, pose and the Gauss-Newton steps of view k from the fit's part r of its stage record (either kernel's).  A stage
+// the view did not reach is NaN, its steps -1.
+static void unpack_fit_stages(const double *r, size_t k, double *H, double *pose0, double *pose, int *steps)
+{
+    for (int i = 0; i < 9; ++i) H[9 * k + i] = r[tscm::kStageH + i];
+    for (int i = 0; i < 6; ++i) { pose0[6 * k + i] = r[tscm::kStagePose0 + i]; pose[6 * k + i] = r[tscm::kStagePose + i]; }
+    steps[k] = std::isnan(r[tscm::kStageSteps]) ? -1 : (int)r[tscm::kStageSteps];
+}
+
 // One launch of k_estimate_extrinsic<STAGES> over every image.  rec: [n_views][STAGES ? kStageRec : 9] host records,
 // uploaded and read back whole (so the fields a view does not reach keep the caller's values); ok: [n_views].
 template <bool STAGES>
@@ -370,22 +235,15 @@ static int extrinsic_views(const double *intr9, const double *pix_u, const doubl
     if (board_w < 1 || n_points / 2 - board_w / 2 - 1 < 0) return tscm_set_error(TSCM_E_INVALID, "board width does not fit the corner count");
     if (int rc = tscm::select_device(device, "tscm_estimate_extrinsic")) return rc;
     if (n_views == 0) return 0;
-    const size_t npix = (size_t)n_views * n_points, nrec = (size_t)n_views * (STAGES ? kStageRec : 9);
+    const size_t nrec = (size_t)n_views * (STAGES ? kStageRec : 9);
     tscm::DeviceMem mem;
-    const double *d_i = nullptr, *d_u = nullptr, *d_v = nullptr, *d_w = nullptr;
-    const int *d_c = nullptr;
-    double *d_rt = nullptr;
+    PoseInputs d;
     unsigned char *d_ok = nullptr;
-    HIP_TRY(mem.upload(&d_i, intr9, 9));
-    HIP_TRY(mem.upload(&d_u, pix_u, npix));
-    HIP_TRY(mem.upload(&d_v, pix_v, npix));
-    HIP_TRY(mem.upload(&d_w, worlds, 3 * (size_t)n_points));
-    HIP_TRY(mem.upload(&d_rt, rec, nrec));      // views without a pose keep the caller's values
-    HIP_TRY(mem.upload(&d_c, count, (size_t)n_views));
+    if (int rc = d.upload(mem, intr9, pix_u, pix_v, count, (size_t)n_views, worlds, n_points, rec, nrec)) return rc;
     HIP_TRY(mem.alloc(&d_ok, (size_t)n_views));
-    hipLaunchKernelGGL(k_estimate_extrinsic<STAGES>, dim3((unsigned)((n_views + 63) / 64)), dim3(64), 0, 0, d_i, d_u, d_v, d_c, n_views, d_w, n_points, board_w, d_rt, d_ok);
+    hipLaunchKernelGGL(k_estimate_extrinsic<STAGES>, dim3((unsigned)((n_views + 63) / 64)), dim3(64), 0, 0, d.intr, d.u, d.v, d.count, n_views, d.worlds, n_points, board_w, d.rec, d_ok);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(rec, d_rt, nrec * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rec, d.rec, nrec * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ok, d_ok, (size_t)n_views, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -421,9 +279,8 @@ extern "C" int tscm_estimate_extrinsic_stages(const double *intr9, const double 
     int done = 0;
     for (int k = 0; k < n_views; ++k) {
         const double *r = rec.data() + (size_t)kStageRec * k;
-        for (int i = 0; i < 9; ++i) { Rt[9 * (size_t)k + i] = r[i]; T[9 * (size_t)k + i] = r[9 + i]; H[9 * (size_t)k + i] = r[18 + i]; }
-        for (int i = 0; i < 6; ++i) { pose0[6 * (size_t)k + i] = r[27 + i]; pose[6 * (size_t)k + i] = r[33 + i]; }
-        steps[k] = std::isnan(r[39]) ? -1 : (int)r[39];
+        for (int i = 0; i < 9; ++i) { Rt[9 * (size_t)k + i] = r[i]; T[9 * (size_t)k + i] = r[kStageT + i]; }
+        unpack_fit_stages(r, k, H, pose0, pose, steps);
         exit_code[k] = code[k];
         done += code[k] >= TSCM_EXTRINSIC_CONVERGED;
     }
@@ -494,17 +351,11 @@ int ransac_views(const double *intr9, const double *pix_u, const double *pix_v, 
     const int H = params->n_hypotheses;
     const size_t V = (size_t)n_views, npix = V * n_points;
     tscm::DeviceMem mem;
-    const double *d_i = nullptr, *d_u = nullptr, *d_v = nullptr, *d_w = nullptr;
-    const int *d_c = nullptr;
-    double *d_rt = nullptr, *d_stage = nullptr;
+    PoseInputs d;
+    double *d_stage = nullptr;
     unsigned char *d_in = nullptr;
     int *d_ninl = nullptr, *d_code = nullptr, *d_samples = nullptr, *d_score = nullptr, *d_winner = nullptr;
-    HIP_TRY(mem.upload(&d_i, intr9, 9));
-    HIP_TRY(mem.upload(&d_u, pix_u, npix));
-    HIP_TRY(mem.upload(&d_v, pix_v, npix));
-    HIP_TRY(mem.upload(&d_w, worlds, 3 * (size_t)n_points));
-    HIP_TRY(mem.upload(&d_rt, Rt, 9 * V));      // views without a pose keep the caller's values
-    HIP_TRY(mem.upload(&d_c, count, V));
+    if (int rc = d.upload(mem, intr9, pix_u, pix_v, count, V, worlds, n_points, Rt, 9 * V)) return rc;
     HIP_TRY(mem.alloc(&d_in, npix));
     HIP_TRY(hipMemset(d_in, 0, npix));
     HIP_TRY(mem.alloc(&d_ninl, V));
@@ -524,11 +375,11 @@ int ransac_views(const double *intr9, const double *pix_u, const double *pix_v, 
     tscm::EventSpan span;
     HIP_TRY(span.create(2));
     HIP_TRY(span.mark(0));
-    hipLaunchKernelGGL(k_estimate_extrinsic_ransac<STAGES>, dim3((unsigned)n_views), dim3(64), lds, 0, d_i, d_u, d_v, d_c, d_w, n_points, board_w, thr2, H,
-                       min_inliers, params->seed, d_rt, d_in, d_ninl, d_code, d_samples, d_score, d_winner, d_stage);
+    hipLaunchKernelGGL(k_estimate_extrinsic_ransac<STAGES>, dim3((unsigned)n_views), dim3(64), lds, 0, d.intr, d.u, d.v, d.count, d.worlds, n_points, board_w, thr2, H,
+                       min_inliers, params->seed, d.rec, d_in, d_ninl, d_code, d_samples, d_score, d_winner, d_stage);
     HIP_TRY(span.finish(1, nullptr, seconds_kernel));
     std::vector<int> code(V), ninl(V);
-    HIP_TRY(hipMemcpy(Rt, d_rt, 9 * V * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(Rt, d.rec, 9 * V * sizeof(double), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(inlier, d_in, npix, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(code.data(), d_code, V * sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ninl.data(), d_ninl, V * sizeof(int), hipMemcpyDeviceToHost));
@@ -539,10 +390,9 @@ int ransac_views(const double *intr9, const double *pix_u, const double *pix_v, 
         HIP_TRY(hipMemcpy(rec.data(), d_stage, rec.size() * sizeof(double), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < V; ++k) {
             const double *r = rec.data() + kRansacRec * k;
-            for (int i = 0; i < 9; ++i) { st.T[9 * k + i] = r[i]; st.H_best[9 * k + i] = r[9 + i]; st.H_refit[9 * k + i] = r[18 + i]; }
-            for (int i = 0; i < 6; ++i) { st.pose0[6 * k + i] = r[27 + i]; st.pose[6 * k + i] = r[33 + i]; }
-            st.steps[k] = std::isnan(r[39]) ? -1 : (int)r[39];
-            st.rms_px[k] = r[40];
+            for (int i = 0; i < 9; ++i) { st.T[9 * k + i] = r[kRansacT + i]; st.H_best[9 * k + i] = r[kRansacHBest + i]; }
+            unpack_fit_stages(r, k, st.H_refit, st.pose0, st.pose, st.steps);
+            st.rms_px[k] = r[kRansacRmsPx];
         }
     }
     int done = 0;

@@ -3,17 +3,20 @@
 //   setup   lanes over corners: un-project, turn, keep u, v, x, y (4 doubles) and the usable flag of every corner in LDS;
 //   search  lane = hypothesis, rounds of 64: integer sample, closed-form homography in registers, one walk over the
 //           LDS corners (every lane reads the same corner: a broadcast), running best (score, h), butterfly reduction;
-//   refit   lanes over the winner's inliers: every sum of the DLT and of each Gauss-Newton step is a per-lane partial in
-//           corner order i = lane, lane + 64, ... followed by the same xor butterfly, so a run gives the same bits every
-//           time.  The 8x8 and 6x6 systems are factored by every lane on identical values: the time of one lane, and no
-//           broadcast of the solution.
-// Included by tscm_init.hip inside its anonymous namespace, behind chol_solve_dev and rotation_vector_dev.
+//   refit   lanes over the winner's inliers: tscm_planar_pose.h's fit with the wave's lane policy, every sum of the DLT and
+//           of each Gauss-Newton step a per-lane partial in corner order i = lane, lane + 64, ... followed by the same xor
+//           butterfly.  The 8x8 and 6x6 systems are factored by every lane on identical values: the time of one lane, and
+//           no broadcast of the solution.
 #pragma once
+
+#include "tscm_planar_pose.h"
+
+namespace {
 
 constexpr int kRansacMaxPoints = 1024;       // 32 x 32 corners (kMaxBoardW squared): 34 KiB of LDS at the cap
 constexpr int kRansacMaxHypotheses = 4096;
 // per-view stage record of the STAGES instantiation: T | H_best | H_refit | rv0 t0 | rv t | GN steps | rms_px
-constexpr int kRansacRec = 41;
+constexpr int kRansacRec = 41, kRansacT = 0, kRansacHBest = 9, kRansacRmsPx = 40;
 
 // MurmurHash3's 32-bit finaliser (fmix32)
 __device__ __forceinline__ unsigned ransac_mix(unsigned h)
@@ -104,14 +107,6 @@ __device__ __forceinline__ bool ransac_inlier(const double *H, const double *T, 
     return du * du + dv * dv <= thr2;
 }
 
-// sum over the wave in a fixed tree; every lane receives the same bits
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 __device__ __forceinline__ void ransac_sampled_homography(unsigned seed, int k, int h, int n, const double *__restrict__ worlds, const double *sx, const double *sy, double H[9])
 {
     int s[4];
@@ -146,22 +141,16 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic_ransac(const double *
     double I[9];
     for (int i = 0; i < 9; ++i) I[i] = intr[i];
     const double *u = pu + (size_t)k * n, *v = pv + (size_t)k * n;
-    // the look-at turn of k_estimate_extrinsic (:175-187)
-    double p[3];
     const int ref = n / 2 - board_w / 2 - 1;
-    tscm::unproject_pixel(I, u[ref], v[ref], p);
-    const double alpha = atan2(p[0], p[2]), beta = asin(p[1]);
-    const double ca = cos(alpha), sa = sin(alpha), cb = cos(beta), sb = sin(beta);
-    const double T[9] = { ca, 0.0, -sa, -sb * sa, cb, -sb * ca, cb * sa, sb, cb * ca };
+    double T[9];
+    tscm::look_at_turn(I, u[ref], v[ref], T);
     if (STAGES && lane == 0)
-        for (int i = 0; i < 9; ++i) stage[i] = T[i];
+        for (int i = 0; i < 9; ++i) stage[kRansacT + i] = T[i];
     // ---- setup: lanes over corners
     for (int i = lane; i < n; i += 64) {
-        double q[3];
         const double ui = u[i], vi = v[i];
-        tscm::unproject_pixel(I, ui, vi, q);
-        const double X = T[0] * q[0] + T[1] * q[1] + T[2] * q[2], Y = T[3] * q[0] + T[4] * q[1] + T[5] * q[2], Z = T[6] * q[0] + T[7] * q[1] + T[8] * q[2];
-        const double x = X / Z, y = Y / Z;
+        double x, y, Z;
+        tscm::turned_corner(I, T, ui, vi, x, y, Z);
         su[i] = ui; sv[i] = vi; sx[i] = x; sy[i] = y;
         sok[i] = isfinite(ui) && isfinite(vi) && isfinite(x) && isfinite(y) && Z > 0.0;
     }
@@ -205,7 +194,7 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic_ransac(const double *
             double f = 0.0;
             for (int i = 0; i < 9; ++i) f += Hb[i] * Hb[i];
             f = sqrt(f);
-            for (int i = 0; i < 9; ++i) stage[9 + i] = Hb[i] / f;     // unit Frobenius norm (the score does not depend on the scale)
+            for (int i = 0; i < 9; ++i) stage[kRansacHBest + i] = Hb[i] / f;     // unit Frobenius norm (the score does not depend on the scale)
         }
     }
     if (best_s < min_inliers) { leave(TSCM_EXTRINSIC_FEW_INLIERS, 0); return; }
@@ -219,132 +208,36 @@ __global__ __launch_bounds__(64) void k_estimate_extrinsic_ransac(const double *
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
     __syncthreads();
-    // ---- refit: the DLT of k_estimate_extrinsic on the masked corners
-    double cx = 0, cy = 0, md = 0;
-    for (int i = lane; i < n; i += 64)
-        if (smask[i]) { cx += worlds[3 * i]; cy += worlds[3 * i + 1]; }
-    cx = wave_sum(cx) / m; cy = wave_sum(cy) / m;
-    for (int i = lane; i < n; i += 64)
-        if (smask[i]) { const double dx = worlds[3 * i] - cx, dy = worlds[3 * i + 1] - cy; md += sqrt(dx * dx + dy * dy); }
-    md = wave_sum(md) / m;
-    if (!(md > 0.0)) { leave(TSCM_EXTRINSIC_DEGENERATE_BOARD, m); return; }
-    const double s = sqrt(2.0) / md;
-    // per-lane partial sums straight into the lower triangle of A (all that chol_solve_dev reads) and b
-    double A[64], b[8];
-#pragma unroll
-    for (int i = 0; i < 64; ++i) A[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) b[i] = 0.0;
-    for (int i = lane; i < n; i += 64) {
-        if (!smask[i]) continue;
-        const double x = sx[i], y = sy[i];
-        const double X = (worlds[3 * i] - cx) * s, Y = (worlds[3 * i + 1] - cy) * s;
-        const double r1[8] = { X, Y, 1, 0, 0, 0, -x * X, -x * Y }, r2[8] = { 0, 0, 0, X, Y, 1, -y * X, -y * Y };
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-#pragma unroll
-            for (int c = 0; c <= a; ++c) A[8 * a + c] += r1[a] * r1[c] + r2[a] * r2[c];
-            b[a] += r1[a] * x + r2[a] * y;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-#pragma unroll
-        for (int c = 0; c <= a; ++c) A[8 * a + c] = wave_sum(A[8 * a + c]);
-        b[a] = wave_sum(b[a]);
-    }
-    if (!chol_solve_dev<8>(A, b)) { leave(TSCM_EXTRINSIC_DLT_FAILED, m); return; }
-    const double Hn[9] = { b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], 1.0 };
-    double H[9];
-    for (int r = 0; r < 3; ++r) {
-        H[3 * r] = Hn[3 * r] * s; H[3 * r + 1] = Hn[3 * r + 1] * s;
-        H[3 * r + 2] = Hn[3 * r + 2] - s * (Hn[3 * r] * cx + Hn[3 * r + 1] * cy);
-    }
-    if (STAGES && lane == 0)
-        for (int i = 0; i < 9; ++i) stage[18 + i] = H[i];
-    const double n1 = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]), n2 = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
-    if (!(n1 > 0.0) || !(n2 > 0.0)) { leave(TSCM_EXTRINSIC_ZERO_COLUMN, m); return; }
-    double lam = 2.0 / (n1 + n2);
-    if (H[8] < 0) lam = -lam;
-    double M[9], t[3], rv[3];
-    for (int r = 0; r < 3; ++r) { M[3 * r] = lam * H[3 * r]; M[3 * r + 1] = lam * H[3 * r + 1]; t[r] = lam * H[3 * r + 2]; }
-    M[2] = M[3] * M[7] - M[6] * M[4]; M[5] = M[6] * M[1] - M[0] * M[7]; M[8] = M[0] * M[4] - M[3] * M[1];
-    rotation_vector_dev(M, rv);
-    if (STAGES && lane == 0)
-        for (int i = 0; i < 3; ++i) { stage[27 + i] = rv[i]; stage[30 + i] = t[i]; }
-    // Gauss-Newton on (rv, t): the per-corner rows of k_estimate_extrinsic, summed over the wave
-    double R[9], dR[27];
-    int steps = 0;
-    int exit_code = TSCM_EXTRINSIC_ITERATION_CAP;
-    for (int it = 0; it < 10; ++it) {
+    // ---- refit: the planar pose fit on the masked corners, every sum over the wave
+    auto inlier_corner = [&](int i, double &x, double &y) {
+        if (!smask[i]) return false;
+        x = sx[i]; y = sy[i];
+        return true;
+    };
+    double rv[3], t[3];
+    const int code = tscm::fit_planar_pose(tscm::WaveLanes{}, inlier_corner, m, worlds, n, lane == 0 ? stage : nullptr, rv, t);
+    if (code >= TSCM_EXTRINSIC_CONVERGED) {
+        double R[9], dR[27];
         tscm::rotation_and_derivatives(rv, R, dR);
-        double JtJ[36], Jtr[6];                                             // lower triangle, as for the DLT
-#pragma unroll
-        for (int i = 0; i < 36; ++i) JtJ[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) Jtr[i] = 0.0;
-        for (int i = lane; i < n; i += 64) {
-            if (!smask[i]) continue;
-            const double x = sx[i], y = sy[i];
-            const double wx = worlds[3 * i], wy = worlds[3 * i + 1];
-            const double PX = R[0] * wx + R[1] * wy + t[0], PY = R[3] * wx + R[4] * wy + t[1], PZ = R[6] * wx + R[7] * wy + t[2];
-            const double iz = 1.0 / PZ, rx = PX * iz - x, ry = PY * iz - y;
-            double J[2][6];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const double dX = dR[9 * q] * wx + dR[9 * q + 1] * wy, dY = dR[9 * q + 3] * wx + dR[9 * q + 4] * wy, dZ = dR[9 * q + 6] * wx + dR[9 * q + 7] * wy;
-                J[0][q] = (dX - PX * iz * dZ) * iz; J[1][q] = (dY - PY * iz * dZ) * iz;
+        if constexpr (STAGES) {
+            // pixel RMS of the masked corners at the refit pose, through the full model
+            double e2 = 0.0;
+            for (int i = lane; i < n; i += 64) {
+                if (!smask[i]) continue;
+                const double wx = worlds[3 * i], wy = worlds[3 * i + 1];
+                const double PX = R[0] * wx + R[1] * wy + t[0], PY = R[3] * wx + R[4] * wy + t[1], PZ = R[6] * wx + R[7] * wy + t[2];
+                const double rx = T[0] * PX + T[3] * PY + T[6] * PZ, ry = T[1] * PX + T[4] * PY + T[7] * PZ, rz = T[2] * PX + T[5] * PY + T[8] * PZ;
+                double qu, qv;
+                tscm::project_point(I, rx, ry, rz, qu, qv);
+                const double du = su[i] - qu, dv = sv[i] - qv;
+                e2 += du * du + dv * dv;
             }
-            J[0][3] = iz; J[0][4] = 0.0; J[0][5] = -PX * iz * iz;
-            J[1][3] = 0.0; J[1][4] = iz; J[1][5] = -PY * iz * iz;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-#pragma unroll
-                for (int c = 0; c <= a; ++c) JtJ[6 * a + c] += J[0][a] * J[0][c] + J[1][a] * J[1][c];
-                Jtr[a] += J[0][a] * rx + J[1][a] * ry;
-            }
+            e2 = tscm::WaveLanes::sum(e2);
+            if (lane == 0) stage[kRansacRmsPx] = sqrt(e2 / m);
         }
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int c = 0; c <= a; ++c) JtJ[6 * a + c] = wave_sum(JtJ[6 * a + c]);
-            Jtr[a] = wave_sum(Jtr[a]);
-        }
-        for (int a = 0; a < 6; ++a) JtJ[7 * a] *= 1.0 + 1e-12;
-        if (!chol_solve_dev<6>(JtJ, Jtr)) { exit_code = TSCM_EXTRINSIC_GN_CHOLESKY; break; }
-        double step = 0.0;
-        for (int a = 0; a < 3; ++a) { rv[a] -= Jtr[a]; t[a] -= Jtr[3 + a]; step += Jtr[a] * Jtr[a] + Jtr[3 + a] * Jtr[3 + a] / fmax(1.0, t[a] * t[a]); }
-        ++steps;
-        if (step < 1e-24) { exit_code = TSCM_EXTRINSIC_CONVERGED; break; }
+        if (lane == 0) tscm::compose_rt(T, R, t, Rt_out + 9 * (size_t)k);
     }
-    tscm::rotation_and_derivatives(rv, R, dR);
-    if constexpr (STAGES) {
-        // pixel RMS of the masked corners at the refit pose, through the full model
-        double e2 = 0.0;
-        for (int i = lane; i < n; i += 64) {
-            if (!smask[i]) continue;
-            const double wx = worlds[3 * i], wy = worlds[3 * i + 1];
-            const double PX = R[0] * wx + R[1] * wy + t[0], PY = R[3] * wx + R[4] * wy + t[1], PZ = R[6] * wx + R[7] * wy + t[2];
-            const double rx = T[0] * PX + T[3] * PY + T[6] * PZ, ry = T[1] * PX + T[4] * PY + T[7] * PZ, rz = T[2] * PX + T[5] * PY + T[8] * PZ;
-            double qu, qv;
-            tscm::project_point(I, rx, ry, rz, qu, qv);
-            const double du = su[i] - qu, dv = sv[i] - qv;
-            e2 += du * du + dv * dv;
-        }
-        e2 = wave_sum(e2);
-        if (lane == 0) {
-            for (int i = 0; i < 3; ++i) { stage[33 + i] = rv[i]; stage[36 + i] = t[i]; }
-            stage[39] = steps;
-            stage[40] = sqrt(e2 / m);
-        }
-    }
-    if (lane == 0) {
-        double *o = Rt_out + 9 * (size_t)k;                                  // Rt = transform^T [r1 r2 t]  (:195-200)
-        for (int r = 0; r < 3; ++r) {
-            o[3 * r] = T[r] * R[0] + T[3 + r] * R[3] + T[6 + r] * R[6];
-            o[3 * r + 1] = T[r] * R[1] + T[3 + r] * R[4] + T[6 + r] * R[7];
-            o[3 * r + 2] = T[r] * t[0] + T[3 + r] * t[1] + T[6 + r] * t[2];
-        }
-    }
-    leave(exit_code, m);
+    leave(code, m);
 }
+
+}  // namespace

@@ -16,13 +16,17 @@
 //   dk/dX = X q, dk/dY = Y q, q = beta/d3 + c3 (lambda/d2 + c2 xi/d1);  dk/dZ = c1 c2 c3
 //   dk/dxi = c3 c2 d1, dk/dlambda = c3 d2, dk/dalpha = d3/(1-alpha)^2
 //   u = fx X/k + cx, v = fy Y/k + cy, residual = observed - (u, v).
-#pragma once
+#ifndef TSCM_MATH_H
+#define TSCM_MATH_H
 
+#ifdef __HIPCC__
 #include <hip/hip_runtime.h>
+#define TSCM_HD __host__ __device__ __forceinline__
+#else
+#define TSCM_HD inline                  // plain C++17: the host checks under tests/native
+#endif
 #include <float.h>
 #include <math.h>
-
-#define TSCM_HD __host__ __device__ __forceinline__
 
 namespace tscm {
 
@@ -264,3 +268,5 @@ TSCM_HD void unproject_pixel(const double I[9], double px, double py, double ray
 }
 
 }  // namespace tscm
+
+#endif
