@@ -234,6 +234,11 @@ int tscm_solver_debug_withhold_handoff(tscm_solver *s, int on);
 /* TESTS ONLY: which wave of a Schur-complement workgroup contracts which boards of its chunk does not change a bit of a
  * solve.  rot = 0 (the default) or 2: every workgroup of every later solve of `s` starts its deal at wave 0 / wave 2. */
 int tscm_solver_debug_schur_rot(tscm_solver *s, int rot);
+/* TESTS AND A/B RUNS ONLY: rigs of up to four cameras take their camera step out of the reduced system's factorisation
+ * where the column plan allows it; on = 1 makes every later solve of `s` back-substitute behind the factorisation
+ * instead (what a plan that does not fit does anyway), 0 is the default.  s NULL: the default of the solvers this
+ * process creates from now on, those of the one-shot entry points among them.  Same mathematics, last bits differ. */
+int tscm_solver_debug_reduced_backsub(tscm_solver *s, int on);
 int tscm_solver_reruns(const tscm_solver *s);                /* solves of `s` that were run again so far (>= 0) */
 int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_summary *summary);
 /* Same as _solve but parameters start from / are left in device memory (used by the

@@ -78,6 +78,11 @@ class Solver:
         (tscm_solver_debug_schur_rot; 0 is the default).  The bits must not depend on it."""
         _l.check(_l.lib().tscm_solver_debug_schur_rot(self._h, int(rot)))
 
+    def debug_reduced_backsub(self, on=True):
+        """Tests and A/B runs only: the later solves of a rig of up to four cameras back-substitute behind the reduced system's
+        factorisation instead of taking the step out of it (tscm_solver_debug_reduced_backsub; off is the default)."""
+        _l.check(_l.lib().tscm_solver_debug_reduced_backsub(self._h, int(bool(on))))
+
     def reruns(self) -> int:
         """Solves of this solver that were run again on separate launches after a late device-side hand-off."""
         n = _l.lib().tscm_solver_reruns(self._h)
@@ -248,6 +253,12 @@ class Group:
 
     def __exit__(self, *a):
         self.close()
+
+
+def debug_reduced_backsub_default(on=True):
+    """Tests and A/B runs only: Solver.debug_reduced_backsub for every solver created from now on, those of the one-shot
+    entry points (calibrate, step, ...) among them.  Set it back to off afterwards."""
+    _l.check(_l.lib().tscm_solver_debug_reduced_backsub(None, int(bool(on))))
 
 
 def _is_normalised(p: Problem) -> bool:

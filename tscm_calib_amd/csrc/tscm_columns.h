@@ -48,6 +48,22 @@ constexpr int kMapH = 0, kMapT = 16, kMapSci = 32, kMapScj = 36, kMapTile = 40, 
 constexpr int kMapOne = 1 << 30;       // "scaling 1": the row of a right-hand side tile
 constexpr int kSolveMapThreads = 256;  // k_solve_reduced<4, 16>: G = 16, one map entry per thread and slot quadruple
 
+// The solution rides through the factorisation (plan_solve_ext): NP more tile rows e_0 .. e_NP-1 = NP + 1 + i start as the
+// identity, tile (e_i, j) for i <= j < NP, and row e_i has one more tile in the right-hand side's column NP, which starts at
+// 0 and ends as -y_i.  Those tiles go to threads without an entry in solve_map; per thread { kind, ri, cj, i }.
+constexpr int kExtNone = 0, kExtRow = 3, kExtSol = 4;   // (1 and 2 are solve_map's matrix and right-hand side tiles)
+constexpr int kSolveExtPanels = 12;     // NP of that path at most: the kernel has LDS for 12 e-rows of a panel column
+// whether the tile of a thread takes part in the trailing update of panel tk: the plan, the CPU checks and k_solve_reduced
+// itself all ask this one function.  kind: solve_map's (1 matrix, 2 right-hand side) or solve_ext's, 0 no tile.  from: the
+// first panel of an e-row's tiles (0 for the others).  An e-row tile of column tk would only become a block of L^-T that
+// nobody reads: it was published raw at the end of panel tk - 1 and rests from then on
+TSCM_LAYOUT_FN bool solve_tile_live(int kind, int ri, int cj, int from, int tk)
+{
+    if (kind == kExtNone || !(ri > tk && cj >= tk && tk >= from)) return false;
+    if (ri == cj && ri == tk + 1) return false;                 // the look-ahead thread has that one
+    return !(kind == kExtRow && cj == tk);
+}
+
 struct ColumnPlan {
     std::vector<unsigned char> col_active;      // [n_pad] 1 = free camera-side column
     std::vector<unsigned char> col_ctl;         // [16 * kMaxCam] the control step's classes: bit 0 counts in |x|, bit 1 free; 0 past n_pad
@@ -56,6 +72,9 @@ struct ColumnPlan {
     int cam_pre[9] = {};                        // the compact numbering as kernel arguments (rigs of <= kMaxCamLds cameras):
     unsigned short cam_free[8] = {};            // camera q's free columns are compact [cam_pre[q], cam_pre[q + 1]) = 16 q + the set bits of cam_free[q]
     std::vector<Int4> solve_map;                // [kSolveMapSlots / 4][kSolveMapThreads] k_solve_reduced's operand map; C <= kDense4Cams only
+    std::vector<Int4> solve_ext;                // [kSolveMapThreads] { kind, ri, cj, i } of the e-row and solution tiles (plan_solve_ext); all kExtNone on the fallback
+    bool ext_fallback = false;                  // the tiles do not fit below the look-ahead thread's wave: k_solve_reduced back-substitutes
+    int wave_sum_old = 0, wave_sum_new = 0;     // sum over the panels of the waves with a tile in the trailing update: solve_map alone / with solve_ext
     bool has_nd = false;                        // C <= kMaxCamLds and n_act > 0: nd holds k_solve_nd's plans
     NdPlan nd[2];                               // [0] along the camera-pair graph, [1] the whole system as one dense block
 };
@@ -110,6 +129,55 @@ inline std::vector<Int4> plan_solve_map(const Layout &L, const ColumnPlan &c)
     return map;
 }
 
+// Owners of the e-row and solution tiles of k_solve_reduced<4, 16> (needs c.solve_map).  Rules: an owner has no entry in
+// solve_map and does not sit in the wave of the look-ahead thread NT - 1 (a lane there would put the trailing update in
+// series with the diagonal factorisation, the panel's critical path).  The scheme is planned only if ALL its tiles --
+// matrix, right-hand side, e-rows, solution -- fit into the waves below that one (NT - 64 threads: NP <= 12); otherwise
+// ext_fallback, an empty table, and the kernel back-substitutes as before.  Among the placements the sum over the panels
+// of the waves that take part in the trailing update is kept small greedily: tiles in the order of their last panel
+// (longest-lived first), each into the wave where it adds the fewest live panels, on a tie the wave that works longest
+// anyway.  wave_sum_old / wave_sum_new record that sum without and with the new tiles.
+inline void plan_solve_ext(ColumnPlan &c)
+{
+    constexpr int TS = 4, NT = kSolveMapThreads, NW = NT / 64;
+    const int NP = (c.n_act + TS - 1) / TS;
+    c.solve_ext.assign((size_t)NT, Int4{ kExtNone, 0, 0, 0 });
+    c.ext_fallback = false; c.wave_sum_old = c.wave_sum_new = 0;
+    std::vector<std::vector<char>> live(NW, std::vector<char>((size_t)std::max(NP, 1), 0));
+    std::vector<std::vector<int>> free_tid(NW);
+    for (int tid = 0; tid < NT; ++tid) {
+        const Int4 v = c.solve_map[(size_t)(kMapTile / 4) * NT + tid];        // { ri, cj, kind, -1 }
+        if (v.z == 0) { if (tid / 64 < NW - 1) free_tid[tid / 64].push_back(tid); continue; }
+        for (int tk = 0; tk < NP; ++tk) if (solve_tile_live(v.z, v.x, v.y, 0, tk)) live[tid / 64][tk] = 1;
+    }
+    auto wave_sum = [&] { int s = 0; for (const auto &w : live) for (char x : w) s += x; return s; };
+    c.wave_sum_old = c.wave_sum_new = wave_sum();
+    if (NP * (NP + 1) + 2 * NP > NT - 64 || NP > kSolveExtPanels) { c.ext_fallback = true; return; }
+    struct Tile { int kind, ri, cj, i, first, last; };      // takes part in the update of panels first .. last (none: last < first)
+    std::vector<Tile> tiles;
+    for (int i = 0; i < NP; ++i) {
+        for (int j = i; j < NP; ++j) tiles.push_back(Tile{ kExtRow, NP + 1 + i, j, i, i, j - 1 });
+        tiles.push_back(Tile{ kExtSol, NP + 1 + i, NP, i, i, NP - 1 });
+    }
+    std::stable_sort(tiles.begin(), tiles.end(), [](const Tile &a, const Tile &b) { return a.last != b.last ? a.last > b.last : a.first < b.first; });
+    size_t room = 0;
+    for (const auto &f : free_tid) room += f.size();
+    if (room < tiles.size()) { c.ext_fallback = true; return; }
+    std::vector<size_t> used(NW, 0);
+    for (const Tile &t : tiles) {
+        int best = -1, best_add = 0, best_base = 0;
+        for (int w = 0; w < NW - 1; ++w) {
+            if (used[w] == free_tid[w].size()) continue;
+            int add = 0, base = 0;
+            for (int tk = 0; tk < NP; ++tk) { add += tk >= t.first && tk <= t.last && !live[w][tk]; base += live[w][tk]; }
+            if (best < 0 || add < best_add || (add == best_add && base > best_base)) { best = w; best_add = add; best_base = base; }
+        }
+        c.solve_ext[(size_t)free_tid[best][used[best]++]] = Int4{ t.kind, t.ri, t.cj, t.i };
+        for (int tk = t.first; tk <= t.last; ++tk) live[best][tk] = 1;
+    }
+    c.wave_sum_new = wave_sum();
+}
+
 // The free camera-side columns of the reduced system and every table derived from them.  A padded column
 // 16 m + a is free if camera m has views, a < kFA, the pose is not held (a < 6) and intrinsic a - 6 is not held (bit a - 6 of
 // fixed[m]; fixed NULL: none is).  Held intrinsics leave the tangent space: no column, no Jacobi scale, no LM diagonal, no
@@ -142,7 +210,7 @@ inline int plan_columns(const Layout &L, int C, const unsigned short *fixed, Col
         int run = 0;
         for (int m = 0; m < C; ++m) { c.cam_pre[m] = run; c.cam_free[m] = word[m]; run += __builtin_popcount(word[m]); }
     }
-    if (C <= kDense4Cams) c.solve_map = plan_solve_map(L, c);
+    if (C <= kDense4Cams) { c.solve_map = plan_solve_map(L, c); plan_solve_ext(c); }
     if (C <= kMaxCamLds && c.n_act > 0) {
         // two plans: [0] along the camera-pair graph, [1] the whole system as one dense block.  A graph whose per-camera panel
         // padding does not fit the tile budget (dense but incomplete pair graphs of 8 free cameras) is solved on the dense plan;

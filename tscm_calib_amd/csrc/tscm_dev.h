@@ -142,6 +142,8 @@ struct DevProblem {
     unsigned short cam_free[8];
     unsigned long long pair_mask;      // bit mi * 8 + mj: the camera pair shares a board (its tile of T follows by a population count)
     const int4 *solve_map;             // [kSolveMapSlots / 4][256] operand offsets of every thread of k_solve_reduced (plan_solve_map)
+    const int4 *solve_ext;             // [256] { kind, ri, cj, i }: the e-row and solution tiles of k_solve_reduced (plan_solve_ext)
+    int solve_ext_on;                  // 1: those tiles take part and the solution falls out of the factor; 0: back-substitution (fallback plan, fp32-Jacobian tier, debug setter)
     int cam_wg[9];                     // cam_chunk_ptr by value for rigs of <= kMaxCamLds cameras (k_reduce_control: no index load in front of the tiles)
     // frame sharding (tscm_solver_create_sharded): this rank / number of ranks; 0 / 1 on a single GPU
     int rank, world;

@@ -672,9 +672,9 @@ __device__ __forceinline__ double load_T_lut(const DevProblem &P, const double *
 // the solution: tail_prefetch() issues their loads early (before the back-substitution where registers allow), so
 // the tail itself waits for no memory.
 struct TailOperands { double x, hg, hrow[kFA]; };
-__device__ __forceinline__ void tail_prefetch(const DevProblem &P, const DevState &S, int cur, const double *H, TailOperands &o)
+// (i: the padded column -- the calling thread's own unless another thread requests the operands for it)
+__device__ __forceinline__ void tail_prefetch(const DevProblem &P, const DevState &S, int cur, const double *H, TailOperands &o, int i)
 {
-    const int i = threadIdx.x;
     o.x = 0.0; o.hg = 0.0;
 #pragma unroll
     for (int b = 0; b < kFA; ++b) o.hrow[b] = 0.0;
@@ -688,6 +688,10 @@ __device__ __forceinline__ void tail_prefetch(const DevProblem &P, const DevStat
             o.hg = H[256 * m + ai * 16 + kFR];
         }
     }
+}
+__device__ __forceinline__ void tail_prefetch(const DevProblem &P, const DevState &S, int cur, const double *H, TailOperands &o)
+{
+    tail_prefetch(P, S, cur, H, o, (int)threadIdx.x);
 }
 // yv: solution by padded column (LDS); s_sc, s_yh, s_act: LDS arrays of n_pad entries.  Every thread of the workgroup calls it.
 // publish_epoch > 0: workgroups of this launch wait for the step (backsub_body<.., true>): yhat and the candidate camera

@@ -46,8 +46,11 @@ __device__ __forceinline__ int compact_to_padded(const DevProblem &P, int ci)
 // substitutes its slice of the rhs while the column threads publish their raw tiles; after ONE
 // barrier every trailing thread forms the needed X = A L_kk^{-T} tiles itself and applies the rank-TS
 // update -- 16 barriers in total.
-// Back-substitution: one wave, w in registers, rows of L streamed from LDS.  Writes
-// yhat = S_c y (camera step = -yhat) and the candidate camera parameters.
+// The solution: identity rows carried through the same panel steps leave it in registers when the last
+// panel is done (ext_on below; plan_solve_ext, tscm_columns.h).  Where the plan cannot place their tiles,
+// in the fp32-Jacobian tier and behind tscm_solver_debug_reduced_backsub: back-substitution by one wave,
+// w in registers, rows of L streamed from LDS.  Writes yhat = S_c y (camera step = -yhat) and the
+// candidate camera parameters.
 // grid 1 x 256, dynamic LDS N*(N+2) + 2*G*(TS*TS+2) + 2*N + 3*NPD doubles.
 // ---------------------------------------------------------------------------------------------
 // G x G threads, thread (ti, tj) owns the TS x TS tile (ti, tj) of the COMPACT system (N = G * TS >= n_act columns);
@@ -124,14 +127,35 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
         const int4 v = P.solve_map[q * NT + tid];
         off[4 * q] = v.x; off[4 * q + 1] = v.y; off[4 * q + 2] = v.z; off[4 * q + 3] = v.w;
     }
-    const int ri = off[kMapTile], cj = off[kMapTile + 1];                // tile (row, column) of this thread
+    // The solution rides along as well (ext_on; plan_solve_ext, tscm_columns.h): NP more tile rows e_i = NP + 1 + i start as
+    // the identity, so at panel k tile (e_i, k) becomes a block of L^-T, and the generic trailing update accumulates
+    // -sum_k (L^-T)_ik w_k = -y_i into the one tile (e_i, NP) of the right-hand side's column.  Their owners are threads
+    // without an entry in solve_map, none of them in the look-ahead thread's wave; row e_i takes part from panel i on (its
+    // tiles are exactly zero before).  When the last panel is done the solution is: no back-substitution, no L in LDS.
+    // Not in the fp32-Jacobian tier (the host clears solve_ext_on for its solves): y = (L^-1)^T w is not backward stable the way a substitution is (measured at
+    // kappa 5e10: backward error 2.8e-13 against 1.4e-16, the forward errors equal), and that tier's Gram matrices carry 1e-7 of
+    // noise into the model's flat valley, where the reduced system reaches kappa 1e12 and the two solutions part by 5e-5.
+    const bool ext_on = TS == 4 && G == 16 && P.solve_ext_on != 0;       // (off: the plan's fallback, tscm_solver_debug_reduced_backsub)
+    const int4 ext = ext_on ? P.solve_ext[tid] : int4{ 0, 0, 0, 0 };
+    const bool etile = ext.x == kExtRow, stile = ext.x == kExtSol;
+    const int ri = ext.x ? ext.y : off[kMapTile], cj = ext.x ? ext.z : off[kMapTile + 1];      // tile (row, column) of this thread
+    const int from = ext.x ? ext.w : 0;                                  // first panel of my tile
     const bool mine = off[kMapTile + 2] == 1, rhsrow = off[kMapTile + 2] == 2;
+    const bool pub = mine || rhsrow || etile;                            // my tile is part of a panel column
+    const int kind = ext.x ? ext.x : off[kMapTile + 2];                  // of my tile, for solve_tile_live (0: none)
+    // my tile row of a panel column: the e-rows' are in a part of Lm that nothing else uses (rows 0 .. 2 * kSolveExtPanels - 1
+    // hold diagonal tiles in columns < 2 * kSolveExtPanels and, on the back-substitution path only, L left of those)
+    constexpr int kExtCol = 40;
+    static_assert(2 * kSolveExtPanels <= kExtCol && kExtCol % 2 == 0 && LD % 2 == 0 && kExtCol + TS * TS <= LD && 2 * kSolveExtPanels <= N, "the e-rows' tiles fit beside the diagonal tiles");
+    const int xo = ext.x ? (ri - NP - 1) * LD + kExtCol : (int)(Xb - lds) + ri * XT, xs = ext.x ? kSolveExtPanels * LD : G * XT;    // offset in buffer 0, buffer stride
     const int cur = S.ctrl->cur;
     const double radius = S.ctrl->radius;
     const double dmin = S.ctrl->opt.min_lm_diagonal, dmax = S.ctrl->opt.max_lm_diagonal;
     const int ctrl_fail = S.ctrl->lin_fail | *S.fac_fail;       // (fac_fail is cleared in the tail, by the one workgroup that solves)
     for (int i = tid; i < NPD; i += NT) { s_sc[i] = i < n ? S.s_c[i] : 1.0; s_act[i] = i < n ? P.col_active[i] : 0; yv[i] = 0.0; }
     if (ctrl_done) return;
+    __shared__ signed char s_c2p[N];                                     // compact index -> padded column for the solution tiles' stores, by the idle last wave
+    if (ext_on && tid >= NT - 64 && tid - (NT - 64) < N) s_c2p[tid - (NT - 64)] = (signed char)compact_to_padded(P, tid - (NT - 64));
     const double *H = S.H[cur];
     double sci[TS], scj[TS], hh[TS][TS], tt[TS][TS];
 #pragma unroll
@@ -144,6 +168,15 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
     for (int r = 0; r < TS; ++r)
 #pragma unroll
         for (int c = 0; c < TS; ++c) { const int oh = off[kMapH + r * TS + c]; hh[r][c] = oh >= 0 ? H[oh] : 0.0; }
+    // The tail's operands hid their round trip under the back-substitution.  Where the solution falls out of the factor
+    // there is none: the idle last wave requests them here, for padded column tcol, and parks them in LDS behind the T
+    // loads (rows 48.. of Lm: nothing else is there when NP <= kSolveExtPanels and L is not published) -- no register is
+    // held through the factorisation and the tail reads LDS, not memory.
+    TailOperands tail_pre = {};
+    const int tcol = tid - (NT - 64);
+    double *tops = Lm + 4 * kSolveExtPanels * LD;       // [2 + kFA][64]
+    static_assert(NPD <= 64 && 4 * kSolveExtPanels * LD + (2 + kFA) * 64 <= N * LD, "the tail's operands fit behind the last diagonal tile");
+    if (ext_on && tcol >= 0) tail_prefetch(P, S, cur, H, tail_pre, tcol);
     if constexpr (FUSED) {
         // everything that does not depend on T is in flight; now the tiles of the other workgroups
         __shared__ int s_late;
@@ -185,8 +218,13 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
             const bool dg = mine && ri == cj && r == c;
             double v = sci[r] * scj[c] * (hh[r][c] - tt[r][c]);
             if (dg) v = (off[kMapSci + r] >= 0 && off[kMapSci + r] != kMapOne) ? v + fmin(fmax(sci[r] * sci[r] * hh[r][c], dmin), dmax) * inv_radius : 1.0;
-            a[r][c] = v;
+            a[r][c] = (etile && cj == from && r == c) ? 1.0 : v;      // (e-row and solution tiles have no operands: v is 0)
         }
+    }
+    if (ext_on && tcol >= 0) {
+        tops[tcol] = tail_pre.x; tops[64 + tcol] = tail_pre.hg;
+#pragma unroll
+        for (int b = 0; b < kFA; ++b) tops[(2 + b) * 64 + tcol] = tail_pre.hrow[b];
     }
     PHASE_STAMP(ts1);
 #ifdef TSCM_PHASE_PROFILE
@@ -264,13 +302,12 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
     };
     __shared__ __attribute__((aligned(16))) double s_dt[2][TS * TS];
     const bool dthread = tid == NT - 1;                     // no tile of its own: NP < G (host-checked)
-    if (cj == 0 && ri > 0 && (mine || rhsrow)) publish_tile(Xb + ri * XT, a);
+    if (cj == 0 && ri > 0 && pub) publish_tile(lds + xo, a);
     if (ri == 1 && cj == 1 && mine) publish_tile(s_dt[0], a);
     if (tid == 0 && NP > 0) factor_diag(a, 0);
     __syncthreads();
     for (int tk = 0; tk < NP; ++tk) {
         const double *Ar = Xb + (tk & 1) * (G * XT);
-        double *ArN = Xb + ((tk + 1) & 1) * (G * XT);
 #ifdef TSCM_PHASE_PROFILE
         __shared__ long long s_ph[8];
         if (tk == 3 && (dthread || tid == 11 * G + 5)) s_ph[dthread ? 0 : 4] = wall_clock64();
@@ -301,11 +338,11 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
             if (tk == 3) s_ph[2] = wall_clock64();
 #endif
         }
-        if ((mine || rhsrow) && ri > tk && cj >= tk && !(ri == cj && ri == tk + 1)) {
+        if (solve_tile_live(kind, ri, cj, from, tk)) {
             PanelFactor f;
             double ai[TS][TS], aj[TS][TS], xi[TS][TS];
             load_factor(f, tk);
-            load_tile(Ar + ri * XT, ai);
+            load_tile(lds + xo + (tk & 1) * xs, ai);
             load_tile(Ar + cj * XT, aj);
             __builtin_amdgcn_sched_barrier(0);
             panel_solve(ai, f, xi);
@@ -335,8 +372,8 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
         }
         {
             // column tk+1 for the next step and diagonal tile tk+2 for the look-ahead thread: ONE store sequence
-            const bool col = cj == tk + 1 && ri > tk + 1 && (mine || rhsrow), dg = ri == tk + 2 && cj == tk + 2 && mine;
-            if (col || dg) publish_tile(col ? ArN + ri * XT : s_dt[(tk + 1) & 1], a);
+            const bool col = cj == tk + 1 && ri > tk + 1 && pub, dg = ri == tk + 2 && cj == tk + 2 && mine;
+            if (col || dg) publish_tile(col ? lds + xo + ((tk + 1) & 1) * xs : s_dt[(tk + 1) & 1], a);
         }
 #ifdef TSCM_PHASE_PROFILE
         if (tk == 3 && tid == 11 * G + 5) { asm volatile("" : "+v"(a[3][3])); s_ph[5] = wall_clock64(); }
@@ -346,8 +383,13 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
         if (tk + 1 < NP) __syncthreads();
 #endif
     }
-    // ---- publish L (the diagonal tiles are there already), back-substitute L^T y = w with one wave -----------
-    if (cj < ri && mine) {
+    // ---- the solution: -column 0 of the solution tiles.  Back-substitution path: publish L (the diagonal tiles are there
+    // already), back-substitute L^T y = w with one wave -----------
+    if (stile) {
+#pragma unroll
+        for (int r = 0; r < TS; ++r) { const int pc = s_c2p[from * TS + r]; if (pc >= 0) yv[pc] = -a[r][0]; }
+    }
+    if (!ext_on && cj < ri && mine) {
 #pragma unroll
         for (int r = 0; r < TS; ++r)
 #pragma unroll
@@ -358,9 +400,14 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
 #ifdef TSCM_PHASE_PROFILE
     const long long cy2 = clock64();
 #endif
-    TailOperands tail_ops;
-    tail_prefetch(P, S, cur, H, tail_ops);        // in flight during the back-substitution (the tiles' registers are free now)
-    if (tid < 64) {
+    TailOperands tail_ops = {};
+    if (!ext_on) tail_prefetch(P, S, cur, H, tail_ops);        // in flight during the back-substitution (the tiles' registers are free now)
+    else if (tid < 64) {
+        tail_ops.x = tops[tid]; tail_ops.hg = tops[64 + tid];
+#pragma unroll
+        for (int b = 0; b < kFA; ++b) tail_ops.hrow[b] = tops[(2 + b) * 64 + tid];
+    }
+    if (!ext_on && tid < 64) {
         // blocked back-substitution, TS unknowns per step: all lanes solve the TS x TS upper-triangular
         // diagonal system redundantly (operands by broadcast), then lane i applies the TS columns to w[i]
         constexpr int R = (N + 63) / 64;
@@ -402,7 +449,7 @@ __global__ __launch_bounds__((G * G + 63) / 64 * 64, FUSED ? 3 : 1) void k_solve
 #pragma unroll
         for (int q = 0; q < R; ++q) { const int pi = tid + 64 * q < N ? compact_to_padded(P, tid + 64 * q) : -1; if (pi >= 0) yv[pi] = w[q]; }    // back to padded columns
     }
-    __syncthreads();
+    if (!ext_on) __syncthreads();
     PHASE_STAMP(ts3);
     reduced_solution_tail(P, S, cur, s_fail, tail_ops, yv, s_sc, s_yh, s_act, sred, FUSED && n_bs > 0 ? epoch : 0);
 #ifdef TSCM_PHASE_PROFILE

@@ -17,6 +17,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -170,6 +171,8 @@ struct tscm_solver {
     std::vector<unsigned short> fixed;
     int n_cu = 1;
     int schur_rot = 0;                  // k_schur_gram's rot: the wave its workgroups start their deal of board groups at, 0 (tests: 2, tscm_solver_debug_schur_rot)
+    bool ext_planned = false;           // the column plan has the e-row and solution tiles of k_solve_reduced (not its fallback)
+    bool force_backsub = false;         // ... but k_solve_reduced back-substitutes all the same (tests, A/B runs: tscm_solver_debug_reduced_backsub)
     double *d_view_sq = nullptr;        // [2 V] k_reproj_error's output for the RMSE of a robust solve (allocated by the first one)
     // dominant-kernel timing
     int timing = 0;                     // 0 = off, n = bracket every n-th launch of the dominant kernel (and every n-th exchange) with HIP events
@@ -271,6 +274,8 @@ extern "C" void tscm_solver_destroy(tscm_solver *s)
     delete s;                           // (s->mem frees the device buffers)
 }
 
+static std::atomic<bool> g_force_backsub{ false };      // tscm_solver_debug_reduced_backsub(NULL, on)
+
 // Uploads a column plan (tscm_columns.h: plan_columns): col_active, the control step's classes col_ctl, act_map /
 // n_act, cam_pre / cam_free (kernel arguments of k_solve_reduced), k_solve_reduced's operand map and both k_solve_nd plans,
 // with the LDS bounds and residency that follow from them.  Run by create and by tscm_solver_set_fixed_intrinsics.
@@ -286,7 +291,12 @@ static int apply_columns(tscm_solver *s, const ColumnPlan &c)
     std::copy(std::begin(c.cam_pre), std::end(c.cam_pre), P.cam_pre);
     std::copy(std::begin(c.cam_free), std::end(c.cam_free), P.cam_free);
     static_assert(sizeof(Int4) == sizeof(int4), "the operand map is uploaded as it is");
-    if (!c.solve_map.empty()) HIP_TRY(hipMemcpy(const_cast<int4 *>(P.solve_map), c.solve_map.data(), sizeof(Int4) * c.solve_map.size(), hipMemcpyHostToDevice));
+    if (!c.solve_map.empty()) {
+        HIP_TRY(hipMemcpy(const_cast<int4 *>(P.solve_map), c.solve_map.data(), sizeof(Int4) * c.solve_map.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(const_cast<int4 *>(P.solve_ext), c.solve_ext.data(), sizeof(Int4) * c.solve_ext.size(), hipMemcpyHostToDevice));
+        s->ext_planned = !c.ext_fallback;
+        P.solve_ext_on = s->ext_planned && !s->force_backsub;
+    }
     if (c.has_nd) {
         for (int v = 0; v < 2; ++v) {
             const NdPlan &pl = c.nd[v];
@@ -514,6 +524,10 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
         int4 *map = nullptr;
         HIP_TRY(s->mem.alloc(&map, (size_t)(kSolveMapSlots / 4) * kSolveMapThreads));
         P.solve_map = map;
+        int4 *ext = nullptr;
+        HIP_TRY(s->mem.alloc(&ext, (size_t)kSolveMapThreads));
+        P.solve_ext = ext;
+        s->force_backsub = g_force_backsub.load();
         const size_t NN = 64, TT = 4, NPD = 64;
         s->lds_dense4 = sizeof(double) * (NN * (NN + 2) + 2 * (NN / TT) * (TT * TT + 2) + 2 * NN + 3 * NPD);
         int per_cu = 0;
@@ -558,6 +572,18 @@ extern "C" int tscm_solver_debug_schur_rot(tscm_solver *s, int rot)
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
     if (rot != 0 && rot != 2) return fail(TSCM_E_INVALID, "rot must be 0 or 2");
     s->schur_rot = rot;
+    return 0;
+}
+
+// For tests and A/B runs of k_solve_reduced (rigs of up to four cameras): on = 1 keeps the back-substitution behind the
+// factorisation where the plan lets the solution fall out of the factor; 0 is the default.  s NULL: the default of the solvers
+// created from now on, in this process (the one-shot entry points create their own).
+extern "C" int tscm_solver_debug_reduced_backsub(tscm_solver *s, int on)
+{
+    if (on != 0 && on != 1) return fail(TSCM_E_INVALID, "on must be 0 or 1");
+    if (!s) { g_force_backsub.store(on != 0); return 0; }
+    s->force_backsub = on != 0;
+    s->P.solve_ext_on = s->ext_planned && !s->force_backsub;
     return 0;
 }
 
@@ -819,6 +845,13 @@ static int enqueue(tscm_solver *s, const Launch &l)
                            s->plan[v].dims(), l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32);
     };
     const size_t lds_dense4 = std::max(s->lds_dense4, l.n_bs ? s->lds_bs : (size_t)0);
+    // k_solve_reduced takes the step out of the factor only in the fp64 tier (the fp32-Jacobian tier's systems are the worst
+    // conditioned ones: tscm_solve_dense4.h); the tier is the solve's, whatever rides in this launch
+    auto dense4 = [&](auto kernel) {
+        DevProblem Pd = P;
+        if (s->xp.f32()) Pd.solve_ext_on = 0;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds_dense4, st, Pd, S, l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32);
+    };
     switch (l.k) {
     case Kern::BeginViewPrep: {
         const bool init = l.start == Start::Init, bak = l.start == Start::Backup;
@@ -842,8 +875,8 @@ static int enqueue(tscm_solver *s, const Launch &l)
     case Kern::SchurRide3: schur(k_schur_gram<3, true>); break;
     case Kern::PairGram: hipLaunchKernelGGL(k_pair_gram, grid, dim3(256), 0, st, P, S); break;
     case Kern::TReduce: hipLaunchKernelGGL(k_T_reduce, grid, dim3(kTEntries * kTSlices), 0, st, P, S); break;
-    case Kern::SolveDense4: hipLaunchKernelGGL((k_solve_reduced<4, 16, 64>), grid, dim3(256), lds_dense4, st, P, S, l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32); break;
-    case Kern::SolveDense4Ride: hipLaunchKernelGGL((k_solve_reduced<4, 16, 64, true>), grid, dim3(256), lds_dense4, st, P, S, l.epoch, l.withhold, l.n_prod, l.n_bs, l.f32); break;
+    case Kern::SolveDense4: dense4(k_solve_reduced<4, 16, 64>); break;
+    case Kern::SolveDense4Ride: dense4(k_solve_reduced<4, 16, 64, true>); break;
     case Kern::SolveNd1: nd(k_solve_nd<1, false>); break;
     case Kern::SolveNd2: nd(k_solve_nd<2, false>); break;
     case Kern::SolveNd1Ride: nd(k_solve_nd<1, true>); break;
