@@ -5,11 +5,13 @@
 //       -Wl,-rpath,$PWD/tscm_calib_amd/csrc -o examples/calibrate_from_corners        (one command line)
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
 //                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
-//                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance]
+//                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance]
 //                                   [--uncertainty STEP[,INV_DISTANCE]]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
+//    --ransac-mask (with --ransac): the inlier masks are the corner masks of every refinement, the joint solve and the covariance
+//                  included; prints the number of corners masked per camera
 //    --ransac: the start poses come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view without consensus leaves
 //    the calibration, and per camera the views kept and the share of inlier corners are printed.
 //    --covariance (rigs): after the joint solve, one line per camera parameter, `name value +- standard deviation`
@@ -33,7 +35,7 @@ int main(int argc, char **argv)
     int loss = TSCM_LOSS_NONE;
     double loss_scale = 1.0;
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
-    bool bad_args = argc < 3, use_ransac = false, covariance = false, uncertainty = false;
+    bool bad_args = argc < 3, use_ransac = false, ransac_mask = false, covariance = false, uncertainty = false;
     double unc_step = 0.0, unc_inv_distance = 0.0;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
@@ -53,6 +55,8 @@ int main(int argc, char **argv)
         } else if (!std::strcmp(argv[i], "--ransac") && i + 1 < argc) {
             use_ransac = true;
             bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
+        } else if (!std::strcmp(argv[i], "--ransac-mask")) {
+            ransac_mask = true;
         } else if (!std::strcmp(argv[i], "--covariance")) {
             covariance = true;
         } else if (!std::strcmp(argv[i], "--uncertainty") && i + 1 < argc) {
@@ -70,9 +74,10 @@ int main(int argc, char **argv)
             bad_args = true;
         }
     }
+    bad_args = bad_args || (ransac_mask && !use_ransac);
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -97,9 +102,10 @@ int main(int argc, char **argv)
             }
             cameras[m].set_loss(loss, loss_scale);
             cameras[m].set_fixed_intrinsics(fixed);                          // (a fresh calibrate starts at xi = lambda = 0)
-            if (use_ransac) cameras[m].set_ransac(&ransac);
+            if (use_ransac) cameras[m].set_ransac(&ransac, ransac_mask);
             const bool ok = cameras[m].calibrate(pixels, has, worlds, image, board);
             if (use_ransac) tscm::print_ransac_summary(cameras[m], has, m);
+            if (ransac_mask) tscm::print_ransac_masked(cameras[m], m);
             std::printf("camera %d: %s, rmse %.4f px, fx %.3f fy %.3f cx %.3f cy %.3f xi %.4f lambda %.4f alpha %.4f\n", m, ok ? "converged" : "NOT converged",
                         cameras[m].summary.rmse, cameras[m].intrinsic_[0], cameras[m].intrinsic_[1], cameras[m].intrinsic_[2], cameras[m].intrinsic_[3],
                         cameras[m].intrinsic_[4], cameras[m].intrinsic_[5], cameras[m].intrinsic_[6]);
@@ -109,6 +115,8 @@ int main(int argc, char **argv)
             tscm::MultiCalib mul_calib(cameras, worlds);                     // main.cpp:233
             mul_calib.set_loss(loss, loss_scale);
             for (int m = 0; m < C; ++m) mul_calib.set_fixed_intrinsics(m, fixed);
+            const std::vector<std::vector<std::vector<double> > > masks = tscm::ransac_corner_masks(cameras);
+            if (ransac_mask) mul_calib.set_corner_weights(&masks);            // the joint solve and the covariance take the masks too
             mul_calib.calibrate();                                           // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             for (int m = 0; m < C; ++m) std::printf("camera_%d reprojection error: %.6f\n", m, mul_calib.camera_error[m]);

@@ -4,9 +4,11 @@
 // Images are 8-bit binary PGM files (P5); the list file holds one line per camera: "<n_frames> path_0 path_1 ..." with "-"
 // for a frame the camera has no image of.  The viewer and the drawing calls of main.cpp are left out.
 //   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
-//                                [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]
+//                                [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]
 //   (--model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
+//    --ransac-mask (with --ransac): the inlier masks are the corner masks of every refinement and of the joint solve; prints the
+//                  number of corners masked per camera
 //    --ransac: the start poses of both calibrate() calls come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view
 //    without consensus leaves the calibration, and per camera the views kept and the share of inlier corners are printed)
 #include <tscm/tscm_calib.hpp>
@@ -97,7 +99,7 @@ int main(int argc, char **argv)
 {
     std::vector<const char *> pos;                  // positional arguments: list, yaml, then cols rows pitch
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
-    bool bad_args = false, use_ransac = false;
+    bool bad_args = false, use_ransac = false, ransac_mask = false;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
     for (int i = 1; i < argc && !bad_args; ++i) {
@@ -112,13 +114,15 @@ int main(int argc, char **argv)
             bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
         } else if (!std::strcmp(argv[i], "--ransac")) {
             bad_args = true;
+        } else if (!std::strcmp(argv[i], "--ransac-mask")) {
+            ransac_mask = true;
         } else {
             pos.push_back(argv[i]);
         }
     }
-    if (bad_args || pos.size() < 2) {
+    if (bad_args || pos.size() < 2 || (ransac_mask && !use_ransac)) {
         std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] "
-                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]]]\n", argv[0]);
+                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -145,12 +149,15 @@ int main(int argc, char **argv)
         for (size_t m = 0; m < images.size(); ++m) {
             std::printf("camera %zu: ", m);
             cameras[m].set_fixed_intrinsics(fixed);                            // (the first calibrate starts at xi = lambda = 0)
-            if (use_ransac) cameras[m].set_ransac(&ransac);
+            if (use_ransac) cameras[m].set_ransac(&ransac, ransac_mask);
             monocular_calib(images[m], size, board, worlds, cameras[m]);
+            if (ransac_mask) tscm::print_ransac_masked(cameras[m], (int)m);
         }
         if (cameras.size() > 1) {
             tscm::MultiCalib mul_calib(cameras, worlds);                       // main.cpp:233
             for (size_t m = 0; m < cameras.size(); ++m) mul_calib.set_fixed_intrinsics((int)m, fixed);
+            const std::vector<std::vector<std::vector<double> > > masks = tscm::ransac_corner_masks(cameras);
+            if (ransac_mask) mul_calib.set_corner_weights(&masks);              // the joint solve takes the masks too
             mul_calib.calibrate();                                             // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             std::printf("average reproject error: %.6f\n", mul_calib.mean_error);

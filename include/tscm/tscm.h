@@ -460,6 +460,52 @@ int tscm_covariance_from_normal_equations(int n_cameras, int n_boards, int n_vie
                                           const unsigned char *cam_free, const unsigned char *board_free, int device_index,
                                           double *cam_cov, double *board_cov, tscm_covariance_info *info);
 
+/* ------------------------------------------------------------------ corner weights and corner masks
+ * Ceres' ScaledLoss on every residual block -- new ScaledLoss(loss, w, TAKE_OWNERSHIP) -- or, with weight 0, the corner's
+ * AddResidualBlock left out.
+ *   - Every corner i has a weight omega_i >= 0, with s_i = r_u^2 + r_v^2.
+ *   - Loss rho of kind TSCM_LOSS_NONE is rho(s) = s, rho' = 1.
+ *   - Block cost is omega_i rho(s_i) / 2.
+ *   - Residual and Jacobian rows are scaled by w_i = sqrt(omega_i rho'(s_i)).  rho' is clamped at DBL_MIN as for a loss, before
+ *     the multiplication by omega, so omega_i = 0 gives w_i = 0 exactly.
+ *   - Every reported cost, gradient, LM diagonal and tolerance test follows from these, exactly as for a loss.
+ * Masked corners.  omega_i = 0 takes the corner out.  The observation of a masked corner may hold anything, NaN and
+ * infinities included: this is how a partial board with a missing interior corner is expressed.  The device copy of a masked
+ * observation is written as 0.0, 0.0 at upload, so no NaN reaches arithmetic.
+ * Counts and RMSE.  summary.n_residual_blocks counts the corners with omega_i > 0; summary.rmse = sqrt(sum omega_i s_i /
+ * sum omega_i) at the accepted point -- for a 0/1 mask the pixel RMSE over the kept corners.  tscm_reprojection_error knows
+ * no weights.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the corner or view: a weight that is negative,
+ * NaN or infinite; a view with view_count > 0 whose weights are all 0 (pass view_count = 0 for it).  Weights with
+ * TSCM_EXEC_GRAM_16X16: TSCM_E_UNSUPPORTED, as for a loss.
+ * weights = NULL is the solve without weights, bit for bit, on a fresh solver and after weights were set and cleared.
+ *
+ * weights: [N] in the problem's corner order -- views in problem order, the corners of a view in order (N = sum of view_count;
+ * view_offset plays no part) -- or NULL for none.  May be called between solves.  A sharded solver takes the full [N] array
+ * and keeps its own views' part.  The shards of a local group must all have weights or all have none
+ * (tscm_solver_solve_group: TSCM_E_INVALID otherwise); across processes this is not checked.
+ * tscm_solver_eval_normal_equations uses the solver's weights.                                                              */
+int tscm_solver_set_corner_weights(tscm_solver *s, const double *weights);
+/* tscm_solve_fixed, tscm_eval_normal_equations_robust and tscm_eval_step_fixed with corner weights (device_index: as `device`
+ * of those) */
+int tscm_solve_weighted(const tscm_problem *problem, const tscm_options *opt, const double *weights, const unsigned short *fixed, int kind,
+                        double scale, tscm_summary *summary);
+int tscm_eval_normal_equations_weighted(const tscm_problem *problem, int device_index, const tscm_options *opt, const double *weights, int kind,
+                                        double scale, double *board_gram, double *board_grad, double *view_cross, double *cam_gram,
+                                        double *cam_grad, double *cost);
+int tscm_eval_step_weighted(const tscm_problem *problem, int device_index, const tscm_options *opt, const double *weights,
+                            const unsigned short *fixed, int kind, double scale, double *cam_rt, double *intr, double *board_rt,
+                            int *valid, tscm_summary *summary);
+/* tscm_solve_mono_batch with weights[k] (or NULL) the corner weights of problem k; weights = NULL: none */
+int tscm_solve_mono_batch_weighted(const tscm_problem *problems, int n_problems, int device_index, const tscm_options *opt,
+                                   const unsigned short *fixed /* [n_problems] or NULL */,
+                                   const double *const *weights /* [n_problems] pointers, entries may be NULL */, int loss_kind,
+                                   double loss_scale, tscm_summary *summaries /* [n_problems] */);
+/* tscm_covariance on the blocks of the weighted normal equations; n_residuals = 2 * #{omega_i > 0} */
+int tscm_covariance_weighted(const tscm_problem *problem, int device_index, const unsigned short *fixed, const double *weights,
+                             int loss_kind, double loss_scale, double *cam_cov, double *board_cov, double *cam_rt_std,
+                             double *intr_std, double *board_rt_std, tscm_covariance_info *info);
+
 /* ------------------------------------------------------------------ projection uncertainty maps
  * The covariance of a projected pixel under the joint parameter covariance of tscm_covariance: what a standard deviation
  * on xi or lambda means in pixels.  A stage of its own behind tscm_covariance; it runs no other kernel of the library.

@@ -144,20 +144,43 @@ public:
     // intrinsics refinement() holds at their current values: TSCM_FIX_* bits (TSCM_MODEL_DS, TSCM_MODEL_UCM,
     // TSCM_FIX_INTRINSICS, ...) -- SetManifold(intrinsic_.data(), new SubsetManifold(9, {...})).  0 = none (the default).
     void set_fixed_intrinsics(unsigned short fixed) { fixed_ = fixed; }
+    // corner weights of refinement() (tscm.h, "corner weights": Ceres' ScaledLoss per residual block, weight 0 takes the corner
+    // out and its pixel may hold anything): weights[i][j] for corner j of view i, shaped like `pixels`; NULL = none (the
+    // default).  A view whose weights are all 0 is left out of the refinement like a view without a chessboard.  After a
+    // calibrate() with set_ransac(params, true) the RANSAC inlier masks take their place.
+    void set_corner_weights(const std::vector<std::vector<double> > *weights)
+    {
+        use_weights_ = weights != NULL;
+        corner_weights_ = weights ? *weights : std::vector<std::vector<double> >();
+    }
+    // weight of corner j of view i in the next refinement(); *weighted: whether there are weights at all
+    double corner_weight(size_t i, size_t j, bool *weighted) const
+    {
+        const bool mask = use_ransac_ && mask_outliers_ && ransac_inliers_.size() == has_chessboard_.size();
+        *weighted = mask || use_weights_;
+        if (mask) return i < ransac_inliers_.size() && j < ransac_inliers_[i].size() && ransac_inliers_[i][j] ? 1.0 : 0.0;
+        if (use_weights_) return i < corner_weights_.size() && j < corner_weights_[i].size() ? corner_weights_[i][j] : 0.0;
+        return 1.0;
+    }
 
     // TS.cpp:247-282: joint refinement of intrinsic_ and rt_[i]; returns termination_type == CONVERGENCE
     bool refinement(const std::vector<std::vector<Point2d> > &pixels, const std::vector<Point3d> &worlds,
                     const tscm_options *options = nullptr)
     {
         const int V = (int)pixels.size(), n = (int)worlds.size();
-        std::vector<double> bxy(2 * (size_t)n), u, v, rt(6 * (size_t)V, 0.0);
+        std::vector<double> bxy(2 * (size_t)n), u, v, w, rt(6 * (size_t)V, 0.0);
         std::vector<int> vc, vb, vo, vn;
+        bool weighted = false;
         for (int j = 0; j < n; ++j) { bxy[2 * j] = worlds[j].x; bxy[2 * j + 1] = worlds[j].y; }
         for (int i = 0; i < V; ++i) {
             if (!has_chessboard_[i]) continue;                           // TS.cpp:253
+            std::memcpy(&rt[6 * (size_t)i], rt_[i].data(), 6 * sizeof(double));
+            bool any = false;
+            for (size_t j = 0; j < pixels[i].size(); ++j) any = corner_weight((size_t)i, j, &weighted) != 0.0 || any;
+            if (weighted && !any) continue;                              // every weight 0: no residual block of this view
+            for (size_t j = 0; j < pixels[i].size(); ++j) w.push_back(corner_weight((size_t)i, j, &weighted));
             vc.push_back(0); vb.push_back(i); vo.push_back((int)u.size()); vn.push_back((int)pixels[i].size());
             for (const Point2d &p : pixels[i]) { u.push_back(p.x); v.push_back(p.y); }
-            std::memcpy(&rt[6 * (size_t)i], rt_[i].data(), 6 * sizeof(double));
         }
         tscm_problem P = tscm_problem();
         P.n_cameras = 1; P.n_boards = V; P.n_points = n; P.n_views = (int)vc.size();
@@ -165,7 +188,8 @@ public:
         P.obs_u = u.data(); P.obs_v = v.data(); P.intr = intrinsic_.data(); P.board_rt = rt.data(); P.mono = 1;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 1);
-        if (fixed_) check(tscm_solve_fixed(&P, &o, &fixed_, loss_kind_, loss_scale_, &summary));
+        if (weighted) check(tscm_solve_weighted(&P, &o, w.data(), fixed_ ? &fixed_ : NULL, loss_kind_, loss_scale_, &summary));
+        else if (fixed_) check(tscm_solve_fixed(&P, &o, &fixed_, loss_kind_, loss_scale_, &summary));
         else if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_mono(&P, &o, &summary));
         else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
@@ -291,9 +315,12 @@ public:
     }
     // calibrate() takes its start poses from estimate_extrinsic_ransac with *params (NULL: from estimate_extrinsic again, the
     // default), clears has_chessboard_ for the views without a pose there, and keeps the masks in ransac_inliers_.
-    void set_ransac(const tscm_ransac_params *params)
+    // mask_outliers: calibrate() and every refinement() behind it pass ransac_inliers_ as the corner mask (set_corner_weights):
+    // a corner outside the consensus set is taken out of the refinement.
+    void set_ransac(const tscm_ransac_params *params, bool mask_outliers = false)
     {
         use_ransac_ = params != NULL;
+        mask_outliers_ = use_ransac_ && mask_outliers;
         if (params) ransac_ = *params;
     }
     std::vector<int> ransac_code_;                                    // TSCM_EXTRINSIC_* per view of the last estimate_extrinsic_ransac
@@ -336,7 +363,10 @@ public:
     double loss_scale_ = 0.0;
     unsigned short fixed_ = 0;
     bool use_ransac_ = false;                 // set_ransac()
+    bool mask_outliers_ = false;
     tscm_ransac_params ransac_;
+    bool use_weights_ = false;                // set_corner_weights()
+    std::vector<std::vector<double> > corner_weights_;
 
     // TS.cpp:62-74
     void poses_from_Rt()
@@ -469,6 +499,29 @@ inline void print_ransac_summary(const TripleSphereCamera &cam, const std::vecto
     std::printf("ransac kept %zu of %zu views, %.1f %% of their corners are inliers\n", kept, offered, corners ? 100.0 * inliers / corners : 0.0);
 }
 
+// Behind calibrate() calls with set_ransac(params, true): the cameras' inlier masks as the weights of
+// MultiCalib::set_corner_weights (weights[m][i][j] = 1 for an inlier, 0 otherwise; a view without a mask gets none)
+inline std::vector<std::vector<std::vector<double> > > ransac_corner_masks(const std::vector<TripleSphereCamera> &cameras)
+{
+    std::vector<std::vector<std::vector<double> > > w(cameras.size());
+    for (size_t m = 0; m < cameras.size(); ++m) {
+        w[m].resize(cameras[m].ransac_inliers_.size());
+        for (size_t i = 0; i < w[m].size(); ++i) w[m][i].assign(cameras[m].ransac_inliers_[i].begin(), cameras[m].ransac_inliers_[i].end());
+    }
+    return w;
+}
+// ... and what the demos print with --ransac-mask: the corners of the kept views that the mask takes out of the refinements
+inline void print_ransac_masked(const TripleSphereCamera &cam, int camera)
+{
+    size_t corners = 0, masked = 0;
+    for (size_t i = 0; i < cam.ransac_inliers_.size(); ++i) {
+        if (i >= cam.has_chessboard_.size() || !cam.has_chessboard_[i]) continue;
+        for (size_t j = 0; j < cam.ransac_inliers_[i].size(); ++j) { ++corners; masked += cam.ransac_inliers_[i][j] ? 0 : 1; }
+    }
+    if (camera >= 0) std::printf("camera %d: ", camera);
+    std::printf("ransac mask takes out %zu of %zu corners\n", masked, corners);
+}
+
 // multi_calib.h:8-83
 class MultiCalib_camera {
 public:
@@ -572,9 +625,22 @@ public:
         fixed_[(size_t)m] = fixed;
     }
 
+    // corner weights of calibrate() and covariance() (TripleSphereCamera::set_corner_weights): weights[m][i][j] for corner j of
+    // board i in camera m, shaped like the cameras' pixel_coordinates_; NULL = none.  A view whose weights are all 0 is left out.
+    // With sharding every rank must set the same.
+    void set_corner_weights(const std::vector<std::vector<std::vector<double> > > *weights)
+    {
+        use_weights_ = weights != NULL;
+        corner_weights_ = weights ? *weights : std::vector<std::vector<std::vector<double> > >();
+    }
+    double corner_weight(size_t m, size_t i, size_t j) const
+    {
+        return m < corner_weights_.size() && i < corner_weights_[m].size() && j < corner_weights_[m][i].size() ? corner_weights_[m][i][j] : 0.0;
+    }
+
     // the problem of multi_calib.cpp:157-207 at the objects' current parameters (the arrays P points into live in here)
     struct JointProblem {
-        std::vector<double> bxy, u, v, crt, I, brt;
+        std::vector<double> bxy, u, v, w, crt, I, brt;
         std::vector<int> vc, vb, vo, vn;
         std::vector<unsigned char> cc;
         std::vector<unsigned short> fixed;
@@ -590,6 +656,13 @@ public:
         for (int m = 0; m < C; ++m)                                      // :162-207: camera m, board i, corner j
             for (int i = 0; i < B; ++i) {
                 if (!chessboards_[i].is_initial() || cameras_[m].pixel_coordinates_[i].empty()) continue;
+                if (use_weights_) {
+                    const size_t nj = cameras_[m].pixel_coordinates_[i].size();
+                    bool any = false;
+                    for (size_t j = 0; j < nj; ++j) any = any || corner_weight((size_t)m, (size_t)i, j) != 0.0;
+                    if (!any) continue;                                  // every weight 0: no residual block of this view
+                    for (size_t j = 0; j < nj; ++j) q.w.push_back(corner_weight((size_t)m, (size_t)i, j));
+                }
                 q.vc.push_back(m); q.vb.push_back(i); q.vo.push_back((int)q.u.size()); q.vn.push_back((int)cameras_[m].pixel_coordinates_[i].size());
                 for (const Point2d &p : cameras_[m].pixel_coordinates_[i]) { q.u.push_back(p.x); q.v.push_back(p.y); }
             }
@@ -628,11 +701,13 @@ public:
             int rc = tscm_solver_set_comm(s, comm_);
             if (rc == 0) rc = tscm_solver_set_loss(s, loss_kind_, loss_scale_);
             if (rc == 0 && any_fixed) rc = tscm_solver_set_fixed_intrinsics(s, fixed.data());
+            if (rc == 0 && use_weights_) rc = tscm_solver_set_corner_weights(s, q.w.data());
             if (rc == 0) rc = tscm_solver_solve(s, &o, &summary);
             tscm_solver_destroy(s);
             check(rc);
         } else {
-            if (any_fixed) check(tscm_solve_fixed(&P, &o, fixed.data(), loss_kind_, loss_scale_, &summary));
+            if (use_weights_) check(tscm_solve_weighted(&P, &o, q.w.data(), any_fixed ? fixed.data() : nullptr, loss_kind_, loss_scale_, &summary));
+            else if (any_fixed) check(tscm_solve_fixed(&P, &o, fixed.data(), loss_kind_, loss_scale_, &summary));
             else if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_multi(&P, &o, &summary));
             else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
         }
@@ -671,6 +746,10 @@ public:
         out.cam_rt_std.assign(6 * C, 0.0); out.intr_std.assign(9 * C, 0.0); out.board_rt_std.assign(6 * B, 0.0);
         out.info = tscm_covariance_info();
         out.info.struct_size = (int)sizeof(tscm_covariance_info);
+        if (use_weights_)
+            check(tscm_covariance_weighted(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, q.w.data(), loss_kind_, loss_scale_, out.cam_cov.data(),
+                                           out.board_cov.data(), out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
+        else
         check(tscm_covariance(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, loss_kind_, loss_scale_, out.cam_cov.data(), out.board_cov.data(),
                               out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
         out.sigma2 = out.info.sigma2;
@@ -750,6 +829,8 @@ public:
     int loss_kind_ = TSCM_LOSS_NONE;          // set_loss()
     double loss_scale_ = 0.0;
     std::vector<unsigned short> fixed_;       // set_fixed_intrinsics(), by camera (missing entries: 0)
+    bool use_weights_ = false;                // set_corner_weights()
+    std::vector<std::vector<std::vector<double> > > corner_weights_;
     tscm_comm *comm_ = nullptr;
     tscm_summary summary;                     // BriefReport data of the solve (:218)
     std::vector<double> camera_error;         // per-camera mean pixel error (:281)

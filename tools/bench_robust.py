@@ -6,7 +6,10 @@ Configs 4 and 5 of BASELINE.json, the fp64 (k_eval_gram4) and fp32-Jacobian (k_e
 --kernel-medians-from DIR the line also carries the median duration of the default and the robust k_eval_gram4 launches
 of a `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_robust.py --profile-run` run.
 
-    python tools/bench_robust.py [--iters N] [--configs 4,5] [--kernel-medians-from DIR]"""
+--weights adds, for no loss and Huber, the same solves with corner weights (20 % of the corners masked, the rest uniform in
+[0.25, 4]: the WEIGHTED instantiations), as <key>_weights, and their cost against the unweighted solve with the same loss.
+
+    python tools/bench_robust.py [--iters N] [--configs 4,5] [--weights] [--kernel-medians-from DIR]"""
 import argparse
 import csv
 import glob
@@ -16,6 +19,8 @@ import re
 import statistics
 import sys
 import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tscm_calib_amd import api, synth                        # noqa: E402
@@ -40,12 +45,15 @@ def kernel_medians(d):
     """Median ns of the k_eval_gram4 launches of a kernel trace, default and robust instantiations apart (launches that
     exit early on ctrl->done, a few microseconds, are left out)."""
     f = sorted(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True))[-1]
-    dur = {"default": [], "robust": []}
+    dur = {"default": [], "robust": [], "weighted": []}
     for r in csv.DictReader(open(f)):
         name = r["Kernel_Name"]
         if "k_eval_gram4" not in name:
             continue
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
+        if "k_eval_gram4_weighted" in name:
+            dur["weighted"].append(ns)
+            continue
         m = re.search(r"k_eval_gram4<\s*\d+\s*,\s*(?:true|false)\s*,\s*(true|false)\s*>", name)
         dur["robust" if m and m.group(1) == "true" else "default"].append(ns)
     out = {}
@@ -54,6 +62,8 @@ def kernel_medians(d):
         out[k] = {"median_ns": int(statistics.median(big)) if big else None, "launches": len(big)}
     if out["default"]["median_ns"] and out["robust"]["median_ns"]:
         out["robust_over_default"] = round(out["robust"]["median_ns"] / out["default"]["median_ns"], 4)
+    if out["robust"]["median_ns"] and out["weighted"]["median_ns"]:
+        out["weighted_over_robust"] = round(out["weighted"]["median_ns"] / out["robust"]["median_ns"], 4)
     return out
 
 
@@ -61,6 +71,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--configs", default="4,5")
+    ap.add_argument("--weights", action="store_true", help="also with corner weights, for no loss and Huber")
     ap.add_argument("--kernel-medians-from", metavar="DIR")
     ap.add_argument("--profile-run", action="store_true", help="config 4, fp64, none and Huber, 60 iterations each (under rocprofv3)")
     a = ap.parse_args()
@@ -77,6 +88,13 @@ def main():
                     s.set_loss(kind, 1.0)
                     key = f"config{cfg}_{'fp32' if fp32 else 'fp64'}_{name}"
                     res[key] = round(iterations_per_s(s, 60 if a.profile_run else a.iters, fp32), 2)
+                    if a.weights and name in ("none", "huber"):
+                        rng = np.random.default_rng(cfg)
+                        w = rng.uniform(0.25, 4.0, p.n_corners)
+                        w[rng.random(p.n_corners) < 0.2] = 0.0
+                        s.set_corner_weights(w)
+                        res[key + "_weights"] = round(iterations_per_s(s, 60 if a.profile_run else a.iters, fp32), 2)
+                        s.set_corner_weights(None)
             s.set_loss(None)
     line = {"metric": "lm_iterations_per_s", "iters": a.iters, "results": res}
     for cfg in configs:
@@ -86,6 +104,9 @@ def main():
                 v = res.get(f"config{cfg}_{tier}_{name}")
                 if base and v:
                     line.setdefault("cost_vs_none", {})[f"config{cfg}_{tier}_{name}"] = round(base / v - 1.0, 4)
+    for key, v in list(res.items()):
+        if key.endswith("_weights") and res.get(key[:-len("_weights")]):
+            line.setdefault("weights_cost_vs_unweighted", {})[key] = round(res[key[:-len("_weights")]] / v - 1.0, 4)
     if a.kernel_medians_from:
         line["k_eval_gram4"] = kernel_medians(a.kernel_medians_from)
     print(json.dumps(line))

@@ -27,16 +27,21 @@ from .problem import Problem
 class Solver:
     """RAII wrapper of tscm_solver (problem uploaded once, parameters in/out per solve)."""
 
-    def __init__(self, problem: Problem, device: int = 0, rank: int = 0, world: int = 1):
+    def __init__(self, problem: Problem, device: int = 0, rank: int = 0, world: int = 1, *, weights=None):
         """rank / world: frame-sharded solve -- every rank passes the same WHOLE problem and keeps the boards it owns
-        (tscm_solver_create_sharded); attach a communicator with set_comm() before solving."""
+        (tscm_solver_create_sharded); attach a communicator with set_comm() before solving.
+        weights (default: problem.weights): corner weights as for set_corner_weights(); a view whose weights are all 0 is
+        created with view_count 0."""
         self.problem = problem.normalised() if not _is_normalised(problem) else problem
         self.problem.validate()
-        self._cp = _l.c_problem(self.problem)
+        self._built, w = _l.corner_weights(self.problem, weights)
+        self._cp = _l.c_problem(self._built)
         self._h = C.c_void_p()
         self.rank, self.world = rank, world
         _l.check(_l.lib().tscm_solver_create_sharded(C.byref(self._cp), device, rank, world, C.byref(self._h)))
         self._comm = None
+        if w is not None:
+            _l.check(_l.lib().tscm_solver_set_corner_weights(self._h, _l.dptr(w)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -60,6 +65,19 @@ class Solver:
         "cauchy" with its scale in pixels -- Ceres' HuberLoss(scale) etc. on every corner -- or None for plain least squares."""
         k, a = _l.loss_args(None if kind is None else (kind, scale))
         _l.check(_l.lib().tscm_solver_set_loss(self._h, k, a))
+
+    def set_corner_weights(self, weights):
+        """The corner weights of every later solve / solve_resident (tscm_solver_set_corner_weights): [n_corners] of the
+        problem in corner order -- views in order, the corners of a view in order -- a bool mask meaning 0 / 1, or None for
+        none.  Ceres' ScaledLoss per residual block; weight 0 takes the corner out, and its observation may hold anything.
+        A view whose weights are all 0 must have been created with view_count 0 (pass weights= to the constructor): ValueError
+        otherwise.  The solver keeps the views it was created with: on one created without some views, later weights for them
+        are not used, and None is the solve without weights of the views it has, not of the whole problem."""
+        if weights is None:
+            _l.check(_l.lib().tscm_solver_set_corner_weights(self._h, None))
+            return
+        _, w = _l.corner_weights(self.problem, weights, self._built.view_count)
+        _l.check(_l.lib().tscm_solver_set_corner_weights(self._h, _l.dptr(w)))
 
     def set_fixed_intrinsics(self, fixed):
         """The held intrinsics of every later solve / solve_resident (tscm_solver_set_fixed_intrinsics): None, names such as
@@ -203,13 +221,15 @@ class Group:
     """`world` shards of one problem on ONE device, solved in lock step with the in-process exchange
     (tscm_comm_create_local + tscm_solver_solve_group): the frame-sharded solver without RCCL, e.g. on a one-GPU box."""
 
-    def __init__(self, problem: Problem, world: int, device: int = 0, *, loss=None, fixed=None):
+    def __init__(self, problem: Problem, world: int, device: int = 0, *, loss=None, fixed=None, weights=None):
         """loss: None, or (kind, scale) as for calibrate(); every shard carries it (Solver.set_loss).
-        fixed: held intrinsics as for calibrate(); every shard holds them (Solver.set_fixed_intrinsics)."""
+        fixed: held intrinsics as for calibrate(); every shard holds them (Solver.set_fixed_intrinsics).
+        weights (default: problem.weights): corner weights as for calibrate(); every shard takes the whole array and keeps
+        its own views' part."""
         self.problem = problem.normalised() if not _is_normalised(problem) else problem
         self.world = world
         self.comms = Comm.local_group(world, device)
-        self.solvers = [Solver(self.problem, device, r, world) for r in range(world)]
+        self.solvers = [Solver(self.problem, device, r, world, weights=weights) for r in range(world)]
         for s, c in zip(self.solvers, self.comms):
             s.set_comm(c)
         if loss is not None:
@@ -269,46 +289,52 @@ def _is_normalised(p: Problem) -> bool:
             and (p.board_pose_constant is None or ok(p.board_pose_constant, np.uint8)))
 
 
-def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, **options) -> dict:
+def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, **options) -> dict:
     """The Ceres block of MultiCalib::calibrate() (multi_calib.cpp:157-218): joint LM over
     camera poses, board poses and intrinsics, in place on `problem`.  Like the reference,
     the outcome is not turned into an error -- inspect summary['termination'].
     loss: None (the reference's NULL loss), or (kind, scale) with kind "huber" | "soft_l1" | "cauchy"
     and scale in pixels: Ceres' HuberLoss(scale) etc. on every corner (tscm_solve_robust).
     fixed: intrinsics held at their start values (tscm_solve_fixed) -- None, names such as ("cx", "cy") for every
-    camera, a [C] int array of TSCM_FIX_* words (lib.FIX, lib.MODEL_DS, ...) or a [C, 9] bool array."""
+    camera, a [C] int array of TSCM_FIX_* words (lib.FIX, lib.MODEL_DS, ...) or a [C, 9] bool array.
+    weights (default: problem.weights): [n_corners] corner weights in corner order, a bool mask meaning 0 / 1 -- Ceres'
+    ScaledLoss per residual block; weight 0 takes the corner out, whatever its observation holds (tscm_solve_weighted).
+    A view whose weights are all 0 goes in with view_count 0."""
     if problem.mono:
         raise ValueError("calibrate() is the multi-camera solve; use refinement() for a mono problem")
     assert _is_normalised(problem), "use Problem.normalised()"
     o = _l.default_options(False, **options)
     s = _l.CSummary()
-    cp = _l.c_problem(problem)
+    q, w = _l.corner_weights(problem, weights)
+    cp = _l.c_problem(q)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_multi)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_multi, w)
     return _l.summary_dict(s)
 
 
-def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, **options):
+def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, **options):
     """TripleSphereCamera::refinement (TS.cpp:247-282): returns (converged, summary) where
     converged == (termination_type == CONVERGENCE), the reference's return value (:281).
-    loss, fixed: as for calibrate()."""
+    loss, fixed, weights: as for calibrate()."""
     if not problem.mono:
         raise ValueError("refinement() is the mono solve")
     assert _is_normalised(problem), "use Problem.normalised()"
     o = _l.default_options(True, **options)
     s = _l.CSummary()
-    cp = _l.c_problem(problem)
+    q, w = _l.corner_weights(problem, weights)
+    cp = _l.c_problem(q)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_mono)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_mono, w)
     d = _l.summary_dict(s)
     return d["termination_type"] == 0, d
 
 
-def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, **options):
+def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, weights=None, **options):
     """n TripleSphereCamera::refinement solves (TS.cpp:247-282) in one batch on one device (tscm_solve_mono_batch):
     returns [(converged, summary), ...] in problem order, each as refinement() would return it for that problem alone.
     Parameters are updated in place.  loss: shared, as for refinement(); fixed: None, or one mask per problem (anything
-    fixed_masks takes for one camera: an int, names, a [9] bool array, or None)."""
+    fixed_masks takes for one camera: an int, names, a [9] bool array, or None); weights: None (then each problem's own
+    .weights), or one entry per problem, each as for refinement() or None (tscm_solve_mono_batch_weighted)."""
     problems = list(problems)
     if not problems:
         raise ValueError("refinement_batch() needs at least one problem")
@@ -318,7 +344,11 @@ def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, **opti
         assert _is_normalised(p), "use Problem.normalised()"
     n = len(problems)
     o = _l.default_options(True, **options)
-    cps = (_l.CProblem * n)(*[_l.c_problem(p) for p in problems])
+    if weights is not None and len(weights) != n:
+        raise ValueError("weights: one entry per problem")
+    built = [_l.corner_weights(p, None if weights is None else weights[i]) for i, p in enumerate(problems)]
+    ws = [w for _, w in built]
+    cps = (_l.CProblem * n)(*[_l.c_problem(q) for q, _ in built])
     sums = (_l.CSummary * n)()
     if fixed is None:
         w = None
@@ -327,7 +357,12 @@ def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, **opti
             raise ValueError("fixed: one mask per problem")
         w = np.array([_l.fixed_masks(f, 1)[0] for f in fixed], dtype=np.uint16)
     k, a = _l.loss_args(loss)
-    _l.check(_l.lib().tscm_solve_mono_batch(cps, n, device, C.byref(o), _l.ushort_ptr(w) if w is not None else None, k, a, sums))
+    if any(x is not None for x in ws):
+        dp = C.POINTER(C.c_double)
+        wp = (dp * n)(*[_l.dptr(x) if x is not None else dp() for x in ws])
+        _l.check(_l.lib().tscm_solve_mono_batch_weighted(cps, n, device, C.byref(o), _l.ushort_ptr(w) if w is not None else None, wp, k, a, sums))
+    else:
+        _l.check(_l.lib().tscm_solve_mono_batch(cps, n, device, C.byref(o), _l.ushort_ptr(w) if w is not None else None, k, a, sums))
     out = []
     for i in range(n):
         d = _l.summary_dict(sums[i])
@@ -335,8 +370,12 @@ def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, **opti
     return out
 
 
-def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, plain):
-    if fixed is not None:
+def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, plain, weights=None):
+    if weights is not None:
+        w = None if fixed is None else _l.fixed_masks(fixed, n_cameras)
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_solve_weighted(C.byref(cp), C.byref(o), _l.dptr(weights), None if w is None else _l.ushort_ptr(w), k, a, C.byref(s)))
+    elif fixed is not None:
         w = _l.fixed_masks(fixed, n_cameras)
         k, a = _l.loss_args(loss)
         _l.check(_l.lib().tscm_solve_fixed(C.byref(cp), C.byref(o), _l.ushort_ptr(w), k, a, C.byref(s)))
@@ -370,26 +409,32 @@ def evaluate_functor(problem: Problem, device: int = 0, jacobians: bool = True):
 
 
 def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0, loss=None,
-                     as_solved: bool = False) -> dict:
+                     as_solved: bool = False, weights=None) -> dict:
     """Schur-form normal equations (unscaled) from the Gram kernel a solve with these options runs:
     k_eval_gram4 by default, k_eval_gram_f32 with jacobian_fp32=1, k_eval_gram with exec_flags=EXEC_GRAM_16X16.
     loss (as for calibrate()): the corrected equations of a robust solve, cost = sum rho / 2.
     as_solved: the evaluation launch exactly as a solve makes it, on a fresh solver (tscm_solver_eval_normal_equations):
-    k_eval_gram4 forms no rotation columns for a camera whose pose block is constant, and those entries are 0."""
+    k_eval_gram4 forms no rotation columns for a camera whose pose block is constant, and those entries are 0.
+    weights (default: problem.weights): corner weights as for calibrate() -- the equations of the rows scaled by
+    sqrt(omega rho'), cost = sum omega rho / 2 (tscm_eval_normal_equations_weighted)."""
     assert _is_normalised(problem)
+    q, w = _l.corner_weights(problem, weights)
     Cn, B, V = problem.n_cameras, problem.n_boards, problem.n_views
     out = dict(board_gram=np.zeros((B, 6, 6)), board_grad=np.zeros((B, 6)), view_cross=np.zeros((V, 6, 15)),
                cam_gram=np.zeros((Cn, 15, 15)), cam_grad=np.zeros((Cn, 15)))
     cost = C.c_double(0.0)
-    cp = _l.c_problem(problem)
+    cp = _l.c_problem(q)
     o = _l.default_options(problem.mono, jacobian_fp32=jacobian_fp32, exec_flags=exec_flags)
     outs = (_l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
             _l.dptr(out["cam_gram"]), _l.dptr(out["cam_grad"]), C.byref(cost))
     if as_solved:
-        with Solver(problem, device) as s:
+        with Solver(problem, device, weights=weights) as s:
             if loss is not None:
                 s.set_loss(*((loss,) if isinstance(loss, str) else loss))
             _l.check(_l.lib().tscm_solver_eval_normal_equations(s._h, C.byref(o), 1, *outs))
+    elif w is not None:
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_eval_normal_equations_weighted(C.byref(cp), device, C.byref(o), _l.dptr(w), k, a, *outs))
     elif loss is None:
         _l.check(_l.lib().tscm_eval_normal_equations_ex(C.byref(cp), device, C.byref(o), *outs))
     else:
@@ -399,19 +444,25 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
     return out
 
 
-def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, **options) -> dict:
+def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, **options) -> dict:
     """The candidate point of the first trust-region step a solve with these options takes (tscm_eval_step_ex), at the
     problem's parameters, which stay as they are: cam_rt, intr, board_rt (x + delta as that solve evaluates it), valid
     (False: the linear solve failed) and the one-iteration summary.  loss: as for calibrate() (tscm_eval_step_robust);
-    fixed: held intrinsics as for calibrate() (tscm_eval_step_fixed)."""
+    fixed: held intrinsics as for calibrate() (tscm_eval_step_fixed); weights: corner weights as for calibrate()
+    (tscm_eval_step_weighted)."""
     assert _is_normalised(problem)
+    q, cw = _l.corner_weights(problem, weights)
     cam, intr, board = np.zeros_like(problem.cam_rt), np.zeros_like(problem.intr), np.zeros_like(problem.board_rt)
     valid = C.c_int(0)
     s = _l.CSummary()
-    cp = _l.c_problem(problem)
+    cp = _l.c_problem(q)
     o = _l.default_options(problem.mono, **options)
     outs = (_l.dptr(cam), _l.dptr(intr), _l.dptr(board), C.byref(valid), C.byref(s))
-    if fixed is not None:
+    if cw is not None:
+        w = None if fixed is None else _l.fixed_masks(fixed, problem.n_cameras)
+        k, a = _l.loss_args(loss)
+        _l.check(_l.lib().tscm_eval_step_weighted(C.byref(cp), device, C.byref(o), _l.dptr(cw), None if w is None else _l.ushort_ptr(w), k, a, *outs))
+    elif fixed is not None:
         w = _l.fixed_masks(fixed, problem.n_cameras)
         k, a = _l.loss_args(loss)
         _l.check(_l.lib().tscm_eval_step_fixed(C.byref(cp), device, C.byref(o), _l.ushort_ptr(w), k, a, *outs))
@@ -464,10 +515,11 @@ def _covariance_dict(info, Cn: int, B: int, cam_cov, board_cov) -> dict:
                 seconds_kernel=tuple(info.seconds_kernel))
 
 
-def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None) -> dict:
+def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None) -> dict:
     """What ceres::Covariance gives a Ceres user, at the problem's parameters (tscm_covariance): (J^T J)^-1 over the free
     columns in Ceres' convention (not multiplied by sigma2), sigma2 = 2 cost / dof and the standard deviations
-    sqrt(sigma2 * diagonal).  loss, fixed: as for calibrate() -- pass what the solve had.
+    sqrt(sigma2 * diagonal).  loss, fixed, weights: as for calibrate() -- pass what the solve had (with weights:
+    tscm_covariance_weighted, the residuals are the corners with a weight > 0).
     -> status (0 ok, 1 singular board block, 2 singular reduced system: every array is then NaN), where, n_free, dof, sigma2,
     cost, min_pivot_ratio (near 0: gauge freedom or an unobservable parameter), cam_cov [C,15,C,15] and board_cov [B,6,6]
     (zero where not free), cam_rt_std [C,6], intr_std [C,9], board_rt_std [B,6] (0 where not free), seconds_kernel (board
@@ -477,11 +529,15 @@ def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None) -> d
     cam_cov, board_cov = np.zeros((Cn * 15, Cn * 15)), np.zeros((B, 6, 6))
     cam_std, intr_std, board_std = np.zeros((Cn, 6)), np.zeros((Cn, 9)), np.zeros((B, 6))
     info = _l.CCovarianceInfo(struct_size=C.sizeof(_l.CCovarianceInfo))
-    cp = _l.c_problem(problem)
+    q, cw = _l.corner_weights(problem, weights)
+    cp = _l.c_problem(q)
     w = None if fixed is None else _l.fixed_masks(fixed, Cn)
     k, a = _l.loss_args(loss)
-    _l.check(_l.lib().tscm_covariance(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), k, a, _l.dptr(cam_cov), _l.dptr(board_cov),
-                                      _l.dptr(cam_std), _l.dptr(intr_std), _l.dptr(board_std), C.byref(info)))
+    outs = (_l.dptr(cam_cov), _l.dptr(board_cov), _l.dptr(cam_std), _l.dptr(intr_std), _l.dptr(board_std), C.byref(info))
+    if cw is not None:
+        _l.check(_l.lib().tscm_covariance_weighted(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), _l.dptr(cw), k, a, *outs))
+    else:
+        _l.check(_l.lib().tscm_covariance(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), k, a, *outs))
     out = _covariance_dict(info, Cn, B, cam_cov, board_cov)
     out.update(cam_rt_std=cam_std, intr_std=intr_std, board_rt_std=board_std)
     return out

@@ -466,8 +466,10 @@ extern "C" int tscm_covariance_from_normal_equations(int n_cameras, int n_boards
     return covariance_run(pl, view_camera, board_gram, view_cross, cam_gram, cam_free, device, "tscm_covariance_from_normal_equations", cam_cov, board_cov, info);
 }
 
-extern "C" int tscm_covariance(const tscm_problem *p, int device, const unsigned short *fixed, int loss_kind, double loss_scale, double *cam_cov,
-                               double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info)
+// weights: the problem's corner weights (tscm_solver_set_corner_weights) or NULL -- the blocks are then those of the weighted
+// normal equations and a corner with weight 0 is no residual
+static int covariance_of_problem(const tscm_problem *p, int device, const unsigned short *fixed, const double *weights, int loss_kind, double loss_scale,
+                                 double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info)
 {
     if (int rc = check_info(info)) return rc;
     reset_info(info);
@@ -491,7 +493,12 @@ extern "C" int tscm_covariance(const tscm_problem *p, int device, const unsigned
     // the blocks, from the default fp64 Gram kernel through the public evaluation
     std::vector<double> bg((size_t)36 * B + 1), vc((size_t)90 * V + 1), cg((size_t)225 * C);
     double cost = 0.0;
-    if (int rc = tscm_eval_normal_equations_robust(p, device, nullptr, loss_kind, loss_scale, bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
+    if (weights) {
+        if (int rc = tscm_eval_normal_equations_weighted(p, device, nullptr, weights, loss_kind, loss_scale, bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
+        long long kept = 0;
+        for (long long i = 0; i < N; ++i) kept += weights[i] > 0.0 ? 1 : 0;
+        N = kept;
+    } else if (int rc = tscm_eval_normal_equations_robust(p, device, nullptr, loss_kind, loss_scale, bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
     const size_t n15 = (size_t)kCovCam * C;
     std::vector<double> own_cam, own_board;
     if (!cam_cov) { own_cam.resize(n15 * n15); cam_cov = own_cam.data(); }
@@ -521,4 +528,17 @@ extern "C" int tscm_covariance(const tscm_problem *p, int device, const unsigned
         if (board_rt_std) std::fill(board_rt_std, board_rt_std + 6 * (size_t)B, nan);
     }
     return 0;
+}
+
+extern "C" int tscm_covariance(const tscm_problem *p, int device, const unsigned short *fixed, int loss_kind, double loss_scale, double *cam_cov,
+                               double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info)
+{
+    return covariance_of_problem(p, device, fixed, nullptr, loss_kind, loss_scale, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
+}
+
+extern "C" int tscm_covariance_weighted(const tscm_problem *p, int device, const unsigned short *fixed, const double *weights, int loss_kind,
+                                        double loss_scale, double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std,
+                                        double *board_rt_std, tscm_covariance_info *info)
+{
+    return covariance_of_problem(p, device, fixed, weights, loss_kind, loss_scale, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
 }

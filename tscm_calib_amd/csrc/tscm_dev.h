@@ -113,6 +113,8 @@ struct DevProblem {
     const double *board_xy;
     const int *view_cam, *view_board, *view_obs, *view_count;
     const double *obs_u, *obs_v;
+    const double *obs_w;               // [N] corner weights in the order of obs_u / obs_v, NULL = none (tscm_solver_set_corner_weights);
+                                       // read by the weighted Gram instantiations and k_reproj_error<true> only
     const int *chunk_vb, *chunk_ve, *chunk_cam, *cam_chunk_ptr;
     const int4 *chunk_desc;            // per chunk of the Gram kernels: camera, first view, end view, observation offset of the first view
     const int *bv_ptr;                 // board -> range of view SLOTS (records are stored board-major)

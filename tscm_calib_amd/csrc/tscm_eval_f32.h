@@ -56,10 +56,13 @@ __host__ __device__ inline int eval_f32_lds_doubles(int n_points, int ks)
 // KS: k-steps of a pass; MULTI: boards of more than 56 corners, P.g4_per corners per pass (the pass plan of k_eval_gram4: g4_plan);
 // ROBUST: a loss L (robust_rho) -- w = sqrt(rho') from the fp64 residual scales the corner's fp32 entries and, in fp64, its
 // residual before the conversion; the cost entry is the fp64 sum of rho (where r^T r sits otherwise).  See k_eval_gram4.
-template <int KS, bool MULTI, bool ROBUST = false>
-__global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState S, int cand, LossArg L)
+// WEIGHTED (with ROBUST): corner weights P.obs_w, fetched beside the observations, into robust_rho<true> (which
+// also takes kind kLossNone); rr is then the fp64 sum of omega rho.  The body of the kernels at the end of this file.
+template <int KS, bool MULTI, bool ROBUST, bool WEIGHTED>
+__device__ __forceinline__ void eval_gram_f32_kernel(const DevProblem &P, const DevState &S, const int cand, const LossArg &L)
 {
     static_assert(KS >= 1 && KS <= kG4MaxKS, "a pass holds at most 56 rows");
+    static_assert(ROBUST || !WEIGHTED, "the weight enters where the loss does");
     // the control block is read together with the static chunk tables (one memory round trip, not two);
     // the early exit is taken right before the first view
     const int ctrl_done = S.ctrl->done, ctrl_cur = S.ctrl->cur;
@@ -89,6 +92,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
     for (int i = lane; i < kTile32; i += 64) lds[i] = 0.0;  // all positions incl. the all-zero 16th tile column and the ones no corner maps to
     int prev_nv = 0;
     double pf_u = 0.0, pf_v = 0.0;
+    double pf_w = 0.0;                             // WEIGHTED: the weight of the corner of pf_u / pf_v
     int warm = 0;
     // k-steps of a pass (kernel-uniform) and this lane's row position as a corner; as an MFMA lane (column, kq): the rows
     // of its K k-steps are positions KB kq .. KB kq + K - 1 of tile column col (B operand) and pi(col) (A operand)
@@ -114,6 +118,8 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
     int m_cnt0 = 0, m_slot0 = 0;
     if (vb + lane < min(ve, vb + 64)) { m_cnt0 = P.view_count[vb + lane]; m_slot0 = P.view_slot[vb + lane]; }
     if (vb < ve) { pf_u = buf_load_f64(r_u, 8u * lane, 8u * (unsigned)off_next); pf_v = buf_load_f64(r_v, 8u * lane, 8u * (unsigned)off_next); }
+    const __amdgpu_buffer_rsrc_t r_w = WEIGHTED ? make_rsrc(P.obs_w, sizeof(double) * (size_t)P.N) : r_u;
+    if constexpr (WEIGHTED) { if (vb < ve) pf_w = buf_load_f64(r_w, 8u * lane, 8u * (unsigned)off_next); }
     {
         // one dword of every 64-byte line of the first view's and the camera's constants (doubles and floats) through the scalar cache
         typedef const int __attribute__((address_space(4))) *cptr4i;
@@ -132,6 +138,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
     else {
         if (vbase + lane < vend) { m_cnt = P.view_count[vbase + lane]; m_slot = P.view_slot[vbase + lane]; }
         pf_u = buf_load_f64(r_u, 8u * lane, 8u * (unsigned)off_next); pf_v = buf_load_f64(r_v, 8u * lane, 8u * (unsigned)off_next);
+        if constexpr (WEIGHTED) pf_w = buf_load_f64(r_w, 8u * lane, 8u * (unsigned)off_next);
     }
     asm volatile("" : "+v"(m_cnt), "+v"(m_slot));       // the loads complete here, outside the view loop
     for (int view = vbase; view < vend; ++view) {
@@ -174,7 +181,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
                 double w = 1.0;
                 if constexpr (ROBUST) {
                     double rho;
-                    robust_rho(L, ru * ru + rv * rv, rho, w);
+                    robust_rho<WEIGHTED>(L, ru * ru + rv * rv, rho, w, pf_w);
                     rr += rho;
                     wf = (float)w;
                 } else {
@@ -252,6 +259,7 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
                 const unsigned noff = more ? (unsigned)(off + c0 + per) : (unsigned)off_next;
                 pf_u = buf_load_f64(r_u, lane < ncnt ? 8u * lane : 0xffffe000u, 8u * noff);
                 pf_v = buf_load_f64(r_v, lane < ncnt ? 8u * lane : 0xffffe000u, 8u * noff);
+                if constexpr (WEIGHTED) pf_w = buf_load_f64(r_w, lane < ncnt ? 8u * lane : 0xffffe000u, 8u * noff);
             }
             wave_lds_fence();
             const int nv = min(per, cnt - c0);
@@ -306,5 +314,18 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState
         part[t] = (lds_all[t] + lds_all[st + t]) + (lds_all[2 * st + t] + lds_all[3 * st + t]);
         part[256 + t] = (lds_all[256 + t] + lds_all[st + 256 + t]) + (lds_all[2 * st + 256 + t] + lds_all[3 * st + 256 + t]);
     }
+}
+
+template <int KS, bool MULTI, bool ROBUST = false>
+__global__ __launch_bounds__(256, 4) void k_eval_gram_f32(DevProblem P, DevState S, int cand, LossArg L)
+{
+    eval_gram_f32_kernel<KS, MULTI, ROBUST, false>(P, S, cand, L);
+}
+
+// ... with corner weights (P.obs_w; L.kind may be kLossNone): the WEIGHTED instantiation
+template <int KS, bool MULTI>
+__global__ __launch_bounds__(256, 4) void k_eval_gram_f32_weighted(DevProblem P, DevState S, int cand, LossArg L)
+{
+    eval_gram_f32_kernel<KS, MULTI, true, true>(P, S, cand, L);
 }
 

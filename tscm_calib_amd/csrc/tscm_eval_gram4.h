@@ -148,14 +148,18 @@ __device__ __forceinline__ double lane_pick(double keep, double take)
 // ROBUST: a loss L (robust_rho): every entry a corner puts into the tile, r column included, is scaled by w = sqrt(rho'), and
 // the cost entry of the camera tile is the lanes' fp64 sum of rho instead of the contraction r^T r.  L is not read
 // by the ROBUST = false instantiations, which compile to the code they had before the switch existed.
+// WEIGHTED (with ROBUST): corner weights P.obs_w -- the weight is fetched like the observation it belongs to (pf_w
+// beside pf_u / pf_v, through a buffer resource: a lane past the end reads 0) and enters robust_rho<true>, which also takes
+// kind kLossNone; rho_sum is then sum(omega rho).  The other instantiations compile to the code they had before.
 // CP: the constant-pose path (above).  The kernel below takes the first trip of the head -- cd: the chunk's descriptor,
 // ctrl_done, ctrl_cur: the control block, my_xy: the lane's board point -- and then one wave-uniform branch into the
 // instantiation of its chunk; cand: 0 or 1.
-template <int KS, bool MULTI, bool ROBUST, bool CP>
+template <int KS, bool MULTI, bool ROBUST, bool CP, bool WEIGHTED = false>
 __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevState &S, const int cand, const LossArg &L, const v4i cd,
                                                 const int ctrl_done, const int ctrl_cur, const d2 my_xy)
 {
     static_assert(KS >= 1 && KS <= kG4MaxKS, "a pass holds at most 56 rows");
+    static_assert(ROBUST || !WEIGHTED, "the weight enters where the loss does");
     constexpr int kTile = g4_tile_doubles(KS);
     constexpr int NQ = CP ? 2 : 3;              // instructions per four rows
 #ifdef TSCM_WAVE_TIMELINE
@@ -196,6 +200,7 @@ __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevSt
     for (int i = lane; i < KS * kG4Stride; i += 64) Fl[i] = 0.0;     // rows of lanes without a corner, the zero column, the padding
     int prev_nv = 0;
     double pf_u = 0.0, pf_v = 0.0;
+    double pf_w = 0.0;                          // WEIGHTED: the weight of the corner of pf_u / pf_v
     int warm = 0;
     double rho_sum = 0.0;                       // ROBUST: this lane's share of sum(rho), fp64
     if (ctrl_done) return;
@@ -205,10 +210,12 @@ __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevSt
     auto CC = [&](int k) { return ccs[k]; };
     const __amdgpu_buffer_rsrc_t r_vc = make_rsrc(S.vconst, sizeof(double) * (size_t)kVStride * P.V);
     const __amdgpu_buffer_rsrc_t r_u = make_rsrc(P.obs_u, sizeof(double) * (size_t)P.N), r_v = make_rsrc(P.obs_v, sizeof(double) * (size_t)P.N);
+    const __amdgpu_buffer_rsrc_t r_w = WEIGHTED ? make_rsrc(P.obs_w, sizeof(double) * (size_t)P.N) : r_u;
     int off_next = cd[3];
     int m_cnt0 = 0, m_slot0 = 0;
     if (vb + lane < min(ve, vb + 64)) { m_cnt0 = P.view_count[vb + lane]; m_slot0 = P.view_slot[vb + lane]; }
     if (vb < ve) { pf_u = buf_load_f64(r_u, 8u * ((unsigned)off_next + lane), 0); pf_v = buf_load_f64(r_v, 8u * ((unsigned)off_next + lane), 0); }
+    if constexpr (WEIGHTED) { if (vb < ve) pf_w = buf_load_f64(r_w, 8u * ((unsigned)off_next + lane), 0); }
     // the scalar cache's lines of the first view's 27 constants (4 lines) and of the camera's 48 (6 lines); retired in front of the loop
     typedef const int __attribute__((address_space(4))) *cptr4i;
     const cptr4i vc0 = (cptr4i)(S.vconst + (size_t)kVStride * min(vb, P.V - 1)), cc0 = (cptr4i)ccs;
@@ -286,6 +293,7 @@ __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevSt
     else {
         if (vbase + lane < vend) { m_cnt = P.view_count[vbase + lane]; m_slot = P.view_slot[vbase + lane]; }
         pf_u = buf_load_f64(r_u, 8u * ((unsigned)off_next + lane), 0); pf_v = buf_load_f64(r_v, 8u * ((unsigned)off_next + lane), 0);
+        if constexpr (WEIGHTED) pf_w = buf_load_f64(r_w, 8u * ((unsigned)off_next + lane), 0);
     }
     asm volatile("" : "+v"(m_cnt), "+v"(m_slot));
     for (int view = vbase; view < vend; ++view) {
@@ -329,9 +337,9 @@ __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevSt
                 // with, merged with them by the compiler), then every entry scaled as it is handed out
                 double ru, rv, rho, w;
                 corner_residual(x, y, pf_u, pf_v, VC, CC, ru, rv);
-                robust_rho(L, ru * ru + rv * rv, rho, w);
+                robust_rho<WEIGHTED>(L, ru * ru + rv * rv, rho, w, pf_w);
                 rho_sum += rho;
-                corner_geometry<!CP>(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], w * u, w * v); });
+                corner_geometry<!CP, WEIGHTED>(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], w * u, w * v); });
             } else {
                 corner_geometry<!CP>(x, y, pf_u, pf_v, VC, CC, [&](int gc, double u, double v) { PUT(tcol[gc], u, v); });
             }
@@ -357,6 +365,7 @@ __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevSt
             const unsigned noff = more ? (unsigned)(off + pb + per) : (unsigned)off_next;
             pf_u = buf_load_f64(r_u, 8u * (noff + lane), 0);
             pf_v = buf_load_f64(r_v, 8u * (noff + lane), 0);
+            if constexpr (WEIGHTED) pf_w = buf_load_f64(r_w, 8u * (noff + lane), 0);
         }
         prev_nv = MULTI ? min(per, max(cnt - pb, 0)) : cnt;
         wave_lds_fence();
@@ -478,9 +487,9 @@ __device__ __forceinline__ void eval_gram4_wave(const DevProblem &P, const DevSt
 #endif
 }
 
-// KS: k-steps of a pass; MULTI, ROBUST: see eval_gram4_wave.  cand: kEvalCand | kEvalSkipConst.
-template <int KS, bool MULTI, bool ROBUST = false>
-__global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S, int cand, LossArg L)
+// the kernels below: the first trip of the head, then one wave-uniform branch into the instantiation of the wave's chunk
+template <int KS, bool MULTI, bool ROBUST, bool WEIGHTED>
+__device__ __forceinline__ void eval_gram4_kernel(const DevProblem &P, const DevState &S, const int cand, const LossArg &L)
 {
     KTL(0);
     const int ctrl_done = S.ctrl->done, ctrl_cur = S.ctrl->cur;
@@ -489,8 +498,22 @@ __global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S,
     const d2 my_xy = *reinterpret_cast<const d2 *>(P.board_xy + 2 * min((int)(threadIdx.x & 63), P.n_points - 1));
     // one camera per chunk and whole workgroups per camera (plan_layout): the branch is uniform in the workgroup
 #ifndef TSCM_G4_FULL_PATH
-    if ((cand & kEvalSkipConst) && (cd[0] & kChunkConstPose)) eval_gram4_wave<KS, MULTI, ROBUST, true>(P, S, cand & kEvalCand, L, cd, ctrl_done, ctrl_cur, my_xy);
+    if ((cand & kEvalSkipConst) && (cd[0] & kChunkConstPose)) eval_gram4_wave<KS, MULTI, ROBUST, true, WEIGHTED>(P, S, cand & kEvalCand, L, cd, ctrl_done, ctrl_cur, my_xy);
     else
 #endif
-        eval_gram4_wave<KS, MULTI, ROBUST, false>(P, S, cand & kEvalCand, L, cd, ctrl_done, ctrl_cur, my_xy);
+        eval_gram4_wave<KS, MULTI, ROBUST, false, WEIGHTED>(P, S, cand & kEvalCand, L, cd, ctrl_done, ctrl_cur, my_xy);
+}
+
+// KS: k-steps of a pass; MULTI, ROBUST: see eval_gram4_wave.  cand: kEvalCand | kEvalSkipConst.
+template <int KS, bool MULTI, bool ROBUST = false>
+__global__ __launch_bounds__(256, 4) void k_eval_gram4(DevProblem P, DevState S, int cand, LossArg L)
+{
+    eval_gram4_kernel<KS, MULTI, ROBUST, false>(P, S, cand, L);
+}
+
+// ... with corner weights (P.obs_w; L.kind may be kLossNone): the WEIGHTED instantiation
+template <int KS, bool MULTI>
+__global__ __launch_bounds__(256, 4) void k_eval_gram4_weighted(DevProblem P, DevState S, int cand, LossArg L)
+{
+    eval_gram4_kernel<KS, MULTI, true, true>(P, S, cand, L);
 }

@@ -100,7 +100,14 @@ enum GCol { gcWb0 = 0, gcWb1, gcWb2, gcTc0, gcTc1, gcTc2, gcWc0, gcWc1, gcWc2, g
 
 // WC = false (k_eval_gram4's path for a camera whose pose is held constant): the camera-rotation columns gcWc0..2 are neither
 // computed nor handed out; every other entry comes from the same operations in the same order.
-template <bool WC = true, typename FV, typename FC, typename FP>
+// PIN_WB (k_eval_gram4's WEIGHTED instantiation): the w_b entries with their FMAs written out, in the pairing the compiler
+// gives the expressions below in the plain instantiation of k_eval_gram4 on both of its paths (read from its gfx950 code:
+// h = fma(x, a, y b); u-row fma(n02, h2, fma(n01, h1, n00 h0)); v-row fma(n12, h2, fma(n10, h0, n11 h1))) -- left to itself the
+// compiler pairs them differently next to corner_residual, and all-ones weights would miss the plain solve's last bits.
+// This is a hand copy of one compiler version's choice: tests/test_gpu_weights.py::test_unit_weights_are_the_plain_gram is its
+// guard.  When it trips after a compiler change, read the plain k_eval_gram4<14, false, false>'s pairing again (DESIGN 27 says how)
+// and restate it here -- or write the unpinned branch with the same explicit fma and refresh tools/regress_bits.expected.
+template <bool WC = true, bool PIN_WB = false, typename FV, typename FC, typename FP>
 __device__ __forceinline__ void corner_geometry(double x, double y, double ou, double ov, FV VC, FC CC, FP PUT)
 {
     const double X = fma(x, VC(0), fma(y, VC(3), VC(6)));
@@ -133,10 +140,17 @@ __device__ __forceinline__ void corner_geometry(double x, double y, double ou, d
     // w_b: -A (x e_k0 + y e_k1),  e = R_c dR_b/dw_k columns
 #pragma unroll
     for (int kk = 0; kk < 3; ++kk) {
-        const double h0 = x * VC(9 + 6 * kk) + y * VC(12 + 6 * kk);
-        const double h1 = x * VC(10 + 6 * kk) + y * VC(13 + 6 * kk);
-        const double h2 = x * VC(11 + 6 * kk) + y * VC(14 + 6 * kk);
-        PUT(gcWb0 + kk, n00 * h0 + n01 * h1 + n02 * h2, n10 * h0 + n11 * h1 + n12 * h2);
+        if constexpr (PIN_WB) {
+            const double h0 = fma(x, VC(9 + 6 * kk), y * VC(12 + 6 * kk));
+            const double h1 = fma(x, VC(10 + 6 * kk), y * VC(13 + 6 * kk));
+            const double h2 = fma(x, VC(11 + 6 * kk), y * VC(14 + 6 * kk));
+            PUT(gcWb0 + kk, fma(n02, h2, fma(n01, h1, n00 * h0)), fma(n12, h2, fma(n10, h0, n11 * h1)));
+        } else {
+            const double h0 = x * VC(9 + 6 * kk) + y * VC(12 + 6 * kk);
+            const double h1 = x * VC(10 + 6 * kk) + y * VC(13 + 6 * kk);
+            const double h2 = x * VC(11 + 6 * kk) + y * VC(14 + 6 * kk);
+            PUT(gcWb0 + kk, n00 * h0 + n01 * h1 + n02 * h2, n10 * h0 + n11 * h1 + n12 * h2);
+        }
     }
     // w_c: -A (dR_c/dw_k P_w) = a_k . (Q' x n)
     if constexpr (WC) {
@@ -197,12 +211,18 @@ __device__ __forceinline__ void corner_residual(double x, double y, double ou, d
 // instantiations get these values as a kernel argument (wave-uniform: scalar registers).
 enum { kLossNone = 0, kLossHuber = 1, kLossSoftL1 = 2, kLossCauchy = 3 };
 struct LossArg { double a, b, c; int kind, pad; };
-// rho(s) and w = sqrt(rho'(s)), rho' clamped from below as Ceres clamps it (std::numeric_limits<double>::min())
-__device__ __forceinline__ void robust_rho(const LossArg &L, double s, double &rho, double &w)
+// rho(s) and w = sqrt(rho'(s)), rho' clamped from below as Ceres clamps it (std::numeric_limits<double>::min()).
+// WEIGHTED (corner weights, DESIGN 27: Ceres' ScaledLoss): the corner's weight omega >= 0 scales both, rho = omega rho(s) and
+// w = sqrt(omega rho'(s)) -- the product formed behind the clamp and before the one sqrt, so omega = 0 gives w = 0 exactly --
+// and kind kLossNone is rho(s) = s, rho' = 1 (weights without a loss).  The instantiations without weights never see that kind.
+template <bool WEIGHTED = false>
+__device__ __forceinline__ void robust_rho(const LossArg &L, double s, double &rho, double &w, double omega = 1.0)
 {
     constexpr double kMin = 2.2250738585072014e-308;
     double r1;
-    if (L.kind == kLossHuber) {
+    if (WEIGHTED && L.kind == kLossNone) {
+        rho = s; r1 = 1.0;
+    } else if (L.kind == kLossHuber) {
         if (s > L.b) { const double r = sqrt(s); rho = 2.0 * L.a * r - L.b; r1 = fmax(kMin, L.a / r); }
         else { rho = s; r1 = 1.0; }
     } else if (L.kind == kLossSoftL1) {
@@ -212,5 +232,6 @@ __device__ __forceinline__ void robust_rho(const LossArg &L, double s, double &r
         const double sum = 1.0 + s * L.c, inv = 1.0 / sum;
         rho = L.b * log(sum); r1 = fmax(kMin, inv);
     }
+    if constexpr (WEIGHTED) { rho *= omega; r1 *= omega; }
     w = sqrt(r1);
 }

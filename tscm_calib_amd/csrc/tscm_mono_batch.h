@@ -33,7 +33,8 @@ constexpr int kMbJw = 14;           // LDS columns of a Jacobian row: E (6), F (
 struct MbDev {
     int K, n_points, n_chunks, n_slots;
     const double *board_xy, *obs_u, *obs_v;
-    const int4 *chunk;                      // [n_chunks] problem, first slot, end slot
+    const double *obs_w;                    // corner weights in the order of obs_u / obs_v, NULL = none
+    const int4 *chunk;                     // [n_chunks] problem, first slot, end slot
     const int *chunk_ptr, *board_ptr;       // [K + 1]
     const int *slot_board, *slot_obs, *slot_count;
     const unsigned char *slot_active;
@@ -165,7 +166,9 @@ __global__ __launch_bounds__(kMbThreads) void k_mb_eval(MbDev D, int init)
             corner_residual_jacobian(vc, D.board_xy[2 * j], D.board_xy[2 * j + 1], D.obs_u[o0 + j], D.obs_v[o0 + j], r, JE, JF);
             const double sq = r[0] * r[0] + r[1] * r[1];
             double w = 1.0, rh = sq;
-            if (robust) robust_rho(D.loss, sq, rh, w);
+            // (corner weights: rho = omega rho(s), w = sqrt(omega rho'); a problem of the batch without weights has omega = 1)
+            if (D.obs_w) robust_rho<true>(D.loss, sq, rh, w, D.obs_w[o0 + j]);
+            else if (robust) robust_rho(D.loss, sq, rh, w);
             rho[j] = rh;
             for (int row = 0; row < 2; ++row) {
                 double *Jr = J + (2 * j + row) * kMbJw;

@@ -28,6 +28,8 @@ __global__ void k_eval_functor(DevProblem P, DevState S, const int *corner_view,
 
 // multi_calib.cpp:233-283: per-view sums of Euclidean pixel error and squared error, with
 // cv::Rodrigues matrices and the skew projection.  one wave per view.
+// WEIGHTED (a solve with corner weights and a loss: summary.rmse): both sums carry the corner's weight P.obs_w.
+template <bool WEIGHTED = false>
 __global__ __launch_bounds__(64) void k_reproj_error(DevProblem P, const double *cam_rt, const double *intr,
                                                     const double *board_rt, double *view_err, double *view_sq)
 {
@@ -48,7 +50,8 @@ __global__ __launch_bounds__(64) void k_reproj_error(DevProblem P, const double 
         double u, v;
         project_point(I, Pc[0], Pc[1], Pc[2], u, v);
         const double du = P.obs_u[P.view_obs[view] + j] - u, dv = P.obs_v[P.view_obs[view] + j] - v;
-        e += sqrt(du * du + dv * dv); sq += du * du + dv * dv;
+        if constexpr (WEIGHTED) { const double om = P.obs_w[P.view_obs[view] + j]; e += om * sqrt(du * du + dv * dv); sq += om * (du * du + dv * dv); }
+        else { e += sqrt(du * du + dv * dv); sq += du * du + dv * dv; }
     }
     for (int s = 32; s > 0; s >>= 1) { e += __shfl_xor(e, s); sq += __shfl_xor(sq, s); }
     if (lane == 0) { view_err[view] = e; view_sq[view] = sq; }

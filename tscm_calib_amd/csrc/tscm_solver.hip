@@ -126,6 +126,33 @@ static EvalKernel f32_kernel_of(int ks, bool multi)     // the fp32-Jacobian tie
     return (multi ? passes : single)[ks - 1];
 }
 static EvalKernel f32_kernel(int ks, bool multi, bool robust) { return robust ? f32_kernel_of<true>(ks, multi) : f32_kernel_of<false>(ks, multi); }
+// ... and with corner weights (WEIGHTED: DESIGN 27), with or without a loss
+static EvalKernel g4_weighted_kernel(int ks, bool multi)
+{
+    static const EvalKernel single[kG4MaxKS] = {
+        k_eval_gram4_weighted<1, false>, k_eval_gram4_weighted<2, false>, k_eval_gram4_weighted<3, false>, k_eval_gram4_weighted<4, false>,
+        k_eval_gram4_weighted<5, false>, k_eval_gram4_weighted<6, false>, k_eval_gram4_weighted<7, false>, k_eval_gram4_weighted<8, false>,
+        k_eval_gram4_weighted<9, false>, k_eval_gram4_weighted<10, false>, k_eval_gram4_weighted<11, false>, k_eval_gram4_weighted<12, false>,
+        k_eval_gram4_weighted<13, false>, k_eval_gram4_weighted<14, false> };
+    static const EvalKernel passes[kG4MaxKS] = {
+        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram4_weighted<8, true>, k_eval_gram4_weighted<9, true>,
+        k_eval_gram4_weighted<10, true>, k_eval_gram4_weighted<11, true>, k_eval_gram4_weighted<12, true>, k_eval_gram4_weighted<13, true>,
+        k_eval_gram4_weighted<14, true> };
+    return (multi ? passes : single)[ks - 1];
+}
+static EvalKernel f32_weighted_kernel(int ks, bool multi)
+{
+    static const EvalKernel single[kG4MaxKS] = {
+        k_eval_gram_f32_weighted<1, false>, k_eval_gram_f32_weighted<2, false>, k_eval_gram_f32_weighted<3, false>, k_eval_gram_f32_weighted<4, false>,
+        k_eval_gram_f32_weighted<5, false>, k_eval_gram_f32_weighted<6, false>, k_eval_gram_f32_weighted<7, false>, k_eval_gram_f32_weighted<8, false>,
+        k_eval_gram_f32_weighted<9, false>, k_eval_gram_f32_weighted<10, false>, k_eval_gram_f32_weighted<11, false>, k_eval_gram_f32_weighted<12, false>,
+        k_eval_gram_f32_weighted<13, false>, k_eval_gram_f32_weighted<14, false> };
+    static const EvalKernel passes[kG4MaxKS] = {
+        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram_f32_weighted<8, true>, k_eval_gram_f32_weighted<9, true>,
+        k_eval_gram_f32_weighted<10, true>, k_eval_gram_f32_weighted<11, true>, k_eval_gram_f32_weighted<12, true>, k_eval_gram_f32_weighted<13, true>,
+        k_eval_gram_f32_weighted<14, true> };
+    return (multi ? passes : single)[ks - 1];
+}
 
 struct tscm_solver {
     int device = 0;
@@ -166,6 +193,15 @@ struct tscm_solver {
     EvalKernel eval4 = nullptr, eval32 = nullptr;   // ... and its instantiation for this problem's board (g4_kernel), the fp32-Jacobian tier's (f32_kernel)
     EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
     LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs eval4 / eval32
+    // corner weights (tscm_solver_set_corner_weights): with weights every evaluation runs eval4w / eval32w (WEIGHTED),
+    // whatever the loss; P.obs_w is d_obs_w then and NULL otherwise
+    EvalKernel eval4w = nullptr, eval32w = nullptr;
+    bool weighted = false;
+    double *d_obs_w = nullptr;          // [N] weights in the device's corner order (allocated by the first call with weights)
+    std::vector<double> h_obs_u, h_obs_v;   // the observations as created, in that order: a masked corner's device copy is 0, 0 while it is masked
+    std::vector<int> p_view_count;      // view_count of the caller's WHOLE problem (the weights' corner order)
+    double w_sum = 0.0;                 // sum of the weights and number of corners with a weight > 0, of the WHOLE job
+    long n_kept = 0;
     // held intrinsics (tscm_solver_set_fixed_intrinsics): the mask word of every camera (the whole-problem facts the
     // free columns are derived from are L.cam_const, L.cam_active, L.pair_present: plan_columns)
     std::vector<unsigned short> fixed;
@@ -259,6 +295,71 @@ extern "C" int tscm_solver_set_loss(tscm_solver *s, int kind, double scale)
     if (int rc = make_loss(kind, scale, L)) return rc;
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
     s->loss = L;
+    return 0;
+}
+
+// corner weights [sum of view_count] in the problem's corner order (views in problem order, corners in order): checked before any
+// device is touched.  sum / kept: the sum of the weights and the number of corners with a weight > 0
+static int check_corner_weights(const int *view_count, int n_views, const double *w, double *sum = nullptr, long *kept = nullptr)
+{
+    double sm = 0.0;
+    long k = 0, n = 0;
+    for (int v = 0; v < n_views; ++v) {
+        bool any = false;
+        for (int j = 0; j < view_count[v]; ++j, ++n) {
+            const double x = w[n];
+            if (!std::isfinite(x) || x < 0.0)
+                return fail(TSCM_E_INVALID, "corner weight " + std::to_string(n) + " (view " + std::to_string(v) + ", corner " + std::to_string(j) + ") is negative, NaN or infinite");
+            if (x > 0.0) { any = true; ++k; sm += x; }
+        }
+        if (view_count[v] > 0 && !any)
+            return fail(TSCM_E_INVALID, "every corner weight of view " + std::to_string(v) + " is 0: pass view_count = 0 for a view without corners");
+    }
+    if (sum) *sum = sm;
+    if (kept) *kept = k;
+    return 0;
+}
+
+extern "C" int tscm_solver_set_corner_weights(tscm_solver *s, const double *weights)
+{
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    const size_t N = (size_t)s->N;
+    if (!weights) {
+        if (!s->weighted) return 0;
+        // the observations as created: the solve without weights, bit for bit
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (N) {
+            HIP_TRY(hipMemcpy(const_cast<double *>(s->P.obs_u), s->h_obs_u.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(const_cast<double *>(s->P.obs_v), s->h_obs_v.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+        }
+        s->weighted = false; s->P.obs_w = nullptr; s->w_sum = 0.0; s->n_kept = 0;
+        return 0;
+    }
+    double sum = 0.0;
+    long kept = 0;
+    if (int rc = check_corner_weights(s->p_view_count.data(), (int)s->p_view_count.size(), weights, &sum, &kept)) return rc;
+    // this rank's part, in the device's corner order; a masked corner's observation is 0, 0 there (it may hold anything, NaN included)
+    std::vector<long> first(s->p_view_count.size(), 0);
+    { long k = 0; for (size_t v = 0; v < first.size(); ++v) { first[v] = k; k += s->p_view_count[v]; } }
+    std::vector<double> w(N), u(s->h_obs_u), q(s->h_obs_v);
+    for (int i = 0; i < s->V; ++i) {
+        const double *src = weights + first[s->L.dev2orig[i]];
+        for (int j = 0; j < s->L.view_count[i]; ++j) {
+            const size_t k = (size_t)s->L.view_obs[i] + j;
+            w[k] = src[j];
+            if (!(src[j] > 0.0)) { u[k] = 0.0; q[k] = 0.0; }
+        }
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (!s->d_obs_w) HIP_TRY(s->mem.alloc(&s->d_obs_w, std::max<size_t>(N, 1)));
+    if (N) {
+        HIP_TRY(hipMemcpy(s->d_obs_w, w.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(const_cast<double *>(s->P.obs_u), u.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(const_cast<double *>(s->P.obs_v), q.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+    }
+    s->weighted = true; s->P.obs_w = s->d_obs_w; s->w_sum = sum; s->n_kept = kept;
     return 0;
 }
 
@@ -391,10 +492,11 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     // the default Gram kernel: k_eval_gram4 instantiated for this board's pass plan (KS k-steps per pass, ceil(n / 56) passes per view)
     const G4Plan g4 = g4_plan(p->n_points);
     const EvalKernel eval4 = g4_kernel(g4.ks, g4.passes > 1, false), eval4r = g4_kernel(g4.ks, g4.passes > 1, true);
+    const EvalKernel eval4w = g4_weighted_kernel(g4.ks, g4.passes > 1);
     const size_t lds_eval4 = 4 * sizeof(double) * (size_t)eval_gram4_lds_doubles(p->n_points, g4.ks);
     if (lds_eval4 > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board with too many corners for the Gram kernel's LDS (more than about 2,000)");
     if (lds_eval4 > 64 * 1024)
-        for (EvalKernel k : { eval4, eval4r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
+        for (EvalKernel k : { eval4, eval4r, eval4w }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
     // the Gram kernels' view chunks are sized for one round of resident waves: LayoutDevice
     int wgs_per_cu = 0;         // resident workgroups per CU (register- and LDS-limited)
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, reinterpret_cast<const void *>(eval4), 256, lds_eval4));
@@ -458,6 +560,8 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     up(&P.board_xy, bxy);
     up(&P.view_cam, L.view_cam); up(&P.view_board, L.view_board); up(&P.view_obs, L.view_obs); up(&P.view_count, L.view_count);
     up(&P.obs_u, u); up(&P.obs_v, w);
+    s->h_obs_u.swap(u); s->h_obs_v.swap(w);
+    s->p_view_count.assign(p->view_count, p->view_count + p->n_views);
     up(&P.chunk_vb, L.chunk_vb); up(&P.chunk_ve, L.chunk_ve); up(&P.chunk_cam, L.chunk_cam); up(&P.chunk_desc, chunk_desc);
     up(&P.cam_chunk_ptr, L.cam_chunk_ptr);
     up(&P.bv_ptr, L.bv_ptr); up(&P.view_slot, L.view_slot); up(&P.slot_cam, L.slot_cam); up(&P.slot_view, L.slot_view); up(&P.slot_board, L.slot_board);
@@ -507,10 +611,11 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     // ---- the evaluation and solve variants -------------------------------------------------------
     s->lds_eval = 4 * lds_eval_bytes;
     s->lds_eval32 = sizeof(double) * (size_t)eval_f32_lds_doubles(p->n_points, g4.ks);
-    s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval4r = eval4r;
+    s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval4r = eval4r; s->eval4w = eval4w;
     s->eval32 = f32_kernel(g4.ks, g4.passes > 1, false); s->eval32r = f32_kernel(g4.ks, g4.passes > 1, true);
+    s->eval32w = f32_weighted_kernel(g4.ks, g4.passes > 1);
     if (s->lds_eval32 > 64 * 1024)
-        for (EvalKernel k : { s->eval32, s->eval32r }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
+        for (EvalKernel k : { s->eval32, s->eval32r, s->eval32w }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
     // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory.
     // The columns of the creation plan (no held intrinsics) are every camera-side column that can be free: held intrinsics
     // only ever take columns away, so the sizes below hold for every mask
@@ -671,10 +776,11 @@ static int launch_eval(tscm_solver *s, int cand)
     if (int rc = timed_pair(s, 0, &e0, &e1)) return rc;
     const dim3 grid(P.n_chunks / 4);
     // (a loss: the ROBUST instantiation; the 16x16 kernel has none -- refused before anything is launched)
-    const bool robust = s->xp.robust;
-    if (s->xp.gram == Gram::F32) launch_eval_kernel(robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
+    // (corner weights: the WEIGHTED instantiation, with or without a loss; refused with the 16x16 kernel like a loss)
+    const bool robust = s->xp.robust, wt = s->weighted;
+    if (s->xp.gram == Gram::F32) launch_eval_kernel(wt ? s->eval32w : robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
     else if (s->xp.gram == Gram::G4)
-        launch_eval_kernel(robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand | (s->xp.skip_const_pose ? kEvalSkipConst : 0), s->loss);
+        launch_eval_kernel(wt ? s->eval4w : robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand | (s->xp.skip_const_pose ? kEvalSkipConst : 0), s->loss);
     else if (s->xp.gram == Gram::G16Pitch58) launch_eval_kernel(k_eval_gram<58>, grid, s->lds_eval, s, e0, e1, cand);
     else launch_eval_kernel(k_eval_gram<0>, grid, s->lds_eval, s, e0, e1, cand);
     return 0;
@@ -990,7 +1096,13 @@ static int read_options(const tscm_options *opt_in, int mono, tscm_options &opt)
     }
     return 0;
 }
-static int check_options(const tscm_options &opt, int loss_kind) { std::string err; const int rc = check_exec_options(opt, loss_kind, err); return rc ? fail(rc, err) : 0; }
+static int check_options(const tscm_options &opt, int loss_kind, bool weighted = false)
+{
+    std::string err;
+    if (const int rc = check_exec_options(opt, loss_kind, err)) return fail(rc, err);
+    if (weighted && (opt.exec_flags & TSCM_EXEC_GRAM_16X16)) return fail(TSCM_E_UNSUPPORTED, "TSCM_EXEC_GRAM_16X16 has no corner-weight kernel");
+    return 0;
+}
 
 // Waits for the solver's stream.  With a multi-rank RCCL communicator a peer that has failed (or died) leaves this
 // rank's all-reduce kernel spinning for ever -- over the intra-node transports an ncclCommAbort on the FAILING rank does
@@ -1059,7 +1171,9 @@ static int accepted_sq(tscm_solver *s, double &sq)
     sq = 0.0;
     if (!s->V) return 0;
     if (!s->d_view_sq) HIP_TRY(s->mem.alloc(&s->d_view_sq, 2 * (size_t)s->V));
-    hipLaunchKernelGGL(k_reproj_error, dim3(s->V), dim3(64), 0, s->stream, s->P, s->S.cam_rt[0], s->S.intr[0], s->S.board_rt[0], s->d_view_sq, s->d_view_sq + s->V);
+    // (corner weights: sum omega s, the weighted variant of the launch)
+    if (s->weighted) hipLaunchKernelGGL(k_reproj_error<true>, dim3(s->V), dim3(64), 0, s->stream, s->P, s->S.cam_rt[0], s->S.intr[0], s->S.board_rt[0], s->d_view_sq, s->d_view_sq + s->V);
+    else hipLaunchKernelGGL(k_reproj_error<false>, dim3(s->V), dim3(64), 0, s->stream, s->P, s->S.cam_rt[0], s->S.intr[0], s->S.board_rt[0], s->d_view_sq, s->d_view_sq + s->V);
     std::vector<double> q(s->V);
     HIP_TRY(hipMemcpyAsync(q.data(), s->d_view_sq + s->V, sizeof(double) * s->V, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1088,7 +1202,11 @@ static int robust_rmse(LmRun &run, tscm_summary *sums)
         HIP_TRY(hipStreamSynchronize(s0->stream));
         if (int rc = comm_check(s0->comm)) return rc;
     }
-    for (size_t r = 0; r < run.m.size(); ++r) sums[r].rmse = run.m[r]->L.N_total ? std::sqrt(sq / (double)run.m[r]->L.N_total) : 0.0;
+    for (size_t r = 0; r < run.m.size(); ++r) {
+        // (corner weights: sum omega s over sum omega)
+        const double den = run.m[r]->weighted ? run.m[r]->w_sum : (double)run.m[r]->L.N_total;
+        sums[r].rmse = den > 0.0 ? std::sqrt(sq / den) : 0.0;
+    }
     return 0;
 }
 
@@ -1098,8 +1216,9 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     for (tscm_solver *s : run.m) if (!s->have_init) return fail(TSCM_E_INVALID, "tscm_solver_upload_params has not been called");
     tscm_options opt;
     if (int rc = read_options(opt_in, s0->mono, opt)) return rc;
-    if (int rc = check_options(opt, s0->loss.kind)) return rc;
+    if (int rc = check_options(opt, s0->loss.kind, s0->weighted)) return rc;
     for (tscm_solver *s : run.m) if (!same_loss(s->loss, s0->loss)) return fail(TSCM_E_INVALID, "the solvers of a group carry different losses (tscm_solver_set_loss)");
+    for (tscm_solver *s : run.m) if (s->weighted != s0->weighted) return fail(TSCM_E_INVALID, "the solvers of a group must all have corner weights or all have none (tscm_solver_set_corner_weights)");
     for (tscm_solver *s : run.m) if (s->fixed != s0->fixed) return fail(TSCM_E_INVALID, "the solvers of a group hold different intrinsics (tscm_solver_set_fixed_intrinsics)");
     HIP_TRY(hipSetDevice(s0->device));
     LmRunGuard guard{ run };
@@ -1159,6 +1278,12 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         if (h->fault) { *late_handoff = true; return fail(TSCM_E_HIP, "a device-side hand-off (Schur-complement tiles -> reduced solve) did not arrive within its time bound: the solve was stopped"); }
         if (!h->done) return fail(TSCM_E_HIP, "device LM loop did not terminate");
         fill_summary(*h, h->log, (long)s->L.N_total, sum);                // cost and N of the WHOLE job
+        if (s->weighted) {
+            // corner weights: the blocks are the corners with a weight > 0, and rmse = sqrt(sum omega s / sum omega) -- without a loss
+            // the cost is sum omega s / 2
+            sum->n_residual_blocks = (int)s->n_kept;
+            sum->rmse = s->w_sum > 0.0 ? std::sqrt(2.0 * h->x_cost / s->w_sum) : 0.0;
+        }
         sum->seconds_solve = 1e-8 * (double)(h->t_end - h->t_begin);      // on the device: first to last kernel of the solve
         sum->seconds_total = t1 - t0;                                     // wall time of the call
     }
@@ -1246,15 +1371,39 @@ extern "C" int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_s
     return 0;
 }
 
-static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{}, const unsigned short *fixed = nullptr)
+// the weights of a one-shot entry point, before its solver is created: the problem's and their own refusals
+static int precheck_weights(const tscm_problem *p, const double *weights)
 {
+    if (!weights) return 0;
+    if (int rc = validate(p)) return rc;
+    return check_corner_weights(p->view_count, p->n_views, weights);
+}
+
+static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{}, const unsigned short *fixed = nullptr,
+                      const double *weights = nullptr)
+{
+    if (int rc = precheck_weights(p, weights)) return rc;
     int dev = 0;
     (void)hipGetDevice(&dev);
     SolverPtr sp;
     if (int rc = create_scoped(p, dev, sp)) return rc;
     sp->loss = loss;
     if (fixed) if (int rc = tscm_solver_set_fixed_intrinsics(sp.get(), fixed)) return rc;
+    if (weights) if (int rc = tscm_solver_set_corner_weights(sp.get(), weights)) return rc;
     return tscm_solver_solve(sp.get(), opt, sum);
+}
+
+extern "C" int tscm_solve_weighted(const tscm_problem *p, const tscm_options *opt, const double *weights, const unsigned short *fixed, int kind, double scale,
+                                   tscm_summary *sum)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
+    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
+    tscm_options o;
+    if (int rc = read_options(opt, p->mono, o)) return rc;
+    if (int rc = check_options(o, L.kind, weights != nullptr)) return rc;
+    return solve_once(p, opt, sum, L, fixed, weights);
 }
 
 extern "C" int tscm_solve_multi(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum)
@@ -1297,20 +1446,22 @@ extern "C" int tscm_solve_fixed(const tscm_problem *p, const tscm_options *opt, 
 // (ctrl->cur = 0 at the start); k_end_solve / k_finish_solve copy it into buffer 0 only if the step was accepted and never
 // write buffer 1, so buffer 1 holds the candidate whether the step was accepted or not
 static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *cam_rt, double *intr,
-                     double *board_rt, int *valid, tscm_summary *summary, const unsigned short *fixed = nullptr)
+                     double *board_rt, int *valid, tscm_summary *summary, const unsigned short *fixed = nullptr, const double *weights = nullptr)
 {
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
     opt.max_num_iterations = 1;
     opt.function_tolerance = opt.gradient_tolerance = opt.parameter_tolerance = 0.0;
-    if ((rc = check_options(opt, loss.kind))) return rc;
+    if ((rc = check_options(opt, loss.kind, weights != nullptr))) return rc;
     if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
+    if ((rc = precheck_weights(p, weights))) return rc;
     SolverPtr sp;
     if ((rc = create_scoped(p, device, sp))) return rc;
     tscm_solver *s = sp.get();
     s->loss = loss;
     if (fixed && (rc = tscm_solver_set_fixed_intrinsics(s, fixed))) return rc;
+    if (weights && (rc = tscm_solver_set_corner_weights(s, weights))) return rc;
     if ((rc = tscm_solver_upload_params(s, p->cam_rt, p->intr, p->board_rt))) return rc;
     tscm_summary sum;
     if ((rc = tscm_solver_solve_resident(s, &opt, &sum, 1))) return rc;
@@ -1345,6 +1496,16 @@ extern "C" int tscm_eval_step_fixed(const tscm_problem *p, int device, const tsc
     if (!p) return fail(TSCM_E_INVALID, "NULL argument");
     if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
     return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary, fixed);
+}
+
+extern "C" int tscm_eval_step_weighted(const tscm_problem *p, int device, const tscm_options *opt, const double *weights, const unsigned short *fixed,
+                                       int kind, double scale, double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    if (!p) return fail(TSCM_E_INVALID, "NULL argument");
+    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
+    return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary, fixed, weights);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1472,16 +1633,18 @@ static int solver_normal_equations(tscm_solver *s, const tscm_options &opt, bool
 }
 
 static int eval_normal_equations(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *board_gram,
-                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
+                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost, const double *weights = nullptr)
 {
     tscm_options opt;
     int rc = read_options(opt_in, p ? p->mono : 0, opt);
     if (rc) return rc;
     opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
-    if ((rc = check_options(opt, loss.kind))) return rc;
+    if ((rc = check_options(opt, loss.kind, weights != nullptr))) return rc;
+    if ((rc = precheck_weights(p, weights))) return rc;
     SolverPtr sp;
     if ((rc = create_scoped(p, device, sp))) return rc;
     sp->loss = loss;
+    if (weights && (rc = tscm_solver_set_corner_weights(sp.get(), weights))) return rc;
     return solver_normal_equations(sp.get(), opt, false, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
 }
 
@@ -1494,7 +1657,7 @@ extern "C" int tscm_solver_eval_normal_equations(tscm_solver *s, const tscm_opti
     int rc = read_options(opt_in, s->mono ? 1 : 0, opt);
     if (rc) return rc;
     opt.max_num_iterations = 0;
-    if ((rc = check_options(opt, s->loss.kind))) return rc;
+    if ((rc = check_options(opt, s->loss.kind, s->weighted))) return rc;
     HIP_TRY(hipSetDevice(s->device));
     rc = solver_normal_equations(s, opt, as_solved != 0, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
     s->xp = ExecPlan{};                 // (per solve: planned again from the options of the next one)
@@ -1514,6 +1677,15 @@ extern "C" int tscm_eval_normal_equations_robust(const tscm_problem *p, int devi
     LossArg L;
     if (int rc = make_loss(kind, scale, L)) return rc;
     return eval_normal_equations(p, device, opt, L, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+}
+
+extern "C" int tscm_eval_normal_equations_weighted(const tscm_problem *p, int device, const tscm_options *opt, const double *weights, int kind,
+                                                   double scale, double *board_gram, double *board_grad, double *view_cross, double *cam_gram,
+                                                   double *cam_grad, double *cost)
+{
+    LossArg L;
+    if (int rc = make_loss(kind, scale, L)) return rc;
+    return eval_normal_equations(p, device, opt, L, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost, weights);
 }
 
 
@@ -1555,7 +1727,7 @@ extern "C" int tscm_reprojection_error(const tscm_problem *p, int device, double
     double *d_e = nullptr, *d_q = nullptr;
     HIP_TRY(s->mem.alloc(&d_e, (size_t)s->V));
     HIP_TRY(s->mem.alloc(&d_q, (size_t)s->V));
-    if (s->V) hipLaunchKernelGGL(k_reproj_error, dim3(s->V), dim3(64), 0, s->stream, s->P, s->d_init_cam, s->d_init_intr, s->d_init_board, d_e, d_q);
+    if (s->V) hipLaunchKernelGGL(k_reproj_error<false>, dim3(s->V), dim3(64), 0, s->stream, s->P, s->d_init_cam, s->d_init_intr, s->d_init_board, d_e, d_q);
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipGetLastError());
     std::vector<double> e(s->V), q(s->V);
@@ -1580,12 +1752,13 @@ struct MbStream {
     ~MbStream() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (s) (void)hipStreamDestroy(s); }
 };
 
-// plain pixel RMSE of one problem at its parameters (a robust solve's summary.rmse, as tscm_reprojection_error computes it)
-static double mb_pixel_rmse(const tscm_problem &p)
+// plain pixel RMSE of one problem at its parameters (a robust solve's summary.rmse, as tscm_reprojection_error computes it);
+// w: the problem's corner weights or NULL -- sqrt(sum omega s / sum omega), a corner with omega = 0 is not read
+static double mb_pixel_rmse(const tscm_problem &p, const double *w = nullptr)
 {
     ViewConst vc;
     mono_view_const(p.intr, vc);
-    double sq = 0.0;
+    double sq = 0.0, wsum = 0.0;
     long n = 0;
     for (int v = 0; v < p.n_views; ++v) {
         if (p.view_count[v] <= 0) continue;
@@ -1597,16 +1770,20 @@ static double mb_pixel_rmse(const tscm_problem &p)
         for (int j = 0; j < p.view_count[v]; ++j) {
             double r[2], JE[2][kE], JF[2][kFA];
             const int o = p.view_offset[v] + j;
+            if (w && !(w[n + j] > 0.0)) continue;
             corner_residual_jacobian(vc, p.board_xy[2 * j], p.board_xy[2 * j + 1], p.obs_u[o], p.obs_v[o], r, JE, JF);
-            sq += r[0] * r[0] + r[1] * r[1];
+            if (w) { sq += w[n + j] * (r[0] * r[0] + r[1] * r[1]); wsum += w[n + j]; }
+            else sq += r[0] * r[0] + r[1] * r[1];
         }
         n += p.view_count[v];
     }
+    if (w) return wsum > 0.0 ? std::sqrt(sq / wsum) : 0.0;
     return n ? std::sqrt(sq / (double)n) : 0.0;
 }
 
-extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in,
-                                     const unsigned short *fixed, int loss_kind, double loss_scale, tscm_summary *summaries)
+// weights: [n_problems] pointers to the problems' corner weights (entries may be NULL), or NULL for none
+static int solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in, const unsigned short *fixed,
+                            const double *const *weights, int loss_kind, double loss_scale, tscm_summary *summaries)
 {
     const double t_call = wall();
     if (!summaries) return fail(TSCM_E_INVALID, "summaries is NULL");
@@ -1619,6 +1796,16 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
     }
     LossArg loss;
     if (int rc = make_loss(loss_kind, loss_scale, loss)) return rc;
+    // corner weights: checked per problem before any device is touched; w_sum / n_kept of each for its summary
+    bool any_w = false;
+    std::vector<double> w_sum(n_problems, 0.0);
+    std::vector<long> n_kept(n_problems, 0);
+    for (int i = 0; weights && i < n_problems; ++i) {
+        if (!weights[i]) continue;
+        if (int rc = check_corner_weights(problems[i].view_count, problems[i].n_views, weights[i], &w_sum[i], &n_kept[i]))
+            return fail(rc, "problem " + std::to_string(i) + ": " + g_err);
+        any_w = true;
+    }
     if (int rc = select_device(device, "tscm_solve_mono_batch")) return rc;
     for (int i = 0; i < n_problems; ++i) std::memset(&summaries[i], 0, sizeof(tscm_summary));
 
@@ -1631,6 +1818,23 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
             const tscm_problem &p = problems[bp.dev_prob[bp.slot_prob[s]]];
             const int v = bp.slot_view[s];
             for (int j = 0; j < bp.slot_count[s]; ++j) { ou[bp.slot_obs[s] + j] = p.obs_u[p.view_offset[v] + j]; ov[bp.slot_obs[s] + j] = p.obs_v[p.view_offset[v] + j]; }
+        }
+        // the weights in slot order (a problem without weights: 1); a masked corner's observation is uploaded as 0, 0
+        std::vector<double> ow(any_w ? (size_t)bp.N : 0, 1.0);
+        std::vector<std::vector<long> > first(any_w ? n_problems : 0);      // per weighted problem: view -> its first corner in corner order
+        for (int i = 0; any_w && i < n_problems; ++i) {
+            if (!weights[i]) continue;
+            first[i].assign((size_t)problems[i].n_views + 1, 0);
+            for (int v = 0; v < problems[i].n_views; ++v) first[i][v + 1] = first[i][v] + problems[i].view_count[v];
+        }
+        for (int s = 0; any_w && s < ns; ++s) {
+            const int i = bp.dev_prob[bp.slot_prob[s]];
+            if (!weights[i]) continue;
+            for (int j = 0; j < bp.slot_count[s]; ++j) {
+                const double x = weights[i][first[i][bp.slot_view[s]] + j];
+                ow[bp.slot_obs[s] + j] = x;
+                if (!(x > 0.0)) { ou[bp.slot_obs[s] + j] = 0.0; ov[bp.slot_obs[s] + j] = 0.0; }
+            }
         }
         for (int k = 0; k < K; ++k) {
             const tscm_problem &p = problems[bp.dev_prob[k]];
@@ -1647,6 +1851,7 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
         const size_t ctrl_bytes = sizeof(CtrlHead) * (size_t)K + sizeof(IterLog) * (size_t)kMaxLog * K;
         HIP_TRY(A.upload(&D.board_xy, problems[0].board_xy, 2 * (size_t)bp.n_points));
         HIP_TRY(A.upload(&D.obs_u, ou)); HIP_TRY(A.upload(&D.obs_v, ov));
+        if (any_w) HIP_TRY(A.upload(&D.obs_w, ow));
         HIP_TRY(A.upload(&D.chunk, chunk));
         HIP_TRY(A.upload(&D.chunk_ptr, bp.chunk_ptr)); HIP_TRY(A.upload(&D.board_ptr, bp.board_ptr));      // [K + 1]
         HIP_TRY(A.upload(&D.slot_board, bp.slot_board)); HIP_TRY(A.upload(&D.slot_obs, bp.slot_obs));      // [ns]
@@ -1713,7 +1918,12 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
             if (p.n_boards) std::memcpy(p.board_rt, &out[9 * (size_t)K + 6 * (size_t)bp.board_ptr[k]], 6 * sizeof(double) * p.n_boards);
             const long N_k = bp.obs_ptr[k + 1] - bp.obs_ptr[k];
             fill_summary(h, logs + (size_t)kMaxLog * k, N_k, sum);
-            if (loss.kind != TSCM_LOSS_NONE) sum->rmse = mb_pixel_rmse(p);
+            const double *w = weights ? weights[i] : nullptr;
+            if (w) {
+                sum->n_residual_blocks = (int)n_kept[i];
+                sum->rmse = w_sum[i] > 0.0 ? std::sqrt(2.0 * h.x_cost / w_sum[i]) : 0.0;
+            }
+            if (loss.kind != TSCM_LOSS_NONE) sum->rmse = mb_pixel_rmse(p, w);
         }
     }
     // problems without a single corner: what the single-problem entry point returns for them
@@ -1725,6 +1935,19 @@ extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problem
     const double t_end = wall();
     for (int i = 0; i < n_problems; ++i) { summaries[i].seconds_total = t_end - t_call; summaries[i].seconds_solve = seconds_solve; }
     return 0;
+}
+
+extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in,
+                                     const unsigned short *fixed, int loss_kind, double loss_scale, tscm_summary *summaries)
+{
+    return solve_mono_batch(problems, n_problems, device, opt_in, fixed, nullptr, loss_kind, loss_scale, summaries);
+}
+
+extern "C" int tscm_solve_mono_batch_weighted(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in,
+                                              const unsigned short *fixed, const double *const *weights, int loss_kind, double loss_scale,
+                                              tscm_summary *summaries)
+{
+    return solve_mono_batch(problems, n_problems, device, opt_in, fixed, weights, loss_kind, loss_scale, summaries);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -213,6 +213,8 @@ EXPORTS = [
     "tscm_solver_eval_normal_equations",
     "tscm_solver_set_fixed_intrinsics", "tscm_solve_fixed", "tscm_eval_step_fixed", "tscm_solve_mono_batch",
     "tscm_covariance", "tscm_covariance_from_normal_equations",
+    "tscm_solver_set_corner_weights", "tscm_solve_weighted", "tscm_eval_normal_equations_weighted", "tscm_eval_step_weighted",
+    "tscm_solve_mono_batch_weighted", "tscm_covariance_weighted",
     "tscm_projection_uncertainty", "tscm_projection_uncertainty_seconds",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
@@ -302,6 +304,13 @@ def lib():
     L.tscm_covariance.argtypes = [C.POINTER(CProblem), C.c_int, usp, C.c_int, C.c_double, dp, dp, dp, dp, dp, cip]
     L.tscm_covariance_from_normal_equations.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_int,
                                                         dp, dp, cip]
+    L.tscm_solver_set_corner_weights.argtypes = [vp, dp]
+    L.tscm_solve_weighted.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), dp, usp, C.c_int, C.c_double, C.POINTER(CSummary)]
+    L.tscm_eval_normal_equations_weighted.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, C.c_int, C.c_double, dp, dp, dp, dp, dp, dp]
+    L.tscm_eval_step_weighted.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, usp, C.c_int, C.c_double, dp, dp, dp, ip, C.POINTER(CSummary)]
+    L.tscm_solve_mono_batch_weighted.argtypes = [C.POINTER(CProblem), C.c_int, C.c_int, C.POINTER(COptions), usp, C.POINTER(dp), C.c_int, C.c_double,
+                                                 C.POINTER(CSummary)]
+    L.tscm_covariance_weighted.argtypes = [C.POINTER(CProblem), C.c_int, usp, dp, C.c_int, C.c_double, dp, dp, dp, dp, dp, cip]
     L.tscm_projection_uncertainty.argtypes = [C.c_int, dp, dp, dp, C.c_double, C.POINTER(CUncertaintyGrid), C.POINTER(CUncertaintyRequest), C.c_int, C.c_int,
                                               dp, C.POINTER(C.c_ubyte), dp, C.POINTER(C.c_longlong)]
     L.tscm_projection_uncertainty_seconds.argtypes = []
@@ -470,6 +479,37 @@ def fixed_masks(fixed, n_cameras: int) -> np.ndarray:
     if np.any(words < 0) or np.any(words & ~FIX_ALL):
         raise ValueError("unknown bits in a fixed-intrinsics mask (bits 0-8: fx fy cx cy xi lambda alpha b c)")
     return words.astype(np.uint16)
+
+
+def corner_weights(problem, weights=None, built_count=None):
+    """The corner weights of a call, and the problem it is made on: -> (problem', w).
+    weights: None (then problem.weights), or [n_corners] in corner order -- views in order, the corners of a view in order; a
+    bool mask means 0 / 1.  w: C-contiguous float64, or None without weights (problem' is problem then).
+    A view whose weights are all 0 goes in with view_count 0, as the C ABI asks: problem' is then a copy of the description
+    that shares every array with `problem` but view_count, and w has that view's entries removed.
+    built_count (Solver.set_corner_weights): the view_count a solver of `problem` was created with.  The views it was created
+    without (count 0 there) stay out whatever their weights are now; any other view whose weights are all 0 raises ValueError."""
+    import dataclasses
+    w = problem.weights if weights is None else weights
+    if w is None:
+        return problem, None
+    w = np.ascontiguousarray(np.asarray(w), dtype=np.float64).ravel()
+    if w.size != problem.n_corners:
+        raise ValueError(f"weights: {w.size} entries for {problem.n_corners} corners (one per corner, views in order)")
+    cnt = np.asarray(problem.view_count)
+    view_of = np.repeat(np.arange(cnt.size), cnt)
+    live = np.zeros(cnt.size, dtype=bool)
+    live[view_of[w != 0.0]] = True              # (NaN counts as live: the library refuses it by name)
+    dead = (cnt > 0) & ~live
+    if built_count is not None:
+        gone = (cnt > 0) & (np.asarray(built_count) == 0)
+        if np.any(dead & ~gone):
+            raise ValueError("a view's weights are all 0: create the Solver with weights= so that the view goes in with view_count 0")
+        dead = gone
+    if not dead.any():
+        return problem, w
+    q = dataclasses.replace(problem, view_count=np.where(dead, 0, cnt).astype(np.int32), weights=None)
+    return q, np.ascontiguousarray(w[~dead[view_of]])
 
 
 def ushort_ptr(a: np.ndarray):

@@ -65,6 +65,13 @@ def _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_int
     return q, count, sel, found
 
 
+def _inlier_weights(found, sel, mask_outliers):
+    """The corner mask of a prepared camera's refinement: the RANSAC inlier mask of the kept views, or None."""
+    if not mask_outliers or found is None:
+        return None
+    return np.asarray(found["inlier"], dtype=bool)[sel].ravel()
+
+
 def _finish_camera(q, count, sel):
     """calibrate_camera behind its refinement (TS.cpp:88-102): intr[9] and Rt[V,3,3] = [r1 r2 t] from the refined problem."""
     R = synth.rodrigues(q.board_rt[:, :3])
@@ -73,7 +80,8 @@ def _finish_camera(q, count, sel):
     return q.intr[0].copy(), Rt
 
 
-def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None, ransac=None):
+def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None, ransac=None,
+                     mask_outliers=False):
     """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
     principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
     intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
@@ -84,22 +92,34 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
     ransac: None (the poses start from the least-squares fit of all corners), or rig.ransac_params(...): they start from
     rig.estimate_extrinsic_ransac, a view without a pose there (exit code outside 5..7) is left out of the refinement (its Rt
     stays 0), and summary["ransac"] = dict(inlier [V,n] bool, code [V], has [V]: the views that were kept).
+    mask_outliers (with ransac): the RANSAC inlier mask of the kept views is the corner mask of the refinement
+    (api.refinement(weights=inlier[has])): a corner the consensus set excludes is taken out instead of weighed down.  False: the
+    calls of a run without it.
     Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
     w = _model_masks(model, fixed, 1)
     q, count, sel, found = _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr, model, ransac)
-    _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
+    cw = _inlier_weights(found, sel, mask_outliers)
+    if cw is not None:
+        _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None, weights=cw)
+    else:
+        _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
     intr, Rt = _finish_camera(q, count, sel)
     if found is not None:
         summary["ransac"] = found
     return intr, Rt, summary
 
 
-def _calibrate_cameras_batched(pus, pvs, hases, cols, rows, pitch, img_sizes, device, init_intrs, loss, model, masks, ransac=None):
+def _calibrate_cameras_batched(pus, pvs, hases, cols, rows, pitch, img_sizes, device, init_intrs, loss, model, masks, ransac=None,
+                               mask_outliers=False):
     """calibrate_camera for every camera, the refinements of all of them in ONE batch (api.refinement_batch): the same
     start, poses and post-processing per camera, each camera's refinement as refinement() would return it alone."""
     prep = [_prepare_camera(pu, pv, has, cols, rows, pitch, size, device, init, model, ransac)
             for pu, pv, has, size, init in zip(pus, pvs, hases, img_sizes, init_intrs)]
-    res = api.refinement_batch([p[0] for p in prep], device, loss=loss, fixed=[int(w) for w in masks])
+    cws = [_inlier_weights(p[3], p[2], mask_outliers) for p in prep]
+    if any(cw is not None for cw in cws):
+        res = api.refinement_batch([p[0] for p in prep], device, loss=loss, fixed=[int(w) for w in masks], weights=cws)
+    else:
+        res = api.refinement_batch([p[0] for p in prep], device, loss=loss, fixed=[int(w) for w in masks])
     out = []
     for (q, count, sel, found), (_, summary) in zip(prep, res):
         if found is not None:
@@ -149,16 +169,17 @@ def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, devi
 
 
 def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                    fixed=None, ransac=None) -> dict:
+                    fixed=None, ransac=None, mask_outliers=False) -> dict:
     """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
     loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
     and held intrinsics of both refinements (calibrate_camera).
     ransac: None, or rig.ransac_params(...) for the start poses of both calibrate() calls (calibrate_camera); a view either
     call drops leaves `has`, and the result carries ransac = the second call's dict(inlier, code, has).
+    mask_outliers (with ransac): each of the two refinements takes its own call's inlier mask as its corner mask (calibrate_camera).
     Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
     img_size, has, pu, pv = _detect(images, cols, rows, sigma, device)
     intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed,
-                                       ransac=ransac)                                                                            # :57
+                                       ransac=ransac, mask_outliers=mask_outliers)                                               # :57
     if ransac is not None:
         has = first["ransac"]["has"]
     _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device)
@@ -166,7 +187,7 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
     intr, Rt, second = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr=warm, loss=loss, model=model,
-                                        fixed=fixed, ransac=ransac)
+                                        fixed=fixed, ransac=ransac, mask_outliers=mask_outliers)
     out = dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
     if ransac is not None:
         out.update(has=second["ransac"]["has"], ransac=second["ransac"])
@@ -174,10 +195,10 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
 
 
 def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None,
-                          model="ts", masks=None, ransac=None) -> list:
+                          model="ts", masks=None, ransac=None, mask_outliers=False) -> list:
     """monocular_calib for every camera, stage by stage across the cameras: detection, the first calibrate, the refinement
     pass, the second calibrate -- each of the two refinements of all cameras in one batch (api.refinement_batch).
-    masks: [C] mask words (model included); ransac: as for monocular_calib.  Returns monocular_calib's dict per camera."""
+    masks: [C] mask words (model included); ransac, mask_outliers: as for monocular_calib.  Returns monocular_calib's dict per camera."""
     n_cam = len(images_by_camera)
     masks = np.zeros(n_cam, dtype=np.uint16) if masks is None else masks
     det = [_detect(imgs, cols, rows, sigma, device) for imgs in images_by_camera]
@@ -185,13 +206,13 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
     has = [d[1] for d in det]
     pu = [d[2] for d in det]
     pv = [d[3] for d in det]
-    first = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, [None] * n_cam, loss, model, masks, ransac)
+    first = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, [None] * n_cam, loss, model, masks, ransac, mask_outliers)
     if ransac is not None:
         has = [f[2]["ransac"]["has"] for f in first]
     for m, imgs in enumerate(images_by_camera):
         _refine_pixels(imgs, first[m][0], first[m][1], has[m], pu[m], pv[m], cols, rows, pitch, sigma, device)
     warm = [f[0] if f[2]["termination_type"] == 0 else None for f in first]
-    second = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, warm, loss, model, masks, ransac)
+    second = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, warm, loss, model, masks, ransac, mask_outliers)
     out = [dict(intr=second[m][0], Rt=second[m][1], has=has[m], pix_u=pu[m], pix_v=pv[m], first=first[m][2], second=second[m][2])
            for m in range(n_cam)]
     if ransac is not None:
@@ -201,7 +222,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -211,6 +232,9 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     all cameras (monocular_calib_batch); False (the default) runs monocular_calib camera after camera.
     ransac: None, or rig.ransac_params(...) for the start poses of every mono calibration (monocular_calib): the views it drops
     are out of `has` when the rig is initialised, and mono[m]["ransac"] holds each camera's masks and codes.
+    mask_outliers (with ransac): the RANSAC inlier masks are the corner masks of every refinement that follows -- both mono
+    refinements of every camera, the joint solve and the covariance (rig_corner_mask: each view's mask from its camera's second
+    calibration; result["corner_mask"] holds the joint problem's).  False: the calls of a run without it.
     covariance: True adds result["covariance"] = api.covariance at the solved parameters, with the loss and masks of the joint
     solve (standard deviations, sigma2, min_pivot_ratio: how well the views determine each parameter).
     uncertainty: None, or dict(step=pixels between grid points, inv_distances=(...)) -- implies covariance and adds
@@ -221,9 +245,11 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
     if batch_mono:
-        mono = monocular_calib_batch(images_by_camera, cols, rows, pitch, sigma, device, loss=loss, model=model, masks=w, ransac=ransac)
+        mono = monocular_calib_batch(images_by_camera, cols, rows, pitch, sigma, device, loss=loss, model=model, masks=w, ransac=ransac,
+                                     mask_outliers=mask_outliers)
     else:
-        mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]), ransac=ransac)
+        mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]), ransac=ransac,
+                                mask_outliers=mask_outliers)
                 for m, imgs in enumerate(images_by_camera)]
     W = board_points(cols, rows, pitch)
     inp = rig.RigInput(W, np.stack([m["intr"] for m in mono]), np.stack([m["has"] for m in mono]), np.stack([m["Rt"] for m in mono]),
@@ -231,10 +257,19 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     g = rig.rig_init(inp, device)
     problem = rig.problem_from_rig(inp, g)
     _start_in_model(problem.intr, model)
-    summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None)
+    cw = rig_corner_mask(problem, mono) if mask_outliers and ransac is not None else None
+    if cw is not None:
+        summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw)
+    else:
+        summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None)
     out = dict(problem=problem, mono=mono, rig_init=g, summary=summary)
+    if cw is not None:
+        out["corner_mask"] = cw
     if covariance or uncertainty is not None:
-        out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None)
+        if cw is not None:
+            out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw)
+        else:
+            out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None)
     if uncertainty is not None:
         step = float(uncertainty["step"])
         img_w, img_h = images_by_camera[0][0].shape[1], images_by_camera[0][0].shape[0]
@@ -242,6 +277,13 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
         out["uncertainty"] = api.projection_uncertainty(problem.cam_rt, problem.intr, out["covariance"], uncertainty_requests(n_cam, uncertainty["inv_distances"]),
                                                         grid, device)
     return out
+
+
+def rig_corner_mask(problem: Problem, mono) -> np.ndarray:
+    """The corner mask of the joint problem (rig.problem_from_rig) from the per-camera results of monocular_calib with ransac:
+    view (camera m, board i) takes mono[m]["ransac"]["inlier"][i], in the problem's corner order."""
+    return np.concatenate([np.asarray(mono[m]["ransac"]["inlier"], dtype=bool)[i][:c]
+                           for m, i, c in zip(problem.view_camera, problem.view_board, problem.view_count)]) if problem.n_views else np.zeros(0, dtype=bool)
 
 
 def uncertainty_requests(n_cameras: int, inv_distances) -> list:

@@ -36,6 +36,9 @@ class Problem:
     mono: bool = False
     meta: dict = field(default_factory=dict)
     board_pose_constant: "np.ndarray | None" = None   # [B] uint8, 1 = pose block held constant (None: all free, as in the reference)
+    # [n_corners] float64 corner weights (bool: a 0/1 mask) in corner order -- views in order, the corners of a view in order -- or
+    # None: Ceres' ScaledLoss per residual block, weight 0 takes the corner out (tscm.h: corner weights)
+    weights: "np.ndarray | None" = None
 
     @property
     def n_points(self) -> int:
@@ -55,7 +58,8 @@ class Problem:
             self.view_board.copy(), self.view_offset.copy(), self.view_count.copy(),
             self.obs_u.copy(), self.obs_v.copy(), self.cam_rt.copy(), self.intr.copy(),
             self.board_rt.copy(), self.cam_pose_constant.copy(), self.mono, dict(self.meta),
-            None if self.board_pose_constant is None else self.board_pose_constant.copy())
+            None if self.board_pose_constant is None else self.board_pose_constant.copy(),
+            None if self.weights is None else self.weights.copy())
 
     def normalised(self) -> "Problem":
         """Contiguous, correctly typed arrays (what the C ABI expects)."""
@@ -66,7 +70,8 @@ class Problem:
             i(self.view_board), i(self.view_offset), i(self.view_count), f(self.obs_u), f(self.obs_v),
             f(self.cam_rt).reshape(-1, 6), f(self.intr).reshape(-1, 9), f(self.board_rt).reshape(-1, 6),
             np.ascontiguousarray(self.cam_pose_constant, dtype=np.uint8), bool(self.mono), dict(self.meta),
-            None if self.board_pose_constant is None else np.ascontiguousarray(self.board_pose_constant, dtype=np.uint8))
+            None if self.board_pose_constant is None else np.ascontiguousarray(self.board_pose_constant, dtype=np.uint8),
+            None if self.weights is None else np.ascontiguousarray(self.weights, dtype=np.float64).ravel())
 
     def validate(self) -> None:
         C, B, V = self.n_cameras, self.n_boards, self.n_views
@@ -89,6 +94,8 @@ class Problem:
             raise ValueError("view_offset+view_count exceeds observation arrays")
         if self.obs_u.shape != self.obs_v.shape:
             raise ValueError("obs_u / obs_v length mismatch")
+        if self.weights is not None and np.size(self.weights) != self.n_corners:
+            raise ValueError("weights must have one entry per corner (sum of view_count)")
 
 
 def shard_frames(p: Problem, rank: int, world: int) -> Problem:
@@ -116,5 +123,9 @@ def shard_frames(p: Problem, rank: int, world: int) -> Problem:
     q.obs_u = p.obs_u[idx]
     q.obs_v = p.obs_v[idx]
     q.view_offset = (np.cumsum(q.view_count) - q.view_count).astype(np.int32)
+    if p.weights is not None:
+        first = np.cumsum(p.view_count) - p.view_count          # corner order: by count, not by view_offset
+        widx = np.concatenate([np.arange(o, o + c) for o, c in zip(first[sel], p.view_count[sel])]) if sel.any() else np.zeros(0, dtype=np.int64)
+        q.weights = np.asarray(p.weights)[widx]
     q.meta = dict(p.meta, rank=rank, world=world, owned_boards=np.nonzero(owner == rank)[0])
     return q
