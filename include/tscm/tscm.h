@@ -259,7 +259,23 @@ int tscm_solver_kernel_time(tscm_solver *s, int enable, int *launches, double *t
  * total milliseconds since the last call.  Zeros without a communicator. */
 int tscm_solver_exchange_time(tscm_solver *s, int *n_T, double *ms_T, int *n_H, double *ms_H);
 
-/* One-shot drop-ins ------------------------------------------------------------
+/* Refusal order of the one-shot entry points ------------------------------------
+ * tscm_solve_*, tscm_eval_step_* and tscm_eval_normal_equations_* are each one path behind
+ * several spellings: an export without a loss, a mask or weights is the most general one of
+ * its family (_weighted) called with TSCM_LOSS_NONE and NULLs, bit for bit.  All of them
+ * refuse, before any device is touched and in this order:
+ *   1. the loss: an unknown kind, a scale that is not finite and > 0;
+ *   2. NULL arguments (tscm_solve_multi / _mono: their mono / multi guard);
+ *   3. the mask: bits 9 and up;
+ *   4. the options struct: a struct_size this library does not know;
+ *   5. the option values: max_num_iterations, unknown exec_flags bits, TSCM_EXEC_GRAM_16X16
+ *      with a loss or with weights (TSCM_E_UNSUPPORTED);
+ *   6. the problem, then the weights.
+ * All TSCM_E_INVALID unless said otherwise.  The device index (TSCM_E_NO_DEVICE) and what the
+ * device cannot hold (TSCM_E_UNSUPPORTED) follow.  tscm_solve_mono_batch* and tscm_covariance*
+ * state their own order below.
+ *
+ * One-shot drop-ins ------------------------------------------------------------
  * tscm_solve_multi replaces the Ceres block of MultiCalib::calibrate()
  *                  (multi_calib.cpp:157-218); the caller then runs update_param()
  *                  (multi_calib.cpp:221-232) on its own objects.
@@ -292,8 +308,7 @@ int tscm_eval_normal_equations(const tscm_problem *problem, int device, double *
 /* The same, formed by the Gram kernel a solve with `opt` runs (NULL = defaults, which
  * is tscm_eval_normal_equations): opt->jacobian_fp32 selects the fp32-Jacobian tier,
  * opt->exec_flags & TSCM_EXEC_GRAM_16X16 the 16x16-tile kernel; the other flags do not
- * change the evaluation and are ignored.  struct_size and exec_flags are checked as
- * tscm_solver_solve checks them (TSCM_E_INVALID).                                   */
+ * change the evaluation and are ignored.                                            */
 int tscm_eval_normal_equations_ex(const tscm_problem *problem, int device, const tscm_options *opt,
                                   double *board_gram, double *board_grad, double *view_cross,
                                   double *cam_gram, double *cam_grad, double *cost);
@@ -305,8 +320,7 @@ int tscm_eval_normal_equations_ex(const tscm_problem *problem, int device, const
  * cam_rt [C*6] (may be NULL for a mono problem), intr [C*9], board_rt [B*6] receive
  * x + delta exactly as that solve evaluates it; constant blocks come back as their input.
  * *valid = 0 if the step is invalid (the linear solve failed: no candidate).  summary
- * (may be NULL) = the one-iteration summary.  Options are checked as in
- * tscm_eval_normal_equations_ex.  For parity tests.                                 */
+ * (may be NULL) = the one-iteration summary.  For parity tests.                      */
 int tscm_eval_step_ex(const tscm_problem *problem, int device, const tscm_options *opt,
                       double *cam_rt, double *intr, double *board_rt, int *valid,
                       tscm_summary *summary);
@@ -322,8 +336,8 @@ int tscm_eval_step_ex(const tscm_problem *problem, int device, const tscm_option
  * relative_decrease all use it; the gradient, the normal equations and the tolerance tests use the
  * Jacobian and residual scaled by sqrt(rho'(s)) (Ceres' Corrector: rho'' <= 0 for all three losses,
  * so no rank-one term).  TSCM_LOSS_NONE is the plain least-squares solve, bit for bit.
- * An unknown kind, or a scale that is not finite or <= 0: TSCM_E_INVALID, checked before any device
- * is touched.  A loss with TSCM_EXEC_GRAM_16X16: TSCM_E_UNSUPPORTED.
+ * An unknown kind, or a scale that is not finite or <= 0: TSCM_E_INVALID.  A loss with
+ * TSCM_EXEC_GRAM_16X16: TSCM_E_UNSUPPORTED.
  *   new ceres::HuberLoss(1.0)  ->  tscm_solver_set_loss(s, TSCM_LOSS_HUBER, 1.0)              */
 enum { TSCM_LOSS_NONE = 0, TSCM_LOSS_HUBER = 1, TSCM_LOSS_SOFT_L1 = 2, TSCM_LOSS_CAUCHY = 3 };
 /* the loss of every later solve / solve_resident of s (scale ignored for TSCM_LOSS_NONE).  The shards
@@ -361,7 +375,7 @@ int tscm_solver_eval_normal_equations(tscm_solver *s, const tscm_options *opt, i
  *   - all of bits 0-6: SetParameterBlockConstant on the block, which leaves the program and x_norm like
  *     a constant camera pose (tscm_problem.cam_pose_constant).
  *   - bits 7-8 (b, c) are accepted and change nothing: b and c are inert in the model.
- *   - bits 9 and up: TSCM_E_INVALID, checked before any device is touched.
+ *   - bits 9 and up: TSCM_E_INVALID.
  *   - mask 0 for every camera (or fixed = NULL) is the solve without held intrinsics, bit for bit.
  * Lambda = 0 makes the Triple Sphere model the Double Sphere model, xi = lambda = 0 the Unified Camera
  * Model: TSCM_MODEL_DS / TSCM_MODEL_UCM with lambda (and xi) at 0 calibrate those models.
@@ -475,8 +489,7 @@ int tscm_covariance_from_normal_equations(int n_cameras, int n_boards, int n_vie
  * Counts and RMSE.  summary.n_residual_blocks counts the corners with omega_i > 0; summary.rmse = sqrt(sum omega_i s_i /
  * sum omega_i) at the accepted point -- for a 0/1 mask the pixel RMSE over the kept corners.  tscm_reprojection_error knows
  * no weights.
- * Refused with TSCM_E_INVALID before any device is touched, the text naming the corner or view: a weight that is negative,
- * NaN or infinite; a view with view_count > 0 whose weights are all 0 (pass view_count = 0 for it).  Weights with
+ * Refused with TSCM_E_INVALID, the text naming the corner or view: a weight that is negative, NaN or infinite; a view with view_count > 0 whose weights are all 0 (pass view_count = 0 for it).  Weights with
  * TSCM_EXEC_GRAM_16X16: TSCM_E_UNSUPPORTED, as for a loss.
  * weights = NULL is the solve without weights, bit for bit, on a fresh solver and after weights were set and cleared.
  *

@@ -188,10 +188,7 @@ public:
         P.obs_u = u.data(); P.obs_v = v.data(); P.intr = intrinsic_.data(); P.board_rt = rt.data(); P.mono = 1;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 1);
-        if (weighted) check(tscm_solve_weighted(&P, &o, w.data(), fixed_ ? &fixed_ : NULL, loss_kind_, loss_scale_, &summary));
-        else if (fixed_) check(tscm_solve_fixed(&P, &o, &fixed_, loss_kind_, loss_scale_, &summary));
-        else if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_mono(&P, &o, &summary));
-        else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
+        check(tscm_solve_weighted(&P, &o, weighted ? w.data() : NULL, fixed_ ? &fixed_ : NULL, loss_kind_, loss_scale_, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
         return summary.termination_type == TSCM_CONVERGENCE;             // TS.cpp:281
     }
@@ -706,10 +703,7 @@ public:
             tscm_solver_destroy(s);
             check(rc);
         } else {
-            if (use_weights_) check(tscm_solve_weighted(&P, &o, q.w.data(), any_fixed ? fixed.data() : nullptr, loss_kind_, loss_scale_, &summary));
-            else if (any_fixed) check(tscm_solve_fixed(&P, &o, fixed.data(), loss_kind_, loss_scale_, &summary));
-            else if (loss_kind_ == TSCM_LOSS_NONE) check(tscm_solve_multi(&P, &o, &summary));
-            else check(tscm_solve_robust(&P, &o, loss_kind_, loss_scale_, &summary));
+            check(tscm_solve_weighted(&P, &o, use_weights_ ? q.w.data() : nullptr, any_fixed ? fixed.data() : nullptr, loss_kind_, loss_scale_, &summary));
         }
         for (int m = 0; m < C; ++m) {                                    // :221-226
             cameras_[m].rt_.assign(&crt[6 * (size_t)m], &crt[6 * (size_t)m] + 6);
@@ -746,12 +740,8 @@ public:
         out.cam_rt_std.assign(6 * C, 0.0); out.intr_std.assign(9 * C, 0.0); out.board_rt_std.assign(6 * B, 0.0);
         out.info = tscm_covariance_info();
         out.info.struct_size = (int)sizeof(tscm_covariance_info);
-        if (use_weights_)
-            check(tscm_covariance_weighted(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, q.w.data(), loss_kind_, loss_scale_, out.cam_cov.data(),
-                                           out.board_cov.data(), out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
-        else
-        check(tscm_covariance(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, loss_kind_, loss_scale_, out.cam_cov.data(), out.board_cov.data(),
-                              out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
+        check(tscm_covariance_weighted(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, use_weights_ ? q.w.data() : nullptr, loss_kind_, loss_scale_,
+                                       out.cam_cov.data(), out.board_cov.data(), out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
         out.sigma2 = out.info.sigma2;
         return out;
     }

@@ -25,6 +25,11 @@ from tests.test_gpu_gram_kernels import f32_excess, g4_plan, ragged
 pytestmark = pytest.mark.gpu
 
 KINDS = ["huber", "soft_l1", "cauchy"]
+# boards at the edges of the Gram kernels' table (eval_kernel: k-steps KS per pass x single / several passes), 2 cameras x 2
+# views each: one corner (the smallest board there is, KS 1), 56 (KS 14, the largest single pass), 57 (two passes of KS 8, the
+# first several-pass entry) and 112 (two passes of KS 14, the last)
+EDGES = {"1x1": (1, 1), "8x7": (8, 7), "19x3": (19, 3), "14x8": (14, 8)}
+EDGE_PLANS = {"1x1": (1, 4, 1), "8x7": (1, 56, 14), "19x3": (2, 32, 8), "14x8": (2, 56, 14)}
 
 
 def _problem(name):
@@ -37,11 +42,15 @@ def _problem(name):
         return ragged(p, 54, g4_plan(54)[1])
     if name == "mono":
         return synth.make_problem(1, 24, 504).normalised()
+    if name in EDGES:
+        p = synth.make_problem(2, 2, 505, cols=EDGES[name][0], rows=EDGES[name][1], pitch=32.0).normalised()
+        assert g4_plan(p.n_points) == EDGE_PLANS[name]
+        return p
     raise KeyError(name)
 
 
 @pytest.mark.parametrize("fp32", [0, 1], ids=["fp64", "fp32"])
-@pytest.mark.parametrize("name", ["9x6", "11x8", "ragged", "mono"])
+@pytest.mark.parametrize("name", ["9x6", "11x8", "ragged", "mono", *EDGES])
 @pytest.mark.parametrize("kind", KINDS)
 def test_normal_equations(hip_device, kind, name, fp32):
     p = _problem(name)

@@ -27,6 +27,11 @@ pytestmark = pytest.mark.gpu
 BLOCKS = ("board_gram", "board_grad", "view_cross", "cam_gram", "cam_grad")
 LOSSES = [None, "huber", "cauchy"]
 NAMES = ["9x6", "11x8", "ragged", "mono"]
+# boards at the edges of the Gram kernels' table (eval_kernel), 2 cameras x 2 views each, with the seed of their weights: three
+# corners (KS 1; the smallest board scattered_weights takes: it masks a first, a last and an interior corner of views of >= 3),
+# 56 (KS 14, the largest single pass), 57 (two passes of KS 8, the first several-pass entry), 112 (two passes of KS 14, the last)
+EDGES = {"3x1": (3, 1, 906), "8x7": (8, 7, 900), "19x3": (19, 3, 900), "14x8": (14, 8, 900)}
+EDGE_PLANS = {"3x1": (1, 4, 1), "8x7": (1, 56, 14), "19x3": (2, 32, 8), "14x8": (2, 56, 14)}
 _cache = {}
 
 
@@ -40,10 +45,14 @@ def _problem(name):
             p = synth.make_problem(4, 12, 502, cols=11, rows=8, pitch=32.0).normalised()
         elif name == "ragged":
             p = ragged(synth.make_problem(4, 40, 503), 54, g4_plan(54)[1])
-        else:
+        elif name == "mono":
             p = synth.make_problem(1, 24, 504).normalised()
+        else:
+            p = synth.make_problem(2, 2, 505, cols=EDGES[name][0], rows=EDGES[name][1], pitch=32.0).normalised()
+            assert g4_plan(p.n_points) == EDGE_PLANS[name]
         per = g4_plan(p.n_points)[1]
-        w = W.scattered_weights(p, 900 + len(_cache), boundary=per if per < p.n_points else None)
+        seed = EDGES[name][2] if name in EDGES else 900 + sum(k not in EDGES for k in _cache)
+        w = W.scattered_weights(p, seed, boundary=per if per < p.n_points else None)
         _cache[name] = (p, w, orc.evaluate(p, jets=True), R.median_scale(p))
     return _cache[name]
 
@@ -65,7 +74,7 @@ def _check(g, o, p, fp32):
 
 @pytest.mark.parametrize("fp32", [0, 1], ids=["fp64", "fp32"])
 @pytest.mark.parametrize("mask", [False, True], ids=["weights", "mask"])
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", [*NAMES, *EDGES])
 @pytest.mark.parametrize("kind", LOSSES)
 def test_normal_equations(hip_device, kind, name, mask, fp32):
     p, w, jets, a = _problem(name)

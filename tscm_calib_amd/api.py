@@ -308,7 +308,7 @@ def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, weigh
     q, w = _l.corner_weights(problem, weights)
     cp = _l.c_problem(q)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_multi, w)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, w)
     return _l.summary_dict(s)
 
 
@@ -324,7 +324,7 @@ def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, weig
     q, w = _l.corner_weights(problem, weights)
     cp = _l.c_problem(q)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, _l.lib().tscm_solve_mono, w)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, w)
     d = _l.summary_dict(s)
     return d["termination_type"] == 0, d
 
@@ -357,12 +357,9 @@ def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, weight
             raise ValueError("fixed: one mask per problem")
         w = np.array([_l.fixed_masks(f, 1)[0] for f in fixed], dtype=np.uint16)
     k, a = _l.loss_args(loss)
-    if any(x is not None for x in ws):
-        dp = C.POINTER(C.c_double)
-        wp = (dp * n)(*[_l.dptr(x) if x is not None else dp() for x in ws])
-        _l.check(_l.lib().tscm_solve_mono_batch_weighted(cps, n, device, C.byref(o), _l.ushort_ptr(w) if w is not None else None, wp, k, a, sums))
-    else:
-        _l.check(_l.lib().tscm_solve_mono_batch(cps, n, device, C.byref(o), _l.ushort_ptr(w) if w is not None else None, k, a, sums))
+    dp = C.POINTER(C.c_double)
+    wp = (dp * n)(*[_l.dptr(x) if x is not None else dp() for x in ws])
+    _l.check(_l.lib().tscm_solve_mono_batch_weighted(cps, n, device, C.byref(o), None if w is None else _l.ushort_ptr(w), wp, k, a, sums))
     out = []
     for i in range(n):
         d = _l.summary_dict(sums[i])
@@ -370,20 +367,11 @@ def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, weight
     return out
 
 
-def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, plain, weights=None):
-    if weights is not None:
-        w = None if fixed is None else _l.fixed_masks(fixed, n_cameras)
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_solve_weighted(C.byref(cp), C.byref(o), _l.dptr(weights), None if w is None else _l.ushort_ptr(w), k, a, C.byref(s)))
-    elif fixed is not None:
-        w = _l.fixed_masks(fixed, n_cameras)
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_solve_fixed(C.byref(cp), C.byref(o), _l.ushort_ptr(w), k, a, C.byref(s)))
-    elif loss is None:
-        _l.check(plain(C.byref(cp), C.byref(o), C.byref(s)))
-    else:
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_solve_robust(C.byref(cp), C.byref(o), k, a, C.byref(s)))
+def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, weights=None):
+    # the most general export; None where nothing is set (tscm_solve_multi / _mono / _robust / _fixed wrap the same path)
+    w = None if fixed is None else _l.fixed_masks(fixed, n_cameras)
+    k, a = _l.loss_args(loss)
+    _l.check(_l.lib().tscm_solve_weighted(C.byref(cp), C.byref(o), _l.dptr(weights), None if w is None else _l.ushort_ptr(w), k, a, C.byref(s)))
 
 
 def _select(device: int):
@@ -432,14 +420,9 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
             if loss is not None:
                 s.set_loss(*((loss,) if isinstance(loss, str) else loss))
             _l.check(_l.lib().tscm_solver_eval_normal_equations(s._h, C.byref(o), 1, *outs))
-    elif w is not None:
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_eval_normal_equations_weighted(C.byref(cp), device, C.byref(o), _l.dptr(w), k, a, *outs))
-    elif loss is None:
-        _l.check(_l.lib().tscm_eval_normal_equations_ex(C.byref(cp), device, C.byref(o), *outs))
     else:
         k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_eval_normal_equations_robust(C.byref(cp), device, C.byref(o), k, a, *outs))
+        _l.check(_l.lib().tscm_eval_normal_equations_weighted(C.byref(cp), device, C.byref(o), _l.dptr(w), k, a, *outs))
     out["cost"] = cost.value
     return out
 
@@ -458,19 +441,9 @@ def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=No
     cp = _l.c_problem(q)
     o = _l.default_options(problem.mono, **options)
     outs = (_l.dptr(cam), _l.dptr(intr), _l.dptr(board), C.byref(valid), C.byref(s))
-    if cw is not None:
-        w = None if fixed is None else _l.fixed_masks(fixed, problem.n_cameras)
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_eval_step_weighted(C.byref(cp), device, C.byref(o), _l.dptr(cw), None if w is None else _l.ushort_ptr(w), k, a, *outs))
-    elif fixed is not None:
-        w = _l.fixed_masks(fixed, problem.n_cameras)
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_eval_step_fixed(C.byref(cp), device, C.byref(o), _l.ushort_ptr(w), k, a, *outs))
-    elif loss is None:
-        _l.check(_l.lib().tscm_eval_step_ex(C.byref(cp), device, C.byref(o), *outs))
-    else:
-        k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_eval_step_robust(C.byref(cp), device, C.byref(o), k, a, *outs))
+    w = None if fixed is None else _l.fixed_masks(fixed, problem.n_cameras)
+    k, a = _l.loss_args(loss)
+    _l.check(_l.lib().tscm_eval_step_weighted(C.byref(cp), device, C.byref(o), _l.dptr(cw), None if w is None else _l.ushort_ptr(w), k, a, *outs))
     return dict(cam_rt=cam, intr=intr, board_rt=board, valid=bool(valid.value), summary=_l.summary_dict(s))
 
 
@@ -534,10 +507,7 @@ def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None, weig
     w = None if fixed is None else _l.fixed_masks(fixed, Cn)
     k, a = _l.loss_args(loss)
     outs = (_l.dptr(cam_cov), _l.dptr(board_cov), _l.dptr(cam_std), _l.dptr(intr_std), _l.dptr(board_std), C.byref(info))
-    if cw is not None:
-        _l.check(_l.lib().tscm_covariance_weighted(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), _l.dptr(cw), k, a, *outs))
-    else:
-        _l.check(_l.lib().tscm_covariance(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), k, a, *outs))
+    _l.check(_l.lib().tscm_covariance_weighted(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), _l.dptr(cw), k, a, *outs))
     out = _covariance_dict(info, Cn, B, cam_cov, board_cov)
     out.update(cam_rt_std=cam_std, intr_std=intr_std, board_rt_std=board_std)
     return out

@@ -13,9 +13,9 @@
 
 #include "tscm_layout.h"
 #include "tscm_exec_plan.h"
+#include "tscm_spec.h"
 
 #include <algorithm>
-#include <cmath>
 #include <string>
 #include <vector>
 
@@ -54,13 +54,14 @@ struct BatchPlan {
     std::vector<Int4> chunk;
     long N = 0;                                 // corners of the device batch
     int B = 0;                                  // concatenated boards
+    LossArg loss{};                             // the shared loss as the kernels take it (make_spec)
 };
 
 // 0, or a TSCM_E_* code and its message in err (out is then untouched).  opt: the caller's options as the library read them
 // (read_options); loss_kind / loss_scale: the shared loss; fixed: [n] masks or NULL.  Refusals in order: the arguments,
-// every problem's own validation (tscm_layout.h: validate), the batch's shape (mono, one camera, one board), the masks, the
-// loss, the options (the same codes as tscm_solve_fixed), what this route does not take (fp32 Jacobians, exec_flags), then
-// a board seen by two views with corners (TSCM_E_INVALID, as the single-problem solver).
+// every problem's own validation (tscm_layout.h: validate), the batch's shape (mono, one camera, one board), the loss, the
+// masks (tscm_spec.h: make_spec), the options (the same codes as tscm_solve_fixed), what this route does not take (fp32
+// Jacobians, exec_flags), then a board seen by two views with corners (TSCM_E_INVALID, as the single-problem solver).
 inline int plan_batch(const tscm_problem *problems, int n, const tscm_options &opt, const unsigned short *fixed, int loss_kind,
                       double loss_scale, BatchPlan &out, std::string &err)
 {
@@ -79,16 +80,14 @@ inline int plan_batch(const tscm_problem *problems, int n, const tscm_options &o
             if (p.board_xy[j] != p0.board_xy[j]) return layout_fail(err, TSCM_E_UNSUPPORTED, "the problems of a batch share one board (board_xy differ)");
     }
     if (p0.n_points > kMbMaxPoints) return layout_fail(err, TSCM_E_UNSUPPORTED, "boards of more than 256 corners are not batched");
-    if (fixed) for (int i = 0; i < n; ++i) if (fixed[i] & ~TSCM_FIX_ALL) return layout_fail(err, TSCM_E_INVALID, "unknown bits in a fixed-intrinsics mask (bits 0-8 only)");
-    if (loss_kind < TSCM_LOSS_NONE || loss_kind > TSCM_LOSS_CAUCHY) return layout_fail(err, TSCM_E_INVALID, "unknown loss kind");
-    if (loss_kind != TSCM_LOSS_NONE && !(std::isfinite(loss_scale) && loss_scale > 0.0))
-        return layout_fail(err, TSCM_E_INVALID, "the scale of a loss must be finite and > 0");
+    SolveSpec spec;                             // (one camera per problem: fixed is the [n] masks of make_spec)
+    if (int rc = make_spec(loss_kind, loss_scale, fixed, n, spec, err)) return rc;
     if (int rc = check_exec_options(opt, loss_kind, err)) return rc;
     if (opt.jacobian_fp32) return layout_fail(err, TSCM_E_UNSUPPORTED, "tscm_solve_mono_batch has no fp32-Jacobian tier");
     if (opt.exec_flags) return layout_fail(err, TSCM_E_UNSUPPORTED, "tscm_solve_mono_batch takes no exec_flags");
 
     BatchPlan b;
-    b.n_problems = n; b.n_points = p0.n_points;
+    b.n_problems = n; b.n_points = p0.n_points; b.loss = spec.loss;
     b.dev_of.assign(n, -1);
     b.slot_ptr.push_back(0); b.chunk_ptr.push_back(0); b.board_ptr.push_back(0); b.obs_ptr.push_back(0);
     for (int i = 0; i < n; ++i) {

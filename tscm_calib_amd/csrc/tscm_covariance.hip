@@ -493,12 +493,12 @@ static int covariance_of_problem(const tscm_problem *p, int device, const unsign
     // the blocks, from the default fp64 Gram kernel through the public evaluation
     std::vector<double> bg((size_t)36 * B + 1), vc((size_t)90 * V + 1), cg((size_t)225 * C);
     double cost = 0.0;
+    if (int rc = tscm_eval_normal_equations_spec(p, device, nullptr, spec_args(loss_kind, loss_scale, nullptr, weights), bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
     if (weights) {
-        if (int rc = tscm_eval_normal_equations_weighted(p, device, nullptr, weights, loss_kind, loss_scale, bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
         long long kept = 0;
         for (long long i = 0; i < N; ++i) kept += weights[i] > 0.0 ? 1 : 0;
         N = kept;
-    } else if (int rc = tscm_eval_normal_equations_robust(p, device, nullptr, loss_kind, loss_scale, bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
+    }
     const size_t n15 = (size_t)kCovCam * C;
     std::vector<double> own_cam, own_board;
     if (!cam_cov) { own_cam.resize(n15 * n15); cam_cov = own_cam.data(); }

@@ -210,7 +210,7 @@ __device__ __forceinline__ void corner_residual(double x, double y, double ou, d
 // Jacobian rows of the block are both scaled by sqrt(rho'), and no rank-one term appears.  The robust Gram-kernel
 // instantiations get these values as a kernel argument (wave-uniform: scalar registers).
 enum { kLossNone = 0, kLossHuber = 1, kLossSoftL1 = 2, kLossCauchy = 3 };
-struct LossArg { double a, b, c; int kind, pad; };
+// (struct LossArg { a, b, c, kind }: tscm_spec.h, with the host code that fills it)
 // rho(s) and w = sqrt(rho'(s)), rho' clamped from below as Ceres clamps it (std::numeric_limits<double>::min()).
 // WEIGHTED (corner weights, DESIGN 27: Ceres' ScaledLoss): the corner's weight omega >= 0 scales both, rho = omega rho(s) and
 // w = sqrt(omega rho'(s)) -- the product formed behind the clamp and before the one sqrt, so omega = 0 gives w = 0 exactly --

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "tscm/tscm.h"
+#include "tscm_spec.h"
 
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,11 @@
 #include <vector>
 
 int tscm_set_error(int code, const std::string &msg);   // tscm_solver.hip: the text of tscm_last_error(); returns code
+
+// tscm_solver.hip: what tscm_eval_normal_equations_weighted and its siblings wrap -- the blocks from the Gram kernel a solve with
+// `opt` runs, under the loss and the weights of `in` (spec_args; a mask plays no part in an evaluation)
+int tscm_eval_normal_equations_spec(const tscm_problem *p, int device, const tscm_options *opt, const tscm::SolveSpec &in, double *board_gram,
+                                    double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost);
 
 // a failed HIP call ends the calling function with TSCM_E_HIP
 #define HIP_TRY(expr)                                                                                  \

@@ -32,6 +32,7 @@
 #include "tscm_exec_plan.h"
 #include "tscm_columns.h"
 #include "tscm_ctrl.h"
+#include "tscm_spec.h"
 
 namespace tscm {
 // one header per stage of an LM iteration, in the order the non-template kernels are defined (= their order in the code object)

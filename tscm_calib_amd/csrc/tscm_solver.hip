@@ -92,67 +92,34 @@ struct tscm_comm {
     int rank = 0, world = 1, device = 0;
 };
 
-// the Gram kernels k_eval_gram4 / k_eval_gram_f32 share one signature; both are instantiated per k-step count of a pass
-// (tscm_exec_plan.h: g4_plan), without and with a robust loss (ROBUST: DESIGN 14)
+// the Gram kernels k_eval_gram4 / k_eval_gram_f32 share one signature; every family is instantiated per k-step count of a pass
+// (tscm_exec_plan.h: g4_plan).  A family is a tier (G4: fp64, F32: the fp32-Jacobian tier on the same pass plan) plus 0 plain,
+// 1 with a robust loss (ROBUST: DESIGN 14), 2 with corner weights, with or without a loss (WEIGHTED: DESIGN 27)
 typedef void (*EvalKernel)(DevProblem, DevState, int, LossArg);
-template <bool ROBUST>
-static EvalKernel g4_kernel_of(int ks, bool multi)
+enum EvalFamily { G4, G4Robust, G4Weighted, F32, F32Robust, F32Weighted, kEvalFamilies };
+template <int KS, bool MULTI>
+static EvalKernel eval_instance(EvalFamily f)
 {
-    static const EvalKernel single[kG4MaxKS] = {
-        k_eval_gram4<1, false, ROBUST>, k_eval_gram4<2, false, ROBUST>, k_eval_gram4<3, false, ROBUST>, k_eval_gram4<4, false, ROBUST>,
-        k_eval_gram4<5, false, ROBUST>, k_eval_gram4<6, false, ROBUST>, k_eval_gram4<7, false, ROBUST>, k_eval_gram4<8, false, ROBUST>,
-        k_eval_gram4<9, false, ROBUST>, k_eval_gram4<10, false, ROBUST>, k_eval_gram4<11, false, ROBUST>, k_eval_gram4<12, false, ROBUST>,
-        k_eval_gram4<13, false, ROBUST>, k_eval_gram4<14, false, ROBUST> };
-    // several passes: ceil(n / passes) >= 29 corners per pass, i.e. at least 8 k-steps
-    static const EvalKernel passes[kG4MaxKS] = {
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram4<8, true, ROBUST>, k_eval_gram4<9, true, ROBUST>,
-        k_eval_gram4<10, true, ROBUST>, k_eval_gram4<11, true, ROBUST>, k_eval_gram4<12, true, ROBUST>, k_eval_gram4<13, true, ROBUST>,
-        k_eval_gram4<14, true, ROBUST> };
-    return (multi ? passes : single)[ks - 1];
+    // several passes: ceil(n / passes) >= 29 corners per pass, i.e. at least 8 k-steps -- nothing below is instantiated
+    if constexpr (MULTI && KS < 8) return nullptr;
+    else switch (f) {
+        case G4: return k_eval_gram4<KS, MULTI, false>;
+        case G4Robust: return k_eval_gram4<KS, MULTI, true>;
+        case G4Weighted: return k_eval_gram4_weighted<KS, MULTI>;
+        case F32: return k_eval_gram_f32<KS, MULTI, false>;
+        case F32Robust: return k_eval_gram_f32<KS, MULTI, true>;
+        case F32Weighted: return k_eval_gram_f32_weighted<KS, MULTI>;
+        default: return nullptr;
+    }
 }
-static EvalKernel g4_kernel(int ks, bool multi, bool robust) { return robust ? g4_kernel_of<true>(ks, multi) : g4_kernel_of<false>(ks, multi); }
-template <bool ROBUST>
-static EvalKernel f32_kernel_of(int ks, bool multi)     // the fp32-Jacobian tier on the same pass plan
+template <int... I>
+static EvalKernel eval_kernel(EvalFamily f, int ks, bool multi, std::integer_sequence<int, I...>)
 {
-    static const EvalKernel single[kG4MaxKS] = {
-        k_eval_gram_f32<1, false, ROBUST>, k_eval_gram_f32<2, false, ROBUST>, k_eval_gram_f32<3, false, ROBUST>, k_eval_gram_f32<4, false, ROBUST>,
-        k_eval_gram_f32<5, false, ROBUST>, k_eval_gram_f32<6, false, ROBUST>, k_eval_gram_f32<7, false, ROBUST>, k_eval_gram_f32<8, false, ROBUST>,
-        k_eval_gram_f32<9, false, ROBUST>, k_eval_gram_f32<10, false, ROBUST>, k_eval_gram_f32<11, false, ROBUST>, k_eval_gram_f32<12, false, ROBUST>,
-        k_eval_gram_f32<13, false, ROBUST>, k_eval_gram_f32<14, false, ROBUST> };
-    static const EvalKernel passes[kG4MaxKS] = {
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram_f32<8, true, ROBUST>, k_eval_gram_f32<9, true, ROBUST>,
-        k_eval_gram_f32<10, true, ROBUST>, k_eval_gram_f32<11, true, ROBUST>, k_eval_gram_f32<12, true, ROBUST>, k_eval_gram_f32<13, true, ROBUST>,
-        k_eval_gram_f32<14, true, ROBUST> };
-    return (multi ? passes : single)[ks - 1];
+    typedef EvalKernel (*Pick)(EvalFamily);
+    static const Pick single[] = { eval_instance<I + 1, false>... }, passes[] = { eval_instance<I + 1, true>... };
+    return (multi ? passes : single)[ks - 1](f);
 }
-static EvalKernel f32_kernel(int ks, bool multi, bool robust) { return robust ? f32_kernel_of<true>(ks, multi) : f32_kernel_of<false>(ks, multi); }
-// ... and with corner weights (WEIGHTED: DESIGN 27), with or without a loss
-static EvalKernel g4_weighted_kernel(int ks, bool multi)
-{
-    static const EvalKernel single[kG4MaxKS] = {
-        k_eval_gram4_weighted<1, false>, k_eval_gram4_weighted<2, false>, k_eval_gram4_weighted<3, false>, k_eval_gram4_weighted<4, false>,
-        k_eval_gram4_weighted<5, false>, k_eval_gram4_weighted<6, false>, k_eval_gram4_weighted<7, false>, k_eval_gram4_weighted<8, false>,
-        k_eval_gram4_weighted<9, false>, k_eval_gram4_weighted<10, false>, k_eval_gram4_weighted<11, false>, k_eval_gram4_weighted<12, false>,
-        k_eval_gram4_weighted<13, false>, k_eval_gram4_weighted<14, false> };
-    static const EvalKernel passes[kG4MaxKS] = {
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram4_weighted<8, true>, k_eval_gram4_weighted<9, true>,
-        k_eval_gram4_weighted<10, true>, k_eval_gram4_weighted<11, true>, k_eval_gram4_weighted<12, true>, k_eval_gram4_weighted<13, true>,
-        k_eval_gram4_weighted<14, true> };
-    return (multi ? passes : single)[ks - 1];
-}
-static EvalKernel f32_weighted_kernel(int ks, bool multi)
-{
-    static const EvalKernel single[kG4MaxKS] = {
-        k_eval_gram_f32_weighted<1, false>, k_eval_gram_f32_weighted<2, false>, k_eval_gram_f32_weighted<3, false>, k_eval_gram_f32_weighted<4, false>,
-        k_eval_gram_f32_weighted<5, false>, k_eval_gram_f32_weighted<6, false>, k_eval_gram_f32_weighted<7, false>, k_eval_gram_f32_weighted<8, false>,
-        k_eval_gram_f32_weighted<9, false>, k_eval_gram_f32_weighted<10, false>, k_eval_gram_f32_weighted<11, false>, k_eval_gram_f32_weighted<12, false>,
-        k_eval_gram_f32_weighted<13, false>, k_eval_gram_f32_weighted<14, false> };
-    static const EvalKernel passes[kG4MaxKS] = {
-        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, k_eval_gram_f32_weighted<8, true>, k_eval_gram_f32_weighted<9, true>,
-        k_eval_gram_f32_weighted<10, true>, k_eval_gram_f32_weighted<11, true>, k_eval_gram_f32_weighted<12, true>, k_eval_gram_f32_weighted<13, true>,
-        k_eval_gram_f32_weighted<14, true> };
-    return (multi ? passes : single)[ks - 1];
-}
+static EvalKernel eval_kernel(EvalFamily f, int ks, bool multi) { return eval_kernel(f, ks, multi, std::make_integer_sequence<int, kG4MaxKS>{}); }
 
 struct tscm_solver {
     int device = 0;
@@ -190,12 +157,10 @@ struct tscm_solver {
     const int *d_nd_tab[2] = { nullptr, nullptr }, *d_nd_bs[2] = { nullptr, nullptr };
     size_t lds_nd[2] = { 0, 0 }, lds_dense4 = 0;
     size_t lds_eval4 = 0;               // dynamic LDS of k_eval_gram4
-    EvalKernel eval4 = nullptr, eval32 = nullptr;   // ... and its instantiation for this problem's board (g4_kernel), the fp32-Jacobian tier's (f32_kernel)
-    EvalKernel eval4r = nullptr, eval32r = nullptr; // ... the same with a robust loss (ROBUST)
-    LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs eval4 / eval32
-    // corner weights (tscm_solver_set_corner_weights): with weights every evaluation runs eval4w / eval32w (WEIGHTED),
+    EvalKernel eval[kEvalFamilies] = {}; // ... and every family's instantiation for this problem's board (eval_kernel)
+    LossArg loss{};                     // tscm_solver_set_loss: kind 0 (TSCM_LOSS_NONE) runs the plain family of the tier
+    // corner weights (tscm_solver_set_corner_weights): with weights every evaluation runs the WEIGHTED family,
     // whatever the loss; P.obs_w is d_obs_w then and NULL otherwise
-    EvalKernel eval4w = nullptr, eval32w = nullptr;
     bool weighted = false;
     double *d_obs_w = nullptr;          // [N] weights in the device's corner order (allocated by the first call with weights)
     std::vector<double> h_obs_u, h_obs_v;   // the observations as created, in that order: a masked corner's device copy is 0, 0 while it is masked
@@ -277,46 +242,27 @@ static int validate(const tscm_problem *p)
     return 0;
 }
 
-// a loss of the C ABI -> the robust kernels' argument (Ceres' constructors: b = a^2, c = 1 / b); checked before any device is touched
-static int make_loss(int kind, double scale, LossArg &L)
+// the refusals of tscm_spec.h with their text in tscm_last_error()
+static int make_spec(int kind, double scale, const unsigned short *fixed, int n_cameras, SolveSpec &spec)
 {
-    L = LossArg{};
-    if (kind < TSCM_LOSS_NONE || kind > TSCM_LOSS_CAUCHY) return fail(TSCM_E_INVALID, "unknown loss kind");
-    if (kind == TSCM_LOSS_NONE) return 0;
-    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(TSCM_E_INVALID, "the scale of a loss must be finite and > 0");
-    L.kind = kind; L.a = scale; L.b = scale * scale; L.c = 1.0 / L.b;
+    std::string err;
+    if (int rc = tscm::make_spec(kind, scale, fixed, n_cameras, spec, err)) return fail(rc, err);
+    return 0;
+}
+static int check_corner_weights(const int *view_count, int n_views, const double *w, double *sum = nullptr, long *kept = nullptr)
+{
+    std::string err;
+    if (int rc = tscm::check_corner_weights(view_count, n_views, w, err, sum, kept)) return fail(rc, err);
     return 0;
 }
 static bool same_loss(const LossArg &x, const LossArg &y) { return x.kind == y.kind && (x.kind == TSCM_LOSS_NONE || x.a == y.a); }
 
 extern "C" int tscm_solver_set_loss(tscm_solver *s, int kind, double scale)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
+    SolveSpec spec;
+    if (int rc = make_spec(kind, scale, nullptr, 0, spec)) return rc;
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
-    s->loss = L;
-    return 0;
-}
-
-// corner weights [sum of view_count] in the problem's corner order (views in problem order, corners in order): checked before any
-// device is touched.  sum / kept: the sum of the weights and the number of corners with a weight > 0
-static int check_corner_weights(const int *view_count, int n_views, const double *w, double *sum = nullptr, long *kept = nullptr)
-{
-    double sm = 0.0;
-    long k = 0, n = 0;
-    for (int v = 0; v < n_views; ++v) {
-        bool any = false;
-        for (int j = 0; j < view_count[v]; ++j, ++n) {
-            const double x = w[n];
-            if (!std::isfinite(x) || x < 0.0)
-                return fail(TSCM_E_INVALID, "corner weight " + std::to_string(n) + " (view " + std::to_string(v) + ", corner " + std::to_string(j) + ") is negative, NaN or infinite");
-            if (x > 0.0) { any = true; ++k; sm += x; }
-        }
-        if (view_count[v] > 0 && !any)
-            return fail(TSCM_E_INVALID, "every corner weight of view " + std::to_string(v) + " is 0: pass view_count = 0 for a view without corners");
-    }
-    if (sum) *sum = sm;
-    if (kept) *kept = k;
+    s->loss = spec.loss;
     return 0;
 }
 
@@ -339,18 +285,11 @@ extern "C" int tscm_solver_set_corner_weights(tscm_solver *s, const double *weig
     double sum = 0.0;
     long kept = 0;
     if (int rc = check_corner_weights(s->p_view_count.data(), (int)s->p_view_count.size(), weights, &sum, &kept)) return rc;
-    // this rank's part, in the device's corner order; a masked corner's observation is 0, 0 there (it may hold anything, NaN included)
-    std::vector<long> first(s->p_view_count.size(), 0);
-    { long k = 0; for (size_t v = 0; v < first.size(); ++v) { first[v] = k; k += s->p_view_count[v]; } }
+    // this rank's part, in the device's corner order; a masked corner's observation is 0, 0 there (scatter_weights)
+    std::vector<CornerRun> runs((size_t)s->V);
+    for (int i = 0; i < s->V; ++i) runs[i] = CornerRun{ s->L.dev2orig[i], s->L.view_obs[i], s->L.view_count[i] };
     std::vector<double> w(N), u(s->h_obs_u), q(s->h_obs_v);
-    for (int i = 0; i < s->V; ++i) {
-        const double *src = weights + first[s->L.dev2orig[i]];
-        for (int j = 0; j < s->L.view_count[i]; ++j) {
-            const size_t k = (size_t)s->L.view_obs[i] + j;
-            w[k] = src[j];
-            if (!(src[j] > 0.0)) { u[k] = 0.0; q[k] = 0.0; }
-        }
-    }
+    scatter_weights(weights, s->p_view_count.data(), (int)s->p_view_count.size(), runs, w.data(), u.data(), q.data());
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (!s->d_obs_w) HIP_TRY(s->mem.alloc(&s->d_obs_w, std::max<size_t>(N, 1)));
@@ -434,17 +373,11 @@ static int apply_columns(tscm_solver *s, const ColumnPlan &c)
     return 0;
 }
 
-// the mask words of tscm_solver_set_fixed_intrinsics / tscm_solve_fixed: checked before any device is touched
-static int check_fixed(const unsigned short *fixed, int C)
-{
-    if (fixed) for (int m = 0; m < C; ++m) if (fixed[m] & ~TSCM_FIX_ALL) return fail(TSCM_E_INVALID, "unknown bits in a fixed-intrinsics mask (bits 0-8 only)");
-    return 0;
-}
-
 extern "C" int tscm_solver_set_fixed_intrinsics(tscm_solver *s, const unsigned short *fixed)
 {
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
-    if (int rc = check_fixed(fixed, s->C)) return rc;
+    SolveSpec spec;
+    if (int rc = make_spec(TSCM_LOSS_NONE, 0.0, fixed, s->C, spec)) return rc;
     std::vector<unsigned short> f(s->C, 0);
     if (fixed) f.assign(fixed, fixed + s->C);
     if (f == s->fixed) return 0;
@@ -491,15 +424,14 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     if (4 * lds_eval_bytes > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_eval_gram<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * lds_eval_bytes)));
     // the default Gram kernel: k_eval_gram4 instantiated for this board's pass plan (KS k-steps per pass, ceil(n / 56) passes per view)
     const G4Plan g4 = g4_plan(p->n_points);
-    const EvalKernel eval4 = g4_kernel(g4.ks, g4.passes > 1, false), eval4r = g4_kernel(g4.ks, g4.passes > 1, true);
-    const EvalKernel eval4w = g4_weighted_kernel(g4.ks, g4.passes > 1);
+    for (int f = 0; f < kEvalFamilies; ++f) s->eval[f] = eval_kernel((EvalFamily)f, g4.ks, g4.passes > 1);
     const size_t lds_eval4 = 4 * sizeof(double) * (size_t)eval_gram4_lds_doubles(p->n_points, g4.ks);
     if (lds_eval4 > 160 * 1024) return fail(TSCM_E_UNSUPPORTED, "board with too many corners for the Gram kernel's LDS (more than about 2,000)");
     if (lds_eval4 > 64 * 1024)
-        for (EvalKernel k : { eval4, eval4r, eval4w }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
+        for (int f = G4; f < F32; ++f) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(s->eval[f]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_eval4));
     // the Gram kernels' view chunks are sized for one round of resident waves: LayoutDevice
     int wgs_per_cu = 0;         // resident workgroups per CU (register- and LDS-limited)
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, reinterpret_cast<const void *>(eval4), 256, lds_eval4));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs_per_cu, reinterpret_cast<const void *>(s->eval[G4]), 256, lds_eval4));
     const int waves_per_cu = 4 * std::max(1, std::min(4, wgs_per_cu));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -611,11 +543,9 @@ extern "C" int tscm_solver_create_sharded(const tscm_problem *p, int device, int
     // ---- the evaluation and solve variants -------------------------------------------------------
     s->lds_eval = 4 * lds_eval_bytes;
     s->lds_eval32 = sizeof(double) * (size_t)eval_f32_lds_doubles(p->n_points, g4.ks);
-    s->lds_eval4 = lds_eval4; s->eval4 = eval4; s->eval4r = eval4r; s->eval4w = eval4w;
-    s->eval32 = f32_kernel(g4.ks, g4.passes > 1, false); s->eval32r = f32_kernel(g4.ks, g4.passes > 1, true);
-    s->eval32w = f32_weighted_kernel(g4.ks, g4.passes > 1);
+    s->lds_eval4 = lds_eval4;
     if (s->lds_eval32 > 64 * 1024)
-        for (EvalKernel k : { s->eval32, s->eval32r, s->eval32w }) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
+        for (int f = F32; f < kEvalFamilies; ++f) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(s->eval[f]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->lds_eval32));
     // reduced solve: up to 8 cameras k_solve_nd on the plan of the camera-pair graph (tscm_nd_plan.h), larger rigs in global memory.
     // The columns of the creation plan (no held intrinsics) are every camera-side column that can be free: held intrinsics
     // only ever take columns away, so the sizes below hold for every mask
@@ -777,10 +707,10 @@ static int launch_eval(tscm_solver *s, int cand)
     const dim3 grid(P.n_chunks / 4);
     // (a loss: the ROBUST instantiation; the 16x16 kernel has none -- refused before anything is launched)
     // (corner weights: the WEIGHTED instantiation, with or without a loss; refused with the 16x16 kernel like a loss)
-    const bool robust = s->xp.robust, wt = s->weighted;
-    if (s->xp.gram == Gram::F32) launch_eval_kernel(wt ? s->eval32w : robust ? s->eval32r : s->eval32, grid, s->lds_eval32, s, e0, e1, cand, s->loss);
+    const int variant = s->weighted ? 2 : s->xp.robust ? 1 : 0;       // (EvalFamily: tier + variant)
+    if (s->xp.gram == Gram::F32) launch_eval_kernel(s->eval[F32 + variant], grid, s->lds_eval32, s, e0, e1, cand, s->loss);
     else if (s->xp.gram == Gram::G4)
-        launch_eval_kernel(wt ? s->eval4w : robust ? s->eval4r : s->eval4, grid, s->lds_eval4, s, e0, e1, cand | (s->xp.skip_const_pose ? kEvalSkipConst : 0), s->loss);
+        launch_eval_kernel(s->eval[G4 + variant], grid, s->lds_eval4, s, e0, e1, cand | (s->xp.skip_const_pose ? kEvalSkipConst : 0), s->loss);
     else if (s->xp.gram == Gram::G16Pitch58) launch_eval_kernel(k_eval_gram<58>, grid, s->lds_eval, s, e0, e1, cand);
     else launch_eval_kernel(k_eval_gram<0>, grid, s->lds_eval, s, e0, e1, cand);
     return 0;
@@ -1143,9 +1073,7 @@ static int run_lm(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, in
         // bits as the fused ones (tests/test_gpu_parity.py).  Only if that fails too is it an error.  With a communicator the
         // ranks would have to agree on the re-run: there the late hand-off stays TSCM_E_HIP.
         tscm_options o2;
-        tscm_default_options(&o2, run.m[0]->mono);
-        if (opt_in) std::memcpy(&o2, opt_in, std::min(opt_in->struct_size, sizeof(tscm_options)));
-        o2.struct_size = sizeof(tscm_options);
+        (void)read_options(opt_in, run.m[0]->mono, o2);      // (read without a refusal by the first attempt)
         o2.exec_flags |= TSCM_EXEC_SEPARATE_T_REDUCE | TSCM_EXEC_SEPARATE_BACKSUB | TSCM_EXEC_SEPARATE_CONTROL;
         const std::string first = g_err;
         bool late2 = false;
@@ -1371,97 +1299,99 @@ extern "C" int tscm_solver_solve(tscm_solver *s, const tscm_options *opt, tscm_s
     return 0;
 }
 
-// the weights of a one-shot entry point, before its solver is created: the problem's and their own refusals
-static int precheck_weights(const tscm_problem *p, const double *weights)
+// The refusals of a one-shot entry point ahead of its problem, in the one order tscm.h documents ("Refusal order"): the loss,
+// NULL arguments (null: one of the entry point's is; null_text: its text for that), the mask, the options struct.  The option
+// values follow once the entry point has put its own in (check_options), the problem and the weights in create_configured.
+// in: the caller's arguments (spec_args); spec: checked, what configures the solver.
+static int preamble(const tscm_problem *p, bool null, const char *null_text, const tscm_options *opt_in, const SolveSpec &in, SolveSpec &spec,
+                    tscm_options &opt)
 {
-    if (!weights) return 0;
-    if (int rc = validate(p)) return rc;
-    return check_corner_weights(p->view_count, p->n_views, weights);
+    if (int rc = make_spec(in.loss.kind, in.loss.a, nullptr, 0, spec)) return rc;
+    if (null) return fail(TSCM_E_INVALID, null_text);
+    if (int rc = make_spec(in.loss.kind, in.loss.a, in.fixed, p->n_cameras, spec)) return rc;
+    spec.weights = in.weights;
+    return read_options(opt_in, p->mono, opt);
 }
 
-static int solve_once(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum, const LossArg &loss = LossArg{}, const unsigned short *fixed = nullptr,
-                      const double *weights = nullptr)
+// a solver of `p` on `device` with a checked spec's loss, mask and weights, alive as long as `sp`.  The problem's and the
+// weights' refusals come before the device is touched
+static int create_configured(const tscm_problem *p, int device, const SolveSpec &spec, SolverPtr &sp)
 {
-    if (int rc = precheck_weights(p, weights)) return rc;
+    if (int rc = validate(p)) return rc;
+    if (spec.weights) if (int rc = check_corner_weights(p->view_count, p->n_views, spec.weights)) return rc;
+    if (int rc = create_scoped(p, device, sp)) return rc;
+    sp->loss = spec.loss;
+    if (spec.fixed) if (int rc = tscm_solver_set_fixed_intrinsics(sp.get(), spec.fixed)) return rc;
+    if (spec.weights) if (int rc = tscm_solver_set_corner_weights(sp.get(), spec.weights)) return rc;
+    return 0;
+}
+
+// one solve on the calling thread's device, with a checked spec
+static int solve_configured(const tscm_problem *p, const tscm_options *opt, const SolveSpec &spec, tscm_summary *sum)
+{
     int dev = 0;
     (void)hipGetDevice(&dev);
     SolverPtr sp;
-    if (int rc = create_scoped(p, dev, sp)) return rc;
-    sp->loss = loss;
-    if (fixed) if (int rc = tscm_solver_set_fixed_intrinsics(sp.get(), fixed)) return rc;
-    if (weights) if (int rc = tscm_solver_set_corner_weights(sp.get(), weights)) return rc;
+    if (int rc = create_configured(p, dev, spec, sp)) return rc;
     return tscm_solver_solve(sp.get(), opt, sum);
+}
+
+static int solve_once(const tscm_problem *p, const tscm_options *opt_in, const SolveSpec &in, tscm_summary *sum)
+{
+    SolveSpec spec;
+    tscm_options opt;
+    if (int rc = preamble(p, !p || !sum, "NULL argument", opt_in, in, spec, opt)) return rc;
+    if (int rc = check_options(opt, spec.loss.kind, spec.weights != nullptr)) return rc;
+    return solve_configured(p, opt_in, spec, sum);
 }
 
 extern "C" int tscm_solve_weighted(const tscm_problem *p, const tscm_options *opt, const double *weights, const unsigned short *fixed, int kind, double scale,
                                    tscm_summary *sum)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
-    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
-    tscm_options o;
-    if (int rc = read_options(opt, p->mono, o)) return rc;
-    if (int rc = check_options(o, L.kind, weights != nullptr)) return rc;
-    return solve_once(p, opt, sum, L, fixed, weights);
+    return solve_once(p, opt, spec_args(kind, scale, fixed, weights), sum);
 }
 
 extern "C" int tscm_solve_multi(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum)
 {
-    if (p && p->mono) return fail(TSCM_E_INVALID, "tscm_solve_multi called with a mono problem");
-    return solve_once(p, opt, sum);
+    if (!p) return validate(p);         // (these two name the problem)
+    if (p->mono) return fail(TSCM_E_INVALID, "tscm_solve_multi called with a mono problem");
+    return solve_once(p, opt, spec_args(TSCM_LOSS_NONE, 0.0, nullptr, nullptr), sum);
 }
 
 extern "C" int tscm_solve_mono(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum)
 {
-    if (p && !p->mono) return fail(TSCM_E_INVALID, "tscm_solve_mono called with a multi-camera problem");
-    return solve_once(p, opt, sum);
+    if (!p) return validate(p);
+    if (!p->mono) return fail(TSCM_E_INVALID, "tscm_solve_mono called with a multi-camera problem");
+    return solve_once(p, opt, spec_args(TSCM_LOSS_NONE, 0.0, nullptr, nullptr), sum);
 }
 
 extern "C" int tscm_solve_robust(const tscm_problem *p, const tscm_options *opt, int kind, double scale, tscm_summary *sum)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
-    tscm_options o;
-    if (int rc = read_options(opt, p->mono, o)) return rc;
-    if (int rc = check_options(o, L.kind)) return rc;
-    return solve_once(p, opt, sum, L);
+    return solve_once(p, opt, spec_args(kind, scale, nullptr, nullptr), sum);
 }
 
 extern "C" int tscm_solve_fixed(const tscm_problem *p, const tscm_options *opt, const unsigned short *fixed, int kind, double scale, tscm_summary *sum)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    if (!p || !sum) return fail(TSCM_E_INVALID, "NULL argument");
-    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
-    tscm_options o;
-    if (int rc = read_options(opt, p->mono, o)) return rc;
-    if (int rc = check_options(o, L.kind)) return rc;
-    return solve_once(p, opt, sum, L, fixed);
+    return solve_once(p, opt, spec_args(kind, scale, fixed, nullptr), sum);
 }
 
 // The candidate of a solve's first trust-region step: the solve itself, stopped after one iteration (termination
 // tolerances zeroed, so nothing ends it before the step is taken).  The first iteration writes its candidate into buffer 1
 // (ctrl->cur = 0 at the start); k_end_solve / k_finish_solve copy it into buffer 0 only if the step was accepted and never
 // write buffer 1, so buffer 1 holds the candidate whether the step was accepted or not
-static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *cam_rt, double *intr,
-                     double *board_rt, int *valid, tscm_summary *summary, const unsigned short *fixed = nullptr, const double *weights = nullptr)
+static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_in, const SolveSpec &in, double *cam_rt, double *intr,
+                     double *board_rt, int *valid, tscm_summary *summary)
 {
+    SolveSpec spec;
     tscm_options opt;
-    int rc = read_options(opt_in, p ? p->mono : 0, opt);
+    int rc = preamble(p, !p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards), "NULL argument", opt_in, in, spec, opt);
     if (rc) return rc;
     opt.max_num_iterations = 1;
     opt.function_tolerance = opt.gradient_tolerance = opt.parameter_tolerance = 0.0;
-    if ((rc = check_options(opt, loss.kind, weights != nullptr))) return rc;
-    if (!p || !intr || !valid || (!cam_rt && !p->mono) || (!board_rt && p->n_boards)) return fail(TSCM_E_INVALID, "NULL argument");
-    if ((rc = precheck_weights(p, weights))) return rc;
+    if ((rc = check_options(opt, spec.loss.kind, spec.weights != nullptr))) return rc;
     SolverPtr sp;
-    if ((rc = create_scoped(p, device, sp))) return rc;
+    if ((rc = create_configured(p, device, spec, sp))) return rc;
     tscm_solver *s = sp.get();
-    s->loss = loss;
-    if (fixed && (rc = tscm_solver_set_fixed_intrinsics(s, fixed))) return rc;
-    if (weights && (rc = tscm_solver_set_corner_weights(s, weights))) return rc;
     if ((rc = tscm_solver_upload_params(s, p->cam_rt, p->intr, p->board_rt))) return rc;
     tscm_summary sum;
     if ((rc = tscm_solver_solve_resident(s, &opt, &sum, 1))) return rc;
@@ -1477,35 +1407,25 @@ static int eval_step(const tscm_problem *p, int device, const tscm_options *opt_
 extern "C" int tscm_eval_step_ex(const tscm_problem *p, int device, const tscm_options *opt, double *cam_rt, double *intr,
                                  double *board_rt, int *valid, tscm_summary *summary)
 {
-    return eval_step(p, device, opt, LossArg{}, cam_rt, intr, board_rt, valid, summary);
+    return eval_step(p, device, opt, spec_args(TSCM_LOSS_NONE, 0.0, nullptr, nullptr), cam_rt, intr, board_rt, valid, summary);
 }
 
 extern "C" int tscm_eval_step_robust(const tscm_problem *p, int device, const tscm_options *opt, int kind, double scale, double *cam_rt,
                                      double *intr, double *board_rt, int *valid, tscm_summary *summary)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary);
+    return eval_step(p, device, opt, spec_args(kind, scale, nullptr, nullptr), cam_rt, intr, board_rt, valid, summary);
 }
 
 extern "C" int tscm_eval_step_fixed(const tscm_problem *p, int device, const tscm_options *opt, const unsigned short *fixed, int kind, double scale,
                                     double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    if (!p) return fail(TSCM_E_INVALID, "NULL argument");
-    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
-    return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary, fixed);
+    return eval_step(p, device, opt, spec_args(kind, scale, fixed, nullptr), cam_rt, intr, board_rt, valid, summary);
 }
 
 extern "C" int tscm_eval_step_weighted(const tscm_problem *p, int device, const tscm_options *opt, const double *weights, const unsigned short *fixed,
                                        int kind, double scale, double *cam_rt, double *intr, double *board_rt, int *valid, tscm_summary *summary)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    if (!p) return fail(TSCM_E_INVALID, "NULL argument");
-    if (int rc = check_fixed(fixed, p->n_cameras)) return rc;
-    return eval_step(p, device, opt, L, cam_rt, intr, board_rt, valid, summary, fixed, weights);
+    return eval_step(p, device, opt, spec_args(kind, scale, fixed, weights), cam_rt, intr, board_rt, valid, summary);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1632,19 +1552,19 @@ static int solver_normal_equations(tscm_solver *s, const tscm_options &opt, bool
     return 0;
 }
 
-static int eval_normal_equations(const tscm_problem *p, int device, const tscm_options *opt_in, const LossArg &loss, double *board_gram,
-                                 double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost, const double *weights = nullptr)
+// the one-shot normal equations of every entry point that has them (tscm_host.h: tscm_covariance's blocks too).  A mask plays
+// no part in an evaluation: in.fixed is not looked at
+int tscm_eval_normal_equations_spec(const tscm_problem *p, int device, const tscm_options *opt_in, const SolveSpec &in, double *board_gram,
+                                    double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
 {
+    SolveSpec spec;
     tscm_options opt;
-    int rc = read_options(opt_in, p ? p->mono : 0, opt);
+    int rc = preamble(p, !p, "problem is NULL", opt_in, spec_args(in.loss.kind, in.loss.a, nullptr, in.weights), spec, opt);
     if (rc) return rc;
     opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
-    if ((rc = check_options(opt, loss.kind, weights != nullptr))) return rc;
-    if ((rc = precheck_weights(p, weights))) return rc;
+    if ((rc = check_options(opt, spec.loss.kind, spec.weights != nullptr))) return rc;
     SolverPtr sp;
-    if ((rc = create_scoped(p, device, sp))) return rc;
-    sp->loss = loss;
-    if (weights && (rc = tscm_solver_set_corner_weights(sp.get(), weights))) return rc;
+    if ((rc = create_configured(p, device, spec, sp))) return rc;
     return solver_normal_equations(sp.get(), opt, false, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
 }
 
@@ -1667,27 +1587,22 @@ extern "C" int tscm_solver_eval_normal_equations(tscm_solver *s, const tscm_opti
 extern "C" int tscm_eval_normal_equations_ex(const tscm_problem *p, int device, const tscm_options *opt, double *board_gram,
                                              double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost)
 {
-    return eval_normal_equations(p, device, opt, LossArg{}, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+    return tscm_eval_normal_equations_spec(p, device, opt, spec_args(TSCM_LOSS_NONE, 0.0, nullptr, nullptr), board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
 }
 
 extern "C" int tscm_eval_normal_equations_robust(const tscm_problem *p, int device, const tscm_options *opt, int kind, double scale,
                                                  double *board_gram, double *board_grad, double *view_cross, double *cam_gram,
                                                  double *cam_grad, double *cost)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    return eval_normal_equations(p, device, opt, L, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+    return tscm_eval_normal_equations_spec(p, device, opt, spec_args(kind, scale, nullptr, nullptr), board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
 }
 
 extern "C" int tscm_eval_normal_equations_weighted(const tscm_problem *p, int device, const tscm_options *opt, const double *weights, int kind,
                                                    double scale, double *board_gram, double *board_grad, double *view_cross, double *cam_gram,
                                                    double *cam_grad, double *cost)
 {
-    LossArg L;
-    if (int rc = make_loss(kind, scale, L)) return rc;
-    return eval_normal_equations(p, device, opt, L, board_gram, board_grad, view_cross, cam_gram, cam_grad, cost, weights);
+    return tscm_eval_normal_equations_spec(p, device, opt, spec_args(kind, scale, nullptr, weights), board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
 }
-
 
 // k_project (3 -> 2) and k_unproject (2 -> 3): n rows of `in` through one camera's intrinsics
 static int map_rows(void (*kernel)(const double *, const double *, int, double *), const char *who, const double *intr9, const double *in, int w_in,
@@ -1794,8 +1709,7 @@ static int solve_mono_batch(const tscm_problem *problems, int n_problems, int de
         std::string err;
         if (int rc = plan_batch(problems, n_problems, opt, fixed, loss_kind, loss_scale, bp, err)) return fail(rc, err);
     }
-    LossArg loss;
-    if (int rc = make_loss(loss_kind, loss_scale, loss)) return rc;
+    const LossArg loss = bp.loss;
     // corner weights: checked per problem before any device is touched; w_sum / n_kept of each for its summary
     bool any_w = false;
     std::vector<double> w_sum(n_problems, 0.0);
@@ -1820,21 +1734,12 @@ static int solve_mono_batch(const tscm_problem *problems, int n_problems, int de
             for (int j = 0; j < bp.slot_count[s]; ++j) { ou[bp.slot_obs[s] + j] = p.obs_u[p.view_offset[v] + j]; ov[bp.slot_obs[s] + j] = p.obs_v[p.view_offset[v] + j]; }
         }
         // the weights in slot order (a problem without weights: 1); a masked corner's observation is uploaded as 0, 0
-        std::vector<double> ow(any_w ? (size_t)bp.N : 0, 1.0);
-        std::vector<std::vector<long> > first(any_w ? n_problems : 0);      // per weighted problem: view -> its first corner in corner order
-        for (int i = 0; any_w && i < n_problems; ++i) {
-            if (!weights[i]) continue;
-            first[i].assign((size_t)problems[i].n_views + 1, 0);
-            for (int v = 0; v < problems[i].n_views; ++v) first[i][v + 1] = first[i][v] + problems[i].view_count[v];
-        }
-        for (int s = 0; any_w && s < ns; ++s) {
-            const int i = bp.dev_prob[bp.slot_prob[s]];
-            if (!weights[i]) continue;
-            for (int j = 0; j < bp.slot_count[s]; ++j) {
-                const double x = weights[i][first[i][bp.slot_view[s]] + j];
-                ow[bp.slot_obs[s] + j] = x;
-                if (!(x > 0.0)) { ou[bp.slot_obs[s] + j] = 0.0; ov[bp.slot_obs[s] + j] = 0.0; }
-            }
+        std::vector<double> ow(any_w ? (size_t)bp.N : 0);
+        for (int k = 0; any_w && k < K; ++k) {
+            const tscm_problem &p = problems[bp.dev_prob[k]];
+            std::vector<CornerRun> runs;
+            for (int s = bp.slot_ptr[k]; s < bp.slot_ptr[k + 1]; ++s) runs.push_back(CornerRun{ bp.slot_view[s], bp.slot_obs[s], bp.slot_count[s] });
+            scatter_weights(weights[bp.dev_prob[k]], p.view_count, p.n_views, runs, ow.data(), ou.data(), ov.data());
         }
         for (int k = 0; k < K; ++k) {
             const tscm_problem &p = problems[bp.dev_prob[k]];
@@ -1929,7 +1834,7 @@ static int solve_mono_batch(const tscm_problem *problems, int n_problems, int de
     // problems without a single corner: what the single-problem entry point returns for them
     for (int i = 0; i < n_problems; ++i) {
         if (bp.dev_of[i] >= 0) continue;
-        if (int rc = solve_once(&problems[i], opt_in, &summaries[i], loss, fixed ? fixed + i : nullptr)) return rc;
+        if (int rc = solve_configured(&problems[i], opt_in, SolveSpec{ loss, fixed ? fixed + i : nullptr, nullptr }, &summaries[i])) return rc;
     }
     // the batch's times in every summary
     const double t_end = wall();
