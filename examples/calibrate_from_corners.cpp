@@ -4,12 +4,16 @@
 //   g++ -std=c++11 -I include examples/calibrate_from_corners.cpp -L tscm_calib_amd/csrc -ltscm_hip
 //       -Wl,-rpath,$PWD/tscm_calib_amd/csrc -o examples/calibrate_from_corners        (one command line)
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
-//                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
+//                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]]
 //                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance]
 //                                   [--uncertainty STEP[,INV_DISTANCE]]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
+//    --prior: Gaussian priors (Ceres' NormalPrior, tscm.h) on the named intrinsics of every camera, in every solve, about the
+//    values that solve starts from; sigma in the parameter's unit against a corner sigma of one pixel; names as for --fix.
+//    Each camera prints the priors that count (a held intrinsic has none): `camera_m mono|rig prior name mean +- sigma`; the
+//    covariance includes the joint solve's.
 //    --ransac-mask (with --ransac): the inlier masks are the corner masks of every refinement, the joint solve and the covariance
 //                  included; prints the number of corners masked per camera
 //    --ransac: the start poses come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view without consensus leaves
@@ -35,6 +39,8 @@ int main(int argc, char **argv)
     int loss = TSCM_LOSS_NONE;
     double loss_scale = 1.0;
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
+    bool use_prior = false;                         // --prior (the last one counts)
+    double prior_sigma[7] = { 0, 0, 0, 0, 0, 0, 0 };
     bool bad_args = argc < 3, use_ransac = false, ransac_mask = false, covariance = false, uncertainty = false;
     double unc_step = 0.0, unc_inv_distance = 0.0;
     tscm_ransac_params ransac;
@@ -52,6 +58,9 @@ int main(int argc, char **argv)
             unsigned short w = 0;
             bad_args = !tscm::fixed_list_mask(argv[++i], w);
             fix = (unsigned short)(fix | w);
+        } else if (!std::strcmp(argv[i], "--prior") && i + 1 < argc) {
+            use_prior = true;
+            bad_args = !tscm::parse_prior_option(argv[++i], prior_sigma);
         } else if (!std::strcmp(argv[i], "--ransac") && i + 1 < argc) {
             use_ransac = true;
             bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
@@ -77,7 +86,7 @@ int main(int argc, char **argv)
     bad_args = bad_args || (ransac_mask && !use_ransac);
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -102,8 +111,10 @@ int main(int argc, char **argv)
             }
             cameras[m].set_loss(loss, loss_scale);
             cameras[m].set_fixed_intrinsics(fixed);                          // (a fresh calibrate starts at xi = lambda = 0)
+            if (use_prior) cameras[m].set_prior_sigmas(prior_sigma);
             if (use_ransac) cameras[m].set_ransac(&ransac, ransac_mask);
             const bool ok = cameras[m].calibrate(pixels, has, worlds, image, board);
+            if (use_prior) tscm::print_effective_priors(cameras[m].last_priors_, 0, m, fixed, "mono");
             if (use_ransac) tscm::print_ransac_summary(cameras[m], has, m);
             if (ransac_mask) tscm::print_ransac_masked(cameras[m], m);
             std::printf("camera %d: %s, rmse %.4f px, fx %.3f fy %.3f cx %.3f cy %.3f xi %.4f lambda %.4f alpha %.4f\n", m, ok ? "converged" : "NOT converged",
@@ -117,6 +128,14 @@ int main(int argc, char **argv)
             for (int m = 0; m < C; ++m) mul_calib.set_fixed_intrinsics(m, fixed);
             const std::vector<std::vector<std::vector<double> > > masks = tscm::ransac_corner_masks(cameras);
             if (ransac_mask) mul_calib.set_corner_weights(&masks);            // the joint solve and the covariance take the masks too
+            tscm::CameraPriors priors;                                       // about the values the joint solve starts from
+            if (use_prior) {
+                std::vector<double> start;
+                for (int m = 0; m < C; ++m) start.insert(start.end(), mul_calib.cameras_[m].intrinsic_.begin(), mul_calib.cameras_[m].intrinsic_.end());
+                priors = tscm::intrinsic_priors_about(start, prior_sigma);
+                mul_calib.set_camera_priors(&priors);
+                for (int m = 0; m < C; ++m) tscm::print_effective_priors(priors, (size_t)m, m, fixed, "rig");
+            }
             mul_calib.calibrate();                                           // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             for (int m = 0; m < C; ++m) std::printf("camera_%d reprojection error: %.6f\n", m, mul_calib.camera_error[m]);

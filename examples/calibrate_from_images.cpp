@@ -4,9 +4,12 @@
 // Images are 8-bit binary PGM files (P5); the list file holds one line per camera: "<n_frames> path_0 path_1 ..." with "-"
 // for a frame the camera has no image of.  The viewer and the drawing calls of main.cpp are left out.
 //   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
-//                                [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]
+//                                [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]
 //   (--model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
+//    --prior: Gaussian priors (Ceres' NormalPrior, tscm.h) on the named intrinsics of every camera, in every solve, about the
+//    values that solve starts from; sigma in the parameter's unit against a corner sigma of one pixel; names as for --fix.
+//    Each camera prints the priors that count: `camera_m mono|rig prior name mean +- sigma` (mono: of its last refinement).
 //    --ransac-mask (with --ransac): the inlier masks are the corner masks of every refinement and of the joint solve; prints the
 //                  number of corners masked per camera
 //    --ransac: the start poses of both calibrate() calls come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view
@@ -99,6 +102,8 @@ int main(int argc, char **argv)
 {
     std::vector<const char *> pos;                  // positional arguments: list, yaml, then cols rows pitch
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
+    bool use_prior = false;                         // --prior (the last one counts)
+    double prior_sigma[7] = { 0, 0, 0, 0, 0, 0, 0 };
     bool bad_args = false, use_ransac = false, ransac_mask = false;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
@@ -109,6 +114,9 @@ int main(int argc, char **argv)
             unsigned short w = 0;
             bad_args = !tscm::fixed_list_mask(argv[++i], w);
             fix = (unsigned short)(fix | w);
+        } else if (!std::strcmp(argv[i], "--prior") && i + 1 < argc) {
+            use_prior = true;
+            bad_args = !tscm::parse_prior_option(argv[++i], prior_sigma);
         } else if (!std::strcmp(argv[i], "--ransac") && i + 1 < argc) {
             use_ransac = true;
             bad_args = !tscm::parse_ransac_option(argv[++i], &ransac);
@@ -121,7 +129,7 @@ int main(int argc, char **argv)
         }
     }
     if (bad_args || pos.size() < 2 || (ransac_mask && !use_ransac)) {
-        std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] "
+        std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] "
                      "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]\n", argv[0]);
         return 2;
     }
@@ -149,8 +157,10 @@ int main(int argc, char **argv)
         for (size_t m = 0; m < images.size(); ++m) {
             std::printf("camera %zu: ", m);
             cameras[m].set_fixed_intrinsics(fixed);                            // (the first calibrate starts at xi = lambda = 0)
+            if (use_prior) cameras[m].set_prior_sigmas(prior_sigma);
             if (use_ransac) cameras[m].set_ransac(&ransac, ransac_mask);
             monocular_calib(images[m], size, board, worlds, cameras[m]);
+            if (use_prior) tscm::print_effective_priors(cameras[m].last_priors_, 0, (int)m, fixed, "mono");
             if (ransac_mask) tscm::print_ransac_masked(cameras[m], (int)m);
         }
         if (cameras.size() > 1) {
@@ -158,6 +168,14 @@ int main(int argc, char **argv)
             for (size_t m = 0; m < cameras.size(); ++m) mul_calib.set_fixed_intrinsics((int)m, fixed);
             const std::vector<std::vector<std::vector<double> > > masks = tscm::ransac_corner_masks(cameras);
             if (ransac_mask) mul_calib.set_corner_weights(&masks);              // the joint solve takes the masks too
+            tscm::CameraPriors priors;                                         // about the values the joint solve starts from
+            if (use_prior) {
+                std::vector<double> start;
+                for (size_t m = 0; m < cameras.size(); ++m) start.insert(start.end(), mul_calib.cameras_[m].intrinsic_.begin(), mul_calib.cameras_[m].intrinsic_.end());
+                priors = tscm::intrinsic_priors_about(start, prior_sigma);
+                mul_calib.set_camera_priors(&priors);
+                for (size_t m = 0; m < cameras.size(); ++m) tscm::print_effective_priors(priors, m, (int)m, fixed, "rig");
+            }
             mul_calib.calibrate();                                             // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             std::printf("average reproject error: %.6f\n", mul_calib.mean_error);

@@ -261,8 +261,8 @@ int tscm_solver_exchange_time(tscm_solver *s, int *n_T, double *ms_T, int *n_H, 
 
 /* Refusal order of the one-shot entry points ------------------------------------
  * tscm_solve_*, tscm_eval_step_* and tscm_eval_normal_equations_* are each one path behind
- * several spellings: an export without a loss, a mask or weights is the most general one of
- * its family (_weighted) called with TSCM_LOSS_NONE and NULLs, bit for bit.  All of them
+ * several spellings: an export without a loss, a mask, weights or priors is the most general
+ * one of its family (_prior) called with TSCM_LOSS_NONE and NULLs, bit for bit.  All of them
  * refuse, before any device is touched and in this order:
  *   1. the loss: an unknown kind, a scale that is not finite and > 0;
  *   2. NULL arguments (tscm_solve_multi / _mono: their mono / multi guard);
@@ -270,7 +270,7 @@ int tscm_solver_exchange_time(tscm_solver *s, int *n_T, double *ms_T, int *n_H, 
  *   4. the options struct: a struct_size this library does not know;
  *   5. the option values: max_num_iterations, unknown exec_flags bits, TSCM_EXEC_GRAM_16X16
  *      with a loss or with weights (TSCM_E_UNSUPPORTED);
- *   6. the problem, then the weights.
+ *   6. the problem, then the weights, then the camera priors.
  * All TSCM_E_INVALID unless said otherwise.  The device index (TSCM_E_NO_DEVICE) and what the
  * device cannot hold (TSCM_E_UNSUPPORTED) follow.  tscm_solve_mono_batch* and tscm_covariance*
  * state their own order below.
@@ -518,6 +518,52 @@ int tscm_solve_mono_batch_weighted(const tscm_problem *problems, int n_problems,
 int tscm_covariance_weighted(const tscm_problem *problem, int device_index, const unsigned short *fixed, const double *weights,
                              int loss_kind, double loss_scale, double *cam_cov, double *board_cov, double *cam_rt_std,
                              double *intr_std, double *board_rt_std, tscm_covariance_info *info);
+
+/* ------------------------------------------------------------------ Gaussian priors on camera parameters
+ * Ceres' NormalPrior on single coordinates of a camera's pose or intrinsic block: one more residual sqrt(w_k) (x_k - mean_k)
+ * per coordinate k with a weight w_k > 0 -- "about this value, give or take sigma", w = (sigma_pixel / sigma)^2.
+ *   - Objective.  The solve's objective (loss and corner weights included) plus 1/2 sum_k w_k (x_k - mean_k)^2 over the
+ *     camera-side coordinates.  Every prior is a residual block of its own with Jacobian sqrt(w_k) and no loss.
+ *   - Where it counts.  In everything a Jacobian row takes part in: the column norms behind the Jacobi scaling, the LM
+ *     diagonal, the gradient and its norms, the cost and the model cost change, tscm_eval_normal_equations* (the diagonal of
+ *     cam_gram, cam_grad, cost) and tscm_eval_step*.  Board blocks and view_cross do not change by a bit.
+ *   - Pose.  The pose prior is on the raw 6-vector (angle-axis and translation differences as stored): a NormalPrior on rt_.
+ *   - Coordinates that are not free.  A weight is taken as 0 (no cost, no gradient) on a coordinate that is not a free column of
+ *     the solve: a held intrinsic, b, c, the pose of a mono problem or of a cam_pose_constant camera, a camera without corners.
+ *     tscm_solver_set_fixed_intrinsics re-derives the effective weights.  tscm_eval_normal_equations* takes no mask: there
+ *     every column that can be free counts.
+ *   - Summary.  n_residual_blocks stays the corner count; with an effective prior, rmse is the plain pixel RMSE at the final
+ *     parameters (sqrt(sum omega s / sum omega) with corner weights), not sqrt(2 final_cost / N): final_cost holds the prior.
+ *   - Covariance.  n_residuals = 2 N + P with P the effective prior rows, sigma2 = 2 cost / (n_residuals - n_free) with the cost
+ *     including the prior, and the blocks include it: a parameter that only the prior determines has a finite variance.
+ *   - No floating-point atomics: two calls give the same bytes.  priors = NULL, or every effective weight 0, is the solve
+ *     without priors: the same launches, summaries and parameters bit for bit.
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a struct_size other than
+ * sizeof(tscm_camera_priors); a mean given without its weight or the reverse; a weight that is negative, NaN or infinite; a
+ * mean that is not finite where its weight is > 0.  In the refusal order of the one-shot entry points the priors follow the
+ * corner weights.  Not served: a sharded solver (tscm_solver_create_sharded with world > 1: TSCM_E_UNSUPPORTED); and
+ * tscm_solve_mono_batch* takes no priors argument.
+ *   problem.AddResidualBlock(new NormalPrior(A, mean), nullptr, intrinsic)  with A = diag(sqrt(w))                          */
+typedef struct tscm_camera_priors {
+    size_t struct_size;                          /* sizeof(tscm_camera_priors), set by the caller                            */
+    const double *cam_rt_mean, *cam_rt_weight;   /* [C*6] in the order of tscm_problem.cam_rt, or both NULL                  */
+    const double *intr_mean,   *intr_weight;     /* [C*9] in the order of tscm_problem.intr,   or both NULL                  */
+} tscm_camera_priors;
+/* the priors of every later solve / solve_resident / tscm_solver_eval_normal_equations of s; the arrays are copied.  May be
+ * called between solves; NULL clears.                                                                                       */
+int tscm_solver_set_camera_priors(tscm_solver *s, const tscm_camera_priors *priors);
+/* tscm_solve_weighted, tscm_eval_normal_equations_weighted, tscm_eval_step_weighted and tscm_covariance_weighted with priors */
+int tscm_solve_prior(const tscm_problem *problem, const tscm_options *opt, const double *weights, const unsigned short *fixed, int kind,
+                     double scale, const tscm_camera_priors *priors, tscm_summary *summary);
+int tscm_eval_normal_equations_prior(const tscm_problem *problem, int device_index, const tscm_options *opt, const double *weights, int kind,
+                                     double scale, const tscm_camera_priors *priors, double *board_gram, double *board_grad,
+                                     double *view_cross, double *cam_gram, double *cam_grad, double *cost);
+int tscm_eval_step_prior(const tscm_problem *problem, int device_index, const tscm_options *opt, const double *weights,
+                         const unsigned short *fixed, int kind, double scale, const tscm_camera_priors *priors, double *cam_rt,
+                         double *intr, double *board_rt, int *valid, tscm_summary *summary);
+int tscm_covariance_prior(const tscm_problem *problem, int device_index, const unsigned short *fixed, const double *weights,
+                          int loss_kind, double loss_scale, const tscm_camera_priors *priors, double *cam_cov, double *board_cov,
+                          double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info);
 
 /* ------------------------------------------------------------------ projection uncertainty maps
  * The covariance of a projected pixel under the joint parameter covariance of tscm_covariance: what a standard deviation

@@ -27,6 +27,8 @@
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
+//   AddResidualBlock(new NormalPrior(A, mean), NULL, x)    CameraPriors, set_camera_priors on both classes, set_prior_sigmas,
+//                                                          parse_prior_option                  -> tscm_solve_prior, tscm_covariance_prior
 //   (cv::solvePnPRansac inside estimate_extrinsic)         TripleSphereCamera::estimate_extrinsic_ransac, set_ransac,
 //                                                          parse_ransac_option                 -> tscm_estimate_extrinsic_ransac
 // (*) deterministic planar PnP in place of cv::solvePnPRansac (see tscm.h)
@@ -107,6 +109,67 @@ inline bool fixed_list_mask(const char *list, unsigned short &word)
     return true;
 }
 
+// Gaussian priors on camera parameters (tscm.h, "Gaussian priors": Ceres' NormalPrior on single coordinates) in the mirror's
+// shape: mean and weight per coordinate, cam_rt_* [C*6] on the raw pose vectors, intr_* [C*9] on fx fy cx cy xi lambda alpha b c;
+// a pair may be empty.  Weight = (pixel sigma / sigma)^2, 0 = no prior; a weight on a coordinate that is not free counts as 0.
+struct CameraPriors {
+    std::vector<double> cam_rt_mean, cam_rt_weight, intr_mean, intr_weight;
+    // the C struct over these vectors (valid while they are)
+    tscm_camera_priors c_struct() const
+    {
+        tscm_camera_priors p = tscm_camera_priors();
+        p.struct_size = sizeof(tscm_camera_priors);
+        p.cam_rt_mean = cam_rt_mean.empty() ? NULL : cam_rt_mean.data(); p.cam_rt_weight = cam_rt_weight.empty() ? NULL : cam_rt_weight.data();
+        p.intr_mean = intr_mean.empty() ? NULL : intr_mean.data(); p.intr_weight = intr_weight.empty() ? NULL : intr_weight.data();
+        return p;
+    }
+};
+// Command-line form of intrinsic priors, for the example programs: "xi:0.1,lambda:0.05" -> sigma[7] by the names of
+// fixed_list_mask (0 where none is given); false for an unknown name, a missing or malformed sigma, or one that is not finite and > 0.
+inline bool parse_prior_option(const char *list, double sigma[7])
+{
+    static const char *const names[7] = { "fx", "fy", "cx", "cy", "xi", "lambda", "alpha" };
+    const std::string l(list);
+    for (int k = 0; k < 7; ++k) sigma[k] = 0.0;
+    for (size_t b = 0; b <= l.size();) {
+        size_t e = l.find(',', b);
+        if (e == std::string::npos) e = l.size();
+        const std::string item = l.substr(b, e - b);
+        const size_t colon = item.find(':');
+        if (colon == std::string::npos || colon + 1 >= item.size()) return false;
+        int k = 0;
+        while (k < 7 && item.substr(0, colon) != names[k]) ++k;
+        if (k == 7) return false;
+        const std::string num = item.substr(colon + 1);
+        if (num[0] != '.' && (num[0] < '0' || num[0] > '9')) return false;
+        char *end = NULL;
+        const double v = std::strtod(num.c_str(), &end);
+        if (*end != '\0' || !(v > 0.0) || !std::isfinite(v)) return false;
+        sigma[k] = v;
+        b = e + 1;
+    }
+    return true;
+}
+// priors on the intrinsics of n cameras about the values intr [n*9] holds now: weight 1 / sigma[k]^2 where sigma[k] > 0
+inline CameraPriors intrinsic_priors_about(const std::vector<double> &intr, const double sigma[7])
+{
+    CameraPriors p;
+    p.intr_mean = intr;
+    p.intr_weight.assign(intr.size(), 0.0);
+    for (size_t i = 0; i < intr.size(); ++i) if (i % 9 < 7 && sigma[i % 9] > 0.0) p.intr_weight[i] = 1.0 / (sigma[i % 9] * sigma[i % 9]);
+    return p;
+}
+// what the example programs print: camera m's priors that count under its held intrinsics `fixed`, one line each
+inline void print_effective_priors(const CameraPriors &p, size_t cam, int m, unsigned short fixed, const char *stage)
+{
+    static const char *const names[7] = { "fx", "fy", "cx", "cy", "xi", "lambda", "alpha" };
+    for (int k = 0; k < 7; ++k) {
+        const size_t i = 9 * cam + (size_t)k;
+        if (i >= p.intr_weight.size() || !(p.intr_weight[i] > 0.0) || ((fixed >> k) & 1)) continue;
+        std::printf("camera_%d %s prior %s %.17g +- %.17g\n", m, stage, names[k], p.intr_mean[i], 1.0 / std::sqrt(p.intr_weight[i]));
+    }
+}
+
 // cv::Rodrigues(r -> R), the conversion update_param() does on the host (multi_calib.h:43-45,105-106)
 inline Mat33 rodrigues(const double r[3])
 {
@@ -153,6 +216,22 @@ public:
         use_weights_ = weights != NULL;
         corner_weights_ = weights ? *weights : std::vector<std::vector<double> >();
     }
+    // Gaussian priors of refinement() (tscm.h, "Gaussian priors"): a CameraPriors of ONE camera -- intr_* [9]; the pose of a mono
+    // problem is not free, so cam_rt_* counts for nothing -- or NULL for none (the default).  Copied.
+    void set_camera_priors(const CameraPriors *priors)
+    {
+        use_priors_ = priors != NULL;
+        priors_ = priors ? *priors : CameraPriors();
+    }
+    // ... or priors about the values each refinement() STARTS from -- calibrate() estimates them first -- with these standard
+    // deviations in the unit of a pixel's (sigma[k] of fx fy cx cy xi lambda alpha, 0 = none); NULL = none.  Explicit priors
+    // (set_camera_priors) come first.  last_priors_: what the last refinement() took.
+    void set_prior_sigmas(const double *sigma7)
+    {
+        use_sigmas_ = sigma7 != NULL;
+        for (int k = 0; k < 7; ++k) prior_sigma_[k] = sigma7 ? sigma7[k] : 0.0;
+    }
+    CameraPriors last_priors_;
     // weight of corner j of view i in the next refinement(); *weighted: whether there are weights at all
     double corner_weight(size_t i, size_t j, bool *weighted) const
     {
@@ -188,7 +267,9 @@ public:
         P.obs_u = u.data(); P.obs_v = v.data(); P.intr = intrinsic_.data(); P.board_rt = rt.data(); P.mono = 1;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 1);
-        check(tscm_solve_weighted(&P, &o, weighted ? w.data() : NULL, fixed_ ? &fixed_ : NULL, loss_kind_, loss_scale_, &summary));
+        last_priors_ = use_priors_ ? priors_ : use_sigmas_ ? intrinsic_priors_about(intrinsic_, prior_sigma_) : CameraPriors();
+        const tscm_camera_priors cp = last_priors_.c_struct();
+        check(tscm_solve_prior(&P, &o, weighted ? w.data() : NULL, fixed_ ? &fixed_ : NULL, loss_kind_, loss_scale_, use_priors_ || use_sigmas_ ? &cp : NULL, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
         return summary.termination_type == TSCM_CONVERGENCE;             // TS.cpp:281
     }
@@ -364,6 +445,9 @@ public:
     tscm_ransac_params ransac_;
     bool use_weights_ = false;                // set_corner_weights()
     std::vector<std::vector<double> > corner_weights_;
+    bool use_priors_ = false, use_sigmas_ = false;      // set_camera_priors(), set_prior_sigmas()
+    CameraPriors priors_;
+    double prior_sigma_[7] = { 0, 0, 0, 0, 0, 0, 0 };
 
     // TS.cpp:62-74
     void poses_from_Rt()
@@ -630,6 +714,14 @@ public:
         use_weights_ = weights != NULL;
         corner_weights_ = weights ? *weights : std::vector<std::vector<std::vector<double> > >();
     }
+    // Gaussian priors of calibrate() and covariance() (tscm.h, "Gaussian priors"): cam_rt_* [C*6] on the cameras' rt_, intr_*
+    // [C*9] on their intrinsic_; NULL = none.  Copied.  Camera 0's pose is constant and held intrinsics are not free: their
+    // weights count for nothing.  Not with sharding (set_sharding with more than one rank): calibrate() then throws.
+    void set_camera_priors(const CameraPriors *priors)
+    {
+        use_priors_ = priors != NULL;
+        priors_ = priors ? *priors : CameraPriors();
+    }
     double corner_weight(size_t m, size_t i, size_t j) const
     {
         return m < corner_weights_.size() && i < corner_weights_[m].size() && j < corner_weights_[m][i].size() ? corner_weights_[m][i][j] : 0.0;
@@ -689,6 +781,7 @@ public:
         const bool any_fixed = q.any_fixed;
         tscm_options o;
         if (options) o = *options; else tscm_default_options(&o, 0);
+        const tscm_camera_priors cp = priors_.c_struct();
         if (comm_) {
             // frame-sharded over the ranks of set_sharding(): every rank builds this same problem, keeps the boards it owns
             // and ends with ALL parameters updated (tscm.h, "multi-GPU").  (A one-rank communicator is legal: the library
@@ -699,11 +792,13 @@ public:
             if (rc == 0) rc = tscm_solver_set_loss(s, loss_kind_, loss_scale_);
             if (rc == 0 && any_fixed) rc = tscm_solver_set_fixed_intrinsics(s, fixed.data());
             if (rc == 0 && use_weights_) rc = tscm_solver_set_corner_weights(s, q.w.data());
+            if (rc == 0 && use_priors_) rc = tscm_solver_set_camera_priors(s, &cp);
             if (rc == 0) rc = tscm_solver_solve(s, &o, &summary);
             tscm_solver_destroy(s);
             check(rc);
         } else {
-            check(tscm_solve_weighted(&P, &o, use_weights_ ? q.w.data() : nullptr, any_fixed ? fixed.data() : nullptr, loss_kind_, loss_scale_, &summary));
+            check(tscm_solve_prior(&P, &o, use_weights_ ? q.w.data() : nullptr, any_fixed ? fixed.data() : nullptr, loss_kind_, loss_scale_,
+                                   use_priors_ ? &cp : nullptr, &summary));
         }
         for (int m = 0; m < C; ++m) {                                    // :221-226
             cameras_[m].rt_.assign(&crt[6 * (size_t)m], &crt[6 * (size_t)m] + 6);
@@ -740,8 +835,9 @@ public:
         out.cam_rt_std.assign(6 * C, 0.0); out.intr_std.assign(9 * C, 0.0); out.board_rt_std.assign(6 * B, 0.0);
         out.info = tscm_covariance_info();
         out.info.struct_size = (int)sizeof(tscm_covariance_info);
-        check(tscm_covariance_weighted(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, use_weights_ ? q.w.data() : nullptr, loss_kind_, loss_scale_,
-                                       out.cam_cov.data(), out.board_cov.data(), out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
+        const tscm_camera_priors cp = priors_.c_struct();
+        check(tscm_covariance_prior(&q.P, device_, q.any_fixed ? q.fixed.data() : nullptr, use_weights_ ? q.w.data() : nullptr, loss_kind_, loss_scale_,
+                                    use_priors_ ? &cp : nullptr, out.cam_cov.data(), out.board_cov.data(), out.cam_rt_std.data(), out.intr_std.data(), out.board_rt_std.data(), &out.info));
         out.sigma2 = out.info.sigma2;
         return out;
     }
@@ -821,6 +917,8 @@ public:
     std::vector<unsigned short> fixed_;       // set_fixed_intrinsics(), by camera (missing entries: 0)
     bool use_weights_ = false;                // set_corner_weights()
     std::vector<std::vector<std::vector<double> > > corner_weights_;
+    bool use_priors_ = false;                 // set_camera_priors()
+    CameraPriors priors_;
     tscm_comm *comm_ = nullptr;
     tscm_summary summary;                     // BriefReport data of the solve (:218)
     std::vector<double> camera_error;         // per-camera mean pixel error (:281)

@@ -11,6 +11,7 @@ get_unit_sphere_coordinate (TS.h:39-57)                unproject(intr, pixels)
 error report (multi_calib.cpp:233-283)                 reprojection_error(problem)
 AddResidualBlock(..., new ceres::HuberLoss(a), ...)    loss=("huber", a); Solver.set_loss("huber", a)
 SetManifold(intrinsic_, new SubsetManifold(9, {..}))   fixed=("cx", "cy"); Solver.set_fixed_intrinsics(...)
+AddResidualBlock(new NormalPrior(A, mean), NULL, x)    priors=camera_priors(problem, intr_sigma={"xi": 0.1})
 
 Everything computes on the GPU through libtscm_hip.so; there is no CPU path.
 """
@@ -27,11 +28,12 @@ from .problem import Problem
 class Solver:
     """RAII wrapper of tscm_solver (problem uploaded once, parameters in/out per solve)."""
 
-    def __init__(self, problem: Problem, device: int = 0, rank: int = 0, world: int = 1, *, weights=None):
+    def __init__(self, problem: Problem, device: int = 0, rank: int = 0, world: int = 1, *, weights=None, priors=None):
         """rank / world: frame-sharded solve -- every rank passes the same WHOLE problem and keeps the boards it owns
         (tscm_solver_create_sharded); attach a communicator with set_comm() before solving.
         weights (default: problem.weights): corner weights as for set_corner_weights(); a view whose weights are all 0 is
-        created with view_count 0."""
+        created with view_count 0.
+        priors: camera priors as for set_camera_priors()."""
         self.problem = problem.normalised() if not _is_normalised(problem) else problem
         self.problem.validate()
         self._built, w = _l.corner_weights(self.problem, weights)
@@ -42,6 +44,8 @@ class Solver:
         self._comm = None
         if w is not None:
             _l.check(_l.lib().tscm_solver_set_corner_weights(self._h, _l.dptr(w)))
+        if priors is not None:
+            self.set_camera_priors(priors)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -84,6 +88,15 @@ class Solver:
         ("cx", "cy") for every camera, a [C] int array of TSCM_FIX_* words or a [C, 9] bool array (lib.fixed_masks)."""
         w = _l.fixed_masks(fixed, self.problem.n_cameras)
         _l.check(_l.lib().tscm_solver_set_fixed_intrinsics(self._h, _l.ushort_ptr(w)))
+
+    def set_camera_priors(self, priors):
+        """The Gaussian priors of every later solve / solve_resident (tscm_solver_set_camera_priors): a lib.CameraPriors
+        (camera_priors() builds one) or None for none.  Ceres' NormalPrior per coordinate: the objective gains
+        1/2 sum w (x - mean)^2; a weight on a coordinate that is not free (held, constant, b, c) counts as 0.  The library
+        copies the arrays.  Not served on a sharded solver (world > 1)."""
+        ptr, keep = _l.priors_ptr(priors, self.problem.n_cameras)
+        _l.check(_l.lib().tscm_solver_set_camera_priors(self._h, ptr))
+        del keep
 
     def debug_withhold_handoff(self, on=True):
         """Tests only: one producer of the device-side hand-off of the NEXT solve never reports in (tscm_solver_debug_withhold_handoff);
@@ -289,7 +302,43 @@ def _is_normalised(p: Problem) -> bool:
             and (p.board_pose_constant is None or ok(p.board_pose_constant, np.uint8)))
 
 
-def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, **options) -> dict:
+def camera_priors(problem: Problem, intr_sigma=None, cam_rt_sigma=None, mean=None, pixel_sigma: float = 1.0) -> "_l.CameraPriors":
+    """Priors "about this value, give or take sigma" for calibrate(), refinement(), Solver, ... (priors=).
+    intr_sigma: {intrinsic name: sigma} for every camera (lib.INTRINSIC_NAMES: fx fy cx cy xi lambda alpha), or a [C, 9] array
+    of sigmas with 0, inf or NaN for "no prior"; cam_rt_sigma: a scalar for all six pose coordinates of every camera, a [6] or
+    a [C, 6] array, same convention.  Weight = (pixel_sigma / sigma)^2: with pixel_sigma the standard deviation of a corner in
+    pixels the prior and the corners are weighted as their variances ask.  mean: None for the problem's current values, or a
+    dict with "intr" [C, 9] and / or "cam_rt" [C, 6]."""
+    Cn = problem.n_cameras
+    mean = mean or {}
+
+    def weights(sig, per):
+        s = np.broadcast_to(np.asarray(sig, dtype=np.float64), (Cn, per)).copy()
+        if np.any(s < 0.0):
+            raise ValueError("a prior's sigma must not be negative")
+        w = np.zeros((Cn, per))
+        ok = np.isfinite(s) & (s > 0.0)
+        w[ok] = (float(pixel_sigma) / s[ok]) ** 2
+        return w
+
+    iw = cw = im = cm = None
+    if intr_sigma is not None:
+        if isinstance(intr_sigma, dict):
+            sig = np.zeros((Cn, 9))
+            for name, v in intr_sigma.items():
+                if name not in _l.INTRINSIC_NAMES:
+                    raise ValueError(f"unknown intrinsic {name!r}: one of {', '.join(_l.INTRINSIC_NAMES)}")
+                sig[:, _l.INTRINSIC_NAMES.index(name)] = float(v)
+            intr_sigma = sig
+        iw = weights(intr_sigma, 9)
+        im = np.array(mean.get("intr", problem.intr), dtype=np.float64).reshape(Cn, 9)
+    if cam_rt_sigma is not None:
+        cw = weights(cam_rt_sigma, 6)
+        cm = np.array(mean.get("cam_rt", problem.cam_rt), dtype=np.float64).reshape(Cn, 6)
+    return _l.CameraPriors(cm, cw, im, iw)
+
+
+def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, priors=None, **options) -> dict:
     """The Ceres block of MultiCalib::calibrate() (multi_calib.cpp:157-218): joint LM over
     camera poses, board poses and intrinsics, in place on `problem`.  Like the reference,
     the outcome is not turned into an error -- inspect summary['termination'].
@@ -299,7 +348,8 @@ def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, weigh
     camera, a [C] int array of TSCM_FIX_* words (lib.FIX, lib.MODEL_DS, ...) or a [C, 9] bool array.
     weights (default: problem.weights): [n_corners] corner weights in corner order, a bool mask meaning 0 / 1 -- Ceres'
     ScaledLoss per residual block; weight 0 takes the corner out, whatever its observation holds (tscm_solve_weighted).
-    A view whose weights are all 0 goes in with view_count 0."""
+    A view whose weights are all 0 goes in with view_count 0.
+    priors: None, or Gaussian priors on camera parameters (camera_priors(), tscm_solve_prior)."""
     if problem.mono:
         raise ValueError("calibrate() is the multi-camera solve; use refinement() for a mono problem")
     assert _is_normalised(problem), "use Problem.normalised()"
@@ -308,14 +358,14 @@ def calibrate(problem: Problem, device: int = 0, *, loss=None, fixed=None, weigh
     q, w = _l.corner_weights(problem, weights)
     cp = _l.c_problem(q)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, w)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, w, priors)
     return _l.summary_dict(s)
 
 
-def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, **options):
+def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, priors=None, **options):
     """TripleSphereCamera::refinement (TS.cpp:247-282): returns (converged, summary) where
     converged == (termination_type == CONVERGENCE), the reference's return value (:281).
-    loss, fixed, weights: as for calibrate()."""
+    loss, fixed, weights, priors: as for calibrate()."""
     if not problem.mono:
         raise ValueError("refinement() is the mono solve")
     assert _is_normalised(problem), "use Problem.normalised()"
@@ -324,17 +374,21 @@ def refinement(problem: Problem, device: int = 0, *, loss=None, fixed=None, weig
     q, w = _l.corner_weights(problem, weights)
     cp = _l.c_problem(q)
     _select(device)
-    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, w)
+    _solve_one_shot(cp, o, s, loss, fixed, problem.n_cameras, w, priors)
     d = _l.summary_dict(s)
     return d["termination_type"] == 0, d
 
 
-def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, weights=None, **options):
+def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, weights=None, priors=None, **options):
     """n TripleSphereCamera::refinement solves (TS.cpp:247-282) in one batch on one device (tscm_solve_mono_batch):
     returns [(converged, summary), ...] in problem order, each as refinement() would return it for that problem alone.
     Parameters are updated in place.  loss: shared, as for refinement(); fixed: None, or one mask per problem (anything
     fixed_masks takes for one camera: an int, names, a [9] bool array, or None); weights: None (then each problem's own
-    .weights), or one entry per problem, each as for refinement() or None (tscm_solve_mono_batch_weighted)."""
+    .weights), or one entry per problem, each as for refinement() or None (tscm_solve_mono_batch_weighted).
+    priors: the batched route has none (tscm_solve_mono_batch* takes no priors argument) -- anything but None raises ValueError
+    here, in the Python layer; solve such problems one by one with refinement()."""
+    if priors is not None:
+        raise ValueError("refinement_batch: the batched mono route has no camera priors (use refinement() per problem)")
     problems = list(problems)
     if not problems:
         raise ValueError("refinement_batch() needs at least one problem")
@@ -367,11 +421,13 @@ def refinement_batch(problems, device: int = 0, *, loss=None, fixed=None, weight
     return out
 
 
-def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, weights=None):
-    # the most general export; None where nothing is set (tscm_solve_multi / _mono / _robust / _fixed wrap the same path)
+def _solve_one_shot(cp, o, s, loss, fixed, n_cameras, weights=None, priors=None):
+    # the most general export; None where nothing is set (tscm_solve_multi / _mono / _robust / _fixed / _weighted wrap the same path)
     w = None if fixed is None else _l.fixed_masks(fixed, n_cameras)
     k, a = _l.loss_args(loss)
-    _l.check(_l.lib().tscm_solve_weighted(C.byref(cp), C.byref(o), _l.dptr(weights), None if w is None else _l.ushort_ptr(w), k, a, C.byref(s)))
+    pr, keep = _l.priors_ptr(priors, n_cameras)
+    _l.check(_l.lib().tscm_solve_prior(C.byref(cp), C.byref(o), _l.dptr(weights), None if w is None else _l.ushort_ptr(w), k, a, pr, C.byref(s)))
+    del keep
 
 
 def _select(device: int):
@@ -397,14 +453,16 @@ def evaluate_functor(problem: Problem, device: int = 0, jacobians: bool = True):
 
 
 def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 0, exec_flags: int = 0, loss=None,
-                     as_solved: bool = False, weights=None) -> dict:
+                     as_solved: bool = False, weights=None, priors=None) -> dict:
     """Schur-form normal equations (unscaled) from the Gram kernel a solve with these options runs:
     k_eval_gram4 by default, k_eval_gram_f32 with jacobian_fp32=1, k_eval_gram with exec_flags=EXEC_GRAM_16X16.
     loss (as for calibrate()): the corrected equations of a robust solve, cost = sum rho / 2.
     as_solved: the evaluation launch exactly as a solve makes it, on a fresh solver (tscm_solver_eval_normal_equations):
     k_eval_gram4 forms no rotation columns for a camera whose pose block is constant, and those entries are 0.
     weights (default: problem.weights): corner weights as for calibrate() -- the equations of the rows scaled by
-    sqrt(omega rho'), cost = sum omega rho / 2 (tscm_eval_normal_equations_weighted)."""
+    sqrt(omega rho'), cost = sum omega rho / 2 (tscm_eval_normal_equations_weighted).
+    priors: camera priors as for calibrate() -- w on the diagonal of cam_gram, w (x - mean) in cam_grad, 1/2 w (x - mean)^2 in
+    the cost, on every column that can be free (tscm_eval_normal_equations_prior); the board blocks do not change."""
     assert _is_normalised(problem)
     q, w = _l.corner_weights(problem, weights)
     Cn, B, V = problem.n_cameras, problem.n_boards, problem.n_views
@@ -416,23 +474,25 @@ def normal_equations(problem: Problem, device: int = 0, *, jacobian_fp32: int = 
     outs = (_l.dptr(out["board_gram"]), _l.dptr(out["board_grad"]), _l.dptr(out["view_cross"]),
             _l.dptr(out["cam_gram"]), _l.dptr(out["cam_grad"]), C.byref(cost))
     if as_solved:
-        with Solver(problem, device, weights=weights) as s:
+        with Solver(problem, device, weights=weights, priors=priors) as s:
             if loss is not None:
                 s.set_loss(*((loss,) if isinstance(loss, str) else loss))
             _l.check(_l.lib().tscm_solver_eval_normal_equations(s._h, C.byref(o), 1, *outs))
     else:
         k, a = _l.loss_args(loss)
-        _l.check(_l.lib().tscm_eval_normal_equations_weighted(C.byref(cp), device, C.byref(o), _l.dptr(w), k, a, *outs))
+        pr, keep = _l.priors_ptr(priors, Cn)
+        _l.check(_l.lib().tscm_eval_normal_equations_prior(C.byref(cp), device, C.byref(o), _l.dptr(w), k, a, pr, *outs))
+        del keep
     out["cost"] = cost.value
     return out
 
 
-def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, **options) -> dict:
+def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, priors=None, **options) -> dict:
     """The candidate point of the first trust-region step a solve with these options takes (tscm_eval_step_ex), at the
     problem's parameters, which stay as they are: cam_rt, intr, board_rt (x + delta as that solve evaluates it), valid
     (False: the linear solve failed) and the one-iteration summary.  loss: as for calibrate() (tscm_eval_step_robust);
     fixed: held intrinsics as for calibrate() (tscm_eval_step_fixed); weights: corner weights as for calibrate()
-    (tscm_eval_step_weighted)."""
+    (tscm_eval_step_weighted); priors: camera priors as for calibrate() (tscm_eval_step_prior)."""
     assert _is_normalised(problem)
     q, cw = _l.corner_weights(problem, weights)
     cam, intr, board = np.zeros_like(problem.cam_rt), np.zeros_like(problem.intr), np.zeros_like(problem.board_rt)
@@ -443,7 +503,9 @@ def step(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=No
     outs = (_l.dptr(cam), _l.dptr(intr), _l.dptr(board), C.byref(valid), C.byref(s))
     w = None if fixed is None else _l.fixed_masks(fixed, problem.n_cameras)
     k, a = _l.loss_args(loss)
-    _l.check(_l.lib().tscm_eval_step_weighted(C.byref(cp), device, C.byref(o), _l.dptr(cw), None if w is None else _l.ushort_ptr(w), k, a, *outs))
+    pr, keep = _l.priors_ptr(priors, problem.n_cameras)
+    _l.check(_l.lib().tscm_eval_step_prior(C.byref(cp), device, C.byref(o), _l.dptr(cw), None if w is None else _l.ushort_ptr(w), k, a, pr, *outs))
+    del keep
     return dict(cam_rt=cam, intr=intr, board_rt=board, valid=bool(valid.value), summary=_l.summary_dict(s))
 
 
@@ -484,15 +546,16 @@ def shard_owner(problem: Problem, world: int) -> np.ndarray:
 def _covariance_dict(info, Cn: int, B: int, cam_cov, board_cov) -> dict:
     dof = int(info.n_residuals) - int(info.n_free)
     return dict(status=info.status, where=info.where, n_free=info.n_free, dof=dof, sigma2=info.sigma2, cost=info.cost,
-                min_pivot_ratio=info.min_pivot_ratio, cam_cov=cam_cov.reshape(Cn, 15, Cn, 15), board_cov=board_cov.reshape(B, 6, 6),
+                n_residuals=int(info.n_residuals), min_pivot_ratio=info.min_pivot_ratio, cam_cov=cam_cov.reshape(Cn, 15, Cn, 15), board_cov=board_cov.reshape(B, 6, 6),
                 seconds_kernel=tuple(info.seconds_kernel))
 
 
-def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None) -> dict:
+def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None, weights=None, priors=None) -> dict:
     """What ceres::Covariance gives a Ceres user, at the problem's parameters (tscm_covariance): (J^T J)^-1 over the free
     columns in Ceres' convention (not multiplied by sigma2), sigma2 = 2 cost / dof and the standard deviations
     sqrt(sigma2 * diagonal).  loss, fixed, weights: as for calibrate() -- pass what the solve had (with weights:
-    tscm_covariance_weighted, the residuals are the corners with a weight > 0).
+    tscm_covariance_weighted, the residuals are the corners with a weight > 0; with priors: tscm_covariance_prior, every prior
+    on a free column is one more residual, in the blocks, the cost and dof).
     -> status (0 ok, 1 singular board block, 2 singular reduced system: every array is then NaN), where, n_free, dof, sigma2,
     cost, min_pivot_ratio (near 0: gauge freedom or an unobservable parameter), cam_cov [C,15,C,15] and board_cov [B,6,6]
     (zero where not free), cam_rt_std [C,6], intr_std [C,9], board_rt_std [B,6] (0 where not free), seconds_kernel (board
@@ -507,7 +570,9 @@ def covariance(problem: Problem, device: int = 0, *, loss=None, fixed=None, weig
     w = None if fixed is None else _l.fixed_masks(fixed, Cn)
     k, a = _l.loss_args(loss)
     outs = (_l.dptr(cam_cov), _l.dptr(board_cov), _l.dptr(cam_std), _l.dptr(intr_std), _l.dptr(board_std), C.byref(info))
-    _l.check(_l.lib().tscm_covariance_weighted(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), _l.dptr(cw), k, a, *outs))
+    pr, keep = _l.priors_ptr(priors, Cn)
+    _l.check(_l.lib().tscm_covariance_prior(C.byref(cp), device, None if w is None else _l.ushort_ptr(w), _l.dptr(cw), k, a, pr, *outs))
+    del keep
     out = _covariance_dict(info, Cn, B, cam_cov, board_cov)
     out.update(cam_rt_std=cam_std, intr_std=intr_std, board_rt_std=board_std)
     return out

@@ -468,8 +468,10 @@ extern "C" int tscm_covariance_from_normal_equations(int n_cameras, int n_boards
 
 // weights: the problem's corner weights (tscm_solver_set_corner_weights) or NULL -- the blocks are then those of the weighted
 // normal equations and a corner with weight 0 is no residual
+// priors: camera priors (tscm_solver_set_camera_priors) or NULL -- a prior on a free column is one more residual, in the blocks,
+// the cost and n_residuals; on a column that is not free it is nothing
 static int covariance_of_problem(const tscm_problem *p, int device, const unsigned short *fixed, const double *weights, int loss_kind, double loss_scale,
-                                 double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info)
+                                 const tscm_camera_priors *priors, double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info)
 {
     if (int rc = check_info(info)) return rc;
     reset_info(info);
@@ -484,8 +486,38 @@ static int covariance_of_problem(const tscm_problem *p, int device, const unsign
     if (loss_kind < TSCM_LOSS_NONE || loss_kind > TSCM_LOSS_CAUCHY) return tscm_set_error(TSCM_E_INVALID, "loss_kind " + std::to_string(loss_kind) + " is not a TSCM_LOSS_* kind");
     if (loss_kind != TSCM_LOSS_NONE && (!std::isfinite(loss_scale) || !(loss_scale > 0.0)))
         return tscm_set_error(TSCM_E_INVALID, "loss_scale must be finite and > 0");
+    if (int rc = check_camera_priors(priors, C, err)) return tscm_set_error(rc, err);
     std::vector<unsigned char> cam_free, board_free;
     cov_masks(p, fixed, cam_free, board_free);
+    // the priors of the free columns, in the caller's layout: what the evaluation below adds and n_residuals counts.  The
+    // evaluation's solver has no mask and zeroes a weight only outside ITS free columns (effective_priors on plan_columns(fixed =
+    // NULL)): what is kept here must lie inside those, or the P of n_residuals is not what the kernel adds.  cov_masks without a
+    // mask states the same rule (pose not mono / constant, camera with corners, never b, c), so cam_free must be a subset of it
+    {
+        std::vector<unsigned char> unmasked, boards;
+        cov_masks(p, nullptr, unmasked, boards);
+        for (size_t i = 0; i < cam_free.size(); ++i)
+            if (cam_free[i] && !unmasked[i]) return tscm_set_error(TSCM_E_UNSUPPORTED, "internal error: a held-intrinsics mask freed a camera column");
+    }
+    std::vector<double> pw_cam, pw_intr;
+    tscm_camera_priors eff{ sizeof(tscm_camera_priors), nullptr, nullptr, nullptr, nullptr };
+    long long n_prior = 0;
+    if (priors) {
+        eff = *priors;
+        auto keep_free = [&](const double *w, int per, int first, std::vector<double> &out) {
+            if (!w) return static_cast<const double *>(nullptr);
+            out.assign(w, w + per * (size_t)C);
+            for (int m = 0; m < C; ++m)
+                for (int a = 0; a < per; ++a) {
+                    double &x = out[per * (size_t)m + a];
+                    if (!cam_free[(size_t)kCovCam * m + first + a]) x = 0.0;
+                    n_prior += x > 0.0 ? 1 : 0;
+                }
+            return static_cast<const double *>(out.data());
+        };
+        eff.cam_rt_weight = keep_free(priors->cam_rt_weight, 6, 0, pw_cam);
+        eff.intr_weight = keep_free(priors->intr_weight, 9, 6, pw_intr);
+    }
     CovPlan pl;
     if (int rc = plan_covariance(C, B, V, p->view_camera, p->view_board, cam_free.data(), board_free.data(), pl, err)) return tscm_set_error(rc, "problem: " + err);
     long long N = 0;
@@ -493,7 +525,7 @@ static int covariance_of_problem(const tscm_problem *p, int device, const unsign
     // the blocks, from the default fp64 Gram kernel through the public evaluation
     std::vector<double> bg((size_t)36 * B + 1), vc((size_t)90 * V + 1), cg((size_t)225 * C);
     double cost = 0.0;
-    if (int rc = tscm_eval_normal_equations_spec(p, device, nullptr, spec_args(loss_kind, loss_scale, nullptr, weights), bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
+    if (int rc = tscm_eval_normal_equations_spec(p, device, nullptr, spec_args(loss_kind, loss_scale, nullptr, weights, priors ? &eff : nullptr), bg.data(), nullptr, vc.data(), cg.data(), nullptr, &cost)) return rc;
     if (weights) {
         long long kept = 0;
         for (long long i = 0; i < N; ++i) kept += weights[i] > 0.0 ? 1 : 0;
@@ -505,8 +537,8 @@ static int covariance_of_problem(const tscm_problem *p, int device, const unsign
     if (!board_cov) { own_board.resize((size_t)36 * B + 1); board_cov = own_board.data(); }
     if (int rc = covariance_run(pl, p->view_camera, bg.data(), vc.data(), cg.data(), cam_free.data(), device, "tscm_covariance", cam_cov, board_cov, info)) return rc;
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    const long long dof = 2 * N - pl.n_free;
-    info->n_residuals = 2 * N;
+    const long long dof = 2 * N + n_prior - pl.n_free;
+    info->n_residuals = 2 * N + n_prior;
     info->cost = cost;
     info->sigma2 = dof > 0 ? 2.0 * cost / (double)dof : nan;
     // standard deviations: sqrt(sigma2 * diagonal), exactly 0 where the column is not free; NaN behind a singular block
@@ -533,12 +565,19 @@ static int covariance_of_problem(const tscm_problem *p, int device, const unsign
 extern "C" int tscm_covariance(const tscm_problem *p, int device, const unsigned short *fixed, int loss_kind, double loss_scale, double *cam_cov,
                                double *board_cov, double *cam_rt_std, double *intr_std, double *board_rt_std, tscm_covariance_info *info)
 {
-    return covariance_of_problem(p, device, fixed, nullptr, loss_kind, loss_scale, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
+    return covariance_of_problem(p, device, fixed, nullptr, loss_kind, loss_scale, nullptr, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
 }
 
 extern "C" int tscm_covariance_weighted(const tscm_problem *p, int device, const unsigned short *fixed, const double *weights, int loss_kind,
                                         double loss_scale, double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std,
                                         double *board_rt_std, tscm_covariance_info *info)
 {
-    return covariance_of_problem(p, device, fixed, weights, loss_kind, loss_scale, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
+    return covariance_of_problem(p, device, fixed, weights, loss_kind, loss_scale, nullptr, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
+}
+
+extern "C" int tscm_covariance_prior(const tscm_problem *p, int device, const unsigned short *fixed, const double *weights, int loss_kind, double loss_scale,
+                                     const tscm_camera_priors *priors, double *cam_cov, double *board_cov, double *cam_rt_std, double *intr_std,
+                                     double *board_rt_std, tscm_covariance_info *info)
+{
+    return covariance_of_problem(p, device, fixed, weights, loss_kind, loss_scale, priors, cam_cov, board_cov, cam_rt_std, intr_std, board_rt_std, info);
 }

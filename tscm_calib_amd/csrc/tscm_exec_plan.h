@@ -68,6 +68,7 @@ struct ExecPlan {
     EvalTail tail = EvalTail::ReduceControl;
     bool ctl_in_schur = false;          // the control step of an evaluation is taken in the head of the next k_schur_gram
     bool stats_ride = false;            // a candidate's reductions ride in it (tail == Ride)
+    bool priors = false;                // the reductions add camera priors: k_reduce_stats_prior
     bool t_in_solve = false;            // k_T_reduce rides in the reduced solve's launch as n_prod producer workgroups
     Solver solver = Solver::Empty;
     int nd = 0, tpt = 1;                // Solver::Nd: plan nd (0 the camera-pair graph, 1 one dense block) and its tpt
@@ -104,12 +105,13 @@ TSCM_PLAN_FN G4Plan g4_plan(int n_points)
 }
 
 inline ExecPlan plan_exec(const Layout &L, int C, int n_act, int comm_kind, int exec_flags, int jacobian_fp32, int loss_kind, int rp,
-                          const ExecDevice &dev, bool inspect = false)
+                          const ExecDevice &dev, bool inspect = false, bool priors = false)
 {
     ExecPlan p;
     p.comm = uses_comm(comm_kind, exec_flags);
     p.gram = plan_gram(exec_flags, jacobian_fp32, rp);
     p.robust = loss_kind != TSCM_LOSS_NONE;
+    p.priors = priors;
     p.skip_const_pose = !inspect && p.gram == Gram::G4;
     // one GPU with <= 8 cameras (finish_evaluation's LDS fits k_schur_gram's) or a communicator; exactly one Schur kernel
     // per iteration.  (A grid of several rounds -- config 5 on one GPU: 1256 workgroups, 2.5 rounds -- pays the step in its
@@ -122,10 +124,15 @@ inline ExecPlan plan_exec(const Layout &L, int C, int n_act, int comm_kind, int 
     // ONE round -- every workgroup that takes a reduction block in front of its chunk is resident (they wait for each
     // other); at config 5 (1256 chunks, 2.5 rounds) the ride costs 2.5 us where it saves 4 at config 4
     const int nv = L.nv_chunks[1] ? 1 : L.nv_chunks[2] ? 2 : 3;
-    p.stats_ride = p.ctl_in_schur && !p.comm && small && !(exec_flags & TSCM_EXEC_SEPARATE_STATS) &&
+    // (camera priors, DESIGN 28: the prior enters in the reductions' launches of their own -- k_schur_gram has no prior
+    // instantiation -- so a solve with priors plans as under TSCM_EXEC_SEPARATE_STATS)
+    p.stats_ride = p.ctl_in_schur && !p.comm && small && !(exec_flags & TSCM_EXEC_SEPARATE_STATS) && !priors &&
                    std::max(reduction_blocks(L, C), L.nv_chunks[nv]) + 1 <= dev.schur_resident_ride[nv];
     // (rigs of more than 8 cameras: k_control as a launch of its own)
     p.tail = p.comm || !small ? EvalTail::Exchange : !p.ctl_in_schur ? EvalTail::ReduceControl : p.stats_ride ? EvalTail::Ride : EvalTail::StatsThenHead;
+    // (camera priors: k_reduce_control has no prior instantiation either -- where it would run, the reductions, k_finalize_eval
+    // and k_control do, as for a rig of more than 8 cameras)
+    if (priors && p.tail == EvalTail::ReduceControl) p.tail = EvalTail::Exchange;
     // one GPU, up to 8 cameras: the T reduction rides in the reduced solve's launch; with a communicator the all-reduce of T
     // sits between the two
     p.t_in_solve = !(exec_flags & TSCM_EXEC_SEPARATE_T_REDUCE) && small && !p.comm && L.n_bids > 0 && L.n_bids <= kSmallBids && n_act > 0;

@@ -3,11 +3,38 @@
 #pragma once
 // (included from tscm_kernels.h inside namespace tscm)
 
+// camera priors (tscm_spec.h: effective_priors): mean and weight per camera-side column, [C][16] each, the weight 0
+// where the column is not free -- an argument of the PRIOR kernels alone
+struct PriorArg { const double *mean, *weight; };
+// The prior's part of raw entry e (of 512: half, tile row, tile column) of camera cam's tile at the target point: w_k on the
+// diagonal entry of column k, w_k d_k on (k, kFR) and (kFR, k) -- the raw tile is kept full -- and sum w_k d_k^2 on (kFR, kFR), with
+// d_k = x_k - mean_k.  camera_tile_entry adds the halves, so a term sits in ONE of them: GU where f_mask(a) & f_mask(b) & 1,
+// else GV (fy, cy).  Columns in order: the same bits on every call
+__device__ __forceinline__ double prior_raw_entry(const DevState &S, const PriorArg &pr, int cam, int e, int tgt)
+{
+    const int h = e >> 8, ta = (e >> 4) & 15, tb = e & 15;
+    double v = 0.0;
+    for (int k = 0; k < kFA; ++k) {
+        const double w = pr.weight[16 * cam + k];
+        if (!(w > 0.0)) continue;
+        const double x = k < 6 ? S.cam_rt[tgt][6 * cam + k] : S.intr[tgt][9 * cam + (k - 6)];
+        const double d = x - pr.mean[16 * cam + k];
+        const int tk = f_tile(k), hk = (f_mask(k) & 1) ? 0 : 1;
+        if (ta == kTcR && tb == kTcR) { if (h == 0) v += w * d * d; }
+        else if (h != hk) continue;
+        else if (ta == tk && tb == tk) v += w;
+        else if ((ta == tk && tb == kTcR) || (ta == kTcR && tb == tk)) v += w * d;
+    }
+    return v;
+}
 // per-camera raw tile (GU | GV) reduction: one block per (camera, slice of 32 of the 512 raw entries).  Eight threads per
 // entry take every eighth workgroup tile -- up to 32 loads per thread requested at once -- and are combined through LDS
 // in a fixed order: campart2[cam][512] holds the finished sums (round 3; before: 16 groups of tiles per camera here and
 // a second level in k_finalize_eval, 16 more dependent loads per thread in a kernel that is nothing but a latency chain)
-__device__ void cam_reduce_block(const DevProblem &P, const DevState &S, int blk, double *sm /* 256 doubles */)
+// PRIOR: behind the fixed-order sum the thread that stores a raw entry adds that entry's prior term at the target point (cand: the
+// candidate, as board_stats_block forms it); PRIOR = false is the code without priors, cam_reduce_block
+template <bool PRIOR>
+__device__ __forceinline__ void cam_reduce(const DevProblem &P, const DevState &S, int blk, double *sm /* 256 doubles */, int cand, const PriorArg &pr)
 {
     const int cam = blk / kCamSl, sl = blk % kCamSl;
     int cb, ce;
@@ -33,10 +60,18 @@ __device__ void cam_reduce_block(const DevProblem &P, const DevState &S, int blk
     }
     sm[t] = acc;
     __syncthreads();
-    if (t < 32)
-        handoff_store(&S.campart2[(size_t)512 * cam + 32 * sl + t], ((sm[t] + sm[32 + t]) + (sm[64 + t] + sm[96 + t])) + ((sm[128 + t] + sm[160 + t]) + (sm[192 + t] + sm[224 + t])));
+    if constexpr (PRIOR) {
+        if (t < 32) {
+            const double sum = ((sm[t] + sm[32 + t]) + (sm[64 + t] + sm[96 + t])) + ((sm[128 + t] + sm[160 + t]) + (sm[192 + t] + sm[224 + t]));
+            handoff_store(&S.campart2[(size_t)512 * cam + 32 * sl + t], sum + prior_raw_entry(S, pr, cam, 32 * sl + t, cand ? (S.ctrl->cur ^ 1) : S.ctrl->cur));
+        }
+    } else {
+        if (t < 32)
+            handoff_store(&S.campart2[(size_t)512 * cam + 32 * sl + t], ((sm[t] + sm[32 + t]) + (sm[64 + t] + sm[96 + t])) + ((sm[128 + t] + sm[160 + t]) + (sm[192 + t] + sm[224 + t])));
+    }
     __syncthreads();
 }
+__device__ void cam_reduce_block(const DevProblem &P, const DevState &S, int blk, double *sm /* 256 doubles */) { cam_reduce<false>(P, S, blk, sm, 0, PriorArg{}); }
 
 // deterministic block reductions (256 threads)
 // Block reductions (256 threads; any multiple of 64 works): DPP butterfly inside each 16-lane row, two xor shuffles across the
@@ -151,6 +186,21 @@ __global__ __launch_bounds__(256) void k_reduce_stats(DevProblem P, DevState S, 
     __shared__ double sm[256];
     const int nc = P.C * kCamSl;
     if ((int)blockIdx.x < nc) cam_reduce_block(P, S, blockIdx.x, sm);
+    else board_stats_block(P, S, cand, init, blockIdx.x - nc, sm);
+}
+// ... of a solve with camera priors (ExecPlan::priors) and of tscm_eval_normal_equations* with them: the same launch with the
+// PRIOR camera-tile reduction.  A kernel of its own, not an instantiation of a shared body, and no k_reduce_control of this
+// kind (plan_exec: k_finalize_eval and k_control follow instead): k_reduce_stats and k_reduce_control keep their code bit for
+// bit only as they are written and instantiated once (tools/same_kernels.py)
+__global__ __launch_bounds__(256) void k_reduce_stats_prior(DevProblem P, DevState S, int cand, int init, PriorArg pr)
+{
+    KTL(1);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < sizeof(CtrlHead) / 8)
+        reinterpret_cast<unsigned long long *>(S.ctrl_snap)[threadIdx.x] = reinterpret_cast<const unsigned long long *>(S.ctrl)[threadIdx.x];
+    if (S.ctrl->done) return;
+    __shared__ double sm[256];
+    const int nc = P.C * kCamSl;
+    if ((int)blockIdx.x < nc) cam_reduce<true>(P, S, blockIdx.x, sm, cand, pr);
     else board_stats_block(P, S, cand, init, blockIdx.x - nc, sm);
 }
 

@@ -167,6 +167,14 @@ struct tscm_solver {
     std::vector<int> p_view_count;      // view_count of the caller's WHOLE problem (the weights' corner order)
     double w_sum = 0.0;                 // sum of the weights and number of corners with a weight > 0, of the WHOLE job
     long n_kept = 0;
+    // camera priors (tscm_solver_set_camera_priors): the caller's arrays as given (empty: not given), and what the
+    // reductions' PRIOR kernel takes of them under the current free columns -- d_prior holds mean [16 C] | weight [16 C]
+    // (effective_priors; allocated by the first call with an effective prior).  n_priors == 0 is the solve without priors
+    std::vector<double> pr_cam_mean, pr_cam_w, pr_intr_mean, pr_intr_w;
+    std::vector<unsigned char> col_free;    // [16 C] ColumnPlan::col_active as uploaded (apply_columns)
+    double *d_prior = nullptr;
+    int n_priors = 0;
+    PriorArg prior_arg() const { return PriorArg{ d_prior, d_prior + 16 * (size_t)C }; }
     // held intrinsics (tscm_solver_set_fixed_intrinsics): the mask word of every camera (the whole-problem facts the
     // free columns are derived from are L.cam_const, L.cam_active, L.pair_present: plan_columns)
     std::vector<unsigned short> fixed;
@@ -255,6 +263,12 @@ static int check_corner_weights(const int *view_count, int n_views, const double
     if (int rc = tscm::check_corner_weights(view_count, n_views, w, err, sum, kept)) return fail(rc, err);
     return 0;
 }
+static int check_camera_priors(const tscm_camera_priors *pr, int n_cameras)
+{
+    std::string err;
+    if (int rc = tscm::check_camera_priors(pr, n_cameras, err)) return fail(rc, err);
+    return 0;
+}
 static bool same_loss(const LossArg &x, const LossArg &y) { return x.kind == y.kind && (x.kind == TSCM_LOSS_NONE || x.a == y.a); }
 
 extern "C" int tscm_solver_set_loss(tscm_solver *s, int kind, double scale)
@@ -300,6 +314,37 @@ extern "C" int tscm_solver_set_corner_weights(tscm_solver *s, const double *weig
     }
     s->weighted = true; s->P.obs_w = s->d_obs_w; s->w_sum = sum; s->n_kept = kept;
     return 0;
+}
+
+// the prior tables of the solver's stored priors under its current free columns (s->col_free), on the device: behind
+// tscm_solver_set_camera_priors and every apply_columns
+static int refresh_priors(tscm_solver *s)
+{
+    const tscm_camera_priors pr{ sizeof(tscm_camera_priors), s->pr_cam_mean.empty() ? nullptr : s->pr_cam_mean.data(), s->pr_cam_w.empty() ? nullptr : s->pr_cam_w.data(),
+                                 s->pr_intr_mean.empty() ? nullptr : s->pr_intr_mean.data(), s->pr_intr_w.empty() ? nullptr : s->pr_intr_w.data() };
+    std::vector<double> mean, weight;
+    const int n = effective_priors(&pr, s->C, s->col_free.data(), mean, weight);
+    if (n) {
+        const size_t n16 = 16 * (size_t)s->C;
+        HIP_TRY(hipSetDevice(s->device));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        if (!s->d_prior) HIP_TRY(s->mem.alloc(&s->d_prior, 2 * n16));
+        HIP_TRY(hipMemcpy(s->d_prior, mean.data(), sizeof(double) * n16, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->d_prior + n16, weight.data(), sizeof(double) * n16, hipMemcpyHostToDevice));
+    }
+    s->n_priors = n;
+    return 0;
+}
+
+extern "C" int tscm_solver_set_camera_priors(tscm_solver *s, const tscm_camera_priors *priors)
+{
+    if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
+    if (int rc = check_camera_priors(priors, s->C)) return rc;
+    if (priors && s->world > 1) return fail(TSCM_E_UNSUPPORTED, "camera priors on a sharded solver (world > 1) are not supported");
+    auto keep = [&](std::vector<double> &dst, const double *src, int per) { if (priors && src) dst.assign(src, src + per * (size_t)s->C); else dst.clear(); };
+    keep(s->pr_cam_mean, priors ? priors->cam_rt_mean : nullptr, 6); keep(s->pr_cam_w, priors ? priors->cam_rt_weight : nullptr, 6);
+    keep(s->pr_intr_mean, priors ? priors->intr_mean : nullptr, 9); keep(s->pr_intr_w, priors ? priors->intr_weight : nullptr, 9);
+    return refresh_priors(s);
 }
 
 extern "C" void tscm_solver_destroy(tscm_solver *s)
@@ -370,7 +415,9 @@ static int apply_columns(tscm_solver *s, const ColumnPlan &c)
         s->lds_solve = std::max(s->lds_nd[0], s->lds_nd[1]);
     }
     if (s->C > kMaxCamLds) s->lds_solve = solve_big_lds_bytes((c.n_act + 15) & ~15, s->n_pad);
-    return 0;
+    // (camera priors: the weight of a column that is not free is taken as 0)
+    s->col_free = c.col_active;
+    return refresh_priors(s);
 }
 
 extern "C" int tscm_solver_set_fixed_intrinsics(tscm_solver *s, const unsigned short *fixed)
@@ -899,7 +946,11 @@ static int enqueue(tscm_solver *s, const Launch &l)
     }
     case Kern::Eval: return launch_eval(s, l.cand);
     case Kern::ReduceControl: hipLaunchKernelGGL(k_reduce_control, grid, dim3(256), 0, st, P, S, l.cand, l.init, l.have_backsub); break;
-    case Kern::ReduceStats: hipLaunchKernelGGL(k_reduce_stats, grid, dim3(256), 0, st, P, S, l.cand, l.init); break;
+    // (camera priors, ExecPlan::priors: the PRIOR kernel adds them behind the camera-tile sums; such a plan has no k_reduce_control)
+    case Kern::ReduceStats:
+        if (s->xp.priors) hipLaunchKernelGGL(k_reduce_stats_prior, grid, dim3(256), 0, st, P, S, l.cand, l.init, s->prior_arg());
+        else hipLaunchKernelGGL(k_reduce_stats, grid, dim3(256), 0, st, P, S, l.cand, l.init);
+        break;
     case Kern::FinalizeEval: hipLaunchKernelGGL(k_finalize_eval, grid, dim3(256), 0, st, P, S, l.have_backsub); break;
     case Kern::Control: hipLaunchKernelGGL(k_control, grid, dim3(256), 0, st, P, S, l.init); break;
     case Kern::SchurFactor: hipLaunchKernelGGL(k_schur_factor, grid, dim3(256), 0, st, P, S); break;
@@ -1151,7 +1202,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
     HIP_TRY(hipSetDevice(s0->device));
     LmRunGuard guard{ run };
     for (tscm_solver *s : run.m) {
-        s->xp = plan_exec(s->L, s->C, s->P.n_act, comm_kind(s->comm_reg), opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev);
+        s->xp = plan_exec(s->L, s->C, s->P.n_act, comm_kind(s->comm_reg), opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev, false, s->n_priors > 0);
         s->comm = s->xp.comm ? s->comm_reg : nullptr;
         s->head = ctrl_head_from_options(opt);
         s->withhold = s->withhold_next; s->withhold_next = 0;
@@ -1215,8 +1266,9 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         sum->seconds_solve = 1e-8 * (double)(h->t_end - h->t_begin);      // on the device: first to last kernel of the solve
         sum->seconds_total = t1 - t0;                                     // wall time of the call
     }
-    // with a loss the cost is sum rho / 2, not the squared pixel error: the RMSE is measured at the accepted point instead
-    if (s0->loss.kind != TSCM_LOSS_NONE) return robust_rmse(run, sums);
+    // with a loss the cost is sum rho / 2, not the squared pixel error: the RMSE is measured at the accepted point instead; with
+    // camera priors the cost holds the prior term as well
+    if (s0->loss.kind != TSCM_LOSS_NONE || s0->n_priors > 0) return robust_rmse(run, sums);
     return 0;
 }
 
@@ -1309,20 +1361,22 @@ static int preamble(const tscm_problem *p, bool null, const char *null_text, con
     if (int rc = make_spec(in.loss.kind, in.loss.a, nullptr, 0, spec)) return rc;
     if (null) return fail(TSCM_E_INVALID, null_text);
     if (int rc = make_spec(in.loss.kind, in.loss.a, in.fixed, p->n_cameras, spec)) return rc;
-    spec.weights = in.weights;
+    spec.weights = in.weights; spec.priors = in.priors;
     return read_options(opt_in, p->mono, opt);
 }
 
-// a solver of `p` on `device` with a checked spec's loss, mask and weights, alive as long as `sp`.  The problem's and the
-// weights' refusals come before the device is touched
+// a solver of `p` on `device` with a checked spec's loss, mask, weights and priors, alive as long as `sp`.  The problem's, the
+// weights' and the priors' refusals come before the device is touched
 static int create_configured(const tscm_problem *p, int device, const SolveSpec &spec, SolverPtr &sp)
 {
     if (int rc = validate(p)) return rc;
     if (spec.weights) if (int rc = check_corner_weights(p->view_count, p->n_views, spec.weights)) return rc;
+    if (int rc = check_camera_priors(spec.priors, p->n_cameras)) return rc;
     if (int rc = create_scoped(p, device, sp)) return rc;
     sp->loss = spec.loss;
     if (spec.fixed) if (int rc = tscm_solver_set_fixed_intrinsics(sp.get(), spec.fixed)) return rc;
     if (spec.weights) if (int rc = tscm_solver_set_corner_weights(sp.get(), spec.weights)) return rc;
+    if (spec.priors) if (int rc = tscm_solver_set_camera_priors(sp.get(), spec.priors)) return rc;
     return 0;
 }
 
@@ -1349,6 +1403,12 @@ extern "C" int tscm_solve_weighted(const tscm_problem *p, const tscm_options *op
                                    tscm_summary *sum)
 {
     return solve_once(p, opt, spec_args(kind, scale, fixed, weights), sum);
+}
+
+extern "C" int tscm_solve_prior(const tscm_problem *p, const tscm_options *opt, const double *weights, const unsigned short *fixed, int kind, double scale,
+                                const tscm_camera_priors *priors, tscm_summary *sum)
+{
+    return solve_once(p, opt, spec_args(kind, scale, fixed, weights, priors), sum);
 }
 
 extern "C" int tscm_solve_multi(const tscm_problem *p, const tscm_options *opt, tscm_summary *sum)
@@ -1428,6 +1488,13 @@ extern "C" int tscm_eval_step_weighted(const tscm_problem *p, int device, const 
     return eval_step(p, device, opt, spec_args(kind, scale, fixed, weights), cam_rt, intr, board_rt, valid, summary);
 }
 
+extern "C" int tscm_eval_step_prior(const tscm_problem *p, int device, const tscm_options *opt, const double *weights, const unsigned short *fixed,
+                                    int kind, double scale, const tscm_camera_priors *priors, double *cam_rt, double *intr, double *board_rt, int *valid,
+                                    tscm_summary *summary)
+{
+    return eval_step(p, device, opt, spec_args(kind, scale, fixed, weights, priors), cam_rt, intr, board_rt, valid, summary);
+}
+
 // ------------------------------------------------------------------------------------------------
 // operator level
 // ------------------------------------------------------------------------------------------------
@@ -1505,12 +1572,14 @@ static int solver_normal_equations(tscm_solver *s, const tscm_options &opt, bool
                                    double *view_cross, double *cam_gram, double *cam_grad, double *cost)
 {
     int rc;
-    s->xp = plan_exec(s->L, s->C, s->P.n_act, kCommNone, opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev, !as_solved);     // (its Gram kernel)
+    s->xp = plan_exec(s->L, s->C, s->P.n_act, kCommNone, opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev, !as_solved, s->n_priors > 0);     // (its Gram kernel)
     if ((rc = prepare_eval(s, s->xp.f32() ? 1 : 0))) return rc;
     const DevProblem &P = s->P;
     DevState &S = s->S;
     if ((rc = launch_eval(s, 0))) return rc;
-    hipLaunchKernelGGL(k_reduce_stats, dim3(P.C * kCamSl), dim3(256), 0, s->stream, P, S, 0, 0);   // camera blocks only
+    // camera blocks only (camera priors: added there, at the problem's parameters in buffer 0)
+    if (s->xp.priors) hipLaunchKernelGGL(k_reduce_stats_prior, dim3(P.C * kCamSl), dim3(256), 0, s->stream, P, S, 0, 0, s->prior_arg());
+    else hipLaunchKernelGGL(k_reduce_stats, dim3(P.C * kCamSl), dim3(256), 0, s->stream, P, S, 0, 0);
     hipLaunchKernelGGL(k_finalize_eval, dim3(P.C), dim3(256), 0, s->stream, P, S, 0);            // camera blocks only
     HIP_TRY(hipStreamSynchronize(s->stream));
     HIP_TRY(hipGetLastError());
@@ -1559,7 +1628,7 @@ int tscm_eval_normal_equations_spec(const tscm_problem *p, int device, const tsc
 {
     SolveSpec spec;
     tscm_options opt;
-    int rc = preamble(p, !p, "problem is NULL", opt_in, spec_args(in.loss.kind, in.loss.a, nullptr, in.weights), spec, opt);
+    int rc = preamble(p, !p, "problem is NULL", opt_in, spec_args(in.loss.kind, in.loss.a, nullptr, in.weights, in.priors), spec, opt);
     if (rc) return rc;
     opt.max_num_iterations = 0;         // (no iteration runs: the caller's count is not used)
     if ((rc = check_options(opt, spec.loss.kind, spec.weights != nullptr))) return rc;
@@ -1602,6 +1671,13 @@ extern "C" int tscm_eval_normal_equations_weighted(const tscm_problem *p, int de
                                                    double *cam_grad, double *cost)
 {
     return tscm_eval_normal_equations_spec(p, device, opt, spec_args(kind, scale, nullptr, weights), board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
+}
+
+extern "C" int tscm_eval_normal_equations_prior(const tscm_problem *p, int device, const tscm_options *opt, const double *weights, int kind, double scale,
+                                                const tscm_camera_priors *priors, double *board_gram, double *board_grad, double *view_cross,
+                                                double *cam_gram, double *cam_grad, double *cost)
+{
+    return tscm_eval_normal_equations_spec(p, device, opt, spec_args(kind, scale, nullptr, weights, priors), board_gram, board_grad, view_cross, cam_gram, cam_grad, cost);
 }
 
 // k_project (3 -> 2) and k_unproject (2 -> 3): n rows of `in` through one camera's intrinsics
@@ -1834,7 +1910,7 @@ static int solve_mono_batch(const tscm_problem *problems, int n_problems, int de
     // problems without a single corner: what the single-problem entry point returns for them
     for (int i = 0; i < n_problems; ++i) {
         if (bp.dev_of[i] >= 0) continue;
-        if (int rc = solve_configured(&problems[i], opt_in, SolveSpec{ loss, fixed ? fixed + i : nullptr, nullptr }, &summaries[i])) return rc;
+        if (int rc = solve_configured(&problems[i], opt_in, SolveSpec{ loss, fixed ? fixed + i : nullptr, nullptr, nullptr }, &summaries[i])) return rc;
     }
     // the batch's times in every summary
     const double t_end = wall();

@@ -178,6 +178,12 @@ class CCovarianceInfo(C.Structure):
                 ("cost", C.c_double), ("sigma2", C.c_double), ("min_pivot_ratio", C.c_double), ("seconds_kernel", C.c_double * 4)]
 
 
+class CCameraPriors(C.Structure):
+    """tscm_camera_priors (tscm.h)"""
+    _fields_ = [("struct_size", C.c_size_t), ("cam_rt_mean", C.c_void_p), ("cam_rt_weight", C.c_void_p), ("intr_mean", C.c_void_p),
+                ("intr_weight", C.c_void_p)]
+
+
 class CUncertaintyGrid(C.Structure):
     """tscm_uncertainty_grid (tscm.h)"""
     _fields_ = [("struct_size", C.c_int), ("nx", C.c_int), ("ny", C.c_int), ("width_b", C.c_int), ("height_b", C.c_int),
@@ -215,6 +221,7 @@ EXPORTS = [
     "tscm_covariance", "tscm_covariance_from_normal_equations",
     "tscm_solver_set_corner_weights", "tscm_solve_weighted", "tscm_eval_normal_equations_weighted", "tscm_eval_step_weighted",
     "tscm_solve_mono_batch_weighted", "tscm_covariance_weighted",
+    "tscm_solver_set_camera_priors", "tscm_solve_prior", "tscm_eval_normal_equations_prior", "tscm_eval_step_prior", "tscm_covariance_prior",
     "tscm_projection_uncertainty", "tscm_projection_uncertainty_seconds",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
@@ -311,6 +318,12 @@ def lib():
     L.tscm_solve_mono_batch_weighted.argtypes = [C.POINTER(CProblem), C.c_int, C.c_int, C.POINTER(COptions), usp, C.POINTER(dp), C.c_int, C.c_double,
                                                  C.POINTER(CSummary)]
     L.tscm_covariance_weighted.argtypes = [C.POINTER(CProblem), C.c_int, usp, dp, C.c_int, C.c_double, dp, dp, dp, dp, dp, cip]
+    pp = C.POINTER(CCameraPriors)
+    L.tscm_solver_set_camera_priors.argtypes = [vp, pp]
+    L.tscm_solve_prior.argtypes = [C.POINTER(CProblem), C.POINTER(COptions), dp, usp, C.c_int, C.c_double, pp, C.POINTER(CSummary)]
+    L.tscm_eval_normal_equations_prior.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, C.c_int, C.c_double, pp, dp, dp, dp, dp, dp, dp]
+    L.tscm_eval_step_prior.argtypes = [C.POINTER(CProblem), C.c_int, C.POINTER(COptions), dp, usp, C.c_int, C.c_double, pp, dp, dp, dp, ip, C.POINTER(CSummary)]
+    L.tscm_covariance_prior.argtypes = [C.POINTER(CProblem), C.c_int, usp, dp, C.c_int, C.c_double, pp, dp, dp, dp, dp, dp, cip]
     L.tscm_projection_uncertainty.argtypes = [C.c_int, dp, dp, dp, C.c_double, C.POINTER(CUncertaintyGrid), C.POINTER(CUncertaintyRequest), C.c_int, C.c_int,
                                               dp, C.POINTER(C.c_ubyte), dp, C.POINTER(C.c_longlong)]
     L.tscm_projection_uncertainty_seconds.argtypes = []
@@ -510,6 +523,39 @@ def corner_weights(problem, weights=None, built_count=None):
         return problem, w
     q = dataclasses.replace(problem, view_count=np.where(dead, 0, cnt).astype(np.int32), weights=None)
     return q, np.ascontiguousarray(w[~dead[view_of]])
+
+
+class CameraPriors:
+    """Gaussian priors on camera-side coordinates (tscm.h: tscm_camera_priors) -- Ceres' NormalPrior on single coordinates:
+    residual sqrt(weight) * (x - mean) per coordinate with a weight > 0.  cam_rt_mean / cam_rt_weight [C, 6] on the raw pose
+    vectors, intr_mean / intr_weight [C, 9] on fx fy cx cy xi lambda alpha b c; either pair may be None.  The library checks the
+    values; a weight on a coordinate that is not free in a solve counts as 0 there.  api.camera_priors() builds one from sigmas."""
+
+    def __init__(self, cam_rt_mean=None, cam_rt_weight=None, intr_mean=None, intr_weight=None):
+        as_array = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        self.cam_rt_mean, self.cam_rt_weight = as_array(cam_rt_mean), as_array(cam_rt_weight)
+        self.intr_mean, self.intr_weight = as_array(intr_mean), as_array(intr_weight)
+
+    def c_struct(self, n_cameras: int) -> CCameraPriors:
+        """The struct of the C ABI; it references this object's arrays: keep the object alive."""
+        q = CCameraPriors(struct_size=C.sizeof(CCameraPriors))
+        for name, per in (("cam_rt_mean", 6), ("cam_rt_weight", 6), ("intr_mean", 9), ("intr_weight", 9)):
+            a = getattr(self, name)
+            if a is not None:
+                if a.size != per * n_cameras:
+                    raise ValueError(f"priors.{name}: {a.size} entries for {n_cameras} cameras ([C, {per}])")
+                setattr(q, name, a.ctypes.data)
+        return q
+
+
+def priors_ptr(priors, n_cameras: int):
+    """(pointer argument of the C ABI, what to keep alive) for None or a CameraPriors"""
+    if priors is None:
+        return None, None
+    if not isinstance(priors, CameraPriors):
+        raise TypeError("priors must be None or a lib.CameraPriors (api.camera_priors builds one)")
+    q = priors.c_struct(n_cameras)
+    return C.byref(q), (q, priors)
 
 
 def ushort_ptr(a: np.ndarray):

@@ -80,8 +80,19 @@ def _finish_camera(q, count, sel):
     return q.intr[0].copy(), Rt
 
 
+def _priors_kw(problem, priors):
+    """{} without priors (the calls of a run without them), or priors= for api.refinement / calibrate / covariance: priors is the
+    keyword arguments of api.camera_priors (intr_sigma, cam_rt_sigma, pixel_sigma) -- Gaussian priors about the values the
+    solve starts from."""
+    if priors is None:
+        return {}
+    if "mean" in priors:
+        raise ValueError("pipeline priors are about the start values: give sigmas (intr_sigma, cam_rt_sigma, pixel_sigma), no mean")
+    return dict(priors=api.camera_priors(problem, **priors))
+
+
 def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None, ransac=None,
-                     mask_outliers=False):
+                     mask_outliers=False, priors=None):
     """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
     principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
     intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
@@ -95,14 +106,16 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
     mask_outliers (with ransac): the RANSAC inlier mask of the kept views is the corner mask of the refinement
     (api.refinement(weights=inlier[has])): a corner the consensus set excludes is taken out instead of weighed down.  False: the
     calls of a run without it.
+    priors: None, or dict(intr_sigma={"xi": 0.1, ...}[, pixel_sigma=...]): Gaussian priors on the intrinsics about the values the
+    refinement starts from (api.camera_priors; the pose of a mono problem is not free, so cam_rt_sigma counts for nothing).
     Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
     w = _model_masks(model, fixed, 1)
     q, count, sel, found = _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr, model, ransac)
     cw = _inlier_weights(found, sel, mask_outliers)
     if cw is not None:
-        _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None, weights=cw)
+        _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None, weights=cw, **_priors_kw(q, priors))
     else:
-        _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None)
+        _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None, **_priors_kw(q, priors))
     intr, Rt = _finish_camera(q, count, sel)
     if found is not None:
         summary["ransac"] = found
@@ -169,17 +182,18 @@ def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, devi
 
 
 def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                    fixed=None, ransac=None, mask_outliers=False) -> dict:
+                    fixed=None, ransac=None, mask_outliers=False, priors=None) -> dict:
     """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
     loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
     and held intrinsics of both refinements (calibrate_camera).
     ransac: None, or rig.ransac_params(...) for the start poses of both calibrate() calls (calibrate_camera); a view either
     call drops leaves `has`, and the result carries ransac = the second call's dict(inlier, code, has).
     mask_outliers (with ransac): each of the two refinements takes its own call's inlier mask as its corner mask (calibrate_camera).
+    priors: Gaussian priors of both refinements, each about its own start values (calibrate_camera).
     Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
     img_size, has, pu, pv = _detect(images, cols, rows, sigma, device)
     intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed,
-                                       ransac=ransac, mask_outliers=mask_outliers)                                               # :57
+                                       ransac=ransac, mask_outliers=mask_outliers, priors=priors)                               # :57
     if ransac is not None:
         has = first["ransac"]["has"]
     _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device)
@@ -187,7 +201,7 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
     intr, Rt, second = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr=warm, loss=loss, model=model,
-                                        fixed=fixed, ransac=ransac, mask_outliers=mask_outliers)
+                                        fixed=fixed, ransac=ransac, mask_outliers=mask_outliers, priors=priors)
     out = dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
     if ransac is not None:
         out.update(has=second["ransac"]["has"], ransac=second["ransac"])
@@ -222,7 +236,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -241,7 +255,12 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     result["uncertainty"] = api.projection_uncertainty on the grid x, y = 0, step, 2 step, ... of the image, with one observe
     request per camera (at the first inverse distance) and one transfer request per ordered pair of adjacent cameras (m, m + 1
     and back; for three and more cameras also the last and the first) per inverse distance: how many pixels a transferred pixel
-    -- and above all its component across the epipolar line -- is uncertain (uncertainty_requests lists them)."""
+    -- and above all its component across the epipolar line -- is uncertain (uncertainty_requests lists them).
+    priors: None, or dict(intr_sigma=..., cam_rt_sigma=...[, pixel_sigma=...]) as for api.camera_priors: Gaussian priors of every
+    mono refinement (intrinsics), of the joint solve about the values it starts from -- the mono intrinsics and rig_init's poses --
+    and, about those same values, of the covariance.  Not with batch_mono (the batched route has no priors): ValueError."""
+    if priors is not None and batch_mono:
+        raise ValueError("batch_mono=True has no priors: the batched mono route does not take them")
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
     if batch_mono:
@@ -249,7 +268,7 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
                                      mask_outliers=mask_outliers)
     else:
         mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]), ransac=ransac,
-                                mask_outliers=mask_outliers)
+                                mask_outliers=mask_outliers, priors=None if priors is None else {k: v for k, v in priors.items() if k != "cam_rt_sigma"})
                 for m, imgs in enumerate(images_by_camera)]
     W = board_points(cols, rows, pitch)
     inp = rig.RigInput(W, np.stack([m["intr"] for m in mono]), np.stack([m["has"] for m in mono]), np.stack([m["Rt"] for m in mono]),
@@ -258,18 +277,21 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     problem = rig.problem_from_rig(inp, g)
     _start_in_model(problem.intr, model)
     cw = rig_corner_mask(problem, mono) if mask_outliers and ransac is not None else None
+    pk = _priors_kw(problem, priors)        # (about the start values: built before the solve moves them)
     if cw is not None:
-        summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw)
+        summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw, **pk)
     else:
-        summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None)
+        summary = api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None, **pk)
     out = dict(problem=problem, mono=mono, rig_init=g, summary=summary)
+    if pk:
+        out["priors"] = pk["priors"]
     if cw is not None:
         out["corner_mask"] = cw
     if covariance or uncertainty is not None:
         if cw is not None:
-            out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw)
+            out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw, **pk)
         else:
-            out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None)
+            out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None, **pk)
     if uncertainty is not None:
         step = float(uncertainty["step"])
         img_w, img_h = images_by_camera[0][0].shape[1], images_by_camera[0][0].shape[0]
