@@ -6,7 +6,7 @@
 //   examples/calibrate_from_corners corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>]
 //                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]]
 //                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance]
-//                                   [--uncertainty STEP[,INV_DISTANCE]]
+//                                   [--uncertainty STEP[,INV_DISTANCE]] [--suggest N[,DISTANCE...]]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
@@ -25,7 +25,10 @@
 //    x, y = 0, STEP, 2 STEP, ... of the corner file's image size at INV_DISTANCE (1 / distance in 1 / the pitch's unit; default
 //    0, infinity): per camera the largest and the median sd_worst of a fixed point seen in that camera, per pair of adjacent
 //    cameras the largest and the median sd_across of a pixel transferred from the first to the second -- the pixels by which
-//    rectified rows stop being rows)
+//    rectified rows stop being rows
+//    --suggest (rigs; implies --covariance): where to hold the board next -- N poses chosen greedily by the covariance each
+//    would remove (MultiCalib::suggest_views; default distances: 5 and 10 board diagonals), printed behind the covariance
+//    report: `suggest k camera_a[+camera_b] pixel u v distance d tilt x y gain_logdet g gain_trace t visible n[,n]`)
 #include <tscm/tscm_calib.hpp>
 
 #include <algorithm>
@@ -43,6 +46,8 @@ int main(int argc, char **argv)
     double prior_sigma[7] = { 0, 0, 0, 0, 0, 0, 0 };
     bool bad_args = argc < 3, use_ransac = false, ransac_mask = false, covariance = false, uncertainty = false;
     double unc_step = 0.0, unc_inv_distance = 0.0;
+    int suggest = 0;
+    std::vector<double> suggest_distances;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
     for (int i = 3; i < argc && !bad_args; ++i) {
@@ -79,6 +84,19 @@ int main(int argc, char **argv)
             }
             bad_args = bad_args || *end != '\0';
             uncertainty = covariance = true;
+        } else if (!std::strcmp(argv[i], "--suggest") && i + 1 < argc) {
+            char *end = nullptr;
+            const char *at = argv[++i];
+            suggest = (int)std::strtol(at, &end, 10);
+            bad_args = end == at || suggest < 1;
+            while (!bad_args && *end == ',') {
+                at = end + 1;
+                const double d = std::strtod(at, &end);
+                bad_args = end == at || !(d > 0.0) || !std::isfinite(d);
+                suggest_distances.push_back(d);
+            }
+            bad_args = bad_args || *end != '\0';
+            covariance = true;
         } else {
             bad_args = true;
         }
@@ -86,7 +104,7 @@ int main(int argc, char **argv)
     bad_args = bad_args || (ransac_mask && !use_ransac);
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]] [--suggest N[,DISTANCE...]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -165,6 +183,24 @@ int main(int argc, char **argv)
                         const double nan = std::nan(""), vmax = v.empty() ? nan : v.back(), vmed = v.empty() ? nan : v[v.size() / 2];
                         if (observe) std::printf("uncertainty camera_%d sd_worst max %.17g median %.17g valid %lld\n", req[r].camera_a, vmax, vmed, unc.n_valid[r]);
                         else std::printf("uncertainty camera_%d->camera_%d sd_across max %.17g median %.17g valid %lld\n", req[r].camera_a, req[r].camera_b, vmax, vmed, unc.n_valid[r]);
+                    }
+                }
+                if (suggest > 0 && cov.info.status == 0) {
+                    if (suggest_distances.empty()) {
+                        const double diag = cs.pitch * std::sqrt((double)((board.width - 1) * (board.width - 1) + (board.height - 1) * (board.height - 1)));
+                        suggest_distances.push_back(5.0 * diag);
+                        suggest_distances.push_back(10.0 * diag);
+                    }
+                    const std::vector<tscm::MultiCalib::SuggestedView> views = mul_calib.suggest_views(cov, image, suggest, suggest_distances);
+                    for (size_t k = 0; k < views.size(); ++k) {
+                        const tscm::MultiCalib::SuggestedView &v = views[k];
+                        const bool pair = v.candidate.camera_a != v.candidate.camera_b;
+                        std::printf("suggest %d camera_%d", (int)k, v.candidate.camera_a);
+                        if (pair) std::printf("+camera_%d", v.candidate.camera_b);
+                        std::printf(" pixel %.1f %.1f distance %.17g tilt %g %g gain_logdet %.17g gain_trace %.17g visible %d", v.pixel[0], v.pixel[1], v.distance, v.tilt_x,
+                                    v.tilt_y, v.gain_logdet, v.gain_trace, v.n_visible[0]);
+                        if (pair) std::printf(",%d", v.n_visible[1]);
+                        std::printf("\n");
                     }
                 }
             }

@@ -642,6 +642,88 @@ int tscm_projection_uncertainty(int n_cameras, const double *cam_rt, const doubl
  * uploads and read-back are outside); 0 after a call that was refused or failed */
 double tscm_projection_uncertainty_seconds(void);
 
+/* ------------------------------------------------------------------ next-best view
+ * Where should the board go next?  A hypothetical view's Jacobian depends on the current parameters only, not on any
+ * observation, so what the view would do to the camera covariance of tscm_covariance is known before the image is taken: a
+ * low-rank update of the camera block (Peng and Sturm, Calibration Wizard, ICCV 2019).  This stage scores many candidate
+ * board poses by the covariance they would remove and can apply one of them, which makes greedy planning possible without a
+ * re-solve.  A stage of its own behind tscm_covariance; it runs no other kernel of the library.
+ *
+ * Inputs.  n_cameras (1..32); cam_rt [C*6], intr [C*9] (b and c are not read); cam_cov [C*15][C*15] as tscm_covariance
+ * returns it (unscaled, zero rows and columns where a column is not free; the lower triangle is read); weights [C*15] or
+ * NULL; the board, n_points (1..1024) and board_xy [n_points*2]; image_size [C*2] (width, height of each camera, > 0);
+ * params (border >= 0 pixels, min_corners >= 4); candidates {camera_a, camera_b, board_rt[6]}, board_rt the board's pose in
+ * the rig frame as tscm_problem.board_rt.  camera_a == camera_b: one camera sees the board; otherwise both cameras see the
+ * same board instance.
+ * A corner in a camera m.  For corner j of the board, with the functor's chain (multi_calib.h:146-195):
+ *   P = R_board (x_j, y_j, 0) + t_board,   p = R_m P + t_m,   the projection of p with I_m, its k, A(p, I_m) and G(p, I_m) as
+ *   the projection uncertainty stage above defines them.
+ * The corner is visible iff k > 0, border <= u <= width_m - 1 - border and border <= v <= height_m - 1 - border.  Its rows:
+ *   E = A R_m [dR_board,k (x, y, 0) (k = 0..2) | I3]       2 x 6, the board side
+ *   F = [A dR_m,k P (k = 0..2) | A | G]                    2 x 13, the camera side: columns w_m, t_m, I_m
+ * (only Gram products are used, so the sign does not matter; both branches of AngleAxisRotatePoint and its derivatives).
+ * A camera of the candidate contributes iff its visible count is >= min_corners.  Invisible corners, and all corners of a
+ * camera that does not contribute, add nothing.
+ * Blocks.  theta = (w_a, t_a, I_a [, w_b, t_b, I_b]), n = 13 or 26 columns whether the cameras contribute or not; theta
+ * column c of camera m is row 15 m + c of cam_cov.  Summed over the contributing cameras' visible corners, in corner order
+ * (a corner's u row, then its v row) and camera order a then b:
+ *   B' = sum E^T E (6 x 6),  W' = sum E^T F (6 x n, into the camera's column group),  C' = sum F^T F (n x n, block diagonal)
+ *   Delta S = C' - W'^T B'^-1 W' = C' - Z^T Z,  B' = Lb Lb^T (6 x 6 Cholesky),  Z = Lb^-1 W'
+ * Delta S is the information about the camera-side parameters the view carries once its own unknown pose is eliminated.
+ * The update.  Sigma_tt [n][n] is gathered from cam_cov; d_k = sqrt(Sigma_tt,kk); Sigma_tt = D G~ G~^T D with G~ the lower
+ * Cholesky factor of the unit-diagonal matrix Sigma_tt,ij / (d_i d_j) (columns with Sigma_tt,kk == 0, not free, are skipped
+ * and give a zero column and row); G = D G~.
+ *   M = I + G^T Delta S G = L L^T  (symmetric, eigenvalues >= 1; the lower triangle of the computed M is factored),
+ *   Y = L^-1 G^T Delta S,   K = Delta S - Y^T Y   (= (Delta S^-1 + Sigma_tt)^-1 wherever that exists)
+ *   Sigma' = Sigma - Sigma[:, theta] K Sigma[theta, :]                 the covariance after the view
+ * Outputs per candidate:
+ *   gain_logdet = 2 sum_k log L_kk = log det Sigma_free - log det Sigma'_free, in nats; scale-free (sigma2 cancels)
+ *   gain_trace  = sum_k w_k (Sigma_kk - Sigma'_kk) = tr(K Q_tt),  Q = Sigma diag(w) Sigma over all 15 C columns, k ascending.
+ *                 weights == NULL: w_k = 1 / Sigma_kk where Sigma_kk > 0, else 0 -- the sum of relative variance reductions.
+ *                 The trace is summed column by column of K Q (row index ascending within a column, then columns ascending).
+ *   n_visible [2] (the second is 0 when camera_a == camera_b)
+ *   flags: bit 0 camera a contributes; bit 1 camera b contributes (only when a != b); bit 2 both gains are numbers; bit 3 a
+ *          pivot of B', of the scaled Sigma_tt or of M was not > 0.
+ * Without a contributing camera nothing behind the blocks is evaluated: the gains are exactly 0, bit 2 is set and bit 3 is
+ * not.  With bit 3 both gains are NaN.
+ * Apply: the same inputs and ONE candidate; that candidate's outputs and cam_cov_out [C*15][C*15] = Sigma'.  Each element
+ * of the lower triangle is Sigma_rc - sum_i Sigma_r,theta_i (sum_j K_ij Sigma_theta_j,c), i and j ascending, and is written to
+ * its mirror too, so the result is symmetric; rows that were zero stay zero.  A copy of cam_cov when no camera contributes;
+ * all NaN with bit 3.
+ * Two calls on the same input give the same bytes, and a candidate's outputs do not depend on its place in the batch (no
+ * floating-point atomics, every sum in a fixed order).
+ *
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a required pointer that is NULL
+ * (all but weights); params->struct_size other than sizeof(tscm_view_gain_params); n_cameras outside 1..32; n_points
+ * outside 1..1024; n_candidates <= 0 or above 2^24; camera_a or camera_b outside [0, n_cameras); a board_rt, board_xy,
+ * cam_rt or intr (its first seven per camera) that is not finite; border negative or not finite; min_corners < 4; an image
+ * size that is not positive; a weight that is negative or not finite.  device_index as elsewhere, after the argument
+ * checks. */
+typedef struct tscm_view_gain_params {
+    int struct_size;               /* sizeof(tscm_view_gain_params), set by the caller                                 */
+    int min_corners;               /* a camera contributes with at least this many visible corners; >= 4               */
+    double border;                 /* pixels a visible corner keeps from the image's edge; >= 0                        */
+} tscm_view_gain_params;
+
+typedef struct tscm_view_candidate {
+    int camera_a, camera_b;        /* equal: one camera sees the board                                                 */
+    double board_rt[6];            /* the board's pose in the rig frame: angle-axis, translation                       */
+} tscm_view_candidate;
+
+/* gain_logdet, gain_trace, flags [n_candidates], n_visible [n_candidates*2].  Host pointers. */
+int tscm_view_gain(int n_cameras, const double *cam_rt, const double *intr, const double *cam_cov, const double *weights,
+                   int n_points, const double *board_xy, const int *image_size, const tscm_view_gain_params *params,
+                   const tscm_view_candidate *candidates, int n_candidates, int device_index, double *gain_logdet,
+                   double *gain_trace, int *n_visible, int *flags);
+/* one candidate: gain_logdet, gain_trace, flags [1], n_visible [2], cam_cov_out [C*15][C*15] (must not alias cam_cov) */
+int tscm_view_gain_apply(int n_cameras, const double *cam_rt, const double *intr, const double *cam_cov, const double *weights,
+                         int n_points, const double *board_xy, const int *image_size, const tscm_view_gain_params *params,
+                         const tscm_view_candidate *candidate, int device_index, double *gain_logdet, double *gain_trace,
+                         int *n_visible, int *flags, double *cam_cov_out);
+/* device seconds of the launches of this thread's last tscm_view_gain or tscm_view_gain_apply call (HIP events around them;
+ * uploads and read-back are outside); 0 after a call that was refused or failed */
+double tscm_view_gain_seconds(void);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

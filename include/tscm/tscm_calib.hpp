@@ -895,6 +895,105 @@ public:
         return req;
     }
 
+    // Next-best view (tscm_view_gain) at the objects' current parameters under the covariance that covariance() returned:
+    // what a view of the board at each candidate pose (rig frame) would remove from the camera covariance.  image: every
+    // camera's image size; weights: [C*15] of gain_trace, empty for 1 / variance.
+    struct ViewGain {
+        std::vector<double> gain_logdet, gain_trace;   // [n_candidates]
+        std::vector<int> n_visible;                    // [n_candidates][2]
+        std::vector<int> flags;                        // [n_candidates]: bit 0 / 1 camera a / b contributes, 2 numbers, 3 a pivot failed
+        std::vector<double> cam_cov;                   // view_gain_apply only: [C*15][C*15], the covariance after the view
+    };
+    ViewGain view_gain(const Covariance &cov, const std::vector<tscm_view_candidate> &candidates, Size image, double border = 0.0, int min_corners = 8,
+                       const std::vector<double> &weights = std::vector<double>()) const
+    {
+        return view_gain_on(cov.cam_cov, candidates.data(), (int)candidates.size(), false, image, border, min_corners, weights);
+    }
+    // one candidate applied (tscm_view_gain_apply) to cam_cov [C*15][C*15] -- covariance().cam_cov or an earlier call's
+    // cam_cov: its outputs and the covariance after the view, for greedy planning without a re-solve
+    ViewGain view_gain_apply(const std::vector<double> &cam_cov, const tscm_view_candidate &candidate, Size image, double border = 0.0, int min_corners = 8,
+                             const std::vector<double> &weights = std::vector<double>()) const
+    {
+        return view_gain_on(cam_cov, &candidate, 1, true, image, border, min_corners, weights);
+    }
+    // Greedy next-best views (pipeline.suggest_views): the candidates are, for every camera alone and (pairs) together with the
+    // next one, the board centred on the ray of each pixel of a grid_x x grid_y grid of the image at each distance, facing the
+    // camera, then tilted by +-tilt_deg about its x and about its y axis; n_views times: score all (view_gain), take the first
+    // arg-max of gain_logdet, apply it (view_gain_apply).  Stops early when no candidate has a positive, finite gain.
+    struct SuggestedView {
+        tscm_view_candidate candidate;
+        double pixel[2], distance, tilt_x, tilt_y;   // of the board centre in camera_a, degrees
+        double gain_logdet, gain_trace;
+        int n_visible[2], flags;
+    };
+    std::vector<SuggestedView> suggest_views(const Covariance &cov, Size image, int n_views, const std::vector<double> &distances, int grid_x = 6, int grid_y = 4,
+                                             double tilt_deg = 25.0, bool pairs = true, double border = 0.0, int min_corners = 8) const
+    {
+        const int C = (int)cameras_.size();
+        double centre[3] = { 0.0, 0.0, 0.0 };
+        for (size_t j = 0; j < worlds_.size(); ++j) { centre[0] += worlds_[j].x / (double)worlds_.size(); centre[1] += worlds_[j].y / (double)worlds_.size(); }
+        const double tilts[5][2] = { { 0, 0 }, { tilt_deg, 0 }, { -tilt_deg, 0 }, { 0, tilt_deg }, { 0, -tilt_deg } };
+        std::vector<double> px;
+        for (int j = 0; j < grid_y; ++j)
+            for (int i = 0; i < grid_x; ++i) { px.push_back((i + 0.5) * image.width / grid_x - 0.5); px.push_back((j + 0.5) * image.height / grid_y - 0.5); }
+        std::vector<SuggestedView> all;
+        std::vector<tscm_view_candidate> cands;
+        for (int m = 0; m < C; ++m) {
+            std::vector<double> rays(3 * px.size() / 2 + 3);
+            check(tscm_unproject_pixels(cameras_[m].intrinsic_.data(), px.data(), (int)(px.size() / 2), device_, rays.data()));
+            double Rm[9];
+            view_rotation(cameras_[m].rt_.data(), Rm);
+            for (int second = 0; second < (pairs && C > 1 && (m + 1 < C || C > 2) ? 2 : 1); ++second)
+                for (size_t q = 0; q < px.size() / 2; ++q) {
+                    const double *z = &rays[3 * q];
+                    if (!(z[0] == z[0] && z[1] == z[1] && z[2] == z[2])) continue;
+                    for (size_t d = 0; d < distances.size(); ++d)
+                        for (int t = 0; t < (tilt_deg != 0.0 ? 5 : 1); ++t) {
+                            // the board's frame in the camera: z the ray, x the camera's x (or y) made orthogonal to it, then the tilts
+                            const double zn = std::sqrt(z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+                            const double zz[3] = { z[0] / zn, z[1] / zn, z[2] / zn };
+                            const int ax = std::fabs(zz[0]) < 0.9 ? 0 : 1;
+                            double x[3] = { -zz[ax] * zz[0], -zz[ax] * zz[1], -zz[ax] * zz[2] };
+                            x[ax] += 1.0;
+                            const double xn = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+                            for (int k = 0; k < 3; ++k) x[k] /= xn;
+                            const double y[3] = { zz[1] * x[2] - zz[2] * x[1], zz[2] * x[0] - zz[0] * x[2], zz[0] * x[1] - zz[1] * x[0] };
+                            double Rcb[9] = { x[0], y[0], zz[0], x[1], y[1], zz[1], x[2], y[2], zz[2] }, T[9], tmp[9];
+                            const double wx[3] = { tilts[t][0] * 3.14159265358979323846 / 180.0, 0.0, 0.0 }, wy[3] = { 0.0, tilts[t][1] * 3.14159265358979323846 / 180.0, 0.0 };
+                            view_rotation(wx, T); view_mul(Rcb, T, tmp); view_rotation(wy, T); view_mul(tmp, T, Rcb);
+                            // t_cb = distance * ray - R_cb centre; rig frame: R = R_m^T R_cb, t = R_m^T (t_cb - t_m)
+                            double tcb[3], Rrb[9];
+                            for (int k = 0; k < 3; ++k) tcb[k] = distances[d] * zz[k] - (Rcb[3 * k] * centre[0] + Rcb[3 * k + 1] * centre[1]) - cameras_[m].rt_[3 + k];
+                            for (int r = 0; r < 3; ++r)
+                                for (int c = 0; c < 3; ++c) Rrb[3 * r + c] = Rm[r] * Rcb[c] + Rm[3 + r] * Rcb[3 + c] + Rm[6 + r] * Rcb[6 + c];
+                            SuggestedView v = SuggestedView();
+                            v.candidate.camera_a = m;
+                            v.candidate.camera_b = second ? (m + 1) % C : m;
+                            view_angle_axis(Rrb, v.candidate.board_rt);
+                            for (int k = 0; k < 3; ++k) v.candidate.board_rt[3 + k] = Rm[k] * tcb[0] + Rm[3 + k] * tcb[1] + Rm[6 + k] * tcb[2];
+                            v.pixel[0] = px[2 * q]; v.pixel[1] = px[2 * q + 1]; v.distance = distances[d]; v.tilt_x = tilts[t][0]; v.tilt_y = tilts[t][1];
+                            all.push_back(v);
+                            cands.push_back(v.candidate);
+                        }
+                }
+        }
+        std::vector<SuggestedView> chosen;
+        std::vector<double> cc = cov.cam_cov;
+        for (int step = 0; step < n_views && !cands.empty(); ++step) {
+            const ViewGain g = view_gain_on(cc, cands.data(), (int)cands.size(), false, image, border, min_corners, std::vector<double>());
+            int best = -1;
+            for (size_t i = 0; i < cands.size(); ++i)
+                if ((g.flags[i] & 4) && g.gain_logdet[i] > 0.0 && (best < 0 || g.gain_logdet[i] > g.gain_logdet[(size_t)best])) best = (int)i;
+            if (best < 0) break;
+            const ViewGain one = view_gain_on(cc, &cands[(size_t)best], 1, true, image, border, min_corners, std::vector<double>());
+            SuggestedView v = all[(size_t)best];
+            v.gain_logdet = one.gain_logdet[0]; v.gain_trace = one.gain_trace[0]; v.n_visible[0] = one.n_visible[0]; v.n_visible[1] = one.n_visible[1]; v.flags = one.flags[0];
+            chosen.push_back(v);
+            cc = one.cam_cov;
+        }
+        return chosen;
+    }
+
     // main.cpp:305-319
     void write_yaml(const std::string &path) const
     {
@@ -925,6 +1024,72 @@ public:
     double mean_error;                        // "average reproject error" (:283)
 
 private:
+    // R (row-major) of an angle-axis vector, both branches of ceres::AngleAxisRotatePoint
+    static void view_rotation(const double *w, double *R)
+    {
+        const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+        if (t2 > 2.220446049250313e-16) {
+            const double th = std::sqrt(t2), c = std::cos(th), s = std::sin(th), k[3] = { w[0] / th, w[1] / th, w[2] / th };
+            for (int r = 0; r < 3; ++r)
+                for (int q = 0; q < 3; ++q) R[3 * r + q] = (r == q ? c : 0.0) + (1.0 - c) * k[r] * k[q];
+            R[1] -= s * k[2]; R[2] += s * k[1]; R[3] += s * k[2]; R[5] -= s * k[0]; R[6] -= s * k[1]; R[7] += s * k[0];
+        } else {
+            const double I[9] = { 1.0, -w[2], w[1], w[2], 1.0, -w[0], -w[1], w[0], 1.0 };
+            std::memcpy(R, I, sizeof(I));
+        }
+    }
+    static void view_mul(const double *A, const double *B, double *out)
+    {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) out[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+    }
+    // the angle-axis vector of a rotation matrix, angle in [0, pi]
+    static void view_angle_axis(const double *R, double *w)
+    {
+        const double v[3] = { R[7] - R[5], R[2] - R[6], R[3] - R[1] };
+        const double s = 0.5 * std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]), c = 0.5 * (R[0] + R[4] + R[8] - 1.0), th = std::atan2(s, c);
+        if (s > 1e-8) { for (int k = 0; k < 3; ++k) w[k] = v[k] * (th / (2.0 * s)); return; }
+        if (c > 0.0) { for (int k = 0; k < 3; ++k) w[k] = 0.5 * v[k]; return; }
+        double k[3], n = 0.0;                                    // angle pi: R = 2 k k^T - I
+        int big = 0;
+        for (int i = 0; i < 3; ++i) { const double h = 0.5 * (R[4 * i] + 1.0); k[i] = std::sqrt(h > 0.0 ? h : 0.0); if (k[i] > k[big]) big = i; }
+        for (int i = 0; i < 3; ++i) { if (i != big && R[3 * big + i] + R[3 * i + big] < 0.0) k[i] = -k[i]; n += k[i] * k[i]; }
+        for (int i = 0; i < 3; ++i) w[i] = th * k[i] / std::sqrt(n);
+    }
+
+    ViewGain view_gain_on(const std::vector<double> &cam_cov, const tscm_view_candidate *candidates, int n, bool apply, Size image, double border,
+                          int min_corners, const std::vector<double> &weights) const
+    {
+        const size_t C = cameras_.size(), R = (size_t)(n > 0 ? n : 0);
+        std::vector<double> crt(6 * C), I(9 * C), xy(2 * worlds_.size());
+        std::vector<int> size(2 * C);
+        for (size_t m = 0; m < C; ++m) {
+            std::memcpy(&crt[6 * m], cameras_[m].rt_.data(), 6 * sizeof(double));
+            std::memcpy(&I[9 * m], cameras_[m].intrinsic_.data(), 9 * sizeof(double));
+            size[2 * m] = image.width; size[2 * m + 1] = image.height;
+        }
+        for (size_t j = 0; j < worlds_.size(); ++j) { xy[2 * j] = worlds_[j].x; xy[2 * j + 1] = worlds_[j].y; }
+        if (cam_cov.size() != 15 * C * 15 * C) throw std::invalid_argument("view_gain: cam_cov is not [C*15][C*15]");
+        if (!weights.empty() && weights.size() != 15 * C) throw std::invalid_argument("view_gain: weights is not [C*15]");
+        tscm_view_gain_params prm = tscm_view_gain_params();
+        prm.struct_size = (int)sizeof(tscm_view_gain_params);
+        prm.min_corners = min_corners;
+        prm.border = border;
+        ViewGain out;
+        out.gain_logdet.assign(R + 1, 0.0); out.gain_trace.assign(R + 1, 0.0); out.n_visible.assign(2 * R + 2, 0); out.flags.assign(R + 1, 0);
+        const double *w = weights.empty() ? nullptr : weights.data();
+        if (apply) {
+            out.cam_cov.assign(cam_cov.size(), 0.0);
+            check(tscm_view_gain_apply((int)C, crt.data(), I.data(), cam_cov.data(), w, (int)worlds_.size(), xy.data(), size.data(), &prm, candidates, device_,
+                                       out.gain_logdet.data(), out.gain_trace.data(), out.n_visible.data(), out.flags.data(), out.cam_cov.data()));
+        } else {
+            check(tscm_view_gain((int)C, crt.data(), I.data(), cam_cov.data(), w, (int)worlds_.size(), xy.data(), size.data(), &prm, candidates, n, device_,
+                                 out.gain_logdet.data(), out.gain_trace.data(), out.n_visible.data(), out.flags.data()));
+        }
+        out.gain_logdet.resize(R); out.gain_trace.resize(R); out.n_visible.resize(2 * R); out.flags.resize(R);
+        return out;
+    }
+
     int device_;
 };
 

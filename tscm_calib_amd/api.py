@@ -630,3 +630,172 @@ def projection_uncertainty(cam_rt, intr, cov: dict, requests, grid: dict, device
                seconds_kernel=float(_l.lib().tscm_projection_uncertainty_seconds()))
     out.update({name: planes[:, k] for k, name in enumerate(UNCERTAINTY_PLANES)})
     return out
+
+
+# ----------------------------------------------------------------------------- next-best view (tscm_view_gain)
+VIEW_GAIN_FLAGS = dict(a_contributes=1, b_contributes=2, numbers=4, pivot=8)
+
+
+def _view_gain_args(cam_rt, intr, cov, board_xy, image_size, candidates, weights, border, min_corners):
+    rt, I = np.ascontiguousarray(cam_rt, dtype=np.float64), np.ascontiguousarray(intr, dtype=np.float64)
+    Cn = rt.shape[0]
+    cc = np.ascontiguousarray(cov["cam_cov"] if isinstance(cov, dict) else cov, dtype=np.float64)
+    xy = np.ascontiguousarray(board_xy, dtype=np.float64)
+    size = np.ascontiguousarray(image_size, dtype=np.int32)
+    if size.size == 2:
+        size = np.ascontiguousarray(np.tile(size.reshape(1, 2), (Cn, 1)))
+    if rt.shape != (Cn, 6) or I.shape != (Cn, 9) or cc.size != (15 * Cn) ** 2 or xy.ndim != 2 or xy.shape[1] != 2 or size.shape != (Cn, 2):
+        raise ValueError("shapes: cam_rt [C,6], intr [C,9], cam_cov [C,15,C,15], board_xy [P,2], image_size (w, h) or [C,2]")
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and w.size != 15 * Cn:
+        raise ValueError("weights: [C,15]")
+    cands = [(int(a), int(b), [float(x) for x in np.asarray(r, dtype=np.float64).reshape(6)]) for a, b, r in candidates]
+    arr = (_l.CViewCandidate * max(len(cands), 1))()
+    for k, (a, b, r) in enumerate(cands):
+        arr[k].camera_a, arr[k].camera_b = a, b
+        arr[k].board_rt[:] = r
+    prm = _l.CViewGainParams(struct_size=C.sizeof(_l.CViewGainParams), min_corners=int(min_corners), border=float(border))
+    keep = (rt, I, cc, xy, size, w, arr, prm)
+    head = (Cn, _l.dptr(rt), _l.dptr(I), _l.dptr(cc), None if w is None else _l.dptr(w), xy.shape[0], _l.dptr(xy), size.ctypes.data_as(C.POINTER(C.c_int)),
+            C.byref(prm), arr)
+    return head, len(cands), Cn, keep
+
+
+def view_gain(cam_rt, intr, cov, board_xy, image_size, candidates, weights=None, border: float = 0.0, min_corners: int = 8, device: int = 0) -> dict:
+    """Next-best view (tscm_view_gain): what a hypothetical view of the board at each candidate pose would remove from the
+    camera covariance.  cam_rt [C,6], intr [C,9]: the calibration; cov: the dict of covariance() or its cam_cov; board_xy
+    [P,2]; image_size (width, height) or [C,2]; candidates: (camera_a, camera_b, board_rt[6]) triples, board_rt in the rig
+    frame (camera_a == camera_b: one camera sees the board); weights [C,15] of gain_trace or None (1 / variance).
+    -> gain_logdet, gain_trace [R], n_visible [R,2], flags [R] (VIEW_GAIN_FLAGS), seconds_kernel."""
+    head, R, _, keep = _view_gain_args(cam_rt, intr, cov, board_xy, image_size, candidates, weights, border, min_corners)
+    ld, tr = np.zeros(R), np.zeros(R)
+    nv, fl = np.zeros((R, 2), dtype=np.int32), np.zeros(R, dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    _l.check(_l.lib().tscm_view_gain(*head, R, device, _l.dptr(ld), _l.dptr(tr), nv.ctypes.data_as(ip), fl.ctypes.data_as(ip)))
+    del keep
+    return dict(gain_logdet=ld, gain_trace=tr, n_visible=nv, flags=fl, seconds_kernel=float(_l.lib().tscm_view_gain_seconds()))
+
+
+def view_gain_apply(cam_rt, intr, cov, board_xy, image_size, candidate, weights=None, border: float = 0.0, min_corners: int = 8, device: int = 0) -> dict:
+    """One candidate applied (tscm_view_gain_apply): its outputs as view_gain gives them (scalars, n_visible [2]) and cam_cov
+    [C,15,C,15], the camera covariance after the view -- what the next view_gain call takes for greedy planning."""
+    head, _, Cn, keep = _view_gain_args(cam_rt, intr, cov, board_xy, image_size, [candidate], weights, border, min_corners)
+    ld, tr = C.c_double(0.0), C.c_double(0.0)
+    nv, fl = np.zeros(2, dtype=np.int32), C.c_int(0)
+    out = np.zeros((15 * Cn, 15 * Cn))
+    _l.check(_l.lib().tscm_view_gain_apply(*head, device, C.byref(ld), C.byref(tr), nv.ctypes.data_as(C.POINTER(C.c_int)), C.byref(fl), _l.dptr(out)))
+    del keep
+    return dict(gain_logdet=ld.value, gain_trace=tr.value, n_visible=nv, flags=fl.value, cam_cov=out.reshape(Cn, 15, Cn, 15),
+                seconds_kernel=float(_l.lib().tscm_view_gain_seconds()))
+
+
+def _rotation_matrix(w) -> np.ndarray:
+    w = np.asarray(w, dtype=np.float64)
+    th = float(np.sqrt(w @ w))
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    if th * th <= np.finfo(np.float64).eps:
+        return np.eye(3) + K
+    K = K / th
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
+
+
+def _angle_axis(R) -> np.ndarray:
+    """The angle-axis vector of a rotation matrix (angle in [0, pi])."""
+    R = np.asarray(R, dtype=np.float64)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = 0.5 * float(np.sqrt(v @ v)), 0.5 * (np.trace(R) - 1.0)
+    th = float(np.arctan2(s, c))
+    if s > 1e-8:
+        return v * (th / (2.0 * s))
+    if c > 0:
+        return 0.5 * v
+    S = 0.5 * (R + np.eye(3))                                   # angle pi: R = 2 k k^T - I
+    k = np.sqrt(np.maximum(np.diag(S), 0.0))
+    i = int(np.argmax(k))
+    k = np.where(S[i] < 0, -k, k)
+    k[i] = abs(k[i])
+    return th * k / np.sqrt(k @ k)
+
+
+def board_pose_facing(cam_rt_m, ray, distance: float, board_xy, tilt_x_deg: float = 0.0, tilt_y_deg: float = 0.0, roll_deg: float = 0.0) -> np.ndarray:
+    """board_rt [6] in the rig frame of a board whose centre (the mean of board_xy) lies at `distance` along the camera-frame
+    direction `ray` of the camera with pose cam_rt_m, its normal along the ray (it faces the camera), its x axis the
+    camera's x axis made orthogonal to the ray; then turned about its own x, y (tilts) and z (roll) axes through the centre."""
+    z = np.asarray(ray, dtype=np.float64)
+    z = z / np.sqrt(z @ z)
+    ex = np.array([1.0, 0.0, 0.0]) if abs(z[0]) < 0.9 else np.array([0.0, 1.0, 0.0])
+    x = ex - (ex @ z) * z
+    x = x / np.sqrt(x @ x)
+    Rcb = np.stack([x, np.cross(z, x), z], axis=1)
+    tx, ty, rz = np.deg2rad([tilt_x_deg, tilt_y_deg, roll_deg])
+    Rcb = Rcb @ _rotation_matrix([tx, 0, 0]) @ _rotation_matrix([0, ty, 0]) @ _rotation_matrix([0, 0, rz])
+    centre = np.append(np.asarray(board_xy, dtype=np.float64).mean(axis=0), 0.0)
+    tcb = float(distance) * z - Rcb @ centre
+    rt = np.asarray(cam_rt_m, dtype=np.float64)
+    Rm = _rotation_matrix(rt[:3])
+    return np.concatenate([_angle_axis(Rm.T @ Rcb), Rm.T @ (tcb - rt[3:])])
+
+
+def _unit_rays(intr_m, px) -> np.ndarray:
+    """get_unit_sphere_coordinate with b = c = 0 on pixels px [P,2] in float64 numpy: rays [P,3], NaN where a pixel does not unproject."""
+    fx, fy, cx, cy, xi, lam, al = (float(x) for x in np.asarray(intr_m, dtype=np.float64)[:7])
+    mx, my = (px[:, 0] - cx) / fx, (px[:, 1] - cy) / fy
+    ks = al / (1 - al)
+    r2 = mx * mx + my * my
+    with np.errstate(invalid="ignore"):
+        gamma = (ks + np.sqrt(1 + (1 - ks * ks) * r2)) / (r2 + 1)
+        gk = gamma - ks
+        yita = lam * gk + np.sqrt((gk * gk - 1) * lam * lam + 1)
+        ml = yita * gk - lam
+        mu = xi * ml + np.sqrt(xi * xi * (ml * ml - 1) + 1)
+    return np.stack([mu * yita * gamma * mx, mu * yita * gamma * my, mu * ml - xi], axis=1)
+
+
+def view_candidates(cam_rt, intr, camera: int, image_size, board_xy, grid=(6, 4), distances=(400.0, 800.0), tilts_deg=(0.0, 25.0, -25.0), rolls_deg=(0.0,),
+                    pair=None):
+    """A deterministic candidate set for view_gain: the board centre on the ray of each pixel of a grid[0] x grid[1] grid of
+    camera `camera`'s image (cell centres) at each distance, facing the camera, then tilted about its x axis and about its y
+    axis by each non-zero tilt and rolled (board_pose_facing).  pair: the second camera of every candidate (None: the camera
+    alone).  -> (candidates, info): (camera_a, camera_b, board_rt) triples and per candidate dict(camera, pixel, distance,
+    tilt_x, tilt_y, roll).  Pixels that do not unproject are left out."""
+    rt, I = np.asarray(cam_rt, dtype=np.float64), np.asarray(intr, dtype=np.float64)
+    w, h = (int(x) for x in np.asarray(image_size).reshape(-1, 2)[camera if np.asarray(image_size).size > 2 else 0])
+    gx, gy = int(grid[0]), int(grid[1])
+    px = np.array([[(i + 0.5) * w / gx - 0.5, (j + 0.5) * h / gy - 0.5] for j in range(gy) for i in range(gx)])
+    rays = _unit_rays(I[camera], px)
+    tilts = [(0.0, 0.0)] + [(t, 0.0) for t in tilts_deg if t != 0] + [(0.0, t) for t in tilts_deg if t != 0]
+    b = camera if pair is None else int(pair)
+    cands, info = [], []
+    for q, ray in zip(px, rays):
+        if not np.all(np.isfinite(ray)):
+            continue
+        for d in distances:
+            for tx, ty in tilts:
+                for roll in rolls_deg:
+                    cands.append((int(camera), b, board_pose_facing(rt[camera], ray, d, board_xy, tx, ty, roll)))
+                    info.append(dict(camera=int(camera), pixel=(float(q[0]), float(q[1])), distance=float(d), tilt_x=float(tx), tilt_y=float(ty), roll=float(roll)))
+    return cands, info
+
+
+def plan_views(cam_rt, intr, cov, board_xy, image_size, candidates, n_views: int = 5, criterion: str = "gain_logdet", weights=None, border: float = 0.0,
+               min_corners: int = 8, device: int = 0) -> list:
+    """Greedy next-best views: score every candidate (view_gain), take the first arg-max of `criterion` (gain_logdet or
+    gain_trace), apply it (view_gain_apply) and repeat on the covariance it leaves, n_views times.  -> a list of dict(index,
+    candidate, gain_logdet, gain_trace, n_visible, flags, scores (the step's view_gain), cam_cov (after the step)).  Stops early
+    when no candidate has a positive, finite score."""
+    if criterion not in ("gain_logdet", "gain_trace"):
+        raise ValueError("criterion: gain_logdet or gain_trace")
+    cc = np.array(cov["cam_cov"] if isinstance(cov, dict) else cov, dtype=np.float64)
+    kw = dict(weights=weights, border=border, min_corners=min_corners, device=device)
+    steps = []
+    for _ in range(int(n_views)):
+        scores = view_gain(cam_rt, intr, cc, board_xy, image_size, candidates, **kw)
+        s = np.where((scores["flags"] & 4) != 0, scores[criterion], -np.inf)
+        best = int(np.argmax(s))
+        if not s[best] > 0:
+            break
+        ap = view_gain_apply(cam_rt, intr, cc, board_xy, image_size, candidates[best], **kw)
+        cc = ap["cam_cov"]
+        steps.append(dict(index=best, candidate=candidates[best], gain_logdet=ap["gain_logdet"], gain_trace=ap["gain_trace"], n_visible=ap["n_visible"],
+                          flags=ap["flags"], scores=scores, cam_cov=cc))
+    return steps

@@ -195,6 +195,16 @@ class CUncertaintyRequest(C.Structure):
     _fields_ = [("camera_a", C.c_int), ("camera_b", C.c_int), ("inv_distance", C.c_double)]
 
 
+class CViewGainParams(C.Structure):
+    """tscm_view_gain_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("min_corners", C.c_int), ("border", C.c_double)]
+
+
+class CViewCandidate(C.Structure):
+    """tscm_view_candidate (tscm.h)"""
+    _fields_ = [("camera_a", C.c_int), ("camera_b", C.c_int), ("board_rt", C.c_double * 6)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -223,6 +233,7 @@ EXPORTS = [
     "tscm_solve_mono_batch_weighted", "tscm_covariance_weighted",
     "tscm_solver_set_camera_priors", "tscm_solve_prior", "tscm_eval_normal_equations_prior", "tscm_eval_step_prior", "tscm_covariance_prior",
     "tscm_projection_uncertainty", "tscm_projection_uncertainty_seconds",
+    "tscm_view_gain", "tscm_view_gain_apply", "tscm_view_gain_seconds",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
@@ -328,6 +339,11 @@ def lib():
                                               dp, C.POINTER(C.c_ubyte), dp, C.POINTER(C.c_longlong)]
     L.tscm_projection_uncertainty_seconds.argtypes = []
     L.tscm_projection_uncertainty_seconds.restype = C.c_double
+    vg = [C.c_int, dp, dp, dp, dp, C.c_int, dp, ip, C.POINTER(CViewGainParams), C.POINTER(CViewCandidate)]
+    L.tscm_view_gain.argtypes = vg + [C.c_int, C.c_int, dp, dp, ip, ip]
+    L.tscm_view_gain_apply.argtypes = vg + [C.c_int, dp, dp, ip, ip, dp]
+    L.tscm_view_gain_seconds.argtypes = []
+    L.tscm_view_gain_seconds.restype = C.c_double
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]

@@ -236,7 +236,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None, suggest=None) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -258,7 +258,10 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     -- and above all its component across the epipolar line -- is uncertain (uncertainty_requests lists them).
     priors: None, or dict(intr_sigma=..., cam_rt_sigma=...[, pixel_sigma=...]) as for api.camera_priors: Gaussian priors of every
     mono refinement (intrinsics), of the joint solve about the values it starts from -- the mono intrinsics and rig_init's poses --
-    and, about those same values, of the covariance.  Not with batch_mono (the batched route has no priors): ValueError."""
+    and, about those same values, of the covariance.  Not with batch_mono (the batched route has no priors): ValueError.
+    suggest: None, or dict(n_views=5[, grid, distances, tilts_deg, rolls_deg, pairs, criterion, border, min_corners]) -- implies
+    covariance and adds result["suggested_views"] = suggest_views(...): where to hold the board next, by the covariance each
+    pose would remove (api.plan_views on the candidates of every camera and of every adjacent pair)."""
     if priors is not None and batch_mono:
         raise ValueError("batch_mono=True has no priors: the batched mono route does not take them")
     n_cam = len(images_by_camera)
@@ -287,7 +290,7 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
         out["priors"] = pk["priors"]
     if cw is not None:
         out["corner_mask"] = cw
-    if covariance or uncertainty is not None:
+    if covariance or uncertainty is not None or suggest is not None:
         if cw is not None:
             out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw, **pk)
         else:
@@ -298,7 +301,34 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
         grid = api.uncertainty_grid(int((img_w - 1) // step) + 1, int((img_h - 1) // step) + 1, 0.0, 0.0, step, step, img_w, img_h)
         out["uncertainty"] = api.projection_uncertainty(problem.cam_rt, problem.intr, out["covariance"], uncertainty_requests(n_cam, uncertainty["inv_distances"]),
                                                         grid, device)
+    if suggest is not None:
+        img_w, img_h = images_by_camera[0][0].shape[1], images_by_camera[0][0].shape[0]
+        out["suggested_views"] = suggest_views(problem, out["covariance"], (img_w, img_h), device=device, **suggest)
     return out
+
+
+def suggest_views(problem: Problem, cov: dict, image_size, n_views: int = 5, grid=(6, 4), distances=None, tilts_deg=(0.0, 25.0, -25.0), rolls_deg=(0.0,),
+                  pairs=True, criterion: str = "gain_logdet", border: float = 0.0, min_corners: int = 8, device: int = 0) -> list:
+    """Greedy next-best views of a calibrated rig (api.plan_views): the candidates are api.view_candidates of every camera
+    alone and, with pairs, of every camera together with the next one (for three and more cameras also the last with the
+    first).  distances: None takes 5 and 10 board diagonals.  -> a list of dict(camera_a, camera_b, board_rt, pixel, distance,
+    tilt_x, tilt_y, roll, gain_logdet, gain_trace, n_visible, flags), one per chosen view, in the order they were chosen."""
+    xy = np.asarray(problem.board_xy, dtype=np.float64)
+    if distances is None:
+        diag = float(np.sqrt(np.sum((xy.max(axis=0) - xy.min(axis=0)) ** 2)))
+        distances = (5.0 * diag, 10.0 * diag)
+    C = problem.n_cameras
+    cands, info = [], []
+    for m in range(C):
+        partners = [None] + ([(m + 1) % C] if pairs and C > 1 and (m + 1 < C or C > 2) else [])
+        for b in partners:
+            c, i = api.view_candidates(problem.cam_rt, problem.intr, m, image_size, xy, grid, distances, tilts_deg, rolls_deg, pair=b)
+            cands += c
+            info += i
+    steps = api.plan_views(problem.cam_rt, problem.intr, cov, xy, image_size, cands, n_views=n_views, criterion=criterion, border=border,
+                           min_corners=min_corners, device=device)
+    return [dict(info[s["index"]], camera_a=s["candidate"][0], camera_b=s["candidate"][1], board_rt=s["candidate"][2], gain_logdet=s["gain_logdet"],
+                 gain_trace=s["gain_trace"], n_visible=s["n_visible"], flags=s["flags"]) for s in steps]
 
 
 def rig_corner_mask(problem: Problem, mono) -> np.ndarray:
