@@ -7,6 +7,7 @@
 //                                   [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]]
 //                                   [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance]
 //                                   [--uncertainty STEP[,INV_DISTANCE]] [--suggest N[,DISTANCE...]]
+//                                   [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]]
 //   (--loss: Ceres' HuberLoss / SoftLOneLoss / CauchyLoss(px) on every corner of every solve; the reference passes NULL.
 //    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
@@ -28,7 +29,13 @@
 //    rectified rows stop being rows
 //    --suggest (rigs; implies --covariance): where to hold the board next -- N poses chosen greedily by the covariance each
 //    would remove (MultiCalib::suggest_views; default distances: 5 and 10 board diagonals), printed behind the covariance
-//    report: `suggest k camera_a[+camera_b] pixel u v distance d tilt x y gain_logdet g gain_trace t visible n[,n]`)
+//    report: `suggest k camera_a[+camera_b] pixel u v distance d tilt x y gain_logdet g gain_trace t visible n[,n]`
+//    --residuals (rigs): after the joint solve, the residual report (MultiCalib::residual_report) to FILE or standard output:
+//    one line per view, `view v camera m board b corners n rms r max x worst j`; --residual-bins K adds per camera the mean radial
+//    and tangential residual over K bins of the incidence angle, 0 .. pi -- what tells a wrong model from a noisy one
+//    --prune (rigs): ROUNDS times (default 1): the views whose rms exceeds their camera's median + K * 1.4826 * MAD leave the
+//    problem (MultiCalib::prune_views, at most MAX_FRACTION of a camera's views, default 0.2) and the joint solve runs again;
+//    the YAML, the covariance and the report are those of the last solve)
 #include <tscm/tscm_calib.hpp>
 
 #include <algorithm>
@@ -48,6 +55,7 @@ int main(int argc, char **argv)
     double unc_step = 0.0, unc_inv_distance = 0.0;
     int suggest = 0;
     std::vector<double> suggest_distances;
+    tscm::ResidualOptions residual;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
     for (int i = 3; i < argc && !bad_args; ++i) {
@@ -98,13 +106,14 @@ int main(int argc, char **argv)
             bad_args = bad_args || *end != '\0';
             covariance = true;
         } else {
-            bad_args = true;
+            bad_args = tscm::parse_residual_option(argc, argv, i, residual) != 1;
         }
     }
     bad_args = bad_args || (ransac_mask && !use_ransac);
     if (bad_args) {
         std::fprintf(stderr, "usage: %s corners.txt calib.yaml [--loss huber|soft_l1|cauchy --loss-scale <px>] [--model ts|ds|ucm] "
-                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]] [--suggest N[,DISTANCE...]]\n", argv[0]);
+                     "[--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--covariance] [--uncertainty STEP[,INV_DISTANCE]] [--suggest N[,DISTANCE...]] "
+                     "[--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -158,6 +167,7 @@ int main(int argc, char **argv)
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             for (int m = 0; m < C; ++m) std::printf("camera_%d reprojection error: %.6f\n", m, mul_calib.camera_error[m]);
             std::printf("average reproject error: %.6f\n", mul_calib.mean_error);
+            tscm::run_residual_options(mul_calib, residual);
             mul_calib.write_yaml(argv[2]);                                   // main.cpp:305-319
             if (covariance) {
                 const tscm::MultiCalib::Covariance cov = mul_calib.covariance();

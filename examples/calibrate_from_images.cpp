@@ -5,6 +5,7 @@
 // for a frame the camera has no image of.  The viewer and the drawing calls of main.cpp are left out.
 //   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
 //                                [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]
+//                                [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]]
 //   (--model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
 //    --prior: Gaussian priors (Ceres' NormalPrior, tscm.h) on the named intrinsics of every camera, in every solve, about the
@@ -13,7 +14,9 @@
 //    --ransac-mask (with --ransac): the inlier masks are the corner masks of every refinement and of the joint solve; prints the
 //                  number of corners masked per camera
 //    --ransac: the start poses of both calibrate() calls come from tscm_estimate_extrinsic_ransac at THRESHOLD pixels; a view
-//    without consensus leaves the calibration, and per camera the views kept and the share of inlier corners are printed)
+//    without consensus leaves the calibration, and per camera the views kept and the share of inlier corners are printed
+//    --residuals, --residual-bins, --prune (rigs): the residual report and outlier-view pruning behind the joint solve, as
+//    calibrate_from_corners has them)
 #include <tscm/tscm_calib.hpp>
 
 #include <cstdio>
@@ -107,7 +110,10 @@ int main(int argc, char **argv)
     bool bad_args = false, use_ransac = false, ransac_mask = false;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
+    tscm::ResidualOptions residual;
     for (int i = 1; i < argc && !bad_args; ++i) {
+        const int taken = tscm::parse_residual_option(argc, argv, i, residual);
+        if (taken != 0) { bad_args = taken < 0; continue; }
         if (!std::strcmp(argv[i], "--model") && i + 1 < argc) {
             bad_args = !tscm::model_mask(argv[++i], model);
         } else if (!std::strcmp(argv[i], "--fix") && i + 1 < argc) {
@@ -130,7 +136,7 @@ int main(int argc, char **argv)
     }
     if (bad_args || pos.size() < 2 || (ransac_mask && !use_ransac)) {
         std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] "
-                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]\n", argv[0]);
+                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -179,6 +185,7 @@ int main(int argc, char **argv)
             mul_calib.calibrate();                                             // main.cpp:234
             std::printf("%s  iterations %d  rmse %.4f px\n", mul_calib.summary.message, mul_calib.summary.num_iterations - 1, mul_calib.summary.rmse);
             std::printf("average reproject error: %.6f\n", mul_calib.mean_error);
+            tscm::run_residual_options(mul_calib, residual);
             mul_calib.write_yaml(pos[1]);                                     // main.cpp:305-319
         } else if (cameras.size() == 1) {
             const double I3[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t0[3] = { 0, 0, 0 };

@@ -724,6 +724,91 @@ int tscm_view_gain_apply(int n_cameras, const double *cam_rt, const double *intr
  * uploads and read-back are outside); 0 after a call that was refused or failed */
 double tscm_view_gain_seconds(void);
 
+/* ------------------------------------------------------------------ residual report
+ * Which views and corners of a calibration are bad, and does the model fit the lens: every corner's residual at the
+ * problem's parameters, statistics per view and per camera, and optional field statistics per camera (an image grid and
+ * bins over the incidence angle).  A stage of its own: no kernel of the LM iteration runs.
+ *
+ * Corner order is the order of the corner weights: views in problem order, the corners of a view in order; N = sum of
+ * view_count.  The residual is the functor form's (no skew terms, both branches of AngleAxisRotatePoint), from the device
+ * function tscm_eval_functor evaluates.
+ * Per corner i of view (camera m, board b), with omega_i its weight (weights == NULL: 1):
+ *   r = observed - projected,  s = r_u^2 + r_v^2,  p = observed - r the projected pixel,  c = (cx, cy) of camera m
+ *   e = (p - c) / |p - c|, or (1, 0) where |p - c| = 0;   r_rad = r . e;   r_tan = e_x r_v - e_y r_u
+ *   angle = atan2(sqrt(X^2 + Y^2), Z) of the camera-frame point (X, Y, Z)
+ *   rho1 = rho'(s) of the loss, clamped as the solver clamps it; 1 for TSCM_LOSS_NONE
+ * A corner with omega_i = 0: its observation may hold anything, NaN included, and is read as (0, 0) as at solver upload;
+ * all six of its outputs are exactly 0 and it takes part in no statistic.
+ * Per view, over its corners with omega > 0 (a view without one: zeros and worst = -1):
+ *   n_used, sum_w = sum omega, rms = sqrt(sum omega s / sum_w), mean_err = sum omega |r| / sum_w, max_err = max |r|,
+ *   worst = index within the view of max_err (lowest on ties), bias_u, bias_v, mean_rad = weighted means of r_u, r_v, r_rad.
+ * Per camera, the same formulas over all its used corners: n_used, sum_w, rms, mean_err, max_err, worst_view (the view of
+ * max_err, lowest on ties, -1 without a used corner), n_views_used.
+ * Per call (info): cost = sum omega rho(s) / 2, rmse = sqrt(sum omega s / sum omega), the used corners and views.
+ *
+ * Field statistics, per camera, over the corners with omega > 0 ("weights only gate": every such corner counts once).  A
+ * corner with max(|r_u|, |r_v|) > clamp (pixels, in (0, 64]) is counted in n_clamped of its cell / bin and in no sum.
+ *   Image grid (grid_w > 0): grid_w x grid_h cells over image_width x image_height.  A corner goes to the cell of its
+ *   OBSERVED pixel, ix = floor(obs_u * grid_w / image_width), iy likewise -- a function of the inputs alone; outside the
+ *   image it is counted in info->grid_outside[camera].  Per cell: count, n_clamped, and mean_u, mean_v, rms.
+ *   Angle bins (n_angle_bins > 0): uniform over [0, max_angle], bin = floor(angle * n_angle_bins / max_angle), the angle
+ *   max_angle itself in the last bin; a larger angle is counted in info->angle_outside[camera].  Per bin: count, n_clamped,
+ *   and mean_rad, mean_tan, rms, mean_angle.
+ * Field accumulation is exact: every addend is llrint(x * 2^24), summed in 64-bit integers; a mean is (double)sum * 2^-24 /
+ * count and rms the square root of that for s.  |r_u|, |r_v| <= 64 gives s <= 2^13 = 2^37 quanta, so 2^26 used corners of
+ * one camera cannot overflow; a camera with more and a field requested is refused with TSCM_E_UNSUPPORTED.
+ * Two calls on the same input give the same bytes in every output: no floating-point atomics, a view's sums by a fixed lane
+ * assignment and butterfly, a camera's sums over its views in problem order by a fixed tree, the field in integers.  A
+ * view's rows do not depend on its place in the problem.
+ *
+ * Refused with TSCM_E_INVALID before any device is touched, the text naming the argument: a NULL problem, params or info;
+ * a struct_size other than the struct's sizeof; an unknown loss kind, or a scale that is not finite and > 0; grid_w or
+ * grid_h outside 0..64 or only one of them 0; a non-positive image size with a grid; n_angle_bins outside 0..64; max_angle
+ * not in (0, pi] with bins; clamp not in (0, 64]; a field requested without its two output arrays; a problem tscm_solver_create
+ * refuses; weights that are negative, NaN or infinite.  Unlike a solve, a view whose weights are all 0 is accepted: it is
+ * unused.  device_index as elsewhere, TSCM_E_NO_DEVICE after the argument checks. */
+typedef struct tscm_residual_params {
+    int struct_size;               /* sizeof(tscm_residual_params), set by tscm_residual_default_params                */
+    int loss_kind;                 /* TSCM_LOSS_*; default TSCM_LOSS_NONE                                              */
+    double loss_scale;             /* pixels                                                                           */
+    int grid_w, grid_h;            /* 1..64 each, or both 0: no image grid (default)                                   */
+    int image_width, image_height; /* pixels; > 0 with a grid                                                          */
+    int n_angle_bins;              /* 1..64, or 0: no angle bins (default)                                             */
+    int pad;
+    double max_angle;              /* radians, in (0, pi]; default pi / 2                                              */
+    double clamp;                  /* pixels, in (0, 64]; default 64                                                   */
+} tscm_residual_params;
+
+typedef struct tscm_residual_info {
+    int struct_size;               /* sizeof(tscm_residual_info), set by the caller                                    */
+    int n_views_used;              /* views with a used corner                                                         */
+    long long n_used;              /* corners with omega > 0                                                           */
+    double sum_w;
+    double cost;                   /* sum omega rho(s) / 2                                                             */
+    double rmse;                   /* sqrt(sum omega s / sum omega); 0 without a used corner                           */
+    long long grid_outside[32];    /* per camera: used corners observed outside the image (grid requested)             */
+    long long angle_outside[32];   /* per camera: used corners with angle > max_angle (bins requested)                 */
+    double seconds_kernel[4];      /* device seconds: views, cameras, field accumulation, field means                  */
+} tscm_residual_info;
+
+void tscm_residual_default_params(tscm_residual_params *params);
+
+/* Every output may be NULL; grid_count and grid are required with a grid, angle_count and angle with bins.  Host pointers.
+ *   corner      [N][6]  r_u r_v r_rad r_tan angle rho1
+ *   view        [V][8]  n_used sum_w rms mean_err max_err bias_u bias_v mean_rad
+ *   view_worst  [V]
+ *   camera      [C][8]  n_used sum_w rms mean_err max_err worst_view n_views_used 0
+ *   grid_count  [C][grid_h][grid_w][2]  count n_clamped      grid  [C][grid_h][grid_w][3]  mean_u mean_v rms
+ *   angle_count [C][K][2]               count n_clamped      angle [C][K][4]  mean_rad mean_tan rms mean_angle */
+int tscm_residual_report(const tscm_problem *problem, int device_index, const double *weights,
+                         const tscm_residual_params *params, double *corner, double *view, int *view_worst, double *camera,
+                         long long *grid_count, double *grid, long long *angle_count, double *angle,
+                         tscm_residual_info *info);
+
+/* Tests only: the corner count at which the field kernel's chunk lists are cut for this thread's next calls (0: the
+ * default).  Cutting them differently changes no output byte. */
+void tscm_residual_debug_chunk_target(int corners);
+
 /* ------------------------------------------------------------------ projection family
  * tscm_project_points   = TripleSphereCamera::project (TS.cpp:332-344), skew terms
  *                         included, n camera-frame points [n*3] -> pixels [n*2].

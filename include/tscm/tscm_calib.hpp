@@ -27,6 +27,8 @@
 //   MultiCalib::MultiCalib               multi_calib.cpp:6-153    MultiCalib::MultiCalib       -> tscm_rig_init
 //   MultiCalib::calibrate                multi_calib.cpp:155-283  MultiCalib::calibrate        -> tscm_solve_multi, tscm_reprojection_error
 //   YAML output                          main.cpp:305-319         MultiCalib::write_yaml       -> tscm_yaml_write
+//   (the error report of multi_calib.cpp:233-283 only)     residual_report on both classes, view_outliers,
+//                                                          MultiCalib::prune_views             -> tscm_residual_report
 //   AddResidualBlock(new NormalPrior(A, mean), NULL, x)    CameraPriors, set_camera_priors on both classes, set_prior_sigmas,
 //                                                          parse_prior_option                  -> tscm_solve_prior, tscm_covariance_prior
 //   (cv::solvePnPRansac inside estimate_extrinsic)         TripleSphereCamera::estimate_extrinsic_ransac, set_ransac,
@@ -37,12 +39,14 @@
 
 #include <tscm/tscm.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace tscm {
@@ -171,6 +175,137 @@ inline void print_effective_priors(const CameraPriors &p, size_t cam, int m, uns
 }
 
 // cv::Rodrigues(r -> R), the conversion update_param() does on the host (multi_calib.h:43-45,105-106)
+// ---- residual report (tscm.h: tscm_residual_report) of a problem as the classes below build it
+struct ResidualReport {
+    tscm_residual_info info;
+    int n_cameras, grid_w, grid_h, n_angle_bins;
+    std::vector<int> view_camera, view_board, view_count;      // the views of the problem that was reported on
+    std::vector<double> corner;            // [N][6]  r_u r_v r_rad r_tan angle rho1
+    std::vector<double> view;              // [V][8]  n_used sum_w rms mean_err max_err bias_u bias_v mean_rad
+    std::vector<int> view_worst;           // [V]
+    std::vector<double> camera;            // [C][8]  n_used sum_w rms mean_err max_err worst_view n_views_used 0
+    std::vector<long long> grid_count, angle_count;     // [C][gh][gw][2], [C][K][2]: count, n_clamped
+    std::vector<double> grid, angle;       // [C][gh][gw][3] mean_u mean_v rms, [C][K][4] mean_rad mean_tan rms mean_angle
+};
+
+// params: NULL = the defaults (no loss, no field); weights: [N] in corner order or NULL
+inline ResidualReport residual_report_of(const tscm_problem &P, int device, const double *weights, const tscm_residual_params *params)
+{
+    tscm_residual_params prm;
+    if (params) prm = *params; else tscm_residual_default_params(&prm);
+    ResidualReport r;
+    const size_t C = (size_t)P.n_cameras, V = (size_t)P.n_views;
+    size_t N = 0;
+    for (size_t v = 0; v < V; ++v) N += (size_t)P.view_count[v];
+    r.n_cameras = P.n_cameras; r.grid_w = prm.grid_w; r.grid_h = prm.grid_h; r.n_angle_bins = prm.n_angle_bins;
+    r.view_camera.assign(P.view_camera, P.view_camera + V); r.view_board.assign(P.view_board, P.view_board + V); r.view_count.assign(P.view_count, P.view_count + V);
+    const size_t cells = (size_t)prm.grid_w * prm.grid_h, K = (size_t)prm.n_angle_bins;
+    r.corner.assign(6 * N + 1, 0.0); r.view.assign(8 * V + 1, 0.0); r.view_worst.assign(V + 1, -1); r.camera.assign(8 * C, 0.0);
+    r.grid_count.assign(2 * C * cells + 1, 0); r.grid.assign(3 * C * cells + 1, 0.0); r.angle_count.assign(2 * C * K + 1, 0); r.angle.assign(4 * C * K + 1, 0.0);
+    r.info = tscm_residual_info();
+    r.info.struct_size = (int)sizeof(tscm_residual_info);
+    check(tscm_residual_report(&P, device, weights, &prm, r.corner.data(), r.view.data(), r.view_worst.data(), r.camera.data(), r.grid_count.data(), r.grid.data(),
+                               r.angle_count.data(), r.angle.data(), &r.info));
+    r.corner.resize(6 * N); r.view.resize(8 * V); r.view_worst.resize(V); r.grid_count.resize(2 * C * cells); r.grid.resize(3 * C * cells);
+    r.angle_count.resize(2 * C * K); r.angle.resize(4 * C * K);
+    return r;
+}
+
+// The views of a report whose rms stands out in their camera (api.view_outliers, the same rule and the same arithmetic): per
+// camera, over its views with n_used > 0, view v is flagged when rms_v > median + k * 1.4826 * MAD of those rms values and
+// rms_v > floor; at most floor(max_fraction * those views) per camera, the worst first, ties to the lower view.
+inline std::vector<bool> view_outliers(const ResidualReport &r, double k = 3.0, double floor = 0.0, double max_fraction = 0.2)
+{
+    const size_t V = r.view_camera.size();
+    std::vector<bool> out(V, false);
+    auto median = [](std::vector<double> x) {
+        std::sort(x.begin(), x.end());
+        const size_t n = x.size();
+        return n % 2 ? x[n / 2] : (x[n / 2 - 1] + x[n / 2]) / 2.0;
+    };
+    for (int m = 0; m < r.n_cameras; ++m) {
+        std::vector<size_t> views;
+        std::vector<double> x;
+        for (size_t v = 0; v < V; ++v)
+            if (r.view_camera[v] == m && r.view[8 * v] > 0.0) { views.push_back(v); x.push_back(r.view[8 * v + 2]); }
+        if (views.empty()) continue;
+        const double med = median(x);
+        std::vector<double> dev(x.size());
+        for (size_t i = 0; i < x.size(); ++i) dev[i] = std::fabs(x[i] - med);
+        const double limit = med + k * 1.4826 * median(dev);
+        std::vector<size_t> hit;
+        for (size_t i = 0; i < x.size(); ++i)
+            if (x[i] > limit && x[i] > floor) hit.push_back(views[i]);
+        std::stable_sort(hit.begin(), hit.end(), [&r](size_t a, size_t b) { return r.view[8 * a + 2] > r.view[8 * b + 2]; });   // hit ascends: ties keep the lower view first
+        const size_t cap = (size_t)std::floor(max_fraction * (double)views.size());
+        for (size_t i = 0; i < hit.size() && i < cap; ++i) out[hit[i]] = true;
+    }
+    return out;
+}
+
+// the residual options of the calibrate_from_* programs: --residuals[=FILE], --residual-bins K, --prune K[,ROUNDS[,MAX_FRACTION]]
+struct ResidualOptions {
+    bool report = false;
+    std::string file;                      // empty: standard output
+    int bins = 0;
+    bool prune = false;
+    double k = 3.0, max_fraction = 0.2;
+    int rounds = 1;
+};
+// argv[i] as one of those options (argv[i + 1] consumed where the option takes a value): 1 taken, 0 not one of them, -1 malformed
+inline int parse_residual_option(int argc, char **argv, int &i, ResidualOptions &o)
+{
+    const char *a = argv[i];
+    if (!std::strcmp(a, "--residuals")) { o.report = true; return 1; }
+    if (!std::strncmp(a, "--residuals=", 12)) { o.report = true; o.file = a + 12; return o.file.empty() ? -1 : 1; }
+    if (!std::strcmp(a, "--residual-bins")) {
+        if (i + 1 >= argc) return -1;
+        char *end = nullptr;
+        const long n = std::strtol(argv[++i], &end, 10);
+        if (end == argv[i] || *end != '\0' || n < 1 || n > 64) return -1;
+        o.bins = (int)n; o.report = true;
+        return 1;
+    }
+    if (!std::strcmp(a, "--prune")) {
+        if (i + 1 >= argc) return -1;
+        char *end = nullptr;
+        const char *at = argv[++i];
+        o.k = std::strtod(at, &end);
+        if (end == at || !(o.k >= 0.0) || !std::isfinite(o.k)) return -1;
+        if (*end == ',') {
+            at = end + 1;
+            const long r = std::strtol(at, &end, 10);
+            if (end == at || r < 1 || r > 100) return -1;
+            o.rounds = (int)r;
+            if (*end == ',') {
+                at = end + 1;
+                o.max_fraction = std::strtod(at, &end);
+                if (end == at || !(o.max_fraction >= 0.0) || !(o.max_fraction <= 1.0)) return -1;
+            }
+        }
+        if (*end != '\0') return -1;
+        o.prune = true;
+        return 1;
+    }
+    return 0;
+}
+
+// the per-view table -- `view camera board corners_used rms max worst_corner` -- and, with angle bins, per camera the profile
+// `camera_m angle lo hi count clamped mean_rad mean_tan rms` (radians; pixels)
+inline void print_residual_report(std::FILE *f, const ResidualReport &r, double max_angle)
+{
+    std::fprintf(f, "residuals: %lld corners in %d views, rmse %.6f px\n", r.info.n_used, r.info.n_views_used, r.info.rmse);
+    for (size_t v = 0; v < r.view_camera.size(); ++v)
+        std::fprintf(f, "view %zu camera %d board %d corners %d rms %.6f max %.6f worst %d\n", v, r.view_camera[v], r.view_board[v], (int)r.view[8 * v],
+                     r.view[8 * v + 2], r.view[8 * v + 4], r.view_worst[v]);
+    for (int m = 0; m < r.n_cameras; ++m)
+        for (int k = 0; k < r.n_angle_bins; ++k) {
+            const size_t o = (size_t)m * r.n_angle_bins + k;
+            std::fprintf(f, "camera_%d angle %.4f %.4f count %lld clamped %lld mean_rad %.6f mean_tan %.6f rms %.6f\n", m, max_angle * k / r.n_angle_bins,
+                         max_angle * (k + 1) / r.n_angle_bins, r.angle_count[2 * o], r.angle_count[2 * o + 1], r.angle[4 * o], r.angle[4 * o + 1], r.angle[4 * o + 2]);
+        }
+}
+
 inline Mat33 rodrigues(const double r[3])
 {
     const double th2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2], th = std::sqrt(th2);
@@ -272,6 +407,33 @@ public:
         check(tscm_solve_prior(&P, &o, weighted ? w.data() : NULL, fixed_ ? &fixed_ : NULL, loss_kind_, loss_scale_, use_priors_ || use_sigmas_ ? &cp : NULL, &summary));
         for (int i = 0; i < V; ++i) if (has_chessboard_[i]) rt_[i].assign(&rt[6 * (size_t)i], &rt[6 * (size_t)i] + 6);
         return summary.termination_type == TSCM_CONVERGENCE;             // TS.cpp:281
+    }
+
+    // Residual report (tscm_residual_report) of the problem refinement() solves, at the object's current intrinsic_ and rt_:
+    // every view with a chessboard, in order; with corner weights (or RANSAC masks) a view whose weights are all 0 stays in as an
+    // unused view.  The loss is the one set on this object unless params carries one.  params: NULL = defaults.
+    ResidualReport residual_report(const std::vector<std::vector<Point2d> > &pixels, const std::vector<Point3d> &worlds,
+                                   const tscm_residual_params *params = nullptr) const
+    {
+        const int V = (int)pixels.size(), n = (int)worlds.size();
+        std::vector<double> bxy(2 * (size_t)n), u, v, w, rt(6 * (size_t)V, 0.0), I(intrinsic_);
+        std::vector<int> vc, vb, vo, vn;
+        bool weighted = false;
+        for (int j = 0; j < n; ++j) { bxy[2 * j] = worlds[j].x; bxy[2 * j + 1] = worlds[j].y; }
+        for (int i = 0; i < V; ++i) {
+            if (!has_chessboard_[i]) continue;
+            std::memcpy(&rt[6 * (size_t)i], rt_[i].data(), 6 * sizeof(double));
+            for (size_t j = 0; j < pixels[i].size(); ++j) w.push_back(corner_weight((size_t)i, j, &weighted));
+            vc.push_back(0); vb.push_back(i); vo.push_back((int)u.size()); vn.push_back((int)pixels[i].size());
+            for (const Point2d &p : pixels[i]) { u.push_back(p.x); v.push_back(p.y); }
+        }
+        tscm_problem P = tscm_problem();
+        P.n_cameras = 1; P.n_boards = V; P.n_points = n; P.n_views = (int)vc.size();
+        P.board_xy = bxy.data(); P.view_camera = vc.data(); P.view_board = vb.data(); P.view_offset = vo.data(); P.view_count = vn.data();
+        P.obs_u = u.data(); P.obs_v = v.data(); P.intr = I.data(); P.board_rt = rt.data(); P.mono = 1;
+        tscm_residual_params prm;
+        if (params) prm = *params; else { tscm_residual_default_params(&prm); prm.loss_kind = loss_kind_; prm.loss_scale = loss_scale_; }
+        return residual_report_of(P, device_, weighted ? w.data() : nullptr, &prm);
     }
 
     // refinement() of several cameras in ONE batch (tscm_solve_mono_batch): cams[k] is refined on pixels[k], all against the
@@ -842,6 +1004,45 @@ public:
         return out;
     }
 
+    // Residual report (tscm_residual_report) of the joint problem at the objects' current parameters, with the weights set on
+    // this object (a view whose weights are all 0 is not part of the joint problem) and, unless params carries one, its loss:
+    // call it after calibrate().  The report's view_camera / view_board name each view.  params: NULL = defaults.
+    ResidualReport residual_report(const tscm_residual_params *params = nullptr) const
+    {
+        JointProblem q;
+        joint_problem(q);
+        tscm_residual_params prm;
+        if (params) prm = *params; else { tscm_residual_default_params(&prm); prm.loss_kind = loss_kind_; prm.loss_scale = loss_scale_; }
+        return residual_report_of(q.P, device_, use_weights_ ? q.w.data() : nullptr, &prm);
+    }
+    // Outlier-view pruning (pipeline.prune_solve's flagging step): residual_report(), view_outliers(k, floor, max_fraction), and
+    // every corner weight of the flagged views set to 0 (weights of 1 are created if none were set), so that the next calibrate()
+    // and covariance() leave those views out.  Returns the flagged (camera, board) pairs, in view order.  No rig-connectivity
+    // logic: a pruned rig that falls apart shows in covariance().info.min_pivot_ratio.
+    std::vector<std::pair<int, int> > prune_views(double k = 3.0, double floor = 0.0, double max_fraction = 0.2)
+    {
+        const ResidualReport rep = residual_report();
+        const std::vector<bool> flags = view_outliers(rep, k, floor, max_fraction);
+        std::vector<std::pair<int, int> > out;
+        for (size_t v = 0; v < flags.size(); ++v)
+            if (flags[v]) out.push_back(std::make_pair(rep.view_camera[v], rep.view_board[v]));
+        if (out.empty()) return out;
+        if (!use_weights_) {
+            corner_weights_.assign(cameras_.size(), std::vector<std::vector<double> >());
+            for (size_t m = 0; m < cameras_.size(); ++m) {
+                corner_weights_[m].resize(cameras_[m].pixel_coordinates_.size());
+                for (size_t i = 0; i < corner_weights_[m].size(); ++i) corner_weights_[m][i].assign(cameras_[m].pixel_coordinates_[i].size(), 1.0);
+            }
+            use_weights_ = true;
+        }
+        for (const std::pair<int, int> &mb : out) {
+            std::vector<std::vector<double> > &cam = corner_weights_[(size_t)mb.first];
+            if (cam.size() <= (size_t)mb.second) cam.resize((size_t)mb.second + 1);
+            cam[(size_t)mb.second].assign(cameras_[(size_t)mb.first].pixel_coordinates_[(size_t)mb.second].size(), 0.0);
+        }
+        return out;
+    }
+
     // Projection uncertainty maps (tscm_projection_uncertainty) at the objects' current parameters under the covariance that
     // covariance() returned: per request (camera_a, camera_b, inv_distance) the covariance of a grid pixel of camera a
     // transferred to camera b (a == b: of a fixed rig-frame point in its own camera), in pixels.
@@ -1096,6 +1297,30 @@ private:
 // ---- corner detection: findCorner(img, sigma) (DetectCorner/findCorner.cpp:7-101) -------------------------------------
 // Same result structure as the reference (Corner_t / Chessboarder_t, chessboard = matrices of indices into corners.p),
 // grey 8-bit image instead of cv::Mat.  Board members carry their sub-pixel position (findCorner.cpp:84-97).
+// What the calibrate_from_* programs do with ResidualOptions behind MultiCalib::calibrate(): --prune: `rounds` times
+// prune_views(k, 0, max_fraction), one line per flagged view, and calibrate() again (a round that flags nothing ends the loop);
+// --residuals / --residual-bins: the report of the final state, over [0, pi] with bins, to the file or standard output.
+inline void run_residual_options(MultiCalib &mul, const ResidualOptions &o)
+{
+    for (int round = 0; o.prune && round < o.rounds; ++round) {
+        const std::vector<std::pair<int, int> > out = mul.prune_views(o.k, 0.0, o.max_fraction);
+        if (out.empty()) break;
+        for (const std::pair<int, int> &mb : out) std::printf("prune round %d: camera %d board %d\n", round + 1, mb.first, mb.second);
+        mul.calibrate();
+        std::printf("pruned solve %d: %s  iterations %d  rmse %.4f px\n", round + 1, mul.summary.message, mul.summary.num_iterations - 1, mul.summary.rmse);
+    }
+    if (!o.report) return;
+    tscm_residual_params prm;
+    tscm_residual_default_params(&prm);
+    prm.loss_kind = mul.loss_kind_; prm.loss_scale = mul.loss_scale_;
+    prm.n_angle_bins = o.bins; prm.max_angle = 3.14159265358979323846;
+    const ResidualReport rep = mul.residual_report(&prm);
+    std::FILE *f = o.file.empty() ? stdout : std::fopen(o.file.c_str(), "w");
+    if (!f) throw std::runtime_error("tscm: cannot write " + o.file);
+    print_residual_report(f, rep, prm.max_angle);
+    if (f != stdout) std::fclose(f);
+}
+
 struct Corner_t {
     std::vector<Point2d> p, v1, v2;
     std::vector<double> score;

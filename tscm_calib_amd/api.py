@@ -597,6 +597,115 @@ def covariance_from_normal_equations(view_camera, view_board, board_gram, view_c
     return _covariance_dict(info, Cn, B, cam_cov, board_cov)
 
 
+RESIDUAL_CORNER = ("r_u", "r_v", "r_rad", "r_tan", "angle", "rho1")
+RESIDUAL_VIEW = ("n_used", "sum_w", "rms", "mean_err", "max_err", "bias_u", "bias_v", "mean_rad")
+RESIDUAL_CAMERA = ("n_used", "sum_w", "rms", "mean_err", "max_err", "worst_view", "n_views_used")
+
+
+def residual_report(problem: Problem, device: int = 0, *, weights=None, loss=None, grid=None, image_size=None, angle_bins: int = 0,
+                    max_angle=None, clamp: float = 64.0) -> dict:
+    """Which views and corners are bad, and does the model fit the lens (tscm_residual_report), at the problem's parameters.
+    weights (default: problem.weights): corner weights as for calibrate(), except that a view whose weights are all 0 is
+    accepted -- it is unused -- so a pruned weights array can be reported on.  loss: as for calibrate(); it sets rho1 and cost.
+    grid=(grid_w, grid_h) with image_size=(width, height): the residual field over the image, by the cell of the OBSERVED
+    pixel.  angle_bins with max_angle (default pi / 2): the field over the incidence angle.  clamp: pixels, in (0, 64].
+    -> corner [N, 6] (RESIDUAL_CORNER; rows of corners with weight 0 are 0) and corner_views (the same rows split per view),
+    view [V, 8] (RESIDUAL_VIEW), view_worst [V] (-1: unused view), camera [C, 8] (RESIDUAL_CAMERA, then 0), cost, rmse, n_used,
+    n_views_used, sum_w, seconds_kernel; with a grid grid_count [C, gh, gw, 2] (count, n_clamped), grid [C, gh, gw, 3] (mean_u,
+    mean_v, rms) and grid_outside [C]; with bins angle_count [C, K, 2], angle [C, K, 4] (mean_rad, mean_tan, rms, mean_angle)
+    and angle_outside [C]."""
+    assert _is_normalised(problem), "use Problem.normalised()"
+    Cn, V, N = problem.n_cameras, problem.n_views, problem.n_corners
+    w = problem.weights if weights is None else weights
+    if w is not None:
+        w = np.ascontiguousarray(np.asarray(w), dtype=np.float64).ravel()
+        if w.size != N:
+            raise ValueError(f"weights: {w.size} entries for {N} corners (one per corner, views in order)")
+    q = _l.CResidualParams()
+    _l.lib().tscm_residual_default_params(C.byref(q))
+    q.loss_kind, q.loss_scale = _l.loss_args(loss)
+    gw = gh = 0
+    if grid is not None:
+        if image_size is None:
+            raise ValueError("grid needs image_size=(width, height)")
+        gw, gh = int(grid[0]), int(grid[1])
+        q.grid_w, q.grid_h, q.image_width, q.image_height = gw, gh, int(image_size[0]), int(image_size[1])
+    K = int(angle_bins)
+    q.n_angle_bins = K
+    if max_angle is not None:
+        q.max_angle = float(max_angle)
+    q.clamp = float(clamp)
+    corner, view, worst, camera = np.zeros((N, 6)), np.zeros((V, 8)), np.zeros(V, dtype=np.int32), np.zeros((Cn, 8))
+    grid_count, grid_mean = np.zeros((Cn, gh, gw, 2), dtype=np.int64), np.zeros((Cn, gh, gw, 3))
+    angle_count, angle_mean = np.zeros((Cn, K, 2), dtype=np.int64), np.zeros((Cn, K, 4))
+    info = _l.CResidualInfo(struct_size=C.sizeof(_l.CResidualInfo))
+    llp = lambda a: a.ctypes.data_as(C.POINTER(C.c_longlong))
+    cp = _l.c_problem(problem)
+    _l.check(_l.lib().tscm_residual_report(C.byref(cp), device, _l.dptr(w), C.byref(q), _l.dptr(corner), _l.dptr(view),
+                                          worst.ctypes.data_as(C.POINTER(C.c_int)), _l.dptr(camera), llp(grid_count) if gw else None,
+                                          _l.dptr(grid_mean) if gw else None, llp(angle_count) if K else None, _l.dptr(angle_mean) if K else None,
+                                          C.byref(info)))
+    first = np.cumsum(problem.view_count) - problem.view_count
+    out = dict(corner=corner, corner_views=[corner[f:f + n] for f, n in zip(first, problem.view_count)], view=view, view_worst=worst,
+               camera=camera, cost=info.cost, rmse=info.rmse, n_used=int(info.n_used), n_views_used=int(info.n_views_used), sum_w=info.sum_w,
+               seconds_kernel=tuple(info.seconds_kernel))
+    if gw:
+        out.update(grid_count=grid_count, grid=grid_mean, grid_outside=np.array(info.grid_outside[:Cn], dtype=np.int64))
+    if K:
+        out.update(angle_count=angle_count, angle=angle_mean, angle_outside=np.array(info.angle_outside[:Cn], dtype=np.int64))
+    return out
+
+
+def view_outliers(report: dict, problem: Problem, k: float = 3.0, floor: float = 0.0, max_fraction: float = 0.2) -> np.ndarray:
+    """bool [V]: the views of a residual_report() whose rms stands out in their camera.  Per camera, over its views with
+    n_used > 0: view v is flagged when rms_v > median + k * 1.4826 * MAD of those rms values and rms_v > floor; at most
+    floor(max_fraction * those views) are flagged per camera, the worst first, ties to the lower view.  Host code."""
+    rms, used = np.asarray(report["view"])[:, 2], np.asarray(report["view"])[:, 0] > 0
+    cam = np.asarray(problem.view_camera)
+    out = np.zeros(cam.size, dtype=bool)
+    for m in range(problem.n_cameras):
+        views = np.nonzero((cam == m) & used)[0]
+        if views.size == 0:
+            continue
+        x = rms[views]
+        med = np.median(x)
+        mad = np.median(np.abs(x - med))
+        hit = views[(x > med + k * 1.4826 * mad) & (x > floor)]
+        cap = int(np.floor(max_fraction * views.size))
+        order = np.lexsort((hit, -rms[hit]))                 # the worst first, then the lower view
+        out[hit[order[:cap]]] = True
+    return out
+
+
+def corner_outliers(report: dict, threshold: float) -> np.ndarray:
+    """bool [N]: the corners of a residual_report() with |r| > threshold (pixels)."""
+    c = np.asarray(report["corner"])
+    return np.hypot(c[:, 0], c[:, 1]) > threshold
+
+
+def prune_weights(problem: Problem, weights=None, views=None, corners=None) -> np.ndarray:
+    """float64 [N]: `weights` (None: problem.weights, or all 1) with the corners of the views in `views` (bool [V] or indices)
+    and the corners in `corners` (bool [N] or indices) set to 0."""
+    N = problem.n_corners
+    w = problem.weights if weights is None else weights
+    w = np.ones(N) if w is None else np.array(w, dtype=np.float64).ravel()
+    if w.size != N:
+        raise ValueError(f"weights: {w.size} entries for {N} corners")
+    if views is not None:
+        flag = np.zeros(problem.n_views, dtype=bool)
+        flag[_index(views)] = True
+        w[np.repeat(flag, problem.view_count)] = 0.0
+    if corners is not None:
+        w[_index(corners)] = 0.0
+    return w
+
+
+def _index(sel) -> np.ndarray:
+    """a bool mask as it is, anything else (an empty list included) as integer indices"""
+    sel = np.asarray(sel)
+    return sel if sel.dtype == np.bool_ else sel.astype(np.int64)
+
+
 UNCERTAINTY_PLANES = ("u_b", "v_b", "c_uu", "c_uv", "c_vv", "sd_worst", "sd_across")
 
 

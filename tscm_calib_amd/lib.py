@@ -205,6 +205,19 @@ class CViewCandidate(C.Structure):
     _fields_ = [("camera_a", C.c_int), ("camera_b", C.c_int), ("board_rt", C.c_double * 6)]
 
 
+class CResidualParams(C.Structure):
+    """tscm_residual_params (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("loss_kind", C.c_int), ("loss_scale", C.c_double), ("grid_w", C.c_int), ("grid_h", C.c_int),
+                ("image_width", C.c_int), ("image_height", C.c_int), ("n_angle_bins", C.c_int), ("pad", C.c_int), ("max_angle", C.c_double),
+                ("clamp", C.c_double)]
+
+
+class CResidualInfo(C.Structure):
+    """tscm_residual_info (tscm.h)"""
+    _fields_ = [("struct_size", C.c_int), ("n_views_used", C.c_int), ("n_used", C.c_longlong), ("sum_w", C.c_double), ("cost", C.c_double),
+                ("rmse", C.c_double), ("grid_outside", C.c_longlong * 32), ("angle_outside", C.c_longlong * 32), ("seconds_kernel", C.c_double * 4)]
+
+
 class CCornerSet(C.Structure):
     _fields_ = [
         ("n_cameras", C.c_int), ("n_boards", C.c_int), ("board_cols", C.c_int), ("board_rows", C.c_int), ("pitch", C.c_double),
@@ -234,6 +247,7 @@ EXPORTS = [
     "tscm_solver_set_camera_priors", "tscm_solve_prior", "tscm_eval_normal_equations_prior", "tscm_eval_step_prior", "tscm_covariance_prior",
     "tscm_projection_uncertainty", "tscm_projection_uncertainty_seconds",
     "tscm_view_gain", "tscm_view_gain_apply", "tscm_view_gain_seconds",
+    "tscm_residual_default_params", "tscm_residual_report", "tscm_residual_debug_chunk_target",
     "tscm_build_maps_ex", "tscm_rectify_points",
     "tscm_stereo_default_params", "tscm_stereo_match", "tscm_stereo_stages", "tscm_stereo_stage_times", "tscm_stereo_points",
     "tscm_stereo_filter_default_params", "tscm_stereo_filter", "tscm_stereo_filter_stages",
@@ -344,6 +358,13 @@ def lib():
     L.tscm_view_gain_apply.argtypes = vg + [C.c_int, dp, dp, ip, ip, dp]
     L.tscm_view_gain_seconds.argtypes = []
     L.tscm_view_gain_seconds.restype = C.c_double
+    llp_ = C.POINTER(C.c_longlong)
+    L.tscm_residual_default_params.argtypes = [C.POINTER(CResidualParams)]
+    L.tscm_residual_default_params.restype = None
+    L.tscm_residual_report.argtypes = [C.POINTER(CProblem), C.c_int, dp, C.POINTER(CResidualParams), dp, dp, ip, dp, llp_, dp, llp_, dp,
+                                       C.POINTER(CResidualInfo)]
+    L.tscm_residual_debug_chunk_target.argtypes = [C.c_int]
+    L.tscm_residual_debug_chunk_target.restype = None
     L.tscm_project_points.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_unproject_pixels.argtypes = [dp, dp, C.c_int, C.c_int, dp]
     L.tscm_reprojection_error.argtypes = [C.POINTER(CProblem), C.c_int, dp, dp, dp]

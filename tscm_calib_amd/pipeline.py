@@ -91,8 +91,43 @@ def _priors_kw(problem, priors):
     return dict(priors=api.camera_priors(problem, **priors))
 
 
+PRUNE_DEFAULTS = dict(k=3.0, floor=0.0, max_fraction=0.2, rounds=1, corner_threshold=None, grid=None, angle_bins=0)
+
+
+def prune_solve(problem, solve, device=0, *, loss=None, weights=None, prune=None, image_size=None) -> dict:
+    """Outlier pruning behind a solve of `problem`, `rounds` times: api.residual_report -> api.view_outliers (k,
+    floor, max_fraction) and, with corner_threshold, api.corner_outliers -> api.prune_weights -> solve(weights), which solves
+    again from the parameters the problem holds, through the weights= path of api.calibrate / api.refinement (a view whose
+    weights are all 0 goes in with count 0).  A round that flags nothing ends the loop.  Then one more report, with grid /
+    angle_bins if given (grid needs image_size).
+    -> weights (None if no round flagged anything and none came in), residuals (the final report), pruned_views [V] bool,
+    pruned_corners [N] bool (without the corners of pruned views), prune_rounds (solves made), summaries (theirs).
+    There is no rig-connectivity logic: a pruned rig that falls apart shows in the covariance's min_pivot_ratio."""
+    opt = dict(PRUNE_DEFAULTS)
+    for k_, v in (prune or {}).items():
+        if k_ not in opt:
+            raise TypeError(f"unknown prune parameter {k_!r}: one of {', '.join(PRUNE_DEFAULTS)}")
+        opt[k_] = v
+    field = dict(grid=opt["grid"], image_size=image_size if opt["grid"] is not None else None, angle_bins=int(opt["angle_bins"]))
+    w = weights
+    views, corners, summaries = np.zeros(problem.n_views, dtype=bool), np.zeros(problem.n_corners, dtype=bool), []
+    for _ in range(int(opt["rounds"])):
+        rep = api.residual_report(problem, device, weights=w, loss=loss)
+        fv = api.view_outliers(rep, problem, opt["k"], opt["floor"], opt["max_fraction"])
+        fc = api.corner_outliers(rep, opt["corner_threshold"]) if opt["corner_threshold"] is not None else np.zeros(problem.n_corners, dtype=bool)
+        fc &= ~np.repeat(fv, problem.view_count)
+        if not fv.any() and not fc.any():
+            break
+        w = api.prune_weights(problem, w, views=fv, corners=fc)
+        views |= fv
+        corners |= fc
+        summaries.append(solve(w))
+    final = api.residual_report(problem, device, weights=w, loss=loss, **field)
+    return dict(weights=w, residuals=final, pruned_views=views, pruned_corners=corners, prune_rounds=len(summaries), summaries=summaries)
+
+
 def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_intr=None, loss=None, model="ts", fixed=None, ransac=None,
-                     mask_outliers=False, priors=None):
+                     mask_outliers=False, priors=None, prune=None):
     """TripleSphereCamera::calibrate (TS.cpp:30-105).  Without an initial guess (has_init_guess_ false, :41-51):
     principal point at the image centre, xi = lambda = 0, alpha = 0.5, estimate_focal.  With init_intr (the member
     intrinsic_ after a converged earlier refinement set has_init_guess_, :78) those steps are skipped and only the
@@ -108,6 +143,9 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
     calls of a run without it.
     priors: None, or dict(intr_sigma={"xi": 0.1, ...}[, pixel_sigma=...]): Gaussian priors on the intrinsics about the values the
     refinement starts from (api.camera_priors; the pose of a mono problem is not free, so cam_rt_sigma counts for nothing).
+    prune: None (the calls of a run without it), or the parameters of prune_solve: behind the refinement, report -> flag ->
+    refine again with the pruned weights; the summary is then the last refinement's and carries residuals, pruned_views,
+    pruned_corners (over the kept views) and prune_rounds.
     Returns (intr[9], Rt[V,3,3] = [r1 r2 t], summary)."""
     w = _model_masks(model, fixed, 1)
     q, count, sel, found = _prepare_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr, model, ransac)
@@ -116,6 +154,13 @@ def calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device=0, init_in
         _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None, weights=cw, **_priors_kw(q, priors))
     else:
         _, summary = api.refinement(q, device, loss=loss, fixed=w if w.any() else None, **_priors_kw(q, priors))
+    if prune is not None:
+        pk = _priors_kw(q, priors)
+        pr = prune_solve(q, lambda cw_: api.refinement(q, device, loss=loss, fixed=w if w.any() else None, weights=cw_, **pk)[1], device, loss=loss,
+                         weights=cw, prune=prune, image_size=img_size)
+        if pr["summaries"]:
+            summary = pr["summaries"][-1]
+        summary.update(residuals=pr["residuals"], pruned_views=pr["pruned_views"], pruned_corners=pr["pruned_corners"], prune_rounds=pr["prune_rounds"])
     intr, Rt = _finish_camera(q, count, sel)
     if found is not None:
         summary["ransac"] = found
@@ -182,7 +227,7 @@ def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, devi
 
 
 def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                    fixed=None, ransac=None, mask_outliers=False, priors=None) -> dict:
+                    fixed=None, ransac=None, mask_outliers=False, priors=None, prune=None) -> dict:
     """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
     loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
     and held intrinsics of both refinements (calibrate_camera).
@@ -190,6 +235,7 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     call drops leaves `has`, and the result carries ransac = the second call's dict(inlier, code, has).
     mask_outliers (with ransac): each of the two refinements takes its own call's inlier mask as its corner mask (calibrate_camera).
     priors: Gaussian priors of both refinements, each about its own start values (calibrate_camera).
+    prune: outlier pruning behind the last refinement (calibrate_camera); second then carries residuals, pruned_views, ...
     Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
     img_size, has, pu, pv = _detect(images, cols, rows, sigma, device)
     intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed,
@@ -201,7 +247,7 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
     intr, Rt, second = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, init_intr=warm, loss=loss, model=model,
-                                        fixed=fixed, ransac=ransac, mask_outliers=mask_outliers, priors=priors)
+                                        fixed=fixed, ransac=ransac, mask_outliers=mask_outliers, priors=priors, **({} if prune is None else dict(prune=prune)))
     out = dict(intr=intr, Rt=Rt, has=has, pix_u=pu, pix_v=pv, first=first, second=second)
     if ransac is not None:
         out.update(has=second["ransac"]["has"], ransac=second["ransac"])
@@ -236,7 +282,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None, suggest=None) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None, suggest=None, prune=None) -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -261,7 +307,13 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     and, about those same values, of the covariance.  Not with batch_mono (the batched route has no priors): ValueError.
     suggest: None, or dict(n_views=5[, grid, distances, tilts_deg, rolls_deg, pairs, criterion, border, min_corners]) -- implies
     covariance and adds result["suggested_views"] = suggest_views(...): where to hold the board next, by the covariance each
-    pose would remove (api.plan_views on the candidates of every camera and of every adjacent pair)."""
+    pose would remove (api.plan_views on the candidates of every camera and of every adjacent pair).
+    prune: None (every function runs the calls it ran before), or dict(k=3.0, floor=0.0, max_fraction=0.2, rounds=1,
+    corner_threshold=None, grid=None, angle_bins=0) -- behind the joint solve, `rounds` times: api.residual_report -> flag
+    (api.view_outliers, api.corner_outliers) -> solve again from the solved parameters with the pruned weights (prune_solve); the
+    result carries residuals (the final report, with the grid over the image and the angle bins if asked for), pruned_views,
+    pruned_corners, prune_rounds and prune_summaries, summary is the last solve's, and a following covariance uses the pruned
+    weights.  There is no rig-connectivity logic: a pruned rig that falls apart shows in the covariance's min_pivot_ratio."""
     if priors is not None and batch_mono:
         raise ValueError("batch_mono=True has no priors: the batched mono route does not take them")
     n_cam = len(images_by_camera)
@@ -290,6 +342,15 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
         out["priors"] = pk["priors"]
     if cw is not None:
         out["corner_mask"] = cw
+    if prune is not None:
+        img = images_by_camera[0][0]
+        pr = prune_solve(problem, lambda cw_: api.calibrate(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw_, **pk), device, loss=loss,
+                         weights=cw, prune=prune, image_size=(img.shape[1], img.shape[0]))
+        if pr["summaries"]:
+            out["summary"] = pr["summaries"][-1]
+            cw = pr["weights"]
+        out.update(residuals=pr["residuals"], pruned_views=pr["pruned_views"], pruned_corners=pr["pruned_corners"], prune_rounds=pr["prune_rounds"],
+                   prune_summaries=pr["summaries"])
     if covariance or uncertainty is not None or suggest is not None:
         if cw is not None:
             out["covariance"] = api.covariance(problem, device, loss=loss, fixed=w if w.any() else None, weights=cw, **pk)
