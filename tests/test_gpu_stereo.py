@@ -1,6 +1,17 @@
 """GPU tests of the stereo matcher (tscm_stereo_*): every stage and the disparity map equal the host restatement
 tests/stereo_ref.py bit for bit (all of it is integer arithmetic), the points agree with an independent two-ray
-construction, and stereo.pair_depth runs the chain from two fisheye images of the rig to points on a plane."""
+construction, and stereo.pair_depth runs the chain from two fisheye images of the rig to points on a plane.
+
+Shapes are the smallest at which each path can go wrong.  96 x 48, 67 x 37, 131 x 53, 200 x 20 and 75 x 21 cover the 1..4
+disparities per lane of k_aggregate (D = 16..256) inside one row segment.  k_cost and k_right_winner cut a row into segments
+of kCostSegment = 256 pixels (tscm_stereo.hip): 256 x 4 is exactly one segment, 257 x 5 gives the second block one column,
+300 x 9 with D = 256 fills the 511 right-hand codes of the first block's window and starts the second block's window in
+mid-row (r0 = 9 at min_disparity -8), 513 x 6 has three blocks, the last with one column, and a positive min_disparity in
+lo = s0 + dmin; the 300 x 12 board ties costs across the seam, and 300 x 9 with the images swapped has its winners at negative
+disparity, the only ones for which k_right_winner's lower bound lo decides.  21 x 75 is taller than wide, so every diagonal of k_aggregate
+restarts at the image edge three times or more, and 75 rows are no multiple of kPrefetch = 4 (tscm_stereo_kernels.h).  3 x 40
+and 1 x 70 leave a vertical or diagonal launch fewer than the 4 scanlines of a block, 70 x 1 does so for the horizontal one,
+8 x 6 is below the 9 x 7 census window, so that every tap of every pixel is a replicated border, and 1 x 1 is the least of all."""
 import functools
 
 import numpy as np
@@ -40,6 +51,8 @@ def _board_pair(w=96, h=48):
 @functools.lru_cache(maxsize=None)
 def _pair(name, w, h):
     left, right = _board_pair(w, h) if name == "board" else _noise_pair(w, h)
+    if name == "noise-swapped":                          # the images trade places: disparity -5 and -12
+        left, right = right, left
     left.setflags(write=False)
     right.setflags(write=False)
     return left, right
@@ -76,7 +89,23 @@ CASES = {
     "board-4-paths": ("board", 96, 48, dict(BASE, paths=4)),
     "board-8-paths": ("board", 96, 48, BASE),
     "board-no-checks": ("board", 96, 48, dict(BASE, uniqueness_ratio=0, disp12_max_diff=-1)),
+    # rows of more than one kCostSegment = 256 pixel segment
+    "exactly-one-segment": ("noise", 256, 4, BASE),
+    "second-segment-of-one-pixel": ("noise", 257, 5, dict(BASE, num_disparities=16, paths=4)),
+    "two-segments-full-window": ("noise", 300, 9, dict(BASE, num_disparities=256, min_disparity=-8)),
+    "three-segments-positive-min": ("noise", 513, 6, dict(BASE, num_disparities=64, min_disparity=3)),
+    "two-segments-board": ("board", 300, 12, BASE),
+    # winners at negative disparity: the kR entries of the second block are fed from columns below s0, inside lo = s0 + dmin
+    "two-segments-negative-disparity": ("noise-swapped", 300, 9, dict(BASE, min_disparity=-24)),
+    # taller than wide, fewer than 4 scanlines, below the census window
+    "tall-diagonals-wrap-thrice": ("noise", 21, 75, BASE),
+    "three-columns": ("noise", 3, 40, dict(BASE, num_disparities=16)),
+    "single-column": ("noise", 1, 70, dict(BASE, num_disparities=16)),
+    "single-row": ("noise", 70, 1, dict(BASE, num_disparities=16)),
+    "below-census-window": ("noise", 8, 6, dict(BASE, num_disparities=16, min_disparity=-4)),
+    "one-pixel": ("noise", 1, 1, dict(BASE, num_disparities=16, paths=4)),
 }
+SEGMENT = 256                    # kCostSegment of tscm_stereo.hip
 
 
 def _differs(a, b):
@@ -112,6 +141,31 @@ def test_row_padding_in_and_out(hip_device):
     assert np.all(out[:, w:] == -12345), "the padding of the disparity rows keeps the caller's values"
     st = stereo.stages(wide[0][:, :w], wide[1][:, :w], device=hip_device, **p)
     assert np.array_equal(st["aggregated"], ref["aggregated"]) and np.array_equal(st["census_right"], ref["census_right"])
+
+
+def test_two_segments_without_left_right_check(hip_device):
+    """300 x 9 with D = 256: the winner over a row of two segments when k_right_winner does not run and the uniqueness rule is
+    off, from contiguous images and from row-padded views into a row-padded output."""
+    w, h, p = 300, 9, dict(BASE, num_disparities=256, disp12_max_diff=-1, uniqueness_ratio=0)
+    left, right = _pair("noise", w, h)
+    ref = _reference("noise", w, h, tuple(sorted(p.items())))
+    got = stereo.stages(left, right, device=hip_device, **p)
+    for stage in ("census_left", "census_right", "cost", "aggregated"):
+        assert got[stage].dtype == ref[stage].dtype and got[stage].shape == ref[stage].shape
+        assert np.array_equal(got[stage], ref[stage]), f"{stage}: {_differs(got[stage], ref[stage])}"
+    disp = stereo.match(left, right, device=hip_device, **p)
+    assert disp.dtype == np.int16 and np.array_equal(disp, ref["disparity"]), _differs(disp, ref["disparity"])
+    assert np.all(disp != 16 * (p.get("min_disparity", 0) - 1))          # neither rule runs: no pixel is invalid
+    wide = [np.full((h, w + 5), 201, dtype=np.uint8) for _ in range(2)]
+    wide[0][:, :w], wide[1][:, :w] = left, right
+    out = np.full((h, w + 3), -12345, dtype=np.int16)
+    padded = stereo.match(wide[0][:, :w], wide[1][:, :w], device=hip_device, out=out[:, :w], **p)
+    assert padded.strides[0] == 2 * (w + 3)
+    assert np.array_equal(out[:, :w], ref["disparity"]), _differs(out[:, :w], ref["disparity"])
+    assert np.all(out[:, w:] == -12345), "the padding of the disparity rows keeps the caller's values"
+    st = stereo.stages(wide[0][:, :w], wide[1][:, :w], device=hip_device, **p)
+    for stage in ("census_left", "census_right", "cost", "aggregated"):
+        assert np.array_equal(st[stage], ref[stage]), f"{stage}, padded: {_differs(st[stage], ref[stage])}"
 
 
 def test_two_calls_give_the_same_bits(hip_device):

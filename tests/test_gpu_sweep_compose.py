@@ -3,7 +3,11 @@ panorama and the coverage equal the host restatement tests/sweep_compose_ref.py 
 arithmetic), a constant index map equals the static composer (tscm_panorama_compose) on that table, and the device chain
 depth -> compose removes the parallax of the sphere scene of tests/test_gpu_sweep.py.  Shapes are those of that file, the
 smallest at which each path can go wrong: 72 x 24 (no multiple of the 64 x 16 pyramid tile, two tiles per row and column),
-64 x 32, 5 x 3 (an odd number of pixels: the last quad holds 3), 2..4 and 8 cameras, D = 16 and 80."""
+64 x 32, 5 x 3 (an odd number of pixels: the last quad holds 3), 2..4 and 8 cameras, D = 16 and 80.  Three shapes take the
+per-frame pyramids to the depths the static composer's LIMIT_CASES reach (kPanoMaxLevels = 6 of tscm_pano_kernels.h):
+64 x 64 at L = 6 ends in a 2 x 2 level over a 1 x 1 top, where col_index wraps on W = 1; 96 x 48 at L = 4, the default level
+count, has level widths 96 .. 6, the last off the 4-pixel vector path; 128 x 64 at L = 5 ends in 4 x 2.  Every one of these
+levels is narrower than the 34 x 10 coarse halo of load_halo (kPanoHaloW, kPanoHaloH)."""
 import ctypes as C
 import functools
 
@@ -69,6 +73,10 @@ CASES = [
     (2, 72, 24, 80, 3, M_, 1, False, False, False, True),
     (8, 64, 32, 16, 3, M_, 3, True, True, False, False),
     (3, 72, 24, 80, 3, F_, 0, True, False, True, False),
+    # the pyramid's depth: the 1 x 1 top of L = 6, the default L = 4 with a 6 x 3 top, the 4 x 2 top of L = 5
+    (8, 64, 64, 16, 3, M_, 6, True, True, True, False),
+    (5, 96, 48, 16, 1, M_, 4, False, True, False, True),
+    (8, 128, 64, 16, 1, M_, 5, True, False, True, True),
 ]
 IDS = ["n%d-%dx%d-D%d-c%d-%s%d-w%d-m%d-g%d-f%d" % (c[:5] + (MODES[c[5]],) + c[6:]) for c in CASES]
 

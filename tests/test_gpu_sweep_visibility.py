@@ -4,7 +4,9 @@ visibility equal the host restatement tests/sweep_visibility_ref.py bit for bit 
 255 and a constant map give the bytes of tscm_sweep_compose; and on the scene with an occluding ball of
 tests/test_sweep_visibility_reference.py the device chain brings the frame nearer to the truth where it takes cameras away.
 Tables, weights, images and index maps are those of tests/test_gpu_sweep.py and tests/test_gpu_sweep_compose.py, at their
-shapes: 72 x 24, 64 x 32, 5 x 3 (the last quad holds 3 pixels), 2..4 and 8 cameras, D = 16 and 80."""
+shapes: 72 x 24, 64 x 32, 5 x 3 (the last quad holds 3 pixels), 2..4 and 8 cameras, D = 16 and 80; and 128 x 64 with 8 cameras
+at L = 5, whose pyramid under the use planes ends in a 4 x 2 level, narrower than the 34 x 10 coarse halo of load_halo
+(kPanoHaloW, kPanoHaloH of tscm_pano_kernels.h)."""
 import ctypes as C
 import functools
 
@@ -34,7 +36,9 @@ SHAPES = [
     (4, 64, 32, 16, True, 0),
     (4, 5, 3, 16, True, 1),
     (3, 5, 3, 80, False, 0),
+    (8, 128, 64, 16, True, 1),
 ]
+LEVELS = {8: 5}               # shape index -> pyramid levels, where they do not rotate with the setting
 
 
 def _settings(D):
@@ -50,10 +54,10 @@ def _case(si, ti):
     r = si + ti
     mode = (S_, F_, M_)[r % 3] if pw > 5 else (S_, F_)[r % 2]
     return dict(n=n, pw=pw, ph=ph, D=D, weights=with_weights, vp=dict(cell_shift=shift, tolerance=tol, dilate=dil, near_is_high=high), ch=(1, 3)[(r // 3) % 2],
-                mode=mode, levels=1 + ti % 3, wrap=bool(r % 2), gains=bool((r // 2) % 2), last=bool(si % 2))
+                mode=mode, levels=LEVELS.get(si, 1 + ti % 3), wrap=bool(r % 2), gains=bool((r // 2) % 2), last=bool(si % 2))
 
 
-CASES = [(si, ti) for si in range(len(SHAPES)) for ti in range(5)]
+CASES = [(si, ti) for si in range(8) for ti in range(5)] + [(8, 3)]           # (8, 3): MULTIBAND, 3 channels, wrap_x, gains, dilate 1
 IDS = ["n%d-%dx%d-D%d-m%d-h%d-s%d-t%d-d%d" % (SHAPES[si] + _settings(SHAPES[si][3])[ti]) for si, ti in CASES]
 
 
