@@ -110,7 +110,11 @@ typedef struct tscm_options {
     double max_trust_region_radius;      /* 1e16                                       */
     double min_trust_region_radius;      /* 1e-32                                      */
     double min_relative_decrease;        /* 1e-3                                       */
-    double min_lm_diagonal;              /* 1e-6                                       */
+    double min_lm_diagonal;              /* 1e-6.  As in Ceres, 0 (or a value that     */
+                                         /* underflows over the radius) makes every    */
+                                         /* step invalid while an intrinsic without a  */
+                                         /* Jacobian column (b, c) is not held: its    */
+                                         /* damped pivot is 0                          */
     double max_lm_diagonal;              /* 1e32                                       */
     int max_num_consecutive_invalid_steps; /* 5                                        */
     int jacobi_scaling;                  /* 1                                          */
@@ -374,7 +378,10 @@ int tscm_solver_eval_normal_equations(tscm_solver *s, const tscm_options *opt, i
  *     still count in x_norm (Ceres' ambient state), as b and c do.  Held values come back bit-identical.
  *   - all of bits 0-6: SetParameterBlockConstant on the block, which leaves the program and x_norm like
  *     a constant camera pose (tscm_problem.cam_pose_constant).
- *   - bits 7-8 (b, c) are accepted and change nothing: b and c are inert in the model.
+ *   - bits 7-8 (b, c): b and c are inert in the model -- no Jacobian column, never moved -- and holding them changes no
+ *     step.  As in Ceres they count as columns of the program while their block is in it and they are not held: their LM
+ *     diagonal is clamp(0, min_lm_diagonal, max_lm_diagonal) / radius, and where that is not > 0 (min_lm_diagonal = 0) the
+ *     factorisation fails and every step is invalid.  Holding both, or all of bits 0-6, takes them out.
  *   - bits 9 and up: TSCM_E_INVALID.
  *   - mask 0 for every camera (or fixed = NULL) is the solve without held intrinsics, bit for bit.
  * Lambda = 0 makes the Triple Sphere model the Double Sphere model, xi = lambda = 0 the Unified Camera

@@ -222,6 +222,26 @@ void exits()
         r.step(110.0, 10.0);
         CHECK(r.logged && ended(r.c, 0, kMinRadius) && r.c.radius == 1250.0 && r.it.radius == 1250.0 && counts(r.c, 2, 3, 1, 2, 0));
     }
+    {
+        // free columns without a Jacobian (b, c): their pivot clamp(0) / radius is 0 with min_lm_diagonal = 0, and the step invalid
+        const unsigned short held[2] = { 128 | 256, 128 | 256 }, one[2] = { 128 | 256, 128 };
+        const unsigned char idle1[2] = { 1, 0 };
+        CHECK(has_inert_columns(nullptr, nullptr, 2) && !has_inert_columns(held, nullptr, 2) && has_inert_columns(one, nullptr, 2) && !has_inert_columns(one, idle1, 2));
+        // all of fx .. alpha held: the block is constant and b, c leave the program with it
+        const unsigned short block[2] = { 127, 127 | 128 }, part[2] = { 127, 126 };
+        CHECK(!has_inert_columns(block, nullptr, 2) && has_inert_columns(part, nullptr, 2) && !has_inert_columns(part, idle1, 2));
+        tscm_options o = defaults();
+        o.min_lm_diagonal = 0.0;
+        Run r(o);
+        r.step(90.0, 20.0);                         // the program has no such column: a good step
+        CHECK(r.logged && r.it.step_is_valid == 1 && r.it.step_is_successful == 1);
+        r.c.inert_cols = 1;
+        r.step(80.0, 20.0);
+        CHECK(r.logged && r.it.step_is_valid == 0 && r.c.num_invalid == 1 && r.c.x_cost == 90.0);
+        r.c.opt.min_lm_diagonal = 1e-6;
+        r.step(80.0, 20.0);
+        CHECK(r.logged && r.it.step_is_valid == 1 && r.it.step_is_successful == 1 && r.c.num_invalid == 0);
+    }
 }
 
 }  // namespace

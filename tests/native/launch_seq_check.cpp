@@ -406,6 +406,7 @@ static int route()
     std::printf("{\"bs_threads\": %d, \"n_bs_blocks\": %d, \"nv_chunks\": [0, %d, %d, %d], \"n_bids\": %d, \"slow_boards\": %d, \"fallback_pairs\": %d, "
                 "\"n_act\": %d, \"dense4_cams\": %d, \"bs_ride_refused\": %d, ", L.bs_threads, L.n_bs_blocks, L.nv_chunks[1], L.nv_chunks[2], L.nv_chunks[3], L.n_bids, (int)L.slow_boards.size(),
                 (int)L.pair_i.size(), cols.n_act, kDense4Cams, (int)bs_ride_refused);
+    std::printf("\"last_dev_view\": %d, \"eval_chunks\": %d, ", L.dev2orig.empty() ? -1 : L.dev2orig.back(), (int)L.chunk_vb.size());      // (the last view of the last evaluation chunk)
     std::printf("\"plan\": {\"comm\": %d, \"gram\": %d, \"robust\": %d, \"tail\": \"%s\", \"ctl_in_schur\": %d, \"stats_ride\": %d, \"t_in_solve\": %d, "
                 "\"solver\": \"%s\", \"nd\": %d, \"tpt\": %d, \"n_prod\": %d, \"n_bs\": %d, \"bs_threads\": %d}, ", x.comm, (int)x.gram, x.robust,
                 tail[(int)x.tail], x.ctl_in_schur, x.stats_ride, x.t_in_solve, solver[(int)x.solver], x.nd, x.tpt, x.n_prod, x.n_bs, x.bs_threads);

@@ -297,7 +297,7 @@ def test_cpp_host_program_through_c_abi(hip_device, tmp_path):
     assert term == os_["termination_type"] and iters == os_["num_iterations"]
 
 
-def test_lm_rejected_and_invalid_steps(hip_device):
+def test_lm_rejected_steps_at_tiny_and_huge_initial_radius(hip_device):
     """A tiny initial radius forces heavily damped steps and a huge one an aggressive first
     step; the accept/reject bookkeeping must follow the oracle either way."""
     p = H.small_rig(4, 10, seed=4)

@@ -40,7 +40,8 @@ struct CtrlHead {
     int done, term_type, term_reason, iteration;
     int cur, lin_fail, num_successful, num_unsuccessful;
     int num_invalid, n_log, lm_iterations, fin_count;   // fin_count: arrival counter of k_reduce_control
-    int fault, pad0;                    // fault: a device-side hand-off timed out (sticky; the host turns it into TSCM_E_HIP)
+    int fault, inert_cols;              // fault: a device-side hand-off timed out (sticky; the host turns it into TSCM_E_HIP)
+                                        // inert_cols: the program has free columns without a Jacobian (has_inert_columns)
     double radius, decrease_factor;
     double x_cost, x_norm, gmax, gnorm;
     double model_cam, stepsq_cam;
@@ -63,6 +64,23 @@ struct StepInput {
     double model_cost_change;           // -(J h)^T (r + J h / 2): positive for a descent step (Ceres' sign)
     double step_norm;                   // |h|, square-rooted
 };
+
+// The skew intrinsics b and c have no Jacobian column.  Ceres keeps them in its program where they are not held: their damped
+// pivots are clamp(0, min_lm_diagonal, max_lm_diagonal) / radius, and a pivot that is not > 0 fails its factorisation, so the
+// step is invalid (min_lm_diagonal = 0, or one that underflows over the radius).  The kernels leave the two columns out of their
+// systems; the control step takes the decision in their place.  A camera's word f leaves b or c in the program unless it holds
+// both (SubsetManifold) or holds all of fx .. alpha (SetParameterBlockConstant: the whole block, b and c with it, leaves the
+// program -- block_const of plan_columns and k_mb_control).  fixed: the TSCM_FIX_* word of each of the n cameras (null: none
+// held), active: whether the camera has views in the whole job (null: all have).
+constexpr unsigned kInertFixBits = 128 | 256;              // TSCM_FIX_B | TSCM_FIX_C
+constexpr unsigned kBlockFixBits = 127;                    // TSCM_FIX_INTRINSICS
+TSCM_CTRL_FN bool inert_free(unsigned f) { return (f & kInertFixBits) != kInertFixBits && (f & kBlockFixBits) != kBlockFixBits; }
+inline int has_inert_columns(const unsigned short *fixed, const unsigned char *active, int n)
+{
+    for (int m = 0; m < n; ++m)
+        if ((!active || active[m]) && (!fixed || inert_free(fixed[m]))) return 1;
+    return 0;
+}
 
 // One step of the LM control (TrustRegionMinimizer + LevenbergMarquardtStrategy + TrustRegionStepEvaluator) on the head c,
 // for every route of the library.  `init` = IterationZero; otherwise the tail of one loop iteration followed by
@@ -88,7 +106,8 @@ TSCM_CTRL_FN bool lm_step(CtrlHead &c, int init, int tgt, const StepInput &in, I
         it.iteration = c.iteration;
         const double model = in.model_cost_change;
         const double step_norm = in.step_norm;
-        const bool valid = !c.lin_fail && isfinite(model) && isfinite(step_norm) && model > 0.0;
+        const bool inert_fail = c.inert_cols && !(fmin(fmax(0.0, o.min_lm_diagonal), o.max_lm_diagonal) / c.radius > 0.0);
+        const bool valid = !c.lin_fail && !inert_fail && isfinite(model) && isfinite(step_norm) && model > 0.0;
         c.lin_fail = 0;
         it.step_is_valid = valid ? 1 : 0;
         it.gradient_max_norm = c.gmax; it.gradient_norm = c.gnorm;

@@ -127,7 +127,7 @@ __device__ __forceinline__ bool mb_frozen(const MbDev &D, int k) { return D.head
 __global__ __launch_bounds__(256) void k_mb_begin(MbDev D, CtrlHead head)
 {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < D.K) D.head[k] = head;
+    if (k < D.K) { head.inert_cols = inert_free(D.mask[k]) ? 1 : 0; D.head[k] = head; }      // (every problem here has views)
     if (k == 0) *D.n_done = 0;
 }
 

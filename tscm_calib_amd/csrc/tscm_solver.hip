@@ -1205,6 +1205,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         s->xp = plan_exec(s->L, s->C, s->P.n_act, comm_kind(s->comm_reg), opt.exec_flags, opt.jacobian_fp32, s->loss.kind, s->P.rp, s->dev, false, s->n_priors > 0);
         s->comm = s->xp.comm ? s->comm_reg : nullptr;
         s->head = ctrl_head_from_options(opt);
+        s->head.inert_cols = has_inert_columns(s->fixed.data(), s->L.cam_active.data(), s->C);
         s->withhold = s->withhold_next; s->withhold_next = 0;
         if (!rerun) { s->no_rerun = s->no_rerun_next; s->no_rerun_next = false; }
     }
