@@ -1,7 +1,7 @@
 // tscm_dev.h -- what every stage of an LM iteration shares on the device: the record and tile constants, buffer and lane
 // helpers, the problem / state structs the kernels take by value, and the in-launch hand-off loads and stores.
 #pragma once
-// (included from tscm_kernels.h inside namespace tscm)
+// (included inside namespace tscm: from tscm_kernels.h, and from tscm_mono_batch.hip)
 
 // the view record regions kRecW / kRecE / kRecG and the rig limits kMaxCamLds / kMaxCam / kSmallBids: tscm_layout.h
 // the operand map of k_solve_reduced (kMap*, kSolveMapSlots, kMapOne): tscm_columns.h

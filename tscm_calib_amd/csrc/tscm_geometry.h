@@ -1,7 +1,7 @@
 // tscm_geometry.h -- stage 1, shared by the Gram kernels: a corner's projection, residual and Jacobian entries, the robust
 // loss, and the epilogue that turns a view's accumulator tiles into its record.
 #pragma once
-// (included from tscm_kernels.h inside namespace tscm)
+// (included inside namespace tscm: from tscm_kernels.h, and from tscm_mono_batch.hip)
 
 // tile column -> (parity mask) bookkeeping shared by the hot kernel's epilogue and k_finalize_eval.
 //   f*   = -X/k on u-rows, -Y/k on v-rows : fx is its u-half, fy its v-half

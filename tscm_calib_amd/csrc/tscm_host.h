@@ -19,6 +19,21 @@ int tscm_set_error(int code, const std::string &msg);   // tscm_solver.hip: the 
 int tscm_eval_normal_equations_spec(const tscm_problem *p, int device, const tscm_options *opt, const tscm::SolveSpec &in, double *board_gram,
                                     double *board_grad, double *view_cross, double *cam_gram, double *cam_grad, double *cost);
 
+// a service of one .hip file to the others: linked across the library's objects, not exported from it
+#define TSCM_INTERNAL __attribute__((visibility("hidden")))
+
+// tscm_solver.hip, for the batched mono route (tscm_mono_batch.hip) and the exchange back-ends (tscm_comm.hip):
+namespace tscm { struct CtrlHead; struct IterLog; }
+TSCM_INTERNAL double wall();                            // seconds of the steady clock
+// the caller's options (NULL: the defaults of a mono / multi solve) in this library's struct; refuses an unknown struct_size
+TSCM_INTERNAL int read_options(const tscm_options *opt_in, int mono, tscm_options &opt);
+// tscm_spec.h's check_corner_weights with its text in tscm_last_error()
+TSCM_INTERNAL int check_corner_weights(const int *view_count, int n_views, const double *w, double *sum = nullptr, long *kept = nullptr);
+// a terminated control block and its iteration log as a summary (times excepted); rmse: that of a plain loss, sqrt(2 cost / N)
+TSCM_INTERNAL void fill_summary(const tscm::CtrlHead &h, const tscm::IterLog *log, long N, tscm_summary *sum);
+// one solve on the calling thread's device, with a checked spec
+TSCM_INTERNAL int solve_configured(const tscm_problem *p, const tscm_options *opt, const tscm::SolveSpec &spec, tscm_summary *sum);
+
 // a failed HIP call ends the calling function with TSCM_E_HIP
 #define HIP_TRY(expr)                                                                                  \
     do {                                                                                               \

@@ -10,7 +10,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -291,8 +290,6 @@ __global__ void k_rig_boards(int C, int B, int n, const unsigned char *has, cons
     for (int i = 0; i < 9; ++i) board_R[9 * (size_t)b + i] = Rs[best].a[i];
     for (int i = 0; i < 3; ++i) board_t[3 * (size_t)b + i] = ts[best].a[i];
 }
-
-double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Rt_to_R_t of every (camera, board) with a detection: [C*B][R (9) | t (3)], zero where there is none
 std::vector<double> host_poses(const tscm_rig_input *in)

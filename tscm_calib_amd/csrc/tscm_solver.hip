@@ -6,15 +6,19 @@
 // The host only enqueues kernels and polls a device-resident control block: accept/reject,
 // the trust-region radius and the termination tests all run on the GPU (k_control), so one LM
 // iteration costs no host<->device round trip.
+//
+// In this file: the solver object and its settings, the LM driver (run_lm) with the launches of tscm_kernels.h, the one-shot
+// and operator-level entry points, the debug read-backs.  Elsewhere: the exchange back-ends and the tscm_comm_* entry points
+// in tscm_comm.hip, asked only through tscm_comm.h; the batched mono route in tscm_mono_batch.hip, which uses the services
+// this file declares in tscm_host.h.
 #include "tscm/tscm.h"
+#include "tscm_comm.h"
 #include "tscm_host.h"
 #include "tscm_kernels.h"
 #include "tscm_launch_seq.h"
-#include "tscm_mono_batch.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
-#include <rccl/rccl.h>
 
 #include <algorithm>
 #include <atomic>
@@ -26,7 +30,6 @@
 #include <memory>
 #include <numeric>
 #include <string>
-#include <thread>
 #include <vector>
 
 using namespace tscm;
@@ -36,61 +39,7 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 int tscm_set_error(int code, const std::string &msg) { return fail(code, msg); }   // tscm_host.h: HIP_TRY, select_device
 
-#define NCCL_TRY(expr)                                                                                 \
-    do {                                                                                               \
-        ncclResult_t r_ = (expr);                                                                      \
-        if (r_ != ncclSuccess)                                                                         \
-            return fail(TSCM_E_RCCL, std::string(#expr) + ": " + ncclGetErrorString(r_));             \
-    } while (0)
-
-static double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// Exchange backends of the frame-sharded solve.  RCCL: one process per GPU (the production path).  LOCAL: all ranks
-// live in ONE process on ONE device and share a stream -- the all-reduce is a kernel that sums the ranks' buffers in
-// rank order (tscm_comm_create_local / tscm_solver_solve_group): it runs every line of the sharded solver on a
-// one-GPU box (RCCL refuses two ranks on one device) and serves hosts that drive several shards from one thread.
-struct tscm_local_group {
-    int world = 0, device = 0, refs = 0;
-    hipStream_t stream = nullptr;
-    double **d_ptrs = nullptr;           // [world] device array of the members' exchange buffers (rewritten per exchange)
-    DeviceMem mem;                       // owns d_ptrs
-    ~tscm_local_group() { if (stream) (void)hipStreamDestroy(stream); }
-};
-// IPC: one process per rank like RCCL, but the exchange is this library's own one-shot all-reduce over memory the ranks
-// map from each other (hipIpcMemHandle: the same device, or peers over xGMI).  Every rank owns a buffer of
-// 2 (parity) x world (source rank) slots of max_doubles doubles and 2 x world arrival flags; an exchange is ONE
-// single-workgroup kernel per rank: store my values into my slot of every rank's buffer, release, raise my flag there;
-// wait for the world flags of my own buffer; sum the slots in rank order (the bits of the LOCAL backend, on every
-// rank).  4 us where an RCCL all-reduce of 16-32 KB takes 15-25 -- and the only back-end that can put several rank
-// PROCESSES on one device, which is how the multi-process path runs on a one-GPU box (tools/ipc_check.py,
-// `bench.py --gpus N` with fewer devices than ranks).  Exercised between processes on ONE device only (no
-// multi-GPU box in reach).  Across devices it is correct by construction since round 5 -- the buffer (slots and flags) is
-// fine-grained device memory (hipExtMallocWithFlags: coherent for a peer's system-scope stores and loads), peer access is
-// enabled explicitly at connect, and a rank whose buffer could only be had coarse-grained refuses peers on other devices --
-// but unmeasured: RCCL stays the default.  A peer that does not arrive within the bound makes the communicator unusable
-// (TSCM_E_PEER from then on, like an aborted RCCL communicator).
-constexpr int kIpcMaxWorld = 16;
-struct IpcPeers { double *base[kIpcMaxWorld]; };
-struct tscm_ipc {
-    int world = 0, rank = 0;
-    size_t max_doubles = 0;             // per slot
-    DeviceMem mem;                      // owns this rank's buffer and d_fault
-    void *mapped[kIpcMaxWorld] = {};    // the ranks' buffers as mapped here (this rank's own at [rank])
-    bool connected = false;
-    long long count = 0;                // exchanges so far: parity and flag value of the next one
-    int *d_fault = nullptr;             // raised by a kernel whose peers did not arrive within the bound
-    bool fine = false;                  // the buffer is fine-grained memory (a peer on another device may use it)
-    bool dead = false;                  // a peer fault or a failed solve: the ranks' exchange counters can no longer be trusted to agree
-    size_t slot_doubles() const { return max_doubles; }
-    size_t flags_offset() const { return 2 * (size_t)world * max_doubles; }        // in doubles (flags are 8-byte words)
-    size_t total_bytes() const { return 8 * (flags_offset() + 2 * (size_t)world); }
-};
-struct tscm_comm {
-    ncclComm_t comm = nullptr;
-    tscm_local_group *group = nullptr;   // LOCAL backend
-    tscm_ipc *ipc = nullptr;             // IPC backend
-    int rank = 0, world = 1, device = 0;
-};
+double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // the Gram kernels k_eval_gram4 / k_eval_gram_f32 share one signature; every family is instantiated per k-step count of a pass
 // (tscm_exec_plan.h: g4_plan).  A family is a tier (G4: fp64, F32: the fp32-Jacobian tier on the same pass plan) plus 0 plain,
@@ -257,7 +206,7 @@ static int make_spec(int kind, double scale, const unsigned short *fixed, int n_
     if (int rc = tscm::make_spec(kind, scale, fixed, n_cameras, spec, err)) return fail(rc, err);
     return 0;
 }
-static int check_corner_weights(const int *view_count, int n_views, const double *w, double *sum = nullptr, long *kept = nullptr)
+int check_corner_weights(const int *view_count, int n_views, const double *w, double *sum, long *kept)
 {
     std::string err;
     if (int rc = tscm::check_corner_weights(view_count, n_views, w, err, sum, kept)) return fail(rc, err);
@@ -635,8 +584,6 @@ extern "C" int tscm_solver_create(const tscm_problem *p, int device, tscm_solver
     return tscm_solver_create_sharded(p, device, 0, 1, out);
 }
 
-static CommKind comm_kind(const tscm_comm *c) { return !c ? kCommNone : c->world > 1 || c->group ? kCommShared : kCommOneRank; }
-
 // Fault injection for the tests of the device-side hand-off: in the NEXT solve of this solver one producer of the fused
 // hand-off never reports in, and the solve must end with TSCM_E_HIP within the hand-off's time bound.  Not an option of
 // a solve (tscm_options carries nothing that can make a production solve fail).
@@ -678,8 +625,8 @@ extern "C" int tscm_solver_reruns(const tscm_solver *s)
 extern "C" int tscm_solver_set_comm(tscm_solver *s, tscm_comm *comm)
 {
     if (!s) return fail(TSCM_E_INVALID, "solver is NULL");
-    if (comm && comm->device != s->device) return fail(TSCM_E_INVALID, "communicator and solver live on different devices");
-    if (comm && (comm->world != s->world || comm->rank != s->rank))
+    if (comm && comm_device(comm) != s->device) return fail(TSCM_E_INVALID, "communicator and solver live on different devices");
+    if (comm && (comm_world(comm) != s->world || comm_rank(comm) != s->rank))
         return fail(TSCM_E_INVALID, "communicator rank / world differ from the solver's shard (tscm_solver_create_sharded)");
     // a single-rank RCCL communicator is a no-op unless a solve asks for its code path (separate k_control,
     // stream-ordered all-reduces) with TSCM_EXEC_KEEP_SINGLE_RANK_COMM: uses_comm()
@@ -803,84 +750,8 @@ extern "C" int tscm_solver_exchange_time(tscm_solver *s, int *n_T, double *ms_T,
 // Per iteration the ranks exchange exactly two buffers, each with a sum all-reduce:
 //   T        n_bids * 256 doubles   the Schur complement tiles, after k_T_reduce
 //   H_stage  256 C + kScal + world  camera tiles, cost, model-cost / norm partials, failure flag, per-rank max slots
+// (tscm_comm.hip: comm_allreduce, comm_group_sum)
 // ------------------------------------------------------------------------------------------------
-__global__ void k_xchg_sum(double *const *bufs, int world, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double a = 0.0;
-    for (int r = 0; r < world; ++r) a += bufs[r][i];       // rank order: every member receives the same bits
-    for (int r = 0; r < world; ++r) bufs[r][i] = a;
-}
-
-// the IPC backend's all-reduce: one workgroup of 1024 threads per rank (n <= max_doubles)
-constexpr long long kIpcTimeoutTicks = 1000000000;      // 10 s of s_memrealtime (100 MHz): the start-up skew between rank processes (code-object loads of a first launch) included
-__global__ __launch_bounds__(1024) void k_ipc_allreduce(double *buf, size_t n, IpcPeers peers, int rank, int world, size_t max_doubles, long long epoch, int *fault)
-{
-    // (a peer that has not arrived once is gone: the exchanges still enqueued behind the failed one do not wait for it again)
-    if (__hip_atomic_load(fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    const int parity = (int)(epoch & 1);
-    const size_t slot = ((size_t)parity * world + rank) * max_doubles, flags = 2 * (size_t)world * max_doubles;
-    for (int p = 0; p < world; ++p) {
-        double *dst = peers.base[p] + slot;
-        for (size_t i = threadIdx.x; i < n; i += 1024) __builtin_nontemporal_store(buf[i], dst + i);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");            // (system scope: my stores are visible wherever the flag is)
-    __syncthreads();
-    if ((int)threadIdx.x < world) {
-        long long *f = reinterpret_cast<long long *>(peers.base[threadIdx.x] + flags) + (size_t)parity * world + rank;
-        __hip_atomic_store(f, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    __shared__ int s_late;
-    if (threadIdx.x == 0) s_late = 0;
-    __syncthreads();
-    if ((int)threadIdx.x < world) {
-        const long long *f = reinterpret_cast<const long long *>(peers.base[rank] + flags) + (size_t)parity * world + threadIdx.x;
-        const long long t0 = wall_clock64();
-        while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < epoch) {
-            __builtin_amdgcn_s_sleep(8);
-            if (wall_clock64() - t0 > kIpcTimeoutTicks) { s_late = 1; break; }
-        }
-    }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    if (s_late) { if (threadIdx.x == 0) __hip_atomic_store(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return; }
-    const double *mine = peers.base[rank] + (size_t)parity * world * max_doubles;
-    for (size_t i = threadIdx.x; i < n; i += 1024) {
-        double a = 0.0;
-        for (int r = 0; r < world; ++r) a += __builtin_nontemporal_load(mine + (size_t)r * max_doubles + i);     // rank order: every rank receives the same bits
-        buf[i] = a;
-    }
-}
-
-// sum all-reduce of n doubles (in place) over the ranks of a multi-process communicator, on `stream`
-static int comm_allreduce(tscm_comm *c, double *buf, size_t n, hipStream_t stream)
-{
-    if (c->ipc) {
-        tscm_ipc *x = c->ipc;
-        if (!x->connected) return fail(TSCM_E_INVALID, "tscm_comm_ipc_connect has not been called");
-        if (x->dead) return fail(TSCM_E_PEER, "the IPC communicator is unusable after an earlier failure (a peer that did not arrive, or a failed solve)");
-        IpcPeers peers{};
-        for (int r = 0; r < x->world; ++r) peers.base[r] = static_cast<double *>(x->mapped[r]);
-        for (size_t off = 0; off < n; off += x->max_doubles) {
-            const size_t m = std::min(x->max_doubles, n - off);
-            hipLaunchKernelGGL(k_ipc_allreduce, dim3(1), dim3(1024), 0, stream, buf + off, m, peers, x->rank, x->world, x->max_doubles, ++x->count, x->d_fault);
-        }
-        return 0;
-    }
-    NCCL_TRY(ncclAllReduce(buf, buf, n, ncclDouble, ncclSum, c->comm, stream));
-    return 0;
-}
-// after a synchronisation: did an IPC exchange give up on a peer?
-static int comm_check(tscm_comm *c)
-{
-    if (!c || !c->ipc) return 0;
-    int f = 0;
-    HIP_TRY(hipMemcpy(&f, c->ipc->d_fault, sizeof(int), hipMemcpyDeviceToHost));
-    if (f) { c->ipc->dead = true; return fail(TSCM_E_PEER, "IPC exchange: a peer rank did not arrive within the bound (failed or gone); the communicator is unusable from here on"); }
-    return 0;
-}
-
 // the members of a run and, per member, the launch sequence of the phase in progress (tscm_launch_seq.h)
 struct LmSeq {
     SeqState st;
@@ -899,11 +770,11 @@ static int exchange(LmRun &run, bool t_buffer)
     const size_t n = t_buffer ? 256 * (size_t)s0->P.n_bids : 256 * (size_t)s0->P.C + kScal + s0->P.world;
     if (n == 0) return 0;
     hipEvent_t e1 = nullptr;
-    if (s0->comm->group) {
-        tscm_local_group *g = s0->comm->group;      // pointer tables: [0, world) the members' T, [world, 2 world) their H_stage (run_lm)
-        if (int rc = timed_begin(s0, t_buffer ? 1 : 2, g->stream, &e1)) return rc;
-        hipLaunchKernelGGL(k_xchg_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g->stream, g->d_ptrs + (t_buffer ? 0 : g->world), g->world, n);
-        if (e1) HIP_TRY(hipEventRecord(e1, g->stream));
+    if (comm_is_local_group(s0->comm)) {
+        const hipStream_t gs = comm_group_stream(s0->comm);     // (the members' buffers: comm_group_bind in run_lm_inner)
+        if (int rc = timed_begin(s0, t_buffer ? 1 : 2, gs, &e1)) return rc;
+        comm_group_sum(s0->comm, t_buffer, n);
+        if (e1) HIP_TRY(hipEventRecord(e1, gs));
         return 0;
     }
     double *buf = t_buffer ? s0->S.T : s0->S.H_stage;
@@ -1039,7 +910,7 @@ struct LmRunGuard {
 };
 
 // a terminated control block and its iteration log as a summary (times excepted); rmse: that of a plain loss, sqrt(2 cost / N)
-static void fill_summary(const CtrlHead &h, const IterLog *log, long N, tscm_summary *sum)
+void fill_summary(const CtrlHead &h, const IterLog *log, long N, tscm_summary *sum)
 {
     sum->termination_type = h.term_type;
     sum->num_iterations = std::min(h.n_log, TSCM_MAX_ITERATIONS + 1);
@@ -1065,7 +936,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
 // the caller's struct may be SHORTER than this library's (built against an older header of ABI >= 6): read what it has, the
 // rest keeps its default.  The shortest struct the library knows ends behind exec_flags (ABI 6); a size of 0, a smaller or a
 // larger one is refused -- a struct of ABI <= 5 has max_num_iterations where struct_size is and never passes
-static int read_options(const tscm_options *opt_in, int mono, tscm_options &opt)
+int read_options(const tscm_options *opt_in, int mono, tscm_options &opt)
 {
     tscm_default_options(&opt, mono);
     if (opt_in) {
@@ -1085,34 +956,8 @@ static int check_options(const tscm_options &opt, int loss_kind, bool weighted =
     return 0;
 }
 
-// Waits for the solver's stream.  With a multi-rank RCCL communicator a peer that has failed (or died) leaves this
-// rank's all-reduce kernel spinning for ever -- over the intra-node transports an ncclCommAbort on the FAILING rank does
-// not reach the others -- so the wait is a poll with a watchdog: no completion within kCommWatchdogSeconds aborts the
-// communicator locally and fails the call with TSCM_E_RCCL.  (A whole solve of the largest supported problem is well
-// under a second of device time; the bound only has to exceed the start-up skew between the rank processes.)
-constexpr double kCommWatchdogSeconds = 60.0;
-static int sync_stream(tscm_solver *s)
-{
-    tscm_comm *c = s->comm;
-    if (!c || c->group || !c->comm || c->world <= 1) { HIP_TRY(hipStreamSynchronize(s->stream)); return 0; }
-    const double t0 = wall();
-    for (;;) {
-        const hipError_t q = hipStreamQuery(s->stream);
-        if (q == hipSuccess) return 0;
-        if (q != hipErrorNotReady) { HIP_TRY(q); }
-        if (wall() - t0 > kCommWatchdogSeconds) {
-            (void)ncclCommAbort(c->comm);
-            c->comm = nullptr;
-            return fail(TSCM_E_RCCL, "no progress on the solver stream within the watchdog interval: a peer rank has failed or is gone (communicator aborted)");
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-}
-
-// An RCCL rank that leaves the loop on an error aborts its communicator (unusable afterwards, like after any RCCL
-// error).  That does NOT unblock its peers by itself: they leave their next all-reduce through the watchdog of
-// sync_stream (TSCM_E_RCCL), or are torn down by whoever started the ranks (bench.py's launcher ends all ranks as soon
-// as one exits non-zero).  A failed rank must not be re-used: start a fresh process.
+// A rank of a multi-rank communicator that leaves the loop on an error other than TSCM_E_INVALID (a refusal: nothing was
+// exchanged) makes its communicator unusable (tscm_comm.hip: comm_fail, and what that means for the peers).
 static int run_lm(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, int reset)
 {
     bool late = false;
@@ -1132,14 +977,7 @@ static int run_lm(LmRun &run, const tscm_options *opt_in, tscm_summary *sums, in
         if (rc == 0) g_err = "note: " + first + "; the solve was run again on separate launches and completed";
         ++run.m[0]->n_reruns;
     }
-    tscm_comm *c = run.m[0]->comm;
-    if (rc != 0 && rc != TSCM_E_INVALID && c && c->ipc && c->world > 1) c->ipc->dead = true;     // (its exchange counter may be behind the peers' now)
-    if (rc != 0 && rc != TSCM_E_INVALID && c && c->comm && c->world > 1) {
-        const std::string keep = g_err;
-        (void)ncclCommAbort(c->comm);
-        c->comm = nullptr;
-        g_err = keep + " (communicator aborted)";
-    }
+    if (rc != 0 && rc != TSCM_E_INVALID) comm_fail(run.m[0]->comm);
     return rc;
 }
 
@@ -1209,16 +1047,15 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         s->withhold = s->withhold_next; s->withhold_next = 0;
         if (!rerun) { s->no_rerun = s->no_rerun_next; s->no_rerun_next = false; }
     }
-    if (s0->comm && !s0->comm->group && !s0->comm->ipc && !s0->comm->comm) return fail(TSCM_E_RCCL, "the communicator was aborted by an earlier failure");
-    if (s0->comm && s0->comm->ipc && s0->comm->ipc->dead) return fail(TSCM_E_PEER, "the IPC communicator is unusable after an earlier failure (a peer that did not arrive, or a failed solve)");
-    if (s0->comm && s0->comm->group) {
+    if (int rc = comm_usable(s0->comm)) return rc;
+    if (comm_is_local_group(s0->comm)) {
         // a local group runs on ONE stream: lock step by stream order, no events
-        tscm_local_group *g = s0->comm->group;
-        if ((int)run.m.size() != g->world) return fail(TSCM_E_INVALID, "a local group solves with all of its members (tscm_solver_solve_group)");
-        std::vector<double *> ptrs(2 * (size_t)g->world);
-        for (int r = 0; r < g->world; ++r) { ptrs[r] = run.m[r]->S.T; ptrs[g->world + r] = run.m[r]->S.H_stage; }
-        HIP_TRY(hipMemcpy(g->d_ptrs, ptrs.data(), sizeof(double *) * ptrs.size(), hipMemcpyHostToDevice));
-        for (tscm_solver *s : run.m) { HIP_TRY(hipStreamSynchronize(s->own_stream)); s->stream = g->stream; }
+        const int world = comm_world(s0->comm);
+        if ((int)run.m.size() != world) return fail(TSCM_E_INVALID, "a local group solves with all of its members (tscm_solver_solve_group)");
+        std::vector<double *> ptrs(2 * (size_t)world);      // [0, world) the members' T, [world, 2 world) their H_stage
+        for (int r = 0; r < world; ++r) { ptrs[r] = run.m[r]->S.T; ptrs[world + r] = run.m[r]->S.H_stage; }
+        if (int rc = comm_group_bind(s0->comm, ptrs)) return rc;
+        for (tscm_solver *s : run.m) { HIP_TRY(hipStreamSynchronize(s->own_stream)); s->stream = comm_group_stream(s0->comm); }
     }
     for (size_t r = 0; r < run.m.size(); ++r) std::memset(&sums[r], 0, sizeof(tscm_summary));
 
@@ -1239,13 +1076,13 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
         if (it % check_every == 0 && it < opt.max_num_iterations) {
             // every rank takes the same decisions from the same all-reduced bits: polling one member is enough
             HIP_TRY(hipMemcpyAsync(s0->h_ctrl, s0->S.ctrl, 64, hipMemcpyDeviceToHost, s0->stream));
-            if ((rc = sync_stream(s0))) return rc;
+            if ((rc = comm_wait(s0->comm, s0->stream))) return rc;
             done = s0->h_ctrl->done != 0;
         }
     }
     for (size_t r = 0; r < run.m.size(); ++r) seq_finish(run.m[r]->L, run.m[r]->C, run.seq[r].st, run.seq[r].todo);
     if ((rc = walk(run))) return rc;
-    if ((rc = sync_stream(s0))) return rc;
+    if ((rc = comm_wait(s0->comm, s0->stream))) return rc;
     for (tscm_solver *s : run.m) if (s->stream != s0->stream) HIP_TRY(hipStreamSynchronize(s->stream));
     if ((rc = comm_check(s0->comm))) return rc;
     const double t1 = wall();
@@ -1276,7 +1113,7 @@ static int run_lm_inner(LmRun &run, const tscm_options *opt_in, tscm_summary *su
 extern "C" int tscm_solver_solve_resident(tscm_solver *s, const tscm_options *opt_in, tscm_summary *sum, int reset)
 {
     if (!s || !sum) return fail(TSCM_E_INVALID, "NULL argument");
-    if (s->comm_reg && s->comm_reg->group && s->world > 1) return fail(TSCM_E_INVALID, "member of a local group: use tscm_solver_solve_group");
+    if (comm_is_local_group(s->comm_reg) && s->world > 1) return fail(TSCM_E_INVALID, "member of a local group: use tscm_solver_solve_group");
     if (s->world > 1 && !s->comm_reg) return fail(TSCM_E_INVALID, "sharded solver without a communicator (tscm_solver_set_comm)");
     LmRun run;
     run.m.push_back(s);
@@ -1290,7 +1127,7 @@ extern "C" int tscm_solver_solve_group(tscm_solver **solvers, int n, const tscm_
     for (int r = 0; r < n; ++r) {
         tscm_solver *s = solvers[r];
         if (!s || s->world != n || s->rank != r) return fail(TSCM_E_INVALID, "solvers[r] must be shard r of n (tscm_solver_create_sharded)");
-        if (n > 1 && (!s->comm_reg || !s->comm_reg->group || s->comm_reg->group != solvers[0]->comm_reg->group))
+        if (n > 1 && !comm_same_group(s->comm_reg, solvers[0]->comm_reg))
             return fail(TSCM_E_INVALID, "the solvers of a group need the communicators of ONE tscm_comm_create_local call");
         run.m.push_back(s);
     }
@@ -1325,7 +1162,7 @@ extern "C" int tscm_solver_gather_boards(tscm_solver *s, double *board_rt)
 {
     if (!s || (!board_rt && s->L.B_total)) return fail(TSCM_E_INVALID, "NULL argument");
     HIP_TRY(hipSetDevice(s->device));
-    if (!s->comm_reg || s->world == 1 || s->comm_reg->group) return tscm_solver_download_params(s, nullptr, nullptr, board_rt);   // local groups share the caller's array
+    if (!s->comm_reg || s->world == 1 || comm_is_local_group(s->comm_reg)) return tscm_solver_download_params(s, nullptr, nullptr, board_rt);   // local groups share the caller's array
     if (s->L.B_total == 0) return 0;
     const size_t n = 6 * (size_t)s->L.B_total;
     std::vector<double> mine(n, 0.0);
@@ -1381,8 +1218,8 @@ static int create_configured(const tscm_problem *p, int device, const SolveSpec 
     return 0;
 }
 
-// one solve on the calling thread's device, with a checked spec
-static int solve_configured(const tscm_problem *p, const tscm_options *opt, const SolveSpec &spec, tscm_summary *sum)
+// one solve on the calling thread's device, with a checked spec (tscm_host.h)
+int solve_configured(const tscm_problem *p, const tscm_options *opt, const SolveSpec &spec, tscm_summary *sum)
 {
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -1733,374 +1570,6 @@ extern "C" int tscm_reprojection_error(const tscm_problem *p, int device, double
     if (global_mean) *global_mean = n ? tot / (double)n : 0.0;
     if (rmse) *rmse = n ? std::sqrt(sq / (double)n) : 0.0;
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// batched mono refinement (tscm_mono_batch.h)
-// ------------------------------------------------------------------------------------------------
-struct MbStream {
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~MbStream() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); if (s) (void)hipStreamDestroy(s); }
-};
-
-// plain pixel RMSE of one problem at its parameters (a robust solve's summary.rmse, as tscm_reprojection_error computes it);
-// w: the problem's corner weights or NULL -- sqrt(sum omega s / sum omega), a corner with omega = 0 is not read
-static double mb_pixel_rmse(const tscm_problem &p, const double *w = nullptr)
-{
-    ViewConst vc;
-    mono_view_const(p.intr, vc);
-    double sq = 0.0, wsum = 0.0;
-    long n = 0;
-    for (int v = 0; v < p.n_views; ++v) {
-        if (p.view_count[v] <= 0) continue;
-        const double *rt = p.board_rt + 6 * (size_t)p.view_board[v];
-        double bc[kBoardConst];
-        board_constants(rt, bc);
-        for (int q = 0; q < 3; ++q) { vc.r1[q] = bc[q]; vc.r2[q] = bc[3 + q]; vc.tb[q] = rt[3 + q]; }
-        for (int kk = 0; kk < 3; ++kk) for (int q = 0; q < 6; ++q) vc.db[kk][q] = bc[6 + 6 * kk + q];
-        for (int j = 0; j < p.view_count[v]; ++j) {
-            double r[2], JE[2][kE], JF[2][kFA];
-            const int o = p.view_offset[v] + j;
-            if (w && !(w[n + j] > 0.0)) continue;
-            corner_residual_jacobian(vc, p.board_xy[2 * j], p.board_xy[2 * j + 1], p.obs_u[o], p.obs_v[o], r, JE, JF);
-            if (w) { sq += w[n + j] * (r[0] * r[0] + r[1] * r[1]); wsum += w[n + j]; }
-            else sq += r[0] * r[0] + r[1] * r[1];
-        }
-        n += p.view_count[v];
-    }
-    if (w) return wsum > 0.0 ? std::sqrt(sq / wsum) : 0.0;
-    return n ? std::sqrt(sq / (double)n) : 0.0;
-}
-
-// weights: [n_problems] pointers to the problems' corner weights (entries may be NULL), or NULL for none
-static int solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in, const unsigned short *fixed,
-                            const double *const *weights, int loss_kind, double loss_scale, tscm_summary *summaries)
-{
-    const double t_call = wall();
-    if (!summaries) return fail(TSCM_E_INVALID, "summaries is NULL");
-    tscm_options opt;
-    if (int rc = read_options(opt_in, 1, opt)) return rc;
-    BatchPlan bp;
-    {
-        std::string err;
-        if (int rc = plan_batch(problems, n_problems, opt, fixed, loss_kind, loss_scale, bp, err)) return fail(rc, err);
-    }
-    const LossArg loss = bp.loss;
-    // corner weights: checked per problem before any device is touched; w_sum / n_kept of each for its summary
-    bool any_w = false;
-    std::vector<double> w_sum(n_problems, 0.0);
-    std::vector<long> n_kept(n_problems, 0);
-    for (int i = 0; weights && i < n_problems; ++i) {
-        if (!weights[i]) continue;
-        if (int rc = check_corner_weights(problems[i].view_count, problems[i].n_views, weights[i], &w_sum[i], &n_kept[i]))
-            return fail(rc, "problem " + std::to_string(i) + ": " + g_err);
-        any_w = true;
-    }
-    if (int rc = select_device(device, "tscm_solve_mono_batch")) return rc;
-    for (int i = 0; i < n_problems; ++i) std::memset(&summaries[i], 0, sizeof(tscm_summary));
-
-    const int K = bp.K, nc = (int)bp.chunk.size(), ns = (int)bp.slot_prob.size(), B = bp.B;
-    double seconds_solve = 0.0;
-    if (K > 0) {
-        // ---- upload: concatenated observations (slot order), boards, intrinsics; both parameter buffers hold the start point
-        std::vector<double> ou((size_t)bp.N), ov((size_t)bp.N), intr((size_t)9 * K), board((size_t)6 * B, 0.0);
-        for (int s = 0; s < ns; ++s) {
-            const tscm_problem &p = problems[bp.dev_prob[bp.slot_prob[s]]];
-            const int v = bp.slot_view[s];
-            for (int j = 0; j < bp.slot_count[s]; ++j) { ou[bp.slot_obs[s] + j] = p.obs_u[p.view_offset[v] + j]; ov[bp.slot_obs[s] + j] = p.obs_v[p.view_offset[v] + j]; }
-        }
-        // the weights in slot order (a problem without weights: 1); a masked corner's observation is uploaded as 0, 0
-        std::vector<double> ow(any_w ? (size_t)bp.N : 0);
-        for (int k = 0; any_w && k < K; ++k) {
-            const tscm_problem &p = problems[bp.dev_prob[k]];
-            std::vector<CornerRun> runs;
-            for (int s = bp.slot_ptr[k]; s < bp.slot_ptr[k + 1]; ++s) runs.push_back(CornerRun{ bp.slot_view[s], bp.slot_obs[s], bp.slot_count[s] });
-            scatter_weights(weights[bp.dev_prob[k]], p.view_count, p.n_views, runs, ow.data(), ou.data(), ov.data());
-        }
-        for (int k = 0; k < K; ++k) {
-            const tscm_problem &p = problems[bp.dev_prob[k]];
-            std::memcpy(&intr[9 * (size_t)k], p.intr, 9 * sizeof(double));
-            if (p.n_boards) std::memcpy(&board[6 * (size_t)bp.board_ptr[k]], p.board_rt, 6 * sizeof(double) * p.n_boards);
-        }
-        std::vector<int4> chunk(nc);
-        for (int c = 0; c < nc; ++c) chunk[c] = make_int4(bp.chunk[c].x, bp.chunk[c].y, bp.chunk[c].z, 0);
-
-        DeviceMem A;
-        MbDev D{};
-        D.K = K; D.n_points = bp.n_points; D.n_chunks = nc; D.n_slots = ns; D.loss = loss;
-        char *d_ctrl = nullptr;
-        const size_t ctrl_bytes = sizeof(CtrlHead) * (size_t)K + sizeof(IterLog) * (size_t)kMaxLog * K;
-        HIP_TRY(A.upload(&D.board_xy, problems[0].board_xy, 2 * (size_t)bp.n_points));
-        HIP_TRY(A.upload(&D.obs_u, ou)); HIP_TRY(A.upload(&D.obs_v, ov));
-        if (any_w) HIP_TRY(A.upload(&D.obs_w, ow));
-        HIP_TRY(A.upload(&D.chunk, chunk));
-        HIP_TRY(A.upload(&D.chunk_ptr, bp.chunk_ptr)); HIP_TRY(A.upload(&D.board_ptr, bp.board_ptr));      // [K + 1]
-        HIP_TRY(A.upload(&D.slot_board, bp.slot_board)); HIP_TRY(A.upload(&D.slot_obs, bp.slot_obs));      // [ns]
-        HIP_TRY(A.upload(&D.slot_count, bp.slot_count)); HIP_TRY(A.upload(&D.slot_active, bp.slot_active));
-        HIP_TRY(A.upload(&D.mask, bp.mask));                                                                // [K]
-        for (int b = 0; b < 2; ++b) {
-            HIP_TRY(A.upload(&D.intr[b], intr)); HIP_TRY(A.upload(&D.board[b], board));
-            HIP_TRY(A.alloc(&D.rec[b], (size_t)kMbRec * ns)); HIP_TRY(A.alloc(&D.part[b], (size_t)kMbPart * nc)); HIP_TRY(A.alloc(&D.tot[b], (size_t)kMbTot * K));
-        }
-        HIP_TRY(A.alloc(&D.schur, (size_t)kMbSp * nc)); HIP_TRY(A.alloc(&D.solvep, 4 * (size_t)nc)); HIP_TRY(A.alloc(&D.cam_mp, 4 * (size_t)K));
-        HIP_TRY(A.alloc(&D.s_b, 6 * (size_t)ns)); HIP_TRY(A.alloc(&D.s_f, 7 * (size_t)K));
-        HIP_TRY(A.alloc(&d_ctrl, ctrl_bytes)); HIP_TRY(A.alloc(&D.n_done, 1)); HIP_TRY(A.alloc(&D.out, 9 * (size_t)K + 6 * (size_t)B));
-        D.head = reinterpret_cast<CtrlHead *>(d_ctrl);
-        D.log = reinterpret_cast<IterLog *>(d_ctrl + sizeof(CtrlHead) * (size_t)K);
-
-        // ---- the loop: four launches per iteration for the whole batch; the host polls the count of terminated problems
-        MbStream ms;
-        HIP_TRY(hipStreamCreateWithFlags(&ms.s, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&ms.e0)); HIP_TRY(hipEventCreate(&ms.e1));
-        const hipStream_t st = ms.s;
-        const CtrlHead head = ctrl_head_from_options(opt);
-        const size_t lds_eval = sizeof(double) * (2 * kMbJw + 1) * (size_t)bp.n_points;
-        HIP_TRY(hipEventRecord(ms.e0, st));
-        hipLaunchKernelGGL(k_mb_begin, dim3((K + 255) / 256), dim3(256), 0, st, D, head);
-        hipLaunchKernelGGL(k_mb_eval, dim3(nc), dim3(kMbThreads), lds_eval, st, D, 1);
-        hipLaunchKernelGGL(k_mb_control, dim3(K), dim3(64), 0, st, D, 1);
-        HIP_TRY(hipGetLastError());
-        const int check_every = std::max(1, opt.check_every);
-        for (int it = 1; it <= opt.max_num_iterations; ++it) {
-            hipLaunchKernelGGL(k_mb_schur, dim3(nc), dim3(kMbThreads), 0, st, D);
-            hipLaunchKernelGGL(k_mb_solve, dim3(nc), dim3(kMbThreads), 0, st, D);
-            hipLaunchKernelGGL(k_mb_eval, dim3(nc), dim3(kMbThreads), lds_eval, st, D, 0);
-            hipLaunchKernelGGL(k_mb_control, dim3(K), dim3(64), 0, st, D, 0);
-            HIP_TRY(hipGetLastError());
-            if (it % check_every == 0 && it < opt.max_num_iterations) {
-                int done = 0;
-                HIP_TRY(hipMemcpyAsync(&done, D.n_done, sizeof(int), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (done >= K) break;
-            }
-        }
-        hipLaunchKernelGGL(k_mb_finish, dim3(K), dim3(256), 0, st, D);
-        HIP_TRY(hipEventRecord(ms.e1, st));
-        std::vector<double> out(9 * (size_t)K + 6 * (size_t)B);
-        std::vector<char> ctrl(ctrl_bytes);
-        HIP_TRY(hipMemcpyAsync(out.data(), D.out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ctrl.data(), d_ctrl, ctrl_bytes, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipGetLastError());
-        float ms_solve = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms_solve, ms.e0, ms.e1));
-        seconds_solve = 1e-3 * (double)ms_solve;
-
-        // ---- results: parameters in place, one summary per problem
-        const CtrlHead *heads = reinterpret_cast<const CtrlHead *>(ctrl.data());
-        const IterLog *logs = reinterpret_cast<const IterLog *>(ctrl.data() + sizeof(CtrlHead) * (size_t)K);
-        for (int k = 0; k < K; ++k) if (!heads[k].done) return fail(TSCM_E_HIP, "device LM loop of a batch problem did not terminate");
-        for (int k = 0; k < K; ++k) {
-            const int i = bp.dev_prob[k];
-            const tscm_problem &p = problems[i];
-            const CtrlHead &h = heads[k];
-            tscm_summary *sum = &summaries[i];
-            std::memcpy(p.intr, &out[9 * (size_t)k], 9 * sizeof(double));
-            if (p.n_boards) std::memcpy(p.board_rt, &out[9 * (size_t)K + 6 * (size_t)bp.board_ptr[k]], 6 * sizeof(double) * p.n_boards);
-            const long N_k = bp.obs_ptr[k + 1] - bp.obs_ptr[k];
-            fill_summary(h, logs + (size_t)kMaxLog * k, N_k, sum);
-            const double *w = weights ? weights[i] : nullptr;
-            if (w) {
-                sum->n_residual_blocks = (int)n_kept[i];
-                sum->rmse = w_sum[i] > 0.0 ? std::sqrt(2.0 * h.x_cost / w_sum[i]) : 0.0;
-            }
-            if (loss.kind != TSCM_LOSS_NONE) sum->rmse = mb_pixel_rmse(p, w);
-        }
-    }
-    // problems without a single corner: what the single-problem entry point returns for them
-    for (int i = 0; i < n_problems; ++i) {
-        if (bp.dev_of[i] >= 0) continue;
-        if (int rc = solve_configured(&problems[i], opt_in, SolveSpec{ loss, fixed ? fixed + i : nullptr, nullptr, nullptr }, &summaries[i])) return rc;
-    }
-    // the batch's times in every summary
-    const double t_end = wall();
-    for (int i = 0; i < n_problems; ++i) { summaries[i].seconds_total = t_end - t_call; summaries[i].seconds_solve = seconds_solve; }
-    return 0;
-}
-
-extern "C" int tscm_solve_mono_batch(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in,
-                                     const unsigned short *fixed, int loss_kind, double loss_scale, tscm_summary *summaries)
-{
-    return solve_mono_batch(problems, n_problems, device, opt_in, fixed, nullptr, loss_kind, loss_scale, summaries);
-}
-
-extern "C" int tscm_solve_mono_batch_weighted(const tscm_problem *problems, int n_problems, int device, const tscm_options *opt_in,
-                                              const unsigned short *fixed, const double *const *weights, int loss_kind, double loss_scale,
-                                              tscm_summary *summaries)
-{
-    return solve_mono_batch(problems, n_problems, device, opt_in, fixed, weights, loss_kind, loss_scale, summaries);
-}
-
-// ------------------------------------------------------------------------------------------------
-// multi-GPU
-// ------------------------------------------------------------------------------------------------
-static_assert(sizeof(ncclUniqueId) <= TSCM_UNIQUE_ID_BYTES, "ncclUniqueId larger than the ABI buffer");
-
-extern "C" int tscm_comm_unique_id(unsigned char id[TSCM_UNIQUE_ID_BYTES])
-{
-    if (!id) return fail(TSCM_E_INVALID, "id is NULL");
-    ncclUniqueId u;
-    NCCL_TRY(ncclGetUniqueId(&u));
-    std::memset(id, 0, TSCM_UNIQUE_ID_BYTES);
-    std::memcpy(id, &u, sizeof(u));
-    return 0;
-}
-
-extern "C" int tscm_comm_create(const unsigned char id[TSCM_UNIQUE_ID_BYTES], int rank, int world, int device, tscm_comm **out)
-{
-    if (!id || !out || world < 1 || rank < 0 || rank >= world) return fail(TSCM_E_INVALID, "bad communicator arguments");
-    *out = nullptr;
-    if (int rc = select_device(device, "tscm_comm_create")) return rc;
-    ncclUniqueId u;
-    std::memcpy(&u, id, sizeof(u));
-    std::unique_ptr<tscm_comm> c(new tscm_comm);
-    c->rank = rank; c->world = world; c->device = device;
-    NCCL_TRY(ncclCommInitRank(&c->comm, world, u, rank));
-    *out = c.release();
-    return 0;
-}
-
-extern "C" int tscm_comm_create_local(int world, int device, tscm_comm **out)
-{
-    if (!out || world < 1) return fail(TSCM_E_INVALID, "bad communicator arguments");
-    for (int r = 0; r < world; ++r) out[r] = nullptr;
-    if (int rc = select_device(device, "tscm_comm_create_local")) return rc;
-    std::unique_ptr<tscm_local_group> g(new tscm_local_group);
-    g->world = world; g->device = device;
-    HIP_TRY(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    if (g->mem.alloc(&g->d_ptrs, 2 * (size_t)world) != hipSuccess) return fail(TSCM_E_NOMEM, "hipMalloc of the group's pointer table failed");
-    for (int r = 0; r < world; ++r) {
-        tscm_comm *c = new tscm_comm;
-        c->rank = r; c->world = world; c->device = device; c->group = g.get();
-        out[r] = c;
-    }
-    g->refs = world;
-    g.release();
-    return 0;
-}
-
-struct IpcIdent { int pci[3]; int fine; };
-static_assert(sizeof(hipIpcMemHandle_t) + sizeof(IpcIdent) <= TSCM_IPC_HANDLE_BYTES, "hipIpcMemHandle_t + identity larger than the ABI buffer");
-
-extern "C" int tscm_comm_ipc_open(int rank, int world, int device, size_t max_doubles, tscm_comm **out, unsigned char handle[TSCM_IPC_HANDLE_BYTES])
-{
-    if (!out || !handle || world < 1 || world > kIpcMaxWorld || rank < 0 || rank >= world || max_doubles == 0) return fail(TSCM_E_INVALID, "bad communicator arguments (IPC: up to 16 ranks)");
-    *out = nullptr;
-    if (int rc = select_device(device, "tscm_comm_ipc_open")) return rc;
-    std::unique_ptr<tscm_comm> c(new tscm_comm);
-    std::unique_ptr<tscm_ipc> x(new tscm_ipc);
-    c->rank = rank; c->world = world; c->device = device;
-    x->rank = rank; x->world = world; x->max_doubles = (max_doubles + 1) & ~(size_t)1;
-    if (x->mem.alloc(&x->d_fault, 1) != hipSuccess) return fail(TSCM_E_NOMEM, "hipMalloc failed");
-    hipIpcMemHandle_t h;
-    // fine-grained first (what a peer on ANOTHER device needs for its system-scope flag stores and my loads of them to meet);
-    // where that cannot be had or exported, ordinary device memory -- enough for ranks that share this device, and the handle
-    // says so: a peer on another device then refuses to connect
-    hipError_t e = hipErrorUnknown;
-    char *own = nullptr;
-    for (int attempt = 0; attempt < 2 && e != hipSuccess; ++attempt) {
-        x->fine = attempt == 0;
-        if (x->fine) {
-            e = hipExtMallocWithFlags(reinterpret_cast<void **>(&own), x->total_bytes(), hipDeviceMallocFinegrained);
-            if (e == hipSuccess) x->mem.adopt(own);
-        } else {
-            e = x->mem.alloc(&own, x->total_bytes());
-        }
-        if (e != hipSuccess) { (void)hipGetLastError(); continue; }
-        e = hipMemset(own, 0, x->total_bytes());
-        if (e == hipSuccess) e = hipMemset(x->d_fault, 0, sizeof(int));
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e == hipSuccess) e = hipIpcGetMemHandle(&h, own);
-        if (e != hipSuccess) { x->mem.release(own); (void)hipGetLastError(); }
-    }
-    if (e != hipSuccess) {
-        return fail(TSCM_E_HIP, std::string("IPC exchange buffer: ") + hipGetErrorString(e) + " (hipIpcGetMemHandle needs HSA_ENABLE_IPC_MODE_LEGACY=0 on hosts whose driver only supports dmabuf IPC)");
-    }
-    std::memset(handle, 0, TSCM_IPC_HANDLE_BYTES);
-    std::memcpy(handle, &h, sizeof(h));
-    {
-        // behind the HIP handle: which device the buffer lives on (PCI address: ordinals differ between processes) and its kind
-        IpcIdent id{};
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        id.pci[0] = prop.pciDomainID; id.pci[1] = prop.pciBusID; id.pci[2] = prop.pciDeviceID; id.fine = x->fine ? 1 : 0;
-        std::memcpy(handle + sizeof(h), &id, sizeof(id));
-    }
-    x->mapped[rank] = own;
-    g_err = x->fine ? "note: IPC exchange buffer in fine-grained device memory" : "note: IPC exchange buffer in ordinary device memory (ranks on this device only)";
-    c->ipc = x.release();
-    *out = c.release();
-    return 0;
-}
-
-extern "C" int tscm_comm_ipc_connect(tscm_comm *c, const unsigned char *handles)
-{
-    if (!c || !c->ipc || !handles) return fail(TSCM_E_INVALID, "not an IPC communicator");
-    tscm_ipc *x = c->ipc;
-    if (x->connected) return fail(TSCM_E_INVALID, "already connected");
-    HIP_TRY(hipSetDevice(c->device));
-    IpcIdent me{};
-    std::memcpy(&me, handles + (size_t)TSCM_IPC_HANDLE_BYTES * x->rank + sizeof(hipIpcMemHandle_t), sizeof(me));
-    for (int r = 0; r < x->world; ++r) {
-        if (r == x->rank) continue;
-        hipIpcMemHandle_t h;
-        IpcIdent id{};
-        std::memcpy(&h, handles + (size_t)TSCM_IPC_HANDLE_BYTES * r, sizeof(h));
-        std::memcpy(&id, handles + (size_t)TSCM_IPC_HANDLE_BYTES * r + sizeof(h), sizeof(id));
-        if (std::memcmp(id.pci, me.pci, sizeof(id.pci)) != 0) {
-            // a peer on another device: both buffers fine-grained, and peer access enabled here and now (not lazily)
-            if (!id.fine || !x->fine) return fail(TSCM_E_UNSUPPORTED, "IPC exchange across devices needs fine-grained exchange buffers on both ranks (one of them is ordinary device memory): put the ranks on one device or use RCCL");
-            const int ndev = tscm_device_count();
-            int peer = -1;
-            for (int d = 0; d < ndev && peer < 0; ++d) {
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, d));
-                if (prop.pciDomainID == id.pci[0] && prop.pciBusID == id.pci[1] && prop.pciDeviceID == id.pci[2]) peer = d;
-            }
-            if (peer < 0) return fail(TSCM_E_UNSUPPORTED, "IPC exchange: a peer rank's device is not visible to this process (HIP_VISIBLE_DEVICES): no peer access");
-            int can = 0;
-            HIP_TRY(hipDeviceCanAccessPeer(&can, c->device, peer));
-            if (!can) return fail(TSCM_E_UNSUPPORTED, "IPC exchange: no peer access between this rank's device and a peer rank's");
-            const hipError_t pe = hipDeviceEnablePeerAccess(peer, 0);
-            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) { HIP_TRY(pe); }
-            (void)hipGetLastError();
-        }
-        HIP_TRY(hipIpcOpenMemHandle(&x->mapped[r], h, hipIpcMemLazyEnablePeerAccess));
-    }
-    x->connected = true;
-    return 0;
-}
-
-extern "C" int tscm_comm_info(const tscm_comm *c, int *rank, int *world, int *backend_ranks)
-{
-    if (!c) return fail(TSCM_E_INVALID, "communicator is NULL");
-    if (rank) *rank = c->rank;
-    if (world) *world = c->world;
-    if (backend_ranks) {
-        int n = c->group ? c->group->world : c->ipc && c->ipc->connected ? c->ipc->world : 0;
-        if (c->comm) NCCL_TRY(ncclCommCount(c->comm, &n));      // what RCCL itself reports for the communicator
-        *backend_ranks = n;
-    }
-    return 0;
-}
-
-extern "C" void tscm_comm_destroy(tscm_comm *c)
-{
-    if (!c) return;
-    if (c->comm) (void)ncclCommDestroy(c->comm);
-    if (c->ipc) {
-        (void)hipSetDevice(c->device);
-        (void)hipDeviceSynchronize();
-        for (int r = 0; r < c->ipc->world; ++r) if (r != c->ipc->rank && c->ipc->mapped[r]) (void)hipIpcCloseMemHandle(c->ipc->mapped[r]);
-        delete c->ipc;                  // (its DeviceMem frees the buffer and the fault word)
-    }
-    if (c->group && --c->group->refs == 0) {
-        (void)hipSetDevice(c->group->device);
-        (void)hipStreamSynchronize(c->group->stream);
-        delete c->group;                // (frees the pointer table, destroys the stream)
-    }
-    delete c;
 }
 
 extern "C" int tscm_shard_frames(const tscm_problem *p, int world, int *owner)
