@@ -5,8 +5,11 @@
 // for a frame the camera has no image of.  The viewer and the drawing calls of main.cpp are left out.
 //   usage: calibrate_from_images list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha]
 //                                [--prior name:sigma[,name:sigma...]] [--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]]
-//                                [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]]
-//   (--model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
+//                                [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]] [--device-boards]
+//   (--device-boards: tscm::findCorners instead of findCorner per image -- a camera's images are detected and their boards
+//    recovered in two calls, the structure recovery as one batch on the device, and the remapped boards of the refinement pass
+//    likewise.
+//    --model ds | ucm: Double Sphere (lambda held at 0) / Unified Camera Model (xi and lambda held at 0) in every solve; the
 //    YAML keeps the 9-vector with those entries 0.  --fix: further intrinsics held at their start values in every solve.
 //    --prior: Gaussian priors (Ceres' NormalPrior, tscm.h) on the named intrinsics of every camera, in every solve, about the
 //    values that solve starts from; sigma in the parameter's unit against a corner sigma of one pixel; names as for --fix.
@@ -25,6 +28,7 @@
 #include <fstream>
 #include <iostream>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -58,25 +62,51 @@ bool board_corners(const tscm::Chessboarder_t &found, tscm::Size board, std::vec
 }
 
 // main.cpp:8-130
-void monocular_calib(const std::vector<Image> &images, double size, tscm::Size board, const std::vector<tscm::Point3d> &worlds, tscm::TripleSphereCamera &cam)
+void monocular_calib(const std::vector<Image> &images, double size, tscm::Size board, const std::vector<tscm::Point3d> &worlds, tscm::TripleSphereCamera &cam,
+                     bool device_boards)
 {
     const int V = (int)images.size();
     std::vector<std::vector<tscm::Point2d> > pixels(V);
     std::vector<bool> has(V, false);
     tscm::Size img_size = { 0, 0 };
+    std::vector<int> which;                                                    // --device-boards: the images of one batch
+    std::vector<const unsigned char *> batch;
     for (int i = 0; i < V; ++i) {                                              // :24-50
         if (!images[i].ok()) continue;
         img_size.width = images[i].w; img_size.height = images[i].h;
+        if (device_boards) { which.push_back(i); batch.push_back(images[i].pix.data()); continue; }
         has[i] = board_corners(tscm::findCorner(images[i].pix.data(), images[i].w, images[i].h, images[i].w, 4, cam.device()), board, pixels[i]);
     }
+    if (device_boards && !batch.empty()) {
+        for (int i : which)
+            if (images[i].w != img_size.width || images[i].h != img_size.height) throw std::runtime_error("--device-boards: a camera's images must have one size");
+        const std::vector<tscm::Chessboarder_t> found = tscm::findCorners(batch, img_size.width, img_size.height, img_size.width, 4, cam.device());
+        for (size_t k = 0; k < which.size(); ++k) has[which[k]] = board_corners(found[k], board, pixels[which[k]]);
+    }
     cam.calibrate(pixels, has, worlds, img_size, board);                       // :57
-    for (int i = 0; i < V; ++i) {                                              // :59-126 refinement pass
+    std::vector<std::vector<unsigned char> > chesses(V);                       // :59-126 refinement pass: the remapped boards
+    std::vector<tscm::Size> sizes(V, tscm::Size{ 0, 0 });
+    std::vector<tscm::Chessboarder_t> remapped(V);
+    which.clear(); batch.clear();
+    for (int i = 0; i < V; ++i) {
         if (!has[i]) continue;
-        std::vector<unsigned char> chess;
-        const tscm::Size cs = cam.undistort_chessboard(images[i].pix.data(), images[i].w, images[i].h, images[i].w, 1, i, board, size, chess);
+        sizes[i] = cam.undistort_chessboard(images[i].pix.data(), images[i].w, images[i].h, images[i].w, 1, i, board, size, chesses[i]);
+        if (sizes[i].width == 0) continue;
+        if (device_boards) { which.push_back(i); batch.push_back(chesses[i].data()); }
+        else remapped[i] = tscm::findCorner(chesses[i].data(), sizes[i].width, sizes[i].height, sizes[i].width, 4, cam.device());
+    }
+    if (device_boards && !batch.empty()) {                                     // (the remapped boards of one board size have one size)
+        const tscm::Size cs = sizes[which[0]];
+        const std::vector<tscm::Chessboarder_t> found = tscm::findCorners(batch, cs.width, cs.height, cs.width, 4, cam.device());
+        for (size_t k = 0; k < which.size(); ++k) remapped[which[k]] = found[k];
+    }
+    for (int i = 0; i < V; ++i) {
+        if (!has[i]) continue;
+        const std::vector<unsigned char> &chess = chesses[i];
+        const tscm::Size cs = sizes[i];
         if (cs.width == 0) continue;
         std::vector<tscm::Point2d> refined;
-        if (board_corners(tscm::findCorner(chess.data(), cs.width, cs.height, cs.width, 4, cam.device()), board, refined)) {
+        if (board_corners(remapped[i], board, refined)) {
             const tscm::Mat33 &Rt = cam.Rt(i);                                 // :92-105: back through [r1 r2 t] and project()
             std::vector<tscm::Point3d> P(refined.size());
             for (size_t k = 0; k < refined.size(); ++k) {
@@ -107,7 +137,7 @@ int main(int argc, char **argv)
     unsigned short model = 0, fix = 0;              // --model (the last one counts), --fix (accumulates)
     bool use_prior = false;                         // --prior (the last one counts)
     double prior_sigma[7] = { 0, 0, 0, 0, 0, 0, 0 };
-    bool bad_args = false, use_ransac = false, ransac_mask = false;
+    bool bad_args = false, use_ransac = false, ransac_mask = false, device_boards = false;
     tscm_ransac_params ransac;
     tscm_ransac_default_params(&ransac);
     tscm::ResidualOptions residual;
@@ -130,13 +160,15 @@ int main(int argc, char **argv)
             bad_args = true;
         } else if (!std::strcmp(argv[i], "--ransac-mask")) {
             ransac_mask = true;
+        } else if (!std::strcmp(argv[i], "--device-boards")) {
+            device_boards = true;
         } else {
             pos.push_back(argv[i]);
         }
     }
     if (bad_args || pos.size() < 2 || (ransac_mask && !use_ransac)) {
         std::fprintf(stderr, "usage: %s list.txt calib.yaml [cols rows pitch] [--model ts|ds|ucm] [--fix fx,fy,cx,cy,xi,lambda,alpha] [--prior name:sigma[,name:sigma...]] "
-                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]]\n", argv[0]);
+                     "[--ransac THRESHOLD[,HYPOTHESES[,MIN_INLIERS]] [--ransac-mask]] [--residuals[=FILE]] [--residual-bins K] [--prune K[,ROUNDS[,MAX_FRACTION]]] [--device-boards]\n", argv[0]);
         return 2;
     }
     const unsigned short fixed = (unsigned short)(model | fix);
@@ -165,7 +197,7 @@ int main(int argc, char **argv)
             cameras[m].set_fixed_intrinsics(fixed);                            // (the first calibrate starts at xi = lambda = 0)
             if (use_prior) cameras[m].set_prior_sigmas(prior_sigma);
             if (use_ransac) cameras[m].set_ransac(&ransac, ransac_mask);
-            monocular_calib(images[m], size, board, worlds, cameras[m]);
+            monocular_calib(images[m], size, board, worlds, cameras[m], device_boards);
             if (use_prior) tscm::print_effective_priors(cameras[m].last_priors_, 0, (int)m, fixed, "mono");
             if (ransac_mask) tscm::print_ransac_masked(cameras[m], (int)m);
         }

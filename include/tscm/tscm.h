@@ -1244,6 +1244,44 @@ typedef struct tscm_chessboards {
 int tscm_chessboards_from_corners(int n, const double *x, const double *y, const double *v1, const double *v2, tscm_chessboards *out);
 void tscm_chessboards_free(tscm_chessboards *b);
 
+/* The structure recovery for a batch of images, one independent job per (image, seed candidate), from ONE definition
+ * for host and device (tscm_boards_core.h).  That definition is the function above operation by
+ * operation except for the extrapolation of three corners p1, p2, p3, which it states without atan2 / cos / sin so that
+ * host and device agree on every bit: a = p2 - p1, b = p3 - p2, (c1, s1) = a / |a|, (c2, s2) = b / |b| (each (1, 0) for
+ * a zero vector), cc = c2 c2 - s2 s2, ss = 2 c2 s2, cos a3 = cc c1 + ss s1, sin a3 = ss c1 - cc s1,
+ * pred = p3 + 0.75 (2 |b| - |a|) (cos a3, sin a3); no fused multiply-add, IEEE sqrt and division.  The final boards are
+ * those of the function above unless two candidates lie at exactly the same distance from a prediction of a winning
+ * proposal.  where = TSCM_BOARDS_HOST runs the serial instantiation and needs no device; TSCM_BOARDS_DEVICE runs the
+ * kernel k_board_seeds, and passes an image of more than TSCM_BOARDS_MAX_DEVICE_CANDIDATES candidates through the host
+ * instantiation (the same definition, the same result).  Of a candidate record only n, x, y, v1, v2 are read.
+ * Refused with TSCM_E_INVALID: NULL cands (with n_images > 0) or out, a NULL list of an image with n > 0, a negative
+ * n_images or n, an unknown `where`, a coordinate that is not finite or beyond 32767 in magnitude (where the integer
+ * squares of the energy's column terms end); more than 65535 candidates are TSCM_E_UNSUPPORTED as above.  n_images = 0
+ * and images with n < 9 give empty results.  out[n_images], each freed with the matching free function.  device_index:
+ * as `device` elsewhere, read by a device call only (TSCM_E_NO_DEVICE outside the range of tscm_device_count).
+ * The stages are the jobs' records per image, in seed order: status (0 blank seed, 1 seed energy > 0, 2 grown, but
+ * energy not < -10, 3 board offered to the overlap resolution), rows x cols, accepted growth steps, energy and the
+ * row-major cells of the board before the turn (none for status 0, the seed for status 1).  The boards of the batch
+ * call are the status-3 records that the ordered overlap resolution keeps, turned so that cols >= rows. */
+#define TSCM_BOARDS_HOST   0
+#define TSCM_BOARDS_DEVICE 1
+#define TSCM_BOARDS_MAX_DEVICE_CANDIDATES 1024
+typedef struct tscm_board_seed_stages {
+    int n;                  /* seeds = candidates of the image                          */
+    int on_device;          /* 1: the image's jobs ran in the kernel                    */
+    int *status;            /* [n]                                                      */
+    int *rows, *cols;       /* [n] 0 x 0 for status 0, 3 x 3 for status 1               */
+    int *steps;             /* [n] rows + cols - 6 for status 2 and 3                   */
+    double *energy;         /* [n] 0 for status 0                                       */
+    int *offset;            /* [n + 1] start of each record's cells                     */
+    int *cells;             /* candidate indices                                        */
+} tscm_board_seed_stages;
+int tscm_chessboards_from_corners_batch(int n_images, const tscm_corner_candidates *cands, int where, int device_index, tscm_chessboards *out);
+int tscm_chessboards_batch_stages(int n_images, const tscm_corner_candidates *cands, int where, int device_index, tscm_board_seed_stages *out);
+void tscm_board_seed_stages_free(tscm_board_seed_stages *s);
+/* device time of k_board_seeds in the calling thread's last device call, seconds (0 after a host call) */
+double tscm_chessboards_batch_seconds(void);
+
 /* ------------------------------------------------------------------ stereo matching on a rectified pair
  * What the rectified pair of tscm_build_maps_ex + tscm_remap is for: matching along rows (PERSPECTIVE or LONGLAT tables of
  * rectify_pair_descs / rectify_pair_maps, where a scene point lies on the same row of both images) and the 3-D points of

@@ -1335,13 +1335,9 @@ struct Chessboarder_t {
     std::vector<IndexMat> chessboard;
 };
 
-inline Chessboarder_t findCorner(const unsigned char *gray, int width, int height, int stride, int sigma, int device = 0)
+// candidates and boards of one image as the reference's Chessboarder_t: a board member's point is its sub-pixel position
+inline Chessboarder_t chessboarder_of(const tscm_corner_candidates &c, const tscm_chessboards &b)
 {
-    tscm_corner_candidates c;
-    check(tscm_detect_corners(gray, width, height, stride, sigma, 0.01, device, &c));
-    tscm_chessboards b;
-    const int rc = tscm_chessboards_from_corners(c.n, c.x, c.y, c.v1, c.v2, &b);
-    if (rc != 0) { tscm_corner_candidates_free(&c); check(rc); }
     Chessboarder_t out;
     for (int i = 0; i < c.n; ++i) {
         out.corners.p.push_back(Point2d{ c.x[i], c.y[i] });
@@ -1359,8 +1355,43 @@ inline Chessboarder_t findCorner(const unsigned char *gray, int width, int heigh
         }
         out.chessboard.push_back(m);
     }
+    return out;
+}
+
+inline Chessboarder_t findCorner(const unsigned char *gray, int width, int height, int stride, int sigma, int device = 0)
+{
+    tscm_corner_candidates c;
+    check(tscm_detect_corners(gray, width, height, stride, sigma, 0.01, device, &c));
+    tscm_chessboards b;
+    const int rc = tscm_chessboards_from_corners(c.n, c.x, c.y, c.v1, c.v2, &b);
+    if (rc != 0) { tscm_corner_candidates_free(&c); check(rc); }
+    const Chessboarder_t out = chessboarder_of(c, b);
     tscm_chessboards_free(&b);
     tscm_corner_candidates_free(&c);
+    return out;
+}
+
+// findCorner for a batch of images of one size in two calls: tscm_detect_corners_batch, then the structure recovery of all
+// of them as independent (image, seed) jobs -- where = TSCM_BOARDS_DEVICE on the device, TSCM_BOARDS_HOST the same
+// definition on the host.  That definition differs from findCorner's recovery in one documented step (tscm.h); the boards
+// agree unless a winning proposal holds an exact tie of two distances.
+inline std::vector<Chessboarder_t> findCorners(const std::vector<const unsigned char *> &images, int width, int height, int stride, int sigma, int device = 0,
+                                               int where = TSCM_BOARDS_DEVICE)
+{
+    const int n = (int)images.size();
+    std::vector<Chessboarder_t> out;
+    if (n == 0) return out;
+    std::vector<tscm_corner_candidates> c((size_t)n);
+    check(tscm_detect_corners_batch(images.data(), n, width, height, stride, sigma, 0.01, device, c.data()));
+    std::vector<tscm_chessboards> b((size_t)n);
+    const int rc = tscm_chessboards_from_corners_batch(n, c.data(), where, device, b.data());
+    if (rc == 0)
+        for (int k = 0; k < n; ++k) {
+            out.push_back(chessboarder_of(c[(size_t)k], b[(size_t)k]));
+            tscm_chessboards_free(&b[(size_t)k]);
+        }
+    for (int k = 0; k < n; ++k) tscm_corner_candidates_free(&c[(size_t)k]);
+    check(rc);
     return out;
 }
 

@@ -126,24 +126,131 @@ def chessboards_from_corners(x, y, v1, v2) -> list:
         fr(C.byref(out))
 
 
-def find_chessboard(gray, cols: int, rows: int, sigma: int = 4, device: int = 0):
+_WHERE = {"host": _l.BOARDS_HOST, "device": _l.BOARDS_DEVICE}
+
+
+def _candidate_records(cands):
+    """Candidate dicts (or (x, y, v1, v2) tuples) as an array of tscm_corner_candidates; only n, x, y, v1, v2 are filled.
+    Returns the arrays kept alive and the records."""
+    keep, recs = [], (_l.CCornerCandidates * max(len(cands), 1))()
+    dp = C.POINTER(C.c_double)
+    for k, c in enumerate(cands):
+        x, y, v1, v2 = (c["x"], c["y"], c["v1"], c["v2"]) if isinstance(c, dict) else c
+        a = [np.ascontiguousarray(x, dtype=np.float64).ravel(), np.ascontiguousarray(y, dtype=np.float64).ravel(),
+             np.ascontiguousarray(v1, dtype=np.float64).ravel(), np.ascontiguousarray(v2, dtype=np.float64).ravel()]
+        n = a[0].shape[0]
+        if a[1].shape[0] != n or a[2].shape[0] != 2 * n or a[3].shape[0] != 2 * n:
+            raise ValueError(f"candidates {k}: x, y of n and v1, v2 of (n, 2) values expected")
+        keep.append(a)
+        recs[k].n = n
+        recs[k].x, recs[k].y, recs[k].v1, recs[k].v2 = (q.ctypes.data_as(dp) for q in a)
+    return keep, recs
+
+
+def _where(where: str) -> int:
+    if where not in _WHERE:
+        raise ValueError(f"where = {where!r}: 'host' or 'device'")
+    return _WHERE[where]
+
+
+def chessboards_from_corners_batch(cands, where: str = "device", device: int = 0) -> list:
+    """tscm_chessboards_from_corners_batch: the structure recovery of a list of candidate sets (the dicts of
+    detect_corners_batch, or (x, y, v1, v2) tuples) in one call, one independent job per (image, seed) -- on the device
+    (k_board_seeds) or, where="host", the same definition on the host.  Returns one list of index matrices per image.  The
+    definition (tscm.h) differs from chessboards_from_corners in one documented step; the boards agree unless a winning
+    proposal holds an exact tie of two distances."""
+    cands = list(cands)
+    keep, recs = _candidate_records(cands)
+    outs = (_l.CChessboards * max(len(cands), 1))()
+    f = _l.lib().tscm_chessboards_from_corners_batch
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    _l.check(f(len(cands), recs, _where(where), int(device), outs))
+    fr = _l.lib().tscm_chessboards_free
+    fr.restype = None
+    fr.argtypes = [C.POINTER(_l.CChessboards)]
+    res = []
+    try:
+        for k in range(len(cands)):
+            o = outs[k]
+            off = np.ctypeslib.as_array(o.offset, shape=(o.n_boards + 1,)) if o.n_boards else np.zeros(1, dtype=np.int32)
+            cells = np.ctypeslib.as_array(o.cells, shape=(int(off[-1]),)).astype(np.int32) if o.n_boards else np.zeros(0, dtype=np.int32)
+            res.append([cells[off[q]:off[q + 1]].reshape(o.rows[q], o.cols[q]).copy() for q in range(o.n_boards)])
+    finally:
+        for k in range(len(cands)):
+            fr(C.byref(outs[k]))
+    return res
+
+
+def chessboards_batch_stages(cands, where: str = "device", device: int = 0) -> list:
+    """tscm_chessboards_batch_stages: per image a dict of the seeds' records in seed order -- status (0 blank seed, 1 seed
+    energy > 0, 2 grown but energy not < -10, 3 offered to the overlap resolution), rows, cols, steps, energy, offset
+    (n + 1) and cells (the boards before the turn, row-major), plus on_device."""
+    cands = list(cands)
+    keep, recs = _candidate_records(cands)
+    outs = (_l.CBoardSeedStages * max(len(cands), 1))()
+    f = _l.lib().tscm_chessboards_batch_stages
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    _l.check(f(len(cands), recs, _where(where), int(device), outs))
+    fr = _l.lib().tscm_board_seed_stages_free
+    fr.restype = None
+    fr.argtypes = [C.POINTER(_l.CBoardSeedStages)]
+    res = []
+    try:
+        for k in range(len(cands)):
+            o, n = outs[k], outs[k].n
+            arr = lambda p, m, dt: np.ctypeslib.as_array(p, shape=(m,)).astype(dt) if m else np.zeros(0, dtype=dt)
+            off = np.ctypeslib.as_array(o.offset, shape=(n + 1,)).astype(np.int32)
+            res.append(dict(n=n, on_device=bool(o.on_device), status=arr(o.status, n, np.int32), rows=arr(o.rows, n, np.int32), cols=arr(o.cols, n, np.int32),
+                            steps=arr(o.steps, n, np.int32), energy=arr(o.energy, n, np.float64), offset=off, cells=arr(o.cells, int(off[-1]), np.int32)))
+    finally:
+        for k in range(len(cands)):
+            fr(C.byref(outs[k]))
+    return res
+
+
+def chessboards_batch_seconds() -> float:
+    """Device time of k_board_seeds in this thread's last device call."""
+    f = _l.lib().tscm_chessboards_batch_seconds
+    f.restype = C.c_double
+    f.argtypes = []
+    return float(f())
+
+
+_RECOVER = ("host", "device", "host-batch")
+
+
+def _recovered(ds, recover: str, device: int) -> list:
+    """The boards of every candidate dict of ds by the route `recover` names."""
+    if recover not in _RECOVER:
+        raise ValueError(f"recover = {recover!r}: one of {_RECOVER}")
+    if recover == "host":
+        return [chessboards_from_corners(d["x"], d["y"], d["v1"], d["v2"]) for d in ds]
+    return chessboards_from_corners_batch(ds, where="device" if recover == "device" else "host", device=device)
+
+
+def find_chessboard(gray, cols: int, rows: int, sigma: int = 4, device: int = 0, recover: str = "host"):
     """The acceptance test of main.cpp:32-46: corner candidates, structure recovery, and -- when exactly one board of
-    cols x rows inner corners came out -- its sub-pixel corners as a (rows * cols, 2) array in board order; else None."""
+    cols x rows inner corners came out -- its sub-pixel corners as a (rows * cols, 2) array in board order; else None.
+    recover: see find_chessboards."""
     d = detect_corners(gray, sigma=sigma, device=device)
-    boards = chessboards_from_corners(d["x"], d["y"], d["v1"], d["v2"])
+    boards = _recovered([d], recover, device)[0]
     if len(boards) != 1 or boards[0].shape != (rows, cols):
         return None
     return d["sub"][boards[0].ravel()]
 
 
-def find_chessboards(images, cols: int, rows: int, sigma: int = 4, device: int = 0, first_board_only: bool = False) -> list:
+def find_chessboards(images, cols: int, rows: int, sigma: int = 4, device: int = 0, first_board_only: bool = False, recover: str = "host") -> list:
     """find_chessboard for a list of images of one size: ONE pass of the detection kernels for all of them
-    (tscm_detect_corners_batch), then the structure recovery per image.  Entries are (rows * cols, 2) arrays or None.
+    (tscm_detect_corners_batch), then the structure recovery.  Entries are (rows * cols, 2) arrays or None.
     Acceptance: exactly one board of rows x cols corners (main.cpp:40-46, the input images); first_board_only: at least
-    one board and board 0 has the right shape (main.cpp:67, the remapped chessboards of the refinement pass)."""
+    one board and board 0 has the right shape (main.cpp:67, the remapped chessboards of the refinement pass).
+    recover: "host" = chessboards_from_corners per image (the default); "device" = one call of
+    chessboards_from_corners_batch for all images on the device; "host-batch" = that definition on the host."""
     out = []
-    for d in detect_corners_batch(images, sigma=sigma, device=device):
-        boards = chessboards_from_corners(d["x"], d["y"], d["v1"], d["v2"])
+    ds = detect_corners_batch(images, sigma=sigma, device=device)
+    for d, boards in zip(ds, _recovered(ds, recover, device)):
         ok = (len(boards) >= 1 if first_board_only else len(boards) == 1) and boards[0].shape == (rows, cols)
         out.append(d["sub"][boards[0].ravel()] if ok else None)
     return out

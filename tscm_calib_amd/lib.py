@@ -259,6 +259,7 @@ EXPORTS = [
     "tscm_sweep_compose_default_params", "tscm_sweep_compose", "tscm_sweep_compose_stages",
     "tscm_sweep_visibility_default_params", "tscm_sweep_visibility", "tscm_sweep_visibility_stages", "tscm_sweep_compose_visible", "tscm_sweep_compose_visible_stages",
     "tscm_ransac_default_params", "tscm_estimate_extrinsic_ransac", "tscm_estimate_extrinsic_ransac_stages",
+    "tscm_chessboards_from_corners_batch", "tscm_chessboards_batch_stages", "tscm_board_seed_stages_free", "tscm_chessboards_batch_seconds",
 ]
 
 
@@ -658,6 +659,15 @@ class CCornerCandidates(C.Structure):
                 ("v1", C.POINTER(C.c_double)), ("v2", C.POINTER(C.c_double)),
                 ("score", C.POINTER(C.c_double)), ("sub", C.POINTER(C.c_double)),
                 ("seconds", C.c_double)]
+
+
+class CBoardSeedStages(C.Structure):
+    """tscm_board_seed_stages (tscm.h)"""
+    _fields_ = [("n", C.c_int), ("on_device", C.c_int), ("status", C.POINTER(C.c_int)), ("rows", C.POINTER(C.c_int)), ("cols", C.POINTER(C.c_int)),
+                ("steps", C.POINTER(C.c_int)), ("energy", C.POINTER(C.c_double)), ("offset", C.POINTER(C.c_int)), ("cells", C.POINTER(C.c_int))]
+
+
+BOARDS_HOST, BOARDS_DEVICE, BOARDS_MAX_DEVICE_CANDIDATES = 0, 1, 1024
 
 
 class CChessboards(C.Structure):

@@ -192,21 +192,22 @@ def _top_left_is_bright(board_img, pitch):
     return g(pitch / 2, pitch / 2) + g(pitch * 3 / 2, pitch * 3 / 2) > g(pitch * 3 / 2, pitch / 2) + g(pitch / 2, pitch * 3 / 2)
 
 
-def _detect(images, cols, rows, sigma, device):
-    """main.cpp:24-50: the grey images, their size, has [V] and the detected corners pu / pv [V, n]."""
+def _detect(images, cols, rows, sigma, device, recover="host"):
+    """main.cpp:24-50: the grey images, their size, has [V] and the detected corners pu / pv [V, n].  recover: the route of the
+    structure recovery (corners.find_chessboards)."""
     n, V = cols * rows, len(images)
     grey = [im if im.ndim == 2 else maps.remap(im, *np.meshgrid(np.arange(im.shape[1], dtype=np.float32), np.arange(im.shape[0], dtype=np.float32)),
                                                 to_gray=True, device=device) for im in images]
     img_size = (grey[0].shape[1], grey[0].shape[0])
     has = np.zeros(V, dtype=np.uint8)
     pu, pv = np.zeros((V, n)), np.zeros((V, n))
-    for i, pts in enumerate(corners.find_chessboards(grey, cols, rows, sigma=sigma, device=device)):     # one batch
+    for i, pts in enumerate(corners.find_chessboards(grey, cols, rows, sigma=sigma, device=device, recover=recover)):     # one batch
         if pts is not None:
             has[i], pu[i], pv[i] = 1, pts[:, 0], pts[:, 1]
     return img_size, has, pu, pv
 
 
-def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device):
+def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device, recover="host"):
     """main.cpp:59-126, the refinement pass on the remapped chessboards with the flip rule (pu / pv in place)."""
     n = cols * rows
     seen = np.flatnonzero(has)
@@ -217,7 +218,8 @@ def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, devi
         board_imgs.append(maps.remap(images[i], mx.reshape(desc.height, desc.width), my.reshape(desc.height, desc.width), to_gray=images[i].ndim == 3,
                                      device=device))
     # (main.cpp:67: the remapped board is rejected only if NO board came out or board 0 has the wrong shape)
-    for i, board_img, pts in zip(seen, board_imgs, corners.find_chessboards(board_imgs, cols, rows, sigma=sigma, device=device, first_board_only=True)):
+    for i, board_img, pts in zip(seen, board_imgs, corners.find_chessboards(board_imgs, cols, rows, sigma=sigma, device=device, first_board_only=True,
+                                                                        recover=recover)):
         if pts is not None:                                                   # :92-105 back through [r1 r2 t] and project()
             P = (Rt[i] @ np.concatenate([pts - pitch, np.ones((n, 1))], axis=1).T).T
             uv = api.project(intr, P, device)
@@ -227,7 +229,7 @@ def _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, devi
 
 
 def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                    fixed=None, ransac=None, mask_outliers=False, priors=None, prune=None) -> dict:
+                    fixed=None, ransac=None, mask_outliers=False, priors=None, prune=None, recover="host") -> dict:
     """main.cpp:8-130 for one camera.  images: list of (H, W) uint8 (or (H, W, 3) BGR) arrays, one per frame.
     loss: the robust loss of both refinements (None: plain least squares, as the reference); model, fixed: the camera model
     and held intrinsics of both refinements (calibrate_camera).
@@ -236,13 +238,15 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
     mask_outliers (with ransac): each of the two refinements takes its own call's inlier mask as its corner mask (calibrate_camera).
     priors: Gaussian priors of both refinements, each about its own start values (calibrate_camera).
     prune: outlier pruning behind the last refinement (calibrate_camera); second then carries residuals, pruned_views, ...
+    recover: the structure recovery behind both detections -- "host" (the default: the sequential function per image), "device"
+    (all images of a detection in one batch on the GPU) or "host-batch" (that definition on the host); corners.find_chessboards.
     Returns intr, Rt [V,3,3], has [V], pix_u / pix_v [V, n] (refined, flip rule applied), the two LM summaries."""
-    img_size, has, pu, pv = _detect(images, cols, rows, sigma, device)
+    img_size, has, pu, pv = _detect(images, cols, rows, sigma, device, recover)
     intr, Rt, first = calibrate_camera(pu, pv, has, cols, rows, pitch, img_size, device, loss=loss, model=model, fixed=fixed,
                                        ransac=ransac, mask_outliers=mask_outliers, priors=priors)                               # :57
     if ransac is not None:
         has = first["ransac"]["has"]
-    _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device)
+    _refine_pixels(images, intr, Rt, has, pu, pv, cols, rows, pitch, sigma, device, recover)
     # :127 -- the second calibrate() of the same object: a converged first refinement left has_init_guess_ set (TS.cpp:78),
     # so it starts from the first-pass intrinsics and only re-estimates the extrinsics
     warm = intr if first["termination_type"] == 0 else None
@@ -255,13 +259,14 @@ def monocular_calib(images, cols: int, rows: int, pitch: float, sigma: int = 4, 
 
 
 def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None,
-                          model="ts", masks=None, ransac=None, mask_outliers=False) -> list:
+                          model="ts", masks=None, ransac=None, mask_outliers=False, recover="host") -> list:
     """monocular_calib for every camera, stage by stage across the cameras: detection, the first calibrate, the refinement
     pass, the second calibrate -- each of the two refinements of all cameras in one batch (api.refinement_batch).
-    masks: [C] mask words (model included); ransac, mask_outliers: as for monocular_calib.  Returns monocular_calib's dict per camera."""
+    masks: [C] mask words (model included); ransac, mask_outliers, recover: as for monocular_calib.  Returns monocular_calib's dict
+    per camera."""
     n_cam = len(images_by_camera)
     masks = np.zeros(n_cam, dtype=np.uint16) if masks is None else masks
-    det = [_detect(imgs, cols, rows, sigma, device) for imgs in images_by_camera]
+    det = [_detect(imgs, cols, rows, sigma, device, recover) for imgs in images_by_camera]
     sizes = [d[0] for d in det]
     has = [d[1] for d in det]
     pu = [d[2] for d in det]
@@ -270,7 +275,7 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
     if ransac is not None:
         has = [f[2]["ransac"]["has"] for f in first]
     for m, imgs in enumerate(images_by_camera):
-        _refine_pixels(imgs, first[m][0], first[m][1], has[m], pu[m], pv[m], cols, rows, pitch, sigma, device)
+        _refine_pixels(imgs, first[m][0], first[m][1], has[m], pu[m], pv[m], cols, rows, pitch, sigma, device, recover)
     warm = [f[0] if f[2]["termination_type"] == 0 else None for f in first]
     second = _calibrate_cameras_batched(pu, pv, has, cols, rows, pitch, sizes, device, warm, loss, model, masks, ransac, mask_outliers)
     out = [dict(intr=second[m][0], Rt=second[m][1], has=has[m], pix_u=pu[m], pix_v=pv[m], first=first[m][2], second=second[m][2])
@@ -282,7 +287,8 @@ def monocular_calib_batch(images_by_camera, cols: int, rows: int, pitch: float, 
 
 
 def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: int = 4, device: int = 0, loss=None, model="ts",
-                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None, suggest=None, prune=None) -> dict:
+                  fixed=None, batch_mono=False, ransac=None, covariance=False, uncertainty=None, mask_outliers=False, priors=None, suggest=None, prune=None,
+                  recover="host") -> dict:
     """main.cpp:196-303: monocular_calib per camera, MultiCalib(cameras, worlds), calibrate().  images_by_camera[m][f] is
     the image of frame f in camera m.  Returns the joint problem (intr, cam_rt, board_rt), the per-camera results
     and the LM summary; write the YAML with calib_io.write_calib_yaml.  loss: the robust loss of every solve (None: as the reference).
@@ -313,17 +319,19 @@ def calibrate_rig(images_by_camera, cols: int, rows: int, pitch: float, sigma: i
     (api.view_outliers, api.corner_outliers) -> solve again from the solved parameters with the pruned weights (prune_solve); the
     result carries residuals (the final report, with the grid over the image and the angle bins if asked for), pruned_views,
     pruned_corners, prune_rounds and prune_summaries, summary is the last solve's, and a following covariance uses the pruned
-    weights.  There is no rig-connectivity logic: a pruned rig that falls apart shows in the covariance's min_pivot_ratio."""
+    weights.  There is no rig-connectivity logic: a pruned rig that falls apart shows in the covariance's min_pivot_ratio.
+    recover: the structure recovery of every detection of the mono calibrations ("host" | "device" | "host-batch", monocular_calib)."""
     if priors is not None and batch_mono:
         raise ValueError("batch_mono=True has no priors: the batched mono route does not take them")
     n_cam = len(images_by_camera)
     w = _model_masks(model, fixed, n_cam)
     if batch_mono:
         mono = monocular_calib_batch(images_by_camera, cols, rows, pitch, sigma, device, loss=loss, model=model, masks=w, ransac=ransac,
-                                     mask_outliers=mask_outliers)
+                                     mask_outliers=mask_outliers, recover=recover)
     else:
         mono = [monocular_calib(imgs, cols, rows, pitch, sigma, device, loss=loss, model=model, fixed=np.array([w[m]]), ransac=ransac,
-                                mask_outliers=mask_outliers, priors=None if priors is None else {k: v for k, v in priors.items() if k != "cam_rt_sigma"})
+                                mask_outliers=mask_outliers, priors=None if priors is None else {k: v for k, v in priors.items() if k != "cam_rt_sigma"},
+                                recover=recover)
                 for m, imgs in enumerate(images_by_camera)]
     W = board_points(cols, rows, pitch)
     inp = rig.RigInput(W, np.stack([m["intr"] for m in mono]), np.stack([m["has"] for m in mono]), np.stack([m["Rt"] for m in mono]),
